@@ -1,17 +1,23 @@
 """Headline benchmark: audio-seconds per wall-second of the encode()+decode() round trip (1/RTF).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[1]): full codec inference at 24 kHz, 80 mel bins, 8 FSQ groups, BigVGAN-base
 vocoder, batch 32 of 1 s clips per GPU, fp32.  A "step" is one encode() + decode(return_audios=True) over one
 batch already resident in HBM; weights are seeded random (the reference ships none), audio is synthetic.
-Steps are independent batches: `--lanes` (default 3) of them are in flight per GPU at a time (dmel_codec_amd/pipeline.py); the
-line also carries the one-batch-at-a-time figure (`one_batch_at_a_time`) timed in the same run.
+Steps are independent batches: `--lanes` (default 3) of them are in flight per GPU at a time (dmel_codec_amd/pipeline.py).
 One process per GPU; utterances shard across ranks with no data-path collective (weak scaling).  Rank 0 prints
-ONE JSON line with the whole-job rate, the roofline of the dominant kernel family (the implicit-GEMM convolutions:
-fp32-grade products from the three-product fp16 split on the decode side and the six-product bf16 split on the
-encode side, timed live with hipEvents on the launch stream) and, at N=1, the CPU baseline (the oracle restatement
-made of the ATen-CPU calls the reference itself makes) timed on the host cores in the same run.
+ONE JSON line with the whole-job rate and `ms_per_step`, the wall time of one timed step.
+
+A plain run does only what that line needs: set up, warm up, time the K steps, write the outputs (`--dump-outputs DIR`: the token
+ids, feature lengths and waveform of the last timed step of rank 0, as DIR/<name>.npy in float32 / float64; inputs, weights and the
+decoder's noise are seeded, so the same arguments give the same inputs in every run) and print.  `--full` adds everything else the
+benchmark measures, after the headline steps: the one-batch-at-a-time figure (`one_batch_at_a_time`) and the check that the ids of a batch
+processed with others in flight equal those of the same batch alone, the latency distribution of single steps (`ms_per_step_events`),
+the roofline of the dominant kernel family (the implicit-GEMM convolutions: fp32-grade products from the three-product fp16 split on the
+decode side and the six-product bf16 split on the encode side, timed live with hipEvents on the launch stream, `roofline`,
+`kernel_ms_per_step`) and, at N=1, the CPU baseline (the oracle restatement made of the ATen-CPU calls the reference itself makes) timed
+on the host cores in the same run.
 """
 from __future__ import annotations
 
@@ -250,28 +256,47 @@ def spawn_ranks(n: int, argv, script: str | None = None, have: int | None = None
     return rc
 
 
+def dump_outputs(outdir: str, outputs: dict) -> None:
+    """What the timed path handed its caller in the last timed step, as outdir/<name>.npy: integer tensors as float64 (exact), floating
+    ones as float32."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in outputs.items():
+        t = t.detach().cpu()
+        t = t.double() if not t.is_floating_point() else t.float()
+        np.save(os.path.join(outdir, name + ".npy"), t.numpy())
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps")
+    ap.add_argument("--warmup", type=int, default=3, help="untimed steps before them (at least one per lane)")
     ap.add_argument("--batch", type=int, default=32, help="clips per GPU per step")
     ap.add_argument("--seconds", type=float, default=1.0, help="clip length")
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
-    ap.add_argument("--cpu-budget", type=float, default=10.0, help="seconds of CPU work for the baseline (0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the token ids, feature lengths and waveform of the last timed step (rank 0) to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps, also measure and check everything else: one batch at a time and the lane ids check, "
+                         "the per-step latency distribution, the per-kernel roofline pass and (N=1) the CPU baseline")
+    ap.add_argument("--cpu-budget", type=float, default=10.0, help="with --full: seconds of CPU work for the baseline (0 = skip)")
     ap.add_argument("--median-steps", type=int, default=100,
-                    help="extra steps timed one by one with events for the median / p10 / p90 of the step time (0 = skip)")
+                    help="with --full: extra steps timed one by one with events for the median / p10 / p90 of the step time (0 = skip)")
     ap.add_argument("--streams", type=int, default=1, choices=(1, 3),
                     help="streams the three AMP blocks of a BigVGAN stage run on WITHIN one batch (3 = overlapped: the round-1/2 default; with "
                          "several batches in flight the lanes already fill the chip and 1 measures faster: profiles/r03_lanes_sweep.txt)")
     ap.add_argument("--lanes", type=int, default=3,
                     help="batches in flight per GPU in the timed region (dmel_codec_amd.pipeline.CodecLanes: replicas of the codec on their "
-                         "own streams, batches dealt round-robin; 1 = one batch at a time, the round-1/2 form, also timed and reported)")
+                         "own streams, batches dealt round-robin; 1 = one batch at a time, the round-1/2 form, also timed and reported "
+                         "with --full)")
     ap.add_argument("--decode-precision", default="fp32", choices=("fp32", "fp32_bf16x3", "bf16"),
                     help="fp32 (default, the parity path and the headline number: fp32-grade products, three-product fp16 split on the "
                          "decode side), fp32_bf16x3 (six-product bf16 split everywhere: the round-1 arithmetic, for A/B) or the opt-in "
                          "bf16-operand mode of the decode-side convolutions (never the default: it is outside the 1e-4 bar)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(spawn_ranks(args.gpus, sys.argv[1:]))     # plain `python bench.py --gpus N`: start the N ranks ourselves
@@ -291,11 +316,11 @@ def main() -> None:
         dist_mod.init_process_group("nccl", device_id=dev)    # RCCL
         dist = dist_mod
 
-    from dmel_codec_amd import _lib
     codec = build(args.workload)
     cpu_base = None
-    if world == 1 and rank == 0 and args.cpu_budget > 0:
-        # the host-core baseline runs first, on the freshly built (CPU-resident) weights, so the GPU legs close the run
+    if args.full and world == 1 and rank == 0 and args.cpu_budget > 0:
+        # the host-core baseline runs first, on the freshly built (CPU-resident) weights, so the GPU legs close the run; it draws from the
+        # CPU generator only, so the GPU steps (and their noise) are those of a plain run
         cpu_base = cpu_baseline(codec, args.workload, args.seconds, args.cpu_budget)
     codec = codec.to(dev)
     sr = WORKLOADS[args.workload]["sample_rate"]
@@ -306,7 +331,7 @@ def main() -> None:
     def step():
         ids, il = codec.encode(audio, lens)
         wav, _ = codec.decode(ids, il, return_audios=True)       # draws its Gaussian noise like the reference (:473)
-        return ids, wav
+        return ids, il, wav
 
     def sync_all():
         torch.cuda.synchronize()
@@ -339,27 +364,73 @@ def main() -> None:
     last = {}
 
     def one_step():
-        last["ids"], last["wav"] = step()
+        last["one"] = step()
 
     def lane_step():
         last["r"] = lanes.roundtrip(audio, lens)
 
-    elapsed_one_lane = timed(one_step) if len(lanes) > 1 else None      # one batch at a time (what rounds 1 and 2 reported), for the record
+    # the headline: K steps, `--lanes` batches in flight
     elapsed = timed(lane_step if len(lanes) > 1 else one_step)
     rank_elapsed = per_rank_times(dist, elapsed, dev)
     elapsed = max_over_ranks(dist, elapsed, dev)
+    ids, il, wav = last["r"].wait() if len(lanes) > 1 else last["one"]      # what the caller of the timed path receives in its last step
+    assert torch.isfinite(wav).all() and wav.shape == (args.batch, 1, (L // 256 // 4) * 4 * 256)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"ids": ids, "feature_lengths": il, "audio": wav})
+
+    extra = {}
     lanes_ids_ok = None
-    if elapsed_one_lane is not None:
-        elapsed_one_lane = max_over_ranks(dist, elapsed_one_lane, dev)
-        ids, _, wav = last["r"].wait()
+    if args.full:
+        # a copy: the last timed step may have run on lane 0, the codec the extra steps run on
+        extra = full_measurements(args, world, dist, dev, codec, lanes, step, sync_all, timed, one_step, last, ids.clone())
+        lanes_ids_ok = extra.pop("lanes_ids_ok")
+
+    if rank == 0:
+        rate = job_rate(world, args.batch, args.seconds, args.steps, elapsed)
+        bf16 = args.decode_precision == "bf16"
+        out = {
+            "metric": "audio-sec/sec (encode+decode RTF) @24 kHz batch 32",
+            "value": round(rate, 2),
+            "unit": "audio-sec/sec",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(1e3 * elapsed / args.steps, 3),
+            "ms_per_step_by_rank": [round(1e3 * e / args.steps, 3) for e in rank_elapsed],
+            "process_group": (dist.get_backend() if dist is not None else None),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "bf16 operands, f32 accumulate in the decode convolutions (opt-in mode); f32 elsewhere" if bf16 else "f32",
+            "data": "synthetic",
+            "config": {"workload": f"{args.workload}: encode+decode, {sr} Hz, {WORKLOADS[args.workload]['n_mels']} mel, "
+                                   f"{WORKLOADS[args.workload]['dmel_groups']} FSQ groups {list(WORKLOADS[args.workload]['levels'])}, "
+                                   f"WaveNet 20+20 layers, BigVGAN-base, batch {args.batch} x {args.seconds:g} s per GPU",
+                       "parallelism": f"{world} x independent utterance shards, no collective; {len(lanes)} independent batch(es) in flight "
+                                      "per GPU (dmel_codec_amd.pipeline.CodecLanes)",
+                       "lanes": len(lanes), "vocoder_streams": args.streams, "lane_ids_equal_single_batch_ids": lanes_ids_ok},
+            "full": args.full,
+        }
+        out.update(extra)
+        if cpu_base is not None:
+            out["cpu_baseline"] = cpu_base
+        print(json.dumps(out), flush=True)
+    if dist is not None:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def full_measurements(args, world, dist, dev, codec, lanes, step, sync_all, timed, one_step, last, lane_ids):
+    """`--full`: what the benchmark measures and checks beyond the headline, run after the headline steps."""
+    from dmel_codec_amd import _lib
+    res = {"lanes_ids_ok": None}
+
+    # the same K steps one batch at a time (what rounds 1 and 2 reported as `value`), for the record
+    elapsed_one_lane = None
+    if len(lanes) > 1:
+        elapsed_one_lane = max_over_ranks(dist, timed(one_step), dev)
         # the token ids do not depend on the decoder's noise: the batch that went through a lane with others in flight must give exactly the
         # ids of the same batch on its own (a kernel-level interference between lanes would show here: profiles/r03_stft_concurrency.txt)
         torch.cuda.synchronize()
-        lanes_ids_ok = bool(torch.equal(ids, last["ids"]))
-        if not lanes_ids_ok:
+        res["lanes_ids_ok"] = bool(torch.equal(lane_ids, last["one"][0]))
+        if not res["lanes_ids_ok"]:
             raise SystemExit("bench.py: token ids of a batch processed with other batches in flight differ from the same batch alone")
-    else:
-        ids, wav = last["ids"], last["wav"]
 
     # Distribution of the step time: `median_steps` further steps ONE BATCH AT A TIME, each bracketed by its own pair of events on the launch
     # stream (the vocoder's side streams fork from and join back into it, so the pair sees the whole step): the latency of a batch.
@@ -373,9 +444,9 @@ def main() -> None:
         sync_all()
         per_step_ms = sorted(a.elapsed_time(b) for a, b in evs)
 
-    # Per-kernel roofline pass.  In the timed region above BigVGAN's three AMP blocks run on three streams, so kernels
-    # overlap and a kernel's own hipEvent interval no longer measures that kernel alone.  The same K steps are therefore
-    # repeated with the vocoder serialised onto one stream and every launch bracketed by hipEvents on its stream.
+    # Per-kernel roofline pass.  In the timed region above the lanes' (and, with --streams 3, BigVGAN's AMP blocks') kernels overlap, so a
+    # kernel's own hipEvent interval no longer measures that kernel alone.  The same K steps are therefore repeated one batch at a time with
+    # the vocoder serialised onto one stream and every launch bracketed by hipEvents on its stream.
     codec.vocoder.set_streams(1)
     step()
     sync_all()
@@ -388,7 +459,6 @@ def main() -> None:
     elapsed_serial = time.perf_counter() - t1
     _lib.prof_enable(False)
     codec.vocoder.set_streams(args.streams)
-    assert torch.isfinite(wav).all() and wav.shape == (args.batch, 1, (L // 256 // 4) * 4 * 256)
 
     conv = _lib.prof_read("conv_igemm")
     snake = _lib.prof_read("aa_snake")
@@ -396,74 +466,51 @@ def main() -> None:
     small = _lib.prof_read("small")
     _lib.prof_reset()
 
-    if rank == 0:
-        rate = job_rate(world, args.batch, args.seconds, args.steps, elapsed)
-        ach = conv["flops"] / (conv["ms"] * 1e-3) / 1e12 if conv["ms"] > 0 else 0.0
-        bf16 = args.decode_precision == "bf16"
-        native = os.environ.get("DMEL_CONV_FP32_MFMA", "0") not in ("", "0")
-        # Matrix-core ceiling of the family: every launch reports the flops it ISSUES for its algorithmic fp32 flops (6x under the three-way
-        # bf16 split: encoder, quantiser; 3x under the two-way fp16 split: decoder WaveNet, vocoder), so the ceiling
-        # for the step's ALGORITHMIC flops is the dense 16-bit MFMA peak divided by the flop-weighted mean of those factors.
-        factor = conv["issue_flops"] / conv["flops"] if conv["flops"] > 0 else 6.0
-        peak = PEAK_BF16_MFMA_TFLOPS / factor
-        if bf16:
-            kernel = "conv_bf16_kernel<NP=1> (v_mfma_f32_32x32x16_bf16) decode side + six-product split on the encoder side"
-        elif native:
-            kernel = "conv_igemm_kernel (fp32 v_mfma_f32_32x32x2_f32)"
-        elif args.decode_precision == "fp32_bf16x3":
-            kernel = ("conv_bf16_kernel<NP=3> (fp32 via exact 3-way bf16 operand split: 6 x v_mfma_f32_32x32x16_bf16 per 32x32x16 "
-                      "block, fp32 accumulate)")
-        else:
-            kernel = ("conv_bf16_kernel<NP=2> on the decode side (fp32 via 2-way fp16 operand split, 22 significant bits per operand as in 3xTF32: 3 x "
-                      "v_mfma_f32_32x32x16_f16 per 32x32x16 block, two fp32 accumulators; inputs staged x 2^-6 with a FIXED scale: domain "
-                      "|x| < 4.19e6, absolute error floor 2^-30 below |x| = 2^-8, include/dmel_hip.h) + <NP=3> / wavenet_fused_kernel on the "
-                      "encode side (3-way bf16 split, 6 MFMAs per block: the ids are defined by it)")
-        out = {
-            "metric": "audio-sec/sec (encode+decode RTF) @24 kHz batch 32",
-            "value": round(rate, 2),
-            "unit": "audio-sec/sec",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(1e3 * elapsed / args.steps, 3),
-            "ms_per_step_by_rank": [round(1e3 * e / args.steps, 3) for e in rank_elapsed],
-            "ms_per_step_events": ({"what": "latency of one batch alone (no other batch in flight)", "n": len(per_step_ms), "median": round(per_step_ms[len(per_step_ms) // 2], 3),
-                                    "p10": round(per_step_ms[len(per_step_ms) // 10], 3),
-                                    "p90": round(per_step_ms[(9 * len(per_step_ms)) // 10], 3)} if per_step_ms else None),
-            "process_group": (dist.get_backend() if dist is not None else None),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "bf16 operands, f32 accumulate in the decode convolutions (opt-in mode); f32 elsewhere" if bf16 else "f32",
-            "data": "synthetic",
-            "config": {"workload": f"{args.workload}: encode+decode, {sr} Hz, {WORKLOADS[args.workload]['n_mels']} mel, "
-                                   f"{WORKLOADS[args.workload]['dmel_groups']} FSQ groups {list(WORKLOADS[args.workload]['levels'])}, "
-                                   f"WaveNet 20+20 layers, BigVGAN-base, batch {args.batch} x {args.seconds:g} s per GPU",
-                       "parallelism": f"{world} x independent utterance shards, no collective; {len(lanes)} independent batch(es) in flight "
-                                      "per GPU (dmel_codec_amd.pipeline.CodecLanes)",
-                       "lanes": len(lanes), "vocoder_streams": args.streams, "lane_ids_equal_single_batch_ids": lanes_ids_ok},
-            "one_batch_at_a_time": ({"value": round(job_rate(world, args.batch, args.seconds, args.steps, elapsed_one_lane), 2),
-                                     "ms_per_step": round(1e3 * elapsed_one_lane / args.steps, 3)} if elapsed_one_lane is not None else None),
-            "roofline": {"bound": "mfma", "kernel": kernel,
-                         "achieved": round(ach, 2), "peak": round(peak, 1), "unit": "TFLOP/s",
-                         "frac": round(ach / peak, 4), "traffic": committed_traffic(conv),
-                         "mfma_flops_issued_per_algorithmic_flop": round(factor, 3),
-                         # the same rate against the ceiling of rounds 1 / early 2, when every convolution issued six products (2500 / 6)
-                         "frac_of_six_product_ceiling": round(ach / (PEAK_BF16_MFMA_TFLOPS / 6.0), 4),
-                         "frac_of_fp32_mfma_peak": round(ach / PEAK_FP32_MFMA_TFLOPS, 4),
-                         "launches_per_step": conv["launches"] // max(1, args.steps),
-                         "avg_launch_us": round(1e3 * conv["ms"] / max(1, conv["launches"]), 2),
-                         "gflop_per_step": round(conv["flops"] / args.steps / 1e9, 1),
-                         "measured_in": "serialised re-run of the same steps (one batch at a time, single stream, hipEvents around every launch); "
-                                        "the timed region overlaps kernels of several batches and streams",
-                         "ms_per_step_serialised": round(1e3 * elapsed_serial / args.steps, 3)},
-            "kernel_ms_per_step": {"conv_igemm": round(conv["ms"] / args.steps, 3), "aa_snake": round(snake["ms"] / args.steps, 3),
-                                   "stft_logmel": round(stft["ms"] / args.steps, 4), "small": round(small["ms"] / args.steps, 3)},
-            "aa_snake_hbm": {"achieved_GBs": round(snake["bytes"] / (snake["ms"] * 1e-3) / 1e9, 1) if snake["ms"] > 0 else 0.0,
-                             "peak_GBs": PEAK_HBM_GBS},
-        }
-        if cpu_base is not None:
-            out["cpu_baseline"] = cpu_base
-        print(json.dumps(out), flush=True)
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+    ach = conv["flops"] / (conv["ms"] * 1e-3) / 1e12 if conv["ms"] > 0 else 0.0
+    bf16 = args.decode_precision == "bf16"
+    native = os.environ.get("DMEL_CONV_FP32_MFMA", "0") not in ("", "0")
+    # Matrix-core ceiling of the family: every launch reports the flops it ISSUES for its algorithmic fp32 flops (6x under the three-way
+    # bf16 split: encoder, quantiser; 3x under the two-way fp16 split: decoder WaveNet, vocoder), so the ceiling
+    # for the step's ALGORITHMIC flops is the dense 16-bit MFMA peak divided by the flop-weighted mean of those factors.
+    factor = conv["issue_flops"] / conv["flops"] if conv["flops"] > 0 else 6.0
+    peak = PEAK_BF16_MFMA_TFLOPS / factor
+    if bf16:
+        kernel = "conv_bf16_kernel<NP=1> (v_mfma_f32_32x32x16_bf16) decode side + six-product split on the encoder side"
+    elif native:
+        kernel = "conv_igemm_kernel (fp32 v_mfma_f32_32x32x2_f32)"
+    elif args.decode_precision == "fp32_bf16x3":
+        kernel = ("conv_bf16_kernel<NP=3> (fp32 via exact 3-way bf16 operand split: 6 x v_mfma_f32_32x32x16_bf16 per 32x32x16 "
+                  "block, fp32 accumulate)")
+    else:
+        kernel = ("conv_bf16_kernel<NP=2> on the decode side (fp32 via 2-way fp16 operand split, 22 significant bits per operand as in 3xTF32: 3 x "
+                  "v_mfma_f32_32x32x16_f16 per 32x32x16 block, two fp32 accumulators; inputs staged x 2^-6 with a FIXED scale: domain "
+                  "|x| < 4.19e6, absolute error floor 2^-30 below |x| = 2^-8, include/dmel_hip.h) + <NP=3> / wavenet_fused_kernel on the "
+                  "encode side (3-way bf16 split, 6 MFMAs per block: the ids are defined by it)")
+    res.update({
+        "ms_per_step_events": ({"what": "latency of one batch alone (no other batch in flight)", "n": len(per_step_ms), "median": round(per_step_ms[len(per_step_ms) // 2], 3),
+                                "p10": round(per_step_ms[len(per_step_ms) // 10], 3),
+                                "p90": round(per_step_ms[(9 * len(per_step_ms)) // 10], 3)} if per_step_ms else None),
+        "one_batch_at_a_time": ({"value": round(job_rate(world, args.batch, args.seconds, args.steps, elapsed_one_lane), 2),
+                                 "ms_per_step": round(1e3 * elapsed_one_lane / args.steps, 3)} if elapsed_one_lane is not None else None),
+        "roofline": {"bound": "mfma", "kernel": kernel,
+                     "achieved": round(ach, 2), "peak": round(peak, 1), "unit": "TFLOP/s",
+                     "frac": round(ach / peak, 4), "traffic": committed_traffic(conv),
+                     "mfma_flops_issued_per_algorithmic_flop": round(factor, 3),
+                     # the same rate against the ceiling of rounds 1 / early 2, when every convolution issued six products (2500 / 6)
+                     "frac_of_six_product_ceiling": round(ach / (PEAK_BF16_MFMA_TFLOPS / 6.0), 4),
+                     "frac_of_fp32_mfma_peak": round(ach / PEAK_FP32_MFMA_TFLOPS, 4),
+                     "launches_per_step": conv["launches"] // max(1, args.steps),
+                     "avg_launch_us": round(1e3 * conv["ms"] / max(1, conv["launches"]), 2),
+                     "gflop_per_step": round(conv["flops"] / args.steps / 1e9, 1),
+                     "measured_in": "serialised re-run of the same steps (one batch at a time, single stream, hipEvents around every launch); "
+                                    "the timed region overlaps kernels of several batches and streams",
+                     "ms_per_step_serialised": round(1e3 * elapsed_serial / args.steps, 3)},
+        "kernel_ms_per_step": {"conv_igemm": round(conv["ms"] / args.steps, 3), "aa_snake": round(snake["ms"] / args.steps, 3),
+                               "stft_logmel": round(stft["ms"] / args.steps, 4), "small": round(small["ms"] / args.steps, 3)},
+        "aa_snake_hbm": {"achieved_GBs": round(snake["bytes"] / (snake["ms"] * 1e-3) / 1e9, 1) if snake["ms"] > 0 else 0.0,
+                         "peak_GBs": PEAK_HBM_GBS},
+    })
+    return res
 
 
 if __name__ == "__main__":

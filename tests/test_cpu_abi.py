@@ -113,39 +113,34 @@ def test_mirror_state_dict_layout():
     assert "decoder.input_projection.conv.weight" not in sd      # 560 == 560: wavenet.py:152-156
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/dmel_codec"), reason="reference only exists in the build container")
 def test_mirror_state_dicts_equal_reference_modules():
-    import subprocess
-    import sys
-    code = r"""
-import sys, warnings
-warnings.filterwarnings('ignore')
-sys.path.insert(0, %r); sys.path.insert(0, '/root/reference')   # the reference's dmel_codec must win over the alias package
-sys.dont_write_bytecode = True
-from dmel_codec.models.modules.wavenet import WaveNet as RW
-from dmel_codec.models.modules.bigvgan.bigvgan import BigVGAN as RB
-from dmel_codec.models.modules.bigvgan.env import AttrDict as RA
-from dmel_codec.models.modules.firefly import ConvNeXtBlock as RC
-from dmel_codec_amd.models.modules.wavenet import WaveNet
-from dmel_codec_amd.models.modules.bigvgan.bigvgan import BigVGAN
-from dmel_codec_amd.models.modules.firefly import ConvNeXtBlock
-from dmel_codec_amd.configs import bigvgan_h, BIGVGAN
-def same(a, b):
-    sa = {k: tuple(v.shape) for k, v in a.state_dict().items()}
-    sb = {k: tuple(v.shape) for k, v in b.state_dict().items()}
-    assert sa == sb, (set(sa) ^ set(sb))
-same(RW(10, None, 70, 20, 4), WaveNet(10, None, 70, 20, 4))
-same(RW(64, 20, 64, 3, 4, False, 64), WaveNet(64, 20, 64, 3, 4, False, 64))
-same(RC(70), ConvNeXtBlock(70))
-for name in ('base_24k_100band',):
-    r, m = RB(RA(dict(BIGVGAN[name]))), BigVGAN(bigvgan_h(name))
-    same(r, m)
-    r.remove_weight_norm(); m.remove_weight_norm()
-    same(r, m)
-print('ok')
-""" % ROOT
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0 and "ok" in out.stdout, out.stderr[-2000:]
+    """The mirror modules carry the reference modules' state dicts: same names, same shapes, with and without weight norm.  The
+    reference's layout is stored as data (tests/golden/state_dict_shapes.json, written by oracle/gen_golden_shapes.py from the reference's
+    own classes built with the same arguments)."""
+    import json
+    from dmel_codec_amd.configs import BIGVGAN, bigvgan_h
+    from dmel_codec_amd.models.modules.bigvgan.bigvgan import BigVGAN
+    from dmel_codec_amd.models.modules.firefly import ConvNeXtBlock
+    from dmel_codec_amd.models.modules.wavenet import WaveNet
+    with open(os.path.join(ROOT, "tests", "golden", "state_dict_shapes.json")) as f:
+        ref = json.load(f)
+
+    def same(m, sd):
+        got = {k: list(v.shape) for k, v in m.state_dict().items()}
+        assert got == sd, (set(got) ^ set(sd)) or [k for k in got if got[k] != sd[k]]
+
+    assert ref["wavenet_enc"]["args"] == [10, None, 70, 20, 4] and ref["wavenet_cond"]["args"] == [64, 20, 64, 3, 4, False, 64]
+    same(WaveNet(10, None, 70, 20, 4), ref["wavenet_enc"]["state_dict"])
+    same(WaveNet(64, 20, 64, 3, 4, False, 64), ref["wavenet_cond"]["state_dict"])
+    assert ref["convnext"]["args"] == [70]
+    same(ConvNeXtBlock(70), ref["convnext"]["state_dict"])
+    for name in ('base_24k_100band',):
+        assert name in BIGVGAN
+        r = ref["bigvgan_" + name]
+        m = BigVGAN(bigvgan_h(name))
+        same(m, r["state_dict"])
+        m.remove_weight_norm()
+        same(m, r["state_dict_without_weight_norm"])
 
 
 def test_yaml_config_builds_the_codec():
@@ -184,14 +179,12 @@ def test_alias_package_serves_reference_paths():
     assert out.returncode == 0 and "ok" in out.stdout, out.stderr[-1500:]
 
 
-@pytest.mark.skipif(not os.path.isfile("/root/reference/dmel_codec/config/codec/dMel_example.yaml"),
-                    reason="reference only exists in the build container")
 def test_reference_yaml_instantiates():
-    """The reference's own example config (read as data, in place) builds the codec once the author-local vocoder
-    paths are overridden."""
+    """The reference's own example config (config/codec/dMel_example.yaml, stored as data in tests/golden/) builds the codec once the
+    author-local vocoder paths are overridden."""
     from dmel_codec_amd import config_loader
     h = os.path.join(ROOT, "dmel_codec_amd", "config", "bigvgan", "base_24k_100band.json")
-    m = config_loader.build_codec_from_config("/root/reference/dmel_codec/config/codec/dMel_example.yaml",
+    m = config_loader.build_codec_from_config(os.path.join(ROOT, "tests", "golden", "dMel_example.yaml"),
                                               overrides={"model": {"vocoder": {"h_path": h, "ckpt_path": None}}},
                                               load_vocoder_ckpt=False)
     assert len(m.encoder.residual_layers) == 8 and m.quantizer.levels == [8, 6] and m.dmel_groups == 10

@@ -54,6 +54,21 @@ def test_single_process_helpers():
     assert torch.equal(a, bench.synth_audio(2, 1000, 7))
 
 
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    """bench.py --dump-outputs: every array as DIR/<name>.npy, integers widened to float64 (exact), floating point as float32."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    ids = torch.randint(0, 175, (2, 8, 23), dtype=torch.int32)
+    lens = torch.tensor([23, 17])
+    wav = torch.randn(2, 1, 300)
+    bench.dump_outputs(str(tmp_path / "out"), {"ids": ids, "feature_lengths": lens, "audio": wav})
+    got = {n: np.load(tmp_path / "out" / (n + ".npy")) for n in ("ids", "feature_lengths", "audio")}
+    assert got["ids"].dtype == np.float64 and np.array_equal(got["ids"], ids.numpy())
+    assert got["feature_lengths"].dtype == np.float64 and np.array_equal(got["feature_lengths"], lens.numpy())
+    assert got["audio"].dtype == np.float32 and np.array_equal(got["audio"], wav.numpy())
+
+
 def _reducer_worker(rank: int, world: int, port: int, out):
     """A stand-in for a native module on the CPU: same bookkeeping (NativeModule._begin_train_call / _can_stream_grads /
     _deliver_grads), a backward that fills ONE flat gradient buffer block by block in reverse order and hands each block to the

@@ -377,13 +377,39 @@ def test_bench_control_path_over_rccl_single_rank(dev):
     env = dict(os.environ, DMEL_BENCH_FORCE_DIST="1", NCCL_SOCKET_IFNAME="lo")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", str(29500 + os.getpid() % 500), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2",
-                        "--warmup", "1", "--cpu-budget", "0", "--median-steps", "0"], capture_output=True, text=True, timeout=600, env=env,
-                       cwd=ROOT)
+                        "--warmup", "1", "--full", "--cpu-budget", "0", "--median-steps", "0"], capture_output=True, text=True, timeout=600,
+                       env=env, cwd=ROOT)
     tail = "\n".join((r.stdout + r.stderr).splitlines()[-12:])
     assert r.returncode == 0, tail
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["value"] > 0 and len(line["ms_per_step_by_rank"]) == 1 and line.get("process_group") == "nccl", tail
 
+
+def test_bench_plain_and_full_runs_dump_the_same_outputs(dev, tmp_path):
+    """`bench.py --dump-outputs DIR`: the ids, feature lengths and waveform of the last timed step, as float .npy files.  Inputs, weights and
+    the decoder's noise are seeded, and --full runs its extra legs after the headline steps: the same arguments give the same arrays with
+    and without it.  The plain line carries the headline only."""
+    import json, subprocess, sys
+    import numpy as np
+    from conftest import ROOT
+    torch.cuda.synchronize()
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--cpu-budget", "0", "--median-steps", "3"])):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / mode), *extra], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        tail = "\n".join((r.stdout + r.stderr).splitlines()[-12:])
+        assert r.returncode == 0, tail
+        lines[mode] = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    for mode, line in lines.items():
+        assert line["value"] > 0 and line["ms_per_step"] > 0 and line["steps"] == 2 and line["unit"] == "audio-sec/sec", line
+        assert line["higher_is_better"] is True and line["dtype"] == "f32" and line["full"] == (mode == "full"), line
+    assert "roofline" not in lines["plain"] and "one_batch_at_a_time" not in lines["plain"]
+    assert lines["full"]["roofline"]["achieved"] > 0 and lines["full"]["one_batch_at_a_time"]["value"] > 0
+    assert lines["full"]["config"]["lane_ids_equal_single_batch_ids"] is True and lines["full"]["ms_per_step_events"]["n"] == 3
+    for name, shape in (("ids", (32, 8, 23)), ("feature_lengths", (32,)), ("audio", (32, 1, 23552))):
+        a, b = np.load(tmp_path / "plain" / (name + ".npy")), np.load(tmp_path / "full" / (name + ".npy"))
+        assert a.shape == shape and a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), (name, a.shape, a.dtype)
+        assert np.array_equal(a, b), name
 
 def test_train_codec_under_torch_distributed_run_two_ranks(dev, tmp_path):
     """`python -m torch.distributed.run --nproc-per-node 2 train_codec.py ...` -- the launch line of INTEGRATION.md -- on this one GPU

@@ -41,8 +41,8 @@ def main():
            "launches_in_profile": launches,
            "algorithmic_bytes_per_launch": None,
            "kernel_source_hash": __import__("bench").kernel_source_hash(),     # bench.py flags the figure as stale when the kernels change
-           "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (two passes) over `bench.py --steps 2 --warmup 1 --cpu-budget 0 "
-                     "--median-steps 0 --streams 1`; conv family = conv_bf16_kernel<...> + conv_pc_kernel<...> + wavenet_fused_kernel; FETCH_SIZE doubled "
+           "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (two passes) over `bench.py --steps 2 --warmup 1 --full "
+                     "--cpu-budget 0 --median-steps 0 --streams 1`; conv family = conv_bf16_kernel<...> + conv_pc_kernel<...> + wavenet_fused_kernel; FETCH_SIZE doubled "
                      "(gfx950 reports half of a wide coalesced read), WRITE_SIZE exact, KB -> bytes; profiles/r03_pmc_*.csv",
            "top_kernels": table}
     with open(out, "w") as f:
