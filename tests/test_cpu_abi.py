@@ -286,3 +286,83 @@ def test_lanes_refuse_a_cpu_codec():
         CodecLanes(codec, 2)
     with pytest.raises(ValueError):
         CodecLanes(codec, 0)
+
+
+def test_conv_matrix_reaches_every_kernel_branch():
+    """tests/test_gpu_conv_matrix.py claims to cover every tile / operand split / halo class of the forward kernel and every branch of
+    launch_wgrad_any and launch_bgrad (csrc/conv_bwd.hip).  Its branch predicates are a Python mirror of lines of conv_bwd.hip: those
+    lines must still read as transcribed, and the parametrisation must reach every branch at least twice."""
+    import collections
+    import test_gpu_conv_matrix as m
+    src = open(os.path.join(ROOT, "dmel_codec_amd", "csrc", "conv_bwd.hip")).read()
+    for line in m.WGRAD_PREDICATE_SOURCE:
+        assert line in src, f"conv_bwd.hip no longer contains `{line}`: update the mirror in test_gpu_conv_matrix.py"
+    wg = collections.Counter(m.wgrad_branch(k, dil, T) for (Cout, Cin, k, dil, T, B) in m.WGRAD_CASES)
+    bg = collections.Counter(m.bgrad_branch(Cout, B, T) for (Cout, Cin, k, dil, T, B) in m.WGRAD_CASES)
+    assert set(wg) == set(m.WGRAD_BRANCHES) and min(wg.values()) >= 2, wg
+    assert set(bg) == set(m.BGRAD_BRANCHES) and min(bg.values()) >= 2, bg
+    # boundaries on both sides: T = 32 | 33 (ipc), 255 | 256 (split), a B that is not a multiple of ipc, > 1024 channels for db
+    Ts = {T for (_, _, _, _, T, _) in m.WGRAD_CASES}
+    assert {32, 33, 255, 256} <= Ts
+    assert any(T <= 32 and B % (64 // T) for (_, _, _, _, T, B) in m.WGRAD_CASES)
+    assert any(Cout > 1024 for (Cout, *_rest) in m.WGRAD_CASES)
+    assert {1, 17, 64, 65, 130} <= {c for (Cout, Cin, *_rest) in m.WGRAD_CASES for c in (Cout, Cin)}
+    # the grouped path with one K slice and with many (slices = max(1, min(ceil(1024 / (tm tn groups)), ceil(B ceil(T / 64) / 8))))
+    slices = set()
+    for (Cout, Cin, k, dil, T, B) in m.WGRAD_CASES:
+        if m.wgrad_branch(k, dil, T) == "grouped":
+            tiles = ((Cout + 63) // 64) * ((Cin + 63) // 64) * (k // 3)
+            slices.add(max(1, min((1024 + tiles - 1) // tiles, (B * ((T + 63) // 64) + 7) // 8)))
+    assert 1 in slices and max(slices) >= 8, slices
+    # forward: every halo class, the edges of each, and the ragged channel / length / batch sets the module promises
+    halos = {(k - 1) * dil for (_, _, k, dil, _, _) in m.FWD_SHAPES}
+    assert {0, 16, 64} <= halos and any(0 < h < 16 for h in halos) and any(16 < h < 64 for h in halos)
+    assert {m.halo_class(k, dil) for (_, _, k, dil, _, _) in m.FWD_SHAPES} == {0, 16, 64}
+    assert {1, 31, 33, 100, 129, 257, 300} <= {s[0] for s in m.FWD_SHAPES}
+    assert {8, 17, 24, 130} <= {s[1] for s in m.FWD_SHAPES}
+    Tf = {s[4] for s in m.FWD_SHAPES}
+    assert {1, 2, 31, 32, 33, 95, 96, 97, 127, 128, 129, 255, 256, 257} <= Tf and max(Tf) >= 3000
+    assert any(T < (k - 1) * dil for (_, _, k, dil, T, _) in m.FWD_SHAPES)
+    assert {1, 3} <= {s[5] for s in m.FWD_SHAPES}
+    assert set(m.NPS) == {1, 2, 3} and list(m.TILES) == list(range(8))
+    assert all(t <= m.TAU_CEIL for t in m.TAU.values()) and m.TAU_CEIL == 2.0 ** -16
+
+
+def test_conv_matrix_guards_catch_missing_and_stray_stores():
+    """The guarded buffers of tests/test_gpu_conv_matrix.py (device-agnostic, exercised here on host tensors): an output element that
+    is never stored, a store past either end of an output and a write into an input's NaN band each fail the check."""
+    import test_gpu_conv_matrix as m
+    cpu = torch.device("cpu")
+    y = m.Out((2, 3, 5), cpu)
+    with pytest.raises(AssertionError, match="never written"):
+        y.check()
+    y.t.copy_(torch.arange(30.0).view(2, 3, 5))
+    y.t[1, 2, 4] = float("nan")
+    with pytest.raises(AssertionError, match="never written"):
+        y.check()
+    y.t[1, 2, 4] = 1.0
+    assert torch.equal(y.check(), y.t)
+    for at in (m.GUARD - 1, m.GUARD + 30, 0, -1):          # just before, just after, and at both far ends
+        y.base[at] = 0.0
+        with pytest.raises(AssertionError, match="guard"):
+            y.check()
+        y.base.view(torch.int32)[at] = m.SENTINEL
+    y.check()
+    y.t[0, 0, 0] = float("inf")
+    with pytest.raises(AssertionError, match="non-finite"):
+        y.check()
+    x = m.In(torch.randn(3, 7), cpu)
+    assert torch.isnan(x.base[:m.GUARD]).all() and torch.isnan(x.base[-m.GUARD:]).all() and not torch.isnan(x.t).any()
+    x.check()
+    x.base[m.GUARD + 21] = 0.0
+    with pytest.raises(AssertionError, match="input"):
+        x.check()
+    # the per-element bound: an error that the global max would hide is caught in the small output it sits in
+    ref = torch.tensor([1e3, 1e-3], dtype=torch.float64)
+    A = ref.abs()
+    assert m.ratio(ref.float(), ref, A) < 1e-7
+    bad = ref.float().clone()
+    bad[1] *= 1.0 + 1e-4
+    assert m.ratio(bad, ref, A) > m.TAU_CEIL
+    from conftest import rel_err
+    assert rel_err(bad, ref) < 1e-9

@@ -161,10 +161,11 @@ def test_conv_igemm(dev, Cout, Cin, k, dil, T, B):
     h = C.c_void_p()
     _lib.check(L.dmel_conv_create(C.byref(h), w.data_ptr(), b.data_ptr(), Cout, Cin, k, dil))
     xd = x.to(dev)
-    y = torch.empty(B, Cout, T, device=dev)
+    y = torch.full((B, Cout, T), float("nan"), device=dev)          # poisoned: an element that is never stored fails the bar
     _lib.check(L.dmel_conv_forward(h, xd.data_ptr(), y.data_ptr(), B, T, _lib.stream_ptr()))
     torch.cuda.synchronize()
     L.dmel_conv_destroy(h)
+    assert not torch.isnan(y).any()
     assert rel_err(y, ref) < 2e-5
 
 
@@ -868,12 +869,16 @@ def test_conv_bf16_operand_mode(dev, Cout, Cin, k, dil, T, B):
         assert L.dmel_conv_set_precision(h, 7) < 0
         _lib.check(L.dmel_conv_set_precision(h, 1))
         xd = x.to(dev)
-        y = torch.empty(B, Cout, T, device=dev)
+        y = torch.full((B, Cout, T), float("nan"), device=dev)      # poisoned before every launch
         _lib.check(L.dmel_conv_forward(h, xd.data_ptr(), y.data_ptr(), B, T, _lib.stream_ptr()))
         torch.cuda.synchronize()
+        assert not torch.isnan(y).any()
         assert rel_err(y, ref) < 1e-5          # only fp32 accumulation order separates the two
         _lib.check(L.dmel_conv_set_precision(h, 0))                     # and back: the fp32 path is untouched
+        y.fill_(float("nan"))
         _lib.check(L.dmel_conv_forward(h, xd.data_ptr(), y.data_ptr(), B, T, _lib.stream_ptr()))
+        torch.cuda.synchronize()
+        assert not torch.isnan(y).any()
         assert rel_err(y, F.conv1d(x, w, b, dilation=dil, padding=dil * (k - 1) // 2)) < 2e-5
     finally:
         L.dmel_conv_destroy(h)
@@ -1039,13 +1044,14 @@ def test_conv_backward_matches_autograd(dev, Cout, Cin, k, dil, T, B):
     _lib.check(L.dmel_conv_create(C.byref(h), w.data_ptr(), b.data_ptr(), Cout, Cin, k, dil))
     try:
         xd, dyd = x.to(dev), dy.to(dev)
-        dx = torch.empty(B, Cin, T, device=dev)
+        dx = torch.full((B, Cin, T), float("nan"), device=dev)           # poisoned: every element must be stored
         dw = torch.full((Cout, Cin, k), float("nan"), device=dev)        # must be overwritten, not accumulated into
         db = torch.full((Cout,), float("nan"), device=dev)
         st = _lib.stream_ptr()
         _lib.check(L.dmel_conv_backward_data(h, dyd.data_ptr(), dx.data_ptr(), B, T, st))
         _lib.check(L.dmel_conv_backward_weight(h, xd.data_ptr(), dyd.data_ptr(), dw.data_ptr(), db.data_ptr(), B, T, st))
         torch.cuda.synchronize()
+        assert not (torch.isnan(dx).any() or torch.isnan(dw).any() or torch.isnan(db).any())
         assert rel_err(dx, x64.grad) < 2e-6
         assert rel_err(dw, w64.grad) < 2e-6
         assert rel_err(db, b64.grad) < 2e-6
