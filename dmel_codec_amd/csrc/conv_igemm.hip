@@ -18,7 +18,9 @@
 #include "conv.h"
 #include "conv_dev.h"
 #include "ops.h"
+#include <numeric>
 #include <type_traits>
+#include <utility>
 
 #include <cmath>
 #include <cstdlib>
@@ -389,11 +391,20 @@ __device__ __forceinline__ uint32_t pack_hi16(float lo, float hi) {      // {bf1
   return __builtin_amdgcn_perm(__float_as_uint(hi), __float_as_uint(lo), 0x07060302u);
 }
 
+// f(std::integral_constant<int, 0>{}), ..., f(std::integral_constant<int, N - 1>{}): a loop whose index is a constant expression in the body
+template <class F, int... I> __device__ __forceinline__ void static_for_impl(F& f, std::integer_sequence<int, I...>) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F> __device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
+
 // (amdgpu_waves_per_eu(2, 2) -- 166 VGPRs, accumulators out of the AGPRs -- was measured: 2-12 % slower on every bench shape, and the
 // allocator still parks one weight set on the B-fragment registers; the default register budget stays.)
-template <int WAVES_M, int WAVES_N, int MT, int NT, int MODE, int HALO, int NP, int KG, int PS = 0>
+// TAPS > 0: the single-segment form of the fp16-split kernel (launch_spec: one segment, unit input stride, TAPS taps, ceil(Cin / 16) a multiple of
+// KG / 2); its K loop is described above the loop.  TAPS = 0: the generic K loop over segments, chunks and taps.
+template <int WAVES_M, int WAVES_N, int MT, int NT, int MODE, int HALO, int NP, int KG, int PS = 0, int TAPS = 0>
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, NP == 2 ? 2 : 1) void conv_bf16_kernel(KArgs a) {
   static_assert(PS == 0 || NP == 2, "pre-split inputs exist for the fp16 split only");
+  static_assert(TAPS == 0 || (NP == 2 && PS == 0), "the single-segment K loop is built for the fp16 split of fp32 inputs");
   constexpr int BM = WAVES_M * MT * 32, BN = WAVES_N * NT * 32;
   constexpr int XS = BN + HALO;
   constexpr int SUB = KG / 2;                            // 16-channel K steps (per tap) per staged chunk
@@ -762,19 +773,88 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, NP == 2 ? 2 : 1) void conv_
     }
     sg = nsg; c16 = nc16; tap = ntap;
   };
-  // unrolled by the PD + 1 weight sets so that they rotate without register copies
-  // (DMEL_BPF: and by the two fragment sets -- the unroll is the least common multiple, so that both rotations are compile-time indices)
-  constexpr int UNR = DMEL_BPF ? ((PD + 1) % 2 ? 2 * (PD + 1) : PD + 1) : PD + 1;
-  static_assert(UNR <= 8, "k_step calls below cover an unroll of up to eight");
-  for (int s = 0; s < a.steps; s += UNR) {
-    k_step(std::integral_constant<int, 0>{}, s);
-    if (s + 1 < a.steps) k_step(std::integral_constant<int, 1>{}, s + 1);
-    if (UNR > 2 && s + 2 < a.steps) k_step(std::integral_constant<int, 2 % UNR>{}, s + 2);
-    if (UNR > 3 && s + 3 < a.steps) k_step(std::integral_constant<int, 3 % UNR>{}, s + 3);
-    if (UNR > 4 && s + 4 < a.steps) k_step(std::integral_constant<int, 4 % UNR>{}, s + 4);
-    if (UNR > 5 && s + 5 < a.steps) k_step(std::integral_constant<int, 5 % UNR>{}, s + 5);
-    if (UNR > 6 && s + 6 < a.steps) k_step(std::integral_constant<int, 6 % UNR>{}, s + 6);
-    if (UNR > 7 && s + 7 < a.steps) k_step(std::integral_constant<int, 7 % UNR>{}, s + 7);
+  if constexpr (TAPS > 0) {
+    // Single-segment K loop: for chunk (run time) { for sub < SUB { for tap < TAPS { step } } }, the steps of a chunk unrolled.  Same K order,
+    // MFMA order, weight ring, waits and staging steps as k_step, so the same bits; what k_step decides per step at run time (next tap / chunk /
+    // segment, whether this step stages x, which weight set, the fragment's row) is a constant here.  A step is: the weight loads of step s + PD
+    // (scalar base + one add), NP * NT ds_read_b128 at immediate offsets from one lane address (+ tap * dil, an SGPR product), the MFMAs, and
+    // the end-of-step vmcnt.  Chunks are unrolled CU at a time so that the weight-set index (step mod PD + 1) is a constant as well.
+    constexpr int SPC = SUB * TAPS;                                  // K steps per staged chunk
+    constexpr int CU = (PD + 1) / std::gcd(SPC, PD + 1);             // chunks per unrolled group: CU * SPC is a multiple of PD + 1
+    const int nck = a.steps / SPC;                                   // staged chunks (launch_b16 checks steps == nck * SPC)
+    const int last = a.steps - 1, dil = cur_dil;
+    const uint4* xl = Xb + h * XS + wave_n * (NT * 32) + l31;        // this lane's B-fragment column in buffer 0, piece 0, first row pair
+    auto chunk_steps = [&](auto U, int c) {
+      const bool more = c + 1 < nck;
+      const uint4* xc = xl + xbuf * (NP * PSZ);
+      static_for<SPC>([&](auto J) {
+        constexpr int j = decltype(J)::value, r = (decltype(U)::value * SPC + j) % (PD + 1);
+        constexpr int sub = j / TAPS, tap = j % TAPS;
+        // unconditional, clamped like k_step's: the last PD steps re-fetch the final step's fragments into a set nobody reads again
+        if (!(DMEL_EXP & 4)) load_w(wa[(r + PD) % (PD + 1)], min(c * SPC + (j + PD), last));
+        const uint4* xp = xc + sub * 2 * XS + tap * dil;
+        bf16x8 bcur[NT][NP];
+#pragma unroll
+        for (int ni = 0; ni < NT; ++ni)
+#pragma unroll
+          for (int p = 0; p < NP; ++p) bcur[ni][p] = __builtin_bit_cast(bf16x8, xp[p * PSZ + ni * 32]);
+#pragma unroll
+        for (int mi = 0; mi < MT; ++mi)
+#pragma unroll
+          for (int ni = 0; ni < NT; ++ni) {
+            const f16x8 ah = __builtin_bit_cast(f16x8, wa[r][mi][0]), al = __builtin_bit_cast(f16x8, wa[r][mi][1]);
+            const f16x8 bh = __builtin_bit_cast(f16x8, bcur[ni][0]), bl = __builtin_bit_cast(f16x8, bcur[ni][1]);
+            acl[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acl[mi][ni], 0, 0, 0);
+            acl[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acl[mi][ni], 0, 0, 0);
+            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[mi][ni], 0, 0, 0);
+          }
+        __builtin_amdgcn_s_waitcnt(kWaitW);
+        // staging as in k_step: the chunk's first step issues the next chunk's x loads, its second (or only) one writes them to the idle
+        // buffer, its last one publishes that buffer
+        if constexpr (j == 0) {
+          if (more && !(DMEL_EXP & 2)) load_x(0, c + 1);
+        }
+        if constexpr (j == (SPC > 1 ? 1 : 0)) {
+          if (more && !(DMEL_EXP & 2)) store_x(Xb + (xbuf ^ 1) * (NP * PSZ), 0, c + 1);
+        }
+        if constexpr (j == SPC - 1) {
+          if (more) {
+            __syncthreads();
+            xbuf ^= 1;
+          }
+        }
+      });
+    };
+    // the exits sit between chunks: a guarded chunk that is skipped but falls through to the back edge would merge a path with other loads
+    // in flight into the loop header, and the compiler answers that with a vmcnt(0) at the top of every group
+    static_assert(CU <= 3, "the chunk group below covers up to three chunks");
+    for (int c = 0;; c += CU) {
+      chunk_steps(std::integral_constant<int, 0>{}, c);
+      if (c + 1 >= nck) break;
+      if constexpr (CU > 1) {
+        chunk_steps(std::integral_constant<int, 1>{}, c + 1);
+        if (c + 2 >= nck) break;
+      }
+      if constexpr (CU > 2) {
+        chunk_steps(std::integral_constant<int, 2>{}, c + 2);
+        if (c + 3 >= nck) break;
+      }
+    }
+  } else {
+    // unrolled by the PD + 1 weight sets so that they rotate without register copies
+    // (DMEL_BPF: and by the two fragment sets -- the unroll is the least common multiple, so that both rotations are compile-time indices)
+    constexpr int UNR = DMEL_BPF ? ((PD + 1) % 2 ? 2 * (PD + 1) : PD + 1) : PD + 1;
+    static_assert(UNR <= 8, "k_step calls below cover an unroll of up to eight");
+    for (int s = 0; s < a.steps; s += UNR) {
+      k_step(std::integral_constant<int, 0>{}, s);
+      if (s + 1 < a.steps) k_step(std::integral_constant<int, 1>{}, s + 1);
+      if (UNR > 2 && s + 2 < a.steps) k_step(std::integral_constant<int, 2 % UNR>{}, s + 2);
+      if (UNR > 3 && s + 3 < a.steps) k_step(std::integral_constant<int, 3 % UNR>{}, s + 3);
+      if (UNR > 4 && s + 4 < a.steps) k_step(std::integral_constant<int, 4 % UNR>{}, s + 4);
+      if (UNR > 5 && s + 5 < a.steps) k_step(std::integral_constant<int, 5 % UNR>{}, s + 5);
+      if (UNR > 6 && s + 6 < a.steps) k_step(std::integral_constant<int, 6 % UNR>{}, s + 6);
+      if (UNR > 7 && s + 7 < a.steps) k_step(std::integral_constant<int, 7 % UNR>{}, s + 7);
+    }
   }
   if constexpr (NP == 2) {
 #pragma unroll
@@ -788,7 +868,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, NP == 2 ? 2 : 1) void conv_
   conv_epilogue<MT, NT, MODE, NP == 2 ? 8 : 4>(a, acc, mblk * BM + wave_m * (MT * 32), q0 + wave_n * (NT * 32) + l31, b, lb, h);
 }
 
-template <int WM, int WN, int MT, int NT, int MODE, int HALO, int NP, int KG, int PS = 0>
+template <int WM, int WN, int MT, int NT, int MODE, int HALO, int NP, int KG, int PS = 0, int TAPS = 0>
 static int launch_b16k(const KArgs& ka, int B, int mblocks, hipStream_t st) {
   constexpr int BN = WN * NT * 32;
 #ifndef DMEL_CONV_LDS_PAD
@@ -800,9 +880,49 @@ static int launch_b16k(const KArgs& ka, int B, int mblocks, hipStream_t st) {
   KArgs k2 = ka;
   dim3 grid;
   DMEL_TRY(conv_grid(k2, (int)((ka.Tcols + BN - 1) / BN), mblocks, B, grid));
-  hipLaunchKernelGGL((conv_bf16_kernel<WM, WN, MT, NT, MODE, HALO, NP, KG, PS>), grid, dim3(64 * WM * WN), lds, st, k2);
+  hipLaunchKernelGGL((conv_bf16_kernel<WM, WN, MT, NT, MODE, HALO, NP, KG, PS, TAPS>), grid, dim3(64 * WM * WN), lds, st, k2);
   DMEL_HIP(hipGetLastError());
   return DMEL_OK;
+}
+
+// DMEL_CONV_SPEC=0: every fp16-split launch takes the generic K loop (A/B, bit-identity tests).  Read per call.
+static bool conv_spec_enabled() {
+  const char* e = getenv("DMEL_CONV_SPEC");
+  return !(e && e[0] == '0');
+}
+
+// Single-segment instances of the fp16-split kernel (conv_bf16_kernel<TAPS > 0>), only for the launches of the vocoder's AMP blocks (taps 3 /
+// 7 / 11 on the 64- to 256-column tiles) and the 1x1 convolutions on the 128 x 96 tile (the decoder WaveNet's residual / skip projection).
+// Returns false when the launch has none.
+template <int WM, int WN, int MT, int NT, int MODE, int KG0, int KGT>
+static bool launch_spec(const KArgs& ka, int halo, int B, int mblocks, hipStream_t st, int& rc) {
+  constexpr bool amp = MODE == EPI_LINEAR && MT == 1 && ((WM == 4 && WN == 1 && (NT == 2 || NT == 3)) || (WM == 2 && WN == 2 && NT == 2) ||
+                                                         (WM == 1 && WN == 4 && NT == 2) || (WM == 8 && WN == 1 && NT == 3));
+  constexpr bool amp64 = amp && NT == 2;             // the halo-64 convolutions of the 96-column tiles run on conv_pc
+  constexpr bool pw = MODE != EPI_GATE && WM == 4 && WN == 1 && MT == 1 && NT == 3;
+  if constexpr (amp || pw) {
+    const SegArgs& sa = ka.seg[0];
+    if (ka.nseg != 1 || sa.tstride != 1 || sa.xp != nullptr || !conv_spec_enabled()) return false;
+    const int taps = sa.taps, sub = halo == 0 ? KG0 / 2 : KGT / 2;
+    if (sa.nchunk % sub != 0 || ka.steps != sa.nchunk * taps) return false;
+    if constexpr (amp) {
+      if (halo > 0 && halo <= 16) {
+        if (taps == 3) { rc = launch_b16k<WM, WN, MT, NT, MODE, 16, 2, KGT, 0, 3>(ka, B, mblocks, st); return true; }
+        if (taps == 7) { rc = launch_b16k<WM, WN, MT, NT, MODE, 16, 2, KGT, 0, 7>(ka, B, mblocks, st); return true; }
+        if (taps == 11) { rc = launch_b16k<WM, WN, MT, NT, MODE, 16, 2, KGT, 0, 11>(ka, B, mblocks, st); return true; }
+      }
+      if constexpr (amp64) {
+        if (halo > 16) {
+          if (taps == 7) { rc = launch_b16k<WM, WN, MT, NT, MODE, 64, 2, KGT, 0, 7>(ka, B, mblocks, st); return true; }
+          if (taps == 11) { rc = launch_b16k<WM, WN, MT, NT, MODE, 64, 2, KGT, 0, 11>(ka, B, mblocks, st); return true; }
+        }
+      }
+    }
+    if constexpr (pw) {
+      if (halo == 0) { rc = launch_b16k<WM, WN, MT, NT, MODE, 0, 2, KG0, 0, 1>(ka, B, mblocks, st); return true; }
+    }
+  }
+  return false;
 }
 
 template <int WM, int WN, int MT, int NT, int MODE, int NP> static int launch_b16(const KArgs& ka, int B, int mblocks, hipStream_t st) {
@@ -810,9 +930,13 @@ template <int WM, int WN, int MT, int NT, int MODE, int NP> static int launch_b1
   for (int s = 0; s < ka.nseg; ++s) halo = std::max(halo, (ka.seg[s].taps - 1) * ka.seg[s].dil);
   // 1x1 convolutions stage 32 channels per barrier (two K steps); everything else 16 (taps K steps)
   constexpr int KG0 = (WN * NT * 32 >= 256 && NP == 3) ? 2 : 4;       // keep the widest tile inside 64 KiB of LDS
+  constexpr int KGT = (NP == 2 && 2 * NP * DMEL_KG2 * (WN * NT * 32 + 64) * 16 <= 65536) ? DMEL_KG2 : 2;
+  if constexpr (NP == 2) {
+    int rc = DMEL_OK;
+    if (launch_spec<WM, WN, MT, NT, MODE, KG0, KGT>(ka, halo, B, mblocks, st, rc)) return rc;
+  }
   if (halo == 0) return launch_b16k<WM, WN, MT, NT, MODE, 0, NP, KG0>(ka, B, mblocks, st);
   // dilation-1 convs (every second conv of an AMP block, k2 transposed-conv phases): a 16-column halo is enough
-  constexpr int KGT = (NP == 2 && 2 * NP * DMEL_KG2 * (WN * NT * 32 + 64) * 16 <= 65536) ? DMEL_KG2 : 2;
   if (halo <= 16) return launch_b16k<WM, WN, MT, NT, MODE, 16, NP, KGT>(ka, B, mblocks, st);
   return launch_b16k<WM, WN, MT, NT, MODE, 64, NP, KGT>(ka, B, mblocks, st);
 }

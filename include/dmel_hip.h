@@ -56,6 +56,9 @@ extern "C" {
  *      tensor is an operand as it is, the fp16 split where the operand is an activation (discriminator / decoder forward) or a gradient
  *      tensor the library first scales by its own maximum (the discriminator's backward-data and long-row weight gradients: a reduction on
  *      the same stream finds max |dy|, the kernel stages dy x 2^(13 - exponent)).
+ *      Single-segment launches (one input, unit input stride: the vocoder's AMP-block convolutions, 1x1 projections) run a form of the
+ *      kernel whose tap count is compiled in; it computes the same bits as the generic form.  DMEL_CONV_SPEC=0 (read per launch) sends
+ *      every launch to the generic form, for A/B timing and bit-identity tests.
  *  FP32_BF16X3: force the six-product bf16 split where FP32 would pick the fp16 one.
  *  BF16: opt-in throughput mode, the library-side equivalent of running the reference's codec under dtype: bfloat16
  *      (config/lm/lm_config.yaml:1,83; models/lm_lit_modules.py:52-55): weights and staged activations rounded to bf16
