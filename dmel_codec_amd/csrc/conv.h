@@ -118,6 +118,9 @@ struct ConvRun {
 };
 
 int launch_conv(const PackedConv& pc, const ConvRun& r, hipStream_t stream);
+// DMEL_CONV_FP32_MFMA: every fp32-grade convolution on the native fp32 MFMA (bench.py's A/B of the split kernels).  Unset, empty or 0 is
+// off; read once per process.  The fused WaveNet kernel, the producer / consumer kernel and the pre-split path stand aside while it is on.
+bool conv_fp32_mfma_forced();
 // x (B, C, T) fp32 -> the two pre-split planes (SegRun::xp layout), columns at or behind len[b / len_div] written as zero; C % 8 == 0
 int launch_split_planes(const float* x, void* planes, int64_t plane_units, const int64_t* len, int len_div, int B, int C, int64_t T,
                         hipStream_t stream);

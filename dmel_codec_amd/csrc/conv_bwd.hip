@@ -139,16 +139,14 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgArgs a) {
 }
 
 // ---- split-fp32 variant ------------------------------------------------------------------------------------------------
-// The same GEMM on the bf16 matrix core with every fp32 operand written as the exact sum of three bf16 pieces (conv_igemm.hip's
-// arithmetic: six partial products per 32 x 32 x 16 block, dropped terms < 2^-21 relative, fp32 accumulate).  Both operands are
-// time-contiguous, i.e. already K-major: a thread loads eight consecutive samples of one row, splits them and stores three
-// 16-byte units -- exactly one lane's MFMA operand -- into the piece planes of the LDS tile.
+// The same GEMM on the 16-bit matrix core with every fp32 operand written as two fp16 pieces (conv_igemm.hip's fp16 split: three partial
+// products per 32 x 32 x 16 block, fp32 accumulate), or rounded to one bf16 piece in the bf16 training mode.  Both operands are
+// time-contiguous, i.e. already K-major: a thread loads eight consecutive samples of one row, splits them and stores one 16-byte unit per
+// piece -- exactly one lane's MFMA operand -- into the piece planes of the LDS tile.  (The six-product split into three exact bf16 pieces
+// that this kernel started with lost every long row to the fp16 split and had no caller left.)
 typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
 typedef __bf16 wg_bf16x8 __attribute__((ext_vector_type(8)));
 
-__device__ __forceinline__ uint32_t wg_pack_hi16(float lo, float hi) {
-  return __builtin_amdgcn_perm(__float_as_uint(hi), __float_as_uint(lo), 0x07060302u);
-}
 typedef _Float16 wg_f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 wg_f16x2 __attribute__((ext_vector_type(2)));
 typedef float wg_f32x2 __attribute__((ext_vector_type(2)));
@@ -165,40 +163,25 @@ __device__ __forceinline__ void wg_split_store(const float (&v)[8], uint4* plane
     }
     plane0[idx] = __builtin_bit_cast(uint4, ph);
     plane0[plane_stride + idx] = __builtin_bit_cast(uint4, pl);
-    return;
-  }
-  if constexpr (NP == 1) {
+  } else {
+    static_assert(NP == 1, "one bf16 piece or two fp16 pieces");
     wg_bf16x8 p;
 #pragma unroll
     for (int e = 0; e < 8; ++e) p[e] = (__bf16)v[e];
     plane0[idx] = __builtin_bit_cast(uint4, p);
-    return;
   }
-  uint32_t p1[4], p2[4], p3[4];
-#pragma unroll
-  for (int e = 0; e < 8; e += 2) {
-    const float r0 = v[e] - __uint_as_float(__float_as_uint(v[e]) & 0xffff0000u);
-    const float r1 = v[e + 1] - __uint_as_float(__float_as_uint(v[e + 1]) & 0xffff0000u);
-    const float s0 = r0 - __uint_as_float(__float_as_uint(r0) & 0xffff0000u);
-    const float s1 = r1 - __uint_as_float(__float_as_uint(r1) & 0xffff0000u);
-    p1[e >> 1] = wg_pack_hi16(v[e], v[e + 1]);
-    p2[e >> 1] = wg_pack_hi16(r0, r1);
-    p3[e >> 1] = wg_pack_hi16(s0, s1);
-  }
-  plane0[idx] = make_uint4(p1[0], p1[1], p1[2], p1[3]);
-  plane0[plane_stride + idx] = make_uint4(p2[0], p2[1], p2[2], p2[3]);
-  plane0[2 * plane_stride + idx] = make_uint4(p3[0], p3[1], p3[2], p3[3]);
 }
 
 // XS = a.xstride (1 or 2); workgroup tile (64 MT) x (64 NT) output x input channels, 2 x 2 waves of (32 MT) x (32 NT); KS samples per
-// staged step.  <1, 1, 64>: the fp32 kernel's tile (default).  <2, 2, 32>: 128 x 128, twice the flops per byte moved from L2 (opt-in).
+// staged step.  <1, 1, 64>, the fp32 kernel's tile, is the one instantiated: 128 x 128 x 32 measured slower on every shape (42-81 vs 67-92
+// TF/s: 256 VGPRs and 60 KB of LDS leave one or two workgroups per CU, and a 32-sample step has two barriers per 48 MFMAs -- the kernel is
+// bound by latency between barriers, not by L2 bytes).
 // grid (ceil(Cin / (64 NT)), ceil(Cout / (64 MT)), taps * slices); a.chunks_per_item counts KS-sample steps.
-// NP = 3: split fp32 (exact products); NP = 1: operands rounded to bf16 (round to nearest even), one MFMA per block -- the bf16 training mode
-// FLAT (round 3): the reduction runs over the flattened sample index n = b * T + t in steps of KS, as conv_wgrad_kernel<2> does, for rows of
-// 33..255 samples (the 92-frame WaveNet GEMMs ran on the fp32 MFMA at its peak, 158 TF/s: the matrix pipe itself was the limit).  Every
-// step takes the clamped scalar loads of the boundary path, with the item index carried per element (a group of 8 samples crosses at
-// most one item boundary because T > 8).
-template <int XS, int MT, int NT, int KS, int NP = 3, bool FLAT = false>
+// NP = 2: fp16 split, dy scaled by the launch's max; NP = 1: operands rounded to bf16 (round to nearest even), one MFMA per block -- the bf16
+// training mode.  Rows of 33..255 samples stay on conv_wgrad_kernel<2>: a flattened-index form of this kernel measured 25.8 -> 30.5 ms of
+// weight-gradient time per training step (its staging -- scalar loads with per-element item indices, masks, scale, split, pack: ~500 vector
+// instructions per 64-sample step and wave -- costs what the 32 fp32 MFMAs it replaces cost, plus one absmax launch per gradient tensor).
+template <int XS, int MT, int NT, int KS, int NP>
 __global__ __launch_bounds__(256) void conv_wgrad_split_kernel(WgArgs a) {
   constexpr int UR = KS / 8 + 1;                                 // uint4 units per LDS row incl. one pad unit: conflict-free 128-bit reads
   constexpr int RM = 64 * MT, RN = 64 * NT;                      // staged rows of dy / x
@@ -236,7 +219,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_split_kernel(WgArgs a) {
     x_mul = kF16XScale;
     out_mul = __uint_as_float((uint32_t)(127 - 13 + e) << 23) * (1.f / kF16XScale);
   }
-  const int total = FLAT ? (a.B * a.T + KS - 1) / KS : a.B * a.chunks_per_item;
+  const int total = a.B * a.chunks_per_item;
   const int c_begin = slice * a.chunks_per_slice, c_end = min(total, c_begin + a.chunks_per_slice);
   const int r31 = lane & 31, hh = lane >> 5;
   const int srow = tid / G, sg = tid % G;                        // staging: row within a pass, group of 8 samples
@@ -247,41 +230,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_split_kernel(WgArgs a) {
   unsigned md[2][PD], mx[2][PX];
   auto fetch = [&](auto set, int c) {
     constexpr int S = decltype(set)::value;
-    if constexpr (FLAT) {
-      const int n0 = c * KS + 8 * sg;
-      const int b0 = n0 / a.T, t0f = n0 - b0 * a.T;
-      int64_t offd[8], offx[8];              // element offsets without the row term
-      unsigned okd = 0, okx = 0;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        int te = t0f + e, be = b0;
-        if (te >= a.T) { te -= a.T; be += 1; }
-        const bool ok = be < a.B;
-        const int bc = min(be, a.B - 1);
-        const int tx = te * XS + a.xoff + shift;
-        offd[e] = (int64_t)bc * a.Cout * a.T + te;
-        offx[e] = (int64_t)bc * a.Cin * a.Tx + min(max(tx, 0), a.Tx - 1);
-        okd |= (unsigned)ok << e;
-        okx |= (unsigned)(ok && tx >= 0 && tx < a.Tx) << e;
-      }
-#pragma unroll
-      for (int ps = 0; ps < PD; ++ps) {
-        const int co = co0 + srow + RP * ps;
-        const float* p = a.dy + (int64_t)min(co, a.Cout - 1) * a.T;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) rd[S][ps][e] = p[offd[e]];
-        md[S][ps] = co < a.Cout ? okd : 0u;
-      }
-#pragma unroll
-      for (int ps = 0; ps < PX; ++ps) {
-        const int ci = ci0 + srow + RP * ps;
-        const float* q = a.x + (int64_t)min(ci, a.Cin - 1) * a.Tx;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) rx[S][ps][e] = q[offx[e]];
-        mx[S][ps] = ci < a.Cin ? okx : 0u;
-      }
-      return;
-    }
     const int b = c / a.chunks_per_item;
     const int t0 = (c - b * a.chunks_per_item) * KS;
     const int t = t0 + 8 * sg;
@@ -390,14 +338,10 @@ __global__ __launch_bounds__(256) void conv_wgrad_split_kernel(WgArgs a) {
             acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[mi][ni], 0, 0, 0);
           }
       } else {
-        constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};   // smallest partial products first
 #pragma unroll
-        for (int u = 0; u < (NP == 3 ? 6 : 1); ++u)
+        for (int mi = 0; mi < MT; ++mi)
 #pragma unroll
-          for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < NT; ++ni)
-              acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[mi][NP == 3 ? PA[u] : 0], bf[ni][NP == 3 ? PB[u] : 0], acc[mi][ni], 0, 0, 0);
+          for (int ni = 0; ni < NT; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[mi][0], bf[ni][0], acc[mi][ni], 0, 0, 0);
       }
     }
   };
@@ -619,18 +563,6 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ v
   }
 }
 
-// DMEL_WGRAD_FP32_MFMA=1 keeps every weight gradient on the native fp32 MFMA kernel (A/B switch)
-static bool wgrad_native_only() {
-  static const bool v = [] { const char* e = getenv("DMEL_WGRAD_FP32_MFMA"); return e && e[0] == '1'; }();
-  return v;
-}
-// DMEL_WGRAD_TILE128=1 moves the split kernel to its 128 x 128 x 32 instantiation where both channel counts allow (A/B switch).
-// Measured slower than 64 x 64 x 64 on every shape (42-81 vs 67-92 TF/s): 256 VGPRs and 60 KB of LDS leave one or two workgroups
-// per CU, and a 32-sample step has two barriers per 48 MFMAs -- the kernel is bound by latency between barriers, not by L2 bytes.
-static bool wgrad_big_tile() {
-  static const bool v = [] { const char* e = getenv("DMEL_WGRAD_TILE128"); return e && e[0] == '1'; }();
-  return v;
-}
 int launch_absmax(const float* v, int64_t n, hipStream_t st, const uint32_t** out) {
   // a ring of device words: launches of one thread are ordered on their stream; the ring keeps earlier launches' words alive while later
   // ones are queued
@@ -652,44 +584,30 @@ int launch_absmax(const float* v, int64_t n, hipStream_t st, const uint32_t** ou
 
 // picks the kernel, then the K slicing for its tile and step (a: everything but chunks_per_item / ipc / slices / chunks_per_slice)
 static int launch_wgrad_any(WgArgs a, hipStream_t st) {
+  const bool bf16_mode = train_precision_override() == DMEL_PRECISION_BF16;      // TrainPrecisionScope
+  // T <= 32: several batch items share one staged 64-sample step
   a.ipc = a.T <= 32 ? kWgK / a.T : 1;
-  // short rows are mostly boundary steps (scalar loads in the split kernel): they stay on the fp32-MFMA kernel
-  const bool split = a.ipc == 1 && !wgrad_native_only() && a.xstride <= 2 && a.T >= 256;
+  const bool ipc = a.ipc > 1;
+  // long rows go to the 16-bit matrix core; short rows are mostly boundary steps (scalar loads in the split kernel): they stay on the
+  // exact fp32-MFMA kernel, which is at least as accurate
+  const bool split = a.ipc == 1 && a.xstride <= 2 && a.T >= 256;
+  // rows of 33..255 samples whose last 64-sample step would be mostly padding (T = 92: 30 % of the MFMA work) reduce over the flattened index
+  const bool flat = !split && !ipc && a.T < 256 && (int64_t)a.B * a.T < ((int64_t)1 << 30) && ((a.T + kWgK - 1) / kWgK) * kWgK * 10 > a.T * 11;
   // the three-tap kernel also serves the bf16 training mode (its fp16 split is more accurate than bf16 operands and, without atomics, faster)
-  const bool can_group = split && a.dil == 1 && a.taps % 3 == 0;
-  // rows of 33..255 samples whose last 64-sample step would be mostly padding (T = 92: 30 % of the MFMA work) reduce over the flattened
-  // index; in fp32 training mode on the fp16-split kernel (FLAT instantiation), which needs the launch's max |dy| like the long rows do
-  static const bool flat_off = [] { const char* e = getenv("DMEL_WGRAD_NOFLAT"); return e != nullptr; }();
-  // measured (round 3, tools/bench_train_step.py): weight-gradient time per step 25.8 -> 30.5 ms with the FLAT fp16-split instantiation --
-  // its staging (scalar loads with per-element item indices, masks, scale, split, pack: ~500 vector instructions per 64-sample step and
-  // wave) costs what the 32 fp32 MFMAs it replaces cost (2048 cycles), plus one absmax launch per gradient tensor.  Opt-in, for A/B.
-  static const bool flat16_off = [] { const char* e = getenv("DMEL_WGRAD_FLAT16"); return !(e && e[0] == '1'); }();
-  static const bool f16_off0 = [] { const char* e = getenv("DMEL_WGRAD_F16X2"); return e && e[0] == '0'; }();
-  const bool flat_shape = !split && a.ipc == 1 && a.T < 256 && (int64_t)a.B * a.T < ((int64_t)1 << 30) &&
-                          ((a.T + kWgK - 1) / kWgK) * kWgK * 10 > a.T * 11 && !flat_off;
-  const bool flat16 = flat_shape && a.T >= 33 && a.xstride <= 2 && !wgrad_native_only() && !flat16_off && !f16_off0 &&
-                      train_precision_override() != DMEL_PRECISION_BF16;
-  if ((split && (train_precision_override() != DMEL_PRECISION_BF16 || can_group)) || flat16) {
+  const bool grouped = split && a.dil == 1 && a.taps % 3 == 0;
+  // what is left of the long rows: the one-piece instantiation of the split kernel in bf16 training mode, the fp16-split one otherwise
+  const bool bf16 = split && !grouped && bf16_mode;
+  if (split && !bf16) {      // the fp16 split scales dy by the launch's max
     if (!a.dy_absmax) DMEL_TRY(launch_absmax(a.dy, (int64_t)a.B * a.Cout * a.T, st, &a.dy_absmax));
   } else {
     a.dy_absmax = nullptr;
   }
-  // bf16 training mode (TrainPrecisionScope): long rows take the one-piece instantiation of the split kernel; short rows (the 92-frame
-  // WaveNet GEMMs, packed image rows) stay on the exact fp32-MFMA kernel, which is at least as accurate
-  static const bool group_off0 = [] { const char* e = getenv("DMEL_WGRAD_TAPGROUP"); return e && e[0] == '0'; }();
-  static const bool f16_off = [] { const char* e = getenv("DMEL_WGRAD_F16X2"); return e && e[0] == '0'; }();
-  const bool bf16 = split && train_precision_override() == DMEL_PRECISION_BF16 && !(can_group && !group_off0 && !f16_off && a.dy_absmax);
-  // fp32 mode: long rows take the fp16-split instantiation (three products, cheaper operand conversion; DMEL_WGRAD_F16X2=0: the six-product one)
-  const bool f16 = split && !bf16 && !f16_off && a.dy_absmax != nullptr;
-  static const bool group_off = [] { const char* e = getenv("DMEL_WGRAD_TAPGROUP"); return e && e[0] == '0'; }();
-  const bool grouped = f16 && !group_off && a.dil == 1 && a.taps % 3 == 0;
   if (grouped) {
     a.chunks_per_item = (a.T + 63) / 64;
     const int tm = (a.Cout + 63) / 64, tn = (a.Cin + 63) / 64, groups = a.taps / 3;
     const int total = a.B * a.chunks_per_item;
     // ~1024 workgroups (two per CU resident): 256 -> 33.9 ms, 512 -> 30.4, 1024 -> 29.9, 2048 -> 29.8 ms of weight-gradient time per training step
-    const char* we = getenv("DMEL_WGRAD_WANT");
-    const int wantg = we ? atoi(we) : 1024;
+    constexpr int wantg = 1024;
     int slices = std::max(1, std::min((wantg + tm * tn * groups - 1) / (tm * tn * groups), (total + 7) / 8));
     slices = std::min(slices, 65535 / groups);
     a.slices = slices;
@@ -720,34 +638,24 @@ static int launch_wgrad_any(WgArgs a, hipStream_t st) {
     DMEL_HIP(hipGetLastError());
     return DMEL_OK;
   }
-  const bool big = split && !bf16 && !f16 && a.Cout >= 128 && a.Cin >= 128 && wgrad_big_tile();
-  const int tile = big ? 128 : kWgTile, ks = big ? 32 : kWgK;
-  a.chunks_per_item = (a.T + ks - 1) / ks;
-  const int tm = (a.Cout + tile - 1) / tile, tn = (a.Cin + tile - 1) / tile;
+  a.chunks_per_item = (a.T + kWgK - 1) / kWgK;
+  const int tm = (a.Cout + kWgTile - 1) / kWgTile, tn = (a.Cin + kWgTile - 1) / kWgTile;
   const int tiles = tm * tn * a.taps;
-  const bool flat = flat_shape;
-  const int total = a.ipc > 1 ? (a.B + a.ipc - 1) / a.ipc : flat ? (a.B * a.T + kWgK - 1) / kWgK : a.B * a.chunks_per_item;
-  // enough K slices to fill the chip (~8 workgroups of the small tile / ~4 of the large one per CU), each at least 8 staged steps long
-  const char* we2 = getenv("DMEL_WGRAD_WANT");
-  const int want = we2 ? atoi(we2) : (big ? 1024 : 2048);
+  const int total = ipc ? (a.B + a.ipc - 1) / a.ipc : flat ? (a.B * a.T + kWgK - 1) / kWgK : a.B * a.chunks_per_item;
+  // enough K slices to fill the chip (~8 workgroups per CU), each at least 8 staged steps long
+  constexpr int want = 2048;
   int slices = std::max(1, std::min((want + tiles - 1) / tiles, (total + 7) / 8));
   slices = std::min(slices, 65535 / a.taps);
   a.slices = slices;
   a.chunks_per_slice = (total + slices - 1) / slices;
   const dim3 grid((unsigned)tn, (unsigned)tm, (unsigned)(a.taps * slices));
-  if (a.ipc > 1) hipLaunchKernelGGL(conv_wgrad_kernel<1>, grid, dim3(256), 0, st, a);
-  else if (flat16 && a.xstride == 1) hipLaunchKernelGGL((conv_wgrad_split_kernel<1, 1, 1, 64, 2, true>), grid, dim3(256), 0, st, a);
-  else if (flat16) hipLaunchKernelGGL((conv_wgrad_split_kernel<2, 1, 1, 64, 2, true>), grid, dim3(256), 0, st, a);
+  if (ipc) hipLaunchKernelGGL(conv_wgrad_kernel<1>, grid, dim3(256), 0, st, a);
   else if (flat) hipLaunchKernelGGL(conv_wgrad_kernel<2>, grid, dim3(256), 0, st, a);
   else if (!split) hipLaunchKernelGGL(conv_wgrad_kernel<0>, grid, dim3(256), 0, st, a);
-  else if (big && a.xstride == 1) hipLaunchKernelGGL((conv_wgrad_split_kernel<1, 2, 2, 32>), grid, dim3(256), 0, st, a);
-  else if (big) hipLaunchKernelGGL((conv_wgrad_split_kernel<2, 2, 2, 32>), grid, dim3(256), 0, st, a);
-  else if (f16 && a.xstride == 1) hipLaunchKernelGGL((conv_wgrad_split_kernel<1, 1, 1, 64, 2>), grid, dim3(256), 0, st, a);
-  else if (f16) hipLaunchKernelGGL((conv_wgrad_split_kernel<2, 1, 1, 64, 2>), grid, dim3(256), 0, st, a);
   else if (bf16 && a.xstride == 1) hipLaunchKernelGGL((conv_wgrad_split_kernel<1, 1, 1, 64, 1>), grid, dim3(256), 0, st, a);
   else if (bf16) hipLaunchKernelGGL((conv_wgrad_split_kernel<2, 1, 1, 64, 1>), grid, dim3(256), 0, st, a);
-  else if (a.xstride == 1) hipLaunchKernelGGL((conv_wgrad_split_kernel<1, 1, 1, 64>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((conv_wgrad_split_kernel<2, 1, 1, 64>), grid, dim3(256), 0, st, a);
+  else if (a.xstride == 1) hipLaunchKernelGGL((conv_wgrad_split_kernel<1, 1, 1, 64, 2>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((conv_wgrad_split_kernel<2, 1, 1, 64, 2>), grid, dim3(256), 0, st, a);
   DMEL_HIP(hipGetLastError());
   return DMEL_OK;
 }

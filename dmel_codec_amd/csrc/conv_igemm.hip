@@ -280,10 +280,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_direct_kernel(KAr
 // when the weights of the launch do not fit one XCD's 4 MiB L2 next to the activations (large-M GEMMs: the WaveNet
 // decoder); small weight sets are L2-resident on every XCD anyway and keep the plain 3-D grid.
 static int conv_grid(KArgs& k, int gx, int gy, int gz, dim3& grid) {
-  static int mode = [] { const char* e = getenv("DMEL_CONV_XCD"); return e ? atoi(e) : -1; }();   // -1 auto, 0 off, 1 on
   k.gx = gx; k.gy = gy; k.gz = gz;
   const double weight_bytes = (double)k.mtiles * 32.0 * k.steps * kCK * 4.0;
-  const bool want = mode == 1 || (mode == -1 && weight_bytes > 2.5e6 && gy >= 8);
+  const bool want = weight_bytes > 2.5e6 && gy >= 8;
   const int64_t total = (int64_t)gx * gy * gz;
   if (want && total < ((int64_t)1 << 30)) {
     k.xcd_chunk = (int)((total + 7) / 8);
@@ -362,30 +361,9 @@ template <int WM, int WN, int MT, int NT, int MODE> static int launch_t(const KA
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-#ifndef DMEL_PD
-#define DMEL_PD 2   // weight prefetch distance in K steps
-#endif
-#ifndef DMEL_EXP
-#define DMEL_EXP 0   // what-if switches for profiling builds (wrong results): 2 no x staging, 4 no weight loads, 8 no epilogue
-#endif
-#ifndef DMEL_PD2
-#define DMEL_PD2 2  // ... of the fp16-split kernel (half the MFMA time per step)
-#endif
-#ifndef DMEL_XTOP
-// 1: issue the next chunk's x loads at the TOP of a chunk's first step, in front of that step's weight prefetch (two steps of MFMAs between
-// issue and use instead of one).  Round-3 experiment, A/B'd interleaved on one device against 0 (profiles/r03_conv_experiments.txt): no
-// shape gained (-4 .. +2 %), with or without a weight prefetch distance of 3 -- the x loads are not what the waves wait for.  Stays 0.
-#define DMEL_XTOP 0
-#endif
-#ifndef DMEL_BPF
-// 1: the B fragments of step s + 1 are read from LDS BEFORE the MFMAs of step s (two fragment register sets), whenever the next step
-// belongs to the same staged chunk.  A lone wave on its SIMD (the decoder WaveNet at 32 x 92 frames: 288 workgroups for 256 CUs) otherwise
-// meets the LDS latency at the top of every step with nothing else to issue.
-#define DMEL_BPF 0
-#endif
-#ifndef DMEL_KG2
-#define DMEL_KG2 2  // 8-channel groups staged per barrier by the fp16-split kernel when the convolution has taps
-#endif
+constexpr int kPD = 2;    // weight prefetch distance in K steps
+constexpr int kPD2 = 2;   // ... of the fp16-split kernel (half the MFMA time per step)
+constexpr int kKG2 = 2;   // 8-channel groups staged per barrier by the fp16-split kernel when the convolution has taps
 
 __device__ __forceinline__ uint32_t pack_hi16(float lo, float hi) {      // {bf16 bits of lo, bf16 bits of hi} by truncation
   return __builtin_amdgcn_perm(__float_as_uint(hi), __float_as_uint(lo), 0x07060302u);
@@ -420,11 +398,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, NP == 2 ? 2 : 1) void conv_
   constexpr int NIT = RPW * NPASS;                       // items per thread per chunk
   constexpr int PSZ = KG * XS;                           // uint4 per piece
   extern __shared__ __attribute__((aligned(16))) float smem[];
-#ifndef DMEL_CONV_LDS_PAD
-#define DMEL_CONV_LDS_PAD 0      // debug: bytes of unused LDS in front of and behind the kernel's own
-#endif
-  constexpr int kLdsPad = ((size_t)2 * NP * KG * XS * 16 + 2 * DMEL_CONV_LDS_PAD <= 65536) ? DMEL_CONV_LDS_PAD : 0;
-  uint4* Xb = reinterpret_cast<uint4*>(smem) + kLdsPad / 16;            // [2][NP][KG][XS] x 16 bytes
+  uint4* Xb = reinterpret_cast<uint4*>(smem);            // [2][NP][KG][XS] x 16 bytes
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wave_m = wave / WAVES_N, wave_n = wave % WAVES_N;
@@ -637,7 +611,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, NP == 2 ? 2 : 1) void conv_
   // Weight loads first, x loads last in the prologue: store_x then waits for the youngest load, so nothing is outstanding
   // when the loop is entered (a prologue load still pending at loop entry forces a static s_waitcnt vmcnt(0) into the loop
   // body, which then drains the NEXT steps' weight prefetch in every iteration).
-  constexpr int PD = NP == 2 ? DMEL_PD2 : DMEL_PD;
+  constexpr int PD = NP == 2 ? kPD2 : kPD;
   uint4 wa[PD + 1][MT][NP];
 #pragma unroll
   for (int d = 0; d < PD; ++d) load_w(wa[d], min(d, a.steps - 1));
@@ -665,13 +639,6 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, NP == 2 ? 2 : 1) void conv_
   // "PD = 3" experiment of profiles/r03_conv_experiments.txt measured nothing.)
   constexpr int kWKeep = (PD - 1) * kWLoads < 63 ? (PD - 1) * kWLoads : 63;
   constexpr int kWaitW = (kWKeep & 15) | (7 << 4) | (15 << 8) | ((kWKeep >> 4) << 14);     // s_waitcnt vmcnt((PD - 1) kWLoads)
-  constexpr int kXLoads = NIT * (PS != 0 ? 2 : 8);                                          // x loads per thread and chunk
-  constexpr int kWX = kWKeep + kXLoads < 63 ? kWKeep + kXLoads : 63;
-  [[maybe_unused]] constexpr int kWaitWX = (kWX & 15) | (7 << 4) | (15 << 8) | ((kWX >> 4) << 14);           // ... that also leaves a chunk of x loads in flight
-#if DMEL_BPF
-  bf16x8 bfrag[2][NT][NP];
-  bool have_frag = false;
-#endif
   auto k_step = [&](auto R, int s) {
     constexpr int r = decltype(R)::value;
     uint4 (&use)[MT][NP] = wa[r % (PD + 1)];
@@ -684,48 +651,16 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, NP == 2 ? 2 : 1) void conv_
       else newx = (nc16 % SUB) == 0;
     }
     const bool has_next = s + 1 < a.steps;
-#if DMEL_XTOP
-    // x loads of the NEXT chunk at the TOP of a chunk's first step, in front of this step's weight prefetch.  vmcnt retires in order: the wait
-    // for the weights of step s + 1 at the end of this step may leave these loads (and the weights of step s + 2) in flight, and only the
-    // wait at the end of step s + 1 -- for weights issued AFTER them -- forces them home.  Issued at the END of the step (as before) they
-    // sat behind one step of MFMAs only: ~300 cycles against an L2 / Infinity-Cache latency of 500-900, the rest a stall in every chunk.
-    bool x_younger = false;
-    if (cstep == 0) {
-      pending = next_chunk(sg, c16 / SUB, psg, pck);
-      if (pending && !(DMEL_EXP & 2)) { load_x(psg, pck); x_younger = !newx; }
-      if (DMEL_EXP & 2) pending = false;
-    }
-#endif
     // unconditional (the last PD steps re-fetch the final step's fragments into a set nobody reads again): a branch here
     // would put a wait-free path into the CFG and with it a conservative vmcnt(0) in front of the MFMAs
-    if (!(DMEL_EXP & 4)) load_w(wa[(r + PD) % (PD + 1)], min(s + PD, a.steps - 1));
+    load_w(wa[(r + PD) % (PD + 1)], min(s + PD, a.steps - 1));
     {
-#if DMEL_BPF
-      bf16x8 (&bcur)[NT][NP] = bfrag[r % 2];
-      bf16x8 (&bnxt)[NT][NP] = bfrag[(r + 1) % 2];
-      if (!have_frag) {
-        const uint4* xp = Xb + xbuf * (NP * PSZ) + ((c16 % SUB) * 2 + h) * XS + wave_n * (NT * 32) + l31 + tap * cur_dil;
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni)
-#pragma unroll
-          for (int p = 0; p < NP; ++p) bcur[ni][p] = __builtin_bit_cast(bf16x8, xp[p * PSZ + ni * 32]);
-      }
-      have_frag = has_next && !newx;
-      if (have_frag) {      // next step reads the same staged chunk: its fragments travel while this step multiplies
-        const uint4* xq = Xb + xbuf * (NP * PSZ) + ((nc16 % SUB) * 2 + h) * XS + wave_n * (NT * 32) + l31 + ntap * cur_dil;
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni)
-#pragma unroll
-          for (int p = 0; p < NP; ++p) bnxt[ni][p] = __builtin_bit_cast(bf16x8, xq[p * PSZ + ni * 32]);
-      }
-#else
       const uint4* xp = Xb + xbuf * (NP * PSZ) + ((c16 % SUB) * 2 + h) * XS + wave_n * (NT * 32) + l31 + tap * cur_dil;
       bf16x8 bcur[NT][NP];
 #pragma unroll
       for (int ni = 0; ni < NT; ++ni)
 #pragma unroll
         for (int p = 0; p < NP; ++p) bcur[ni][p] = __builtin_bit_cast(bf16x8, xp[p * PSZ + ni * 32]);
-#endif
       if constexpr (NP == 2) {
 #pragma unroll
         for (int mi = 0; mi < MT; ++mi)
@@ -749,18 +684,12 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, NP == 2 ? 2 : 1) void conv_
                                                                     bcur[ni][NP == 3 ? PB[t] : 0], acc[mi][ni], 0, 0, 0);
       }
     }
-#if DMEL_XTOP
-    if (x_younger) __builtin_amdgcn_s_waitcnt(kWaitWX);      // the weights of step s + 1 are older than the x loads: those may stay in flight
-    else __builtin_amdgcn_s_waitcnt(kWaitW);
-#else
     __builtin_amdgcn_s_waitcnt(kWaitW);
     if (cstep == 0) {
       pending = next_chunk(sg, c16 / SUB, psg, pck);
-      if (pending && !(DMEL_EXP & 2)) load_x(psg, pck);
-      if (DMEL_EXP & 2) pending = false;
+      if (pending) load_x(psg, pck);
     }
-#endif
-    if (pending && (((DMEL_EXP & 1) ? false : cstep == 1) || newx)) {       // second step of the chunk, or its only one
+    if (pending && (cstep == 1 || newx)) {       // second step of the chunk, or its only one
       store_x(Xb + (xbuf ^ 1) * (NP * PSZ), psg, pck);
       pending = false;
     }
@@ -791,7 +720,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, NP == 2 ? 2 : 1) void conv_
         constexpr int j = decltype(J)::value, r = (decltype(U)::value * SPC + j) % (PD + 1);
         constexpr int sub = j / TAPS, tap = j % TAPS;
         // unconditional, clamped like k_step's: the last PD steps re-fetch the final step's fragments into a set nobody reads again
-        if (!(DMEL_EXP & 4)) load_w(wa[(r + PD) % (PD + 1)], min(c * SPC + (j + PD), last));
+        load_w(wa[(r + PD) % (PD + 1)], min(c * SPC + (j + PD), last));
         const uint4* xp = xc + sub * 2 * XS + tap * dil;
         bf16x8 bcur[NT][NP];
 #pragma unroll
@@ -812,10 +741,10 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, NP == 2 ? 2 : 1) void conv_
         // staging as in k_step: the chunk's first step issues the next chunk's x loads, its second (or only) one writes them to the idle
         // buffer, its last one publishes that buffer
         if constexpr (j == 0) {
-          if (more && !(DMEL_EXP & 2)) load_x(0, c + 1);
+          if (more) load_x(0, c + 1);
         }
         if constexpr (j == (SPC > 1 ? 1 : 0)) {
-          if (more && !(DMEL_EXP & 2)) store_x(Xb + (xbuf ^ 1) * (NP * PSZ), 0, c + 1);
+          if (more) store_x(Xb + (xbuf ^ 1) * (NP * PSZ), 0, c + 1);
         }
         if constexpr (j == SPC - 1) {
           if (more) {
@@ -842,18 +771,13 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, NP == 2 ? 2 : 1) void conv_
     }
   } else {
     // unrolled by the PD + 1 weight sets so that they rotate without register copies
-    // (DMEL_BPF: and by the two fragment sets -- the unroll is the least common multiple, so that both rotations are compile-time indices)
-    constexpr int UNR = DMEL_BPF ? ((PD + 1) % 2 ? 2 * (PD + 1) : PD + 1) : PD + 1;
-    static_assert(UNR <= 8, "k_step calls below cover an unroll of up to eight");
+    constexpr int UNR = PD + 1;
+    static_assert(UNR <= 4, "k_step calls below cover an unroll of up to four");
     for (int s = 0; s < a.steps; s += UNR) {
       k_step(std::integral_constant<int, 0>{}, s);
       if (s + 1 < a.steps) k_step(std::integral_constant<int, 1>{}, s + 1);
       if (UNR > 2 && s + 2 < a.steps) k_step(std::integral_constant<int, 2 % UNR>{}, s + 2);
       if (UNR > 3 && s + 3 < a.steps) k_step(std::integral_constant<int, 3 % UNR>{}, s + 3);
-      if (UNR > 4 && s + 4 < a.steps) k_step(std::integral_constant<int, 4 % UNR>{}, s + 4);
-      if (UNR > 5 && s + 5 < a.steps) k_step(std::integral_constant<int, 5 % UNR>{}, s + 5);
-      if (UNR > 6 && s + 6 < a.steps) k_step(std::integral_constant<int, 6 % UNR>{}, s + 6);
-      if (UNR > 7 && s + 7 < a.steps) k_step(std::integral_constant<int, 7 % UNR>{}, s + 7);
     }
   }
   if constexpr (NP == 2) {
@@ -864,18 +788,13 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, NP == 2 ? 2 : 1) void conv_
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[mi][ni][r] = fmaf(acl[mi][ni][r], 1.f / kF16LoScale, acc[mi][ni][r]) * f16_out;
   }
-  if ((DMEL_EXP & 8) && acc[0][0][0] != 12345.f) return;
   conv_epilogue<MT, NT, MODE, NP == 2 ? 8 : 4>(a, acc, mblk * BM + wave_m * (MT * 32), q0 + wave_n * (NT * 32) + l31, b, lb, h);
 }
 
 template <int WM, int WN, int MT, int NT, int MODE, int HALO, int NP, int KG, int PS = 0, int TAPS = 0>
 static int launch_b16k(const KArgs& ka, int B, int mblocks, hipStream_t st) {
   constexpr int BN = WN * NT * 32;
-#ifndef DMEL_CONV_LDS_PAD
-#define DMEL_CONV_LDS_PAD 0
-#endif
-  constexpr size_t lds0 = (size_t)2 * NP * KG * (BN + HALO) * 16;
-  constexpr size_t lds = lds0 + (lds0 + 2 * DMEL_CONV_LDS_PAD <= 65536 ? 2 * DMEL_CONV_LDS_PAD : 0);
+  constexpr size_t lds = (size_t)2 * NP * KG * (BN + HALO) * 16;
   static_assert(lds <= 64 * 1024, "bf16 conv tile exceeds the default dynamic LDS limit");
   KArgs k2 = ka;
   dim3 grid;
@@ -930,7 +849,7 @@ template <int WM, int WN, int MT, int NT, int MODE, int NP> static int launch_b1
   for (int s = 0; s < ka.nseg; ++s) halo = std::max(halo, (ka.seg[s].taps - 1) * ka.seg[s].dil);
   // 1x1 convolutions stage 32 channels per barrier (two K steps); everything else 16 (taps K steps)
   constexpr int KG0 = (WN * NT * 32 >= 256 && NP == 3) ? 2 : 4;       // keep the widest tile inside 64 KiB of LDS
-  constexpr int KGT = (NP == 2 && 2 * NP * DMEL_KG2 * (WN * NT * 32 + 64) * 16 <= 65536) ? DMEL_KG2 : 2;
+  constexpr int KGT = (NP == 2 && 2 * NP * kKG2 * (WN * NT * 32 + 64) * 16 <= 65536) ? kKG2 : 2;
   if constexpr (NP == 2) {
     int rc = DMEL_OK;
     if (launch_spec<WM, WN, MT, NT, MODE, KG0, KGT>(ka, halo, B, mblocks, st, rc)) return rc;
@@ -941,13 +860,10 @@ template <int WM, int WN, int MT, int NT, int MODE, int NP> static int launch_b1
   return launch_b16k<WM, WN, MT, NT, MODE, 64, NP, KGT>(ka, B, mblocks, st);
 }
 
-#ifndef DMEL_TILE5_NARROW
-#define DMEL_TILE5_NARROW 1      // tile 5 = 128 x 32 (four waves of 32 x 32): the few-column launches of pick_tile_bf16; 0: the old 64 x 128 (2,1,1,4), never chosen
-#endif
 template <int MODE, int NP> static int launch_mode_bf16(const KArgs& ka, int tile, int B, hipStream_t st) {
-  const int bm[8] = {128, 128, 64, 32, 128, DMEL_TILE5_NARROW ? 128 : 64, 128, 256};
+  const int bm[8] = {128, 128, 64, 32, 128, 128, 128, 256};
   // bf16 tiles: 0: 128x128 (2,2,2,2), 1: 128x96 (4,1,1,3), 2: 64x128 (2,2,1,2), 3: 32x256 (1,4,1,2), 4: 128x128 (4,1,1,4),
-  // 5: 128x32 (4,1,1,1) [64x128 (2,1,1,4) with DMEL_TILE5_NARROW=0], 6: 128x64 (4,1,1,2), 7: 256x96 (8,1,1,3: eight waves)
+  // 5: 128x32 (4,1,1,1), 6: 128x64 (4,1,1,2), 7: 256x96 (8,1,1,3: eight waves)
   const int mblocks = (ka.mtiles * 32 + bm[tile] - 1) / bm[tile];
   switch (tile) {
     case 0: return launch_b16<2, 2, 2, 2, MODE, NP>(ka, B, mblocks, st);
@@ -957,11 +873,7 @@ template <int MODE, int NP> static int launch_mode_bf16(const KArgs& ka, int til
     case 4: return launch_b16<4, 1, 1, 4, MODE, NP>(ka, B, mblocks, st);
     case 6: return launch_b16<4, 1, 1, 2, MODE, NP>(ka, B, mblocks, st);
     case 7: return launch_b16<8, 1, 1, 3, MODE, NP>(ka, B, mblocks, st);
-#if DMEL_TILE5_NARROW
     default: return launch_b16<4, 1, 1, 1, MODE, NP>(ka, B, mblocks, st);      // 128 x 32 (four waves of 32 x 32)
-#else
-    default: return launch_b16<2, 1, 1, 4, MODE, NP>(ka, B, mblocks, st);
-#endif
   }
 }
 
@@ -988,15 +900,14 @@ static int pick_tile_bf16(int mtiles, int64_t T, int np, int steps, int B) {
   // still equals the whole-sequence decode (tests).  Measured (tools/bench_stream.py, batch 1, pipelined): 64-token chunks 480 -> 589
   // audio-s/s, 128-token 877 -> 1025 (profiles/r03_stream.txt).
   if (np == 2 && mtiles >= 4) {
-    static const int bm[8] = {128, 128, 64, 32, 128, DMEL_TILE5_NARROW ? 128 : 64, 128, 256};
-    static const int bn[8] = {128, 96, 128, 256, 128, DMEL_TILE5_NARROW ? 32 : 128, 64, 96};
+    static const int bm[8] = {128, 128, 64, 32, 128, 128, 128, 256};
+    static const int bn[8] = {128, 96, 128, 256, 128, 32, 64, 96};
     auto wgs = [&](int tt) { return (int64_t)((mtiles * 32 + bm[tt] - 1) / bm[tt]) * ((T + bn[tt] - 1) / bn[tt]) * B; };
-    static const bool off = [] { const char* f = getenv("DMEL_CONV_SMALLN"); return f && f[0] == '0'; }();
-    if (!off && wgs(t) < 128) {
+    if (wgs(t) < 128) {
       t = 6;
       // ... and the 128 x 32 tile where even that leaves most CUs idle (a 64-token chunk: 44 -> 88 workgroups; forced on every launch it
       // measured 580 -> 634 audio-s/s at 64-token chunks, 299 -> 332 at 32)
-      if (DMEL_TILE5_NARROW && wgs(6) < 128) t = 5;
+      if (wgs(6) < 128) t = 5;
     }
   }
   return t;
@@ -1012,11 +923,11 @@ template <int MODE> static int launch_presplit(const KArgs& ka, int B, int64_t T
   if (wide) {
     const int mblocks = (ka.mtiles * 32 + 255) / 256;
     if (halo == 0) return launch_b16k<8, 1, 1, 3, MODE, 0, 2, 4, 1>(ka, B, mblocks, st);
-    return launch_b16k<8, 1, 1, 3, MODE, 16, 2, DMEL_KG2, 1>(ka, B, mblocks, st);
+    return launch_b16k<8, 1, 1, 3, MODE, 16, 2, kKG2, 1>(ka, B, mblocks, st);
   }
   const int mblocks = (ka.mtiles * 32 + 127) / 128;
   if (halo == 0) return launch_b16k<4, 1, 1, 3, MODE, 0, 2, 4, 1>(ka, B, mblocks, st);
-  return launch_b16k<4, 1, 1, 3, MODE, 16, 2, DMEL_KG2, 1>(ka, B, mblocks, st);
+  return launch_b16k<4, 1, 1, 3, MODE, 16, 2, kKG2, 1>(ka, B, mblocks, st);
 }
 
 template <int NP> static int launch_bf16_any(const KArgs& ka, EpiMode mode, int B, int64_t Tcols, hipStream_t st) {
@@ -1043,30 +954,17 @@ static const TileCfg kTiles[] = {
     {1, 4, 1, 2, 0.90f},  //  32 x 256
     {1, 4, 1, 1, 0.80f},  //  32 x 128
     {1, 3, 1, 1, 0.80f},  //  32 x  96, 3 waves
-    // register-direct variants (conv_direct_kernel), ids 7..: not picked automatically yet
-    {1, 4, 1, 1, 0.00f},  //  7: 32 x 128, 4 waves
-    {1, 3, 1, 1, 0.00f},  //  8: 32 x  96, 3 waves
-    {1, 4, 1, 2, 0.00f},  //  9: 32 x 256
-    {2, 2, 1, 2, 0.00f},  // 10: 64 x 128
-    {4, 1, 1, 3, 0.00f},  // 11: 128 x 96
-    {2, 2, 2, 2, 0.00f},  // 12: 128 x 128
-    {2, 2, 1, 1, 0.00f},  // 13: 64 x 64
 };
 constexpr int kNumTiles = sizeof(kTiles) / sizeof(kTiles[0]);
+constexpr int kTileDirect = kNumTiles;   // the register-direct kernel (conv_direct_kernel) at 32 x 96, 3 waves: chosen by rule, not by cost
 
 static int pick_tile(int mtiles, int64_t T, int B) {
-  static int forced = [] {
-    const char* e = getenv("DMEL_CONV_TILE");
-    return e ? atoi(e) : -1;
-  }();
-  if (forced >= 0 && forced < kNumTiles) return forced;
   // One column tile per batch item (1 s clips through the WaveNets, conv_pre): too few workgroups for x-tile sharing
-  // through LDS to pay; the register-direct kernel measured 1.06-1.4x faster there (tools/ab_tiles.sh).
-  if (T <= 96 && mtiles >= 4) return 8;
+  // through LDS to pay; the register-direct kernel measured 1.06-1.4x faster there.
+  if (T <= 96 && mtiles >= 4) return kTileDirect;
   int best = 0;
   double best_cost = 1e300;
   for (int i = 0; i < kNumTiles; ++i) {
-    if (kTiles[i].eff <= 0.f) continue;
     const int bm = kTiles[i].wm * kTiles[i].mt * 32, bn = kTiles[i].wn * kTiles[i].nt * 32;
     const double wgs = (double)((mtiles * 32 + bm - 1) / bm) * (double)((T + bn - 1) / bn) * B;
     const double rounds = std::ceil(wgs / 256.0);
@@ -1078,6 +976,7 @@ static int pick_tile(int mtiles, int64_t T, int B) {
 }
 
 template <int MODE> static int launch_mode(const KArgs& ka, int tile, int B, hipStream_t st) {
+  if (tile == kTileDirect) return launch_d<1, 3, 1, 1, MODE>(ka, B, ka.mtiles, st);
   const TileCfg& t = kTiles[tile];
   const int mblocks = (ka.mtiles * 32 + t.wm * t.mt * 32 - 1) / (t.wm * t.mt * 32);
   switch (tile) {
@@ -1087,14 +986,7 @@ template <int MODE> static int launch_mode(const KArgs& ka, int tile, int B, hip
     case 3: return launch_t<2, 1, 1, 3, MODE>(ka, B, mblocks, st);
     case 4: return launch_t<1, 4, 1, 2, MODE>(ka, B, mblocks, st);
     case 5: return launch_t<1, 4, 1, 1, MODE>(ka, B, mblocks, st);
-    case 6: return launch_t<1, 3, 1, 1, MODE>(ka, B, mblocks, st);
-    case 7: return launch_d<1, 4, 1, 1, MODE>(ka, B, mblocks, st);
-    case 8: return launch_d<1, 3, 1, 1, MODE>(ka, B, mblocks, st);
-    case 9: return launch_d<1, 4, 1, 2, MODE>(ka, B, mblocks, st);
-    case 10: return launch_d<2, 2, 1, 2, MODE>(ka, B, mblocks, st);
-    case 11: return launch_d<4, 1, 1, 3, MODE>(ka, B, mblocks, st);
-    case 12: return launch_d<2, 2, 2, 2, MODE>(ka, B, mblocks, st);
-    default: return launch_d<2, 2, 1, 1, MODE>(ka, B, mblocks, st);
+    default: return launch_t<1, 3, 1, 1, MODE>(ka, B, mblocks, st);
   }
 }
 
@@ -1163,6 +1055,11 @@ static int check_f16_range(const PackedConv& pc, const ConvRun& r, hipStream_t s
   return DMEL_OK;
 }
 
+bool conv_fp32_mfma_forced() {
+  static const bool on = [] { const char* e = getenv("DMEL_CONV_FP32_MFMA"); return e && atoi(e) != 0; }();
+  return on;
+}
+
 int launch_conv(const PackedConv& pc, const ConvRun& r, hipStream_t stream) {
   {  // producer / consumer kernel for the launches it was measured to win on (conv_pc.hip); DMEL_CONV_PC=0 is the A/B switch, read per call
     const char* e = getenv("DMEL_CONV_PC");
@@ -1186,7 +1083,7 @@ int launch_conv(const PackedConv& pc, const ConvRun& r, hipStream_t stream) {
     DMEL_CHECK_ARG((r.seg[s].xp != nullptr) == (r.seg[0].xp != nullptr), "conv: either every input segment is pre-split or none is");
     // taps on a strided view (polyphase branches of a stride-2 convolution: the discriminator) are staged correctly by the bf16
     // matrix-core kernels only; the native fp32-MFMA kernels were never built for it
-    DMEL_CHECK_ARG(sd.taps == 1 || sd.tstride == 1 || (r.precision != DMEL_PRECISION_FP32_MFMA && !getenv("DMEL_CONV_FP32_MFMA")),
+    DMEL_CHECK_ARG(sd.taps == 1 || sd.tstride == 1 || (r.precision != DMEL_PRECISION_FP32_MFMA && !conv_fp32_mfma_forced()),
                    "conv: taps>1 with strided input is unsupported by the native fp32-MFMA kernel");
     o.x = r.seg[s].x; o.bstride = r.seg[s].bstride; o.cstride = r.seg[s].cstride; o.Tin = r.seg[s].Tin;
     o.in_len = r.seg[s].in_len; o.in_scale = r.seg[s].in_scale;
@@ -1230,7 +1127,7 @@ int launch_conv(const PackedConv& pc, const ConvRun& r, hipStream_t stream) {
   else if (d.mode == EPI_GATE) out_elems = (double)d.C * (double)r.Tcols;
   else out_elems = (double)d.C * (double)r.Tcols * (r.skip_first ? 3.0 : 4.0);
   double alg_bytes = 4.0 * r.B * (in_elems + out_elems);      // + the weight image read once, added below when the arithmetic is known
-  static const int native_fp32 = [] { const char* e = getenv("DMEL_CONV_FP32_MFMA"); return e ? atoi(e) : 0; }();
+  const bool native_fp32 = conv_fp32_mfma_forced();
   const bool one_piece = r.precision == DMEL_PRECISION_BF16 || train_precision_override() == DMEL_PRECISION_BF16;
   const bool native = !one_piece && (native_fp32 || r.precision == DMEL_PRECISION_FP32_MFMA);
   const double products = one_piece ? 1.0 : native ? 16.0 /* fp32 MFMA: 1/16 of the bf16 rate */ : r.precision == DMEL_PRECISION_FP32_F16X2 ? 3.0 : 6.0;

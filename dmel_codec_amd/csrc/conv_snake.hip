@@ -435,13 +435,7 @@ int launch_conv_snake(const PackedConv& pc, const ConvRun& r, const float* alpha
   if (alpha == nullptr) {
     // plain convolution: EIGHT consumer waves in every configuration (two per SIMD hide each other's waits; with four the lean loop
     // measured 0.55-0.75x of conv_bf16_kernel, with eight 1.10-1.19x) and four producers for the conversion
-    static const int cfg = [] { const char* e = getenv("DMEL_LEAN_CFG"); return e ? atoi(e) : 0; }();     // A/B: 1 = sixteen-wave workgroups
     if (mt >= 5) return launch_cs_h<8, 1, 3, 4, false>(ka, sa, r.B, halo, stream);
-    if (cfg == 1) {      // 8 consumers of 32 x 64 + 8 producers, <= 128 registers, four waves per SIMD
-      if (mt >= 3) return launch_cs_h<4, 2, 2, 8, false>(ka, sa, r.B, halo, stream);
-      if (mt == 2) return launch_cs_h<2, 4, 2, 8, false>(ka, sa, r.B, halo, stream);
-      return launch_cs_h<1, 8, 2, 8, false>(ka, sa, r.B, halo, stream);
-    }
     if (mt >= 3) return launch_cs_h<4, 2, 3, 4, false>(ka, sa, r.B, halo, stream);
     if (mt == 2) return launch_cs_h<2, 4, 3, 4, false>(ka, sa, r.B, halo, stream);
     return launch_cs_h<1, 8, 3, 4, false>(ka, sa, r.B, halo, stream);

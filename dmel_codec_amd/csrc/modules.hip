@@ -469,7 +469,7 @@ extern "C" int dmel_wavenet_forward(const dmel_wavenet* m, const float* x, const
   const int C = m->C, div = group_repeat > 0 ? group_repeat : 1;
   {  // DMEL_WAVENET_FUSED=0 keeps the layered path (A/B); read per call
     const char* e = getenv("DMEL_WAVENET_FUSED");
-    if (m->fused.ok && T <= 96 && m->precision == DMEL_PRECISION_FP32 && !(e && e[0] == '0') && !getenv("DMEL_CONV_FP32_MFMA"))
+    if (m->fused.ok && T <= 96 && m->precision == DMEL_PRECISION_FP32 && !(e && e[0] == '0') && !conv_fp32_mfma_forced())
       return launch_wavenet_fused(m->fused, x, y, in_lengths, out_lengths, div, N, T, st);
   }
   const FoldGeom fold = wavenet_fold(m, N, T);
@@ -491,7 +491,7 @@ extern "C" int dmel_wavenet_forward(const dmel_wavenet* m, const float* x, const
   // what these kernels wait for either.
   const char* ps_env = getenv("DMEL_WAVENET_PRESPLIT");
   const bool presplit = m->precision == DMEL_PRECISION_FP32_F16X2 && C % 8 == 0 && (m->Ccond % 8) == 0 &&
-                        (m->cycle ? 1 << std::min(m->L - 1, m->cycle - 1) : 1) <= 8 && ps_env && ps_env[0] == '1' && !getenv("DMEL_CONV_FP32_MFMA");
+                        (m->cycle ? 1 << std::min(m->L - 1, m->cycle - 1) : 1) <= 8 && ps_env && ps_env[0] == '1' && !conv_fp32_mfma_forced();
   const int64_t units = (int64_t)N * (C / 8) * T, cunits = (int64_t)N * (m->Ccond / 8) * T;
   if (presplit) {
     DMEL_TRY(launch_split_planes(xb, p.xp, units, nullptr, 1, N, C, T, st));
@@ -696,8 +696,7 @@ extern "C" int dmel_wavenet_forward_train(const dmel_wavenet* m, const float* x,
   hipStream_t st = (hipStream_t)stream;
   // the forward of a CONDITIONED WaveNet (the decoder: nothing discrete downstream) runs on the three-product fp16 split like its inference
   // forward; an unconditioned one (the encoder: its output is quantised) and every backward pass keep the six-product split
-  static const bool fwd_f16 = [] { const char* e = getenv("DMEL_TRAIN_FWD_F16X2"); return !(e && e[0] == '0'); }();
-  const int C = m->C, prec = (train_precision(m) == DMEL_PRECISION_FP32 && m->Ccond > 0 && fwd_f16) ? DMEL_PRECISION_FP32_F16X2 : train_precision(m);
+  const int C = m->C, prec = (train_precision(m) == DMEL_PRECISION_FP32 && m->Ccond > 0) ? DMEL_PRECISION_FP32_F16X2 : train_precision(m);
   const size_t n = p.n;
   if (m->has_in) {  // wavenet.py:205-207
     ConvRun r = run_1seg(x, m->Cin, T, p.U, C, T, N);
@@ -2116,8 +2115,7 @@ extern "C" int dmel_discriminator_backward(const dmel_discriminator* d, const fl
       for (int ph = 0; ph < nph; ++ph) {
         ConvRun r = run_1seg(g - (int64_t)(dh - 1) * p.P[i + 1], l.Cout, Tout, dst, l.Cin, Tin, B);
         r.accumulate = k > 0;
-        static const bool dgrad_f16 = [] { const char* e = getenv("DMEL_DGRAD_F16X2"); return !(e && e[0] == '0'); }();
-        if (g_absmax && dgrad_f16) { r.precision = DMEL_PRECISION_FP32_F16X2; r.seg[0].in_absmax = g_absmax; }
+        if (g_absmax) { r.precision = DMEL_PRECISION_FP32_F16X2; r.seg[0].in_absmax = g_absmax; }
         if (l.sw == 2) {
           r.out_tstride = 2; r.phase_base = ph; r.Tcols = Tin / 2; r.Tout = Tin;
         }
@@ -2384,8 +2382,7 @@ extern "C" int dmel_bigvgan_finalize(dmel_bigvgan* m) {
     }
   }
   if (!m->ev_fork) {
-    const char* e = getenv("DMEL_BIGVGAN_STREAMS");
-    m->multi = !(e && atoi(e) == 1) && c.num_kernels <= 3 && c.num_kernels > 1;
+    m->multi = c.num_kernels <= 3 && c.num_kernels > 1;
     DMEL_HIP(hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming));
     for (int i = 0; i < 3; ++i) DMEL_HIP(hipEventCreateWithFlags(&m->ev_chain[i], hipEventDisableTiming));
     for (int i = 0; i < 3; ++i) DMEL_HIP(hipEventCreateWithFlags(&m->ev_stag[i], hipEventDisableTiming));
@@ -2452,9 +2449,8 @@ extern "C" int dmel_bigvgan_forward(const dmel_bigvgan* m, const float* mel, flo
   hipStream_t st = (hipStream_t)stream;
   const dmel_bigvgan_config& c = m->cfg;
   // "fp32-grade, library's choice": nothing downstream of the vocoder is discrete, so its default is the three-product fp16 split
-  // (include/dmel_hip.h); DMEL_VOCODER_F16X2=0 is the A/B switch back to the six-product bf16 split
-  const char* f16_env = getenv("DMEL_VOCODER_F16X2");
-  const int prec = m->precision == DMEL_PRECISION_FP32 && !(f16_env && f16_env[0] == '0') ? DMEL_PRECISION_FP32_F16X2 : m->precision;
+  // (include/dmel_hip.h); DMEL_PRECISION_FP32_BF16X3 asks for the six-product bf16 split
+  const int prec = m->precision == DMEL_PRECISION_FP32 ? DMEL_PRECISION_FP32_F16X2 : m->precision;
   const int logscale = c.snake_logscale;
   float *x = bufs[0], *xu = bufs[1], *xs = bufs[2];
   float* ua = bufs[4];   // block 0's activation scratch doubles as the post-activation buffer
@@ -2483,7 +2479,6 @@ extern "C" int dmel_bigvgan_forward(const dmel_bigvgan* m, const float* mel, flo
       hipStream_t sj = (multi && j > 0) ? m->side[j - 1] : st;
       float *xj = bufs[3 + 3 * j], *uj = bufs[4 + 3 * j], *vj = bufs[5 + 3 * j];
       const float* xin = xu;
-      static const int stagger = [] { const char* e = getenv("DMEL_BIGVGAN_STAGGER"); return e ? atoi(e) : 1; }();
       // DMEL_FUSE_SNAKE=1: every act -> conv pair as ONE kernel (conv_snake.hip: producer waves compute the activation, consumer waves run
       // the MFMA loop).  Bit-identical to the two-kernel form and measured SLOWER on every vocoder shape (0.54-1.03x,
       // profiles/r03_fused_vs_two_kernels.txt; DESIGN.md section 4 has the probes that explain it), so the two-kernel form stays the
@@ -2493,14 +2488,14 @@ extern "C" int dmel_bigvgan_forward(const dmel_bigvgan* m, const float* mel, flo
       for (int l = 0; l < 3; ++l) {
         // stagger the branches by one kernel: started together they run snake|snake|snake then conv|conv|conv in lockstep
         // and the VALU-bound activations never meet the matrix-pipe-bound convolutions on a CU
-        if (l == 0 && multi && stagger && j > 0) DMEL_HIP(hipStreamWaitEvent(sj, m->ev_stag[j - 1], 0));
+        if (l == 0 && multi && j > 0) DMEL_HIP(hipStreamWaitEvent(sj, m->ev_stag[j - 1], 0));
         if (c.resblock_type == 2) {   // AMPBlock2.forward (bigvgan.py:232-237): xt = a(x); xt = c(xt); x = xt + x
           ConvRun r2 = run_1seg(uj, ch, Tc, l < 2 ? xj : xs, ch, Tc, B);
           r2.res = xin; r2.res_bs = bs; r2.res_cs = Tc;
           r2.precision = prec;
           const bool fuse2 = fuse && conv_snake_eligible(ab.c1[l], r2);
           if (!fuse2) DMEL_TRY(launch_aa_snake(xin, uj, ab.act[l].alpha.as<float>(), ab.act[l].beta.as<float>(), m->taps_up, m->taps_dn, logscale, B, ch, Tc, sj));
-          if (!fuse2 && l == 0 && multi && stagger && j + 1 < c.num_kernels) DMEL_HIP(hipEventRecord(m->ev_stag[j], sj));
+          if (!fuse2 && l == 0 && multi && j + 1 < c.num_kernels) DMEL_HIP(hipEventRecord(m->ev_stag[j], sj));
           if (l == 2) {
             r2.accumulate = j > 0;
             if (j == c.num_kernels - 1) r2.out_div = (float)c.num_kernels;
@@ -2509,7 +2504,7 @@ extern "C" int dmel_bigvgan_forward(const dmel_bigvgan* m, const float* mel, flo
           if (fuse2) {
             r2.seg[0].x = xin;
             DMEL_TRY(launch_conv_snake(ab.c1[l], r2, ab.act[l].alpha.as<float>(), ab.act[l].beta.as<float>(), m->taps_up, m->taps_dn, logscale, sj));
-            if (l == 0 && multi && stagger && j + 1 < c.num_kernels) DMEL_HIP(hipEventRecord(m->ev_stag[j], sj));
+            if (l == 0 && multi && j + 1 < c.num_kernels) DMEL_HIP(hipEventRecord(m->ev_stag[j], sj));
           } else {
             DMEL_TRY(launch_conv(ab.c1[l], r2, sj));
           }
@@ -2522,10 +2517,10 @@ extern "C" int dmel_bigvgan_forward(const dmel_bigvgan* m, const float* mel, flo
         if (fuse && conv_snake_eligible(ab.c1[l], r1)) {       // act -> conv as ONE kernel: the activated tensor never exists in HBM
           r1.seg[0].x = xin;
           DMEL_TRY(launch_conv_snake(ab.c1[l], r1, ab.act[2 * l].alpha.as<float>(), ab.act[2 * l].beta.as<float>(), m->taps_up, m->taps_dn, logscale, sj));
-          if (l == 0 && multi && stagger && j + 1 < c.num_kernels) DMEL_HIP(hipEventRecord(m->ev_stag[j], sj));
+          if (l == 0 && multi && j + 1 < c.num_kernels) DMEL_HIP(hipEventRecord(m->ev_stag[j], sj));
         } else {
           DMEL_TRY(launch_aa_snake(xin, uj, ab.act[2 * l].alpha.as<float>(), ab.act[2 * l].beta.as<float>(), m->taps_up, m->taps_dn, logscale, B, ch, Tc, sj));
-          if (l == 0 && multi && stagger && j + 1 < c.num_kernels) DMEL_HIP(hipEventRecord(m->ev_stag[j], sj));
+          if (l == 0 && multi && j + 1 < c.num_kernels) DMEL_HIP(hipEventRecord(m->ev_stag[j], sj));
           DMEL_TRY(launch_conv(ab.c1[l], r1, sj));
         }
         ConvRun r2 = run_1seg(uj, ch, Tc, l < 2 ? xj : xs, ch, Tc, B);

@@ -288,6 +288,23 @@ def test_lanes_refuse_a_cpu_codec():
         CodecLanes(codec, 0)
 
 
+def test_env_switches_are_the_documented_ones():
+    """The DMEL_* names that csrc/ passes to getenv are exactly the rows of the environment-variable table of DESIGN.md, and the six files
+    that used to carry A/B variants define no compile-time -D switch: a new knob has to be written down, with the test that uses it."""
+    import glob
+    csrc = os.path.join(ROOT, "dmel_codec_amd", "csrc")
+    read = set()
+    for path in glob.glob(os.path.join(csrc, "*")):
+        read |= set(re.findall(r'getenv\(\s*"(DMEL_[A-Z0-9_]+)"', open(path).read()))
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    table = design[design.index("### Environment variables read by the library"):]
+    table = table[:table.index("\n## ")]
+    documented = set(re.findall(r"^\| `(DMEL_[A-Z0-9_]+)` \|", table, flags=re.M))
+    assert read and read == documented, (sorted(read - documented), sorted(documented - read))
+    for name in ("conv_igemm.hip", "conv_pc.hip", "conv_bwd.hip", "aa_snake.hip", "conv_snake.hip", "modules.hip"):
+        assert "#ifndef DMEL_" not in open(os.path.join(csrc, name)).read(), name
+
+
 def test_conv_matrix_reaches_every_kernel_branch():
     """tests/test_gpu_conv_matrix.py claims to cover every tile / operand split / halo class of the forward kernel and every branch of
     launch_wgrad_any and launch_bgrad (csrc/conv_bwd.hip).  Its branch predicates are a Python mirror of lines of conv_bwd.hip: those

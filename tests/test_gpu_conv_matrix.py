@@ -439,9 +439,9 @@ BGRAD_BRANCHES = ("flat1", "flat-atomic", "pieces1", "pieces-atomic")
 # the lines of conv_bwd.hip the mirror below transcribes (tests/test_cpu_abi.py fails if one of them changes)
 WGRAD_PREDICATE_SOURCE = (
     "a.ipc = a.T <= 32 ? kWgK / a.T : 1;",
-    "const bool split = a.ipc == 1 && !wgrad_native_only() && a.xstride <= 2 && a.T >= 256;",
+    "const bool split = a.ipc == 1 && a.xstride <= 2 && a.T >= 256;",
     "((a.T + kWgK - 1) / kWgK) * kWgK * 10 > a.T * 11",
-    "const bool grouped = f16 && !group_off && a.dil == 1 && a.taps % 3 == 0;",
+    "const bool grouped = split && a.dil == 1 && a.taps % 3 == 0;",
     "if (T < 256) {",
     "const int total = B * ((T + kBgPiece - 1) / kBgPiece);",
     "const int splits = std::max(1, std::min(total, 2048 / std::max(1, Cout)));",
