@@ -134,6 +134,13 @@ PROTOTYPES = {
     "dmel_conv_transpose1d_set_precision": (C.c_int, [vp, C.c_int]),
     "dmel_conv_transpose1d_forward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int64, vp]),
     "dmel_conv_post_f32": (C.c_int, [vp, vp, C.c_float, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp]),
+    "dmel_aa_snake_backward_input_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp]),
+    "dmel_bigvgan_enable_input_grad": (C.c_int, [vp, C.c_int]),
+    "dmel_bigvgan_train_workspace_bytes": (C.c_size_t, [vp, C.c_int, C.c_int64]),
+    "dmel_bigvgan_forward_train": (C.c_int, [vp, vp, vp, C.c_int, C.c_int64, vp, C.c_size_t, vp]),
+    "dmel_bigvgan_backward_input": (C.c_int, [vp, vp, vp, C.c_int, C.c_int64, vp, C.c_size_t, vp]),
+    "dmel_conv_transpose1d_backward_data": (C.c_int, [vp, vp, vp, C.c_int, C.c_int64, vp]),
+    "dmel_conv_post_backward_f32": (C.c_int, [vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp]),
     "dmel_conv_backward_data": (C.c_int, [vp, vp, vp, C.c_int, C.c_int64, vp]),
     "dmel_conv_backward_weight": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int64, vp]),
     "dmel_conv_forward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int64, vp]),

@@ -141,10 +141,16 @@ __global__ __launch_bounds__(256) void aa_snake_kernel(const float* __restrict__
 // transposed filters by scatter-adding into LDS (ds_add_f32), which handles the replicate padding at the row ends with the same
 // code as the interior.  Parameter gradients: block reduction, one atomic per workgroup.  Correctness first: this kernel has not
 // been tuned (the vocoder is frozen in the reference's training_step; it matters for vocoder fine-tuning only).
+// PARAMS = false is the frozen-vocoder form (dmel_bigvgan_backward_input): no dalpha / dbeta sums, no block reduction, no atomics to
+// HBM -- dx goes through exactly the same operations, so it is bit-identical -- and the store may add up to two tensors of dx's shape:
+// dx = (dx_act + radd) + racc.  radd is the residual branch of an AMP layer (x = xt + x); racc is the running sum over the blocks of a
+// stage and may alias dx (every element is read and written by the same thread).
+template <bool PARAMS>
 __global__ __launch_bounds__(256) void aa_snake_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy,
-                                                            float* __restrict__ dx, const float* __restrict__ alpha,
+                                                            float* dx, const float* __restrict__ alpha,
                                                             const float* __restrict__ beta, float* __restrict__ dalpha,
-                                                            float* __restrict__ dbeta, Taps12 tu, Taps12 td, int logscale, int C, int T) {
+                                                            float* __restrict__ dbeta, const float* __restrict__ radd, const float* racc,
+                                                            Taps12 tu, Taps12 td, int logscale, int C, int T) {
   __shared__ float xs[kSnakeTile + 12];
   __shared__ float dys[kSnakeTile + 12];
   __shared__ float dvs[2 * (kSnakeTile + 6)];
@@ -170,16 +176,33 @@ __global__ __launch_bounds__(256) void aa_snake_bwd_kernel(const float* __restri
   for (int i = tid; i < 2 * (len + 6); i += 256) dvs[i] = 0.f;
   for (int i = tid; i < len; i += 256) dxs[i] = 0.f;
   __syncthreads();
-  // transposed low-pass: every dy sample in reach scatters its 12 taps into the pairs this tile owns (m in [t0-3, t0+len+3))
-  for (int i = tid; i < len + 12; i += 256) {
-    const int t = t0 - 6 + i;
-    if (t < 0 || t >= T) continue;
-    const float g = dys[i];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) {
-      const int vi = min(max(2 * t + k - 5, 0), 2 * T - 1);
-      const int p = (vi >> 1) - (t0 - 3);
-      if (p >= 0 && p < len + 6) atomicAdd(&dvs[2 * p + (vi & 1)], td.f[k] * g);
+  // transposed low-pass: every dy sample in reach adds its 12 taps into the pairs this tile owns (m in [t0-3, t0+len+3)).  One tap per
+  // round: within a round every sample writes a different element, so plain adds in a FIXED order replace atomics (dx is reproducible
+  // bit for bit, and the same in both instantiations).  Taps that the replicate padding folds onto the row ends are left to one thread.
+  auto near_end = [&](int v) { return v <= 2 || v >= T - 3; };
+  for (int k = 0; k < 12; ++k) {
+    for (int i = tid; i < len + 12; i += 256) {
+      const int t = t0 - 6 + i;
+      if (t < 0 || t >= T) continue;
+      const int raw = 2 * t + k - 5;
+      if (raw < 0 || raw > 2 * T - 1) continue;
+      const int p = (raw >> 1) - (t0 - 3);
+      if (p >= 0 && p < len + 6) dvs[2 * p + (raw & 1)] += td.f[k] * dys[i];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    for (int t = 0; t < T; t = (t == 2 && T - 3 > 3) ? T - 3 : t + 1) {     // t = 0, 1, 2 and T-3, T-2, T-1, each once
+      if (!near_end(t)) break;
+      const int i = t - (t0 - 6);
+      if (i < 0 || i >= len + 12) continue;
+      for (int k = 0; k < 12; ++k) {
+        const int raw = 2 * t + k - 5;
+        if (raw >= 0 && raw <= 2 * T - 1) continue;
+        const int vi = raw < 0 ? 0 : 2 * T - 1;
+        const int p = (vi >> 1) - (t0 - 3);
+        if (p >= 0 && p < len + 6) dvs[2 * p + (vi & 1)] += td.f[k] * dys[i];
+      }
     }
   }
   __syncthreads();
@@ -197,16 +220,52 @@ __global__ __launch_bounds__(256) void aa_snake_bwd_kernel(const float* __restri
     const float dve = dvs[2 * p], dvo = dvs[2 * p + 1];
     const float s2e = sinf(2.f * a * ue), s2o = sinf(2.f * a * uo);
     const float due = dve * fmaf(a * inv_b, s2e, 1.f), duo = dvo * fmaf(a * inv_b, s2o, 1.f);
-    if (m >= t0 && m < t0 + len) {                // parameter gradients: every pair is counted by exactly one tile
+    if (PARAMS && m >= t0 && m < t0 + len) {      // parameter gradients: every pair is counted by exactly one tile
       sa += inv_b * (dve * ue * s2e + dvo * uo * s2o);
       sb += dve * sin_sq(a * ue) + dvo * sin_sq(a * uo);
     }
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      const int se = min(max(m + 2 - j, 0), T - 1) - t0, so = min(max(m + 3 - j, 0), T - 1) - t0;
-      if (se >= 0 && se < len) atomicAdd(&dxs[se], tu.f[2 * j + 1] * due);
-      if (so >= 0 && so < len) atomicAdd(&dxs[so], tu.f[2 * j] * duo);
+    dvs[2 * p] = due;                             // the pair is this thread's: du replaces dv in place
+    dvs[2 * p + 1] = duo;
+  }
+  __syncthreads();
+  // transposed up-sampler, the same way: one (tap, parity) per round, the folded ends by one thread
+  for (int r = 0; r < 12; ++r) {
+    const int j = r >> 1, odd = r & 1;
+    const float coef = odd ? tu.f[2 * j] : tu.f[2 * j + 1];
+    for (int p = tid; p < len + 6; p += 256) {
+      const int m = t0 - 3 + p;
+      if (m < 0 || m > T - 1) continue;
+      const int sraw = m + 2 + odd - j;
+      if (sraw < 0 || sraw > T - 1) continue;
+      const int sl = sraw - t0;
+      if (sl >= 0 && sl < len) dxs[sl] += coef * dvs[2 * p + odd];
     }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    for (int m = 0; m < T; m = (m == 2 && T - 3 > 3) ? T - 3 : m + 1) {
+      if (!near_end(m)) break;
+      const int p = m - (t0 - 3);
+      if (p < 0 || p >= len + 6) continue;
+      for (int r = 0; r < 12; ++r) {
+        const int j = r >> 1, odd = r & 1;
+        const int sraw = m + 2 + odd - j;
+        if (sraw >= 0 && sraw <= T - 1) continue;
+        const int sl = (sraw < 0 ? 0 : T - 1) - t0;
+        if (sl >= 0 && sl < len) dxs[sl] += (odd ? tu.f[2 * j] : tu.f[2 * j + 1]) * dvs[2 * p + odd];
+      }
+    }
+  }
+  if (!PARAMS) {
+    __syncthreads();
+    const int64_t row = ((int64_t)b * C + c) * T + t0;
+    for (int i = tid; i < len; i += 256) {
+      float v = dxs[i];
+      if (radd) v += radd[row + i];
+      if (racc) v += racc[row + i];
+      dxr[t0 + i] = v;
+    }
+    return;
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -241,7 +300,25 @@ int launch_aa_snake_bwd(const float* x, const float* dy, float* dx, const float*
   dim3 grid((unsigned)((T + kSnakeTile - 1) / kSnakeTile), (unsigned)C, (unsigned)B);
   {
     ProfScope ps("aa_snake_bwd", s, 0.0, 12.0 * (double)B * C * (double)T);
-    hipLaunchKernelGGL(aa_snake_bwd_kernel, grid, dim3(256), 0, s, x, dy, dx, alpha, beta, dalpha, dbeta, tu, td, logscale, C, (int)T);
+    hipLaunchKernelGGL(aa_snake_bwd_kernel<true>, grid, dim3(256), 0, s, x, dy, dx, alpha, beta, dalpha, dbeta, (const float*)nullptr,
+                       (const float*)nullptr, tu, td, logscale, C, (int)T);
+  }
+  DMEL_HIP(hipGetLastError());
+  return DMEL_OK;
+}
+
+int launch_aa_snake_bwd_input(const float* x, const float* dy, float* dx, const float* radd, const float* racc, const float* alpha,
+                              const float* beta, const float* up_taps_host, const float* down_taps_host, int logscale, int B, int C,
+                              int64_t T, hipStream_t s) {
+  DMEL_CHECK_ARG(x && dy && dx && alpha && up_taps_host && down_taps_host, "aa_snake_backward_input: NULL argument");
+  DMEL_CHECK_ARG(B > 0 && C > 0 && T > 0 && B <= 65535 && C <= 65535 && T < ((int64_t)1 << 29), "aa_snake_backward_input: bad shape");
+  Taps12 tu, td;
+  for (int i = 0; i < 12; ++i) { tu.f[i] = 2.f * up_taps_host[i]; td.f[i] = down_taps_host[i]; }
+  dim3 grid((unsigned)((T + kSnakeTile - 1) / kSnakeTile), (unsigned)C, (unsigned)B);
+  {
+    ProfScope ps("aa_snake_bwd", s, 0.0, (12.0 + (radd ? 4.0 : 0.0) + (racc ? 4.0 : 0.0)) * (double)B * C * (double)T);
+    hipLaunchKernelGGL(aa_snake_bwd_kernel<false>, grid, dim3(256), 0, s, x, dy, dx, alpha, beta, (float*)nullptr, (float*)nullptr, radd,
+                       racc, tu, td, logscale, C, (int)T);
   }
   DMEL_HIP(hipGetLastError());
   return DMEL_OK;
@@ -273,6 +350,13 @@ extern "C" int dmel_aa_snake_backward_f32(const float* x, const float* dy, float
                                           int logscale, int B, int C, int64_t T, void* stream) {
   return dmel::launch_aa_snake_bwd(x, dy, dx, alpha, beta, dalpha, dbeta, up_filter12_host, down_filter12_host, logscale, B, C, T,
                                    (hipStream_t)stream);
+}
+
+extern "C" int dmel_aa_snake_backward_input_f32(const float* x, const float* dy, const float* add /*nullable*/, float* dx, const float* alpha,
+                                                const float* beta, const float* up_filter12_host, const float* down_filter12_host,
+                                                int logscale, int B, int C, int64_t T, void* stream) {
+  return dmel::launch_aa_snake_bwd_input(x, dy, dx, add, nullptr, alpha, beta, up_filter12_host, down_filter12_host, logscale, B, C, T,
+                                         (hipStream_t)stream);
 }
 
 extern "C" int dmel_aa_snake_f32(const float* x, float* y, const float* alpha, const float* beta, const float* up_filter12_host,

@@ -2140,11 +2140,13 @@ struct AmpBlock {             // AMPBlock1, bigvgan.py:31-147
   int k;
   int dil[3];
   PackedConv c1[3], c2[3];
+  PackedConv c1T[3], c2T[3];  // backward-data images (transposed, tap-reversed), packed by dmel_bigvgan_enable_input_grad
   SnakeP act[6];
 };
 struct UpStage {
   int u, k, Cin, Cout;
   PackedConv lo, hi;          // phases [0,u/2) with taps d={-1,0}; phases [u/2,u) with taps d={0,+1}
+  std::vector<PackedConv> dgrad;   // backward-data: u/2 images of two strided two-tap segments each (pack_up_stage_dgrad); empty until asked for
 };
 // ConvTranspose1d(Cin, Cout, k = 2u, stride u, padding u/2) as two groups of u/2 phase sub-convolutions with two taps each:
 //   y[co, u q + ph] = sum_ci sum_d W[ci, co, ph + u/2 - u d] x[ci, q + d]                    (bigvgan.py:320-334, :371-374)
@@ -2176,12 +2178,83 @@ int launch_up_stage(const UpStage& us, const float* x, float* y, int B, int64_t 
   }
   return DMEL_OK;
 }
+// Host copy of a packed fp32 weight image, and the value at (packed row m, K step, reduction row k of the step): the inverse of the
+// layout pack_conv writes (conv.h).  The backward-data images are packed from it after finalize has dropped the state dict; the fp32
+// image holds the folded weights exactly.
+struct HostImage {
+  std::vector<float> w;
+  int steps = 0;
+  int load(const PackedConv& pc) {
+    steps = pc.steps;
+    w.resize(pc.w.bytes / sizeof(float));
+    if (!w.empty()) DMEL_HIP(hipMemcpy(w.data(), pc.w.p, pc.w.bytes, hipMemcpyDeviceToHost));
+    return DMEL_OK;
+  }
+  float at(int m, int step, int k) const {
+    const int tile = m >> 5, r = m & 31, h = k & 1, kk = k >> 1, hf = kk >> 2, j = kk & 3;
+    return w[((((size_t)tile * steps + step) * 2 + hf) * 64 + 32 * h + r) * 4 + j];
+  }
+};
+// W[co][ci][tap] of a "same" convolution packed by pack_same_conv (one segment, identity row map)
+float same_conv_weight(const HostImage& im, int taps, int co, int ci, int tap) { return im.at(co, (ci / kCK) * taps + tap, ci % kCK); }
+// (Cin, Cout, k) weights of a transposed convolution back from the two forward images of pack_up_stage
+int unpack_up_stage(const UpStage& us, std::vector<float>& w) {
+  const int u = us.u, k = us.k, hu = u / 2, Co = us.Cout;
+  w.assign((size_t)us.Cin * Co * k, 0.f);
+  for (int half = 0; half < 2; ++half) {
+    const PackedConv& pc = half == 0 ? us.lo : us.hi;
+    HostImage im;
+    DMEL_TRY(im.load(pc));
+    for (int p = 0; p < hu; ++p)
+      for (int co = 0; co < Co; ++co)
+        for (int ci = 0; ci < us.Cin; ++ci)
+          for (int tap = 0; tap < 2; ++tap) {
+            const int ph = p + half * hu, dd = tap - (half == 0 ? 1 : 0), kk = ph + hu - u * dd;
+            if (kk >= 0 && kk < k) w[((size_t)ci * Co + co) * k + kk] = im.at(p * pc.RP + co, (ci / kCK) * 2 + tap, ci % kCK);
+          }
+  }
+  return DMEL_OK;
+}
+// Backward-data of the transposed convolution:  dx[ci, q] = scale * sum_co sum_kk W[ci, co, kk] dy[co, u q + kk - u/2]  (zero outside
+// dy) -- a stride-u, 2u-tap convolution of dy.  Tap kk = u m + ph (m = 0, 1; ph < u) reads dy[u (q + m) + ph - u/2]: phase ph is one
+// strided segment of the implicit-GEMM kernel (SegDesc::tstride = u, toff = ph, pad_left = u/2, two taps that step by u).  A launch
+// carries two segments, so the u phases are u/2 launches, the later ones accumulating into dx (the small tensor of the pair).
+// scale: the vocoder folds the 1 / num_kernels of the stage's block average in here.
+int pack_up_stage_dgrad(UpStage& us, const float* w, float scale) {
+  const int u = us.u, k = us.k, Co = us.Cout;
+  us.dgrad.clear();
+  us.dgrad.resize(u / 2);
+  for (int j = 0; j < u / 2; ++j) {
+    PackDesc d;
+    d.mode = EPI_LINEAR; d.nseg = 2; d.C = us.Cin; d.phases = 1;
+    for (int sg = 0; sg < 2; ++sg) {
+      d.seg[sg].Cin = Co; d.seg[sg].taps = 2; d.seg[sg].dil = 1; d.seg[sg].tstride = u; d.seg[sg].toff = 2 * j + sg; d.seg[sg].pad_left = u / 2;
+    }
+    DMEL_TRY(pack_conv(us.dgrad[j], d,
+                       [&](int sg, int row /*ci*/, int cc /*co*/, int tap) { return scale * w[((size_t)row * Co + cc) * k + u * tap + 2 * j + sg]; },
+                       [&](int) { return 0.f; }));
+  }
+  return DMEL_OK;
+}
+// dy (B, Cout, u T) -> dx (B, Cin, T); six-product split (a gradient tensor is the operand)
+int launch_up_stage_dgrad(const UpStage& us, const float* dy, float* dx, int B, int64_t T, hipStream_t st) {
+  const int64_t Tu = T * us.u;
+  for (size_t j = 0; j < us.dgrad.size(); ++j) {
+    ConvRun r = run_1seg(dy, us.Cout, Tu, dx, us.Cin, T, B);
+    r.seg[1] = r.seg[0];
+    r.accumulate = j > 0;
+    r.precision = DMEL_PRECISION_FP32;
+    DMEL_TRY(launch_conv(us.dgrad[j], r, st));
+  }
+  return DMEL_OK;
+}
 }  // namespace
 
 // ---- standalone transposed convolution / output convolution (C-ABI rows convT1d, conv_post of SURVEY section 8(b)) ---------------
 struct dmel_conv_transpose {
   UpStage us;
   int precision = 0;
+  std::vector<float> w_host;      // kept for the lazily packed backward-data images
 };
 extern "C" int dmel_conv_transpose1d_create(dmel_conv_transpose** out, const float* w_host, const float* bias_host, int Cin, int Cout, int k,
                                             int stride) {
@@ -2195,8 +2268,21 @@ extern "C" int dmel_conv_transpose1d_create(dmel_conv_transpose** out, const flo
   h->us.u = stride; h->us.k = k; h->us.Cin = Cin; h->us.Cout = Cout;
   const int rc = pack_up_stage(h->us, w_host, bias_host);
   if (rc != DMEL_OK) { delete h; return rc; }
+  h->w_host.assign(w_host, w_host + (size_t)Cin * Cout * k);
   *out = h;
   return DMEL_OK;
+}
+extern "C" int dmel_conv_transpose1d_backward_data(dmel_conv_transpose* h, const float* dy, float* dx, int B, int64_t T, void* stream) {
+  DMEL_CHECK_ARG(h && dy && dx, "conv_transpose1d_backward_data: NULL argument");
+  DMEL_CHECK_ARG(B > 0 && T > 0, "conv_transpose1d_backward_data: bad shape");
+  if (h->us.dgrad.empty()) DMEL_TRY(pack_up_stage_dgrad(h->us, h->w_host.data(), 1.f));
+  return launch_up_stage_dgrad(h->us, dy, dx, B, T, (hipStream_t)stream);
+}
+extern "C" int dmel_conv_post_backward_f32(const float* y, const float* dy, const float* w_dev, int act, float* dx, int B, int C, int K,
+                                           int64_t T, void* stream) {
+  DMEL_CHECK_ARG(dy && w_dev && dx && (y || act == 0), "conv_post_backward: NULL argument");
+  DMEL_CHECK_ARG(act == 0 || act == 2 || act == 3, "conv_post_backward: act must be 0 (none), 2 (tanh) or 3 (clamp to [-1, 1])");
+  return launch_conv_post_bwd(y, dy, dx, w_dev, act == 0 ? ACT_NONE : act == 2 ? ACT_TANH : ACT_CLAMP1, B, C, K, T, (hipStream_t)stream);
 }
 extern "C" void dmel_conv_transpose1d_destroy(dmel_conv_transpose* h) { delete h; }
 extern "C" int dmel_conv_transpose1d_set_precision(dmel_conv_transpose* h, int precision) {
@@ -2238,6 +2324,8 @@ struct dmel_bigvgan {
              ev_stag[3] = {nullptr, nullptr, nullptr};
   bool multi = false;
   int precision = 0;
+  PackedConv conv_preT;     // backward-data image of conv_pre
+  bool input_grad = false;  // the backward-data images are packed (dmel_bigvgan_enable_input_grad)
   ~dmel_bigvgan() {
     for (int i = 0; i < kSide; ++i) {
       if (side[i]) (void)hipStreamDestroy(side[i]);
@@ -2406,6 +2494,8 @@ extern "C" int dmel_bigvgan_finalize(dmel_bigvgan* m) {
   }
   m->ts.t.clear();
   m->ready = true;
+  m->input_grad = false;    // the images belong to the previous weights
+  m->conv_preT = PackedConv();
   return DMEL_OK;
 }
 
@@ -2556,4 +2646,267 @@ extern "C" int dmel_bigvgan_forward(const dmel_bigvgan* m, const float* mel, flo
   DMEL_TRY(launch_aa_snake(x, ua, m->act_post.alpha.as<float>(), m->act_post.beta.as<float>(), m->taps_up, m->taps_dn, logscale, B, ch, Tc, st));
   return launch_conv_post(ua, audio, m->post_w.as<float>(), m->post_bias, c.use_tanh_at_final ? ACT_TANH : ACT_CLAMP1, B, ch, 7,
                           Tc, st);
+}
+
+// ---- input gradient through the frozen generator (bigvgan.py:367-393 under autograd, weights frozen as in codec_lit_modules.py:68-72) ----
+extern "C" int dmel_bigvgan_enable_input_grad(dmel_bigvgan* m, int on) {
+  DMEL_CHECK_ARG(m, "bigvgan_enable_input_grad: NULL handle");
+  if (!m->ready) { set_error("bigvgan_enable_input_grad: handle not finalized"); return DMEL_EMISSING; }
+  const dmel_bigvgan_config& c = m->cfg;
+  if (!on) {
+    m->input_grad = false;
+    m->conv_preT = PackedConv();
+    for (auto& us : m->ups) us.dgrad.clear();
+    for (auto& ab : m->blocks)
+      for (int l = 0; l < 3; ++l) { ab.c1T[l] = PackedConv(); ab.c2T[l] = PackedConv(); }
+    return DMEL_OK;
+  }
+  if (m->input_grad) return DMEL_OK;
+  // dx = conv1d(dy, W transposed and tap-reversed): the image dmel_conv_backward_data packs, from the forward image's own values
+  auto pack_T = [](PackedConv& dst, const PackedConv& fwd, int Cout, int Cin, int k, int dil) -> int {
+    HostImage im;
+    DMEL_TRY(im.load(fwd));
+    PackDesc d;
+    d.mode = EPI_LINEAR; d.nseg = 1; d.C = Cin; d.phases = 1;
+    d.seg[0].Cin = Cout; d.seg[0].taps = k; d.seg[0].dil = dil; d.seg[0].pad_left = dil * (k - 1) / 2;
+    return pack_conv(dst, d, [&](int, int row /*ci*/, int cc /*co*/, int tap) { return same_conv_weight(im, k, cc, row, k - 1 - tap); },
+                     [&](int) { return 0.f; });
+  };
+  DMEL_TRY(pack_T(m->conv_preT, m->conv_pre, c.upsample_initial_channel, c.num_mels, 7, 1));
+  for (int i = 0; i < c.num_upsamples; ++i) {
+    UpStage& us = m->ups[i];
+    std::vector<float> w;
+    DMEL_TRY(unpack_up_stage(us, w));
+    DMEL_TRY(pack_up_stage_dgrad(us, w.data(), 1.f / (float)c.num_kernels));   // the block average of the stage rides on these weights
+    for (int j = 0; j < c.num_kernels; ++j) {
+      AmpBlock& ab = m->blocks[(size_t)i * c.num_kernels + j];
+      for (int l = 0; l < 3; ++l) {
+        DMEL_TRY(pack_T(ab.c1T[l], ab.c1[l], us.Cout, us.Cout, ab.k, ab.dil[l]));
+        if (c.resblock_type != 2) DMEL_TRY(pack_T(ab.c2T[l], ab.c2[l], us.Cout, us.Cout, ab.k, 1));
+      }
+    }
+  }
+  m->input_grad = true;
+  return DMEL_OK;
+}
+
+namespace {
+// Workspace of forward_train / backward_input.  Saved for the backward (untouched between the two calls): the audio, per stage the
+// up-sampled tensor and per AMP block the x of layers 1, 2 and (AMPBlock1) the three conv1 outputs -- 16 slots per stage with three
+// blocks -- and the input of activation_post (the last of the two ping-pong stage buffers).  Scratch: one activation buffer per block
+// for the forward; two gradient ping-pong buffers, the stage's input gradient and four buffers per block for the backward.
+struct BvTrainPlan {
+  float* audio;
+  float* ping[2];
+  float* ua[8];
+  struct Stage { float* xu; float* xl[8][3]; float* v[8][3]; } st[8];
+  float *G[2], *D;
+  float* blk[8][4];
+  size_t bytes;
+};
+size_t bigvgan_train_plan(const dmel_bigvgan* m, int B, int64_t T, void* ws, BvTrainPlan* p) {
+  const dmel_bigvgan_config& c = m->cfg;
+  BvTrainPlan local;
+  BvTrainPlan& q = p ? *p : local;
+  Arena a(ws, (size_t)-1);
+  size_t mx = (size_t)std::max(c.upsample_initial_channel, c.num_mels) * T;
+  int64_t Tc = T;
+  q.audio = a.take<float>((size_t)B * T * m->total_up);
+  for (int i = 0; i < c.num_upsamples; ++i) {
+    Tc *= c.upsample_rates[i];
+    const size_t n = (size_t)(c.upsample_initial_channel >> (i + 1)) * Tc;
+    mx = std::max(mx, n);
+    q.st[i].xu = a.take<float>(n * B);
+    for (int j = 0; j < c.num_kernels; ++j)
+      for (int l = 0; l < 3; ++l) {
+        q.st[i].xl[j][l] = l > 0 ? a.take<float>(n * B) : q.st[i].xu;
+        q.st[i].v[j][l] = c.resblock_type == 2 ? nullptr : a.take<float>(n * B);
+      }
+  }
+  for (int k = 0; k < 2; ++k) q.ping[k] = a.take<float>(mx * B);
+  for (int j = 0; j < c.num_kernels; ++j) q.ua[j] = a.take<float>(mx * B);
+  for (int k = 0; k < 2; ++k) q.G[k] = a.take<float>(mx * B);
+  q.D = a.take<float>(mx * B);
+  for (int j = 0; j < c.num_kernels; ++j)
+    for (int k = 0; k < 4; ++k) q.blk[j][k] = a.take<float>(mx * B);
+  q.bytes = align_up(a.off, 256);
+  return q.bytes;
+}
+}  // namespace
+
+extern "C" size_t dmel_bigvgan_train_workspace_bytes(const dmel_bigvgan* m, int B, int64_t T) {
+  if (!m || B <= 0 || T <= 0) return 0;
+  return bigvgan_train_plan(m, B, T, nullptr, nullptr);
+}
+
+// dmel_bigvgan_forward with the input of every activation kept: the same launches with the same arguments on other buffers (always the
+// two-kernel act -> conv form), so the audio is bit-identical to dmel_bigvgan_forward's.
+extern "C" int dmel_bigvgan_forward_train(const dmel_bigvgan* m, const float* mel, float* audio, int B, int64_t T, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+  DMEL_CHECK_ARG(m && mel && audio && workspace, "bigvgan_forward_train: NULL argument");
+  DMEL_CHECK_ARG(m->input_grad, "bigvgan_forward_train: dmel_bigvgan_enable_input_grad(m, 1) has not been called on this handle");
+  if (!m->ready) { set_error("bigvgan_forward_train: handle not finalized"); return DMEL_EMISSING; }
+  DMEL_CHECK_ARG(B > 0 && T > 0, "bigvgan_forward_train: bad shape");
+  BvTrainPlan p;
+  const size_t need = bigvgan_train_plan(m, B, T, workspace, &p);
+  DMEL_CHECK_ARG(workspace_bytes >= need, "bigvgan_forward_train: workspace too small (%zu < %zu)", workspace_bytes, need);
+  hipStream_t st = (hipStream_t)stream;
+  const dmel_bigvgan_config& c = m->cfg;
+  const int prec = m->precision == DMEL_PRECISION_FP32 ? DMEL_PRECISION_FP32_F16X2 : m->precision;
+  const int logscale = c.snake_logscale;
+  const bool multi = m->multi;
+  float* x = p.ping[0];
+  {  // conv_pre (bigvgan.py:369)
+    ConvRun r = run_1seg(mel, c.num_mels, T, x, c.upsample_initial_channel, T, B);
+    r.precision = prec;
+    DMEL_TRY(launch_conv(m->conv_pre, r, st));
+  }
+  int64_t Tc = T;
+  int ch = c.upsample_initial_channel;
+  for (int i = 0; i < c.num_upsamples; ++i) {
+    const UpStage& us = m->ups[i];
+    float* xu = p.st[i].xu;
+    float* xs = p.ping[(i + 1) & 1];
+    DMEL_TRY(launch_up_stage(us, x, xu, B, Tc, prec, st));
+    ch = us.Cout;
+    Tc *= us.u;
+    const int64_t bs = (int64_t)ch * Tc;
+    if (multi) {
+      DMEL_HIP(hipEventRecord(m->ev_fork, st));
+      for (int k = 0; k < dmel_bigvgan::kSide; ++k) DMEL_HIP(hipStreamWaitEvent(m->side[k], m->ev_fork, 0));
+    }
+    for (int j = 0; j < c.num_kernels; ++j) {
+      const AmpBlock& ab = m->blocks[(size_t)i * c.num_kernels + j];
+      hipStream_t sj = (multi && j > 0) ? m->side[j - 1] : st;
+      float* uj = p.ua[j];
+      for (int l = 0; l < 3; ++l) {
+        const float* xin = p.st[i].xl[j][l];
+        float* xout = l < 2 ? p.st[i].xl[j][l + 1] : xs;
+        if (l == 0 && multi && j > 0) DMEL_HIP(hipStreamWaitEvent(sj, m->ev_stag[j - 1], 0));
+        const bool two = c.resblock_type != 2;
+        const SnakeP& a1 = ab.act[two ? 2 * l : l];
+        DMEL_TRY(launch_aa_snake(xin, uj, a1.alpha.as<float>(), a1.beta.as<float>(), m->taps_up, m->taps_dn, logscale, B, ch, Tc, sj));
+        if (l == 0 && multi && j + 1 < c.num_kernels) DMEL_HIP(hipEventRecord(m->ev_stag[j], sj));
+        if (two) {
+          float* vj = p.st[i].v[j][l];
+          ConvRun r1 = run_1seg(uj, ch, Tc, vj, ch, Tc, B);
+          r1.precision = prec;
+          DMEL_TRY(launch_conv(ab.c1[l], r1, sj));
+          const SnakeP& a2 = ab.act[2 * l + 1];
+          DMEL_TRY(launch_aa_snake(vj, uj, a2.alpha.as<float>(), a2.beta.as<float>(), m->taps_up, m->taps_dn, logscale, B, ch, Tc, sj));
+        }
+        ConvRun r2 = run_1seg(uj, ch, Tc, xout, ch, Tc, B);
+        r2.res = xin; r2.res_bs = bs; r2.res_cs = Tc;
+        r2.precision = prec;
+        if (l == 2) {  // xs = ((out_0 + out_1) + out_2) / num_kernels in the reference's order, as in dmel_bigvgan_forward
+          r2.accumulate = j > 0;
+          if (j == c.num_kernels - 1) r2.out_div = (float)c.num_kernels;
+          if (multi && j > 0) DMEL_HIP(hipStreamWaitEvent(sj, m->ev_chain[j - 1], 0));
+        }
+        DMEL_TRY(launch_conv(two ? ab.c2[l] : ab.c1[l], r2, sj));
+        if (l == 2 && multi && j + 1 < c.num_kernels) DMEL_HIP(hipEventRecord(m->ev_chain[j], sj));
+      }
+    }
+    if (multi) {
+      for (int k = 0; k < dmel_bigvgan::kSide && k + 1 < c.num_kernels; ++k) {
+        DMEL_HIP(hipEventRecord(m->ev_join[k], m->side[k]));
+        DMEL_HIP(hipStreamWaitEvent(st, m->ev_join[k], 0));
+      }
+    }
+    x = xs;
+  }
+  float* ua = p.ua[0];
+  DMEL_TRY(launch_aa_snake(x, ua, m->act_post.alpha.as<float>(), m->act_post.beta.as<float>(), m->taps_up, m->taps_dn, logscale, B, ch, Tc, st));
+  DMEL_TRY(launch_conv_post(ua, audio, m->post_w.as<float>(), m->post_bias, c.use_tanh_at_final ? ACT_TANH : ACT_CLAMP1, B, ch, 7, Tc, st));
+  DMEL_HIP(hipMemcpyAsync(p.audio, audio, (size_t)B * Tc * sizeof(float), hipMemcpyDeviceToDevice, st));   // act' of conv_post needs it
+  return DMEL_OK;
+}
+
+// The forward in reverse: conv_post', activation_post', per stage the AMP blocks and the transposed conv's backward-data, conv_pre's
+// backward-data.  Inside a block the gradient is carried UNSCALED (the block is linear in it); the blocks' input gradients are summed
+// in block order by the store of each block's last activation backward (dx = (dx_act + residual) + running sum: one stream and three
+// give equal bits), and the 1 / num_kernels of the average sits in the transposed conv's backward-data weights.  No add / scale launch.
+extern "C" int dmel_bigvgan_backward_input(const dmel_bigvgan* m, const float* daudio, float* dmel, int B, int64_t T, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+  DMEL_CHECK_ARG(m && daudio && dmel && workspace, "bigvgan_backward_input: NULL argument");
+  DMEL_CHECK_ARG(m->input_grad, "bigvgan_backward_input: dmel_bigvgan_enable_input_grad(m, 1) has not been called on this handle");
+  if (!m->ready) { set_error("bigvgan_backward_input: handle not finalized"); return DMEL_EMISSING; }
+  DMEL_CHECK_ARG(B > 0 && T > 0, "bigvgan_backward_input: bad shape");
+  BvTrainPlan p;
+  const size_t need = bigvgan_train_plan(m, B, T, workspace, &p);
+  DMEL_CHECK_ARG(workspace_bytes >= need, "bigvgan_backward_input: workspace too small (%zu < %zu)", workspace_bytes, need);
+  hipStream_t st = (hipStream_t)stream;
+  const dmel_bigvgan_config& c = m->cfg;
+  const int logscale = c.snake_logscale;
+  const bool multi = m->multi;
+  const bool two = c.resblock_type != 2;
+  const int nu = c.num_upsamples;
+  int ch = c.upsample_initial_channel >> nu;
+  int64_t Tc = T * m->total_up;
+  auto snake_bwd = [&](const SnakeP& a, const float* xin, const float* dy, float* dx, const float* radd, const float* racc, int C,
+                       int64_t Tn, hipStream_t s) {
+    return launch_aa_snake_bwd_input(xin, dy, dx, radd, racc, a.alpha.as<float>(), a.beta.as<float>(), m->taps_up, m->taps_dn, logscale, B,
+                                     C, Tn, s);
+  };
+  auto dgrad = [&](const PackedConv& pc, const float* dy, float* dx, int C, int64_t Tn, hipStream_t s) {
+    ConvRun r = run_1seg(dy, C, Tn, dx, C, Tn, B);
+    r.precision = DMEL_PRECISION_FP32;      // six-product split: the operand is a gradient tensor as it is
+    return launch_conv(pc, r, s);
+  };
+  float* g = p.G[0];
+  {  // conv_post' (with the derivative of tanh | clamp from the saved audio), activation_post'
+    float* dua = p.blk[0][0];
+    DMEL_TRY(launch_conv_post_bwd(p.audio, daudio, dua, m->post_w.as<float>(), c.use_tanh_at_final ? ACT_TANH : ACT_CLAMP1, B, ch, 7, Tc, st));
+    DMEL_TRY(snake_bwd(m->act_post, p.ping[nu & 1], dua, g, nullptr, nullptr, ch, Tc, st));
+  }
+  for (int i = nu - 1; i >= 0; --i) {
+    const UpStage& us = m->ups[i];
+    ch = us.Cout;
+    if (multi) {
+      DMEL_HIP(hipEventRecord(m->ev_fork, st));
+      for (int k = 0; k < dmel_bigvgan::kSide; ++k) DMEL_HIP(hipStreamWaitEvent(m->side[k], m->ev_fork, 0));
+    }
+    for (int j = 0; j < c.num_kernels; ++j) {
+      const AmpBlock& ab = m->blocks[(size_t)i * c.num_kernels + j];
+      hipStream_t sj = (multi && j > 0) ? m->side[j - 1] : st;
+      float *t1 = p.blk[j][2], *t2 = p.blk[j][3];
+      const float* gx = g;                  // gradient of x_{l+1}; the stage's output gradient for the last layer
+      for (int l = 2; l >= 0; --l) {
+        const float* xin = p.st[i].xl[j][l];
+        float* gout = l > 0 ? p.blk[j][l - 1] : p.D;
+        // layer l: x_{l+1} = c2(a2(c1(a1(x_l)))) + x_l   (AMPBlock2: x_{l+1} = c(a(x_l)) + x_l)
+        if (two) {
+          DMEL_TRY(dgrad(ab.c2T[l], gx, t1, ch, Tc, sj));
+          DMEL_TRY(snake_bwd(ab.act[2 * l + 1], p.st[i].v[j][l], t1, t2, nullptr, nullptr, ch, Tc, sj));
+          DMEL_TRY(dgrad(ab.c1T[l], t2, t1, ch, Tc, sj));
+        } else {
+          DMEL_TRY(dgrad(ab.c1T[l], gx, t1, ch, Tc, sj));
+        }
+        const float* racc = nullptr;
+        if (l == 0 && j > 0) {              // D = ((d_0 + d_1) + d_2): block j's last store runs behind block j-1's
+          racc = p.D;
+          if (multi) DMEL_HIP(hipStreamWaitEvent(sj, m->ev_chain[j - 1], 0));
+        }
+        DMEL_TRY(snake_bwd(ab.act[two ? 2 * l : l], xin, t1, gout, gx, racc, ch, Tc, sj));
+        if (l == 0 && multi && j + 1 < c.num_kernels) DMEL_HIP(hipEventRecord(m->ev_chain[j], sj));
+        gx = gout;
+      }
+    }
+    if (multi) {
+      for (int k = 0; k < dmel_bigvgan::kSide && k + 1 < c.num_kernels; ++k) {
+        DMEL_HIP(hipEventRecord(m->ev_join[k], m->side[k]));
+        DMEL_HIP(hipStreamWaitEvent(st, m->ev_join[k], 0));
+      }
+    }
+    Tc /= us.u;
+    float* gn = g == p.G[0] ? p.G[1] : p.G[0];
+    DMEL_TRY(launch_up_stage_dgrad(us, p.D, gn, B, Tc, st));   // carries the 1 / num_kernels
+    g = gn;
+  }
+  {  // conv_pre backward-data
+    ConvRun r = run_1seg(g, c.upsample_initial_channel, T, dmel, c.num_mels, T, B);
+    r.precision = DMEL_PRECISION_FP32;
+    DMEL_TRY(launch_conv(m->conv_preT, r, st));
+  }
+  return DMEL_OK;
 }

@@ -28,6 +28,9 @@ int launch_dwconv_ln(const float* x, float* y, const float* dw_w, const float* d
 // act: 2 = tanh, 3 = clamp(-1, 1), else none (values of enum Act)
 int launch_conv_post(const float* x, float* y, const float* w_dev, float bias, int act, int B, int C, int K, int64_t T,
                      hipStream_t s);
+// dx (B, C, T) = conv_post^T(dy * act'(y)): y the saved OUTPUT of launch_conv_post (may be NULL when act is none), same act codes
+int launch_conv_post_bwd(const float* y, const float* dy, float* dx, const float* w_dev, int act, int B, int C, int K, int64_t T,
+                         hipStream_t s);
 int launch_masked_copy(const float* x, float* y, const int64_t* len, int div, int N, int C, int64_t T, hipStream_t s);
 // Folded batch of short items (see ConvRun::fold_pitch): xf (C, pitch) holds item n's T columns at [n*P, n*P + T), zeros elsewhere.
 // fold: xf[c][n*P + t] = x[n][c][t] * (t < len[n / div]) (len nullable), every other column of the `pitch`-wide rows zeroed.
@@ -52,7 +55,11 @@ int launch_wavenet_fused(const WaveNetFused& f, const float* x, float* y, const 
                          int64_t T, hipStream_t st);
 int launch_aa_snake(const float* x, float* y, const float* alpha, const float* beta, const float* up_taps_host,
                     const float* down_taps_host, int logscale, int B, int C, int64_t T, hipStream_t s);
-
+// dx of the anti-aliased Snake only (frozen parameters): bit-identical to the dx of the full backward; dx = (dx_act + radd) + racc,
+// both nullable, racc may alias dx
+int launch_aa_snake_bwd_input(const float* x, const float* dy, float* dx, const float* radd, const float* racc, const float* alpha,
+                              const float* beta, const float* up_taps_host, const float* down_taps_host, int logscale, int B, int C,
+                              int64_t T, hipStream_t s);
 
 // Anti-aliased Snake fused into the convolution that reads it (conv_snake.hip): y = conv(snake(x)) with ConvRun's LINEAR epilogue
 // (bias, residual, running sum, 1 / out_div); r.seg[0].x is the tensor BEFORE the activation.  Bit-identical to launch_aa_snake +

@@ -494,6 +494,56 @@ int launch_conv_post(const float* x, float* y, const float* w_dev, float bias, i
   return DMEL_OK;
 }
 
+// Backward-data of conv_post: dx[b,c,t] = sum_k w[c,k] g[b, t - k + K/2], g = dy * act'(y) with act' taken from the SAVED output y
+// (tanh: 1 - y^2; clamp: 1 where |y| < 1, 0 where the output was clamped; none: 1).  One workgroup owns 1024 columns of one item: g
+// (+ K-1 halo) is formed once in LDS, then every channel's row is K fmas per element and one coalesced store -- bound by the C*B*T write.
+__global__ __launch_bounds__(256) void conv_post_bwd_kernel(const float* __restrict__ y, const float* __restrict__ dy,
+                                                            float* __restrict__ dx, const float* __restrict__ w, int C, int K, int T,
+                                                            int act) {
+  extern __shared__ float wsm[];   // [C][K] weights, then kPostTile + K - 1 values of g
+  float* gs = wsm + C * K;
+  for (int i = threadIdx.x; i < C * K; i += 256) wsm[i] = w[i];
+  const int b = blockIdx.y;
+  const int t0 = blockIdx.x * kPostTile;
+  const int pad = (K - 1) / 2;
+  for (int i = threadIdx.x; i < kPostTile + K - 1; i += 256) {
+    const int s = t0 - pad + i;
+    float g = 0.f;
+    if (s >= 0 && s < T) {
+      const float yv = y ? y[(int64_t)b * T + s] : 0.f;
+      const float d = act == 2 ? 1.f - yv * yv : (act == 3 ? (fabsf(yv) < 1.f ? 1.f : 0.f) : 1.f);
+      g = dy[(int64_t)b * T + s] * d;
+    }
+    gs[i] = g;
+  }
+  __syncthreads();
+  float* xb = dx + (int64_t)b * C * T;
+  for (int c = 0; c < C; ++c) {
+    const float* wc = wsm + c * K;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int lt = threadIdx.x + 256 * e;
+      float acc = 0.f;
+      for (int k = 0; k < K; ++k) acc = fmaf(wc[k], gs[lt + K - 1 - k], acc);      // g[t - k + pad] sits at gs[(t - t0) + 2 pad - k]
+      if (t0 + lt < T) xb[(int64_t)c * T + t0 + lt] = acc;
+    }
+  }
+}
+
+int launch_conv_post_bwd(const float* y, const float* dy, float* dx, const float* w_dev, int act, int B, int C, int K, int64_t T,
+                         hipStream_t s) {
+  DMEL_CHECK_ARG(B > 0 && B <= 65535 && C > 0 && K > 0 && (K % 2) == 1 && T > 0 && T < ((int64_t)1 << 30), "conv_post_backward: bad shape");
+  const size_t lds = ((size_t)C * K + kPostTile + K - 1) * sizeof(float);
+  DMEL_CHECK_ARG(lds <= 48 * 1024, "conv_post_backward: weight table too large");
+  dim3 grid((unsigned)((T + kPostTile - 1) / kPostTile), (unsigned)B);
+  {
+    ProfScope ps("small", s, 0.0, 4.0 * B * (double)T * (C + 2));
+    hipLaunchKernelGGL(conv_post_bwd_kernel, grid, dim3(256), lds, s, y, dy, dx, w_dev, C, K, (int)T, act);
+  }
+  DMEL_HIP(hipGetLastError());
+  return DMEL_OK;
+}
+
 // ---- z = z * mask + (w * value + bias)      codec_lit_modules.py:520-526 --------------------------
 __global__ __launch_bounds__(256) void mask_add_quality_kernel(float* __restrict__ z, const int64_t* __restrict__ len,
                                                                const float* __restrict__ w, const float* __restrict__ bias,

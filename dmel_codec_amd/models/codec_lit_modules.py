@@ -30,7 +30,7 @@ class VQGAN(nn.Module):
                  decoder: WaveNet | None = None, weight_adv: float = 1.0, weight_vq: float = 1.0,
                  weight_mel: float = 1.0, sampling_rate: int = 44100, freeze_encoder: bool = False,
                  dmel_groups: int = 0, quanlity_linear: int = 768, dtype: torch.dtype | str = "bfloat16",
-                 accumulate_grad: int = 1, load_vocoder_ckpt: bool = True):
+                 accumulate_grad: int = 1, load_vocoder_ckpt: bool = True, weight_mrstft: float = 0.0):
         super().__init__()
         # codec_lit_modules.py:52-56.  The native path computes in fp32 (the reference's codec-training dtype,
         # dMel_example.yaml:47); a bf16 request (LM configs) is honoured at the API boundary only.
@@ -66,6 +66,22 @@ class VQGAN(nn.Module):
         self.accumulate_grad = accumulate_grad
         if dmel_groups <= 0:
             raise NotImplementedError("only the dMel layout (dmel_groups > 0) works in the reference (SURVEY.md App. C)")
+        # Extension (absent from the reference): a multi-resolution STFT loss on the waveform the frozen vocoder makes of gen_mel, added
+        # to the generator step with this weight.  0 (default): training_step is the reference's, no vocoder call.
+        self.weight_mrstft = float(weight_mrstft)
+        self.mrstft = None
+        if self.weight_mrstft > 0:
+            tr = self.gt_mel_transform or self.encode_mel_transform
+            if self.vocoder is None:
+                raise ValueError("weight_mrstft > 0 needs a vocoder")
+            up = 1
+            for u in self.vocoder.h.upsample_rates:
+                up *= u
+            if up != tr.hop_length or int(self.vocoder.h.get("sampling_rate", tr.sample_rate)) != int(tr.sample_rate):
+                raise ValueError(f"weight_mrstft > 0: the vocoder (x{up}, {self.vocoder.h.get('sampling_rate')} Hz) does not match the mel "
+                                 f"transform (hop {tr.hop_length}, {tr.sample_rate} Hz)")
+            from ..utils.mrstft import MultiResolutionSTFTLoss
+            self.mrstft = MultiResolutionSTFTLoss()
         self.set_decode_precision("fp32")
 
     def set_decode_precision(self, precision) -> None:
@@ -139,6 +155,16 @@ class VQGAN(nn.Module):
         high = avg_with_mask(mel_distance[:, 70:, :], mel_masks_float_conv)
         allb = avg_with_mask(mel_distance, mel_masks_float_conv)
         return (low * 0.6 + mid * 0.3 + high * 0.1) * 0.5 + allb * 0.5
+
+    def mrstft_loss(self, gen_mel, audios, audio_lengths):
+        """Extension: sc + mag of the multi-resolution STFT loss between the frozen vocoder's waveform of gen_mel and the input audio
+        (cropped to frames * hop samples, items masked at mel_lengths * hop).  The gradient reaches gen_mel through
+        BigVGAN's input gradient; the vocoder's parameters receive none."""
+        hop = (self.gt_mel_transform or self.encode_mel_transform).hop_length
+        n = gen_mel.shape[2] * hop
+        lengths = (self._lengths(audio_lengths).to(gen_mel.device) // hop) * hop
+        sc, mag = self.mrstft(self.vocoder(gen_mel), audios.float().reshape(audios.shape[0], 1, -1)[..., :n], lengths=lengths)
+        return sc + mag
 
     # Lightning's trainer owns optimizers / schedulers / logging in the reference; the mirror is a plain nn.Module, so the few hooks
     # training_step uses are provided here with the same names and the same effects.
@@ -237,7 +263,12 @@ class VQGAN(nn.Module):
         loss_mel = self.mel_loss(gen_mel, gt_mels, mel_masks_float_conv)                                         # :246-263
         fake_logits = self.discriminator(gen_mel)                                                                # :265-267
         loss_adv = avg_with_mask((fake_logits - 1) ** 2, d_mask)
-        loss = (self.weight_vq * loss_vq + self.weight_mel * loss_mel + self.weight_adv * loss_adv) / self.accumulate_grad
+        loss = self.weight_vq * loss_vq + self.weight_mel * loss_mel + self.weight_adv * loss_adv
+        if self.weight_mrstft > 0:
+            loss_mrstft = self.mrstft_loss(gen_mel, audios, audio_lengths)
+            loss = loss + self.weight_mrstft * loss_mrstft
+            self.log("train/generator/loss_mrstft", loss_mrstft, batch_size=batch_size)
+        loss = loss / self.accumulate_grad
         self.log("train/generator/loss", loss * self.accumulate_grad, batch_size=batch_size)
         self.log("train/generator/loss_vq", loss_vq, batch_size=batch_size)
         self.log("train/generator/loss_mel", loss_mel, batch_size=batch_size)

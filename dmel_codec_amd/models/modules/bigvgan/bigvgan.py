@@ -219,20 +219,78 @@ class BigVGAN(NativeModule):
         with torch.cuda.device(self._device()):
             _lib.check(_lib.lib().dmel_bigvgan_set_streams(self.native(), n_streams), "bigvgan_set_streams")
 
-    @torch.no_grad()
+    def enable_input_grad(self) -> None:
+        """Pack the backward-data images of the current native handle (dmel_bigvgan_enable_input_grad: a transposed, tap-reversed copy
+        of every convolution -- the vocoder's weight memory doubles).  Called lazily by the first forward that needs a gradient."""
+        with torch.cuda.device(self._device()):
+            h = self.native()
+            if getattr(self, "_input_grad_handle", None) != (h, self._generation):
+                _lib.check(_lib.lib().dmel_bigvgan_enable_input_grad(h, 1), "bigvgan_enable_input_grad")
+                self._input_grad_handle = (h, self._generation)
+
     def forward(self, x):
-        """mel (B, num_mels, T) -> audio (B, 1, T * prod(upsample_rates))        (bigvgan.py:367-393)"""
+        """mel (B, num_mels, T) -> audio (B, 1, T * prod(upsample_rates))        (bigvgan.py:367-393)
+
+        With grad enabled and a mel that requires grad the call is differentiable with respect to the MEL (waveform-domain losses on
+        whatever produced it): dmel_bigvgan_forward_train / dmel_bigvgan_backward_input, same audio bits as the inference path.  The
+        vocoder stays frozen, as in the reference (codec_lit_modules.py:68-72): its parameters NEVER receive a gradient, whatever their
+        requires_grad says.  Every other call (no grad, a mel that does not require grad, the streaming decoder) runs the inference
+        path."""
+        if torch.is_grad_enabled() and x.requires_grad:
+            return self._forward_train(x)
+        with torch.no_grad():
+            return self._forward_infer(x)
+
+    def _check_mel(self, x):
         _lib.require_cuda(x, "mel")
         if x.ndim != 3 or x.shape[1] != self.h.num_mels:
             raise ValueError(f"expected (B, {self.h.num_mels}, T), got {tuple(x.shape)}")
-        x = x.float().contiguous()
-        B, _, T = x.shape
+
+    def _total_up(self) -> int:
         up = 1
         for u in self.h.upsample_rates:
             up *= u
+        return up
+
+    def _forward_train(self, x):
+        self._check_mel(x)
+        self.enable_input_grad()
+        return _BigVGANInputGradFn.apply(self, x.float().contiguous())
+
+    def _forward_infer(self, x):
+        self._check_mel(x)
+        x = x.float().contiguous()
+        B, _, T = x.shape
+        up = self._total_up()
         L = _lib.lib()
         with torch.cuda.device(x.device):
             h = self.native()
             ws = self._ws.get(L.dmel_bigvgan_workspace_bytes(h, B, T), x.device)
         # through PyTorch's dispatcher (dmel_codec_amd/torch_ops.py): torch.ops.dmel_hip.bigvgan_forward -> dmel_bigvgan_forward
         return torch.ops.dmel_hip.bigvgan_forward(h, x, up, ws)
+
+
+class _BigVGANInputGradFn(torch.autograd.Function):
+    """mel -> audio with d loss / d mel.  Every call owns the workspace its saved activations live in (not the module's shared one):
+    two forwards before one backward both survive."""
+
+    @staticmethod
+    def forward(ctx, module, mel):
+        B, _, T = mel.shape
+        L = _lib.lib()
+        with torch.cuda.device(mel.device):
+            h = module.native()
+            ws = torch.empty(L.dmel_bigvgan_train_workspace_bytes(h, B, T), dtype=torch.uint8, device=mel.device)
+        ctx.module, ctx.handle, ctx.ws = module, h, ws
+        ctx.generation = module._generation
+        return torch.ops.dmel_hip.bigvgan_forward_train(h, mel, module._total_up(), ws)
+
+    @staticmethod
+    def backward(ctx, daudio):
+        module = ctx.module
+        if module._handle != ctx.handle or module._generation != ctx.generation:
+            raise RuntimeError("BigVGAN: parameters changed (load_state_dict / .to()) between a differentiable forward and its backward")
+        # the backward reads the saved slots of the workspace and writes only its scratch part: a second backward through a retained
+        # graph is valid, so the workspace lives as long as the graph does
+        dmel = torch.ops.dmel_hip.bigvgan_backward_input(ctx.handle, daudio.float().contiguous(), module.h.num_mels, module._total_up(), ctx.ws)
+        return None, dmel

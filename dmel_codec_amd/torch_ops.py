@@ -9,6 +9,9 @@ is (`anti_alias_activation_cuda.forward`, alias_free_activation/cuda/anti_alias_
     torch.ops.dmel_hip.stft_magnitude(audio, n_fft, win_length, hop_length)                           # + autograd (DFT-as-GEMM backward)
     torch.ops.dmel_hip.wavenet_forward(handle, x, condition?, in_lengths?, out_lengths?, group_repeat, out_channels)
     torch.ops.dmel_hip.bigvgan_forward(handle, mel, total_upsampling)
+    torch.ops.dmel_hip.bigvgan_forward_train(handle, mel, total_upsampling, workspace)                # keeps what backward_input needs
+    torch.ops.dmel_hip.bigvgan_backward_input(handle, daudio, num_mels, total_upsampling, workspace)  # d loss / d mel, frozen weights
+    torch.ops.dmel_hip.conv_transpose1d(x, weight, bias?, stride), conv_post(x, weight, bias, activation)   # + autograd for x only
 
 Module-level ops take the native handle (an integer, owned by the mirror module) -- weights live inside the handle in MFMA tile
 order, not in tensors.  Every op has a fake (meta) implementation for shape propagation; none has a CPU implementation: the product
@@ -305,6 +308,116 @@ def _(x, weight, bias, activation):
     return x.new_empty((x.shape[0], 1, x.shape[2]), dtype=torch.float32)
 
 
+def _frozen_only(ctx, what: str, positions) -> None:
+    """The vocoder is frozen: these ops differentiate with respect to x only.  A request for a weight / bias gradient is an error,
+    not a silent None."""
+    if any(ctx.needs_input_grad[i] for i in positions):
+        raise NotImplementedError(f"{what}: only the gradient of x is built (the vocoder's weights are frozen); "
+                                  "detach weight / bias or turn off their requires_grad")
+
+
+@torch.library.custom_op("dmel_hip::conv_transpose1d_backward", mutates_args=(), device_types="cuda")
+def conv_transpose1d_backward(dy: Tensor, weight: Tensor, stride: int) -> Tensor:
+    """d loss / d x of conv_transpose1d: dy (B, Cout, T * stride) -> (B, Cin, T), a stride-`stride` convolution of dy on the
+    implicit-GEMM kernel (dmel_conv_transpose1d_backward_data)."""
+    _lib.require_cuda(dy, "dy")
+    dy = dy.float().contiguous()
+    B, Cout, Tu = dy.shape
+    if weight.ndim != 3 or weight.shape[1] != Cout or Tu % stride != 0:
+        raise ValueError(f"dy {tuple(dy.shape)} does not match weight {tuple(weight.shape)} at stride {stride}")
+    T = Tu // stride
+    dx = torch.empty(B, weight.shape[0], T, dtype=torch.float32, device=dy.device)
+    with torch.cuda.device(dy.device):
+        h = _convt_cache.get(weight, stride, None, any_other=True)       # backward-data does not read the bias: the forward's handle
+        if h is None:
+            h = _convt_handle(weight, None, stride)
+        _lib.check(_lib.lib().dmel_conv_transpose1d_backward_data(h, dy.data_ptr(), dx.data_ptr(), B, T, _lib.stream_ptr()),
+                   "conv_transpose1d_backward_data")
+    return dx
+
+
+@conv_transpose1d_backward.register_fake
+def _(dy, weight, stride):
+    return dy.new_empty((dy.shape[0], weight.shape[0], dy.shape[2] // stride), dtype=torch.float32)
+
+
+def _convt_setup(ctx, inputs, output):
+    x, weight, bias, stride = inputs
+    ctx.save_for_backward(weight)
+    ctx.stride = stride
+
+
+def _convt_backward(ctx, dy):
+    _frozen_only(ctx, "conv_transpose1d", (1, 2))
+    (weight,) = ctx.saved_tensors
+    return conv_transpose1d_backward(dy, weight, ctx.stride), None, None, None
+
+
+conv_transpose1d.register_autograd(_convt_backward, setup_context=_convt_setup)
+
+
+@torch.library.custom_op("dmel_hip::conv_post_backward", mutates_args=(), device_types="cuda")
+def conv_post_backward(y: Tensor, dy: Tensor, weight: Tensor, activation: str) -> Tensor:
+    """d loss / d x of conv_post from its saved OUTPUT y (B, 1, T) and dy: tanh' = 1 - y^2, clamp' = 1 where |y| < 1 and 0 where the
+    output was clamped (dmel_conv_post_backward_f32)."""
+    _lib.require_cuda(dy, "dy")
+    y = y.float().contiguous()
+    dy = dy.float().contiguous()
+    B, _, T = dy.shape
+    act = {"none": 0, "tanh": 2, "clamp": 3}[activation]
+    w = weight.detach().to(dy.device, torch.float32).contiguous()
+    dx = torch.empty(B, weight.shape[1], T, dtype=torch.float32, device=dy.device)
+    with torch.cuda.device(dy.device):
+        _lib.check(_lib.lib().dmel_conv_post_backward_f32(y.data_ptr(), dy.data_ptr(), w.data_ptr(), act, dx.data_ptr(), B, weight.shape[1],
+                                                          weight.shape[2], T, _lib.stream_ptr()), "conv_post_backward")
+    return dx
+
+
+@conv_post_backward.register_fake
+def _(y, dy, weight, activation):
+    return dy.new_empty((dy.shape[0], weight.shape[1], dy.shape[2]), dtype=torch.float32)
+
+
+def _conv_post_setup(ctx, inputs, output):
+    x, weight, bias, activation = inputs
+    ctx.save_for_backward(output, weight)
+    ctx.activation = activation
+
+
+def _conv_post_backward(ctx, dy):
+    _frozen_only(ctx, "conv_post", (1,))
+    y, weight = ctx.saved_tensors
+    return conv_post_backward(y, dy, weight, ctx.activation), None, None, None
+
+
+conv_post.register_autograd(_conv_post_backward, setup_context=_conv_post_setup)
+
+
+@torch.library.custom_op("dmel_hip::aa_snake_backward_input", mutates_args=(), device_types="cuda")
+def aa_snake_backward_input(x: Tensor, dy: Tensor, add: Optional[Tensor], alpha: Tensor, beta: Optional[Tensor], up_filter: Tensor,
+                            down_filter: Tensor, logscale: bool) -> Tensor:
+    """dx of aa_snake alone (frozen alpha / beta: no parameter reductions), bit-identical to aa_snake_backward's dx; `add` (x's shape,
+    optional) is added in the store: dx = dx_act + add."""
+    x = x.float().contiguous()
+    dy = dy.float().contiguous()
+    r = add.float().contiguous() if add is not None else None
+    B, Cc, T = x.shape
+    a = alpha.detach().to(x.device, torch.float32).contiguous()
+    b = beta.detach().to(x.device, torch.float32).contiguous() if beta is not None else None
+    dx = torch.empty_like(x)
+    up, dn = _host_taps(up_filter), _host_taps(down_filter)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().dmel_aa_snake_backward_input_f32(x.data_ptr(), dy.data_ptr(), _lib.ptr(r), dx.data_ptr(), a.data_ptr(),
+                                                               _lib.ptr(b), up.data_ptr(), dn.data_ptr(), int(logscale), B, Cc, T,
+                                                               _lib.stream_ptr()), "aa_snake_backward_input")
+    return dx
+
+
+@aa_snake_backward_input.register_fake
+def _(x, dy, add, alpha, beta, up_filter, down_filter, logscale):
+    return torch.empty_like(x, dtype=torch.float32)
+
+
 # ----------------------------------------------------------------------------------------------------- STFT -> log-mel
 _plans: dict = {}
 
@@ -472,3 +585,39 @@ def bigvgan_forward(handle: int, mel: Tensor, total_upsampling: int, workspace: 
 @bigvgan_forward.register_fake
 def _(handle, mel, total_upsampling, workspace):
     return mel.new_empty((mel.shape[0], 1, mel.shape[2] * total_upsampling), dtype=torch.float32)
+
+
+@torch.library.custom_op("dmel_hip::bigvgan_forward_train", mutates_args=("workspace",), device_types="cuda")
+def bigvgan_forward_train(handle: int, mel: Tensor, total_upsampling: int, workspace: Tensor) -> Tensor:
+    """dmel_bigvgan_forward_train: BigVGAN.forward with the input of every activation kept in `workspace` (at least
+    dmel_bigvgan_train_workspace_bytes(handle, B, T) bytes, owned by the caller until bigvgan_backward_input has run).  Same bits as
+    bigvgan_forward.  The handle must have been through dmel_bigvgan_enable_input_grad."""
+    B, _, T = mel.shape
+    y = torch.empty(B, 1, T * total_upsampling, dtype=torch.float32, device=mel.device)
+    with torch.cuda.device(mel.device):
+        _lib.check(_lib.lib().dmel_bigvgan_forward_train(handle, mel.data_ptr(), y.data_ptr(), B, T, workspace.data_ptr(), workspace.numel(),
+                                                         _lib.stream_ptr()), "bigvgan_forward_train")
+    return y
+
+
+@bigvgan_forward_train.register_fake
+def _(handle, mel, total_upsampling, workspace):
+    return mel.new_empty((mel.shape[0], 1, mel.shape[2] * total_upsampling), dtype=torch.float32)
+
+
+@torch.library.custom_op("dmel_hip::bigvgan_backward_input", mutates_args=("workspace",), device_types="cuda")
+def bigvgan_backward_input(handle: int, daudio: Tensor, num_mels: int, total_upsampling: int, workspace: Tensor) -> Tensor:
+    """dmel_bigvgan_backward_input: d loss / d audio (B, 1, T * up) -> d loss / d mel (B, num_mels, T), through the frozen generator,
+    from the workspace bigvgan_forward_train filled."""
+    B, _, Tf = daudio.shape
+    T = Tf // total_upsampling
+    dmel = torch.empty(B, num_mels, T, dtype=torch.float32, device=daudio.device)
+    with torch.cuda.device(daudio.device):
+        _lib.check(_lib.lib().dmel_bigvgan_backward_input(handle, daudio.data_ptr(), dmel.data_ptr(), B, T, workspace.data_ptr(),
+                                                          workspace.numel(), _lib.stream_ptr()), "bigvgan_backward_input")
+    return dmel
+
+
+@bigvgan_backward_input.register_fake
+def _(handle, daudio, num_mels, total_upsampling, workspace):
+    return daudio.new_empty((daudio.shape[0], num_mels, daudio.shape[2] // total_upsampling), dtype=torch.float32)

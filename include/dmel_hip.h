@@ -165,6 +165,13 @@ int dmel_aa_snake_backward_f32(const float* x, const float* dy, float* dx, const
                                float* dalpha, float* dbeta /*nullable*/, const float* up_filter12_host,
                                const float* down_filter12_host, int logscale, int B, int C, int64_t T, void* stream);
 
+/* dx of the same backward alone, for frozen parameters (the vocoder under a waveform loss): no dalpha / dbeta reductions, memsets or
+ * atomics; dx is BIT-IDENTICAL to dmel_aa_snake_backward_f32's.  add (B, C, T), nullable: dx = dx_act + add, the residual branch
+ * x = xt + x of an AMP layer (bigvgan/bigvgan.py:132-141) without an add kernel of its own. */
+int dmel_aa_snake_backward_input_f32(const float* x, const float* dy, const float* add /*nullable*/, float* dx, const float* alpha,
+                                     const float* beta /*nullable*/, const float* up_filter12_host, const float* down_filter12_host,
+                                     int logscale, int B, int C, int64_t T, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Module handles.  Weights are handed over as HOST fp32 arrays under the reference's state-dict key names
  * (key names are part of the contract); the library folds weight norm (weight_g / weight_v),
@@ -345,6 +352,25 @@ int dmel_bigvgan_set_precision(dmel_bigvgan* m, int precision);   /* DMEL_PRECIS
 int dmel_bigvgan_forward(const dmel_bigvgan* m, const float* mel, float* audio, int B, int64_t T,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* Input gradient through the FROZEN generator (bigvgan.py:367-393 under autograd; the reference keeps the vocoder's weights frozen,
+ * codec_lit_modules.py:68-72): d loss / d mel from d loss / d audio, for waveform-domain losses on the codec's decoder.  No parameter
+ * gradient is produced.
+ *   enable_input_grad(m, 1), AFTER finalize, packs the backward-data images (transposed, tap-reversed copies of every convolution: the
+ *     vocoder's weight memory doubles); (m, 0) frees them.  A later finalize drops them.
+ *   forward_train = dmel_bigvgan_forward with the input of every activation kept in `workspace` (per stage the up-sampled tensor and
+ *     per AMP layer its x and conv1 output: 16 tensors per stage with three AMPBlock1s) instead of recycled; always the two-kernel
+ *     act -> conv form.  Its audio is bit-identical to dmel_bigvgan_forward's, with one stream and with three.
+ *   backward_input must be given the SAME workspace, untouched, and the same B, T: daudio (B, 1, T * up) -> dmel (B, num_mels, T),
+ *     overwritten.  Convolutions run their backward-data on the six-product bf16 split; the sum over the AMP blocks of a stage is
+ *     taken in block order whatever dmel_bigvgan_set_streams says, so one stream and three give equal bits.
+ * Errors (handle not enabled, bad B / T, workspace smaller than dmel_bigvgan_train_workspace_bytes, NULL) write nothing. */
+int dmel_bigvgan_enable_input_grad(dmel_bigvgan* m, int on);
+size_t dmel_bigvgan_train_workspace_bytes(const dmel_bigvgan* m, int B, int64_t T);
+int dmel_bigvgan_forward_train(const dmel_bigvgan* m, const float* mel, float* audio, int B, int64_t T, void* workspace,
+                               size_t workspace_bytes, void* stream);
+int dmel_bigvgan_backward_input(const dmel_bigvgan* m, const float* daudio, float* dmel, int B, int64_t T, void* workspace,
+                                size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Discriminator (models/modules/discriminator.py:6-35): six weight-normed Conv2d (3 x 9 | 3 x 3, stride (1, 1|2)) + SiLU over the mel
  * image.  set_tensor keys as in the reference's state dict: blocks.{0,2,..,10}.bias, blocks.{i}.parametrizations.weight.original0|1
@@ -418,6 +444,16 @@ void dmel_conv_transpose1d_destroy(dmel_conv_transpose* h);
 int dmel_conv_transpose1d_set_precision(dmel_conv_transpose* h, int precision);   /* DMEL_PRECISION_* */
 int dmel_conv_transpose1d_forward(const dmel_conv_transpose* h, const float* x, float* y, int B, int64_t T, void* stream);
 int dmel_conv_post_f32(const float* x, const float* w_dev, float bias, int act, float* y, int B, int C, int K, int64_t T, void* stream);
+/* Backward-data of the two (what autograd runs through F.conv_transpose1d / F.conv1d + tanh | clamp in bigvgan.py:371-374, :386-391):
+ *   conv_transpose1d_backward_data: dx[b,ci,q] = sum_co sum_kk W[ci,co,kk] dy[b,co, u q + kk - u/2] (zero outside dy), dy (B, Cout, T * stride)
+ *     -> dx (B, Cin, T): a stride-u, 2u-tap convolution of dy on the implicit-GEMM kernel (u strided two-tap segments, two per launch),
+ *     six-product split.  The images are packed on the FIRST call, from a host copy of the weights the handle keeps: that call
+ *     modifies the handle and must not race with another call on it.
+ *   conv_post_backward: dx[b,c,t] = sum_k w[c,k] g[b, t - k + K/2], g = dy * act', act' from the saved OUTPUT y (B, 1, T): tanh 1 - y^2,
+ *     clamp 1 where |y| < 1 and 0 where the output was clamped, none 1 (y may then be NULL).  dx (B, C, T) is overwritten. */
+int dmel_conv_transpose1d_backward_data(dmel_conv_transpose* h, const float* dy, float* dx, int B, int64_t T, void* stream);
+int dmel_conv_post_backward_f32(const float* y, const float* dy, const float* w_dev, int act, float* dx, int B, int C, int K, int64_t T,
+                                void* stream);
 
 /* Timing hook used by bench.py: when enabled, every launch of the named kernel family on `stream` is
  * bracketed by hipEvents; dmel_prof_read returns the launch count and total milliseconds since the last reset
