@@ -1332,17 +1332,26 @@ extern "C" int dmel_quantizer_refresh(dmel_quantizer* q, int n, const char* cons
     DMEL_CHECK_ARG(keys[i] && device_tensors[i], "quantizer_refresh: NULL entry %d", i);
     dev[keys[i]] = device_tensors[i];
   }
-  bool missing = false;
-  auto T = [&](const std::string& k) -> const float* {
-    auto it = dev.find(k);
-    if (it == dev.end()) { set_error("quantizer_refresh: tensor '%s' was not provided", k.c_str()); missing = true; return nullptr; }
-    return it->second;
-  };
+  const int C = q->Cg, G = q->G, D = q->D;
+  {  // every key is resolved before the first copy or launch: a refused refresh leaves the handle as it was
+    std::vector<std::string> need;
+    for (int i = 0; i < q->nf; ++i)
+      for (const char* side : {"downsample.", "upsample."}) {
+        const std::string p = side + std::to_string(i) + ".";
+        for (const char* k : {"0.weight", "0.bias", "1.pwconv1.weight", "1.pwconv1.bias", "1.pwconv2.weight", "1.pwconv2.bias", "1.dwconv.weight",
+                              "1.dwconv.bias", "1.norm.weight", "1.norm.bias", "1.gamma"})
+          need.push_back(p + k);
+      }
+    for (int g = 0; g < G; ++g)
+      for (const char* k : {"project_in.weight", "project_in.bias", "project_out.weight", "project_out.bias"})
+        need.push_back("residual_fsq.rvqs." + std::to_string(g) + "." + k);
+    for (const auto& k : need)
+      if (!dev.count(k)) { set_error("quantizer_refresh: tensor '%s' was not provided", k.c_str()); return DMEL_EMISSING; }
+  }
+  auto T = [&](const std::string& k) -> const float* { return dev.find(k)->second; };      // present: checked above
   hipStream_t st = (hipStream_t)stream;
   RepackBatch batch(st);
-  const int C = q->Cg, G = q->G, D = q->D;
   auto copy = [&](DevBuf& dst, const float* src, size_t count) -> int {
-    if (!src) return DMEL_EMISSING;
     DMEL_HIP(hipMemcpyAsync(dst.p, src, count * sizeof(float), hipMemcpyDeviceToDevice, st));
     return DMEL_OK;
   };
@@ -1355,7 +1364,6 @@ extern "C" int dmel_quantizer_refresh(dmel_quantizer* q, int n, const char* cons
     const float *w1 = T(p + "pwconv1.weight"), *b1 = T(p + "pwconv1.bias"), *w2 = T(p + "pwconv2.weight"), *b2 = T(p + "pwconv2.bias");
     const float *dw = T(p + "dwconv.weight"), *db = T(p + "dwconv.bias"), *lw = T(p + "norm.weight"), *lb = T(p + "norm.bias");
     const float* ga = T(p + "gamma");
-    if (missing) return DMEL_EMISSING;
     DMEL_TRY(copy(cx.dw_w, dw, (size_t)C * 7)); DMEL_TRY(copy(cx.dw_b, db, C)); DMEL_TRY(copy(cx.ln_w, lw, C));
     DMEL_TRY(copy(cx.ln_b, lb, C)); DMEL_TRY(copy(cx.gamma, ga, C));
     RepackSrc a; a.seg[0] = seg(w1, C, 1); a.b0 = b1;
@@ -1373,7 +1381,6 @@ extern "C" int dmel_quantizer_refresh(dmel_quantizer* q, int n, const char* cons
   for (int i = 0; i < q->nf; ++i) {
     const std::string pd = "downsample." + std::to_string(i) + ".", pu = "upsample." + std::to_string(i) + ".";
     const float *wd = T(pd + "0.weight"), *bd = T(pd + "0.bias"), *wu = T(pu + "0.weight"), *bu = T(pu + "0.bias");
-    if (missing) return DMEL_EMISSING;
     {  // value(sg, row, ci) = wd[(row*C + ci)*2 + sg]
       RepackSrc a; a.seg[0] = seg(wd, 2 * C, 2); a.seg[1] = seg(wd + 1, 2 * C, 2); a.b0 = bd;
       DMEL_TRY(launch_repack(q->down[i], a, st));
@@ -1398,7 +1405,6 @@ extern "C" int dmel_quantizer_refresh(dmel_quantizer* q, int n, const char* cons
   for (int g = 0; g < G; ++g) {
     const std::string p = "residual_fsq.rvqs." + std::to_string(g) + ".";
     const float *a = T(p + "project_in.weight"), *ab = T(p + "project_in.bias"), *o = T(p + "project_out.weight"), *ob = T(p + "project_out.bias");
-    if (missing) return DMEL_EMISSING;
     DMEL_HIP(hipMemcpyAsync(q->w_in.as<float>() + (size_t)g * D * C, a, (size_t)D * C * sizeof(float), hipMemcpyDeviceToDevice, st));
     DMEL_HIP(hipMemcpyAsync(q->b_in.as<float>() + (size_t)g * D, ab, (size_t)D * sizeof(float), hipMemcpyDeviceToDevice, st));
     DMEL_HIP(hipMemcpyAsync(q->w_out.as<float>() + (size_t)g * C * D, o, (size_t)C * D * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -1981,6 +1987,18 @@ extern "C" int dmel_discriminator_refresh(dmel_discriminator* d, int n, const ch
     DMEL_CHECK_ARG(keys[i] && device_tensors[i], "discriminator_refresh: NULL entry %d", i);
     dev[keys[i]] = device_tensors[i];
   }
+  // every key is resolved before the first launch: a refused refresh leaves the handle as it was
+  const float *bias[kDiscLayers], *wg[kDiscLayers], *wv[kDiscLayers];
+  for (int i = 0; i < kDiscLayers; ++i) {
+    const std::string p = "blocks." + std::to_string(2 * i) + ".";
+    const std::pair<const char*, const float**> want[3] = {
+        {"bias", &bias[i]}, {"parametrizations.weight.original0", &wg[i]}, {"parametrizations.weight.original1", &wv[i]}};
+    for (const auto& kv : want) {
+      auto it = dev.find(p + kv.first);
+      if (it == dev.end()) { set_error("discriminator_refresh: tensor '%s%s' was not provided", p.c_str(), kv.first); return DMEL_EMISSING; }
+      *kv.second = it->second;
+    }
+  }
   hipStream_t st = (hipStream_t)stream;
   DevBuf& fold = *thread_scratch(2, st);
   const size_t need = (size_t)1024 * 512 * 9 * sizeof(float);
@@ -1991,13 +2009,7 @@ extern "C" int dmel_discriminator_refresh(dmel_discriminator* d, int n, const ch
   }
   for (int i = 0; i < kDiscLayers; ++i) {
     DLayer& l = d->layer[i];
-    const std::string p = "blocks." + std::to_string(2 * i) + ".";
-    auto get = [&](const std::string& k) -> const float* {
-      auto it = dev.find(k);
-      return it == dev.end() ? nullptr : it->second;
-    };
-    const float *b = get(p + "bias"), *g = get(p + "parametrizations.weight.original0"), *v = get(p + "parametrizations.weight.original1");
-    if (!b || !g || !v) { set_error("discriminator_refresh: tensors of '%s' were not provided", p.c_str()); return DMEL_EMISSING; }
+    const float *b = bias[i], *g = wg[i], *v = wv[i];
     const int64_t inner = (int64_t)l.Cin * 3 * l.kw;
     float* w = fold.as<float>();
     hipLaunchKernelGGL(weight_norm_fwd_kernel, dim3((unsigned)l.Cout), dim3(256), 0, st, v, g, w, inner);

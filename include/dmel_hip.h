@@ -213,7 +213,9 @@ int dmel_wavenet_enable_training(dmel_wavenet* m, int on);
 int dmel_wavenet_set_train_precision(dmel_wavenet* m, int precision);
 /* Re-pack every weight image of a finalized handle from DEVICE tensors (after an optimiser step): keys / device_tensors
  * name the state-dict tensors (weights (Cout, Cin, k) and biases, contiguous fp32) as they currently live on the device.
- * Runs on `stream`, no host copy, no allocation; produces bit-identical images to set_tensor + finalize on the same values. */
+ * Runs on `stream`, no host copy, no allocation; produces bit-identical images to set_tensor + finalize on the same values.
+ * All or nothing: every key is resolved before the first copy or launch, a missing one is DMEL_EMISSING (named by dmel_last_error)
+ * and leaves the handle as it was.  The same holds for the other two refresh entry points. */
 int dmel_wavenet_refresh(dmel_wavenet* m, int n, const char* const* keys, const float* const* device_tensors, void* stream);
 size_t dmel_wavenet_train_workspace_bytes(const dmel_wavenet* m, int N, int64_t T);
 int64_t dmel_wavenet_grad_floats(const dmel_wavenet* m);

@@ -1140,6 +1140,7 @@ def test_wavenet_training_forward_backward(dev, cfg):
             p.mul_(1.0)                    # version bump, same values: refresh path again
     g4 = torch.autograd.grad(m(xd.detach(), condition=cd.detach() if cd is not None else None).sum(), m.skip_projection.conv.weight)[0]
     assert rel_err(g4, g3) < 1e-6          # (wgrad uses atomics: equal to rounding, not bitwise)
+    # (both sides went through a refresh: test_gpu_repack.py holds the refreshed training images to a rebuild and to float64)
 
 
 def test_wavenet_three_adamw_steps_match_cpu_training(dev):
@@ -1346,6 +1347,7 @@ def test_quantizer_training_forward_backward(dev, levels, prebound, G, T, B):
             p.mul_(1.0)
     g2 = torch.autograd.grad(q(zd.detach()).z.sum(), q.downsample[0][0].weight)[0]
     assert rel_err(g2, g1) < 1e-6
+    # (both sides went through a refresh: test_gpu_repack.py holds the refreshed training images to a rebuild and to float64)
 
 
 def test_generator_half_of_training_step(dev):
