@@ -536,13 +536,32 @@ extern "C" int dmel_wavenet_forward(const dmel_wavenet* m, const float* x, const
 }
 
 // ---- incremental forward (include/dmel_hip.h: dmel_wavenet_stream_step) ----------------------------------------------------
+static int wavenet_stream_step_impl(const dmel_wavenet* m, const float* xraw, float* hist, float* skip, const float* cond, float* y,
+                                    float* scratch, int N, int64_t cap, const int64_t* prev, const int64_t* next,
+                                    const int64_t* out_lengths, int group_repeat, int64_t origin, bool ex, void* stream);
+
 extern "C" int dmel_wavenet_stream_step(const dmel_wavenet* m, float* hist, float* skip, const float* cond, float* y, float* scratch,
                                         int N, int64_t cap, const int64_t* prev, const int64_t* next, void* stream) {
+  return wavenet_stream_step_impl(m, nullptr, hist, skip, cond, y, scratch, N, cap, prev, next, nullptr, 1, 0, false, stream);
+}
+
+extern "C" int dmel_wavenet_stream_step_ex(const dmel_wavenet* m, const float* x, float* hist, float* skip, const float* cond, float* y,
+                                           float* scratch, int N, int64_t cap, const int64_t* prev, const int64_t* next,
+                                           const int64_t* out_lengths, int group_repeat, int64_t origin, void* stream) {
+  return wavenet_stream_step_impl(m, x, hist, skip, cond, y, scratch, N, cap, prev, next, out_lengths, group_repeat, origin, true, stream);
+}
+
+static int wavenet_stream_step_impl(const dmel_wavenet* m, const float* xraw, float* hist, float* skip, const float* cond, float* y,
+                                    float* scratch, int N, int64_t cap, const int64_t* prev, const int64_t* next,
+                                    const int64_t* out_lengths, int group_repeat, int64_t origin, bool ex, void* stream) {
   DMEL_CHECK_ARG(m && hist && skip && y && scratch && prev && next, "wavenet_stream_step: NULL argument");
   if (!m->ready) { set_error("wavenet_stream_step: handle not finalized"); return DMEL_EMISSING; }
   DMEL_CHECK_ARG((m->Ccond != 0) == (cond != nullptr), "wavenet_stream_step: condition tensor does not match the configuration");
-  if (m->has_in) { set_error("wavenet_stream_step: models with an input projection are not supported (the decoder has none)"); return DMEL_EUNSUPPORTED; }
+  if (!ex && m->has_in) { set_error("wavenet_stream_step: models with an input projection are not supported (the decoder has none)"); return DMEL_EUNSUPPORTED; }
+  DMEL_CHECK_ARG(m->has_in == (xraw != nullptr), "wavenet_stream_step: the raw input is given exactly when the model has an input projection");
   DMEL_CHECK_ARG(N > 0 && cap > 0, "wavenet_stream_step: bad shape");
+  const int div = group_repeat > 0 ? group_repeat : 1;
+  DMEL_CHECK_ARG(origin >= 0 && (!out_lengths || N % div == 0), "wavenet_stream_step: bad origin / group_repeat");
   const int C = m->C, L = m->L;
   const bool final_step = next[L] == next[0];
   for (int l = 0; l <= L; ++l) {
@@ -556,6 +575,19 @@ extern "C" int dmel_wavenet_stream_step(const dmel_wavenet* m, float* hist, floa
     }
   }
   hipStream_t st = (hipStream_t)stream;
+  if (origin > 0) {
+    // column 0 is not the start of the sequence: a window that reaches in front of it would read zero padding where history belongs
+    for (int l = 1; l <= L; ++l) {
+      const int dil = m->cycle ? 1 << ((l - 1) % m->cycle) : 1;
+      DMEL_CHECK_ARG(next[l] == prev[l] || prev[l] >= dil, "wavenet_stream_step: level %d needs history in front of the buffer (origin %lld)", l,
+                     (long long)origin);
+    }
+  }
+  if (ex) {  // DMEL_WAVENET_STREAM_FUSED=0 keeps the layered step (A/B); read per call
+    const char* e = getenv("DMEL_WAVENET_STREAM_FUSED");
+    if (m->fused.ok && L <= kStreamMaxL && m->precision == DMEL_PRECISION_FP32 && !(e && e[0] == '0') && !conv_fp32_mfma_forced())
+      return launch_wavenet_stream(m->fused, xraw, hist, skip, y, out_lengths, div, N, cap, prev, next, st);
+  }
   const int64_t bs = (int64_t)C * cap, lvl = (int64_t)N * bs;
   float* zb = scratch;                        // gate output of the block being computed, (N, C, cap)
   auto sub = [&](const float* x, int Cin, int64_t valid, int64_t p, float* out, int Cout, int64_t cols) {
@@ -565,6 +597,11 @@ extern "C" int dmel_wavenet_stream_step(const dmel_wavenet* m, float* hist, floa
     r.precision = m->precision;
     return r;
   };
+  if (m->has_in && next[0] > prev[0]) {  // wavenet.py:205-207 on the new columns of level 0
+    ConvRun r = sub(xraw, m->Cin, next[0], prev[0], hist, C, next[0] - prev[0]);
+    r.act = ACT_SILU;
+    DMEL_TRY(launch_conv(m->in_proj, r, st));
+  }
   for (int i = 0; i < L; ++i) {  // wavenet.py:116-135 on the new columns of block i + 1
     const int64_t p = prev[i + 1], cols = next[i + 1] - p;
     if (cols <= 0) continue;
@@ -589,10 +626,18 @@ extern "C" int dmel_wavenet_stream_step(const dmel_wavenet* m, float* hist, floa
       float* tb = scratch + (int64_t)N * bs;    // second half of the scratch
       ConvRun r = sub(skip, C, next[L], p, m->has_out ? tb : y, C, cols);
       r.seg[0].in_scale = (float)(1.0 / std::sqrt((double)m->L));
+      // the output mask of the whole-sequence call, in the store: the launch's columns start at p, so its lengths are taken relative to p
+      int64_t* rel = nullptr;
+      if (out_lengths) {
+        rel = reinterpret_cast<int64_t*>(scratch + 2 * (int64_t)N * bs);
+        DMEL_TRY(launch_shift_lengths(out_lengths, p, rel, N / div, st));
+      }
       if (m->has_out) r.act = ACT_SILU;
+      else { r.out_len = rel; r.len_div = div; }
       DMEL_TRY(launch_conv(m->skip_proj, r, st));
       if (m->has_out) {
         ConvRun o = sub(tb, C, next[L], p, y, m->Cout, cols);
+        o.out_len = rel; o.len_div = div;
         DMEL_TRY(launch_conv(m->out_proj, o, st));
       }
     }

@@ -53,6 +53,13 @@ struct WaveNetFused {
 };
 int launch_wavenet_fused(const WaveNetFused& f, const float* x, float* y, const int64_t* in_len, const int64_t* out_len, int len_div, int N,
                          int64_t T, hipStream_t st);
+// One-launch streaming step of the same stacks (wavenet_stream.hip): the new columns [prev[l], next[l]) of every level of the absolute-time
+// history (dmel_wavenet_stream_step_ex's buffers), cut into sub-steps of <= 96 columns per level.  out_len is relative to column 0.
+constexpr int kStreamMaxL = 32;
+int launch_wavenet_stream(const WaveNetFused& f, const float* x, float* hist, float* skip, float* y, const int64_t* out_len, int len_div,
+                          int N, int64_t cap, const int64_t* prev, const int64_t* next, hipStream_t st);
+// out[i] = max(len[i] - shift, 0): lengths relative to the first column of a sub-range launch
+int launch_shift_lengths(const int64_t* len, int64_t shift, int64_t* out, int n, hipStream_t st);
 int launch_aa_snake(const float* x, float* y, const float* alpha, const float* beta, const float* up_taps_host,
                     const float* down_taps_host, int logscale, int B, int C, int64_t T, hipStream_t s);
 // dx of the anti-aliased Snake only (frozen parameters): bit-identical to the dx of the full backward; dx = (dx_act + radd) + racc,

@@ -164,7 +164,7 @@ __attribute__((amdgpu_waves_per_eu(DMEL_STFT_WPE, DMEL_STFT_WPE)))
 __global__ __launch_bounds__(kThreads) void stft_logmel_kernel(StftTables tb, const float* __restrict__ audio,
                                                           int64_t row_stride, const int64_t* __restrict__ lengths,
                                                           float* __restrict__ out, float* __restrict__ linear, int64_t L, int64_t T,
-                                                          int hop, int pad, int n_mels, int mel_passes) {
+                                                          int hop, int pad, int n_mels, int mel_passes, int64_t s0, int64_t f0) {
   constexpr int H = 64 * P, N = 128 * P, U = (P + 7) / 8, EX = P * 72, NR = P / 2 + 1;
   extern __shared__ __attribute__((aligned(16))) float smem_stft[];
 #ifndef DMEL_STFT_LDS_PAD
@@ -224,17 +224,19 @@ __global__ __launch_bounds__(kThreads) void stft_logmel_kernel(StftTables tb, co
     if (t >= T) break;                 // wave-uniform: the rest of this wave's frames are past the clip
     cf r[P];
     // ---- load + reflect pad + window; lane = n2, reg j = n1, point n = 64 j + lane
-    const int fstart = (int)t * hop - pad;                       // host checks L < 2^30: 32-bit sample offsets
-    const bool interior = (fstart >= 0) && (fstart + N <= (int)L);
-    const float* xf = x + fstart + 2 * lane;
+    // Window launches (dmel_stft_window_f32): the T frames of the launch are the absolute frames f0 .. f0 + T - 1 of a signal of L samples
+    // whose sample s0 sits in x[0]; reflection happens at the signal's own ends only.  Whole-clip launches have s0 = f0 = 0.
+    const int64_t fstart = (f0 + t) * hop - pad;                 // absolute sample; the host checks that every sample read is in the buffer
+    const bool interior = (fstart >= 0) && (fstart + N <= L);
+    const float* xf = x + (fstart - s0) + 2 * lane;
 #pragma unroll
     for (int j = 0; j < P; ++j) {
       const cf w = kRegTables ? wz[kRegTables ? j : 0] : tb.winz[64 * j + lane];
       if (interior) {
         r[j] = {xf[128 * j] * w.x, xf[128 * j + 1] * w.y};
       } else {
-        const int64_t s0 = reflect_index(fstart + 2 * lane + 128 * j, L), s1 = reflect_index(fstart + 2 * lane + 128 * j + 1, L);
-        r[j] = {x[s0] * w.x, x[s1] * w.y};
+        const int64_t r0 = reflect_index(fstart + 2 * lane + 128 * j, L), r1 = reflect_index(fstart + 2 * lane + 128 * j + 1, L);
+        r[j] = {x[r0 - s0] * w.x, x[r1 - s0] * w.y};
       }
     }
     // ---- pass 1: DFT over n1, twiddle W_H^(k1 n2)
@@ -335,12 +337,12 @@ __global__ __launch_bounds__(kThreads) void stft_logmel_kernel(StftTables tb, co
   }
   __syncthreads();
   if (!out) return;
-  const int64_t n_valid = lengths ? lengths[b] / hop : T;
+  const int64_t n_valid = lengths ? lengths[b] / hop : f0 + T;      // in absolute frames
   float* o = out + (int64_t)b * n_mels * T;
   for (int idx = tid; idx < n_mels * kFramesPerWG; idx += kThreads) {
     const int m = idx / kFramesPerWG, f = idx % kFramesPerWG;
     const int64_t t = t0 + f;
-    if (t < T) o[(int64_t)m * T + t] = (t < n_valid) ? tile[m][f] : 0.f;
+    if (t < T) o[(int64_t)m * T + t] = (f0 + t < n_valid) ? tile[m][f] : 0.f;
   }
 }
 
@@ -565,6 +567,34 @@ extern "C" int dmel_stft_logmel_f32(const dmel_stft_plan* p, const float* audio,
   return dmel_stft_f32(p, audio, row_stride, lengths, out, nullptr, B, L, stream);
 }
 
+// one launch over `T` frames starting at absolute frame f0 of a signal of L samples, x[0] = absolute sample s0
+static int stft_launch(const dmel_stft_plan* p, const float* audio, int64_t row_stride, const int64_t* lengths, float* out, float* linear,
+                       int B, int64_t L, int64_t T, int64_t s0, int64_t f0, int64_t samples, void* stream) {
+  StftTables tb{p->winz.as<cf>(), p->tw1.as<cf>(), p->tw2.as<cf>(), p->twr.as<cf>(), p->mel_start.as<int>(),
+                p->mel_cnt.as<int>(), p->mel_ptr.as<int>(), p->mel_w.as<float>(), p->ch_k0.as<int>(), p->ch_w.as<float>(),
+                p->band_pbeg.as<int>(), p->band_pcnt.as<int>()};
+  dim3 grid((unsigned)((T + kFramesPerWG - 1) / kFramesPerWG), (unsigned)B);
+  hipStream_t s = (hipStream_t)stream;
+  {
+    ProfScope ps("stft_logmel", s, 0.0, (double)B * (4.0 * (double)samples + 4.0 * p->n_mels * (double)T));
+    switch (p->n_fft) {
+      case 512:
+        hipLaunchKernelGGL(stft_logmel_kernel<4>, grid, dim3(kThreads), stft_launch_lds<4>(p), s, tb, audio, row_stride, lengths, out,
+                           linear, L, T, p->hop, p->pad, p->n_mels, p->mel_passes, s0, f0);
+        break;
+      case 1024:
+        hipLaunchKernelGGL(stft_logmel_kernel<8>, grid, dim3(kThreads), stft_launch_lds<8>(p), s, tb, audio, row_stride, lengths, out,
+                           linear, L, T, p->hop, p->pad, p->n_mels, p->mel_passes, s0, f0);
+        break;
+      default:
+        hipLaunchKernelGGL(stft_logmel_kernel<16>, grid, dim3(kThreads), stft_launch_lds<16>(p), s, tb, audio, row_stride, lengths,
+                           out, linear, L, T, p->hop, p->pad, p->n_mels, p->mel_passes, s0, f0);
+    }
+  }
+  DMEL_HIP(hipGetLastError());
+  return DMEL_OK;
+}
+
 extern "C" int dmel_stft_f32(const dmel_stft_plan* p, const float* audio, int64_t row_stride, const int64_t* lengths, float* out,
                              float* linear, int B, int64_t L, void* stream) {
   DMEL_CHECK_ARG(p && audio && (out || linear), "NULL argument");
@@ -574,27 +604,31 @@ extern "C" int dmel_stft_f32(const dmel_stft_plan* p, const float* audio, int64_
   DMEL_CHECK_ARG(L < ((int64_t)1 << 30), "clip longer than 2^30 samples");
   const int64_t T = dmel_stft_num_frames(p, L);
   DMEL_CHECK_ARG(T > 0, "clip too short for one frame");
-  StftTables tb{p->winz.as<cf>(), p->tw1.as<cf>(), p->tw2.as<cf>(), p->twr.as<cf>(), p->mel_start.as<int>(),
-                p->mel_cnt.as<int>(), p->mel_ptr.as<int>(), p->mel_w.as<float>(), p->ch_k0.as<int>(), p->ch_w.as<float>(),
-                p->band_pbeg.as<int>(), p->band_pcnt.as<int>()};
-  dim3 grid((unsigned)((T + kFramesPerWG - 1) / kFramesPerWG), (unsigned)B);
-  hipStream_t s = (hipStream_t)stream;
-  {
-    ProfScope ps("stft_logmel", s, 0.0, (double)B * (4.0 * (double)L + 4.0 * p->n_mels * (double)T));
-    switch (p->n_fft) {
-      case 512:
-        hipLaunchKernelGGL(stft_logmel_kernel<4>, grid, dim3(kThreads), stft_launch_lds<4>(p), s, tb, audio, row_stride, lengths, out,
-                           linear, L, T, p->hop, p->pad, p->n_mels, p->mel_passes);
-        break;
-      case 1024:
-        hipLaunchKernelGGL(stft_logmel_kernel<8>, grid, dim3(kThreads), stft_launch_lds<8>(p), s, tb, audio, row_stride, lengths, out,
-                           linear, L, T, p->hop, p->pad, p->n_mels, p->mel_passes);
-        break;
-      default:
-        hipLaunchKernelGGL(stft_logmel_kernel<16>, grid, dim3(kThreads), stft_launch_lds<16>(p), s, tb, audio, row_stride, lengths,
-                           out, linear, L, T, p->hop, p->pad, p->n_mels, p->mel_passes);
-    }
+  return stft_launch(p, audio, row_stride, lengths, out, linear, B, L, T, 0, 0, L, stream);
+}
+
+// ---- frames of a window of a longer signal (include/dmel_hip.h: dmel_stft_window_f32) ---------------------------------------------
+extern "C" int dmel_stft_window_f32(const dmel_stft_plan* p, const float* audio, int64_t row_stride, int64_t n_samples, int64_t s0,
+                                    const int64_t* lengths, float* out, float* linear, int B, int64_t first_frame, int64_t n_frames,
+                                    int64_t total_length, void* stream) {
+  DMEL_CHECK_ARG(p && audio && (out || linear), "NULL argument");
+  DMEL_CHECK_ARG(B > 0 && B <= 65535, "batch %d out of range", B);
+  DMEL_CHECK_ARG(n_samples > 0 && row_stride >= n_samples && s0 >= 0 && first_frame >= 0 && n_frames > 0, "stft_window: bad window");
+  const bool known = total_length >= 0;
+  const int N = p->n_fft, pad = p->pad, hop = p->hop;
+  const int64_t have_end = s0 + n_samples;                 // the buffer holds absolute samples [s0, have_end)
+  if (known) {
+    DMEL_CHECK_ARG(total_length > pad, "clip length %lld must exceed the reflect pad %d", (long long)total_length, pad);
+    DMEL_CHECK_ARG(have_end <= total_length, "stft_window: the buffer runs past the end of the signal");
+    DMEL_CHECK_ARG(first_frame + n_frames <= dmel_stft_num_frames(p, total_length), "stft_window: frames past the last frame of the signal");
   }
-  DMEL_HIP(hipGetLastError());
-  return DMEL_OK;
+  const int64_t L = known ? total_length : ((int64_t)1 << 62);
+  // every sample the frames read, reflections included, must lie in the buffer
+  const int64_t first_start = first_frame * hop - pad, last_end = (first_frame + n_frames - 1) * hop - pad + N;
+  int64_t lo = std::max<int64_t>(first_start, 0), hi = std::min(last_end, L);
+  if (first_start < 0) hi = std::max(hi, std::min<int64_t>(L, (int64_t)pad + 1));      // left reflection reads samples 1 .. pad
+  if (last_end > L) lo = std::min(lo, std::max<int64_t>(0, 2 * (L - 1) - (last_end - 1)));   // right reflection reads back from L - 2
+  DMEL_CHECK_ARG(s0 <= lo && hi <= have_end, "stft_window: frames [%lld, %lld) read samples [%lld, %lld), the buffer holds [%lld, %lld)",
+                 (long long)first_frame, (long long)(first_frame + n_frames), (long long)lo, (long long)hi, (long long)s0, (long long)have_end);
+  return stft_launch(p, audio, row_stride, lengths, out, linear, B, L, n_frames, s0, first_frame, n_samples, stream);
 }

@@ -18,6 +18,7 @@ from torch import nn
 from .. import _lib
 from ..utils.spectrogram import LogMelSpectrogram
 from ..utils.utils import avg_with_mask, sequence_mask
+from .stream_schedule import EncodeGeometry, EncodeSchedule
 from .modules.bigvgan.bigvgan import BigVGAN
 from .modules.dowmsample_fsq import DownsampleFiniteScalarQuantize
 from .modules.wavenet import WaveNet
@@ -352,6 +353,39 @@ class VQGAN(nn.Module):
         """codec_lit_modules.py:462-466 -> indices (B, G, T4) int32, indices_lengths (B,)"""
         feats, mel_lengths = self.encode_unquantized(audios, audio_lengths)
         return self.get_indices_from_unquantized_features(feats, mel_lengths)
+
+    # ------------------------------------------------------------------------------ streaming encode (extension)
+    def streaming_encoder(self, batch: int = 1, audio_lengths: Optional[torch.Tensor] = None):
+        """Incremental encode with state carry, the other half of a live conversation (streaming_decoder is the first): feed audio as it
+        arrives with .push(audio (B, n) or (B, 1, n)) -- n arbitrary: 0, less than a hop, no multiple of the hop --, get the token ids
+        (B, G, m) int32 that became final with it; .finish() flushes.  The concatenated ids are the bits of encode() on the whole clip.
+        audio_lengths (B,): the items' true lengths in samples if the rows are ragged (the mask of encode()), known up front.
+        See StreamingEncoder for the lookahead."""
+        return StreamingEncoder(self, batch, audio_lengths)
+
+    @torch.no_grad()
+    def encode_stream(self, audios, audio_lengths: Optional[torch.Tensor] = None, *, chunk_samples: int = 7680):
+        """Generator: encode() fed `chunk_samples` samples at a time (audios: a (B, L) / (B, 1, L) tensor, or any iterable of (B, n)
+        chunks), yielding the (B, G, m) int32 id pieces (m > 0) whose concatenation is BIT-identical to encode(audios, audio_lengths)[0].
+        The lengths encode() returns next to the ids are StreamingEncoder.indices_lengths_for(audio_lengths)."""
+        if torch.is_tensor(audios):
+            a = audios[:, 0] if audios.ndim == 3 else audios
+            chunks = (a[:, i:i + chunk_samples] for i in range(0, a.shape[1], chunk_samples))
+            batch = a.shape[0]
+        else:
+            import itertools
+            chunks = iter(audios)
+            first = next(chunks)
+            batch = first.shape[0]
+            chunks = itertools.chain([first], chunks)
+        enc = self.streaming_encoder(batch, audio_lengths)
+        for c in chunks:
+            ids = enc.push(c)
+            if ids.shape[-1]:
+                yield ids
+        ids = enc.finish()
+        if ids.shape[-1]:
+            yield ids
 
     # ------------------------------------------------------------------------------ decode side
     @torch.no_grad()
@@ -769,3 +803,162 @@ class StreamingDecoder:
         G = self.tokens.shape[1]
         empty = torch.empty(self.B, G, 0, dtype=torch.int32, device=self.tokens.device)
         return self.push(empty, noise=torch.empty(self.B, self.C, 0, device=self.tokens.device), final=True)
+
+
+class StreamingEncoder:
+    """State of one incremental encode (VQGAN.streaming_encoder): audio chunks in, token ids out, equal to encode().
+
+    Lookahead.  The stack is not causal, and the ids are only worth streaming if they are the ids encode() gives the finished clip, so
+    token j (whose first sample is 4 j hop) is emitted once everything it depends on has arrived:
+        quantiser  -- two k2 s2 convs and two ConvNeXt blocks (k = 7 depthwise): features 4 j - 18 .. 4 j + 21;
+        encoder    -- 20 blocks, dilations (1, 2, 4, 8) x 5: 75 mel frames on each side;
+        STFT       -- frame t reads samples below t hop + n_fft - pad, pad = (n_fft - hop) / 2;
+    i.e. after sample (4 j + 96) hop + n_fft - pad: 96 frames + most of a window = 1.05 s at 24 kHz / hop 256 / n_fft 1024
+    (EncodeGeometry.lookahead_samples: 25216 samples).  It is inherent to the model, not to this implementation; finish() (or
+    push(final=True)) emits the rest, computed with the true end of the signal: reflection, zero padding and the floor of T // 4.
+
+    What is carried, in absolute time: the sample tail the next frames still need (< one window), the mel frames / the output history
+    of every encoder block / the skip sum / the features in buffers whose column 0 is frame `origin` (columns nothing reads again are
+    dropped and the buffers re-based, as StreamingDecoder._ensure does), so memory is bounded by the chunk size, not by the stream
+    length.  Per push: one STFT launch over the new frames (dmel_stft_window_f32), one encoder step over the new columns of every
+    level (dmel_wavenet_stream_step_ex: ONE launch for the dMel encoder's shape; DMEL_WAVENET_STREAM_FUSED=0 forces the ~45-launch
+    layered step, same bits), and the quantiser on the new features plus context, cropped.
+
+    The STFT launches are the library's ordinary ones, so DESIGN section 7's unexplained wrong-frame behaviour applies here too: a caller
+    that runs a streaming encode next to convolutions on ANOTHER STREAM of the same process -- a streaming decode, for example -- must
+    call dmel_stft_set_exclusive_cu(1) first, exactly as pipeline.CodecLanes does.  A `sample_rate` other than the codec's is out of
+    scope (no streaming resampler)."""
+
+    def __init__(self, codec: VQGAN, batch: int, audio_lengths=None):
+        enc, tr = codec.encoder, codec.encode_mel_transform
+        if enc.condition_channels or enc.output_projection is not None:
+            raise NotImplementedError("streaming encode needs an unconditioned encoder without output projection")
+        self.codec, self.B, self.G = codec, int(batch), codec.dmel_groups
+        self.L, self.C = len(enc.residual_layers), enc.residual_channels
+        dils = tuple(2 ** (i % enc.dilation_cycle) if enc.dilation_cycle else 1 for i in range(self.L))
+        self.maxdil = max(dils)
+        self.geo = EncodeGeometry(hop=tr.hop_length, n_fft=tr.n_fft, dilations=dils,
+                                  downsample_factor=tuple(codec.quantizer.downsample_factor))
+        self.sched = EncodeSchedule(self.geo)
+        self.n_mels = tr.n_mels
+        self.lengths = None
+        if audio_lengths is not None:
+            self.lengths = VQGAN._lengths(audio_lengths).to(torch.int64).reshape(-1)
+            if self.lengths.numel() != self.B:
+                raise ValueError("audio_lengths must have one entry per batch item")
+        self.samples = None           # (B, n) absolute samples [s0, s0 + n): what the next frames still need
+        self.s0 = 0
+        self.origin = 0               # absolute frame held in column 0 of the buffers
+        self.cap = 0
+        self.buf = None
+        self.finished = False
+
+    def indices_lengths_for(self, audio_lengths: torch.Tensor) -> torch.Tensor:
+        """the second value encode() returns for these audio lengths"""
+        return (VQGAN._lengths(audio_lengths) // self.geo.hop) // self.geo.factor
+
+    @property
+    def tokens_emitted(self) -> int:
+        return self.sched.tokens
+
+    @property
+    def capacity(self) -> int:
+        """columns of the state buffers (frames); does not grow with the stream"""
+        return self.cap
+
+    # -- buffers ---------------------------------------------------------------------------------------------------
+    def _ensure(self, st, dev) -> None:
+        """make room for the frames of step `st`: drop columns nothing will read again, grow if that is not enough"""
+        upto = st.frames[1]
+        if self.cap and upto - self.origin <= self.cap:
+            return
+        # the oldest column this step (and so any later one) reads: the last level's window, the quantiser's left context
+        need_from = max(0, min(st.prev[self.L] - self.maxdil, st.quant_window[0]))
+        shift = need_from - self.origin
+        keep = max(0, st.frames[0] - need_from)
+        want = upto - need_from
+        N = self.B * self.G
+        keys = ("mel", "hist", "skip", "feat")
+        if self.cap == 0 or want > self.cap:
+            cap = max(256, 2 * want)
+            new = dict(mel=torch.zeros(self.B, self.n_mels, cap, dtype=torch.float32, device=dev),
+                       hist=torch.zeros(self.L + 1, N, self.C, cap, dtype=torch.float32, device=dev),
+                       skip=torch.zeros(N, self.C, cap, dtype=torch.float32, device=dev),
+                       feat=torch.zeros(N, self.C, cap, dtype=torch.float32, device=dev),
+                       scratch=torch.empty(2 * N * self.C * cap + 2 * N, dtype=torch.float32, device=dev))
+            if self.cap:
+                for k in keys:
+                    new[k][..., :keep] = self.buf[k][..., shift:shift + keep]
+            self.buf, self.cap = new, cap
+        elif shift > 0:
+            for k in keys:
+                self.buf[k][..., :keep] = self.buf[k][..., shift:shift + keep].clone()
+        self.origin = need_from
+
+    # -- one step ---------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def push(self, audio: torch.Tensor, final: bool = False) -> torch.Tensor:
+        """audio (B, n) or (B, 1, n), n >= 0 -> ids (B, G, m) int32 for the m >= 0 tokens that became final with these samples."""
+        if self.finished:
+            raise RuntimeError("stream already finished")
+        _lib.require_cuda(audio, "audio")
+        if audio.ndim == 3:
+            if audio.shape[1] != 1:
+                raise ValueError(f"expected mono audio (B, 1, n), got {tuple(audio.shape)}")
+            audio = audio[:, 0]
+        if audio.ndim != 2 or audio.shape[0] != self.B:
+            raise ValueError(f"expected ({self.B}, n) or ({self.B}, 1, n), got {tuple(audio.shape)}")
+        codec, geo, dev = self.codec, self.geo, audio.device
+        if final and self.sched.samples + audio.shape[1] <= geo.pad:        # checked before any state changes
+            raise ValueError(f"the stream is {self.sched.samples + audio.shape[1]} samples long: encode() needs more than the reflect pad {geo.pad}")
+        audio = audio.float()
+        self.samples = audio.contiguous() if self.samples is None else torch.cat([self.samples, audio], dim=1)
+        st = self.sched.step(audio.shape[1], final)
+        if self.lengths is not None and self.lengths.device != dev:
+            self.lengths = self.lengths.to(dev)                              # once, not per push
+        lens = self.lengths
+        # ---- STFT: the new frames, from the sample tail
+        f0, f1 = st.frames
+        if f1 > 0:
+            self._ensure(st, dev)
+        o = self.origin
+        if f1 > f0:
+            mel = codec.encode_mel_transform.spectrogram.forward_window(self.samples, self.s0, f0, f1 - f0, st.total_length, lens)
+            self.buf["mel"][:, :, f0 - o:f1 - o] = mel
+            drop = max(0, f1 * geo.hop - geo.pad) - self.s0
+            if drop > 0:
+                self.samples, self.s0 = self.samples[:, drop:].contiguous(), self.s0 + drop
+        # ---- encoder WaveNet: every level advances to its new frontier
+        if st.next != st.prev:
+            prev = (C.c_int64 * (self.L + 1))(*[p - o for p in st.prev])
+            new = (C.c_int64 * (self.L + 1))(*[p - o for p in st.next])
+            ol = ((lens // geo.hop) - o).clamp(min=0).contiguous() if lens is not None else None
+            b = self.buf
+            with torch.cuda.device(dev):
+                h = codec.encoder.native()
+                x = b["mel"].data_ptr() if codec.encoder.input_projection is not None else None
+                if x is None:
+                    b["hist"][0][:, :, st.prev[0] - o:st.next[0] - o] = \
+                        b["mel"].view(self.B * self.G, -1, self.cap)[:, :, st.prev[0] - o:st.next[0] - o]
+                _lib.check(_lib.lib().dmel_wavenet_stream_step_ex(h, x, b["hist"].data_ptr(), b["skip"].data_ptr(), None, b["feat"].data_ptr(),
+                                                                  b["scratch"].data_ptr(), self.B * self.G, self.cap, prev, new,
+                                                                  _lib.ptr(ol), self.G, o, _lib.stream_ptr()), "wavenet_stream_step_ex")
+        # ---- quantiser: the new tokens from a feature window with context, cropped
+        j0, j1 = st.tokens
+        if j1 > j0:
+            lo, hi = st.quant_window
+            win = self.buf["feat"][:, :, lo - o:hi - o].to(codec.encode_dtype).contiguous()
+            ids = codec.quantizer.encode(win)
+            ids = ids[:, :, j0 - lo // geo.factor:j1 - lo // geo.factor].contiguous()
+        else:
+            ids = torch.empty(self.B, self.G, 0, dtype=torch.int32, device=dev)
+        if final:
+            self.finished = True
+            self.samples = self.buf = None
+        return ids
+
+    def finish(self) -> torch.Tensor:
+        """no more audio: emit every token that was waiting for right context, computed with the true end of the signal"""
+        if self.samples is None:
+            raise RuntimeError("finish() before any audio")
+        return self.push(torch.empty(self.B, 0, dtype=torch.float32, device=self.samples.device), final=True)

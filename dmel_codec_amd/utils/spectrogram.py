@@ -78,6 +78,30 @@ class LinearSpectrogram(nn.Module):
         return torch.ops.dmel_hip.stft_logmel(y, lens, self.sample_rate, self.n_fft, self.win_length, self.hop_length, self.num_mels,
                                               float(self.f_min or 0.0), float(self.f_max) if self.f_max else 0.0)
 
+    def forward_window(self, samples: Tensor, s0: int, first_frame: int, n_frames: int, total_length: int = -1,
+                       lengths: Optional[Tensor] = None) -> Tensor:
+        """Frames [first_frame, first_frame + n_frames) of a stream of which `samples` (B, n) holds the absolute samples [s0, s0 + n)
+        -> (B, num_mels, n_frames), each frame bit-identical to the same frame of forward() on the whole clip (dmel_stft_window_f32).
+        total_length: the stream's length once it is known, else -1 (no reflection at the right end yet).  lengths: absolute samples."""
+        from ..torch_ops import _stft_plan
+        _lib.require_cuda(samples, "audio")
+        if samples.ndim != 2 or samples.dtype != torch.float32 or samples.stride(-1) != 1:
+            raise ValueError("expected a (B, n) fp32 tensor with contiguous rows")
+        lens = None
+        if lengths is not None:
+            lens = lengths.reshape(-1).to(device=samples.device, dtype=torch.int64).contiguous()
+            if lens.numel() != samples.shape[0]:
+                raise ValueError("lengths must have one entry per batch item")
+        B, n = samples.shape
+        out = torch.empty(B, self.num_mels, n_frames, dtype=torch.float32, device=samples.device)
+        with torch.cuda.device(samples.device):
+            plan = _stft_plan(samples.device, self.sample_rate, self.n_fft, self.win_length, self.hop_length, self.num_mels,
+                              float(self.f_min or 0.0), float(self.f_max) if self.f_max else 0.0)
+            _lib.check(_lib.lib().dmel_stft_window_f32(plan, samples.data_ptr(), samples.stride(0), n, int(s0), _lib.ptr(lens),
+                                                       out.data_ptr(), None, B, int(first_frame), int(n_frames), int(total_length),
+                                                       _lib.stream_ptr()), "stft_window")
+        return out
+
 
 class LogMelSpectrogram(nn.Module):
     """Reference: utils/spectrogram.py:84-127."""

@@ -111,6 +111,16 @@ int dmel_stft_set_exclusive_cu(int on);
  * skipped).  Consumer: the multi-resolution STFT loss BASELINE.json's north_star names (absent from the reference). */
 int dmel_stft_f32(const dmel_stft_plan* plan, const float* audio, int64_t audio_row_stride, const int64_t* lengths,
                   float* logmel_out /*nullable*/, float* linear_out /*nullable*/, int B, int64_t L, void* stream);
+/* The frames of a WINDOW of a longer signal (streaming encode; the reference frames a finished clip once, utils/spectrogram.py:58-79):
+ * audio (B, n_samples) holds the absolute samples [s0, s0 + n_samples) of a stream; the call writes the absolute frames
+ * [first_frame, first_frame + n_frames) to logmel_out (B, n_mels, n_frames) / linear_out (B, n_frames, n_fft/2 + 1).  total_length is
+ * the length of the whole signal, or < 0 while it is not known yet.  Reflection happens only where the signal itself starts (absolute
+ * sample 0) and, once the length is known, where it ends; every frame has the bits dmel_stft_logmel_f32 gives it on the whole clip (same
+ * kernel, same per-frame arithmetic).  lengths: as above, in absolute samples (frames t >= lengths[b]/hop are written as 0).  Every
+ * sample the frames read -- frame t reads [t*hop - pad, t*hop - pad + n_fft), reflected at the ends -- must lie in the buffer (checked). */
+int dmel_stft_window_f32(const dmel_stft_plan* plan, const float* audio, int64_t audio_row_stride, int64_t n_samples, int64_t s0,
+                         const int64_t* lengths, float* logmel_out /*nullable*/, float* linear_out /*nullable*/, int B,
+                         int64_t first_frame, int64_t n_frames, int64_t total_length, void* stream);
 
 /* Backward of the linear magnitudes of dmel_stft_f32 -- what turns the multi-resolution STFT loss BASELINE.json's north_star names into a
  * LOSS (the reference has neither; its STFT framing is utils/spectrogram.py:58-76).  grad_linear (B, T, n_fft/2 + 1) = dL/d|S|, frame-major
@@ -251,6 +261,23 @@ int dmel_wavenet_backward_hooked(const dmel_wavenet* m, const float* x, const fl
  * Numerically identical to dmel_wavenet_forward column by column (same kernels, same reduction order). */
 int dmel_wavenet_stream_step(const dmel_wavenet* m, float* hist, float* skip, const float* cond /*nullable*/, float* y, float* scratch,
                              int N, int64_t cap, const int64_t* prev, const int64_t* next, void* stream);
+/* The same step for stacks WITH an input projection and with the output mask -- the encoder side of a live conversation: audio chunks
+ * in, token ids out, equal to encode() (replaces, incrementally, codec_lit_modules.py:462-466, 486-513 over wavenet.py:204-225).
+ *   x (N, Cin, cap), given exactly when the model has an input projection: the raw input in the same window coordinates; the call fills
+ *     hist[0][:, :, prev[0]:next[0]] = silu(input_projection(x)) (wavenet.py:205-207).  Without one the caller writes hist[0] as above.
+ *   out_lengths (N / group_repeat,) or NULL, relative to column 0: y columns at or behind it are written as 0 (the output mask of
+ *     dmel_wavenet_forward, codec_lit_modules.py:505-506).
+ *   origin: the absolute frame held in column 0.  origin > 0 declares that column 0 is NOT the start of the sequence: a step whose
+ *     windows would reach in front of it (prev[l] < dilation_l with new columns on level l) is refused instead of reading zero padding.
+ *   scratch: N * 2 C * cap floats followed by N int64.
+ * Narrow unconditioned stacks (the conditions of the whole-sequence kernel: residual channels in (32, 80], no condition, no output
+ * projection, dilations <= 8, DMEL_PRECISION_FP32) run the step as ONE launch (csrc/wavenet_stream.hip), cut into sub-steps of at most 96
+ * new columns per level; everything else, and every call under DMEL_WAVENET_STREAM_FUSED=0, runs the layered step.  Both produce the
+ * bits of dmel_wavenet_forward column by column.  Measured at 30 new frames per push, 70 channels (profiles/stream_encode.txt): a whole
+ * push 0.69 against 1.02 ms at 8 items, 0.71 against 1.10 ms at 128 items -- hence the default at every batch size. */
+int dmel_wavenet_stream_step_ex(const dmel_wavenet* m, const float* x /*nullable*/, float* hist, float* skip, const float* cond /*nullable*/,
+                                float* y, float* scratch, int N, int64_t cap, const int64_t* prev, const int64_t* next,
+                                const int64_t* out_lengths /*nullable*/, int group_repeat, int64_t origin, void* stream);
 
 /* ConvNeXtBlock (models/modules/firefly.py:337-402; C-ABI row `convnext_block`), standalone: y = x + gamma * pwconv2(gelu(pwconv1(
  * LayerNorm_C(dwconv7(x))))), x / y (N, dim, T).  set_tensor keys: dwconv.weight (dim,1,7), dwconv.bias, norm.weight, norm.bias,

@@ -1,0 +1,90 @@
+"""Streaming-encode benchmark: per-push time and audio-seconds per second of VQGAN.streaming_encoder for 0.32 s pushes of 24 kHz audio
+at batch 1 and batch 16, cfg-2 encoder shapes (80 mel, 8 groups, 70 channels, 20 layers).
+
+    python tools/bench_stream_encode.py [--pushes 62] [--warmup 8] [--out profiles/stream_encode.txt]
+
+The one-launch encoder step and the forced layered step (DMEL_WAVENET_STREAM_FUSED=0, read per call) run INTERLEAVED in one process:
+two encoders fed the same audio, push i of one followed by push i of the other, each push bracketed by a host synchronisation and
+timed on the wall clock (what a microphone loop pays).  Pushes before the stream's steady state (the first `--warmup`: lookahead fill,
+buffer allocation, handle creation) are discarded; medians and the 10th / 90th percentiles are taken over the rest (>= 50).  For
+scale, encode() of the whole clip is timed in the same run.  Prints one JSON line and writes the table to --out."""
+import argparse, json, os, statistics, sys, time
+import torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from dmel_codec_amd.configs import build_codec
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--pushes", type=int, default=62, help="pushes per stream (62 x 0.32 s = 19.84 s)")
+ap.add_argument("--warmup", type=int, default=8)
+ap.add_argument("--chunk", type=int, default=7680, help="samples per push (0.32 s at 24 kHz)")
+ap.add_argument("--batches", default="1,16")
+ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "stream_encode.txt"))
+args = ap.parse_args()
+assert args.pushes - args.warmup >= 50, "medians over at least 50 steady-state pushes"
+SR = 24000
+dev = torch.device("cuda:0")
+torch.manual_seed(0)
+codec = build_codec(sample_rate=SR, n_mels=80, dmel_groups=8, levels=(7, 5, 5), vocoder=None, decoder_layers=1).to(dev)
+
+
+def pct(v, q):
+    s = sorted(v)
+    return s[min(len(s) - 1, int(q * len(s)))]
+
+
+def timed_push(enc, chunk, layered):
+    if layered:
+        os.environ["DMEL_WAVENET_STREAM_FUSED"] = "0"
+    else:
+        os.environ.pop("DMEL_WAVENET_STREAM_FUSED", None)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    ids = enc.push(chunk)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3, ids
+
+
+rows, result = [], {"chunk_samples": args.chunk, "chunk_s": args.chunk / SR, "pushes": args.pushes, "warmup": args.warmup, "batch": {}}
+for B in [int(b) for b in args.batches.split(",")]:
+    audio = torch.randn(B, args.pushes * args.chunk, device=dev) * 0.1
+    encs = {"one_launch": codec.streaming_encoder(B), "layered": codec.streaming_encoder(B)}
+    ms = {k: [] for k in encs}
+    same = True
+    for i in range(args.pushes):
+        chunk = audio[:, i * args.chunk:(i + 1) * args.chunk]
+        order = ("one_launch", "layered") if i % 2 == 0 else ("layered", "one_launch")       # neither path always goes first
+        got = {}
+        for k in order:
+            t, got[k] = timed_push(encs[k], chunk, k == "layered")
+            if i >= args.warmup:
+                ms[k].append(t)
+        same = same and torch.equal(got["one_launch"], got["layered"])
+    os.environ.pop("DMEL_WAVENET_STREAM_FUSED", None)
+    for e in encs.values():
+        e.finish()
+    lens = torch.full((B,), audio.shape[1], device=dev)
+    whole = []
+    for i in range(7):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        codec.encode(audio, lens)
+        torch.cuda.synchronize()
+        whole.append((time.perf_counter() - t0) * 1e3)
+    r = {"ids_equal": bool(same), "encode_whole_clip_ms": round(statistics.median(whole[2:]), 3), "clip_s": audio.shape[1] / SR}
+    for k, v in ms.items():
+        med = statistics.median(v)
+        r[k] = {"median_ms": round(med, 3), "p10_ms": round(pct(v, 0.1), 3), "p90_ms": round(pct(v, 0.9), 3), "n": len(v),
+                "audio_s_per_s": round(B * args.chunk / SR / (med / 1e3), 1)}
+        rows.append(f"{B:5d}  {k:10s}  {med:9.3f}  {pct(v, 0.1):9.3f}  {pct(v, 0.9):9.3f}  {r[k]['audio_s_per_s']:11.1f}  {len(v):4d}")
+    r["layered_over_one_launch"] = round(r["layered"]["median_ms"] / r["one_launch"]["median_ms"], 2)
+    rows.append(f"{B:5d}  encode() of the whole {r['clip_s']:.2f} s clip: {r['encode_whole_clip_ms']:.3f} ms; ids equal: {same}")
+    result["batch"][str(B)] = r
+
+table = ["streaming encode, 0.32 s pushes of 24 kHz audio, 80 mel / 8 groups / 70 channels / 20 layers (tools/bench_stream_encode.py)",
+         f"per-push wall time incl. host synchronisation, {args.pushes - args.warmup} steady-state pushes, the two paths interleaved in one process",
+         "batch  path        median ms     p10 ms     p90 ms  audio-s / s     n"] + rows
+os.makedirs(os.path.dirname(args.out), exist_ok=True)
+with open(args.out, "w") as f:
+    f.write("\n".join(table) + "\n")
+print("\n".join(table), file=sys.stderr)
+print(json.dumps(result))
