@@ -51,6 +51,8 @@ PROTOTYPES = {
     "dmel_stft_num_frames": (C.c_int64, [vp, C.c_int64]),
     "dmel_stft_logmel_f32": (C.c_int, [vp, vp, C.c_int64, vp, vp, C.c_int, C.c_int64, vp]),
     "dmel_resample_f32": (C.c_int, [vp, vp, vp, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, vp]),
+    "dmel_resample_window_f32": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                           C.c_int, vp]),
     "dmel_stft_f32": (C.c_int, [vp, vp, C.c_int64, vp, vp, vp, C.c_int, C.c_int64, vp]),
     "dmel_stft_window_f32": (C.c_int, [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, vp]),
     "dmel_aa_snake_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp]),

@@ -39,6 +39,8 @@ int launch_fold(const float* x, float* xf, const int64_t* len, int div, int N, i
 int launch_unfold(const float* xf, float* y, const int64_t* len, int div, int N, int C, int64_t T, int P, int64_t pitch, hipStream_t s);
 int launch_resample(const float* x, float* y, const float* bank_dev, int B, int64_t L, int64_t Lout, int down, int up, int width,
                     hipStream_t s);
+int launch_resample_window(const float* x, int64_t row_stride, int64_t s0, int64_t n_samples, float* y, const float* bank_dev, int B,
+                           int64_t L, int64_t o0, int64_t n_out, int down, int up, int width, hipStream_t s);
 // Whole-WaveNet kernel for narrow unconditioned stacks on short items (wavenet_fused.hip): device pointers into the handle's existing
 // split-bf16 weight images and biases; `table` = device array [gate_w[L] | gate_b[L] | rs_w[L] | rs_b[L]] of pointers.
 struct WaveNetFused {

@@ -407,42 +407,57 @@ int launch_unfold(const float* xf, float* y, const int64_t* len, int div, int N,
 // 3 x 16 taps; 44.1 -> 24 kHz: 80 x 171), the input window comes through L1 (neighbouring outputs share all but `down` samples).
 // HBM-bound: 4 bytes read per input + 4 written per output sample.
 constexpr int kResampleLdsFloats = 15 * 1024;
-__global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ bank,
-                                                       int64_t L, int64_t Lout, int down, int up, int width, int kw, int bank_in_lds) {
+// The taps of one output sample, shared by the whole-clip and the window launch so that both give an output the same bits: one fmaf per
+// tap, k = 0 .. kw - 1 in order, zero for a tap outside the signal [0, L).  xb points at absolute sample `base` of the row.
+__device__ __forceinline__ float resample_taps(const float* __restrict__ xb, int64_t base, const float* __restrict__ w, int64_t first,
+                                               int64_t L, int kw) {
+  float acc = 0.f;
+  for (int k = 0; k < kw; ++k) {
+    const int64_t s = first + k;
+    const float v = (s >= 0 && s < L) ? xb[s - base] : 0.f;
+    acc = fmaf(w[k], v, acc);
+  }
+  return acc;
+}
+
+// x (B, row_stride) holds the absolute samples [s0, ...) of a signal of L samples; the launch writes the absolute outputs
+// [o0, o0 + n_out) to y (B, n_out).  The whole clip is (s0, o0, n_out) = (0, 0, Lout).  The host has checked that every tap inside
+// [0, L) lies in the buffer (dmel_resample_window_f32).
+__global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__ x, int64_t row_stride, int64_t s0, float* __restrict__ y,
+                                                       const float* __restrict__ bank, int64_t L, int64_t o0, int64_t n_out, int down,
+                                                       int up, int width, int kw, int bank_in_lds) {
   extern __shared__ float bsm[];
   if (bank_in_lds) {
     for (int i = threadIdx.x; i < up * kw; i += 256) bsm[i] = bank[i];
     __syncthreads();
   }
   const float* bk = bank_in_lds ? bsm : bank;
-  const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (o >= Lout) return;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_out) return;
   const int b = blockIdx.y;
+  const int64_t o = o0 + i;
   const int64_t n = o / up;
   const int p = (int)(o - n * up);
-  const float* xb = x + (int64_t)b * L;
-  const float* w = bk + (int64_t)p * kw;
-  const int64_t s0 = n * down - width;
-  float acc = 0.f;
-  for (int k = 0; k < kw; ++k) {
-    const int64_t s = s0 + k;
-    const float v = (s >= 0 && s < L) ? xb[s] : 0.f;
-    acc = fmaf(w[k], v, acc);
+  y[(int64_t)b * n_out + i] = resample_taps(x + (int64_t)b * row_stride, s0, bk + (int64_t)p * kw, n * down - width, L, kw);
+}
+
+int launch_resample_window(const float* x, int64_t row_stride, int64_t s0, int64_t n_samples, float* y, const float* bank_dev, int B,
+                           int64_t L, int64_t o0, int64_t n_out, int down, int up, int width, hipStream_t s) {
+  const int kw = 2 * width + down;
+  const int in_lds = up * kw <= kResampleLdsFloats;
+  {
+    ProfScope ps("small", s, 0.0, 4.0 * (double)B * ((double)n_samples + (double)n_out));
+    hipLaunchKernelGGL(resample_kernel, dim3((unsigned)((n_out + 255) / 256), (unsigned)B), dim3(256),
+                       in_lds ? (size_t)up * kw * sizeof(float) : 0, s, x, row_stride, s0, y, bank_dev, L, o0, n_out, down, up, width, kw,
+                       in_lds);
   }
-  y[(int64_t)b * Lout + o] = acc;
+  DMEL_HIP(hipGetLastError());
+  return DMEL_OK;
 }
 
 int launch_resample(const float* x, float* y, const float* bank_dev, int B, int64_t L, int64_t Lout, int down, int up, int width,
                     hipStream_t s) {
-  const int kw = 2 * width + down;
-  const int in_lds = up * kw <= kResampleLdsFloats;
-  {
-    ProfScope ps("small", s, 0.0, 4.0 * (double)B * ((double)L + (double)Lout));
-    hipLaunchKernelGGL(resample_kernel, dim3((unsigned)((Lout + 255) / 256), (unsigned)B), dim3(256),
-                       in_lds ? (size_t)up * kw * sizeof(float) : 0, s, x, y, bank_dev, L, Lout, down, up, width, kw, in_lds);
-  }
-  DMEL_HIP(hipGetLastError());
-  return DMEL_OK;
+  return launch_resample_window(x, L, 0, L, y, bank_dev, B, L, 0, Lout, down, up, width, s);
 }
 
 // ---- conv_post: C -> 1 channel, k taps, zero "same" padding, then tanh | clamp   (bigvgan.py:386-391) -----------
@@ -641,4 +656,32 @@ extern "C" int dmel_resample_f32(const float* x, float* y, const float* filter_b
   DMEL_CHECK_ARG(B > 0 && B <= 65535 && L > 0 && Lout > 0 && orig_freq > 0 && new_freq > 0 && width >= 0, "resample: bad shape");
   DMEL_CHECK_ARG(Lout <= (L * new_freq + orig_freq - 1) / orig_freq, "resample: Lout exceeds ceil(new_freq * L / orig_freq)");
   return dmel::launch_resample(x, y, filter_bank_dev, B, L, Lout, orig_freq, new_freq, width, (hipStream_t)stream);
+}
+
+// ---- outputs of a window of a longer signal (include/dmel_hip.h: dmel_resample_window_f32) ----------------------------------------
+extern "C" int dmel_resample_window_f32(const float* x, int64_t x_row_stride, int64_t n_samples, int64_t s0, float* y,
+                                        const float* filter_bank_dev, int B, int64_t o0, int64_t n_out, int64_t total_length,
+                                        int orig_freq, int new_freq, int width, void* stream) {
+  DMEL_CHECK_ARG(x && y && filter_bank_dev, "resample_window: NULL argument");
+  DMEL_CHECK_ARG(B > 0 && B <= 65535 && orig_freq > 0 && new_freq > 0 && width >= 0, "resample_window: bad shape");
+  DMEL_CHECK_ARG(n_samples > 0 && x_row_stride >= n_samples && s0 >= 0 && o0 >= 0 && n_out > 0, "resample_window: bad window");
+  const bool known = total_length >= 0;
+  const int64_t have_end = s0 + n_samples;                 // the buffer holds absolute samples [s0, have_end)
+  DMEL_CHECK_ARG(have_end < ((int64_t)1 << 40) && o0 + n_out < ((int64_t)1 << 40), "resample_window: position out of range");
+  if (known) {
+    DMEL_CHECK_ARG(total_length < ((int64_t)1 << 40), "resample_window: position out of range");
+    DMEL_CHECK_ARG(have_end <= total_length, "resample_window: the buffer runs past the end of the signal");
+    DMEL_CHECK_ARG(o0 + n_out <= (total_length * new_freq + orig_freq - 1) / orig_freq,
+                   "resample_window: outputs past ceil(new_freq * total_length / orig_freq)");
+  }
+  const int64_t L = known ? total_length : ((int64_t)1 << 62);
+  // every sample the outputs read must lie in the buffer or in the zero padding: output o reads
+  // [(o / up) * down - width, (o / up) * down + width + down)
+  const int64_t first = (o0 / new_freq) * orig_freq - width, last_end = ((o0 + n_out - 1) / new_freq) * orig_freq + width + orig_freq;
+  const int64_t lo = std::max<int64_t>(first, 0), hi = std::min(last_end, L);
+  DMEL_CHECK_ARG(lo >= hi || (s0 <= lo && hi <= have_end),
+                 "resample_window: outputs [%lld, %lld) read samples [%lld, %lld), the buffer holds [%lld, %lld)", (long long)o0,
+                 (long long)(o0 + n_out), (long long)lo, (long long)hi, (long long)s0, (long long)have_end);
+  return dmel::launch_resample_window(x, x_row_stride, s0, n_samples, y, filter_bank_dev, B, L, o0, n_out, orig_freq, new_freq, width,
+                                      (hipStream_t)stream);
 }

@@ -7,6 +7,7 @@ dmel_codec/models/codec_lit_modules.py (reference): same ctor kwargs, attribute 
 Every tensor op of the path is a native HIP launch; torch only owns the memory and the stream."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 from pathlib import Path
@@ -16,6 +17,7 @@ import torch
 from torch import nn
 
 from .. import _lib
+from ..utils.resample import StreamResampler, resample
 from ..utils.spectrogram import LogMelSpectrogram
 from ..utils.utils import avg_with_mask, sequence_mask
 from .stream_schedule import EncodeGeometry, EncodeSchedule
@@ -349,25 +351,35 @@ class VQGAN(nn.Module):
         return self.quantizer.encode(unquantized_features), indices_lengths
 
     @torch.no_grad()
-    def encode(self, audios, audio_lengths):
-        """codec_lit_modules.py:462-466 -> indices (B, G, T4) int32, indices_lengths (B,)"""
+    def encode(self, audios, audio_lengths, sample_rate: Optional[int] = None):
+        """codec_lit_modules.py:462-466 -> indices (B, G, T4) int32, indices_lengths (B,).  sample_rate (extension): the rate of
+        `audios` and `audio_lengths` if it is not the mel transform's; the clip is resampled and the lengths converted as
+        LogMelSpectrogram.forward(x, sample_rate=...) does it (ceil(len * new / orig))."""
+        sr = self.encode_mel_transform.sample_rate
+        if sample_rate is not None and int(sample_rate) != int(sr):
+            audios = resample(audios.float(), int(sample_rate), int(sr))
+            audio_lengths = (self._lengths(audio_lengths).to(torch.int64) * int(sr) + int(sample_rate) - 1) // int(sample_rate)
         feats, mel_lengths = self.encode_unquantized(audios, audio_lengths)
         return self.get_indices_from_unquantized_features(feats, mel_lengths)
 
     # ------------------------------------------------------------------------------ streaming encode (extension)
-    def streaming_encoder(self, batch: int = 1, audio_lengths: Optional[torch.Tensor] = None):
+    def streaming_encoder(self, batch: int = 1, audio_lengths: Optional[torch.Tensor] = None, sample_rate: Optional[int] = None):
         """Incremental encode with state carry, the other half of a live conversation (streaming_decoder is the first): feed audio as it
         arrives with .push(audio (B, n) or (B, 1, n)) -- n arbitrary: 0, less than a hop, no multiple of the hop --, get the token ids
         (B, G, m) int32 that became final with it; .finish() flushes.  The concatenated ids are the bits of encode() on the whole clip.
         audio_lengths (B,): the items' true lengths in samples if the rows are ragged (the mask of encode()), known up front.
+        sample_rate: the rate of the pushed audio and of audio_lengths if it is not the codec's (a microphone's 16 / 44.1 / 48 kHz); a
+        StreamResampler in front then converts it, and the ids are the bits of encode(..., sample_rate=sample_rate).
         See StreamingEncoder for the lookahead."""
-        return StreamingEncoder(self, batch, audio_lengths)
+        return StreamingEncoder(self, batch, audio_lengths, sample_rate)
 
     @torch.no_grad()
-    def encode_stream(self, audios, audio_lengths: Optional[torch.Tensor] = None, *, chunk_samples: int = 7680):
+    def encode_stream(self, audios, audio_lengths: Optional[torch.Tensor] = None, *, chunk_samples: int = 7680,
+                      sample_rate: Optional[int] = None):
         """Generator: encode() fed `chunk_samples` samples at a time (audios: a (B, L) / (B, 1, L) tensor, or any iterable of (B, n)
         chunks), yielding the (B, G, m) int32 id pieces (m > 0) whose concatenation is BIT-identical to encode(audios, audio_lengths)[0].
-        The lengths encode() returns next to the ids are StreamingEncoder.indices_lengths_for(audio_lengths)."""
+        The lengths encode() returns next to the ids are StreamingEncoder.indices_lengths_for(audio_lengths).  sample_rate: the rate of
+        the audio, the lengths and chunk_samples if it is not the codec's; the ids are then those of encode(..., sample_rate=...)."""
         if torch.is_tensor(audios):
             a = audios[:, 0] if audios.ndim == 3 else audios
             chunks = (a[:, i:i + chunk_samples] for i in range(0, a.shape[1], chunk_samples))
@@ -378,7 +390,7 @@ class VQGAN(nn.Module):
             first = next(chunks)
             batch = first.shape[0]
             chunks = itertools.chain([first], chunks)
-        enc = self.streaming_encoder(batch, audio_lengths)
+        enc = self.streaming_encoder(batch, audio_lengths, sample_rate)
         for c in chunks:
             ids = enc.push(c)
             if ids.shape[-1]:
@@ -428,17 +440,21 @@ class VQGAN(nn.Module):
 
     # ------------------------------------------------------------------------------ streaming decode (extension)
     def streaming_decoder(self, batch: int = 1, feature_lengths: Optional[torch.Tensor] = None, return_audios: bool = True,
-                          graph_chunk_tokens: Optional[int] = None, overlap_vocoder: bool = False):
+                          graph_chunk_tokens: Optional[int] = None, overlap_vocoder: bool = False,
+                          output_sample_rate: Optional[int] = None):
         """Incremental decode with state carry (the reference decodes once, after the LM has finished,
         lm_lit_modules.py:467-471): feed token chunks as they arrive with .push(ids (B, G, n)), get audio back as soon as its right
         context exists; .finish() flushes.  See StreamingDecoder.  graph_chunk_tokens = n: once the stream has reached its steady state, a
         push of exactly n tokens is ONE HIP-graph replay instead of ~250 launches (an unbounded stream: feature_lengths must be None).
-        overlap_vocoder: the vocoder of a push runs on its own stream (StreamingDecoder.wait_audio before the audio is used)."""
-        return StreamingDecoder(self, batch, feature_lengths, return_audios, graph_chunk_tokens, overlap_vocoder)
+        overlap_vocoder: the vocoder of a push runs on its own stream (StreamingDecoder.wait_audio before the audio is used).
+        output_sample_rate: the playback device's rate if it is not the vocoder's; the audio pieces then pass through a StreamResampler
+        and concatenate to resample(decode() audio, vocoder rate, output_sample_rate), bit for bit (the mel pieces are unchanged)."""
+        return StreamingDecoder(self, batch, feature_lengths, return_audios, graph_chunk_tokens, overlap_vocoder, output_sample_rate)
 
     @torch.no_grad()
     def decode_stream(self, indices, feature_lengths=None, *, chunk_tokens: int = 64, noise: Optional[torch.Tensor] = None,
-                      return_audios: bool = True, use_graph: bool = False, pipeline: bool = False):
+                      return_audios: bool = True, use_graph: bool = False, pipeline: bool = False,
+                      output_sample_rate: Optional[int] = None):
         """Generator: decode() fed `chunk_tokens` tokens at a time (indices: a (B, G, T4) tensor, or any iterable of (B, G, n) chunks),
         yielding (audio | None, gen_mel) pieces whose concatenation is BIT-identical to decode() on the whole sequence.  The decoder
         WaveNet keeps the output history of every block and only ever computes new columns (dmel_wavenet_stream_step: total work 1.0x);
@@ -447,7 +463,8 @@ class VQGAN(nn.Module):
         noise: (B, C, 4 T4) for reproducible runs (tensor input only), else drawn per chunk like decode() draws it.
         pipeline=True: the vocoder runs on its own stream and a piece is yielded one chunk LATER -- after the next chunk has been pulled from
         `indices` and pushed -- so that the vocoder of chunk i overlaps the decoder WaveNet of chunk i + 1 (same pieces, same bits; an
-        iterator that blocks until the LM has produced the next chunk delays every piece by that long)."""
+        iterator that blocks until the LM has produced the next chunk delays every piece by that long).
+        output_sample_rate: see streaming_decoder; the audio pieces then concatenate to the resampled decode() audio."""
         if torch.is_tensor(indices):
             T4 = indices.shape[2]
             chunks = (indices[:, :, a:a + chunk_tokens] for a in range(0, T4, chunk_tokens))
@@ -459,7 +476,7 @@ class VQGAN(nn.Module):
             import itertools
             chunks = itertools.chain([first], chunks)
         dec = self.streaming_decoder(batch, feature_lengths, return_audios, graph_chunk_tokens=chunk_tokens if use_graph else None,
-                                     overlap_vocoder=pipeline and return_audios)
+                                     overlap_vocoder=pipeline and return_audios, output_sample_rate=output_sample_rate)
         factor = math.prod(self.quantizer.downsample_factor)
         pos = 0
         held = None                                   # pipeline: (piece, its vocoder's event), yielded after the NEXT push was enqueued
@@ -484,7 +501,7 @@ class VQGAN(nn.Module):
         out = dec.finish()
         if held is not None:
             yield release(held)
-        if out[1].shape[-1]:
+        if out[1].shape[-1] or (out[0] is not None and out[0].shape[-1]):       # the resampler's flush can be audio without a mel frame
             yield (dec.wait_audio(out[0]), out[1]) if pipeline and return_audios else out
 
     #: mel frames of context the decode path needs on each side of a chunk for its interior to be exact:
@@ -546,7 +563,7 @@ class StreamingDecoder:
     QUANT_HALO_TOKENS = 4        # ConvNeXt k7 at rates 2 and 4: 3 / 2 + 3 / 4 tokens of context on each side
 
     def __init__(self, codec: VQGAN, batch: int, feature_lengths, return_audios: bool, graph_chunk_tokens: Optional[int] = None,
-                 overlap_vocoder: bool = False):
+                 overlap_vocoder: bool = False, output_sample_rate: Optional[int] = None):
         if codec.decoder is None:
             raise ValueError("Decoder is not loaded")
         if overlap_vocoder and graph_chunk_tokens is not None:
@@ -555,7 +572,17 @@ class StreamingDecoder:
             raise ValueError("graph_chunk_tokens needs an unbounded stream (feature_lengths=None): length masks change from push to push")
         if return_audios and codec.vocoder is None:
             raise ValueError("Vocoder is not loaded")
+        if output_sample_rate is not None and graph_chunk_tokens is not None:
+            raise ValueError("graph_chunk_tokens and output_sample_rate exclude each other: the resampler's carried tail would have to "
+                             "be a static buffer of the graph")
         self.codec, self.B, self.return_audios = codec, int(batch), return_audios
+        # the playback rate: the vocoder's audio pieces go through a stateful resampler (its launch and its tail update run wherever the
+        # vocoder ran, in front of `audio_event` when that is a side stream)
+        self._rs = None
+        if return_audios and output_sample_rate is not None:
+            voc_sr = int(codec.vocoder.h.get("sampling_rate", codec.encode_mel_transform.sample_rate))
+            if int(output_sample_rate) != voc_sr:
+                self._rs = StreamResampler(voc_sr, int(output_sample_rate), self.B)
         dec = codec.decoder
         if dec.input_projection is not None:
             raise NotImplementedError("streaming needs a decoder without input projection (input_channels == residual_channels)")
@@ -772,12 +799,27 @@ class StreamingDecoder:
                     self._voc_stream.wait_stream(cur)               # the window copy above (and everything before it) is done
                     with torch.cuda.stream(self._voc_stream):
                         wav = codec.vocoder(win)
+                        audio = wav[:, :, (self.emitted - lo) * self.up:(e_new - lo) * self.up]
+                        if self._rs is not None:
+                            audio = self._rs.push(audio[:, 0], final=final)[:, None]
                         self.audio_event = torch.cuda.Event()
                         self.audio_event.record(self._voc_stream)
                     win.record_stream(self._voc_stream)
                 else:
                     wav = codec.vocoder(win)
-                audio = wav[:, :, (self.emitted - lo) * self.up:(e_new - lo) * self.up]
+                    audio = wav[:, :, (self.emitted - lo) * self.up:(e_new - lo) * self.up]
+                    if self._rs is not None:
+                        audio = self._rs.push(audio[:, 0], final=final)[:, None]
+            elif self._rs is not None and final and not self._rs.finished:
+                # nothing left to vocode, but the resampler still holds outputs that waited for the end of the signal
+                side = self._overlap and self._voc_stream is not None
+                if side:
+                    self._voc_stream.wait_stream(torch.cuda.current_stream(dev))
+                with torch.cuda.stream(self._voc_stream) if side else contextlib.nullcontext():
+                    audio = self._rs.finish()[:, None]
+                    if side:
+                        self.audio_event = torch.cuda.Event()
+                        self.audio_event.record(self._voc_stream)
             else:
                 audio = torch.empty(self.B, 1, 0, dtype=torch.float32, device=dev)
         self.emitted = e_new
@@ -826,10 +868,15 @@ class StreamingEncoder:
 
     The STFT launches are the library's ordinary ones, so DESIGN section 7's unexplained wrong-frame behaviour applies here too: a caller
     that runs a streaming encode next to convolutions on ANOTHER STREAM of the same process -- a streaming decode, for example -- must
-    call dmel_stft_set_exclusive_cu(1) first, exactly as pipeline.CodecLanes does.  A `sample_rate` other than the codec's is out of
-    scope (no streaming resampler)."""
+    call dmel_stft_set_exclusive_cu(1) first, exactly as pipeline.CodecLanes does.
 
-    def __init__(self, codec: VQGAN, batch: int, audio_lengths=None):
+    sample_rate: pushes and audio_lengths are in samples of that rate; a StreamResampler in front (one more launch per push) feeds the
+    push at the codec's rate, final=True flushes it first, and the lengths are converted once (ceil(len * new / orig)).  The ids are the
+    bits of encode(..., sample_rate=sample_rate).  The lookahead above stays what it is at the codec's rate; in source samples it is
+    `lookahead_source_samples` (token_ready_source_samples(0)): the resampler's inverse of it, i.e. the same time plus the filter's
+    right context (48 kHz: 50445 samples, 16 kHz: 16819)."""
+
+    def __init__(self, codec: VQGAN, batch: int, audio_lengths=None, sample_rate: Optional[int] = None):
         enc, tr = codec.encoder, codec.encode_mel_transform
         if enc.condition_channels or enc.output_projection is not None:
             raise NotImplementedError("streaming encode needs an unconditioned encoder without output projection")
@@ -846,6 +893,12 @@ class StreamingEncoder:
             self.lengths = VQGAN._lengths(audio_lengths).to(torch.int64).reshape(-1)
             if self.lengths.numel() != self.B:
                 raise ValueError("audio_lengths must have one entry per batch item")
+        self.sample_rate = int(tr.sample_rate if sample_rate is None else sample_rate)
+        self.resampler = None
+        if self.sample_rate != int(tr.sample_rate):
+            self.resampler = StreamResampler(self.sample_rate, int(tr.sample_rate), self.B)
+            if self.lengths is not None:                                     # once: source samples -> codec samples
+                self.lengths = (self.lengths * int(tr.sample_rate) + self.sample_rate - 1) // self.sample_rate
         self.samples = None           # (B, n) absolute samples [s0, s0 + n): what the next frames still need
         self.s0 = 0
         self.origin = 0               # absolute frame held in column 0 of the buffers
@@ -854,8 +907,23 @@ class StreamingEncoder:
         self.finished = False
 
     def indices_lengths_for(self, audio_lengths: torch.Tensor) -> torch.Tensor:
-        """the second value encode() returns for these audio lengths"""
-        return (VQGAN._lengths(audio_lengths) // self.geo.hop) // self.geo.factor
+        """the second value encode() returns for these audio lengths (in samples of the stream's own rate)"""
+        lens = VQGAN._lengths(audio_lengths)
+        if self.resampler is not None:
+            sr = int(self.codec.encode_mel_transform.sample_rate)
+            lens = (lens.to(torch.int64) * sr + self.sample_rate - 1) // self.sample_rate
+        return (lens // self.geo.hop) // self.geo.factor
+
+    def token_ready_source_samples(self, j: int) -> int:
+        """pushed samples (at the stream's own rate) after which token j is final mid-stream: EncodeGeometry.token_ready_samples(j)
+        samples at the codec's rate, and the input the resampler needs before it has emitted that many"""
+        k = self.geo.token_ready_samples(j)
+        return k if self.resampler is None else self.resampler.sched.samples_needed(k)
+
+    @property
+    def lookahead_source_samples(self) -> int:
+        """EncodeGeometry.lookahead_samples in samples of the stream's own rate, the resampler's right context included"""
+        return self.token_ready_source_samples(0)
 
     @property
     def tokens_emitted(self) -> int:
@@ -909,6 +977,12 @@ class StreamingEncoder:
         if audio.ndim != 2 or audio.shape[0] != self.B:
             raise ValueError(f"expected ({self.B}, n) or ({self.B}, 1, n), got {tuple(audio.shape)}")
         codec, geo, dev = self.codec, self.geo, audio.device
+        if self.resampler is not None:
+            rs = self.resampler.sched
+            if final and rs.total_outputs(rs.samples + audio.shape[1]) <= geo.pad:
+                raise ValueError(f"the stream is {rs.total_outputs(rs.samples + audio.shape[1])} samples long at the codec's rate: "
+                                 f"encode() needs more than the reflect pad {geo.pad}")
+            audio = self.resampler.push(audio.float(), final=final)
         if final and self.sched.samples + audio.shape[1] <= geo.pad:        # checked before any state changes
             raise ValueError(f"the stream is {self.sched.samples + audio.shape[1]} samples long: encode() needs more than the reflect pad {geo.pad}")
         audio = audio.float()

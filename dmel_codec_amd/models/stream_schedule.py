@@ -12,6 +12,7 @@ so token j is final as soon as `token_ready_samples(j)` samples have arrived -- 
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
@@ -128,5 +129,97 @@ class EncodeSchedule:
                         tokens=(self.tokens, j_new), quant_window=(lo_tok * F, ready),
                         total_length=self.samples if final else -1)
         self.frames, self.levels, self.tokens = f_new, nxt, j_new
+        self.finished = final
+        return st
+
+
+# ---------------------------------------------------------------------------------------------------- streaming sample-rate conversion
+def resample_width(orig: int, new: int, lowpass_filter_width: int = 6, rolloff: float = 0.99) -> int:
+    """half width of the windowed sinc in input samples (orig, new already divided by their gcd): torchaudio's
+    `_get_sinc_resample_kernel`, as utils/resample.py: sinc_resample_bank evaluates it"""
+    return int(math.ceil(lowpass_filter_width * orig / (min(orig, new) * rolloff)))
+
+
+@dataclass(frozen=True)
+class ResampleStep:
+    samples: int                      # input samples received so far
+    final: bool
+    outputs: Tuple[int, int]          # output samples [a, b) that become final now
+    reads: Tuple[int, int]            # input samples [lo, hi) they read inside the signal (lo == hi: none)
+    keep_from: int                    # oldest input sample a later output still reads: the tail carried to the next step starts here
+    total_length: int                 # -1 until the stream's end is known
+
+
+class ResampleSchedule:
+    """The counters of a streamed polyphase resampler (utils/resample.py: StreamResampler).  With down / up = orig / new in lowest terms,
+    output o = n up + p (phase p of group n) reads the inputs [n down - width, n down + width + down), zero outside the signal.
+
+    Mid-stream, after k input samples, group n is final once its last tap has arrived: n down + width + down - 1 < k, so
+    groups_ready(k) = (k - width - down) // down + 1 for k >= width + down, else 0, and whole groups are emitted:
+    outputs_ready(k) = up * groups_ready(k).  When the stream ends at length L the rest is emitted up to ceil(up L / down), the
+    whole-clip output length, with zeros behind the end.
+
+    Carried: the next group to emit, n = emitted / up, reads from n down - width, and nothing later reads in front of that.  Group n is
+    not ready, so k < n down + width + down: the tail [n down - width, k) is shorter than kw = 2 width + down samples -- `width` of left
+    context, and less than width + down of a group whose right context is still arriving.
+
+    Latency: output m (0-based count m + 1) is final after samples_needed(m + 1) = ceil((m + 1) / up) down + width input samples, which is
+    at most width + down source samples behind that output's own position m down / up: the latency the resampler adds."""
+
+    def __init__(self, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99):
+        if orig_freq <= 0 or new_freq <= 0:
+            raise ValueError("Original frequency and desired frequecy should be positive")
+        g = math.gcd(int(orig_freq), int(new_freq))
+        self.down, self.up = int(orig_freq) // g, int(new_freq) // g
+        self.width = resample_width(self.down, self.up, lowpass_filter_width, rolloff)
+        self.kw = 2 * self.width + self.down
+        self.samples = 0
+        self.emitted = 0
+        self.finished = False
+
+    # -- pure functions of the rates --------------------------------------------------------------------------------
+    def outputs_ready(self, k: int) -> int:
+        """outputs whose every tap is among the first k samples of an unfinished stream (whole groups)"""
+        need = self.width + self.down
+        return 0 if k < need else ((k - need) // self.down + 1) * self.up
+
+    def samples_needed(self, m: int) -> int:
+        """inverse: the smallest k with outputs_ready(k) >= m"""
+        return 0 if m <= 0 else -(-m // self.up) * self.down + self.width
+
+    def total_outputs(self, length: int) -> int:
+        """outputs of a finished clip of `length` samples: ceil(new * length / orig)"""
+        return -(-self.up * length // self.down)
+
+    def first_read(self, o: int) -> int:
+        """oldest input sample output o reads (may be negative: zero padding)"""
+        return (o // self.up) * self.down - self.width
+
+    @property
+    def max_tail(self) -> int:
+        """the carried tail is always shorter than this"""
+        return self.kw
+
+    @property
+    def tail_start(self) -> int:
+        return max(0, self.first_read(self.emitted))
+
+    # -- the stream ---------------------------------------------------------------------------------------------------
+    def step(self, n: int, final: bool = False) -> ResampleStep:
+        if self.finished:
+            raise RuntimeError("stream already finished")
+        if n < 0:
+            raise ValueError("negative sample count")
+        self.samples += n
+        k = self.samples
+        o_new = self.total_outputs(k) if final else self.outputs_ready(k)
+        o_new = max(o_new, self.emitted)
+        lo = hi = 0
+        if o_new > self.emitted:
+            lo = max(0, self.first_read(self.emitted))
+            hi = max(lo, min(k, self.first_read(o_new - 1) + self.kw))
+        st = ResampleStep(samples=k, final=final, outputs=(self.emitted, o_new), reads=(lo, hi),
+                          keep_from=k if final else min(k, max(0, self.first_read(o_new))), total_length=k if final else -1)
+        self.emitted = o_new
         self.finished = final
         return st

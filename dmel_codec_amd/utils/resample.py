@@ -1,7 +1,8 @@
 """Sample-rate conversion on the MI355X: `torchaudio.functional.resample(x, orig_freq, new_freq)` as the reference calls it in
 LogMelSpectrogram.forward(x, sample_rate=...) (utils/spectrogram.py:122-123; torchaudio's defaults: sinc_interp_hann,
 lowpass_filter_width 6, rolloff 0.99).  The polyphase filter bank is built once per (orig, new, device) on the host, the filtering is
-one HIP launch (csrc/small_ops.hip: resample_kernel, through torch.ops.dmel_hip.resample)."""
+one HIP launch (csrc/small_ops.hip: resample_kernel, through torch.ops.dmel_hip.resample).  StreamResampler is the same conversion fed
+chunk by chunk (torch.ops.dmel_hip.resample_window -> dmel_resample_window_f32): same kernel, same bits."""
 from __future__ import annotations
 
 import math
@@ -10,6 +11,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..models.stream_schedule import ResampleSchedule
 
 _banks: dict = {}
 
@@ -53,6 +55,36 @@ def _(x, bank, orig, new, width):
     return x.new_empty((x.shape[0], (new * x.shape[1] + orig - 1) // orig), dtype=torch.float32)
 
 
+@torch.library.custom_op("dmel_hip::resample_window", mutates_args=(), device_types="cuda")
+def _resample_window_op(x: torch.Tensor, bank: torch.Tensor, orig: int, new: int, width: int, s0: int, o0: int, n_out: int,
+                        total_length: int) -> torch.Tensor:
+    """x (B, n) fp32, rows contiguous (any row stride): the absolute samples [s0, s0 + n) of a stream -> its absolute outputs
+    [o0, o0 + n_out), each with the bits resample() gives it on the whole clip.  total_length: the stream's length, -1 while unknown."""
+    if x.ndim != 2 or x.dtype != torch.float32 or x.stride(-1) != 1:
+        raise ValueError("expected a (B, n) fp32 tensor with contiguous rows")
+    B, n = x.shape
+    y = torch.empty(B, n_out, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().dmel_resample_window_f32(x.data_ptr(), x.stride(0) if B > 1 else max(n, x.stride(0)), n, s0, y.data_ptr(),
+                                                       bank.data_ptr(), B, o0, n_out, total_length, orig, new, width,
+                                                       _lib.stream_ptr()), "resample_window")
+    return y
+
+
+@_resample_window_op.register_fake
+def _(x, bank, orig, new, width, s0, o0, n_out, total_length):
+    return x.new_empty((x.shape[0], n_out), dtype=torch.float32)
+
+
+def filter_bank(orig_freq: int, new_freq: int, device):
+    """(bank on `device`, width, orig, new), orig / new in lowest terms; built once per (orig, new, device)"""
+    key = (int(orig_freq), int(new_freq), str(device))
+    if key not in _banks:
+        kern, width, orig, new = sinc_resample_bank(orig_freq, new_freq)
+        _banks[key] = (torch.from_numpy(kern).to(device).contiguous(), width, orig, new)
+    return _banks[key]
+
+
 def resample(waveform: torch.Tensor, orig_freq: int, new_freq: int) -> torch.Tensor:
     """waveform (..., L) fp32 on the GPU -> (..., ceil(new_freq * L / orig_freq))."""
     if orig_freq <= 0 or new_freq <= 0:
@@ -60,12 +92,86 @@ def resample(waveform: torch.Tensor, orig_freq: int, new_freq: int) -> torch.Ten
     if int(orig_freq) == int(new_freq):
         return waveform
     _lib.require_cuda(waveform, "waveform")
-    key = (int(orig_freq), int(new_freq), str(waveform.device))
-    if key not in _banks:
-        kern, width, orig, new = sinc_resample_bank(orig_freq, new_freq)
-        _banks[key] = (torch.from_numpy(kern).to(waveform.device).contiguous(), width, orig, new)
-    bank, width, orig, new = _banks[key]
+    bank, width, orig, new = filter_bank(orig_freq, new_freq, waveform.device)
     shape = waveform.shape
     x = waveform.float().reshape(-1, shape[-1]).contiguous()
     y = torch.ops.dmel_hip.resample(x, bank, orig, new, width)
     return y.reshape(*shape[:-1], y.shape[-1])
+
+
+class StreamResampler:
+    """resample() fed chunk by chunk: .push(x (B, n), final=False) -> y (B, m), the m >= 0 outputs that became final with these samples;
+    .finish() flushes.  n is arbitrary (0, less than the filter's width, ...); the concatenated pieces are torch.equal to
+    resample(whole, orig_freq, new_freq).  An output is final once its last tap has arrived, so mid-stream the resampler is at most
+    `width + down` source samples behind (ResampleSchedule.samples_needed; 15 samples for 48 -> 24 kHz, 9 for 16 -> 24 kHz, 159 for
+    44.1 -> 24 kHz), and whole phase groups are emitted.
+
+    Carried on the device: the input tail the next outputs still read, fewer than kw = 2 width + down samples, at the front of one of
+    two buffers of constant capacity (they grow only if a larger push arrives).  Per push: the chunk is copied behind the tail, ONE
+    resample launch (dmel_resample_window_f32) reads the buffer, and the new tail is copied to the front of the other buffer.  No host
+    synchronisation; everything runs on the current stream, so a caller keeps to one stream (or orders its streams itself).  Equal
+    rates pass the chunks through untouched."""
+
+    def __init__(self, orig_freq: int, new_freq: int, batch: int):
+        self.sched = ResampleSchedule(orig_freq, new_freq)
+        self.orig_freq, self.new_freq, self.B = int(orig_freq), int(new_freq), int(batch)
+        self.identity = self.orig_freq == self.new_freq
+        self.buf = self.spare = None      # (B, cap): buf[:, :fill] holds the absolute input samples [s0, s0 + fill)
+        self.s0 = 0
+        self.fill = 0
+        self._dev = None                  # where the last push lived: finish() makes its empty chunk there
+
+    @property
+    def capacity(self) -> int:
+        """samples per row of the carried buffer; does not grow with the stream"""
+        return 0 if self.buf is None else self.buf.shape[1]
+
+    @property
+    def finished(self) -> bool:
+        return self.sched.finished
+
+    @torch.no_grad()
+    def push(self, x: torch.Tensor, final: bool = False) -> torch.Tensor:
+        _lib.require_cuda(x, "waveform")
+        if x.ndim != 2 or x.shape[0] != self.B:
+            raise ValueError(f"expected ({self.B}, n), got {tuple(x.shape)}")
+        sc = self.sched
+        n = x.shape[1]
+        self._dev = x.device
+        if self.identity:
+            sc.step(n, final)
+            return x
+        st = sc.step(n, final)
+        dev = x.device
+        bank, width, orig, new = filter_bank(self.orig_freq, self.new_freq, dev)
+        assert (width, orig, new) == (sc.width, sc.down, sc.up)
+        if self.fill + n > self.capacity:
+            cap = self.fill + n + sc.kw               # room for this chunk behind the longest tail: equal pushes never grow it again
+            grown = torch.empty(self.B, cap, dtype=torch.float32, device=dev)
+            if self.fill:
+                grown[:, :self.fill] = self.buf[:, :self.fill]
+            self.buf, self.spare = grown, torch.empty_like(grown)
+        if n:
+            self.buf[:, self.fill:self.fill + n] = x
+            self.fill += n
+        o0, o1 = st.outputs
+        if o1 > o0:
+            y = torch.ops.dmel_hip.resample_window(self.buf[:, :self.fill], bank, orig, new, width, self.s0, o0, o1 - o0, st.total_length)
+        else:
+            y = torch.empty(self.B, 0, dtype=torch.float32, device=dev)
+        if final:
+            self.buf = self.spare = None
+            self.fill = 0
+        elif st.keep_from > self.s0:
+            drop = st.keep_from - self.s0
+            keep = self.fill - drop
+            if keep:
+                self.spare[:, :keep] = self.buf[:, drop:self.fill]
+            self.buf, self.spare = self.spare, self.buf
+            self.s0, self.fill = st.keep_from, keep
+        return y
+
+    def finish(self) -> torch.Tensor:
+        """no more samples: the outputs that were waiting for right context, computed with the true end of the signal"""
+        dev = self._dev if self._dev is not None else torch.device("cuda", torch.cuda.current_device())
+        return self.push(torch.empty(self.B, 0, dtype=torch.float32, device=dev), final=True)

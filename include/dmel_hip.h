@@ -144,6 +144,16 @@ int dmel_stft_magnitude_backward_f32(const dmel_stft_grad* h, const float* audio
  * ---------------------------------------------------------------------------------------------- */
 int dmel_resample_f32(const float* x, float* y, const float* filter_bank_dev, int B, int64_t L, int64_t Lout, int orig_freq,
                       int new_freq, int width, void* stream);
+/* The outputs of a WINDOW of a longer signal (streaming at the sound card's rate; the reference resamples a finished clip once,
+ * utils/spectrogram.py:122-123): x (B, n_samples), rows x_row_stride floats apart, holds the absolute input samples [s0, s0 + n_samples)
+ * of a stream; the call writes the absolute output samples [o0, o0 + n_out) to y (B, n_out).  o0 may be any value, not only a multiple
+ * of new_freq.  total_length is the length of the whole input, or < 0 while it is not known yet.  Zero padding happens only where the
+ * signal itself starts (absolute sample < 0) and, once the length is known, where it ends (>= total_length); every output has the bits
+ * dmel_resample_f32 gives it on the whole clip (same kernel, same tap loop).  filter_bank_dev, orig_freq, new_freq, width: as above.
+ * Every sample the outputs read -- output o reads [(o / new) * orig - width, (o / new) * orig + width + orig) -- must lie in the buffer
+ * or in the zero padding (checked: DMEL_EINVAL, nothing is launched, y is left as it was). */
+int dmel_resample_window_f32(const float* x, int64_t x_row_stride, int64_t n_samples, int64_t s0, float* y, const float* filter_bank_dev,
+                             int B, int64_t o0, int64_t n_out, int64_t total_length, int orig_freq, int new_freq, int width, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Data front end on the GPU: what LhotseTTSDataset.__getitem__ + collate_fn do to the decoded clips of

@@ -276,6 +276,9 @@ int main() {
   {
     auto x = buf(3 * 5000), y = buf(3 * 7500), bank = buf(3 * 16), al = buf(8), be = buf(8), taps = buf(12);
     CK(dmel_resample_f32(x.data(), y.data(), bank.data(), 3, 5000, 7500, 2, 3, 7, nullptr));
+    // outputs [100, 1100) of a stream whose samples [50, 850) are in the buffer: they read [(100 / 3) * 2 - 7, (1099 / 3) * 2 + 9) = [59, 741)
+    CK(dmel_resample_window_f32(x.data(), 5000, 800, 50, y.data(), bank.data(), 3, 100, 1000, -1, 2, 3, 7, nullptr));
+    if (dmel_resample_window_f32(x.data(), 5000, 800, 60, y.data(), bank.data(), 3, 100, 1000, -1, 2, 3, 7, nullptr) == 0) { std::printf("FAIL resample_window accepted a buffer that misses a tap\n"); ++failures; }
     auto xs = buf(2 * 8 * 3000), ys = buf(2 * 8 * 3000), da = buf(8), db = buf(8);
     CK(dmel_aa_snake_f32(xs.data(), ys.data(), al.data(), be.data(), taps.data(), taps.data(), 1, 2, 8, 3000, nullptr));
     CK(dmel_aa_snake_backward_f32(xs.data(), ys.data(), xs.data(), al.data(), be.data(), da.data(), db.data(), taps.data(), taps.data(), 1, 2, 8, 3000, nullptr));

@@ -1,7 +1,13 @@
 """Streaming decode benchmark (BASELINE.json configs[4], codec side): token ids (1, G, T4) arrive in chunks, audio leaves as soon as its
 right context exists (VQGAN.decode_stream: WaveNet state carry + windowed vocoder).  Reports the latency from the first token to the
-first audio, the sustained audio-seconds per second at batch 1, and the windowed (stateless, halo re-run) form for comparison."""
-import json, os, sys, time
+first audio, the sustained audio-seconds per second at batch 1, and the windowed (stateless, halo re-run) form for comparison.
+
+    python tools/bench_stream.py --output-sample-rate 48000 [--out profiles/stream_resample.txt]
+
+runs only this: two streaming decoders fed the same 64-token chunks, one at the vocoder's rate (output_sample_rate=None) and one with a
+StreamResampler behind the vocoder, push i of one followed by push i of the other, each push bracketed by a host synchronisation and timed
+on the wall clock; median and 10th / 90th percentile over the steady-state pushes, at batch 1 and 16, APPENDED to --out."""
+import json, os, statistics, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
@@ -13,6 +19,59 @@ T4 = 469                                      # 20 s of audio at 23.4 token fram
 ids = torch.randint(0, 175, (1, 10, T4), generator=g, dtype=torch.int32).to(dev)
 flen = torch.tensor([T4], device=dev)
 ONLY_PIPE = "--pipeline-only" in sys.argv
+
+
+def arg_after(flag, default=None):
+    return sys.argv[sys.argv.index(flag) + 1] if flag in sys.argv else default
+
+
+def output_rate_section(sr, out):
+    chunk, warmup, T4L = 64, 6, 64 * 60
+    pct = lambda v, q: sorted(v)[min(len(v) - 1, int(q * len(v)))]
+    gl = torch.Generator().manual_seed(6)
+    ids_long = torch.randint(0, 175, (1, 10, T4L), generator=gl, dtype=torch.int32).to(dev)
+    rows, result = [], {"output_sample_rate": sr, "chunk_tokens": chunk, "batch": {}}
+    for B in (1, 16):
+        ids_b = ids_long.expand(B, -1, -1).contiguous()
+        decs = {"vocoder_rate": codec.streaming_decoder(B, None, True), f"to_{sr}": codec.streaming_decoder(B, None, True, output_sample_rate=sr)}
+        ms = {k: [] for k in decs}
+        samples = {k: 0 for k in decs}
+        keys = list(decs)
+        for i, a0 in enumerate(range(0, T4L, chunk)):
+            noise = torch.randn(B, codec.decoder.input_channels, chunk * 4, device=dev)
+            for k in (keys if i % 2 == 0 else keys[::-1]):                  # neither path always goes first
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                a, m = decs[k].push(ids_b[:, :, a0:a0 + chunk], noise=noise)
+                torch.cuda.synchronize()
+                if i >= warmup:
+                    ms[k].append((time.perf_counter() - t0) * 1e3)
+                samples[k] += a.shape[-1]
+        for k, d in decs.items():
+            samples[k] += d.finish()[0].shape[-1]
+        r = {"audio_samples": samples}
+        for k, v in ms.items():
+            med = statistics.median(v)
+            r[k] = {"median_ms": round(med, 3), "p10_ms": round(pct(v, 0.1), 3), "p90_ms": round(pct(v, 0.9), 3), "n": len(v)}
+            rows.append(f"{B:5d}  {k:12s}  {med:9.3f}  {pct(v, 0.1):9.3f}  {pct(v, 0.9):9.3f}  {len(v):4d}")
+        r["added_median_ms"] = round(r[f"to_{sr}"]["median_ms"] - r["vocoder_rate"]["median_ms"], 3)
+        rows.append(f"{B:5d}  conversion adds {r['added_median_ms']:.3f} ms to the median push ({chunk * 4 * 256} vocoder samples per item)")
+        result["batch"][str(B)] = r
+    table = [f"streaming decode to {sr} Hz, {chunk}-token pushes (2.73 s of audio), 100 mel / 10 groups, BigVGAN base (tools/bench_stream.py --output-sample-rate {sr})",
+             f"per-push wall time incl. host synchronisation, {T4L // chunk - warmup} steady-state pushes, the two decoders interleaved in one process;",
+             "vocoder_rate = output_sample_rate=None (no resampler), the other = a StreamResampler behind the vocoder",
+             "batch  output        median ms     p10 ms     p90 ms     n"] + rows
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "a") as f:
+        f.write("\n".join(table) + "\n\n")
+    print("\n".join(table), file=sys.stderr)
+    print(json.dumps(result))
+
+
+if "--output-sample-rate" in sys.argv:
+    output_rate_section(int(arg_after("--output-sample-rate")),
+                        arg_after("--out", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "stream_resample.txt")))
+    sys.exit(0)
 
 
 def pipeline_section():

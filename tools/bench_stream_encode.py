@@ -7,7 +7,13 @@ The one-launch encoder step and the forced layered step (DMEL_WAVENET_STREAM_FUS
 two encoders fed the same audio, push i of one followed by push i of the other, each push bracketed by a host synchronisation and
 timed on the wall clock (what a microphone loop pays).  Pushes before the stream's steady state (the first `--warmup`: lookahead fill,
 buffer allocation, handle creation) are discarded; medians and the 10th / 90th percentiles are taken over the rest (>= 50).  For
-scale, encode() of the whole clip is timed in the same run.  Prints one JSON line and writes the table to --out."""
+scale, encode() of the whole clip is timed in the same run.  Prints one JSON line and writes the table to --out.
+
+    python tools/bench_stream_encode.py --sample-rate 48000 [--out profiles/stream_resample.txt]
+
+compares, the same way, an encoder fed 0.32 s pushes at the codec's rate (sample_rate=None: no resampler) with one fed 0.32 s pushes of
+the same duration at --sample-rate (a StreamResampler in front: two small copies and one resample launch more per push), and APPENDS its
+table to --out."""
 import argparse, json, os, statistics, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -18,8 +24,12 @@ ap.add_argument("--pushes", type=int, default=62, help="pushes per stream (62 x 
 ap.add_argument("--warmup", type=int, default=8)
 ap.add_argument("--chunk", type=int, default=7680, help="samples per push (0.32 s at 24 kHz)")
 ap.add_argument("--batches", default="1,16")
-ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "stream_encode.txt"))
+ap.add_argument("--sample-rate", type=int, default=None, help="compare pushes at this source rate with pushes at the codec's rate")
+ap.add_argument("--out", default=None)
 args = ap.parse_args()
+if args.out is None:
+    args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                            "stream_resample.txt" if args.sample_rate else "stream_encode.txt")
 assert args.pushes - args.warmup >= 50, "medians over at least 50 steady-state pushes"
 SR = 24000
 dev = torch.device("cuda:0")
@@ -30,6 +40,49 @@ codec = build_codec(sample_rate=SR, n_mels=80, dmel_groups=8, levels=(7, 5, 5), 
 def pct(v, q):
     s = sorted(v)
     return s[min(len(s) - 1, int(q * len(s)))]
+
+
+def resample_section():
+    """codec-rate pushes against pushes at --sample-rate, interleaved; the source clip is noise at the source rate and the codec-rate
+    encoder is fed its resampled form, so both encode the same signal"""
+    from dmel_codec_amd.utils.resample import resample
+    sr = args.sample_rate
+    n_src = args.chunk * sr // SR
+    rows, result = [], {"sample_rate": sr, "chunk_s": args.chunk / SR, "pushes": args.pushes, "warmup": args.warmup, "batch": {}}
+    for B in [int(b) for b in args.batches.split(",")]:
+        src = torch.randn(B, args.pushes * n_src, device=dev) * 0.1
+        at_codec = resample(src, sr, SR)[:, :args.pushes * args.chunk].contiguous()
+        encs = {"codec_rate": codec.streaming_encoder(B), f"from_{sr}": codec.streaming_encoder(B, sample_rate=sr)}
+        feed = {"codec_rate": (at_codec, args.chunk), f"from_{sr}": (src, n_src)}
+        ms = {k: [] for k in encs}
+        tokens = {k: 0 for k in encs}
+        keys = list(encs)
+        for i in range(args.pushes):
+            for k in (keys if i % 2 == 0 else keys[::-1]):                  # neither path always goes first
+                a, n = feed[k]
+                t, ids = timed_push(encs[k], a[:, i * n:(i + 1) * n], False)
+                tokens[k] += ids.shape[2]
+                if i >= args.warmup:
+                    ms[k].append(t)
+        for e in encs.values():
+            e.finish()
+        r = {"tokens": tokens}
+        for k, v in ms.items():
+            med = statistics.median(v)
+            r[k] = {"median_ms": round(med, 3), "p10_ms": round(pct(v, 0.1), 3), "p90_ms": round(pct(v, 0.9), 3), "n": len(v)}
+            rows.append(f"{B:5d}  {k:11s}  {med:9.3f}  {pct(v, 0.1):9.3f}  {pct(v, 0.9):9.3f}  {len(v):4d}")
+        r["added_median_ms"] = round(r[f"from_{sr}"]["median_ms"] - r["codec_rate"]["median_ms"], 3)
+        rows.append(f"{B:5d}  conversion adds {r['added_median_ms']:.3f} ms to the median push ({n_src} source samples -> ~{args.chunk} per item)")
+        result["batch"][str(B)] = r
+    table = [f"streaming encode from {sr} Hz, 0.32 s pushes, 80 mel / 8 groups / 70 channels / 20 layers (tools/bench_stream_encode.py --sample-rate {sr})",
+             f"per-push wall time incl. host synchronisation, {args.pushes - args.warmup} steady-state pushes, the two encoders interleaved in one process;",
+             "codec_rate = sample_rate=None (no resampler), the other = a StreamResampler in front",
+             "batch  input        median ms     p10 ms     p90 ms     n"] + rows
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "a") as f:
+        f.write("\n".join(table) + "\n\n")
+    print("\n".join(table), file=sys.stderr)
+    print(json.dumps(result))
 
 
 def timed_push(enc, chunk, layered):
@@ -43,6 +96,10 @@ def timed_push(enc, chunk, layered):
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) * 1e3, ids
 
+
+if args.sample_rate:
+    resample_section()
+    sys.exit(0)
 
 rows, result = [], {"chunk_samples": args.chunk, "chunk_s": args.chunk / SR, "pushes": args.pushes, "warmup": args.warmup, "batch": {}}
 for B in [int(b) for b in args.batches.split(",")]:
