@@ -55,6 +55,7 @@ PROTOTYPES = {
                                            C.c_int, vp]),
     "dmel_stft_f32": (C.c_int, [vp, vp, C.c_int64, vp, vp, vp, C.c_int, C.c_int64, vp]),
     "dmel_stft_window_f32": (C.c_int, [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, vp]),
+    "dmel_stft_window_items_f32": (C.c_int, [vp, vp, C.c_int64, C.c_int64, i64p, i64p, vp, vp, vp, C.c_int, i64p, i64p, i64p, vp, vp]),
     "dmel_aa_snake_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp]),
     "dmel_aa_snake_backward_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp]),
     "dmel_discriminator_create": (C.c_int, [C.POINTER(vp)]),
@@ -99,6 +100,7 @@ PROTOTYPES = {
     "dmel_wavenet_backward_hooked": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int64, vp, C.c_size_t, vp, GRAD_READY_FN, vp]),
     "dmel_wavenet_stream_step": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int64, i64p, i64p, vp]),
     "dmel_wavenet_stream_step_ex": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int64, i64p, i64p, vp, C.c_int, C.c_int64, vp]),
+    "dmel_wavenet_stream_step_items": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int64, i64p, i64p, vp, C.c_int, i64p, vp]),
     "dmel_wavenet_set_tensor": (C.c_int, [vp, C.c_char_p, vp, i64p, C.c_int]),
     "dmel_wavenet_finalize": (C.c_int, [vp]),
     "dmel_wavenet_workspace_bytes": (C.c_size_t, [vp, C.c_int, C.c_int64]),

@@ -153,6 +153,10 @@ struct TrainPrecisionScope {
   ~TrainPrecisionScope() { train_precision_override() = saved; }
 };
 
+// A small host table (a multiple of 4 bytes) into device memory, in stream order, carried in the ARGUMENTS of tiny launches
+// (small_ops.hip): the host memory is read before the call returns -- which an asynchronous copy from pageable memory does not promise.
+int launch_table_put(const void* host, size_t bytes, void* dst_dev, hipStream_t st);
+
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // Bump allocator over the caller's workspace.

@@ -536,6 +536,33 @@ extern "C" int dmel_wavenet_forward(const dmel_wavenet* m, const float* x, const
 }
 
 // ---- incremental forward (include/dmel_hip.h: dmel_wavenet_stream_step) ----------------------------------------------------
+// The frontier rules of one (prev, next) row; utt >= 0 names the utterance of a per-item table in the message.
+static int stream_row_check(const dmel_wavenet* m, const int64_t* prev, const int64_t* next, int64_t cap, int64_t origin, int utt) {
+  char who[48] = "";
+  if (utt >= 0) std::snprintf(who, sizeof(who), "utterance %d: ", utt);
+  const int L = m->L;
+  const bool final_step = next[L] == next[0];
+  for (int l = 0; l <= L; ++l) {
+    DMEL_CHECK_ARG(prev[l] >= 0 && prev[l] <= next[l] && next[l] <= cap, "wavenet_stream_step: %slevel %d: need 0 <= prev <= next <= cap", who, l);
+    if (l > 0) {
+      const int dil = m->cycle ? 1 << ((l - 1) % m->cycle) : 1;
+      DMEL_CHECK_ARG(final_step ? next[l] == next[0] : (next[l] == prev[l] || next[l] + dil <= next[l - 1]),
+                     "wavenet_stream_step: %slevel %d runs ahead of its input (next %lld, input next %lld, dilation %d)", who, l,
+                     (long long)next[l], (long long)next[l - 1], dil);
+      DMEL_CHECK_ARG(prev[l] <= prev[l - 1], "wavenet_stream_step: %slevel %d is ahead of level %d", who, l, l - 1);
+    }
+  }
+  if (origin > 0) {
+    // column 0 is not the start of the sequence: a window that reaches in front of it would read zero padding where history belongs
+    for (int l = 1; l <= L; ++l) {
+      const int dil = m->cycle ? 1 << ((l - 1) % m->cycle) : 1;
+      DMEL_CHECK_ARG(next[l] == prev[l] || prev[l] >= dil, "wavenet_stream_step: %slevel %d needs history in front of the buffer (origin %lld)",
+                     who, l, (long long)origin);
+    }
+  }
+  return DMEL_OK;
+}
+
 static int wavenet_stream_step_impl(const dmel_wavenet* m, const float* xraw, float* hist, float* skip, const float* cond, float* y,
                                     float* scratch, int N, int64_t cap, const int64_t* prev, const int64_t* next,
                                     const int64_t* out_lengths, int group_repeat, int64_t origin, bool ex, void* stream);
@@ -551,6 +578,30 @@ extern "C" int dmel_wavenet_stream_step_ex(const dmel_wavenet* m, const float* x
   return wavenet_stream_step_impl(m, x, hist, skip, cond, y, scratch, N, cap, prev, next, out_lengths, group_repeat, origin, true, stream);
 }
 
+// per-utterance frontiers (include/dmel_hip.h): every row checked, then the one-launch kernel over all items -- or nothing
+extern "C" int dmel_wavenet_stream_step_items(const dmel_wavenet* m, const float* x, float* hist, float* skip, const float* cond, float* y,
+                                              float* scratch, int N, int64_t cap, const int64_t* prev, const int64_t* next,
+                                              const int64_t* out_lengths, int group_repeat, const int64_t* origin, void* stream) {
+  DMEL_CHECK_ARG(m && hist && skip && y && scratch && prev && next && origin, "wavenet_stream_step_items: NULL argument");
+  if (!m->ready) { set_error("wavenet_stream_step_items: handle not finalized"); return DMEL_EMISSING; }
+  if (m->Ccond || cond || !m->fused.ok || m->L > kStreamMaxL || m->precision != DMEL_PRECISION_FP32 || conv_fp32_mfma_forced()) {
+    set_error("wavenet_stream_step_items: only the stacks of the one-launch kernel are taken (residual channels in (32, 80], no condition, no "
+              "output projection, dilations <= 8, DMEL_PRECISION_FP32); there is no layered per-item step");
+    return DMEL_EUNSUPPORTED;
+  }
+  DMEL_CHECK_ARG(m->has_in == (x != nullptr), "wavenet_stream_step_items: the raw input is given exactly when the model has an input projection");
+  const int div = group_repeat > 0 ? group_repeat : 1;
+  DMEL_CHECK_ARG(N > 0 && cap > 0 && N % div == 0, "wavenet_stream_step_items: bad shape / group_repeat");
+  const int R = N / div, L1 = m->L + 1;
+  for (int r = 0; r < R; ++r) {
+    DMEL_CHECK_ARG(origin[r] >= 0, "wavenet_stream_step_items: utterance %d: negative origin", r);
+    DMEL_TRY(stream_row_check(m, prev + (size_t)r * L1, next + (size_t)r * L1, cap, origin[r], r));
+  }
+  // the table lies behind dmel_wavenet_stream_step_ex's scratch: N * 2 C * cap floats, N int64
+  int32_t* tab = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(scratch) + (size_t)2 * N * m->C * cap * sizeof(float) + (size_t)N * sizeof(int64_t));
+  return launch_wavenet_stream_items(m->fused, x, hist, skip, y, out_lengths, div, N, cap, prev, next, tab, (hipStream_t)stream);
+}
+
 static int wavenet_stream_step_impl(const dmel_wavenet* m, const float* xraw, float* hist, float* skip, const float* cond, float* y,
                                     float* scratch, int N, int64_t cap, const int64_t* prev, const int64_t* next,
                                     const int64_t* out_lengths, int group_repeat, int64_t origin, bool ex, void* stream) {
@@ -563,26 +614,8 @@ static int wavenet_stream_step_impl(const dmel_wavenet* m, const float* xraw, fl
   const int div = group_repeat > 0 ? group_repeat : 1;
   DMEL_CHECK_ARG(origin >= 0 && (!out_lengths || N % div == 0), "wavenet_stream_step: bad origin / group_repeat");
   const int C = m->C, L = m->L;
-  const bool final_step = next[L] == next[0];
-  for (int l = 0; l <= L; ++l) {
-    DMEL_CHECK_ARG(prev[l] >= 0 && prev[l] <= next[l] && next[l] <= cap, "wavenet_stream_step: level %d: need 0 <= prev <= next <= cap", l);
-    if (l > 0) {
-      const int dil = m->cycle ? 1 << ((l - 1) % m->cycle) : 1;
-      DMEL_CHECK_ARG(final_step ? next[l] == next[0] : (next[l] == prev[l] || next[l] + dil <= next[l - 1]),
-                     "wavenet_stream_step: level %d runs ahead of its input (next %lld, input next %lld, dilation %d)", l,
-                     (long long)next[l], (long long)next[l - 1], dil);
-      DMEL_CHECK_ARG(prev[l] <= prev[l - 1], "wavenet_stream_step: level %d is ahead of level %d", l, l - 1);
-    }
-  }
+  DMEL_TRY(stream_row_check(m, prev, next, cap, origin, -1));
   hipStream_t st = (hipStream_t)stream;
-  if (origin > 0) {
-    // column 0 is not the start of the sequence: a window that reaches in front of it would read zero padding where history belongs
-    for (int l = 1; l <= L; ++l) {
-      const int dil = m->cycle ? 1 << ((l - 1) % m->cycle) : 1;
-      DMEL_CHECK_ARG(next[l] == prev[l] || prev[l] >= dil, "wavenet_stream_step: level %d needs history in front of the buffer (origin %lld)", l,
-                     (long long)origin);
-    }
-  }
   if (ex) {  // DMEL_WAVENET_STREAM_FUSED=0 keeps the layered step (A/B); read per call
     const char* e = getenv("DMEL_WAVENET_STREAM_FUSED");
     if (m->fused.ok && L <= kStreamMaxL && m->precision == DMEL_PRECISION_FP32 && !(e && e[0] == '0') && !conv_fp32_mfma_forced())

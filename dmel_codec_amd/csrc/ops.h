@@ -60,6 +60,11 @@ int launch_wavenet_fused(const WaveNetFused& f, const float* x, float* y, const 
 constexpr int kStreamMaxL = 32;
 int launch_wavenet_stream(const WaveNetFused& f, const float* x, float* hist, float* skip, float* y, const int64_t* out_len, int len_div,
                           int N, int64_t cap, const int64_t* prev, const int64_t* next, hipStream_t st);
+// The same step with per-utterance frontiers (dmel_wavenet_stream_step_items): prev / next are host tables of (N / len_div) rows of L + 1
+// entries, already validated; tab_dev holds (N / len_div) * kStreamRowInts(L) int32, rewritten for every sub-step.
+constexpr int kStreamRowInts(int L) { return 2 * (L + 1) + 1; }      // prev[0..L], next[0..L], block count (< 0: the row is idle)
+int launch_wavenet_stream_items(const WaveNetFused& f, const float* x, float* hist, float* skip, float* y, const int64_t* out_len, int len_div,
+                                int N, int64_t cap, const int64_t* prev, const int64_t* next, int32_t* tab_dev, hipStream_t st);
 // out[i] = max(len[i] - shift, 0): lengths relative to the first column of a sub-range launch
 int launch_shift_lengths(const int64_t* len, int64_t shift, int64_t* out, int n, hipStream_t st);
 int launch_aa_snake(const float* x, float* y, const float* alpha, const float* beta, const float* up_taps_host,

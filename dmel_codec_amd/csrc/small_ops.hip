@@ -633,6 +633,32 @@ extern "C" int dmel_collate_peak_f32(const float* const* clips_dev, const int64_
 }
 
 namespace dmel {
+
+// ---- host table -> device memory through launch arguments (common.h: launch_table_put) ------------------------------------------
+constexpr int kPutWords = 448;      // 1792 bytes of the 4 KB an argument block may hold
+struct PutChunk {
+  uint32_t v[kPutWords];
+};
+__global__ __launch_bounds__(kPutWords) void table_put_kernel(PutChunk c, uint32_t* __restrict__ dst, int n) {
+  const int i = threadIdx.x;
+  if (i < n) dst[i] = c.v[i];
+}
+
+int launch_table_put(const void* host, size_t bytes, void* dst_dev, hipStream_t st) {
+  DMEL_CHECK_ARG(host && dst_dev && bytes % 4 == 0, "table_put: bad argument");
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(host);
+  uint32_t* dst = reinterpret_cast<uint32_t*>(dst_dev);
+  for (size_t done = 0, words = bytes / 4; done < words; done += kPutWords) {
+    const int n = (int)std::min<size_t>(kPutWords, words - done);
+    PutChunk c;
+    std::memcpy(c.v, src + done, (size_t)n * 4);
+    std::memset(c.v + n, 0, (size_t)(kPutWords - n) * 4);
+    hipLaunchKernelGGL(table_put_kernel, dim3(1), dim3(kPutWords), 0, st, c, dst + done, n);
+  }
+  DMEL_HIP(hipGetLastError());
+  return DMEL_OK;
+}
+
 }  // namespace dmel
 
 extern "C" int dmel_mask_add_quality_f32(float* z, const int64_t* lengths, const float* w, const float* bias, float value,

@@ -157,14 +157,23 @@ constexpr int kMaxMelW = 2304;   // non-zero mel weights (each FFT bin feeds at 
 // pass 1 is a P-point DFT per lane (+ twiddle W_{N/2}^{k1 n2}); every k1 row then needs a 64-point DFT over n2, done as
 // 8 x 8 with two LDS transposes (passes 2 and 3: P*8 independent 8-point DFTs each, i.e. P/8 per lane; for P = 4 half
 // the lanes idle in those passes).  Output index k = k1 + P (j1 + 8 j2).
-template <int P>
+// ITEMS (dmel_stft_window_items_f32): clip b has a window of its own -- (s0, f0, T, L) are row b of `items`, the launch's T is the
+// widest item's and only the row pitch of the outputs.  Only where a workgroup finds its window differs; a frame's arithmetic does not.
+template <int P, bool ITEMS>
 #if DMEL_STFT_WPE
 __attribute__((amdgpu_waves_per_eu(DMEL_STFT_WPE, DMEL_STFT_WPE)))
 #endif
 __global__ __launch_bounds__(kThreads) void stft_logmel_kernel(StftTables tb, const float* __restrict__ audio,
                                                           int64_t row_stride, const int64_t* __restrict__ lengths,
                                                           float* __restrict__ out, float* __restrict__ linear, int64_t L, int64_t T,
-                                                          int hop, int pad, int n_mels, int mel_passes, int64_t s0, int64_t f0) {
+                                                          int hop, int pad, int n_mels, int mel_passes, int64_t s0, int64_t f0,
+                                                          const int64_t* __restrict__ items) {
+  const int64_t Tpitch = T;                       // columns of an output row
+  if constexpr (ITEMS) {
+    const int64_t* it = items + 4 * (int64_t)blockIdx.y;      // the same four words for every thread of the workgroup
+    s0 = it[0]; f0 = it[1]; T = it[2]; L = it[3];
+    if ((int64_t)blockIdx.x * kFramesPerWG >= T) return;      // workgroup-uniform, before any barrier: no frame of this item here
+  }
   constexpr int H = 64 * P, N = 128 * P, U = (P + 7) / 8, EX = P * 72, NR = P / 2 + 1;
   extern __shared__ __attribute__((aligned(16))) float smem_stft[];
 #ifndef DMEL_STFT_LDS_PAD
@@ -306,7 +315,7 @@ __global__ __launch_bounds__(kThreads) void stft_logmel_kernel(StftTables tb, co
     wave_sync();
     // ---- optional linear-magnitude output, frame-major (B, T, H + 1): one coalesced row per frame (multi-resolution STFT loss)
     if (linear) {
-      float* lo = linear + ((int64_t)b * T + t) * (H + 1);
+      float* lo = linear + ((int64_t)b * Tpitch + t) * (H + 1);
       for (int k = lane; k <= H; k += 64) lo[k] = mg[k];
     }
     // ---- mel: chunk partial sums (ascending-bin fma chains, weights from LDS) into the free exchange buffer, then per band the
@@ -338,11 +347,11 @@ __global__ __launch_bounds__(kThreads) void stft_logmel_kernel(StftTables tb, co
   __syncthreads();
   if (!out) return;
   const int64_t n_valid = lengths ? lengths[b] / hop : f0 + T;      // in absolute frames
-  float* o = out + (int64_t)b * n_mels * T;
+  float* o = out + (int64_t)b * n_mels * Tpitch;
   for (int idx = tid; idx < n_mels * kFramesPerWG; idx += kThreads) {
     const int m = idx / kFramesPerWG, f = idx % kFramesPerWG;
     const int64_t t = t0 + f;
-    if (t < T) o[(int64_t)m * T + t] = (f0 + t < n_valid) ? tile[m][f] : 0.f;
+    if (t < T) o[(int64_t)m * Tpitch + t] = (f0 + t < n_valid) ? tile[m][f] : 0.f;
   }
 }
 
@@ -459,8 +468,11 @@ extern "C" int dmel_stft_plan_create(dmel_stft_plan** out, int sample_rate, int 
     for (int k = 0; k < cnt[m]; ++k) packed.push_back(p->basis[(size_t)m * nb + st[m] + k]);
   }
   {  // the n_fft = 2048 instantiation needs 78 KB of dynamic LDS: raise the per-kernel limit (default 64 KB)
-    hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&stft_logmel_kernel<16>),
+    hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&stft_logmel_kernel<16, false>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)stft_lds_bytes<16>());
+    if (e1 == hipSuccess)
+      e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&stft_logmel_kernel<16, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)stft_lds_bytes<16>());
     if (e1 != hipSuccess && P == 16) {
       set_error("stft_logmel: cannot reserve %zu bytes of LDS: %s", stft_lds_bytes<16>(), hipGetErrorString(e1));
       delete p;
@@ -553,10 +565,10 @@ extern "C" int dmel_stft_set_exclusive_cu(int on) {
   g_exclusive_cu.store(on ? 1 : 0);
   return DMEL_OK;
 }
-template <int P> static size_t stft_launch_lds(const dmel_stft_plan* p) {
+template <int P, bool ITEMS> static size_t stft_launch_lds(const dmel_stft_plan* p) {
   const size_t need = stft_lds_bytes<P>(p->mel_passes, DMEL_STFT_FULL_TILE ? kMaxMels : p->n_mels);
   if (!g_exclusive_cu.load()) return need;
-  static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&stft_logmel_kernel<P>), hipFuncAttributeMaxDynamicSharedMemorySize,
+  static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&stft_logmel_kernel<P, ITEMS>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                              (int)kExclusiveLds) == hipSuccess;
   return ok ? std::max(need, kExclusiveLds) : need;
 }
@@ -567,32 +579,34 @@ extern "C" int dmel_stft_logmel_f32(const dmel_stft_plan* p, const float* audio,
   return dmel_stft_f32(p, audio, row_stride, lengths, out, nullptr, B, L, stream);
 }
 
-// one launch over `T` frames starting at absolute frame f0 of a signal of L samples, x[0] = absolute sample s0
-static int stft_launch(const dmel_stft_plan* p, const float* audio, int64_t row_stride, const int64_t* lengths, float* out, float* linear,
-                       int B, int64_t L, int64_t T, int64_t s0, int64_t f0, int64_t samples, void* stream) {
+// one launch over `T` frames starting at absolute frame f0 of a signal of L samples, x[0] = absolute sample s0; with `items` (device,
+// B x (s0, f0, T, L)) every clip has its own window and T is the widest
+template <bool ITEMS>
+static int stft_launch_t(const dmel_stft_plan* p, const float* audio, int64_t row_stride, const int64_t* lengths, float* out, float* linear,
+                         int B, int64_t L, int64_t T, int64_t s0, int64_t f0, double samples, const int64_t* items, void* stream) {
   StftTables tb{p->winz.as<cf>(), p->tw1.as<cf>(), p->tw2.as<cf>(), p->twr.as<cf>(), p->mel_start.as<int>(),
                 p->mel_cnt.as<int>(), p->mel_ptr.as<int>(), p->mel_w.as<float>(), p->ch_k0.as<int>(), p->ch_w.as<float>(),
                 p->band_pbeg.as<int>(), p->band_pcnt.as<int>()};
   dim3 grid((unsigned)((T + kFramesPerWG - 1) / kFramesPerWG), (unsigned)B);
   hipStream_t s = (hipStream_t)stream;
   {
-    ProfScope ps("stft_logmel", s, 0.0, (double)B * (4.0 * (double)samples + 4.0 * p->n_mels * (double)T));
+    ProfScope ps("stft_logmel", s, 0.0, (double)B * (4.0 * samples + 4.0 * p->n_mels * (double)T));
+    auto go = [&](auto kernel, size_t lds) {
+      hipLaunchKernelGGL(kernel, grid, dim3(kThreads), lds, s, tb, audio, row_stride, lengths, out, linear, L, T, p->hop, p->pad, p->n_mels,
+                         p->mel_passes, s0, f0, items);
+    };
     switch (p->n_fft) {
-      case 512:
-        hipLaunchKernelGGL(stft_logmel_kernel<4>, grid, dim3(kThreads), stft_launch_lds<4>(p), s, tb, audio, row_stride, lengths, out,
-                           linear, L, T, p->hop, p->pad, p->n_mels, p->mel_passes, s0, f0);
-        break;
-      case 1024:
-        hipLaunchKernelGGL(stft_logmel_kernel<8>, grid, dim3(kThreads), stft_launch_lds<8>(p), s, tb, audio, row_stride, lengths, out,
-                           linear, L, T, p->hop, p->pad, p->n_mels, p->mel_passes, s0, f0);
-        break;
-      default:
-        hipLaunchKernelGGL(stft_logmel_kernel<16>, grid, dim3(kThreads), stft_launch_lds<16>(p), s, tb, audio, row_stride, lengths,
-                           out, linear, L, T, p->hop, p->pad, p->n_mels, p->mel_passes, s0, f0);
+      case 512: go(&stft_logmel_kernel<4, ITEMS>, stft_launch_lds<4, ITEMS>(p)); break;
+      case 1024: go(&stft_logmel_kernel<8, ITEMS>, stft_launch_lds<8, ITEMS>(p)); break;
+      default: go(&stft_logmel_kernel<16, ITEMS>, stft_launch_lds<16, ITEMS>(p));
     }
   }
   DMEL_HIP(hipGetLastError());
   return DMEL_OK;
+}
+static int stft_launch(const dmel_stft_plan* p, const float* audio, int64_t row_stride, const int64_t* lengths, float* out, float* linear,
+                       int B, int64_t L, int64_t T, int64_t s0, int64_t f0, int64_t samples, void* stream) {
+  return stft_launch_t<false>(p, audio, row_stride, lengths, out, linear, B, L, T, s0, f0, (double)samples, nullptr, stream);
 }
 
 extern "C" int dmel_stft_f32(const dmel_stft_plan* p, const float* audio, int64_t row_stride, const int64_t* lengths, float* out,
@@ -608,19 +622,17 @@ extern "C" int dmel_stft_f32(const dmel_stft_plan* p, const float* audio, int64_
 }
 
 // ---- frames of a window of a longer signal (include/dmel_hip.h: dmel_stft_window_f32) ---------------------------------------------
-extern "C" int dmel_stft_window_f32(const dmel_stft_plan* p, const float* audio, int64_t row_stride, int64_t n_samples, int64_t s0,
-                                    const int64_t* lengths, float* out, float* linear, int B, int64_t first_frame, int64_t n_frames,
-                                    int64_t total_length, void* stream) {
-  DMEL_CHECK_ARG(p && audio && (out || linear), "NULL argument");
-  DMEL_CHECK_ARG(B > 0 && B <= 65535, "batch %d out of range", B);
-  DMEL_CHECK_ARG(n_samples > 0 && row_stride >= n_samples && s0 >= 0 && first_frame >= 0 && n_frames > 0, "stft_window: bad window");
+// the window rules for one buffer [s0, s0 + n_samples); *L_out: the signal length the kernel reflects at.  who: "" or "item b: "
+static int stft_window_check(const dmel_stft_plan* p, int64_t n_samples, int64_t s0, int64_t first_frame, int64_t n_frames,
+                             int64_t total_length, const char* who, int64_t* L_out) {
+  DMEL_CHECK_ARG(n_samples > 0 && s0 >= 0 && first_frame >= 0 && n_frames > 0, "stft_window: %sbad window", who);
   const bool known = total_length >= 0;
   const int N = p->n_fft, pad = p->pad, hop = p->hop;
   const int64_t have_end = s0 + n_samples;                 // the buffer holds absolute samples [s0, have_end)
   if (known) {
-    DMEL_CHECK_ARG(total_length > pad, "clip length %lld must exceed the reflect pad %d", (long long)total_length, pad);
-    DMEL_CHECK_ARG(have_end <= total_length, "stft_window: the buffer runs past the end of the signal");
-    DMEL_CHECK_ARG(first_frame + n_frames <= dmel_stft_num_frames(p, total_length), "stft_window: frames past the last frame of the signal");
+    DMEL_CHECK_ARG(total_length > pad, "%sclip length %lld must exceed the reflect pad %d", who, (long long)total_length, pad);
+    DMEL_CHECK_ARG(have_end <= total_length, "stft_window: %sthe buffer runs past the end of the signal", who);
+    DMEL_CHECK_ARG(first_frame + n_frames <= dmel_stft_num_frames(p, total_length), "stft_window: %sframes past the last frame of the signal", who);
   }
   const int64_t L = known ? total_length : ((int64_t)1 << 62);
   // every sample the frames read, reflections included, must lie in the buffer
@@ -628,7 +640,48 @@ extern "C" int dmel_stft_window_f32(const dmel_stft_plan* p, const float* audio,
   int64_t lo = std::max<int64_t>(first_start, 0), hi = std::min(last_end, L);
   if (first_start < 0) hi = std::max(hi, std::min<int64_t>(L, (int64_t)pad + 1));      // left reflection reads samples 1 .. pad
   if (last_end > L) lo = std::min(lo, std::max<int64_t>(0, 2 * (L - 1) - (last_end - 1)));   // right reflection reads back from L - 2
-  DMEL_CHECK_ARG(s0 <= lo && hi <= have_end, "stft_window: frames [%lld, %lld) read samples [%lld, %lld), the buffer holds [%lld, %lld)",
+  DMEL_CHECK_ARG(s0 <= lo && hi <= have_end, "stft_window: %sframes [%lld, %lld) read samples [%lld, %lld), the buffer holds [%lld, %lld)", who,
                  (long long)first_frame, (long long)(first_frame + n_frames), (long long)lo, (long long)hi, (long long)s0, (long long)have_end);
+  *L_out = L;
+  return DMEL_OK;
+}
+
+extern "C" int dmel_stft_window_f32(const dmel_stft_plan* p, const float* audio, int64_t row_stride, int64_t n_samples, int64_t s0,
+                                    const int64_t* lengths, float* out, float* linear, int B, int64_t first_frame, int64_t n_frames,
+                                    int64_t total_length, void* stream) {
+  DMEL_CHECK_ARG(p && audio && (out || linear), "NULL argument");
+  DMEL_CHECK_ARG(B > 0 && B <= 65535, "batch %d out of range", B);
+  DMEL_CHECK_ARG(row_stride >= n_samples, "stft_window: bad window");
+  int64_t L;
+  DMEL_TRY(stft_window_check(p, n_samples, s0, first_frame, n_frames, total_length, "", &L));
   return stft_launch(p, audio, row_stride, lengths, out, linear, B, L, n_frames, s0, first_frame, n_samples, stream);
+}
+
+// ---- the same for B independent streams (include/dmel_hip.h: dmel_stft_window_items_f32) -----------------------------------------
+extern "C" int dmel_stft_window_items_f32(const dmel_stft_plan* p, const float* audio, int64_t row_stride, int64_t n_samples,
+                                          const int64_t* s0, const int64_t* n_valid, const int64_t* lengths, float* out, float* linear, int B,
+                                          const int64_t* first_frame, const int64_t* n_frames, const int64_t* total_length,
+                                          int64_t* table_scratch, void* stream) {
+  DMEL_CHECK_ARG(p && audio && (out || linear) && s0 && first_frame && n_frames && total_length && table_scratch, "NULL argument");
+  DMEL_CHECK_ARG(B > 0 && B <= 65535, "batch %d out of range", B);
+  DMEL_CHECK_ARG(n_samples > 0 && row_stride >= n_samples, "stft_window_items: bad buffer width");
+  std::vector<int64_t> tab((size_t)4 * B, 0);       // (s0, f0, T, L) per item; an idle item keeps T = 0
+  int64_t Tmax = 0;
+  double samples = 0.0;
+  for (int b = 0; b < B; ++b) {
+    DMEL_CHECK_ARG(n_frames[b] >= 0, "stft_window_items: item %d: negative frame count", b);
+    if (n_frames[b] == 0) continue;
+    const int64_t have = n_valid ? n_valid[b] : n_samples;
+    DMEL_CHECK_ARG(have <= n_samples, "stft_window_items: item %d: %lld valid samples in a buffer of %lld", b, (long long)have, (long long)n_samples);
+    char who[32];
+    std::snprintf(who, sizeof(who), "item %d: ", b);
+    int64_t L;
+    DMEL_TRY(stft_window_check(p, have, s0[b], first_frame[b], n_frames[b], total_length[b], who, &L));
+    tab[4 * b] = s0[b]; tab[4 * b + 1] = first_frame[b]; tab[4 * b + 2] = n_frames[b]; tab[4 * b + 3] = L;
+    Tmax = std::max(Tmax, n_frames[b]);
+    samples += (double)have;
+  }
+  if (Tmax == 0) return DMEL_OK;                    // every item idle
+  DMEL_TRY(launch_table_put(tab.data(), tab.size() * sizeof(int64_t), table_scratch, (hipStream_t)stream));
+  return stft_launch_t<true>(p, audio, row_stride, lengths, out, linear, B, 0, Tmax, 0, 0, samples / B, table_scratch, stream);
 }

@@ -19,6 +19,10 @@
 //     output mask in the store.
 // Eligibility = that of the whole-sequence kernel (residual channels <= 80, no condition, no output projection, dilations <= 8) and at
 // most 96 new columns per level per launch; a larger push is cut into consecutive sub-steps by the host code below.
+//
+// Nothing above needs the items of a launch to agree on their frontiers: a workgroup only ever touches its own item.  The per-item form
+// (dmel_wavenet_stream_step_items: independent live sessions in one launch) is the same kernel body reading prev / next / the block count
+// from its utterance's row of a device table instead of the launch arguments; a row that has nothing to do leaves before the first barrier.
 #include "ops.h"
 
 namespace dmel {
@@ -51,6 +55,8 @@ struct StreamArgs {
   const void* const* rs_w;
   const float* const* rs_b;
   int prev[kStreamMaxL + 1], next[kStreamMaxL + 1];
+  // per-item form (dmel_wavenet_stream_step_items): row n / len_div of `tab` replaces prev / next / nblk for workgroup n
+  const int32_t* tab;        // (N / len_div, kStreamRowInts(L)): prev[0..L] | next[0..L] | block count, < 0 = idle row
 };
 
 __device__ __forceinline__ uint32_t s_pack_hi16(float lo, float hi) {
@@ -86,8 +92,11 @@ __device__ __forceinline__ void s_split8_store(const float (&v)[8], uint4* d0, u
   *d2 = make_uint4(p3[0], p3[1], p3[2], p3[3]);
 }
 
-// NCH = 16-channel chunks of the residual width (C <= 16 NCH); NG = 2 NCH eight-channel groups
-template <int NCH>
+// NCH = 16-channel chunks of the residual width (C <= 16 NCH); NG = 2 NCH eight-channel groups.
+// ITEMS: the frontiers are this workgroup's row of a.tab instead of the launch's a.prev / a.next / a.nblk.  Every thread reads the row at
+// the same addresses and nothing writes the table while the kernel runs, so whatever is derived from it -- the idle early-out, the
+// block count, every trip count around a barrier -- is uniform across the workgroup; readfirstlane keeps the values in scalar registers.
+template <int NCH, bool ITEMS>
 __global__ __launch_bounds__(192 * NCH) void wavenet_stream_kernel(StreamArgs a) {
   constexpr int NG = 2 * NCH, CP = 16 * NCH, NW = 3 * NCH, NTHR = 64 * NW;
   constexpr int GS = 3 * NCH, RS = NCH, LS = GS + RS;             // K steps of the gated conv, of the projection, per block
@@ -100,6 +109,20 @@ __global__ __launch_bounds__(192 * NCH) void wavenet_stream_kernel(StreamArgs a)
   const int wave = wv / 3, nb = wv - 3 * wave;          // row tile, column block of this wave
   const int q = nb * 32 + l31;                          // this lane's column of the launch's new columns
   const int n = blockIdx.x, C = a.C;
+  const int32_t* row = ITEMS ? a.tab + (size_t)(n / a.len_div) * kStreamRowInts(a.L) : nullptr;
+  auto PREV = [&](int l) -> int {
+    if constexpr (ITEMS) return __builtin_amdgcn_readfirstlane(row[l]);
+    else return a.prev[l];
+  };
+  auto NEXT = [&](int l) -> int {
+    if constexpr (ITEMS) return __builtin_amdgcn_readfirstlane(row[a.L + 1 + l]);
+    else return a.next[l];
+  };
+  int nblk = a.nblk;
+  if constexpr (ITEMS) {
+    nblk = __builtin_amdgcn_readfirstlane(row[2 * (a.L + 1)]);
+    if (nblk < 0) return;                               // idle item: before the first barrier, nothing is written
+  }
   const int64_t cap = a.cap;
   const int64_t item = (int64_t)n * C * cap, lvl = (int64_t)a.N * C * cap;
   const int olim = a.out_len ? (int)min(a.out_len[n / a.len_div], (int64_t)0x7fffffff) : 0x7fffffff;
@@ -135,8 +158,8 @@ __global__ __launch_bounds__(192 * NCH) void wavenet_stream_kernel(StreamArgs a)
   };
 
   // ---- level 0: silu(input_projection(x)) on its new columns [prev[0], next[0])       (wavenet.py:205-207)
-  if (a.has_in && a.next[0] > a.prev[0]) {
-    const int p0 = a.prev[0], W0 = a.next[0] - p0;
+  if (a.has_in && NEXT(0) > PREV(0)) {
+    const int p0 = PREV(0), W0 = NEXT(0) - p0;
     const float* xin = a.x + (int64_t)n * a.Cin * cap + p0;
     for (int i = tid; i < 2 * kST; i += NTHR) {          // raw input (<= 16 channels: one chunk) into Zp groups 0..1
       const int g = i / kST, qq = i - g * kST;
@@ -183,12 +206,12 @@ __global__ __launch_bounds__(192 * NCH) void wavenet_stream_kernel(StreamArgs a)
 #pragma unroll
   for (int d = 0; d < kSPD; ++d) fetch(wa[d], 0, d);
 
-  for (int blk = 0; blk < a.nblk; ++blk) {
+  for (int blk = 0; blk < nblk; ++blk) {
     const int dil = a.cycle ? 1 << (blk % a.cycle) : 1;
     const float* gb = a.gate_b[blk];
     const float* rb = a.rs_b[blk];
-    const int p = a.prev[blk + 1], W = a.next[blk + 1] - p;    // new columns [p, p + W) of level blk + 1
-    const int valid = a.next[blk];                              // level blk holds columns [0, valid)
+    const int p = PREV(blk + 1), W = NEXT(blk + 1) - p;        // new columns [p, p + W) of level blk + 1
+    const int valid = NEXT(blk);                                // level blk holds columns [0, valid)
     // Only the 32-column blocks that hold new columns are computed (a 30-frame push: one of three); `active` is uniform per wave and
     // mma_step contains no barrier.  The window is staged as far as the active waves read it.
     const bool active = nb * 32 < W;
@@ -268,7 +291,7 @@ __global__ __launch_bounds__(192 * NCH) void wavenet_stream_kernel(StreamArgs a)
   }
 
   // ---- skip_projection(sum of skips / sqrt(L)) on the columns whose sum is complete      (wavenet.py:218-219), masked store
-  const int pL = a.prev[a.L], WL = a.next[a.L] - pL;
+  const int pL = PREV(a.L), WL = NEXT(a.L) - pL;
   if (WL <= 0) return;
   {
     const float* sb = a.skip + item + pL;
@@ -305,16 +328,16 @@ __global__ __launch_bounds__(192 * NCH) void wavenet_stream_kernel(StreamArgs a)
   }
 }
 
-template <int NCH> int launch_stream_t(const StreamArgs& a, hipStream_t st) {
+template <int NCH, bool ITEMS> int launch_stream_t(const StreamArgs& a, hipStream_t st) {
   constexpr int NG = 2 * NCH, CP = 16 * NCH;
   constexpr size_t lds = (size_t)3 * NG * (kSXS + kST) * 16 + (size_t)CP * kST * 4;
   static bool raised = false;
   if (!raised && lds > 64 * 1024) {
-    DMEL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wavenet_stream_kernel<NCH>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    DMEL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wavenet_stream_kernel<NCH, ITEMS>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)lds));
     raised = true;
   }
-  hipLaunchKernelGGL(wavenet_stream_kernel<NCH>, dim3((unsigned)a.N), dim3(192 * NCH), lds, st, a);
+  hipLaunchKernelGGL((wavenet_stream_kernel<NCH, ITEMS>), dim3((unsigned)a.N), dim3(192 * NCH), lds, st, a);
   DMEL_HIP(hipGetLastError());
   return DMEL_OK;
 }
@@ -332,9 +355,29 @@ int launch_shift_lengths(const int64_t* len, int64_t shift, int64_t* out, int n,
   return DMEL_OK;
 }
 
-int launch_wavenet_stream(const WaveNetFused& f, const float* x, float* hist, float* skip, float* y, const int64_t* out_len, int len_div,
-                          int N, int64_t cap, const int64_t* prev, const int64_t* next, hipStream_t st) {
-  StreamArgs a{};
+// One sub-step of one row of frontiers: from cur[] towards next[], at most kST new columns per level.  A level may only run up to
+// `dilation` columns behind its input's frontier -- unless that frontier is the end of the sequence (final step: next[l] == next[0] for
+// every l), where the zero padding is real.  mid[]: the frontiers after the sub-step; *nblk: blocks 0 .. *nblk - 1 have new columns.
+// Returns whether any level advances.
+static bool stream_substep(const WaveNetFused& f, const int64_t* next, const int64_t* cur, int64_t* mid, int* nblk) {
+  const bool final_step = next[f.L] == next[0];
+  const int64_t total = next[0];
+  bool any = false;
+  *nblk = 0;
+  for (int l = 0; l <= f.L; ++l) {
+    int64_t lim = std::min(next[l], cur[l] + kST);
+    if (l > 0) {
+      const int dil = f.cycle ? 1 << ((l - 1) % f.cycle) : 1;
+      lim = std::min(lim, (final_step && mid[l - 1] == total) ? total : mid[l - 1] - dil);
+    }
+    mid[l] = std::max(cur[l], lim);
+    if (mid[l] > cur[l]) { any = true; if (l > 0) *nblk = l; }
+  }
+  return any;
+}
+
+static int stream_args(StreamArgs& a, const WaveNetFused& f, const float* x, float* hist, float* skip, float* y, const int64_t* out_len,
+                       int len_div, int N, int64_t cap) {
   a.x = x; a.hist = hist; a.skip = skip; a.y = y; a.out_len = out_len; a.len_div = len_div > 0 ? len_div : 1;
   a.N = N; a.Cin = f.Cin; a.C = f.C; a.L = f.L; a.cycle = f.cycle; a.has_in = f.has_in; a.cap = cap;
   a.skip_scale = f.skip_scale;
@@ -344,48 +387,100 @@ int launch_wavenet_stream(const WaveNetFused& f, const float* x, float* hist, fl
   a.rs_w = reinterpret_cast<const void* const*>(reinterpret_cast<const char*>(f.table.p) + (size_t)2 * f.L * sizeof(void*));
   a.rs_b = reinterpret_cast<const float* const*>(reinterpret_cast<const char*>(f.table.p) + (size_t)3 * f.L * sizeof(void*));
   if (f.L > kStreamMaxL || cap >= ((int64_t)1 << 30)) { set_error("wavenet_stream: %d blocks / %lld columns out of range", f.L, (long long)cap); return DMEL_EUNSUPPORTED; }
-  // Cut the step into sub-steps of at most kST new columns per level.  A level may only run up to `dilation` columns behind its input's
-  // frontier -- unless that frontier is the end of the sequence (final step: next[l] == next[0] for every l), where the zero padding is real.
-  const bool final_step = next[f.L] == next[0];
-  const int64_t total = next[0];
+  return DMEL_OK;
+}
+
+template <bool ITEMS> static int launch_stream(const StreamArgs& a, hipStream_t st) {
+  switch ((a.C + 15) / 16) {
+    case 5: return launch_stream_t<5, ITEMS>(a, st);
+    case 4: return launch_stream_t<4, ITEMS>(a, st);
+    case 3: return launch_stream_t<3, ITEMS>(a, st);
+    // not reachable: WaveNetFused::ok (modules.hip, the caller's condition) admits 32 < C <= 80 only, i.e. nch 3 .. 5
+    default: set_error("wavenet_stream: %d channels not instantiated", a.C); return DMEL_EUNSUPPORTED;
+  }
+}
+
+// algorithmic flops / bytes of one item advancing from cur[] to mid[]
+static void stream_cost(const WaveNetFused& f, const int64_t* cur, const int64_t* mid, double* flops, double* bytes) {
+  int64_t cols = 0;
+  for (int l = 1; l <= f.L; ++l) cols += mid[l] - cur[l];
+  *flops = 2.0 * ((double)cols * (2.0 * f.C * 3 * f.C + 2.0 * f.C * f.C) + (double)(mid[f.L] - cur[f.L]) * f.C * f.C +
+                  (f.has_in ? (double)(mid[0] - cur[0]) * f.C * f.Cin : 0.0));
+  *bytes = 4.0 * (double)f.C * (3.0 * cols + 2.0 * kSH * f.L);
+}
+
+int launch_wavenet_stream(const WaveNetFused& f, const float* x, float* hist, float* skip, float* y, const int64_t* out_len, int len_div,
+                          int N, int64_t cap, const int64_t* prev, const int64_t* next, hipStream_t st) {
+  StreamArgs a{};
+  DMEL_TRY(stream_args(a, f, x, hist, skip, y, out_len, len_div, N, cap));
+  // Cut the step into sub-steps of at most kST new columns per level.
   int64_t cur[kStreamMaxL + 1];
   for (int l = 0; l <= f.L; ++l) cur[l] = prev[l];
-  const int nch = (f.C + 15) / 16;
   for (;;) {
-    bool any = false;
     int64_t mid[kStreamMaxL + 1];
-    a.nblk = 0;
-    for (int l = 0; l <= f.L; ++l) {
-      int64_t lim = std::min(next[l], cur[l] + kST);
-      if (l > 0) {
-        const int dil = f.cycle ? 1 << ((l - 1) % f.cycle) : 1;
-        lim = std::min(lim, (final_step && mid[l - 1] == total) ? total : mid[l - 1] - dil);
-      }
-      mid[l] = std::max(cur[l], lim);
-      if (mid[l] > cur[l]) { any = true; if (l > 0) a.nblk = l; }
-      a.prev[l] = (int)cur[l]; a.next[l] = (int)mid[l];
-    }
-    if (!any) break;
-    int64_t cols = 0;
-    for (int l = 1; l <= f.L; ++l) cols += mid[l] - cur[l];
-    const double flops = 2.0 * N * ((double)cols * (2.0 * f.C * 3 * f.C + 2.0 * f.C * f.C) + (double)(mid[f.L] - cur[f.L]) * f.C * f.C +
-                                    (f.has_in ? (double)(mid[0] - cur[0]) * f.C * f.Cin : 0.0));
+    if (!stream_substep(f, next, cur, mid, &a.nblk)) break;
+    for (int l = 0; l <= f.L; ++l) { a.prev[l] = (int)cur[l]; a.next[l] = (int)mid[l]; }
+    double flops, bytes;
+    stream_cost(f, cur, mid, &flops, &bytes);
     {
-      ProfScope ps("conv_igemm", st, flops, 4.0 * N * (double)f.C * (3.0 * cols + 2.0 * kSH * f.L), 6.0 * flops);
-      int rc;
-      switch (nch) {
-        case 5: rc = launch_stream_t<5>(a, st); break;
-        case 4: rc = launch_stream_t<4>(a, st); break;
-        case 3: rc = launch_stream_t<3>(a, st); break;
-        // not reachable: WaveNetFused::ok (modules.hip, the caller's condition) admits 32 < C <= 80 only, i.e. nch 3 .. 5
-        default: set_error("wavenet_stream: %d channels not instantiated", f.C); return DMEL_EUNSUPPORTED;
-      }
-      if (rc) return rc;
+      ProfScope ps("conv_igemm", st, N * flops, N * bytes, 6.0 * N * flops);
+      DMEL_TRY(launch_stream<false>(a, st));
     }
     for (int l = 0; l <= f.L; ++l) cur[l] = mid[l];
   }
   for (int l = 0; l <= f.L; ++l)
     if (cur[l] != next[l]) { set_error("wavenet_stream: level %d cannot reach %lld from %lld", l, (long long)next[l], (long long)cur[l]); return DMEL_EINVAL; }
+  return DMEL_OK;
+}
+
+// Per-utterance rows.  All sub-steps are planned on the host first -- a row that cannot reach its frontiers is refused before anything is
+// launched -- then every sub-step is one table upload (launch arguments: the host tables are not read after this returns) and one launch
+// over all N items; a row that is done is marked idle.  Launches on one stream run in order, so the one table is rewritten in place.
+int launch_wavenet_stream_items(const WaveNetFused& f, const float* x, float* hist, float* skip, float* y, const int64_t* out_len, int len_div,
+                                int N, int64_t cap, const int64_t* prev, const int64_t* next, int32_t* tab_dev, hipStream_t st) {
+  StreamArgs a{};
+  DMEL_TRY(stream_args(a, f, x, hist, skip, y, out_len, len_div, N, cap));
+  a.tab = tab_dev;
+  const int R = N / a.len_div, L1 = f.L + 1, RI = kStreamRowInts(f.L);
+  std::vector<int64_t> cur(prev, prev + (size_t)R * L1);
+  std::vector<int32_t> plan;                 // sub-step major: R rows of RI ints each
+  std::vector<double> cost;                  // flops, bytes per sub-step, summed over the rows (x len_div items)
+  for (;;) {
+    bool any = false;
+    const size_t base = plan.size();
+    plan.resize(base + (size_t)R * RI);
+    double fl = 0.0, by = 0.0;
+    for (int r = 0; r < R; ++r) {
+      int64_t mid[kStreamMaxL + 1];
+      int nblk;
+      int64_t* c = cur.data() + (size_t)r * L1;
+      int32_t* t = plan.data() + base + (size_t)r * RI;
+      const bool adv = stream_substep(f, next + (size_t)r * L1, c, mid, &nblk);
+      for (int l = 0; l < L1; ++l) { t[l] = (int32_t)c[l]; t[L1 + l] = (int32_t)(adv ? mid[l] : c[l]); }
+      t[2 * L1] = adv ? nblk : -1;
+      if (!adv) continue;
+      any = true;
+      double f1, b1;
+      stream_cost(f, c, mid, &f1, &b1);
+      fl += a.len_div * f1; by += a.len_div * b1;
+      for (int l = 0; l < L1; ++l) c[l] = mid[l];
+    }
+    if (!any) { plan.resize(base); break; }
+    cost.push_back(fl); cost.push_back(by);
+  }
+  for (int r = 0; r < R; ++r)
+    for (int l = 0; l < L1; ++l)
+      if (cur[(size_t)r * L1 + l] != next[(size_t)r * L1 + l]) {
+        set_error("wavenet_stream: utterance %d: level %d cannot reach %lld from %lld", r, l, (long long)next[(size_t)r * L1 + l],
+                  (long long)cur[(size_t)r * L1 + l]);
+        return DMEL_EINVAL;
+      }
+  const size_t steps = plan.size() / ((size_t)R * RI);
+  for (size_t s = 0; s < steps; ++s) {
+    DMEL_TRY(launch_table_put(plan.data() + s * R * RI, (size_t)R * RI * sizeof(int32_t), tab_dev, st));
+    ProfScope ps("conv_igemm", st, cost[2 * s], cost[2 * s + 1], 6.0 * cost[2 * s]);
+    DMEL_TRY(launch_stream<true>(a, st));
+  }
   return DMEL_OK;
 }
 

@@ -399,6 +399,14 @@ class VQGAN(nn.Module):
         if ids.shape[-1]:
             yield ids
 
+    def encode_sessions(self, slots: int, max_push_samples: int = 7680, sample_rate: Optional[int] = None):
+        """A pool of `slots` INDEPENDENT incremental encodes served by one streaming step: sessions open, receive their own number of
+        samples per step (at most max_push_samples), stall and close on their own -- what streaming_encoder(batch=B), B streams in
+        lockstep, cannot do -- and each one's concatenated ids are the bits of encode() on its own clip.  One STFT launch and one encoder
+        launch per step whatever the number of slots.  Codec rate only; see models/stream_sessions.py: EncodeSessions."""
+        from .stream_sessions import EncodeSessions
+        return EncodeSessions(self, slots, max_push_samples, sample_rate)
+
     # ------------------------------------------------------------------------------ decode side
     @torch.no_grad()
     def get_quantized_features_from_indices(self, indices, feature_lengths):

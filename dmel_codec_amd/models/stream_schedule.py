@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple
+from typing import List, Mapping, Optional, Sequence, Tuple
 
 
 def quantizer_context(downsample_factor: Sequence[int], dw_kernel: int = 7) -> Tuple[int, int]:
@@ -131,6 +131,30 @@ class EncodeSchedule:
         self.frames, self.levels, self.tokens = f_new, nxt, j_new
         self.finished = final
         return st
+
+
+def session_rows(slots: int, steps: Mapping[int, EncodeStep], origins: Sequence[int]) -> Tuple[List[int], List[int], List[int]]:
+    """A pool of independent streams (EncodeSessions) holds one EncodeSchedule per slot; one step of the pool hands the encoder one
+    (prev, next) row per slot (dmel_wavenet_stream_step_items).  steps: slot -> this step's EncodeStep of every slot that takes part;
+    origins[slot]: the absolute frame in column 0 of that slot's buffers.  Returns (prev, next, origin): prev / next are `slots` rows of
+    L + 1 frontiers, flattened row-major and relative to the slot's own origin; origin has one entry per slot.  A slot without a step is
+    idle: a row of zeros (next == prev on every level), origin 0."""
+    if not steps:
+        raise ValueError("no step to make rows of")
+    width = len(next(iter(steps.values())).prev)
+    prev, nxt, org = [0] * (slots * width), [0] * (slots * width), [0] * slots
+    for slot, st in steps.items():
+        if not 0 <= slot < slots:
+            raise ValueError(f"slot {slot} out of range")
+        if len(st.prev) != width or len(st.next) != width:
+            raise ValueError("steps of different depth")
+        o = origins[slot]
+        if o < 0 or o > min(st.prev):
+            raise ValueError(f"slot {slot}: origin {o} is behind a frontier that is still in use")
+        prev[slot * width:(slot + 1) * width] = [p - o for p in st.prev]
+        nxt[slot * width:(slot + 1) * width] = [p - o for p in st.next]
+        org[slot] = o
+    return prev, nxt, org
 
 
 # ---------------------------------------------------------------------------------------------------- streaming sample-rate conversion

@@ -1,0 +1,273 @@
+"""A pool of independent live encode sessions served by ONE streaming step (VQGAN.encode_sessions).
+
+StreamingEncoder(batch=B) is B streams in lockstep: one schedule, one origin, one (prev, next) row.  Microphones do not behave like that:
+they start, stall and hang up on their own.  EncodeSessions keeps one EncodeSchedule, one origin and one sample tail PER SLOT and hands
+the kernels one row per slot (dmel_stft_window_items_f32, dmel_wavenet_stream_step_items), so that any subset of the slots advances, each
+by its own number of samples, in one STFT launch and one encoder launch."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, Iterable, List, Mapping, Optional
+
+import torch
+
+from .. import _lib
+from .stream_schedule import EncodeGeometry, EncodeSchedule, session_rows
+
+
+class EncodeSessions:
+    """`slots` independent incremental encodes, each with the ids of encode() on its own finished clip.
+
+        slot = pool.open()                                   # a free slot, fresh state
+        ids = pool.push({slot: audio_1d, ...}, final=())     # one step for any subset of the open slots -> {slot: ids (G, m) int32}
+        ids = pool.close(slot)                               # = push({slot: empty}, final=(slot,))[slot]
+
+    Every named slot gets its own number of samples (0 is allowed, more than `max_push_samples` is refused); slots that are not named are
+    idle in the step.  A slot in `final` ends with these samples: the step returns its remaining tokens, computed with the true end of
+    its signal (reflection, zero padding, the floor of T // 4), and frees the slot.  The lookahead of StreamingEncoder applies per slot.
+
+    Per step: one STFT launch over the new frames of all slots, one encoder step over the new columns of every level of all slots, and
+    the quantiser once per group of slots whose feature windows have the same length and the same finality (a final slot's window ends at
+    the true end of its signal and must not be right-padded into a longer batch) -- in steady state with equal pushes, one call.
+
+    State: buffers of (slots * G, C, cap) laid out like StreamingEncoder's, `cap` fixed at construction from `max_push_samples`; each slot
+    has its own origin (the absolute frame in column 0 of ITS rows), its own s0 and sample tail; re-basing shifts one slot's columns
+    only.  Memory grows neither with the length of a stream nor with the number of sessions served over time.
+
+    Only the codec's own sample rate, and only encoders the one-launch streaming kernel takes (residual channels in (32, 80], no
+    condition, no output projection, dilations <= 8, fp32): anything else is refused at construction.
+
+    All launches are on the current stream, so nothing new meets DESIGN section 7's unexplained wrong-frame behaviour of the STFT next to
+    convolutions.  The warning of StreamingEncoder stands: a caller that runs sessions next to convolutions on ANOTHER STREAM of the same
+    process -- a streaming decode, for example -- must call dmel_stft_set_exclusive_cu(1) first, exactly as pipeline.CodecLanes does."""
+
+    def __init__(self, codec, slots: int, max_push_samples: int = 7680, sample_rate: Optional[int] = None):
+        enc, tr = codec.encoder, codec.encode_mel_transform
+        if sample_rate is not None and int(sample_rate) != int(tr.sample_rate):
+            raise NotImplementedError(f"sessions run at the codec's own rate ({tr.sample_rate} Hz); resample in front (StreamResampler)")
+        if int(slots) <= 0 or int(max_push_samples) <= 0:
+            raise ValueError("slots and max_push_samples must be positive")
+        L, Cres = len(enc.residual_layers), enc.residual_channels
+        cycle = enc.dilation_cycle or 0
+        why = None
+        if enc.condition_channels or enc.output_projection is not None:
+            why = "it is conditioned or has an output projection"
+        elif not 32 < Cres <= 80:
+            why = f"{Cres} residual channels are outside (32, 80]"
+        elif cycle > 4:
+            why = f"dilation cycle {cycle} reaches dilations above 8"
+        elif enc.input_projection is not None and enc.input_channels > 16:
+            why = f"{enc.input_channels} input channels exceed 16"
+        elif L > 32:
+            why = f"{L} blocks exceed 32"
+        elif getattr(enc, "_precision", 0):
+            why = "its precision is not fp32"
+        if why:
+            raise NotImplementedError(f"encode sessions need an encoder the one-launch streaming kernel takes: {why}")
+        self.codec, self.S, self.G = codec, int(slots), codec.dmel_groups
+        self.L, self.C = L, Cres
+        dils = tuple(2 ** (i % cycle) if cycle else 1 for i in range(L))
+        self.maxdil = max(dils)
+        self.geo = EncodeGeometry(hop=tr.hop_length, n_fft=tr.n_fft, dilations=dils,
+                                  downsample_factor=tuple(codec.quantizer.downsample_factor))
+        self.n_mels = tr.n_mels
+        self.max_push = int(max_push_samples)
+        g = self.geo
+        left, right = g.quant_context
+        F = g.factor
+        # Columns a slot holds: from the oldest one a later step reads -- the quantiser's left context in front of the next token, which
+        # lies at most `hold` frames behind the newest frame -- to the newest frame of a push (+ 1 for the hop's remainder, + the frames
+        # only the end of the signal releases).  Twice that, so that a slot is re-based once in several pushes and not in every one.
+        hold = g.encoder_context + right + 1 + F * ((left + F - 1) // F) + F
+        self.want_max = hold + self.max_push // g.hop + 1 + (g.n_fft - g.pad + g.hop - 1) // g.hop
+        self.cap = (2 * self.want_max + 31) // 32 * 32
+        self.width = g.n_fft + self.max_push          # samples per row: a tail is shorter than one window
+        self.sched: List[Optional[EncodeSchedule]] = [None] * self.S
+        self.origin = [0] * self.S
+        self.s0 = [0] * self.S
+        self.tail = [0] * self.S                      # valid samples in the slot's row
+        self._fresh = [False] * self.S                # opened, state not zeroed yet (done with the slot's first push)
+        self.buf = None
+
+    # -- bookkeeping (no device call) ------------------------------------------------------------------------------------
+    @property
+    def capacity(self) -> int:
+        """columns of the state buffers (frames); fixed at construction"""
+        return self.cap
+
+    @property
+    def open_slots(self) -> List[int]:
+        return [s for s in range(self.S) if self.sched[s] is not None]
+
+    def allocated_bytes(self) -> int:
+        return 0 if self.buf is None else sum(t.numel() * t.element_size() for t in self.buf.values())
+
+    def tokens_emitted(self, slot: int) -> int:
+        self._check_open(slot)
+        return self.sched[slot].tokens
+
+    def open(self) -> int:
+        """take a free slot: fresh schedule, state zeroed before its first push.  Raises when every slot is taken."""
+        for s in range(self.S):
+            if self.sched[s] is None:
+                self.sched[s] = EncodeSchedule(self.geo)
+                self.origin[s] = self.s0[s] = self.tail[s] = 0
+                self._fresh[s] = True
+                return s
+        raise RuntimeError(f"all {self.S} slots are taken")
+
+    def _check_open(self, slot) -> None:
+        if not isinstance(slot, int) or not 0 <= slot < self.S:
+            raise ValueError(f"slot {slot!r} out of range (0 .. {self.S - 1})")
+        if self.sched[slot] is None:
+            raise RuntimeError(f"slot {slot} is not open")
+
+    def _validate(self, audio: Mapping[int, torch.Tensor], final) -> Dict[int, torch.Tensor]:
+        """everything that can be refused, before any state changes and before any device call"""
+        if not audio:
+            raise ValueError("push needs at least one slot")
+        out = {}
+        for slot, a in audio.items():
+            self._check_open(slot)
+            if a.ndim == 2 and a.shape[0] == 1:
+                a = a[0]
+            if a.ndim != 1:
+                raise ValueError(f"slot {slot}: expected mono audio (n,) or (1, n), got {tuple(a.shape)}")
+            if a.shape[0] > self.max_push:
+                raise ValueError(f"slot {slot}: a push of {a.shape[0]} samples exceeds max_push_samples = {self.max_push}")
+            out[slot] = a
+        for slot in final:
+            if slot not in audio:
+                raise ValueError(f"slot {slot} is in `final` but not among the pushed slots")
+            total = self.sched[slot].samples + out[slot].shape[0]
+            if total <= self.geo.pad:
+                raise ValueError(f"slot {slot}: the stream is {total} samples long: encode() needs more than the reflect pad {self.geo.pad}")
+        for slot, a in out.items():
+            _lib.require_cuda(a, "audio")
+        return out
+
+    # -- buffers -----------------------------------------------------------------------------------------------------------
+    def _allocate(self, dev) -> None:
+        N = self.S * self.G
+        rows = self.S * (2 * (self.L + 1) + 1)
+        self.buf = dict(mel=torch.zeros(self.S, self.n_mels, self.cap, dtype=torch.float32, device=dev),
+                        hist=torch.zeros(self.L + 1, N, self.C, self.cap, dtype=torch.float32, device=dev),
+                        skip=torch.zeros(N, self.C, self.cap, dtype=torch.float32, device=dev),
+                        feat=torch.zeros(N, self.C, self.cap, dtype=torch.float32, device=dev),
+                        samples=torch.zeros(self.S, self.width, dtype=torch.float32, device=dev),
+                        # dmel_wavenet_stream_step_items: the scratch of _ex (2 N C cap floats, N int64) and the row table behind it
+                        scratch=torch.empty(2 * N * self.C * self.cap + 2 * N + rows, dtype=torch.float32, device=dev),
+                        stft_tab=torch.empty(4 * self.S, dtype=torch.int64, device=dev))
+
+    def _slot_views(self, s: int):
+        b, G = self.buf, self.G
+        return (b["mel"][s], b["hist"][:, s * G:(s + 1) * G], b["skip"][s * G:(s + 1) * G], b["feat"][s * G:(s + 1) * G])
+
+    def _rebase(self, s: int, st) -> None:
+        """make room for the frames of step `st` in slot s: drop the columns nothing reads again and shift that slot's rows"""
+        if st.frames[1] - self.origin[s] <= self.cap:
+            return
+        need_from = max(0, min(st.prev[self.L] - self.maxdil, st.quant_window[0]))
+        shift, keep = need_from - self.origin[s], max(0, st.frames[0] - need_from)
+        if st.frames[1] - need_from > self.cap:       # cannot happen: cap covers twice the widest window (want_max)
+            raise RuntimeError(f"slot {s}: {st.frames[1] - need_from} columns do not fit the capacity {self.cap}")
+        for v in self._slot_views(s):
+            v[..., :keep] = v[..., shift:shift + keep].clone()
+        self.origin[s] = need_from
+
+    # -- one step ----------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def push(self, audio: Mapping[int, torch.Tensor], final: Iterable[int] = ()) -> Dict[int, torch.Tensor]:
+        """audio: {slot: (n,) samples, n >= 0}; final: slots that end with these samples -> {slot: ids (G, m) int32, m >= 0}"""
+        final = set(final)
+        audio = self._validate(audio, final)
+        codec, geo, G, S = self.codec, self.geo, self.G, self.S
+        dev = next(iter(audio.values())).device
+        if self.buf is None:
+            self._allocate(dev)
+        b = self.buf
+        steps = {}
+        for s, a in audio.items():
+            if self._fresh[s]:
+                for v in self._slot_views(s):
+                    v.zero_()
+                self._fresh[s] = False
+            n = a.shape[0]
+            if n:
+                b["samples"][s, self.tail[s]:self.tail[s] + n] = a
+                self.tail[s] += n
+            steps[s] = self.sched[s].step(n, s in final)
+        lib = _lib.lib()
+        I64 = C.c_int64 * S
+        with torch.cuda.device(dev):
+            # ---- STFT: the new frames of every slot, each from its own sample tail
+            n_frames = [0] * S
+            for s, st in steps.items():
+                if st.frames[1] > 0:
+                    self._rebase(s, st)
+                n_frames[s] = st.frames[1] - st.frames[0]
+            tmax = max(n_frames)
+            if tmax:
+                from ..torch_ops import _stft_plan
+                sp = codec.encode_mel_transform.spectrogram
+                plan = _stft_plan(dev, sp.sample_rate, sp.n_fft, sp.win_length, sp.hop_length, sp.num_mels, float(sp.f_min or 0.0),
+                                  float(sp.f_max) if sp.f_max else 0.0)
+                mel = torch.empty(S, self.n_mels, tmax, dtype=torch.float32, device=dev)
+                first = [steps[s].frames[0] if s in steps else 0 for s in range(S)]
+                total = [steps[s].total_length if s in steps else -1 for s in range(S)]
+                _lib.check(lib.dmel_stft_window_items_f32(plan, b["samples"].data_ptr(), self.width, self.width, I64(*self.s0), I64(*self.tail),
+                                                          None, mel.data_ptr(), None, S, I64(*first), I64(*n_frames), I64(*total),
+                                                          b["stft_tab"].data_ptr(), _lib.stream_ptr()), "stft_window_items")
+                for s, st in steps.items():
+                    f0, f1 = st.frames
+                    if f1 > f0:
+                        o = self.origin[s]
+                        b["mel"][s, :, f0 - o:f1 - o] = mel[s, :, :f1 - f0]
+                        drop = max(0, f1 * geo.hop - geo.pad) - self.s0[s]
+                        if drop > 0:
+                            keep = self.tail[s] - drop
+                            row = b["samples"][s]
+                            row[:keep] = row[drop:drop + keep] if drop >= keep else row[drop:drop + keep].clone()
+                            self.s0[s], self.tail[s] = self.s0[s] + drop, keep
+            # ---- encoder WaveNet: every level of every slot advances to its own new frontier
+            if any(st.next != st.prev for st in steps.values()):
+                prev, nxt, org = session_rows(S, steps, self.origin)
+                rows = C.c_int64 * (S * (self.L + 1))
+                x = b["mel"].data_ptr() if codec.encoder.input_projection is not None else None
+                if x is None:
+                    for s, st in steps.items():
+                        o = self.origin[s]
+                        b["hist"][0][s * G:(s + 1) * G, :, st.prev[0] - o:st.next[0] - o] = \
+                            b["mel"][s].view(G, -1, self.cap)[:, :, st.prev[0] - o:st.next[0] - o]
+                _lib.check(lib.dmel_wavenet_stream_step_items(codec.encoder.native(), x, b["hist"].data_ptr(), b["skip"].data_ptr(), None,
+                                                              b["feat"].data_ptr(), b["scratch"].data_ptr(), S * G, self.cap, rows(*prev),
+                                                              rows(*nxt), None, G, I64(*org), _lib.stream_ptr()),
+                           "wavenet_stream_step_items")
+            # ---- quantiser: once per group of slots with equal window length and equal finality, cropped per slot
+            out: Dict[int, torch.Tensor] = {}
+            groups: Dict[tuple, List[int]] = {}
+            for s, st in steps.items():
+                if st.tokens[1] > st.tokens[0]:
+                    groups.setdefault((st.quant_window[1] - st.quant_window[0], st.final), []).append(s)
+                else:
+                    out[s] = torch.empty(G, 0, dtype=torch.int32, device=dev)
+            for (_, _), members in groups.items():
+                wins = []
+                for s in members:
+                    lo, hi = steps[s].quant_window
+                    o = self.origin[s]
+                    wins.append(b["feat"][s * G:(s + 1) * G, :, lo - o:hi - o])
+                ids = codec.quantizer.encode(torch.cat(wins, dim=0).to(codec.encode_dtype).contiguous())
+                for i, s in enumerate(members):
+                    st = steps[s]
+                    j = st.quant_window[0] // geo.factor
+                    out[s] = ids[i, :, st.tokens[0] - j:st.tokens[1] - j].contiguous()
+        for s in final:
+            self.sched[s] = None          # the slot is free; its rows are zeroed when it is opened and pushed to again
+        return out
+
+    def close(self, slot: int) -> torch.Tensor:
+        """no more audio for this slot: its remaining tokens, and the slot is free"""
+        self._check_open(slot)
+        dev = self.buf["samples"].device if self.buf is not None else next(self.codec.parameters()).device
+        return self.push({slot: torch.empty(0, dtype=torch.float32, device=dev)}, final=(slot,))[slot]

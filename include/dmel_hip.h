@@ -121,6 +121,20 @@ int dmel_stft_f32(const dmel_stft_plan* plan, const float* audio, int64_t audio_
 int dmel_stft_window_f32(const dmel_stft_plan* plan, const float* audio, int64_t audio_row_stride, int64_t n_samples, int64_t s0,
                          const int64_t* lengths, float* logmel_out /*nullable*/, float* linear_out /*nullable*/, int B,
                          int64_t first_frame, int64_t n_frames, int64_t total_length, void* stream);
+/* The same launch for B INDEPENDENT streams (a pool of live encode sessions: every microphone starts, stalls and ends on its own):
+ * s0, n_valid, first_frame, n_frames, total_length are HOST tables of B entries.  audio (B, n_samples) is one buffer width; row b holds
+ * the absolute samples [s0[b], s0[b] + n_valid[b]) of stream b, n_valid[b] <= n_samples (n_valid == NULL: n_samples for every item).
+ * Item b's frames [first_frame[b], first_frame[b] + n_frames[b]) go to the first n_frames[b] columns of its rows of logmel_out
+ * (B, n_mels, Tmax) / linear_out (B, Tmax, n_fft/2 + 1), Tmax = max n_frames; the columns behind them are NOT written.  n_frames[b] == 0
+ * is an idle item: nothing of it is read or written (and nothing is launched when every item is idle).  Every item is checked by the
+ * rules of dmel_stft_window_f32 against its own [s0[b], s0[b] + n_valid[b]); a failure is DMEL_EINVAL, names the item, and nothing is
+ * launched.  Same kernel body, same per-frame arithmetic: a frame has the bits dmel_stft_window_f32 gives it.  lengths: device, as above.
+ * table_scratch: device memory for 4 B int64 (the per-item windows as the kernel reads them).  The host tables are copied as launch
+ * arguments: the caller may overwrite them as soon as the call returns.  dmel_stft_set_exclusive_cu applies as to every STFT launch. */
+int dmel_stft_window_items_f32(const dmel_stft_plan* plan, const float* audio, int64_t audio_row_stride, int64_t n_samples,
+                               const int64_t* s0, const int64_t* n_valid /*nullable*/, const int64_t* lengths /*nullable*/,
+                               float* logmel_out /*nullable*/, float* linear_out /*nullable*/, int B, const int64_t* first_frame,
+                               const int64_t* n_frames, const int64_t* total_length, int64_t* table_scratch, void* stream);
 
 /* Backward of the linear magnitudes of dmel_stft_f32 -- what turns the multi-resolution STFT loss BASELINE.json's north_star names into a
  * LOSS (the reference has neither; its STFT framing is utils/spectrogram.py:58-76).  grad_linear (B, T, n_fft/2 + 1) = dL/d|S|, frame-major
@@ -288,6 +302,22 @@ int dmel_wavenet_stream_step(const dmel_wavenet* m, float* hist, float* skip, co
 int dmel_wavenet_stream_step_ex(const dmel_wavenet* m, const float* x /*nullable*/, float* hist, float* skip, const float* cond /*nullable*/,
                                 float* y, float* scratch, int N, int64_t cap, const int64_t* prev, const int64_t* next,
                                 const int64_t* out_lengths /*nullable*/, int group_repeat, int64_t origin, void* stream);
+/* The same step with PER-UTTERANCE frontiers -- independent live sessions in one launch: item n belongs to utterance n / group_repeat
+ * (N % group_repeat == 0), and prev, next (N / group_repeat, L + 1) and origin (N / group_repeat) are HOST tables with one row per
+ * utterance, each in the window coordinates of that utterance's own column 0; out_lengths stays per utterance and relative to that
+ * column 0.  A row with next == prev on every level is an IDLE item: its workgroups write nothing to hist, skip or y.  Every row is
+ * checked on the host by the rules of dmel_wavenet_stream_step_ex (frontier order, no window in front of an origin > 0, ranges within
+ * cap); a bad row is DMEL_EINVAL, dmel_last_error names the utterance, and nothing is launched.  A row may carry any number of new
+ * columns: the step is cut into sub-steps of at most 96 new columns per level, as many as the longest row needs, and a row that is done
+ * early is idle in the later ones.  Only the stacks of the one-launch kernel are taken (residual channels in (32, 80], no condition, no
+ * output projection, dilations <= 8, DMEL_PRECISION_FP32): everything else is DMEL_EUNSUPPORTED -- there is no layered per-item step.
+ *   scratch: that of dmel_wavenet_stream_step_ex (N * 2 C * cap floats followed by N int64) FOLLOWED BY
+ *     (N / group_repeat) * (2 (L + 1) + 1) int32: the rows of a sub-step as the kernel reads them.
+ * The host tables are copied as launch arguments: the caller may overwrite them as soon as the call returns.  Every item has the bits
+ * dmel_wavenet_stream_step_ex gives it when it is stepped alone (same kernel body, same K order, same epilogues). */
+int dmel_wavenet_stream_step_items(const dmel_wavenet* m, const float* x /*nullable*/, float* hist, float* skip, const float* cond /*NULL*/,
+                                   float* y, float* scratch, int N, int64_t cap, const int64_t* prev, const int64_t* next,
+                                   const int64_t* out_lengths /*nullable*/, int group_repeat, const int64_t* origin, void* stream);
 
 /* ConvNeXtBlock (models/modules/firefly.py:337-402; C-ABI row `convnext_block`), standalone: y = x + gamma * pwconv2(gelu(pwconv1(
  * LayerNorm_C(dwconv7(x))))), x / y (N, dim, T).  set_tensor keys: dwconv.weight (dim,1,7), dwconv.bias, norm.weight, norm.bias,

@@ -77,6 +77,58 @@ static void wavenet(int Cin, int Cout, int C, int L, int cycle, int Cc, int N, i
     for (int l = 0; l <= L; ++l) next[l] = 230;
     CK(dmel_wavenet_stream_step(m, hist.data(), skip.data(), Cc ? cond.data() : nullptr, yy.data(), sc.data(), N, cap, prev.data(), next.data(), nullptr));
   }
+  if (Cin != C && Cout == C && !Cc && C > 32 && C <= 80) {   // encoder side: the step with an input projection, lockstep and per utterance
+    const int64_t cap = 256;
+    const int G = 2, R = N / G, L1 = L + 1;
+    auto xr = buf((size_t)N * Cin * cap), hist = buf((size_t)L1 * N * C * cap), skip = buf((size_t)N * C * cap), yy = buf((size_t)N * C * cap);
+    // the scratch of _ex (2 N C cap floats, N int64) followed by the row table of _items ((N / G) * (2 (L + 1) + 1) int32), exactly
+    std::vector<float> sc((size_t)2 * N * C * cap + 2 * N + (size_t)R * (2 * L1 + 1));
+    std::vector<int64_t> prev(L1, 0), next(L1), lens(R, 190);
+    next[0] = 200;
+    for (int l = 1; l <= L; ++l) next[l] = std::max<int64_t>(0, next[l - 1] - (cycle ? 1 << ((l - 1) % cycle) : 1));
+    CK(dmel_wavenet_stream_step_ex(m, xr.data(), hist.data(), skip.data(), nullptr, yy.data(), sc.data(), N, cap, prev.data(), next.data(),
+                                   lens.data(), G, 0, nullptr));
+    // rows: 0 mid-stream over several sub-steps, 1 final, 2 idle, the rest mid-stream behind an origin
+    std::vector<int64_t> P((size_t)R * L1), Q((size_t)R * L1), O(R, 0);
+    for (int r = 0; r < R; ++r)
+      for (int l = 0; l <= L; ++l) {
+        const int64_t p = next[l], q = r == 1 ? 230 : r == 2 ? p : r == 0 ? p : p + 20;
+        P[(size_t)r * L1 + l] = r == 0 ? 0 : p;
+        Q[(size_t)r * L1 + l] = q;
+        if (r > 2) O[r] = 7;
+      }
+    auto items = [&]() {
+      return dmel_wavenet_stream_step_items(m, xr.data(), hist.data(), skip.data(), nullptr, yy.data(), sc.data(), N, cap, P.data(), Q.data(),
+                                            lens.data(), G, O.data(), nullptr);
+    };
+    CK(items());
+    auto refused = [&](const char* what, const char* names) {
+      const int rc = items();
+      if (rc != DMEL_EINVAL || !std::strstr(dmel_last_error(), names)) { std::printf("FAIL stream_step_items accepted %s (%d: %s)\n", what, rc, dmel_last_error()); ++failures; }
+    };
+    const auto Q0 = Q;
+    if (L >= 2) { Q[(size_t)1 * L1 + 2] = 229; refused("a final row with a level short of the end", "utterance 1"); Q = Q0; }
+    Q[(size_t)(R - 1) * L1] = cap + 1; refused("a row past the capacity", R == 2 ? "utterance 1" : "utterance"); Q = Q0;
+    if (R > 3) {
+      const auto P0 = P;
+      for (int l = 0; l <= L; ++l) { Q[(size_t)3 * L1 + l] -= P[(size_t)3 * L1 + L]; P[(size_t)3 * L1 + l] -= P0[(size_t)3 * L1 + L]; }
+      refused("a window in front of an origin > 0", "utterance 3");
+      P = P0; Q = Q0;
+    }
+    O[0] = -1; refused("a negative origin", "utterance 0"); O[0] = 0;
+    if (dmel_wavenet_stream_step_items(m, xr.data(), hist.data(), skip.data(), nullptr, yy.data(), sc.data(), N + 1, cap, P.data(), Q.data(),
+                                       lens.data(), G, O.data(), nullptr) != DMEL_EINVAL) { std::printf("FAIL stream_step_items accepted N %% group_repeat != 0\n"); ++failures; }
+  } else if (Cin == C) {   // stacks outside the one-launch kernel have no per-item step
+    const int64_t cap = 64;
+    auto hist = buf((size_t)(L + 1) * N * C * cap), skip = buf((size_t)N * C * cap), cond = buf((size_t)N * (Cc ? Cc : 1) * cap),
+         yy = buf((size_t)N * Cout * cap), sc = buf((size_t)2 * N * C * cap + 2 * N + (size_t)N * (2 * L + 3));
+    std::vector<int64_t> z((size_t)N * (L + 1), 0), o(N, 0);
+    if ((Cc || Cout != C || C > 80) &&
+        dmel_wavenet_stream_step_items(m, nullptr, hist.data(), skip.data(), Cc ? cond.data() : nullptr, yy.data(), sc.data(), N, cap, z.data(),
+                                       z.data(), nullptr, 1, o.data(), nullptr) != DMEL_EUNSUPPORTED) {
+      std::printf("FAIL stream_step_items took a stack outside the one-launch kernel\n"); ++failures;
+    }
+  }
   dmel_wavenet_destroy(m);
 }
 
@@ -269,6 +321,28 @@ int main() {
     auto mel = buf((size_t)B * 128 * T), lin = buf((size_t)B * T * (nfft / 2 + 1));
     CK(dmel_stft_logmel_f32(p, a.data(), L, nullptr, mel.data(), B, L, nullptr));
     CK(dmel_stft_f32(p, a.data(), L, nullptr, nullptr, lin.data(), B, L, nullptr));
+    {   // windows of longer signals: one for the whole batch, then one per item
+      const int hop = nfft / 4, pad = (nfft - hop) / 2;
+      const int64_t f0 = 6, nf = 7, s0 = f0 * hop - pad, n = (f0 + nf - 1) * hop - pad + nfft - s0;
+      CK(dmel_stft_window_f32(p, a.data(), L, n, s0, nullptr, mel.data(), nullptr, B, f0, nf, -1, nullptr));
+      // item 0: the head of a stream (left reflection), its row only partly valid; item 1: the tail of a signal of 9000 samples
+      const int64_t Lt = 9000, Tt = dmel_stft_num_frames(p, Lt);
+      int64_t S0[2] = {0, (Tt - 3) * hop - pad}, F0[2] = {0, Tt - 3}, NF[2] = {5, 3}, TL[2] = {-1, Lt};
+      int64_t NV[2] = {4 * hop - pad + nfft, Lt - S0[1]};
+      const int64_t width = std::max(NV[0], NV[1]);
+      std::vector<int64_t> tab(8);      // exactly the 4 B int64 the header asks for
+      CK(dmel_stft_window_items_f32(p, a.data(), L, width, S0, NV, nullptr, mel.data(), lin.data(), B, F0, NF, TL, tab.data(), nullptr));
+      NF[0] = 0;                        // an idle item
+      CK(dmel_stft_window_items_f32(p, a.data(), L, width, S0, NV, nullptr, mel.data(), nullptr, B, F0, NF, TL, tab.data(), nullptr));
+      NF[0] = 5; NV[0] -= 1;            // item 0's last frame reads a sample its row does not hold
+      int rc = dmel_stft_window_items_f32(p, a.data(), L, width, S0, NV, nullptr, mel.data(), nullptr, B, F0, NF, TL, tab.data(), nullptr);
+      if (rc != DMEL_EINVAL || !std::strstr(dmel_last_error(), "item 0")) { std::printf("FAIL stft_window_items accepted a row that misses a sample (%d: %s)\n", rc, dmel_last_error()); ++failures; }
+      NV[0] += 1; NF[1] = 4;            // item 1: a frame past the last frame of its signal
+      rc = dmel_stft_window_items_f32(p, a.data(), L, width, S0, NV, nullptr, mel.data(), nullptr, B, F0, NF, TL, tab.data(), nullptr);
+      if (rc != DMEL_EINVAL || !std::strstr(dmel_last_error(), "item 1")) { std::printf("FAIL stft_window_items accepted frames past the end (%d: %s)\n", rc, dmel_last_error()); ++failures; }
+      NF[1] = 3; NV[1] = width + 1;     // more valid samples than the buffer is wide
+      if (dmel_stft_window_items_f32(p, a.data(), L, width, S0, NV, nullptr, mel.data(), nullptr, B, F0, NF, TL, tab.data(), nullptr) != DMEL_EINVAL) { std::printf("FAIL stft_window_items accepted n_valid > n_samples\n"); ++failures; }
+    }
     std::vector<float> basis((size_t)128 * (nfft / 2 + 1));
     CK(dmel_stft_plan_mel_basis(p, basis.data()));
     dmel_stft_plan_destroy(p);

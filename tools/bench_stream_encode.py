@@ -13,7 +13,14 @@ scale, encode() of the whole clip is timed in the same run.  Prints one JSON lin
 
 compares, the same way, an encoder fed 0.32 s pushes at the codec's rate (sample_rate=None: no resampler) with one fed 0.32 s pushes of
 the same duration at --sample-rate (a StreamResampler in front: two small copies and one resample launch more per push), and APPENDS its
-table to --out."""
+table to --out.
+
+    python tools/bench_stream_encode.py --sessions 16 [--out profiles/stream_sessions.txt]
+
+times a steady-state step of S independent sessions (VQGAN.encode_sessions: one STFT launch and one encoder launch for all of them)
+whose starts are offset by a third of a push, so that no two frontiers agree, against what there was for the same job before: S
+StreamingEncoder(batch=1) fed the same audio and stepped one after another.  Both run interleaved in one process; a "step" is one push
+for every stream, bracketed by a host synchronisation.  APPENDS its table to --out."""
 import argparse, json, os, statistics, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -25,11 +32,12 @@ ap.add_argument("--warmup", type=int, default=8)
 ap.add_argument("--chunk", type=int, default=7680, help="samples per push (0.32 s at 24 kHz)")
 ap.add_argument("--batches", default="1,16")
 ap.add_argument("--sample-rate", type=int, default=None, help="compare pushes at this source rate with pushes at the codec's rate")
+ap.add_argument("--sessions", type=int, default=0, help="time a step of this many staggered independent sessions")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 if args.out is None:
     args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                            "stream_resample.txt" if args.sample_rate else "stream_encode.txt")
+                            "stream_sessions.txt" if args.sessions else "stream_resample.txt" if args.sample_rate else "stream_encode.txt")
 assert args.pushes - args.warmup >= 50, "medians over at least 50 steady-state pushes"
 SR = 24000
 dev = torch.device("cuda:0")
@@ -97,6 +105,63 @@ def timed_push(enc, chunk, layered):
     return (time.perf_counter() - t0) * 1e3, ids
 
 
+def sessions_section():
+    """S staggered sessions in one pool against S batch-1 encoders stepped in turn; the same audio, the same pushes, equal ids"""
+    S, n = args.sessions, args.chunk
+    audio = torch.randn(S, (args.pushes + 1) * n, device=dev) * 0.1
+    pool = codec.encode_sessions(slots=S, max_push_samples=n)
+    slots = [pool.open() for _ in range(S)]
+    singles = [codec.streaming_encoder(1) for _ in range(S)]
+    pos = [0] * S
+    first = [n * (1 + s % 3) // 3 for s in range(S)]            # the starts differ by a third of a push
+    ms = {"sessions": [], "one_by_one": []}
+    same, tokens = True, 0
+    for i in range(args.pushes):
+        size = first if i == 0 else [n] * S
+        chunks = [audio[s, pos[s]:pos[s] + size[s]] for s in range(S)]
+        pos = [p + k for p, k in zip(pos, size)]
+        got = {}
+        for k in (("sessions", "one_by_one") if i % 2 == 0 else ("one_by_one", "sessions")):      # neither always goes first
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if k == "sessions":
+                ids = pool.push({slots[s]: chunks[s] for s in range(S)})
+                got[k] = [ids[slots[s]] for s in range(S)]
+            else:
+                got[k] = [singles[s].push(chunks[s][None])[0] for s in range(S)]
+            torch.cuda.synchronize()
+            if i >= args.warmup:
+                ms[k].append((time.perf_counter() - t0) * 1e3)
+        same = same and all(torch.equal(a, b) for a, b in zip(got["sessions"], got["one_by_one"]))
+        tokens += sum(a.shape[1] for a in got["sessions"])
+    for s in range(S):
+        pool.close(slots[s])
+        singles[s].finish()
+    r = {"sessions": S, "chunk_s": n / SR, "pushes": args.pushes, "warmup": args.warmup, "ids_equal": bool(same), "tokens": tokens}
+    rows = []
+    for k, v in ms.items():
+        med = statistics.median(v)
+        r[k] = {"median_ms": round(med, 3), "p10_ms": round(pct(v, 0.1), 3), "p90_ms": round(pct(v, 0.9), 3), "n": len(v),
+                "audio_s_per_s": round(S * n / SR / (med / 1e3), 1)}
+        rows.append(f"{S:8d}  {k:10s}  {med:9.3f}  {pct(v, 0.1):9.3f}  {pct(v, 0.9):9.3f}  {r[k]['audio_s_per_s']:11.1f}  {len(v):4d}")
+    r["one_by_one_over_sessions"] = round(r["one_by_one"]["median_ms"] / r["sessions"]["median_ms"], 2)
+    rows.append(f"{S:8d}  one pool step is {r['one_by_one_over_sessions']:.2f}x faster than {S} batch-1 pushes in turn; ids equal: {same}")
+    table = [f"independent encode sessions, 0.32 s pushes of 24 kHz audio, starts staggered by a third of a push, 80 mel / 8 groups / 70 channels / "
+             f"20 layers (tools/bench_stream_encode.py --sessions {S})",
+             f"wall time of one step (one push for every stream) incl. host synchronisation, {args.pushes - args.warmup} steady-state steps, the two "
+             "forms interleaved in one process;",
+             "sessions = one VQGAN.encode_sessions pool, one_by_one = that many StreamingEncoder(batch=1) stepped in turn",
+             "sessions  form        median ms     p10 ms     p90 ms  audio-s / s     n"] + rows
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "a") as f:
+        f.write("\n".join(table) + "\n\n")
+    print("\n".join(table), file=sys.stderr)
+    print(json.dumps(r))
+
+
+if args.sessions:
+    sessions_section()
+    sys.exit(0)
 if args.sample_rate:
     resample_section()
     sys.exit(0)
