@@ -115,6 +115,18 @@ struct ConvRun {
   void* yp = nullptr;
   int64_t yp_plane = 0;
   int yp_only = 0;
+  // Per-item column windows (the per-item layered streaming step: independent sessions in one launch).  `win` is a device table of
+  // (B / len_div) rows of win_stride int32; batch item b uses row b / len_div:
+  //   shift = row[win_shift]           added to the input column of every segment and to the y / skip / res column of every store
+  //   cols  = row[win_end] - shift     stores are masked to q < cols; an item with cols <= 0 is left alone
+  //   row[win_valid[s]]                valid input length of segment s, in the place of SegRun::Tin / in_len
+  // so that item b computes what a launch of its own with seg[].tshift = shift, y + shift, Tcols = cols, seg[].Tin = valid computes, bit
+  // for bit.  y / skip / res point at column 0 of the items' rows, Tcols is the LARGEST cols of the launch (grid and tile choice), tshift
+  // and in_len stay unset, every tstride is 1.  Served by the split kernels (fp16 split, fp32_bf16x3) only; every other path refuses.
+  const int32_t* win = nullptr;
+  int win_stride = 0, win_shift = 0, win_end = 0, win_valid[2] = {0, 0};
+  int64_t win_cols_total = 0;     // sum of cols over the B items, and the number of items with cols > 0: what the profile scope counts
+  int win_active = 0;
 };
 
 int launch_conv(const PackedConv& pc, const ConvRun& r, hipStream_t stream);

@@ -44,6 +44,9 @@ struct KArgs {
   uint4* yp;
   int64_t yp_plane;
   int yp_g8, yp_only;
+  // per-item column windows (conv.h ConvRun::win), read by conv_bf16_kernel<WIN> only: row b / len_div of `win`, win_stride int32 each
+  const int32_t* win;
+  int win_stride, win_shift, win_end, win_valid[2];
 };
 
 __device__ __forceinline__ float act_apply(float v, int act) {

@@ -379,10 +379,17 @@ template <int N, class F> __device__ __forceinline__ void static_for(F&& f) { st
 // allocator still parks one weight set on the B-fragment registers; the default register budget stays.)
 // TAPS > 0: the single-segment form of the fp16-split kernel (launch_spec: one segment, unit input stride, TAPS taps, ceil(Cin / 16) a multiple of
 // KG / 2); its K loop is described above the loop.  TAPS = 0: the generic K loop over segments, chunks and taps.
-template <int WAVES_M, int WAVES_N, int MT, int NT, int MODE, int HALO, int NP, int KG, int PS = 0, int TAPS = 0>
+// WIN: per-item column windows (conv.h ConvRun::win; the per-item layered streaming step).  The workgroup reads its item's row of a.win:
+// `shift` is added to every input column and to every column it stores, stores are masked to `cols` columns, and a valid length per
+// segment stands where Tin / in_len stand otherwise.  Every thread reads the row at the same addresses and nothing writes the table while
+// the kernel runs, so what is derived from it -- the early exit in front of the first barrier included -- is uniform across the workgroup;
+// readfirstlane keeps it in scalar registers.  Same K order, partial products and epilogue expressions: a column has the bits a
+// single-item launch with SegRun::tshift gives it.
+template <int WAVES_M, int WAVES_N, int MT, int NT, int MODE, int HALO, int NP, int KG, int PS = 0, int TAPS = 0, bool WIN = false>
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, NP == 2 ? 2 : 1) void conv_bf16_kernel(KArgs a) {
   static_assert(PS == 0 || NP == 2, "pre-split inputs exist for the fp16 split only");
   static_assert(TAPS == 0 || (NP == 2 && PS == 0), "the single-segment K loop is built for the fp16 split of fp32 inputs");
+  static_assert(!WIN || (PS == 0 && TAPS == 0 && NP != 1), "per-item windows: generic K loop over fp32 inputs, NP = 2 or 3");
   constexpr int BM = WAVES_M * MT * 32, BN = WAVES_N * NT * 32;
   constexpr int XS = BN + HALO;
   constexpr int SUB = KG / 2;                            // 16-channel K steps (per tap) per staged chunk
@@ -407,6 +414,14 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, NP == 2 ? 2 : 1) void conv_
   if (!conv_block_coords(a, tile_n, mblk, b)) return;
   const int q0 = tile_n * BN;
   const int lb = b / a.len_div;
+  const int32_t* wrow = nullptr;
+  int wshift = 0, wcols = 0;
+  if constexpr (WIN) {
+    wrow = a.win + (size_t)lb * a.win_stride;
+    wshift = __builtin_amdgcn_readfirstlane(wrow[a.win_shift]);
+    wcols = __builtin_amdgcn_readfirstlane(wrow[a.win_end]) - wshift;
+    if (q0 >= wcols) return;          // nothing of this item in the tile (an idle item: cols = 0): before the first barrier, nothing is written
+  }
   // (Round 2, fp16-split kernel: waves in odd SIMD slots sleeping 256-2048 cycles before the K loop -- to put the two workgroups of a CU out of
   // phase -- changed nothing either: 0 +- 3 % on every shape.)
   // (Delaying the workgroups that land in odd wave slots -- so that a CU's two workgroups alternate between their MFMA loop and their
@@ -453,6 +468,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, NP == 2 ? 2 : 1) void conv_
 
   // valid input length per segment, read once (a global load inside the K loop would drain the weight prefetch behind it)
   auto seg_limit = [&](int sg) {
+    if constexpr (WIN) return __builtin_amdgcn_readfirstlane(wrow[a.win_valid[sg]]);
     const int tin = (int)a.seg[sg].Tin;
     return a.seg[sg].in_len ? (int)min(a.seg[sg].in_len[lb], (int64_t)tin) : tin;
   };
@@ -501,9 +517,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, NP == 2 ? 2 : 1) void conv_
     const char* xb = reinterpret_cast<const char*>(a.seg[sg].x + (int64_t)b * a.seg[sg].bstride);
     const int taps = a.seg[sg].taps, dil = a.seg[sg].dil, tstride = a.seg[sg].tstride, Cin = a.seg[sg].Cin;
     const int wx = BN + (taps - 1) * dil;
-    const int tin = (int)a.seg[sg].Tin;
     const int lim = sg == 0 ? lim0 : lim1;
-    const int tau0 = q0 * tstride + a.seg[sg].toff - a.seg[sg].pad_left;
+    const int tin = WIN ? max(lim, 1) : (int)a.seg[sg].Tin;      // addresses are clamped into [0, tin): never in front of the row
+    const int tau0 = q0 * tstride + a.seg[sg].toff - a.seg[sg].pad_left + wshift;      // WIN: unit tstride (launch_conv)
     const uint32_t cs4 = (uint32_t)a.seg[sg].cstride * 4u, last = (uint32_t)(Cin - 1) * cs4;
 #pragma unroll
     for (int rr = 0; rr < RPW; ++rr) {
@@ -788,10 +804,20 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, NP == 2 ? 2 : 1) void conv_
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[mi][ni][r] = fmaf(acl[mi][ni][r], 1.f / kF16LoScale, acc[mi][ni][r]) * f16_out;
   }
-  conv_epilogue<MT, NT, MODE, NP == 2 ? 8 : 4>(a, acc, mblk * BM + wave_m * (MT * 32), q0 + wave_n * (NT * 32) + l31, b, lb, h);
+  if constexpr (WIN) {
+    // the epilogue of a single-item launch over this item's window: `cols` columns starting at column `shift` of the item's rows
+    KArgs aw = a;
+    aw.Tcols = wcols; aw.Tout = wcols;
+    aw.y = a.y + wshift;
+    if (a.skip) aw.skip = a.skip + wshift;
+    if (a.res) aw.res = a.res + wshift;
+    conv_epilogue<MT, NT, MODE, NP == 2 ? 8 : 4>(aw, acc, mblk * BM + wave_m * (MT * 32), q0 + wave_n * (NT * 32) + l31, b, lb, h);
+  } else {
+    conv_epilogue<MT, NT, MODE, NP == 2 ? 8 : 4>(a, acc, mblk * BM + wave_m * (MT * 32), q0 + wave_n * (NT * 32) + l31, b, lb, h);
+  }
 }
 
-template <int WM, int WN, int MT, int NT, int MODE, int HALO, int NP, int KG, int PS = 0, int TAPS = 0>
+template <int WM, int WN, int MT, int NT, int MODE, int HALO, int NP, int KG, int PS = 0, int TAPS = 0, bool WIN = false>
 static int launch_b16k(const KArgs& ka, int B, int mblocks, hipStream_t st) {
   constexpr int BN = WN * NT * 32;
   constexpr size_t lds = (size_t)2 * NP * KG * (BN + HALO) * 16;
@@ -799,7 +825,7 @@ static int launch_b16k(const KArgs& ka, int B, int mblocks, hipStream_t st) {
   KArgs k2 = ka;
   dim3 grid;
   DMEL_TRY(conv_grid(k2, (int)((ka.Tcols + BN - 1) / BN), mblocks, B, grid));
-  hipLaunchKernelGGL((conv_bf16_kernel<WM, WN, MT, NT, MODE, HALO, NP, KG, PS, TAPS>), grid, dim3(64 * WM * WN), lds, st, k2);
+  hipLaunchKernelGGL((conv_bf16_kernel<WM, WN, MT, NT, MODE, HALO, NP, KG, PS, TAPS, WIN>), grid, dim3(64 * WM * WN), lds, st, k2);
   DMEL_HIP(hipGetLastError());
   return DMEL_OK;
 }
@@ -884,14 +910,16 @@ template <int MODE, int NP> static int launch_mode_bf16(const KArgs& ka, int til
 // length (bv2, 128 rows x 5888 columns: 176 / 233 / 250 TF/s against 117 / 182 / 206).
 // Within NP = 2 (MI355X, tools/bench_conv.py --precision 3): 256-row problems with long rows gain 5-8 % from the eight-wave 256 x 96 tile (x is
 // converted once per 256 rows); 128-row problems with >= 40 K steps gain 6-17 % from 128 x 64 (124 registers, four waves per SIMD).
-static int pick_tile_bf16(int mtiles, int64_t T, int np, int steps, int B) {
+// win (per-item windows, T = the largest window of the launch): the rule is the same, but the long-row tile 4 -- a window of more than
+// 2048 new columns is not a streaming push -- stays on the 96-column tile, so that NP = 2 can return 1, 2, 3, 5, 6, 7 and NP = 3 1, 2, 3.
+static int pick_tile_bf16(int mtiles, int64_t T, int np, int steps, int B, bool win = false) {
   const char* e = getenv("DMEL_CONV_TILE_BF16");        // per call: tools/ab_wavenet.py switches tiles inside one process
   const int forced = (e && e[0]) ? atoi(e) : -1;
   if (forced >= 0 && forced < 8) return forced;
   int t;
   if (np == 2 && mtiles >= 8 && T > 96) t = 7;
   else if (np == 2 && mtiles >= 4 && mtiles < 8 && steps >= 40) t = 6;
-  else if (mtiles >= 4) t = (T > 2048 && np != 2) ? 4 : 1;
+  else if (mtiles >= 4) t = (T > 2048 && np != 2 && !win) ? 4 : 1;
   else if (mtiles >= 2) t = 2;
   else t = 3;
   // FEW COLUMNS (streaming decode of one stream: 128-512 frames per push; round 3): when the choice above makes fewer workgroups than half
@@ -936,6 +964,55 @@ template <int NP> static int launch_bf16_any(const KArgs& ka, EpiMode mode, int 
     case EPI_LINEAR: return launch_mode_bf16<EPI_LINEAR, NP>(ka, t16, B, st);
     case EPI_GATE: return launch_mode_bf16<EPI_GATE, NP>(ka, t16, B, st);
     default: return launch_mode_bf16<EPI_RESSKIP, NP>(ka, t16, B, st);
+  }
+}
+
+// Per-item column windows (ConvRun::win): the generic K loop of the split kernels with WIN set, instantiated for what the per-item layered
+// streaming step launches -- gated convolutions with taps (16- or 64-column halo), pointwise LINEAR / RESSKIP convolutions -- on the tiles
+// pick_tile_bf16 returns under a table.  Anything else is refused: nothing runs such a launch without honouring the table.
+template <int WM, int WN, int MT, int NT, int MODE, int NP> static int launch_b16_win(const KArgs& ka, int B, int mblocks, hipStream_t st) {
+  int halo = 0;
+  for (int s = 0; s < ka.nseg; ++s) halo = std::max(halo, (ka.seg[s].taps - 1) * ka.seg[s].dil);
+  constexpr int KG0 = (WN * NT * 32 >= 256 && NP == 3) ? 2 : 4;       // as launch_b16
+  constexpr int KGT = (NP == 2 && 2 * NP * kKG2 * (WN * NT * 32 + 64) * 16 <= 65536) ? kKG2 : 2;
+  if constexpr (MODE == EPI_GATE) {
+    if (halo > 0 && halo <= 16) return launch_b16k<WM, WN, MT, NT, MODE, 16, NP, KGT, 0, 0, true>(ka, B, mblocks, st);
+    if (halo > 16) return launch_b16k<WM, WN, MT, NT, MODE, 64, NP, KGT, 0, 0, true>(ka, B, mblocks, st);
+  } else {
+    if (halo == 0) return launch_b16k<WM, WN, MT, NT, MODE, 0, NP, KG0, 0, 0, true>(ka, B, mblocks, st);
+  }
+  set_error("conv (per-item windows): built for gated convolutions with taps and for pointwise LINEAR / RESSKIP convolutions; mode %d with a "
+            "receptive field of %d columns is neither", MODE, halo);
+  return DMEL_EUNSUPPORTED;
+}
+
+template <int MODE, int NP> static int launch_mode_win(const KArgs& ka, int tile, int B, hipStream_t st) {
+  const int bm[8] = {128, 128, 64, 32, 128, 128, 128, 256};
+  const int mblocks = (ka.mtiles * 32 + bm[tile] - 1) / bm[tile];
+  switch (tile) {
+    case 1: return launch_b16_win<4, 1, 1, 3, MODE, NP>(ka, B, mblocks, st);
+    case 2: return launch_b16_win<2, 2, 1, 2, MODE, NP>(ka, B, mblocks, st);
+    case 3: return launch_b16_win<1, 4, 1, 2, MODE, NP>(ka, B, mblocks, st);
+    default: break;
+  }
+  if constexpr (NP == 2) {
+    switch (tile) {
+      case 5: return launch_b16_win<4, 1, 1, 1, MODE, NP>(ka, B, mblocks, st);
+      case 6: return launch_b16_win<4, 1, 1, 2, MODE, NP>(ka, B, mblocks, st);
+      case 7: return launch_b16_win<8, 1, 1, 3, MODE, NP>(ka, B, mblocks, st);
+      default: break;
+    }
+  }
+  set_error("conv (per-item windows): tile %d (DMEL_CONV_TILE_BF16) is not instantiated for %d operand pieces", tile, NP);
+  return DMEL_EUNSUPPORTED;
+}
+
+template <int NP> static int launch_win_any(const KArgs& ka, EpiMode mode, int B, int64_t Tcols, hipStream_t st) {
+  const int t16 = pick_tile_bf16(ka.mtiles, Tcols, NP, ka.steps, B, true);
+  switch (mode) {
+    case EPI_LINEAR: return launch_mode_win<EPI_LINEAR, NP>(ka, t16, B, st);
+    case EPI_GATE: return launch_mode_win<EPI_GATE, NP>(ka, t16, B, st);
+    default: return launch_mode_win<EPI_RESSKIP, NP>(ka, t16, B, st);
   }
 }
 
@@ -1091,6 +1168,12 @@ int launch_conv(const PackedConv& pc, const ConvRun& r, hipStream_t stream) {
     o.xp = reinterpret_cast<const uint4*>(r.seg[s].xp); o.xp_plane = r.seg[s].xp_plane; o.xp_g8 = sd.Cin / 8;
     o.Cin = sd.Cin; o.nchunk = (sd.Cin + kCK - 1) / kCK; o.taps = sd.taps; o.dil = sd.dil;
     o.pad_left = sd.pad_left; o.tstride = sd.tstride; o.toff = sd.toff + (int)(r.seg[s].tshift * sd.tstride);
+    if (r.win) {
+      if (sd.tstride != 1) { set_error("conv (per-item windows): input stride %d of segment %d; only unit stride is taken", sd.tstride, s); return DMEL_EUNSUPPORTED; }
+      if (r.seg[s].xp) { set_error("conv (per-item windows): the pre-split input path does not read the window table"); return DMEL_EUNSUPPORTED; }
+      DMEL_CHECK_ARG(r.seg[s].tshift == 0 && r.seg[s].in_len == nullptr && r.seg[s].in_absmax == nullptr && r.win_valid[s] >= 0 && r.win_valid[s] < r.win_stride,
+                     "conv (per-item windows): the table replaces tshift / Tin / in_len of segment %d", s);
+    }
     max_halo = std::max(max_halo, (sd.taps - 1) * sd.dil);
     // the staging code addresses one batch item with unsigned 32-bit BYTE offsets
     DMEL_CHECK_ARG((int64_t)sd.Cin * o.cstride < ((int64_t)1 << 30) && o.Tin * sd.tstride < ((int64_t)1 << 30),
@@ -1110,6 +1193,15 @@ int launch_conv(const PackedConv& pc, const ConvRun& r, hipStream_t stream) {
   ka.res = r.res; ka.res_bs = r.res_bs; ka.res_cs = r.res_cs; ka.row_scale = r.row_scale;
   ka.out_len = r.out_len; ka.skip = r.skip;
   ka.fold_pitch = r.fold_pitch; ka.fold_valid = r.fold_valid;
+  ka.win = r.win; ka.win_stride = r.win_stride; ka.win_shift = r.win_shift; ka.win_end = r.win_end;
+  ka.win_valid[0] = r.win_valid[0]; ka.win_valid[1] = r.win_valid[1];
+  if (r.win) {
+    if (r.fold_pitch != 0) { set_error("conv (per-item windows): the folded batch has one time axis for all items and no table"); return DMEL_EUNSUPPORTED; }
+    if (r.yp) { set_error("conv (per-item windows): the pre-split output path does not read the window table"); return DMEL_EUNSUPPORTED; }
+    DMEL_CHECK_ARG(r.win_stride > 0 && r.win_shift >= 0 && r.win_shift < r.win_stride && r.win_end >= 0 && r.win_end < r.win_stride &&
+                   r.out_tstride == 1 && r.phase_base == 0 && d.phases == 1 && r.win_cols_total >= 0 && r.win_active >= 0,
+                   "conv (per-item windows): bad table description, or an output stride / phases");
+  }
   DMEL_CHECK_ARG(r.yp == nullptr || (d.mode != EPI_LINEAR && d.C % 8 == 0 && r.out_tstride == 1), "conv: pre-split output needs a paired mode and C %% 8 == 0");
   ka.yp = reinterpret_cast<uint4*>(r.yp); ka.yp_plane = r.yp_plane; ka.yp_g8 = d.C / 8; ka.yp_only = r.yp_only;
   DMEL_CHECK_ARG(r.fold_pitch == 0 || (r.fold_pitch >= r.fold_valid && r.fold_valid > 0 && r.B == 1 && r.out_tstride == 1),
@@ -1127,13 +1219,32 @@ int launch_conv(const PackedConv& pc, const ConvRun& r, hipStream_t stream) {
   else if (d.mode == EPI_GATE) out_elems = (double)d.C * (double)r.Tcols;
   else out_elems = (double)d.C * (double)r.Tcols * (r.skip_first ? 3.0 : 4.0);
   double alg_bytes = 4.0 * r.B * (in_elems + out_elems);      // + the weight image read once, added below when the arithmetic is known
+  double alg_cols = (double)r.B * (double)r.Tcols;            // output columns of the launch
+  if (r.win) {      // per-item windows: the sums over the items' own column counts (idle items cost nothing)
+    alg_cols = (double)r.win_cols_total;
+    double in_rows = 0.0;
+    for (int s = 0; s < d.nseg; ++s) in_rows += (double)d.seg[s].Cin;
+    alg_bytes = 4.0 * (in_rows * (alg_cols + (double)r.win_active * max_halo) + out_elems / (double)r.Tcols * alg_cols);
+  }
   const bool native_fp32 = conv_fp32_mfma_forced();
   const bool one_piece = r.precision == DMEL_PRECISION_BF16 || train_precision_override() == DMEL_PRECISION_BF16;
   const bool native = !one_piece && (native_fp32 || r.precision == DMEL_PRECISION_FP32_MFMA);
   const double products = one_piece ? 1.0 : native ? 16.0 /* fp32 MFMA: 1/16 of the bf16 rate */ : r.precision == DMEL_PRECISION_FP32_F16X2 ? 3.0 : 6.0;
   alg_bytes += (double)pc.Mpad * pc.steps * kCK * (one_piece ? 2.0 : native ? 4.0 : r.precision == DMEL_PRECISION_FP32_F16X2 ? 4.0 : 6.0);
-  const double alg_flops = 2.0 * r.B * (double)r.Tcols * rows_real * pc.k_real;
+  const double alg_flops = 2.0 * alg_cols * rows_real * pc.k_real;
+  if (r.win && (one_piece || native)) {
+    set_error("conv (per-item windows): %s does not read the window table (the fp16 split and fp32_bf16x3 do)",
+              one_piece ? "the bf16-operand kernel" : "the native fp32-MFMA kernel");
+    return DMEL_EUNSUPPORTED;
+  }
   ProfScope ps("conv_igemm", stream, alg_flops, alg_bytes, alg_flops * products);
+  if (r.win) {
+    if (r.precision == DMEL_PRECISION_FP32_F16X2) {
+      DMEL_TRY(check_f16_range(pc, r, stream));
+      return launch_win_any<2>(ka, d.mode, r.B, r.Tcols, stream);
+    }
+    return launch_win_any<3>(ka, d.mode, r.B, r.Tcols, stream);
+  }
   if (r.precision == DMEL_PRECISION_BF16 || train_precision_override() == DMEL_PRECISION_BF16)
     return launch_bf16_any<1>(ka, d.mode, r.B, r.Tcols, stream);
   // fp32: the split kernel is the default everywhere (after the wait-placement fixes it also wins on the 32-row, K < 128

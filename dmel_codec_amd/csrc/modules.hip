@@ -602,6 +602,104 @@ extern "C" int dmel_wavenet_stream_step_items(const dmel_wavenet* m, const float
   return launch_wavenet_stream_items(m->fused, x, hist, skip, y, out_lengths, div, N, cap, prev, next, tab, (hipStream_t)stream);
 }
 
+// Per-utterance frontiers through the LAYERED step (include/dmel_hip.h): wavenet_stream_step_impl's launches below, each over all N items
+// with per-item column windows (ConvRun::win) read from ONE device table of the rows -- prev[0..L] | next[0..L] per utterance, uploaded
+// once -- so every launch only names the level it works on.  Any stack the layered lockstep step serves.
+extern "C" int dmel_wavenet_stream_step_items_layered(const dmel_wavenet* m, const float* x, float* hist, float* skip, const float* cond,
+                                                      float* y, float* scratch, int N, int64_t cap, const int64_t* prev, const int64_t* next,
+                                                      const int64_t* out_lengths, int group_repeat, const int64_t* origin, void* stream) {
+  DMEL_CHECK_ARG(m && hist && skip && y && scratch && prev && next && origin, "wavenet_stream_step_items_layered: NULL argument");
+  if (!m->ready) { set_error("wavenet_stream_step_items_layered: handle not finalized"); return DMEL_EMISSING; }
+  DMEL_CHECK_ARG((m->Ccond != 0) == (cond != nullptr), "wavenet_stream_step_items_layered: condition tensor does not match the configuration");
+  DMEL_CHECK_ARG(m->has_in == (x != nullptr), "wavenet_stream_step_items_layered: the raw input is given exactly when the model has an input projection");
+  const int div = group_repeat > 0 ? group_repeat : 1;
+  DMEL_CHECK_ARG(N > 0 && N <= 65535 && cap > 0 && cap < ((int64_t)1 << 30) && N % div == 0, "wavenet_stream_step_items_layered: bad shape / group_repeat");
+  if (conv_fp32_mfma_forced() || m->precision == DMEL_PRECISION_FP32_MFMA || m->precision == DMEL_PRECISION_BF16 ||
+      train_precision_override() == DMEL_PRECISION_BF16) {
+    set_error("wavenet_stream_step_items_layered: per-item column windows are built into the split kernels only (DMEL_PRECISION_FP32 / "
+              "FP32_BF16X3 / FP32_F16X2); a forced native fp32 MFMA and the bf16-operand mode are not served");
+    return DMEL_EUNSUPPORTED;
+  }
+  const int C = m->C, L = m->L, L1 = L + 1, R = N / div, RI = kStreamRowInts(L);
+  for (int r = 0; r < R; ++r) {
+    DMEL_CHECK_ARG(origin[r] >= 0, "wavenet_stream_step_items_layered: utterance %d: negative origin", r);
+    DMEL_TRY(stream_row_check(m, prev + (size_t)r * L1, next + (size_t)r * L1, cap, origin[r], r));
+  }
+  // the table: prev[0..L] | next[0..L] | idle flag per utterance; per level the largest window, the columns of all items and the active items
+  std::vector<int32_t> rows((size_t)R * RI);
+  std::vector<int64_t> maxc(L1, 0), sumc(L1, 0);
+  std::vector<int> act(L1, 0);
+  for (int r = 0; r < R; ++r) {
+    bool idle = true;
+    for (int l = 0; l < L1; ++l) {
+      const int64_t p = prev[(size_t)r * L1 + l], n = next[(size_t)r * L1 + l];
+      rows[(size_t)r * RI + l] = (int32_t)p;
+      rows[(size_t)r * RI + L1 + l] = (int32_t)n;
+      maxc[l] = std::max(maxc[l], n - p);
+      sumc[l] += div * (n - p);
+      if (n > p) { act[l] += div; idle = false; }
+    }
+    rows[(size_t)r * RI + 2 * L1] = idle ? -1 : 0;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  // behind dmel_wavenet_stream_step_ex's scratch (N * 2 C * cap floats, N int64), as dmel_wavenet_stream_step_items places its table
+  const int64_t bs = (int64_t)C * cap, lvl = (int64_t)N * bs;
+  int64_t* rel = reinterpret_cast<int64_t*>(scratch + 2 * lvl);
+  int32_t* tab = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(scratch) + (size_t)2 * lvl * sizeof(float) + (size_t)N * sizeof(int64_t));
+  bool any = false;
+  for (int l = 0; l < L1; ++l) any = any || maxc[l] > 0;
+  if (!any) return DMEL_OK;                     // every row idle: nothing to do
+  DMEL_TRY(launch_table_put(rows.data(), rows.size() * sizeof(int32_t), tab, st));
+  float* zb = scratch;                          // gate output of the block being computed, (N, C, cap)
+  // new columns of level `lev` from an input whose valid length is next[vlev]: the windows of wavenet_stream_step_impl's sub(), per item
+  auto sub = [&](const float* xin, int Cin, int vlev, int lev, float* out, int Cout) {
+    ConvRun r;
+    r.seg[0].x = xin; r.seg[0].bstride = (int64_t)Cin * cap; r.seg[0].cstride = cap;
+    r.B = N; r.Tcols = maxc[lev]; r.y = out; r.y_bs = (int64_t)Cout * cap; r.y_cs = cap; r.Tout = maxc[lev];
+    r.len_div = div;
+    r.win = tab; r.win_stride = RI; r.win_shift = lev; r.win_end = L1 + lev; r.win_valid[0] = L1 + vlev;
+    r.win_cols_total = sumc[lev]; r.win_active = act[lev];
+    r.precision = m->precision;
+    return r;
+  };
+  if (m->has_in && maxc[0] > 0) {  // wavenet.py:205-207 on the new columns of level 0
+    ConvRun r = sub(x, m->Cin, 0, 0, hist, C);
+    r.act = ACT_SILU;
+    DMEL_TRY(launch_conv(m->in_proj, r, st));
+  }
+  for (int i = 0; i < L; ++i) {  // wavenet.py:116-135 on the new columns of block i + 1
+    if (maxc[i + 1] <= 0) continue;
+    const float* xin = hist + (int64_t)i * lvl;
+    float* xout = hist + (int64_t)(i + 1) * lvl;
+    ConvRun g = sub(xin, C, i, i + 1, zb, C);
+    if (m->Ccond) {
+      g.seg[1].x = cond; g.seg[1].bstride = (int64_t)m->Ccond * cap; g.seg[1].cstride = cap; g.win_valid[1] = L1 + 0;
+    }
+    DMEL_TRY(launch_conv(m->gate[i], g, st));
+    // block i's input survives as history: its new columns are copied into block i + 1's rows and updated there (see the lockstep step)
+    DMEL_TRY(launch_copy_windows(xin, xout, N, C, cap, tab, RI, i + 1, L1 + i + 1, div, maxc[i + 1], sumc[i + 1], st));
+    ConvRun r = sub(zb, C, i + 1, i + 1, xout, C);
+    r.skip = skip; r.skip_first = (i == 0);
+    DMEL_TRY(launch_conv(m->resskip[i], r, st));
+  }
+  if (maxc[L] > 0) {  // wavenet.py:218-223 on the columns whose skip sum is complete
+    float* tb = scratch + lvl;                  // second half of the scratch
+    ConvRun r = sub(skip, C, L, L, m->has_out ? tb : y, C);
+    r.seg[0].in_scale = (float)(1.0 / std::sqrt((double)m->L));
+    // the output mask in the store: an item's columns start at its prev[L], so its length is taken relative to that
+    if (out_lengths) DMEL_TRY(launch_shift_lengths_items(out_lengths, tab, RI, L, rel, R, st));
+    if (m->has_out) r.act = ACT_SILU;
+    else r.out_len = out_lengths ? rel : nullptr;
+    DMEL_TRY(launch_conv(m->skip_proj, r, st));
+    if (m->has_out) {
+      ConvRun o = sub(tb, C, L, L, y, m->Cout);
+      o.out_len = out_lengths ? rel : nullptr;
+      DMEL_TRY(launch_conv(m->out_proj, o, st));
+    }
+  }
+  return DMEL_OK;
+}
+
 static int wavenet_stream_step_impl(const dmel_wavenet* m, const float* xraw, float* hist, float* skip, const float* cond, float* y,
                                     float* scratch, int N, int64_t cap, const int64_t* prev, const int64_t* next,
                                     const int64_t* out_lengths, int group_repeat, int64_t origin, bool ex, void* stream) {

@@ -67,6 +67,12 @@ int launch_wavenet_stream_items(const WaveNetFused& f, const float* x, float* hi
                                 int N, int64_t cap, const int64_t* prev, const int64_t* next, int32_t* tab_dev, hipStream_t st);
 // out[i] = max(len[i] - shift, 0): lengths relative to the first column of a sub-range launch
 int launch_shift_lengths(const int64_t* len, int64_t shift, int64_t* out, int n, hipStream_t st);
+// Per-item column windows (conv.h ConvRun::win) outside the convolutions: dst[n][c][shift + q] = src[n][c][shift + q], q < cols, both
+// (N, C, cap), shift = row[i_shift] and cols = row[i_end] - shift of row n / len_div of the device table (`stride` int32 per row); and
+// out[r] = max(len[r] - row r's shift, 0).  max_cols: the largest cols (grid), cols_total: their sum over the N items (profile scope).
+int launch_copy_windows(const float* src, float* dst, int N, int C, int64_t cap, const int32_t* tab, int stride, int i_shift, int i_end,
+                        int len_div, int64_t max_cols, int64_t cols_total, hipStream_t st);
+int launch_shift_lengths_items(const int64_t* len, const int32_t* tab, int stride, int i_shift, int64_t* out, int n, hipStream_t st);
 int launch_aa_snake(const float* x, float* y, const float* alpha, const float* beta, const float* up_taps_host,
                     const float* down_taps_host, int logscale, int B, int C, int64_t T, hipStream_t s);
 // dx of the anti-aliased Snake only (frozen parameters): bit-identical to the dx of the full backward; dx = (dx_act + radd) + racc,

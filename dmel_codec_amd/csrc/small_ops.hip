@@ -659,6 +659,44 @@ int launch_table_put(const void* host, size_t bytes, void* dst_dev, hipStream_t 
   return DMEL_OK;
 }
 
+// ---- per-item column windows (conv.h ConvRun::win): the copies and lengths of the per-item layered streaming step ------------------
+// dst[n][c][shift + q] = src[n][c][shift + q] for q < cols, shift / cols from row n / len_div of the table: what hipMemcpy2DAsync does for
+// the lockstep step's one window.  The row is read at the same addresses by every thread of a workgroup.
+__global__ __launch_bounds__(256) void copy_windows_kernel(const float* __restrict__ src, float* __restrict__ dst, int C, int64_t cap,
+                                                           const int32_t* __restrict__ tab, int stride, int i_shift, int i_end, int len_div) {
+  const int n = blockIdx.z, c = blockIdx.y;
+  const int32_t* row = tab + (size_t)(n / len_div) * stride;
+  const int shift = __builtin_amdgcn_readfirstlane(row[i_shift]);
+  const int cols = __builtin_amdgcn_readfirstlane(row[i_end]) - shift;
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= cols) return;
+  const int64_t o = ((int64_t)n * C + c) * cap + shift + q;
+  dst[o] = src[o];
+}
+int launch_copy_windows(const float* src, float* dst, int N, int C, int64_t cap, const int32_t* tab, int stride, int i_shift, int i_end,
+                        int len_div, int64_t max_cols, int64_t cols_total, hipStream_t st) {
+  DMEL_CHECK_ARG(src && dst && tab && N > 0 && N <= 65535 && C > 0 && C <= 65535 && max_cols > 0 && max_cols <= cap && len_div > 0 && stride > 0 &&
+                     i_shift >= 0 && i_shift < stride && i_end >= 0 && i_end < stride, "copy_windows: bad argument");
+  ProfScope ps("small", st, 0.0, 8.0 * C * (double)cols_total);
+  hipLaunchKernelGGL(copy_windows_kernel, dim3((unsigned)((max_cols + 255) / 256), (unsigned)C, (unsigned)N), dim3(256), 0, st, src, dst, C, cap,
+                     tab, stride, i_shift, i_end, len_div);
+  DMEL_HIP(hipGetLastError());
+  return DMEL_OK;
+}
+
+// out[r] = max(len[r] - row r's shift, 0): an item's output length relative to the first column of its window
+__global__ void shift_lengths_items_kernel(const int64_t* __restrict__ len, const int32_t* __restrict__ tab, int stride, int i_shift,
+                                           int64_t* __restrict__ out, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = max(len[i] - (int64_t)tab[(size_t)i * stride + i_shift], (int64_t)0);
+}
+int launch_shift_lengths_items(const int64_t* len, const int32_t* tab, int stride, int i_shift, int64_t* out, int n, hipStream_t st) {
+  DMEL_CHECK_ARG(len && tab && out && n > 0 && stride > 0 && i_shift >= 0 && i_shift < stride, "shift_lengths_items: bad argument");
+  hipLaunchKernelGGL(shift_lengths_items_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, len, tab, stride, i_shift, out, n);
+  DMEL_HIP(hipGetLastError());
+  return DMEL_OK;
+}
+
 }  // namespace dmel
 
 extern "C" int dmel_mask_add_quality_f32(float* z, const int64_t* lengths, const float* w, const float* bias, float value,

@@ -459,6 +459,15 @@ class VQGAN(nn.Module):
         and concatenate to resample(decode() audio, vocoder rate, output_sample_rate), bit for bit (the mel pieces are unchanged)."""
         return StreamingDecoder(self, batch, feature_lengths, return_audios, graph_chunk_tokens, overlap_vocoder, output_sample_rate)
 
+    def decode_sessions(self, slots: int, max_push_tokens: int = 64, return_audios: bool = True, **options):
+        """A pool of `slots` INDEPENDENT incremental decodes served by one streaming step: replies open, grow by their own number of
+        tokens per step (at most max_push_tokens), stall and close on their own -- what streaming_decoder(batch=B), B streams in
+        lockstep, cannot do -- and each one's concatenated audio and mel are the bits of decode() on its own ids.  One decoder WaveNet
+        step per pool step whatever the number of slots.  overlap_vocoder, graph_chunk_tokens and output_sample_rate are
+        NotImplementedError here; see models/stream_sessions.py: DecodeSessions."""
+        from .stream_sessions import DecodeSessions
+        return DecodeSessions(self, slots, max_push_tokens, return_audios, **options)
+
     @torch.no_grad()
     def decode_stream(self, indices, feature_lengths=None, *, chunk_tokens: int = 64, noise: Optional[torch.Tensor] = None,
                       return_audios: bool = True, use_graph: bool = False, pipeline: bool = False,

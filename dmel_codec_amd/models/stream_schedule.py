@@ -157,6 +157,135 @@ def session_rows(slots: int, steps: Mapping[int, EncodeStep], origins: Sequence[
     return prev, nxt, org
 
 
+# ---------------------------------------------------------------------------------------------------- the decode side
+@dataclass(frozen=True)
+class DecodeGeometry:
+    """What the frontier arithmetic of an incremental decode depends on: mel frames per token, the decoder WaveNet's dilations, the
+    vocoder's context in frames on each side (0: mel only) and the quantiser's context in tokens on each side."""
+    factor: int
+    dilations: Tuple[int, ...]
+    voc_halo: int = 0
+    quant_halo_tokens: int = 4
+
+    @property
+    def decoder_context(self) -> int:
+        return sum(self.dilations)
+
+    @property
+    def max_dilation(self) -> int:
+        return max(self.dilations) if self.dilations else 1
+
+    @property
+    def hold_frames(self) -> int:
+        """frames between the oldest column a later step still reads and the newest frame received, at most, in front of a push: the
+        quantiser holds back H tokens, the last level runs sum(dilations) behind the condition, and behind the last level the next
+        block window reaches max(dilations) back and the vocoder window 2 voc_halo (emitted is voc_halo behind, its window another)"""
+        return self.quant_halo_tokens * self.factor + self.decoder_context + max(self.max_dilation, 2 * self.voc_halo)
+
+
+@dataclass(frozen=True)
+class DecodeStep:
+    tokens: int                       # tokens received so far
+    final: bool
+    need_from: int                    # oldest column this and every later step reads: min(prev[L] - maxdil, emitted - voc_halo), >= 0
+    upto: int                         # tokens * factor: the buffers must hold the absolute frames [need_from, upto)
+    tok_window: Tuple[int, int]       # tokens [lo, hi) the quantiser decodes now (lo == hi: nothing)
+    tok_keep_from: int                # oldest token a later window reads: the carried token tail starts here
+    z: Tuple[int, int]                # condition / level-0 frames [a, b) written now, cropped from the window's output
+    prev: Tuple[int, ...]             # decoder level frontiers before / after the WaveNet step (prev == next: no step)
+    next: Tuple[int, ...]
+    emit: Tuple[int, int]             # mel frames [a, b) handed out now
+    voc_window: Tuple[int, int]       # mel frames [lo, hi) the vocoder runs on for them (lo == hi: nothing to vocode)
+
+
+class DecodeSchedule:
+    """The counters StreamingDecoder._push_eager keeps inline (models/codec_lit_modules.py), as a pure class: step(n, final) accounts for n
+    more tokens and says what to compute.  Time is in mel frames, absolute.
+
+        condition   z_valid -> all frames if final, else (tokens - H) * factor: the quantiser's last H tokens wait for right context
+        level l     next[l] = max(prev[l], next[l - 1] - dilation[l - 1]); the total on the final step (the zero padding is real then)
+        emitted     -> prev[L] - voc_halo (prev[L] if final or mel only)
+
+    As in StreamingDecoder the WaveNet step is skipped -- and the frontiers stay where they are -- while the last level cannot advance."""
+
+    def __init__(self, geo: DecodeGeometry):
+        self.geo = geo
+        self.tokens = 0
+        self.z_valid = 0
+        self.levels: List[int] = [0] * (len(geo.dilations) + 1)
+        self.emitted = 0
+        self.tok_origin = 0
+        self.finished = False
+
+    @property
+    def need_from(self) -> int:
+        g = self.geo
+        return max(0, min(self.levels[-1] - g.max_dilation, self.emitted - g.voc_halo))
+
+    def step(self, n: int, final: bool = False) -> DecodeStep:
+        if self.finished:
+            raise RuntimeError("stream already finished")
+        if n < 0:
+            raise ValueError("negative token count")
+        g = self.geo
+        f, H = g.factor, g.quant_halo_tokens
+        need_from = self.need_from
+        self.tokens += n
+        total = self.tokens * f
+        z_new = total if final else max(self.z_valid, (self.tokens - H) * f)
+        tok_window = (0, 0)
+        z = (self.z_valid, self.z_valid)
+        if z_new > self.z_valid:
+            tok_window = (max(0, self.z_valid // f - H), self.tokens)
+            z = (self.z_valid, z_new)
+            self.z_valid = z_new
+            self.tok_origin = max(self.tok_origin, self.z_valid // f - H)
+        nxt = [self.z_valid]
+        for l, d in enumerate(g.dilations):
+            nxt.append(self.z_valid if final else max(self.levels[l + 1], nxt[-1] - d))
+        prev = tuple(self.levels)
+        if final or nxt[-1] > self.levels[-1]:
+            self.levels = nxt
+        ready = self.levels[-1]
+        e_new = ready if (final or g.voc_halo == 0) else max(self.emitted, ready - g.voc_halo)
+        voc = (0, 0)
+        if g.voc_halo and e_new > self.emitted:
+            voc = (max(0, self.emitted - g.voc_halo), min(ready, e_new + g.voc_halo))
+        st = DecodeStep(tokens=self.tokens, final=final, need_from=need_from, upto=total, tok_window=tok_window,
+                        tok_keep_from=self.tok_origin, z=z, prev=prev, next=tuple(self.levels), emit=(self.emitted, e_new), voc_window=voc)
+        self.emitted = e_new
+        self.finished = final
+        return st
+
+
+def decode_capacity(geo: DecodeGeometry, max_push_tokens: int) -> int:
+    """Columns of a decode slot's state buffers.  In front of a push a slot holds at most geo.hold_frames columns that are still read;
+    the push adds max_push_tokens * factor.  Four pushes of room instead of one, rounded up to 32, so that a slot that pushes the maximum
+    every time is re-based (decode_rebase) once in four pushes and one that pushes less, less often."""
+    if max_push_tokens <= 0:
+        raise ValueError("max_push_tokens must be positive")
+    return (geo.hold_frames + 4 * max_push_tokens * geo.factor + 31) // 32 * 32
+
+
+def decode_rebase(origin: int, st: DecodeStep, cap: int) -> int:
+    """The absolute frame column 0 of a slot's buffers holds after making room for step `st`: unchanged while [origin, st.upto) fits
+    `cap` columns, else the oldest column still needed."""
+    if st.upto - origin <= cap:
+        return origin
+    if st.upto - st.need_from > cap:
+        raise RuntimeError(f"{st.upto - st.need_from} columns do not fit the capacity {cap}: a push beyond max_push_tokens")
+    return st.need_from
+
+
+def decode_session_rows(slots: int, steps: Mapping[int, DecodeStep], origins: Sequence[int]) -> Tuple[List[int], List[int], List[int]]:
+    """session_rows for decode steps: one (prev, next) row per slot, relative to the slot's own origin; a slot without a step, or whose
+    step runs no WaveNet step, is idle (a row of zeros, origin 0)."""
+    live = {s: st for s, st in steps.items() if st.next != st.prev}
+    if not live:
+        raise ValueError("no step to make rows of")
+    return session_rows(slots, live, origins)
+
+
 # ---------------------------------------------------------------------------------------------------- streaming sample-rate conversion
 def resample_width(orig: int, new: int, lowpass_filter_width: int = 6, rolloff: float = 0.99) -> int:
     """half width of the windowed sinc in input samples (orig, new already divided by their gcd): torchaudio's

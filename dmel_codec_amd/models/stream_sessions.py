@@ -1,4 +1,5 @@
-"""A pool of independent live encode sessions served by ONE streaming step (VQGAN.encode_sessions).
+"""Pools of independent live sessions served by ONE streaming step: EncodeSessions (VQGAN.encode_sessions, below) and DecodeSessions
+(VQGAN.decode_sessions, at the end of the file).
 
 StreamingEncoder(batch=B) is B streams in lockstep: one schedule, one origin, one (prev, next) row.  Microphones do not behave like that:
 they start, stall and hang up on their own.  EncodeSessions keeps one EncodeSchedule, one origin and one sample tail PER SLOT and hands
@@ -7,12 +8,14 @@ by its own number of samples, in one STFT launch and one encoder launch."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Iterable, List, Mapping, Optional
+import math
+from typing import Dict, Iterable, List, Mapping, Optional, Tuple
 
 import torch
 
 from .. import _lib
-from .stream_schedule import EncodeGeometry, EncodeSchedule, session_rows
+from .stream_schedule import (DecodeGeometry, DecodeSchedule, EncodeGeometry, EncodeSchedule, decode_capacity, decode_rebase,
+                              decode_session_rows, session_rows)
 
 
 class EncodeSessions:
@@ -271,3 +274,245 @@ class EncodeSessions:
         self._check_open(slot)
         dev = self.buf["samples"].device if self.buf is not None else next(self.codec.parameters()).device
         return self.push({slot: torch.empty(0, dtype=torch.float32, device=dev)}, final=(slot,))[slot]
+
+
+class DecodeSessions:
+    """`slots` independent incremental decodes, each with the audio and mel of decode() on its own finished token sequence.
+
+        slot = pool.open()                                              # a free slot, fresh state
+        out = pool.push({slot: ids (G, n) int, ...}, noise=None | {slot: (C, n * factor)}, final=())
+                                                                        # -> {slot: (audio (1, m * up) | None, mel (n_mels, m))}
+        out = pool.close(slot)                                          # = push({slot: empty}, final=(slot,))[slot]
+
+    StreamingDecoder(batch=B) is B replies in lockstep: one token count, one origin, one (prev, next) row, one `finished`.  An LM server's
+    replies start at different times, grow by different token counts and end on their own.  Here any subset of the open slots is named
+    in a step, each with its own token count (0 is allowed, more than `max_push_tokens` is refused); slots that are not named are idle.
+    A slot in `final` ends with these tokens: the step flushes everything that waited for right context, computed with the true end of
+    its sequence, and frees the slot.  m >= 0 frames become final per step, after the lookahead StreamingDecoder has (quantiser 4 tokens,
+    decoder WaveNet sum(dilations) frames, vocoder receptive_field_frames()).  noise: the decoder's input noise for the pushed frames
+    (reproducible runs); a slot without an entry draws its own, as decode() does.
+
+    Per step: the quantiser decode once per group of slots whose token windows have the same length and the same finality, ONE decoder
+    WaveNet step over all slots (dmel_wavenet_stream_step_items_layered: every launch of the layered step covers all slots, each with
+    its own column window), and the vocoder once per group of slots whose mel windows have the same length, cropped per slot as
+    StreamingDecoder crops -- in steady state with equal pushes, one call of each.
+
+    State: buffers of (L + 1, slots, C, cap) and so on, laid out like StreamingDecoder's, `cap` fixed at construction from
+    max_push_tokens (stream_schedule.decode_capacity); each slot has its own origin (the absolute frame in column 0 of ITS rows), its own
+    token tail and noise tail; re-basing shifts one slot's columns only; a reopened slot's rows are zeroed before its first push.  Memory
+    grows neither with the length of a stream nor with the number of sessions served over time.
+
+    Out of scope, NotImplementedError: overlap_vocoder, graph_chunk_tokens, output_sample_rate (the codec's own rate only).
+
+    All launches are on the current stream; there is no side stream for the vocoder.  The warning of StreamingEncoder / EncodeSessions
+    about the STFT next to convolutions on ANOTHER STREAM applies to this pool's convolutions: a caller that runs
+    encode sessions on a second stream beside this pool must call dmel_stft_set_exclusive_cu(1) first, exactly as pipeline.CodecLanes
+    does."""
+
+    def __init__(self, codec, slots: int, max_push_tokens: int = 64, return_audios: bool = True, overlap_vocoder: bool = False,
+                 graph_chunk_tokens: Optional[int] = None, output_sample_rate: Optional[int] = None):
+        if overlap_vocoder or graph_chunk_tokens is not None or output_sample_rate is not None:
+            raise NotImplementedError("decode sessions launch everything on the current stream, eagerly, at the codec's own sample rate: "
+                                      "overlap_vocoder, graph_chunk_tokens and output_sample_rate belong to StreamingDecoder")
+        if codec.decoder is None:
+            raise ValueError("Decoder is not loaded")
+        if return_audios and codec.vocoder is None:
+            raise ValueError("Vocoder is not loaded")
+        if int(slots) <= 0 or int(max_push_tokens) <= 0:
+            raise ValueError("slots and max_push_tokens must be positive")
+        dec = codec.decoder
+        if dec.input_projection is not None:
+            raise NotImplementedError("streaming needs a decoder without input projection (input_channels == residual_channels)")
+        self.codec, self.S, self.G = codec, int(slots), codec.dmel_groups
+        self.return_audios = bool(return_audios)
+        self.L, self.C = len(dec.residual_layers), dec.residual_channels
+        cycle = dec.dilation_cycle or 0
+        dils = tuple(2 ** (i % cycle) if cycle else 1 for i in range(self.L))
+        self.geo = DecodeGeometry(factor=math.prod(codec.quantizer.downsample_factor), dilations=dils,
+                                  voc_halo=codec.vocoder.receptive_field_frames() if return_audios else 0)
+        self.up = math.prod(codec.vocoder.h.upsample_rates) if return_audios else 1
+        self.max_push = int(max_push_tokens)
+        self.cap = decode_capacity(self.geo, self.max_push)
+        H, f = self.geo.quant_halo_tokens, self.geo.factor
+        self.tok_width = 2 * H + self.max_push            # the token tail starts at most 2 H tokens behind the newest token of the last push
+        self.noise_width = (H + self.max_push) * f        # frames [z_valid, tokens * factor): at most H tokens of them in front of a push
+        self.sched: List[Optional[DecodeSchedule]] = [None] * self.S
+        self.origin = [0] * self.S
+        self.tok_origin = [0] * self.S                    # absolute index of the token in column 0 of the slot's token tail
+        self.n_noise = [0] * self.S                       # valid frames in the slot's noise tail
+        self._fresh = [False] * self.S
+        self.buf = None
+
+    # -- bookkeeping (no device call) ------------------------------------------------------------------------------------
+    @property
+    def capacity(self) -> int:
+        """columns of the state buffers (mel frames); fixed at construction"""
+        return self.cap
+
+    @property
+    def open_slots(self) -> List[int]:
+        return [s for s in range(self.S) if self.sched[s] is not None]
+
+    def allocated_bytes(self) -> int:
+        return 0 if self.buf is None else sum(t.numel() * t.element_size() for t in self.buf.values())
+
+    def frames_emitted(self, slot: int) -> int:
+        self._check_open(slot)
+        return self.sched[slot].emitted
+
+    def open(self) -> int:
+        """take a free slot: fresh schedule, state zeroed before its first push.  Raises when every slot is taken."""
+        for s in range(self.S):
+            if self.sched[s] is None:
+                self.sched[s] = DecodeSchedule(self.geo)
+                self.origin[s] = self.tok_origin[s] = self.n_noise[s] = 0
+                self._fresh[s] = True
+                return s
+        raise RuntimeError(f"all {self.S} slots are taken")
+
+    def _check_open(self, slot) -> None:
+        if not isinstance(slot, int) or not 0 <= slot < self.S:
+            raise ValueError(f"slot {slot!r} out of range (0 .. {self.S - 1})")
+        if self.sched[slot] is None:
+            raise RuntimeError(f"slot {slot} is not open")
+
+    def _validate(self, ids: Mapping[int, torch.Tensor], noise, final) -> None:
+        """everything that can be refused, before any state changes and before any device call"""
+        if not ids:
+            raise ValueError("push needs at least one slot")
+        f = self.geo.factor
+        for slot, t in ids.items():
+            self._check_open(slot)
+            if t.ndim != 2 or t.shape[0] != self.G:
+                raise ValueError(f"slot {slot}: expected ids of shape ({self.G}, n), got {tuple(t.shape)}")
+            if t.shape[1] > self.max_push:
+                raise ValueError(f"slot {slot}: a push of {t.shape[1]} tokens exceeds max_push_tokens = {self.max_push}")
+            _lib.require_cuda(t, "indices")
+        for slot in final:
+            if slot not in ids:
+                raise ValueError(f"slot {slot} is in `final` but not among the pushed slots")
+        for slot, z in (noise or {}).items():
+            if slot not in ids:
+                raise ValueError(f"noise for slot {slot}, which is not among the pushed slots")
+            if tuple(z.shape) != (self.C, ids[slot].shape[1] * f):
+                raise ValueError(f"slot {slot}: noise must have shape {(self.C, ids[slot].shape[1] * f)}")
+
+    # -- buffers -----------------------------------------------------------------------------------------------------------
+    def _allocate(self, dev) -> None:
+        S, dec = self.S, self.codec.decoder
+        rows = S * (2 * (self.L + 1) + 1)
+        self.buf = dict(hist=torch.zeros(self.L + 1, S, self.C, self.cap, dtype=torch.float32, device=dev),
+                        skip=torch.zeros(S, self.C, self.cap, dtype=torch.float32, device=dev),
+                        cond=torch.zeros(S, dec.condition_channels, self.cap, dtype=torch.float32, device=dev),
+                        mel=torch.zeros(S, dec.output_channels, self.cap, dtype=torch.float32, device=dev),
+                        tokens=torch.zeros(S, self.G, self.tok_width, dtype=torch.int32, device=dev),
+                        noise=torch.zeros(S, self.C, self.noise_width, dtype=torch.float32, device=dev),
+                        # dmel_wavenet_stream_step_items_layered: 2 S C cap floats, S int64, and the row table behind them
+                        scratch=torch.empty(2 * S * self.C * self.cap + 2 * S + rows, dtype=torch.float32, device=dev))
+
+    def _slot_views(self, s: int):
+        b = self.buf
+        return (b["hist"][:, s], b["skip"][s], b["cond"][s], b["mel"][s])
+
+    def _rebase(self, s: int, st) -> None:
+        """make room for the frames of step `st` in slot s: drop the columns nothing reads again and shift that slot's rows"""
+        new = decode_rebase(self.origin[s], st, self.cap)
+        shift = new - self.origin[s]
+        if shift <= 0:
+            return
+        keep = max(0, st.z[0] - new)                  # nothing behind the condition frontier has been written
+        if keep:
+            for v in self._slot_views(s):
+                v[..., :keep] = v[..., shift:shift + keep].clone()
+        self.origin[s] = new
+
+    # -- one step ----------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def push(self, ids: Mapping[int, torch.Tensor], noise: Optional[Mapping[int, torch.Tensor]] = None,
+             final: Iterable[int] = ()) -> Dict[int, Tuple[Optional[torch.Tensor], torch.Tensor]]:
+        """ids: {slot: (G, n) int, n >= 0}; noise: {slot: (C, n * factor)} for any of them; final: slots that end with these tokens
+        -> {slot: (audio (1, m * up) | None, mel (n_mels, m))} for the m >= 0 frames of that slot that became final with this step"""
+        final = set(final)
+        self._validate(ids, noise, final)
+        codec, f, S, L = self.codec, self.geo.factor, self.S, self.L
+        dev = next(iter(ids.values())).device
+        if self.buf is None:
+            self._allocate(dev)
+        b = self.buf
+        steps = {}
+        with torch.cuda.device(dev):
+            for s, t in ids.items():
+                if self._fresh[s]:
+                    for v in self._slot_views(s):
+                        v.zero_()
+                    self._fresh[s] = False
+                sch = self.sched[s]
+                n = t.shape[1]
+                if n:
+                    at = sch.tokens - self.tok_origin[s]
+                    b["tokens"][s, :, at:at + n] = t.to(torch.int32)
+                    z = noise.get(s) if noise else None
+                    if z is None:
+                        z = torch.randn(self.C, n * f, dtype=torch.float32, device=dev)
+                    b["noise"][s, :, self.n_noise[s]:self.n_noise[s] + n * f] = z.to(dev, torch.float32)
+                    self.n_noise[s] += n * f
+                steps[s] = st = sch.step(n, s in final)
+                self._rebase(s, st)
+            # ---- quantiser: once per group of slots with equal token-window length and equal finality, cropped per slot
+            groups: Dict[tuple, List[int]] = {}
+            for s, st in steps.items():
+                if st.z[1] > st.z[0]:
+                    groups.setdefault((st.tok_window[1] - st.tok_window[0], st.final), []).append(s)
+            for (width, _), members in groups.items():
+                wins = [b["tokens"][s, :, steps[s].tok_window[0] - self.tok_origin[s]:steps[s].tok_window[1] - self.tok_origin[s]]
+                        for s in members]
+                wl = torch.full((len(members),), width, dtype=torch.int64, device=dev)
+                z, _ = codec.get_quantized_features_from_indices(torch.stack(wins).contiguous(), wl)
+                for i, s in enumerate(members):
+                    st, o = steps[s], self.origin[s]
+                    lo = st.tok_window[0] * f
+                    k = st.z[1] - st.z[0]
+                    b["cond"][s, :, st.z[0] - o:st.z[1] - o] = z[i, :, st.z[0] - lo:st.z[1] - lo]
+                    b["hist"][0, s, :, st.z[0] - o:st.z[1] - o] = b["noise"][s, :, :k]
+                    rest = self.n_noise[s] - k
+                    if rest:
+                        b["noise"][s, :, :rest] = b["noise"][s, :, k:k + rest].clone()
+                    self.n_noise[s] = rest
+                    drop = st.tok_keep_from - self.tok_origin[s]
+                    if drop > 0:
+                        keep = st.tokens - st.tok_keep_from
+                        b["tokens"][s, :, :keep] = b["tokens"][s, :, drop:drop + keep].clone()
+                        self.tok_origin[s] = st.tok_keep_from
+            # ---- decoder WaveNet: every level of every slot advances to its own new frontier, in one layered step over all slots
+            if any(st.next != st.prev for st in steps.values()):
+                prev, nxt, org = decode_session_rows(S, steps, self.origin)
+                rows = C.c_int64 * (S * (L + 1))
+                _lib.check(_lib.lib().dmel_wavenet_stream_step_items_layered(
+                    codec.decoder.native(), None, b["hist"].data_ptr(), b["skip"].data_ptr(), b["cond"].data_ptr(), b["mel"].data_ptr(),
+                    b["scratch"].data_ptr(), S, self.cap, rows(*prev), rows(*nxt), None, 1, (C.c_int64 * S)(*org), _lib.stream_ptr()),
+                    "wavenet_stream_step_items_layered")
+            # ---- emit: the mel frames whose vocoder context exists; the vocoder once per group of slots with equal window length
+            out: Dict[int, Tuple[Optional[torch.Tensor], torch.Tensor]] = {}
+            vgroups: Dict[int, List[int]] = {}
+            for s, st in steps.items():
+                o = self.origin[s]
+                mel = b["mel"][s, :, st.emit[0] - o:st.emit[1] - o].clone()
+                out[s] = (torch.empty(1, 0, dtype=torch.float32, device=dev) if self.return_audios else None, mel)
+                if st.voc_window[1] > st.voc_window[0]:
+                    vgroups.setdefault(st.voc_window[1] - st.voc_window[0], []).append(s)
+            for _, members in vgroups.items():
+                wins = [b["mel"][s, :, steps[s].voc_window[0] - self.origin[s]:steps[s].voc_window[1] - self.origin[s]] for s in members]
+                wav = codec.vocoder(torch.stack(wins).contiguous())
+                for i, s in enumerate(members):
+                    st = steps[s]
+                    lo = st.voc_window[0]
+                    out[s] = (wav[i, :, (st.emit[0] - lo) * self.up:(st.emit[1] - lo) * self.up].clone(), out[s][1])
+        for s in final:
+            self.sched[s] = None          # the slot is free; its rows are zeroed when it is opened and pushed to again
+        return out
+
+    def close(self, slot: int):
+        """no more tokens for this slot: its remaining (audio, mel), and the slot is free"""
+        self._check_open(slot)
+        dev = self.buf["mel"].device if self.buf is not None else next(self.codec.parameters()).device
+        return self.push({slot: torch.empty(self.G, 0, dtype=torch.int32, device=dev)}, final=(slot,))[slot]

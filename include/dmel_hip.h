@@ -310,7 +310,8 @@ int dmel_wavenet_stream_step_ex(const dmel_wavenet* m, const float* x /*nullable
  * cap); a bad row is DMEL_EINVAL, dmel_last_error names the utterance, and nothing is launched.  A row may carry any number of new
  * columns: the step is cut into sub-steps of at most 96 new columns per level, as many as the longest row needs, and a row that is done
  * early is idle in the later ones.  Only the stacks of the one-launch kernel are taken (residual channels in (32, 80], no condition, no
- * output projection, dilations <= 8, DMEL_PRECISION_FP32): everything else is DMEL_EUNSUPPORTED -- there is no layered per-item step.
+ * output projection, dilations <= 8, DMEL_PRECISION_FP32): everything else is DMEL_EUNSUPPORTED from this entry -- the layered per-item
+ * step is dmel_wavenet_stream_step_items_layered below.
  *   scratch: that of dmel_wavenet_stream_step_ex (N * 2 C * cap floats followed by N int64) FOLLOWED BY
  *     (N / group_repeat) * (2 (L + 1) + 1) int32: the rows of a sub-step as the kernel reads them.
  * The host tables are copied as launch arguments: the caller may overwrite them as soon as the call returns.  Every item has the bits
@@ -318,6 +319,20 @@ int dmel_wavenet_stream_step_ex(const dmel_wavenet* m, const float* x /*nullable
 int dmel_wavenet_stream_step_items(const dmel_wavenet* m, const float* x /*nullable*/, float* hist, float* skip, const float* cond /*NULL*/,
                                    float* y, float* scratch, int N, int64_t cap, const int64_t* prev, const int64_t* next,
                                    const int64_t* out_lengths /*nullable*/, int group_repeat, const int64_t* origin, void* stream);
+
+/* The same per-utterance step through the LAYERED path, for every stack dmel_wavenet_stream_step / _ex serve layer by layer: conditioned
+ * (cond (N, Ccond, cap), the caller writes its new columns), any width, with or without input and output projection -- the decoder
+ * WaveNet of independent live decode sessions.  Arguments, host tables, row checks (a bad row is DMEL_EINVAL naming the utterance, nothing
+ * is launched), idle rows and the scratch (table included) are those of dmel_wavenet_stream_step_items.  The rows go to the device once
+ * per call, as launch arguments; each of the ~2 L + 3 launches (input projection, L x (gate conv, copy, res / skip conv), skip and
+ * output projection) runs over all N items and reads its level's window of every item from that table, so an item's columns have the
+ * bits dmel_wavenet_stream_step gives them when that item is stepped alone (same K order, partial products and epilogues; every tile
+ * accumulates K in the same order).  The windows are built into the split kernels: DMEL_PRECISION_FP32 / FP32_BF16X3 / FP32_F16X2.  A
+ * handle at DMEL_PRECISION_BF16 or FP32_MFMA, or a process with DMEL_CONV_FP32_MFMA set, is DMEL_EUNSUPPORTED with nothing touched. */
+int dmel_wavenet_stream_step_items_layered(const dmel_wavenet* m, const float* x /*nullable*/, float* hist, float* skip,
+                                           const float* cond /*nullable*/, float* y, float* scratch, int N, int64_t cap, const int64_t* prev,
+                                           const int64_t* next, const int64_t* out_lengths /*nullable*/, int group_repeat,
+                                           const int64_t* origin, void* stream);
 
 /* ConvNeXtBlock (models/modules/firefly.py:337-402; C-ABI row `convnext_block`), standalone: y = x + gamma * pwconv2(gelu(pwconv1(
  * LayerNorm_C(dwconv7(x))))), x / y (N, dim, T).  set_tensor keys: dwconv.weight (dim,1,7), dwconv.bias, norm.weight, norm.bias,

@@ -129,6 +129,54 @@ static void wavenet(int Cin, int Cout, int C, int L, int cycle, int Cc, int N, i
       std::printf("FAIL stream_step_items took a stack outside the one-launch kernel\n"); ++failures;
     }
   }
+  if (Cin == C) {   // any of these stacks per utterance through the LAYERED step: per-item column windows, good and bad tables
+    const int64_t cap = 256;
+    const int L1 = L + 1, R = N;
+    auto hist = buf((size_t)L1 * N * C * cap), skip = buf((size_t)N * C * cap), cond = buf((size_t)N * (Cc ? Cc : 1) * cap),
+         yy = buf((size_t)N * Cout * cap);
+    std::vector<float> sc((size_t)2 * N * C * cap + 2 * N + (size_t)R * (2 * L1 + 1));
+    std::vector<int64_t> F(L1), lens(R, 125);
+    F[0] = 100;
+    for (int l = 1; l <= L; ++l) F[l] = F[l - 1] - (cycle ? 1 << ((l - 1) % cycle) : 1);
+    // rows: 0 the first push from frame 0, 1 mid-stream behind an origin, 2 final, 3 idle
+    std::vector<int64_t> P((size_t)R * L1), Q((size_t)R * L1), O(R, 0);
+    for (int r = 0; r < R; ++r)
+      for (int l = 0; l <= L; ++l) {
+        P[(size_t)r * L1 + l] = r % 4 == 0 ? 0 : F[l];
+        Q[(size_t)r * L1 + l] = r % 4 == 1 ? F[l] + 20 : r % 4 == 2 ? 130 : F[l];
+        if (r % 4 == 1) O[r] = 7;
+      }
+    auto layered = [&](int n) {
+      return dmel_wavenet_stream_step_items_layered(m, nullptr, hist.data(), skip.data(), Cc ? cond.data() : nullptr, yy.data(), sc.data(), n, cap,
+                                                    P.data(), Q.data(), lens.data(), 1, O.data(), nullptr);
+    };
+    CK(dmel_wavenet_set_precision(m, DMEL_PRECISION_FP32));
+    CK(layered(N));
+    auto refused = [&](const char* what, int code, const char* names) {
+      const int rc = layered(N);
+      if (rc != code || !std::strstr(dmel_last_error(), names)) { std::printf("FAIL stream_step_items_layered accepted %s (%d: %s)\n", what, rc, dmel_last_error()); ++failures; }
+    };
+    const auto P0 = P, Q0 = Q;
+    if (L >= 2 && R > 1) { Q[(size_t)1 * L1 + 2] = Q[(size_t)1 * L1 + 1]; refused("a level as far as its input", DMEL_EINVAL, "utterance 1"); Q = Q0; }
+    Q[(size_t)(R - 1) * L1] = cap + 1; refused("a row past the capacity", DMEL_EINVAL, "utterance"); Q = Q0;
+    if (R > 1) {
+      for (int l = 0; l <= L; ++l) { Q[(size_t)1 * L1 + l] -= P0[(size_t)1 * L1 + L]; P[(size_t)1 * L1 + l] -= P0[(size_t)1 * L1 + L]; }
+      refused("a window in front of an origin > 0", DMEL_EINVAL, "utterance 1");
+      P = P0; Q = Q0;
+    }
+    O[0] = -1; refused("a negative origin", DMEL_EINVAL, "utterance 0"); O[0] = 0;
+    for (int prec : {DMEL_PRECISION_BF16, DMEL_PRECISION_FP32_MFMA}) {
+      CK(dmel_wavenet_set_precision(m, prec));
+      refused("a mode without per-item windows", DMEL_EUNSUPPORTED, "split kernels");
+    }
+    for (int prec : {DMEL_PRECISION_FP32_F16X2, DMEL_PRECISION_FP32_BF16X3, DMEL_PRECISION_FP32}) {
+      CK(dmel_wavenet_set_precision(m, prec));
+      CK(layered(N));
+    }
+    for (auto& v : Q) v = 0;      // every row idle: nothing to launch
+    for (auto& v : P) v = 0;
+    CK(layered(N));
+  }
   dmel_wavenet_destroy(m);
 }
 

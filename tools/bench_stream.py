@@ -6,7 +6,13 @@ first audio, the sustained audio-seconds per second at batch 1, and the windowed
 
 runs only this: two streaming decoders fed the same 64-token chunks, one at the vocoder's rate (output_sample_rate=None) and one with a
 StreamResampler behind the vocoder, push i of one followed by push i of the other, each push bracketed by a host synchronisation and timed
-on the wall clock; median and 10th / 90th percentile over the steady-state pushes, at batch 1 and 16, APPENDED to --out."""
+on the wall clock; median and 10th / 90th percentile over the steady-state pushes, at batch 1 and 16, APPENDED to --out.
+
+    python tools/bench_stream.py --sessions 16 [--out profiles/decode_sessions.txt]
+
+runs only this: S independent replies whose starts are offset by a third of a push, served (a) by ONE VQGAN.decode_sessions pool step and
+(b) by S StreamingDecoder(batch=1) stepped in turn -- what a server could do before the pool existed, so (b) stands for the parent commit.
+Both get the same tokens and noise, are interleaved in one process, and every piece of (a) is checked to equal the piece of (b)."""
 import json, os, statistics, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -67,6 +73,69 @@ def output_rate_section(sr, out):
     print("\n".join(table), file=sys.stderr)
     print(json.dumps(result))
 
+
+def sessions_section(S, out):
+    chunk, warmup, steps = 64, 6, 40
+    pct = lambda v, q: sorted(v)[min(len(v) - 1, int(q * len(v)))]
+    gl = torch.Generator().manual_seed(7)
+    G, Cn = codec.dmel_groups, codec.decoder.input_channels
+    total = chunk * (steps + 1)
+    ids = torch.randint(0, 175, (S, G, total), generator=gl, dtype=torch.int32).to(dev)
+    noise = torch.randn(S, Cn, total * 4, device=dev)
+    pool = codec.decode_sessions(S, max_push_tokens=chunk)
+    slots = [pool.open() for _ in range(S)]
+    singles = [codec.streaming_decoder(1, None, True) for _ in range(S)]
+    pos = [0] * S
+    ms = {"pool": [], "singles": []}
+
+    def run_pool(n):
+        out = pool.push({slots[i]: ids[i, :, pos[i]:pos[i] + n[i]] for i in range(S)},
+                        noise={slots[i]: noise[i, :, 4 * pos[i]:4 * (pos[i] + n[i])] for i in range(S)})
+        return [out[slots[i]][0] for i in range(S)]
+
+    def run_singles(n):
+        return [singles[i].push(ids[i:i + 1, :, pos[i]:pos[i] + n[i]], noise=noise[i:i + 1, :, 4 * pos[i]:4 * (pos[i] + n[i])])[0][0]
+                for i in range(S)]
+
+    for step in range(steps):
+        # the first push of session i is (i % 3) thirds of a push short, so the sessions' frontiers stay a third of a push apart
+        n = [chunk - (i % 3) * (chunk // 3) if step == 0 else chunk for i in range(S)]
+        got = {}
+        for k, fn in ((("pool", run_pool), ("singles", run_singles)) if step % 2 == 0 else (("singles", run_singles), ("pool", run_pool))):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            got[k] = fn(n)
+            torch.cuda.synchronize()
+            if step >= warmup:
+                ms[k].append((time.perf_counter() - t0) * 1e3)
+        for i in range(S):
+            assert torch.equal(got["pool"][i], got["singles"][i]), f"step {step}, session {i}: the pool's audio differs"
+            pos[i] += n[i]
+    audio_s = S * chunk * 4 * 256 / 24000
+    rows, result = [], {"sessions": S, "chunk_tokens": chunk}
+    for k, v in ms.items():
+        med = statistics.median(v)
+        result[k] = {"median_ms": round(med, 3), "p10_ms": round(pct(v, 0.1), 3), "p90_ms": round(pct(v, 0.9), 3), "n": len(v),
+                     "audio_sec_per_sec": round(audio_s / (med * 1e-3), 1)}
+        rows.append(f"{S:8d}  {k:8s}  {med:9.3f}  {pct(v, 0.1):9.3f}  {pct(v, 0.9):9.3f}  {len(v):4d}  {audio_s / (med * 1e-3):10.1f}")
+    result["speedup_median"] = round(result["singles"]["median_ms"] / result["pool"]["median_ms"], 3)
+    table = [f"{S} independent decode sessions, {chunk}-token pushes, starts a third of a push apart, 100 mel / 10 groups, BigVGAN base "
+             f"(tools/bench_stream.py --sessions {S})",
+             f"wall time of one step of all sessions incl. host synchronisation, {steps - warmup} steady-state steps, the two interleaved in one process, "
+             "equal audio checked;",
+             "pool = one VQGAN.decode_sessions step; singles = S StreamingDecoder(batch=1) pushed in turn (the parent commit's way)",
+             "sessions  served by  median ms     p10 ms     p90 ms     n  audio-s / s"] + rows + [f"pool / singles: {result['speedup_median']:.3f}x at the median"]
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "a") as f:
+        f.write("\n".join(table) + "\n\n")
+    print("\n".join(table), file=sys.stderr)
+    print(json.dumps(result))
+
+
+if "--sessions" in sys.argv:
+    sessions_section(int(arg_after("--sessions")),
+                     arg_after("--out", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "decode_sessions.txt")))
+    sys.exit(0)
 
 if "--output-sample-rate" in sys.argv:
     output_rate_section(int(arg_after("--output-sample-rate")),
