@@ -53,6 +53,8 @@ PROTOTYPES = {
     "dmel_resample_f32": (C.c_int, [vp, vp, vp, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, vp]),
     "dmel_resample_window_f32": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                            C.c_int, vp]),
+    "dmel_resample_window_items_f32": (C.c_int, [vp, C.c_int64, C.c_int64, i64p, i64p, vp, C.c_int64, i64p, vp, C.c_int64, i64p, C.c_int, i64p,
+                                                 C.c_int, i64p, i64p, i64p, vp, vp]),
     "dmel_stft_f32": (C.c_int, [vp, vp, C.c_int64, vp, vp, vp, C.c_int, C.c_int64, vp]),
     "dmel_stft_window_f32": (C.c_int, [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, vp]),
     "dmel_stft_window_items_f32": (C.c_int, [vp, vp, C.c_int64, C.c_int64, i64p, i64p, vp, vp, vp, C.c_int, i64p, i64p, i64p, vp, vp]),

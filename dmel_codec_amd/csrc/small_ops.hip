@@ -423,10 +423,41 @@ __device__ __forceinline__ float resample_taps(const float* __restrict__ xb, int
 // x (B, row_stride) holds the absolute samples [s0, ...) of a signal of L samples; the launch writes the absolute outputs
 // [o0, o0 + n_out) to y (B, n_out).  The whole clip is (s0, o0, n_out) = (0, 0, Lout).  The host has checked that every tap inside
 // [0, L) lies in the buffer (dmel_resample_window_f32).
+// ITEMS (dmel_resample_window_items_f32): row b is a stream of its own, with its own window AND its own rate pair.  (s0, n_valid, o0,
+// n_out, L, y_off, rate) are row blockIdx.y of `items`, (bank_off, down, up, width) row `rate` of `rates`; `bank` is then the arena
+// all banks lie in, and item b's outputs go to y + b * y_row_stride + y_off.  Only where a workgroup finds its window, its bank and
+// its store differs; the taps of an output do not.
+constexpr int kResampleItemWords = 7, kResampleRateWords = 4;
+// one int64 of a table row, read at the same address by every thread of the workgroup
+__device__ __forceinline__ int64_t uniform_i64(const int64_t* p) {
+  const int64_t v = *p;
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+  const uint32_t hi = __builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)v >> 32));
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+template <bool ITEMS>
 __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__ x, int64_t row_stride, int64_t s0, float* __restrict__ y,
                                                        const float* __restrict__ bank, int64_t L, int64_t o0, int64_t n_out, int down,
-                                                       int up, int width, int kw, int bank_in_lds) {
+                                                       int up, int width, int kw, int bank_in_lds, const int64_t* __restrict__ items,
+                                                       const int64_t* __restrict__ rates, int64_t y_row_stride) {
   extern __shared__ float bsm[];
+  int64_t y_at = (int64_t)blockIdx.y * n_out;                 // where the row's first output of this launch goes
+  if constexpr (ITEMS) {
+    const int64_t* it = items + kResampleItemWords * (int64_t)blockIdx.y;
+    n_out = uniform_i64(it + 3);
+    if ((int64_t)blockIdx.x * 256 >= n_out) return;           // workgroup-uniform, before the bank is staged and before the barrier
+    s0 = uniform_i64(it);
+    o0 = uniform_i64(it + 2);
+    L = uniform_i64(it + 4);
+    y_at = (int64_t)blockIdx.y * y_row_stride + uniform_i64(it + 5);
+    const int64_t* rt = rates + kResampleRateWords * uniform_i64(it + 6);
+    bank += uniform_i64(rt);
+    down = (int)uniform_i64(rt + 1);
+    up = (int)uniform_i64(rt + 2);
+    width = (int)uniform_i64(rt + 3);
+    kw = 2 * width + down;
+    bank_in_lds = up * kw <= kResampleLdsFloats;              // the launch's LDS covers the largest bank that is staged
+  }
   if (bank_in_lds) {
     for (int i = threadIdx.x; i < up * kw; i += 256) bsm[i] = bank[i];
     __syncthreads();
@@ -438,7 +469,7 @@ __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__
   const int64_t o = o0 + i;
   const int64_t n = o / up;
   const int p = (int)(o - n * up);
-  y[(int64_t)b * n_out + i] = resample_taps(x + (int64_t)b * row_stride, s0, bk + (int64_t)p * kw, n * down - width, L, kw);
+  y[y_at + i] = resample_taps(x + (int64_t)b * row_stride, s0, bk + (int64_t)p * kw, n * down - width, L, kw);
 }
 
 int launch_resample_window(const float* x, int64_t row_stride, int64_t s0, int64_t n_samples, float* y, const float* bank_dev, int B,
@@ -447,9 +478,23 @@ int launch_resample_window(const float* x, int64_t row_stride, int64_t s0, int64
   const int in_lds = up * kw <= kResampleLdsFloats;
   {
     ProfScope ps("small", s, 0.0, 4.0 * (double)B * ((double)n_samples + (double)n_out));
-    hipLaunchKernelGGL(resample_kernel, dim3((unsigned)((n_out + 255) / 256), (unsigned)B), dim3(256),
+    hipLaunchKernelGGL(resample_kernel<false>, dim3((unsigned)((n_out + 255) / 256), (unsigned)B), dim3(256),
                        in_lds ? (size_t)up * kw * sizeof(float) : 0, s, x, row_stride, s0, y, bank_dev, L, o0, n_out, down, up, width, kw,
-                       in_lds);
+                       in_lds, nullptr, nullptr, 0);
+  }
+  DMEL_HIP(hipGetLastError());
+  return DMEL_OK;
+}
+
+// items / rates: the device tables the ITEMS kernel reads; max_out: the longest item's n_out; lds_floats: the largest staged bank
+int launch_resample_window_items(const float* x, int64_t row_stride, float* y, int64_t y_row_stride, const float* arena_dev, int B,
+                                 const int64_t* items_dev, const int64_t* rates_dev, int64_t max_out, int lds_floats, double bytes,
+                                 hipStream_t s) {
+  {
+    ProfScope ps("small", s, 0.0, bytes);
+    hipLaunchKernelGGL(resample_kernel<true>, dim3((unsigned)((max_out + 255) / 256), (unsigned)B), dim3(256),
+                       (size_t)lds_floats * sizeof(float), s, x, row_stride, 0, y, arena_dev, 0, 0, 0, 0, 0, 0, 0, 0, items_dev, rates_dev,
+                       y_row_stride);
   }
   DMEL_HIP(hipGetLastError());
   return DMEL_OK;
@@ -723,20 +768,18 @@ extern "C" int dmel_resample_f32(const float* x, float* y, const float* filter_b
 }
 
 // ---- outputs of a window of a longer signal (include/dmel_hip.h: dmel_resample_window_f32) ----------------------------------------
-extern "C" int dmel_resample_window_f32(const float* x, int64_t x_row_stride, int64_t n_samples, int64_t s0, float* y,
-                                        const float* filter_bank_dev, int B, int64_t o0, int64_t n_out, int64_t total_length,
-                                        int orig_freq, int new_freq, int width, void* stream) {
-  DMEL_CHECK_ARG(x && y && filter_bank_dev, "resample_window: NULL argument");
-  DMEL_CHECK_ARG(B > 0 && B <= 65535 && orig_freq > 0 && new_freq > 0 && width >= 0, "resample_window: bad shape");
-  DMEL_CHECK_ARG(n_samples > 0 && x_row_stride >= n_samples && s0 >= 0 && o0 >= 0 && n_out > 0, "resample_window: bad window");
+// the window rules for one buffer [s0, s0 + n_samples) and one rate pair; *L_out: the signal length the kernel pads at.  who: "" or "item b: "
+static int resample_window_check(int64_t n_samples, int64_t s0, int64_t o0, int64_t n_out, int64_t total_length, int64_t orig_freq,
+                                 int64_t new_freq, int64_t width, const char* who, int64_t* L_out) {
+  DMEL_CHECK_ARG(n_samples > 0 && s0 >= 0 && o0 >= 0 && n_out > 0, "resample_window: %sbad window", who);
   const bool known = total_length >= 0;
   const int64_t have_end = s0 + n_samples;                 // the buffer holds absolute samples [s0, have_end)
-  DMEL_CHECK_ARG(have_end < ((int64_t)1 << 40) && o0 + n_out < ((int64_t)1 << 40), "resample_window: position out of range");
+  DMEL_CHECK_ARG(have_end < ((int64_t)1 << 40) && o0 + n_out < ((int64_t)1 << 40), "resample_window: %sposition out of range", who);
   if (known) {
-    DMEL_CHECK_ARG(total_length < ((int64_t)1 << 40), "resample_window: position out of range");
-    DMEL_CHECK_ARG(have_end <= total_length, "resample_window: the buffer runs past the end of the signal");
+    DMEL_CHECK_ARG(total_length < ((int64_t)1 << 40), "resample_window: %sposition out of range", who);
+    DMEL_CHECK_ARG(have_end <= total_length, "resample_window: %sthe buffer runs past the end of the signal", who);
     DMEL_CHECK_ARG(o0 + n_out <= (total_length * new_freq + orig_freq - 1) / orig_freq,
-                   "resample_window: outputs past ceil(new_freq * total_length / orig_freq)");
+                   "resample_window: %soutputs past ceil(new_freq * total_length / orig_freq)", who);
   }
   const int64_t L = known ? total_length : ((int64_t)1 << 62);
   // every sample the outputs read must lie in the buffer or in the zero padding: output o reads
@@ -744,8 +787,71 @@ extern "C" int dmel_resample_window_f32(const float* x, int64_t x_row_stride, in
   const int64_t first = (o0 / new_freq) * orig_freq - width, last_end = ((o0 + n_out - 1) / new_freq) * orig_freq + width + orig_freq;
   const int64_t lo = std::max<int64_t>(first, 0), hi = std::min(last_end, L);
   DMEL_CHECK_ARG(lo >= hi || (s0 <= lo && hi <= have_end),
-                 "resample_window: outputs [%lld, %lld) read samples [%lld, %lld), the buffer holds [%lld, %lld)", (long long)o0,
+                 "resample_window: %soutputs [%lld, %lld) read samples [%lld, %lld), the buffer holds [%lld, %lld)", who, (long long)o0,
                  (long long)(o0 + n_out), (long long)lo, (long long)hi, (long long)s0, (long long)have_end);
+  *L_out = L;
+  return DMEL_OK;
+}
+
+extern "C" int dmel_resample_window_f32(const float* x, int64_t x_row_stride, int64_t n_samples, int64_t s0, float* y,
+                                        const float* filter_bank_dev, int B, int64_t o0, int64_t n_out, int64_t total_length,
+                                        int orig_freq, int new_freq, int width, void* stream) {
+  DMEL_CHECK_ARG(x && y && filter_bank_dev, "resample_window: NULL argument");
+  DMEL_CHECK_ARG(B > 0 && B <= 65535 && orig_freq > 0 && new_freq > 0 && width >= 0, "resample_window: bad shape");
+  DMEL_CHECK_ARG(x_row_stride >= n_samples, "resample_window: bad window");
+  int64_t L;
+  DMEL_TRY(resample_window_check(n_samples, s0, o0, n_out, total_length, orig_freq, new_freq, width, "", &L));
   return dmel::launch_resample_window(x, x_row_stride, s0, n_samples, y, filter_bank_dev, B, L, o0, n_out, orig_freq, new_freq, width,
                                       (hipStream_t)stream);
+}
+
+// ---- the same for B independent streams, each at its own rate (include/dmel_hip.h: dmel_resample_window_items_f32) ---------------
+extern "C" int dmel_resample_window_items_f32(const float* x, int64_t x_row_stride, int64_t n_samples, const int64_t* s0,
+                                              const int64_t* n_valid, float* y, int64_t y_row_stride, const int64_t* y_off,
+                                              const float* bank_arena_dev, int64_t bank_arena_floats, const int64_t* rates, int n_rates,
+                                              const int64_t* rate_index, int B, const int64_t* o0, const int64_t* n_out,
+                                              const int64_t* total_length, int64_t* table_scratch, void* stream) {
+  using namespace dmel;
+  DMEL_CHECK_ARG(x && y && bank_arena_dev && s0 && n_valid && y_off && rates && rate_index && o0 && n_out && total_length && table_scratch,
+                 "resample_window_items: NULL argument");
+  DMEL_CHECK_ARG(B > 0 && B <= 65535 && n_rates > 0 && n_rates <= 4096, "resample_window_items: bad shape");
+  DMEL_CHECK_ARG(n_samples > 0 && x_row_stride >= n_samples && y_row_stride > 0 && bank_arena_floats > 0,
+                 "resample_window_items: bad buffer width");
+  std::vector<int64_t> tab((size_t)kResampleItemWords * B + (size_t)kResampleRateWords * n_rates, 0);   // an idle item keeps n_out = 0
+  int64_t max_out = 0;
+  int lds_floats = 0;
+  double bytes = 0.0;
+  for (int b = 0; b < B; ++b) {
+    DMEL_CHECK_ARG(n_out[b] >= 0, "resample_window_items: item %d: negative output count", b);
+    if (n_out[b] == 0) continue;
+    DMEL_CHECK_ARG(rate_index[b] >= 0 && rate_index[b] < n_rates, "resample_window_items: item %d: rate %lld of %d", b,
+                   (long long)rate_index[b], n_rates);
+    const int64_t* r = rates + kResampleRateWords * rate_index[b];
+    const int64_t bank_off = r[0], orig = r[1], nw = r[2], width = r[3];
+    DMEL_CHECK_ARG(orig > 0 && nw > 0 && width >= 0 && orig < (1 << 20) && nw < (1 << 20) && width < (1 << 20),
+                   "resample_window_items: item %d: bad rate %lld -> %lld, width %lld", b, (long long)orig, (long long)nw, (long long)width);
+    const int64_t kw = 2 * width + orig;
+    DMEL_CHECK_ARG(bank_off >= 0 && bank_off + nw * kw <= bank_arena_floats,
+                   "resample_window_items: item %d: its bank [%lld, %lld) lies outside the arena of %lld floats", b, (long long)bank_off,
+                   (long long)(bank_off + nw * kw), (long long)bank_arena_floats);
+    DMEL_CHECK_ARG(n_valid[b] <= n_samples, "resample_window_items: item %d: %lld valid samples in a buffer of %lld", b,
+                   (long long)n_valid[b], (long long)n_samples);
+    DMEL_CHECK_ARG(y_off[b] >= 0 && y_off[b] + n_out[b] <= y_row_stride,
+                   "resample_window_items: item %d: outputs [%lld, %lld) do not fit an output row of %lld", b, (long long)y_off[b],
+                   (long long)(y_off[b] + n_out[b]), (long long)y_row_stride);
+    char who[32];
+    std::snprintf(who, sizeof(who), "item %d: ", b);
+    int64_t L;
+    DMEL_TRY(resample_window_check(n_valid[b], s0[b], o0[b], n_out[b], total_length[b], orig, nw, width, who, &L));
+    int64_t* it = tab.data() + (size_t)kResampleItemWords * b;
+    it[0] = s0[b]; it[1] = n_valid[b]; it[2] = o0[b]; it[3] = n_out[b]; it[4] = L; it[5] = y_off[b]; it[6] = rate_index[b];
+    max_out = std::max(max_out, n_out[b]);
+    if (nw * kw <= kResampleLdsFloats) lds_floats = std::max(lds_floats, (int)(nw * kw));
+    bytes += 4.0 * ((double)n_valid[b] + (double)n_out[b]);
+  }
+  if (max_out == 0) return DMEL_OK;                   // every item idle
+  std::memcpy(tab.data() + (size_t)kResampleItemWords * B, rates, (size_t)kResampleRateWords * n_rates * sizeof(int64_t));
+  DMEL_TRY(launch_table_put(tab.data(), tab.size() * sizeof(int64_t), table_scratch, (hipStream_t)stream));
+  return launch_resample_window_items(x, x_row_stride, y, y_row_stride, bank_arena_dev, B, table_scratch,
+                                      table_scratch + (size_t)kResampleItemWords * B, max_out, lds_floats, bytes, (hipStream_t)stream);
 }

@@ -399,13 +399,16 @@ class VQGAN(nn.Module):
         if ids.shape[-1]:
             yield ids
 
-    def encode_sessions(self, slots: int, max_push_samples: int = 7680, sample_rate: Optional[int] = None):
+    def encode_sessions(self, slots: int, max_push_samples: int = 7680, sample_rate: Optional[int] = None, sample_rates=()):
         """A pool of `slots` INDEPENDENT incremental encodes served by one streaming step: sessions open, receive their own number of
         samples per step (at most max_push_samples), stall and close on their own -- what streaming_encoder(batch=B), B streams in
         lockstep, cannot do -- and each one's concatenated ids are the bits of encode() on its own clip.  One STFT launch and one encoder
-        launch per step whatever the number of slots.  Codec rate only; see models/stream_sessions.py: EncodeSessions."""
+        launch per step whatever the number of slots.  sample_rates: the rates sessions may arrive at (a browser's 48 kHz, telephony's
+        16 kHz, ...); pool.open(sample_rate=r) then starts a session whose pushes are in samples of rate r and whose ids are the bits of
+        encode(clip, len, sample_rate=r), all slots of a step converted by one resample launch.  sample_rate names the codec's own rate
+        only (a pool has no rate of its own).  See models/stream_sessions.py: EncodeSessions."""
         from .stream_sessions import EncodeSessions
-        return EncodeSessions(self, slots, max_push_samples, sample_rate)
+        return EncodeSessions(self, slots, max_push_samples, sample_rate, sample_rates)
 
     # ------------------------------------------------------------------------------ decode side
     @torch.no_grad()
@@ -463,7 +466,9 @@ class VQGAN(nn.Module):
         """A pool of `slots` INDEPENDENT incremental decodes served by one streaming step: replies open, grow by their own number of
         tokens per step (at most max_push_tokens), stall and close on their own -- what streaming_decoder(batch=B), B streams in
         lockstep, cannot do -- and each one's concatenated audio and mel are the bits of decode() on its own ids.  One decoder WaveNet
-        step per pool step whatever the number of slots.  overlap_vocoder, graph_chunk_tokens and output_sample_rate are
+        step per pool step whatever the number of slots.  output_sample_rates=(48000, ...): the playback rates replies may leave at;
+        pool.open(output_sample_rate=r) then starts a reply whose audio is the bits of resample(decode() audio, vocoder rate, r), all
+        slots of a step converted by one resample launch.  overlap_vocoder, graph_chunk_tokens and the pool-wide output_sample_rate are
         NotImplementedError here; see models/stream_sessions.py: DecodeSessions."""
         from .stream_sessions import DecodeSessions
         return DecodeSessions(self, slots, max_push_tokens, return_audios, **options)

@@ -376,3 +376,43 @@ class ResampleSchedule:
         self.emitted = o_new
         self.finished = final
         return st
+
+
+def resample_max_outputs(orig_freq: int, new_freq: int, n: int) -> int:
+    """The largest number of outputs one step of at most `n` samples can release, from any state a ResampleSchedule of this rate pair
+    can be in: what the rows of a pool of resamplers (utils/resample.py: SessionResampler) and of the pools behind it are sized by.
+
+    Mid-stream whole groups are released.  After k samples groups_ready(k) = (k - width) // down for k >= width + down (else 0) of them
+    are out, and floor((k + n - width) / down) - floor((k - width) / down) <= n // down + 1: at most (n // down + 1) * up outputs.
+    The final step flushes up to total_outputs(k + n) = ceil(up (k + n) / down).  With k = width + q down + r, 0 <= r < down, q up
+    outputs are out already (fewer than `width` samples: none, and the flush is shorter still), which leaves
+    ceil(up (width + r + n) / down), largest at r = down - 1.  That covers the mid-stream case as well (width >= 1), so it is the
+    bound."""
+    if n < 0:
+        raise ValueError("negative sample count")
+    sc = ResampleSchedule(orig_freq, new_freq)
+    mid = (n // sc.down + 1) * sc.up
+    last = sc.total_outputs(n + sc.width + sc.down - 1)
+    return max(mid, last)
+
+
+def resample_session_rows(slots: int, steps: Mapping[int, ResampleStep], s0: Sequence[int],
+                          fill: Sequence[int]) -> Tuple[List[int], List[int], List[int], List[int], List[int]]:
+    """session_rows for a pool of resamplers: the per-item tables of dmel_resample_window_items_f32.  steps: slot -> this step's
+    ResampleStep of every slot that takes part; the slot's row holds the absolute samples [s0[slot], s0[slot] + fill[slot]), this
+    step's chunk included.  Returns (s0, n_valid, o0, n_out, total_length), one entry per slot.  A slot without a step, or whose step
+    releases no output, is idle: n_out 0 (and zeros, length unknown).  A step that reads outside its row is refused here, with the
+    slot's name, before the library has to."""
+    rs0, nv, o0, n_out, total = [0] * slots, [0] * slots, [0] * slots, [0] * slots, [-1] * slots
+    for slot, st in steps.items():
+        if not 0 <= slot < slots:
+            raise ValueError(f"slot {slot} out of range")
+        a, b = st.outputs
+        if b <= a:
+            continue
+        lo, hi = st.reads
+        if hi > lo and not (s0[slot] <= lo and hi <= s0[slot] + fill[slot]):
+            raise ValueError(f"slot {slot}: outputs [{a}, {b}) read samples [{lo}, {hi}), the row holds "
+                             f"[{s0[slot]}, {s0[slot] + fill[slot]})")
+        rs0[slot], nv[slot], o0[slot], n_out[slot], total[slot] = s0[slot], fill[slot], a, b - a, st.total_length
+    return rs0, nv, o0, n_out, total

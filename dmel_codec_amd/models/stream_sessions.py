@@ -4,7 +4,9 @@
 StreamingEncoder(batch=B) is B streams in lockstep: one schedule, one origin, one (prev, next) row.  Microphones do not behave like that:
 they start, stall and hang up on their own.  EncodeSessions keeps one EncodeSchedule, one origin and one sample tail PER SLOT and hands
 the kernels one row per slot (dmel_stft_window_items_f32, dmel_wavenet_stream_step_items), so that any subset of the slots advances, each
-by its own number of samples, in one STFT launch and one encoder launch."""
+by its own number of samples, in one STFT launch and one encoder launch.  Sessions whose sound cards do not run at the codec's rate
+declare their own rate when they open; all of them, whatever their rates, are converted by one resample launch per step
+(utils/resample.py: SessionResampler, dmel_resample_window_items_f32)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -15,13 +17,13 @@ import torch
 
 from .. import _lib
 from .stream_schedule import (DecodeGeometry, DecodeSchedule, EncodeGeometry, EncodeSchedule, decode_capacity, decode_rebase,
-                              decode_session_rows, session_rows)
+                              decode_session_rows, resample_max_outputs, session_rows)
 
 
 class EncodeSessions:
     """`slots` independent incremental encodes, each with the ids of encode() on its own finished clip.
 
-        slot = pool.open()                                   # a free slot, fresh state
+        slot = pool.open()                                   # a free slot, fresh state; open(sample_rate=48000): a session at that rate
         ids = pool.push({slot: audio_1d, ...}, final=())     # one step for any subset of the open slots -> {slot: ids (G, m) int32}
         ids = pool.close(slot)                               # = push({slot: empty}, final=(slot,))[slot]
 
@@ -37,17 +39,26 @@ class EncodeSessions:
     has its own origin (the absolute frame in column 0 of ITS rows), its own s0 and sample tail; re-basing shifts one slot's columns
     only.  Memory grows neither with the length of a stream nor with the number of sessions served over time.
 
-    Only the codec's own sample rate, and only encoders the one-launch streaming kernel takes (residual channels in (32, 80], no
-    condition, no output projection, dilations <= 8, fp32): anything else is refused at construction.
+    Sample rates belong to SESSIONS, not to the pool: `sample_rates` declares the rates sessions may arrive at, open(sample_rate=r)
+    starts one.  Such a slot takes its pushes in samples of ITS rate (max_push_samples bounds them in those samples) and its ids are
+    the bits of encode(clip, len, sample_rate=r).  All slots of a step that need converting go through ONE resample launch, which
+    writes straight behind each slot's carried sample tail; the STFT launch and the encoder step follow unchanged.  The rows and the
+    capacity are sized from the most codec-rate samples one push can release over the declared rates (resample_max_outputs).  The
+    constructor's own `sample_rate` only names the codec's rate, as before: a pool has no rate of its own.
+
+    Only encoders the one-launch streaming kernel takes (residual channels in (32, 80], no condition, no output projection,
+    dilations <= 8, fp32): anything else is refused at construction.
 
     All launches are on the current stream, so nothing new meets DESIGN section 7's unexplained wrong-frame behaviour of the STFT next to
     convolutions.  The warning of StreamingEncoder stands: a caller that runs sessions next to convolutions on ANOTHER STREAM of the same
     process -- a streaming decode, for example -- must call dmel_stft_set_exclusive_cu(1) first, exactly as pipeline.CodecLanes does."""
 
-    def __init__(self, codec, slots: int, max_push_samples: int = 7680, sample_rate: Optional[int] = None):
+    def __init__(self, codec, slots: int, max_push_samples: int = 7680, sample_rate: Optional[int] = None,
+                 sample_rates: Iterable[int] = ()):
         enc, tr = codec.encoder, codec.encode_mel_transform
         if sample_rate is not None and int(sample_rate) != int(tr.sample_rate):
-            raise NotImplementedError(f"sessions run at the codec's own rate ({tr.sample_rate} Hz); resample in front (StreamResampler)")
+            raise NotImplementedError(f"sessions run at the codec's own rate ({tr.sample_rate} Hz); resample in front (StreamResampler), "
+                                      f"or declare the sessions' rates (sample_rates=) and open each one at its own (open(sample_rate=))")
         if int(slots) <= 0 or int(max_push_samples) <= 0:
             raise ValueError("slots and max_push_samples must be positive")
         L, Cres = len(enc.residual_layers), enc.residual_channels
@@ -75,6 +86,16 @@ class EncodeSessions:
                                   downsample_factor=tuple(codec.quantizer.downsample_factor))
         self.n_mels = tr.n_mels
         self.max_push = int(max_push_samples)
+        self.codec_rate = int(tr.sample_rate)
+        self.sample_rates = tuple(sorted({int(r) for r in sample_rates} - {self.codec_rate}))
+        if any(r <= 0 for r in self.sample_rates):
+            raise ValueError("sample rates must be positive")
+        # the most samples at the codec's rate one push can put into a slot's row, over the declared rates
+        self.codec_push = max([self.max_push] + [resample_max_outputs(r, self.codec_rate, self.max_push) for r in self.sample_rates])
+        self.rs = None                                # the per-slot resamplers in front, if any rate was declared
+        if self.sample_rates:
+            from ..utils.resample import SessionResampler
+            self.rs = SessionResampler(self.S, [(r, self.codec_rate) for r in self.sample_rates], self.max_push)
         g = self.geo
         left, right = g.quant_context
         F = g.factor
@@ -82,13 +103,14 @@ class EncodeSessions:
         # lies at most `hold` frames behind the newest frame -- to the newest frame of a push (+ 1 for the hop's remainder, + the frames
         # only the end of the signal releases).  Twice that, so that a slot is re-based once in several pushes and not in every one.
         hold = g.encoder_context + right + 1 + F * ((left + F - 1) // F) + F
-        self.want_max = hold + self.max_push // g.hop + 1 + (g.n_fft - g.pad + g.hop - 1) // g.hop
+        self.want_max = hold + self.codec_push // g.hop + 1 + (g.n_fft - g.pad + g.hop - 1) // g.hop
         self.cap = (2 * self.want_max + 31) // 32 * 32
-        self.width = g.n_fft + self.max_push          # samples per row: a tail is shorter than one window
+        self.width = g.n_fft + self.codec_push        # samples per row: a tail is shorter than one window
         self.sched: List[Optional[EncodeSchedule]] = [None] * self.S
         self.origin = [0] * self.S
         self.s0 = [0] * self.S
         self.tail = [0] * self.S                      # valid samples in the slot's row
+        self.rate = [self.codec_rate] * self.S        # the rate the slot's pushes arrive at
         self._fresh = [False] * self.S                # opened, state not zeroed yet (done with the slot's first push)
         self.buf = None
 
@@ -103,21 +125,33 @@ class EncodeSessions:
         return [s for s in range(self.S) if self.sched[s] is not None]
 
     def allocated_bytes(self) -> int:
-        return 0 if self.buf is None else sum(t.numel() * t.element_size() for t in self.buf.values())
+        own = 0 if self.buf is None else sum(t.numel() * t.element_size() for t in self.buf.values())
+        return own + (self.rs.allocated_bytes() if self.rs is not None else 0)
 
     def tokens_emitted(self, slot: int) -> int:
         self._check_open(slot)
         return self.sched[slot].tokens
 
-    def open(self) -> int:
-        """take a free slot: fresh schedule, state zeroed before its first push.  Raises when every slot is taken."""
+    def open(self, sample_rate: Optional[int] = None) -> int:
+        """take a free slot: fresh schedule, state zeroed before its first push.  sample_rate: the rate this session's pushes arrive
+        at, one of the declared `sample_rates` (None: the codec's).  Raises when every slot is taken."""
+        rate = self.codec_rate if sample_rate is None else int(sample_rate)
+        if rate != self.codec_rate and rate not in self.sample_rates:
+            raise ValueError(f"a session at {rate} Hz: the pool was built for {(self.codec_rate,) + self.sample_rates} Hz "
+                             f"(declare the rate in sample_rates=)")
         for s in range(self.S):
             if self.sched[s] is None:
                 self.sched[s] = EncodeSchedule(self.geo)
                 self.origin[s] = self.s0[s] = self.tail[s] = 0
+                self.rate[s] = rate
+                if self.rs is not None:
+                    self.rs.open(s, rate, self.codec_rate)
                 self._fresh[s] = True
                 return s
         raise RuntimeError(f"all {self.S} slots are taken")
+
+    def _converts(self, slot: int) -> bool:
+        return self.rate[slot] != self.codec_rate
 
     def _check_open(self, slot) -> None:
         if not isinstance(slot, int) or not 0 <= slot < self.S:
@@ -143,6 +177,9 @@ class EncodeSessions:
             if slot not in audio:
                 raise ValueError(f"slot {slot} is in `final` but not among the pushed slots")
             total = self.sched[slot].samples + out[slot].shape[0]
+            if self._converts(slot):                  # its length at the codec's rate, as encode(..., sample_rate=) converts it
+                rs = self.rs.sched[slot]
+                total = rs.total_outputs(rs.samples + out[slot].shape[0])
             if total <= self.geo.pad:
                 raise ValueError(f"slot {slot}: the stream is {total} samples long: encode() needs more than the reflect pad {self.geo.pad}")
         for slot, a in out.items():
@@ -188,17 +225,25 @@ class EncodeSessions:
         dev = next(iter(audio.values())).device
         if self.buf is None:
             self._allocate(dev)
+            if self.rs is not None:
+                self.rs.allocate(dev)
         b = self.buf
         steps = {}
+        # ---- the sound cards' rates: ONE launch converts every slot that needs it, straight behind the slot's sample tail
+        converted = {s: a for s, a in audio.items() if self._converts(s)}
+        released = self.rs.push(converted, final & set(converted), out=b["samples"], out_off=self.tail) if converted else {}
         for s, a in audio.items():
             if self._fresh[s]:
                 for v in self._slot_views(s):
                     v.zero_()
                 self._fresh[s] = False
-            n = a.shape[0]
-            if n:
-                b["samples"][s, self.tail[s]:self.tail[s] + n] = a
-                self.tail[s] += n
+            if s in released:
+                n = released[s]
+            else:
+                n = a.shape[0]
+                if n:
+                    b["samples"][s, self.tail[s]:self.tail[s] + n] = a
+            self.tail[s] += n
             steps[s] = self.sched[s].step(n, s in final)
         lib = _lib.lib()
         I64 = C.c_int64 * S
@@ -279,7 +324,7 @@ class EncodeSessions:
 class DecodeSessions:
     """`slots` independent incremental decodes, each with the audio and mel of decode() on its own finished token sequence.
 
-        slot = pool.open()                                              # a free slot, fresh state
+        slot = pool.open()                                              # a free slot, fresh state; open(output_sample_rate=48000)
         out = pool.push({slot: ids (G, n) int, ...}, noise=None | {slot: (C, n * factor)}, final=())
                                                                         # -> {slot: (audio (1, m * up) | None, mel (n_mels, m))}
         out = pool.close(slot)                                          # = push({slot: empty}, final=(slot,))[slot]
@@ -302,7 +347,15 @@ class DecodeSessions:
     token tail and noise tail; re-basing shifts one slot's columns only; a reopened slot's rows are zeroed before its first push.  Memory
     grows neither with the length of a stream nor with the number of sessions served over time.
 
-    Out of scope, NotImplementedError: overlap_vocoder, graph_chunk_tokens, output_sample_rate (the codec's own rate only).
+    Playback rates belong to SESSIONS, not to the pool: `output_sample_rates` declares the rates replies may leave at,
+    open(output_sample_rate=r) starts one.  After the vocoder groups every such slot's new audio piece is copied behind that slot's
+    resampler tail (the copy the codec-rate path spends on detaching the piece from the vocoder's batch), ONE resample launch converts
+    all slots (utils/resample.py: SessionResampler), and a final slot is flushed with its true length.  The slot's audio pieces then
+    concatenate to resample(decode() audio, vocoder rate, r), bit for bit, m * up samples no longer; its mel is the unchanged decode()
+    mel.  return_audios=False with a declared rate is a ValueError.
+
+    Out of scope, NotImplementedError: overlap_vocoder, graph_chunk_tokens, and a pool-wide output_sample_rate (a pool has no rate of
+    its own).
 
     All launches are on the current stream; there is no side stream for the vocoder.  The warning of StreamingEncoder / EncodeSessions
     about the STFT next to convolutions on ANOTHER STREAM applies to this pool's convolutions: a caller that runs
@@ -310,10 +363,17 @@ class DecodeSessions:
     does."""
 
     def __init__(self, codec, slots: int, max_push_tokens: int = 64, return_audios: bool = True, overlap_vocoder: bool = False,
-                 graph_chunk_tokens: Optional[int] = None, output_sample_rate: Optional[int] = None):
+                 graph_chunk_tokens: Optional[int] = None, output_sample_rate: Optional[int] = None,
+                 output_sample_rates: Iterable[int] = ()):
         if overlap_vocoder or graph_chunk_tokens is not None or output_sample_rate is not None:
-            raise NotImplementedError("decode sessions launch everything on the current stream, eagerly, at the codec's own sample rate: "
-                                      "overlap_vocoder, graph_chunk_tokens and output_sample_rate belong to StreamingDecoder")
+            raise NotImplementedError("decode sessions launch everything on the current stream, eagerly, and have no rate of their own: "
+                                      "overlap_vocoder, graph_chunk_tokens and output_sample_rate belong to StreamingDecoder (a session's "
+                                      "playback rate: output_sample_rates= and open(output_sample_rate=))")
+        output_sample_rates = tuple(int(r) for r in output_sample_rates)
+        if output_sample_rates and not return_audios:
+            raise ValueError("output_sample_rates without audio: return_audios=False leaves nothing to resample")
+        if any(r <= 0 for r in output_sample_rates):
+            raise ValueError("sample rates must be positive")
         if codec.decoder is None:
             raise ValueError("Decoder is not loaded")
         if return_audios and codec.vocoder is None:
@@ -336,6 +396,16 @@ class DecodeSessions:
         H, f = self.geo.quant_halo_tokens, self.geo.factor
         self.tok_width = 2 * H + self.max_push            # the token tail starts at most 2 H tokens behind the newest token of the last push
         self.noise_width = (H + self.max_push) * f        # frames [z_valid, tokens * factor): at most H tokens of them in front of a push
+        self.voc_rate = self.rs = None
+        self.output_sample_rates: Tuple[int, ...] = ()
+        if return_audios:
+            self.voc_rate = int(codec.vocoder.h.get("sampling_rate", codec.encode_mel_transform.sample_rate))
+            self.output_sample_rates = tuple(sorted(set(output_sample_rates) - {self.voc_rate}))
+        if self.output_sample_rates:
+            from ..utils.resample import SessionResampler
+            # a step emits frames that all lie in the slot's `cap` columns: at most cap * up samples reach a slot's resampler at once
+            self.rs = SessionResampler(self.S, [(self.voc_rate, r) for r in self.output_sample_rates], self.cap * self.up)
+        self.rate = [self.voc_rate] * self.S              # the rate the slot's audio leaves at
         self.sched: List[Optional[DecodeSchedule]] = [None] * self.S
         self.origin = [0] * self.S
         self.tok_origin = [0] * self.S                    # absolute index of the token in column 0 of the slot's token tail
@@ -354,18 +424,27 @@ class DecodeSessions:
         return [s for s in range(self.S) if self.sched[s] is not None]
 
     def allocated_bytes(self) -> int:
-        return 0 if self.buf is None else sum(t.numel() * t.element_size() for t in self.buf.values())
+        own = 0 if self.buf is None else sum(t.numel() * t.element_size() for t in self.buf.values())
+        return own + (self.rs.allocated_bytes() if self.rs is not None else 0)
 
     def frames_emitted(self, slot: int) -> int:
         self._check_open(slot)
         return self.sched[slot].emitted
 
-    def open(self) -> int:
-        """take a free slot: fresh schedule, state zeroed before its first push.  Raises when every slot is taken."""
+    def open(self, output_sample_rate: Optional[int] = None) -> int:
+        """take a free slot: fresh schedule, state zeroed before its first push.  output_sample_rate: the rate this session's audio
+        leaves at, one of the declared `output_sample_rates` (None: the vocoder's).  Raises when every slot is taken."""
+        rate = self.voc_rate if output_sample_rate is None else int(output_sample_rate)
+        if rate != self.voc_rate and rate not in self.output_sample_rates:
+            raise ValueError(f"a session at {rate} Hz: the pool was built for {(self.voc_rate,) + self.output_sample_rates} Hz "
+                             f"(declare the rate in output_sample_rates=)")
         for s in range(self.S):
             if self.sched[s] is None:
                 self.sched[s] = DecodeSchedule(self.geo)
                 self.origin[s] = self.tok_origin[s] = self.n_noise[s] = 0
+                self.rate[s] = rate
+                if self.rs is not None:
+                    self.rs.open(s, self.voc_rate, rate)
                 self._fresh[s] = True
                 return s
         raise RuntimeError(f"all {self.S} slots are taken")
@@ -438,6 +517,8 @@ class DecodeSessions:
         dev = next(iter(ids.values())).device
         if self.buf is None:
             self._allocate(dev)
+            if self.rs is not None:
+                self.rs.allocate(dev)
         b = self.buf
         steps = {}
         with torch.cuda.device(dev):
@@ -500,13 +581,27 @@ class DecodeSessions:
                 out[s] = (torch.empty(1, 0, dtype=torch.float32, device=dev) if self.return_audios else None, mel)
                 if st.voc_window[1] > st.voc_window[0]:
                     vgroups.setdefault(st.voc_window[1] - st.voc_window[0], []).append(s)
+            pieces: Dict[int, torch.Tensor] = {}       # the new audio of the slots that leave at another rate, still in the vocoder's batch
             for _, members in vgroups.items():
                 wins = [b["mel"][s, :, steps[s].voc_window[0] - self.origin[s]:steps[s].voc_window[1] - self.origin[s]] for s in members]
                 wav = codec.vocoder(torch.stack(wins).contiguous())
                 for i, s in enumerate(members):
                     st = steps[s]
                     lo = st.voc_window[0]
-                    out[s] = (wav[i, :, (st.emit[0] - lo) * self.up:(st.emit[1] - lo) * self.up].clone(), out[s][1])
+                    piece = wav[i, :, (st.emit[0] - lo) * self.up:(st.emit[1] - lo) * self.up]
+                    if self.rate[s] != self.voc_rate:
+                        pieces[s] = piece[0]
+                    else:
+                        out[s] = (piece.clone(), out[s][1])
+            # ---- the playback rates: each piece goes behind its slot's resampler tail, ONE launch converts all slots; a slot without a
+            # new piece still takes part when it ends (the outputs that waited for the end of its signal)
+            if self.rs is not None:
+                for s in steps:
+                    if self.rate[s] != self.voc_rate and s not in pieces and s in final:
+                        pieces[s] = torch.empty(0, dtype=torch.float32, device=dev)
+                if pieces:
+                    for s, y in self.rs.push(pieces, final & set(pieces)).items():
+                        out[s] = (y[None], out[s][1])
         for s in final:
             self.sched[s] = None          # the slot is free; its rows are zeroed when it is opened and pushed to again
         return out

@@ -2,16 +2,19 @@
 LogMelSpectrogram.forward(x, sample_rate=...) (utils/spectrogram.py:122-123; torchaudio's defaults: sinc_interp_hann,
 lowpass_filter_width 6, rolloff 0.99).  The polyphase filter bank is built once per (orig, new, device) on the host, the filtering is
 one HIP launch (csrc/small_ops.hip: resample_kernel, through torch.ops.dmel_hip.resample).  StreamResampler is the same conversion fed
-chunk by chunk (torch.ops.dmel_hip.resample_window -> dmel_resample_window_f32): same kernel, same bits."""
+chunk by chunk (torch.ops.dmel_hip.resample_window -> dmel_resample_window_f32): same kernel, same bits.  SessionResampler is a pool
+of such streams, each at its own rate pair, converted by ONE launch per step (dmel_resample_window_items_f32)."""
 from __future__ import annotations
 
+import ctypes as C
 import math
+from typing import Dict, Iterable, List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from .. import _lib
-from ..models.stream_schedule import ResampleSchedule
+from ..models.stream_schedule import ResampleSchedule, resample_max_outputs, resample_session_rows
 
 _banks: dict = {}
 
@@ -175,3 +178,152 @@ class StreamResampler:
         """no more samples: the outputs that were waiting for right context, computed with the true end of the signal"""
         dev = self._dev if self._dev is not None else torch.device("cuda", torch.cuda.current_device())
         return self.push(torch.empty(self.B, 0, dtype=torch.float32, device=dev), final=True)
+
+
+class SessionResampler:
+    """`slots` independent StreamResamplers, each at its own (orig, new) pair, served by ONE resample launch per step
+    (dmel_resample_window_items_f32) whatever the number of slots and of rates among them.
+
+        pool = SessionResampler(slots, pairs=[(48000, 24000), (16000, 24000)], max_push=n)
+        pool.open(slot, 48000, 24000)                        # fresh schedule; a pair that was not declared is a ValueError
+        pieces = pool.push({slot: chunk_1d, ...}, final=())  # -> {slot: the (m,) outputs that became final with this chunk}
+        counts = pool.push(chunks, final, out=rows, out_off={slot: column})
+                                                             # the launch stores slot s's outputs at rows[s, column:]: -> {slot: m}
+
+    A slot's concatenated pieces are torch.equal to resample(its whole signal, orig, new).  A slot whose rates are equal passes through
+    untouched (its chunk is returned, or copied to `out`).  A slot in `final` is flushed with its true length and closed.
+
+    State: one ResampleSchedule, one s0 and one tail per slot; rows of constant width, sized at construction from the declared pairs
+    (the longest tail any of them carries, kw - 1 samples) and `max_push`; one arena with the banks of all declared pairs.  Per step:
+    every named slot's chunk is copied behind its tail, ONE launch converts all named slots, every slot's new tail moves to the front
+    of its row.  No host synchronisation; everything runs on the current stream."""
+
+    def __init__(self, slots: int, pairs: Iterable[Tuple[int, int]], max_push: int):
+        if int(slots) <= 0 or int(max_push) <= 0:
+            raise ValueError("slots and max_push must be positive")
+        self.S, self.max_push = int(slots), int(max_push)
+        self.pairs: List[Tuple[int, int]] = []
+        for o, n in pairs:
+            o, n = int(o), int(n)
+            if o <= 0 or n <= 0:
+                raise ValueError("Original frequency and desired frequecy should be positive")
+            if o != n and (o, n) not in self.pairs:
+                self.pairs.append((o, n))
+        if not self.pairs:
+            raise ValueError("no rate pair to convert: equal rates need no resampler")
+        scheds = [ResampleSchedule(o, n) for o, n in self.pairs]
+        self.width = max(sc.kw for sc in scheds) - 1 + self.max_push        # samples per row: the longest tail and one chunk
+        self.max_out = max(resample_max_outputs(o, n, self.max_push) for o, n in self.pairs)
+        # the rate descriptors of the C entry: (bank_off, down, up, width) per declared pair, banks back to back in one arena
+        self.rates: List[int] = []
+        off = 0
+        for sc in scheds:
+            self.rates += [off, sc.down, sc.up, sc.width]
+            off += sc.up * sc.kw
+        self.arena_floats = off
+        self.sched: List[Optional[ResampleSchedule]] = [None] * self.S
+        self.rate = [0] * self.S                      # index into pairs; -1: equal rates, nothing to convert
+        self.s0 = [0] * self.S
+        self.fill = [0] * self.S                      # valid samples in the slot's row
+        self.buf = None
+
+    def allocated_bytes(self) -> int:
+        return 0 if self.buf is None else sum(t.numel() * t.element_size() for t in self.buf.values())
+
+    def open(self, slot: int, orig_freq: int, new_freq: int) -> None:
+        """slot starts a fresh stream at this pair (whatever it held before is forgotten)"""
+        if not 0 <= slot < self.S:
+            raise ValueError(f"slot {slot!r} out of range (0 .. {self.S - 1})")
+        o, n = int(orig_freq), int(new_freq)
+        if o != n and (o, n) not in self.pairs:
+            raise ValueError(f"{o} -> {n} Hz was not declared at construction ({self.pairs})")
+        self.sched[slot] = ResampleSchedule(o, n)
+        self.rate[slot] = -1 if o == n else self.pairs.index((o, n))
+        self.s0[slot] = self.fill[slot] = 0
+
+    def close(self, slot: int) -> None:
+        self.sched[slot] = None
+
+    def is_open(self, slot: int) -> bool:
+        return self.sched[slot] is not None
+
+    def allocate(self, dev) -> None:
+        """the rows, the bank arena and the table scratch, once"""
+        if self.buf is not None:
+            return
+        arena = torch.cat([filter_bank(o, n, dev)[0].reshape(-1) for o, n in self.pairs])
+        assert arena.numel() == self.arena_floats
+        self.buf = dict(rows=torch.zeros(self.S, self.width, dtype=torch.float32, device=dev), arena=arena.contiguous(),
+                        table=torch.empty(7 * self.S + len(self.rates), dtype=torch.int64, device=dev))
+
+    @torch.no_grad()
+    def push(self, chunks: Mapping[int, torch.Tensor], final: Iterable[int] = (), out: Optional[torch.Tensor] = None,
+             out_off: Optional[Mapping[int, int]] = None) -> Dict[int, object]:
+        final = set(final)
+        for s, x in chunks.items():
+            if not 0 <= s < self.S or self.sched[s] is None:
+                raise RuntimeError(f"slot {s} is not open")
+            if x.ndim != 1:
+                raise ValueError(f"slot {s}: expected (n,) samples, got {tuple(x.shape)}")
+            if x.shape[0] > self.max_push:
+                raise ValueError(f"slot {s}: a push of {x.shape[0]} samples exceeds max_push = {self.max_push}")
+            _lib.require_cuda(x, "waveform")
+        if final - set(chunks):
+            raise ValueError(f"slots {sorted(final - set(chunks))} are in `final` but not among the pushed slots")
+        if out is not None and (out.ndim != 2 or out.shape[0] != self.S or out.dtype != torch.float32 or out.stride(1) != 1):
+            raise ValueError(f"out must be ({self.S}, w) fp32 with contiguous rows")
+        if not chunks:
+            return {}
+        dev = next(iter(chunks.values())).device
+        self.allocate(dev)
+        rows = self.buf["rows"]
+        S = self.S
+        steps, res = {}, {}
+        y_off = [0] * S
+        for s, x in chunks.items():
+            n = x.shape[0]
+            st = self.sched[s].step(n, s in final)
+            if self.rate[s] < 0:                                 # equal rates: untouched
+                if out is not None:
+                    at = int(out_off[s])
+                    if n:
+                        out[s, at:at + n] = x
+                    res[s] = n
+                else:
+                    res[s] = x
+                continue
+            if n:
+                rows[s, self.fill[s]:self.fill[s] + n] = x
+                self.fill[s] += n
+            steps[s] = st
+            if out is not None:
+                y_off[s] = int(out_off[s])
+        if steps:
+            rs0, nv, o0, n_out, total = resample_session_rows(S, steps, self.s0, self.fill)
+            m = max(n_out)
+            if out is None:
+                y = torch.empty(S, max(m, 1), dtype=torch.float32, device=dev)      # the pieces handed out are views of it
+            else:
+                y = out
+            if m:
+                I64 = C.c_int64 * S
+                with torch.cuda.device(dev):
+                    _lib.check(_lib.lib().dmel_resample_window_items_f32(
+                        rows.data_ptr(), self.width, self.width, I64(*rs0), I64(*nv), y.data_ptr(), y.stride(0), I64(*y_off),
+                        self.buf["arena"].data_ptr(), self.arena_floats, (C.c_int64 * len(self.rates))(*self.rates), len(self.pairs),
+                        I64(*[max(r, 0) for r in self.rate]), S, I64(*o0), I64(*n_out), I64(*total), self.buf["table"].data_ptr(),
+                        _lib.stream_ptr()), "resample_window_items")
+            for s, st in steps.items():
+                res[s] = n_out[s] if out is not None else y[s, :n_out[s]]
+                if st.final:
+                    self.fill[s] = 0
+                elif st.keep_from > self.s0[s]:
+                    drop = st.keep_from - self.s0[s]
+                    keep = self.fill[s] - drop
+                    if keep:
+                        row = rows[s]
+                        row[:keep] = row[drop:drop + keep] if drop >= keep else row[drop:drop + keep].clone()
+                    self.s0[s], self.fill[s] = st.keep_from, keep
+        for s in final:
+            self.sched[s] = None
+        return res

@@ -168,6 +168,27 @@ int dmel_resample_f32(const float* x, float* y, const float* filter_bank_dev, in
  * or in the zero padding (checked: DMEL_EINVAL, nothing is launched, y is left as it was). */
 int dmel_resample_window_f32(const float* x, int64_t x_row_stride, int64_t n_samples, int64_t s0, float* y, const float* filter_bank_dev,
                              int B, int64_t o0, int64_t n_out, int64_t total_length, int orig_freq, int new_freq, int width, void* stream);
+/* The same launch for B INDEPENDENT streams, EACH WITH ITS OWN RATE PAIR (a pool of live sessions whose sound cards run at 48, 44.1
+ * and 16 kHz): ONE launch converts all of them.  s0, n_valid, y_off, rate_index, o0, n_out, total_length are HOST tables of B entries,
+ * rates a HOST table of n_rates descriptors of four int64: (bank_off, orig_freq, new_freq, width), the rates divided by their gcd, the
+ * bank of that pair -- (new_freq, 2 * width + orig_freq) fp32, as above -- at bank_arena_dev + bank_off (checked to lie inside the
+ * arena of bank_arena_floats floats).  x (B, n_samples) is one buffer width, rows x_row_stride floats apart; row b holds the absolute
+ * samples [s0[b], s0[b] + n_valid[b]) of stream b, n_valid[b] <= n_samples, at rate rates[rate_index[b]].  Item b's outputs
+ * [o0[b], o0[b] + n_out[b]) go to y + b * y_row_stride + y_off[b]; NOTHING ELSE of y is written, so y may be rows that already hold
+ * data in front of y_off[b] (a pool lets the launch write straight behind a slot's carried sample tail).  n_out[b] == 0 is an idle
+ * item: nothing of it is read, checked or written (and nothing is launched, DMEL_OK, when every item is idle).  Every other item is
+ * checked by the rules of dmel_resample_window_f32 against its own [s0[b], s0[b] + n_valid[b]) and its own rate, and
+ * y_off[b] + n_out[b] <= y_row_stride; a failure is DMEL_EINVAL, names the item, nothing is launched and y is left as it was.  Same
+ * kernel text, same tap loop: an output has the bits dmel_resample_f32 gives it on the whole clip.  A workgroup stages ITS item's bank
+ * in LDS when it has at most 15 K floats and reads it from the arena otherwise (44.1 -> 48 kHz: 160 x 161); a workgroup behind its
+ * item's last output leaves before either.  Grid (ceil(max n_out / 256), B).
+ * table_scratch: device memory for 7 B + 4 n_rates int64 (the items and rates as the kernel reads them).  The host tables are copied as
+ * launch arguments: the caller may overwrite them as soon as the call returns. */
+int dmel_resample_window_items_f32(const float* x, int64_t x_row_stride, int64_t n_samples, const int64_t* s0, const int64_t* n_valid,
+                                   float* y, int64_t y_row_stride, const int64_t* y_off, const float* bank_arena_dev,
+                                   int64_t bank_arena_floats, const int64_t* rates, int n_rates, const int64_t* rate_index, int B,
+                                   const int64_t* o0, const int64_t* n_out, const int64_t* total_length, int64_t* table_scratch,
+                                   void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Data front end on the GPU: what LhotseTTSDataset.__getitem__ + collate_fn do to the decoded clips of

@@ -401,6 +401,29 @@ int main() {
     // outputs [100, 1100) of a stream whose samples [50, 850) are in the buffer: they read [(100 / 3) * 2 - 7, (1099 / 3) * 2 + 9) = [59, 741)
     CK(dmel_resample_window_f32(x.data(), 5000, 800, 50, y.data(), bank.data(), 3, 100, 1000, -1, 2, 3, 7, nullptr));
     if (dmel_resample_window_f32(x.data(), 5000, 800, 60, y.data(), bank.data(), 3, 100, 1000, -1, 2, 3, 7, nullptr) == 0) { std::printf("FAIL resample_window accepted a buffer that misses a tap\n"); ++failures; }
+    {   // three streams at two rates in one call: 2 -> 3 (width 7, 3 x 16 taps at arena offset 0) and 3 -> 2 (width 10, 2 x 23 at 48)
+      auto arena = buf(48 + 46);
+      int64_t RT[8] = {0, 2, 3, 7, 48, 3, 2, 10};
+      // item 0: outputs [100, 1100) of samples [50, 850), as above; item 1: the head of a 3 -> 2 stream, outputs [0, 300) read [-10, 460);
+      // item 2: the end of a 3 -> 2 signal of 900 samples, outputs [500, 600) read [740, 900) and zeros behind
+      int64_t S0[3] = {50, 0, 700}, NV[3] = {800, 460, 200}, O0[3] = {100, 0, 500}, NO[3] = {1000, 300, 100}, TL[3] = {-1, -1, 900};
+      int64_t YO[3] = {6500, 10, 0}, RI[3] = {0, 1, 1};
+      std::vector<int64_t> tab(7 * 3 + 4 * 2);      // exactly the 7 B + 4 n_rates int64 the header asks for
+      auto items = [&]() {
+        return dmel_resample_window_items_f32(x.data(), 5000, 800, S0, NV, y.data(), 7500, YO, arena.data(), 94, RT, 2, RI, 3, O0, NO, TL,
+                                              tab.data(), nullptr);
+      };
+      CK(items());
+      NV[1] = 459;                        // item 1's last output reads a sample its row does not hold
+      int rc = items();
+      if (rc != DMEL_EINVAL || !std::strstr(dmel_last_error(), "item 1")) { std::printf("FAIL resample_window_items accepted a row that misses a tap (%d: %s)\n", rc, dmel_last_error()); ++failures; }
+      NV[1] = 460; YO[0] = 6501;          // item 0's outputs run over the end of its output row
+      rc = items();
+      if (rc != DMEL_EINVAL || !std::strstr(dmel_last_error(), "item 0")) { std::printf("FAIL resample_window_items accepted a y_off overflow (%d: %s)\n", rc, dmel_last_error()); ++failures; }
+      YO[0] = 6500; NO[0] = NO[1] = NO[2] = 0;      // every item idle: nothing to check, nothing to launch
+      RI[0] = 7; NV[1] = 9000;
+      CK(items());
+    }
     auto xs = buf(2 * 8 * 3000), ys = buf(2 * 8 * 3000), da = buf(8), db = buf(8);
     CK(dmel_aa_snake_f32(xs.data(), ys.data(), al.data(), be.data(), taps.data(), taps.data(), 1, 2, 8, 3000, nullptr));
     CK(dmel_aa_snake_backward_f32(xs.data(), ys.data(), xs.data(), al.data(), be.data(), da.data(), db.data(), taps.data(), taps.data(), 1, 2, 8, 3000, nullptr));

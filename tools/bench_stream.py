@@ -12,7 +12,14 @@ on the wall clock; median and 10th / 90th percentile over the steady-state pushe
 
 runs only this: S independent replies whose starts are offset by a third of a push, served (a) by ONE VQGAN.decode_sessions pool step and
 (b) by S StreamingDecoder(batch=1) stepped in turn -- what a server could do before the pool existed, so (b) stands for the parent commit.
-Both get the same tokens and noise, are interleaved in one process, and every piece of (a) is checked to equal the piece of (b)."""
+Both get the same tokens and noise, are interleaved in one process, and every piece of (a) is checked to equal the piece of (b).
+
+    python tools/bench_stream.py --sessions 16 --output-sample-rate 48000,16000 [--steps 40] [--out profiles/sessions_resample.txt]
+
+runs only this: S replies that leave at the given rates (session i at rate i mod len), served (a) by a pool that was told the rates
+(decode_sessions(output_sample_rates=...), open(output_sample_rate=r): ONE resample launch per step) and (b) by the codec-rate pool with
+S StreamResampler(batch=1) behind it, one resample launch and two copies per reply: the parent commit's way.  Same tokens and noise,
+interleaved in one process, equal audio checked, median and 10th / 90th percentile APPENDED to --out."""
 import json, os, statistics, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -131,6 +138,81 @@ def sessions_section(S, out):
     print("\n".join(table), file=sys.stderr)
     print(json.dumps(result))
 
+
+def sessions_rates_section(S, rates, steps, out):
+    from dmel_codec_amd.utils.resample import StreamResampler
+    chunk, warmup = 64, 6
+    pct = lambda v, q: sorted(v)[min(len(v) - 1, int(q * len(v)))]
+    gl = torch.Generator().manual_seed(8)
+    G, Cn = codec.dmel_groups, codec.decoder.input_channels
+    total = chunk * (steps + 1)
+    ids = torch.randint(0, 175, (S, G, total), generator=gl, dtype=torch.int32).to(dev)
+    noise = torch.randn(S, Cn, total * 4, device=dev)
+    rate = [rates[i % len(rates)] for i in range(S)]
+    pool = codec.decode_sessions(S, max_push_tokens=chunk, output_sample_rates=rates)
+    slots = [pool.open(output_sample_rate=rate[i]) for i in range(S)]
+    plain = codec.decode_sessions(S, max_push_tokens=chunk)
+    pslots = [plain.open() for _ in range(S)]
+    behind = [StreamResampler(pool.voc_rate, rate[i], 1) for i in range(S)]
+    pos = [0] * S
+    ms = {"per_slot_rates": [], "resamplers_behind": []}
+
+    def feed(sl, n):
+        return ({sl[i]: ids[i, :, pos[i]:pos[i] + n[i]] for i in range(S)},
+                {sl[i]: noise[i, :, 4 * pos[i]:4 * (pos[i] + n[i])] for i in range(S)})
+
+    def run_pool(n):
+        t, z = feed(slots, n)
+        out = pool.push(t, noise=z)
+        return [out[slots[i]][0] for i in range(S)]
+
+    def run_behind(n):
+        t, z = feed(pslots, n)
+        out = plain.push(t, noise=z)
+        return [behind[i].push(out[pslots[i]][0]) for i in range(S)]
+
+    for step in range(steps):
+        n = [chunk - (i % 3) * (chunk // 3) if step == 0 else chunk for i in range(S)]
+        got = {}
+        order = (("per_slot_rates", run_pool), ("resamplers_behind", run_behind))
+        for k, fn in (order if step % 2 == 0 else order[::-1]):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            got[k] = fn(n)
+            torch.cuda.synchronize()
+            if step >= warmup:
+                ms[k].append((time.perf_counter() - t0) * 1e3)
+        for i in range(S):
+            assert torch.equal(got["per_slot_rates"][i], got["resamplers_behind"][i]), f"step {step}, session {i}: the pool's audio differs"
+            pos[i] += n[i]
+    rows, result = [], {"sessions": S, "output_sample_rates": rates, "chunk_tokens": chunk, "audio_equal": True}
+    for k, v in ms.items():
+        med = statistics.median(v)
+        result[k] = {"median_ms": round(med, 3), "p10_ms": round(pct(v, 0.1), 3), "p90_ms": round(pct(v, 0.9), 3), "n": len(v)}
+        rows.append(f"{S:8d}  {k:17s}  {med:9.3f}  {pct(v, 0.1):9.3f}  {pct(v, 0.9):9.3f}  {len(v):4d}")
+    result["behind_over_per_slot"] = round(result["resamplers_behind"]["median_ms"] / result["per_slot_rates"]["median_ms"], 3)
+    rl = ",".join(map(str, rates))
+    table = [f"{S} decode sessions leaving at {rl} Hz, {chunk}-token pushes, starts a third of a push apart, 100 mel / 10 groups, BigVGAN base "
+             f"(tools/bench_stream.py --sessions {S} --output-sample-rate {rl})",
+             f"wall time of one step of all sessions incl. host synchronisation, {steps - warmup} steady-state steps, the two interleaved in one process, "
+             "equal audio checked;",
+             "per_slot_rates = decode_sessions(output_sample_rates=...): one resample launch per step; resamplers_behind = the codec-rate pool "
+             "with one StreamResampler(batch=1) per session behind it",
+             "sessions  form               median ms     p10 ms     p90 ms     n"] + rows + [
+                 f"resamplers behind / per-slot rates: {result['behind_over_per_slot']:.3f} at the median"]
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "a") as f:
+        f.write("\n".join(table) + "\n\n")
+    print("\n".join(table), file=sys.stderr)
+    print(json.dumps(result))
+
+
+if "--sessions" in sys.argv and "--output-sample-rate" in sys.argv:
+    sessions_rates_section(int(arg_after("--sessions")), [int(r) for r in arg_after("--output-sample-rate").split(",")],
+                           int(arg_after("--steps", "40")),
+                           arg_after("--out", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                           "sessions_resample.txt")))
+    sys.exit(0)
 
 if "--sessions" in sys.argv:
     sessions_section(int(arg_after("--sessions")),

@@ -20,7 +20,14 @@ table to --out.
 times a steady-state step of S independent sessions (VQGAN.encode_sessions: one STFT launch and one encoder launch for all of them)
 whose starts are offset by a third of a push, so that no two frontiers agree, against what there was for the same job before: S
 StreamingEncoder(batch=1) fed the same audio and stepped one after another.  Both run interleaved in one process; a "step" is one push
-for every stream, bracketed by a host synchronisation.  APPENDS its table to --out."""
+for every stream, bracketed by a host synchronisation.  APPENDS its table to --out.
+
+    python tools/bench_stream_encode.py --sessions 16 --sample-rate 48000,16000,44100 [--out profiles/sessions_resample.txt]
+
+times a steady-state step of S sessions that arrive at the given rates (slot s at rate s mod len) in a pool that was told the rates
+(encode_sessions(sample_rates=...), open(sample_rate=r): ONE resample launch per step, written behind each slot's sample tail) against
+what there was for the same job before: the same codec-rate pool behind S StreamResampler(batch=1), one resample launch and two copies
+per caller.  Interleaved in one process, equal ids checked, median and 10th / 90th percentile.  APPENDS its table to --out."""
 import argparse, json, os, statistics, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -31,13 +38,16 @@ ap.add_argument("--pushes", type=int, default=62, help="pushes per stream (62 x 
 ap.add_argument("--warmup", type=int, default=8)
 ap.add_argument("--chunk", type=int, default=7680, help="samples per push (0.32 s at 24 kHz)")
 ap.add_argument("--batches", default="1,16")
-ap.add_argument("--sample-rate", type=int, default=None, help="compare pushes at this source rate with pushes at the codec's rate")
+ap.add_argument("--sample-rate", default=None,
+                help="compare pushes at this source rate with pushes at the codec's rate; with --sessions: the sessions' rates, SR[,SR...]")
 ap.add_argument("--sessions", type=int, default=0, help="time a step of this many staggered independent sessions")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
+rates = [int(r) for r in args.sample_rate.split(",")] if args.sample_rate else []
+args.sample_rate = rates[0] if rates else None
 if args.out is None:
     args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                            "stream_sessions.txt" if args.sessions else "stream_resample.txt" if args.sample_rate else "stream_encode.txt")
+                            "sessions_resample.txt" if args.sessions and rates else "stream_sessions.txt" if args.sessions else "stream_resample.txt" if args.sample_rate else "stream_encode.txt")
 assert args.pushes - args.warmup >= 50, "medians over at least 50 steady-state pushes"
 SR = 24000
 dev = torch.device("cuda:0")
@@ -159,6 +169,70 @@ def sessions_section():
     print(json.dumps(r))
 
 
+def sessions_resample_section():
+    """S staggered sessions at their own rates: one pool that converts them in one launch against the codec-rate pool behind S
+    StreamResampler(batch=1); the same audio, the same pushes, equal ids"""
+    from dmel_codec_amd.models.stream_schedule import resample_max_outputs
+    from dmel_codec_amd.utils.resample import StreamResampler
+    S = args.sessions
+    rate = [rates[s % len(rates)] for s in range(S)]
+    n = [args.chunk * r // SR for r in rate]                     # 0.32 s of every slot's own rate
+    audio = [torch.randn((args.pushes + 1) * n[s], device=dev) * 0.1 for s in range(S)]
+    pool = codec.encode_sessions(slots=S, max_push_samples=max(n), sample_rates=rates)
+    slots = [pool.open(sample_rate=rate[s]) for s in range(S)]
+    behind = codec.encode_sessions(slots=S, max_push_samples=max(resample_max_outputs(r, SR, max(n)) for r in rates))
+    bslots = [behind.open() for _ in range(S)]
+    front = [StreamResampler(rate[s], SR, 1) for s in range(S)]
+    pos = [0] * S
+    first = [n[s] * (1 + s % 3) // 3 for s in range(S)]          # the starts differ by a third of a push
+    ms = {"per_slot_rates": [], "resamplers_in_front": []}
+    same, tokens = True, 0
+    for i in range(args.pushes):
+        size = first if i == 0 else n
+        chunks = [audio[s][pos[s]:pos[s] + size[s]] for s in range(S)]
+        pos = [p + k for p, k in zip(pos, size)]
+        got = {}
+        keys = list(ms)
+        for k in (keys if i % 2 == 0 else keys[::-1]):           # neither always goes first
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if k == "per_slot_rates":
+                ids = pool.push({slots[s]: chunks[s] for s in range(S)})
+                got[k] = [ids[slots[s]] for s in range(S)]
+            else:
+                ids = behind.push({bslots[s]: front[s].push(chunks[s][None])[0] for s in range(S)})
+                got[k] = [ids[bslots[s]] for s in range(S)]
+            torch.cuda.synchronize()
+            if i >= args.warmup:
+                ms[k].append((time.perf_counter() - t0) * 1e3)
+        same = same and all(torch.equal(a, b) for a, b in zip(*got.values()))
+        tokens += sum(a.shape[1] for a in got["per_slot_rates"])
+    r = {"sessions": S, "sample_rates": rates, "chunk_s": args.chunk / SR, "pushes": args.pushes, "warmup": args.warmup,
+         "ids_equal": bool(same), "tokens": tokens}
+    rows = []
+    for k, v in ms.items():
+        med = statistics.median(v)
+        r[k] = {"median_ms": round(med, 3), "p10_ms": round(pct(v, 0.1), 3), "p90_ms": round(pct(v, 0.9), 3), "n": len(v)}
+        rows.append(f"{S:8d}  {k:19s}  {med:9.3f}  {pct(v, 0.1):9.3f}  {pct(v, 0.9):9.3f}  {len(v):4d}")
+    r["in_front_over_per_slot"] = round(r["resamplers_in_front"]["median_ms"] / r["per_slot_rates"]["median_ms"], 3)
+    rows.append(f"{S:8d}  median step with {S} resamplers in front / with per-slot rates: {r['in_front_over_per_slot']:.3f}; ids equal: {same}")
+    table = [f"encode sessions at {','.join(map(str, rates))} Hz, 0.32 s pushes, starts staggered by a third of a push, 80 mel / 8 groups / "
+             f"70 channels / 20 layers (tools/bench_stream_encode.py --sessions {S} --sample-rate {','.join(map(str, rates))})",
+             f"wall time of one step (one push for every stream) incl. host synchronisation, {args.pushes - args.warmup} steady-state steps, the two "
+             "forms interleaved in one process;",
+             "per_slot_rates = encode_sessions(sample_rates=...): one resample launch per step; resamplers_in_front = the codec-rate pool behind "
+             "one StreamResampler(batch=1) per session",
+             "sessions  form                 median ms     p10 ms     p90 ms     n"] + rows
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "a") as f:
+        f.write("\n".join(table) + "\n\n")
+    print("\n".join(table), file=sys.stderr)
+    print(json.dumps(r))
+
+
+if args.sessions and rates:
+    sessions_resample_section()
+    sys.exit(0)
 if args.sessions:
     sessions_section()
     sys.exit(0)
