@@ -729,6 +729,83 @@ int launch_copy_windows(const float* src, float* dst, int N, int C, int64_t cap,
   return DMEL_OK;
 }
 
+// ---- ragged convert-copy over a pointer table (include/dmel_hip.h: dmel_pcm_convert_items) --------------------------------------------
+// Item blockIdx.y is row (src, dst, n, src_fmt | dst_fmt << 8) of `items`; a workgroup owns elements [2048 x, 2048 (x + 1)) of its item.
+// The rounding rule lives in these two functions and nowhere else: both paths of the kernel call them, so an element has the same bits on
+// either.  s16 -> f32 is exact (|x| <= 2^15 times a power of two).  f32 -> s16: x 32768 is exact, the clamp comes first so that the
+// conversion to int never sees a value out of range, rintf is v_rndne_f32 (nearest, ties to even, whatever the rounding mode); NaN -> 0.
+constexpr int kPcmItemWords = 4, kPcmPerThread = 8, kPcmTile = 256 * kPcmPerThread;
+__device__ __forceinline__ float pcm_s16_to_f32(int16_t v) { return (float)v * 0x1p-15f; }
+__device__ __forceinline__ int16_t pcm_f32_to_s16(float v) {
+  v = v != v ? 0.f : v;
+  return (int16_t)(int)__builtin_rintf(fminf(fmaxf(v * 32768.f, -32768.f), 32767.f));
+}
+__device__ __forceinline__ uint32_t pcm_pack2(float lo, float hi) {
+  return (uint32_t)(uint16_t)pcm_f32_to_s16(lo) | ((uint32_t)(uint16_t)pcm_f32_to_s16(hi) << 16);
+}
+// SIN / SOUT: the source / destination holds int16.  f32 -> f32 moves the words untouched.  `wide`: src and dst of the item are both
+// 16-byte aligned (workgroup-uniform); then a thread whose 8 consecutive elements all lie in the item moves them with 16-byte loads and
+// stores.  Everything else -- an unaligned item, the elements behind the last whole 8 -- goes element by element, element e of the tile
+// to thread e % 256 so that a wave still reads and writes consecutive addresses.
+template <bool SIN, bool SOUT>
+__device__ __forceinline__ void pcm_convert_tile(const void* src, void* dst, int64_t n, int64_t base, bool wide) {
+  const int16_t* s16 = static_cast<const int16_t*>(src);
+  const uint32_t* s32 = static_cast<const uint32_t*>(src);
+  int16_t* d16 = static_cast<int16_t*>(dst);
+  uint32_t* d32 = static_cast<uint32_t*>(dst);
+  int64_t from = base;                                         // the element-wise path covers [from, min(n, base + kPcmTile))
+  if (wide) {
+    const int64_t whole = base + (min(n - base, (int64_t)kPcmTile) & ~(int64_t)(kPcmPerThread - 1));
+    const int64_t e = base + (int64_t)threadIdx.x * kPcmPerThread;
+    if (e < whole) {
+      if constexpr (SIN) {
+        const uint4 a = *reinterpret_cast<const uint4*>(s16 + e);
+        const uint32_t w[4] = {a.x, a.y, a.z, a.w};
+        float f[8];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          f[2 * j] = pcm_s16_to_f32((int16_t)(w[j] & 0xffffu));
+          f[2 * j + 1] = pcm_s16_to_f32((int16_t)(w[j] >> 16));
+        }
+        float4* o = reinterpret_cast<float4*>(d32 + e);
+        o[0] = make_float4(f[0], f[1], f[2], f[3]);
+        o[1] = make_float4(f[4], f[5], f[6], f[7]);
+      } else if constexpr (SOUT) {
+        const float4* p = reinterpret_cast<const float4*>(s32 + e);
+        const float4 a = p[0], b = p[1];
+        *reinterpret_cast<uint4*>(d16 + e) = make_uint4(pcm_pack2(a.x, a.y), pcm_pack2(a.z, a.w), pcm_pack2(b.x, b.y), pcm_pack2(b.z, b.w));
+      } else {
+        const uint4* p = reinterpret_cast<const uint4*>(s32 + e);
+        const uint4 a = p[0], b = p[1];
+        uint4* o = reinterpret_cast<uint4*>(d32 + e);
+        o[0] = a;
+        o[1] = b;
+      }
+    }
+    from = whole;
+  }
+  const int64_t end = min(n, base + kPcmTile);
+  for (int64_t e = from + threadIdx.x; e < end; e += 256) {
+    if constexpr (SIN) reinterpret_cast<float*>(d32)[e] = pcm_s16_to_f32(s16[e]);
+    else if constexpr (SOUT) d16[e] = pcm_f32_to_s16(reinterpret_cast<const float*>(s32)[e]);
+    else d32[e] = s32[e];
+  }
+}
+__global__ __launch_bounds__(256) void pcm_convert_kernel(const int64_t* __restrict__ items) {
+  const int64_t* it = items + kPcmItemWords * (int64_t)blockIdx.y;
+  const int64_t n = uniform_i64(it + 2);
+  const int64_t base = (int64_t)blockIdx.x * kPcmTile;
+  if (base >= n) return;                                       // workgroup-uniform: every workgroup of an idle item leaves here
+  const uint64_t sa = (uint64_t)uniform_i64(it), da = (uint64_t)uniform_i64(it + 1);
+  const int64_t fmt = uniform_i64(it + 3);
+  const void* src = reinterpret_cast<const void*>(sa);
+  void* dst = reinterpret_cast<void*>(da);
+  const bool wide = ((sa | da) & 15) == 0;
+  if ((fmt & 0xff) == DMEL_SAMPLE_S16) pcm_convert_tile<true, false>(src, dst, n, base, wide);
+  else if ((fmt >> 8) == DMEL_SAMPLE_S16) pcm_convert_tile<false, true>(src, dst, n, base, wide);
+  else pcm_convert_tile<false, false>(src, dst, n, base, wide);
+}
+
 // out[r] = max(len[r] - row r's shift, 0): an item's output length relative to the first column of its window
 __global__ void shift_lengths_items_kernel(const int64_t* __restrict__ len, const int32_t* __restrict__ tab, int stride, int i_shift,
                                            int64_t* __restrict__ out, int n) {
@@ -854,4 +931,45 @@ extern "C" int dmel_resample_window_items_f32(const float* x, int64_t x_row_stri
   DMEL_TRY(launch_table_put(tab.data(), tab.size() * sizeof(int64_t), table_scratch, (hipStream_t)stream));
   return launch_resample_window_items(x, x_row_stride, y, y_row_stride, bank_arena_dev, B, table_scratch,
                                       table_scratch + (size_t)kResampleItemWords * B, max_out, lds_floats, bytes, (hipStream_t)stream);
+}
+
+// ---- B ragged convert-copies between 16-bit PCM and fp32 in one launch (include/dmel_hip.h: dmel_pcm_convert_items) ----------------
+extern "C" int dmel_pcm_convert_items(const void* const* src, const int32_t* src_fmt, void* const* dst, const int32_t* dst_fmt,
+                                      const int64_t* n, int B, void* table_scratch, void* stream) {
+  using namespace dmel;
+  DMEL_CHECK_ARG(src && src_fmt && dst && dst_fmt && n && table_scratch, "pcm_convert_items: NULL argument");
+  DMEL_CHECK_ARG(B >= 1 && B <= 65535, "pcm_convert_items: %d items, expected 1 .. 65535", B);
+  DMEL_CHECK_ARG(((uintptr_t)table_scratch & 7) == 0, "pcm_convert_items: table_scratch is not 8-byte aligned");
+  std::vector<int64_t> tab((size_t)kPcmItemWords * B, 0);           // an idle item keeps n = 0
+  int64_t max_n = 0;
+  double bytes = 0.0;
+  for (int b = 0; b < B; ++b) {
+    const int sf = src_fmt[b], df = dst_fmt[b];
+    DMEL_CHECK_ARG((sf == DMEL_SAMPLE_F32 || sf == DMEL_SAMPLE_S16) && (df == DMEL_SAMPLE_F32 || df == DMEL_SAMPLE_S16),
+                   "pcm_convert_items: item %d: sample formats %d -> %d, expected DMEL_SAMPLE_F32 (0) or DMEL_SAMPLE_S16 (1)", b, sf, df);
+    DMEL_CHECK_ARG(!(sf == DMEL_SAMPLE_S16 && df == DMEL_SAMPLE_S16), "pcm_convert_items: item %d: s16 -> s16 is not a conversion", b);
+    DMEL_CHECK_ARG(n[b] >= 0 && n[b] < ((int64_t)1 << 40), "pcm_convert_items: item %d: sample count %lld out of range", b, (long long)n[b]);
+    if (n[b] == 0) continue;
+    DMEL_CHECK_ARG(src[b] && dst[b], "pcm_convert_items: item %d: NULL pointer with %lld samples", b, (long long)n[b]);
+    const uintptr_t sa = (uintptr_t)src[b], da = (uintptr_t)dst[b];
+    const int ss = sf == DMEL_SAMPLE_S16 ? 2 : 4, ds = df == DMEL_SAMPLE_S16 ? 2 : 4;
+    DMEL_CHECK_ARG(sa % ss == 0 && da % ds == 0, "pcm_convert_items: item %d: a pointer is not aligned to its sample size (%d -> %d bytes)", b,
+                   ss, ds);
+    int64_t* it = tab.data() + (size_t)kPcmItemWords * b;
+    it[0] = (int64_t)sa; it[1] = (int64_t)da; it[2] = n[b]; it[3] = sf | (df << 8);
+    max_n = std::max(max_n, n[b]);
+    bytes += (double)n[b] * (ss + ds);
+  }
+  if (max_n == 0) return DMEL_OK;                     // every item idle
+  hipStream_t s = (hipStream_t)stream;
+  DMEL_TRY(launch_table_put(tab.data(), tab.size() * sizeof(int64_t), table_scratch, s));
+  {
+    // "small" carries the time and the bytes; the second scope only counts: one record per convert launch, so that a caller can tell
+    // this launch from the other small ones of a step (dmel_prof_read("pcm_convert"))
+    ProfScope ps("small", s, 0.0, bytes), count("pcm_convert", s, 0.0, 0.0);
+    hipLaunchKernelGGL(pcm_convert_kernel, dim3((unsigned)((max_n + kPcmTile - 1) / kPcmTile), (unsigned)B), dim3(256), 0, s,
+                       static_cast<const int64_t*>(table_scratch));
+  }
+  DMEL_HIP(hipGetLastError());
+  return DMEL_OK;
 }

@@ -6,7 +6,9 @@ they start, stall and hang up on their own.  EncodeSessions keeps one EncodeSche
 the kernels one row per slot (dmel_stft_window_items_f32, dmel_wavenet_stream_step_items), so that any subset of the slots advances, each
 by its own number of samples, in one STFT launch and one encoder launch.  Sessions whose sound cards do not run at the codec's rate
 declare their own rate when they open; all of them, whatever their rates, are converted by one resample launch per step
-(utils/resample.py: SessionResampler, dmel_resample_window_items_f32)."""
+(utils/resample.py: SessionResampler, dmel_resample_window_items_f32).  Sessions whose wire carries 16-bit PCM declare that too
+(open(sample_format="s16")): the conversion is folded into the per-slot copy a pool makes anyway, one launch for all slots of a step
+(utils/pcm.py, dmel_pcm_convert_items)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -16,6 +18,7 @@ from typing import Dict, Iterable, List, Mapping, Optional, Tuple
 import torch
 
 from .. import _lib
+from ..utils import pcm
 from .stream_schedule import (DecodeGeometry, DecodeSchedule, EncodeGeometry, EncodeSchedule, decode_capacity, decode_rebase,
                               decode_session_rows, resample_max_outputs, session_rows)
 
@@ -45,6 +48,15 @@ class EncodeSessions:
     writes straight behind each slot's carried sample tail; the STFT launch and the encoder step follow unchanged.  The rows and the
     capacity are sized from the most codec-rate samples one push can release over the declared rates (resample_max_outputs).  The
     constructor's own `sample_rate` only names the codec's rate, as before: a pool has no rate of its own.
+
+    The sample format belongs to a session as well and sizes nothing: open(sample_format="s16") starts a session whose pushes are
+    torch.int16 (16-bit signed PCM, in samples of its own rate as before) and whose ids are the bits of the same session opened as "f32"
+    and fed pcm.float() / 32768 -- of encode(from_pcm16(clip), len[, sample_rate=r]).  In a step that names at least one s16 slot, ALL
+    named slots with samples go through ONE dmel_pcm_convert_items launch (f32 slots as plain copies) that writes exactly where the
+    per-slot copies of the float path write: behind the slot's sample tail, or behind its tail in the SessionResampler's rows; the
+    resample launch, the STFT launch and the encoder step follow unchanged.  A step without an s16 slot takes the float path as it was.
+    A push whose dtype does not match its slot's format is a ValueError.  Out of scope: the lockstep StreamingEncoder and whole-clip
+    encode() (callers have utils.pcm.from_pcm16), other formats (s24, s32, u8, mu-law), dither.
 
     Only encoders the one-launch streaming kernel takes (residual channels in (32, 80], no condition, no output projection,
     dilations <= 8, fp32): anything else is refused at construction.
@@ -111,6 +123,7 @@ class EncodeSessions:
         self.s0 = [0] * self.S
         self.tail = [0] * self.S                      # valid samples in the slot's row
         self.rate = [self.codec_rate] * self.S        # the rate the slot's pushes arrive at
+        self.fmt = ["f32"] * self.S                   # the sample format the slot's pushes arrive in (utils/pcm.py: FORMATS)
         self._fresh = [False] * self.S                # opened, state not zeroed yet (done with the slot's first push)
         self.buf = None
 
@@ -132,9 +145,11 @@ class EncodeSessions:
         self._check_open(slot)
         return self.sched[slot].tokens
 
-    def open(self, sample_rate: Optional[int] = None) -> int:
+    def open(self, sample_rate: Optional[int] = None, sample_format: str = "f32") -> int:
         """take a free slot: fresh schedule, state zeroed before its first push.  sample_rate: the rate this session's pushes arrive
-        at, one of the declared `sample_rates` (None: the codec's).  Raises when every slot is taken."""
+        at, one of the declared `sample_rates` (None: the codec's).  sample_format: "f32", or "s16" for torch.int16 pushes (16-bit
+        signed PCM, x / 32768).  Raises when every slot is taken."""
+        pcm.check_format(sample_format)
         rate = self.codec_rate if sample_rate is None else int(sample_rate)
         if rate != self.codec_rate and rate not in self.sample_rates:
             raise ValueError(f"a session at {rate} Hz: the pool was built for {(self.codec_rate,) + self.sample_rates} Hz "
@@ -144,6 +159,7 @@ class EncodeSessions:
                 self.sched[s] = EncodeSchedule(self.geo)
                 self.origin[s] = self.s0[s] = self.tail[s] = 0
                 self.rate[s] = rate
+                self.fmt[s] = sample_format
                 if self.rs is not None:
                     self.rs.open(s, rate, self.codec_rate)
                 self._fresh[s] = True
@@ -172,6 +188,8 @@ class EncodeSessions:
                 raise ValueError(f"slot {slot}: expected mono audio (n,) or (1, n), got {tuple(a.shape)}")
             if a.shape[0] > self.max_push:
                 raise ValueError(f"slot {slot}: a push of {a.shape[0]} samples exceeds max_push_samples = {self.max_push}")
+            if (a.dtype == torch.int16) if self.fmt[slot] == "f32" else (a.dtype != torch.int16):
+                raise ValueError(f"slot {slot} was opened with sample_format={self.fmt[slot]!r}: a {a.dtype} push does not match")
             out[slot] = a
         for slot in final:
             if slot not in audio:
@@ -197,7 +215,8 @@ class EncodeSessions:
                         samples=torch.zeros(self.S, self.width, dtype=torch.float32, device=dev),
                         # dmel_wavenet_stream_step_items: the scratch of _ex (2 N C cap floats, N int64) and the row table behind it
                         scratch=torch.empty(2 * N * self.C * self.cap + 2 * N + rows, dtype=torch.float32, device=dev),
-                        stft_tab=torch.empty(4 * self.S, dtype=torch.int64, device=dev))
+                        stft_tab=torch.empty(4 * self.S, dtype=torch.int64, device=dev),
+                        pcm_tab=torch.empty(4 * self.S, dtype=torch.int64, device=dev))
 
     def _slot_views(self, s: int):
         b, G = self.buf, self.G
@@ -231,7 +250,18 @@ class EncodeSessions:
         steps = {}
         # ---- the sound cards' rates: ONE launch converts every slot that needs it, straight behind the slot's sample tail
         converted = {s: a for s, a in audio.items() if self._converts(s)}
-        released = self.rs.push(converted, final & set(converted), out=b["samples"], out_off=self.tail) if converted else {}
+        # ---- the wire's format: a step that names an s16 slot puts ALL its chunks in place with ONE convert launch, each where the
+        # float path's per-slot copy would put it -- behind the slot's resampler tail or behind its sample tail
+        placed = any(self.fmt[s] == "s16" for s in audio)
+        if placed:
+            converted = self.rs.destinations({s: a.shape[0] for s, a in converted.items()}) if converted else {}
+            moves = [((a.to(torch.float32) if self.fmt[s] == "f32" else a).contiguous(),
+                      converted[s] if s in converted else b["samples"][s, self.tail[s]:self.tail[s] + a.shape[0]])
+                     for s, a in audio.items() if a.shape[0]]
+            if moves:
+                pcm.convert_items([x for x, _ in moves], [y for _, y in moves], table=b["pcm_tab"])
+        released = (self.rs.push(converted, final & set(converted), out=b["samples"], out_off=self.tail, placed=placed)
+                    if converted else {})
         for s, a in audio.items():
             if self._fresh[s]:
                 for v in self._slot_views(s):
@@ -241,7 +271,7 @@ class EncodeSessions:
                 n = released[s]
             else:
                 n = a.shape[0]
-                if n:
+                if n and not placed:
                     b["samples"][s, self.tail[s]:self.tail[s] + n] = a
             self.tail[s] += n
             steps[s] = self.sched[s].step(n, s in final)
@@ -318,7 +348,7 @@ class EncodeSessions:
         """no more audio for this slot: its remaining tokens, and the slot is free"""
         self._check_open(slot)
         dev = self.buf["samples"].device if self.buf is not None else next(self.codec.parameters()).device
-        return self.push({slot: torch.empty(0, dtype=torch.float32, device=dev)}, final=(slot,))[slot]
+        return self.push({slot: torch.empty(0, dtype=pcm.FORMATS[self.fmt[slot]][1], device=dev)}, final=(slot,))[slot]
 
 
 class DecodeSessions:
@@ -353,6 +383,15 @@ class DecodeSessions:
     all slots (utils/resample.py: SessionResampler), and a final slot is flushed with its true length.  The slot's audio pieces then
     concatenate to resample(decode() audio, vocoder rate, r), bit for bit, m * up samples no longer; its mel is the unchanged decode()
     mel.  return_audios=False with a declared rate is a ValueError.
+
+    The sample format belongs to a session as well and sizes nothing: open(sample_format="s16") starts a reply whose audio comes back as
+    torch.int16 (16-bit signed PCM) of the same shape, the rounding of utils/pcm.py (x 32768, clamp, nearest with ties to even) applied to
+    the float audio the same session would have returned; its mel is unchanged.  After the vocoder groups and the one resample launch,
+    ONE dmel_pcm_convert_items launch takes every s16 slot's new piece -- the crop inside the vocoder's batch, or the slot's resampler
+    output -- and writes it into one packed int16 buffer of the step; the tensors returned are views of that buffer (this takes the
+    place of the clone that detaches a float piece).  f32 slots of such a step keep their path and their bits.  "s16" with
+    return_audios=False is a ValueError at open.  Out of scope: the lockstep StreamingDecoder and whole-clip decode() (callers have
+    utils.pcm.to_pcm16), other formats (s24, s32, u8, mu-law), dither.
 
     Out of scope, NotImplementedError: overlap_vocoder, graph_chunk_tokens, and a pool-wide output_sample_rate (a pool has no rate of
     its own).
@@ -406,6 +445,7 @@ class DecodeSessions:
             # a step emits frames that all lie in the slot's `cap` columns: at most cap * up samples reach a slot's resampler at once
             self.rs = SessionResampler(self.S, [(self.voc_rate, r) for r in self.output_sample_rates], self.cap * self.up)
         self.rate = [self.voc_rate] * self.S              # the rate the slot's audio leaves at
+        self.fmt = ["f32"] * self.S                       # the sample format the slot's audio leaves in (utils/pcm.py: FORMATS)
         self.sched: List[Optional[DecodeSchedule]] = [None] * self.S
         self.origin = [0] * self.S
         self.tok_origin = [0] * self.S                    # absolute index of the token in column 0 of the slot's token tail
@@ -431,9 +471,12 @@ class DecodeSessions:
         self._check_open(slot)
         return self.sched[slot].emitted
 
-    def open(self, output_sample_rate: Optional[int] = None) -> int:
+    def open(self, output_sample_rate: Optional[int] = None, sample_format: str = "f32") -> int:
         """take a free slot: fresh schedule, state zeroed before its first push.  output_sample_rate: the rate this session's audio
-        leaves at, one of the declared `output_sample_rates` (None: the vocoder's).  Raises when every slot is taken."""
+        leaves at, one of the declared `output_sample_rates` (None: the vocoder's).  sample_format: "f32", or "s16" for audio returned
+        as torch.int16 (16-bit signed PCM).  Raises when every slot is taken."""
+        if pcm.check_format(sample_format) != "f32" and not self.return_audios:
+            raise ValueError(f"sample_format={sample_format!r} without audio: return_audios=False leaves nothing to convert")
         rate = self.voc_rate if output_sample_rate is None else int(output_sample_rate)
         if rate != self.voc_rate and rate not in self.output_sample_rates:
             raise ValueError(f"a session at {rate} Hz: the pool was built for {(self.voc_rate,) + self.output_sample_rates} Hz "
@@ -443,6 +486,7 @@ class DecodeSessions:
                 self.sched[s] = DecodeSchedule(self.geo)
                 self.origin[s] = self.tok_origin[s] = self.n_noise[s] = 0
                 self.rate[s] = rate
+                self.fmt[s] = sample_format
                 if self.rs is not None:
                     self.rs.open(s, self.voc_rate, rate)
                 self._fresh[s] = True
@@ -487,7 +531,8 @@ class DecodeSessions:
                         tokens=torch.zeros(S, self.G, self.tok_width, dtype=torch.int32, device=dev),
                         noise=torch.zeros(S, self.C, self.noise_width, dtype=torch.float32, device=dev),
                         # dmel_wavenet_stream_step_items_layered: 2 S C cap floats, S int64, and the row table behind them
-                        scratch=torch.empty(2 * S * self.C * self.cap + 2 * S + rows, dtype=torch.float32, device=dev))
+                        scratch=torch.empty(2 * S * self.C * self.cap + 2 * S + rows, dtype=torch.float32, device=dev),
+                        pcm_tab=torch.empty(4 * S, dtype=torch.int64, device=dev))
 
     def _slot_views(self, s: int):
         b = self.buf
@@ -578,10 +623,11 @@ class DecodeSessions:
             for s, st in steps.items():
                 o = self.origin[s]
                 mel = b["mel"][s, :, st.emit[0] - o:st.emit[1] - o].clone()
-                out[s] = (torch.empty(1, 0, dtype=torch.float32, device=dev) if self.return_audios else None, mel)
+                out[s] = (torch.empty(1, 0, dtype=pcm.FORMATS[self.fmt[s]][1], device=dev) if self.return_audios else None, mel)
                 if st.voc_window[1] > st.voc_window[0]:
                     vgroups.setdefault(st.voc_window[1] - st.voc_window[0], []).append(s)
             pieces: Dict[int, torch.Tensor] = {}       # the new audio of the slots that leave at another rate, still in the vocoder's batch
+            wire: Dict[int, torch.Tensor] = {}         # the new float audio of the s16 slots, where it lies: converted at the end of the step
             for _, members in vgroups.items():
                 wins = [b["mel"][s, :, steps[s].voc_window[0] - self.origin[s]:steps[s].voc_window[1] - self.origin[s]] for s in members]
                 wav = codec.vocoder(torch.stack(wins).contiguous())
@@ -591,6 +637,8 @@ class DecodeSessions:
                     piece = wav[i, :, (st.emit[0] - lo) * self.up:(st.emit[1] - lo) * self.up]
                     if self.rate[s] != self.voc_rate:
                         pieces[s] = piece[0]
+                    elif self.fmt[s] == "s16":
+                        wire[s] = piece[0]
                     else:
                         out[s] = (piece.clone(), out[s][1])
             # ---- the playback rates: each piece goes behind its slot's resampler tail, ONE launch converts all slots; a slot without a
@@ -601,7 +649,23 @@ class DecodeSessions:
                         pieces[s] = torch.empty(0, dtype=torch.float32, device=dev)
                 if pieces:
                     for s, y in self.rs.push(pieces, final & set(pieces)).items():
-                        out[s] = (y[None], out[s][1])
+                        if self.fmt[s] == "s16":
+                            wire[s] = y
+                        else:
+                            out[s] = (y[None], out[s][1])
+            # ---- the wire's format: ONE launch converts every s16 slot's new piece into one packed int16 buffer of the step (each
+            # piece at a multiple of 8 samples = 16 bytes); the tensors handed out are views of it
+            wire = {s: y for s, y in wire.items() if y.shape[0]}
+            if wire:
+                at, total = {}, 0
+                for s, y in wire.items():
+                    at[s] = total
+                    total += (y.shape[0] + 7) // 8 * 8
+                packed = torch.empty(total, dtype=torch.int16, device=dev)
+                dsts = [packed[at[s]:at[s] + y.shape[0]] for s, y in wire.items()]
+                pcm.convert_items(list(wire.values()), dsts, table=b["pcm_tab"])
+                for (s, _), d in zip(wire.items(), dsts):
+                    out[s] = (d[None], out[s][1])
         for s in final:
             self.sched[s] = None          # the slot is free; its rows are zeroed when it is opened and pushed to again
         return out

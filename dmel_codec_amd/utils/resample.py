@@ -189,6 +189,8 @@ class SessionResampler:
         pieces = pool.push({slot: chunk_1d, ...}, final=())  # -> {slot: the (m,) outputs that became final with this chunk}
         counts = pool.push(chunks, final, out=rows, out_off={slot: column})
                                                              # the launch stores slot s's outputs at rows[s, column:]: -> {slot: m}
+        views = pool.destinations({slot: n, ...})            # where the next chunk of n samples of each slot belongs: a caller that
+        pieces = pool.push(views, final=(), placed=True)     # WRITES its chunks there itself (a converting launch) spares the copy
 
     A slot's concatenated pieces are torch.equal to resample(its whole signal, orig, new).  A slot whose rates are equal passes through
     untouched (its chunk is returned, or copied to `out`).  A slot in `final` is flushed with its true length and closed.
@@ -256,9 +258,27 @@ class SessionResampler:
         self.buf = dict(rows=torch.zeros(self.S, self.width, dtype=torch.float32, device=dev), arena=arena.contiguous(),
                         table=torch.empty(7 * self.S + len(self.rates), dtype=torch.int64, device=dev))
 
+    def destinations(self, counts: Mapping[int, int]) -> Dict[int, torch.Tensor]:
+        """{slot: n} -> {slot: the (n,) fp32 view of the slot's row behind its carried tail}: where push() would copy a chunk of n
+        samples.  A caller fills the views (one launch for all of them) and hands THEM to push(..., placed=True) in place of the
+        chunks.  Nothing changes here; the views hold until that push.  Needs allocate(); a slot at equal rates has no row."""
+        if self.buf is None:
+            raise RuntimeError("destinations: allocate() first")
+        out = {}
+        for s, n in counts.items():
+            if not 0 <= s < self.S or self.sched[s] is None:
+                raise RuntimeError(f"slot {s} is not open")
+            if self.rate[s] < 0:
+                raise ValueError(f"slot {s}: equal rates, nothing is carried for it")
+            if not 0 <= n <= self.max_push:
+                raise ValueError(f"slot {s}: a push of {n} samples exceeds max_push = {self.max_push}")
+            out[s] = self.buf["rows"][s, self.fill[s]:self.fill[s] + n]
+        return out
+
     @torch.no_grad()
     def push(self, chunks: Mapping[int, torch.Tensor], final: Iterable[int] = (), out: Optional[torch.Tensor] = None,
-             out_off: Optional[Mapping[int, int]] = None) -> Dict[int, object]:
+             out_off: Optional[Mapping[int, int]] = None, placed: bool = False) -> Dict[int, object]:
+        """placed: every chunk is the view destinations() handed out for it and already holds its samples -- the copy is skipped"""
         final = set(final)
         for s, x in chunks.items():
             if not 0 <= s < self.S or self.sched[s] is None:
@@ -268,6 +288,9 @@ class SessionResampler:
             if x.shape[0] > self.max_push:
                 raise ValueError(f"slot {s}: a push of {x.shape[0]} samples exceeds max_push = {self.max_push}")
             _lib.require_cuda(x, "waveform")
+            if placed and (self.buf is None or self.rate[s] < 0 or x.dtype != torch.float32 or
+                           (x.shape[0] and x.data_ptr() != self.buf["rows"][s, self.fill[s]:].data_ptr())):
+                raise ValueError(f"slot {s}: placed=True takes the views destinations() handed out")
         if final - set(chunks):
             raise ValueError(f"slots {sorted(final - set(chunks))} are in `final` but not among the pushed slots")
         if out is not None and (out.ndim != 2 or out.shape[0] != self.S or out.dtype != torch.float32 or out.stride(1) != 1):
@@ -293,7 +316,8 @@ class SessionResampler:
                     res[s] = x
                 continue
             if n:
-                rows[s, self.fill[s]:self.fill[s] + n] = x
+                if not placed:
+                    rows[s, self.fill[s]:self.fill[s] + n] = x
                 self.fill[s] += n
             steps[s] = st
             if out is not None:

@@ -191,6 +191,31 @@ int dmel_resample_window_items_f32(const float* x, int64_t x_row_stride, int64_t
                                    void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The sample format of the wire: 16-bit signed PCM <-> fp32, B ragged convert-copies in ONE launch (a pool of live sessions whose
+ * microphones, RTP streams and sound cards carry int16; no reference counterpart: the reference reads finished float clips).
+ * src, src_fmt, dst, dst_fmt, n are HOST tables of B entries; src[b] / dst[b] are DEVICE pointers to n[b] samples of format
+ * src_fmt[b] / dst_fmt[b].  Item b:
+ *   s16 -> f32   y = (float)x * 2^-15: exact; full scale is -1.0 and the largest value 1 - 2^-15.
+ *   f32 -> s16   y = rne(clamp(x * 32768, -32768, 32767)): the product is exact (a power of two), rne is round to nearest, ties to
+ *                EVEN (v_rndne_f32; not the current rounding mode, not truncation, not half away from zero): 0.5 / 32768 -> 0,
+ *                1.5 / 32768 -> 2, 2.5 / 32768 -> 2.  NaN -> 0, +-inf saturate, no dither: the result is deterministic.
+ *   f32 -> f32   the words copied untouched (a pool with mixed sessions still makes one launch).
+ *   s16 -> s16   refused.
+ * n[b] == 0 is an idle item: its pointers are not looked at, nothing of it is read or written (and nothing is launched, DMEL_OK, when
+ * every item is idle).  Checked before anything is launched -- a failure is DMEL_EINVAL, names the item, and leaves every destination
+ * as it was: 1 <= B <= 65535, formats in range, n[b] >= 0, non-NULL pointers where n[b] > 0, an s16 pointer 2-byte and an f32
+ * pointer 4-byte aligned.  NOT checked: that no destination overlaps a source or another destination (the caller's to guarantee).
+ * Grid (ceil(max n / 2048), B); a workgroup behind its item's last sample leaves at once.  An item whose src AND dst are 16-byte
+ * aligned moves whole groups of 8 samples with 16-byte loads and stores, any other item goes sample by sample: same arithmetic, same
+ * bits.  table_scratch: device memory for 4 B int64, 8-byte aligned (the items as the kernel reads them).  The host tables are
+ * copied as launch arguments: the caller may overwrite them as soon as the call returns.
+ * ---------------------------------------------------------------------------------------------- */
+#define DMEL_SAMPLE_F32 0
+#define DMEL_SAMPLE_S16 1
+int dmel_pcm_convert_items(const void* const* src, const int32_t* src_fmt, void* const* dst, const int32_t* dst_fmt, const int64_t* n,
+                           int B, void* table_scratch, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Data front end on the GPU: what LhotseTTSDataset.__getitem__ + collate_fn do to the decoded clips of
  * a batch (dataset/lhotse_tts_dataset.py:29-32, :46-65): every clip peak-normalised, `librosa.util.normalize(audio) * 0.95` =
  * x / max|x| * peak (a clip whose peak is below the smallest normal float is left unscaled, as librosa does), right-padded with zeros

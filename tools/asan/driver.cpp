@@ -424,6 +424,26 @@ int main() {
       RI[0] = 7; NV[1] = 9000;
       CK(items());
     }
+    {
+      // the ragged convert-copy: three items in the three directions, tables of exactly B entries, a table scratch of exactly 4 B int64
+      std::vector<float> f(5000, 0.5f), g(2049);
+      std::vector<int16_t> p(2049), q(5000);
+      const void* SRC[3] = {f.data(), p.data(), f.data()};
+      void* DST[3] = {q.data(), g.data(), g.data()};
+      int32_t SF[3] = {DMEL_SAMPLE_F32, DMEL_SAMPLE_S16, DMEL_SAMPLE_F32}, DF[3] = {DMEL_SAMPLE_S16, DMEL_SAMPLE_F32, DMEL_SAMPLE_F32};
+      int64_t N[3] = {5000, 2049, 0};
+      std::vector<int64_t> tab(4 * 3);
+      auto conv = [&]() { return dmel_pcm_convert_items(SRC, SF, DST, DF, N, 3, tab.data(), nullptr); };
+      CK(conv());
+      DF[1] = DMEL_SAMPLE_S16;
+      int rc = conv();
+      if (rc != DMEL_EINVAL || !std::strstr(dmel_last_error(), "item 1")) { std::printf("FAIL pcm_convert_items accepted s16 -> s16 (%d: %s)\n", rc, dmel_last_error()); ++failures; }
+      DF[1] = DMEL_SAMPLE_F32; SRC[1] = reinterpret_cast<const char*>(p.data()) + 1;
+      rc = conv();
+      if (rc != DMEL_EINVAL || !std::strstr(dmel_last_error(), "item 1")) { std::printf("FAIL pcm_convert_items accepted an odd s16 pointer (%d: %s)\n", rc, dmel_last_error()); ++failures; }
+      N[0] = N[1] = 0; SRC[0] = nullptr;          // every item idle: pointers are not looked at, nothing to launch
+      CK(conv());
+    }
     auto xs = buf(2 * 8 * 3000), ys = buf(2 * 8 * 3000), da = buf(8), db = buf(8);
     CK(dmel_aa_snake_f32(xs.data(), ys.data(), al.data(), be.data(), taps.data(), taps.data(), 1, 2, 8, 3000, nullptr));
     CK(dmel_aa_snake_backward_f32(xs.data(), ys.data(), xs.data(), al.data(), be.data(), da.data(), db.data(), taps.data(), taps.data(), 1, 2, 8, 3000, nullptr));

@@ -19,7 +19,15 @@ Both get the same tokens and noise, are interleaved in one process, and every pi
 runs only this: S replies that leave at the given rates (session i at rate i mod len), served (a) by a pool that was told the rates
 (decode_sessions(output_sample_rates=...), open(output_sample_rate=r): ONE resample launch per step) and (b) by the codec-rate pool with
 S StreamResampler(batch=1) behind it, one resample launch and two copies per reply: the parent commit's way.  Same tokens and noise,
-interleaved in one process, equal audio checked, median and 10th / 90th percentile APPENDED to --out."""
+interleaved in one process, equal audio checked, median and 10th / 90th percentile APPENDED to --out.
+
+    python tools/bench_stream.py --sessions 16 --sample-format s16 [--output-sample-rate 48000,16000] [--steps 40] [--out profiles/sessions_pcm.txt]
+
+runs only this: S replies whose wire carries 16-bit PCM, served (a) by a pool that was told so (open(sample_format="s16"): ONE convert
+launch per step into one packed int16 buffer) and (b) by the same pool with f32 sessions and the conversion every caller would do behind
+it, `(y * 32768).round().clamp(-32768, 32767).to(int16)` per reply.  With --output-sample-rate the replies also leave at those rates
+(both forms).  Same tokens and noise, interleaved in one process, equal audio checked, median and 10th / 90th percentile APPENDED to
+--out."""
 import json, os, statistics, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -206,6 +214,74 @@ def sessions_rates_section(S, rates, steps, out):
     print("\n".join(table), file=sys.stderr)
     print(json.dumps(result))
 
+
+def sessions_pcm_section(S, rates, steps, out):
+    chunk, warmup = 64, 6
+    pct = lambda v, q: sorted(v)[min(len(v) - 1, int(q * len(v)))]
+    gl = torch.Generator().manual_seed(9)
+    G, Cn = codec.dmel_groups, codec.decoder.input_channels
+    total = chunk * (steps + 1)
+    ids = torch.randint(0, 175, (S, G, total), generator=gl, dtype=torch.int32).to(dev)
+    noise = torch.randn(S, Cn, total * 4, device=dev)
+    rate = [rates[i % len(rates)] if rates else None for i in range(S)]
+    pools = {"s16_sessions": codec.decode_sessions(S, max_push_tokens=chunk, output_sample_rates=rates),
+             "torch_behind": codec.decode_sessions(S, max_push_tokens=chunk, output_sample_rates=rates)}
+    slots = {"s16_sessions": [pools["s16_sessions"].open(output_sample_rate=rate[i], sample_format="s16") for i in range(S)],
+             "torch_behind": [pools["torch_behind"].open(output_sample_rate=rate[i]) for i in range(S)]}
+    pos = [0] * S
+    ms = {k: [] for k in pools}
+
+    def run(k, n):
+        sl = slots[k]
+        out = pools[k].push({sl[i]: ids[i, :, pos[i]:pos[i] + n[i]] for i in range(S)},
+                            noise={sl[i]: noise[i, :, 4 * pos[i]:4 * (pos[i] + n[i])] for i in range(S)})
+        if k == "s16_sessions":
+            return [out[sl[i]][0] for i in range(S)]
+        return [(out[sl[i]][0] * 32768).round().clamp(-32768, 32767).to(torch.int16) for i in range(S)]
+
+    for step in range(steps):
+        n = [chunk - (i % 3) * (chunk // 3) if step == 0 else chunk for i in range(S)]
+        got = {}
+        keys = list(ms)
+        for k in (keys if step % 2 == 0 else keys[::-1]):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            got[k] = run(k, n)
+            torch.cuda.synchronize()
+            if step >= warmup:
+                ms[k].append((time.perf_counter() - t0) * 1e3)
+        for i in range(S):
+            assert got["s16_sessions"][i].dtype == torch.int16 and torch.equal(got["s16_sessions"][i], got["torch_behind"][i]), \
+                f"step {step}, session {i}: the pool's audio differs"
+            pos[i] += n[i]
+    rows, result = [], {"sessions": S, "sample_format": "s16", "output_sample_rates": rates, "chunk_tokens": chunk, "audio_equal": True}
+    for k, v in ms.items():
+        med = statistics.median(v)
+        result[k] = {"median_ms": round(med, 3), "p10_ms": round(pct(v, 0.1), 3), "p90_ms": round(pct(v, 0.9), 3), "n": len(v)}
+        rows.append(f"{S:8d}  {k:12s}  {med:9.3f}  {pct(v, 0.1):9.3f}  {pct(v, 0.9):9.3f}  {len(v):4d}")
+    result["torch_over_s16"] = round(result["torch_behind"]["median_ms"] / result["s16_sessions"]["median_ms"], 3)
+    rl = ",".join(map(str, rates)) if rates else "the vocoder's rate"
+    table = [f"{S} decode sessions returning 16-bit PCM at {rl}, {chunk}-token pushes, starts a third of a push apart, 100 mel / 10 groups, BigVGAN base "
+             f"(tools/bench_stream.py --sessions {S} --sample-format s16" + (f" --output-sample-rate {rl})" if rates else ")"),
+             f"wall time of one step of all sessions incl. host synchronisation, {steps - warmup} steady-state steps, the two interleaved in one process, "
+             "equal audio checked;",
+             "s16_sessions = open(sample_format=\"s16\"): one convert launch per step; torch_behind = f32 sessions, "
+             "(y * 32768).round().clamp().to(int16) per reply",
+             "sessions  form          median ms     p10 ms     p90 ms     n"] + rows + [
+                 f"torch behind / s16 sessions: {result['torch_over_s16']:.3f} at the median"]
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "a") as f:
+        f.write("\n".join(table) + "\n\n")
+    print("\n".join(table), file=sys.stderr)
+    print(json.dumps(result))
+
+
+if "--sessions" in sys.argv and arg_after("--sample-format", "f32") == "s16":
+    sessions_pcm_section(int(arg_after("--sessions")), [int(r) for r in arg_after("--output-sample-rate", "").split(",") if r],
+                         int(arg_after("--steps", "40")),
+                         arg_after("--out", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                         "sessions_pcm.txt")))
+    sys.exit(0)
 
 if "--sessions" in sys.argv and "--output-sample-rate" in sys.argv:
     sessions_rates_section(int(arg_after("--sessions")), [int(r) for r in arg_after("--output-sample-rate").split(",")],
