@@ -31,10 +31,14 @@ __device__ __forceinline__ float sin_sq(float x) {
   return ((int)n & 1) ? 1.0f - s2 : s2;
 }
 
-// Branch-free body of sin_sq for |x| <= 8192, and the whole function out of line.  Callers that evaluate several values test ALL of them
-// with one wave-uniform branch (ballot) and run either the straight-line bodies -- which the compiler can then interleave: with the
-// branch inside, every evaluation is a basic block of its own and four independent 20-deep dependency chains run one after the other --
-// or, when any lane of the wave holds a large argument (never, for a trained network), the out-of-line copy.  Same values, bit for bit.
+// Branch-free sin^2 for |x| <= 8192 -- the form the activation's FORWARD uses (sin_sq above, the pi/2 form, serves the backward's parameter
+// sums only).  Callers that evaluate several values test ALL of them with one wave-uniform branch (ballot) and run either the straight-line
+// bodies -- which the compiler can then interleave: with the branch inside, every evaluation is a basic block of its own and four
+// independent 20-deep dependency chains run one after the other -- or, when any lane of the wave holds a large argument (never, for a
+// trained network), the out-of-line copy sin_sq_call, which decides PER LANE: |x| > 8192 takes sinf(x)^2, every other lane the same
+// sin_sq_small as on the fast path.  So a value depends on its own argument only, never on what the other 63 lanes of its wave hold --
+// i.e. never on where a tile or a streaming window starts (the bit-identity of decode_stream and of conv_snake.hip with the two-kernel
+// path rest on this; the two polynomials differ in the last bits, so routing small arguments of a mixed wave through sin_sq did not hold it).
 __device__ __forceinline__ float sin_sq_small(float x) {
   // sin^2 has period pi: reduce x to r = x - n pi, |r| <= pi / 2 (three-term Cody-Waite: pi = 3.140625 + 9.67502593994140625e-4 +
   // 1.509957990978376432e-7, the products n * piece exact for |n| < 2^13), then (r + r^3 P(r^2))^2 with a degree-11 odd near-minimax
@@ -54,7 +58,13 @@ __device__ __forceinline__ float sin_sq_small(float x) {
   const float s = fmaf(r * r2, p, r);
   return s * s;
 }
-static __device__ __attribute__((noinline)) float sin_sq_call(float x) { return sin_sq(x); }
+static __device__ __attribute__((noinline)) float sin_sq_call(float x) {
+  if (fabsf(x) > 8192.f) {
+    const float s = sinf(x);
+    return s * s;
+  }
+  return sin_sq_small(x);
+}
 // v[i] <- v[i] + inv_b[i] * sin^2(a[i] * v[i]), N values at once
 template <int N> __device__ __forceinline__ void snake_n(float (&v)[N], const float (&a)[N], const float (&inv_b)[N]) {
   float w[N];
