@@ -9,83 +9,49 @@
 //   up[2m]   = 2 * sum_j f[2j+1] * x[clamp(m+2-j)]      j = 0..5
 //   up[2m+1] = 2 * sum_j f[2j]   * x[clamp(m+3-j)]
 //   out[t]   = sum_k f[k] * v[clamp(2t+k-5, 0, 2T-1)],  v = snake(up)
-// One workgroup owns up to 1024 consecutive outputs of one (b, c) row: the row segment (+6/+6 halo) is read
-// from HBM once with coalesced dword loads into LDS, the activated 2x signal lives only in LDS as
-// (even, odd) pairs, and the store is coalesced.  HBM traffic = 1 read + 1 write per element, which is the
+// One workgroup owns up to 3 x 1008 consecutive outputs of one (b, c) row: each tile's row segment (+6/+6 halo) is read from HBM once
+// into LDS, the activated 2x signal lives only in LDS, and the store is coalesced.  HBM traffic = 1 read + 1 write per element, the
 // algorithmic minimum (8 B/element); the reference kernel's stride-32-per-thread addressing is uncoalesced.
-// Measured (rocprofv3 --pmc, round 1): ~120 vector instructions per output and VALU active ~100 % of the kernel, i.e.
-// the kernel is VALU-issue bound at 2.3-2.6 TB/s, not HBM bound; the two sin^2 per input sample are a third of it.
+// Measured on the MI355X (profiles/aa_snake_blocked.txt), register-blocked form against the one-output-per-thread form it replaced, same
+// bits: 51 against 86 vector instructions and 15.7 against 45.9 LDS-array cycles per 64 outputs (rocprofv3 --pmc, no bank conflicts in
+// either), 3.9-4.6 against 3.0-3.7 TB/s on the 24 M-element benchmark tensors, 2.99 against 3.60 ms per benchmark step.  Both earlier
+// notes in this file against this form are superseded: v_pk_fma_f32 (which the compiler emits for the neighbouring samples' FMA chains,
+// about half of the kernel's vector instructions) does not issue at half rate, and four samples per thread, 0.84x when it was tried
+// before the two-tile prefetch, is 1.2x with it.
 #include "ops.h"
 #include "snake_dev.h"
 
 namespace dmel {
 
-constexpr int kSnakeTile = 1024;
+constexpr int kSnakeTile = 1024;        // the backward kernels' tile
+constexpr int kSnakeFwdTile = 1008;     // the forward kernel's: 4 * 252 outputs, 1014 pairs, a 1020-sample row segment
 
-// 32-bit indices, and tiles that do not touch a sequence edge (block-uniform test) skip every clamp and select.
-// (A v_pk_fma_f32 version of this kernel measured 0.6x: packed fp32 issues at half rate on gfx950.  Four consecutive samples
-// per thread with ds_read_b128 windows -- 8 LDS reads instead of 56 per four outputs -- measured 0.84x: 2.26 vs 2.74 TB/s.)
-// tu: the up-sampling taps times 2 (the x2 gain of UpSample1d, resample.py:37; exact in fp32), td: the low-pass taps of DownSample1d
-// STAGED: xs was filled (and the workgroup synchronised) by the caller -- the software-pipelined kernel below
-template <bool EDGE, bool STAGED = false>
-__device__ __forceinline__ void aa_snake_tile(const float* __restrict__ xr, float* __restrict__ yr, const Taps12& tu, const Taps12& td,
-                                              float a, float inv_b, int t0, int len, int T, float* xs, float2* vs, int tid) {
-  if (!STAGED) {
-    for (int i = tid; i < len + 12; i += 256) {
-      int s = t0 - 6 + i;
-      if (EDGE) s = min(max(s, 0), T - 1);
-      xs[i] = xr[s];
-    }
-    __syncthreads();
-  }
-  for (int p = tid; p < len + 6; p += 256) {
-    const int m = t0 - 3 + p;
-    const int mc = EDGE ? min(max(m, 0), T - 1) : m;
-    const float* xp = xs + (mc - t0 + 6);          // xp[d] = x[clamp(mc + d)]
-    float ue = 0.f, uo = 0.f;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      ue = fmaf(tu.f[2 * j + 1], xp[2 - j], ue);
-      uo = fmaf(tu.f[2 * j], xp[3 - j], uo);
-    }
-    // both evaluations of sin^2 behind ONE wave-uniform test of the large-argument case: as two calls of sin_sq each is a basic block of
-    // its own and the two 20-deep dependency chains run one after the other (snake_dev.h)
-    float uu[2] = {ue, uo};
-    const float aa[2] = {a, a}, bb[2] = {inv_b, inv_b};
-    snake_n(uu, aa, bb);
-    float ve = uu[0], vo = uu[1];
-    if (EDGE) {
-      if (m < 0) vo = ve;          // replicate pad of the 2x signal: v[0] on the left ...
-      if (m > T - 1) ve = vo;      // ... v[2T-1] on the right
-    }
-    vs[p] = make_float2(ve, vo);
-  }
-  __syncthreads();
-  for (int o = tid; o < len; o += 256) {
-    float2 pv[7];
-    lds_read7_b64(vs + o, pv);          // seven conflict-free ds_read_b64 (the compiler's six ds_read2_b32 were two-way conflicts each)
-    const float2 p0 = pv[0], p1 = pv[1], p2 = pv[2], p3 = pv[3], p4 = pv[4], p5 = pv[5], p6 = pv[6];
-    float acc = td.f[0] * p0.y;
-    acc = fmaf(td.f[1], p1.x, acc);
-    acc = fmaf(td.f[2], p1.y, acc);
-    acc = fmaf(td.f[3], p2.x, acc);
-    acc = fmaf(td.f[4], p2.y, acc);
-    acc = fmaf(td.f[5], p3.x, acc);
-    acc = fmaf(td.f[6], p3.y, acc);
-    acc = fmaf(td.f[7], p4.x, acc);
-    acc = fmaf(td.f[8], p4.y, acc);
-    acc = fmaf(td.f[9], p5.x, acc);
-    acc = fmaf(td.f[10], p5.y, acc);
-    acc = fmaf(td.f[11], p6.x, acc);
-    yr[t0 + o] = acc;
-  }
-}
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// Register-blocked forward: every thread owns FOUR consecutive elements in each of the three stages of a tile, and every LDS access
+// and (on aligned rows) every global access is 16 bytes wide.  For the tile that starts at output t0 (a multiple of 4):
+//   xs[k] = x[clamp(t0 - 8 + k)], k = 0..1023     thread q fills xs[4q .. 4q+3]: one global_load_dwordx4 from x + t0 - 8 + 4q when the
+//                                                 row is 16-byte aligned and T % 4 == 0 (VEC), one ds_write_b128
+//   pair p <-> m = t0 - 3 + p, p = 0..len+5       thread q computes pairs 4q .. 4q+3 from the 10 samples x[m-3 .. m+3+3] = xs[4q+2 .. 4q+11]
+//                                                 (xp[d] of the formulas above is xs[p + 5 + d]): three ds_read_b128 of xs[4q .. 4q+11]
+//   ve[p], vo[p]: the activated 2x signal as two planes, written as one ds_write_b128 each at [4q .. 4q+3]
+//   out[t0 + o] needs vo[o .. o+5], ve[o+1 .. o+6] thread r computes o = 4r .. 4r+3 from ve[4r+1 .. 4r+9], vo[4r .. 4r+8]: three
+//                                                 ds_read_b128 of each plane at [4r .. 4r+11], one global_store_dwordx4 to y + t0 + 4r
+// Alignment: xs, ve and vo are 16-byte aligned arrays of 1024 floats and every 16-byte LDS access above starts at float index 4q + {0, 4, 8}
+// -- a multiple of 16 bytes by construction, whatever t0, len or T are.  The largest index touched is 4 * 253 + 11 = 1023 (pairs: 4q <=
+// len + 5 <= 1013; outputs: 4r <= len - 1 <= 1007).  At a 16-byte lane stride ds_read_b128 is conflict-free (MI355X lane groups).
+// Whole passes: 1008 outputs = 252 threads x 4, 1014 pairs = 254 threads x 4 (the last two of 1016 are computed and never read), and the
+// 1020-sample segment t0-6 .. t0+1013 sits at k = 2..1021 of the 1024 floats that 256 threads x 4 load: one pass per stage, no straggler.
+// The arithmetic of every element is the one of the formulas above in the same order, so where a tile or a row starts, and which of the
+// two instantiations runs, never changes a bit.  Replicate padding of the 2x signal (pairs m < 0 and m > T-1) is patched into the planes by
+// three threads between the stages, in the tiles that touch a row end only (block-uniform test).
+template <bool VEC>
 __global__ __launch_bounds__(256) void aa_snake_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                           const float* __restrict__ alpha, const float* __restrict__ beta,
                                                           Taps12 tu, Taps12 td, int logscale, int C, int T, int nsub) {
-  __shared__ float xs[kSnakeTile + 12];
-  __shared__ float2 vs[kSnakeTile + 6];
+  __shared__ __attribute__((aligned(16))) float xs[kSnakeFwdTile + 16];
+  __shared__ __attribute__((aligned(16))) float ve[kSnakeFwdTile + 16];
+  __shared__ __attribute__((aligned(16))) float vo[kSnakeFwdTile + 16];
   const int c = blockIdx.y, b = blockIdx.z;
   const float* xr = x + ((int64_t)b * C + c) * T;
   float* yr = y + ((int64_t)b * C + c) * T;
@@ -96,37 +62,86 @@ __global__ __launch_bounds__(256) void aa_snake_kernel(const float* __restrict__
   }
   const float inv_b = 1.0f / (bt + 1e-9f);
   // nsub consecutive tiles per workgroup, SOFTWARE-PIPELINED: the row segment of tile s + 1 is fetched into registers before tile s is
-  // computed.  The kernel reads 4 KB per workgroup and then computes for ~4 us without touching memory: with 8 workgroups per CU only
-  // ~10 KB per CU were in flight at any time, and bytes-in-flight / latency (Little's law: 10 KB / 2 us x 256 CUs = 1.3 TB/s) was
-  // exactly the read rate the kernel achieved -- it was bound by memory-level parallelism, not by instruction issue.
+  // computed.  A workgroup reads 4 KB and then computes for microseconds without touching memory; without the prefetch the bytes in
+  // flight per CU, not instruction issue, set the read rate (Little's law).
   const int tid = threadIdx.x;
-  constexpr int NR = (kSnakeTile + 12 + 255) / 256;
-  float pre[NR];
   auto fetch = [&](int t0) {
-    const int len = min(kSnakeTile, T - t0);
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-      const int i = tid + 256 * k;
-      const int sidx = min(max(t0 - 6 + min(i, len + 11), 0), T - 1);
-      pre[k] = xr[sidx];
-    }
+    const int s = t0 - 8 + 4 * tid;
+    if (VEC && s >= 0 && s + 4 <= T) return *reinterpret_cast<const f32x4*>(xr + s);
+    f32x4 v;
+    v.x = xr[min(max(s, 0), T - 1)];
+    v.y = xr[min(max(s + 1, 0), T - 1)];
+    v.z = xr[min(max(s + 2, 0), T - 1)];
+    v.w = xr[min(max(s + 3, 0), T - 1)];
+    return v;
   };
-  const int first = blockIdx.x * nsub * kSnakeTile;
-  if (first < T) fetch(first);
-  for (int sub = 0; sub < nsub; ++sub) {
-    const int t0 = first + sub * kSnakeTile;
-    if (t0 >= T) break;
-    const int len = min(kSnakeTile, T - t0);
-    if (sub) __syncthreads();                  // the previous tile's reads of xs / vs are done
+  float aa[8], bb[8];
 #pragma unroll
-    for (int k = 0; k < NR; ++k) {
-      const int i = tid + 256 * k;
-      if (i < len + 12) xs[i] = pre[k];
-    }
-    if (sub + 1 < nsub && t0 + kSnakeTile < T) fetch(t0 + kSnakeTile);     // in flight while this tile is computed
+  for (int i = 0; i < 8; ++i) { aa[i] = a; bb[i] = inv_b; }
+  const int first = blockIdx.x * nsub * kSnakeFwdTile;
+  f32x4 pre = {0.f, 0.f, 0.f, 0.f};
+  if (first < T) pre = fetch(first);
+  for (int sub = 0; sub < nsub; ++sub) {
+    const int t0 = first + sub * kSnakeFwdTile;
+    if (t0 >= T) break;
+    const int len = min(kSnakeFwdTile, T - t0);
+    if (sub) __syncthreads();                  // the previous tile's reads of xs / ve / vo are done
+    *reinterpret_cast<f32x4*>(xs + 4 * tid) = pre;
+    if (sub + 1 < nsub && t0 + kSnakeFwdTile < T) pre = fetch(t0 + kSnakeFwdTile);     // in flight while this tile is computed
     __syncthreads();
-    if (t0 >= 6 && t0 + len + 6 <= T) aa_snake_tile<false, true>(xr, yr, tu, td, a, inv_b, t0, len, T, xs, vs, tid);
-    else aa_snake_tile<true, true>(xr, yr, tu, td, a, inv_b, t0, len, T, xs, vs, tid);
+    if (4 * tid < len + 6) {
+      float w[12];
+      lds_read3_b128(xs + 4 * tid, w);
+      float u[8];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        float ue = 0.f, uo = 0.f;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+          ue = fmaf(tu.f[2 * j + 1], w[i + 7 - j], ue);
+          uo = fmaf(tu.f[2 * j], w[i + 8 - j], uo);
+        }
+        u[2 * i] = ue;
+        u[2 * i + 1] = uo;
+      }
+      // all eight sin^2 behind ONE wave-uniform test of the large-argument case, so the straight-line bodies interleave (snake_dev.h)
+      snake_n(u, aa, bb);
+      *reinterpret_cast<f32x4*>(ve + 4 * tid) = f32x4{u[0], u[2], u[4], u[6]};
+      *reinterpret_cast<f32x4*>(vo + 4 * tid) = f32x4{u[1], u[3], u[5], u[7]};
+    }
+    __syncthreads();
+    const int pe = T - t0 + 3;                 // the first pair past the row's end
+    if (t0 == 0 || pe < len + 6) {             // replicate pad of the 2x signal: v[0] on the left, v[2T-1] on the right
+      if (tid < 3) {
+        if (t0 == 0) ve[tid] = vo[tid] = ve[3];
+        if (pe + tid < len + 6) ve[pe + tid] = vo[pe + tid] = vo[pe - 1];
+      }
+      __syncthreads();
+    }
+    if (4 * tid < len) {
+      float e[12], o[12];
+      lds_read3_b128(ve + 4 * tid, e);
+      lds_read3_b128(vo + 4 * tid, o);
+      f32x4 out;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        float acc = td.f[0] * o[i];
+#pragma unroll
+        for (int k = 1; k < 6; ++k) {
+          acc = fmaf(td.f[2 * k - 1], e[i + k], acc);
+          acc = fmaf(td.f[2 * k], o[i + k], acc);
+        }
+        out[i] = fmaf(td.f[11], e[i + 6], acc);
+      }
+      float* yp = yr + t0 + 4 * tid;
+      if (VEC) {                               // T % 4 == 0: len is a multiple of 4, the thread's four outputs are all inside
+        *reinterpret_cast<f32x4*>(yp) = out;
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (4 * tid + i < len) yp[i] = out[i];
+      }
+    }
   }
 }
 
@@ -330,14 +345,18 @@ int launch_aa_snake(const float* x, float* y, const float* alpha, const float* b
   DMEL_CHECK_ARG(B > 0 && C > 0 && T > 0 && B <= 65535 && C <= 65535 && T < ((int64_t)1 << 30), "aa_snake: bad shape");
   Taps12 tu, td;
   for (int i = 0; i < 12; ++i) { tu.f[i] = 2.f * up_taps_host[i]; td.f[i] = down_taps_host[i]; }
-  // two tiles per workgroup (the second one's row segment is in flight while the first is computed): +4-8 % over one; four or eight
-  // leave the last workgroup of a 5888- or 11776-sample row with a fraction of the work (measured 15-25 % slower on those rows)
-  constexpr int nsub = 2;
-  constexpr int tile = kSnakeTile * nsub;
-  dim3 grid((unsigned)((T + tile - 1) / tile), (unsigned)C, (unsigned)B);
+  // three tiles per workgroup (the next one's row segment is in flight while one is computed).  On the MI355X, us per launch at batch 32
+  // for nsub = 2 / 3 / 4: 128 x 5888: 45.1 / 45.3 / 55.9 (four leave the second workgroup of a row 1.84 tiles against 4), 64 x 11776:
+  // 44.1 / 42.6 / 42.1, 32 x 23552: 43.2 / 42.1 / 41.2 (profiles/aa_snake_blocked.txt)
+  constexpr int nsub = 3;
+  constexpr int span = kSnakeFwdTile * nsub;
+  dim3 grid((unsigned)((T + span - 1) / span), (unsigned)C, (unsigned)B);
+  // 16-byte global accesses need every row to start on a 16-byte boundary; the other instantiation computes the same bits
+  const bool vec = T % 4 == 0 && (reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) % 16 == 0;
   {
     ProfScope ps("aa_snake", s, 0.0, 8.0 * (double)B * C * (double)T);
-    hipLaunchKernelGGL(aa_snake_kernel, grid, dim3(256), 0, s, x, y, alpha, beta, tu, td, logscale, C, (int)T, nsub);
+    if (vec) hipLaunchKernelGGL(aa_snake_kernel<true>, grid, dim3(256), 0, s, x, y, alpha, beta, tu, td, logscale, C, (int)T, nsub);
+    else hipLaunchKernelGGL(aa_snake_kernel<false>, grid, dim3(256), 0, s, x, y, alpha, beta, tu, td, logscale, C, (int)T, nsub);
   }
   DMEL_HIP(hipGetLastError());
   return DMEL_OK;

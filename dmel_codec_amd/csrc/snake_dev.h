@@ -94,4 +94,19 @@ __device__ __forceinline__ void lds_read7_b64(const float2* p, float2 (&v)[7]) {
       : "memory");
 }
 
+// Twelve consecutive floats from a 16-byte-aligned LDS address as three ds_read_b128 (4 LDS cycles each, conflict-free at a 16-byte lane
+// stride), written out like lds_read7_b64 so that the access width never depends on what the compiler can prove about the alignment
+// (a ds_read2_b64 moves the same bytes at half the rate).
+__device__ __forceinline__ void lds_read3_b128(const float* p, float (&v)[12]) {
+  typedef float f32x4_t __attribute__((ext_vector_type(4)));
+  const uint32_t a = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) const char*)p);
+  f32x4_t r0, r1, r2;
+  asm volatile("ds_read_b128 %0, %3\n\tds_read_b128 %1, %3 offset:16\n\tds_read_b128 %2, %3 offset:32\n\ts_waitcnt lgkmcnt(0)"
+               : "=&v"(r0), "=&v"(r1), "=&v"(r2)
+               : "v"(a)
+               : "memory");
+#pragma unroll
+  for (int i = 0; i < 4; ++i) { v[i] = r0[i]; v[4 + i] = r1[i]; v[8 + i] = r2[i]; }
+}
+
 }  // namespace dmel
