@@ -791,6 +791,88 @@ __device__ __forceinline__ void pcm_convert_tile(const void* src, void* dst, int
     else d32[e] = s32[e];
   }
 }
+// G.711 (include/dmel_hip.h has the rule): 8-bit mu-law / A-law <-> the s16 value, integer arithmetic on every lane alike -- the segment
+// is a count of leading zeros, never a search or a table, and the selects are v_cndmask, not branches.  x is an s16 value in an int.
+__device__ __forceinline__ uint32_t g711_ulaw_encode(int x) {
+  const int v = x >> 2;
+  const bool neg = v < 0;
+  const int m = min((neg ? -v : v) + 33, 8191);                 // 33 .. 8191: bit 5 is always set, so seg is 0 .. 7
+  const int seg = 26 - __clz(m);                                // floor(log2 m) - 5
+  return (uint32_t)(((seg << 4) | ((m >> (seg + 1)) & 15)) ^ (neg ? 0x7F : 0xFF));
+}
+__device__ __forceinline__ int g711_ulaw_decode(uint32_t code) {
+  const uint32_t u = ~code & 0xFFu;
+  const int t = (int)((((u & 15u) << 3) + 0x84u) << ((u & 0x70u) >> 4));
+  return (u & 0x80u) ? 0x84 - t : t - 0x84;
+}
+__device__ __forceinline__ uint32_t g711_alaw_encode(int x) {
+  const int v = x >> 3;
+  const bool neg = v < 0;
+  const int m = neg ? -v - 1 : v;                               // 0 .. 4095
+  const int seg = max(27 - __clz(max(m, 1)), 0);                // max(floor(log2 max(m, 1)) - 4, 0): 0 .. 7
+  const int mant = (m >> max(seg, 1)) & 15;                     // segments 0 and 1 both have a step of 2
+  return (uint32_t)(((seg << 4) | mant) ^ (neg ? 0x55 : 0xD5));
+}
+__device__ __forceinline__ int g711_alaw_decode(uint32_t code) {
+  const uint32_t a = (code ^ 0x55u) & 0xFFu;
+  const int seg = (int)((a & 0x70u) >> 4);
+  int t = (int)((a & 15u) << 4);
+  t = seg == 0 ? t + 8 : (t + 0x108) << max(seg - 1, 0);
+  return (a & 0x80u) ? t : -t;
+}
+// ALAW: the law; both directions of both paths go through these two
+template <bool ALAW>
+__device__ __forceinline__ float g711_to_f32(uint32_t code) {
+  return (float)(ALAW ? g711_alaw_decode(code) : g711_ulaw_decode(code)) * 0x1p-15f;   // |x| < 2^15: exact
+}
+template <bool ALAW>
+__device__ __forceinline__ uint32_t g711_from_f32(float v) {
+  const int x = pcm_f32_to_s16(v);                              // the s16 rounding rule, unchanged
+  return ALAW ? g711_alaw_encode(x) : g711_ulaw_encode(x);
+}
+// ENC: f32 -> law (the destination holds bytes), else law -> f32 (the source does).  `wide`: the item's f32 pointer is 16-byte and its
+// law pointer 8-byte aligned (workgroup-uniform); then a thread whose 8 consecutive elements all lie in the item moves them as 8 bytes on
+// the law side and 2 x 16 bytes on the f32 side.  Everything else goes element by element as in pcm_convert_tile: one byte and one dword
+// per lane, a wave on consecutive addresses.
+template <bool ALAW, bool ENC>
+__device__ __forceinline__ void g711_convert_tile(const void* src, void* dst, int64_t n, int64_t base, bool wide) {
+  const uint8_t* s8 = static_cast<const uint8_t*>(src);
+  const float* sf = static_cast<const float*>(src);
+  uint8_t* d8 = static_cast<uint8_t*>(dst);
+  float* df = static_cast<float*>(dst);
+  int64_t from = base;                                         // the element-wise path covers [from, min(n, base + kPcmTile))
+  if (wide) {
+    const int64_t whole = base + (min(n - base, (int64_t)kPcmTile) & ~(int64_t)(kPcmPerThread - 1));
+    const int64_t e = base + (int64_t)threadIdx.x * kPcmPerThread;
+    if (e < whole) {
+      if constexpr (ENC) {
+        const float4* p = reinterpret_cast<const float4*>(sf + e);
+        const float4 a = p[0], b = p[1];
+        const float f[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+        uint32_t w[2] = {0u, 0u};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) w[j >> 2] |= g711_from_f32<ALAW>(f[j]) << (8 * (j & 3));
+        *reinterpret_cast<uint2*>(d8 + e) = make_uint2(w[0], w[1]);
+      } else {
+        const uint2 a = *reinterpret_cast<const uint2*>(s8 + e);
+        const uint32_t w[2] = {a.x, a.y};
+        float f[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) f[j] = g711_to_f32<ALAW>((w[j >> 2] >> (8 * (j & 3))) & 0xFFu);
+        float4* o = reinterpret_cast<float4*>(df + e);
+        o[0] = make_float4(f[0], f[1], f[2], f[3]);
+        o[1] = make_float4(f[4], f[5], f[6], f[7]);
+      }
+    }
+    from = whole;
+  }
+  const int64_t end = min(n, base + kPcmTile);
+  for (int64_t e = from + threadIdx.x; e < end; e += 256) {
+    if constexpr (ENC) d8[e] = (uint8_t)g711_from_f32<ALAW>(sf[e]);
+    else df[e] = g711_to_f32<ALAW>(s8[e]);
+  }
+}
+__device__ __forceinline__ bool pcm_is_law(int64_t f) { return f == DMEL_SAMPLE_ULAW || f == DMEL_SAMPLE_ALAW; }
 __global__ __launch_bounds__(256) void pcm_convert_kernel(const int64_t* __restrict__ items) {
   const int64_t* it = items + kPcmItemWords * (int64_t)blockIdx.y;
   const int64_t n = uniform_i64(it + 2);
@@ -800,6 +882,18 @@ __global__ __launch_bounds__(256) void pcm_convert_kernel(const int64_t* __restr
   const int64_t fmt = uniform_i64(it + 3);
   const void* src = reinterpret_cast<const void*>(sa);
   void* dst = reinterpret_cast<void*>(da);
+  if (pcm_is_law(fmt & 0xff)) {                                // law -> f32 (the entry admits no other destination)
+    const bool wide8 = (sa & 7) == 0 && (da & 15) == 0;
+    if ((fmt & 0xff) == DMEL_SAMPLE_ULAW) g711_convert_tile<false, false>(src, dst, n, base, wide8);
+    else g711_convert_tile<true, false>(src, dst, n, base, wide8);
+    return;
+  }
+  if (pcm_is_law(fmt >> 8)) {                                  // f32 -> law
+    const bool wide8 = (sa & 15) == 0 && (da & 7) == 0;
+    if ((fmt >> 8) == DMEL_SAMPLE_ULAW) g711_convert_tile<false, true>(src, dst, n, base, wide8);
+    else g711_convert_tile<true, true>(src, dst, n, base, wide8);
+    return;
+  }
   const bool wide = ((sa | da) & 15) == 0;
   if ((fmt & 0xff) == DMEL_SAMPLE_S16) pcm_convert_tile<true, false>(src, dst, n, base, wide);
   else if ((fmt >> 8) == DMEL_SAMPLE_S16) pcm_convert_tile<false, true>(src, dst, n, base, wide);
@@ -933,7 +1027,11 @@ extern "C" int dmel_resample_window_items_f32(const float* x, int64_t x_row_stri
                                       table_scratch + (size_t)kResampleItemWords * B, max_out, lds_floats, bytes, (hipStream_t)stream);
 }
 
-// ---- B ragged convert-copies between 16-bit PCM and fp32 in one launch (include/dmel_hip.h: dmel_pcm_convert_items) ----------------
+// ---- B ragged convert-copies between 16-bit PCM, G.711 and fp32 in one launch (include/dmel_hip.h: dmel_pcm_convert_items) ---------
+// bytes of one sample of a DMEL_SAMPLE_* format; 0: not a format (2 .. 7 are not assigned)
+static int pcm_sample_bytes(int fmt) {
+  return fmt == DMEL_SAMPLE_F32 ? 4 : fmt == DMEL_SAMPLE_S16 ? 2 : (fmt == DMEL_SAMPLE_ULAW || fmt == DMEL_SAMPLE_ALAW) ? 1 : 0;
+}
 extern "C" int dmel_pcm_convert_items(const void* const* src, const int32_t* src_fmt, void* const* dst, const int32_t* dst_fmt,
                                       const int64_t* n, int B, void* table_scratch, void* stream) {
   using namespace dmel;
@@ -945,14 +1043,18 @@ extern "C" int dmel_pcm_convert_items(const void* const* src, const int32_t* src
   double bytes = 0.0;
   for (int b = 0; b < B; ++b) {
     const int sf = src_fmt[b], df = dst_fmt[b];
-    DMEL_CHECK_ARG((sf == DMEL_SAMPLE_F32 || sf == DMEL_SAMPLE_S16) && (df == DMEL_SAMPLE_F32 || df == DMEL_SAMPLE_S16),
-                   "pcm_convert_items: item %d: sample formats %d -> %d, expected DMEL_SAMPLE_F32 (0) or DMEL_SAMPLE_S16 (1)", b, sf, df);
+    DMEL_CHECK_ARG(pcm_sample_bytes(sf) && pcm_sample_bytes(df),
+                   "pcm_convert_items: item %d: sample formats %d -> %d, expected DMEL_SAMPLE_F32 (0), DMEL_SAMPLE_S16 (1), "
+                   "DMEL_SAMPLE_ULAW (8) or DMEL_SAMPLE_ALAW (9)", b, sf, df);
     DMEL_CHECK_ARG(!(sf == DMEL_SAMPLE_S16 && df == DMEL_SAMPLE_S16), "pcm_convert_items: item %d: s16 -> s16 is not a conversion", b);
+    DMEL_CHECK_ARG(sf == DMEL_SAMPLE_F32 || df == DMEL_SAMPLE_F32,
+                   "pcm_convert_items: item %d: %d -> %d is not a conversion served here: mu-law and A-law convert from and to f32 only", b, sf,
+                   df);
     DMEL_CHECK_ARG(n[b] >= 0 && n[b] < ((int64_t)1 << 40), "pcm_convert_items: item %d: sample count %lld out of range", b, (long long)n[b]);
     if (n[b] == 0) continue;
     DMEL_CHECK_ARG(src[b] && dst[b], "pcm_convert_items: item %d: NULL pointer with %lld samples", b, (long long)n[b]);
     const uintptr_t sa = (uintptr_t)src[b], da = (uintptr_t)dst[b];
-    const int ss = sf == DMEL_SAMPLE_S16 ? 2 : 4, ds = df == DMEL_SAMPLE_S16 ? 2 : 4;
+    const int ss = pcm_sample_bytes(sf), ds = pcm_sample_bytes(df);   // a law pointer (1 byte) needs no alignment
     DMEL_CHECK_ARG(sa % ss == 0 && da % ds == 0, "pcm_convert_items: item %d: a pointer is not aligned to its sample size (%d -> %d bytes)", b,
                    ss, ds);
     int64_t* it = tab.data() + (size_t)kPcmItemWords * b;

@@ -7,7 +7,8 @@ the kernels one row per slot (dmel_stft_window_items_f32, dmel_wavenet_stream_st
 by its own number of samples, in one STFT launch and one encoder launch.  Sessions whose sound cards do not run at the codec's rate
 declare their own rate when they open; all of them, whatever their rates, are converted by one resample launch per step
 (utils/resample.py: SessionResampler, dmel_resample_window_items_f32).  Sessions whose wire carries 16-bit PCM declare that too
-(open(sample_format="s16")): the conversion is folded into the per-slot copy a pool makes anyway, one launch for all slots of a step
+(open(sample_format="s16")), and so do sessions whose wire is telephony's G.711 (open(sample_format="ulaw" | "alaw"), 8-bit codes,
+usually at 8 kHz): the conversion is folded into the per-slot copy a pool makes anyway, one launch for all slots of a step
 (utils/pcm.py, dmel_pcm_convert_items)."""
 from __future__ import annotations
 
@@ -21,6 +22,8 @@ from .. import _lib
 from ..utils import pcm
 from .stream_schedule import (DecodeGeometry, DecodeSchedule, EncodeGeometry, EncodeSchedule, decode_capacity, decode_rebase,
                               decode_session_rows, resample_max_outputs, session_rows)
+
+_WIRE_DTYPES = {dt for name, (_, dt) in pcm.FORMATS.items() if name != "f32"}     # torch.int16, torch.uint8
 
 
 class EncodeSessions:
@@ -55,8 +58,11 @@ class EncodeSessions:
     named slots with samples go through ONE dmel_pcm_convert_items launch (f32 slots as plain copies) that writes exactly where the
     per-slot copies of the float path write: behind the slot's sample tail, or behind its tail in the SessionResampler's rows; the
     resample launch, the STFT launch and the encoder step follow unchanged.  A step without an s16 slot takes the float path as it was.
-    A push whose dtype does not match its slot's format is a ValueError.  Out of scope: the lockstep StreamingEncoder and whole-clip
-    encode() (callers have utils.pcm.from_pcm16), other formats (s24, s32, u8, mu-law), dither.
+    A push whose dtype does not match its slot's format is a ValueError.  open(sample_format="ulaw" | "alaw") starts a G.711 session
+    the same way: its pushes are torch.uint8 codes, its ids the bits of the same session opened as "f32" and fed
+    from_g711(clip, law) -- of encode(from_g711(clip, law), len, sample_rate=r); the one convert launch of the step decodes them
+    (the companding rule of utils/pcm.py).  Out of scope: the lockstep StreamingEncoder and whole-clip encode() (callers have
+    utils.pcm.from_pcm16 / from_g711), other formats (s24, s32, u8), dither.
 
     Only encoders the one-launch streaming kernel takes (residual channels in (32, 80], no condition, no output projection,
     dilations <= 8, fp32): anything else is refused at construction.
@@ -147,8 +153,8 @@ class EncodeSessions:
 
     def open(self, sample_rate: Optional[int] = None, sample_format: str = "f32") -> int:
         """take a free slot: fresh schedule, state zeroed before its first push.  sample_rate: the rate this session's pushes arrive
-        at, one of the declared `sample_rates` (None: the codec's).  sample_format: "f32", or "s16" for torch.int16 pushes (16-bit
-        signed PCM, x / 32768).  Raises when every slot is taken."""
+        at, one of the declared `sample_rates` (None: the codec's).  sample_format: "f32", "s16" for torch.int16 pushes (16-bit
+        signed PCM, x / 32768), or "ulaw" / "alaw" for torch.uint8 pushes (G.711 codes).  Raises when every slot is taken."""
         pcm.check_format(sample_format)
         rate = self.codec_rate if sample_rate is None else int(sample_rate)
         if rate != self.codec_rate and rate not in self.sample_rates:
@@ -188,7 +194,8 @@ class EncodeSessions:
                 raise ValueError(f"slot {slot}: expected mono audio (n,) or (1, n), got {tuple(a.shape)}")
             if a.shape[0] > self.max_push:
                 raise ValueError(f"slot {slot}: a push of {a.shape[0]} samples exceeds max_push_samples = {self.max_push}")
-            if (a.dtype == torch.int16) if self.fmt[slot] == "f32" else (a.dtype != torch.int16):
+            # the push's dtype is the dtype of the slot's format; an f32 slot refuses the dtypes of the other formats
+            if (a.dtype in _WIRE_DTYPES) if self.fmt[slot] == "f32" else (a.dtype != pcm.FORMATS[self.fmt[slot]][1]):
                 raise ValueError(f"slot {slot} was opened with sample_format={self.fmt[slot]!r}: a {a.dtype} push does not match")
             out[slot] = a
         for slot in final:
@@ -250,16 +257,17 @@ class EncodeSessions:
         steps = {}
         # ---- the sound cards' rates: ONE launch converts every slot that needs it, straight behind the slot's sample tail
         converted = {s: a for s, a in audio.items() if self._converts(s)}
-        # ---- the wire's format: a step that names an s16 slot puts ALL its chunks in place with ONE convert launch, each where the
+        # ---- the wire's format: a step that names an s16 or a G.711 slot puts ALL its chunks in place with ONE convert launch, each where the
         # float path's per-slot copy would put it -- behind the slot's resampler tail or behind its sample tail
-        placed = any(self.fmt[s] == "s16" for s in audio)
+        placed = any(self.fmt[s] != "f32" for s in audio)
         if placed:
             converted = self.rs.destinations({s: a.shape[0] for s, a in converted.items()}) if converted else {}
             moves = [((a.to(torch.float32) if self.fmt[s] == "f32" else a).contiguous(),
-                      converted[s] if s in converted else b["samples"][s, self.tail[s]:self.tail[s] + a.shape[0]])
+                      converted[s] if s in converted else b["samples"][s, self.tail[s]:self.tail[s] + a.shape[0]], self.fmt[s])
                      for s, a in audio.items() if a.shape[0]]
             if moves:
-                pcm.convert_items([x for x, _ in moves], [y for _, y in moves], table=b["pcm_tab"])
+                pcm.convert_items([x for x, _, _ in moves], [y for _, y, _ in moves], table=b["pcm_tab"],
+                                  src_formats=[f for _, _, f in moves])
         released = (self.rs.push(converted, final & set(converted), out=b["samples"], out_off=self.tail, placed=placed)
                     if converted else {})
         for s, a in audio.items():
@@ -390,8 +398,11 @@ class DecodeSessions:
     ONE dmel_pcm_convert_items launch takes every s16 slot's new piece -- the crop inside the vocoder's batch, or the slot's resampler
     output -- and writes it into one packed int16 buffer of the step; the tensors returned are views of that buffer (this takes the
     place of the clone that detaches a float piece).  f32 slots of such a step keep their path and their bits.  "s16" with
-    return_audios=False is a ValueError at open.  Out of scope: the lockstep StreamingDecoder and whole-clip decode() (callers have
-    utils.pcm.to_pcm16), other formats (s24, s32, u8, mu-law), dither.
+    return_audios=False is a ValueError at open.  open(sample_format="ulaw" | "alaw") starts a G.711 reply the same way: its audio
+    comes back as torch.uint8 codes, the companding rule of utils/pcm.py applied to the s16 rounding of that float audio.  The packed
+    buffer of the step holds bytes, each piece at a multiple of 16 of them; s16 pieces are int16 views of it, law pieces uint8 views.
+    Out of scope: the lockstep StreamingDecoder and whole-clip decode() (callers have utils.pcm.to_pcm16 / to_g711), other formats
+    (s24, s32, u8), dither.
 
     Out of scope, NotImplementedError: overlap_vocoder, graph_chunk_tokens, and a pool-wide output_sample_rate (a pool has no rate of
     its own).
@@ -473,8 +484,8 @@ class DecodeSessions:
 
     def open(self, output_sample_rate: Optional[int] = None, sample_format: str = "f32") -> int:
         """take a free slot: fresh schedule, state zeroed before its first push.  output_sample_rate: the rate this session's audio
-        leaves at, one of the declared `output_sample_rates` (None: the vocoder's).  sample_format: "f32", or "s16" for audio returned
-        as torch.int16 (16-bit signed PCM).  Raises when every slot is taken."""
+        leaves at, one of the declared `output_sample_rates` (None: the vocoder's).  sample_format: "f32", "s16" for audio returned
+        as torch.int16 (16-bit signed PCM), or "ulaw" / "alaw" for torch.uint8 (G.711 codes).  Raises when every slot is taken."""
         if pcm.check_format(sample_format) != "f32" and not self.return_audios:
             raise ValueError(f"sample_format={sample_format!r} without audio: return_audios=False leaves nothing to convert")
         rate = self.voc_rate if output_sample_rate is None else int(output_sample_rate)
@@ -627,7 +638,7 @@ class DecodeSessions:
                 if st.voc_window[1] > st.voc_window[0]:
                     vgroups.setdefault(st.voc_window[1] - st.voc_window[0], []).append(s)
             pieces: Dict[int, torch.Tensor] = {}       # the new audio of the slots that leave at another rate, still in the vocoder's batch
-            wire: Dict[int, torch.Tensor] = {}         # the new float audio of the s16 slots, where it lies: converted at the end of the step
+            wire: Dict[int, torch.Tensor] = {}         # the new float audio of the non-f32 slots, where it lies: converted at the end of the step
             for _, members in vgroups.items():
                 wins = [b["mel"][s, :, steps[s].voc_window[0] - self.origin[s]:steps[s].voc_window[1] - self.origin[s]] for s in members]
                 wav = codec.vocoder(torch.stack(wins).contiguous())
@@ -637,7 +648,7 @@ class DecodeSessions:
                     piece = wav[i, :, (st.emit[0] - lo) * self.up:(st.emit[1] - lo) * self.up]
                     if self.rate[s] != self.voc_rate:
                         pieces[s] = piece[0]
-                    elif self.fmt[s] == "s16":
+                    elif self.fmt[s] != "f32":
                         wire[s] = piece[0]
                     else:
                         out[s] = (piece.clone(), out[s][1])
@@ -649,21 +660,22 @@ class DecodeSessions:
                         pieces[s] = torch.empty(0, dtype=torch.float32, device=dev)
                 if pieces:
                     for s, y in self.rs.push(pieces, final & set(pieces)).items():
-                        if self.fmt[s] == "s16":
+                        if self.fmt[s] != "f32":
                             wire[s] = y
                         else:
                             out[s] = (y[None], out[s][1])
-            # ---- the wire's format: ONE launch converts every s16 slot's new piece into one packed int16 buffer of the step (each
-            # piece at a multiple of 8 samples = 16 bytes); the tensors handed out are views of it
+            # ---- the wire's format: ONE launch converts every non-f32 slot's new piece into one packed buffer of bytes of the step (each
+            # piece at a multiple of 16 bytes); the tensors handed out are views of it, int16 for s16 and uint8 for the G.711 laws
             wire = {s: y for s, y in wire.items() if y.shape[0]}
             if wire:
                 at, total = {}, 0
                 for s, y in wire.items():
                     at[s] = total
-                    total += (y.shape[0] + 7) // 8 * 8
-                packed = torch.empty(total, dtype=torch.int16, device=dev)
-                dsts = [packed[at[s]:at[s] + y.shape[0]] for s, y in wire.items()]
-                pcm.convert_items(list(wire.values()), dsts, table=b["pcm_tab"])
+                    total += (y.shape[0] * pcm.FORMATS[self.fmt[s]][1].itemsize + 15) // 16 * 16
+                packed = torch.empty(total, dtype=torch.uint8, device=dev)
+                dsts = [packed[at[s]:at[s] + y.shape[0] * pcm.FORMATS[self.fmt[s]][1].itemsize].view(pcm.FORMATS[self.fmt[s]][1])
+                        for s, y in wire.items()]
+                pcm.convert_items(list(wire.values()), dsts, table=b["pcm_tab"], dst_formats=[self.fmt[s] for s in wire])
                 for (s, _), d in zip(wire.items(), dsts):
                     out[s] = (d[None], out[s][1])
         for s in final:

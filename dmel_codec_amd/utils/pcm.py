@@ -1,5 +1,6 @@
-"""The sample format of the wire on the MI355X: 16-bit signed PCM <-> fp32 (csrc/small_ops.hip: pcm_convert_kernel, through
-dmel_pcm_convert_items).  Microphones, RTP, WebSocket audio and sound cards carry int16; the codec computes in fp32.
+"""The sample format of the wire on the MI355X: 16-bit signed PCM or 8-bit G.711 (mu-law, A-law) <-> fp32 (csrc/small_ops.hip:
+pcm_convert_kernel, through dmel_pcm_convert_items).  Microphones, RTP, WebSocket audio and sound cards carry int16, telephony (PSTN
+gateways, SIP trunks, RTP payload types 0 and 8) carries G.711 at 8 kHz; the codec computes in fp32.
 
 The rounding rule, written down once:
 
@@ -10,10 +11,27 @@ The rounding rule, written down once:
                  saturate; no dither, so the result is deterministic.  On the CPU:
                  clamp(round(nan_to_num(y, nan=0) * 32768), -32768, 32767).to(int16)
 
-from_pcm16 / to_pcm16 convert a whole tensor, convert_items any list of ragged pieces, each in ONE launch.  The session pools
-(models/stream_sessions.py) fold the same launch into the per-slot copies they make anyway: open(sample_format="s16").
+The companding rule, written down once: ITU-T G.711 as Sun's g711.c and CPython's audioop restate it.  Integer arithmetic on the s16
+value x (>> is an arithmetic shift), so every check of it is an equality of bits:
 
-Out of scope: other formats (s24, s32, u8, mu-law) and dither."""
+    mu-law encode   v = x >> 2; neg = v < 0; m = min((neg ? -v : v) + 33, 8191); seg = floor(log2(m)) - 5       (0 .. 7)
+                    code = ((seg << 4) | ((m >> (seg + 1)) & 15)) ^ (neg ? 0x7F : 0xFF)
+    mu-law decode   u = ~code & 0xFF; t = (((u & 15) << 3) + 0x84) << ((u & 0x70) >> 4); x = (u & 0x80) ? 0x84 - t : t - 0x84
+    A-law encode    v = x >> 3; neg = v < 0; m = neg ? -v - 1 : v; seg = max(floor(log2(max(m, 1))) - 4, 0)
+                    mant = seg < 2 ? (m >> 1) & 15 : (m >> seg) & 15; code = ((seg << 4) | mant) ^ (neg ? 0x55 : 0xD5)
+    A-law decode    a = code ^ 0x55; t = (a & 15) << 4; seg = (a & 0x70) >> 4; t = seg == 0 ? t + 8 : (t + 0x108) << (seg - 1)
+                    x = (a & 0x80) ? t : -t
+    law -> f32      y = decode(code) / 32768                        exact
+    f32 -> law      code = encode(the f32 -> s16 rule above, unchanged): NaN and 0.0 give 0xFF (mu-law) and 0xD5 (A-law)
+
+encode(decode(c)) == c for all 256 A-law codes and for every mu-law code but 0x7F ("negative zero": it decodes to 0, which encodes as
+0xFF).  law <-> s16 and law <-> law are not served.
+
+from_pcm16 / to_pcm16 and from_g711 / to_g711 convert a whole tensor, convert_items any list of ragged pieces, each in ONE launch.  The
+session pools (models/stream_sessions.py) fold the same launch into the per-slot copies they make anyway:
+open(sample_format="s16" | "ulaw" | "alaw").
+
+Out of scope: other formats (s24, s32, u8), law <-> s16 transcoding, packet-loss concealment and dither."""
 from __future__ import annotations
 
 import ctypes as C
@@ -24,8 +42,9 @@ import torch
 from .. import _lib
 
 # sample_format -> (DMEL_SAMPLE_* of include/dmel_hip.h, dtype)
-FORMATS = {"f32": (0, torch.float32), "s16": (1, torch.int16)}
-_CODE = {dt: code for code, dt in FORMATS.values()}
+FORMATS = {"f32": (0, torch.float32), "s16": (1, torch.int16), "ulaw": (8, torch.uint8), "alaw": (9, torch.uint8)}
+LAWS = ("ulaw", "alaw")
+_INFER = {torch.float32: "f32", torch.int16: "s16"}                # torch.uint8 alone does not say which law
 MAX_ITEMS = 65535
 
 
@@ -35,21 +54,43 @@ def check_format(sample_format) -> str:
     return sample_format
 
 
+def _formats(pieces, names, what: str):
+    """the format name of every piece: the one the caller gave, else the one its dtype implies (None: no format has that dtype)"""
+    if names is not None and len(names) != len(pieces):
+        raise ValueError(f"{what}_formats names {len(names)} pieces, expected {len(pieces)}")
+    out = []
+    for i, t in enumerate(pieces):
+        name = None if names is None else names[i]
+        if name is None:
+            if t.dtype == torch.uint8:
+                raise ValueError(f"item {i}: a torch.uint8 {what} is mu-law or A-law: name it ({what}_formats=, one of {list(LAWS)})")
+            name = _INFER.get(t.dtype)
+        elif t.dtype != FORMATS[check_format(name)][1]:
+            raise ValueError(f"item {i}: a {what} of format {name!r} is {FORMATS[name][1]}, got {t.dtype}")
+        out.append(name)
+    return out
+
+
 @torch.no_grad()
-def convert_items(srcs: Sequence[torch.Tensor], dsts: Sequence[torch.Tensor], table: Optional[torch.Tensor] = None) -> None:
-    """dsts[i][:] = convert(srcs[i]) for lists of 1-D CUDA tensors with contiguous samples, int16 or float32, in ONE launch: s16 -> f32,
-    f32 -> s16 (the rounding rule of the module docstring) or f32 -> f32 (a copy); s16 -> s16 is refused.  Pieces may have any
-    lengths, 0 included, and any alignment; no destination may overlap a source or another destination.  table: device scratch of
-    4 * len(srcs) int64 a caller that converts every step keeps (default: allocated here).  Runs on the current stream."""
+def convert_items(srcs: Sequence[torch.Tensor], dsts: Sequence[torch.Tensor], table: Optional[torch.Tensor] = None,
+                  src_formats: Optional[Sequence[Optional[str]]] = None, dst_formats: Optional[Sequence[Optional[str]]] = None) -> None:
+    """dsts[i][:] = convert(srcs[i]) for lists of 1-D CUDA tensors with contiguous samples, in ONE launch: s16 -> f32, f32 -> s16 (the
+    rounding rule of the module docstring), f32 -> f32 (a copy), ulaw / alaw -> f32 and f32 -> ulaw / alaw (the companding rule of
+    the module docstring); s16 -> s16, law <-> s16 and law <-> law are refused.  src_formats / dst_formats: the name of each piece's
+    format (utils/pcm.py: FORMATS; an entry may be None); by default a piece's dtype says it, float32 or int16 -- a torch.uint8 piece
+    must be named, because its dtype does not say which law.  Pieces may have any lengths, 0 included, and any alignment; no
+    destination may overlap a source or another destination.  table: device scratch of 4 * len(srcs) int64 a caller that converts
+    every step keeps (default: allocated here).  Runs on the current stream."""
     B = len(srcs)
     if B != len(dsts) or not 1 <= B <= MAX_ITEMS:
         raise ValueError(f"expected as many destinations as sources, 1 .. {MAX_ITEMS} of them (got {B} and {len(dsts)})")
+    sf, df = _formats(srcs, src_formats, "source"), _formats(dsts, dst_formats, "destination")
     dev = srcs[0].device
     for i, (x, y) in enumerate(zip(srcs, dsts)):
         _lib.require_cuda(x, "source")
         _lib.require_cuda(y, "destination")
-        if x.dtype not in _CODE or y.dtype not in _CODE:
-            raise ValueError(f"item {i}: {x.dtype} -> {y.dtype}: samples are torch.int16 or torch.float32")
+        if sf[i] is None or df[i] is None:
+            raise ValueError(f"item {i}: {x.dtype} -> {y.dtype}: samples are torch.int16, torch.float32 or (named) torch.uint8")
         if x.ndim != 1 or y.ndim != 1 or x.shape != y.shape or (x.shape[0] > 1 and (x.stride(0) != 1 or y.stride(0) != 1)):
             raise ValueError(f"item {i}: expected two 1-D tensors of equal length with contiguous samples, got {tuple(x.shape)} "
                              f"(stride {x.stride()}) -> {tuple(y.shape)} (stride {y.stride()})")
@@ -61,8 +102,8 @@ def convert_items(srcs: Sequence[torch.Tensor], dsts: Sequence[torch.Tensor], ta
         raise ValueError(f"table must hold {4 * B} contiguous int64 on {dev}")
     P, I32, I64 = C.c_void_p * B, C.c_int32 * B, C.c_int64 * B
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().dmel_pcm_convert_items(P(*[x.data_ptr() for x in srcs]), I32(*[_CODE[x.dtype] for x in srcs]),
-                                                     P(*[y.data_ptr() for y in dsts]), I32(*[_CODE[y.dtype] for y in dsts]),
+        _lib.check(_lib.lib().dmel_pcm_convert_items(P(*[x.data_ptr() for x in srcs]), I32(*[FORMATS[f][0] for f in sf]),
+                                                     P(*[y.data_ptr() for y in dsts]), I32(*[FORMATS[f][0] for f in df]),
                                                      I64(*[x.shape[0] for x in srcs]), B, table.data_ptr(), _lib.stream_ptr()),
                    "pcm_convert_items")
 
@@ -76,22 +117,42 @@ def _rows(x: torch.Tensor, dtype, what: str) -> torch.Tensor:
     return x.contiguous()
 
 
-def _convert_rows(x: torch.Tensor, dtype) -> torch.Tensor:
-    y = torch.empty(x.shape, dtype=dtype, device=x.device)
+def _convert_rows(x: torch.Tensor, src_format: str, dst_format: str) -> torch.Tensor:
+    y = torch.empty(x.shape, dtype=FORMATS[dst_format][1], device=x.device)
     xs, ys = (x[None], y[None]) if x.ndim == 1 else (x, y)
     if x.numel():
         for a in range(0, xs.shape[0], MAX_ITEMS):                 # one item per row; a launch takes 65535 of them
-            convert_items(list(xs[a:a + MAX_ITEMS].unbind(0)), list(ys[a:a + MAX_ITEMS].unbind(0)))
+            k = min(MAX_ITEMS, xs.shape[0] - a)
+            convert_items(list(xs[a:a + k].unbind(0)), list(ys[a:a + k].unbind(0)), src_formats=[src_format] * k,
+                          dst_formats=[dst_format] * k)
     return y
 
 
 def from_pcm16(x: torch.Tensor) -> torch.Tensor:
     """x (B, n) or (n,) torch.int16 on the GPU -> float32 of the same shape, x / 32768 (exact).  What a caller puts in front of the
     whole-clip encode()."""
-    return _convert_rows(_rows(x, torch.int16, "pcm"), torch.float32)
+    return _convert_rows(_rows(x, torch.int16, "pcm"), "s16", "f32")
 
 
 def to_pcm16(y: torch.Tensor) -> torch.Tensor:
     """y (B, n) or (n,) torch.float32 on the GPU -> torch.int16 of the same shape by the rounding rule of the module docstring.
     What a caller puts behind the whole-clip decode()."""
-    return _convert_rows(_rows(y, torch.float32, "waveform"), torch.int16)
+    return _convert_rows(_rows(y, torch.float32, "waveform"), "f32", "s16")
+
+
+def _check_law(law) -> str:
+    if law not in LAWS:
+        raise ValueError(f"unknown companding law {law!r}: expected one of {list(LAWS)}")
+    return law
+
+
+def from_g711(x: torch.Tensor, law: str) -> torch.Tensor:
+    """x (B, n) or (n,) torch.uint8 on the GPU, G.711 codes of `law` ("ulaw" | "alaw") -> float32 of the same shape, decode(code) /
+    32768 (exact).  What a caller puts in front of the whole-clip encode(..., sample_rate=8000)."""
+    return _convert_rows(_rows(x, torch.uint8, "g711"), _check_law(law), "f32")
+
+
+def to_g711(y: torch.Tensor, law: str) -> torch.Tensor:
+    """y (B, n) or (n,) torch.float32 on the GPU -> torch.uint8 G.711 codes of `law` ("ulaw" | "alaw") of the same shape: the s16
+    rounding rule, then the companding rule of the module docstring.  What a caller puts behind the whole-clip decode()."""
+    return _convert_rows(_rows(y, torch.float32, "waveform"), "f32", _check_law(law))

@@ -191,7 +191,7 @@ int dmel_resample_window_items_f32(const float* x, int64_t x_row_stride, int64_t
                                    void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * The sample format of the wire: 16-bit signed PCM <-> fp32, B ragged convert-copies in ONE launch (a pool of live sessions whose
+ * The sample format of the wire: 16-bit signed PCM or 8-bit G.711 (mu-law, A-law) <-> fp32, B ragged convert-copies in ONE launch (a pool of live sessions whose
  * microphones, RTP streams and sound cards carry int16; no reference counterpart: the reference reads finished float clips).
  * src, src_fmt, dst, dst_fmt, n are HOST tables of B entries; src[b] / dst[b] are DEVICE pointers to n[b] samples of format
  * src_fmt[b] / dst_fmt[b].  Item b:
@@ -201,17 +201,36 @@ int dmel_resample_window_items_f32(const float* x, int64_t x_row_stride, int64_t
  *                1.5 / 32768 -> 2, 2.5 / 32768 -> 2.  NaN -> 0, +-inf saturate, no dither: the result is deterministic.
  *   f32 -> f32   the words copied untouched (a pool with mixed sessions still makes one launch).
  *   s16 -> s16   refused.
+ * G.711, the wire of telephony (8-bit mu-law or A-law; RTP payload types 0 and 8): the rule of ITU-T G.711 as Sun's g711.c and CPython's
+ * audioop restate it, on the s16 value x, >> an arithmetic shift, every comparison of it an equality of bits:
+ *   mu-law encode   v = x >> 2; neg = v < 0; m = min((neg ? -v : v) + 33, 8191); seg = floor(log2 m) - 5  (0 .. 7);
+ *                   code = ((seg << 4) | ((m >> (seg + 1)) & 15)) ^ (neg ? 0x7F : 0xFF)
+ *   mu-law decode   u = ~code & 0xFF; t = (((u & 15) << 3) + 0x84) << ((u & 0x70) >> 4); x = (u & 0x80) ? 0x84 - t : t - 0x84
+ *   A-law encode    v = x >> 3; neg = v < 0; m = neg ? -v - 1 : v; seg = max(floor(log2 max(m, 1)) - 4, 0);
+ *                   mant = seg < 2 ? (m >> 1) & 15 : (m >> seg) & 15; code = ((seg << 4) | mant) ^ (neg ? 0x55 : 0xD5)
+ *   A-law decode    a = code ^ 0x55; t = (a & 15) << 4; seg = (a & 0x70) >> 4; t = seg == 0 ? t + 8 : (t + 0x108) << (seg - 1);
+ *                   x = (a & 0x80) ? t : -t
+ *   law -> f32   y = decode(code) * 2^-15: exact.
+ *   f32 -> law   code = encode(the f32 -> s16 rule above, unchanged): NaN and 0.0 give 0xFF (mu-law) and 0xD5 (A-law).
+ *   law <-> s16 and law <-> law are refused: not conversions served here.
+ * encode(decode(c)) == c for all 256 A-law codes and for every mu-law code but 0x7F ("negative zero": decodes to 0, encodes as 0xFF).
+ * The segment is a count of leading zeros, so every lane runs the same instructions whatever its sample.
+ * Format codes 2 .. 7 and codes above 9 are not assigned and are refused.
  * n[b] == 0 is an idle item: its pointers are not looked at, nothing of it is read or written (and nothing is launched, DMEL_OK, when
  * every item is idle).  Checked before anything is launched -- a failure is DMEL_EINVAL, names the item, and leaves every destination
  * as it was: 1 <= B <= 65535, formats in range, n[b] >= 0, non-NULL pointers where n[b] > 0, an s16 pointer 2-byte and an f32
- * pointer 4-byte aligned.  NOT checked: that no destination overlaps a source or another destination (the caller's to guarantee).
+ * pointer 4-byte aligned (a law pointer needs no alignment).  NOT checked: that no destination overlaps a source or another
+ * destination (the caller's to guarantee).
  * Grid (ceil(max n / 2048), B); a workgroup behind its item's last sample leaves at once.  An item whose src AND dst are 16-byte
- * aligned moves whole groups of 8 samples with 16-byte loads and stores, any other item goes sample by sample: same arithmetic, same
- * bits.  table_scratch: device memory for 4 B int64, 8-byte aligned (the items as the kernel reads them).  The host tables are
+ * aligned moves whole groups of 8 samples with 16-byte loads and stores -- a law item whose f32 pointer is 16-byte and whose law pointer
+ * is 8-byte aligned, with one 8-byte access on the law side and two 16-byte ones on the f32 side -- any other item goes sample by
+ * sample: same arithmetic, same bits.  table_scratch: device memory for 4 B int64, 8-byte aligned (the items as the kernel reads them).  The host tables are
  * copied as launch arguments: the caller may overwrite them as soon as the call returns.
  * ---------------------------------------------------------------------------------------------- */
 #define DMEL_SAMPLE_F32 0
 #define DMEL_SAMPLE_S16 1
+#define DMEL_SAMPLE_ULAW 8 /* the 8-bit formats start at 8 */
+#define DMEL_SAMPLE_ALAW 9
 int dmel_pcm_convert_items(const void* const* src, const int32_t* src_fmt, void* const* dst, const int32_t* dst_fmt, const int64_t* n,
                            int B, void* table_scratch, void* stream);
 

@@ -27,7 +27,13 @@ runs only this: S replies whose wire carries 16-bit PCM, served (a) by a pool th
 launch per step into one packed int16 buffer) and (b) by the same pool with f32 sessions and the conversion every caller would do behind
 it, `(y * 32768).round().clamp(-32768, 32767).to(int16)` per reply.  With --output-sample-rate the replies also leave at those rates
 (both forms).  Same tokens and noise, interleaved in one process, equal audio checked, median and 10th / 90th percentile APPENDED to
---out."""
+--out.
+
+    python tools/bench_stream.py --sessions 16 --sample-format ulaw|alaw --output-sample-rate 8000 [--steps 40] [--out profiles/sessions_g711.txt]
+
+the same for replies whose wire carries G.711 (open(sample_format="ulaw" | "alaw"), torch.uint8 codes, telephony's 8 kHz): (b) is the
+same pool with f32 sessions and the companding every caller would do behind it in torch, the s16 rounding and then a clamp / exponent /
+shift / xor chain per reply."""
 import json, os, statistics, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -215,8 +221,26 @@ def sessions_rates_section(S, rates, steps, out):
     print(json.dumps(result))
 
 
-def sessions_pcm_section(S, rates, steps, out):
+def torch_g711(y, law):
+    """what a caller without G.711 sessions runs behind every reply: the s16 rounding, then the companding rule of utils/pcm.py in
+    torch integer ops (the segment from the float exponent, which is exact)"""
+    x = (y * 32768).round().clamp(-32768, 32767).to(torch.int32)
+    v = x >> (2 if law == "ulaw" else 3)
+    neg = v < 0
+    if law == "ulaw":
+        m = (torch.where(neg, -v, v) + 33).clamp(max=8191)
+        seg = torch.frexp(m.float())[1] - 6
+        code = ((seg << 4) | ((m >> (seg + 1)) & 15)) ^ torch.where(neg, 0x7F, 0xFF)
+    else:
+        m = torch.where(neg, -v - 1, v)
+        seg = (torch.frexp(m.clamp(min=1).float())[1] - 5).clamp(min=0)
+        code = ((seg << 4) | ((m >> seg.clamp(min=1)) & 15)) ^ torch.where(neg, 0x55, 0xD5)
+    return code.to(torch.uint8)
+
+
+def sessions_pcm_section(S, rates, steps, out, fmt="s16"):
     chunk, warmup = 64, 6
+    wire, wire_dtype = f"{fmt}_sessions", torch.int16 if fmt == "s16" else torch.uint8
     pct = lambda v, q: sorted(v)[min(len(v) - 1, int(q * len(v)))]
     gl = torch.Generator().manual_seed(9)
     G, Cn = codec.dmel_groups, codec.decoder.input_channels
@@ -224,9 +248,9 @@ def sessions_pcm_section(S, rates, steps, out):
     ids = torch.randint(0, 175, (S, G, total), generator=gl, dtype=torch.int32).to(dev)
     noise = torch.randn(S, Cn, total * 4, device=dev)
     rate = [rates[i % len(rates)] if rates else None for i in range(S)]
-    pools = {"s16_sessions": codec.decode_sessions(S, max_push_tokens=chunk, output_sample_rates=rates),
+    pools = {wire: codec.decode_sessions(S, max_push_tokens=chunk, output_sample_rates=rates),
              "torch_behind": codec.decode_sessions(S, max_push_tokens=chunk, output_sample_rates=rates)}
-    slots = {"s16_sessions": [pools["s16_sessions"].open(output_sample_rate=rate[i], sample_format="s16") for i in range(S)],
+    slots = {wire: [pools[wire].open(output_sample_rate=rate[i], sample_format=fmt) for i in range(S)],
              "torch_behind": [pools["torch_behind"].open(output_sample_rate=rate[i]) for i in range(S)]}
     pos = [0] * S
     ms = {k: [] for k in pools}
@@ -235,8 +259,10 @@ def sessions_pcm_section(S, rates, steps, out):
         sl = slots[k]
         out = pools[k].push({sl[i]: ids[i, :, pos[i]:pos[i] + n[i]] for i in range(S)},
                             noise={sl[i]: noise[i, :, 4 * pos[i]:4 * (pos[i] + n[i])] for i in range(S)})
-        if k == "s16_sessions":
+        if k == wire:
             return [out[sl[i]][0] for i in range(S)]
+        if fmt != "s16":
+            return [torch_g711(out[sl[i]][0], fmt) for i in range(S)]
         return [(out[sl[i]][0] * 32768).round().clamp(-32768, 32767).to(torch.int16) for i in range(S)]
 
     for step in range(steps):
@@ -251,24 +277,26 @@ def sessions_pcm_section(S, rates, steps, out):
             if step >= warmup:
                 ms[k].append((time.perf_counter() - t0) * 1e3)
         for i in range(S):
-            assert got["s16_sessions"][i].dtype == torch.int16 and torch.equal(got["s16_sessions"][i], got["torch_behind"][i]), \
+            assert got[wire][i].dtype == wire_dtype and torch.equal(got[wire][i], got["torch_behind"][i]), \
                 f"step {step}, session {i}: the pool's audio differs"
             pos[i] += n[i]
-    rows, result = [], {"sessions": S, "sample_format": "s16", "output_sample_rates": rates, "chunk_tokens": chunk, "audio_equal": True}
+    rows, result = [], {"sessions": S, "sample_format": fmt, "output_sample_rates": rates, "chunk_tokens": chunk, "audio_equal": True}
     for k, v in ms.items():
         med = statistics.median(v)
         result[k] = {"median_ms": round(med, 3), "p10_ms": round(pct(v, 0.1), 3), "p90_ms": round(pct(v, 0.9), 3), "n": len(v)}
-        rows.append(f"{S:8d}  {k:12s}  {med:9.3f}  {pct(v, 0.1):9.3f}  {pct(v, 0.9):9.3f}  {len(v):4d}")
-    result["torch_over_s16"] = round(result["torch_behind"]["median_ms"] / result["s16_sessions"]["median_ms"], 3)
+        rows.append(f"{S:8d}  {k:13s}  {med:9.3f}  {pct(v, 0.1):9.3f}  {pct(v, 0.9):9.3f}  {len(v):4d}")
+    result[f"torch_over_{fmt}"] = round(result["torch_behind"]["median_ms"] / result[wire]["median_ms"], 3)
     rl = ",".join(map(str, rates)) if rates else "the vocoder's rate"
-    table = [f"{S} decode sessions returning 16-bit PCM at {rl}, {chunk}-token pushes, starts a third of a push apart, 100 mel / 10 groups, BigVGAN base "
-             f"(tools/bench_stream.py --sessions {S} --sample-format s16" + (f" --output-sample-rate {rl})" if rates else ")"),
+    name = {"s16": "16-bit PCM", "ulaw": "G.711 mu-law", "alaw": "G.711 A-law"}[fmt]
+    table = [f"{S} decode sessions returning {name} at {rl}, {chunk}-token pushes, starts a third of a push apart, 100 mel / 10 groups, BigVGAN base "
+             f"(tools/bench_stream.py --sessions {S} --sample-format {fmt}" + (f" --output-sample-rate {rl})" if rates else ")"),
              f"wall time of one step of all sessions incl. host synchronisation, {steps - warmup} steady-state steps, the two interleaved in one process, "
              "equal audio checked;",
-             "s16_sessions = open(sample_format=\"s16\"): one convert launch per step; torch_behind = f32 sessions, "
-             "(y * 32768).round().clamp().to(int16) per reply",
-             "sessions  form          median ms     p10 ms     p90 ms     n"] + rows + [
-                 f"torch behind / s16 sessions: {result['torch_over_s16']:.3f} at the median"]
+             f"{wire} = open(sample_format=\"{fmt}\"): one convert launch per step; torch_behind = f32 sessions, " +
+             ("(y * 32768).round().clamp().to(int16) per reply" if fmt == "s16" else
+              "the s16 rounding and a clamp / exponent / shift / xor chain in torch per reply"),
+             "sessions  form           median ms     p10 ms     p90 ms     n"] + rows + [
+                 f"torch behind / {fmt} sessions: {result[f'torch_over_{fmt}']:.3f} at the median"]
     os.makedirs(os.path.dirname(out), exist_ok=True)
     with open(out, "a") as f:
         f.write("\n".join(table) + "\n\n")
@@ -276,11 +304,14 @@ def sessions_pcm_section(S, rates, steps, out):
     print(json.dumps(result))
 
 
-if "--sessions" in sys.argv and arg_after("--sample-format", "f32") == "s16":
+if "--sessions" in sys.argv and arg_after("--sample-format", "f32") != "f32":
+    wire_format = arg_after("--sample-format")
+    assert wire_format in ("s16", "ulaw", "alaw"), f"--sample-format {wire_format}: expected f32, s16, ulaw or alaw"
     sessions_pcm_section(int(arg_after("--sessions")), [int(r) for r in arg_after("--output-sample-rate", "").split(",") if r],
                          int(arg_after("--steps", "40")),
                          arg_after("--out", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                                         "sessions_pcm.txt")))
+                                                         "sessions_pcm.txt" if wire_format == "s16" else "sessions_g711.txt")),
+                         wire_format)
     sys.exit(0)
 
 if "--sessions" in sys.argv and "--output-sample-rate" in sys.argv:

@@ -34,7 +34,12 @@ per caller.  Interleaved in one process, equal ids checked, median and 10th / 90
 times a steady-state step of S sessions whose wire carries 16-bit PCM in a pool that was told so (open(sample_format="s16"): ONE convert
 launch per step, written where the per-slot copies write) against the same pool with f32 sessions and the conversion every caller
 would do in front, `.to(float32) / 32768` per slot.  With --sample-rate the sessions also arrive at those rates (both forms).
-Interleaved in one process, equal ids checked, median and 10th / 90th percentile.  APPENDS its table to --out."""
+Interleaved in one process, equal ids checked, median and 10th / 90th percentile.  APPENDS its table to --out.
+
+    python tools/bench_stream_encode.py --sessions 16 --sample-format ulaw|alaw --sample-rate 8000 [--out profiles/sessions_g711.txt]
+
+the same for sessions whose wire carries G.711 (open(sample_format="ulaw" | "alaw"), torch.uint8 codes, telephony's 8 kHz): the
+baseline is the same pool with f32 sessions and the expansion every caller would do in front, a 256-entry table gather per slot."""
 import argparse, json, os, statistics, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -48,7 +53,8 @@ ap.add_argument("--batches", default="1,16")
 ap.add_argument("--sample-rate", default=None,
                 help="compare pushes at this source rate with pushes at the codec's rate; with --sessions: the sessions' rates, SR[,SR...]")
 ap.add_argument("--sessions", type=int, default=0, help="time a step of this many staggered independent sessions")
-ap.add_argument("--sample-format", default="f32", choices=("f32", "s16"), help="with --sessions: s16 sessions against torch conversions in front")
+ap.add_argument("--sample-format", default="f32", choices=("f32", "s16", "ulaw", "alaw"),
+                help="with --sessions: s16 / G.711 sessions against torch conversions in front")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 rates = [int(r) for r in args.sample_rate.split(",")] if args.sample_rate else []
@@ -56,6 +62,7 @@ args.sample_rate = rates[0] if rates else None
 if args.out is None:
     args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                             "sessions_pcm.txt" if args.sessions and args.sample_format == "s16" else
+                            "sessions_g711.txt" if args.sessions and args.sample_format != "f32" else
                             "sessions_resample.txt" if args.sessions and rates else "stream_sessions.txt" if args.sessions else "stream_resample.txt" if args.sample_rate else "stream_encode.txt")
 assert args.pushes - args.warmup >= 50, "medians over at least 50 steady-state pushes"
 SR = 24000
@@ -240,15 +247,25 @@ def sessions_resample_section():
 
 
 def sessions_pcm_section():
-    """S staggered s16 sessions (at their own rates, if any were given): one pool that converts all slots in one launch against the
-    same pool with f32 sessions behind one torch conversion per slot; the same PCM, the same pushes, equal ids"""
-    S = args.sessions
+    """S staggered s16 or G.711 sessions (at their own rates, if any were given): one pool that converts all slots in one launch
+    against the same pool with f32 sessions behind one torch conversion per slot (s16: a cast and a scale; G.711: a 256-entry table
+    gather); the same samples, the same pushes, equal ids"""
+    from dmel_codec_amd.utils import pcm
+    S, fmt = args.sessions, args.sample_format
+    wire = f"{fmt}_sessions"
     rate = [rates[s % len(rates)] if rates else SR for s in range(S)]
     n = [args.chunk * r // SR for r in rate]                     # 0.32 s of every slot's own rate
-    audio = [(torch.randn((args.pushes + 1) * n[s], device=dev) * 0.1 * 32768).round().clamp(-32768, 32767).to(torch.int16) for s in range(S)]
-    pools = {"s16_sessions": codec.encode_sessions(slots=S, max_push_samples=max(n), sample_rates=rates),
+    noise = [torch.randn((args.pushes + 1) * n[s], device=dev) * 0.1 for s in range(S)]
+    if fmt == "s16":
+        audio = [(x * 32768).round().clamp(-32768, 32767).to(torch.int16) for x in noise]
+        in_front = lambda c: c.to(torch.float32) / 32768
+    else:
+        audio = [pcm.to_g711(x, fmt) for x in noise]
+        lut = pcm.from_g711(torch.arange(256, device=dev).to(torch.uint8), fmt)         # what a caller keeps: code -> float
+        in_front = lambda c: lut[c.long()]
+    pools = {wire: codec.encode_sessions(slots=S, max_push_samples=max(n), sample_rates=rates),
              "torch_in_front": codec.encode_sessions(slots=S, max_push_samples=max(n), sample_rates=rates)}
-    slots = {"s16_sessions": [pools["s16_sessions"].open(sample_rate=rate[s], sample_format="s16") for s in range(S)],
+    slots = {wire: [pools[wire].open(sample_rate=rate[s], sample_format=fmt) for s in range(S)],
              "torch_in_front": [pools["torch_in_front"].open(sample_rate=rate[s]) for s in range(S)]}
     pos = [0] * S
     first = [n[s] * (1 + s % 3) // 3 for s in range(S)]          # the starts differ by a third of a push
@@ -263,31 +280,33 @@ def sessions_pcm_section():
         for k in (keys if i % 2 == 0 else keys[::-1]):           # neither always goes first
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            if k == "s16_sessions":
+            if k == wire:
                 ids = pools[k].push({slots[k][s]: chunks[s] for s in range(S)})
             else:
-                ids = pools[k].push({slots[k][s]: chunks[s].to(torch.float32) / 32768 for s in range(S)})
+                ids = pools[k].push({slots[k][s]: in_front(chunks[s]) for s in range(S)})
             got[k] = [ids[slots[k][s]] for s in range(S)]
             torch.cuda.synchronize()
             if i >= args.warmup:
                 ms[k].append((time.perf_counter() - t0) * 1e3)
         same = same and all(torch.equal(a, b) for a, b in zip(*got.values()))
-        tokens += sum(a.shape[1] for a in got["s16_sessions"])
-    r = {"sessions": S, "sample_format": "s16", "sample_rates": rates or [SR], "chunk_s": args.chunk / SR, "pushes": args.pushes,
+        tokens += sum(a.shape[1] for a in got[wire])
+    r = {"sessions": S, "sample_format": fmt, "sample_rates": rates or [SR], "chunk_s": args.chunk / SR, "pushes": args.pushes,
          "warmup": args.warmup, "ids_equal": bool(same), "tokens": tokens}
     rows = []
     for k, v in ms.items():
         med = statistics.median(v)
         r[k] = {"median_ms": round(med, 3), "p10_ms": round(pct(v, 0.1), 3), "p90_ms": round(pct(v, 0.9), 3), "n": len(v)}
         rows.append(f"{S:8d}  {k:14s}  {med:9.3f}  {pct(v, 0.1):9.3f}  {pct(v, 0.9):9.3f}  {len(v):4d}")
-    r["torch_over_s16"] = round(r["torch_in_front"]["median_ms"] / r["s16_sessions"]["median_ms"], 3)
-    rows.append(f"{S:8d}  median step with {S} torch conversions in front / with s16 sessions: {r['torch_over_s16']:.3f}; ids equal: {same}")
+    r[f"torch_over_{fmt}"] = round(r["torch_in_front"]["median_ms"] / r[wire]["median_ms"], 3)
+    rows.append(f"{S:8d}  median step with {S} torch conversions in front / with {fmt} sessions: {r[f'torch_over_{fmt}']:.3f}; ids equal: {same}")
     what = ",".join(map(str, rates)) if rates else "the codec's rate"
-    table = [f"encode sessions fed 16-bit PCM at {what}, 0.32 s pushes, starts staggered by a third of a push, 80 mel / 8 groups / 70 channels / "
-             f"20 layers (tools/bench_stream_encode.py --sessions {S} --sample-format s16" + (f" --sample-rate {what})" if rates else ")"),
+    name = {"s16": "16-bit PCM", "ulaw": "G.711 mu-law", "alaw": "G.711 A-law"}[fmt]
+    table = [f"encode sessions fed {name} at {what}, 0.32 s pushes, starts staggered by a third of a push, 80 mel / 8 groups / 70 channels / "
+             f"20 layers (tools/bench_stream_encode.py --sessions {S} --sample-format {fmt}" + (f" --sample-rate {what})" if rates else ")"),
              f"wall time of one step (one push for every stream) incl. host synchronisation, {args.pushes - args.warmup} steady-state steps, the two "
              "forms interleaved in one process;",
-             "s16_sessions = open(sample_format=\"s16\"): one convert launch per step; torch_in_front = f32 sessions, .to(float32) / 32768 per slot",
+             f"{wire} = open(sample_format=\"{fmt}\"): one convert launch per step; torch_in_front = f32 sessions, " +
+             (".to(float32) / 32768 per slot" if fmt == "s16" else "a 256-entry table gather per slot"),
              "sessions  form            median ms     p10 ms     p90 ms     n"] + rows
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "a") as f:
@@ -296,7 +315,7 @@ def sessions_pcm_section():
     print(json.dumps(r))
 
 
-if args.sessions and args.sample_format == "s16":
+if args.sessions and args.sample_format != "f32":
     sessions_pcm_section()
     sys.exit(0)
 if args.sessions and rates:
