@@ -56,6 +56,7 @@ PROTOTYPES = {
     "dmel_resample_window_items_f32": (C.c_int, [vp, C.c_int64, C.c_int64, i64p, i64p, vp, C.c_int64, i64p, vp, C.c_int64, i64p, C.c_int, i64p,
                                                  C.c_int, i64p, i64p, i64p, vp, vp]),
     "dmel_pcm_convert_items": (C.c_int, [C.POINTER(vp), i32p, C.POINTER(vp), i32p, i64p, C.c_int, vp, vp]),
+    "dmel_pcm_convert_items_ch": (C.c_int, [C.POINTER(vp), i32p, i32p, i32p, C.POINTER(vp), i32p, i32p, i64p, C.c_int, vp, vp]),
     "dmel_stft_f32": (C.c_int, [vp, vp, C.c_int64, vp, vp, vp, C.c_int, C.c_int64, vp]),
     "dmel_stft_window_f32": (C.c_int, [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, vp]),
     "dmel_stft_window_items_f32": (C.c_int, [vp, vp, C.c_int64, C.c_int64, i64p, i64p, vp, vp, vp, C.c_int, i64p, i64p, i64p, vp, vp]),

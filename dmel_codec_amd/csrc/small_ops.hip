@@ -872,17 +872,159 @@ __device__ __forceinline__ void g711_convert_tile(const void* src, void* dst, in
     else df[e] = g711_to_f32<ALAW>(s8[e]);
   }
 }
+// ---- interleaved channels (include/dmel_hip.h has the rule): c -> 1 by the mean or by picking one channel, 1 -> c by storing the
+// converted sample c times.  F is a DMEL_SAMPLE_* code.  Sample j of a thread's dwords w (as many as 16 samples of F fill), as f32 by the
+// format's rule above -- an f32 sample is its word, no arithmetic -- and the other way round: the bits of an f32 value in format F.
+template <int F>
+__device__ __forceinline__ float pcm_word_sample(const uint32_t* w, int j) {
+  if constexpr (F == DMEL_SAMPLE_S16) return pcm_s16_to_f32((int16_t)((w[j >> 1] >> (16 * (j & 1))) & 0xffffu));
+  else if constexpr (F == DMEL_SAMPLE_ULAW) return g711_to_f32<false>((w[j >> 2] >> (8 * (j & 3))) & 0xFFu);
+  else if constexpr (F == DMEL_SAMPLE_ALAW) return g711_to_f32<true>((w[j >> 2] >> (8 * (j & 3))) & 0xFFu);
+  else return __uint_as_float(w[j]);
+}
+template <int F>
+__device__ __forceinline__ float pcm_sample_at(const void* p, int64_t i) {
+  if constexpr (F == DMEL_SAMPLE_S16) return pcm_s16_to_f32(static_cast<const int16_t*>(p)[i]);
+  else if constexpr (F == DMEL_SAMPLE_ULAW) return g711_to_f32<false>(static_cast<const uint8_t*>(p)[i]);
+  else if constexpr (F == DMEL_SAMPLE_ALAW) return g711_to_f32<true>(static_cast<const uint8_t*>(p)[i]);
+  else return __uint_as_float(static_cast<const uint32_t*>(p)[i]);
+}
+template <int F>
+__device__ __forceinline__ uint32_t pcm_sample_bits(float v) {
+  if constexpr (F == DMEL_SAMPLE_S16) return (uint32_t)(uint16_t)pcm_f32_to_s16(v);
+  else if constexpr (F == DMEL_SAMPLE_ULAW) return g711_from_f32<false>(v);
+  else if constexpr (F == DMEL_SAMPLE_ALAW) return g711_from_f32<true>(v);
+  else return __float_as_uint(v);
+}
+template <int F>
+__device__ __forceinline__ void pcm_put_sample(void* p, int64_t i, uint32_t bits) {
+  if constexpr (F == DMEL_SAMPLE_S16) static_cast<uint16_t*>(p)[i] = (uint16_t)bits;
+  else if constexpr (F == DMEL_SAMPLE_ULAW || F == DMEL_SAMPLE_ALAW) static_cast<uint8_t*>(p)[i] = (uint8_t)bits;
+  else static_cast<uint32_t*>(p)[i] = bits;
+}
+template <int F> constexpr int kPcmBytes = F == DMEL_SAMPLE_F32 ? 4 : F == DMEL_SAMPLE_S16 ? 2 : 1;
+// c channels of format F -> mono f32; n and base count FRAMES.  pick < 0: acc = x_0; acc += x_1; ...; y = acc / (float)c -- the IEEE
+// division, in channel order; pick = k: y = x_k.  c, pick and `wide` are workgroup-uniform.  `wide`: c == 2 and both pointers 16-byte
+// aligned; then a thread whose 8 consecutive frames all lie in the item loads their 16 samples with 16-byte loads (4 for f32, 2 for s16,
+// 1 for a law) and stores 2 x 16 bytes.  x / 2.0f is a correctly rounded division whatever the compiler makes of it, so a frame has the
+// same bits on either path.  Everything else goes frame by frame, one frame per lane.
+template <int F>
+__device__ __forceinline__ void pcm_downmix_tile(const void* src, void* dst, int64_t n, int64_t base, int c, int pick, bool wide) {
+  float* df = static_cast<float*>(dst);
+  int64_t from = base;
+  if (wide) {
+    const int64_t whole = base + (min(n - base, (int64_t)kPcmTile) & ~(int64_t)(kPcmPerThread - 1));
+    const int64_t e = base + (int64_t)threadIdx.x * kPcmPerThread;
+    if (e < whole) {
+      constexpr int kQuads = kPcmBytes<F>;                       // 16 samples of F are kPcmBytes<F> x 16 bytes
+      const uint4* p = reinterpret_cast<const uint4*>(static_cast<const uint8_t*>(src) + 2 * e * kPcmBytes<F>);
+      uint32_t w[4 * kQuads];
+#pragma unroll
+      for (int q = 0; q < kQuads; ++q) {
+        const uint4 a = p[q];
+        w[4 * q] = a.x; w[4 * q + 1] = a.y; w[4 * q + 2] = a.z; w[4 * q + 3] = a.w;
+      }
+      float f[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float l = pcm_word_sample<F>(w, 2 * j), r = pcm_word_sample<F>(w, 2 * j + 1);
+        if (pick < 0) {
+          float acc = l;
+          acc += r;
+          f[j] = acc / 2.0f;
+        } else {
+          f[j] = pick ? r : l;
+        }
+      }
+      float4* o = reinterpret_cast<float4*>(df + e);
+      o[0] = make_float4(f[0], f[1], f[2], f[3]);
+      o[1] = make_float4(f[4], f[5], f[6], f[7]);
+    }
+    from = whole;
+  }
+  const int64_t end = min(n, base + kPcmTile);
+  for (int64_t e = from + threadIdx.x; e < end; e += 256) {
+    float y;
+    if (pick >= 0) {
+      y = pcm_sample_at<F>(src, e * c + pick);
+    } else {
+      float acc = pcm_sample_at<F>(src, e * c);
+      for (int j = 1; j < c; ++j) acc += pcm_sample_at<F>(src, e * c + j);
+      y = acc / (float)c;
+    }
+    df[e] = y;
+  }
+}
+// mono f32 -> c channels of format F: the sample is converted ONCE and its bits are stored c times.  `wide`: c == 2 and both pointers
+// 16-byte aligned; a thread's 8 frames are then 2 x 16 bytes loaded and 16 samples stored with 16-byte stores (4, 2 or 1 of them).
+template <int F>
+__device__ __forceinline__ void pcm_fanout_tile(const void* src, void* dst, int64_t n, int64_t base, int c, bool wide) {
+  const float* sf = static_cast<const float*>(src);
+  int64_t from = base;
+  if (wide) {
+    const int64_t whole = base + (min(n - base, (int64_t)kPcmTile) & ~(int64_t)(kPcmPerThread - 1));
+    const int64_t e = base + (int64_t)threadIdx.x * kPcmPerThread;
+    if (e < whole) {
+      const float4* p = reinterpret_cast<const float4*>(sf + e);
+      const float4 a = p[0], b = p[1];
+      const float f[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+      constexpr int kQuads = kPcmBytes<F>;
+      uint32_t w[4 * kQuads];
+#pragma unroll
+      for (int j = 0; j < 4 * kQuads; ++j) w[j] = 0u;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const uint32_t v = pcm_sample_bits<F>(f[j]);
+        if constexpr (F == DMEL_SAMPLE_F32) w[2 * j] = w[2 * j + 1] = v;
+        else if constexpr (F == DMEL_SAMPLE_S16) w[j] = v | (v << 16);
+        else w[j >> 1] |= (v | (v << 8)) << (16 * (j & 1));
+      }
+      uint4* o = reinterpret_cast<uint4*>(static_cast<uint8_t*>(dst) + 2 * e * kPcmBytes<F>);
+#pragma unroll
+      for (int q = 0; q < kQuads; ++q) o[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+    }
+    from = whole;
+  }
+  const int64_t end = min(n, base + kPcmTile);
+  for (int64_t e = from + threadIdx.x; e < end; e += 256) {
+    const uint32_t v = pcm_sample_bits<F>(sf[e]);
+    for (int j = 0; j < c; ++j) pcm_put_sample<F>(dst, e * c + j, v);
+  }
+}
 __device__ __forceinline__ bool pcm_is_law(int64_t f) { return f == DMEL_SAMPLE_ULAW || f == DMEL_SAMPLE_ALAW; }
+// The item's fourth word: src_fmt | dst_fmt << 8 | (src_ch - 1) << 16 | (dst_ch - 1) << 20 | (pick + 1) << 24.  A mono item has nothing
+// above bit 15 -- the word it always had -- and takes the code below the channel block unchanged.
 __global__ __launch_bounds__(256) void pcm_convert_kernel(const int64_t* __restrict__ items) {
   const int64_t* it = items + kPcmItemWords * (int64_t)blockIdx.y;
   const int64_t n = uniform_i64(it + 2);
   const int64_t base = (int64_t)blockIdx.x * kPcmTile;
   if (base >= n) return;                                       // workgroup-uniform: every workgroup of an idle item leaves here
   const uint64_t sa = (uint64_t)uniform_i64(it), da = (uint64_t)uniform_i64(it + 1);
-  const int64_t fmt = uniform_i64(it + 3);
+  const int64_t word = uniform_i64(it + 3);
+  const int64_t fmt = word & 0xffff;
   const void* src = reinterpret_cast<const void*>(sa);
   void* dst = reinterpret_cast<void*>(da);
-  if (pcm_is_law(fmt & 0xff)) {                                // law -> f32 (the entry admits no other destination)
+  if (word >> 16) {                                            // channels (the entry admits c -> 1 and 1 -> c only, one side f32)
+    const int sc = (int)((word >> 16) & 7) + 1, dc = (int)((word >> 20) & 7) + 1, pick = (int)((word >> 24) & 15) - 1;
+    const bool wide2 = ((sa | da) & 15) == 0 && (sc == 2 || dc == 2);
+    if (sc > 1) {
+      switch ((int)(fmt & 0xff)) {
+        case DMEL_SAMPLE_S16: pcm_downmix_tile<DMEL_SAMPLE_S16>(src, dst, n, base, sc, pick, wide2); break;
+        case DMEL_SAMPLE_ULAW: pcm_downmix_tile<DMEL_SAMPLE_ULAW>(src, dst, n, base, sc, pick, wide2); break;
+        case DMEL_SAMPLE_ALAW: pcm_downmix_tile<DMEL_SAMPLE_ALAW>(src, dst, n, base, sc, pick, wide2); break;
+        default: pcm_downmix_tile<DMEL_SAMPLE_F32>(src, dst, n, base, sc, pick, wide2); break;
+      }
+    } else {
+      switch ((int)(fmt >> 8)) {
+        case DMEL_SAMPLE_S16: pcm_fanout_tile<DMEL_SAMPLE_S16>(src, dst, n, base, dc, wide2); break;
+        case DMEL_SAMPLE_ULAW: pcm_fanout_tile<DMEL_SAMPLE_ULAW>(src, dst, n, base, dc, wide2); break;
+        case DMEL_SAMPLE_ALAW: pcm_fanout_tile<DMEL_SAMPLE_ALAW>(src, dst, n, base, dc, wide2); break;
+        default: pcm_fanout_tile<DMEL_SAMPLE_F32>(src, dst, n, base, dc, wide2); break;
+      }
+    }
+    return;
+  }
+  if (pcm_is_law(fmt & 0xff)) {                              // law -> f32 (the entry admits no other destination)
     const bool wide8 = (sa & 7) == 0 && (da & 15) == 0;
     if ((fmt & 0xff) == DMEL_SAMPLE_ULAW) g711_convert_tile<false, false>(src, dst, n, base, wide8);
     else g711_convert_tile<true, false>(src, dst, n, base, wide8);
@@ -1034,6 +1176,12 @@ static int pcm_sample_bytes(int fmt) {
 }
 extern "C" int dmel_pcm_convert_items(const void* const* src, const int32_t* src_fmt, void* const* dst, const int32_t* dst_fmt,
                                       const int64_t* n, int B, void* table_scratch, void* stream) {
+  return dmel_pcm_convert_items_ch(src, src_fmt, nullptr, nullptr, dst, dst_fmt, nullptr, n, B, table_scratch, stream);
+}
+// the same with interleaved channels: n counts frames; src_ch / dst_ch / src_pick may be NULL (all 1, all 1, all -1)
+extern "C" int dmel_pcm_convert_items_ch(const void* const* src, const int32_t* src_fmt, const int32_t* src_ch, const int32_t* src_pick,
+                                         void* const* dst, const int32_t* dst_fmt, const int32_t* dst_ch, const int64_t* n, int B,
+                                         void* table_scratch, void* stream) {
   using namespace dmel;
   DMEL_CHECK_ARG(src && src_fmt && dst && dst_fmt && n && table_scratch, "pcm_convert_items: NULL argument");
   DMEL_CHECK_ARG(B >= 1 && B <= 65535, "pcm_convert_items: %d items, expected 1 .. 65535", B);
@@ -1050,7 +1198,16 @@ extern "C" int dmel_pcm_convert_items(const void* const* src, const int32_t* src
     DMEL_CHECK_ARG(sf == DMEL_SAMPLE_F32 || df == DMEL_SAMPLE_F32,
                    "pcm_convert_items: item %d: %d -> %d is not a conversion served here: mu-law and A-law convert from and to f32 only", b, sf,
                    df);
-    DMEL_CHECK_ARG(n[b] >= 0 && n[b] < ((int64_t)1 << 40), "pcm_convert_items: item %d: sample count %lld out of range", b, (long long)n[b]);
+    const int sc = src_ch ? src_ch[b] : 1, dc = dst_ch ? dst_ch[b] : 1, pick = src_pick ? src_pick[b] : -1;
+    DMEL_CHECK_ARG(sc >= 1 && sc <= DMEL_MAX_CHANNELS && dc >= 1 && dc <= DMEL_MAX_CHANNELS,
+                   "pcm_convert_items: item %d: channel counts %d -> %d, expected 1 .. %d", b, sc, dc, DMEL_MAX_CHANNELS);
+    DMEL_CHECK_ARG(sc == 1 || dc == 1, "pcm_convert_items: item %d: %d -> %d channels is not served: one side is mono", b, sc, dc);
+    DMEL_CHECK_ARG(pick == -1 || (sc > 1 && pick >= 0 && pick < sc),
+                   "pcm_convert_items: item %d: pick %d with %d source channels, expected -1 (the mean)%s", b, pick, sc,
+                   sc > 1 ? " or a channel of the source" : "");
+    const int ch = std::max(sc, dc);
+    DMEL_CHECK_ARG(n[b] >= 0 && n[b] < ((int64_t)1 << 40) && n[b] * ch < ((int64_t)1 << 40),
+                   "pcm_convert_items: item %d: sample count %lld out of range", b, (long long)n[b]);
     if (n[b] == 0) continue;
     DMEL_CHECK_ARG(src[b] && dst[b], "pcm_convert_items: item %d: NULL pointer with %lld samples", b, (long long)n[b]);
     const uintptr_t sa = (uintptr_t)src[b], da = (uintptr_t)dst[b];
@@ -1058,9 +1215,10 @@ extern "C" int dmel_pcm_convert_items(const void* const* src, const int32_t* src
     DMEL_CHECK_ARG(sa % ss == 0 && da % ds == 0, "pcm_convert_items: item %d: a pointer is not aligned to its sample size (%d -> %d bytes)", b,
                    ss, ds);
     int64_t* it = tab.data() + (size_t)kPcmItemWords * b;
-    it[0] = (int64_t)sa; it[1] = (int64_t)da; it[2] = n[b]; it[3] = sf | (df << 8);
+    it[0] = (int64_t)sa; it[1] = (int64_t)da; it[2] = n[b];
+    it[3] = sf | (df << 8) | ((sc - 1) << 16) | ((dc - 1) << 20) | ((pick + 1) << 24);   // a mono item: the word it always had
     max_n = std::max(max_n, n[b]);
-    bytes += (double)n[b] * (ss + ds);
+    bytes += (double)n[b] * (ss * sc + ds * dc);
   }
   if (max_n == 0) return DMEL_OK;                     // every item idle
   hipStream_t s = (hipStream_t)stream;

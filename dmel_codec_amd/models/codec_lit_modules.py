@@ -407,8 +407,9 @@ class VQGAN(nn.Module):
         16 kHz, ...); pool.open(sample_rate=r) then starts a session whose pushes are in samples of rate r and whose ids are the bits of
         encode(clip, len, sample_rate=r), all slots of a step converted by one resample launch.  sample_rate names the codec's own rate
         only (a pool has no rate of its own).  pool.open(sample_format="s16") starts a session fed torch.int16 (16-bit PCM), converted with
-        all other slots of the step in one launch; a format sizes nothing, so there is no argument for it here.  See
-        models/stream_sessions.py: EncodeSessions."""
+        all other slots of the step in one launch; a format sizes nothing, so there is no argument for it here.  Neither does a channel
+        count: pool.open(channels=2) starts a session fed interleaved stereo frames (n, 2), downmixed (the mean, or channel=k) inside
+        that same launch.  See models/stream_sessions.py: EncodeSessions."""
         from .stream_sessions import EncodeSessions
         return EncodeSessions(self, slots, max_push_samples, sample_rate, sample_rates)
 
@@ -472,7 +473,8 @@ class VQGAN(nn.Module):
         pool.open(output_sample_rate=r) then starts a reply whose audio is the bits of resample(decode() audio, vocoder rate, r), all
         slots of a step converted by one resample launch.  overlap_vocoder, graph_chunk_tokens and the pool-wide output_sample_rate are
         NotImplementedError here.  pool.open(sample_format="s16") starts a reply whose audio comes back as torch.int16 (16-bit PCM), all
-        such slots of a step converted by one launch; see models/stream_sessions.py: DecodeSessions."""
+        such slots of a step converted by one launch; pool.open(channels=2) starts a reply whose audio comes back as interleaved stereo
+        frames (n, 2), fanned out inside that same launch.  See models/stream_sessions.py: DecodeSessions."""
         from .stream_sessions import DecodeSessions
         return DecodeSessions(self, slots, max_push_tokens, return_audios, **options)
 

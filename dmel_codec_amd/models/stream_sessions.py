@@ -29,7 +29,8 @@ _WIRE_DTYPES = {dt for name, (_, dt) in pcm.FORMATS.items() if name != "f32"}   
 class EncodeSessions:
     """`slots` independent incremental encodes, each with the ids of encode() on its own finished clip.
 
-        slot = pool.open()                                   # a free slot, fresh state; open(sample_rate=48000): a session at that rate
+        slot = pool.open()                                   # a free slot, fresh state; open(sample_rate=48000): a session at that rate;
+                                                             # open(sample_format="s16", channels=2): stereo 16-bit frames (n, 2)
         ids = pool.push({slot: audio_1d, ...}, final=())     # one step for any subset of the open slots -> {slot: ids (G, m) int32}
         ids = pool.close(slot)                               # = push({slot: empty}, final=(slot,))[slot]
 
@@ -63,6 +64,18 @@ class EncodeSessions:
     from_g711(clip, law) -- of encode(from_g711(clip, law), len, sample_rate=r); the one convert launch of the step decodes them
     (the companding rule of utils/pcm.py).  Out of scope: the lockstep StreamingEncoder and whole-clip encode() (callers have
     utils.pcm.from_pcm16 / from_g711), other formats (s24, s32, u8), dither.
+
+    The channel count belongs to a session too and sizes nothing (the codec is mono): open(channels=c), 1 < c <= 8, starts a session
+    whose pushes are contiguous INTERLEAVED frames (n, c) in the dtype of its format, n <= max_push_samples frames at its own rate.
+    Its ids are the bits of the same session opened mono "f32" and fed the downmix of the channel rule of utils/pcm.py -- of
+    encode(pcm.downmix(clip, format), len[, sample_rate=r]): every channel to f32 by its format's rule, the fp32 sum in channel order,
+    one IEEE division by c (numpy.mean over the channel-first array, what librosa's to_mono computes).  open(channels=c, channel=k)
+    encodes channel k alone: two sessions pushed the same stereo tensor with channel=0 and channel=1 are the two parties of a call
+    recording.  A step that names at least one slot with a non-f32 format OR more than one channel takes the path above: ONE convert
+    launch for all named slots with samples (dmel_pcm_convert_items_ch), the downmix inside it.  A step of mono f32 slots keeps the
+    float path with no convert launch.  A 1-D or (1, n) push to a slot with channels, or an (n, c) push to a mono slot, is a
+    ValueError.  Not served: weights, channel maps, more than 8 channels, planar (channel-first) pushes, the lockstep
+    StreamingEncoder and whole-clip encode() (callers have utils.pcm.downmix).
 
     Only encoders the one-launch streaming kernel takes (residual channels in (32, 80], no condition, no output projection,
     dilations <= 8, fp32): anything else is refused at construction.
@@ -130,6 +143,8 @@ class EncodeSessions:
         self.tail = [0] * self.S                      # valid samples in the slot's row
         self.rate = [self.codec_rate] * self.S        # the rate the slot's pushes arrive at
         self.fmt = ["f32"] * self.S                   # the sample format the slot's pushes arrive in (utils/pcm.py: FORMATS)
+        self.ch = [1] * self.S                        # the channels of the slot's pushes (interleaved frames when above 1)
+        self.pick = [-1] * self.S                     # the channel of them the slot encodes; -1: their mean
         self._fresh = [False] * self.S                # opened, state not zeroed yet (done with the slot's first push)
         self.buf = None
 
@@ -151,11 +166,16 @@ class EncodeSessions:
         self._check_open(slot)
         return self.sched[slot].tokens
 
-    def open(self, sample_rate: Optional[int] = None, sample_format: str = "f32") -> int:
+    def open(self, sample_rate: Optional[int] = None, sample_format: str = "f32", channels: int = 1,
+             channel: Optional[int] = None) -> int:
         """take a free slot: fresh schedule, state zeroed before its first push.  sample_rate: the rate this session's pushes arrive
         at, one of the declared `sample_rates` (None: the codec's).  sample_format: "f32", "s16" for torch.int16 pushes (16-bit
-        signed PCM, x / 32768), or "ulaw" / "alaw" for torch.uint8 pushes (G.711 codes).  Raises when every slot is taken."""
+        signed PCM, x / 32768), or "ulaw" / "alaw" for torch.uint8 pushes (G.711 codes).  channels: 1 .. 8; above 1 the pushes are
+        interleaved frames (n, channels), downmixed to their mean, or to channel `channel` of them (0 .. channels - 1).  Raises when
+        every slot is taken; a refused open takes no slot."""
         pcm.check_format(sample_format)
+        channels = pcm._check_channels(channels)
+        pick = pcm.check_channel(channel, channels)
         rate = self.codec_rate if sample_rate is None else int(sample_rate)
         if rate != self.codec_rate and rate not in self.sample_rates:
             raise ValueError(f"a session at {rate} Hz: the pool was built for {(self.codec_rate,) + self.sample_rates} Hz "
@@ -166,6 +186,7 @@ class EncodeSessions:
                 self.origin[s] = self.s0[s] = self.tail[s] = 0
                 self.rate[s] = rate
                 self.fmt[s] = sample_format
+                self.ch[s], self.pick[s] = channels, pick
                 if self.rs is not None:
                     self.rs.open(s, rate, self.codec_rate)
                 self._fresh[s] = True
@@ -188,10 +209,16 @@ class EncodeSessions:
         out = {}
         for slot, a in audio.items():
             self._check_open(slot)
-            if a.ndim == 2 and a.shape[0] == 1:
-                a = a[0]
-            if a.ndim != 1:
-                raise ValueError(f"slot {slot}: expected mono audio (n,) or (1, n), got {tuple(a.shape)}")
+            c = self.ch[slot]
+            if c > 1:
+                if a.ndim != 2 or a.shape[1] != c or not a.is_contiguous():
+                    raise ValueError(f"slot {slot} was opened with channels={c}: expected contiguous interleaved frames (n, {c}), got "
+                                     f"{tuple(a.shape)} (stride {a.stride()})")
+            else:
+                if a.ndim == 2 and a.shape[0] == 1:
+                    a = a[0]
+                if a.ndim != 1:
+                    raise ValueError(f"slot {slot}: expected mono audio (n,) or (1, n), got {tuple(a.shape)}")
             if a.shape[0] > self.max_push:
                 raise ValueError(f"slot {slot}: a push of {a.shape[0]} samples exceeds max_push_samples = {self.max_push}")
             # the push's dtype is the dtype of the slot's format; an f32 slot refuses the dtypes of the other formats
@@ -257,17 +284,19 @@ class EncodeSessions:
         steps = {}
         # ---- the sound cards' rates: ONE launch converts every slot that needs it, straight behind the slot's sample tail
         converted = {s: a for s, a in audio.items() if self._converts(s)}
-        # ---- the wire's format: a step that names an s16 or a G.711 slot puts ALL its chunks in place with ONE convert launch, each where the
-        # float path's per-slot copy would put it -- behind the slot's resampler tail or behind its sample tail
-        placed = any(self.fmt[s] != "f32" for s in audio)
+        # ---- the wire's format and channels: a step that names an s16, a G.711 or a multi-channel slot puts ALL its chunks in place with
+        # ONE convert launch (which downmixes on the way), each where the float path's per-slot copy would put it -- behind the slot's
+        # resampler tail or behind its sample tail
+        placed = any(self.fmt[s] != "f32" or self.ch[s] > 1 for s in audio)
         if placed:
             converted = self.rs.destinations({s: a.shape[0] for s, a in converted.items()}) if converted else {}
             moves = [((a.to(torch.float32) if self.fmt[s] == "f32" else a).contiguous(),
-                      converted[s] if s in converted else b["samples"][s, self.tail[s]:self.tail[s] + a.shape[0]], self.fmt[s])
+                      converted[s] if s in converted else b["samples"][s, self.tail[s]:self.tail[s] + a.shape[0]], s)
                      for s, a in audio.items() if a.shape[0]]
             if moves:
                 pcm.convert_items([x for x, _, _ in moves], [y for _, y, _ in moves], table=b["pcm_tab"],
-                                  src_formats=[f for _, _, f in moves])
+                                  src_formats=[self.fmt[s] for _, _, s in moves], src_channels=[self.ch[s] for _, _, s in moves],
+                                  src_pick=[self.pick[s] for _, _, s in moves])
         released = (self.rs.push(converted, final & set(converted), out=b["samples"], out_off=self.tail, placed=placed)
                     if converted else {})
         for s, a in audio.items():
@@ -356,7 +385,8 @@ class EncodeSessions:
         """no more audio for this slot: its remaining tokens, and the slot is free"""
         self._check_open(slot)
         dev = self.buf["samples"].device if self.buf is not None else next(self.codec.parameters()).device
-        return self.push({slot: torch.empty(0, dtype=pcm.FORMATS[self.fmt[slot]][1], device=dev)}, final=(slot,))[slot]
+        shape = (0,) if self.ch[slot] == 1 else (0, self.ch[slot])
+        return self.push({slot: torch.empty(shape, dtype=pcm.FORMATS[self.fmt[slot]][1], device=dev)}, final=(slot,))[slot]
 
 
 class DecodeSessions:
@@ -403,6 +433,14 @@ class DecodeSessions:
     buffer of the step holds bytes, each piece at a multiple of 16 of them; s16 pieces are int16 views of it, law pieces uint8 views.
     Out of scope: the lockstep StreamingDecoder and whole-clip decode() (callers have utils.pcm.to_pcm16 / to_g711), other formats
     (s24, s32, u8), dither.
+
+    The channel count belongs to a session too and sizes nothing: open(channels=c), 1 < c <= 8, starts a reply for a playback device
+    opened with c channels.  Its audio comes back as interleaved frames (m * up, c) -- or (its resampled length, c) -- in its format's
+    dtype, the empty piece as (0, c): every channel is, bit for bit, the audio of the same session opened with channels=1 (the sample
+    is converted once and stored c times: the fan-out of the channel rule of utils/pcm.py).  Every slot whose format is not f32 OR
+    whose channel count exceeds 1 joins the ONE convert launch into the packed buffer of the step; mono f32 slots keep their path and
+    their bits.  channels > 1 with return_audios=False is a ValueError at open.  Not served: channel maps, more than 8 channels,
+    planar (channel-first) audio, the lockstep StreamingDecoder and whole-clip decode() (callers have utils.pcm.fan_out).
 
     Out of scope, NotImplementedError: overlap_vocoder, graph_chunk_tokens, and a pool-wide output_sample_rate (a pool has no rate of
     its own).
@@ -457,6 +495,7 @@ class DecodeSessions:
             self.rs = SessionResampler(self.S, [(self.voc_rate, r) for r in self.output_sample_rates], self.cap * self.up)
         self.rate = [self.voc_rate] * self.S              # the rate the slot's audio leaves at
         self.fmt = ["f32"] * self.S                       # the sample format the slot's audio leaves in (utils/pcm.py: FORMATS)
+        self.ch = [1] * self.S                            # the channels the slot's audio leaves with (interleaved frames when above 1)
         self.sched: List[Optional[DecodeSchedule]] = [None] * self.S
         self.origin = [0] * self.S
         self.tok_origin = [0] * self.S                    # absolute index of the token in column 0 of the slot's token tail
@@ -482,12 +521,16 @@ class DecodeSessions:
         self._check_open(slot)
         return self.sched[slot].emitted
 
-    def open(self, output_sample_rate: Optional[int] = None, sample_format: str = "f32") -> int:
+    def open(self, output_sample_rate: Optional[int] = None, sample_format: str = "f32", channels: int = 1) -> int:
         """take a free slot: fresh schedule, state zeroed before its first push.  output_sample_rate: the rate this session's audio
         leaves at, one of the declared `output_sample_rates` (None: the vocoder's).  sample_format: "f32", "s16" for audio returned
-        as torch.int16 (16-bit signed PCM), or "ulaw" / "alaw" for torch.uint8 (G.711 codes).  Raises when every slot is taken."""
+        as torch.int16 (16-bit signed PCM), or "ulaw" / "alaw" for torch.uint8 (G.711 codes).  channels: 1 .. 8; above 1 the audio
+        comes back as interleaved frames (n, channels), every channel the mono audio.  Raises when every slot is taken; a refused
+        open takes no slot."""
         if pcm.check_format(sample_format) != "f32" and not self.return_audios:
             raise ValueError(f"sample_format={sample_format!r} without audio: return_audios=False leaves nothing to convert")
+        if pcm._check_channels(channels) > 1 and not self.return_audios:
+            raise ValueError(f"channels={channels} without audio: return_audios=False leaves nothing to fan out")
         rate = self.voc_rate if output_sample_rate is None else int(output_sample_rate)
         if rate != self.voc_rate and rate not in self.output_sample_rates:
             raise ValueError(f"a session at {rate} Hz: the pool was built for {(self.voc_rate,) + self.output_sample_rates} Hz "
@@ -498,11 +541,16 @@ class DecodeSessions:
                 self.origin[s] = self.tok_origin[s] = self.n_noise[s] = 0
                 self.rate[s] = rate
                 self.fmt[s] = sample_format
+                self.ch[s] = channels
                 if self.rs is not None:
                     self.rs.open(s, self.voc_rate, rate)
                 self._fresh[s] = True
                 return s
         raise RuntimeError(f"all {self.S} slots are taken")
+
+    def _wired(self, slot: int) -> bool:
+        """the slot's audio leaves through the convert launch of the step: another format than f32, or more than one channel"""
+        return self.fmt[slot] != "f32" or self.ch[slot] > 1
 
     def _check_open(self, slot) -> None:
         if not isinstance(slot, int) or not 0 <= slot < self.S:
@@ -634,11 +682,12 @@ class DecodeSessions:
             for s, st in steps.items():
                 o = self.origin[s]
                 mel = b["mel"][s, :, st.emit[0] - o:st.emit[1] - o].clone()
-                out[s] = (torch.empty(1, 0, dtype=pcm.FORMATS[self.fmt[s]][1], device=dev) if self.return_audios else None, mel)
+                out[s] = (torch.empty((1, 0) if self.ch[s] == 1 else (0, self.ch[s]), dtype=pcm.FORMATS[self.fmt[s]][1], device=dev)
+                          if self.return_audios else None, mel)
                 if st.voc_window[1] > st.voc_window[0]:
                     vgroups.setdefault(st.voc_window[1] - st.voc_window[0], []).append(s)
             pieces: Dict[int, torch.Tensor] = {}       # the new audio of the slots that leave at another rate, still in the vocoder's batch
-            wire: Dict[int, torch.Tensor] = {}         # the new float audio of the non-f32 slots, where it lies: converted at the end of the step
+            wire: Dict[int, torch.Tensor] = {}         # the new float audio of the non-f32 and the multi-channel slots, where it lies
             for _, members in vgroups.items():
                 wins = [b["mel"][s, :, steps[s].voc_window[0] - self.origin[s]:steps[s].voc_window[1] - self.origin[s]] for s in members]
                 wav = codec.vocoder(torch.stack(wins).contiguous())
@@ -648,7 +697,7 @@ class DecodeSessions:
                     piece = wav[i, :, (st.emit[0] - lo) * self.up:(st.emit[1] - lo) * self.up]
                     if self.rate[s] != self.voc_rate:
                         pieces[s] = piece[0]
-                    elif self.fmt[s] != "f32":
+                    elif self._wired(s):
                         wire[s] = piece[0]
                     else:
                         out[s] = (piece.clone(), out[s][1])
@@ -660,24 +709,27 @@ class DecodeSessions:
                         pieces[s] = torch.empty(0, dtype=torch.float32, device=dev)
                 if pieces:
                     for s, y in self.rs.push(pieces, final & set(pieces)).items():
-                        if self.fmt[s] != "f32":
+                        if self._wired(s):
                             wire[s] = y
                         else:
                             out[s] = (y[None], out[s][1])
-            # ---- the wire's format: ONE launch converts every non-f32 slot's new piece into one packed buffer of bytes of the step (each
-            # piece at a multiple of 16 bytes); the tensors handed out are views of it, int16 for s16 and uint8 for the G.711 laws
+            # ---- the wire's format and channels: ONE launch converts every non-f32 or multi-channel slot's new piece into one packed
+            # buffer of bytes of the step (each piece at a multiple of 16 bytes), fanning it out into the slot's channels on the way; the
+            # tensors handed out are views of it, int16 for s16, uint8 for the G.711 laws, (n, c) for c > 1 channels
             wire = {s: y for s, y in wire.items() if y.shape[0]}
             if wire:
-                at, total = {}, 0
+                at, total, size = {}, 0, {}
                 for s, y in wire.items():
                     at[s] = total
-                    total += (y.shape[0] * pcm.FORMATS[self.fmt[s]][1].itemsize + 15) // 16 * 16
+                    size[s] = y.shape[0] * self.ch[s] * pcm.FORMATS[self.fmt[s]][1].itemsize
+                    total += (size[s] + 15) // 16 * 16
                 packed = torch.empty(total, dtype=torch.uint8, device=dev)
-                dsts = [packed[at[s]:at[s] + y.shape[0] * pcm.FORMATS[self.fmt[s]][1].itemsize].view(pcm.FORMATS[self.fmt[s]][1])
-                        for s, y in wire.items()]
-                pcm.convert_items(list(wire.values()), dsts, table=b["pcm_tab"], dst_formats=[self.fmt[s] for s in wire])
+                dsts = [packed[at[s]:at[s] + size[s]].view(pcm.FORMATS[self.fmt[s]][1]) for s in wire]
+                dsts = [d if self.ch[s] == 1 else d.view(-1, self.ch[s]) for s, d in zip(wire, dsts)]
+                pcm.convert_items(list(wire.values()), dsts, table=b["pcm_tab"], dst_formats=[self.fmt[s] for s in wire],
+                                  dst_channels=[self.ch[s] for s in wire])
                 for (s, _), d in zip(wire.items(), dsts):
-                    out[s] = (d[None], out[s][1])
+                    out[s] = (d[None] if self.ch[s] == 1 else d, out[s][1])
         for s in final:
             self.sched[s] = None          # the slot is free; its rows are zeroed when it is opened and pushed to again
         return out

@@ -233,6 +233,33 @@ int dmel_resample_window_items_f32(const float* x, int64_t x_row_stride, int64_t
 #define DMEL_SAMPLE_ALAW 9
 int dmel_pcm_convert_items(const void* const* src, const int32_t* src_fmt, void* const* dst, const int32_t* dst_fmt, const int64_t* n,
                            int B, void* table_scratch, void* stream);
+/* The same launch with INTERLEAVED CHANNELS (the codec is mono; sound cards, WAV, RTP L16 and WebRTC deliver interleaved frames, usually
+ * stereo, and a playback device opened as stereo wants them).  An interleaved piece of n frames and c channels is a contiguous (n, c)
+ * array: frame i, channel j is element i * c + j; 1 <= c <= DMEL_MAX_CHANNELS (8).  n[b] counts FRAMES.  src_ch / dst_ch: int32 HOST
+ * tables of the channel counts (NULL: all 1); src_pick: NULL, or per item -1 (the mean) or a channel 0 .. src_ch - 1.  Item b:
+ *   downmix (c -> 1)   each channel's sample goes to f32 by its format's rule above (s16: x / 32768; law: decode / 32768; f32: the value
+ *                      itself); then acc = x_0; acc += x_1; ... acc += x_{c-1} in fp32, in channel order; then y = acc / (float)c, the
+ *                      IEEE correctly rounded fp32 division -- NOT a multiply by a rounded reciprocal.  Bit for bit numpy.mean(y, axis=0)
+ *                      of the channel-first float32 array, which is what librosa's to_mono computes (the reference loads its clips with
+ *                      librosa.load(..., mono=True): dataset/lhotse_tts_dataset.py:29-30, evaluation/evaluation_utils.py:215-224).  For
+ *                      s16 and law sources the channel values and their sum are exact in fp32 (at most 16 + 3 bits), so the result is the
+ *                      fp64 mean rounded once.  Nothing is sanitised: an f32 NaN or inf propagates as in a mono f32 item.
+ *   pick (c -> 1, k)   y = x_k by its format's rule, no arithmetic; for f32 the word is untouched.
+ *   fan-out (1 -> c)   the mono sample is converted ONCE by the f32 -> format rule above and stored c times, frame by frame; for
+ *                      f32 -> f32 the word is copied.
+ * The rule that one side of every item is f32 holds unchanged (stereo s16 -> mono s16 is refused like s16 -> s16).  Refused as well,
+ * before anything is launched, DMEL_EINVAL naming the item: a channel count outside 1 .. 8; both counts of an item above 1; a pick
+ * outside the source's channels or given with src_ch == 1.  Not served at all: weights, channel maps, planar (channel-first) pieces.
+ * Pointers are aligned to the sample size as before; n[b] * c < 2^40.  With every count 1 and no pick this IS dmel_pcm_convert_items
+ * (which calls it with NULL tables): the items' table words, the code path and the bits are the same.
+ * A workgroup owns 2048 frames of its item.  A stereo item (c == 2) whose src AND dst are 16-byte aligned moves a thread's 8 consecutive
+ * frames -- 8 mono elements on one side, 16 channel samples on the other -- with 16-byte loads and stores; any other channel count, an
+ * unaligned item and the frames behind the last whole 8 go frame by frame: same functions, same bits.  The channel counts and the pick
+ * ride in spare bits of the item's fourth table word: table_scratch stays 4 B int64. */
+#define DMEL_MAX_CHANNELS 8
+int dmel_pcm_convert_items_ch(const void* const* src, const int32_t* src_fmt, const int32_t* src_ch, const int32_t* src_pick,
+                              void* const* dst, const int32_t* dst_fmt, const int32_t* dst_ch, const int64_t* n, int B,
+                              void* table_scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Data front end on the GPU: what LhotseTTSDataset.__getitem__ + collate_fn do to the decoded clips of

@@ -33,7 +33,14 @@ it, `(y * 32768).round().clamp(-32768, 32767).to(int16)` per reply.  With --outp
 
 the same for replies whose wire carries G.711 (open(sample_format="ulaw" | "alaw"), torch.uint8 codes, telephony's 8 kHz): (b) is the
 same pool with f32 sessions and the companding every caller would do behind it in torch, the s16 rounding and then a clamp / exponent /
-shift / xor chain per reply."""
+shift / xor chain per reply.
+
+    python tools/bench_stream.py --sessions 16 --channels 2 --sample-format s16 [--output-sample-rate 48000] [--steps 40] [--out profiles/sessions_channels.txt]
+
+runs only this: S replies for playback devices opened with C channels, served (a) by a pool that was told so (open(sample_format=...,
+channels=C): the ONE convert launch of the step fans every piece out into interleaved frames) and (b) by the same pool with mono
+sessions of the same format and what every caller would do behind it, `repeat_interleave(C)` per reply.  Same tokens and noise,
+interleaved in one process, equal audio asserted, median and 10th / 90th percentile APPENDED to --out."""
 import json, os, statistics, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -303,6 +310,82 @@ def sessions_pcm_section(S, rates, steps, out, fmt="s16"):
     print("\n".join(table), file=sys.stderr)
     print(json.dumps(result))
 
+
+def sessions_channels_section(S, rates, steps, out, fmt, ch):
+    chunk, warmup = 64, 6
+    wire = f"{ch}ch_sessions"
+    pct = lambda v, q: sorted(v)[min(len(v) - 1, int(q * len(v)))]
+    gl = torch.Generator().manual_seed(10)
+    G, Cn = codec.dmel_groups, codec.decoder.input_channels
+    total = chunk * (steps + 1)
+    ids = torch.randint(0, 175, (S, G, total), generator=gl, dtype=torch.int32).to(dev)
+    noise = torch.randn(S, Cn, total * 4, device=dev)
+    rate = [rates[i % len(rates)] if rates else None for i in range(S)]
+    pools = {wire: codec.decode_sessions(S, max_push_tokens=chunk, output_sample_rates=rates),
+             "torch_behind": codec.decode_sessions(S, max_push_tokens=chunk, output_sample_rates=rates)}
+    slots = {wire: [pools[wire].open(output_sample_rate=rate[i], sample_format=fmt, channels=ch) for i in range(S)],
+             "torch_behind": [pools["torch_behind"].open(output_sample_rate=rate[i], sample_format=fmt) for i in range(S)]}
+    pos = [0] * S
+    ms = {k: [] for k in pools}
+
+    def run(k, n):
+        sl = slots[k]
+        out = pools[k].push({sl[i]: ids[i, :, pos[i]:pos[i] + n[i]] for i in range(S)},
+                            noise={sl[i]: noise[i, :, 4 * pos[i]:4 * (pos[i] + n[i])] for i in range(S)})
+        if k == wire:
+            return [out[sl[i]][0] for i in range(S)]
+        return [out[sl[i]][0][0].repeat_interleave(ch).view(-1, ch) for i in range(S)]
+
+    for step in range(steps):
+        n = [chunk - (i % 3) * (chunk // 3) if step == 0 else chunk for i in range(S)]
+        got = {}
+        keys = list(ms)
+        for k in (keys if step % 2 == 0 else keys[::-1]):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            got[k] = run(k, n)
+            torch.cuda.synchronize()
+            if step >= warmup:
+                ms[k].append((time.perf_counter() - t0) * 1e3)
+        for i in range(S):
+            a, b = got[wire][i], got["torch_behind"][i]
+            assert a.shape == b.shape and a.dtype == b.dtype and torch.equal(a.view(torch.uint8), b.view(torch.uint8)), \
+                f"step {step}, session {i}: the pool's audio differs"
+            pos[i] += n[i]
+    rows, result = [], {"sessions": S, "channels": ch, "sample_format": fmt, "output_sample_rates": rates, "chunk_tokens": chunk,
+                        "audio_equal": True, "runs": 1}
+    for k, v in ms.items():
+        med = statistics.median(v)
+        result[k] = {"median_ms": round(med, 3), "p10_ms": round(pct(v, 0.1), 3), "p90_ms": round(pct(v, 0.9), 3), "n": len(v)}
+        rows.append(f"{S:8d}  {k:13s}  {med:9.3f}  {pct(v, 0.1):9.3f}  {pct(v, 0.9):9.3f}  {len(v):4d}")
+    result["torch_over_channels"] = round(result["torch_behind"]["median_ms"] / result[wire]["median_ms"], 3)
+    rl = ",".join(map(str, rates)) if rates else "the vocoder's rate"
+    table = [f"{S} decode sessions returning interleaved {ch}-channel {fmt} frames at {rl}, {chunk}-token pushes, starts a third of a push apart, "
+             f"100 mel / 10 groups, BigVGAN base (tools/bench_stream.py --sessions {S} --channels {ch} --sample-format {fmt}" +
+             (f" --output-sample-rate {rl})" if rates else ")"),
+             f"wall time of one step of all sessions incl. host synchronisation, {steps - warmup} steady-state steps, the two interleaved in one process, "
+             "equal audio asserted;",
+             f"{wire} = open(sample_format=\"{fmt}\", channels={ch}): one convert launch per step, the fan-out inside it; torch_behind = mono {fmt} "
+             f"sessions, repeat_interleave({ch}) per reply",
+             "sessions  form           median ms     p10 ms     p90 ms     n"] + rows + [
+                 f"torch behind / {ch}-channel sessions: {result['torch_over_channels']:.3f} at the median; one run"]
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "a") as f:
+        f.write("\n".join(table) + "\n\n")
+    print("\n".join(table), file=sys.stderr)
+    print(json.dumps(result))
+
+
+if "--channels" in sys.argv and int(arg_after("--channels")) != 1:
+    assert "--sessions" in sys.argv, "--channels needs --sessions"
+    wire_format = arg_after("--sample-format", "f32")
+    assert wire_format in ("f32", "s16", "ulaw", "alaw"), f"--sample-format {wire_format}: expected f32, s16, ulaw or alaw"
+    sessions_channels_section(int(arg_after("--sessions")), [int(r) for r in arg_after("--output-sample-rate", "").split(",") if r],
+                              int(arg_after("--steps", "40")),
+                              arg_after("--out", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                              "sessions_channels.txt")),
+                              wire_format, int(arg_after("--channels")))
+    sys.exit(0)
 
 if "--sessions" in sys.argv and arg_after("--sample-format", "f32") != "f32":
     wire_format = arg_after("--sample-format")

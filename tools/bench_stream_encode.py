@@ -39,7 +39,14 @@ Interleaved in one process, equal ids checked, median and 10th / 90th percentile
     python tools/bench_stream_encode.py --sessions 16 --sample-format ulaw|alaw --sample-rate 8000 [--out profiles/sessions_g711.txt]
 
 the same for sessions whose wire carries G.711 (open(sample_format="ulaw" | "alaw"), torch.uint8 codes, telephony's 8 kHz): the
-baseline is the same pool with f32 sessions and the expansion every caller would do in front, a 256-entry table gather per slot."""
+baseline is the same pool with f32 sessions and the expansion every caller would do in front, a 256-entry table gather per slot.
+
+    python tools/bench_stream_encode.py --sessions 16 --channels 2 --sample-format s16 [--sample-rate 48000] [--out profiles/sessions_channels.txt]
+
+times a steady-state step of S sessions whose wire carries interleaved frames of C channels in a pool that was told so
+(open(sample_format=..., channels=C): ONE convert launch per step that downmixes on the way) against the same pool with mono f32
+sessions and the downmix every caller would do in front, `x.float().sum(1) / C` (with the format's scale or table) per slot.
+Interleaved in one process, equal ids asserted, median and 10th / 90th percentile.  APPENDS its table to --out."""
 import argparse, json, os, statistics, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -55,12 +62,15 @@ ap.add_argument("--sample-rate", default=None,
 ap.add_argument("--sessions", type=int, default=0, help="time a step of this many staggered independent sessions")
 ap.add_argument("--sample-format", default="f32", choices=("f32", "s16", "ulaw", "alaw"),
                 help="with --sessions: s16 / G.711 sessions against torch conversions in front")
+ap.add_argument("--channels", type=int, default=1, help="with --sessions: sessions fed interleaved frames of this many channels against the "
+                                                        "torch downmix in front")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 rates = [int(r) for r in args.sample_rate.split(",")] if args.sample_rate else []
 args.sample_rate = rates[0] if rates else None
 if args.out is None:
     args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                            "sessions_channels.txt" if args.sessions and args.channels > 1 else
                             "sessions_pcm.txt" if args.sessions and args.sample_format == "s16" else
                             "sessions_g711.txt" if args.sessions and args.sample_format != "f32" else
                             "sessions_resample.txt" if args.sessions and rates else "stream_sessions.txt" if args.sessions else "stream_resample.txt" if args.sample_rate else "stream_encode.txt")
@@ -315,6 +325,87 @@ def sessions_pcm_section():
     print(json.dumps(r))
 
 
+def sessions_channels_section():
+    """S staggered sessions fed interleaved frames of C channels in the chosen format (at their own rates, if any were given): one
+    pool that downmixes all slots in its one convert launch against the same pool with mono f32 sessions behind one torch downmix per
+    slot; the same frames, the same pushes, equal ids"""
+    from dmel_codec_amd.utils import pcm
+    S, fmt, ch = args.sessions, args.sample_format, args.channels
+    wire = f"{ch}ch_sessions"
+    rate = [rates[s % len(rates)] if rates else SR for s in range(S)]
+    n = [args.chunk * r // SR for r in rate]                     # 0.32 s of every slot's own rate, in frames
+    noise = [torch.randn((args.pushes + 1) * n[s], ch, device=dev) * 0.1 for s in range(S)]
+    # the divisor lives on the device: torch divides by a Python scalar as a multiply by its rounded reciprocal, which is not the rule
+    div = torch.full((), float(ch) * (32768.0 if fmt == "s16" else 1.0), device=dev)
+    if fmt == "f32":
+        audio = noise
+        in_front = lambda c: c.sum(1) / div
+    elif fmt == "s16":
+        audio = [(x * 32768).round().clamp(-32768, 32767).to(torch.int16) for x in noise]
+        in_front = lambda c: c.to(torch.float32).sum(1) / div   # the sum of up to 8 s16 values is exact in fp32
+    else:
+        audio = [pcm.to_g711(x.reshape(-1), fmt).view(-1, ch) for x in noise]
+        lut = pcm.from_g711(torch.arange(256, device=dev).to(torch.uint8), fmt)         # what a caller keeps: code -> float
+        in_front = lambda c: lut[c.long()].sum(1) / div
+    pools = {wire: codec.encode_sessions(slots=S, max_push_samples=max(n), sample_rates=rates),
+             "torch_in_front": codec.encode_sessions(slots=S, max_push_samples=max(n), sample_rates=rates)}
+    slots = {wire: [pools[wire].open(sample_rate=rate[s], sample_format=fmt, channels=ch) for s in range(S)],
+             "torch_in_front": [pools["torch_in_front"].open(sample_rate=rate[s]) for s in range(S)]}
+    pos = [0] * S
+    first = [n[s] * (1 + s % 3) // 3 for s in range(S)]          # the starts differ by a third of a push
+    ms = {k: [] for k in pools}
+    same, tokens = True, 0
+    for i in range(args.pushes):
+        size = first if i == 0 else n
+        chunks = [audio[s][pos[s]:pos[s] + size[s]] for s in range(S)]
+        pos = [p + k for p, k in zip(pos, size)]
+        got = {}
+        keys = list(ms)
+        for k in (keys if i % 2 == 0 else keys[::-1]):           # neither always goes first
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if k == wire:
+                ids = pools[k].push({slots[k][s]: chunks[s] for s in range(S)})
+            else:
+                ids = pools[k].push({slots[k][s]: in_front(chunks[s]) for s in range(S)})
+            got[k] = [ids[slots[k][s]] for s in range(S)]
+            torch.cuda.synchronize()
+            if i >= args.warmup:
+                ms[k].append((time.perf_counter() - t0) * 1e3)
+        same = same and all(torch.equal(a, b) for a, b in zip(*got.values()))
+        tokens += sum(a.shape[1] for a in got[wire])
+    r = {"sessions": S, "channels": ch, "sample_format": fmt, "sample_rates": rates or [SR], "chunk_s": args.chunk / SR,
+         "pushes": args.pushes, "warmup": args.warmup, "ids_equal": bool(same), "tokens": tokens, "runs": 1}
+    rows = []
+    for k, v in ms.items():
+        med = statistics.median(v)
+        r[k] = {"median_ms": round(med, 3), "p10_ms": round(pct(v, 0.1), 3), "p90_ms": round(pct(v, 0.9), 3), "n": len(v)}
+        rows.append(f"{S:8d}  {k:14s}  {med:9.3f}  {pct(v, 0.1):9.3f}  {pct(v, 0.9):9.3f}  {len(v):4d}")
+    r["torch_over_channels"] = round(r["torch_in_front"]["median_ms"] / r[wire]["median_ms"], 3)
+    rows.append(f"{S:8d}  median step with {S} torch downmixes in front / with {ch}-channel sessions: {r['torch_over_channels']:.3f}; "
+                f"ids equal: {same}; one run")
+    what = ",".join(map(str, rates)) if rates else "the codec's rate"
+    table = [f"encode sessions fed interleaved {ch}-channel {fmt} frames at {what}, 0.32 s pushes, starts staggered by a third of a push, 80 mel / "
+             f"8 groups / 70 channels / 20 layers (tools/bench_stream_encode.py --sessions {S} --channels {ch} --sample-format {fmt}" +
+             (f" --sample-rate {what})" if rates else ")"),
+             f"wall time of one step (one push for every stream) incl. host synchronisation, {args.pushes - args.warmup} steady-state steps, the two "
+             "forms interleaved in one process;",
+             f"{wire} = open(sample_format=\"{fmt}\", channels={ch}): one convert launch per step, the downmix inside it; torch_in_front = mono f32 "
+             "sessions, the format's conversion and .sum(1) / C per slot",
+             "sessions  form            median ms     p10 ms     p90 ms     n"] + rows
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "a") as f:
+        f.write("\n".join(table) + "\n\n")
+    print("\n".join(table), file=sys.stderr)
+    print(json.dumps(r))
+    assert same, "the ids of the channel-carrying sessions differ from those of the torch downmix in front"
+
+
+if args.channels != 1 and not args.sessions:
+    ap.error("--channels needs --sessions")
+if args.sessions and args.channels > 1:
+    sessions_channels_section()
+    sys.exit(0)
 if args.sessions and args.sample_format != "f32":
     sessions_pcm_section()
     sys.exit(0)
