@@ -730,7 +730,9 @@ int launch_copy_windows(const float* src, float* dst, int N, int C, int64_t cap,
 }
 
 // ---- ragged convert-copy over a pointer table (include/dmel_hip.h: dmel_pcm_convert_items) --------------------------------------------
-// Item blockIdx.y is row (src, dst, n, src_fmt | dst_fmt << 8) of `items`; a workgroup owns elements [2048 x, 2048 (x + 1)) of its item.
+// Item blockIdx.y is row (src, dst, n, word) of `items`; a workgroup owns FRAMES [2048 x, 2048 (x + 1)) of its item.  Every item has a
+// mono f32 side and a wire side of c interleaved channels of format F (a DMEL_SAMPLE_* code), and one of two directions: IN, wire ->
+// mono f32, and OUT, mono f32 -> wire.
 // The rounding rule lives in these two functions and nowhere else: both paths of the kernel call them, so an element has the same bits on
 // either.  s16 -> f32 is exact (|x| <= 2^15 times a power of two).  f32 -> s16: x 32768 is exact, the clamp comes first so that the
 // conversion to int never sees a value out of range, rintf is v_rndne_f32 (nearest, ties to even, whatever the rounding mode); NaN -> 0.
@@ -739,57 +741,6 @@ __device__ __forceinline__ float pcm_s16_to_f32(int16_t v) { return (float)v * 0
 __device__ __forceinline__ int16_t pcm_f32_to_s16(float v) {
   v = v != v ? 0.f : v;
   return (int16_t)(int)__builtin_rintf(fminf(fmaxf(v * 32768.f, -32768.f), 32767.f));
-}
-__device__ __forceinline__ uint32_t pcm_pack2(float lo, float hi) {
-  return (uint32_t)(uint16_t)pcm_f32_to_s16(lo) | ((uint32_t)(uint16_t)pcm_f32_to_s16(hi) << 16);
-}
-// SIN / SOUT: the source / destination holds int16.  f32 -> f32 moves the words untouched.  `wide`: src and dst of the item are both
-// 16-byte aligned (workgroup-uniform); then a thread whose 8 consecutive elements all lie in the item moves them with 16-byte loads and
-// stores.  Everything else -- an unaligned item, the elements behind the last whole 8 -- goes element by element, element e of the tile
-// to thread e % 256 so that a wave still reads and writes consecutive addresses.
-template <bool SIN, bool SOUT>
-__device__ __forceinline__ void pcm_convert_tile(const void* src, void* dst, int64_t n, int64_t base, bool wide) {
-  const int16_t* s16 = static_cast<const int16_t*>(src);
-  const uint32_t* s32 = static_cast<const uint32_t*>(src);
-  int16_t* d16 = static_cast<int16_t*>(dst);
-  uint32_t* d32 = static_cast<uint32_t*>(dst);
-  int64_t from = base;                                         // the element-wise path covers [from, min(n, base + kPcmTile))
-  if (wide) {
-    const int64_t whole = base + (min(n - base, (int64_t)kPcmTile) & ~(int64_t)(kPcmPerThread - 1));
-    const int64_t e = base + (int64_t)threadIdx.x * kPcmPerThread;
-    if (e < whole) {
-      if constexpr (SIN) {
-        const uint4 a = *reinterpret_cast<const uint4*>(s16 + e);
-        const uint32_t w[4] = {a.x, a.y, a.z, a.w};
-        float f[8];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          f[2 * j] = pcm_s16_to_f32((int16_t)(w[j] & 0xffffu));
-          f[2 * j + 1] = pcm_s16_to_f32((int16_t)(w[j] >> 16));
-        }
-        float4* o = reinterpret_cast<float4*>(d32 + e);
-        o[0] = make_float4(f[0], f[1], f[2], f[3]);
-        o[1] = make_float4(f[4], f[5], f[6], f[7]);
-      } else if constexpr (SOUT) {
-        const float4* p = reinterpret_cast<const float4*>(s32 + e);
-        const float4 a = p[0], b = p[1];
-        *reinterpret_cast<uint4*>(d16 + e) = make_uint4(pcm_pack2(a.x, a.y), pcm_pack2(a.z, a.w), pcm_pack2(b.x, b.y), pcm_pack2(b.z, b.w));
-      } else {
-        const uint4* p = reinterpret_cast<const uint4*>(s32 + e);
-        const uint4 a = p[0], b = p[1];
-        uint4* o = reinterpret_cast<uint4*>(d32 + e);
-        o[0] = a;
-        o[1] = b;
-      }
-    }
-    from = whole;
-  }
-  const int64_t end = min(n, base + kPcmTile);
-  for (int64_t e = from + threadIdx.x; e < end; e += 256) {
-    if constexpr (SIN) reinterpret_cast<float*>(d32)[e] = pcm_s16_to_f32(s16[e]);
-    else if constexpr (SOUT) d16[e] = pcm_f32_to_s16(reinterpret_cast<const float*>(s32)[e]);
-    else d32[e] = s32[e];
-  }
 }
 // G.711 (include/dmel_hip.h has the rule): 8-bit mu-law / A-law <-> the s16 value, integer arithmetic on every lane alike -- the segment
 // is a count of leading zeros, never a search or a table, and the selects are v_cndmask, not branches.  x is an s16 value in an int.
@@ -820,180 +771,160 @@ __device__ __forceinline__ int g711_alaw_decode(uint32_t code) {
   t = seg == 0 ? t + 8 : (t + 0x108) << max(seg - 1, 0);
   return (a & 0x80u) ? t : -t;
 }
-// ALAW: the law; both directions of both paths go through these two
-template <bool ALAW>
-__device__ __forceinline__ float g711_to_f32(uint32_t code) {
-  return (float)(ALAW ? g711_alaw_decode(code) : g711_ulaw_decode(code)) * 0x1p-15f;   // |x| < 2^15: exact
-}
-template <bool ALAW>
-__device__ __forceinline__ uint32_t g711_from_f32(float v) {
-  const int x = pcm_f32_to_s16(v);                              // the s16 rounding rule, unchanged
-  return ALAW ? g711_alaw_encode(x) : g711_ulaw_encode(x);
-}
-// ENC: f32 -> law (the destination holds bytes), else law -> f32 (the source does).  `wide`: the item's f32 pointer is 16-byte and its
-// law pointer 8-byte aligned (workgroup-uniform); then a thread whose 8 consecutive elements all lie in the item moves them as 8 bytes on
-// the law side and 2 x 16 bytes on the f32 side.  Everything else goes element by element as in pcm_convert_tile: one byte and one dword
-// per lane, a wave on consecutive addresses.
-template <bool ALAW, bool ENC>
-__device__ __forceinline__ void g711_convert_tile(const void* src, void* dst, int64_t n, int64_t base, bool wide) {
-  const uint8_t* s8 = static_cast<const uint8_t*>(src);
-  const float* sf = static_cast<const float*>(src);
-  uint8_t* d8 = static_cast<uint8_t*>(dst);
-  float* df = static_cast<float*>(dst);
-  int64_t from = base;                                         // the element-wise path covers [from, min(n, base + kPcmTile))
-  if (wide) {
-    const int64_t whole = base + (min(n - base, (int64_t)kPcmTile) & ~(int64_t)(kPcmPerThread - 1));
-    const int64_t e = base + (int64_t)threadIdx.x * kPcmPerThread;
-    if (e < whole) {
-      if constexpr (ENC) {
-        const float4* p = reinterpret_cast<const float4*>(sf + e);
-        const float4 a = p[0], b = p[1];
-        const float f[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-        uint32_t w[2] = {0u, 0u};
-#pragma unroll
-        for (int j = 0; j < 8; ++j) w[j >> 2] |= g711_from_f32<ALAW>(f[j]) << (8 * (j & 3));
-        *reinterpret_cast<uint2*>(d8 + e) = make_uint2(w[0], w[1]);
-      } else {
-        const uint2 a = *reinterpret_cast<const uint2*>(s8 + e);
-        const uint32_t w[2] = {a.x, a.y};
-        float f[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] = g711_to_f32<ALAW>((w[j >> 2] >> (8 * (j & 3))) & 0xFFu);
-        float4* o = reinterpret_cast<float4*>(df + e);
-        o[0] = make_float4(f[0], f[1], f[2], f[3]);
-        o[1] = make_float4(f[4], f[5], f[6], f[7]);
-      }
-    }
-    from = whole;
-  }
-  const int64_t end = min(n, base + kPcmTile);
-  for (int64_t e = from + threadIdx.x; e < end; e += 256) {
-    if constexpr (ENC) d8[e] = (uint8_t)g711_from_f32<ALAW>(sf[e]);
-    else df[e] = g711_to_f32<ALAW>(s8[e]);
-  }
-}
-// ---- interleaved channels (include/dmel_hip.h has the rule): c -> 1 by the mean or by picking one channel, 1 -> c by storing the
-// converted sample c times.  F is a DMEL_SAMPLE_* code.  Sample j of a thread's dwords w (as many as 16 samples of F fill), as f32 by the
-// format's rule above -- an f32 sample is its word, no arithmetic -- and the other way round: the bits of an f32 value in format F.
-template <int F>
-__device__ __forceinline__ float pcm_word_sample(const uint32_t* w, int j) {
-  if constexpr (F == DMEL_SAMPLE_S16) return pcm_s16_to_f32((int16_t)((w[j >> 1] >> (16 * (j & 1))) & 0xffffu));
-  else if constexpr (F == DMEL_SAMPLE_ULAW) return g711_to_f32<false>((w[j >> 2] >> (8 * (j & 3))) & 0xFFu);
-  else if constexpr (F == DMEL_SAMPLE_ALAW) return g711_to_f32<true>((w[j >> 2] >> (8 * (j & 3))) & 0xFFu);
-  else return __uint_as_float(w[j]);
-}
-template <int F>
-__device__ __forceinline__ float pcm_sample_at(const void* p, int64_t i) {
-  if constexpr (F == DMEL_SAMPLE_S16) return pcm_s16_to_f32(static_cast<const int16_t*>(p)[i]);
-  else if constexpr (F == DMEL_SAMPLE_ULAW) return g711_to_f32<false>(static_cast<const uint8_t*>(p)[i]);
-  else if constexpr (F == DMEL_SAMPLE_ALAW) return g711_to_f32<true>(static_cast<const uint8_t*>(p)[i]);
-  else return __uint_as_float(static_cast<const uint32_t*>(p)[i]);
-}
-template <int F>
-__device__ __forceinline__ uint32_t pcm_sample_bits(float v) {
-  if constexpr (F == DMEL_SAMPLE_S16) return (uint32_t)(uint16_t)pcm_f32_to_s16(v);
-  else if constexpr (F == DMEL_SAMPLE_ULAW) return g711_from_f32<false>(v);
-  else if constexpr (F == DMEL_SAMPLE_ALAW) return g711_from_f32<true>(v);
-  else return __float_as_uint(v);
-}
-template <int F>
-__device__ __forceinline__ void pcm_put_sample(void* p, int64_t i, uint32_t bits) {
-  if constexpr (F == DMEL_SAMPLE_S16) static_cast<uint16_t*>(p)[i] = (uint16_t)bits;
-  else if constexpr (F == DMEL_SAMPLE_ULAW || F == DMEL_SAMPLE_ALAW) static_cast<uint8_t*>(p)[i] = (uint8_t)bits;
-  else static_cast<uint32_t*>(p)[i] = bits;
-}
+// The four per-sample helpers.  The bits of a sample of format F (in the low end of a dword; what lies above them is ignored) as f32,
+// and the bits of an f32 value in format F, by the rules above -- an f32 sample is its word, no arithmetic.
 template <int F> constexpr int kPcmBytes = F == DMEL_SAMPLE_F32 ? 4 : F == DMEL_SAMPLE_S16 ? 2 : 1;
-// c channels of format F -> mono f32; n and base count FRAMES.  pick < 0: acc = x_0; acc += x_1; ...; y = acc / (float)c -- the IEEE
-// division, in channel order; pick = k: y = x_k.  c, pick and `wide` are workgroup-uniform.  `wide`: c == 2 and both pointers 16-byte
-// aligned; then a thread whose 8 consecutive frames all lie in the item loads their 16 samples with 16-byte loads (4 for f32, 2 for s16,
-// 1 for a law) and stores 2 x 16 bytes.  x / 2.0f is a correctly rounded division whatever the compiler makes of it, so a frame has the
-// same bits on either path.  Everything else goes frame by frame, one frame per lane.
 template <int F>
-__device__ __forceinline__ void pcm_downmix_tile(const void* src, void* dst, int64_t n, int64_t base, int c, int pick, bool wide) {
-  float* df = static_cast<float*>(dst);
-  int64_t from = base;
-  if (wide) {
-    const int64_t whole = base + (min(n - base, (int64_t)kPcmTile) & ~(int64_t)(kPcmPerThread - 1));
-    const int64_t e = base + (int64_t)threadIdx.x * kPcmPerThread;
-    if (e < whole) {
-      constexpr int kQuads = kPcmBytes<F>;                       // 16 samples of F are kPcmBytes<F> x 16 bytes
-      const uint4* p = reinterpret_cast<const uint4*>(static_cast<const uint8_t*>(src) + 2 * e * kPcmBytes<F>);
-      uint32_t w[4 * kQuads];
+__device__ __forceinline__ float pcm_to_f32(uint32_t bits) {
+  if constexpr (F == DMEL_SAMPLE_S16) return pcm_s16_to_f32((int16_t)bits);
+  else if constexpr (F == DMEL_SAMPLE_ULAW) return (float)g711_ulaw_decode(bits) * 0x1p-15f;   // |x| < 2^15: exact
+  else if constexpr (F == DMEL_SAMPLE_ALAW) return (float)g711_alaw_decode(bits) * 0x1p-15f;
+  else return __uint_as_float(bits);
+}
+template <int F>
+__device__ __forceinline__ uint32_t pcm_from_f32(float v) {
+  if constexpr (F == DMEL_SAMPLE_F32) return __float_as_uint(v);
+  else if constexpr (F == DMEL_SAMPLE_S16) return (uint32_t)(uint16_t)pcm_f32_to_s16(v);
+  else if constexpr (F == DMEL_SAMPLE_ULAW) return g711_ulaw_encode(pcm_f32_to_s16(v));   // the s16 rounding rule, unchanged
+  else return g711_alaw_encode(pcm_f32_to_s16(v));
+}
+// Sample i of w, and its store.  w is the wire itself (T is the format's own type, one sample each) or a thread's register dwords (T =
+// uint32_t, 4 / kPcmBytes<F> samples each: i is then a constant of an unrolled loop, the shifts fold, and w starts as zeros for a put).
+template <int F, typename T>
+__device__ __forceinline__ uint32_t pcm_get(const T* w, int64_t i) {
+  constexpr int kPer = sizeof(T) / kPcmBytes<F>;
+  return (uint32_t)w[i / kPer] >> (8 * kPcmBytes<F> * (int)(i % kPer));
+}
+template <int F, typename T>
+__device__ __forceinline__ void pcm_put(T* w, int64_t i, uint32_t bits) {
+  constexpr int kPer = sizeof(T) / kPcmBytes<F>;
+  if constexpr (kPer == 1) w[i] = (T)bits;
+  else w[i / kPer] |= bits << (8 * kPcmBytes<F> * (int)(i % kPer));
+}
+// NW dwords between memory and registers: one 8-byte access (NW == 2) or NW / 4 16-byte accesses
+template <int NW>
+__device__ __forceinline__ void pcm_load(uint32_t* w, const void* p) {
+  if constexpr (NW == 2) {
+    const uint2 a = *static_cast<const uint2*>(p);
+    w[0] = a.x; w[1] = a.y;
+  } else {
 #pragma unroll
-      for (int q = 0; q < kQuads; ++q) {
-        const uint4 a = p[q];
-        w[4 * q] = a.x; w[4 * q + 1] = a.y; w[4 * q + 2] = a.z; w[4 * q + 3] = a.w;
-      }
-      float f[8];
+    for (int q = 0; q < NW / 4; ++q) {
+      const uint4 a = static_cast<const uint4*>(p)[q];
+      w[4 * q] = a.x; w[4 * q + 1] = a.y; w[4 * q + 2] = a.z; w[4 * q + 3] = a.w;
+    }
+  }
+}
+template <int NW>
+__device__ __forceinline__ void pcm_store(void* p, const uint32_t* w) {
+  if constexpr (NW == 2) {
+    *static_cast<uint2*>(p) = make_uint2(w[0], w[1]);
+  } else {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float l = pcm_word_sample<F>(w, 2 * j), r = pcm_word_sample<F>(w, 2 * j + 1);
+    for (int q = 0; q < NW / 4; ++q) static_cast<uint4*>(p)[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+  }
+}
+// The wide body: the 8 consecutive frames from frame e on, all inside the item, C = 1 or 2 channels.  On the f32 side they are two
+// 16-byte accesses, on the wire side NW = 2, 4, 8 or 16 dwords, unpacked and packed in registers.  The stereo mean is acc = l; acc += r;
+// acc / 2.0f -- a correctly rounded division whatever the compiler makes of it, so a frame has the bits the frame loop gives it.
+template <int F, int C, bool IN>
+__device__ __forceinline__ void pcm_wide(const void* src, void* dst, int64_t e, int pick) {
+  constexpr int NW = kPcmPerThread * C * kPcmBytes<F> / 4;
+  uint32_t w[NW], f[kPcmPerThread];
+  if constexpr (IN) {
+    pcm_load<NW>(w, static_cast<const uint8_t*>(src) + e * C * kPcmBytes<F>);
+#pragma unroll
+    for (int j = 0; j < kPcmPerThread; ++j) {
+      float y = pcm_to_f32<F>(pcm_get<F>(w, C * j));
+      if constexpr (C == 2) {
+        const float l = y, r = pcm_to_f32<F>(pcm_get<F>(w, C * j + 1));
         if (pick < 0) {
           float acc = l;
           acc += r;
-          f[j] = acc / 2.0f;
+          y = acc / 2.0f;
         } else {
-          f[j] = pick ? r : l;
+          y = pick ? r : l;
         }
       }
-      float4* o = reinterpret_cast<float4*>(df + e);
-      o[0] = make_float4(f[0], f[1], f[2], f[3]);
-      o[1] = make_float4(f[4], f[5], f[6], f[7]);
+      f[j] = __float_as_uint(y);
     }
-    from = whole;
-  }
-  const int64_t end = min(n, base + kPcmTile);
-  for (int64_t e = from + threadIdx.x; e < end; e += 256) {
-    float y;
-    if (pick >= 0) {
-      y = pcm_sample_at<F>(src, e * c + pick);
-    } else {
-      float acc = pcm_sample_at<F>(src, e * c);
-      for (int j = 1; j < c; ++j) acc += pcm_sample_at<F>(src, e * c + j);
-      y = acc / (float)c;
+    pcm_store<kPcmPerThread>(static_cast<float*>(dst) + e, f);
+  } else {
+    pcm_load<kPcmPerThread>(f, static_cast<const float*>(src) + e);
+#pragma unroll
+    for (int j = 0; j < NW; ++j) w[j] = 0u;
+#pragma unroll
+    for (int j = 0; j < kPcmPerThread; ++j) {
+      const uint32_t v = pcm_from_f32<F>(__uint_as_float(f[j]));
+#pragma unroll
+      for (int k = 0; k < C; ++k) pcm_put<F>(w, C * j + k, v);
     }
-    df[e] = y;
+    pcm_store<NW>(static_cast<uint8_t*>(dst) + e * C * kPcmBytes<F>, w);
   }
 }
-// mono f32 -> c channels of format F: the sample is converted ONCE and its bits are stored c times.  `wide`: c == 2 and both pointers
-// 16-byte aligned; a thread's 8 frames are then 2 x 16 bytes loaded and 16 samples stored with 16-byte stores (4, 2 or 1 of them).
-template <int F>
-__device__ __forceinline__ void pcm_fanout_tile(const void* src, void* dst, int64_t n, int64_t base, int c, bool wide) {
-  const float* sf = static_cast<const float*>(src);
-  int64_t from = base;
+// One item's tile.  IN: c channels of format F -> mono f32; pick = k: y = x_k, no arithmetic; pick < 0: acc = x_0; acc += x_1; ...;
+// y = acc / (float)c, the IEEE division, in channel order.  OUT: the sample is converted ONCE and its bits are stored c times.  c, pick
+// and `wide` are workgroup-uniform.  `wide`: c <= 2, the f32 side 16-byte aligned and the wire side aligned to what a thread moves at
+// once -- 8 bytes for a mono law, 16 for everything else; then a thread whose 8 consecutive frames all lie in the item takes pcm_wide.
+// Everything else -- another c, an unaligned item, the frames behind the last whole 8 -- goes frame by frame, frame e of the tile to
+// thread e % 256 so that a wave still reads and writes consecutive addresses.
+template <int F, bool IN>
+__device__ __forceinline__ void pcm_tile_c(const void* src, void* dst, uint64_t sa, uint64_t da, int64_t n, int64_t base, int c, int pick) {
+  using T = std::conditional_t<kPcmBytes<F> == 4, uint32_t, std::conditional_t<kPcmBytes<F> == 2, uint16_t, uint8_t>>;
+  const bool wide = c <= 2 && ((IN ? da : sa) & 15) == 0 && ((IN ? sa : da) & (kPcmBytes<F> == 1 && c == 1 ? 7 : 15)) == 0;
+  int64_t from = base;                                         // the frame-wise path covers [from, min(n, base + kPcmTile))
   if (wide) {
     const int64_t whole = base + (min(n - base, (int64_t)kPcmTile) & ~(int64_t)(kPcmPerThread - 1));
     const int64_t e = base + (int64_t)threadIdx.x * kPcmPerThread;
     if (e < whole) {
-      const float4* p = reinterpret_cast<const float4*>(sf + e);
-      const float4 a = p[0], b = p[1];
-      const float f[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-      constexpr int kQuads = kPcmBytes<F>;
-      uint32_t w[4 * kQuads];
-#pragma unroll
-      for (int j = 0; j < 4 * kQuads; ++j) w[j] = 0u;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const uint32_t v = pcm_sample_bits<F>(f[j]);
-        if constexpr (F == DMEL_SAMPLE_F32) w[2 * j] = w[2 * j + 1] = v;
-        else if constexpr (F == DMEL_SAMPLE_S16) w[j] = v | (v << 16);
-        else w[j >> 1] |= (v | (v << 8)) << (16 * (j & 1));
-      }
-      uint4* o = reinterpret_cast<uint4*>(static_cast<uint8_t*>(dst) + 2 * e * kPcmBytes<F>);
-#pragma unroll
-      for (int q = 0; q < kQuads; ++q) o[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+      if (c == 1) pcm_wide<F, 1, IN>(src, dst, e, pick);
+      else pcm_wide<F, 2, IN>(src, dst, e, pick);
     }
     from = whole;
   }
   const int64_t end = min(n, base + kPcmTile);
   for (int64_t e = from + threadIdx.x; e < end; e += 256) {
-    const uint32_t v = pcm_sample_bits<F>(sf[e]);
-    for (int j = 0; j < c; ++j) pcm_put_sample<F>(dst, e * c + j, v);
+    if constexpr (IN) {
+      const T* s = static_cast<const T*>(src);
+      float y;
+      if (pick >= 0) {
+        y = pcm_to_f32<F>(pcm_get<F>(s, e * c + pick));
+      } else {
+        float acc = pcm_to_f32<F>(pcm_get<F>(s, e * c));
+        for (int j = 1; j < c; ++j) acc += pcm_to_f32<F>(pcm_get<F>(s, e * c + j));
+        y = acc / (float)c;
+      }
+      static_cast<float*>(dst)[e] = y;
+    } else {
+      const uint32_t v = pcm_from_f32<F>(static_cast<const float*>(src)[e]);
+      for (int j = 0; j < c; ++j) pcm_put<F>(static_cast<T*>(dst), e * c + j, v);
+    }
   }
 }
-__device__ __forceinline__ bool pcm_is_law(int64_t f) { return f == DMEL_SAMPLE_ULAW || f == DMEL_SAMPLE_ALAW; }
-// The item's fourth word: src_fmt | dst_fmt << 8 | (src_ch - 1) << 16 | (dst_ch - 1) << 20 | (pick + 1) << 24.  A mono item has nothing
-// above bit 15 -- the word it always had -- and takes the code below the channel block unchanged.
+// The counts that have a wide body reach pcm_tile_c as literals, so that their frame loop is compiled for them as well: with a
+// run-time c a mono item's loop keeps a multiply and an inner loop per frame, and an unaligned mono item of a million samples was
+// measured 5 to 34 % slower for them.  A mono item runs as pick = 0: its sample is moved, never acc / 1.0f, which would quiet a
+// signalling NaN (OUT ignores the pick).
+template <int F, bool IN>
+__device__ __forceinline__ void pcm_tile(const void* src, void* dst, uint64_t sa, uint64_t da, int64_t n, int64_t base, int c, int pick) {
+  if (c == 1) pcm_tile_c<F, IN>(src, dst, sa, da, n, base, 1, 0);
+  else if (c == 2) pcm_tile_c<F, IN>(src, dst, sa, da, n, base, 2, pick);
+  else pcm_tile_c<F, IN>(src, dst, sa, da, n, base, c, pick);
+}
+// the switch on the wire format f, one per direction
+template <bool IN>
+__device__ __forceinline__ void pcm_tile_of(int f, const void* src, void* dst, uint64_t sa, uint64_t da, int64_t n, int64_t base, int c,
+                                            int pick) {
+  switch (f) {
+    case DMEL_SAMPLE_S16: pcm_tile<DMEL_SAMPLE_S16, IN>(src, dst, sa, da, n, base, c, pick); break;
+    case DMEL_SAMPLE_ULAW: pcm_tile<DMEL_SAMPLE_ULAW, IN>(src, dst, sa, da, n, base, c, pick); break;
+    case DMEL_SAMPLE_ALAW: pcm_tile<DMEL_SAMPLE_ALAW, IN>(src, dst, sa, da, n, base, c, pick); break;
+    default: pcm_tile<DMEL_SAMPLE_F32, IN>(src, dst, sa, da, n, base, c, pick); break;
+  }
+}
+// The item's fourth word: src_fmt | dst_fmt << 8 | (src_ch - 1) << 16 | (dst_ch - 1) << 20 | (pick + 1) << 24 (the entry admits c -> 1
+// and 1 -> c only, one side f32).  An item is OUT when its destination has channels or a format other than f32; mono f32 -> f32 is IN
+// with F = f32.
 __global__ __launch_bounds__(256) void pcm_convert_kernel(const int64_t* __restrict__ items) {
   const int64_t* it = items + kPcmItemWords * (int64_t)blockIdx.y;
   const int64_t n = uniform_i64(it + 2);
@@ -1001,45 +932,12 @@ __global__ __launch_bounds__(256) void pcm_convert_kernel(const int64_t* __restr
   if (base >= n) return;                                       // workgroup-uniform: every workgroup of an idle item leaves here
   const uint64_t sa = (uint64_t)uniform_i64(it), da = (uint64_t)uniform_i64(it + 1);
   const int64_t word = uniform_i64(it + 3);
-  const int64_t fmt = word & 0xffff;
+  const int sf = (int)(word & 0xff), df = (int)((word >> 8) & 0xff);
+  const int sc = (int)((word >> 16) & 7) + 1, dc = (int)((word >> 20) & 7) + 1, pick = (int)((word >> 24) & 15) - 1;
   const void* src = reinterpret_cast<const void*>(sa);
   void* dst = reinterpret_cast<void*>(da);
-  if (word >> 16) {                                            // channels (the entry admits c -> 1 and 1 -> c only, one side f32)
-    const int sc = (int)((word >> 16) & 7) + 1, dc = (int)((word >> 20) & 7) + 1, pick = (int)((word >> 24) & 15) - 1;
-    const bool wide2 = ((sa | da) & 15) == 0 && (sc == 2 || dc == 2);
-    if (sc > 1) {
-      switch ((int)(fmt & 0xff)) {
-        case DMEL_SAMPLE_S16: pcm_downmix_tile<DMEL_SAMPLE_S16>(src, dst, n, base, sc, pick, wide2); break;
-        case DMEL_SAMPLE_ULAW: pcm_downmix_tile<DMEL_SAMPLE_ULAW>(src, dst, n, base, sc, pick, wide2); break;
-        case DMEL_SAMPLE_ALAW: pcm_downmix_tile<DMEL_SAMPLE_ALAW>(src, dst, n, base, sc, pick, wide2); break;
-        default: pcm_downmix_tile<DMEL_SAMPLE_F32>(src, dst, n, base, sc, pick, wide2); break;
-      }
-    } else {
-      switch ((int)(fmt >> 8)) {
-        case DMEL_SAMPLE_S16: pcm_fanout_tile<DMEL_SAMPLE_S16>(src, dst, n, base, dc, wide2); break;
-        case DMEL_SAMPLE_ULAW: pcm_fanout_tile<DMEL_SAMPLE_ULAW>(src, dst, n, base, dc, wide2); break;
-        case DMEL_SAMPLE_ALAW: pcm_fanout_tile<DMEL_SAMPLE_ALAW>(src, dst, n, base, dc, wide2); break;
-        default: pcm_fanout_tile<DMEL_SAMPLE_F32>(src, dst, n, base, dc, wide2); break;
-      }
-    }
-    return;
-  }
-  if (pcm_is_law(fmt & 0xff)) {                              // law -> f32 (the entry admits no other destination)
-    const bool wide8 = (sa & 7) == 0 && (da & 15) == 0;
-    if ((fmt & 0xff) == DMEL_SAMPLE_ULAW) g711_convert_tile<false, false>(src, dst, n, base, wide8);
-    else g711_convert_tile<true, false>(src, dst, n, base, wide8);
-    return;
-  }
-  if (pcm_is_law(fmt >> 8)) {                                  // f32 -> law
-    const bool wide8 = (sa & 15) == 0 && (da & 7) == 0;
-    if ((fmt >> 8) == DMEL_SAMPLE_ULAW) g711_convert_tile<false, true>(src, dst, n, base, wide8);
-    else g711_convert_tile<true, true>(src, dst, n, base, wide8);
-    return;
-  }
-  const bool wide = ((sa | da) & 15) == 0;
-  if ((fmt & 0xff) == DMEL_SAMPLE_S16) pcm_convert_tile<true, false>(src, dst, n, base, wide);
-  else if ((fmt >> 8) == DMEL_SAMPLE_S16) pcm_convert_tile<false, true>(src, dst, n, base, wide);
-  else pcm_convert_tile<false, false>(src, dst, n, base, wide);
+  if (dc > 1 || df != DMEL_SAMPLE_F32) pcm_tile_of<false>(df, src, dst, sa, da, n, base, dc, -1);
+  else pcm_tile_of<true>(sf, src, dst, sa, da, n, base, sc, pick);
 }
 
 // out[r] = max(len[r] - row r's shift, 0): an item's output length relative to the first column of its window

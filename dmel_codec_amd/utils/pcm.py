@@ -181,14 +181,20 @@ def _rows(x: torch.Tensor, dtype, what: str) -> torch.Tensor:
     return x.contiguous()
 
 
-def _convert_rows(x: torch.Tensor, src_format: str, dst_format: str) -> torch.Tensor:
-    y = torch.empty(x.shape, dtype=FORMATS[dst_format][1], device=x.device)
-    xs, ys = (x[None], y[None]) if x.ndim == 1 else (x, y)
+def _convert_rows(x: torch.Tensor, src_format: str, dst_format: str, src_channels: Optional[int] = None,
+                  dst_channels: Optional[int] = None, pick: int = -1) -> torch.Tensor:
+    """x: contiguous rows (n,) / (B, n), with the channels as one more, last axis where src_channels names them (1 included) -> the
+    converted rows, with such an axis where dst_channels names them.  One item per row; a launch takes 65535 of them."""
+    frames = tuple(x.shape if src_channels is None else x.shape[:-1])
+    sc, dc = src_channels or 1, dst_channels or 1
+    y = torch.empty(frames if dst_channels is None else frames + (dc,), dtype=FORMATS[dst_format][1], device=x.device)
     if x.numel():
-        for a in range(0, xs.shape[0], MAX_ITEMS):                 # one item per row; a launch takes 65535 of them
+        rows = (-1, frames[-1])                                    # a 1-channel row is a view of its samples, a mono piece
+        xs, ys = x.view(rows if sc == 1 else rows + (sc,)), y.view(rows if dc == 1 else rows + (dc,))
+        for a in range(0, xs.shape[0], MAX_ITEMS):
             k = min(MAX_ITEMS, xs.shape[0] - a)
             convert_items(list(xs[a:a + k].unbind(0)), list(ys[a:a + k].unbind(0)), src_formats=[src_format] * k,
-                          dst_formats=[dst_format] * k)
+                          dst_formats=[dst_format] * k, src_channels=[sc] * k, dst_channels=[dc] * k, src_pick=[pick] * k)
     return y
 
 
@@ -253,16 +259,7 @@ def downmix(x: torch.Tensor, sample_format: Optional[str] = None, channel: Optio
         raise ValueError(f"{c} channels: expected 1 .. {MAX_CHANNELS} (interleaved frames, channels last)")
     pick = check_channel(channel, c)
     _lib.require_cuda(x, "audio")
-    x = x.contiguous()
-    y = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device)
-    xs, ys = (x[None], y[None]) if x.ndim == 2 else (x, y)
-    if x.numel():
-        for a in range(0, xs.shape[0], MAX_ITEMS):
-            k = min(MAX_ITEMS, xs.shape[0] - a)
-            srcs = [r[:, 0] for r in xs[a:a + k].unbind(0)] if c == 1 else list(xs[a:a + k].unbind(0))
-            convert_items(srcs, list(ys[a:a + k].unbind(0)), src_formats=[fmt] * k, dst_formats=["f32"] * k, src_channels=[c] * k,
-                          src_pick=[pick] * k)
-    return y
+    return _convert_rows(x.contiguous(), fmt, "f32", src_channels=c, pick=pick)
 
 
 def fan_out(y: torch.Tensor, channels: int, sample_format: str = "f32") -> torch.Tensor:
@@ -271,13 +268,4 @@ def fan_out(y: torch.Tensor, channels: int, sample_format: str = "f32") -> torch
     rows.  What a caller puts behind the whole-clip decode()."""
     c = _check_channels(channels)
     check_format(sample_format)
-    y = _rows(y, torch.float32, "waveform")
-    out = torch.empty(tuple(y.shape) + (c,), dtype=FORMATS[sample_format][1], device=y.device)
-    ys, os_ = (y[None], out[None]) if y.ndim == 1 else (y, out)
-    if y.numel():
-        for a in range(0, ys.shape[0], MAX_ITEMS):
-            k = min(MAX_ITEMS, ys.shape[0] - a)
-            dsts = [r[:, 0] for r in os_[a:a + k].unbind(0)] if c == 1 else list(os_[a:a + k].unbind(0))
-            convert_items(list(ys[a:a + k].unbind(0)), dsts, src_formats=["f32"] * k, dst_formats=[sample_format] * k,
-                          dst_channels=[c] * k)
-    return out
+    return _convert_rows(_rows(y, torch.float32, "waveform"), "f32", sample_format, dst_channels=c)

@@ -152,10 +152,14 @@ def test_fan_out_equals_the_restatement(dev, fmt, c):
 
 
 def test_f32_pick_and_fan_out_move_the_words(dev):
-    """-0.0, denormals, inf and a NaN pass through a pick and a fan-out as the words they are"""
+    """-0.0, denormals, inf and NaNs -- a signalling one and a negative one with a payload among them -- pass through a pick and a
+    fan-out as the words they are"""
     special = torch.tensor([-0.0, 0.0, 2.0 ** -149, -(2.0 ** -149), 1e-40, -1e-40, 2.0 ** -126, float("inf"), float("-inf"), float("nan"),
                             1.0, -1.0, FLT_MAX, -FLT_MAX, 1.0 - 2.0 ** -24, 3.0])
-    x = special.repeat(40)                                                              # 640 frames: wide groups and a tail of none
+    nans = torch.tensor([0x7FA00001, 0xFFC12345 - 2 ** 32], dtype=torch.int32)          # any arithmetic would quiet the first
+    special = torch.cat([special[:2], nans.view(torch.float32), special[2:]])           # 18 words; x[632:634] are the two: in 637's tail
+    x = special.repeat(36)[:640].contiguous()                                           # 640 frames: wide groups and a tail of none
+    assert torch.equal(words(x)[632:634], nans)
     for n in (640, 637):
         for off in ((0, 0), (1, 1)):
             for c in (2, 3):
@@ -167,6 +171,7 @@ def test_f32_pick_and_fan_out_move_the_words(dev):
                     got = dst.t.cpu()
                     assert torch.equal(words(got), words(frames[:, k].contiguous())) and dst.guards_intact() and src.untouched()
                     assert bool((words(got) == -2 ** 31).any()) and bool((words(got) == 1).any())        # -0.0 and 2^-149 are there
+                    assert bool((words(got) == 0x7FA00001).any()) and bool((words(got) == 0xFFC12345 - 2 ** 32).any())
                 src, dst = Guarded(n, "f32", dev, off[0], fill=x[:n]), Guarded(n * c, "f32", dev, off[1])
                 rc, msg = call([src], [dst], [n], dc=[c])
                 assert rc == 0, msg

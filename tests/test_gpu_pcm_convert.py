@@ -133,10 +133,14 @@ def test_s16_to_f32_all_values(dev, offsets):
 @pytest.mark.parametrize("offsets", [(0, 0), (1, 3)])
 def test_f32_to_f32_is_a_copy_of_the_words(dev, offsets):
     y = float_master(3000)
+    nans = torch.tensor([0x7FA00001, 0xFFC12345 - 2 ** 32], dtype=torch.int32)     # a signalling NaN, a negative NaN with a payload
+    words(y)[1000:1002] = nans                                                     # any arithmetic on the way would quiet the first
+    words(y)[2998:] = nans
     src, dst = Guarded(3000, torch.float32, dev, offsets[0], fill=y), Guarded(3000, torch.float32, dev, offsets[1])
     rc, msg = call([src], [dst])
     assert rc == 0, msg
     finite = torch.isfinite(y)
+    assert torch.equal(words(y)[[1000, 1001, 2998, 2999]], nans.repeat(2))         # the input holds them as the words they are
     assert torch.equal(dst.t.cpu()[finite], y[finite]) and torch.equal(words(dst.t.cpu()), words(y))
     assert dst.guards_intact() and src.untouched()
 
