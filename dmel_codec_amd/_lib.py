@@ -61,6 +61,7 @@ PROTOTYPES = {
     "dmel_stft_window_f32": (C.c_int, [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, vp]),
     "dmel_stft_window_items_f32": (C.c_int, [vp, vp, C.c_int64, C.c_int64, i64p, i64p, vp, vp, vp, C.c_int, i64p, i64p, i64p, vp, vp]),
     "dmel_aa_snake_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp]),
+    "dmel_aa_snake_items_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp, vp]),
     "dmel_aa_snake_backward_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp]),
     "dmel_discriminator_create": (C.c_int, [C.POINTER(vp)]),
     "dmel_discriminator_destroy": (None, [vp]),
@@ -137,6 +138,8 @@ PROTOTYPES = {
     "dmel_stft_set_exclusive_cu": (C.c_int, [C.c_int]),
     "dmel_bigvgan_set_precision": (C.c_int, [vp, C.c_int]),
     "dmel_bigvgan_forward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int64, vp, C.c_size_t, vp]),
+    "dmel_bigvgan_items_workspace_bytes": (C.c_size_t, [vp, C.c_int, C.c_int64]),
+    "dmel_bigvgan_forward_items": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int64, vp, C.c_size_t, vp]),
     "dmel_conv_create": (C.c_int, [C.POINTER(vp), vp, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "dmel_conv_destroy": (None, [vp]),
     "dmel_conv_set_precision": (C.c_int, [vp, C.c_int]),
@@ -145,6 +148,7 @@ PROTOTYPES = {
     "dmel_conv_transpose1d_set_precision": (C.c_int, [vp, C.c_int]),
     "dmel_conv_transpose1d_forward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int64, vp]),
     "dmel_conv_post_f32": (C.c_int, [vp, vp, C.c_float, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp]),
+    "dmel_conv_post_items_f32": (C.c_int, [vp, vp, C.c_float, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp, vp]),
     "dmel_aa_snake_backward_input_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp]),
     "dmel_bigvgan_enable_input_grad": (C.c_int, [vp, C.c_int]),
     "dmel_bigvgan_train_workspace_bytes": (C.c_size_t, [vp, C.c_int, C.c_int64]),

@@ -45,16 +45,12 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // The arithmetic of every element is the one of the formulas above in the same order, so where a tile or a row starts, and which of the
 // two instantiations runs, never changes a bit.  Replicate padding of the 2x signal (pairs m < 0 and m > T-1) is patched into the planes by
 // three threads between the stages, in the tiles that touch a row end only (block-uniform test).
+// The tiles of ONE row: xr / yr point at column 0 of the (b, c) row, T is the number of valid columns of that row (its replicate padding
+// ends at T - 1; nothing at or behind column T is read or written), `first` the first output of this workgroup's nsub tiles.
 template <bool VEC>
-__global__ __launch_bounds__(256) void aa_snake_kernel(const float* __restrict__ x, float* __restrict__ y,
-                                                          const float* __restrict__ alpha, const float* __restrict__ beta,
-                                                          Taps12 tu, Taps12 td, int logscale, int C, int T, int nsub) {
-  __shared__ __attribute__((aligned(16))) float xs[kSnakeFwdTile + 16];
-  __shared__ __attribute__((aligned(16))) float ve[kSnakeFwdTile + 16];
-  __shared__ __attribute__((aligned(16))) float vo[kSnakeFwdTile + 16];
-  const int c = blockIdx.y, b = blockIdx.z;
-  const float* xr = x + ((int64_t)b * C + c) * T;
-  float* yr = y + ((int64_t)b * C + c) * T;
+__device__ __forceinline__ void aa_snake_row(const float* __restrict__ xr, float* __restrict__ yr, const float* __restrict__ alpha,
+                                             const float* __restrict__ beta, const Taps12& tu, const Taps12& td, int logscale, int c, int T,
+                                             int first, int nsub, float* xs, float* ve, float* vo) {
   float a = alpha[c], bt = beta ? beta[c] : a;
   if (logscale) {
     bt = beta ? expf(bt) : expf(a);
@@ -78,7 +74,6 @@ __global__ __launch_bounds__(256) void aa_snake_kernel(const float* __restrict__
   float aa[8], bb[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) { aa[i] = a; bb[i] = inv_b; }
-  const int first = blockIdx.x * nsub * kSnakeFwdTile;
   f32x4 pre = {0.f, 0.f, 0.f, 0.f};
   if (first < T) pre = fetch(first);
   for (int sub = 0; sub < nsub; ++sub) {
@@ -143,6 +138,41 @@ __global__ __launch_bounds__(256) void aa_snake_kernel(const float* __restrict__
       }
     }
   }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void aa_snake_kernel(const float* __restrict__ x, float* __restrict__ y,
+                                                          const float* __restrict__ alpha, const float* __restrict__ beta,
+                                                          Taps12 tu, Taps12 td, int logscale, int C, int T, int nsub) {
+  __shared__ __attribute__((aligned(16))) float xs[kSnakeFwdTile + 16];
+  __shared__ __attribute__((aligned(16))) float ve[kSnakeFwdTile + 16];
+  __shared__ __attribute__((aligned(16))) float vo[kSnakeFwdTile + 16];
+  const int c = blockIdx.y, b = blockIdx.z;
+  const int64_t row = ((int64_t)b * C + c) * T;
+  aa_snake_row<VEC>(x + row, y + row, alpha, beta, tu, td, logscale, c, T, blockIdx.x * nsub * kSnakeFwdTile, nsub, xs, ve, vo);
+}
+
+// Per-item form: rows of pitch T, item b has len[b] <= T valid columns and is computed as a row of that length -- its replicate padding
+// ends at len[b] - 1, tiles at or beyond len[b] do nothing (a workgroup of an empty item returns at once), and nothing at or beyond
+// column len[b] is read or written.  Columns [0, len[b]) are the bits of aa_snake_kernel on the row alone with T = len[b].  The 16-byte
+// path is chosen per ROW (block-uniform): the row's address depends on the pitch, the whole-vector store on len[b] % 4.
+__global__ __launch_bounds__(256) void aa_snake_items_kernel(const float* __restrict__ x, float* __restrict__ y,
+                                                                const float* __restrict__ alpha, const float* __restrict__ beta,
+                                                                Taps12 tu, Taps12 td, int logscale, int C, int T,
+                                                                const int64_t* __restrict__ len, int nsub) {
+  __shared__ __attribute__((aligned(16))) float xs[kSnakeFwdTile + 16];
+  __shared__ __attribute__((aligned(16))) float ve[kSnakeFwdTile + 16];
+  __shared__ __attribute__((aligned(16))) float vo[kSnakeFwdTile + 16];
+  const int c = blockIdx.y, b = blockIdx.z;
+  const int n = (int)min(max(len[b], (int64_t)0), (int64_t)T);      // never past the pitch, whatever the table holds
+  const int first = blockIdx.x * nsub * kSnakeFwdTile;
+  if (first >= n) return;
+  const int64_t row = ((int64_t)b * C + c) * T;
+  const float* xr = x + row;
+  float* yr = y + row;
+  const bool vec = n % 4 == 0 && (reinterpret_cast<uintptr_t>(xr) | reinterpret_cast<uintptr_t>(yr)) % 16 == 0;
+  if (vec) aa_snake_row<true>(xr, yr, alpha, beta, tu, td, logscale, c, n, first, nsub, xs, ve, vo);
+  else aa_snake_row<false>(xr, yr, alpha, beta, tu, td, logscale, c, n, first, nsub, xs, ve, vo);
 }
 
 // ---- backward ------------------------------------------------------------------------------------------------------
@@ -362,7 +392,32 @@ int launch_aa_snake(const float* x, float* y, const float* alpha, const float* b
   return DMEL_OK;
 }
 
+// x, y (B, C, T) with T the row pitch; len: B device int64, item b's valid columns (clamped into [0, T] by the kernel)
+int launch_aa_snake_items(const float* x, float* y, const float* alpha, const float* beta, const float* up_taps_host,
+                          const float* down_taps_host, int logscale, int B, int C, int64_t T, const int64_t* len, hipStream_t s) {
+  DMEL_CHECK_ARG(x && y && alpha && up_taps_host && down_taps_host && len, "aa_snake_items: NULL argument");
+  DMEL_CHECK_ARG(B > 0 && C > 0 && T > 0 && B <= 65535 && C <= 65535 && T < ((int64_t)1 << 30), "aa_snake_items: bad shape");
+  Taps12 tu, td;
+  for (int i = 0; i < 12; ++i) { tu.f[i] = 2.f * up_taps_host[i]; td.f[i] = down_taps_host[i]; }
+  constexpr int nsub = 3;      // as launch_aa_snake
+  constexpr int span = kSnakeFwdTile * nsub;
+  dim3 grid((unsigned)((T + span - 1) / span), (unsigned)C, (unsigned)B);      // sized by the pitch: the lengths stay on the device
+  {
+    ProfScope ps("aa_snake", s, 0.0, 8.0 * (double)B * C * (double)T);
+    hipLaunchKernelGGL(aa_snake_items_kernel, grid, dim3(256), 0, s, x, y, alpha, beta, tu, td, logscale, C, (int)T, len, nsub);
+  }
+  DMEL_HIP(hipGetLastError());
+  return DMEL_OK;
+}
+
 }  // namespace dmel
+
+extern "C" int dmel_aa_snake_items_f32(const float* x, float* y, const float* alpha, const float* beta, const float* up_filter12_host,
+                                       const float* down_filter12_host, int logscale, int B, int C, int64_t T, const int64_t* lengths_dev,
+                                       void* stream) {
+  return dmel::launch_aa_snake_items(x, y, alpha, beta, up_filter12_host, down_filter12_host, logscale, B, C, T, lengths_dev,
+                                     (hipStream_t)stream);
+}
 
 extern "C" int dmel_aa_snake_backward_f32(const float* x, const float* dy, float* dx, const float* alpha, const float* beta,
                                           float* dalpha, float* dbeta, const float* up_filter12_host, const float* down_filter12_host,

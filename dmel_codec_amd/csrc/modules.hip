@@ -2356,10 +2356,12 @@ int pack_up_stage(UpStage& us, const float* w, const float* bias) {
   }
   return DMEL_OK;
 }
-// x (B, Cin, T) -> y (B, Cout, u T)
-int launch_up_stage(const UpStage& us, const float* x, float* y, int B, int64_t T, int precision, hipStream_t st) {
+// x (B, Cin, T) -> y (B, Cout, u T).  in_len (nullable, B device int64): item b's valid input columns; what lies behind them reads as zero
+int launch_up_stage(const UpStage& us, const float* x, float* y, int B, int64_t T, int precision, hipStream_t st,
+                    const int64_t* in_len = nullptr) {
   for (int half = 0; half < 2; ++half) {
     ConvRun r = run_1seg(x, us.Cin, T, y, us.Cout, T * us.u, B);
+    r.seg[0].in_len = in_len;
     r.Tcols = T; r.out_tstride = us.u; r.phase_base = half * (us.u / 2); r.Tout = T * us.u;
     r.precision = precision;
     DMEL_TRY(launch_conv(half == 0 ? us.lo : us.hi, r, st));
@@ -2487,6 +2489,13 @@ extern "C" int dmel_conv_post_f32(const float* x, const float* w_dev, float bias
   DMEL_CHECK_ARG(x && w_dev && y, "conv_post: NULL argument");
   DMEL_CHECK_ARG(act == 0 || act == 2 || act == 3, "conv_post: act must be 0 (none), 2 (tanh) or 3 (clamp to [-1, 1])");
   return launch_conv_post(x, y, w_dev, bias, act == 0 ? ACT_NONE : act == 2 ? ACT_TANH : ACT_CLAMP1, B, C, K, T, (hipStream_t)stream);
+}
+
+extern "C" int dmel_conv_post_items_f32(const float* x, const float* w_dev, float bias, int act, float* y, int B, int C, int K, int64_t T,
+                                        const int64_t* lengths_dev, void* stream) {
+  DMEL_CHECK_ARG(x && w_dev && y && lengths_dev, "conv_post_items: NULL argument");
+  DMEL_CHECK_ARG(act == 0 || act == 2 || act == 3, "conv_post_items: act must be 0 (none), 2 (tanh) or 3 (clamp to [-1, 1])");
+  return launch_conv_post(x, y, w_dev, bias, act == 0 ? ACT_NONE : act == 2 ? ACT_TANH : ACT_CLAMP1, B, C, K, T, (hipStream_t)stream, lengths_dev);
 }
 
 struct dmel_bigvgan {
@@ -2716,16 +2725,47 @@ extern "C" size_t dmel_bigvgan_workspace_bytes(const dmel_bigvgan* m, int B, int
   return bigvgan_plan(m, B, T, nullptr, nullptr);
 }
 
-extern "C" int dmel_bigvgan_forward(const dmel_bigvgan* m, const float* mel, float* audio, int B, int64_t T, void* workspace,
-                                    size_t workspace_bytes, void* stream) {
-  DMEL_CHECK_ARG(m && mel && audio && workspace, "bigvgan_forward: NULL argument");
-  if (!m->ready) { set_error("bigvgan_forward: handle not finalized"); return DMEL_EMISSING; }
-  DMEL_CHECK_ARG(B > 0 && T > 0, "bigvgan_forward: bad shape");
+// The per-stage length tables of the items form live behind the buffers of the plain plan: (num_upsamples + 1) x B int64.
+static size_t bigvgan_items_plan(const dmel_bigvgan* m, int B, int64_t T, void* ws, float* bufs[kBigvganBufs], int64_t** tabs) {
+  const size_t off = bigvgan_plan(m, B, T, ws, bufs);
+  if (tabs) *tabs = reinterpret_cast<int64_t*>(static_cast<char*>(ws) + off);
+  return align_up(off + (size_t)(m->cfg.num_upsamples + 1) * B * sizeof(int64_t), 256);
+}
+
+extern "C" size_t dmel_bigvgan_items_workspace_bytes(const dmel_bigvgan* m, int B, int64_t T) {
+  if (!m || B <= 0 || T <= 0) return 0;
+  return bigvgan_items_plan(m, B, T, nullptr, nullptr, nullptr);
+}
+
+// lengths == nullptr: dmel_bigvgan_forward.  Otherwise dmel_bigvgan_forward_items: the same launches, each told its stage's lengths.
+static int bigvgan_forward_impl(const dmel_bigvgan* m, const float* mel, const int64_t* lengths, float* audio, int B, int64_t T,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = lengths ? "bigvgan_forward_items" : "bigvgan_forward";
+  DMEL_CHECK_ARG(m && mel && audio && workspace, "%s: NULL argument", who);
+  if (!m->ready) { set_error("%s: handle not finalized", who); return DMEL_EMISSING; }
+  DMEL_CHECK_ARG(B > 0 && T > 0, "%s: bad shape", who);
   float* bufs[kBigvganBufs];
-  const size_t need = bigvgan_plan(m, B, T, workspace, bufs);
-  DMEL_CHECK_ARG(workspace_bytes >= need, "bigvgan_forward: workspace too small (%zu < %zu)", workspace_bytes, need);
+  int64_t* tab = nullptr;
+  const size_t need = lengths ? bigvgan_items_plan(m, B, T, workspace, bufs, &tab) : bigvgan_plan(m, B, T, workspace, bufs);
+  DMEL_CHECK_ARG(workspace_bytes >= need, "%s: workspace too small (%zu < %zu)", who, workspace_bytes, need);
   hipStream_t st = (hipStream_t)stream;
   const dmel_bigvgan_config& c = m->cfg;
+  // Items: table i holds every item's length at stage i (lengths[b] * prod(upsample_rates[:i]), clamped into the pitch), and ONE
+  // invariant holds from conv_pre to conv_post: columns at or beyond an item's length hold garbage, and NOTHING READS THEM -- every
+  // convolution's staging turns them into its zero padding (SegRun::in_len), the activations and conv_post take the item forms, and the
+  // epilogues (bias, residual, running sum, 1 / out_div) are column-wise.  So columns [0, length) of an item are, launch by launch, the
+  // bits of a batch of one at T = length, whatever its batch peers hold.
+  if (lengths) {
+    LenScales sc;
+    sc.v[0] = 1;
+    for (int i = 0; i < c.num_upsamples; ++i) sc.v[i + 1] = sc.v[i] * c.upsample_rates[i];
+    DMEL_TRY(launch_length_tables(lengths, tab, B, T, c.num_upsamples + 1, sc, st));
+  }
+  auto len_at = [&](int stage) -> const int64_t* { return lengths ? tab + (size_t)stage * B : nullptr; };
+  auto act = [&](const float* in, float* out, const SnakeP& p, int ch_, int64_t Tc_, const int64_t* len, hipStream_t s_) {
+    if (len) return launch_aa_snake_items(in, out, p.alpha.as<float>(), p.beta.as<float>(), m->taps_up, m->taps_dn, c.snake_logscale, B, ch_, Tc_, len, s_);
+    return launch_aa_snake(in, out, p.alpha.as<float>(), p.beta.as<float>(), m->taps_up, m->taps_dn, c.snake_logscale, B, ch_, Tc_, s_);
+  };
   // "fp32-grade, library's choice": nothing downstream of the vocoder is discrete, so its default is the three-product fp16 split
   // (include/dmel_hip.h); DMEL_PRECISION_FP32_BF16X3 asks for the six-product bf16 split
   const int prec = m->precision == DMEL_PRECISION_FP32 ? DMEL_PRECISION_FP32_F16X2 : m->precision;
@@ -2735,6 +2775,7 @@ extern "C" int dmel_bigvgan_forward(const dmel_bigvgan* m, const float* mel, flo
 
   {  // conv_pre (bigvgan.py:369)
     ConvRun r = run_1seg(mel, c.num_mels, T, x, c.upsample_initial_channel, T, B);
+    r.seg[0].in_len = len_at(0);
     r.precision = prec;
     DMEL_TRY(launch_conv(m->conv_pre, r, st));
   }
@@ -2743,11 +2784,12 @@ extern "C" int dmel_bigvgan_forward(const dmel_bigvgan* m, const float* mel, flo
   for (int i = 0; i < c.num_upsamples; ++i) {
     const UpStage& us = m->ups[i];
     const int64_t Tn = Tc * us.u;
-    DMEL_TRY(launch_up_stage(us, x, xu, B, Tc, prec, st));  // transposed conv as two phase groups (bigvgan.py:371-374)
+    DMEL_TRY(launch_up_stage(us, x, xu, B, Tc, prec, st, len_at(i)));  // transposed conv as two phase groups (bigvgan.py:371-374)
     ch = us.Cout;
     Tc = Tn;
     const int64_t bs = (int64_t)ch * Tc;
     const bool multi = m->multi;
+    const int64_t* len = len_at(i + 1);
     if (multi) {  // fork: the side streams start behind the transposed conv
       DMEL_HIP(hipEventRecord(m->ev_fork, st));
       for (int k = 0; k < dmel_bigvgan::kSide; ++k) DMEL_HIP(hipStreamWaitEvent(m->side[k], m->ev_fork, 0));
@@ -2760,19 +2802,21 @@ extern "C" int dmel_bigvgan_forward(const dmel_bigvgan* m, const float* mel, flo
       // DMEL_FUSE_SNAKE=1: every act -> conv pair as ONE kernel (conv_snake.hip: producer waves compute the activation, consumer waves run
       // the MFMA loop).  Bit-identical to the two-kernel form and measured SLOWER on every vocoder shape (0.54-1.03x,
       // profiles/r03_fused_vs_two_kernels.txt; DESIGN.md section 4 has the probes that explain it), so the two-kernel form stays the
-      // default.  Read per call so that a test can flip it inside one process.
+      // default.  Read per call so that a test can flip it inside one process.  The fused kernel has one row length for the whole batch:
+      // it stands aside for items.
       const char* fuse_env = getenv("DMEL_FUSE_SNAKE");
-      const bool fuse = fuse_env && fuse_env[0] == '1';
+      const bool fuse = fuse_env && fuse_env[0] == '1' && !lengths;
       for (int l = 0; l < 3; ++l) {
         // stagger the branches by one kernel: started together they run snake|snake|snake then conv|conv|conv in lockstep
         // and the VALU-bound activations never meet the matrix-pipe-bound convolutions on a CU
         if (l == 0 && multi && j > 0) DMEL_HIP(hipStreamWaitEvent(sj, m->ev_stag[j - 1], 0));
         if (c.resblock_type == 2) {   // AMPBlock2.forward (bigvgan.py:232-237): xt = a(x); xt = c(xt); x = xt + x
           ConvRun r2 = run_1seg(uj, ch, Tc, l < 2 ? xj : xs, ch, Tc, B);
+          r2.seg[0].in_len = len;
           r2.res = xin; r2.res_bs = bs; r2.res_cs = Tc;
           r2.precision = prec;
           const bool fuse2 = fuse && conv_snake_eligible(ab.c1[l], r2);
-          if (!fuse2) DMEL_TRY(launch_aa_snake(xin, uj, ab.act[l].alpha.as<float>(), ab.act[l].beta.as<float>(), m->taps_up, m->taps_dn, logscale, B, ch, Tc, sj));
+          if (!fuse2) DMEL_TRY(act(xin, uj, ab.act[l], ch, Tc, len, sj));
           if (!fuse2 && l == 0 && multi && j + 1 < c.num_kernels) DMEL_HIP(hipEventRecord(m->ev_stag[j], sj));
           if (l == 2) {
             r2.accumulate = j > 0;
@@ -2791,21 +2835,23 @@ extern "C" int dmel_bigvgan_forward(const dmel_bigvgan* m, const float* mel, flo
           continue;
         }
         ConvRun r1 = run_1seg(uj, ch, Tc, vj, ch, Tc, B);
+        r1.seg[0].in_len = len;
         r1.precision = prec;
         if (fuse && conv_snake_eligible(ab.c1[l], r1)) {       // act -> conv as ONE kernel: the activated tensor never exists in HBM
           r1.seg[0].x = xin;
           DMEL_TRY(launch_conv_snake(ab.c1[l], r1, ab.act[2 * l].alpha.as<float>(), ab.act[2 * l].beta.as<float>(), m->taps_up, m->taps_dn, logscale, sj));
           if (l == 0 && multi && j + 1 < c.num_kernels) DMEL_HIP(hipEventRecord(m->ev_stag[j], sj));
         } else {
-          DMEL_TRY(launch_aa_snake(xin, uj, ab.act[2 * l].alpha.as<float>(), ab.act[2 * l].beta.as<float>(), m->taps_up, m->taps_dn, logscale, B, ch, Tc, sj));
+          DMEL_TRY(act(xin, uj, ab.act[2 * l], ch, Tc, len, sj));
           if (l == 0 && multi && j + 1 < c.num_kernels) DMEL_HIP(hipEventRecord(m->ev_stag[j], sj));
           DMEL_TRY(launch_conv(ab.c1[l], r1, sj));
         }
         ConvRun r2 = run_1seg(uj, ch, Tc, l < 2 ? xj : xs, ch, Tc, B);
+        r2.seg[0].in_len = len;
         r2.res = xin; r2.res_bs = bs; r2.res_cs = Tc;
         r2.precision = prec;
         const bool fuse2 = fuse && conv_snake_eligible(ab.c2[l], r2);
-        if (!fuse2) DMEL_TRY(launch_aa_snake(vj, uj, ab.act[2 * l + 1].alpha.as<float>(), ab.act[2 * l + 1].beta.as<float>(), m->taps_up, m->taps_dn, logscale, B, ch, Tc, sj));
+        if (!fuse2) DMEL_TRY(act(vj, uj, ab.act[2 * l + 1], ch, Tc, len, sj));
         if (l == 2) {
           // xs = ((out_0 + out_1) + out_2) / 3, in the reference's order: block j's last conv runs behind block j-1's
           r2.accumulate = j > 0;
@@ -2831,9 +2877,21 @@ extern "C" int dmel_bigvgan_forward(const dmel_bigvgan* m, const float* mel, flo
     std::swap(x, xs);
   }
   // activation_post, conv_post, tanh | clamp (bigvgan.py:385-391)
-  DMEL_TRY(launch_aa_snake(x, ua, m->act_post.alpha.as<float>(), m->act_post.beta.as<float>(), m->taps_up, m->taps_dn, logscale, B, ch, Tc, st));
+  const int64_t* len_out = len_at(c.num_upsamples);
+  DMEL_TRY(act(x, ua, m->act_post, ch, Tc, len_out, st));
   return launch_conv_post(ua, audio, m->post_w.as<float>(), m->post_bias, c.use_tanh_at_final ? ACT_TANH : ACT_CLAMP1, B, ch, 7,
-                          Tc, st);
+                          Tc, st, len_out);
+}
+
+extern "C" int dmel_bigvgan_forward(const dmel_bigvgan* m, const float* mel, float* audio, int B, int64_t T, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+  return bigvgan_forward_impl(m, mel, nullptr, audio, B, T, workspace, workspace_bytes, stream);
+}
+
+extern "C" int dmel_bigvgan_forward_items(const dmel_bigvgan* m, const float* mel, const int64_t* lengths_dev, float* audio, int B, int64_t T,
+                                          void* workspace, size_t workspace_bytes, void* stream) {
+  DMEL_CHECK_ARG(lengths_dev, "bigvgan_forward_items: NULL lengths");
+  return bigvgan_forward_impl(m, mel, lengths_dev, audio, B, T, workspace, workspace_bytes, stream);
 }
 
 // ---- input gradient through the frozen generator (bigvgan.py:367-393 under autograd, weights frozen as in codec_lit_modules.py:68-72) ----

@@ -25,9 +25,10 @@ int launch_fsq_backward(const float* x, const float* dout, const float* w_in, co
 // h0 (nullable): also store the pre-norm depthwise-conv output (N, C, T) -- the training path keeps it for the LayerNorm backward
 int launch_dwconv_ln(const float* x, float* y, const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b,
                      int N, int C, int64_t T, hipStream_t s, float* h0 = nullptr);
-// act: 2 = tanh, 3 = clamp(-1, 1), else none (values of enum Act)
+// act: 2 = tanh, 3 = clamp(-1, 1), else none (values of enum Act).  len (B device int64, nullable): per-item form -- item b is a row of
+// len[b] <= T columns with its own zero padding behind it; y[b, len[b]:] = 0
 int launch_conv_post(const float* x, float* y, const float* w_dev, float bias, int act, int B, int C, int K, int64_t T,
-                     hipStream_t s);
+                     hipStream_t s, const int64_t* len = nullptr);
 // dx (B, C, T) = conv_post^T(dy * act'(y)): y the saved OUTPUT of launch_conv_post (may be NULL when act is none), same act codes
 int launch_conv_post_bwd(const float* y, const float* dy, float* dx, const float* w_dev, int act, int B, int C, int K, int64_t T,
                          hipStream_t s);
@@ -73,8 +74,18 @@ int launch_shift_lengths(const int64_t* len, int64_t shift, int64_t* out, int n,
 int launch_copy_windows(const float* src, float* dst, int N, int C, int64_t cap, const int32_t* tab, int stride, int i_shift, int i_end,
                         int len_div, int64_t max_cols, int64_t cols_total, hipStream_t st);
 int launch_shift_lengths_items(const int64_t* len, const int32_t* tab, int stride, int i_shift, int64_t* out, int n, hipStream_t st);
+// tab (stages, n) device int64: tab[i][b] = clamp(len[b], 0, T) * scale.v[i] -- per-stage length tables of an up-sampling stack
+struct LenScales {
+  static constexpr int kMax = 9;
+  int64_t v[kMax];
+};
+int launch_length_tables(const int64_t* len, int64_t* tab, int n, int64_t T, int stages, const LenScales& scale, hipStream_t st);
 int launch_aa_snake(const float* x, float* y, const float* alpha, const float* beta, const float* up_taps_host,
                     const float* down_taps_host, int logscale, int B, int C, int64_t T, hipStream_t s);
+// The same over items: T is the row pitch, item b a row of len[b] <= T columns (B device int64) with its own replicate padding; columns at
+// or beyond len[b] are neither read nor written
+int launch_aa_snake_items(const float* x, float* y, const float* alpha, const float* beta, const float* up_taps_host,
+                          const float* down_taps_host, int logscale, int B, int C, int64_t T, const int64_t* len, hipStream_t s);
 // dx of the anti-aliased Snake only (frozen parameters): bit-identical to the dx of the full backward; dx = (dx_act + radd) + racc,
 // both nullable, racc may alias dx
 int launch_aa_snake_bwd_input(const float* x, const float* dy, float* dx, const float* radd, const float* racc, const float* alpha,

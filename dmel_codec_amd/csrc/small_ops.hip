@@ -509,14 +509,22 @@ int launch_resample(const float* x, float* y, const float* bank_dev, int B, int6
 // One output row: a 32-row MFMA tile would be 97 % zeros, so this is a plain reduction over (channel, tap) -- HBM
 // bound (C*T*4 bytes read per item, each input row read once per workgroup through L1).
 constexpr int kPostTile = 1024;
+// ITEMS: item b is a row of n = len[b] <= T columns inside the pitch T.  Taps at or beyond n read as zero (the item's own zero padding;
+// nothing there is loaded), outputs in [n, T) are written as 0, and outputs in [0, n) are the bits of the plain form on the item alone.
+template <bool ITEMS>
 __global__ __launch_bounds__(256) void conv_post_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                         const float* __restrict__ w, float bias, int C, int K, int T,
-                                                        int act) {
+                                                        int act, const int64_t* __restrict__ len) {
   extern __shared__ float wsm[];   // [C][K]
-  for (int i = threadIdx.x; i < C * K; i += 256) wsm[i] = w[i];
-  __syncthreads();
   const int b = blockIdx.y;
   const int t0 = blockIdx.x * kPostTile;
+  const int n = ITEMS ? (int)min(max(len[b], (int64_t)0), (int64_t)T) : T;
+  if (ITEMS && t0 >= n) {          // a tile wholly behind the item's end (block-uniform): zeros, no reduction
+    for (int t = t0 + threadIdx.x; t < min(t0 + kPostTile, T); t += 256) y[(int64_t)b * T + t] = 0.f;
+    return;
+  }
+  for (int i = threadIdx.x; i < C * K; i += 256) wsm[i] = w[i];
+  __syncthreads();
   const float* xb = x + (int64_t)b * C * T;
   const int pad = (K - 1) / 2;
   float acc[4];
@@ -530,25 +538,30 @@ __global__ __launch_bounds__(256) void conv_post_kernel(const float* __restrict_
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int s = tt[e] + k - pad;
-        const float v = (s >= 0 && s < T) ? xr[s] : 0.f;
+        const float v = (s >= 0 && s < n) ? xr[s] : 0.f;
         acc[e] = fmaf(wv, v, acc[e]);
       }
     }
   }
 #pragma unroll
   for (int e = 0; e < 4; ++e)
-    if (tt[e] < T) y[(int64_t)b * T + tt[e]] = act == 2 ? tanhf(acc[e]) : (act == 3 ? fminf(fmaxf(acc[e], -1.f), 1.f) : acc[e]);
+    if (tt[e] < T) {
+      const float v = act == 2 ? tanhf(acc[e]) : (act == 3 ? fminf(fmaxf(acc[e], -1.f), 1.f) : acc[e]);
+      y[(int64_t)b * T + tt[e]] = (!ITEMS || tt[e] < n) ? v : 0.f;
+    }
 }
 
+// len (nullable): B device int64, the per-item form
 int launch_conv_post(const float* x, float* y, const float* w_dev, float bias, int act, int B, int C, int K, int64_t T,
-                     hipStream_t s) {
+                     hipStream_t s, const int64_t* len) {
   DMEL_CHECK_ARG(B > 0 && B <= 65535 && C > 0 && K > 0 && (K % 2) == 1 && T > 0 && T < ((int64_t)1 << 30), "conv_post: bad shape");
   const size_t lds = (size_t)C * K * sizeof(float);
   DMEL_CHECK_ARG(lds <= 48 * 1024, "conv_post: weight table too large");
   dim3 grid((unsigned)((T + kPostTile - 1) / kPostTile), (unsigned)B);
   {
     ProfScope ps("small", s, 0.0, 4.0 * B * (double)T * (C + 1));
-    hipLaunchKernelGGL(conv_post_kernel, grid, dim3(256), lds, s, x, y, w_dev, bias, C, K, (int)T, act);
+    if (len) hipLaunchKernelGGL(conv_post_kernel<true>, grid, dim3(256), lds, s, x, y, w_dev, bias, C, K, (int)T, act, len);
+    else hipLaunchKernelGGL(conv_post_kernel<false>, grid, dim3(256), lds, s, x, y, w_dev, bias, C, K, (int)T, act, len);
   }
   DMEL_HIP(hipGetLastError());
   return DMEL_OK;
@@ -949,6 +962,21 @@ __global__ void shift_lengths_items_kernel(const int64_t* __restrict__ len, cons
 int launch_shift_lengths_items(const int64_t* len, const int32_t* tab, int stride, int i_shift, int64_t* out, int n, hipStream_t st) {
   DMEL_CHECK_ARG(len && tab && out && n > 0 && stride > 0 && i_shift >= 0 && i_shift < stride, "shift_lengths_items: bad argument");
   hipLaunchKernelGGL(shift_lengths_items_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, len, tab, stride, i_shift, out, n);
+  DMEL_HIP(hipGetLastError());
+  return DMEL_OK;
+}
+
+// tab[i * n + b] = clamp(len[b], 0, T) * scale.v[i]: the items' lengths at every stage of an up-sampling stack, made on the device (no host
+// read of the lengths, no synchronisation)
+__global__ void length_tables_kernel(const int64_t* __restrict__ len, int64_t* __restrict__ tab, int n, int64_t T, int stages, LenScales scale) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= n) return;
+  const int64_t l = min(max(len[b], (int64_t)0), T);
+  for (int i = 0; i < stages; ++i) tab[(size_t)i * n + b] = l * scale.v[i];
+}
+int launch_length_tables(const int64_t* len, int64_t* tab, int n, int64_t T, int stages, const LenScales& scale, hipStream_t st) {
+  DMEL_CHECK_ARG(len && tab && n > 0 && T > 0 && stages > 0 && stages <= LenScales::kMax, "length_tables: bad argument");
+  hipLaunchKernelGGL(length_tables_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, len, tab, n, T, stages, scale);
   DMEL_HIP(hipGetLastError());
   return DMEL_OK;
 }

@@ -432,9 +432,12 @@ class VQGAN(nn.Module):
         return z, mask
 
     @torch.no_grad()
-    def decode(self, indices, feature_lengths, return_audios=False, noise: Optional[torch.Tensor] = None):
+    def decode(self, indices, feature_lengths, return_audios=False, noise: Optional[torch.Tensor] = None, item_audio: bool = False):
         """codec_lit_modules.py:468-484.  noise (extension): the Gaussian decoder input the reference draws with
-        torch.randn_like (:473); pass it for reproducible / parity runs."""
+        torch.randn_like (:473); pass it for reproducible / parity runs.  item_audio (extension): False is the reference, which
+        vocodes the PADDED mel, so the tail of a shorter item's audio depends on the padding behind it; True passes
+        feature_lengths * factor to the vocoder as per-item lengths (BigVGAN.forward(x, lengths)): item b's audio is then
+        vocoder(gen_mel[b:b+1, :, :len_b]) whatever its batch peers are, with zeros behind it."""
         if self.decoder is None:
             raise ValueError("Decoder is not loaded")
         feature_lengths = self._lengths(feature_lengths)
@@ -449,6 +452,8 @@ class VQGAN(nn.Module):
         if return_audios:
             if self.vocoder is None:
                 raise ValueError("Vocoder is not loaded")
+            if item_audio:
+                return self.vocoder(gen_mel, lengths=lens), gen_mel
             return self.vocoder(gen_mel), gen_mel
         return gen_mel
 

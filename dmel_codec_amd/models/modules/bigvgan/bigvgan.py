@@ -228,18 +228,68 @@ class BigVGAN(NativeModule):
                 _lib.check(_lib.lib().dmel_bigvgan_enable_input_grad(h, 1), "bigvgan_enable_input_grad")
                 self._input_grad_handle = (h, self._generation)
 
-    def forward(self, x):
+    def forward(self, x, lengths=None):
         """mel (B, num_mels, T) -> audio (B, 1, T * prod(upsample_rates))        (bigvgan.py:367-393)
 
         With grad enabled and a mel that requires grad the call is differentiable with respect to the MEL (waveform-domain losses on
         whatever produced it): dmel_bigvgan_forward_train / dmel_bigvgan_backward_input, same audio bits as the inference path.  The
         vocoder stays frozen, as in the reference (codec_lit_modules.py:68-72): its parameters NEVER receive a gradient, whatever their
         requires_grad says.  Every other call (no grad, a mel that does not require grad, the streaming decoder) runs the inference
-        path."""
+        path.
+
+        lengths (extension; None is the call above, untouched): B mel windows of DIFFERENT lengths in one pass
+        (dmel_bigvgan_forward_items).  x is right-padded to the largest window, lengths[b] <= T is item b's own length, and
+        audio[b, :, :lengths[b] * up] has the bits of forward(x[b:b+1, :, :lengths[b]]) -- every layer sees the item's own end -- with
+        zeros behind it; what x holds at or beyond an item's length is never read.  A sequence of ints or a CPU tensor is checked here
+        (negative, longer than T or not B of them: ValueError before any device call); a CUDA int64 tensor is not read by the host, and
+        the kernels clamp it into [0, T].  Runs without grad; a mel that requires grad is NotImplementedError (the input gradient over
+        items is not built)."""
+        if lengths is not None:
+            lengths = self._check_lengths(lengths, x)
+            if torch.is_grad_enabled() and x.requires_grad:
+                raise NotImplementedError("BigVGAN.forward(x, lengths=...): the input gradient over items is not built; "
+                                          "detach the mel, or call forward per item")
+            with torch.no_grad():
+                return self._forward_items(x, lengths)
         if torch.is_grad_enabled() and x.requires_grad:
             return self._forward_train(x)
         with torch.no_grad():
             return self._forward_infer(x)
+
+    @staticmethod
+    def _check_lengths(lengths, x):
+        """-> a list of B ints (checked against T), or the CUDA int64 tensor itself (shape and dtype checked; never read by the host)"""
+        if x.ndim != 3:
+            raise ValueError(f"expected a (B, num_mels, T) mel, got {tuple(x.shape)}")
+        B, T = x.shape[0], x.shape[2]
+        if torch.is_tensor(lengths) and lengths.is_cuda:
+            if lengths.dtype != torch.int64 or tuple(lengths.shape) != (B,):
+                raise ValueError(f"lengths on the GPU must be ({B},) int64, got {tuple(lengths.shape)} {lengths.dtype}")
+            return lengths
+        if torch.is_tensor(lengths):
+            if lengths.ndim != 1 or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
+                raise ValueError(f"lengths must be a 1-D integer tensor, got {tuple(lengths.shape)} {lengths.dtype}")
+            lengths = lengths.tolist()
+        lengths = list(lengths)
+        if len(lengths) != B or not all(isinstance(n, int) and not isinstance(n, bool) for n in lengths):
+            raise ValueError(f"lengths must be {B} integers (one per item), got {lengths!r}")
+        if any(n < 0 or n > T for n in lengths):
+            raise ValueError(f"lengths must lie in [0, {T}] (the mel has {T} frames), got {lengths!r}")
+        return lengths
+
+    def _forward_items(self, x, lengths):
+        self._check_mel(x)
+        x = x.float().contiguous()
+        B, _, T = x.shape
+        if not torch.is_tensor(lengths):
+            lengths = torch.tensor(lengths, dtype=torch.int64).to(x.device, non_blocking=True)
+        elif lengths.device != x.device:
+            raise ValueError(f"lengths live on {lengths.device}, the mel on {x.device}")
+        L = _lib.lib()
+        with torch.cuda.device(x.device):
+            h = self.native()
+            ws = self._ws.get(L.dmel_bigvgan_items_workspace_bytes(h, B, T), x.device)
+        return torch.ops.dmel_hip.bigvgan_forward_items(h, x, lengths.contiguous(), self._total_up(), ws)
 
     def _check_mel(self, x):
         _lib.require_cuda(x, "mel")

@@ -389,6 +389,19 @@ class EncodeSessions:
         return self.push({slot: torch.empty(shape, dtype=pcm.FORMATS[self.fmt[slot]][1], device=dev)}, final=(slot,))[slot]
 
 
+def pad_windows(wins: List[torch.Tensor]) -> Tuple[torch.Tensor, Optional[List[int]]]:
+    """(C, W_i) windows -> ((n, C, Wmax) batch, None) when every W_i is Wmax, else (the batch with every window right-padded by zeros,
+    [W_0, ..., W_{n-1}]).  The padding is never read: the lengths travel with the batch."""
+    widths = [int(w.shape[-1]) for w in wins]
+    wmax = max(widths)
+    if all(w == wmax for w in widths):
+        return torch.stack(wins).contiguous(), None
+    batch = wins[0].new_zeros((len(wins), wins[0].shape[0], wmax))
+    for i, w in enumerate(wins):
+        batch[i, :, :widths[i]] = w
+    return batch, widths
+
+
 class DecodeSessions:
     """`slots` independent incremental decodes, each with the audio and mel of decode() on its own finished token sequence.
 
@@ -407,8 +420,10 @@ class DecodeSessions:
 
     Per step: the quantiser decode once per group of slots whose token windows have the same length and the same finality, ONE decoder
     WaveNet step over all slots (dmel_wavenet_stream_step_items_layered: every launch of the layered step covers all slots, each with
-    its own column window), and the vocoder once per group of slots whose mel windows have the same length, cropped per slot as
-    StreamingDecoder crops -- in steady state with equal pushes, one call of each.
+    its own column window), and ONE vocoder call over all slots, whatever the lengths of their mel windows: the windows are right-padded
+    into one (n, n_mels, Wmax) batch and passed with their lengths (BigVGAN.forward(x, lengths): every layer sees each item's own end),
+    then cropped per slot as StreamingDecoder crops.  A step whose windows all have one length -- the steady state of equal pushes --
+    makes the plain call, vocoder(x), as it always did.
 
     State: buffers of (L + 1, slots, C, cap) and so on, laid out like StreamingDecoder's, `cap` fixed at construction from
     max_push_tokens (stream_schedule.decode_capacity); each slot has its own origin (the absolute frame in column 0 of ITS rows), its own
@@ -416,7 +431,7 @@ class DecodeSessions:
     grows neither with the length of a stream nor with the number of sessions served over time.
 
     Playback rates belong to SESSIONS, not to the pool: `output_sample_rates` declares the rates replies may leave at,
-    open(output_sample_rate=r) starts one.  After the vocoder groups every such slot's new audio piece is copied behind that slot's
+    open(output_sample_rate=r) starts one.  After the vocoder call every such slot's new audio piece is copied behind that slot's
     resampler tail (the copy the codec-rate path spends on detaching the piece from the vocoder's batch), ONE resample launch converts
     all slots (utils/resample.py: SessionResampler), and a final slot is flushed with its true length.  The slot's audio pieces then
     concatenate to resample(decode() audio, vocoder rate, r), bit for bit, m * up samples no longer; its mel is the unchanged decode()
@@ -424,7 +439,7 @@ class DecodeSessions:
 
     The sample format belongs to a session as well and sizes nothing: open(sample_format="s16") starts a reply whose audio comes back as
     torch.int16 (16-bit signed PCM) of the same shape, the rounding of utils/pcm.py (x 32768, clamp, nearest with ties to even) applied to
-    the float audio the same session would have returned; its mel is unchanged.  After the vocoder groups and the one resample launch,
+    the float audio the same session would have returned; its mel is unchanged.  After the vocoder call and the one resample launch,
     ONE dmel_pcm_convert_items launch takes every s16 slot's new piece -- the crop inside the vocoder's batch, or the slot's resampler
     output -- and writes it into one packed int16 buffer of the step; the tensors returned are views of that buffer (this takes the
     place of the clone that detaches a float piece).  f32 slots of such a step keep their path and their bits.  "s16" with
@@ -676,21 +691,22 @@ class DecodeSessions:
                     codec.decoder.native(), None, b["hist"].data_ptr(), b["skip"].data_ptr(), b["cond"].data_ptr(), b["mel"].data_ptr(),
                     b["scratch"].data_ptr(), S, self.cap, rows(*prev), rows(*nxt), None, 1, (C.c_int64 * S)(*org), _lib.stream_ptr()),
                     "wavenet_stream_step_items_layered")
-            # ---- emit: the mel frames whose vocoder context exists; the vocoder once per group of slots with equal window length
+            # ---- emit: the mel frames whose vocoder context exists; ONE vocoder call over every slot that has a window
             out: Dict[int, Tuple[Optional[torch.Tensor], torch.Tensor]] = {}
-            vgroups: Dict[int, List[int]] = {}
+            members: List[int] = []
             for s, st in steps.items():
                 o = self.origin[s]
                 mel = b["mel"][s, :, st.emit[0] - o:st.emit[1] - o].clone()
                 out[s] = (torch.empty((1, 0) if self.ch[s] == 1 else (0, self.ch[s]), dtype=pcm.FORMATS[self.fmt[s]][1], device=dev)
                           if self.return_audios else None, mel)
                 if st.voc_window[1] > st.voc_window[0]:
-                    vgroups.setdefault(st.voc_window[1] - st.voc_window[0], []).append(s)
+                    members.append(s)
             pieces: Dict[int, torch.Tensor] = {}       # the new audio of the slots that leave at another rate, still in the vocoder's batch
             wire: Dict[int, torch.Tensor] = {}         # the new float audio of the non-f32 and the multi-channel slots, where it lies
-            for _, members in vgroups.items():
+            if members:
                 wins = [b["mel"][s, :, steps[s].voc_window[0] - self.origin[s]:steps[s].voc_window[1] - self.origin[s]] for s in members]
-                wav = codec.vocoder(torch.stack(wins).contiguous())
+                mel_batch, widths = pad_windows(wins)
+                wav = codec.vocoder(mel_batch) if widths is None else codec.vocoder(mel_batch, lengths=widths)
                 for i, s in enumerate(members):
                     st = steps[s]
                     lo = st.voc_window[0]

@@ -9,6 +9,7 @@ is (`anti_alias_activation_cuda.forward`, alias_free_activation/cuda/anti_alias_
     torch.ops.dmel_hip.stft_magnitude(audio, n_fft, win_length, hop_length)                           # + autograd (DFT-as-GEMM backward)
     torch.ops.dmel_hip.wavenet_forward(handle, x, condition?, in_lengths?, out_lengths?, group_repeat, out_channels)
     torch.ops.dmel_hip.bigvgan_forward(handle, mel, total_upsampling)
+    torch.ops.dmel_hip.bigvgan_forward_items(handle, mel, lengths, total_upsampling, workspace)       # windows of different lengths
     torch.ops.dmel_hip.bigvgan_forward_train(handle, mel, total_upsampling, workspace)                # keeps what backward_input needs
     torch.ops.dmel_hip.bigvgan_backward_input(handle, daudio, num_mels, total_upsampling, workspace)  # d loss / d mel, frozen weights
     torch.ops.dmel_hip.conv_transpose1d(x, weight, bias?, stride), conv_post(x, weight, bias, activation)   # + autograd for x only
@@ -584,6 +585,28 @@ def bigvgan_forward(handle: int, mel: Tensor, total_upsampling: int, workspace: 
 
 @bigvgan_forward.register_fake
 def _(handle, mel, total_upsampling, workspace):
+    return mel.new_empty((mel.shape[0], 1, mel.shape[2] * total_upsampling), dtype=torch.float32)
+
+
+@torch.library.custom_op("dmel_hip::bigvgan_forward_items", mutates_args=("workspace",), device_types="cuda")
+def bigvgan_forward_items(handle: int, mel: Tensor, lengths: Tensor, total_upsampling: int, workspace: Tensor) -> Tensor:
+    """dmel_bigvgan_forward_items: mel (B, n_mels, T) windows of different lengths in one pass.  lengths: (B) int64 on mel's device,
+    0 <= lengths[b] <= T (the caller has checked them; they are not read here).  y[b, 0, :lengths[b] * up] has the bits of
+    bigvgan_forward on mel[b:b+1, :, :lengths[b]], the rest of the row is 0.  workspace: caller-owned uint8 scratch of at least
+    dmel_bigvgan_items_workspace_bytes(handle, B, T) bytes."""
+    B, _, T = mel.shape
+    if lengths.dtype != torch.int64 or lengths.device != mel.device or tuple(lengths.shape) != (B,) or not lengths.is_contiguous():
+        raise ValueError(f"lengths must be a contiguous ({B},) int64 tensor on {mel.device}")
+    y = torch.empty(B, 1, T * total_upsampling, dtype=torch.float32, device=mel.device)
+    with torch.cuda.device(mel.device):
+        _lib.check(_lib.lib().dmel_bigvgan_forward_items(handle, mel.data_ptr(), lengths.data_ptr(), y.data_ptr(), B, T,
+                                                         workspace.data_ptr(), workspace.numel(), _lib.stream_ptr()),
+                   "bigvgan_forward_items")
+    return y
+
+
+@bigvgan_forward_items.register_fake
+def _(handle, mel, lengths, total_upsampling, workspace):
     return mel.new_empty((mel.shape[0], 1, mel.shape[2] * total_upsampling), dtype=torch.float32)
 
 

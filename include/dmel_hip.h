@@ -283,6 +283,14 @@ int dmel_collate_peak_f32(const float* const* clips_dev, const int64_t* lengths_
  * ---------------------------------------------------------------------------------------------- */
 int dmel_aa_snake_f32(const float* x, float* y, const float* alpha, const float* beta, const float* up_filter12_host,
                       const float* down_filter12_host, int logscale, int B, int C, int64_t T, void* stream);
+/* The same over ITEMS of different lengths in one launch (extension; the reference pads a batch and activates the padding): x, y
+ * (B, C, T) with T the row PITCH, lengths_dev (B) device int64, 0 <= lengths[b] <= T (clamped into that range on the device).  Item b
+ * is a row of lengths[b] columns: its replicate padding ends at column lengths[b] - 1, y[b, :, :lengths[b]] is BIT-IDENTICAL to
+ * dmel_aa_snake_f32 on x[b:b+1, :, :lengths[b]], and nothing at or beyond column lengths[b] of a row is read or written (an item of
+ * length 0 is left alone).  No host read of the lengths, no synchronisation. */
+int dmel_aa_snake_items_f32(const float* x, float* y, const float* alpha, const float* beta, const float* up_filter12_host,
+                            const float* down_filter12_host, int logscale, int B, int C, int64_t T, const int64_t* lengths_dev,
+                            void* stream);
 /* Backward of dmel_aa_snake_f32 (the reference's fused kernel has none: alias_free_activation/cuda/activation1d.py:29-32;
  * SURVEY.md section 8(f) rank 1, C-ABI row `aa_snake(+_bwd)`): dx (B, C, T), dalpha (C), dbeta (C; NULL exactly when beta is NULL,
  * i.e. Snake, whose single parameter then receives both contributions).  Gradients are with respect to the STORED parameters
@@ -527,6 +535,18 @@ int dmel_bigvgan_set_precision(dmel_bigvgan* m, int precision);   /* DMEL_PRECIS
 /* mel (B, num_mels, T) -> audio (B, 1, T * prod(upsample_rates)) */
 int dmel_bigvgan_forward(const dmel_bigvgan* m, const float* mel, float* audio, int B, int64_t T,
                          void* workspace, size_t workspace_bytes, void* stream);
+/* One pass over mel windows of DIFFERENT lengths (extension: a pool of live sessions whose replies grow by different amounts vocodes
+ * all of them at once).  mel (B, num_mels, T) with T the largest window, lengths_dev (B) device int64, 0 <= lengths[b] <= T (clamped on
+ * the device; never read by the host, no synchronisation).  audio (B, 1, T * up): audio[b, 0, :lengths[b] * up] is BIT-IDENTICAL to
+ * dmel_bigvgan_forward on mel[b:b+1, :, :lengths[b]] -- every layer sees the item's own end: zero padding in the convolutions, replicate
+ * padding in the anti-aliased activations -- and the rest of the row is 0 (an item of length 0: a row of zeros).  What mel holds at or
+ * beyond an item's length is never read (NaN there is harmless).  The launches are those of dmel_bigvgan_forward plus one that expands
+ * the lengths into per-stage tables in the workspace; every precision and both stream settings are served.  The fused act -> conv
+ * kernel (DMEL_FUSE_SNAKE) and the producer / consumer convolution have one length per batch and stand aside.  workspace: at least
+ * dmel_bigvgan_items_workspace_bytes(m, B, T).  Errors (NULL, handle not finalized, bad B / T, workspace too small) write nothing. */
+size_t dmel_bigvgan_items_workspace_bytes(const dmel_bigvgan* m, int B, int64_t T);
+int dmel_bigvgan_forward_items(const dmel_bigvgan* m, const float* mel, const int64_t* lengths_dev, float* audio, int B, int64_t T,
+                               void* workspace, size_t workspace_bytes, void* stream);
 
 /* Input gradient through the FROZEN generator (bigvgan.py:367-393 under autograd; the reference keeps the vocoder's weights frozen,
  * codec_lit_modules.py:68-72): d loss / d mel from d loss / d audio, for waveform-domain losses on the codec's decoder.  No parameter
@@ -620,6 +640,11 @@ void dmel_conv_transpose1d_destroy(dmel_conv_transpose* h);
 int dmel_conv_transpose1d_set_precision(dmel_conv_transpose* h, int precision);   /* DMEL_PRECISION_* */
 int dmel_conv_transpose1d_forward(const dmel_conv_transpose* h, const float* x, float* y, int B, int64_t T, void* stream);
 int dmel_conv_post_f32(const float* x, const float* w_dev, float bias, int act, float* y, int B, int C, int K, int64_t T, void* stream);
+/* dmel_conv_post_f32 over items: T is the row pitch, lengths_dev (B) device int64 in [0, T].  Taps at or beyond lengths[b] read as zero
+ * (the item's own zero padding; x is not read there), y[b, 0, :lengths[b]] is BIT-IDENTICAL to dmel_conv_post_f32 on the item alone and
+ * y[b, 0, lengths[b]:] = 0. */
+int dmel_conv_post_items_f32(const float* x, const float* w_dev, float bias, int act, float* y, int B, int C, int K, int64_t T,
+                             const int64_t* lengths_dev, void* stream);
 /* Backward-data of the two (what autograd runs through F.conv_transpose1d / F.conv1d + tanh | clamp in bigvgan.py:371-374, :386-391):
  *   conv_transpose1d_backward_data: dx[b,ci,q] = sum_co sum_kk W[ci,co,kk] dy[b,co, u q + kk - u/2] (zero outside dy), dy (B, Cout, T * stride)
  *     -> dx (B, Cin, T): a stride-u, 2u-tap convolution of dy on the implicit-GEMM kernel (u strided two-tap segments, two per launch),

@@ -14,6 +14,13 @@ runs only this: S independent replies whose starts are offset by a third of a pu
 (b) by S StreamingDecoder(batch=1) stepped in turn -- what a server could do before the pool existed, so (b) stands for the parent commit.
 Both get the same tokens and noise, are interleaved in one process, and every piece of (a) is checked to equal the piece of (b).
 
+    python tools/bench_stream.py --sessions 16 --ragged [--label NAME] [--out profiles/decode_sessions_ragged.txt]
+
+the same with the pushes an LM server makes: every session pushes its own number of tokens in every step, from a seeded list in
+[chunk / 2, chunk], so the sessions' mel windows have different lengths in (nearly) every step -- one vocoder pass over all of them in a
+pool that has BigVGAN.forward(x, lengths), one pass per group of equal windows in one that has not.  --label names the table (the
+commit measured).
+
     python tools/bench_stream.py --sessions 16 --output-sample-rate 48000,16000 [--steps 40] [--out profiles/sessions_resample.txt]
 
 runs only this: S replies that leave at the given rates (session i at rate i mod len), served (a) by a pool that was told the rates
@@ -102,8 +109,11 @@ def output_rate_section(sr, out):
     print(json.dumps(result))
 
 
-def sessions_section(S, out):
+def sessions_section(S, out, ragged=False, label=""):
+    import random
     chunk, warmup, steps = 64, 6, 40
+    rng = random.Random(11)
+    sizes = [[rng.randint(chunk // 2, chunk) if ragged else chunk for _ in range(S)] for _ in range(steps)]
     pct = lambda v, q: sorted(v)[min(len(v) - 1, int(q * len(v)))]
     gl = torch.Generator().manual_seed(7)
     G, Cn = codec.dmel_groups, codec.decoder.input_channels
@@ -127,7 +137,7 @@ def sessions_section(S, out):
 
     for step in range(steps):
         # the first push of session i is (i % 3) thirds of a push short, so the sessions' frontiers stay a third of a push apart
-        n = [chunk - (i % 3) * (chunk // 3) if step == 0 else chunk for i in range(S)]
+        n = [chunk - (i % 3) * (chunk // 3) if step == 0 and not ragged else sizes[step][i] for i in range(S)]
         got = {}
         for k, fn in ((("pool", run_pool), ("singles", run_singles)) if step % 2 == 0 else (("singles", run_singles), ("pool", run_pool))):
             torch.cuda.synchronize()
@@ -139,16 +149,18 @@ def sessions_section(S, out):
         for i in range(S):
             assert torch.equal(got["pool"][i], got["singles"][i]), f"step {step}, session {i}: the pool's audio differs"
             pos[i] += n[i]
-    audio_s = S * chunk * 4 * 256 / 24000
-    rows, result = [], {"sessions": S, "chunk_tokens": chunk}
+    audio_s = statistics.mean(sum(n) for n in sizes[warmup:]) * 4 * 256 / 24000      # of a steady-state step, all sessions
+    rows, result = [], {"sessions": S, "chunk_tokens": chunk, "ragged": ragged, "label": label}
     for k, v in ms.items():
         med = statistics.median(v)
         result[k] = {"median_ms": round(med, 3), "p10_ms": round(pct(v, 0.1), 3), "p90_ms": round(pct(v, 0.9), 3), "n": len(v),
                      "audio_sec_per_sec": round(audio_s / (med * 1e-3), 1)}
         rows.append(f"{S:8d}  {k:8s}  {med:9.3f}  {pct(v, 0.1):9.3f}  {pct(v, 0.9):9.3f}  {len(v):4d}  {audio_s / (med * 1e-3):10.1f}")
     result["speedup_median"] = round(result["singles"]["median_ms"] / result["pool"]["median_ms"], 3)
-    table = [f"{S} independent decode sessions, {chunk}-token pushes, starts a third of a push apart, 100 mel / 10 groups, BigVGAN base "
-             f"(tools/bench_stream.py --sessions {S})",
+    pushes = f"pushes of {chunk // 2}..{chunk} tokens, another size per session and step (seeded)" if ragged else \
+        f"{chunk}-token pushes, starts a third of a push apart"
+    table = [(f"[{label}] " if label else "") + f"{S} independent decode sessions, {pushes}, 100 mel / 10 groups, BigVGAN base "
+             f"(tools/bench_stream.py --sessions {S}" + (" --ragged)" if ragged else ")"),
              f"wall time of one step of all sessions incl. host synchronisation, {steps - warmup} steady-state steps, the two interleaved in one process, "
              "equal audio checked;",
              "pool = one VQGAN.decode_sessions step; singles = S StreamingDecoder(batch=1) pushed in turn (the parent commit's way)",
@@ -406,7 +418,9 @@ if "--sessions" in sys.argv and "--output-sample-rate" in sys.argv:
 
 if "--sessions" in sys.argv:
     sessions_section(int(arg_after("--sessions")),
-                     arg_after("--out", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "decode_sessions.txt")))
+                     arg_after("--out", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                     "decode_sessions_ragged.txt" if "--ragged" in sys.argv else "decode_sessions.txt")),
+                     "--ragged" in sys.argv, arg_after("--label", ""))
     sys.exit(0)
 
 if "--output-sample-rate" in sys.argv:
