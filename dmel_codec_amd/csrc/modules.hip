@@ -1056,14 +1056,21 @@ int build_convnext(ConvNeXt& cx, const TensorStore& ts, const std::string& p, in
   return DMEL_OK;
 }
 // y = x + gamma * pwconv2(gelu(pwconv1(LN(dwconv(x)))))      x, y: (N, C, T); y may alias x; h1: (N,C,T), h2: (N,4C,T)
-int run_convnext(const ConvNeXt& cx, const float* x, float* y, float* h1, float* h2, int N, int C, int64_t T, hipStream_t st) {
-  DMEL_TRY(launch_dwconv_ln(x, h1, cx.dw_w.as<float>(), cx.dw_b.as<float>(), cx.ln_w.as<float>(), cx.ln_b.as<float>(), N, C, T, st));
+// len (nullable, N / len_div device int64): per-item form -- row n is an item of len[n / len_div] <= T columns.  The depthwise convolution
+// pads each item with its own zeros, the pointwise convolutions are column-local, and h1, h2 and y come out zero behind the item; x is
+// not read there by the depthwise taps or the staging (the residual load of a masked column is discarded, never stored).
+int run_convnext(const ConvNeXt& cx, const float* x, float* y, float* h1, float* h2, int N, int C, int64_t T, hipStream_t st,
+                 const int64_t* len = nullptr, int len_div = 1) {
+  DMEL_TRY(launch_dwconv_ln(x, h1, cx.dw_w.as<float>(), cx.dw_b.as<float>(), cx.ln_w.as<float>(), cx.ln_b.as<float>(), N, C, T, st, nullptr,
+                            len, len_div));
   ConvRun a = run_1seg(h1, C, T, h2, 4 * C, T, N);
   a.act = ACT_GELU;
+  a.seg[0].in_len = len; a.out_len = len; a.len_div = len_div;
   DMEL_TRY(launch_conv(cx.pw1, a, st));
   ConvRun b = run_1seg(h2, 4 * C, T, y, C, T, N);
   b.row_scale = cx.gamma.as<float>();
   b.res = x; b.res_bs = (int64_t)C * T; b.res_cs = T;
+  b.seg[0].in_len = len; b.out_len = len; b.len_div = len_div;
   return launch_conv(cx.pw2, b, st);
 }
 }  // namespace
@@ -1140,6 +1147,14 @@ extern "C" int dmel_convnext_forward(const dmel_convnext* m, const float* x, flo
   DMEL_CHECK_ARG(N > 0 && T > 0 && workspace_bytes >= dmel_convnext_workspace_bytes(m, N, T), "convnext_forward: bad shape or workspace");
   float* h1 = reinterpret_cast<float*>(workspace);
   return run_convnext(m->cx, x, y, h1, h1 + (size_t)N * m->C * T, N, m->C, T, (hipStream_t)stream);
+}
+extern "C" int dmel_convnext_forward_items(const dmel_convnext* m, const float* x, const int64_t* lengths_dev, float* y, int N, int64_t T,
+                                           void* workspace, size_t workspace_bytes, void* stream) {
+  DMEL_CHECK_ARG(m && x && lengths_dev && y && workspace, "convnext_forward_items: NULL argument");
+  if (!m->ready) { set_error("convnext_forward_items: handle not finalized"); return DMEL_EMISSING; }
+  DMEL_CHECK_ARG(N > 0 && T > 0 && workspace_bytes >= dmel_convnext_workspace_bytes(m, N, T), "convnext_forward_items: bad shape or workspace");
+  float* h1 = reinterpret_cast<float*>(workspace);
+  return run_convnext(m->cx, x, y, h1, h1 + (size_t)N * m->C * T, N, m->C, T, (hipStream_t)stream, lengths_dev, 1);
 }
 
 namespace {
@@ -1439,18 +1454,40 @@ extern "C" int dmel_quantizer_encode(const dmel_quantizer* q, const float* z, in
   return dmel_quantizer_encode_ex(q, z, ids, prequant, nullptr, B, T, workspace, workspace_bytes, stream);
 }
 
-extern "C" int dmel_quantizer_encode_ex(const dmel_quantizer* q, const float* z, int32_t* ids, float* prequant, float* latents, int B,
-                                        int64_t T, void* workspace, size_t workspace_bytes, void* stream) {
+// Per-item form of both directions (lengths != nullptr): one launch expands the lengths into a table of nf + 1 stages at the end of the
+// workspace, and every layer sees each item's own end from the row of its stage -- the k2s2 convolutions and the pointwise ones through
+// SegRun::in_len / ConvRun::out_len (columns behind an item staged as zeros, results behind it stored as zeros), the depthwise k = 7
+// convolution and FSQ through their item forms.  Every buffer is therefore zero behind each item after every launch, nothing behind an
+// item's length in the caller's tensor is read, and the columns in front of it go through the same arithmetic, in the same order, as a
+// call on the item alone.
+static size_t quantizer_items_plan(const dmel_quantizer* q, int B, int64_t Tmax, void* ws, float** a, float** b, float** h1, float** h2,
+                                   int64_t** tab) {
+  const size_t off = quantizer_plan(q, B, Tmax, ws, a, b, h1, h2);
+  if (tab) *tab = reinterpret_cast<int64_t*>(static_cast<char*>(ws) + off);
+  return off + align_up((size_t)(q->nf + 1) * B * sizeof(int64_t), 256);
+}
+
+extern "C" size_t dmel_quantizer_items_workspace_bytes(const dmel_quantizer* q, int B, int64_t T) {
+  if (!q || B <= 0 || T <= 0) return 0;
+  return quantizer_items_plan(q, B, T, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+static int quantizer_encode_run(const dmel_quantizer* q, const float* z, const int64_t* lengths, int32_t* ids, float* prequant,
+                                float* latents, int B, int64_t T, void* workspace, size_t workspace_bytes, void* stream) {
   DMEL_CHECK_ARG(q && z && ids && workspace, "quantizer_encode: NULL argument");
   if (!q->ready) { set_error("quantizer_encode: handle not finalized"); return DMEL_EMISSING; }
   int64_t Tq = T;
   for (int i = 0; i < q->nf; ++i) Tq /= 2;
   DMEL_CHECK_ARG(B > 0 && Tq > 0, "quantizer_encode: sequence too short for the downsampling (T=%lld)", (long long)T);
   float *pa, *pb, *h1, *h2;
-  const size_t need = quantizer_plan(q, B, T, workspace, &pa, &pb, &h1, &h2);
+  int64_t* tab = nullptr;
+  const size_t need = lengths ? quantizer_items_plan(q, B, T, workspace, &pa, &pb, &h1, &h2, &tab)
+                              : quantizer_plan(q, B, T, workspace, &pa, &pb, &h1, &h2);
   DMEL_CHECK_ARG(workspace_bytes >= need, "quantizer_encode: workspace too small (%zu < %zu)", workspace_bytes, need);
   hipStream_t st = (hipStream_t)stream;
   const int N = B * q->G, C = q->Cg;
+  if (lengths) DMEL_TRY(launch_stage_lengths(lengths, tab, B, T, q->nf + 1, /*down=*/1, st));      // len, len / 2, len / 4
+  auto len_at = [&](int stage) -> const int64_t* { return lengths ? tab + (size_t)stage * B : nullptr; };
   const float* cur = z;
   int64_t Tc = T;
   float* bufs[2] = {pa, pb};
@@ -1458,31 +1495,50 @@ extern "C" int dmel_quantizer_encode_ex(const dmel_quantizer* q, const float* z,
     const int64_t Tn = Tc / 2;
     float* o = bufs[i & 1];
     ConvRun r;
-    for (int s = 0; s < 2; ++s) { r.seg[s].x = cur; r.seg[s].bstride = (int64_t)C * Tc; r.seg[s].cstride = Tc; r.seg[s].Tin = Tc; }
+    for (int s = 0; s < 2; ++s) {
+      r.seg[s].x = cur; r.seg[s].bstride = (int64_t)C * Tc; r.seg[s].cstride = Tc; r.seg[s].Tin = Tc;
+      r.seg[s].in_len = len_at(i);
+    }
     r.B = N; r.Tcols = Tn; r.y = o; r.y_bs = (int64_t)C * Tn; r.y_cs = Tn; r.Tout = Tn;
+    r.out_len = len_at(i + 1); r.len_div = lengths ? q->G : 1;
     DMEL_TRY(launch_conv(q->down[i], r, st));
-    DMEL_TRY(run_convnext(q->down_cx[i], o, o, h1, h2, N, C, Tn, st));
+    DMEL_TRY(run_convnext(q->down_cx[i], o, o, h1, h2, N, C, Tn, st, len_at(i + 1), lengths ? q->G : 1));
     cur = o;
     Tc = Tn;
   }
   if (latents) DMEL_HIP(hipMemcpyAsync(latents, cur, (size_t)N * C * Tc * sizeof(float), hipMemcpyDeviceToDevice, st));
   // "(b g) f t -> b (g f) t" is a view; FSQ per group (dowmsample_fsq.py:127-132)
-  return launch_fsq_encode(cur, q->w_in.as<float>(), q->b_in.as<float>(), ids, prequant, q->fk, B, q->G, C, Tc, st);
+  return launch_fsq_encode(cur, q->w_in.as<float>(), q->b_in.as<float>(), ids, prequant, q->fk, B, q->G, C, Tc, st, len_at(q->nf));
 }
 
-extern "C" int dmel_quantizer_decode(const dmel_quantizer* q, const int32_t* ids, float* zout, int B, int64_t T4, void* workspace,
-                                     size_t workspace_bytes, void* stream) {
+extern "C" int dmel_quantizer_encode_ex(const dmel_quantizer* q, const float* z, int32_t* ids, float* prequant, float* latents, int B,
+                                        int64_t T, void* workspace, size_t workspace_bytes, void* stream) {
+  return quantizer_encode_run(q, z, nullptr, ids, prequant, latents, B, T, workspace, workspace_bytes, stream);
+}
+
+extern "C" int dmel_quantizer_encode_items(const dmel_quantizer* q, const float* z, const int64_t* lengths_dev, int32_t* ids, int B,
+                                           int64_t T, void* workspace, size_t workspace_bytes, void* stream) {
+  DMEL_CHECK_ARG(lengths_dev, "quantizer_encode_items: NULL lengths");
+  return quantizer_encode_run(q, z, lengths_dev, ids, nullptr, nullptr, B, T, workspace, workspace_bytes, stream);
+}
+
+static int quantizer_decode_run(const dmel_quantizer* q, const int32_t* ids, const int64_t* lengths, float* zout, int B, int64_t T4,
+                                void* workspace, size_t workspace_bytes, void* stream) {
   DMEL_CHECK_ARG(q && ids && zout && workspace, "quantizer_decode: NULL argument");
   if (!q->ready) { set_error("quantizer_decode: handle not finalized"); return DMEL_EMISSING; }
   DMEL_CHECK_ARG(B > 0 && T4 > 0, "quantizer_decode: bad shape");
   int64_t Tfull = T4;
   for (int i = 0; i < q->nf; ++i) Tfull *= 2;
   float *pa, *pb, *h1, *h2;
-  const size_t need = quantizer_plan(q, B, Tfull, workspace, &pa, &pb, &h1, &h2);
+  int64_t* tab = nullptr;
+  const size_t need = lengths ? quantizer_items_plan(q, B, Tfull, workspace, &pa, &pb, &h1, &h2, &tab)
+                              : quantizer_plan(q, B, Tfull, workspace, &pa, &pb, &h1, &h2);
   DMEL_CHECK_ARG(workspace_bytes >= need, "quantizer_decode: workspace too small (%zu < %zu)", workspace_bytes, need);
   hipStream_t st = (hipStream_t)stream;
   const int N = B * q->G, C = q->Cg;
-  DMEL_TRY(launch_fsq_decode(ids, q->w_out.as<float>(), q->b_out.as<float>(), pa, q->fk, B, q->G, C, T4, st));
+  if (lengths) DMEL_TRY(launch_stage_lengths(lengths, tab, B, T4, q->nf + 1, /*down=*/0, st));      // len, 2 len, 4 len
+  auto len_at = [&](int stage) -> const int64_t* { return lengths ? tab + (size_t)stage * B : nullptr; };
+  DMEL_TRY(launch_fsq_decode(ids, q->w_out.as<float>(), q->b_out.as<float>(), pa, q->fk, B, q->G, C, T4, st, len_at(0)));
   const float* cur = pa;
   int64_t Tc = T4;
   float* bufs[2] = {pb, pa};
@@ -1491,12 +1547,24 @@ extern "C" int dmel_quantizer_decode(const dmel_quantizer* q, const int32_t* ids
     float* o = (j == q->nf - 1) ? zout : bufs[j & 1];
     ConvRun r = run_1seg(cur, C, Tc, o, C, Tn, N);
     r.Tcols = Tc; r.out_tstride = 2; r.Tout = Tn;
+    r.seg[0].in_len = len_at(j); r.out_len = len_at(j + 1); r.len_div = lengths ? q->G : 1;      // out_len counts OUTPUT columns (conv_dev.h)
     DMEL_TRY(launch_conv(q->up[j], r, st));
-    DMEL_TRY(run_convnext(q->up_cx[j], o, o, h1, h2, N, C, Tn, st));
+    DMEL_TRY(run_convnext(q->up_cx[j], o, o, h1, h2, N, C, Tn, st, len_at(j + 1), lengths ? q->G : 1));
     cur = o;
     Tc = Tn;
   }
   return DMEL_OK;
+}
+
+extern "C" int dmel_quantizer_decode(const dmel_quantizer* q, const int32_t* ids, float* zout, int B, int64_t T4, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+  return quantizer_decode_run(q, ids, nullptr, zout, B, T4, workspace, workspace_bytes, stream);
+}
+
+extern "C" int dmel_quantizer_decode_items(const dmel_quantizer* q, const int32_t* ids, const int64_t* lengths_dev, float* zout, int B,
+                                           int64_t T4, void* workspace, size_t workspace_bytes, void* stream) {
+  DMEL_CHECK_ARG(lengths_dev, "quantizer_decode_items: NULL lengths");
+  return quantizer_decode_run(q, ids, lengths_dev, zout, B, T4, workspace, workspace_bytes, stream);
 }
 
 // Re-pack every weight image and parameter buffer of a finalized quantiser from device tensors (after an optimiser step).

@@ -13,18 +13,22 @@ struct FsqConst {
 };
 
 int make_fsq_const(FsqConst& k, const int* levels, int n, int prebound);
+// len (B device int64, nullable): per-item form, in tokens, clamped to [0, T4] on the device -- ids / z at or behind item b's count are
+// written as 0 / 0.f, and the z / ids there are not read
 int launch_fsq_encode(const float* z, const float* w_in, const float* b_in, int32_t* ids, float* prequant,
-                      const FsqConst& k, int B, int G, int C, int64_t T4, hipStream_t s);
+                      const FsqConst& k, int B, int G, int C, int64_t T4, hipStream_t s, const int64_t* len = nullptr);
 int launch_fsq_decode(const int32_t* ids, const float* w_out, const float* b_out, float* z, const FsqConst& k, int B,
-                      int G, int C, int64_t T4, hipStream_t s);
+                      int G, int C, int64_t T4, hipStream_t s, const int64_t* len = nullptr);
 // FSQ straight-through backward: dx (B*G, C, T4) from dout (same layout) and the saved FSQ input x; parameter gradients in the
 // handle's packed layouts (w_in (G,D,C), b_in (G,D), w_out (G,C,D), b_out (G,C)); scratch >= 2*B*G*T4*D floats
 int launch_fsq_backward(const float* x, const float* dout, const float* w_in, const float* b_in, const float* w_out, float* dx,
                         float* dw_in, float* db_in, float* dw_out, float* db_out, float* scratch, const FsqConst& k, int B, int G, int C,
                         int64_t T4, hipStream_t s);
 // h0 (nullable): also store the pre-norm depthwise-conv output (N, C, T) -- the training path keeps it for the LayerNorm backward
+// len (N / len_div device int64, nullable): per-item form -- row n has clamp(len[n / len_div], 0, T) columns and its own zero padding
+// behind them; y and h0 are zero there and x is not read there
 int launch_dwconv_ln(const float* x, float* y, const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b,
-                     int N, int C, int64_t T, hipStream_t s, float* h0 = nullptr);
+                     int N, int C, int64_t T, hipStream_t s, float* h0 = nullptr, const int64_t* len = nullptr, int len_div = 1);
 // act: 2 = tanh, 3 = clamp(-1, 1), else none (values of enum Act).  len (B device int64, nullable): per-item form -- item b is a row of
 // len[b] <= T columns with its own zero padding behind it; y[b, len[b]:] = 0
 int launch_conv_post(const float* x, float* y, const float* w_dev, float bias, int act, int B, int C, int K, int64_t T,
@@ -80,6 +84,8 @@ struct LenScales {
   int64_t v[kMax];
 };
 int launch_length_tables(const int64_t* len, int64_t* tab, int n, int64_t T, int stages, const LenScales& scale, hipStream_t st);
+// tab (stages, n) device int64: tab[i][b] = clamp(len[b], 0, T) >> i (down != 0) or << i -- the quantiser's factor-2 stacks
+int launch_stage_lengths(const int64_t* len, int64_t* tab, int n, int64_t T, int stages, int down, hipStream_t st);
 int launch_aa_snake(const float* x, float* y, const float* alpha, const float* beta, const float* up_taps_host,
                     const float* down_taps_host, int logscale, int B, int C, int64_t T, hipStream_t s);
 // The same over items: T is the row pitch, item b a row of len[b] <= T columns (B device int64) with its own replicate padding; columns at

@@ -8,11 +8,15 @@ namespace dmel {
 // firefly.py:386-388 (dwconv, permute, norm).  x, y: (N, C, T).
 constexpr int kDwTile = 32;
 
+// ITEMS: row n is an item of lim = clamp(len[n / len_div], 0, T) columns with its own zero padding behind it: the taps read zero at or
+// behind lim, y and h0 are zero there, and x is never read there (a neighbour's padding, NaN included, is harmless).  Columns in front
+// of lim run the same fmaf chain as the plain kernel on a row of T = lim.  len / len_div are not read by the plain instantiation.
+template <bool ITEMS>
 __global__ __launch_bounds__(256) void dwconv_ln_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                         const float* __restrict__ dw_w, const float* __restrict__ dw_b,
                                                         const float* __restrict__ ln_w, const float* __restrict__ ln_b,
                                                         float* __restrict__ h0 /*nullable: pre-norm output, kept for training*/,
-                                                        int C, int64_t T, float eps) {
+                                                        int C, int64_t T, float eps, const int64_t* __restrict__ len, int len_div) {
   extern __shared__ float sm[];
   float* hbuf = sm;                         // [C][kDwTile+1]
   float* stat = sm + (size_t)C * (kDwTile + 1);  // [2][kDwTile]
@@ -20,16 +24,31 @@ __global__ __launch_bounds__(256) void dwconv_ln_kernel(const float* __restrict_
   const int n = blockIdx.y;
   const int64_t t0 = (int64_t)blockIdx.x * kDwTile;
   const float* xn = x + (int64_t)n * C * T;
+  int64_t lim = T;
+  if constexpr (ITEMS) {
+    lim = min(max(len[n / len_div], (int64_t)0), T);
+    if (t0 >= lim) {      // the whole tile lies behind the item (uniform over the workgroup: in front of the first barrier)
+      for (int idx = tid; idx < C * kDwTile; idx += 256) {
+        const int c = idx / kDwTile, j = idx % kDwTile;
+        const int64_t t = t0 + j;
+        if (t < T) {
+          y[((int64_t)n * C + c) * T + t] = 0.f;
+          if (h0) h0[((int64_t)n * C + c) * T + t] = 0.f;
+        }
+      }
+      return;
+    }
+  }
   for (int idx = tid; idx < C * kDwTile; idx += 256) {
     const int c = idx / kDwTile, j = idx % kDwTile;
     const int64_t t = t0 + j;
     float acc = 0.f;
-    if (t < T) {
+    if (t < lim) {
       acc = dw_b[c];
 #pragma unroll
       for (int k = 0; k < 7; ++k) {
         const int64_t s = t + k - 3;
-        if (s >= 0 && s < T) acc = fmaf(dw_w[c * 7 + k], xn[(int64_t)c * T + s], acc);
+        if (s >= 0 && s < lim) acc = fmaf(dw_w[c * 7 + k], xn[(int64_t)c * T + s], acc);
       }
     }
     hbuf[c * (kDwTile + 1) + j] = acc;
@@ -54,6 +73,11 @@ __global__ __launch_bounds__(256) void dwconv_ln_kernel(const float* __restrict_
     const int c = idx / kDwTile, j = idx % kDwTile;
     const int64_t t = t0 + j;
     if (t < T) {
+      if (ITEMS && t >= lim) {
+        yn[(int64_t)c * T + t] = 0.f;
+        if (h0) h0[((int64_t)n * C + c) * T + t] = 0.f;
+        continue;
+      }
       yn[(int64_t)c * T + t] = (hbuf[c * (kDwTile + 1) + j] - stat[j]) * stat[kDwTile + j] * ln_w[c] + ln_b[c];
       if (h0) h0[((int64_t)n * C + c) * T + t] = hbuf[c * (kDwTile + 1) + j];
     }
@@ -61,14 +85,18 @@ __global__ __launch_bounds__(256) void dwconv_ln_kernel(const float* __restrict_
 }
 
 int launch_dwconv_ln(const float* x, float* y, const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b,
-                     int N, int C, int64_t T, hipStream_t s, float* h0) {
+                     int N, int C, int64_t T, hipStream_t s, float* h0, const int64_t* len, int len_div) {
   DMEL_CHECK_ARG(N > 0 && N <= 65535 && C > 0 && T > 0, "dwconv_ln: bad shape");
+  DMEL_CHECK_ARG(len == nullptr || (len_div > 0 && N % len_div == 0), "dwconv_ln: %d rows are no multiple of len_div = %d", N, len_div);
   const size_t lds = ((size_t)C * (kDwTile + 1) + 2 * kDwTile) * sizeof(float);
   DMEL_CHECK_ARG(lds <= 64 * 1024, "dwconv_ln: %d channels exceed the LDS tile", C);
   dim3 grid((unsigned)((T + kDwTile - 1) / kDwTile), (unsigned)N);
   {
     ProfScope ps("small", s, 0.0, 8.0 * N * C * (double)T);
-    hipLaunchKernelGGL(dwconv_ln_kernel, grid, dim3(256), lds, s, x, y, dw_w, dw_b, ln_w, ln_b, h0, C, T, 1e-6f);
+    if (len)
+      hipLaunchKernelGGL(dwconv_ln_kernel<true>, grid, dim3(256), lds, s, x, y, dw_w, dw_b, ln_w, ln_b, h0, C, T, 1e-6f, len, len_div);
+    else
+      hipLaunchKernelGGL(dwconv_ln_kernel<false>, grid, dim3(256), lds, s, x, y, dw_w, dw_b, ln_w, ln_b, h0, C, T, 1e-6f, len, 1);
   }
   DMEL_HIP(hipGetLastError());
   return DMEL_OK;
@@ -81,17 +109,21 @@ __device__ __forceinline__ float fsq_bound(float z, const FsqConst& k, int j) {
 }
 
 // z: (B*G, C, T4) channel-major rows of group g of item b at row b*G+g.  w_in: (G, D, C), b_in: (G, D).
-// ids: (B, G, T4) int32.  prequant (optional): (G, B, T4, D).
+// ids: (B, G, T4) int32.  prequant (optional): (G, B, T4, D).  len (nullable, B device int64): per-item token counts, clamped to [0, T4].
 __global__ __launch_bounds__(256) void fsq_encode_kernel(const float* __restrict__ z, const float* __restrict__ w_in,
                                                          const float* __restrict__ b_in, int32_t* __restrict__ ids,
                                                          float* __restrict__ prequant, FsqConst k, int B, int G, int C,
-                                                         int64_t T4) {
+                                                         int64_t T4, const int64_t* __restrict__ len) {
   const int64_t total = (int64_t)B * G * T4;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
   const int64_t l = i % T4;
   const int g = (int)((i / T4) % G);
   const int b = (int)(i / (T4 * G));
+  if (len && l >= min(max(len[b], (int64_t)0), T4)) {      // items: behind item b's token count the id is 0 and z is not read
+    ids[i] = 0;
+    return;
+  }
   const float* zr = z + ((int64_t)(b * G + g) * C) * T4 + l;
   float acc[4];
 #pragma unroll
@@ -145,9 +177,10 @@ __global__ __launch_bounds__(256) void fsq_encode_kernel(const float* __restrict
 }
 
 // ids (B, G, T4) -> z (B*G, C, T4):  code_j = (digit_j - hw_j) / hw_j ; z = W_out code + b_out.  w_out: (G, C, D).
+// len (nullable, B device int64): per-item token counts, clamped to [0, T4].
 __global__ __launch_bounds__(256) void fsq_decode_kernel(const int32_t* __restrict__ ids, const float* __restrict__ w_out,
                                                          const float* __restrict__ b_out, float* __restrict__ z, FsqConst k,
-                                                         int B, int G, int C, int64_t T4) {
+                                                         int B, int G, int C, int64_t T4, const int64_t* __restrict__ len) {
   const int64_t total = (int64_t)B * G * C * T4;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
@@ -155,6 +188,10 @@ __global__ __launch_bounds__(256) void fsq_decode_kernel(const int32_t* __restri
   const int c = (int)((i / T4) % C);
   const int64_t bg = i / (T4 * C);
   const int g = (int)(bg % G);
+  if (len && l >= min(max(len[bg / G], (int64_t)0), T4)) {      // items: behind the item's token count z is 0.f and the id is not read
+    z[i] = 0.f;
+    return;
+  }
   const int id = ids[bg * T4 + l];
   float acc = 0.f;
 #pragma unroll
@@ -312,24 +349,24 @@ int make_fsq_const(FsqConst& k, const int* levels, int n, int prebound) {
 }
 
 int launch_fsq_encode(const float* z, const float* w_in, const float* b_in, int32_t* ids, float* prequant,
-                      const FsqConst& k, int B, int G, int C, int64_t T4, hipStream_t s) {
+                      const FsqConst& k, int B, int G, int C, int64_t T4, hipStream_t s, const int64_t* len) {
   const int64_t total = (int64_t)B * G * T4;
   {
     ProfScope ps("small", s, 0.0, 4.0 * B * G * C * (double)T4);
     hipLaunchKernelGGL(fsq_encode_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, z, w_in, b_in, ids,
-                       prequant, k, B, G, C, T4);
+                       prequant, k, B, G, C, T4, len);
   }
   DMEL_HIP(hipGetLastError());
   return DMEL_OK;
 }
 
 int launch_fsq_decode(const int32_t* ids, const float* w_out, const float* b_out, float* z, const FsqConst& k, int B,
-                      int G, int C, int64_t T4, hipStream_t s) {
+                      int G, int C, int64_t T4, hipStream_t s, const int64_t* len) {
   const int64_t total = (int64_t)B * G * C * T4;
   {
     ProfScope ps("small", s, 0.0, 4.0 * (double)total);
     hipLaunchKernelGGL(fsq_decode_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, ids, w_out, b_out, z, k,
-                       B, G, C, T4);
+                       B, G, C, T4, len);
   }
   DMEL_HIP(hipGetLastError());
   return DMEL_OK;
@@ -977,6 +1014,21 @@ __global__ void length_tables_kernel(const int64_t* __restrict__ len, int64_t* _
 int launch_length_tables(const int64_t* len, int64_t* tab, int n, int64_t T, int stages, const LenScales& scale, hipStream_t st) {
   DMEL_CHECK_ARG(len && tab && n > 0 && T > 0 && stages > 0 && stages <= LenScales::kMax, "length_tables: bad argument");
   hipLaunchKernelGGL(length_tables_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, len, tab, n, T, stages, scale);
+  DMEL_HIP(hipGetLastError());
+  return DMEL_OK;
+}
+
+// tab[i * n + b] = clamp(len[b], 0, T) >> i (down) or << i (up): the items' lengths at every stage of the quantiser's factor-2 down- or
+// up-sampling stack.  The floors of the down form are those of the strided convolutions (7 -> 3 -> 1).  One thread per item.
+__global__ void stage_lengths_kernel(const int64_t* __restrict__ len, int64_t* __restrict__ tab, int n, int64_t T, int stages, int down) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= n) return;
+  const int64_t l = min(max(len[b], (int64_t)0), T);
+  for (int i = 0; i < stages; ++i) tab[(size_t)i * n + b] = down ? (l >> i) : (l << i);
+}
+int launch_stage_lengths(const int64_t* len, int64_t* tab, int n, int64_t T, int stages, int down, hipStream_t st) {
+  DMEL_CHECK_ARG(len && tab && n > 0 && T > 0 && stages > 0 && stages <= 31, "stage_lengths: bad argument");
+  hipLaunchKernelGGL(stage_lengths_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, len, tab, n, T, stages, down);
   DMEL_HIP(hipGetLastError());
   return DMEL_OK;
 }

@@ -402,8 +402,8 @@ class VQGAN(nn.Module):
     def encode_sessions(self, slots: int, max_push_samples: int = 7680, sample_rate: Optional[int] = None, sample_rates=()):
         """A pool of `slots` INDEPENDENT incremental encodes served by one streaming step: sessions open, receive their own number of
         samples per step (at most max_push_samples), stall and close on their own -- what streaming_encoder(batch=B), B streams in
-        lockstep, cannot do -- and each one's concatenated ids are the bits of encode() on its own clip.  One STFT launch and one encoder
-        launch per step whatever the number of slots.  sample_rates: the rates sessions may arrive at (a browser's 48 kHz, telephony's
+        lockstep, cannot do -- and each one's concatenated ids are the bits of encode() on its own clip.  One STFT launch, one encoder
+        launch and one quantiser call per step whatever the number of slots and the sizes of their pushes.  sample_rates: the rates sessions may arrive at (a browser's 48 kHz, telephony's
         16 kHz, ...); pool.open(sample_rate=r) then starts a session whose pushes are in samples of rate r and whose ids are the bits of
         encode(clip, len, sample_rate=r), all slots of a step converted by one resample launch.  sample_rate names the codec's own rate
         only (a pool has no rate of its own).  pool.open(sample_format="s16") starts a session fed torch.int16 (16-bit PCM), converted with
@@ -415,12 +415,21 @@ class VQGAN(nn.Module):
 
     # ------------------------------------------------------------------------------ decode side
     @torch.no_grad()
-    def get_quantized_features_from_indices(self, indices, feature_lengths):
-        """codec_lit_modules.py:515-527 -> z (B, G*C, 4*T4), mask (B, 1, 4*T4)"""
+    def get_quantized_features_from_indices(self, indices, feature_lengths, item_features: bool = False):
+        """codec_lit_modules.py:515-527 -> z (B, G*C, 4*T4), mask (B, 1, 4*T4).  item_features (extension): False is the reference,
+        which runs the quantiser's up-sampling stack over the PADDED ids, so the last frames of a shorter item depend on the ids behind
+        it (the depthwise k = 7 convolutions reach three columns across the item's end, per stage); True passes feature_lengths to
+        quantizer.decode as per-item lengths: item b's features are then those of its own ids alone, whatever its batch peers are."""
         feature_lengths = self._lengths(feature_lengths)
         factor = math.prod(self.quantizer.downsample_factor)
         _lib.require_cuda(indices, "indices")
-        z = self.quantizer.decode(indices)
+        if item_features:
+            fl = feature_lengths
+            if torch.is_tensor(fl) and not fl.is_cuda and not (fl.dtype.is_floating_point or fl.dtype == torch.bool):
+                fl = fl.to(torch.int64)
+            z = self.quantizer.decode(indices, lengths=fl)
+        else:
+            z = self.quantizer.decode(indices)
         B, Cc, T = z.shape
         lens = (feature_lengths.to(device=z.device, dtype=torch.int64) * factor).contiguous()
         w = self.quality_projection.weight.detach().reshape(-1).to(z.device, torch.float32).contiguous()
@@ -432,17 +441,20 @@ class VQGAN(nn.Module):
         return z, mask
 
     @torch.no_grad()
-    def decode(self, indices, feature_lengths, return_audios=False, noise: Optional[torch.Tensor] = None, item_audio: bool = False):
+    def decode(self, indices, feature_lengths, return_audios=False, noise: Optional[torch.Tensor] = None, item_audio: bool = False,
+               item_features: bool = False):
         """codec_lit_modules.py:468-484.  noise (extension): the Gaussian decoder input the reference draws with
         torch.randn_like (:473); pass it for reproducible / parity runs.  item_audio (extension): False is the reference, which
         vocodes the PADDED mel, so the tail of a shorter item's audio depends on the padding behind it; True passes
         feature_lengths * factor to the vocoder as per-item lengths (BigVGAN.forward(x, lengths)): item b's audio is then
-        vocoder(gen_mel[b:b+1, :, :len_b]) whatever its batch peers are, with zeros behind it."""
+        vocoder(gen_mel[b:b+1, :, :len_b]) whatever its batch peers are, with zeros behind it.  item_features=True
+        closes the same gap at the quantiser (see get_quantized_features_from_indices): the conditioning of the last frames of a
+        shorter item then no longer depends on the ids behind it."""
         if self.decoder is None:
             raise ValueError("Decoder is not loaded")
         feature_lengths = self._lengths(feature_lengths)
         factor = math.prod(self.quantizer.downsample_factor)
-        z, _ = self.get_quantized_features_from_indices(indices, feature_lengths)
+        z, _ = self.get_quantized_features_from_indices(indices, feature_lengths, item_features=item_features)
         if noise is None:
             noise = torch.randn_like(z)
         elif noise.shape != z.shape:
@@ -473,8 +485,8 @@ class VQGAN(nn.Module):
     def decode_sessions(self, slots: int, max_push_tokens: int = 64, return_audios: bool = True, **options):
         """A pool of `slots` INDEPENDENT incremental decodes served by one streaming step: replies open, grow by their own number of
         tokens per step (at most max_push_tokens), stall and close on their own -- what streaming_decoder(batch=B), B streams in
-        lockstep, cannot do -- and each one's concatenated audio and mel are the bits of decode() on its own ids.  One decoder WaveNet
-        step per pool step whatever the number of slots.  output_sample_rates=(48000, ...): the playback rates replies may leave at;
+        lockstep, cannot do -- and each one's concatenated audio and mel are the bits of decode() on its own ids.  One quantiser call,
+        one decoder WaveNet step and one vocoder call per pool step whatever the number of slots and the sizes of their pushes.  output_sample_rates=(48000, ...): the playback rates replies may leave at;
         pool.open(output_sample_rate=r) then starts a reply whose audio is the bits of resample(decode() audio, vocoder rate, r), all
         slots of a step converted by one resample launch.  overlap_vocoder, graph_chunk_tokens and the pool-wide output_sample_rate are
         NotImplementedError here.  pool.open(sample_format="s16") starts a reply whose audio comes back as torch.int16 (16-bit PCM), all

@@ -142,11 +142,51 @@ class DownsampleFiniteScalarQuantize(NativeModule):
         self._create_native_train(h)
         return h.value
 
+    @staticmethod
+    def _check_lengths(lengths, B: int, T: int, what: str):
+        """-> a list of B ints (checked against T), or the CUDA int64 tensor itself (shape and dtype checked; never read by the host):
+        the rules of BigVGAN._check_lengths"""
+        if torch.is_tensor(lengths) and lengths.is_cuda:
+            if lengths.dtype != torch.int64 or tuple(lengths.shape) != (B,):
+                raise ValueError(f"lengths on the GPU must be ({B},) int64, got {tuple(lengths.shape)} {lengths.dtype}")
+            return lengths
+        if torch.is_tensor(lengths):
+            if lengths.ndim != 1 or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
+                raise ValueError(f"lengths must be a 1-D integer tensor, got {tuple(lengths.shape)} {lengths.dtype}")
+            lengths = lengths.tolist()
+        lengths = list(lengths)
+        if len(lengths) != B or not all(isinstance(n, int) and not isinstance(n, bool) for n in lengths):
+            raise ValueError(f"lengths must be {B} integers (one per item), got {lengths!r}")
+        if any(n < 0 or n > T for n in lengths):
+            raise ValueError(f"lengths must lie in [0, {T}] (the batch has {T} {what}), got {lengths!r}")
+        return lengths
+
+    @staticmethod
+    def _device_lengths(lengths, like: torch.Tensor) -> torch.Tensor:
+        if not torch.is_tensor(lengths):
+            return torch.tensor(lengths, dtype=torch.int64).to(like.device, non_blocking=True)
+        if lengths.device != like.device:
+            raise ValueError(f"lengths live on {lengths.device}, the batch on {like.device}")
+        return lengths.contiguous()
+
     @torch.no_grad()
-    def encode(self, z: torch.Tensor, return_prequant: bool = False, return_latents: bool = False):
-        """z (B*G, C, T) -> indices (B, G, T // prod(factors)) int32      (dowmsample_fsq.py:124-133)"""
-        _lib.require_cuda(z, "z")
+    def encode(self, z: torch.Tensor, return_prequant: bool = False, return_latents: bool = False, lengths=None):
+        """z (B*G, C, T) -> indices (B, G, T // prod(factors)) int32      (dowmsample_fsq.py:124-133)
+
+        lengths (extension; None is the call above): B feature-frame counts, item b being z[b*G:(b+1)*G, :, :lengths[b]] right-padded
+        to T -- a sequence of ints or a CPU integer tensor (checked against B and T before any device call), or a CUDA int64 (B,)
+        tensor (passed through unread, clamped into [0, T] on the device).  indices[b, :, :lengths[b] // 4] then has the bits of
+        encode(z[b*G:(b+1)*G, :, :lengths[b]]) whatever z holds behind the item (it is never read) and whatever its batch peers are;
+        everything behind is 0, and an item of fewer than 4 frames is a row of zeros.  One launch more than the plain call
+        (dmel_quantizer_encode_items).  return_prequant / return_latents are not offered together with lengths."""
         cg = self.input_dim // self.groups
+        if lengths is not None:                            # refused before any device call
+            if return_prequant or return_latents:
+                raise ValueError("return_prequant / return_latents are not offered together with lengths")
+            if z.ndim != 3 or z.shape[1] != cg or z.shape[0] % self.groups:
+                raise ValueError(f"expected (B*{self.groups}, {cg}, T), got {tuple(z.shape)}")
+            lengths = self._check_lengths(lengths, z.shape[0] // self.groups, z.shape[2], "feature frames")
+        _lib.require_cuda(z, "z")
         if z.ndim != 3 or z.shape[1] != cg or z.shape[0] % self.groups:
             raise ValueError(f"expected (B*{self.groups}, {cg}, T), got {tuple(z.shape)}")
         z = z.float().contiguous()
@@ -155,6 +195,16 @@ class DownsampleFiniteScalarQuantize(NativeModule):
         if T4 < 1:
             raise ValueError(f"T={T} is shorter than the downsampling factor")
         ids = torch.empty(B, self.groups, T4, dtype=torch.int32, device=z.device)
+        if lengths is not None:
+            lengths = self._device_lengths(lengths, z)
+            L = _lib.lib()
+            with torch.cuda.device(z.device):
+                h = self.native()
+                _lib.check(L.dmel_quantizer_set_strict(h, int(bool(self.strict_encode))), "quantizer_set_strict")
+                ws = self._ws.get(L.dmel_quantizer_items_workspace_bytes(h, B, T), z.device)
+                _lib.check(L.dmel_quantizer_encode_items(h, z.data_ptr(), lengths.data_ptr(), ids.data_ptr(), B, T, ws.data_ptr(),
+                                                         ws.numel(), _lib.stream_ptr()), "quantizer_encode_items")
+            return ids
         pre = torch.empty(self.groups, B, T4, len(self.levels), dtype=torch.float32, device=z.device) if return_prequant else None
         L = _lib.lib()
         with torch.cuda.device(z.device):
@@ -168,8 +218,17 @@ class DownsampleFiniteScalarQuantize(NativeModule):
         return out if len(out) > 1 else ids
 
     @torch.no_grad()
-    def decode(self, indices: torch.Tensor) -> torch.Tensor:
-        """indices (B, G, L) -> z (B, G*C, L * prod(factors))             (dowmsample_fsq.py:135-147)"""
+    def decode(self, indices: torch.Tensor, lengths=None) -> torch.Tensor:
+        """indices (B, G, L) -> z (B, G*C, L * prod(factors))             (dowmsample_fsq.py:135-147)
+
+        lengths (extension; None is the call above): B token counts, item b being indices[b, :, :lengths[b]] right-padded to L; the
+        argument is checked as in encode().  z[b, :, :4 * lengths[b]] then has the bits of decode(indices[b:b+1, :, :lengths[b]])
+        whatever ids stand behind the item (they are never read); everything behind is 0, an item of 0 tokens a row of zeros
+        (dmel_quantizer_decode_items)."""
+        if lengths is not None:                            # refused before any device call
+            if indices.ndim != 3 or indices.shape[1] != self.groups:
+                raise ValueError(f"expected (B, {self.groups}, L), got {tuple(indices.shape)}")
+            lengths = self._check_lengths(lengths, indices.shape[0], indices.shape[2], "tokens")
         _lib.require_cuda(indices, "indices")
         if indices.ndim != 3 or indices.shape[1] != self.groups:
             raise ValueError(f"expected (B, {self.groups}, L), got {tuple(indices.shape)}")
@@ -180,6 +239,14 @@ class DownsampleFiniteScalarQuantize(NativeModule):
         z = torch.empty(B, self.input_dim, Tf, dtype=torch.float32, device=ids.device)
         L = _lib.lib()
         del n_codes
+        if lengths is not None:
+            lengths = self._device_lengths(lengths, ids)
+            with torch.cuda.device(ids.device):
+                h = self.native()
+                ws = self._ws.get(L.dmel_quantizer_items_workspace_bytes(h, B, Tf), ids.device)
+                _lib.check(L.dmel_quantizer_decode_items(h, ids.data_ptr(), lengths.data_ptr(), z.data_ptr(), B, T4, ws.data_ptr(),
+                                                         ws.numel(), _lib.stream_ptr()), "quantizer_decode_items")
+            return z
         with torch.cuda.device(ids.device):
             h = self.native()
             ws = self._ws.get(L.dmel_quantizer_workspace_bytes(h, B, Tf), ids.device)

@@ -39,8 +39,11 @@ class EncodeSessions:
     its signal (reflection, zero padding, the floor of T // 4), and frees the slot.  The lookahead of StreamingEncoder applies per slot.
 
     Per step: one STFT launch over the new frames of all slots, one encoder step over the new columns of every level of all slots, and
-    the quantiser once per group of slots whose feature windows have the same length and the same finality (a final slot's window ends at
-    the true end of its signal and must not be right-padded into a longer batch) -- in steady state with equal pushes, one call.
+    ONE quantiser call over all slots with new tokens, whatever the lengths of their feature windows and whether they end or go on: the
+    windows are right-padded into one batch and passed with their lengths (quantizer.encode(z, lengths=): every layer sees each item's
+    own end -- the depthwise k = 7 convolutions of the ConvNeXt blocks pad each item with its own zeros -- so a final slot's window,
+    which ends at the true end of its signal, may sit in a longer batch).  A step whose windows all have one length -- the steady state
+    of equal pushes -- makes the plain call, quantizer.encode(z), as it always did.
 
     State: buffers of (slots * G, C, cap) laid out like StreamingEncoder's, `cap` fixed at construction from `max_push_samples`; each slot
     has its own origin (the absolute frame in column 0 of ITS rows), its own s0 and sample tail; re-basing shifts one slot's columns
@@ -358,21 +361,23 @@ class EncodeSessions:
                                                               b["feat"].data_ptr(), b["scratch"].data_ptr(), S * G, self.cap, rows(*prev),
                                                               rows(*nxt), None, G, I64(*org), _lib.stream_ptr()),
                            "wavenet_stream_step_items")
-            # ---- quantiser: once per group of slots with equal window length and equal finality, cropped per slot
+            # ---- quantiser: ONE call over every slot with new tokens, whatever the lengths of their windows, cropped per slot
             out: Dict[int, torch.Tensor] = {}
-            groups: Dict[tuple, List[int]] = {}
+            members: List[int] = []
             for s, st in steps.items():
                 if st.tokens[1] > st.tokens[0]:
-                    groups.setdefault((st.quant_window[1] - st.quant_window[0], st.final), []).append(s)
+                    members.append(s)
                 else:
                     out[s] = torch.empty(G, 0, dtype=torch.int32, device=dev)
-            for (_, _), members in groups.items():
+            if members:
                 wins = []
                 for s in members:
                     lo, hi = steps[s].quant_window
                     o = self.origin[s]
                     wins.append(b["feat"][s * G:(s + 1) * G, :, lo - o:hi - o])
-                ids = codec.quantizer.encode(torch.cat(wins, dim=0).to(codec.encode_dtype).contiguous())
+                feat, widths = pad_windows(wins)                                  # (n, G, C, Wmax)
+                feat = feat.view(len(members) * G, self.C, -1).to(codec.encode_dtype).contiguous()
+                ids = codec.quantizer.encode(feat) if widths is None else codec.quantizer.encode(feat, lengths=widths)
                 for i, s in enumerate(members):
                     st = steps[s]
                     j = st.quant_window[0] // geo.factor
@@ -391,14 +396,15 @@ class EncodeSessions:
 
 def pad_windows(wins: List[torch.Tensor]) -> Tuple[torch.Tensor, Optional[List[int]]]:
     """(C, W_i) windows -> ((n, C, Wmax) batch, None) when every W_i is Wmax, else (the batch with every window right-padded by zeros,
-    [W_0, ..., W_{n-1}]).  The padding is never read: the lengths travel with the batch."""
+    [W_0, ..., W_{n-1}]).  The padding is never read: the lengths travel with the batch.  Windows with more leading dimensions -- the
+    (G, C, W_i) feature windows of the encode pool -- are padded along the last one in the same way: (n, G, C, Wmax)."""
     widths = [int(w.shape[-1]) for w in wins]
     wmax = max(widths)
     if all(w == wmax for w in widths):
         return torch.stack(wins).contiguous(), None
-    batch = wins[0].new_zeros((len(wins), wins[0].shape[0], wmax))
+    batch = wins[0].new_zeros((len(wins),) + tuple(wins[0].shape[:-1]) + (wmax,))
     for i, w in enumerate(wins):
-        batch[i, :, :widths[i]] = w
+        batch[i, ..., :widths[i]] = w
     return batch, widths
 
 
@@ -418,7 +424,9 @@ class DecodeSessions:
     decoder WaveNet sum(dilations) frames, vocoder receptive_field_frames()).  noise: the decoder's input noise for the pushed frames
     (reproducible runs); a slot without an entry draws its own, as decode() does.
 
-    Per step: the quantiser decode once per group of slots whose token windows have the same length and the same finality, ONE decoder
+    Per step: ONE quantiser decode over all slots with new condition frames, whatever the lengths of their token windows (right-padded
+    into one batch and passed with their lengths: get_quantized_features_from_indices(..., item_features=True); a step whose token
+    windows all have one length makes the plain call), ONE decoder
     WaveNet step over all slots (dmel_wavenet_stream_step_items_layered: every launch of the layered step covers all slots, each with
     its own column window), and ONE vocoder call over all slots, whatever the lengths of their mel windows: the windows are right-padded
     into one (n, n_mels, Wmax) batch and passed with their lengths (BigVGAN.forward(x, lengths): every layer sees each item's own end),
@@ -658,16 +666,18 @@ class DecodeSessions:
                     self.n_noise[s] += n * f
                 steps[s] = st = sch.step(n, s in final)
                 self._rebase(s, st)
-            # ---- quantiser: once per group of slots with equal token-window length and equal finality, cropped per slot
-            groups: Dict[tuple, List[int]] = {}
-            for s, st in steps.items():
-                if st.z[1] > st.z[0]:
-                    groups.setdefault((st.tok_window[1] - st.tok_window[0], st.final), []).append(s)
-            for (width, _), members in groups.items():
+            # ---- quantiser: ONE call over every slot with new condition frames, whatever the lengths of their token windows, cropped per slot
+            members = [s for s, st in steps.items() if st.z[1] > st.z[0]]
+            if members:
                 wins = [b["tokens"][s, :, steps[s].tok_window[0] - self.tok_origin[s]:steps[s].tok_window[1] - self.tok_origin[s]]
                         for s in members]
-                wl = torch.full((len(members),), width, dtype=torch.int64, device=dev)
-                z, _ = codec.get_quantized_features_from_indices(torch.stack(wins).contiguous(), wl)
+                tok_batch, widths = pad_windows(wins)
+                if widths is None:
+                    wl = torch.full((len(members),), tok_batch.shape[-1], dtype=torch.int64, device=dev)
+                    z, _ = codec.get_quantized_features_from_indices(tok_batch, wl)
+                else:
+                    wl = torch.tensor(widths, dtype=torch.int64).to(dev, non_blocking=True)
+                    z, _ = codec.get_quantized_features_from_indices(tok_batch, wl, item_features=True)
                 for i, s in enumerate(members):
                     st, o = steps[s], self.origin[s]
                     lo = st.tok_window[0] * f

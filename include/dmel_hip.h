@@ -449,6 +449,10 @@ int dmel_convnext_finalize(dmel_convnext* m);
 size_t dmel_convnext_workspace_bytes(const dmel_convnext* m, int N, int64_t T);
 int dmel_convnext_forward(const dmel_convnext* m, const float* x, float* y, int N, int64_t T, void* workspace, size_t workspace_bytes,
                           void* stream);
+/* The block over rows of DIFFERENT lengths: lengths_dev (N) device int64; y[n, :, :lengths[n]] is BIT-IDENTICAL to dmel_convnext_forward on
+ * x[n:n+1, :, :lengths[n]] and the rest of the row is 0.  The depthwise convolution never reads x at or behind a row's length. */
+int dmel_convnext_forward_items(const dmel_convnext* m, const float* x, const int64_t* lengths_dev, float* y, int N, int64_t T,
+                                void* workspace, size_t workspace_bytes, void* stream);
 size_t dmel_convnext_train_workspace_bytes(const dmel_convnext* m, int N, int64_t T);
 int64_t dmel_convnext_grad_floats(const dmel_convnext* m);
 int dmel_convnext_grad_slot(const dmel_convnext* m, const char* key, int64_t* offset, int64_t* numel);
@@ -482,6 +486,24 @@ int dmel_quantizer_encode_ex(const dmel_quantizer* q, const float* z, int32_t* i
 /* ids (B, G, T4) -> z (B, G*C, T4*prod(factors)) */
 int dmel_quantizer_decode(const dmel_quantizer* q, const int32_t* ids, float* z, int B, int64_t T4,
                           void* workspace, size_t workspace_bytes, void* stream);
+/* Both directions over items of DIFFERENT lengths (extension: a pool of live sessions whose windows differ quantises all of them at
+ * once).  z (B*G, C, T) / ids (B, G, T4) hold the items right-padded to the largest; lengths_dev (B) is a device int64 array, in feature
+ * frames for encode and in tokens for decode, clamped into [0, T] / [0, T4] on the device (never read by the host, no synchronisation).
+ *   encode_items: ids[b, :, :lengths[b] / 4] is BIT-IDENTICAL to dmel_quantizer_encode on z[b*G:(b+1)*G, :, :lengths[b]], the rest of the
+ *                 row is 0 (an item of fewer than prod(factors) frames: a row of zeros).  Floors as in the strided convolutions: 7 -> 3 -> 1.
+ *   decode_items: z[b, :, :4 * lengths[b]] is BIT-IDENTICAL to dmel_quantizer_decode on ids[b:b+1, :, :lengths[b]], the rest is 0.f.
+ * Every layer sees the item's own end: the depthwise k = 7 convolutions of the ConvNeXt blocks pad each item with its own zeros, the
+ * column-local layers (k2s2 down / up convolutions, pointwise convolutions, FSQ) store zeros behind it.  What z / ids hold at or behind
+ * an item's length is never read (NaN or any code there is harmless).  The launches are those of dmel_quantizer_encode_ex /
+ * dmel_quantizer_decode plus one that expands the lengths into a per-stage table in the workspace (len, len / 2, len / 4 or len, 2 len,
+ * 4 len).  Strict mode (dmel_quantizer_set_strict) applies to encode_items as to encode; prequant / latents are not offered.  workspace:
+ * at least dmel_quantizer_items_workspace_bytes(q, B, T) with T in feature frames (= T4 * prod(factors) for decode).  Errors (NULL, handle
+ * not finalized, bad B / T, workspace too small) write nothing. */
+size_t dmel_quantizer_items_workspace_bytes(const dmel_quantizer* q, int B, int64_t T);
+int dmel_quantizer_encode_items(const dmel_quantizer* q, const float* z, const int64_t* lengths_dev, int32_t* ids, int B, int64_t T,
+                                void* workspace, size_t workspace_bytes, void* stream);
+int dmel_quantizer_decode_items(const dmel_quantizer* q, const int32_t* ids, const int64_t* lengths_dev, float* z, int B, int64_t T4,
+                                void* workspace, size_t workspace_bytes, void* stream);
 /* Training path of the quantiser: DownsampleFiniteScalarQuantize.forward (dowmsample_fsq.py:86-122) with the straight-through FSQ of
  * vector_quantize_pytorch, and its backward.  z (B*G, Cg, T) -> zq (B*G, Cg, T) (= (B, G*Cg, T); zero-padded from 2^nf * T4 back to T
  * with left = diff / 2), ids (B, G, T4) and latents (B*G, Cg, T4) (both nullable).  Same conventions as the WaveNet training entry

@@ -18,8 +18,9 @@ Both get the same tokens and noise, are interleaved in one process, and every pi
 
 the same with the pushes an LM server makes: every session pushes its own number of tokens in every step, from a seeded list in
 [chunk / 2, chunk], so the sessions' mel windows have different lengths in (nearly) every step -- one vocoder pass over all of them in a
-pool that has BigVGAN.forward(x, lengths), one pass per group of equal windows in one that has not.  --label names the table (the
-commit measured).
+pool that has BigVGAN.forward(x, lengths), one pass per group of equal windows in one that has not; the same holds for the token windows
+and the quantiser (quantizer.decode(ids, lengths=)).  Both --sessions forms print the quantiser calls per step of the pool.  --label
+names the table (the commit measured).
 
     python tools/bench_stream.py --sessions 16 --output-sample-rate 48000,16000 [--steps 40] [--out profiles/sessions_resample.txt]
 
@@ -126,9 +127,18 @@ def sessions_section(S, out, ragged=False, label=""):
     pos = [0] * S
     ms = {"pool": [], "singles": []}
 
+    q_calls, q_decode, calls_per_step = [0], codec.quantizer.decode, []      # quantiser calls of the pool's steps (the counter costs a Python call)
+
+    def counted_decode(*a, **kw):
+        q_calls[0] += 1
+        return q_decode(*a, **kw)
+
     def run_pool(n):
+        codec.quantizer.decode, q_calls[0] = counted_decode, 0
         out = pool.push({slots[i]: ids[i, :, pos[i]:pos[i] + n[i]] for i in range(S)},
                         noise={slots[i]: noise[i, :, 4 * pos[i]:4 * (pos[i] + n[i])] for i in range(S)})
+        del codec.quantizer.decode
+        calls_per_step.append(q_calls[0])
         return [out[slots[i]][0] for i in range(S)]
 
     def run_singles(n):
@@ -150,7 +160,8 @@ def sessions_section(S, out, ragged=False, label=""):
             assert torch.equal(got["pool"][i], got["singles"][i]), f"step {step}, session {i}: the pool's audio differs"
             pos[i] += n[i]
     audio_s = statistics.mean(sum(n) for n in sizes[warmup:]) * 4 * 256 / 24000      # of a steady-state step, all sessions
-    rows, result = [], {"sessions": S, "chunk_tokens": chunk, "ragged": ragged, "label": label}
+    rows, result = [], {"sessions": S, "chunk_tokens": chunk, "ragged": ragged, "label": label,
+                        "quantizer_calls_per_step": {"mean": round(statistics.mean(calls_per_step[warmup:]), 2), "max": max(calls_per_step[warmup:])}}
     for k, v in ms.items():
         med = statistics.median(v)
         result[k] = {"median_ms": round(med, 3), "p10_ms": round(pct(v, 0.1), 3), "p90_ms": round(pct(v, 0.9), 3), "n": len(v),
@@ -164,7 +175,9 @@ def sessions_section(S, out, ragged=False, label=""):
              f"wall time of one step of all sessions incl. host synchronisation, {steps - warmup} steady-state steps, the two interleaved in one process, "
              "equal audio checked;",
              "pool = one VQGAN.decode_sessions step; singles = S StreamingDecoder(batch=1) pushed in turn (the parent commit's way)",
-             "sessions  served by  median ms     p10 ms     p90 ms     n  audio-s / s"] + rows + [f"pool / singles: {result['speedup_median']:.3f}x at the median"]
+             "sessions  served by  median ms     p10 ms     p90 ms     n  audio-s / s"] + rows + [
+                 f"pool / singles: {result['speedup_median']:.3f}x at the median",
+                 f"quantiser calls per pool step: mean {result['quantizer_calls_per_step']['mean']:.2f}, max {result['quantizer_calls_per_step']['max']}"]
     os.makedirs(os.path.dirname(out), exist_ok=True)
     with open(out, "a") as f:
         f.write("\n".join(table) + "\n\n")

@@ -22,6 +22,13 @@ whose starts are offset by a third of a push, so that no two frontiers agree, ag
 StreamingEncoder(batch=1) fed the same audio and stepped one after another.  Both run interleaved in one process; a "step" is one push
 for every stream, bracketed by a host synchronisation.  APPENDS its table to --out.
 
+    python tools/bench_stream_encode.py --sessions 16 --ragged [--label NAME] [--out profiles/encode_sessions_ragged.txt]
+
+the same with the pushes live microphones make: every session pushes its own number of samples in every step, from a seeded list in
+[chunk / 2, chunk], so the sessions' feature windows have different lengths in (nearly) every step -- one quantiser call over all of
+them in a pool that has quantizer.encode(z, lengths=), one call per group of equal windows in one that has not.  Both --sessions forms
+print the quantiser calls per step of the pool.  --label names the table (the commit measured).
+
     python tools/bench_stream_encode.py --sessions 16 --sample-rate 48000,16000,44100 [--out profiles/sessions_resample.txt]
 
 times a steady-state step of S sessions that arrive at the given rates (slot s at rate s mod len) in a pool that was told the rates
@@ -64,6 +71,8 @@ ap.add_argument("--sample-format", default="f32", choices=("f32", "s16", "ulaw",
                 help="with --sessions: s16 / G.711 sessions against torch conversions in front")
 ap.add_argument("--channels", type=int, default=1, help="with --sessions: sessions fed interleaved frames of this many channels against the "
                                                         "torch downmix in front")
+ap.add_argument("--ragged", action="store_true", help="with --sessions: another push size per session and step (seeded), chunk / 2 .. chunk")
+ap.add_argument("--label", default="", help="with --sessions: names the table (the commit measured)")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 rates = [int(r) for r in args.sample_rate.split(",")] if args.sample_rate else []
@@ -73,7 +82,8 @@ if args.out is None:
                             "sessions_channels.txt" if args.sessions and args.channels > 1 else
                             "sessions_pcm.txt" if args.sessions and args.sample_format == "s16" else
                             "sessions_g711.txt" if args.sessions and args.sample_format != "f32" else
-                            "sessions_resample.txt" if args.sessions and rates else "stream_sessions.txt" if args.sessions else "stream_resample.txt" if args.sample_rate else "stream_encode.txt")
+                            "sessions_resample.txt" if args.sessions and rates else "encode_sessions_ragged.txt" if args.sessions and args.ragged else
+                            "stream_sessions.txt" if args.sessions else "stream_resample.txt" if args.sample_rate else "stream_encode.txt")
 assert args.pushes - args.warmup >= 50, "medians over at least 50 steady-state pushes"
 SR = 24000
 dev = torch.device("cuda:0")
@@ -143,7 +153,10 @@ def timed_push(enc, chunk, layered):
 
 def sessions_section():
     """S staggered sessions in one pool against S batch-1 encoders stepped in turn; the same audio, the same pushes, equal ids"""
+    import random
     S, n = args.sessions, args.chunk
+    rng = random.Random(11)
+    ragged = [[rng.randint(n // 2, n) for _ in range(S)] for _ in range(args.pushes)]
     audio = torch.randn(S, (args.pushes + 1) * n, device=dev) * 0.1
     pool = codec.encode_sessions(slots=S, max_push_samples=n)
     slots = [pool.open() for _ in range(S)]
@@ -152,8 +165,14 @@ def sessions_section():
     first = [n * (1 + s % 3) // 3 for s in range(S)]            # the starts differ by a third of a push
     ms = {"sessions": [], "one_by_one": []}
     same, tokens = True, 0
+    q_calls, q_encode = [0], codec.quantizer.encode              # quantiser calls of the pool's steps (the counter costs a Python call)
+
+    def counted_encode(*a, **kw):
+        q_calls[0] += 1
+        return q_encode(*a, **kw)
+    calls_per_step = []
     for i in range(args.pushes):
-        size = first if i == 0 else [n] * S
+        size = ragged[i] if args.ragged else first if i == 0 else [n] * S
         chunks = [audio[s, pos[s]:pos[s] + size[s]] for s in range(S)]
         pos = [p + k for p, k in zip(pos, size)]
         got = {}
@@ -161,29 +180,39 @@ def sessions_section():
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             if k == "sessions":
+                codec.quantizer.encode, q_calls[0] = counted_encode, 0
                 ids = pool.push({slots[s]: chunks[s] for s in range(S)})
+                del codec.quantizer.encode
                 got[k] = [ids[slots[s]] for s in range(S)]
             else:
                 got[k] = [singles[s].push(chunks[s][None])[0] for s in range(S)]
             torch.cuda.synchronize()
             if i >= args.warmup:
                 ms[k].append((time.perf_counter() - t0) * 1e3)
+                if k == "sessions":
+                    calls_per_step.append(q_calls[0])
         same = same and all(torch.equal(a, b) for a, b in zip(got["sessions"], got["one_by_one"]))
         tokens += sum(a.shape[1] for a in got["sessions"])
     for s in range(S):
         pool.close(slots[s])
         singles[s].finish()
-    r = {"sessions": S, "chunk_s": n / SR, "pushes": args.pushes, "warmup": args.warmup, "ids_equal": bool(same), "tokens": tokens}
+    r = {"sessions": S, "chunk_s": n / SR, "pushes": args.pushes, "warmup": args.warmup, "ids_equal": bool(same), "tokens": tokens,
+         "ragged": args.ragged, "label": args.label,
+         "quantizer_calls_per_step": {"mean": round(statistics.mean(calls_per_step), 2), "max": max(calls_per_step)}}
     rows = []
+    samples = statistics.mean(sum(v) for v in ragged[args.warmup:]) if args.ragged else S * n      # of a steady-state step, all sessions
     for k, v in ms.items():
         med = statistics.median(v)
         r[k] = {"median_ms": round(med, 3), "p10_ms": round(pct(v, 0.1), 3), "p90_ms": round(pct(v, 0.9), 3), "n": len(v),
-                "audio_s_per_s": round(S * n / SR / (med / 1e3), 1)}
+                "audio_s_per_s": round(samples / SR / (med / 1e3), 1)}
         rows.append(f"{S:8d}  {k:10s}  {med:9.3f}  {pct(v, 0.1):9.3f}  {pct(v, 0.9):9.3f}  {r[k]['audio_s_per_s']:11.1f}  {len(v):4d}")
     r["one_by_one_over_sessions"] = round(r["one_by_one"]["median_ms"] / r["sessions"]["median_ms"], 2)
     rows.append(f"{S:8d}  one pool step is {r['one_by_one_over_sessions']:.2f}x faster than {S} batch-1 pushes in turn; ids equal: {same}")
-    table = [f"independent encode sessions, 0.32 s pushes of 24 kHz audio, starts staggered by a third of a push, 80 mel / 8 groups / 70 channels / "
-             f"20 layers (tools/bench_stream_encode.py --sessions {S})",
+    rows.append(f"{S:8d}  quantiser calls per pool step: mean {r['quantizer_calls_per_step']['mean']:.2f}, max {r['quantizer_calls_per_step']['max']}")
+    pushes = (f"pushes of {n // 2}..{n} samples of 24 kHz audio, another size per session and step (seeded)" if args.ragged else
+              "0.32 s pushes of 24 kHz audio, starts staggered by a third of a push")
+    table = [(f"[{args.label}] " if args.label else "") + f"independent encode sessions, {pushes}, 80 mel / 8 groups / 70 channels / "
+             f"20 layers (tools/bench_stream_encode.py --sessions {S}" + (" --ragged)" if args.ragged else ")"),
              f"wall time of one step (one push for every stream) incl. host synchronisation, {args.pushes - args.warmup} steady-state steps, the two "
              "forms interleaved in one process;",
              "sessions = one VQGAN.encode_sessions pool, one_by_one = that many StreamingEncoder(batch=1) stepped in turn",
