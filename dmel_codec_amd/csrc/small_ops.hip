@@ -1211,3 +1211,98 @@ extern "C" int dmel_pcm_convert_items_ch(const void* const* src, const int32_t* 
   DMEL_HIP(hipGetLastError());
   return DMEL_OK;
 }
+
+namespace dmel {
+
+// ---- fork of streaming state between items of the same buffers (include/dmel_hip.h: dmel_stream_fork_items) --------------------------
+// Row r of the table is (src, dst, lo, hi, first tile); a workgroup owns one tile of kForkTile columns of one channel row -- blockIdx.y
+// runs over the (L + 1) C channel rows of hist, then the C of skip, the Ccond of cond and the Cout of mel -- of the row that owns tile
+// blockIdx.x: the last one whose first tile is not behind it (an idle row owns no tile, so the row behind it starts where it does).
+// The search and the row are uniform over the workgroup.  The 16-byte path is chosen per (row, channel): both addresses depend on the
+// pitch, whole vectors on lo % 4 and hi % 4.  No LDS, no atomics; src and dst are different items, so no element is read and written.
+constexpr int kForkWords = 5, kForkTile = 1024;
+__global__ __launch_bounds__(256) void stream_fork_kernel(float* hist, float* skip, float* cond, float* mel, int L1, int N, int C, int Ccond,
+                                                          int Cout, int64_t cap, const int32_t* __restrict__ tab, int R) {
+  const int tile = blockIdx.x;
+  int a = 0, b = R - 1;
+  while (a < b) {
+    const int mid = (a + b + 1) >> 1;
+    if (tab[(size_t)mid * kForkWords + 4] <= tile) a = mid;
+    else b = mid - 1;
+  }
+  const int32_t* row = tab + (size_t)a * kForkWords;
+  const int src = __builtin_amdgcn_readfirstlane(row[0]), dst = __builtin_amdgcn_readfirstlane(row[1]);
+  const int lo = __builtin_amdgcn_readfirstlane(row[2]), hi = __builtin_amdgcn_readfirstlane(row[3]);
+  const int first = lo + (tile - __builtin_amdgcn_readfirstlane(row[4])) * kForkTile;
+  if (first < lo || first >= hi) return;
+  int j = blockIdx.y;
+  float* base;
+  int64_t so, dn;
+  if (j < L1 * C) {
+    const int lev = j / C, c = j % C;
+    base = hist; so = (((int64_t)lev * N + src) * C + c) * cap; dn = (((int64_t)lev * N + dst) * C + c) * cap;
+  } else if ((j -= L1 * C) < C) {
+    base = skip; so = ((int64_t)src * C + j) * cap; dn = ((int64_t)dst * C + j) * cap;
+  } else if ((j -= C) < Ccond) {
+    base = cond; so = ((int64_t)src * Ccond + j) * cap; dn = ((int64_t)dst * Ccond + j) * cap;
+  } else {
+    j -= Ccond;
+    if (j >= Cout) return;
+    base = mel; so = ((int64_t)src * Cout + j) * cap; dn = ((int64_t)dst * Cout + j) * cap;
+  }
+  const float* s = base + so;
+  float* d = base + dn;
+  const int end = min(hi, first + kForkTile);
+  const bool vec = ((lo | hi) & 3) == 0 && ((reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(d)) & 15) == 0;
+  if (vec) {
+    const int t = first + 4 * (int)threadIdx.x;
+    if (t < end) *reinterpret_cast<float4*>(d + t) = *reinterpret_cast<const float4*>(s + t);
+  } else {
+    for (int t = first + (int)threadIdx.x; t < end; t += 256) d[t] = s[t];
+  }
+}
+
+}  // namespace dmel
+
+extern "C" int dmel_stream_fork_items(float* hist, float* skip, float* cond, float* mel, int L, int N, int C, int Ccond, int Cout, int64_t cap,
+                                      int R, const int64_t* src, const int64_t* dst, const int64_t* lo, const int64_t* hi,
+                                      void* table_scratch, void* stream) {
+  using namespace dmel;
+  DMEL_CHECK_ARG(hist && skip && mel && src && dst && lo && hi && table_scratch, "stream_fork_items: NULL argument");
+  DMEL_CHECK_ARG((Ccond != 0) == (cond != nullptr), "stream_fork_items: the condition tensor is given exactly when Ccond is not 0");
+  DMEL_CHECK_ARG(L >= 0 && N > 0 && N <= 65535 && C > 0 && Ccond >= 0 && Cout > 0 && cap > 0 && cap < ((int64_t)1 << 30) && R > 0 && R <= 65535,
+                 "stream_fork_items: bad shape");
+  const int64_t chan_rows = (int64_t)(L + 2) * C + Ccond + Cout;
+  DMEL_CHECK_ARG(chan_rows <= 65535, "stream_fork_items: %lld channel rows per item exceed 65535", (long long)chan_rows);
+  DMEL_CHECK_ARG(((uintptr_t)table_scratch & 3) == 0, "stream_fork_items: table_scratch is not 4-byte aligned");
+  std::vector<int32_t> tab((size_t)kForkWords * R);
+  std::vector<int> role(N, -1);                       // the row that writes the item; -2: some row reads it
+  int64_t tiles = 0, cols = 0;
+  for (int r = 0; r < R; ++r) {
+    DMEL_CHECK_ARG(src[r] >= 0 && src[r] < N && dst[r] >= 0 && dst[r] < N, "stream_fork_items: row %d: items %lld -> %lld outside [0, %d)", r,
+                   (long long)src[r], (long long)dst[r], N);
+    DMEL_CHECK_ARG(src[r] != dst[r], "stream_fork_items: row %d: item %lld is forked into itself", r, (long long)src[r]);
+    DMEL_CHECK_ARG(lo[r] >= 0 && lo[r] <= hi[r] && hi[r] <= cap, "stream_fork_items: row %d: window [%lld, %lld) outside [0, %lld]", r,
+                   (long long)lo[r], (long long)hi[r], (long long)cap);
+  }
+  for (int r = 0; r < R; ++r) role[src[r]] = -2;
+  for (int r = 0; r < R; ++r) {
+    DMEL_CHECK_ARG(role[dst[r]] == -1, "stream_fork_items: row %d: its destination, item %lld, is %s", r, (long long)dst[r],
+                   role[dst[r]] == -2 ? "the source of a row" : "the destination of another row as well");
+    role[dst[r]] = r;
+    int32_t* it = tab.data() + (size_t)kForkWords * r;
+    it[0] = (int32_t)src[r]; it[1] = (int32_t)dst[r]; it[2] = (int32_t)lo[r]; it[3] = (int32_t)hi[r]; it[4] = (int32_t)tiles;
+    tiles += (hi[r] - lo[r] + kForkTile - 1) / kForkTile;
+    cols += hi[r] - lo[r];
+  }
+  if (tiles == 0) return DMEL_OK;                     // every row idle
+  hipStream_t s = (hipStream_t)stream;
+  DMEL_TRY(launch_table_put(tab.data(), tab.size() * sizeof(int32_t), table_scratch, s));
+  {
+    ProfScope ps("small", s, 0.0, 8.0 * (double)chan_rows * (double)cols), count("stream_fork", s, 0.0, 0.0);
+    hipLaunchKernelGGL(stream_fork_kernel, dim3((unsigned)tiles, (unsigned)chan_rows), dim3(256), 0, s, hist, skip, cond, mel, L + 1, N, C, Ccond,
+                       Cout, cap, static_cast<const int32_t*>(table_scratch), R);
+  }
+  DMEL_HIP(hipGetLastError());
+  return DMEL_OK;
+}

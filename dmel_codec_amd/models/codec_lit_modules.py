@@ -491,7 +491,11 @@ class VQGAN(nn.Module):
         slots of a step converted by one resample launch.  overlap_vocoder, graph_chunk_tokens and the pool-wide output_sample_rate are
         NotImplementedError here.  pool.open(sample_format="s16") starts a reply whose audio comes back as torch.int16 (16-bit PCM), all
         such slots of a step converted by one launch; pool.open(channels=2) starts a reply whose audio comes back as interleaved stereo
-        frames (n, 2), fanned out inside that same launch.  See models/stream_sessions.py: DecodeSessions."""
+        frames (n, 2), fanned out inside that same launch.  early_emit=True: replies may start speaking before their right context has
+        arrived -- pool.open(lookahead_frames=k) starts a reply that hands out every mel frame at most k frames behind the newest
+        one received (k = 0: at once), each piece cut from decode() of the tokens received SO FAR (the last piece from decode() of
+        the whole sequence); such a pool holds a shadow row per slot, and sessions opened without a look-ahead stay exact in it.
+        See models/stream_sessions.py: DecodeSessions."""
         from .stream_sessions import DecodeSessions
         return DecodeSessions(self, slots, max_push_tokens, return_audios, **options)
 

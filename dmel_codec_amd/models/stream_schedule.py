@@ -286,6 +286,83 @@ def decode_session_rows(slots: int, steps: Mapping[int, DecodeStep], origins: Se
     return session_rows(slots, live, origins)
 
 
+@dataclass(frozen=True)
+class EarlyDecodeStep:
+    """One step of a decode session that emits with bounded look-ahead: the committed DecodeStep, untouched, and what is computed on a
+    fork of the committed state (the shadow row) to hand out frames whose right context has not arrived.  Frames are absolute."""
+    step: DecodeStep                  # what the exact schedule does with this push: the committed row runs it as it always did
+    emit: Tuple[int, int]             # mel frames [a, b) handed out now; b may lie ahead of step.next[-1]
+    shadow: bool                      # the emitted frames come from the shadow row (else from the committed one, and nothing is forked)
+    prev: Tuple[int, ...]             # the shadow row: from the committed frontiers in front of this step ...
+    next: Tuple[int, ...]             # ... to `upto` on every level, a final-style row (prev == next: no shadow step)
+    fork: Tuple[int, int]             # columns [lo, hi) the shadow reads from committed state: copied from the committed row
+    tok_window: Tuple[int, int]       # tokens [lo, hi) the quantiser decodes now, for the committed and the shadow row alike
+    z: Tuple[int, int]                # condition / level-0 frames [a, b) written to the shadow row: from the committed frontier to `upto`
+    voc_window: Tuple[int, int]       # mel frames [lo, hi) the vocoder runs on, hi the window's own end (lo == hi: nothing to vocode)
+
+    @property
+    def need_from(self) -> int:
+        return self.step.need_from
+
+    @property
+    def upto(self) -> int:
+        return self.step.upto
+
+
+class EarlyDecodeSchedule:
+    """A DecodeSchedule that hands frames out at most `lookahead` frames behind the newest one received.  The committed counters are a
+    DecodeSchedule's, stepped exactly as an exact session steps them; on top of them `emitted` runs ahead of the last level:
+
+        non-final   emitted -> max(emitted, the exact schedule's frontier, tokens * factor - lookahead)
+        final       emitted -> tokens * factor, from the committed row (its final step is the true end: no shadow)
+
+    When the third term wins, the frames come from the shadow row: a copy of the committed columns [fork) stepped from the committed
+    frontiers to the newest frame on every level, as if the stream ended here.  With lookahead >= geo.hold_frames it never wins:
+    every step is the exact schedule's, range for range.  The columns the shadow and its vocoder window read start at or behind the
+    committed step's need_from, so decode_rebase and decode_capacity hold as they are."""
+
+    def __init__(self, geo: DecodeGeometry, lookahead: int):
+        if int(lookahead) < 0:
+            raise ValueError("lookahead_frames must be >= 0")
+        self.geo, self.lookahead = geo, int(lookahead)
+        self.exact = DecodeSchedule(geo)
+        self.emitted = 0
+
+    @property
+    def tokens(self) -> int:
+        return self.exact.tokens
+
+    @property
+    def finished(self) -> bool:
+        return self.exact.finished
+
+    @property
+    def need_from(self) -> int:
+        return self.exact.need_from
+
+    def step(self, n: int, final: bool = False) -> EarlyDecodeStep:
+        g, ex = self.geo, self.exact
+        z_before = ex.z_valid
+        st = ex.step(n, final)
+        T, e_prev, e_exact = st.upto, self.emitted, st.emit[1]
+        e_new = T if final else max(e_prev, e_exact, T - self.lookahead)
+        shadow = not final and e_new > max(e_prev, e_exact)
+        halo = g.voc_halo
+        idle = (0, 0)
+        if shadow:
+            lo = min([st.prev[l + 1] - d for l, d in enumerate(g.dilations)] + [e_prev - halo])
+            lo = max(0, min(lo, ex.z_valid))
+            row = dict(prev=st.prev, next=(T,) * len(st.prev), fork=(lo, ex.z_valid),
+                       tok_window=(max(0, z_before // g.factor - g.quant_halo_tokens), st.tokens), z=(ex.z_valid, T),
+                       voc_window=(max(0, e_prev - halo), T) if halo else idle)
+        else:
+            ready = st.next[-1]
+            row = dict(prev=st.prev, next=st.prev, fork=idle, tok_window=st.tok_window, z=(ex.z_valid, ex.z_valid),
+                       voc_window=(max(0, e_prev - halo), min(ready, e_new + halo)) if halo and e_new > e_prev else idle)
+        self.emitted = e_new
+        return EarlyDecodeStep(step=st, emit=(e_prev, e_new), shadow=shadow, **row)
+
+
 # ---------------------------------------------------------------------------------------------------- streaming sample-rate conversion
 def resample_width(orig: int, new: int, lowpass_filter_width: int = 6, rolloff: float = 0.99) -> int:
     """half width of the windowed sinc in input samples (orig, new already divided by their gcd): torchaudio's

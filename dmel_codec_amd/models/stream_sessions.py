@@ -20,8 +20,8 @@ import torch
 
 from .. import _lib
 from ..utils import pcm
-from .stream_schedule import (DecodeGeometry, DecodeSchedule, EncodeGeometry, EncodeSchedule, decode_capacity, decode_rebase,
-                              decode_session_rows, resample_max_outputs, session_rows)
+from .stream_schedule import (DecodeGeometry, DecodeSchedule, EarlyDecodeSchedule, EncodeGeometry, EncodeSchedule, decode_capacity,
+                              decode_rebase, resample_max_outputs, session_rows)
 
 _WIRE_DTYPES = {dt for name, (_, dt) in pcm.FORMATS.items() if name != "f32"}     # torch.int16, torch.uint8
 
@@ -411,7 +411,8 @@ def pad_windows(wins: List[torch.Tensor]) -> Tuple[torch.Tensor, Optional[List[i
 class DecodeSessions:
     """`slots` independent incremental decodes, each with the audio and mel of decode() on its own finished token sequence.
 
-        slot = pool.open()                                              # a free slot, fresh state; open(output_sample_rate=48000)
+        slot = pool.open()                                              # a free slot, fresh state; open(output_sample_rate=48000);
+                                                                        # open(lookahead_frames=8) in a pool built with early_emit=True
         out = pool.push({slot: ids (G, n) int, ...}, noise=None | {slot: (C, n * factor)}, final=())
                                                                         # -> {slot: (audio (1, m * up) | None, mel (n_mels, m))}
         out = pool.close(slot)                                          # = push({slot: empty}, final=(slot,))[slot]
@@ -465,6 +466,28 @@ class DecodeSessions:
     their bits.  channels > 1 with return_audios=False is a ValueError at open.  Not served: channel maps, more than 8 channels,
     planar (channel-first) audio, the lockstep StreamingDecoder and whole-clip decode() (callers have utils.pcm.fan_out).
 
+    The look-ahead belongs to a session too.  An exact session hands a frame out once its whole right context exists -- the quantiser's
+    4 tokens, the decoder WaveNet's sum(dilations) frames, the vocoder's halo: about 110 frames, 1.2 s, before a reply's first
+    sample.  A pool built with early_emit=True also serves sessions opened with open(lookahead_frames=k), k >= 0 mel frames: after a
+    push that brings the session to n tokens, T = n * factor frames, it has handed out the frames [0, max(what it had, what the exact
+    schedule has, T - k)), and the piece of the push is cut, bit for bit, from the PREFIX decode
+    decode(ids[:, :n][None], [n], return_audios, noise=the session's noise for those frames) -- the stream as if it ended here.  A
+    final push hands out the rest, cut from decode() of the whole sequence.  So: the pieces tile [0, T_total) without gap or overlap
+    and the total length is decode()'s; a frame that had its full context when it left carries decode()'s bits, one that left earlier
+    carries the bits of the decode of a shorter clip (audio may be provisional -- token ids never are, which is why EncodeSessions has
+    no such option); k = 0 hands out every received frame at once; with k >= geo.hold_frames (k = 10 ** 6) the session IS the exact
+    one, piece for piece, and costs nothing more.  Rate, format and channels consume the float piece as before: the resampler sees
+    the concatenation of the pieces.  return_audios=False works too (mel only).  stream_schedule.EarlyDecodeSchedule has the rule.
+    How: such a pool's state buffers have 2 * slots item rows, row slots + s the SHADOW of slot s.  The committed row of every slot
+    advances exactly as an exact session's.  In a step in which T - k lies ahead of it, the quantiser call of the step -- still ONE,
+    the slot's token window ends at its newest token anyway -- also yields the frames that wait for right context; ONE
+    dmel_stream_fork_items launch copies the committed columns the shadows read (every level's history, the partial skip sums,
+    condition, mel) into the shadow rows; the ONE layered WaveNet step runs over all 2 * slots rows, the shadows as final-style rows
+    from the committed frontiers to T on every level (the fork comes first and the shadow recomputes the few columns the committed
+    row also computes: that keeps the one call); and the ONE vocoder call takes the shadow's window [emitted - halo, T) with its own
+    end.  A step that serves only exact sessions launches what it always did; a pool built without early_emit allocates what it
+    always did, and refuses lookahead_frames at open.  The final step of an early session is the committed row's: no shadow.
+
     Out of scope, NotImplementedError: overlap_vocoder, graph_chunk_tokens, and a pool-wide output_sample_rate (a pool has no rate of
     its own).
 
@@ -475,7 +498,7 @@ class DecodeSessions:
 
     def __init__(self, codec, slots: int, max_push_tokens: int = 64, return_audios: bool = True, overlap_vocoder: bool = False,
                  graph_chunk_tokens: Optional[int] = None, output_sample_rate: Optional[int] = None,
-                 output_sample_rates: Iterable[int] = ()):
+                 output_sample_rates: Iterable[int] = (), early_emit: bool = False):
         if overlap_vocoder or graph_chunk_tokens is not None or output_sample_rate is not None:
             raise NotImplementedError("decode sessions launch everything on the current stream, eagerly, and have no rate of their own: "
                                       "overlap_vocoder, graph_chunk_tokens and output_sample_rate belong to StreamingDecoder (a session's "
@@ -496,6 +519,8 @@ class DecodeSessions:
             raise NotImplementedError("streaming needs a decoder without input projection (input_channels == residual_channels)")
         self.codec, self.S, self.G = codec, int(slots), codec.dmel_groups
         self.return_audios = bool(return_audios)
+        self.early_emit = bool(early_emit)
+        self.N = 2 * self.S if self.early_emit else self.S    # item rows of the state buffers: rows S .. 2 S - 1 are the shadows
         self.L, self.C = len(dec.residual_layers), dec.residual_channels
         cycle = dec.dilation_cycle or 0
         dils = tuple(2 ** (i % cycle) if cycle else 1 for i in range(self.L))
@@ -519,7 +544,7 @@ class DecodeSessions:
         self.rate = [self.voc_rate] * self.S              # the rate the slot's audio leaves at
         self.fmt = ["f32"] * self.S                       # the sample format the slot's audio leaves in (utils/pcm.py: FORMATS)
         self.ch = [1] * self.S                            # the channels the slot's audio leaves with (interleaved frames when above 1)
-        self.sched: List[Optional[DecodeSchedule]] = [None] * self.S
+        self.sched: List[Optional[DecodeSchedule | EarlyDecodeSchedule]] = [None] * self.S
         self.origin = [0] * self.S
         self.tok_origin = [0] * self.S                    # absolute index of the token in column 0 of the slot's token tail
         self.n_noise = [0] * self.S                       # valid frames in the slot's noise tail
@@ -544,12 +569,19 @@ class DecodeSessions:
         self._check_open(slot)
         return self.sched[slot].emitted
 
-    def open(self, output_sample_rate: Optional[int] = None, sample_format: str = "f32", channels: int = 1) -> int:
+    def open(self, output_sample_rate: Optional[int] = None, sample_format: str = "f32", channels: int = 1,
+             lookahead_frames: Optional[int] = None) -> int:
         """take a free slot: fresh schedule, state zeroed before its first push.  output_sample_rate: the rate this session's audio
         leaves at, one of the declared `output_sample_rates` (None: the vocoder's).  sample_format: "f32", "s16" for audio returned
         as torch.int16 (16-bit signed PCM), or "ulaw" / "alaw" for torch.uint8 (G.711 codes).  channels: 1 .. 8; above 1 the audio
-        comes back as interleaved frames (n, channels), every channel the mono audio.  Raises when every slot is taken; a refused
-        open takes no slot."""
+        comes back as interleaved frames (n, channels), every channel the mono audio.  lookahead_frames: None for the exact session;
+        k >= 0 (mel frames) for a session that emits every frame at most k behind the newest one received, on a pool built with
+        early_emit=True.  Raises when every slot is taken; a refused open takes no slot."""
+        if lookahead_frames is not None:
+            if not self.early_emit:
+                raise ValueError("lookahead_frames on a pool built without early_emit=True: it has no shadow rows to decode ahead in")
+            if isinstance(lookahead_frames, bool) or not isinstance(lookahead_frames, int) or lookahead_frames < 0:
+                raise ValueError(f"lookahead_frames must be an integer >= 0 (mel frames) or None, got {lookahead_frames!r}")
         if pcm.check_format(sample_format) != "f32" and not self.return_audios:
             raise ValueError(f"sample_format={sample_format!r} without audio: return_audios=False leaves nothing to convert")
         if pcm._check_channels(channels) > 1 and not self.return_audios:
@@ -560,7 +592,8 @@ class DecodeSessions:
                              f"(declare the rate in output_sample_rates=)")
         for s in range(self.S):
             if self.sched[s] is None:
-                self.sched[s] = DecodeSchedule(self.geo)
+                self.sched[s] = (DecodeSchedule(self.geo) if lookahead_frames is None
+                                 else EarlyDecodeSchedule(self.geo, lookahead_frames))
                 self.origin[s] = self.tok_origin[s] = self.n_noise[s] = 0
                 self.rate[s] = rate
                 self.fmt[s] = sample_format
@@ -604,17 +637,19 @@ class DecodeSessions:
 
     # -- buffers -----------------------------------------------------------------------------------------------------------
     def _allocate(self, dev) -> None:
-        S, dec = self.S, self.codec.decoder
-        rows = S * (2 * (self.L + 1) + 1)
-        self.buf = dict(hist=torch.zeros(self.L + 1, S, self.C, self.cap, dtype=torch.float32, device=dev),
-                        skip=torch.zeros(S, self.C, self.cap, dtype=torch.float32, device=dev),
-                        cond=torch.zeros(S, dec.condition_channels, self.cap, dtype=torch.float32, device=dev),
-                        mel=torch.zeros(S, dec.output_channels, self.cap, dtype=torch.float32, device=dev),
+        S, N, dec = self.S, self.N, self.codec.decoder
+        rows = N * (2 * (self.L + 1) + 1)
+        self.buf = dict(hist=torch.zeros(self.L + 1, N, self.C, self.cap, dtype=torch.float32, device=dev),
+                        skip=torch.zeros(N, self.C, self.cap, dtype=torch.float32, device=dev),
+                        cond=torch.zeros(N, dec.condition_channels, self.cap, dtype=torch.float32, device=dev),
+                        mel=torch.zeros(N, dec.output_channels, self.cap, dtype=torch.float32, device=dev),
                         tokens=torch.zeros(S, self.G, self.tok_width, dtype=torch.int32, device=dev),
                         noise=torch.zeros(S, self.C, self.noise_width, dtype=torch.float32, device=dev),
-                        # dmel_wavenet_stream_step_items_layered: 2 S C cap floats, S int64, and the row table behind them
-                        scratch=torch.empty(2 * S * self.C * self.cap + 2 * S + rows, dtype=torch.float32, device=dev),
+                        # dmel_wavenet_stream_step_items_layered: 2 N C cap floats, N int64, and the row table behind them
+                        scratch=torch.empty(2 * N * self.C * self.cap + 2 * N + rows, dtype=torch.float32, device=dev),
                         pcm_tab=torch.empty(4 * S, dtype=torch.int64, device=dev))
+        if self.early_emit:                           # dmel_stream_fork_items: 5 int32 per fork, at most one fork per slot
+            self.buf["fork_tab"] = torch.empty(5 * S, dtype=torch.int32, device=dev)
 
     def _slot_views(self, s: int):
         b = self.buf
@@ -648,6 +683,7 @@ class DecodeSessions:
                 self.rs.allocate(dev)
         b = self.buf
         steps = {}
+        early = {}                                     # slot -> EarlyDecodeStep of the slots opened with a look-ahead
         with torch.cuda.device(dev):
             for s, t in ids.items():
                 if self._fresh[s]:
@@ -664,13 +700,20 @@ class DecodeSessions:
                         z = torch.randn(self.C, n * f, dtype=torch.float32, device=dev)
                     b["noise"][s, :, self.n_noise[s]:self.n_noise[s] + n * f] = z.to(dev, torch.float32)
                     self.n_noise[s] += n * f
-                steps[s] = st = sch.step(n, s in final)
+                st = sch.step(n, s in final)
+                if isinstance(sch, EarlyDecodeSchedule):
+                    early[s], st = st, st.step         # the committed row runs the exact schedule's step, as an exact slot's does
+                steps[s] = st
                 self._rebase(s, st)
-            # ---- quantiser: ONE call over every slot with new condition frames, whatever the lengths of their token windows, cropped per slot
-            members = [s for s, st in steps.items() if st.z[1] > st.z[0]]
+            shadows = {s: es for s, es in early.items() if es.shadow}
+            # ---- quantiser: ONE call over every slot with new condition frames, whatever the lengths of their token windows, cropped per
+            # slot.  A slot that decodes ahead needs no item of its own: its window ends at its newest token already, so the frames the
+            # committed row leaves waiting for right context are the shadow row's, with the end of the window as their end
+            members = [s for s, st in steps.items() if st.z[1] > st.z[0] or s in shadows]
+            ahead = []                                 # (slot, its row of z): the shadow rows' condition, written behind the fork
             if members:
-                wins = [b["tokens"][s, :, steps[s].tok_window[0] - self.tok_origin[s]:steps[s].tok_window[1] - self.tok_origin[s]]
-                        for s in members]
+                tok_win = {s: shadows[s].tok_window if s in shadows else steps[s].tok_window for s in members}
+                wins = [b["tokens"][s, :, tok_win[s][0] - self.tok_origin[s]:tok_win[s][1] - self.tok_origin[s]] for s in members]
                 tok_batch, widths = pad_windows(wins)
                 if widths is None:
                     wl = torch.full((len(members),), tok_batch.shape[-1], dtype=torch.int64, device=dev)
@@ -680,33 +723,59 @@ class DecodeSessions:
                     z, _ = codec.get_quantized_features_from_indices(tok_batch, wl, item_features=True)
                 for i, s in enumerate(members):
                     st, o = steps[s], self.origin[s]
-                    lo = st.tok_window[0] * f
+                    lo = tok_win[s][0] * f
                     k = st.z[1] - st.z[0]
-                    b["cond"][s, :, st.z[0] - o:st.z[1] - o] = z[i, :, st.z[0] - lo:st.z[1] - lo]
-                    b["hist"][0, s, :, st.z[0] - o:st.z[1] - o] = b["noise"][s, :, :k]
-                    rest = self.n_noise[s] - k
-                    if rest:
-                        b["noise"][s, :, :rest] = b["noise"][s, :, k:k + rest].clone()
-                    self.n_noise[s] = rest
+                    if k:
+                        b["cond"][s, :, st.z[0] - o:st.z[1] - o] = z[i, :, st.z[0] - lo:st.z[1] - lo]
+                        b["hist"][0, s, :, st.z[0] - o:st.z[1] - o] = b["noise"][s, :, :k]
+                        rest = self.n_noise[s] - k
+                        if rest:
+                            b["noise"][s, :, :rest] = b["noise"][s, :, k:k + rest].clone()
+                        self.n_noise[s] = rest
+                    if s in shadows:
+                        ahead.append((s, z[i], lo))
                     drop = st.tok_keep_from - self.tok_origin[s]
                     if drop > 0:
                         keep = st.tokens - st.tok_keep_from
                         b["tokens"][s, :, :keep] = b["tokens"][s, :, drop:drop + keep].clone()
                         self.tok_origin[s] = st.tok_keep_from
             # ---- decoder WaveNet: every level of every slot advances to its own new frontier, in one layered step over all slots
-            if any(st.next != st.prev for st in steps.values()):
-                prev, nxt, org = decode_session_rows(S, steps, self.origin)
-                rows = C.c_int64 * (S * (L + 1))
+            N = self.N
+            live = {s: st for s, st in steps.items() if st.next != st.prev}
+            if shadows:
+                # ---- fork: ONE launch copies, for every slot that decodes ahead, the committed columns its shadow row reads -- every
+                # level's history, the partial skip sums, condition and mel -- into row S + slot.  In front of the committed step, so
+                # that the shadow starts from the frontiers that step starts from and both go through the one call below.  The window
+                # is widened to whole 16-byte vectors: what the copy adds in front is never read, what it adds behind is written next
+                # (condition, level 0) or recomputed by the shadow step (the other levels, skip, mel)
+                I64 = C.c_int64 * len(shadows)
+                lo = [(es.fork[0] - self.origin[s]) // 4 * 4 for s, es in shadows.items()]
+                hi = [(es.fork[1] - self.origin[s] + 3) // 4 * 4 for s, es in shadows.items()]
+                _lib.check(_lib.lib().dmel_stream_fork_items(
+                    b["hist"].data_ptr(), b["skip"].data_ptr(), b["cond"].data_ptr() if b["cond"].shape[1] else None, b["mel"].data_ptr(),
+                    L, N, self.C, b["cond"].shape[1], b["mel"].shape[1], self.cap, len(shadows), I64(*shadows), I64(*[S + s for s in shadows]),
+                    I64(*lo), I64(*hi), b["fork_tab"].data_ptr(), _lib.stream_ptr()), "stream_fork_items")
+                for s, zi, lo_z in ahead:              # behind the committed frontier: the waiting frames, with the waiting noise
+                    es, o = shadows[s], self.origin[s]
+                    b["cond"][S + s, :, es.z[0] - o:es.z[1] - o] = zi[:, es.z[0] - lo_z:es.z[1] - lo_z]
+                    b["hist"][0, S + s, :, es.z[0] - o:es.z[1] - o] = b["noise"][s, :, :es.z[1] - es.z[0]]
+                    live[S + s] = es                   # prev: the committed frontiers, next: the newest frame on every level
+            if live:
+                prev, nxt, org = session_rows(N, live, self.origin * (N // S))
+                rows = C.c_int64 * (N * (L + 1))
                 _lib.check(_lib.lib().dmel_wavenet_stream_step_items_layered(
                     codec.decoder.native(), None, b["hist"].data_ptr(), b["skip"].data_ptr(), b["cond"].data_ptr(), b["mel"].data_ptr(),
-                    b["scratch"].data_ptr(), S, self.cap, rows(*prev), rows(*nxt), None, 1, (C.c_int64 * S)(*org), _lib.stream_ptr()),
+                    b["scratch"].data_ptr(), N, self.cap, rows(*prev), rows(*nxt), None, 1, (C.c_int64 * N)(*org), _lib.stream_ptr()),
                     "wavenet_stream_step_items_layered")
             # ---- emit: the mel frames whose vocoder context exists; ONE vocoder call over every slot that has a window
             out: Dict[int, Tuple[Optional[torch.Tensor], torch.Tensor]] = {}
             members: List[int] = []
+            # a slot with a look-ahead emits by its own rule, from its shadow row when that ran ahead of the committed one
+            steps = {s: early.get(s, st) for s, st in steps.items()}
+            row = {s: S + s if s in shadows else s for s in steps}
             for s, st in steps.items():
                 o = self.origin[s]
-                mel = b["mel"][s, :, st.emit[0] - o:st.emit[1] - o].clone()
+                mel = b["mel"][row[s], :, st.emit[0] - o:st.emit[1] - o].clone()
                 out[s] = (torch.empty((1, 0) if self.ch[s] == 1 else (0, self.ch[s]), dtype=pcm.FORMATS[self.fmt[s]][1], device=dev)
                           if self.return_audios else None, mel)
                 if st.voc_window[1] > st.voc_window[0]:
@@ -714,7 +783,7 @@ class DecodeSessions:
             pieces: Dict[int, torch.Tensor] = {}       # the new audio of the slots that leave at another rate, still in the vocoder's batch
             wire: Dict[int, torch.Tensor] = {}         # the new float audio of the non-f32 and the multi-channel slots, where it lies
             if members:
-                wins = [b["mel"][s, :, steps[s].voc_window[0] - self.origin[s]:steps[s].voc_window[1] - self.origin[s]] for s in members]
+                wins = [b["mel"][row[s], :, steps[s].voc_window[0] - self.origin[s]:steps[s].voc_window[1] - self.origin[s]] for s in members]
                 mel_batch, widths = pad_windows(wins)
                 wav = codec.vocoder(mel_batch) if widths is None else codec.vocoder(mel_batch, lengths=widths)
                 for i, s in enumerate(members):

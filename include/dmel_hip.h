@@ -434,6 +434,20 @@ int dmel_wavenet_stream_step_items_layered(const dmel_wavenet* m, const float* x
                                            const int64_t* next, const int64_t* out_lengths /*nullable*/, int group_repeat,
                                            const int64_t* origin, void* stream);
 
+/* Fork the streaming state of some items into other items of the SAME buffers, in one launch: for every row r of the host tables the
+ * columns [lo[r], hi[r]) of all channels of item src[r] are copied to item dst[r] -- in every level of hist (L + 1, N, C, cap), in
+ * skip (N, C, cap) (its partial sums behind prev[1] are state), in cond (N, Ccond, cap; NULL exactly when Ccond == 0) and in
+ * mel (N, Cout, cap), the y of the step.  A decode session that emits early (models/stream_sessions.py: DecodeSessions) steps such a
+ * copy to the end of what it has received while the item it was copied from keeps the exact frontiers.  Nothing outside the windows of
+ * the dst items is written.  A row with lo == hi is idle.  DMEL_EINVAL, nothing launched, dmel_last_error naming the row: src == dst, a
+ * dst that is another row's src or dst, a window outside [0, cap], an item outside [0, N).  src, dst, lo, hi are HOST tables of R rows,
+ * copied as launch arguments into table_scratch (5 R int32 of device memory, 4-byte aligned): the caller may overwrite them as soon as
+ * the call returns.  The grid covers the columns of the rows' windows, not cap; a (row, channel) whose two addresses are 16-byte
+ * aligned and whose lo and hi are multiples of 4 moves 16 bytes per lane, every other one 4. */
+int dmel_stream_fork_items(float* hist, float* skip, float* cond /*nullable*/, float* mel, int L, int N, int C, int Ccond, int Cout,
+                           int64_t cap, int R, const int64_t* src, const int64_t* dst, const int64_t* lo, const int64_t* hi,
+                           void* table_scratch, void* stream);
+
 /* ConvNeXtBlock (models/modules/firefly.py:337-402; C-ABI row `convnext_block`), standalone: y = x + gamma * pwconv2(gelu(pwconv1(
  * LayerNorm_C(dwconv7(x))))), x / y (N, dim, T).  set_tensor keys: dwconv.weight (dim,1,7), dwconv.bias, norm.weight, norm.bias,
  * pwconv1.weight (4 dim, dim), pwconv1.bias, pwconv2.weight (dim, 4 dim), pwconv2.bias, gamma.  The training entry points follow the

@@ -444,6 +444,29 @@ int main() {
       N[0] = N[1] = 0; SRC[0] = nullptr;          // every item idle: pointers are not looked at, nothing to launch
       CK(conv());
     }
+    {
+      // the state fork: its refusals read the host tables only (R entries each), and a step of idle rows launches nothing
+      const int Lf = 2, Nf = 6, Cf = 5, Cc = 3, Co = 2;
+      const int64_t capf = 96;
+      auto hist = buf((size_t)(Lf + 1) * Nf * Cf * capf), skip = buf((size_t)Nf * Cf * capf), cond = buf((size_t)Nf * Cc * capf), mel = buf((size_t)Nf * Co * capf);
+      std::vector<int32_t> tab(5 * 2);            // exactly the 5 R int32 the header asks for
+      int64_t SRC[2] = {0, 1}, DST[2] = {3, 4}, LO[2] = {0, 4}, HI[2] = {8, 40};
+      auto fork = [&]() {
+        return dmel_stream_fork_items(hist.data(), skip.data(), cond.data(), mel.data(), Lf, Nf, Cf, Cc, Co, capf, 2, SRC, DST, LO, HI, tab.data(), nullptr);
+      };
+      auto refused = [&](const char* what) {
+        const int rc = fork();
+        if (rc != DMEL_EINVAL || !std::strstr(dmel_last_error(), "row 1")) { std::printf("FAIL stream_fork_items accepted %s (%d: %s)\n", what, rc, dmel_last_error()); ++failures; }
+      };
+      DST[1] = 1; refused("a row forked into itself");
+      DST[1] = 3; refused("two rows with one destination");
+      DST[1] = 0; refused("a destination that is a source");
+      DST[1] = 6; refused("an item outside [0, N)");
+      DST[1] = 4; HI[1] = 97; refused("a window behind cap");
+      HI[1] = 40; LO[1] = 41; refused("a window that ends in front of its start");
+      LO[0] = HI[0] = 8; LO[1] = HI[1] = 40;      // every row idle
+      CK(fork());
+    }
     auto xs = buf(2 * 8 * 3000), ys = buf(2 * 8 * 3000), da = buf(8), db = buf(8);
     CK(dmel_aa_snake_f32(xs.data(), ys.data(), al.data(), be.data(), taps.data(), taps.data(), 1, 2, 8, 3000, nullptr));
     CK(dmel_aa_snake_backward_f32(xs.data(), ys.data(), xs.data(), al.data(), be.data(), da.data(), db.data(), taps.data(), taps.data(), 1, 2, 8, 3000, nullptr));

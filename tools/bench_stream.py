@@ -48,8 +48,15 @@ shift / xor chain per reply.
 runs only this: S replies for playback devices opened with C channels, served (a) by a pool that was told so (open(sample_format=...,
 channels=C): the ONE convert launch of the step fans every piece out into interleaved frames) and (b) by the same pool with mono
 sessions of the same format and what every caller would do behind it, `repeat_interleave(C)` per reply.  Same tokens and noise,
-interleaved in one process, equal audio asserted, median and 10th / 90th percentile APPENDED to --out."""
-import json, os, statistics, sys, time
+interleaved in one process, equal audio asserted, median and 10th / 90th percentile APPENDED to --out.
+
+    python tools/bench_stream.py --sessions 16 --lookahead 0,8,32 [--push-tokens 1,4,16] [--steps 40] [--out profiles/sessions_early.txt]
+
+runs only this: S replies that emit with bounded look-ahead (decode_sessions(early_emit=True), open(lookahead_frames=K)) against the same
+replies in a pool built without early_emit, for every K of the list and every push size: the step time of both (median, p10, p90, p99),
+the tokens and stream milliseconds from the first push to the first audio sample (from the schedule), and how far the provisional audio
+is from decode()'s (SNR, largest difference at piece boundaries) on the bench's synthetic weights."""
+import json, math, os, statistics, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
@@ -400,6 +407,104 @@ def sessions_channels_section(S, rates, steps, out, fmt, ch):
     print("\n".join(table), file=sys.stderr)
     print(json.dumps(result))
 
+
+def sessions_early_section(S, lookaheads, pushes, steps, out, label=""):
+    """early against exact sessions: S replies pushed `p` tokens per step, served by a pool built without early_emit (today's path) and by
+    one built with it whose sessions were opened with lookahead_frames=k; the two interleaved in one process"""
+    from dmel_codec_amd.models.stream_schedule import DecodeSchedule, EarlyDecodeSchedule
+    pct = lambda v, q: sorted(v)[min(len(v) - 1, int(q * len(v)))]
+    G, Cn = codec.dmel_groups, codec.decoder.input_channels
+    rows, results = [], []
+    for p in pushes:
+        for k in lookaheads:
+            pools = {"exact": codec.decode_sessions(S, max_push_tokens=max(pushes)),
+                     f"early_k{k}": codec.decode_sessions(S, max_push_tokens=max(pushes), early_emit=True)}
+            early = f"early_k{k}"
+            geo = pools["exact"].geo
+            hold_tokens = -(-geo.hold_frames // geo.factor)
+            warmup = max(6, hold_tokens // p + 3)                     # the early path re-decodes up to the hold: steady only behind it
+            total = p * (warmup + steps)
+            gl = torch.Generator().manual_seed(12)
+            ids = torch.randint(0, 175, (S, G, total), generator=gl, dtype=torch.int32).to(dev)
+            noise = torch.randn(S, Cn, total * 4, generator=gl).to(dev)
+            slots = {"exact": [pools["exact"].open() for _ in range(S)], early: [pools[early].open(lookahead_frames=k) for _ in range(S)]}
+            ms = {name: [] for name in pools}
+            pieces = []                                               # session 0 of the early pool
+            for step in range(warmup + steps):
+                a = p * step
+                names = list(pools)
+                for name in (names if step % 2 == 0 else names[::-1]):
+                    sl = slots[name]
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    got = pools[name].push({sl[i]: ids[i, :, a:a + p] for i in range(S)},
+                                           noise={sl[i]: noise[i, :, 4 * a:4 * (a + p)] for i in range(S)})
+                    torch.cuda.synchronize()
+                    if step >= warmup:
+                        ms[name].append((time.perf_counter() - t0) * 1e3)
+                    if name == early:
+                        pieces.append(got[sl[0]][0])
+            for name, pool in pools.items():
+                for i, s in enumerate(slots[name]):
+                    last = pool.close(s)
+                    if name == early and i == 0:
+                        pieces.append(last[0])
+            # (c) how far the provisional audio is from decode()'s, on these synthetic weights
+            ref = codec.decode(ids[:1], torch.tensor([total], device=dev), return_audios=True, noise=noise[:1])[0][0]
+            mine = torch.cat(pieces, dim=1)
+            assert mine.shape == ref.shape, (mine.shape, ref.shape)
+            d = (mine - ref).double()
+            err = float((d * d).sum())
+            snr = float("inf") if err == 0 else 10 * math.log10(float((ref.double() ** 2).sum()) / err)
+            cuts, at = [], 0
+            for piece in pieces[:-1]:
+                at += piece.shape[1]
+                if 0 < at < ref.shape[1]:
+                    cuts += [at - 1, at]
+            edge = float(d[0, sorted(set(cuts))].abs().max()) if cuts else 0.0
+            # (b) first audio: from the schedule, in tokens received and in the stream time they stand for
+            first = {}
+            for name, sch in (("exact", DecodeSchedule(geo)), (early, EarlyDecodeSchedule(geo, k))):
+                n = 0
+                while True:
+                    n += p
+                    if sch.step(p).emit[1] > 0:
+                        break
+                first[name] = n
+            tok_s = 24000 / (256 * geo.factor)
+            r = {"push_tokens": p, "lookahead_frames": k, "snr_db": round(snr, 2) if snr != float("inf") else "inf",
+                 "max_abs_diff_at_piece_boundaries": edge, "peak": float(ref.abs().max())}
+            for name, v in ms.items():
+                med = statistics.median(v)
+                r[name] = {"median_ms": round(med, 3), "p10_ms": round(pct(v, 0.1), 3), "p90_ms": round(pct(v, 0.9), 3),
+                           "p99_ms": round(pct(v, 0.99), 3), "n": len(v), "first_audio_after_tokens": first[name],
+                           "first_audio_after_ms": round(first[name] / tok_s * 1e3, 1)}
+                rows.append(f"{p:4d}  {name:11s}  {med:9.3f}  {pct(v, 0.1):9.3f}  {pct(v, 0.9):9.3f}  {pct(v, 0.99):9.3f}  {len(v):4d}  "
+                            f"{first[name]:6d}  {first[name] / tok_s * 1e3:8.1f}" +
+                            (f"  {r['snr_db']:>7}  {edge:9.2e}" if name == early else ""))
+            results.append(r)
+    table = [(f"[{label}] " if label else "") + f"{S} decode sessions, early against exact, pushes of {','.join(map(str, pushes))} tokens, 100 mel / 10 groups, "
+             f"BigVGAN base (tools/bench_stream.py --sessions {S} --lookahead {','.join(map(str, lookaheads))})",
+             f"wall time of one step of all sessions incl. host synchronisation, {steps} steady-state steps, the two pools interleaved in one process;",
+             "exact = a pool built without early_emit; early_kK = decode_sessions(early_emit=True), every session open(lookahead_frames=K);",
+             "first audio: tokens received, and the stream time they stand for, when the first sample leaves -- from the schedule, not a timer;",
+             "SNR / edge: session 0's concatenated early audio against decode()'s, edge = largest |difference| one sample either side of a piece "
+             "boundary.  SYNTHETIC weights: this says nothing about a trained checkpoint",
+             "push  pool         median ms     p10 ms     p90 ms     p99 ms     n  first: tokens    ms   SNR dB       edge"] + rows
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "a") as f:
+        f.write("\n".join(table) + "\n\n")
+    print("\n".join(table), file=sys.stderr)
+    print(json.dumps({"sessions": S, "label": label, "results": results}))
+
+
+if "--lookahead" in sys.argv:
+    assert "--sessions" in sys.argv, "--lookahead needs --sessions"
+    sessions_early_section(int(arg_after("--sessions")), [int(k) for k in arg_after("--lookahead").split(",")],
+                           [int(p) for p in arg_after("--push-tokens", "1,4,16").split(",")], int(arg_after("--steps", "40")),
+                           arg_after("--out", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                           "sessions_early.txt")), arg_after("--label", ""))
+    sys.exit(0)
 
 if "--channels" in sys.argv and int(arg_after("--channels")) != 1:
     assert "--sessions" in sys.argv, "--channels needs --sessions"
