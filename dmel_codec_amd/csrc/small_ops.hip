@@ -1306,3 +1306,84 @@ extern "C" int dmel_stream_fork_items(float* hist, float* skip, float* cond, flo
   DMEL_HIP(hipGetLastError());
   return DMEL_OK;
 }
+
+namespace dmel {
+
+// ---- cross-fade of provisional audio pieces (include/dmel_hip.h: dmel_crossfade_items) -------------------------------------------------
+// Row r of the table is (blend, tail, save, w, F), five int64; a workgroup owns kFadeTile elements of row blockIdx.y, a lane four
+// consecutive ones.  Per element: old = tail[i]; blend[i] = old + w[i] * (blend[i] - old) where blend is set; tail[i] = save[i] where save
+// is set.  The three operations are rounded one by one (fp contract(off) in fade_blend: nothing is fused into an fma), which is what
+// the fp32 torch expression gives on the host.  The row is uniform over the workgroup; its 16-byte path is taken when F is a
+// multiple of 4 and every pointer of the row is 16-byte aligned.  No LDS, no atomics; a lane reads its tail before it writes it, and
+// the blend and save regions of a row do not overlap (the caller's contract), so no element is read after another lane wrote it.
+constexpr int kFadeWords = 5, kFadeTile = 1024;
+__device__ __forceinline__ float fade_blend(float old, float w, float now) {
+  // hipcc contracts by default, and through __fmul_rn / __fadd_rn as well (they are plain operators here): the pragma is what keeps
+  // the product rounded before the sum
+#pragma clang fp contract(off)
+  const float d = now - old;
+  const float p = w * d;
+  return old + p;
+}
+__global__ __launch_bounds__(256) void crossfade_kernel(const int64_t* __restrict__ tab) {
+  const int64_t* row = tab + (size_t)blockIdx.y * kFadeWords;
+  float* blend = reinterpret_cast<float*>(row[0]);
+  float* tail = reinterpret_cast<float*>(row[1]);
+  const float* save = reinterpret_cast<const float*>(row[2]);
+  const float* w = reinterpret_cast<const float*>(row[3]);
+  const int F = (int)row[4];
+  const int i = (int)blockIdx.x * kFadeTile + 4 * (int)threadIdx.x;
+  if (i >= F) return;
+  const bool vec = (F & 3) == 0 && ((row[0] | row[1] | row[2] | row[3]) & 15) == 0;   // a NULL pointer is aligned
+  if (vec) {
+    const float4 old = *reinterpret_cast<const float4*>(tail + i);
+    if (blend) {
+      const float4 x = *reinterpret_cast<const float4*>(blend + i), ww = *reinterpret_cast<const float4*>(w + i);
+      *reinterpret_cast<float4*>(blend + i) = make_float4(fade_blend(old.x, ww.x, x.x), fade_blend(old.y, ww.y, x.y),
+                                                          fade_blend(old.z, ww.z, x.z), fade_blend(old.w, ww.w, x.w));
+    }
+    if (save) *reinterpret_cast<float4*>(tail + i) = *reinterpret_cast<const float4*>(save + i);
+  } else {
+    const int end = min(F, i + 4);
+    for (int t = i; t < end; ++t) {
+      const float old = tail[t];
+      if (blend) blend[t] = fade_blend(old, w[t], blend[t]);
+      if (save) tail[t] = save[t];
+    }
+  }
+}
+
+}  // namespace dmel
+
+extern "C" int dmel_crossfade_items(float* const* blend, float* const* tail, const float* const* save, const float* const* w,
+                                    const int64_t* F, int R, void* table_scratch, void* stream) {
+  using namespace dmel;
+  DMEL_CHECK_ARG(blend && tail && save && w && F && table_scratch, "crossfade_items: NULL argument");
+  DMEL_CHECK_ARG(R >= 1 && R <= 65535, "crossfade_items: %d rows, expected 1 .. 65535", R);
+  DMEL_CHECK_ARG(((uintptr_t)table_scratch & 7) == 0, "crossfade_items: table_scratch is not 8-byte aligned");
+  std::vector<int64_t> tab((size_t)kFadeWords * R);
+  int64_t max_f = 0;
+  double bytes = 0.0;
+  for (int r = 0; r < R; ++r) {
+    DMEL_CHECK_ARG(F[r] >= 1 && F[r] <= 4096, "crossfade_items: row %d: a fade of %lld samples, expected 1 .. 4096", r, (long long)F[r]);
+    DMEL_CHECK_ARG(tail[r] && w[r], "crossfade_items: row %d: NULL tail or weights", r);
+    DMEL_CHECK_ARG(blend[r] || save[r], "crossfade_items: row %d: neither blend nor save: nothing to do", r);
+    DMEL_CHECK_ARG((((uintptr_t)blend[r] | (uintptr_t)tail[r] | (uintptr_t)save[r] | (uintptr_t)w[r]) & 3) == 0,
+                   "crossfade_items: row %d: a pointer is not 4-byte aligned", r);
+    int64_t* it = tab.data() + (size_t)kFadeWords * r;
+    it[0] = (int64_t)(uintptr_t)blend[r]; it[1] = (int64_t)(uintptr_t)tail[r]; it[2] = (int64_t)(uintptr_t)save[r];
+    it[3] = (int64_t)(uintptr_t)w[r]; it[4] = F[r];
+    max_f = std::max(max_f, F[r]);
+    bytes += 4.0 * (double)F[r] * ((blend[r] ? 3 : 0) + (save[r] ? 2 : 0) + 1);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  DMEL_TRY(launch_table_put(tab.data(), tab.size() * sizeof(int64_t), table_scratch, s));
+  {
+    // "small" carries the time and the bytes; the second scope only counts: one record per cross-fade launch (dmel_prof_read("crossfade"))
+    ProfScope ps("small", s, 0.0, bytes), count("crossfade", s, 0.0, 0.0);
+    hipLaunchKernelGGL(crossfade_kernel, dim3((unsigned)((max_f + kFadeTile - 1) / kFadeTile), (unsigned)R), dim3(256), 0, s,
+                       static_cast<const int64_t*>(table_scratch));
+  }
+  DMEL_HIP(hipGetLastError());
+  return DMEL_OK;
+}

@@ -495,6 +495,9 @@ class VQGAN(nn.Module):
         arrived -- pool.open(lookahead_frames=k) starts a reply that hands out every mel frame at most k frames behind the newest
         one received (k = 0: at once), each piece cut from decode() of the tokens received SO FAR (the last piece from decode() of
         the whole sequence); such a pool holds a shadow row per slot, and sessions opened without a look-ahead stay exact in it.
+        crossfade_samples=Fmax with it: pool.open(lookahead_frames=k, crossfade_samples=F) starts a reply whose pieces join without a
+        step (the last F samples of a piece wait and are cross-faded into the next decode: utils/crossfade.py);
+        pool.set_lookahead(slot, k) moves a live reply's look-ahead.
         See models/stream_sessions.py: DecodeSessions."""
         from .stream_sessions import DecodeSessions
         return DecodeSessions(self, slots, max_push_tokens, return_audios, **options)

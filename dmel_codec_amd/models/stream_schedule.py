@@ -258,13 +258,14 @@ class DecodeSchedule:
         return st
 
 
-def decode_capacity(geo: DecodeGeometry, max_push_tokens: int) -> int:
-    """Columns of a decode slot's state buffers.  In front of a push a slot holds at most geo.hold_frames columns that are still read;
-    the push adds max_push_tokens * factor.  Four pushes of room instead of one, rounded up to 32, so that a slot that pushes the maximum
-    every time is re-based (decode_rebase) once in four pushes and one that pushes less, less often."""
+def decode_capacity(geo: DecodeGeometry, max_push_tokens: int, extra_hold: int = 0) -> int:
+    """Columns of a decode slot's state buffers.  In front of a push a slot holds at most geo.hold_frames columns that are still read
+    (+ extra_hold: the one frame more a cross-fading session keeps, EarlyDecodeSchedule(fade_frames=1)); the push adds
+    max_push_tokens * factor.  Four pushes of room instead of one, rounded up to 32, so that a slot that pushes the maximum every time
+    is re-based (decode_rebase) once in four pushes and one that pushes less, less often."""
     if max_push_tokens <= 0:
         raise ValueError("max_push_tokens must be positive")
-    return (geo.hold_frames + 4 * max_push_tokens * geo.factor + 31) // 32 * 32
+    return (geo.hold_frames + extra_hold + 4 * max_push_tokens * geo.factor + 31) // 32 * 32
 
 
 def decode_rebase(origin: int, st: DecodeStep, cap: int) -> int:
@@ -299,10 +300,11 @@ class EarlyDecodeStep:
     tok_window: Tuple[int, int]       # tokens [lo, hi) the quantiser decodes now, for the committed and the shadow row alike
     z: Tuple[int, int]                # condition / level-0 frames [a, b) written to the shadow row: from the committed frontier to `upto`
     voc_window: Tuple[int, int]       # mel frames [lo, hi) the vocoder runs on, hi the window's own end (lo == hi: nothing to vocode)
+    fade: int = 0                     # frames in front of emit[0] the vocoder window also renders (a cross-fading session: 1)
 
     @property
     def need_from(self) -> int:
-        return self.step.need_from
+        return max(0, self.step.need_from - self.fade)
 
     @property
     def upto(self) -> int:
@@ -319,14 +321,31 @@ class EarlyDecodeSchedule:
     When the third term wins, the frames come from the shadow row: a copy of the committed columns [fork) stepped from the committed
     frontiers to the newest frame on every level, as if the stream ended here.  With lookahead >= geo.hold_frames it never wins:
     every step is the exact schedule's, range for range.  The columns the shadow and its vocoder window read start at or behind the
-    committed step's need_from, so decode_rebase and decode_capacity hold as they are."""
+    committed step's need_from, so decode_rebase and decode_capacity hold as they are.
 
-    def __init__(self, geo: DecodeGeometry, lookahead: int):
-        if int(lookahead) < 0:
-            raise ValueError("lookahead_frames must be >= 0")
-        self.geo, self.lookahead = geo, int(lookahead)
+    `lookahead` may change between steps (set_lookahead): the rule above is applied with the value of the moment.  What has left
+    never comes back, so raising it only pauses emission until tokens * factor - lookahead passes `emitted`; every piece is still a
+    crop of the prefix decode, and from a step with lookahead >= geo.hold_frames on the third term never wins again.
+
+    fade_frames = 1 is the schedule of a session that cross-fades its audio pieces (utils/crossfade.py): the last samples of the frame
+    in front of the emitted frontier are rendered again by the next decode, so the vocoder window starts one frame earlier,
+    [emitted - voc_halo - 1, ...), and with it the fork window; need_from moves one frame back so that no re-base drops that
+    column (the early frontier is never behind the exact one, so the widened window is at most one frame behind the exact
+    need_from), and the capacity is decode_capacity(geo, max_push_tokens, extra_hold=1).  The wrapped DecodeSchedule is untouched."""
+
+    def __init__(self, geo: DecodeGeometry, lookahead: int, fade_frames: int = 0):
+        if fade_frames not in (0, 1):
+            raise ValueError("fade_frames is 0 or 1: a cross-fade is at most one mel frame long")
+        self.geo, self.fade_frames = geo, int(fade_frames)
+        self.set_lookahead(lookahead)
         self.exact = DecodeSchedule(geo)
         self.emitted = 0
+
+    def set_lookahead(self, lookahead: int) -> None:
+        """the look-ahead of every later step"""
+        if int(lookahead) < 0:
+            raise ValueError("lookahead_frames must be >= 0")
+        self.lookahead = int(lookahead)
 
     @property
     def tokens(self) -> int:
@@ -338,7 +357,7 @@ class EarlyDecodeSchedule:
 
     @property
     def need_from(self) -> int:
-        return self.exact.need_from
+        return max(0, self.exact.need_from - self.fade_frames)
 
     def step(self, n: int, final: bool = False) -> EarlyDecodeStep:
         g, ex = self.geo, self.exact
@@ -347,20 +366,21 @@ class EarlyDecodeSchedule:
         T, e_prev, e_exact = st.upto, self.emitted, st.emit[1]
         e_new = T if final else max(e_prev, e_exact, T - self.lookahead)
         shadow = not final and e_new > max(e_prev, e_exact)
-        halo = g.voc_halo
+        halo, fade = g.voc_halo, self.fade_frames
+        v_lo = max(0, e_prev - halo - fade)               # the vocoder window's first frame
         idle = (0, 0)
         if shadow:
-            lo = min([st.prev[l + 1] - d for l, d in enumerate(g.dilations)] + [e_prev - halo])
+            lo = min([st.prev[l + 1] - d for l, d in enumerate(g.dilations)] + [e_prev - halo - fade])
             lo = max(0, min(lo, ex.z_valid))
             row = dict(prev=st.prev, next=(T,) * len(st.prev), fork=(lo, ex.z_valid),
                        tok_window=(max(0, z_before // g.factor - g.quant_halo_tokens), st.tokens), z=(ex.z_valid, T),
-                       voc_window=(max(0, e_prev - halo), T) if halo else idle)
+                       voc_window=(v_lo, T) if halo else idle)
         else:
             ready = st.next[-1]
             row = dict(prev=st.prev, next=st.prev, fork=idle, tok_window=st.tok_window, z=(ex.z_valid, ex.z_valid),
-                       voc_window=(max(0, e_prev - halo), min(ready, e_new + halo)) if halo and e_new > e_prev else idle)
+                       voc_window=(v_lo, min(ready, e_new + halo)) if halo and e_new > e_prev else idle)
         self.emitted = e_new
-        return EarlyDecodeStep(step=st, emit=(e_prev, e_new), shadow=shadow, **row)
+        return EarlyDecodeStep(step=st, emit=(e_prev, e_new), shadow=shadow, fade=fade, **row)
 
 
 # ---------------------------------------------------------------------------------------------------- streaming sample-rate conversion

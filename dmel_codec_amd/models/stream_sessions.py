@@ -19,7 +19,7 @@ from typing import Dict, Iterable, List, Mapping, Optional, Tuple
 import torch
 
 from .. import _lib
-from ..utils import pcm
+from ..utils import crossfade, pcm
 from .stream_schedule import (DecodeGeometry, DecodeSchedule, EarlyDecodeSchedule, EncodeGeometry, EncodeSchedule, decode_capacity,
                               decode_rebase, resample_max_outputs, session_rows)
 
@@ -412,7 +412,9 @@ class DecodeSessions:
     """`slots` independent incremental decodes, each with the audio and mel of decode() on its own finished token sequence.
 
         slot = pool.open()                                              # a free slot, fresh state; open(output_sample_rate=48000);
-                                                                        # open(lookahead_frames=8) in a pool built with early_emit=True
+                                                                        # open(lookahead_frames=8) in a pool built with early_emit=True;
+                                                                        # open(lookahead_frames=0, crossfade_samples=256) in one built
+                                                                        # with crossfade_samples=256 as well; set_lookahead(slot, 8)
         out = pool.push({slot: ids (G, n) int, ...}, noise=None | {slot: (C, n * factor)}, final=())
                                                                         # -> {slot: (audio (1, m * up) | None, mel (n_mels, m))}
         out = pool.close(slot)                                          # = push({slot: empty}, final=(slot,))[slot]
@@ -488,6 +490,30 @@ class DecodeSessions:
     end.  A step that serves only exact sessions launches what it always did; a pool built without early_emit allocates what it
     always did, and refuses lookahead_frames at open.  The final step of an early session is the committed row's: no shadow.
 
+    The look-ahead may move while the session lives: set_lookahead(slot, k) applies from the slot's next push.  The emit rule is the
+    one above with the k of the moment; what has left never comes back, so raising k only pauses the session until T - k passes what
+    it had, and every piece is still the crop of the prefix decode.  From a push with k >= geo.hold_frames on nothing is forked.
+    Start at k = 0 for a fast first sample and raise k once the playback buffer has slack, as a jitter buffer does.
+
+    Pieces cut from different prefix decodes step where they meet.  A pool built with crossfade_samples=Fmax (with early_emit=True
+    and audio; 1 <= Fmax <= samples per mel frame) also serves sessions opened with open(lookahead_frames=k, crossfade_samples=F),
+    1 <= F <= Fmax, whose pieces join without a step -- the rule of utils/crossfade.py, which is also the host reference the pool is
+    tested against bit for bit.  With [A, B) the raw sample range of a push (what it hands out without a fade): a non-final push
+    with new frames hands out only up to B - F and keeps the tail P[B - F, B) as F floats of slot state; the next push with new
+    frames begins with old + w * (new - old) over the tail and the new prefix decode's version of the same samples, w the raised
+    cosine 0.5 - 0.5 cos(pi (i + 0.5) / F) in fp32, three separately rounded fp32 operations; a push without new frames keeps the
+    tail; a final push without new frames hands it out as it is.  The pieces still tile [0, total); the audio runs F samples (at
+    most one frame, 10.7 ms at 24 kHz) behind the mel, whose pieces are unchanged.  Where both decodes agree the blend returns the old
+    sample, so with k >= geo.hold_frames the session returns decode()'s audio exactly, F samples late.  How: the vocoder window of
+    such a slot starts one frame earlier ([emitted - halo - 1, ...): the frame in front of the frontier is rendered again with the
+    prefix decode's bits; EarlyDecodeSchedule(fade_frames=1) widens the fork window and need_from with it, and `cap` is sized from
+    hold_frames + 1).  After the ONE vocoder call, ONE dmel_crossfade_items launch blends in place in the vocoder's batch and saves
+    the new tails, for all fading slots of the step; each slot's piece is then the view shifted by F and goes, unchanged, to the
+    clone, the resampler or the convert launch -- rate, format and channels see the cross-faded float piece.  A step without a
+    fading slot launches what it did; sessions without a fade in such a pool return the pieces they always returned; a pool built
+    with crossfade_samples=0 allocates, sizes `cap` and launches exactly as before and refuses crossfade_samples at open.  A fade
+    without lookahead_frames or with return_audios=False is a ValueError.  Not served: fades longer than a frame, other windows.
+
     Out of scope, NotImplementedError: overlap_vocoder, graph_chunk_tokens, and a pool-wide output_sample_rate (a pool has no rate of
     its own).
 
@@ -498,7 +524,7 @@ class DecodeSessions:
 
     def __init__(self, codec, slots: int, max_push_tokens: int = 64, return_audios: bool = True, overlap_vocoder: bool = False,
                  graph_chunk_tokens: Optional[int] = None, output_sample_rate: Optional[int] = None,
-                 output_sample_rates: Iterable[int] = (), early_emit: bool = False):
+                 output_sample_rates: Iterable[int] = (), early_emit: bool = False, crossfade_samples: int = 0):
         if overlap_vocoder or graph_chunk_tokens is not None or output_sample_rate is not None:
             raise NotImplementedError("decode sessions launch everything on the current stream, eagerly, and have no rate of their own: "
                                       "overlap_vocoder, graph_chunk_tokens and output_sample_rate belong to StreamingDecoder (a session's "
@@ -528,7 +554,14 @@ class DecodeSessions:
                                   voc_halo=codec.vocoder.receptive_field_frames() if return_audios else 0)
         self.up = math.prod(codec.vocoder.h.upsample_rates) if return_audios else 1
         self.max_push = int(max_push_tokens)
-        self.cap = decode_capacity(self.geo, self.max_push)
+        # the longest cross-fade a session of this pool may open with (0: none, and the pool is what it was without the option)
+        self.fade_max = 0
+        if crossfade_samples != 0:
+            if not self.early_emit or not return_audios:
+                raise ValueError("crossfade_samples joins the audio pieces of sessions that emit early: it needs early_emit=True and "
+                                 "return_audios=True")
+            self.fade_max = crossfade.check_fade(crossfade_samples, self.up)
+        self.cap = decode_capacity(self.geo, self.max_push, extra_hold=1 if self.fade_max else 0)
         H, f = self.geo.quant_halo_tokens, self.geo.factor
         self.tok_width = 2 * H + self.max_push            # the token tail starts at most 2 H tokens behind the newest token of the last push
         self.noise_width = (H + self.max_push) * f        # frames [z_valid, tokens * factor): at most H tokens of them in front of a push
@@ -544,6 +577,8 @@ class DecodeSessions:
         self.rate = [self.voc_rate] * self.S              # the rate the slot's audio leaves at
         self.fmt = ["f32"] * self.S                       # the sample format the slot's audio leaves in (utils/pcm.py: FORMATS)
         self.ch = [1] * self.S                            # the channels the slot's audio leaves with (interleaved frames when above 1)
+        self.fade = [0] * self.S                          # the slot's cross-fade in samples (0: none)
+        self.has_tail = [False] * self.S                  # the slot holds back the last `fade` samples of its newest piece
         self.sched: List[Optional[DecodeSchedule | EarlyDecodeSchedule]] = [None] * self.S
         self.origin = [0] * self.S
         self.tok_origin = [0] * self.S                    # absolute index of the token in column 0 of the slot's token tail
@@ -570,13 +605,27 @@ class DecodeSessions:
         return self.sched[slot].emitted
 
     def open(self, output_sample_rate: Optional[int] = None, sample_format: str = "f32", channels: int = 1,
-             lookahead_frames: Optional[int] = None) -> int:
+             lookahead_frames: Optional[int] = None, crossfade_samples: int = 0) -> int:
         """take a free slot: fresh schedule, state zeroed before its first push.  output_sample_rate: the rate this session's audio
         leaves at, one of the declared `output_sample_rates` (None: the vocoder's).  sample_format: "f32", "s16" for audio returned
         as torch.int16 (16-bit signed PCM), or "ulaw" / "alaw" for torch.uint8 (G.711 codes).  channels: 1 .. 8; above 1 the audio
         comes back as interleaved frames (n, channels), every channel the mono audio.  lookahead_frames: None for the exact session;
         k >= 0 (mel frames) for a session that emits every frame at most k behind the newest one received, on a pool built with
-        early_emit=True.  Raises when every slot is taken; a refused open takes no slot."""
+        early_emit=True.  crossfade_samples: F >= 1 samples (at most the pool's crossfade_samples and one mel frame) over which
+        such a session blends every piece into the next (utils/crossfade.py); its audio runs F samples behind its mel.  Raises when
+        every slot is taken; a refused open takes no slot."""
+        if isinstance(crossfade_samples, bool) or not isinstance(crossfade_samples, int) or crossfade_samples < 0:
+            raise ValueError(f"crossfade_samples must be an integer >= 0 (samples), got {crossfade_samples!r}")
+        if crossfade_samples:
+            if not self.fade_max:
+                raise ValueError("crossfade_samples on a pool built without crossfade_samples=: it has no tails to blend with")
+            if lookahead_frames is None:
+                raise ValueError("crossfade_samples without lookahead_frames: the pieces of an exact session join as they are")
+            if not self.return_audios:
+                raise ValueError("crossfade_samples without audio: return_audios=False leaves nothing to blend")
+            if crossfade_samples > self.fade_max:
+                raise ValueError(f"crossfade_samples={crossfade_samples} exceeds the pool's crossfade_samples={self.fade_max} (and a "
+                                 f"fade is at most one mel frame, {self.up} samples)")
         if lookahead_frames is not None:
             if not self.early_emit:
                 raise ValueError("lookahead_frames on a pool built without early_emit=True: it has no shadow rows to decode ahead in")
@@ -593,8 +642,9 @@ class DecodeSessions:
         for s in range(self.S):
             if self.sched[s] is None:
                 self.sched[s] = (DecodeSchedule(self.geo) if lookahead_frames is None
-                                 else EarlyDecodeSchedule(self.geo, lookahead_frames))
+                                 else EarlyDecodeSchedule(self.geo, lookahead_frames, fade_frames=1 if crossfade_samples else 0))
                 self.origin[s] = self.tok_origin[s] = self.n_noise[s] = 0
+                self.fade[s], self.has_tail[s] = crossfade_samples, False
                 self.rate[s] = rate
                 self.fmt[s] = sample_format
                 self.ch[s] = channels
@@ -603,6 +653,17 @@ class DecodeSessions:
                 self._fresh[s] = True
                 return s
         raise RuntimeError(f"all {self.S} slots are taken")
+
+    def set_lookahead(self, slot: int, lookahead_frames: int) -> None:
+        """the look-ahead of an open early session from its next push on.  What has left never comes back: raising it pauses the
+        session's emission until the newest frame is that far ahead; from a push with lookahead_frames >= geo.hold_frames on, the
+        steps are the exact session's and nothing is forked."""
+        self._check_open(slot)
+        if not isinstance(self.sched[slot], EarlyDecodeSchedule):
+            raise ValueError(f"slot {slot} was opened without lookahead_frames: an exact session has no look-ahead to move")
+        if isinstance(lookahead_frames, bool) or not isinstance(lookahead_frames, int) or lookahead_frames < 0:
+            raise ValueError(f"lookahead_frames must be an integer >= 0 (mel frames), got {lookahead_frames!r}")
+        self.sched[slot].set_lookahead(lookahead_frames)
 
     def _wired(self, slot: int) -> bool:
         """the slot's audio leaves through the convert launch of the step: another format than f32, or more than one channel"""
@@ -650,14 +711,19 @@ class DecodeSessions:
                         pcm_tab=torch.empty(4 * S, dtype=torch.int64, device=dev))
         if self.early_emit:                           # dmel_stream_fork_items: 5 int32 per fork, at most one fork per slot
             self.buf["fork_tab"] = torch.empty(5 * S, dtype=torch.int32, device=dev)
+        if self.fade_max:                             # dmel_crossfade_items: a tail and the weights per slot, 5 int64 per row of the table
+            self.buf["fade_tail"] = torch.zeros(S, self.fade_max, dtype=torch.float32, device=dev)
+            self.buf["fade_w"] = torch.zeros(S, self.fade_max, dtype=torch.float32, device=dev)
+            self.buf["fade_tab"] = torch.empty(5 * S, dtype=torch.int64, device=dev)
 
     def _slot_views(self, s: int):
         b = self.buf
         return (b["hist"][:, s], b["skip"][s], b["cond"][s], b["mel"][s])
 
-    def _rebase(self, s: int, st) -> None:
-        """make room for the frames of step `st` in slot s: drop the columns nothing reads again and shift that slot's rows"""
-        new = decode_rebase(self.origin[s], st, self.cap)
+    def _rebase(self, s: int, st, room=None) -> None:
+        """make room for the frames of step `st` in slot s: drop the columns nothing reads again and shift that slot's rows.  room:
+        the step whose need_from says what is still read, when that is not st's own (a cross-fading slot keeps one frame more)"""
+        new = decode_rebase(self.origin[s], room or st, self.cap)
         shift = new - self.origin[s]
         if shift <= 0:
             return
@@ -689,6 +755,8 @@ class DecodeSessions:
                 if self._fresh[s]:
                     for v in self._slot_views(s):
                         v.zero_()
+                    if self.fade[s]:
+                        b["fade_w"][s, :self.fade[s]] = crossfade.weights(self.fade[s]).to(dev)
                     self._fresh[s] = False
                 sch = self.sched[s]
                 n = t.shape[1]
@@ -701,10 +769,12 @@ class DecodeSessions:
                     b["noise"][s, :, self.n_noise[s]:self.n_noise[s] + n * f] = z.to(dev, torch.float32)
                     self.n_noise[s] += n * f
                 st = sch.step(n, s in final)
+                room = None
                 if isinstance(sch, EarlyDecodeSchedule):
                     early[s], st = st, st.step         # the committed row runs the exact schedule's step, as an exact slot's does
+                    room = early[s] if early[s].fade else None
                 steps[s] = st
-                self._rebase(s, st)
+                self._rebase(s, st, room)
             shadows = {s: es for s, es in early.items() if es.shadow}
             # ---- quantiser: ONE call over every slot with new condition frames, whatever the lengths of their token windows, cropped per
             # slot.  A slot that decodes ahead needs no item of its own: its window ends at its newest token already, so the frames the
@@ -786,16 +856,44 @@ class DecodeSessions:
                 wins = [b["mel"][row[s], :, steps[s].voc_window[0] - self.origin[s]:steps[s].voc_window[1] - self.origin[s]] for s in members]
                 mel_batch, widths = pad_windows(wins)
                 wav = codec.vocoder(mel_batch) if widths is None else codec.vocoder(mel_batch, lengths=widths)
+                # ---- cross-fade: ONE launch blends, in place in the vocoder's batch, the F samples in front of every fading slot's new
+                # piece with the tail the slot held back, and saves the piece's last F samples as the new tail (not on a final step).
+                # The piece handed on is the view shifted by F; the two regions of a row lie a whole frame (up >= F samples) apart
+                fading = [(i, s) for i, s in enumerate(members) if self.fade[s]]
+                cut = {}                                                   # slot -> (samples taken in front, samples held back)
+                if fading:
+                    rows = []
+                    for i, s in fading:
+                        st, F = steps[s], self.fade[s]
+                        a, e = (st.emit[0] - st.voc_window[0]) * self.up, (st.emit[1] - st.voc_window[0]) * self.up
+                        cut[s] = (F if self.has_tail[s] else 0, 0 if s in final else F)
+                        rows.append((wav[i, 0, a - F:a] if self.has_tail[s] else None, b["fade_tail"][s, :F],
+                                     None if s in final else wav[i, 0, e - F:e], b["fade_w"][s, :F]))
+                        self.has_tail[s] = s not in final
+                    rows = [r for r in rows if r[0] is not None or r[2] is not None]
+                    if rows:
+                        crossfade.crossfade_items(rows, table=b["fade_tab"])
                 for i, s in enumerate(members):
                     st = steps[s]
                     lo = st.voc_window[0]
-                    piece = wav[i, :, (st.emit[0] - lo) * self.up:(st.emit[1] - lo) * self.up]
+                    front, back = cut.get(s, (0, 0))
+                    piece = wav[i, :, (st.emit[0] - lo) * self.up - front:(st.emit[1] - lo) * self.up - back]
                     if self.rate[s] != self.voc_rate:
                         pieces[s] = piece[0]
                     elif self._wired(s):
                         wire[s] = piece[0]
                     else:
                         out[s] = (piece.clone(), out[s][1])
+            for s in final:                            # a fading slot that ends without new frames: its tail leaves as it is
+                if self.has_tail[s] and s in steps:
+                    tail = b["fade_tail"][s, :self.fade[s]]
+                    if self.rate[s] != self.voc_rate:
+                        pieces[s] = tail
+                    elif self._wired(s):
+                        wire[s] = tail
+                    else:
+                        out[s] = (tail[None].clone(), out[s][1])
+                    self.has_tail[s] = False
             # ---- the playback rates: each piece goes behind its slot's resampler tail, ONE launch converts all slots; a slot without a
             # new piece still takes part when it ends (the outputs that waited for the end of its signal)
             if self.rs is not None:

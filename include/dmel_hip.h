@@ -448,6 +448,23 @@ int dmel_stream_fork_items(float* hist, float* skip, float* cond /*nullable*/, f
                            int64_t cap, int R, const int64_t* src, const int64_t* dst, const int64_t* lo, const int64_t* hi,
                            void* table_scratch, void* stream);
 
+/* Cross-fade of provisional audio pieces, R rows in ONE launch (csrc/small_ops.hip).  A decode session that emits early hands out
+ * pieces cut from different prefix decodes; with a cross-fade of F samples it holds back the last F samples of a piece (the tail) and
+ * blends them with the next decode's version of the same samples.  Row r, for i in [0, F[r]):
+ *     old = tail[r][i];   if blend[r]: blend[r][i] = old + w[r][i] * (blend[r][i] - old);   if save[r]: tail[r][i] = save[r][i]
+ * the blend as three separately rounded fp32 operations (subtract, multiply, add; no fma), bit for bit `old + w * (new - old)` on CPU
+ * fp32 torch tensors.  blend[r] (nullable) points at F floats inside the vocoder's output, overwritten in place; save[r] (nullable:
+ * the step ends the session) at the F floats that become the new tail; tail[r] and w[r] at F floats of state and F weights.  The
+ * blend and save regions of a row MUST NOT overlap and no two rows may share a tail or a region that is written: in a session they
+ * are the last F samples in front of, and the last F samples of, a piece of at least one mel frame (`up` >= F samples), which are
+ * disjoint.  DMEL_EINVAL, nothing launched, dmel_last_error naming the row: R outside [1, 65535], F[r] outside [1, 4096], a NULL
+ * tail or w, a row with neither blend nor save, a pointer that is not 4-byte aligned.  blend, tail, save, w, F are HOST tables of R
+ * entries, copied as launch arguments into table_scratch (5 R int64 of device memory, 8-byte aligned): the caller may overwrite them as
+ * soon as the call returns.  The grid covers the rows' elements; a row whose F is a multiple of 4 and whose pointers are all 16-byte
+ * aligned moves 16 bytes per lane, every other one 4.  No LDS, no atomics. */
+int dmel_crossfade_items(float* const* blend /*entries nullable*/, float* const* tail, const float* const* save /*entries nullable*/,
+                         const float* const* w, const int64_t* F, int R, void* table_scratch, void* stream);
+
 /* ConvNeXtBlock (models/modules/firefly.py:337-402; C-ABI row `convnext_block`), standalone: y = x + gamma * pwconv2(gelu(pwconv1(
  * LayerNorm_C(dwconv7(x))))), x / y (N, dim, T).  set_tensor keys: dwconv.weight (dim,1,7), dwconv.bias, norm.weight, norm.bias,
  * pwconv1.weight (4 dim, dim), pwconv1.bias, pwconv2.weight (dim, 4 dim), pwconv2.bias, gamma.  The training entry points follow the

@@ -467,6 +467,31 @@ int main() {
       LO[0] = HI[0] = 8; LO[1] = HI[1] = 40;      // every row idle
       CK(fork());
     }
+    {
+      // the cross-fade: tables of exactly R entries, a table scratch of exactly 5 R int64; its refusals read the host tables only
+      auto wav = buf(4096), tails = buf(2 * 512), wts = buf(512);
+      float* BL[2] = {wav.data() + 256, wav.data() + 1024};
+      float* TA[2] = {tails.data(), tails.data() + 512};
+      const float* SA[2] = {wav.data() + 768, nullptr};
+      const float* WT[2] = {wts.data(), wts.data()};
+      int64_t FA[2] = {512, 255};
+      std::vector<int64_t> tab(5 * 2);
+      auto fade = [&](int R) { return dmel_crossfade_items(BL, TA, SA, WT, FA, R, tab.data(), nullptr); };
+      CK(fade(2));
+      auto refused = [&](int R, const char* row, const char* what) {
+        const int rc = fade(R);
+        if (rc != DMEL_EINVAL || !std::strstr(dmel_last_error(), row)) { std::printf("FAIL crossfade_items accepted %s (%d: %s)\n", what, rc, dmel_last_error()); ++failures; }
+      };
+      refused(0, "0 rows", "no row");
+      refused(65536, "65536 rows", "more than 65535 rows");
+      FA[1] = 0; refused(2, "row 1", "a fade of 0 samples");
+      FA[1] = 4097; refused(2, "row 1", "a fade of 4097 samples");
+      FA[1] = 255; TA[1] = nullptr; refused(2, "row 1", "a NULL tail");
+      TA[1] = tails.data() + 512; WT[0] = nullptr; refused(2, "row 0", "NULL weights");
+      WT[0] = wts.data(); BL[1] = nullptr; refused(2, "row 1", "a row with neither blend nor save");
+      SA[1] = wav.data() + 2048;                  // a row that only saves
+      CK(fade(2));
+    }
     auto xs = buf(2 * 8 * 3000), ys = buf(2 * 8 * 3000), da = buf(8), db = buf(8);
     CK(dmel_aa_snake_f32(xs.data(), ys.data(), al.data(), be.data(), taps.data(), taps.data(), 1, 2, 8, 3000, nullptr));
     CK(dmel_aa_snake_backward_f32(xs.data(), ys.data(), xs.data(), al.data(), be.data(), da.data(), db.data(), taps.data(), taps.data(), 1, 2, 8, 3000, nullptr));

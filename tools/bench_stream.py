@@ -55,7 +55,14 @@ interleaved in one process, equal audio asserted, median and 10th / 90th percent
 runs only this: S replies that emit with bounded look-ahead (decode_sessions(early_emit=True), open(lookahead_frames=K)) against the same
 replies in a pool built without early_emit, for every K of the list and every push size: the step time of both (median, p10, p90, p99),
 the tokens and stream milliseconds from the first push to the first audio sample (from the schedule), and how far the provisional audio
-is from decode()'s (SNR, largest difference at piece boundaries) on the bench's synthetic weights."""
+is from decode()'s (SNR, largest difference at piece boundaries) on the bench's synthetic weights.
+
+    python tools/bench_stream.py --sessions 16 --lookahead 0 --crossfade 256 [--push-tokens 1,4,16] [--steps 40] [--out profiles/sessions_crossfade.txt]
+
+runs only this: S early replies with look-ahead K that cross-fade their pieces over F samples (decode_sessions(early_emit=True,
+crossfade_samples=F), open(lookahead_frames=K, crossfade_samples=F)) against the same replies with F = 0, interleaved in one process:
+the step time of both, and for session 0 of both the largest sample-to-sample step at the piece boundaries beside the median step of
+the stream, on the bench's synthetic weights."""
 import json, math, os, statistics, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -497,6 +504,94 @@ def sessions_early_section(S, lookaheads, pushes, steps, out, label=""):
     print("\n".join(table), file=sys.stderr)
     print(json.dumps({"sessions": S, "label": label, "results": results}))
 
+
+def sessions_crossfade_section(S, k, fade, pushes, steps, out, label=""):
+    """cross-fading against plain early sessions: S replies pushed `p` tokens per step with look-ahead k, served by a pool built with
+    crossfade_samples=fade whose sessions were opened with it and by the same pool with F = 0; the two interleaved in one process.
+    For session 0 of both: the sample-to-sample step |x[i + 1] - x[i]| of the concatenated audio across the pool's own piece
+    boundaries (`fade` samples earlier with the fade), over the `fade` samples in front of every raw boundary -- the blended region
+    of one pool, the same samples and the raw cut behind them in the other -- and its median and 99th percentile everywhere"""
+    pct = lambda v, q: sorted(v)[min(len(v) - 1, int(q * len(v)))]
+    G, Cn = codec.dmel_groups, codec.decoder.input_channels
+    rows, results = [], []
+    for p in pushes:
+        pools = {"early_F0": codec.decode_sessions(S, max_push_tokens=max(pushes), early_emit=True),
+                 f"fade_F{fade}": codec.decode_sessions(S, max_push_tokens=max(pushes), early_emit=True, crossfade_samples=fade)}
+        plain, faded = list(pools)
+        geo, up = pools[plain].geo, pools[plain].up
+        warmup = max(6, -(-geo.hold_frames // geo.factor) // p + 3)
+        total = p * (warmup + steps)
+        gl = torch.Generator().manual_seed(12)
+        ids = torch.randint(0, 175, (S, G, total), generator=gl, dtype=torch.int32).to(dev)
+        noise = torch.randn(S, Cn, total * 4, generator=gl).to(dev)
+        slots = {plain: [pools[plain].open(lookahead_frames=k) for _ in range(S)],
+                 faded: [pools[faded].open(lookahead_frames=k, crossfade_samples=fade) for _ in range(S)]}
+        ms = {name: [] for name in pools}
+        pieces = {name: [] for name in pools}                         # session 0 of each pool
+        frames = []                                                   # the mel frames session 0 has handed out after every push
+        for step in range(warmup + steps):
+            a = p * step
+            names = list(pools)
+            for name in (names if step % 2 == 0 else names[::-1]):
+                sl = slots[name]
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                got = pools[name].push({sl[i]: ids[i, :, a:a + p] for i in range(S)},
+                                       noise={sl[i]: noise[i, :, 4 * a:4 * (a + p)] for i in range(S)})
+                torch.cuda.synchronize()
+                if step >= warmup:
+                    ms[name].append((time.perf_counter() - t0) * 1e3)
+                pieces[name].append(got[sl[0]][0])
+                if name == plain:
+                    frames.append(pools[name].frames_emitted(sl[0]))
+        for name, pool in pools.items():
+            for i, s in enumerate(slots[name]):
+                last = pool.close(s)
+                if i == 0:
+                    pieces[name].append(last[0])
+        cuts = sorted({f * up for f in frames if 0 < f * up < total * geo.factor * up})    # the raw piece boundaries, in samples
+        r = {"push_tokens": p, "lookahead_frames": k, "crossfade_samples": fade, "piece_boundaries": len(cuts)}
+        for name in pools:
+            x = torch.cat(pieces[name], dim=1)[0].double()
+            assert x.shape[0] == total * geo.factor * up, (name, x.shape)
+            d = (x[1:] - x[:-1]).abs()                                # d[i]: the step from sample i to sample i + 1
+            own = torch.tensor([c - 1 - (fade if name == faded else 0) for c in cuts], device=dev)
+            near = torch.tensor(sorted({i for c in cuts for i in range(max(0, c - fade - 1), c)}), device=dev)
+            edge, region = (float(d[own].max()), float(d[near].max())) if cuts else (0.0, 0.0)
+            v = ms[name]
+            med = statistics.median(v)
+            r[name] = {"median_ms": round(med, 3), "p10_ms": round(pct(v, 0.1), 3), "p90_ms": round(pct(v, 0.9), 3),
+                       "p99_ms": round(pct(v, 0.99), 3), "n": len(v), "max_step_across_piece_boundaries": edge,
+                       "max_step_in_the_fade_regions": region,
+                       "median_step": float(d.median()), "p99_step": float(d.quantile(0.99)), "peak": float(x.abs().max())}
+            rows.append(f"{p:4d}  {name:11s}  {med:9.3f}  {pct(v, 0.1):9.3f}  {pct(v, 0.9):9.3f}  {pct(v, 0.99):9.3f}  {len(v):4d}  "
+                        f"{len(cuts):5d}  {edge:9.2e}  {region:9.2e}  {float(d.median()):9.2e}  {float(d.quantile(0.99)):9.2e}  {float(x.abs().max()):6.3f}")
+        results.append(r)
+    table = [(f"[{label}] " if label else "") + f"{S} early decode sessions, look-ahead {k} frames, cross-fade {fade} samples against none, pushes of "
+             f"{','.join(map(str, pushes))} tokens, 100 mel / 10 groups, BigVGAN base (tools/bench_stream.py --sessions {S} --lookahead {k} "
+             f"--crossfade {fade})",
+             f"wall time of one step of all sessions incl. host synchronisation, {steps} steady-state steps, the two pools interleaved in one process;",
+             f"early_F0 = decode_sessions(early_emit=True), every session open(lookahead_frames={k}); fade_F{fade} = the same with "
+             f"crossfade_samples={fade} at the pool and at every open: one cross-fade launch more per step;",
+             "step = |x[i + 1] - x[i]| of session 0's concatenated audio: `boundary` its largest value across the pool's own piece boundaries (one "
+             f"step per piece), `region` over the {fade} samples in front of every raw boundary and the step behind them (the blended samples of the "
+             "fading pool; the same samples and the raw cut in the other), median / p99 over the whole stream.",
+             "SYNTHETIC weights: this says nothing about a trained checkpoint",
+             "push  pool         median ms     p10 ms     p90 ms     p99 ms     n   cuts   boundary     region  median st     p99 st    peak"] + rows
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "a") as f:
+        f.write("\n".join(table) + "\n\n")
+    print("\n".join(table), file=sys.stderr)
+    print(json.dumps({"sessions": S, "label": label, "results": results}))
+
+
+if "--crossfade" in sys.argv:
+    assert "--sessions" in sys.argv and "--lookahead" in sys.argv, "--crossfade needs --sessions and --lookahead K"
+    sessions_crossfade_section(int(arg_after("--sessions")), int(arg_after("--lookahead")), int(arg_after("--crossfade")),
+                               [int(p) for p in arg_after("--push-tokens", "1,4,16").split(",")], int(arg_after("--steps", "40")),
+                               arg_after("--out", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                               "sessions_crossfade.txt")), arg_after("--label", ""))
+    sys.exit(0)
 
 if "--lookahead" in sys.argv:
     assert "--sessions" in sys.argv, "--lookahead needs --sessions"
