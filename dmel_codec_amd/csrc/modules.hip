@@ -462,6 +462,9 @@ extern "C" int dmel_wavenet_forward(const dmel_wavenet* m, const float* x, const
   if (!m->ready) { set_error("wavenet_forward: handle not finalized"); return DMEL_EMISSING; }
   DMEL_CHECK_ARG((m->Ccond != 0) == (condition != nullptr), "wavenet_forward: condition tensor does not match the configuration");
   DMEL_CHECK_ARG(N > 0 && T > 0, "wavenet_forward: bad shape");
+  // the lengths are indexed by n / group_repeat: a batch that is no multiple of it would read behind them
+  DMEL_CHECK_ARG((!in_lengths && !out_lengths) || group_repeat <= 1 || N % group_repeat == 0,
+                 "wavenet_forward: N = %d is no multiple of group_repeat = %d", N, group_repeat);
   const WavePlan p = wavenet_plan(m, N, T, workspace);
   float *xb = p.xb, *zb = p.zb, *sb = p.sb, *tb = p.tb;
   DMEL_CHECK_ARG(workspace_bytes >= p.bytes, "wavenet_forward: workspace too small (%zu < %zu)", workspace_bytes, p.bytes);

@@ -325,7 +325,12 @@ size_t dmel_wavenet_workspace_bytes(const dmel_wavenet* m, int N, int64_t T);
 /* x (N, Cin, T), condition (N, Ccond, T) or NULL, y (N, Cout, T).
  * in_lengths / out_lengths: NULL or N int64 frame counts; x is read as x * (t < in_lengths[n]) and y is
  * written as y * (t < out_lengths[n])  (the mask multiplies of codec_lit_modules.py:471-477,505-506).
- * group_repeat: lengths index = n / group_repeat (expand_mask, codec_lit_modules.py:156-157). */
+ * group_repeat: lengths index = n / group_repeat (expand_mask, codec_lit_modules.py:156-157); with lengths given N must be a
+ *   multiple of it (DMEL_EINVAL otherwise, nothing is written).
+ * A length above T counts as T.  A length of 0 masks the whole item: an in_length of 0 feeds the stack zeros (y is then what the
+ *   biases give), an out_length of 0 writes the item's y as zeros.  What stands in x at or behind in_lengths does not reach the
+ *   result (1e30 there changes no bit).  The one-launch kernel and the layered path agree on all of this bit for bit
+ *   (tests/test_gpu_wavenet_one_launch_matrix.py). */
 int dmel_wavenet_forward(const dmel_wavenet* m, const float* x, const float* condition, float* y, int N, int64_t T,
                          const int64_t* in_lengths, const int64_t* out_lengths, int group_repeat,
                          void* workspace, size_t workspace_bytes, void* stream);

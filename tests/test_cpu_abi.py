@@ -345,6 +345,43 @@ def test_conv_matrix_reaches_every_kernel_branch():
     assert all(t <= m.TAU_CEIL for t in m.TAU.values()) and m.TAU_CEIL == 2.0 ** -16
 
 
+# the lines of csrc/ that tests/test_gpu_wavenet_one_launch_matrix.py transcribes (its eligible(), MAX_T, MAX_STREAM_L, SUBSTEP), per file
+ONE_LAUNCH_PREDICATE_SOURCE = {
+    "modules.hip": (
+        "if (C > 32 && C <= 80 && !m->Ccond && !m->has_out && (!m->has_in || m->Cin <= 16) && (m->cycle == 0 || m->cycle <= 4)) {",
+        "if (m->fused.ok && T <= 96 && m->precision == DMEL_PRECISION_FP32 && !(e && e[0] == '0') && !conv_fp32_mfma_forced())",
+        "if (m->Ccond || cond || !m->fused.ok || m->L > kStreamMaxL || m->precision != DMEL_PRECISION_FP32 || conv_fp32_mfma_forced()) {",
+        "if (m->fused.ok && L <= kStreamMaxL && m->precision == DMEL_PRECISION_FP32 && !(e && e[0] == '0') && !conv_fp32_mfma_forced())",
+    ),
+    "ops.h": ("constexpr int kStreamMaxL = 32;",),
+    "wavenet_fused.hip": ("constexpr int kFT = 96;", "constexpr int kFH = 8;"),
+    "wavenet_stream.hip": ("constexpr int kST = 96;", "constexpr int kSH = 8;"),
+}
+
+
+def test_one_launch_matrix_mirrors_the_dispatch_of_the_wavenet_kernels():
+    """tests/test_gpu_wavenet_one_launch_matrix.py places its cases by a Python mirror of the conditions under which dmel_wavenet_forward and
+    the streaming entries take the one-launch kernels.  The lines it transcribes must still read as transcribed, and the mirror must say
+    what they say at every edge."""
+    import test_gpu_wavenet_one_launch_matrix as m
+    for name, lines in ONE_LAUNCH_PREDICATE_SOURCE.items():
+        src = open(os.path.join(ROOT, "dmel_codec_amd", "csrc", name)).read()
+        for line in lines:
+            assert line in src, (f"{name} no longer contains `{line}`: update eligible() / MAX_T / MAX_STREAM_L / SUBSTEP and the case tables of "
+                                 "test_gpu_wavenet_one_launch_matrix.py")
+    assert (m.MAX_T, m.MAX_STREAM_L, m.SUBSTEP) == (96, 32, 96)
+
+    def ok(C, has_in, Cin, Ccond, has_out, cycle):          # the first line, term for term
+        return C > 32 and C <= 80 and not Ccond and not has_out and (not has_in or Cin <= 16) and (cycle == 0 or cycle <= 4)
+
+    for C in (1, 32, 33, 80, 81, 512):
+        for Cin in (None, 1, 16, 17, 80):
+            for Ccond in (None, 0, 8):
+                for has_out in (False, True):
+                    for cycle in (0, 1, 4, 5):
+                        assert m.eligible(C, Cin, Ccond, has_out, cycle) == ok(C, Cin is not None, Cin or C, Ccond or 0, has_out, cycle)
+
+
 def test_conv_matrix_guards_catch_missing_and_stray_stores():
     """The guarded buffers of tests/test_gpu_conv_matrix.py (device-agnostic, exercised here on host tensors): an output element that
     is never stored, a store past either end of an output and a write into an input's NaN band each fail the check."""
