@@ -1387,3 +1387,98 @@ extern "C" int dmel_crossfade_items(float* const* blend, float* const* tail, con
   DMEL_HIP(hipGetLastError());
   return DMEL_OK;
 }
+
+namespace dmel {
+
+// ---- ragged 2-D copies of 4-byte words: streaming state into and out of a snapshot (include/dmel_hip.h: dmel_stream_pack_items) ------
+// Row r of the table is (src, dst, rows, cols, src pitch, dst pitch, first tile, column tiles), eight int64; a workgroup owns one tile of
+// kPackRows rows by kPackCols columns of the descriptor that owns tile blockIdx.x: the last one whose first tile is not behind it (an
+// idle descriptor owns no tile, so the one behind it starts where it does).  The search and the row are uniform over the workgroup.
+// A wave takes one row of the tile at a time, rows w and w + 4: in the 16-byte path a lane moves one uint4, 1 KiB per wave and
+// instruction, and the lane that meets the end of the row moves its last cols % 4 words one by one; in the word path a lane moves the
+// words lane, lane + 64, ... of the row.  Words are uint32 on both paths: no float is ever formed.  No LDS, no atomics.
+constexpr int kPackWords = 8, kPackRows = 8, kPackCols = 256;
+__global__ __launch_bounds__(256) void stream_pack_kernel(const int64_t* __restrict__ tab, int R) {
+  const int64_t tile = blockIdx.x;
+  int a = 0, b = R - 1;
+  while (a < b) {
+    const int mid = (a + b + 1) >> 1;
+    if (tab[(size_t)mid * kPackWords + 6] <= tile) a = mid;
+    else b = mid - 1;
+  }
+  const int64_t* row = tab + (size_t)a * kPackWords;
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(row[0]);
+  uint32_t* dst = reinterpret_cast<uint32_t*>(row[1]);
+  const int64_t rows = row[2], cols = row[3], sp = row[4], dp = row[5], local = tile - row[6], ct = row[7];
+  if (ct <= 0 || local < 0) return;
+  const int64_t r0 = (local / ct) * kPackRows, c0 = (local % ct) * kPackCols;
+  if (r0 >= rows || c0 >= cols) return;
+  const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+  const bool vec = ((row[0] | row[1]) & 15) == 0 && (rows == 1 || ((sp | dp) & 3) == 0);
+  for (int k = wave; k < kPackRows; k += 4) {
+    const int64_t i = r0 + k;
+    if (i >= rows) break;
+    const uint32_t* s = src + i * sp;
+    uint32_t* d = dst + i * dp;
+    if (vec) {
+      const int64_t c = c0 + 4 * lane;
+      if (c + 4 <= cols) {
+        *reinterpret_cast<uint4*>(d + c) = *reinterpret_cast<const uint4*>(s + c);
+      } else {
+        for (int64_t t = c; t < cols; ++t) d[t] = s[t];
+      }
+    } else {
+      const int64_t end = c0 + kPackCols < cols ? c0 + kPackCols : cols;
+      for (int64_t t = c0 + lane; t < end; t += 64) d[t] = s[t];
+    }
+  }
+}
+
+}  // namespace dmel
+
+extern "C" int dmel_stream_pack_items(const void* const* src, void* const* dst, const int64_t* rows, const int64_t* cols,
+                                      const int64_t* src_pitch, const int64_t* dst_pitch, int R, void* table_scratch, void* stream) {
+  using namespace dmel;
+  DMEL_CHECK_ARG(src && dst && rows && cols && src_pitch && dst_pitch && table_scratch, "stream_pack_items: NULL argument");
+  DMEL_CHECK_ARG(R >= 1 && R <= 65535, "stream_pack_items: %d rows, expected 1 .. 65535", R);
+  DMEL_CHECK_ARG(((uintptr_t)table_scratch & 7) == 0, "stream_pack_items: table_scratch is not 8-byte aligned");
+  std::vector<int64_t> tab((size_t)kPackWords * R);
+  const int64_t limit = (int64_t)1 << 40;
+  int64_t tiles = 0;
+  double words = 0.0;
+  for (int r = 0; r < R; ++r) {
+    DMEL_CHECK_ARG(rows[r] >= 0 && cols[r] >= 0, "stream_pack_items: row %d: %lld rows of %lld words: a negative count", r, (long long)rows[r],
+                   (long long)cols[r]);
+    int64_t* it = tab.data() + (size_t)kPackWords * r;
+    it[6] = tiles;
+    if (rows[r] == 0 || cols[r] == 0) continue;       // idle: its pointers and pitches are not looked at (the table row stays 0)
+    DMEL_CHECK_ARG(src[r] && dst[r], "stream_pack_items: row %d: NULL source or destination", r);
+    DMEL_CHECK_ARG((((uintptr_t)src[r] | (uintptr_t)dst[r]) & 3) == 0, "stream_pack_items: row %d: a pointer is not 4-byte aligned", r);
+    DMEL_CHECK_ARG(rows[r] < limit && cols[r] < limit, "stream_pack_items: row %d: %lld rows of %lld words exceed 2^40", r, (long long)rows[r],
+                   (long long)cols[r]);
+    if (rows[r] > 1) {
+      DMEL_CHECK_ARG(src_pitch[r] >= cols[r] && dst_pitch[r] >= cols[r],
+                     "stream_pack_items: row %d: pitches %lld and %lld are below its %lld words per row", r, (long long)src_pitch[r],
+                     (long long)dst_pitch[r], (long long)cols[r]);
+      const int64_t top = (limit - 1) / rows[r];       // rows * pitch < 2^40 without forming a product that can overflow int64
+      DMEL_CHECK_ARG(src_pitch[r] <= top && dst_pitch[r] <= top,
+                     "stream_pack_items: row %d: %lld rows at pitches %lld and %lld exceed 2^40 words", r, (long long)rows[r],
+                     (long long)src_pitch[r], (long long)dst_pitch[r]);
+    }
+    const int64_t ct = (cols[r] + kPackCols - 1) / kPackCols, rt = (rows[r] + kPackRows - 1) / kPackRows;
+    it[0] = (int64_t)(uintptr_t)src[r]; it[1] = (int64_t)(uintptr_t)dst[r]; it[2] = rows[r]; it[3] = cols[r];
+    it[4] = rows[r] > 1 ? src_pitch[r] : 0; it[5] = rows[r] > 1 ? dst_pitch[r] : 0; it[7] = ct;
+    tiles += ct * rt;
+    DMEL_CHECK_ARG(tiles <= 0x7fffffff, "stream_pack_items: row %d: more than 2^31 - 1 tiles", r);
+    words += (double)rows[r] * (double)cols[r];
+  }
+  if (tiles == 0) return DMEL_OK;                     // every row idle
+  hipStream_t s = (hipStream_t)stream;
+  DMEL_TRY(launch_table_put(tab.data(), tab.size() * sizeof(int64_t), table_scratch, s));
+  {
+    ProfScope ps("small", s, 0.0, 8.0 * words), count("stream_pack", s, 0.0, 0.0);
+    hipLaunchKernelGGL(stream_pack_kernel, dim3((unsigned)tiles), dim3(256), 0, s, static_cast<const int64_t*>(table_scratch), R);
+  }
+  DMEL_HIP(hipGetLastError());
+  return DMEL_OK;
+}

@@ -132,6 +132,41 @@ class EncodeSchedule:
         self.finished = final
         return st
 
+    def state(self) -> dict:
+        """the counters as plain Python values -- nothing derived from the geometry: what a snapshot of a session carries"""
+        return dict(samples=self.samples, frames=self.frames, levels=list(self.levels), tokens=self.tokens, finished=self.finished)
+
+    @classmethod
+    def from_state(cls, geo: EncodeGeometry, state: Mapping) -> "EncodeSchedule":
+        """the schedule that returns, for every later step(n, final), the step the one state() was taken from returns"""
+        sc = cls(geo)
+        sc.levels = _state_levels(state, len(geo.dilations) + 1)
+        sc.samples, sc.frames, sc.tokens, sc.finished = int(state["samples"]), int(state["frames"]), int(state["tokens"]), bool(state["finished"])
+        return sc
+
+
+def _state_levels(state: Mapping, depth: int) -> List[int]:
+    levels = [int(v) for v in state["levels"]]
+    if len(levels) != depth:
+        raise ValueError(f"a state of {len(levels)} level frontiers for a schedule of {depth}: the depth of the WaveNet differs")
+    return levels
+
+
+def encode_need_from(geo: EncodeGeometry, last_level: int, tokens: int) -> int:
+    """The oldest column an encode slot still reads when a step starts from the frontier `last_level` of the last WaveNet level and
+    `tokens` released tokens: the next block window reaches max(dilations) behind the last level, the quantiser's window starts its
+    left context in front of the next token (EncodeStep.quant_window[0])."""
+    left, _ = geo.quant_context
+    F = geo.factor
+    return max(0, min(last_level - max(geo.dilations), max(0, tokens - (left + F - 1) // F) * F))
+
+
+def encode_live_window(sched: EncodeSchedule) -> Tuple[int, int]:
+    """[lo, hi) in absolute frames: the columns of an encode slot a later step reads -- exactly what a re-base in front of the next push
+    would keep (EncodeSessions._rebase) -- up to the newest mel frame."""
+    lo = encode_need_from(sched.geo, sched.levels[-1], sched.tokens)
+    return lo, max(lo, sched.frames)
+
 
 def session_rows(slots: int, steps: Mapping[int, EncodeStep], origins: Sequence[int]) -> Tuple[List[int], List[int], List[int]]:
     """A pool of independent streams (EncodeSessions) holds one EncodeSchedule per slot; one step of the pool hands the encoder one
@@ -256,6 +291,29 @@ class DecodeSchedule:
         self.emitted = e_new
         self.finished = final
         return st
+
+    def state(self) -> dict:
+        """the counters as plain Python values -- nothing derived from the geometry: what a snapshot of a session carries"""
+        return dict(tokens=self.tokens, z_valid=self.z_valid, levels=list(self.levels), emitted=self.emitted, tok_origin=self.tok_origin,
+                    finished=self.finished)
+
+    @classmethod
+    def from_state(cls, geo: DecodeGeometry, state: Mapping) -> "DecodeSchedule":
+        """the schedule that returns, for every later step(n, final), the step the one state() was taken from returns"""
+        sc = cls(geo)
+        sc.levels = _state_levels(state, len(geo.dilations) + 1)
+        sc.tokens, sc.z_valid, sc.emitted = int(state["tokens"]), int(state["z_valid"]), int(state["emitted"])
+        sc.tok_origin, sc.finished = int(state["tok_origin"]), bool(state["finished"])
+        return sc
+
+
+def decode_live_window(sched) -> Tuple[int, int]:
+    """[lo, hi) in absolute frames: the columns of a decode slot a later step reads -- from the schedule's need_from, which is what a
+    re-base in front of the next push would keep (decode_rebase; an EarlyDecodeSchedule with a fade keeps one frame more), to the
+    condition frontier, behind which nothing has been written.  sched: a DecodeSchedule or an EarlyDecodeSchedule."""
+    z_valid = sched.exact.z_valid if isinstance(sched, EarlyDecodeSchedule) else sched.z_valid
+    lo = sched.need_from
+    return lo, max(lo, z_valid)
 
 
 def decode_capacity(geo: DecodeGeometry, max_push_tokens: int, extra_hold: int = 0) -> int:
@@ -382,6 +440,18 @@ class EarlyDecodeSchedule:
         self.emitted = e_new
         return EarlyDecodeStep(step=st, emit=(e_prev, e_new), shadow=shadow, fade=fade, **row)
 
+    def state(self) -> dict:
+        """the look-ahead of the moment, the fade, the early frontier and the wrapped exact schedule's counters, as plain values"""
+        return dict(lookahead=self.lookahead, fade_frames=self.fade_frames, emitted=self.emitted, exact=self.exact.state())
+
+    @classmethod
+    def from_state(cls, geo: DecodeGeometry, state: Mapping) -> "EarlyDecodeSchedule":
+        """the schedule that returns, for every later step(n, final), the step the one state() was taken from returns"""
+        sc = cls(geo, int(state["lookahead"]), fade_frames=int(state["fade_frames"]))
+        sc.exact = DecodeSchedule.from_state(geo, state["exact"])
+        sc.emitted = int(state["emitted"])
+        return sc
+
 
 # ---------------------------------------------------------------------------------------------------- streaming sample-rate conversion
 def resample_width(orig: int, new: int, lowpass_filter_width: int = 6, rolloff: float = 0.99) -> int:
@@ -473,6 +543,20 @@ class ResampleSchedule:
         self.emitted = o_new
         self.finished = final
         return st
+
+    def state(self) -> dict:
+        """the counters as plain Python values -- nothing derived from the rates: what a snapshot of a session carries"""
+        return dict(samples=self.samples, emitted=self.emitted, finished=self.finished)
+
+    @classmethod
+    def from_state(cls, rates: Tuple[int, int], state: Mapping) -> "ResampleSchedule":
+        """rates: (orig_freq, new_freq).  The schedule that returns, for every later step(n, final), the step the one state() was
+        taken from returns.  A state that no schedule of these rates can be in (outputs that are not whole groups) is refused."""
+        sc = cls(int(rates[0]), int(rates[1]))
+        sc.samples, sc.emitted, sc.finished = int(state["samples"]), int(state["emitted"]), bool(state["finished"])
+        if sc.samples < 0 or sc.emitted < 0 or (not sc.finished and sc.emitted != sc.outputs_ready(sc.samples)):
+            raise ValueError(f"a resampler state of {sc.emitted} outputs after {sc.samples} samples: not a state of {rates[0]} -> {rates[1]} Hz")
+        return sc
 
 
 def resample_max_outputs(orig_freq: int, new_freq: int, n: int) -> int:

@@ -13,6 +13,7 @@ usually at 8 kHz): the conversion is folded into the per-slot copy a pool makes 
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import math
 from typing import Dict, Iterable, List, Mapping, Optional, Tuple
 
@@ -20,13 +21,14 @@ import torch
 
 from .. import _lib
 from ..utils import crossfade, pcm
+from .stream_park import VERSION as PARK_VERSION, ParkingPool, plain
 from .stream_schedule import (DecodeGeometry, DecodeSchedule, EarlyDecodeSchedule, EncodeGeometry, EncodeSchedule, decode_capacity,
-                              decode_rebase, resample_max_outputs, session_rows)
+                              decode_live_window, decode_rebase, encode_live_window, encode_need_from, resample_max_outputs, session_rows)
 
 _WIRE_DTYPES = {dt for name, (_, dt) in pcm.FORMATS.items() if name != "f32"}     # torch.int16, torch.uint8
 
 
-class EncodeSessions:
+class EncodeSessions(ParkingPool):
     """`slots` independent incremental encodes, each with the ids of encode() on its own finished clip.
 
         slot = pool.open()                                   # a free slot, fresh state; open(sample_rate=48000): a session at that rate;
@@ -79,6 +81,15 @@ class EncodeSessions:
     float path with no convert launch.  A 1-D or (1, n) push to a slot with channels, or an (n, c) push to a mono slot, is a
     ValueError.  Not served: weights, channel maps, more than 8 channels, planar (channel-first) pushes, the lockstep
     StreamingEncoder and whole-clip encode() (callers have utils.pcm.downmix).
+
+    A session is not tied to its slot: snapshot(slots) gathers everything the named sessions own -- the live window of mel, of every
+    level's history, of the skip sums and of the features (stream_schedule.encode_live_window: what a re-base in front of the next
+    push would keep), the sample tail, the resampler tail, the counters -- with ONE dmel_stream_pack_items launch into one blob;
+    drop(slot) frees a slot without flushing it; park(slots) is both; restore(snapshots) continues the sessions in free slots of
+    this or another pool of the same codec (other slots, max_push_samples and capacity are fine) with ONE launch, each window at
+    column 0 of its zeroed rows.  The ids of a parked and restored session are the bits of the uninterrupted one.  Refused with
+    ValueError, no slot taken: the other kind, another geometry, width or depth, a rate the pool did not declare, a window or a
+    tail that does not fit, an unknown format version.  Equal weights are the caller's contract (models/stream_park.py).
 
     Only encoders the one-launch streaming kernel takes (residual channels in (32, 80], no condition, no output projection,
     dilations <= 8, fp32): anything else is refused at construction.
@@ -263,13 +274,85 @@ class EncodeSessions:
         """make room for the frames of step `st` in slot s: drop the columns nothing reads again and shift that slot's rows"""
         if st.frames[1] - self.origin[s] <= self.cap:
             return
-        need_from = max(0, min(st.prev[self.L] - self.maxdil, st.quant_window[0]))
+        need_from = encode_need_from(self.geo, st.prev[self.L], st.tokens[0])     # the lower end of encode_live_window in front of the step
         shift, keep = need_from - self.origin[s], max(0, st.frames[0] - need_from)
         if st.frames[1] - need_from > self.cap:       # cannot happen: cap covers twice the widest window (want_max)
             raise RuntimeError(f"slot {s}: {st.frames[1] - need_from} columns do not fit the capacity {self.cap}")
         for v in self._slot_views(s):
             v[..., :keep] = v[..., shift:shift + keep].clone()
         self.origin[s] = need_from
+
+    # -- a session leaves its slot and comes back (models/stream_park.py) ----------------------------------------------------
+    _park_kind, _park_windowed = "encode", ("mel", "hist.", "skip", "feat")
+
+    def _park_meta(self, s: int) -> dict:
+        lo, hi = encode_live_window(self.sched[s])
+        return dict(version=PARK_VERSION, kind="encode", geometry=plain(dataclasses.asdict(self.geo)), G=self.G, C=self.C, L=self.L,
+                    n_mels=self.n_mels, codec_rate=self.codec_rate, rate=self.rate[s], sample_format=self.fmt[s], channels=self.ch[s],
+                    channel=None if self.pick[s] < 0 else self.pick[s], lookahead=None, fade=0, has_tail=False, s0=self.s0[s],
+                    tail=self.tail[s], schedule=self.sched[s].state(),
+                    resampler=self.rs.slot_state(s) if self.rs is not None and self._converts(s) else None, window=[lo, hi])
+
+    def _park_shapes(self, meta: Mapping) -> List[Tuple[str, int, int]]:
+        W, rows = meta["window"][1] - meta["window"][0], self.G * self.C
+        rs = meta["resampler"]
+        return ([("mel", self.n_mels, W)] + [(f"hist.{l}", rows, W) for l in range(self.L + 1)] + [("skip", rows, W), ("feat", rows, W),
+                ("samples", 1, meta["tail"]), ("resampler", 1, rs["fill"] if rs else 0)])
+
+    def _park_rows(self, s: int) -> Dict[str, torch.Tensor]:
+        b, G = self.buf, self.G
+        rows = {"mel": b["mel"][s], "skip": b["skip"][s * G:(s + 1) * G], "feat": b["feat"][s * G:(s + 1) * G],
+                "samples": b["samples"][s:s + 1]}
+        for l in range(self.L + 1):
+            rows[f"hist.{l}"] = b["hist"][l, s * G:(s + 1) * G]             # the slot's G rows are contiguous: one piece per level
+        if self.rs is not None and self.rs.buf is not None:
+            rows["resampler"] = self.rs.buf["rows"][s:s + 1]
+        return rows
+
+    def _park_check(self, meta: Mapping) -> None:
+        g = self.geo
+        if plain(meta["geometry"]) != plain(dataclasses.asdict(g)):
+            raise ValueError(f"a session of geometry {meta['geometry']} into a pool of geometry {dataclasses.asdict(g)}")
+        for key, mine in (("G", self.G), ("C", self.C), ("L", self.L), ("n_mels", self.n_mels), ("codec_rate", self.codec_rate)):
+            if meta[key] != mine:
+                raise ValueError(f"a session with {key} = {meta[key]} into a pool with {key} = {mine}")
+        if meta["rate"] != self.codec_rate and meta["rate"] not in self.sample_rates:
+            raise ValueError(f"a session at {meta['rate']} Hz: the pool was built for {(self.codec_rate,) + self.sample_rates} Hz "
+                             f"(declare the rate in sample_rates=)")
+        pcm.check_format(meta["sample_format"])
+        pcm.check_channel(meta["channel"], pcm._check_channels(meta["channels"]))
+        sc = EncodeSchedule.from_state(g, meta["schedule"])
+        if list(encode_live_window(sc)) != list(meta["window"]):
+            raise ValueError(f"window {meta['window']} is not the live window {encode_live_window(sc)} of the session's schedule")
+        if sc.finished:
+            raise ValueError("the session has finished")
+        lo, hi = meta["window"]
+        room = self.codec_push // g.hop + 1 + (g.n_fft - g.pad + g.hop - 1) // g.hop
+        if hi - lo + room > self.cap:
+            raise ValueError(f"a window of {hi - lo} frames and one maximal push ({room} frames) do not fit the capacity {self.cap}")
+        if not 0 <= meta["tail"] <= self.width - self.codec_push:
+            raise ValueError(f"a sample tail of {meta['tail']} samples and one maximal push do not fit a row of {self.width} samples")
+        if (meta["resampler"] is not None) != (meta["rate"] != self.codec_rate):
+            raise ValueError("a resampler state goes with a session at another rate than the codec's, and only with it")
+        if meta["resampler"] is not None:
+            if list(meta["resampler"]["pair"]) != [meta["rate"], self.codec_rate]:
+                raise ValueError(f"a resampler state for {meta['resampler']['pair']} Hz in a session at {meta['rate']} Hz")
+            self.rs.check_state(meta["resampler"])
+
+    def _park_adopt(self, s: int, meta: Mapping) -> None:
+        self.sched[s] = EncodeSchedule.from_state(self.geo, meta["schedule"])
+        self.origin[s], self.s0[s], self.tail[s] = meta["window"][0], meta["s0"], meta["tail"]
+        self.rate[s], self.fmt[s], self.ch[s] = meta["rate"], meta["sample_format"], meta["channels"]
+        self.pick[s] = -1 if meta["channel"] is None else meta["channel"]
+        if self.rs is not None:
+            if meta["resampler"] is not None:
+                self.rs.adopt(s, meta["resampler"])
+            else:
+                self.rs.open(s, self.codec_rate, self.codec_rate)
+
+    def _park_zero(self, s: int) -> None:
+        for v in self._slot_views(s):
+            v.zero_()
 
     # -- one step ----------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -408,7 +491,7 @@ def pad_windows(wins: List[torch.Tensor]) -> Tuple[torch.Tensor, Optional[List[i
     return batch, widths
 
 
-class DecodeSessions:
+class DecodeSessions(ParkingPool):
     """`slots` independent incremental decodes, each with the audio and mel of decode() on its own finished token sequence.
 
         slot = pool.open()                                              # a free slot, fresh state; open(output_sample_rate=48000);
@@ -513,6 +596,20 @@ class DecodeSessions:
     fading slot launches what it did; sessions without a fade in such a pool return the pieces they always returned; a pool built
     with crossfade_samples=0 allocates, sizes `cap` and launches exactly as before and refuses crossfade_samples at open.  A fade
     without lookahead_frames or with return_audios=False is a ValueError.  Not served: fades longer than a frame, other windows.
+
+    A session is not tied to its slot: snapshot(slots) gathers everything the named sessions own -- the live window of every level's
+    history, of the skip sums, the condition and the mel (stream_schedule.decode_live_window: what a re-base in front of the next push
+    would keep), the valid part of the token tail and of the noise tail, the fade tail when one is held, the resampler tail, the
+    counters -- with ONE dmel_stream_pack_items launch into one blob; drop(slot) frees a slot without flushing it (a reply's abort);
+    park(slots) is both; restore(snapshots) continues the sessions in free slots of this or another pool of the same codec (other
+    slots, max_push_tokens and capacity are fine) with ONE launch, each window at column 0 of its zeroed rows.  Every later piece of
+    a parked and restored session carries the bits of the uninterrupted one; a snapshot restored while its session lives on is a
+    BRANCH: both go on from the same state (an LM server's two continuations, or the roll-back of rejected tokens).  Not shipped:
+    shadow rows, fade weights, table scratch, and torch's RNG -- a session pushed without noise draws at the time of the push, in
+    the process it runs in.  Refused with ValueError, no slot taken: the other kind, another geometry, width or depth, a rate the
+    pool did not declare, an early session into a pool without early_emit, a fade above the pool's, audio into a
+    return_audios=False pool, a window or tail that does not fit, an unknown format version.  Equal weights are the caller's
+    contract (models/stream_park.py).
 
     Out of scope, NotImplementedError: overlap_vocoder, graph_chunk_tokens, and a pool-wide output_sample_rate (a pool has no rate of
     its own).
@@ -732,6 +829,106 @@ class DecodeSessions:
             for v in self._slot_views(s):
                 v[..., :keep] = v[..., shift:shift + keep].clone()
         self.origin[s] = new
+
+    # -- a session leaves its slot and comes back (models/stream_park.py) ----------------------------------------------------
+    _park_kind, _park_windowed = "decode", ("hist.", "skip", "cond", "mel")
+
+    def _park_meta(self, s: int) -> dict:
+        sch = self.sched[s]
+        early = isinstance(sch, EarlyDecodeSchedule)
+        lo, hi = decode_live_window(sch)
+        dec = self.codec.decoder
+        return dict(version=PARK_VERSION, kind="decode", geometry=plain(dataclasses.asdict(self.geo)), G=self.G, C=self.C, L=self.L,
+                    cond_channels=dec.condition_channels, n_mels=dec.output_channels, up=self.up, return_audios=self.return_audios,
+                    voc_rate=self.voc_rate, rate=self.rate[s], sample_format=self.fmt[s], channels=self.ch[s], channel=None,
+                    lookahead=sch.lookahead if early else None, fade=self.fade[s], has_tail=self.has_tail[s],
+                    tok_origin=self.tok_origin[s], n_noise=self.n_noise[s], schedule=sch.state(),
+                    resampler=self.rs.slot_state(s) if self.rs is not None and self.rate[s] != self.voc_rate else None, window=[lo, hi])
+
+    @staticmethod
+    def _park_exact(meta: Mapping) -> Mapping:
+        return meta["schedule"] if meta["lookahead"] is None else meta["schedule"]["exact"]
+
+    def _park_shapes(self, meta: Mapping) -> List[Tuple[str, int, int]]:
+        W = meta["window"][1] - meta["window"][0]
+        rs = meta["resampler"]
+        return ([(f"hist.{l}", self.C, W) for l in range(self.L + 1)] +
+                [("skip", self.C, W), ("cond", meta["cond_channels"], W), ("mel", meta["n_mels"], W),
+                 ("tokens", self.G, self._park_exact(meta)["tokens"] - meta["tok_origin"]), ("noise", self.C, meta["n_noise"]),
+                 ("fade_tail", 1, meta["fade"] if meta["has_tail"] else 0), ("resampler", 1, rs["fill"] if rs else 0)])
+
+    def _park_rows(self, s: int) -> Dict[str, torch.Tensor]:
+        b = self.buf
+        rows = {"skip": b["skip"][s], "cond": b["cond"][s], "mel": b["mel"][s], "tokens": b["tokens"][s], "noise": b["noise"][s]}
+        for l in range(self.L + 1):
+            rows[f"hist.{l}"] = b["hist"][l, s]
+        if "fade_tail" in b:
+            rows["fade_tail"] = b["fade_tail"][s:s + 1]
+        if self.rs is not None and self.rs.buf is not None:
+            rows["resampler"] = self.rs.buf["rows"][s:s + 1]
+        return rows
+
+    def _park_check(self, meta: Mapping) -> None:
+        g, f, dec = self.geo, self.geo.factor, self.codec.decoder
+        if plain(meta["geometry"]) != plain(dataclasses.asdict(g)):
+            raise ValueError(f"a session of geometry {meta['geometry']} into a pool of geometry {dataclasses.asdict(g)}")
+        for key, mine in (("G", self.G), ("C", self.C), ("L", self.L), ("cond_channels", dec.condition_channels),
+                          ("n_mels", dec.output_channels), ("up", self.up), ("voc_rate", self.voc_rate)):
+            if meta[key] != mine:
+                raise ValueError(f"a session with {key} = {meta[key]} into a pool with {key} = {mine}")
+        if not self.return_audios and (meta["return_audios"] or meta["sample_format"] != "f32" or meta["channels"] != 1 or
+                                       meta["rate"] is not None):
+            raise ValueError("a session with audio (its format, rate or channels) into a pool built with return_audios=False")
+        if meta["rate"] != self.voc_rate and meta["rate"] not in self.output_sample_rates:
+            raise ValueError(f"a session at {meta['rate']} Hz: the pool was built for {(self.voc_rate,) + self.output_sample_rates} Hz "
+                             f"(declare the rate in output_sample_rates=)")
+        pcm.check_format(meta["sample_format"])
+        pcm._check_channels(meta["channels"])
+        if meta["lookahead"] is not None and not self.early_emit:
+            raise ValueError("a session with lookahead_frames into a pool built without early_emit=True: it has no shadow rows to "
+                             "decode ahead in")
+        if meta["fade"] > self.fade_max:
+            raise ValueError(f"a session with crossfade_samples={meta['fade']} into a pool built with crossfade_samples={self.fade_max}")
+        if meta["fade"] < 0 or (meta["fade"] and meta["lookahead"] is None) or (meta["has_tail"] and not meta["fade"]):
+            raise ValueError("a cross-fade goes with a look-ahead, and a tail with a cross-fade")
+        sc = (DecodeSchedule if meta["lookahead"] is None else EarlyDecodeSchedule).from_state(g, meta["schedule"])
+        if meta["lookahead"] is not None and sc.fade_frames != (1 if meta["fade"] else 0):
+            raise ValueError("the schedule's fade_frames do not go with the session's cross-fade")
+        if list(decode_live_window(sc)) != list(meta["window"]):
+            raise ValueError(f"window {meta['window']} is not the live window {decode_live_window(sc)} of the session's schedule")
+        if sc.finished:
+            raise ValueError("the session has finished")
+        lo, hi = meta["window"]
+        if sc.tokens * f - lo + self.max_push * f > self.cap:
+            raise ValueError(f"the frames [{lo}, {sc.tokens * f}) and one maximal push ({self.max_push * f} frames) do not fit the "
+                             f"capacity {self.cap}")
+        if not 0 <= sc.tokens - meta["tok_origin"] <= self.tok_width - self.max_push:
+            raise ValueError(f"a token tail of {sc.tokens - meta['tok_origin']} tokens does not fit this pool's {self.tok_width}")
+        if not 0 <= meta["n_noise"] <= self.noise_width - self.max_push * f:
+            raise ValueError(f"a noise tail of {meta['n_noise']} frames does not fit this pool's {self.noise_width}")
+        if (meta["resampler"] is not None) != (meta["rate"] != self.voc_rate):
+            raise ValueError("a resampler state goes with a session at another rate than the vocoder's, and only with it")
+        if meta["resampler"] is not None:
+            if list(meta["resampler"]["pair"]) != [self.voc_rate, meta["rate"]]:
+                raise ValueError(f"a resampler state for {meta['resampler']['pair']} Hz in a session at {meta['rate']} Hz")
+            self.rs.check_state(meta["resampler"])
+
+    def _park_adopt(self, s: int, meta: Mapping) -> None:
+        self.sched[s] = (DecodeSchedule if meta["lookahead"] is None else EarlyDecodeSchedule).from_state(self.geo, meta["schedule"])
+        self.origin[s], self.tok_origin[s], self.n_noise[s] = meta["window"][0], meta["tok_origin"], meta["n_noise"]
+        self.fade[s], self.has_tail[s] = meta["fade"], meta["has_tail"]
+        self.rate[s], self.fmt[s], self.ch[s] = meta["rate"], meta["sample_format"], meta["channels"]
+        if self.rs is not None:
+            if meta["resampler"] is not None:
+                self.rs.adopt(s, meta["resampler"])
+            else:
+                self.rs.open(s, self.voc_rate, self.voc_rate)
+
+    def _park_zero(self, s: int) -> None:
+        for v in self._slot_views(s):
+            v.zero_()
+        if self.fade[s]:                              # not state: rebuilt from F, as a fresh slot's are
+            self.buf["fade_w"][s, :self.fade[s]] = crossfade.weights(self.fade[s]).to(self.buf["fade_w"].device)
 
     # -- one step ----------------------------------------------------------------------------------------------------------
     @torch.no_grad()

@@ -225,6 +225,7 @@ class SessionResampler:
         self.arena_floats = off
         self.sched: List[Optional[ResampleSchedule]] = [None] * self.S
         self.rate = [0] * self.S                      # index into pairs; -1: equal rates, nothing to convert
+        self.pair: List[Tuple[int, int]] = [(0, 0)] * self.S     # the rates the slot was opened with, by value
         self.s0 = [0] * self.S
         self.fill = [0] * self.S                      # valid samples in the slot's row
         self.buf = None
@@ -241,10 +242,40 @@ class SessionResampler:
             raise ValueError(f"{o} -> {n} Hz was not declared at construction ({self.pairs})")
         self.sched[slot] = ResampleSchedule(o, n)
         self.rate[slot] = -1 if o == n else self.pairs.index((o, n))
+        self.pair[slot] = (o, n)
         self.s0[slot] = self.fill[slot] = 0
 
     def close(self, slot: int) -> None:
         self.sched[slot] = None
+
+    # -- a slot's state leaves and comes back (models/stream_sessions.py: snapshot / restore) ------------------------------------
+    def slot_state(self, slot: int) -> dict:
+        """what an open slot carries besides the samples of its tail -- buf["rows"][slot, :fill], ONE descriptor of a pack launch --
+        as plain values: the rate PAIR by value (another pool may declare its pairs in another order), s0, the length of the tail
+        and the schedule's counters"""
+        if not 0 <= slot < self.S or self.sched[slot] is None:
+            raise RuntimeError(f"slot {slot} is not open")
+        return dict(pair=list(self.pair[slot]), s0=self.s0[slot], fill=self.fill[slot], sched=self.sched[slot].state())
+
+    def check_state(self, state: Mapping) -> None:
+        """ValueError when no slot of this pool can take the state: a pair that was not declared, a tail that does not fit a row"""
+        o, n = (int(v) for v in state["pair"])
+        if o != n and (o, n) not in self.pairs:
+            raise ValueError(f"{o} -> {n} Hz was not declared at construction ({self.pairs})")
+        sc = ResampleSchedule.from_state((o, n), state["sched"])
+        if not 0 <= int(state["fill"]) <= self.width - self.max_push or (o != n and int(state["fill"]) >= sc.kw):
+            raise ValueError(f"a resampler tail of {state['fill']} samples does not fit a row of this pool")
+
+    def adopt(self, slot: int, state: Mapping) -> None:
+        """slot continues the stream slot_state() was taken from; the samples of its tail belong at buf["rows"][slot, :fill]"""
+        if not 0 <= slot < self.S:
+            raise ValueError(f"slot {slot!r} out of range (0 .. {self.S - 1})")
+        self.check_state(state)
+        o, n = (int(v) for v in state["pair"])
+        self.sched[slot] = ResampleSchedule.from_state((o, n), state["sched"])
+        self.rate[slot] = -1 if o == n else self.pairs.index((o, n))
+        self.pair[slot] = (o, n)
+        self.s0[slot], self.fill[slot] = int(state["s0"]), int(state["fill"])
 
     def is_open(self, slot: int) -> bool:
         return self.sched[slot] is not None

@@ -470,6 +470,25 @@ int dmel_stream_fork_items(float* hist, float* skip, float* cond /*nullable*/, f
 int dmel_crossfade_items(float* const* blend /*entries nullable*/, float* const* tail, const float* const* save /*entries nullable*/,
                          const float* const* w, const int64_t* F, int R, void* table_scratch, void* stream);
 
+/* R independent 2-D copies of 4-byte words in ONE launch (csrc/small_ops.hip): what takes the streaming state of live sessions out of
+ * a pool's buffers into a snapshot and back (models/stream_sessions.py: snapshot / restore).  Descriptor r copies rows[r] rows of
+ * cols[r] words: row i goes from src[r] + i * src_pitch[r] to dst[r] + i * dst_pitch[r], pitches in words.  Packing reads windows of
+ * rows of pitch `cap` and writes a dense blob (pitch == cols); unpacking is the same call with the roles swapped, into rows of any
+ * other pitch.  Words move as uint32: NaN payloads and int32 ids come out bit for bit, nothing is canonicalised, no float arithmetic
+ * is done.  A descriptor with rows * cols == 0 is idle and its pointers and pitches are not looked at; when every descriptor is idle
+ * the call returns DMEL_OK and launches nothing.  DMEL_EINVAL, nothing launched, dmel_last_error naming the row: R outside
+ * [1, 65535], a negative count, a NULL or not 4-byte aligned pointer on either side of a live row, a pitch below cols where
+ * rows > 1 (the pitches of a single row are ignored), rows * pitch (or rows, or cols) of 2^40 or more, more than 2^31 - 1 tiles.
+ * OVERLAP IS THE CALLER'S CONTRACT: nothing checks that the destination of one descriptor is not the source or the destination of
+ * another (or of itself); the result of such a call is undefined.  src, dst, rows, cols, src_pitch, dst_pitch are HOST tables of R
+ * entries, copied as launch arguments into table_scratch (8 R int64 of device memory, 8-byte aligned): the caller may overwrite them
+ * as soon as the call returns.  The grid covers the descriptors' own tiles of 8 rows x 256 words, not a bounding box.  A descriptor
+ * whose two base addresses are 16-byte aligned and, where rows > 1, whose two pitches are multiples of 4 words moves 16 bytes per
+ * lane and the last cols % 4 words of a row one by one; every other descriptor moves 4 bytes per lane.  Both paths give the same
+ * bits.  No LDS, no atomics. */
+int dmel_stream_pack_items(const void* const* src, void* const* dst, const int64_t* rows, const int64_t* cols, const int64_t* src_pitch,
+                           const int64_t* dst_pitch, int R, void* table_scratch, void* stream);
+
 /* ConvNeXtBlock (models/modules/firefly.py:337-402; C-ABI row `convnext_block`), standalone: y = x + gamma * pwconv2(gelu(pwconv1(
  * LayerNorm_C(dwconv7(x))))), x / y (N, dim, T).  set_tensor keys: dwconv.weight (dim,1,7), dwconv.bias, norm.weight, norm.bias,
  * pwconv1.weight (4 dim, dim), pwconv1.bias, pwconv2.weight (dim, 4 dim), pwconv2.bias, gamma.  The training entry points follow the

@@ -492,6 +492,35 @@ int main() {
       SA[1] = wav.data() + 2048;                  // a row that only saves
       CK(fade(2));
     }
+    {
+      // the ragged pack: tables of exactly R entries, a table scratch of exactly 8 R int64; its refusals read the host tables only
+      auto state = buf(5 * 99 + 8), blob = buf(5 * 33 + 40);
+      const void* SRC[2] = {state.data() + 1, state.data()};
+      void* DST[2] = {blob.data(), blob.data() + 5 * 33};
+      int64_t RW[2] = {5, 1}, CL[2] = {33, 40}, SP[2] = {99, 0}, DP[2] = {33, 0};
+      std::vector<int64_t> tab(8 * 2);
+      auto pack = [&](int R) { return dmel_stream_pack_items(SRC, DST, RW, CL, SP, DP, R, tab.data(), nullptr); };
+      CK(pack(2));
+      auto refused = [&](int R, const char* row, const char* what) {
+        const int rc = pack(R);
+        if (rc != DMEL_EINVAL || !std::strstr(dmel_last_error(), row)) { std::printf("FAIL stream_pack_items accepted %s (%d: %s)\n", what, rc, dmel_last_error()); ++failures; }
+      };
+      refused(0, "0 rows", "no row");
+      refused(65536, "65536 rows", "more than 65535 rows");
+      RW[1] = -1; refused(2, "row 1", "a negative row count");
+      RW[1] = 1; CL[1] = -40; refused(2, "row 1", "a negative word count");
+      CL[1] = 40; SRC[1] = nullptr; refused(2, "row 1", "a NULL source");
+      SRC[1] = state.data(); DST[0] = nullptr; refused(2, "row 0", "a NULL destination");
+      DST[0] = reinterpret_cast<char*>(blob.data()) + 2; refused(2, "row 0", "a destination that is not 4-byte aligned");
+      DST[0] = blob.data(); SP[0] = 32; refused(2, "row 0", "a source pitch below cols");
+      SP[0] = 99; DP[0] = 32; refused(2, "row 0", "a destination pitch below cols");
+      DP[0] = 33; RW[0] = (int64_t)1 << 34; SP[0] = (int64_t)1 << 6; refused(2, "row 0", "rows * pitch of 2^40");
+      RW[0] = (int64_t)1 << 33; CL[0] = 1; SP[0] = (int64_t)1 << 30; refused(2, "row 0", "rows * pitch of 2^63, which wraps as an int64 product");
+      SP[0] = 99; DP[0] = (int64_t)1 << 30; refused(2, "row 0", "rows * destination pitch of 2^63");
+      CL[0] = 33; DP[0] = 33;
+      RW[0] = 0; CL[1] = 0; SRC[0] = nullptr; DST[1] = nullptr; SP[0] = DP[0] = -1;   // every row idle: pointers and pitches are not looked at
+      CK(pack(2));
+    }
     auto xs = buf(2 * 8 * 3000), ys = buf(2 * 8 * 3000), da = buf(8), db = buf(8);
     CK(dmel_aa_snake_f32(xs.data(), ys.data(), al.data(), be.data(), taps.data(), taps.data(), 1, 2, 8, 3000, nullptr));
     CK(dmel_aa_snake_backward_f32(xs.data(), ys.data(), xs.data(), al.data(), be.data(), da.data(), db.data(), taps.data(), taps.data(), 1, 2, 8, 3000, nullptr));

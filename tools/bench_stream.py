@@ -62,7 +62,13 @@ is from decode()'s (SNR, largest difference at piece boundaries) on the bench's 
 runs only this: S early replies with look-ahead K that cross-fade their pieces over F samples (decode_sessions(early_emit=True,
 crossfade_samples=F), open(lookahead_frames=K, crossfade_samples=F)) against the same replies with F = 0, interleaved in one process:
 the step time of both, and for session 0 of both the largest sample-to-sample step at the piece boundaries beside the median step of
-the stream, on the bench's synthetic weights."""
+the stream, on the bench's synthetic weights.
+
+    python tools/bench_stream.py --sessions 16 --park [--steps 40] [--out profiles/sessions_park.txt]
+
+runs only this: S replies in steady state (64-token pushes), then snapshot + restore of all S of them, (a) as the pool does it -- ONE
+dmel_stream_pack_items launch per direction -- and (b) with one torch slice .clone() per state tensor per slot and a torch.cat, and
+the inverse (tools/bench_park.py): microseconds, bytes moved and GB/s of both, interleaved in one process, APPENDED to --out."""
 import json, math, os, statistics, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -591,6 +597,39 @@ if "--crossfade" in sys.argv:
                                [int(p) for p in arg_after("--push-tokens", "1,4,16").split(",")], int(arg_after("--steps", "40")),
                                arg_after("--out", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                                                "sessions_crossfade.txt")), arg_after("--label", ""))
+    sys.exit(0)
+
+def sessions_park_section(S, steps, out):
+    import bench_park
+    chunk, pushes = 64, 8
+    gl = torch.Generator().manual_seed(7)
+    G, Cn = codec.dmel_groups, codec.decoder.input_channels
+    ids = torch.randint(0, 175, (S, G, chunk * pushes), generator=gl, dtype=torch.int32).to(dev)
+    pool = codec.decode_sessions(S, max_push_tokens=chunk)
+    slots = [pool.open() for _ in range(S)]
+    for j in range(pushes):                                                  # steady state: every slot holds its widest window
+        pool.push({s: ids[i, :, j * chunk:(j + 1) * chunk] for i, s in enumerate(slots)},
+                  noise={s: torch.randn(Cn, chunk * 4, device=dev) for s in slots})
+    result, rows, slots = bench_park.measure(pool, slots, reps=steps)
+    table = [f"snapshot + restore of {S} decode sessions in steady state ({chunk}-token pushes), 100 mel / 10 groups, {pool.L} decoder layers of "
+             f"{pool.C} channels, cap {pool.cap} (tools/bench_stream.py --sessions {S} --park)",
+             f"wall time of one snapshot of all sessions and one restore of all of them incl. host synchronisation, {result['cycles']} cycles, the two "
+             "interleaved in one process, equal words checked;",
+             "one_launch = pool.park + pool.restore (ONE dmel_stream_pack_items launch each); torch_slices = a slice .clone() per tensor per slot "
+             "and a cat, and a slice copy per tensor back",
+             "sessions  way            median us      p10 us      p90 us     n  bytes moved      GB/s"] + rows
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "a") as f:
+        f.write("\n".join(table) + "\n\n")
+    print("\n".join(table), file=sys.stderr)
+    print(json.dumps(result))
+
+
+if "--park" in sys.argv:
+    assert "--sessions" in sys.argv, "--park needs --sessions"
+    sessions_park_section(int(arg_after("--sessions")), int(arg_after("--steps", "40")),
+                          arg_after("--out", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                          "sessions_park.txt")))
     sys.exit(0)
 
 if "--lookahead" in sys.argv:

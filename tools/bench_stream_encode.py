@@ -53,7 +53,13 @@ baseline is the same pool with f32 sessions and the expansion every caller would
 times a steady-state step of S sessions whose wire carries interleaved frames of C channels in a pool that was told so
 (open(sample_format=..., channels=C): ONE convert launch per step that downmixes on the way) against the same pool with mono f32
 sessions and the downmix every caller would do in front, `x.float().sum(1) / C` (with the format's scale or table) per slot.
-Interleaved in one process, equal ids asserted, median and 10th / 90th percentile.  APPENDS its table to --out."""
+Interleaved in one process, equal ids asserted, median and 10th / 90th percentile.  APPENDS its table to --out.
+
+    python tools/bench_stream_encode.py --sessions 16 --park [--out profiles/sessions_park.txt]
+
+S sessions in steady state, then snapshot + restore of all S of them, as the pool does it -- ONE dmel_stream_pack_items launch per
+direction -- against one torch slice .clone() per state tensor per slot and a torch.cat, and the inverse (tools/bench_park.py):
+microseconds, bytes moved and GB/s of both, interleaved in one process.  APPENDS its table to --out."""
 import argparse, json, os, statistics, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -72,6 +78,7 @@ ap.add_argument("--sample-format", default="f32", choices=("f32", "s16", "ulaw",
 ap.add_argument("--channels", type=int, default=1, help="with --sessions: sessions fed interleaved frames of this many channels against the "
                                                         "torch downmix in front")
 ap.add_argument("--ragged", action="store_true", help="with --sessions: another push size per session and step (seeded), chunk / 2 .. chunk")
+ap.add_argument("--park", action="store_true", help="with --sessions: snapshot + restore of all sessions, one launch against torch slices")
 ap.add_argument("--label", default="", help="with --sessions: names the table (the commit measured)")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
@@ -79,6 +86,7 @@ rates = [int(r) for r in args.sample_rate.split(",")] if args.sample_rate else [
 args.sample_rate = rates[0] if rates else None
 if args.out is None:
     args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                            "sessions_park.txt" if args.sessions and args.park else
                             "sessions_channels.txt" if args.sessions and args.channels > 1 else
                             "sessions_pcm.txt" if args.sessions and args.sample_format == "s16" else
                             "sessions_g711.txt" if args.sessions and args.sample_format != "f32" else
@@ -430,6 +438,34 @@ def sessions_channels_section():
     assert same, "the ids of the channel-carrying sessions differ from those of the torch downmix in front"
 
 
+def sessions_park_section():
+    import bench_park
+    S, n, pushes = args.sessions, args.chunk, 12
+    audio = torch.randn(S, pushes * n, device=dev) * 0.1
+    pool = codec.encode_sessions(slots=S, max_push_samples=n)
+    slots = [pool.open() for _ in range(S)]
+    for j in range(pushes):                                                  # steady state: every slot holds its live window
+        pool.push({s: audio[i, j * n:(j + 1) * n] for i, s in enumerate(slots)})
+    r, rows, slots = bench_park.measure(pool, slots)
+    table = [f"snapshot + restore of {S} encode sessions in steady state ({n / SR:.2f} s pushes), 80 mel / 8 groups / 70 channels / 20 layers, "
+             f"cap {pool.cap} (tools/bench_stream_encode.py --sessions {S} --park)",
+             f"wall time of one snapshot of all sessions and one restore of all of them incl. host synchronisation, {r['cycles']} cycles, the two "
+             "interleaved in one process, equal words checked;",
+             "one_launch = pool.park + pool.restore (ONE dmel_stream_pack_items launch each); torch_slices = a slice .clone() per tensor per slot "
+             "and a cat, and a slice copy per tensor back",
+             "sessions  way            median us      p10 us      p90 us     n  bytes moved      GB/s"] + rows
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "a") as f:
+        f.write("\n".join(table) + "\n\n")
+    print("\n".join(table), file=sys.stderr)
+    print(json.dumps(r))
+
+
+if args.park and not args.sessions:
+    ap.error("--park needs --sessions")
+if args.sessions and args.park:
+    sessions_park_section()
+    sys.exit(0)
 if args.channels != 1 and not args.sessions:
     ap.error("--channels needs --sessions")
 if args.sessions and args.channels > 1:
