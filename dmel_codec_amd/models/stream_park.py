@@ -23,11 +23,13 @@ from __future__ import annotations
 
 import copy
 import ctypes as C
+import dataclasses
 from typing import Dict, Iterable, List, Mapping, Optional, Sequence, Tuple
 
 import torch
 
 from .. import _lib
+from ..utils import pcm
 
 VERSION = 1
 PACK_TABLE_WORDS = 8                                   # int64 of table scratch per descriptor of dmel_stream_pack_items
@@ -107,21 +109,156 @@ def _view2d(t: torch.Tensor) -> torch.Tensor:
 
 
 class ParkingPool:
-    """snapshot / drop / park / restore of a pool of sessions.  The pool says what a slot owns:
+    """What a pool of session slots is, once for EncodeSessions and DecodeSessions: which slots are open, the wire options of each
+    session (rate, sample format, channels), buffers from the first use on, a slot's rows made ready for its session, and
+    snapshot / drop / park / restore.  The pool says what a slot owns:
 
-        _park_meta(slot)               the host state of an open slot as plain values (with "window")
+        _resamples_in                  the slot's resampler entry runs (session rate -> own rate); else (own rate -> session rate)
+        _allocate(dev), _slot_views(s) the state buffers; the slot's rows of them, zeroed before its session's first step
+        _park_meta(slot)               the host state of an open slot as plain values (with "window"): the shared keys, its own on top
+        _park_schedule(meta)           the schedule of that state, rebuilt; _live_window(schedule): its live window
         _park_shapes(meta)             [(name, rows, cols)]: the segments of the blob, a pure function of meta and the pool's widths
         _park_rows(slot)               {name: the slot's rows of that piece of device state, (rows, row width)}; a name that starts
                                        with one of _park_windowed is a window of columns of the state buffers (it moves with the
                                        slot's origin), the others are tails that start at column 0
-        _park_check(meta)              ValueError when no slot of this pool can continue the session
-        _park_adopt(slot, meta)        the slot continues the session (host state only)
-        _park_zero(slot)               what a fresh slot zeroes before its first push
+        _park_widths()                 ((key, the pool's value), ...): the widths besides G, C, L, in the meta and equal to restore
+        _park_fits(meta, schedule)     ValueError where the pool's own keys and sizes cannot continue the session
+        _park_adopt(slot, meta)        the slot continues the session (host state only): the shared lists, its own on top
     """
 
     _pack_tab: Optional[torch.Tensor] = None
     _park_windowed: Tuple[str, ...] = ()
     _park_addr: Optional[dict] = None
+    _has_audio = True                                  # a pool that returns no audio (DecodeSessions(return_audios=False)) has no wire
+
+    def _init_slots(self, own_rate: Optional[int], rates_option: str, rs_push: int) -> None:
+        """the per-slot lists both pools keep and the slots' resamplers; own_rate: the codec's (encode) or the vocoder's (decode) rate"""
+        S = self.S
+        self.own_rate, self._rates_option, self.rs = own_rate, rates_option, None
+        if getattr(self, rates_option):
+            from ..utils.resample import SessionResampler
+            self.rs = SessionResampler(S, [self._rate_pair(r) for r in getattr(self, rates_option)], rs_push)
+        self.sched: List[Optional[object]] = [None] * S
+        self.origin = [0] * S                          # the absolute frame in column 0 of the slot's rows
+        self.rate = [own_rate] * S                     # the rate the slot's pushes arrive at (encode) / its audio leaves at (decode)
+        self.fmt = ["f32"] * S                         # the sample format of that wire (utils/pcm.py: FORMATS)
+        self.ch = [1] * S                              # its channels (interleaved frames when above 1)
+        self._fresh = [False] * S                      # opened, rows not prepared yet (done with the slot's first push)
+        self.buf = None
+
+    # -- bookkeeping (no device call) ------------------------------------------------------------------------------------
+    @property
+    def capacity(self) -> int:
+        """columns of the state buffers (frames); fixed at construction"""
+        return self.cap
+
+    @property
+    def open_slots(self) -> List[int]:
+        return [s for s in range(self.S) if self.sched[s] is not None]
+
+    def allocated_bytes(self) -> int:
+        own = 0 if self.buf is None else sum(t.numel() * t.element_size() for t in self.buf.values())
+        return own + (self.rs.allocated_bytes() if self.rs is not None else 0)
+
+    def _check_open(self, slot) -> None:
+        if not isinstance(slot, int) or not 0 <= slot < self.S:
+            raise ValueError(f"slot {slot!r} out of range (0 .. {self.S - 1})")
+        if self.sched[slot] is None:
+            raise RuntimeError(f"slot {slot} is not open")
+
+    def _free_slots(self) -> List[int]:
+        return [s for s in range(self.S) if self.sched[s] is None]
+
+    def _first_free(self) -> int:
+        free = self._free_slots()
+        if not free:
+            raise RuntimeError(f"all {self.S} slots are taken")
+        return free[0]
+
+    def _check_wire(self, rate, sample_format, channels, channel=None) -> int:
+        """the wire options of one session, refused here for open() and for restore() alike -> the pick of `channel`"""
+        if pcm.check_format(sample_format) != "f32" and not self._has_audio:
+            raise ValueError(f"sample_format={sample_format!r} without audio: return_audios=False leaves nothing to convert")
+        if pcm._check_channels(channels) > 1 and not self._has_audio:
+            raise ValueError(f"channels={channels} without audio: return_audios=False leaves nothing to fan out")
+        pick = pcm.check_channel(channel, channels)
+        declared = getattr(self, self._rates_option)
+        if rate != self.own_rate and rate not in declared:
+            raise ValueError(f"a session at {rate} Hz: the pool was built for {(self.own_rate,) + declared} Hz "
+                             f"(declare the rate in {self._rates_option}=)")
+        return pick
+
+    def _rate_pair(self, rate) -> Tuple[int, int]:
+        return (rate, self.own_rate) if self._resamples_in else (self.own_rate, rate)
+
+    def _occupy(self, s: int, sched, origin: int, rate, sample_format: str, channels: int, resampler: Optional[Mapping] = None) -> None:
+        """slot s is this session's, its rows to be prepared; its resampler entry is opened, or adopted from a parked one's state"""
+        self.sched[s], self.origin[s], self._fresh[s] = sched, origin, True
+        self.rate[s], self.fmt[s], self.ch[s] = rate, sample_format, channels
+        if self.rs is not None and resampler is not None:
+            self.rs.adopt(s, resampler)
+        elif self.rs is not None:
+            self.rs.open(s, *self._rate_pair(rate))
+
+    def _converts(self, slot: int) -> bool:             # the session runs at another rate than the pool's own: its resampler has work
+        return self.rate[slot] != self.own_rate
+
+    def _wired(self, slot: int) -> bool:                # the wire is not mono f32: the slot takes part in the step's convert launch
+        return self.fmt[slot] != "f32" or self.ch[slot] > 1
+
+    def _release(self, slots: Iterable[int]) -> None:
+        for s in slots:
+            self.sched[s] = None          # the slot is free; its rows are zeroed when it is opened and pushed to again
+
+    # -- buffers -----------------------------------------------------------------------------------------------------------
+    def _device(self):
+        return next(iter(self.buf.values())).device if self.buf is not None else next(self.codec.parameters()).device
+
+    def _ensure_buffers(self, dev) -> None:
+        if self.buf is None:
+            self._allocate(dev)
+            if self.rs is not None:
+                self.rs.allocate(dev)
+
+    def _prepare_slot(self, s: int) -> None:
+        """the slot's rows as its session's first step, or the scatter of a restore, must find them: zeroed"""
+        for v in self._slot_views(s):
+            v.zero_()
+        self._fresh[s] = False
+
+    # -- a session leaves its slot and comes back ------------------------------------------------------------------------
+    def _park_meta(self, s: int) -> dict:
+        sch = self.sched[s]
+        return dict(version=VERSION, kind=self._park_kind, geometry=plain(dataclasses.asdict(self.geo)), G=self.G, C=self.C, L=self.L,
+                    rate=self.rate[s], sample_format=self.fmt[s], channels=self.ch[s], channel=None, lookahead=None, fade=0,
+                    has_tail=False, schedule=sch.state(), window=list(self._live_window(sch)), **dict(self._park_widths()),
+                    resampler=self.rs.slot_state(s) if self.rs is not None and self._converts(s) else None)
+
+    def _park_check(self, meta: Mapping) -> None:
+        """ValueError when no slot of this pool can continue the session"""
+        if plain(meta["geometry"]) != plain(dataclasses.asdict(self.geo)):
+            raise ValueError(f"a session of geometry {meta['geometry']} into a pool of geometry {dataclasses.asdict(self.geo)}")
+        for key, mine in (("G", self.G), ("C", self.C), ("L", self.L)) + self._park_widths():
+            if meta[key] != mine:
+                raise ValueError(f"a session with {key} = {meta[key]} into a pool with {key} = {mine}")
+        sc = self._park_schedule(meta)
+        self._park_fits(meta, sc)
+        self._check_wire(meta["rate"], meta["sample_format"], meta["channels"], meta["channel"])
+        if list(self._live_window(sc)) != list(meta["window"]):
+            raise ValueError(f"window {meta['window']} is not the live window {self._live_window(sc)} of the session's schedule")
+        if sc.finished:
+            raise ValueError("the session has finished")
+        rs = meta["resampler"]
+        if (rs is not None) != (meta["rate"] != self.own_rate):
+            raise ValueError(f"a resampler state goes with a session at another rate than the {self._own_rate_of}, and only with it")
+        if rs is not None:
+            if list(rs["pair"]) != list(self._rate_pair(meta["rate"])):
+                raise ValueError(f"a resampler state for {rs['pair']} Hz in a session at {meta['rate']} Hz")
+            self.rs.check_state(rs)
+
+    def _park_adopt(self, s: int, meta: Mapping) -> None:
+        self._occupy(s, self._park_schedule(meta), meta["window"][0], meta["rate"], meta["sample_format"], meta["channels"],
+                     meta["resampler"])
 
     def _park_places(self, s: int) -> Dict[str, Tuple[int, int, bool]]:
         """{name: (address of column 0 of the slot's rows, pitch in words, windowed)}: plain integers, kept per slot, so that a
@@ -173,7 +310,7 @@ class ParkingPool:
                     ptr, pitch, windowed = places[name]
                     items.append((ptr + 4 * col0 if windowed else ptr, 4 * (total + off), rows, cols, pitch, cols))
             total += words
-        dev = self.buf["mel"].device if self.buf is not None else next(self.codec.parameters()).device
+        dev = self._device()
         blob = torch.empty(total, dtype=torch.int32, device=dev)
         if items:
             base = blob.data_ptr()
@@ -203,7 +340,7 @@ class ParkingPool:
         a pool with another capacity, slot count or maximal push is a valid target.  ValueError, no slot taken, nothing launched:
         a snapshot this pool cannot continue (see the class).  RuntimeError, no slot taken: fewer free slots than snapshots."""
         snaps = list(snapshots.values()) if isinstance(snapshots, Mapping) else list(snapshots)
-        dev = self.buf["mel"].device if self.buf is not None else None
+        dev = self._device() if self.buf is not None else None
         for sn in snaps:
             if not isinstance(sn, SessionSnapshot):
                 raise ValueError(f"restore takes SessionSnapshots, got {type(sn).__name__}")
@@ -223,27 +360,21 @@ class ParkingPool:
                 if dev is not None and sn.blob.device != dev:
                     raise ValueError(f"a blob on {sn.blob.device} into a pool whose buffers are on {dev}")
                 dev = sn.blob.device
-        free = [s for s in range(self.S) if self.sched[s] is None]
+        free = self._free_slots()
         if len(free) < len(snaps):
             raise RuntimeError(f"{len(snaps)} snapshots to restore, {len(free)} of {self.S} slots are free")
-        if dev is not None and self.buf is None:
-            self._allocate(dev)
-            if self.rs is not None:
-                self.rs.allocate(dev)
-        items, taken = [], []
-        for s, sn in zip(free, snaps):
-            meta = sn.meta
-            self._park_adopt(s, meta)
-            taken.append(s)
+        if dev is not None:
+            self._ensure_buffers(dev)
+        items, taken = [], free[:len(snaps)]
+        for s, sn in zip(taken, snaps):
+            self._park_adopt(s, sn.meta)
             if self.buf is None:                       # nothing was ever pushed, here or there: the first push zeroes the rows
-                self._fresh[s] = True
                 continue
             with torch.cuda.device(dev):
-                self._park_zero(s)
-            self._fresh[s] = False
+                self._prepare_slot(s)
             if sn.blob.numel():
                 places, base = self._park_places(s), sn.blob.data_ptr()
-                for name, rows, cols, off in meta["layout"]:
+                for name, rows, cols, off in sn.meta["layout"]:
                     ptr, pitch, _ = places[name]                 # the window lands at column 0
                     items.append((base + 4 * off, ptr, rows, cols, cols, pitch))
         if items:

@@ -13,7 +13,6 @@ usually at 8 kHz): the conversion is folded into the per-slot copy a pool makes 
 from __future__ import annotations
 
 import ctypes as C
-import dataclasses
 import math
 from typing import Dict, Iterable, List, Mapping, Optional, Tuple
 
@@ -21,7 +20,7 @@ import torch
 
 from .. import _lib
 from ..utils import crossfade, pcm
-from .stream_park import VERSION as PARK_VERSION, ParkingPool, plain
+from .stream_park import ParkingPool
 from .stream_schedule import (DecodeGeometry, DecodeSchedule, EarlyDecodeSchedule, EncodeGeometry, EncodeSchedule, decode_capacity,
                               decode_live_window, decode_rebase, encode_live_window, encode_need_from, resample_max_outputs, session_rows)
 
@@ -137,10 +136,6 @@ class EncodeSessions(ParkingPool):
             raise ValueError("sample rates must be positive")
         # the most samples at the codec's rate one push can put into a slot's row, over the declared rates
         self.codec_push = max([self.max_push] + [resample_max_outputs(r, self.codec_rate, self.max_push) for r in self.sample_rates])
-        self.rs = None                                # the per-slot resamplers in front, if any rate was declared
-        if self.sample_rates:
-            from ..utils.resample import SessionResampler
-            self.rs = SessionResampler(self.S, [(r, self.codec_rate) for r in self.sample_rates], self.max_push)
         g = self.geo
         left, right = g.quant_context
         F = g.factor
@@ -151,30 +146,10 @@ class EncodeSessions(ParkingPool):
         self.want_max = hold + self.codec_push // g.hop + 1 + (g.n_fft - g.pad + g.hop - 1) // g.hop
         self.cap = (2 * self.want_max + 31) // 32 * 32
         self.width = g.n_fft + self.codec_push        # samples per row: a tail is shorter than one window
-        self.sched: List[Optional[EncodeSchedule]] = [None] * self.S
-        self.origin = [0] * self.S
+        self._init_slots(self.codec_rate, "sample_rates", self.max_push)          # the per-slot resamplers in front, if any rate was declared
         self.s0 = [0] * self.S
         self.tail = [0] * self.S                      # valid samples in the slot's row
-        self.rate = [self.codec_rate] * self.S        # the rate the slot's pushes arrive at
-        self.fmt = ["f32"] * self.S                   # the sample format the slot's pushes arrive in (utils/pcm.py: FORMATS)
-        self.ch = [1] * self.S                        # the channels of the slot's pushes (interleaved frames when above 1)
-        self.pick = [-1] * self.S                     # the channel of them the slot encodes; -1: their mean
-        self._fresh = [False] * self.S                # opened, state not zeroed yet (done with the slot's first push)
-        self.buf = None
-
-    # -- bookkeeping (no device call) ------------------------------------------------------------------------------------
-    @property
-    def capacity(self) -> int:
-        """columns of the state buffers (frames); fixed at construction"""
-        return self.cap
-
-    @property
-    def open_slots(self) -> List[int]:
-        return [s for s in range(self.S) if self.sched[s] is not None]
-
-    def allocated_bytes(self) -> int:
-        own = 0 if self.buf is None else sum(t.numel() * t.element_size() for t in self.buf.values())
-        return own + (self.rs.allocated_bytes() if self.rs is not None else 0)
+        self.pick = [-1] * self.S                     # the channel of its pushes the slot encodes; -1: their mean
 
     def tokens_emitted(self, slot: int) -> int:
         self._check_open(slot)
@@ -187,34 +162,12 @@ class EncodeSessions(ParkingPool):
         signed PCM, x / 32768), or "ulaw" / "alaw" for torch.uint8 pushes (G.711 codes).  channels: 1 .. 8; above 1 the pushes are
         interleaved frames (n, channels), downmixed to their mean, or to channel `channel` of them (0 .. channels - 1).  Raises when
         every slot is taken; a refused open takes no slot."""
-        pcm.check_format(sample_format)
-        channels = pcm._check_channels(channels)
-        pick = pcm.check_channel(channel, channels)
         rate = self.codec_rate if sample_rate is None else int(sample_rate)
-        if rate != self.codec_rate and rate not in self.sample_rates:
-            raise ValueError(f"a session at {rate} Hz: the pool was built for {(self.codec_rate,) + self.sample_rates} Hz "
-                             f"(declare the rate in sample_rates=)")
-        for s in range(self.S):
-            if self.sched[s] is None:
-                self.sched[s] = EncodeSchedule(self.geo)
-                self.origin[s] = self.s0[s] = self.tail[s] = 0
-                self.rate[s] = rate
-                self.fmt[s] = sample_format
-                self.ch[s], self.pick[s] = channels, pick
-                if self.rs is not None:
-                    self.rs.open(s, rate, self.codec_rate)
-                self._fresh[s] = True
-                return s
-        raise RuntimeError(f"all {self.S} slots are taken")
-
-    def _converts(self, slot: int) -> bool:
-        return self.rate[slot] != self.codec_rate
-
-    def _check_open(self, slot) -> None:
-        if not isinstance(slot, int) or not 0 <= slot < self.S:
-            raise ValueError(f"slot {slot!r} out of range (0 .. {self.S - 1})")
-        if self.sched[slot] is None:
-            raise RuntimeError(f"slot {slot} is not open")
+        pick = self._check_wire(rate, sample_format, channels, channel)
+        s = self._first_free()
+        self._occupy(s, EncodeSchedule(self.geo), 0, rate, sample_format, channels)
+        self.s0[s], self.tail[s], self.pick[s] = 0, 0, pick
+        return s
 
     def _validate(self, audio: Mapping[int, torch.Tensor], final) -> Dict[int, torch.Tensor]:
         """everything that can be refused, before any state changes and before any device call"""
@@ -283,19 +236,17 @@ class EncodeSessions(ParkingPool):
         self.origin[s] = need_from
 
     # -- a session leaves its slot and comes back (models/stream_park.py) ----------------------------------------------------
-    _park_kind, _park_windowed = "encode", ("mel", "hist.", "skip", "feat")
+    _park_kind, _park_windowed, _own_rate_of, _resamples_in = "encode", ("mel", "hist.", "skip", "feat"), "codec's", True
+    _live_window = staticmethod(encode_live_window)
 
     def _park_meta(self, s: int) -> dict:
-        lo, hi = encode_live_window(self.sched[s])
-        return dict(version=PARK_VERSION, kind="encode", geometry=plain(dataclasses.asdict(self.geo)), G=self.G, C=self.C, L=self.L,
-                    n_mels=self.n_mels, codec_rate=self.codec_rate, rate=self.rate[s], sample_format=self.fmt[s], channels=self.ch[s],
-                    channel=None if self.pick[s] < 0 else self.pick[s], lookahead=None, fade=0, has_tail=False, s0=self.s0[s],
-                    tail=self.tail[s], schedule=self.sched[s].state(),
-                    resampler=self.rs.slot_state(s) if self.rs is not None and self._converts(s) else None, window=[lo, hi])
+        return dict(super()._park_meta(s), s0=self.s0[s], tail=self.tail[s], channel=None if self.pick[s] < 0 else self.pick[s])
+
+    def _park_schedule(self, meta: Mapping) -> EncodeSchedule:
+        return EncodeSchedule.from_state(self.geo, meta["schedule"])
 
     def _park_shapes(self, meta: Mapping) -> List[Tuple[str, int, int]]:
-        W, rows = meta["window"][1] - meta["window"][0], self.G * self.C
-        rs = meta["resampler"]
+        W, rows, rs = meta["window"][1] - meta["window"][0], self.G * self.C, meta["resampler"]
         return ([("mel", self.n_mels, W)] + [(f"hist.{l}", rows, W) for l in range(self.L + 1)] + [("skip", rows, W), ("feat", rows, W),
                 ("samples", 1, meta["tail"]), ("resampler", 1, rs["fill"] if rs else 0)])
 
@@ -309,50 +260,20 @@ class EncodeSessions(ParkingPool):
             rows["resampler"] = self.rs.buf["rows"][s:s + 1]
         return rows
 
-    def _park_check(self, meta: Mapping) -> None:
-        g = self.geo
-        if plain(meta["geometry"]) != plain(dataclasses.asdict(g)):
-            raise ValueError(f"a session of geometry {meta['geometry']} into a pool of geometry {dataclasses.asdict(g)}")
-        for key, mine in (("G", self.G), ("C", self.C), ("L", self.L), ("n_mels", self.n_mels), ("codec_rate", self.codec_rate)):
-            if meta[key] != mine:
-                raise ValueError(f"a session with {key} = {meta[key]} into a pool with {key} = {mine}")
-        if meta["rate"] != self.codec_rate and meta["rate"] not in self.sample_rates:
-            raise ValueError(f"a session at {meta['rate']} Hz: the pool was built for {(self.codec_rate,) + self.sample_rates} Hz "
-                             f"(declare the rate in sample_rates=)")
-        pcm.check_format(meta["sample_format"])
-        pcm.check_channel(meta["channel"], pcm._check_channels(meta["channels"]))
-        sc = EncodeSchedule.from_state(g, meta["schedule"])
-        if list(encode_live_window(sc)) != list(meta["window"]):
-            raise ValueError(f"window {meta['window']} is not the live window {encode_live_window(sc)} of the session's schedule")
-        if sc.finished:
-            raise ValueError("the session has finished")
-        lo, hi = meta["window"]
+    def _park_widths(self):
+        return ("n_mels", self.n_mels), ("codec_rate", self.codec_rate)
+
+    def _park_fits(self, meta: Mapping, sc: EncodeSchedule) -> None:
+        g, (lo, hi) = self.geo, meta["window"]
         room = self.codec_push // g.hop + 1 + (g.n_fft - g.pad + g.hop - 1) // g.hop
         if hi - lo + room > self.cap:
             raise ValueError(f"a window of {hi - lo} frames and one maximal push ({room} frames) do not fit the capacity {self.cap}")
         if not 0 <= meta["tail"] <= self.width - self.codec_push:
             raise ValueError(f"a sample tail of {meta['tail']} samples and one maximal push do not fit a row of {self.width} samples")
-        if (meta["resampler"] is not None) != (meta["rate"] != self.codec_rate):
-            raise ValueError("a resampler state goes with a session at another rate than the codec's, and only with it")
-        if meta["resampler"] is not None:
-            if list(meta["resampler"]["pair"]) != [meta["rate"], self.codec_rate]:
-                raise ValueError(f"a resampler state for {meta['resampler']['pair']} Hz in a session at {meta['rate']} Hz")
-            self.rs.check_state(meta["resampler"])
 
     def _park_adopt(self, s: int, meta: Mapping) -> None:
-        self.sched[s] = EncodeSchedule.from_state(self.geo, meta["schedule"])
-        self.origin[s], self.s0[s], self.tail[s] = meta["window"][0], meta["s0"], meta["tail"]
-        self.rate[s], self.fmt[s], self.ch[s] = meta["rate"], meta["sample_format"], meta["channels"]
-        self.pick[s] = -1 if meta["channel"] is None else meta["channel"]
-        if self.rs is not None:
-            if meta["resampler"] is not None:
-                self.rs.adopt(s, meta["resampler"])
-            else:
-                self.rs.open(s, self.codec_rate, self.codec_rate)
-
-    def _park_zero(self, s: int) -> None:
-        for v in self._slot_views(s):
-            v.zero_()
+        super()._park_adopt(s, meta)
+        self.s0[s], self.tail[s], self.pick[s] = meta["s0"], meta["tail"], -1 if meta["channel"] is None else meta["channel"]
 
     # -- one step ----------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -360,20 +281,25 @@ class EncodeSessions(ParkingPool):
         """audio: {slot: (n,) samples, n >= 0}; final: slots that end with these samples -> {slot: ids (G, m) int32, m >= 0}"""
         final = set(final)
         audio = self._validate(audio, final)
-        codec, geo, G, S = self.codec, self.geo, self.G, self.S
         dev = next(iter(audio.values())).device
-        if self.buf is None:
-            self._allocate(dev)
-            if self.rs is not None:
-                self.rs.allocate(dev)
+        self._ensure_buffers(dev)
+        converted, placed = self._place(audio)
+        released = self._resample(converted, final, placed)
+        steps = self._intake(audio, released, placed, final)
+        with torch.cuda.device(dev):
+            self._stft(steps, dev)
+            self._wavenet(steps)
+            out = self._quantise(steps, dev)
+        self._release(final)
+        return out
+
+    def _place(self, audio) -> Tuple[Dict[int, torch.Tensor], bool]:
+        """the wire's format and channels: a step that names an s16, a G.711 or a multi-channel slot puts ALL its chunks in place with
+        ONE convert launch (which downmixes on the way), each where the float path's per-slot copy would put it -- behind the slot's
+        resampler tail or behind its sample tail.  -> ({slot: what the resample launch takes for it}, whether the chunks are placed)"""
         b = self.buf
-        steps = {}
-        # ---- the sound cards' rates: ONE launch converts every slot that needs it, straight behind the slot's sample tail
         converted = {s: a for s, a in audio.items() if self._converts(s)}
-        # ---- the wire's format and channels: a step that names an s16, a G.711 or a multi-channel slot puts ALL its chunks in place with
-        # ONE convert launch (which downmixes on the way), each where the float path's per-slot copy would put it -- behind the slot's
-        # resampler tail or behind its sample tail
-        placed = any(self.fmt[s] != "f32" or self.ch[s] > 1 for s in audio)
+        placed = any(self._wired(s) for s in audio)
         if placed:
             converted = self.rs.destinations({s: a.shape[0] for s, a in converted.items()}) if converted else {}
             moves = [((a.to(torch.float32) if self.fmt[s] == "f32" else a).contiguous(),
@@ -383,98 +309,112 @@ class EncodeSessions(ParkingPool):
                 pcm.convert_items([x for x, _, _ in moves], [y for _, y, _ in moves], table=b["pcm_tab"],
                                   src_formats=[self.fmt[s] for _, _, s in moves], src_channels=[self.ch[s] for _, _, s in moves],
                                   src_pick=[self.pick[s] for _, _, s in moves])
-        released = (self.rs.push(converted, final & set(converted), out=b["samples"], out_off=self.tail, placed=placed)
-                    if converted else {})
+        return converted, placed
+
+    def _resample(self, converted, final, placed: bool) -> Dict[int, int]:
+        """the sound cards' rates: ONE launch converts every slot that needs it, straight behind its sample tail -> {slot: samples released}"""
+        if not converted:
+            return {}
+        return self.rs.push(converted, final & set(converted), out=self.buf["samples"], out_off=self.tail, placed=placed)
+
+    def _intake(self, audio, released, placed: bool, final) -> dict:
+        """every named slot's new samples behind its tail (the float path's copy, where neither launch above placed them) and its
+        schedule stepped -> {slot: its step}"""
+        steps = {}
         for s, a in audio.items():
             if self._fresh[s]:
-                for v in self._slot_views(s):
-                    v.zero_()
-                self._fresh[s] = False
+                self._prepare_slot(s)
             if s in released:
                 n = released[s]
             else:
                 n = a.shape[0]
                 if n and not placed:
-                    b["samples"][s, self.tail[s]:self.tail[s] + n] = a
+                    self.buf["samples"][s, self.tail[s]:self.tail[s] + n] = a
             self.tail[s] += n
             steps[s] = self.sched[s].step(n, s in final)
-        lib = _lib.lib()
+        return steps
+
+    def _stft(self, steps, dev) -> None:
+        """STFT: the new frames of every slot, each from its own sample tail (re-based first), into the slot's mel columns; the
+        samples no later frame reads leave the tail"""
+        b, geo, S = self.buf, self.geo, self.S
         I64 = C.c_int64 * S
-        with torch.cuda.device(dev):
-            # ---- STFT: the new frames of every slot, each from its own sample tail
-            n_frames = [0] * S
+        n_frames = [0] * S
+        for s, st in steps.items():
+            if st.frames[1] > 0:
+                self._rebase(s, st)
+            n_frames[s] = st.frames[1] - st.frames[0]
+        tmax = max(n_frames)
+        if not tmax:
+            return
+        from ..torch_ops import _stft_plan
+        sp = self.codec.encode_mel_transform.spectrogram
+        plan = _stft_plan(dev, sp.sample_rate, sp.n_fft, sp.win_length, sp.hop_length, sp.num_mels, float(sp.f_min or 0.0),
+                          float(sp.f_max) if sp.f_max else 0.0)
+        mel = torch.empty(S, self.n_mels, tmax, dtype=torch.float32, device=dev)
+        first = [steps[s].frames[0] if s in steps else 0 for s in range(S)]
+        total = [steps[s].total_length if s in steps else -1 for s in range(S)]
+        _lib.check(_lib.lib().dmel_stft_window_items_f32(plan, b["samples"].data_ptr(), self.width, self.width, I64(*self.s0),
+                                                         I64(*self.tail), None, mel.data_ptr(), None, S, I64(*first), I64(*n_frames),
+                                                         I64(*total), b["stft_tab"].data_ptr(), _lib.stream_ptr()), "stft_window_items")
+        for s, st in steps.items():
+            f0, f1 = st.frames
+            if f1 > f0:
+                o = self.origin[s]
+                b["mel"][s, :, f0 - o:f1 - o] = mel[s, :, :f1 - f0]
+                drop = max(0, f1 * geo.hop - geo.pad) - self.s0[s]
+                if drop > 0:
+                    keep = self.tail[s] - drop
+                    row = b["samples"][s]
+                    row[:keep] = row[drop:drop + keep] if drop >= keep else row[drop:drop + keep].clone()
+                    self.s0[s], self.tail[s] = self.s0[s] + drop, keep
+
+    def _wavenet(self, steps) -> None:
+        """encoder WaveNet: every level of every slot advances to its own new frontier"""
+        if not any(st.next != st.prev for st in steps.values()):
+            return
+        b, codec, G, S = self.buf, self.codec, self.G, self.S
+        prev, nxt, org = session_rows(S, steps, self.origin)
+        rows = C.c_int64 * (S * (self.L + 1))
+        x = b["mel"].data_ptr() if codec.encoder.input_projection is not None else None
+        if x is None:
             for s, st in steps.items():
-                if st.frames[1] > 0:
-                    self._rebase(s, st)
-                n_frames[s] = st.frames[1] - st.frames[0]
-            tmax = max(n_frames)
-            if tmax:
-                from ..torch_ops import _stft_plan
-                sp = codec.encode_mel_transform.spectrogram
-                plan = _stft_plan(dev, sp.sample_rate, sp.n_fft, sp.win_length, sp.hop_length, sp.num_mels, float(sp.f_min or 0.0),
-                                  float(sp.f_max) if sp.f_max else 0.0)
-                mel = torch.empty(S, self.n_mels, tmax, dtype=torch.float32, device=dev)
-                first = [steps[s].frames[0] if s in steps else 0 for s in range(S)]
-                total = [steps[s].total_length if s in steps else -1 for s in range(S)]
-                _lib.check(lib.dmel_stft_window_items_f32(plan, b["samples"].data_ptr(), self.width, self.width, I64(*self.s0), I64(*self.tail),
-                                                          None, mel.data_ptr(), None, S, I64(*first), I64(*n_frames), I64(*total),
-                                                          b["stft_tab"].data_ptr(), _lib.stream_ptr()), "stft_window_items")
-                for s, st in steps.items():
-                    f0, f1 = st.frames
-                    if f1 > f0:
-                        o = self.origin[s]
-                        b["mel"][s, :, f0 - o:f1 - o] = mel[s, :, :f1 - f0]
-                        drop = max(0, f1 * geo.hop - geo.pad) - self.s0[s]
-                        if drop > 0:
-                            keep = self.tail[s] - drop
-                            row = b["samples"][s]
-                            row[:keep] = row[drop:drop + keep] if drop >= keep else row[drop:drop + keep].clone()
-                            self.s0[s], self.tail[s] = self.s0[s] + drop, keep
-            # ---- encoder WaveNet: every level of every slot advances to its own new frontier
-            if any(st.next != st.prev for st in steps.values()):
-                prev, nxt, org = session_rows(S, steps, self.origin)
-                rows = C.c_int64 * (S * (self.L + 1))
-                x = b["mel"].data_ptr() if codec.encoder.input_projection is not None else None
-                if x is None:
-                    for s, st in steps.items():
-                        o = self.origin[s]
-                        b["hist"][0][s * G:(s + 1) * G, :, st.prev[0] - o:st.next[0] - o] = \
-                            b["mel"][s].view(G, -1, self.cap)[:, :, st.prev[0] - o:st.next[0] - o]
-                _lib.check(lib.dmel_wavenet_stream_step_items(codec.encoder.native(), x, b["hist"].data_ptr(), b["skip"].data_ptr(), None,
-                                                              b["feat"].data_ptr(), b["scratch"].data_ptr(), S * G, self.cap, rows(*prev),
-                                                              rows(*nxt), None, G, I64(*org), _lib.stream_ptr()),
-                           "wavenet_stream_step_items")
-            # ---- quantiser: ONE call over every slot with new tokens, whatever the lengths of their windows, cropped per slot
-            out: Dict[int, torch.Tensor] = {}
-            members: List[int] = []
-            for s, st in steps.items():
-                if st.tokens[1] > st.tokens[0]:
-                    members.append(s)
-                else:
-                    out[s] = torch.empty(G, 0, dtype=torch.int32, device=dev)
-            if members:
-                wins = []
-                for s in members:
-                    lo, hi = steps[s].quant_window
-                    o = self.origin[s]
-                    wins.append(b["feat"][s * G:(s + 1) * G, :, lo - o:hi - o])
-                feat, widths = pad_windows(wins)                                  # (n, G, C, Wmax)
-                feat = feat.view(len(members) * G, self.C, -1).to(codec.encode_dtype).contiguous()
-                ids = codec.quantizer.encode(feat) if widths is None else codec.quantizer.encode(feat, lengths=widths)
-                for i, s in enumerate(members):
-                    st = steps[s]
-                    j = st.quant_window[0] // geo.factor
-                    out[s] = ids[i, :, st.tokens[0] - j:st.tokens[1] - j].contiguous()
-        for s in final:
-            self.sched[s] = None          # the slot is free; its rows are zeroed when it is opened and pushed to again
+                o = self.origin[s]
+                b["hist"][0][s * G:(s + 1) * G, :, st.prev[0] - o:st.next[0] - o] = \
+                    b["mel"][s].view(G, -1, self.cap)[:, :, st.prev[0] - o:st.next[0] - o]
+        _lib.check(_lib.lib().dmel_wavenet_stream_step_items(codec.encoder.native(), x, b["hist"].data_ptr(), b["skip"].data_ptr(), None,
+                                                             b["feat"].data_ptr(), b["scratch"].data_ptr(), S * G, self.cap, rows(*prev),
+                                                             rows(*nxt), None, G, (C.c_int64 * S)(*org), _lib.stream_ptr()),
+                   "wavenet_stream_step_items")
+
+    def _quantise(self, steps, dev) -> Dict[int, torch.Tensor]:
+        """quantiser: ONE call over every slot with new tokens, whatever the lengths of their windows, cropped per slot"""
+        b, codec, G = self.buf, self.codec, self.G
+        out, members = {}, []
+        for s, st in steps.items():
+            if st.tokens[1] > st.tokens[0]:
+                members.append(s)
+            else:
+                out[s] = torch.empty(G, 0, dtype=torch.int32, device=dev)
+        if members:
+            wins = []
+            for s in members:
+                (lo, hi), o = steps[s].quant_window, self.origin[s]
+                wins.append(b["feat"][s * G:(s + 1) * G, :, lo - o:hi - o])
+            feat, widths = pad_windows(wins)                                  # (n, G, C, Wmax)
+            feat = feat.view(len(members) * G, self.C, -1).to(codec.encode_dtype).contiguous()
+            ids = codec.quantizer.encode(feat) if widths is None else codec.quantizer.encode(feat, lengths=widths)
+            for i, s in enumerate(members):
+                st = steps[s]
+                j = st.quant_window[0] // self.geo.factor
+                out[s] = ids[i, :, st.tokens[0] - j:st.tokens[1] - j].contiguous()
         return out
 
     def close(self, slot: int) -> torch.Tensor:
         """no more audio for this slot: its remaining tokens, and the slot is free"""
         self._check_open(slot)
-        dev = self.buf["samples"].device if self.buf is not None else next(self.codec.parameters()).device
         shape = (0,) if self.ch[slot] == 1 else (0, self.ch[slot])
-        return self.push({slot: torch.empty(shape, dtype=pcm.FORMATS[self.fmt[slot]][1], device=dev)}, final=(slot,))[slot]
+        return self.push({slot: torch.empty(shape, dtype=pcm.FORMATS[self.fmt[slot]][1], device=self._device())}, final=(slot,))[slot]
 
 
 def pad_windows(wins: List[torch.Tensor]) -> Tuple[torch.Tensor, Optional[List[int]]]:
@@ -641,7 +581,7 @@ class DecodeSessions(ParkingPool):
         if dec.input_projection is not None:
             raise NotImplementedError("streaming needs a decoder without input projection (input_channels == residual_channels)")
         self.codec, self.S, self.G = codec, int(slots), codec.dmel_groups
-        self.return_audios = bool(return_audios)
+        self.return_audios = self._has_audio = bool(return_audios)
         self.early_emit = bool(early_emit)
         self.N = 2 * self.S if self.early_emit else self.S    # item rows of the state buffers: rows S .. 2 S - 1 are the shadows
         self.L, self.C = len(dec.residual_layers), dec.residual_channels
@@ -662,40 +602,14 @@ class DecodeSessions(ParkingPool):
         H, f = self.geo.quant_halo_tokens, self.geo.factor
         self.tok_width = 2 * H + self.max_push            # the token tail starts at most 2 H tokens behind the newest token of the last push
         self.noise_width = (H + self.max_push) * f        # frames [z_valid, tokens * factor): at most H tokens of them in front of a push
-        self.voc_rate = self.rs = None
-        self.output_sample_rates: Tuple[int, ...] = ()
-        if return_audios:
-            self.voc_rate = int(codec.vocoder.h.get("sampling_rate", codec.encode_mel_transform.sample_rate))
-            self.output_sample_rates = tuple(sorted(set(output_sample_rates) - {self.voc_rate}))
-        if self.output_sample_rates:
-            from ..utils.resample import SessionResampler
-            # a step emits frames that all lie in the slot's `cap` columns: at most cap * up samples reach a slot's resampler at once
-            self.rs = SessionResampler(self.S, [(self.voc_rate, r) for r in self.output_sample_rates], self.cap * self.up)
-        self.rate = [self.voc_rate] * self.S              # the rate the slot's audio leaves at
-        self.fmt = ["f32"] * self.S                       # the sample format the slot's audio leaves in (utils/pcm.py: FORMATS)
-        self.ch = [1] * self.S                            # the channels the slot's audio leaves with (interleaved frames when above 1)
+        self.voc_rate = int(codec.vocoder.h.get("sampling_rate", codec.encode_mel_transform.sample_rate)) if return_audios else None
+        self.output_sample_rates = tuple(sorted(set(output_sample_rates) - {self.voc_rate}))      # none without audio (refused above)
+        # a step emits frames that all lie in the slot's `cap` columns: at most cap * up samples reach a slot's resampler at once
+        self._init_slots(self.voc_rate, "output_sample_rates", self.cap * self.up)
         self.fade = [0] * self.S                          # the slot's cross-fade in samples (0: none)
         self.has_tail = [False] * self.S                  # the slot holds back the last `fade` samples of its newest piece
-        self.sched: List[Optional[DecodeSchedule | EarlyDecodeSchedule]] = [None] * self.S
-        self.origin = [0] * self.S
         self.tok_origin = [0] * self.S                    # absolute index of the token in column 0 of the slot's token tail
         self.n_noise = [0] * self.S                       # valid frames in the slot's noise tail
-        self._fresh = [False] * self.S
-        self.buf = None
-
-    # -- bookkeeping (no device call) ------------------------------------------------------------------------------------
-    @property
-    def capacity(self) -> int:
-        """columns of the state buffers (mel frames); fixed at construction"""
-        return self.cap
-
-    @property
-    def open_slots(self) -> List[int]:
-        return [s for s in range(self.S) if self.sched[s] is not None]
-
-    def allocated_bytes(self) -> int:
-        own = 0 if self.buf is None else sum(t.numel() * t.element_size() for t in self.buf.values())
-        return own + (self.rs.allocated_bytes() if self.rs is not None else 0)
 
     def frames_emitted(self, slot: int) -> int:
         self._check_open(slot)
@@ -728,28 +642,15 @@ class DecodeSessions(ParkingPool):
                 raise ValueError("lookahead_frames on a pool built without early_emit=True: it has no shadow rows to decode ahead in")
             if isinstance(lookahead_frames, bool) or not isinstance(lookahead_frames, int) or lookahead_frames < 0:
                 raise ValueError(f"lookahead_frames must be an integer >= 0 (mel frames) or None, got {lookahead_frames!r}")
-        if pcm.check_format(sample_format) != "f32" and not self.return_audios:
-            raise ValueError(f"sample_format={sample_format!r} without audio: return_audios=False leaves nothing to convert")
-        if pcm._check_channels(channels) > 1 and not self.return_audios:
-            raise ValueError(f"channels={channels} without audio: return_audios=False leaves nothing to fan out")
         rate = self.voc_rate if output_sample_rate is None else int(output_sample_rate)
-        if rate != self.voc_rate and rate not in self.output_sample_rates:
-            raise ValueError(f"a session at {rate} Hz: the pool was built for {(self.voc_rate,) + self.output_sample_rates} Hz "
-                             f"(declare the rate in output_sample_rates=)")
-        for s in range(self.S):
-            if self.sched[s] is None:
-                self.sched[s] = (DecodeSchedule(self.geo) if lookahead_frames is None
-                                 else EarlyDecodeSchedule(self.geo, lookahead_frames, fade_frames=1 if crossfade_samples else 0))
-                self.origin[s] = self.tok_origin[s] = self.n_noise[s] = 0
-                self.fade[s], self.has_tail[s] = crossfade_samples, False
-                self.rate[s] = rate
-                self.fmt[s] = sample_format
-                self.ch[s] = channels
-                if self.rs is not None:
-                    self.rs.open(s, self.voc_rate, rate)
-                self._fresh[s] = True
-                return s
-        raise RuntimeError(f"all {self.S} slots are taken")
+        self._check_wire(rate, sample_format, channels)
+        s = self._first_free()
+        sched = (DecodeSchedule(self.geo) if lookahead_frames is None
+                 else EarlyDecodeSchedule(self.geo, lookahead_frames, fade_frames=1 if crossfade_samples else 0))
+        self._occupy(s, sched, 0, rate, sample_format, channels)
+        self.tok_origin[s] = self.n_noise[s] = 0
+        self.fade[s], self.has_tail[s] = crossfade_samples, False
+        return s
 
     def set_lookahead(self, slot: int, lookahead_frames: int) -> None:
         """the look-ahead of an open early session from its next push on.  What has left never comes back: raising it pauses the
@@ -761,16 +662,6 @@ class DecodeSessions(ParkingPool):
         if isinstance(lookahead_frames, bool) or not isinstance(lookahead_frames, int) or lookahead_frames < 0:
             raise ValueError(f"lookahead_frames must be an integer >= 0 (mel frames), got {lookahead_frames!r}")
         self.sched[slot].set_lookahead(lookahead_frames)
-
-    def _wired(self, slot: int) -> bool:
-        """the slot's audio leaves through the convert launch of the step: another format than f32, or more than one channel"""
-        return self.fmt[slot] != "f32" or self.ch[slot] > 1
-
-    def _check_open(self, slot) -> None:
-        if not isinstance(slot, int) or not 0 <= slot < self.S:
-            raise ValueError(f"slot {slot!r} out of range (0 .. {self.S - 1})")
-        if self.sched[slot] is None:
-            raise RuntimeError(f"slot {slot} is not open")
 
     def _validate(self, ids: Mapping[int, torch.Tensor], noise, final) -> None:
         """everything that can be refused, before any state changes and before any device call"""
@@ -831,30 +722,24 @@ class DecodeSessions(ParkingPool):
         self.origin[s] = new
 
     # -- a session leaves its slot and comes back (models/stream_park.py) ----------------------------------------------------
-    _park_kind, _park_windowed = "decode", ("hist.", "skip", "cond", "mel")
+    _park_kind, _park_windowed, _own_rate_of, _resamples_in = "decode", ("hist.", "skip", "cond", "mel"), "vocoder's", False
+    _live_window = staticmethod(decode_live_window)
 
     def _park_meta(self, s: int) -> dict:
         sch = self.sched[s]
-        early = isinstance(sch, EarlyDecodeSchedule)
-        lo, hi = decode_live_window(sch)
-        dec = self.codec.decoder
-        return dict(version=PARK_VERSION, kind="decode", geometry=plain(dataclasses.asdict(self.geo)), G=self.G, C=self.C, L=self.L,
-                    cond_channels=dec.condition_channels, n_mels=dec.output_channels, up=self.up, return_audios=self.return_audios,
-                    voc_rate=self.voc_rate, rate=self.rate[s], sample_format=self.fmt[s], channels=self.ch[s], channel=None,
-                    lookahead=sch.lookahead if early else None, fade=self.fade[s], has_tail=self.has_tail[s],
-                    tok_origin=self.tok_origin[s], n_noise=self.n_noise[s], schedule=sch.state(),
-                    resampler=self.rs.slot_state(s) if self.rs is not None and self.rate[s] != self.voc_rate else None, window=[lo, hi])
+        return dict(super()._park_meta(s), return_audios=self.return_audios, fade=self.fade[s], has_tail=self.has_tail[s],
+                    lookahead=sch.lookahead if isinstance(sch, EarlyDecodeSchedule) else None, tok_origin=self.tok_origin[s],
+                    n_noise=self.n_noise[s])
 
-    @staticmethod
-    def _park_exact(meta: Mapping) -> Mapping:
-        return meta["schedule"] if meta["lookahead"] is None else meta["schedule"]["exact"]
+    def _park_schedule(self, meta: Mapping):
+        return (DecodeSchedule if meta["lookahead"] is None else EarlyDecodeSchedule).from_state(self.geo, meta["schedule"])
 
     def _park_shapes(self, meta: Mapping) -> List[Tuple[str, int, int]]:
-        W = meta["window"][1] - meta["window"][0]
-        rs = meta["resampler"]
+        W, rs = meta["window"][1] - meta["window"][0], meta["resampler"]
+        exact = meta["schedule"] if meta["lookahead"] is None else meta["schedule"]["exact"]
         return ([(f"hist.{l}", self.C, W) for l in range(self.L + 1)] +
                 [("skip", self.C, W), ("cond", meta["cond_channels"], W), ("mel", meta["n_mels"], W),
-                 ("tokens", self.G, self._park_exact(meta)["tokens"] - meta["tok_origin"]), ("noise", self.C, meta["n_noise"]),
+                 ("tokens", self.G, exact["tokens"] - meta["tok_origin"]), ("noise", self.C, meta["n_noise"]),
                  ("fade_tail", 1, meta["fade"] if meta["has_tail"] else 0), ("resampler", 1, rs["fill"] if rs else 0)])
 
     def _park_rows(self, s: int) -> Dict[str, torch.Tensor]:
@@ -868,22 +753,15 @@ class DecodeSessions(ParkingPool):
             rows["resampler"] = self.rs.buf["rows"][s:s + 1]
         return rows
 
-    def _park_check(self, meta: Mapping) -> None:
-        g, f, dec = self.geo, self.geo.factor, self.codec.decoder
-        if plain(meta["geometry"]) != plain(dataclasses.asdict(g)):
-            raise ValueError(f"a session of geometry {meta['geometry']} into a pool of geometry {dataclasses.asdict(g)}")
-        for key, mine in (("G", self.G), ("C", self.C), ("L", self.L), ("cond_channels", dec.condition_channels),
-                          ("n_mels", dec.output_channels), ("up", self.up), ("voc_rate", self.voc_rate)):
-            if meta[key] != mine:
-                raise ValueError(f"a session with {key} = {meta[key]} into a pool with {key} = {mine}")
+    def _park_widths(self):
+        dec = self.codec.decoder
+        return (("cond_channels", dec.condition_channels), ("n_mels", dec.output_channels), ("up", self.up), ("voc_rate", self.voc_rate))
+
+    def _park_fits(self, meta: Mapping, sc) -> None:
+        f = self.geo.factor
         if not self.return_audios and (meta["return_audios"] or meta["sample_format"] != "f32" or meta["channels"] != 1 or
                                        meta["rate"] is not None):
             raise ValueError("a session with audio (its format, rate or channels) into a pool built with return_audios=False")
-        if meta["rate"] != self.voc_rate and meta["rate"] not in self.output_sample_rates:
-            raise ValueError(f"a session at {meta['rate']} Hz: the pool was built for {(self.voc_rate,) + self.output_sample_rates} Hz "
-                             f"(declare the rate in output_sample_rates=)")
-        pcm.check_format(meta["sample_format"])
-        pcm._check_channels(meta["channels"])
         if meta["lookahead"] is not None and not self.early_emit:
             raise ValueError("a session with lookahead_frames into a pool built without early_emit=True: it has no shadow rows to "
                              "decode ahead in")
@@ -891,14 +769,9 @@ class DecodeSessions(ParkingPool):
             raise ValueError(f"a session with crossfade_samples={meta['fade']} into a pool built with crossfade_samples={self.fade_max}")
         if meta["fade"] < 0 or (meta["fade"] and meta["lookahead"] is None) or (meta["has_tail"] and not meta["fade"]):
             raise ValueError("a cross-fade goes with a look-ahead, and a tail with a cross-fade")
-        sc = (DecodeSchedule if meta["lookahead"] is None else EarlyDecodeSchedule).from_state(g, meta["schedule"])
         if meta["lookahead"] is not None and sc.fade_frames != (1 if meta["fade"] else 0):
             raise ValueError("the schedule's fade_frames do not go with the session's cross-fade")
-        if list(decode_live_window(sc)) != list(meta["window"]):
-            raise ValueError(f"window {meta['window']} is not the live window {decode_live_window(sc)} of the session's schedule")
-        if sc.finished:
-            raise ValueError("the session has finished")
-        lo, hi = meta["window"]
+        lo = meta["window"][0]
         if sc.tokens * f - lo + self.max_push * f > self.cap:
             raise ValueError(f"the frames [{lo}, {sc.tokens * f}) and one maximal push ({self.max_push * f} frames) do not fit the "
                              f"capacity {self.cap}")
@@ -906,28 +779,15 @@ class DecodeSessions(ParkingPool):
             raise ValueError(f"a token tail of {sc.tokens - meta['tok_origin']} tokens does not fit this pool's {self.tok_width}")
         if not 0 <= meta["n_noise"] <= self.noise_width - self.max_push * f:
             raise ValueError(f"a noise tail of {meta['n_noise']} frames does not fit this pool's {self.noise_width}")
-        if (meta["resampler"] is not None) != (meta["rate"] != self.voc_rate):
-            raise ValueError("a resampler state goes with a session at another rate than the vocoder's, and only with it")
-        if meta["resampler"] is not None:
-            if list(meta["resampler"]["pair"]) != [self.voc_rate, meta["rate"]]:
-                raise ValueError(f"a resampler state for {meta['resampler']['pair']} Hz in a session at {meta['rate']} Hz")
-            self.rs.check_state(meta["resampler"])
 
     def _park_adopt(self, s: int, meta: Mapping) -> None:
-        self.sched[s] = (DecodeSchedule if meta["lookahead"] is None else EarlyDecodeSchedule).from_state(self.geo, meta["schedule"])
-        self.origin[s], self.tok_origin[s], self.n_noise[s] = meta["window"][0], meta["tok_origin"], meta["n_noise"]
-        self.fade[s], self.has_tail[s] = meta["fade"], meta["has_tail"]
-        self.rate[s], self.fmt[s], self.ch[s] = meta["rate"], meta["sample_format"], meta["channels"]
-        if self.rs is not None:
-            if meta["resampler"] is not None:
-                self.rs.adopt(s, meta["resampler"])
-            else:
-                self.rs.open(s, self.voc_rate, self.voc_rate)
+        super()._park_adopt(s, meta)
+        for name in ("tok_origin", "n_noise", "fade", "has_tail"):
+            getattr(self, name)[s] = meta[name]
 
-    def _park_zero(self, s: int) -> None:
-        for v in self._slot_views(s):
-            v.zero_()
-        if self.fade[s]:                              # not state: rebuilt from F, as a fresh slot's are
+    def _prepare_slot(self, s: int) -> None:
+        super()._prepare_slot(s)
+        if self.fade[s]:                              # not state: rebuilt from F, for a fresh slot and for a restored one
             self.buf["fade_w"][s, :self.fade[s]] = crossfade.weights(self.fade[s]).to(self.buf["fade_w"].device)
 
     # -- one step ----------------------------------------------------------------------------------------------------------
@@ -938,194 +798,203 @@ class DecodeSessions(ParkingPool):
         -> {slot: (audio (1, m * up) | None, mel (n_mels, m))} for the m >= 0 frames of that slot that became final with this step"""
         final = set(final)
         self._validate(ids, noise, final)
-        codec, f, S, L = self.codec, self.geo.factor, self.S, self.L
         dev = next(iter(ids.values())).device
-        if self.buf is None:
-            self._allocate(dev)
-            if self.rs is not None:
-                self.rs.allocate(dev)
-        b = self.buf
-        steps = {}
-        early = {}                                     # slot -> EarlyDecodeStep of the slots opened with a look-ahead
+        self._ensure_buffers(dev)
         with torch.cuda.device(dev):
-            for s, t in ids.items():
-                if self._fresh[s]:
-                    for v in self._slot_views(s):
-                        v.zero_()
-                    if self.fade[s]:
-                        b["fade_w"][s, :self.fade[s]] = crossfade.weights(self.fade[s]).to(dev)
-                    self._fresh[s] = False
-                sch = self.sched[s]
-                n = t.shape[1]
-                if n:
-                    at = sch.tokens - self.tok_origin[s]
-                    b["tokens"][s, :, at:at + n] = t.to(torch.int32)
-                    z = noise.get(s) if noise else None
-                    if z is None:
-                        z = torch.randn(self.C, n * f, dtype=torch.float32, device=dev)
-                    b["noise"][s, :, self.n_noise[s]:self.n_noise[s] + n * f] = z.to(dev, torch.float32)
-                    self.n_noise[s] += n * f
-                st = sch.step(n, s in final)
-                room = None
-                if isinstance(sch, EarlyDecodeSchedule):
-                    early[s], st = st, st.step         # the committed row runs the exact schedule's step, as an exact slot's does
-                    room = early[s] if early[s].fade else None
-                steps[s] = st
-                self._rebase(s, st, room)
+            steps, early = self._intake(ids, noise, final, dev)
             shadows = {s: es for s, es in early.items() if es.shadow}
-            # ---- quantiser: ONE call over every slot with new condition frames, whatever the lengths of their token windows, cropped per
-            # slot.  A slot that decodes ahead needs no item of its own: its window ends at its newest token already, so the frames the
-            # committed row leaves waiting for right context are the shadow row's, with the end of the window as their end
-            members = [s for s, st in steps.items() if st.z[1] > st.z[0] or s in shadows]
-            ahead = []                                 # (slot, its row of z): the shadow rows' condition, written behind the fork
-            if members:
-                tok_win = {s: shadows[s].tok_window if s in shadows else steps[s].tok_window for s in members}
-                wins = [b["tokens"][s, :, tok_win[s][0] - self.tok_origin[s]:tok_win[s][1] - self.tok_origin[s]] for s in members]
-                tok_batch, widths = pad_windows(wins)
-                if widths is None:
-                    wl = torch.full((len(members),), tok_batch.shape[-1], dtype=torch.int64, device=dev)
-                    z, _ = codec.get_quantized_features_from_indices(tok_batch, wl)
-                else:
-                    wl = torch.tensor(widths, dtype=torch.int64).to(dev, non_blocking=True)
-                    z, _ = codec.get_quantized_features_from_indices(tok_batch, wl, item_features=True)
-                for i, s in enumerate(members):
-                    st, o = steps[s], self.origin[s]
-                    lo = tok_win[s][0] * f
-                    k = st.z[1] - st.z[0]
-                    if k:
-                        b["cond"][s, :, st.z[0] - o:st.z[1] - o] = z[i, :, st.z[0] - lo:st.z[1] - lo]
-                        b["hist"][0, s, :, st.z[0] - o:st.z[1] - o] = b["noise"][s, :, :k]
-                        rest = self.n_noise[s] - k
-                        if rest:
-                            b["noise"][s, :, :rest] = b["noise"][s, :, k:k + rest].clone()
-                        self.n_noise[s] = rest
-                    if s in shadows:
-                        ahead.append((s, z[i], lo))
-                    drop = st.tok_keep_from - self.tok_origin[s]
-                    if drop > 0:
-                        keep = st.tokens - st.tok_keep_from
-                        b["tokens"][s, :, :keep] = b["tokens"][s, :, drop:drop + keep].clone()
-                        self.tok_origin[s] = st.tok_keep_from
-            # ---- decoder WaveNet: every level of every slot advances to its own new frontier, in one layered step over all slots
-            N = self.N
+            ahead = self._quantise(steps, shadows, dev)
             live = {s: st for s, st in steps.items() if st.next != st.prev}
             if shadows:
-                # ---- fork: ONE launch copies, for every slot that decodes ahead, the committed columns its shadow row reads -- every
-                # level's history, the partial skip sums, condition and mel -- into row S + slot.  In front of the committed step, so
-                # that the shadow starts from the frontiers that step starts from and both go through the one call below.  The window
-                # is widened to whole 16-byte vectors: what the copy adds in front is never read, what it adds behind is written next
-                # (condition, level 0) or recomputed by the shadow step (the other levels, skip, mel)
-                I64 = C.c_int64 * len(shadows)
-                lo = [(es.fork[0] - self.origin[s]) // 4 * 4 for s, es in shadows.items()]
-                hi = [(es.fork[1] - self.origin[s] + 3) // 4 * 4 for s, es in shadows.items()]
-                _lib.check(_lib.lib().dmel_stream_fork_items(
-                    b["hist"].data_ptr(), b["skip"].data_ptr(), b["cond"].data_ptr() if b["cond"].shape[1] else None, b["mel"].data_ptr(),
-                    L, N, self.C, b["cond"].shape[1], b["mel"].shape[1], self.cap, len(shadows), I64(*shadows), I64(*[S + s for s in shadows]),
-                    I64(*lo), I64(*hi), b["fork_tab"].data_ptr(), _lib.stream_ptr()), "stream_fork_items")
-                for s, zi, lo_z in ahead:              # behind the committed frontier: the waiting frames, with the waiting noise
-                    es, o = shadows[s], self.origin[s]
-                    b["cond"][S + s, :, es.z[0] - o:es.z[1] - o] = zi[:, es.z[0] - lo_z:es.z[1] - lo_z]
-                    b["hist"][0, S + s, :, es.z[0] - o:es.z[1] - o] = b["noise"][s, :, :es.z[1] - es.z[0]]
-                    live[S + s] = es                   # prev: the committed frontiers, next: the newest frame on every level
+                self._fork(shadows, ahead, live)
             if live:
-                prev, nxt, org = session_rows(N, live, self.origin * (N // S))
-                rows = C.c_int64 * (N * (L + 1))
-                _lib.check(_lib.lib().dmel_wavenet_stream_step_items_layered(
-                    codec.decoder.native(), None, b["hist"].data_ptr(), b["skip"].data_ptr(), b["cond"].data_ptr(), b["mel"].data_ptr(),
-                    b["scratch"].data_ptr(), N, self.cap, rows(*prev), rows(*nxt), None, 1, (C.c_int64 * N)(*org), _lib.stream_ptr()),
-                    "wavenet_stream_step_items_layered")
-            # ---- emit: the mel frames whose vocoder context exists; ONE vocoder call over every slot that has a window
-            out: Dict[int, Tuple[Optional[torch.Tensor], torch.Tensor]] = {}
-            members: List[int] = []
+                self._wavenet(live)
             # a slot with a look-ahead emits by its own rule, from its shadow row when that ran ahead of the committed one
             steps = {s: early.get(s, st) for s, st in steps.items()}
-            row = {s: S + s if s in shadows else s for s in steps}
-            for s, st in steps.items():
-                o = self.origin[s]
-                mel = b["mel"][row[s], :, st.emit[0] - o:st.emit[1] - o].clone()
-                out[s] = (torch.empty((1, 0) if self.ch[s] == 1 else (0, self.ch[s]), dtype=pcm.FORMATS[self.fmt[s]][1], device=dev)
-                          if self.return_audios else None, mel)
-                if st.voc_window[1] > st.voc_window[0]:
-                    members.append(s)
-            pieces: Dict[int, torch.Tensor] = {}       # the new audio of the slots that leave at another rate, still in the vocoder's batch
-            wire: Dict[int, torch.Tensor] = {}         # the new float audio of the non-f32 and the multi-channel slots, where it lies
-            if members:
-                wins = [b["mel"][row[s], :, steps[s].voc_window[0] - self.origin[s]:steps[s].voc_window[1] - self.origin[s]] for s in members]
-                mel_batch, widths = pad_windows(wins)
-                wav = codec.vocoder(mel_batch) if widths is None else codec.vocoder(mel_batch, lengths=widths)
-                # ---- cross-fade: ONE launch blends, in place in the vocoder's batch, the F samples in front of every fading slot's new
-                # piece with the tail the slot held back, and saves the piece's last F samples as the new tail (not on a final step).
-                # The piece handed on is the view shifted by F; the two regions of a row lie a whole frame (up >= F samples) apart
-                fading = [(i, s) for i, s in enumerate(members) if self.fade[s]]
-                cut = {}                                                   # slot -> (samples taken in front, samples held back)
-                if fading:
-                    rows = []
-                    for i, s in fading:
-                        st, F = steps[s], self.fade[s]
-                        a, e = (st.emit[0] - st.voc_window[0]) * self.up, (st.emit[1] - st.voc_window[0]) * self.up
-                        cut[s] = (F if self.has_tail[s] else 0, 0 if s in final else F)
-                        rows.append((wav[i, 0, a - F:a] if self.has_tail[s] else None, b["fade_tail"][s, :F],
-                                     None if s in final else wav[i, 0, e - F:e], b["fade_w"][s, :F]))
-                        self.has_tail[s] = s not in final
-                    rows = [r for r in rows if r[0] is not None or r[2] is not None]
-                    if rows:
-                        crossfade.crossfade_items(rows, table=b["fade_tab"])
-                for i, s in enumerate(members):
-                    st = steps[s]
-                    lo = st.voc_window[0]
-                    front, back = cut.get(s, (0, 0))
-                    piece = wav[i, :, (st.emit[0] - lo) * self.up - front:(st.emit[1] - lo) * self.up - back]
-                    if self.rate[s] != self.voc_rate:
-                        pieces[s] = piece[0]
-                    elif self._wired(s):
-                        wire[s] = piece[0]
-                    else:
-                        out[s] = (piece.clone(), out[s][1])
-            for s in final:                            # a fading slot that ends without new frames: its tail leaves as it is
-                if self.has_tail[s] and s in steps:
-                    tail = b["fade_tail"][s, :self.fade[s]]
-                    if self.rate[s] != self.voc_rate:
-                        pieces[s] = tail
-                    elif self._wired(s):
-                        wire[s] = tail
-                    else:
-                        out[s] = (tail[None].clone(), out[s][1])
-                    self.has_tail[s] = False
-            # ---- the playback rates: each piece goes behind its slot's resampler tail, ONE launch converts all slots; a slot without a
-            # new piece still takes part when it ends (the outputs that waited for the end of its signal)
-            if self.rs is not None:
-                for s in steps:
-                    if self.rate[s] != self.voc_rate and s not in pieces and s in final:
-                        pieces[s] = torch.empty(0, dtype=torch.float32, device=dev)
-                if pieces:
-                    for s, y in self.rs.push(pieces, final & set(pieces)).items():
-                        if self._wired(s):
-                            wire[s] = y
-                        else:
-                            out[s] = (y[None], out[s][1])
-            # ---- the wire's format and channels: ONE launch converts every non-f32 or multi-channel slot's new piece into one packed
-            # buffer of bytes of the step (each piece at a multiple of 16 bytes), fanning it out into the slot's channels on the way; the
-            # tensors handed out are views of it, int16 for s16, uint8 for the G.711 laws, (n, c) for c > 1 channels
-            wire = {s: y for s, y in wire.items() if y.shape[0]}
-            if wire:
-                at, total, size = {}, 0, {}
-                for s, y in wire.items():
-                    at[s] = total
-                    size[s] = y.shape[0] * self.ch[s] * pcm.FORMATS[self.fmt[s]][1].itemsize
-                    total += (size[s] + 15) // 16 * 16
-                packed = torch.empty(total, dtype=torch.uint8, device=dev)
-                dsts = [packed[at[s]:at[s] + size[s]].view(pcm.FORMATS[self.fmt[s]][1]) for s in wire]
-                dsts = [d if self.ch[s] == 1 else d.view(-1, self.ch[s]) for s, d in zip(wire, dsts)]
-                pcm.convert_items(list(wire.values()), dsts, table=b["pcm_tab"], dst_formats=[self.fmt[s] for s in wire],
-                                  dst_channels=[self.ch[s] for s in wire])
-                for (s, _), d in zip(wire.items(), dsts):
-                    out[s] = (d[None] if self.ch[s] == 1 else d, out[s][1])
-        for s in final:
-            self.sched[s] = None          # the slot is free; its rows are zeroed when it is opened and pushed to again
+            row = {s: self.S + s if s in shadows else s for s in steps}
+            out, pieces, wire = self._emit(steps, row, final, dev)
+            self._flush_tails(steps, final, out, pieces, wire)
+            self._resample(steps, final, out, pieces, wire, dev)
+            self._to_wire(out, wire)
+        self._release(final)
         return out
+
+    def _intake(self, ids, noise, final, dev) -> Tuple[dict, dict]:
+        """tokens and noise behind the slots' tails, the schedules stepped, the slots re-based
+        -> ({slot: the step of its committed row}, {slot: EarlyDecodeStep of the slots opened with a look-ahead})"""
+        b, f = self.buf, self.geo.factor
+        steps, early = {}, {}
+        for s, t in ids.items():
+            if self._fresh[s]:
+                self._prepare_slot(s)
+            sch, n = self.sched[s], t.shape[1]
+            if n:
+                at = sch.tokens - self.tok_origin[s]
+                b["tokens"][s, :, at:at + n] = t.to(torch.int32)
+                z = noise.get(s) if noise else None
+                if z is None:
+                    z = torch.randn(self.C, n * f, dtype=torch.float32, device=dev)
+                b["noise"][s, :, self.n_noise[s]:self.n_noise[s] + n * f] = z.to(dev, torch.float32)
+                self.n_noise[s] += n * f
+            st = sch.step(n, s in final)
+            room = None
+            if isinstance(sch, EarlyDecodeSchedule):
+                early[s], st = st, st.step         # the committed row runs the exact schedule's step, as an exact slot's does
+                room = early[s] if early[s].fade else None
+            steps[s] = st
+            self._rebase(s, st, room)
+        return steps, early
+
+    def _quantise(self, steps, shadows, dev) -> list:
+        """quantiser: ONE call over every slot with new condition frames, whatever the lengths of their token windows, cropped per
+        slot.  A slot that decodes ahead needs no item of its own: its window ends at its newest token already, so the frames the
+        committed row leaves waiting for right context are the shadow row's -> [(slot, its row of z, that row's first frame)]"""
+        b, codec, f = self.buf, self.codec, self.geo.factor
+        members = [s for s, st in steps.items() if st.z[1] > st.z[0] or s in shadows]
+        ahead = []
+        if not members:
+            return ahead
+        tok_win = {s: shadows[s].tok_window if s in shadows else steps[s].tok_window for s in members}
+        wins = [b["tokens"][s, :, tok_win[s][0] - self.tok_origin[s]:tok_win[s][1] - self.tok_origin[s]] for s in members]
+        tok_batch, widths = pad_windows(wins)
+        if widths is None:
+            wl = torch.full((len(members),), tok_batch.shape[-1], dtype=torch.int64, device=dev)
+            z, _ = codec.get_quantized_features_from_indices(tok_batch, wl)
+        else:
+            wl = torch.tensor(widths, dtype=torch.int64).to(dev, non_blocking=True)
+            z, _ = codec.get_quantized_features_from_indices(tok_batch, wl, item_features=True)
+        for i, s in enumerate(members):
+            st, o = steps[s], self.origin[s]
+            lo = tok_win[s][0] * f
+            k = st.z[1] - st.z[0]
+            if k:
+                b["cond"][s, :, st.z[0] - o:st.z[1] - o] = z[i, :, st.z[0] - lo:st.z[1] - lo]
+                b["hist"][0, s, :, st.z[0] - o:st.z[1] - o] = b["noise"][s, :, :k]
+                rest = self.n_noise[s] - k
+                if rest:
+                    b["noise"][s, :, :rest] = b["noise"][s, :, k:k + rest].clone()
+                self.n_noise[s] = rest
+            if s in shadows:
+                ahead.append((s, z[i], lo))
+            drop = st.tok_keep_from - self.tok_origin[s]
+            if drop > 0:
+                keep = st.tokens - st.tok_keep_from
+                b["tokens"][s, :, :keep] = b["tokens"][s, :, drop:drop + keep].clone()
+                self.tok_origin[s] = st.tok_keep_from
+        return ahead
+
+    def _fork(self, shadows, ahead, live) -> None:
+        """fork: ONE launch copies, for every slot that decodes ahead, the committed columns its shadow row reads -- every level's
+        history, the partial skip sums, condition and mel -- into row S + slot.  In front of the committed step, so that the shadow
+        starts from the frontiers that step starts from and both go through the one WaveNet call (the shadow rows join `live`).
+        The window is widened to whole 16-byte vectors: what the copy adds in front is never read, what it adds behind is written
+        next (condition, level 0) or recomputed by the shadow step (the other levels, skip, mel)"""
+        b, S = self.buf, self.S
+        I64 = C.c_int64 * len(shadows)
+        lo = [(es.fork[0] - self.origin[s]) // 4 * 4 for s, es in shadows.items()]
+        hi = [(es.fork[1] - self.origin[s] + 3) // 4 * 4 for s, es in shadows.items()]
+        _lib.check(_lib.lib().dmel_stream_fork_items(
+            b["hist"].data_ptr(), b["skip"].data_ptr(), b["cond"].data_ptr() if b["cond"].shape[1] else None, b["mel"].data_ptr(),
+            self.L, self.N, self.C, b["cond"].shape[1], b["mel"].shape[1], self.cap, len(shadows), I64(*shadows),
+            I64(*[S + s for s in shadows]), I64(*lo), I64(*hi), b["fork_tab"].data_ptr(), _lib.stream_ptr()), "stream_fork_items")
+        for s, zi, lo_z in ahead:              # behind the committed frontier: the waiting frames, with the waiting noise
+            es, o = shadows[s], self.origin[s]
+            b["cond"][S + s, :, es.z[0] - o:es.z[1] - o] = zi[:, es.z[0] - lo_z:es.z[1] - lo_z]
+            b["hist"][0, S + s, :, es.z[0] - o:es.z[1] - o] = b["noise"][s, :, :es.z[1] - es.z[0]]
+            live[S + s] = es                   # prev: the committed frontiers, next: the newest frame on every level
+
+    def _wavenet(self, live) -> None:
+        """decoder WaveNet: every level of every slot advances to its own new frontier, in one layered step over all slots"""
+        b, N = self.buf, self.N
+        prev, nxt, org = session_rows(N, live, self.origin * (N // self.S))
+        rows = C.c_int64 * (N * (self.L + 1))
+        _lib.check(_lib.lib().dmel_wavenet_stream_step_items_layered(
+            self.codec.decoder.native(), None, b["hist"].data_ptr(), b["skip"].data_ptr(), b["cond"].data_ptr(), b["mel"].data_ptr(),
+            b["scratch"].data_ptr(), N, self.cap, rows(*prev), rows(*nxt), None, 1, (C.c_int64 * N)(*org), _lib.stream_ptr()),
+            "wavenet_stream_step_items_layered")
+
+    def _route(self, s: int, piece: torch.Tensor, out, pieces, wire) -> None:
+        """a new float piece (1, n) of slot s goes to the resampler, else to the wire convert, else it is cloned out"""
+        if self._converts(s):
+            pieces[s] = piece[0]
+        elif self._wired(s):
+            wire[s] = piece[0]
+        else:
+            out[s] = (piece.clone(), out[s][1])
+
+    def _emit(self, steps, row, final, dev) -> Tuple[dict, dict, dict]:
+        """emit: the mel frames whose vocoder context exists; ONE vocoder call over every slot that has a window -> (out, pieces: the new
+        audio of the slots that leave at another rate, still in the vocoder's batch, wire: that of the non-f32 and multi-channel slots)"""
+        b, up = self.buf, self.up
+        out, members = {}, []
+        for s, st in steps.items():
+            o = self.origin[s]
+            mel = b["mel"][row[s], :, st.emit[0] - o:st.emit[1] - o].clone()
+            out[s] = (torch.empty((1, 0) if self.ch[s] == 1 else (0, self.ch[s]), dtype=pcm.FORMATS[self.fmt[s]][1], device=dev)
+                      if self.return_audios else None, mel)
+            if st.voc_window[1] > st.voc_window[0]:
+                members.append(s)
+        pieces, wire = {}, {}
+        if not members:
+            return out, pieces, wire
+        wins = [b["mel"][row[s], :, steps[s].voc_window[0] - self.origin[s]:steps[s].voc_window[1] - self.origin[s]] for s in members]
+        mel_batch, widths = pad_windows(wins)
+        wav = self.codec.vocoder(mel_batch) if widths is None else self.codec.vocoder(mel_batch, lengths=widths)
+        # ---- cross-fade: ONE launch blends, in place in the vocoder's batch, the F samples in front of every fading slot's new
+        # piece with the tail the slot held back, and saves the piece's last F samples as the new tail (not on a final step).
+        # The piece handed on is the view shifted by F; the two regions of a row lie a whole frame (up >= F samples) apart
+        fading = [(i, s) for i, s in enumerate(members) if self.fade[s]]
+        cut = {}                                                   # slot -> (samples taken in front, samples held back)
+        if fading:
+            rows = []
+            for i, s in fading:
+                st, F = steps[s], self.fade[s]
+                a, e = (st.emit[0] - st.voc_window[0]) * up, (st.emit[1] - st.voc_window[0]) * up
+                cut[s] = (F if self.has_tail[s] else 0, 0 if s in final else F)
+                rows.append((wav[i, 0, a - F:a] if self.has_tail[s] else None, b["fade_tail"][s, :F],
+                             None if s in final else wav[i, 0, e - F:e], b["fade_w"][s, :F]))
+                self.has_tail[s] = s not in final
+            rows = [r for r in rows if r[0] is not None or r[2] is not None]
+            if rows:
+                crossfade.crossfade_items(rows, table=b["fade_tab"])
+        for i, s in enumerate(members):
+            st, (front, back) = steps[s], cut.get(s, (0, 0))
+            lo = st.voc_window[0]
+            self._route(s, wav[i, :, (st.emit[0] - lo) * up - front:(st.emit[1] - lo) * up - back], out, pieces, wire)
+        return out, pieces, wire
+
+    def _flush_tails(self, steps, final, out, pieces, wire) -> None:
+        """a fading slot that ends without new frames: its tail leaves as it is"""
+        for s in final:
+            if self.has_tail[s] and s in steps:
+                self._route(s, self.buf["fade_tail"][s, :self.fade[s]][None], out, pieces, wire)
+                self.has_tail[s] = False
+
+    def _resample(self, steps, final, out, pieces, wire, dev) -> None:
+        """the playback rates: each piece goes behind its slot's resampler tail, ONE launch converts all slots; a slot without a
+        new piece still takes part when it ends (the outputs that waited for the end of its signal)"""
+        if self.rs is None:
+            return
+        for s in steps:
+            if self._converts(s) and s not in pieces and s in final:
+                pieces[s] = torch.empty(0, dtype=torch.float32, device=dev)
+        if pieces:
+            for s, y in self.rs.push(pieces, final & set(pieces)).items():
+                if self._wired(s):
+                    wire[s] = y
+                else:
+                    out[s] = (y[None], out[s][1])
+
+    def _to_wire(self, out, wire) -> None:
+        """the wire's format and channels: ONE launch converts every non-f32 or multi-channel slot's new piece into one packed buffer of
+        the step (pcm.convert_packed); the tensors handed out are views of it, int16 for s16, uint8 for G.711, (n, c) for c > 1 channels"""
+        wire = {s: y for s, y in wire.items() if y.shape[0]}
+        if wire:
+            dsts = pcm.convert_packed(list(wire.values()), [self.fmt[s] for s in wire], [self.ch[s] for s in wire], self.buf["pcm_tab"])
+            for s, d in zip(wire, dsts):
+                out[s] = (d[None] if self.ch[s] == 1 else d, out[s][1])
 
     def close(self, slot: int):
         """no more tokens for this slot: its remaining (audio, mel), and the slot is free"""
         self._check_open(slot)
-        dev = self.buf["mel"].device if self.buf is not None else next(self.codec.parameters()).device
-        return self.push({slot: torch.empty(self.G, 0, dtype=torch.int32, device=dev)}, final=(slot,))[slot]
+        return self.push({slot: torch.empty(self.G, 0, dtype=torch.int32, device=self._device())}, final=(slot,))[slot]

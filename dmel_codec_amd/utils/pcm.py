@@ -172,6 +172,23 @@ def convert_items(srcs: Sequence[torch.Tensor], dsts: Sequence[torch.Tensor], ta
                    "pcm_convert_items")
 
 
+def convert_packed(srcs: Sequence[torch.Tensor], formats: Sequence[str], channels: Sequence[int],
+                   table: Optional[torch.Tensor] = None) -> list:
+    """mono f32 pieces -> each in its format and fanned out into its channels, all by ONE convert_items launch into one packed buffer
+    of bytes, each piece at a multiple of 16 of them.  -> the destinations: views of that buffer in the format's dtype, (n,) for
+    one channel and interleaved frames (n, c) for c > 1"""
+    at, total = [], 0
+    for y, f, c in zip(srcs, formats, channels):
+        size = y.shape[0] * c * FORMATS[f][1].itemsize
+        at.append((total, size))
+        total += (size + 15) // 16 * 16
+    packed = torch.empty(total, dtype=torch.uint8, device=srcs[0].device)
+    dsts = [packed[a:a + size].view(FORMATS[f][1]) for (a, size), f in zip(at, formats)]
+    dsts = [d if c == 1 else d.view(-1, c) for d, c in zip(dsts, channels)]
+    convert_items(srcs, dsts, table=table, dst_formats=formats, dst_channels=channels)
+    return dsts
+
+
 def _rows(x: torch.Tensor, dtype, what: str) -> torch.Tensor:
     _lib.require_cuda(x, what)
     if x.dtype != dtype:

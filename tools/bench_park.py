@@ -3,7 +3,7 @@ all S sessions of a pool in steady state (ONE dmel_stream_pack_items launch per 
 without the entry -- one torch slice .clone() per state tensor per slot and a torch.cat into the slot's blob, and per slot the inverse,
 one slice copy per tensor.  Both move the same words, zero the same rows, do the same host bookkeeping, are interleaved in one
 process, and each cycle is bracketed by host synchronisations and timed on the wall clock.  The baseline is written against the
-pools' private hooks (_park_meta, _park_shapes, _park_rows, _park_adopt, _park_zero) on purpose: it has to slice the very windows
+pools' private hooks (_park_meta, _park_shapes, _park_rows, _park_adopt, _prepare_slot) on purpose: it has to slice the very windows
 the launch packs and to do the very bookkeeping restore() does, or the two columns of the table would not measure the same work."""
 import statistics
 import time
@@ -31,19 +31,18 @@ def slice_snapshot(pool, slots):
         meta["layout"], _ = dense_layout(pool._park_shapes(meta))
         views = slot_views(pool, s, meta, meta["window"][0] - pool.origin[s])
         parts = [views[name].clone().view(torch.int32).reshape(-1) for name, _, _, _ in meta["layout"]]
-        out[s] = (meta, torch.cat(parts) if parts else torch.empty(0, dtype=torch.int32, device=pool.buf["mel"].device))
+        out[s] = (meta, torch.cat(parts) if parts else torch.empty(0, dtype=torch.int32, device=pool._device()))
     return out
 
 
 def slice_restore(pool, slot, meta, blob):
     """the inverse: the slot's rows zeroed as restore() zeroes them, one slice copy per tensor, the window at column 0"""
     pool._park_adopt(slot, meta)
-    pool._park_zero(slot)
+    pool._prepare_slot(slot)
     views = slot_views(pool, slot, meta, 0)
     for name, rows, cols, off in meta["layout"]:
         v = views[name]
         v.copy_(blob[off:off + rows * cols].view(v.dtype).view(v.shape))
-    pool._fresh[slot] = False
 
 
 def measure(pool, slots, reps=40, warmup=6):
