@@ -38,8 +38,9 @@ struct PackedConv {
 };
 
 // Device-side re-pack (training: the weights change every optimiser step and live on the device).  A segment's source is an
-// affine view of a device tensor: value(src_row, ci, tap) = w[src_row*rs + ci*cs + (rev ? taps-1-tap : tap)*ts]; the bias of
-// a source row is b0[row] (+ b1[row]), or 0.  launch_repack rewrites pc.w / pc.w16 / pc.w48 / pc.bias in place from such
+// affine view of a device tensor: value(sr, ci, tap) = w[ro + ci*cs], ro = (pC > 0 ? (sr % pC)*rs + (sr / pC)*ps : sr*rs) +
+// (rev ? taps-1-tap : tap)*ts, with w already advanced by the view's base offset; the bias of a source row is b0[i] (+ b1[i]),
+// i = bias_mod ? sr % bias_mod : sr, or 0.  ("One description per weight image".)  launch_repack rewrites pc.w / pc.w16 / pc.w48 / pc.bias in place from such
 // views, producing bit-identical images to pack_conv on the same values (tests hold it to that).
 struct RepackSeg {
   const float* w = nullptr;
@@ -171,7 +172,19 @@ template <class FW, class FB> int pack_conv(PackedConv& pc, const PackDesc& d, F
   // Weight image in MFMA A-fragment order: [32-row tile][K step][half][lane 0..63][4].  Lane l = 32*h + r holds,
   // for half hf and j = 0..3, W[row 32*tile + r][k = 2*(4*hf + j) + h] of the step's 16 reduction rows, so a wave
   // fetches a step's fragments with two fully coalesced 1 KiB dwordx4 loads and no LDS round trip.
+  // bf16 images for the 32x32x16 MFMA: [32-row tile][K step][piece][lane 0..63][8]; lane l = 32*h + r holds W[row r][k = 8*h + j].
+  // w16: one piece, round-to-nearest-even.  w48: three pieces by truncation, w = p1 + p2 + p3 exactly (see conv_igemm.hip).
+  // Every source weight is fetched ONCE and written into all four images.
   std::vector<float> w((size_t)pc.Mpad * pc.steps * kCK, 0.f), b(pc.Mpad, 0.f);
+  std::vector<uint16_t> w16((size_t)pc.Mpad * pc.steps * kCK, 0), w48((size_t)pc.Mpad * pc.steps * kCK * 3, 0);
+  std::vector<uint16_t> w32h((size_t)pc.Mpad * pc.steps * kCK * 2, 0);
+  auto bits = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
+  auto from_bits = [](uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; };
+  auto to_bf16 = [&](float f) -> uint16_t {
+    uint32_t u = bits(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN stays NaN
+    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);                    // round to nearest even
+  };
   for (int m = 0; m < pc.Mpad; ++m) {
     int sr = src_row(m);
     if (sr < 0) continue;
@@ -186,57 +199,31 @@ template <class FW, class FB> int pack_conv(PackedConv& pc, const PackDesc& d, F
           for (int k = 0; k < kCK; ++k) {
             int ci = ch * kCK + k;
             if (ci >= sd.Cin) continue;
-            const int h = k & 1, kk = k >> 1, hf = kk >> 2, j = kk & 3, lane = 32 * h + r;
-            w[((((size_t)tile * pc.steps + step) * 2 + hf) * 64 + lane) * 4 + j] = get_w(s, sr, ci, tp);
+            const float v = get_w(s, sr, ci, tp);
+            const size_t ts = (size_t)tile * pc.steps + step;
+            {
+              const int h = k & 1, kk = k >> 1, hf = kk >> 2, j = kk & 3, lane = 32 * h + r;
+              w[(((ts * 2 + hf) * 64 + lane) * 4) + j] = v;
+            }
+            const int h = k >> 3, j = k & 7, lane = 32 * h + r;
+            w16[(ts * 64 + lane) * 8 + j] = to_bf16(v);
+            const float p1 = from_bits(bits(v) & 0xffff0000u), r1 = v - p1;
+            const float p2 = from_bits(bits(r1) & 0xffff0000u), r2 = r1 - p2;
+            const size_t base = ts * 3;
+            w48[((base + 0) * 64 + lane) * 8 + j] = (uint16_t)(bits(p1) >> 16);
+            w48[((base + 1) * 64 + lane) * 8 + j] = (uint16_t)(bits(p2) >> 16);
+            w48[((base + 2) * 64 + lane) * 8 + j] = (uint16_t)(bits(r2) >> 16);
+            const float vs = v * kF16WScale;
+            const uint16_t hi = f32_to_f16_bits(vs);
+            const size_t bh = ts * 2;
+            w32h[((bh + 0) * 64 + lane) * 8 + j] = hi;
+            w32h[((bh + 1) * 64 + lane) * 8 + j] = f32_to_f16_bits((vs - f16_bits_to_f32(hi)) * kF16LoScale);
           }
     }
   }
-  // bf16 images for the 32x32x16 MFMA: [32-row tile][K step][piece][lane 0..63][8]; lane l = 32*h + r holds W[row r][k = 8*h + j].
-  // w16: one piece, round-to-nearest-even.  w48: three pieces by truncation, w = p1 + p2 + p3 exactly (see conv_igemm.hip).
-  {
-    auto bits = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
-    auto from_bits = [](uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; };
-    auto to_bf16 = [&](float f) -> uint16_t {
-      uint32_t u = bits(f);
-      if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN stays NaN
-      return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);                    // round to nearest even
-    };
-    std::vector<uint16_t> w16((size_t)pc.Mpad * pc.steps * kCK, 0), w48((size_t)pc.Mpad * pc.steps * kCK * 3, 0);
-    std::vector<uint16_t> w32h((size_t)pc.Mpad * pc.steps * kCK * 2, 0);
-    for (int m = 0; m < pc.Mpad; ++m) {
-      int sr = src_row(m);
-      if (sr < 0) continue;
-      const int tile = m >> 5, r = m & 31;
-      int step = 0;
-      for (int s2 = 0; s2 < d.nseg; ++s2) {
-        const SegDesc& sd = d.seg[s2];
-        int nchunk = (sd.Cin + kCK - 1) / kCK;
-        for (int ch = 0; ch < nchunk; ++ch)
-          for (int tp = 0; tp < sd.taps; ++tp, ++step)
-            for (int k = 0; k < kCK; ++k) {
-              int ci = ch * kCK + k;
-              if (ci >= sd.Cin) continue;
-              const int h = k >> 3, j = k & 7, lane = 32 * h + r;
-              const float v = get_w(s2, sr, ci, tp);
-              w16[(((size_t)tile * pc.steps + step) * 64 + lane) * 8 + j] = to_bf16(v);
-              const float p1 = from_bits(bits(v) & 0xffff0000u), r1 = v - p1;
-              const float p2 = from_bits(bits(r1) & 0xffff0000u), r2 = r1 - p2;
-              const size_t base = ((size_t)tile * pc.steps + step) * 3;
-              w48[((base + 0) * 64 + lane) * 8 + j] = (uint16_t)(bits(p1) >> 16);
-              w48[((base + 1) * 64 + lane) * 8 + j] = (uint16_t)(bits(p2) >> 16);
-              w48[((base + 2) * 64 + lane) * 8 + j] = (uint16_t)(bits(r2) >> 16);
-              const float vs = v * kF16WScale;
-              const uint16_t hi = f32_to_f16_bits(vs);
-              const size_t bh = ((size_t)tile * pc.steps + step) * 2;
-              w32h[((bh + 0) * 64 + lane) * 8 + j] = hi;
-              w32h[((bh + 1) * 64 + lane) * 8 + j] = f32_to_f16_bits((vs - f16_bits_to_f32(hi)) * kF16LoScale);
-            }
-      }
-    }
-    DMEL_TRY(pc.w16.upload(w16.data(), w16.size() * sizeof(uint16_t)));
-    DMEL_TRY(pc.w48.upload(w48.data(), w48.size() * sizeof(uint16_t)));
-    DMEL_TRY(pc.w32h.upload(w32h.data(), w32h.size() * sizeof(uint16_t)));
-  }
+  DMEL_TRY(pc.w16.upload(w16.data(), w16.size() * sizeof(uint16_t)));
+  DMEL_TRY(pc.w48.upload(w48.data(), w48.size() * sizeof(uint16_t)));
+  DMEL_TRY(pc.w32h.upload(w32h.data(), w32h.size() * sizeof(uint16_t)));
   DMEL_TRY(pc.w.upload(w.data(), w.size() * sizeof(float)));
   DMEL_TRY(pc.bias.upload(b.data(), b.size() * sizeof(float)));
   return DMEL_OK;

@@ -46,8 +46,20 @@ struct TensorStore {
     }
     return h;
   }
+  // w[i, ...] = g[i] * v[i, ...] / |v[i, ...]|: the sum of squares in double, the scale rounded to float before it multiplies
+  static void fold_weight_norm(const HostTensor& v, const HostTensor& g, int64_t n0, std::vector<float>& out) {
+    const int64_t inner = v.numel() / n0;
+    out.resize(v.v.size());
+    for (int64_t i = 0; i < n0; ++i) {
+      double ss = 0;
+      for (int64_t j = 0; j < inner; ++j) ss += (double)v.v[i * inner + j] * v.v[i * inner + j];
+      const float scale = g.v[i] / (float)std::sqrt(ss);
+      for (int64_t j = 0; j < inner; ++j) out[i * inner + j] = v.v[i * inner + j] * scale;
+    }
+  }
   // conv weight with optional old-style weight norm (weight_g, weight_v; norm over all dims but 0), torch._weight_norm
   bool conv_weight(const std::string& prefix, std::initializer_list<int64_t> shape, std::vector<float>& out) const {
+    const int64_t n0 = *shape.begin();
     if (find(prefix + "weight")) {
       const HostTensor* w = need(prefix + "weight", shape);
       if (!w) return false;
@@ -57,31 +69,15 @@ struct TensorStore {
     if (find(prefix + "parametrizations.weight.original1")) {      // torch.nn.utils.parametrizations.weight_norm (dim 0)
       const HostTensor* v1 = need(prefix + "parametrizations.weight.original1", shape);
       const HostTensor* g1 = find(prefix + "parametrizations.weight.original0");
-      const int64_t n1 = *shape.begin();
-      if (!v1 || !g1 || g1->numel() != n1) { set_error("missing or mis-shaped '%sparametrizations.weight.original0'", prefix.c_str()); return false; }
-      const int64_t inner1 = v1->numel() / n1;
-      out.resize(v1->v.size());
-      for (int64_t i = 0; i < n1; ++i) {
-        double ss = 0;
-        for (int64_t j = 0; j < inner1; ++j) ss += (double)v1->v[i * inner1 + j] * v1->v[i * inner1 + j];
-        const float scale = g1->v[i] / (float)std::sqrt(ss);
-        for (int64_t j = 0; j < inner1; ++j) out[i * inner1 + j] = v1->v[i * inner1 + j] * scale;
-      }
+      if (!v1 || !g1 || g1->numel() != n0) { set_error("missing or mis-shaped '%sparametrizations.weight.original0'", prefix.c_str()); return false; }
+      fold_weight_norm(*v1, *g1, n0, out);
       return true;
     }
     const HostTensor* v = need(prefix + "weight_v", shape);
     if (!v) { set_error("missing state-dict tensor '%sweight' (or weight_g/weight_v)", prefix.c_str()); return false; }
     const HostTensor* g = find(prefix + "weight_g");
-    const int64_t n0 = *shape.begin();
     if (!g || g->numel() != n0) { set_error("missing or mis-shaped '%sweight_g'", prefix.c_str()); return false; }
-    const int64_t inner = v->numel() / n0;
-    out.resize(v->v.size());
-    for (int64_t i = 0; i < n0; ++i) {
-      double ss = 0;
-      for (int64_t j = 0; j < inner; ++j) ss += (double)v->v[i * inner + j] * v->v[i * inner + j];
-      const float scale = g->v[i] / (float)std::sqrt(ss);
-      for (int64_t j = 0; j < inner; ++j) out[i * inner + j] = v->v[i * inner + j] * scale;
-    }
+    fold_weight_norm(*v, *g, n0, out);
     return true;
   }
 };
@@ -95,40 +91,221 @@ ConvRun run_1seg(const float* x, int Cin, int64_t Tin, float* y, int Cout, int64
   return r;
 }
 
+// ---- base of the trainable handles (WaveNet, ConvNeXt, quantiser, discriminator) ---------------------------------------------------
+// The state-dict store, the finalize / training flags and the table of where each parameter's gradient lies in the flat gradient buffer.
+// The extern "C" entries forward to the train_* functions below with the module's name for the messages; a NULL handle is refused there.
+struct TrainHandle {
+  TensorStore ts;
+  bool ready = false;
+  bool train = false, train_ready = false;      // enable_training before finalize; train_ready: the training images are packed
+  int train_precision = 0;                      // DMEL_PRECISION_BF16: bf16 training mode
+  struct GradSlot { std::string key; int64_t offset, numel; };
+  std::vector<GradSlot> slots;
+  int64_t grad_floats = 0;
+  void clear_slots() { slots.clear(); grad_floats = 0; }
+  void add(const std::string& key, int64_t numel) { slots.push_back({key, grad_floats, numel}); grad_floats += numel; }
+  int64_t offset_of(const std::string& key) const {
+    for (const auto& s : slots)
+      if (s.key == key) return s.offset;
+    return -1;
+  }
+};
+inline int train_set_tensor(TrainHandle* h, const char* key, const float* data, const int64_t* shape, int ndim) {
+  DMEL_CHECK_ARG(h, "NULL handle");
+  h->ready = false;
+  return h->ts.set(key, data, shape, ndim);
+}
+inline int train_enable(TrainHandle* h, int on) {
+  DMEL_CHECK_ARG(h, "NULL handle");
+  h->train = on != 0;
+  h->ready = false;          // takes effect at the next finalize (the host tensors are needed)
+  h->train_ready = false;
+  return DMEL_OK;
+}
+inline int train_set_precision(TrainHandle* h, const char* who, int precision) {
+  DMEL_CHECK_ARG(h && (precision == DMEL_PRECISION_FP32 || precision == DMEL_PRECISION_BF16),
+                 "%s_set_train_precision: DMEL_PRECISION_FP32 or DMEL_PRECISION_BF16", who);
+  h->train_precision = precision;
+  return DMEL_OK;
+}
+inline int64_t train_grad_floats(const TrainHandle* h) { return h && h->train_ready ? h->grad_floats : 0; }
+// what: "a trained parameter of this WaveNet", ...
+inline int train_grad_slot(const TrainHandle* h, const char* who, const char* what, const char* key, int64_t* offset, int64_t* numel) {
+  DMEL_CHECK_ARG(h && key && offset && numel, "%s_grad_slot: NULL argument", who);
+  if (!h->train_ready) { set_error("%s_grad_slot: training was not enabled before finalize", who); return DMEL_EMISSING; }
+  for (const auto& s : h->slots)
+    if (s.key == key) { *offset = s.offset; *numel = s.numel; return DMEL_OK; }
+  set_error("%s_grad_slot: '%s' is not %s", who, key, what);
+  return DMEL_EINVAL;
+}
+
+// ---- one description per weight image -----------------------------------------------------------------------------------------------
+// A trainable convolution's packed image is described ONCE, as affine views (conv.h: RepackSeg / RepackSrc) over tensors that are named,
+// not pointed to: by state-dict key, or as kFoldedWeight, "the weight-norm-folded weight of this layer".  finalize resolves the names to
+// host pointers and packs with pack_conv through view_weight / view_bias; refresh resolves the same names to device pointers and hands
+// the same views to launch_repack, whose kernel (train_ops.hip: repack_unit) evaluates them with the same addressing:
+//   ro = (pC > 0 ? (sr % pC) * rs + (sr / pC) * ps : sr * rs) + (rev ? taps - 1 - tap : tap) * ts;   value = w[off + ro + ci * cs]
+//   bias(sr) = b0[i] (+ b1[i]),  i = bias_mod ? sr % bias_mod : sr;   0 without a bias source
+constexpr const char* kFoldedWeight = "#folded";
+struct ImageSeg {
+  std::string key;           // empty: the image has no such segment
+  int64_t off = 0;           // base offset into the tensor, in floats
+  int64_t rs = 0, cs = 0, ts = 0;
+  int rev = 0;
+  int64_t ps = 0;
+  int pC = 0;
+};
+struct ImageSrc {
+  ImageSeg seg[2];
+  std::string b0, b1;
+  int bias_mod = 0;
+};
+// the image and its description live together
+struct WeightImage : PackedConv {
+  ImageSrc src;
+  bool described() const { return !src.seg[0].key.empty(); }
+};
+
+// rows x (Cin, taps) weight read as it lies: value(row, ci, tap) = w[(row * Cin + ci) * taps + tap]
+inline ImageSeg seg_rows(const std::string& key, int Cin, int taps = 1) {
+  ImageSeg s;
+  s.key = key; s.rs = (int64_t)Cin * taps; s.cs = taps; s.ts = taps > 1 ? 1 : 0;
+  return s;
+}
+// its transpose with the taps reversed, the backward-data image: value(row, cc, tap) = w[(cc * R + row) * taps + taps - 1 - tap]
+inline ImageSeg seg_cols(const std::string& key, int R, int taps = 1) {
+  ImageSeg s;
+  s.key = key; s.rs = taps; s.cs = (int64_t)R * taps; s.ts = taps > 1 ? 1 : 0; s.rev = taps > 1;
+  return s;
+}
+
+// names -> pointers; find(key) returns nullptr (error set) for a tensor that is not there
+template <class Find> int resolve_image(const ImageSrc& src, Find&& find, RepackSrc& out) {
+  for (int sg = 0; sg < 2; ++sg) {
+    const ImageSeg& s = src.seg[sg];
+    RepackSeg& o = out.seg[sg];
+    if (s.key.empty()) continue;
+    const float* w = find(s.key);
+    if (!w) return DMEL_EMISSING;
+    o.w = w + s.off; o.rs = s.rs; o.cs = s.cs; o.ts = s.ts; o.rev = s.rev; o.ps = s.ps; o.pC = s.pC;
+  }
+  for (int b = 0; b < 2; ++b) {
+    const std::string& k = b ? src.b1 : src.b0;
+    if (k.empty()) continue;
+    const float* p = find(k);
+    if (!p) return DMEL_EMISSING;
+    (b ? out.b1 : out.b0) = p;
+  }
+  out.bias_mod = src.bias_mod;
+  return DMEL_OK;
+}
+
+// the host evaluator: repack_unit's addressing (train_ops.hip), line for line
+inline float view_weight(const RepackSeg& s, int taps, int sr, int ci, int tp) {
+  const int t = s.rev ? taps - 1 - tp : tp;
+  const int64_t ro = (s.pC > 0 ? (int64_t)(sr % s.pC) * s.rs + (int64_t)(sr / s.pC) * s.ps : (int64_t)sr * s.rs) + t * s.ts;
+  return s.w[ro + (int64_t)ci * s.cs];
+}
+inline float view_bias(const RepackSrc& a, int sr) {
+  float b = 0.f;
+  const int bi = a.bias_mod > 0 ? sr % a.bias_mod : sr;
+  if (a.b0) b = a.b0[bi];
+  if (a.b1) b += a.b1[bi];
+  return b;
+}
+
+// host route: record the description with the image and pack it from the store (and, for kFoldedWeight, from `folded`)
+inline int pack_image(WeightImage& im, const PackDesc& d, ImageSrc src, const TensorStore& ts, const float* folded = nullptr) {
+  im.src = std::move(src);
+  RepackSrc v;
+  DMEL_TRY(resolve_image(im.src, [&](const std::string& k) -> const float* {
+    if (k == kFoldedWeight) return folded;
+    const HostTensor* h = ts.find(k);
+    if (!h) set_error("missing state-dict tensor '%s'", k.c_str());
+    return h ? h->v.data() : nullptr;
+  }, v));
+  // the views are captured by value and the accessor is inlined into pack_conv's channel loop, as the per-image lambdas were
+  const int taps[2] = {d.seg[0].taps, d.seg[1].taps};
+  return pack_conv(im, d,
+                   [v, taps](int sg, int sr, int ci, int tp) __attribute__((always_inline)) { return view_weight(v.seg[sg], taps[sg], sr, ci, tp); },
+                   [v](int sr) { return view_bias(v, sr); });
+}
+
+// ---- the refresh skeleton -----------------------------------------------------------------------------------------------------------
+// open() builds the key -> device pointer map; need() / add() resolve every tensor and image BEFORE the first copy or launch, so that a
+// refused refresh leaves the handle as it was; run() makes the copies queued so far and sends the images added so far as ONE repack launch.
+struct Refresh {
+  const char* who;           // "wavenet_refresh", ...: the prefix of every message
+  hipStream_t st;
+  std::map<std::string, const float*> dev;
+  std::vector<std::pair<PackedConv*, RepackSrc>> jobs;
+  struct Copy { float* dst; const float* src; size_t count; };
+  std::vector<Copy> copies;      // parameters that are used as they lie: plain device-to-device copies
+  Refresh(const char* who_, void* stream) : who(who_), st((hipStream_t)stream) {}
+  int open(int n, const char* const* keys, const float* const* device_tensors) {
+    for (int i = 0; i < n; ++i) {
+      DMEL_CHECK_ARG(keys[i] && device_tensors[i], "%s: NULL entry %d", who, i);
+      dev[keys[i]] = device_tensors[i];
+    }
+    return DMEL_OK;
+  }
+  const float* find(const std::string& k) const {
+    auto it = dev.find(k);
+    if (it == dev.end()) { set_error("%s: tensor '%s' was not provided", who, k.c_str()); return nullptr; }
+    return it->second;
+  }
+  int need(const std::string& k, const float** out) const { return (*out = find(k)) ? DMEL_OK : DMEL_EMISSING; }
+  int add(WeightImage& im, const float* folded = nullptr) {
+    if (!im.described()) return DMEL_OK;
+    RepackSrc src;
+    DMEL_TRY(resolve_image(im.src, [&](const std::string& k) { return k == kFoldedWeight ? folded : find(k); }, src));
+    jobs.push_back({&im, src});
+    return DMEL_OK;
+  }
+  int copy(float* dst, const std::string& key, size_t count) {
+    const float* src;
+    DMEL_TRY(need(key, &src));
+    copies.push_back({dst, src, count});
+    return DMEL_OK;
+  }
+  int run() {
+    for (auto& c : copies) DMEL_HIP(hipMemcpyAsync(c.dst, c.src, c.count * sizeof(float), hipMemcpyDeviceToDevice, st));
+    copies.clear();
+    RepackBatch batch(st);
+    for (auto& j : jobs) DMEL_TRY(launch_repack(*j.first, j.second, st));
+    jobs.clear();
+    return batch.flush();
+  }
+};
+
 }  // namespace
 
 // =====================================================================================================
 // WaveNet                                               models/modules/wavenet.py:138-225
 // =====================================================================================================
-struct dmel_wavenet {
+struct dmel_wavenet : TrainHandle {
   int Cin, Cout, C, L, cycle, Ccond;
-  TensorStore ts;
-  bool ready = false;
   bool has_in = false, has_out = false;
-  PackedConv in_proj, skip_proj, out_proj;
-  std::vector<PackedConv> gate, resskip;
+  WeightImage in_proj, skip_proj, out_proj;
+  std::vector<WeightImage> gate, resskip;
   int precision = 0;
-  int train_precision = 0;     // DMEL_PRECISION_BF16: bf16 training mode (dmel_wavenet_set_train_precision)
   // training path (enable_training before finalize): unfused forward images that expose the gate pre-activations, and the
   // transposed images that turn every backward-data into a forward convolution
-  bool train = false, train_ready = false;
-  struct TrainLayer { PackedConv pre_lin, out_lin, pre_dx, pre_dc, out_dz; int dil = 1; };
+  struct TrainLayer { WeightImage pre_lin, out_lin, pre_dx, pre_dc, out_dz; int dil = 1; };
   std::vector<TrainLayer> tl;
-  PackedConv in_dx, skip_dx, out_dx;
-  // how every weight image derives from the state-dict tensors, for the device-side re-pack after an optimiser step
-  struct Recipe {
-    PackedConv* pc;
-    struct Seg { std::string key; int64_t rs, cs, ts; int rev; } seg[2];
-    std::string b0, b1;
-  };
-  std::vector<Recipe> recipes;
-  void recipe(PackedConv* pc, Recipe::Seg s0, Recipe::Seg s1 = {"", 0, 0, 0, 0}, std::string b0 = "", std::string b1 = "") {
-    recipes.push_back({pc, {s0, s1}, b0, b1});
-  }
-  struct GradSlot { std::string key; int64_t offset, numel; };
-  std::vector<GradSlot> slots;
-  int64_t grad_floats = 0;
+  WeightImage in_dx, skip_dx, out_dx;
   WaveNetFused fused;          // whole-stack kernel for narrow unconditioned WaveNets on short items (the dMel encoder)
+  // every image a refresh re-packs (those of absent projections carry no description and are passed over)
+  template <class F> int each_image(F&& f) {
+    DMEL_TRY(f(in_proj));
+    for (int i = 0; i < L; ++i) { DMEL_TRY(f(gate[i])); DMEL_TRY(f(resskip[i])); }
+    DMEL_TRY(f(skip_proj)); DMEL_TRY(f(out_proj));
+    if (!train_ready) return DMEL_OK;
+    DMEL_TRY(f(in_dx));
+    for (auto& t : tl) { DMEL_TRY(f(t.pre_lin)); DMEL_TRY(f(t.out_lin)); DMEL_TRY(f(t.pre_dx)); DMEL_TRY(f(t.pre_dc)); DMEL_TRY(f(t.out_dz)); }
+    DMEL_TRY(f(skip_dx));
+    return f(out_dx);
+  }
 };
 
 
@@ -154,178 +331,136 @@ extern "C" int dmel_wavenet_set_precision(dmel_wavenet* m, int precision) {
   return DMEL_OK;
 }
 extern "C" int dmel_wavenet_set_tensor(dmel_wavenet* m, const char* key, const float* data, const int64_t* shape, int ndim) {
-  DMEL_CHECK_ARG(m, "NULL handle");
-  m->ready = false;
-  return m->ts.set(key, data, shape, ndim);
+  return train_set_tensor(m, key, data, shape, ndim);
 }
 
-static int pack_pointwise(PackedConv& pc, const TensorStore& ts, const std::string& prefix, int Cout, int Cin) {
+// 1x1 convolution `prefix` (Cout, Cin, 1) with its bias
+static int pack_pointwise(WeightImage& im, const TensorStore& ts, const std::string& prefix, int Cout, int Cin) {
   const HostTensor* w = ts.need(prefix + "weight", {Cout, Cin, 1});
   const HostTensor* b = ts.need(prefix + "bias", {Cout});
   if (!w || !b) return DMEL_EMISSING;
   PackDesc d;
   d.mode = EPI_LINEAR; d.nseg = 1; d.C = Cout; d.seg[0].Cin = Cin;
-  return pack_conv(pc, d, [&](int, int row, int ci, int) { return w->v[(size_t)row * Cin + ci]; },
-                   [&](int row) { return b->v[row]; });
+  ImageSrc src;
+  src.seg[0] = seg_rows(prefix + "weight", Cin); src.b0 = prefix + "bias";
+  return pack_image(im, d, src, ts);
 }
 
 // transposed 1x1: y (rows = Cin of the forward conv) = W^T applied to a (Cout-channel) gradient; no bias
-static int pack_pointwise_T(PackedConv& pc, const HostTensor* w, int Cout, int Cin) {
+static int pack_pointwise_T(WeightImage& im, const TensorStore& ts, const std::string& key, int Cout, int Cin) {
   PackDesc d;
   d.mode = EPI_LINEAR; d.nseg = 1; d.C = Cin; d.seg[0].Cin = Cout;
-  return pack_conv(pc, d, [&](int, int row, int cc, int) { return w->v[(size_t)cc * Cin + row]; }, [&](int) { return 0.f; });
+  ImageSrc src;
+  src.seg[0] = seg_cols(key, Cin);
+  return pack_image(im, d, src, ts);
+}
+
+// checks the shapes of all tensors of residual layer `p` (dilated conv, output projection, condition projection) and describes the
+// gate's two-segment source (dilated conv + condition projection, biases summed)
+static int wavenet_layer_src(const dmel_wavenet* m, const std::string& p, ImageSrc& gate) {
+  const int C = m->C, Cc = m->Ccond;
+  const HostTensor* cw = m->ts.need(p + "conv_layer.conv.weight", {2 * C, C, 3});
+  const HostTensor* cb = m->ts.need(p + "conv_layer.conv.bias", {2 * C});
+  const HostTensor* ow = m->ts.need(p + "output_projection.conv.weight", {2 * C, C, 1});
+  const HostTensor* ob = m->ts.need(p + "output_projection.conv.bias", {2 * C});
+  if (!cw || !cb || !ow || !ob) return DMEL_EMISSING;
+  gate = ImageSrc();
+  gate.seg[0] = seg_rows(p + "conv_layer.conv.weight", C, 3); gate.b0 = p + "conv_layer.conv.bias";
+  if (Cc) {
+    const HostTensor* qw = m->ts.need(p + "condition_projection.conv.weight", {2 * C, Cc, 1});
+    const HostTensor* qb = m->ts.need(p + "condition_projection.conv.bias", {2 * C});
+    if (!qw || !qb) return DMEL_EMISSING;
+    gate.seg[1] = seg_rows(p + "condition_projection.conv.weight", Cc); gate.b1 = p + "condition_projection.conv.bias";
+  }
+  return DMEL_OK;
 }
 
 static int wavenet_pack_training(dmel_wavenet* m) {
   const int C = m->C, Cc = m->Ccond;
   m->tl.clear();
   m->tl.resize(m->L);
-  m->slots.clear();
-  int64_t off = 0;
-  auto slot = [&](const std::string& key, int64_t numel) { m->slots.push_back({key, off, numel}); off += numel; };
+  m->clear_slots();
   if (m->has_in) {
-    const HostTensor* w = m->ts.need("input_projection.conv.weight", {C, m->Cin, 1});
-    if (!w) return DMEL_EMISSING;
-    DMEL_TRY(pack_pointwise_T(m->in_dx, w, C, m->Cin));
-    m->recipe(&m->in_dx, {"input_projection.conv.weight", 1, m->Cin, 0, 0});
-    slot("input_projection.conv.weight", (int64_t)C * m->Cin);
-    slot("input_projection.conv.bias", C);
+    if (!m->ts.need("input_projection.conv.weight", {C, m->Cin, 1})) return DMEL_EMISSING;
+    DMEL_TRY(pack_pointwise_T(m->in_dx, m->ts, "input_projection.conv.weight", C, m->Cin));
+    m->add("input_projection.conv.weight", (int64_t)C * m->Cin);
+    m->add("input_projection.conv.bias", C);
   }
   for (int i = 0; i < m->L; ++i) {
     const std::string p = "residual_layers." + std::to_string(i) + ".";
     const int dil = m->cycle ? 1 << (i % m->cycle) : 1;
     dmel_wavenet::TrainLayer& t = m->tl[i];
     t.dil = dil;
-    const HostTensor* cw = m->ts.need(p + "conv_layer.conv.weight", {2 * C, C, 3});
-    const HostTensor* cb = m->ts.need(p + "conv_layer.conv.bias", {2 * C});
-    const HostTensor* ow = m->ts.need(p + "output_projection.conv.weight", {2 * C, C, 1});
-    const HostTensor* ob = m->ts.need(p + "output_projection.conv.bias", {2 * C});
-    if (!cw || !cb || !ow || !ob) return DMEL_EMISSING;
-    const HostTensor *qw = nullptr, *qb = nullptr;
-    if (Cc) {
-      qw = m->ts.need(p + "condition_projection.conv.weight", {2 * C, Cc, 1});
-      qb = m->ts.need(p + "condition_projection.conv.bias", {2 * C});
-      if (!qw || !qb) return DMEL_EMISSING;
-    }
+    ImageSrc gate, out, dx;
+    DMEL_TRY(wavenet_layer_src(m, p, gate));
     PackDesc d;      // pre-activation of the gate, rows in their natural order (wavenet.py:121-127)
     d.mode = EPI_LINEAR; d.C = 2 * C; d.nseg = Cc ? 2 : 1;
     d.seg[0].Cin = C; d.seg[0].taps = 3; d.seg[0].dil = dil; d.seg[0].pad_left = dil;
     d.seg[1].Cin = Cc;
-    DMEL_TRY(pack_conv(t.pre_lin, d,
-                       [&](int sg, int row, int ci, int tap) {
-                         return sg == 0 ? cw->v[((size_t)row * C + ci) * 3 + tap] : qw->v[(size_t)row * Cc + ci];
-                       },
-                       [&](int row) { return cb->v[row] + (qb ? qb->v[row] : 0.f); }));
+    DMEL_TRY(pack_image(t.pre_lin, d, gate, m->ts));
     PackDesc e;
     e.mode = EPI_LINEAR; e.C = 2 * C; e.nseg = 1; e.seg[0].Cin = C;
-    DMEL_TRY(pack_conv(t.out_lin, e, [&](int, int row, int ci, int) { return ow->v[(size_t)row * C + ci]; },
-                       [&](int row) { return ob->v[row]; }));
+    out.seg[0] = seg_rows(p + "output_projection.conv.weight", C); out.b0 = p + "output_projection.conv.bias";
+    DMEL_TRY(pack_image(t.out_lin, e, out, m->ts));
     PackDesc g;      // d pre -> d x: transposed, tap-reversed dilated conv
     g.mode = EPI_LINEAR; g.C = C; g.nseg = 1;
     g.seg[0].Cin = 2 * C; g.seg[0].taps = 3; g.seg[0].dil = dil; g.seg[0].pad_left = dil;
-    DMEL_TRY(pack_conv(t.pre_dx, g, [&](int, int row, int cc, int tap) { return cw->v[((size_t)cc * C + row) * 3 + (2 - tap)]; },
-                       [&](int) { return 0.f; }));
-    if (Cc) DMEL_TRY(pack_pointwise_T(t.pre_dc, qw, 2 * C, Cc));
-    DMEL_TRY(pack_pointwise_T(t.out_dz, ow, 2 * C, C));
-    m->recipe(&t.pre_lin, {p + "conv_layer.conv.weight", 3 * C, 3, 1, 0},
-              Cc ? dmel_wavenet::Recipe::Seg{p + "condition_projection.conv.weight", Cc, 1, 0, 0} : dmel_wavenet::Recipe::Seg{"", 0, 0, 0, 0},
-              p + "conv_layer.conv.bias", Cc ? p + "condition_projection.conv.bias" : "");
-    m->recipe(&t.out_lin, {p + "output_projection.conv.weight", C, 1, 0, 0}, {"", 0, 0, 0, 0}, p + "output_projection.conv.bias");
-    m->recipe(&t.pre_dx, {p + "conv_layer.conv.weight", 3, 3 * C, 1, 1});
-    if (Cc) m->recipe(&t.pre_dc, {p + "condition_projection.conv.weight", 1, Cc, 0, 0});
-    m->recipe(&t.out_dz, {p + "output_projection.conv.weight", 1, C, 0, 0});
-    slot(p + "conv_layer.conv.weight", (int64_t)2 * C * C * 3);
-    slot(p + "conv_layer.conv.bias", 2 * C);
+    dx.seg[0] = seg_cols(p + "conv_layer.conv.weight", C, 3);
+    DMEL_TRY(pack_image(t.pre_dx, g, dx, m->ts));
+    if (Cc) DMEL_TRY(pack_pointwise_T(t.pre_dc, m->ts, p + "condition_projection.conv.weight", 2 * C, Cc));
+    DMEL_TRY(pack_pointwise_T(t.out_dz, m->ts, p + "output_projection.conv.weight", 2 * C, C));
+    m->add(p + "conv_layer.conv.weight", (int64_t)2 * C * C * 3);
+    m->add(p + "conv_layer.conv.bias", 2 * C);
     if (Cc) {
-      slot(p + "condition_projection.conv.weight", (int64_t)2 * C * Cc);
-      slot(p + "condition_projection.conv.bias", 2 * C);
+      m->add(p + "condition_projection.conv.weight", (int64_t)2 * C * Cc);
+      m->add(p + "condition_projection.conv.bias", 2 * C);
     }
-    slot(p + "output_projection.conv.weight", (int64_t)2 * C * C);
-    slot(p + "output_projection.conv.bias", 2 * C);
+    m->add(p + "output_projection.conv.weight", (int64_t)2 * C * C);
+    m->add(p + "output_projection.conv.bias", 2 * C);
   }
   {
-    const HostTensor* w = m->ts.need("skip_projection.conv.weight", {C, C, 1});
-    if (!w) return DMEL_EMISSING;
-    DMEL_TRY(pack_pointwise_T(m->skip_dx, w, C, C));
-    m->recipe(&m->skip_dx, {"skip_projection.conv.weight", 1, C, 0, 0});
-    slot("skip_projection.conv.weight", (int64_t)C * C);
-    slot("skip_projection.conv.bias", C);
+    if (!m->ts.need("skip_projection.conv.weight", {C, C, 1})) return DMEL_EMISSING;
+    DMEL_TRY(pack_pointwise_T(m->skip_dx, m->ts, "skip_projection.conv.weight", C, C));
+    m->add("skip_projection.conv.weight", (int64_t)C * C);
+    m->add("skip_projection.conv.bias", C);
   }
   if (m->has_out) {
-    const HostTensor* w = m->ts.need("output_projection.conv.weight", {m->Cout, C, 1});
-    if (!w) return DMEL_EMISSING;
-    DMEL_TRY(pack_pointwise_T(m->out_dx, w, m->Cout, C));
-    m->recipe(&m->out_dx, {"output_projection.conv.weight", 1, C, 0, 0});
-    slot("output_projection.conv.weight", (int64_t)m->Cout * C);
-    slot("output_projection.conv.bias", m->Cout);
+    if (!m->ts.need("output_projection.conv.weight", {m->Cout, C, 1})) return DMEL_EMISSING;
+    DMEL_TRY(pack_pointwise_T(m->out_dx, m->ts, "output_projection.conv.weight", m->Cout, C));
+    m->add("output_projection.conv.weight", (int64_t)m->Cout * C);
+    m->add("output_projection.conv.bias", m->Cout);
   }
-  m->grad_floats = off;
   m->train_ready = true;
   return DMEL_OK;
 }
 
-extern "C" int dmel_wavenet_set_train_precision(dmel_wavenet* m, int precision) {
-  DMEL_CHECK_ARG(m && (precision == DMEL_PRECISION_FP32 || precision == DMEL_PRECISION_BF16), "wavenet_set_train_precision: DMEL_PRECISION_FP32 or DMEL_PRECISION_BF16");
-  m->train_precision = precision;
-  return DMEL_OK;
-}
-extern "C" int dmel_wavenet_enable_training(dmel_wavenet* m, int on) {
-  DMEL_CHECK_ARG(m, "NULL handle");
-  m->train = on != 0;
-  m->ready = false;          // takes effect at the next finalize (the host tensors are needed)
-  m->train_ready = false;
-  return DMEL_OK;
-}
+extern "C" int dmel_wavenet_set_train_precision(dmel_wavenet* m, int precision) { return train_set_precision(m, "wavenet", precision); }
+extern "C" int dmel_wavenet_enable_training(dmel_wavenet* m, int on) { return train_enable(m, on); }
 
 extern "C" int dmel_wavenet_finalize(dmel_wavenet* m) {
   DMEL_CHECK_ARG(m, "NULL handle");
+  m->ready = m->train_ready = false;      // until every image is packed: a finalize that fails leaves a handle that refuses to run
   const int C = m->C;
-  m->recipes.clear();
-  if (m->has_in) {
-    DMEL_TRY(pack_pointwise(m->in_proj, m->ts, "input_projection.conv.", C, m->Cin));
-    m->recipe(&m->in_proj, {"input_projection.conv.weight", m->Cin, 1, 0, 0}, {"", 0, 0, 0, 0}, "input_projection.conv.bias");
-  }
+  if (m->has_in) DMEL_TRY(pack_pointwise(m->in_proj, m->ts, "input_projection.conv.", C, m->Cin));
   m->gate.clear(); m->resskip.clear();
   m->gate.resize(m->L); m->resskip.resize(m->L);
   for (int i = 0; i < m->L; ++i) {
     const std::string p = "residual_layers." + std::to_string(i) + ".";
     const int dil = m->cycle ? 1 << (i % m->cycle) : 1;   // wavenet.py:169
-    const HostTensor* cw = m->ts.need(p + "conv_layer.conv.weight", {2 * C, C, 3});
-    const HostTensor* cb = m->ts.need(p + "conv_layer.conv.bias", {2 * C});
-    const HostTensor* ow = m->ts.need(p + "output_projection.conv.weight", {2 * C, C, 1});
-    const HostTensor* ob = m->ts.need(p + "output_projection.conv.bias", {2 * C});
-    if (!cw || !cb || !ow || !ob) return DMEL_EMISSING;
-    const HostTensor *qw = nullptr, *qb = nullptr;
-    if (m->Ccond) {
-      qw = m->ts.need(p + "condition_projection.conv.weight", {2 * C, m->Ccond, 1});
-      qb = m->ts.need(p + "condition_projection.conv.bias", {2 * C});
-      if (!qw || !qb) return DMEL_EMISSING;
-    }
+    ImageSrc gate, out;
+    DMEL_TRY(wavenet_layer_src(m, p, gate));
     PackDesc d;
     d.mode = EPI_GATE; d.C = C; d.nseg = m->Ccond ? 2 : 1;
     d.seg[0].Cin = C; d.seg[0].taps = 3; d.seg[0].dil = dil; d.seg[0].pad_left = dil;
     d.seg[1].Cin = m->Ccond;
-    const int Cc = m->Ccond;
-    DMEL_TRY(pack_conv(m->gate[i], d,
-                       [&](int sg, int row, int ci, int tap) {
-                         return sg == 0 ? cw->v[((size_t)row * C + ci) * 3 + tap] : qw->v[(size_t)row * Cc + ci];
-                       },
-                       [&](int row) { return cb->v[row] + (qb ? qb->v[row] : 0.f); }));
+    DMEL_TRY(pack_image(m->gate[i], d, gate, m->ts));
     PackDesc e;
     e.mode = EPI_RESSKIP; e.C = C; e.nseg = 1; e.seg[0].Cin = C;
-    DMEL_TRY(pack_conv(m->resskip[i], e, [&](int, int row, int ci, int) { return ow->v[(size_t)row * C + ci]; },
-                       [&](int row) { return ob->v[row]; }));
-    m->recipe(&m->gate[i], {p + "conv_layer.conv.weight", 3 * C, 3, 1, 0},
-              Cc ? dmel_wavenet::Recipe::Seg{p + "condition_projection.conv.weight", Cc, 1, 0, 0} : dmel_wavenet::Recipe::Seg{"", 0, 0, 0, 0},
-              p + "conv_layer.conv.bias", Cc ? p + "condition_projection.conv.bias" : "");
-    m->recipe(&m->resskip[i], {p + "output_projection.conv.weight", C, 1, 0, 0}, {"", 0, 0, 0, 0}, p + "output_projection.conv.bias");
+    out.seg[0] = seg_rows(p + "output_projection.conv.weight", C); out.b0 = p + "output_projection.conv.bias";
+    DMEL_TRY(pack_image(m->resskip[i], e, out, m->ts));
   }
   DMEL_TRY(pack_pointwise(m->skip_proj, m->ts, "skip_projection.conv.", C, C));
-  m->recipe(&m->skip_proj, {"skip_projection.conv.weight", C, 1, 0, 0}, {"", 0, 0, 0, 0}, "skip_projection.conv.bias");
-  if (m->has_out) {
-    DMEL_TRY(pack_pointwise(m->out_proj, m->ts, "output_projection.conv.", m->Cout, C));
-    m->recipe(&m->out_proj, {"output_projection.conv.weight", C, 1, 0, 0}, {"", 0, 0, 0, 0}, "output_projection.conv.bias");
-  }
+  if (m->has_out) DMEL_TRY(pack_pointwise(m->out_proj, m->ts, "output_projection.conv.", m->Cout, C));
   if (m->train) DMEL_TRY(wavenet_pack_training(m));
   // whole-stack kernel (wavenet_fused.hip): narrow, unconditioned, no output projection, dilations <= 8
   m->fused.ok = false;
@@ -823,44 +958,19 @@ extern "C" int dmel_wavenet_refresh(dmel_wavenet* m, int n, const char* const* k
                                     void* stream) {
   DMEL_CHECK_ARG(m && keys && device_tensors && n > 0, "wavenet_refresh: bad argument");
   if (!m->ready) { set_error("wavenet_refresh: handle not finalized"); return DMEL_EMISSING; }
-  std::map<std::string, const float*> dev;
-  for (int i = 0; i < n; ++i) {
-    DMEL_CHECK_ARG(keys[i] && device_tensors[i], "wavenet_refresh: NULL entry %d", i);
-    dev[keys[i]] = device_tensors[i];
-  }
-  auto find = [&](const std::string& k, const float** out) -> int {
-    if (k.empty()) { *out = nullptr; return DMEL_OK; }
-    auto it = dev.find(k);
-    if (it == dev.end()) { set_error("wavenet_refresh: tensor '%s' was not provided", k.c_str()); return DMEL_EMISSING; }
-    *out = it->second;
-    return DMEL_OK;
-  };
-  RepackBatch batch((hipStream_t)stream);      // all convolutions of the network in one launch
-  for (auto& r : m->recipes) {
-    RepackSrc src;
-    for (int sgi = 0; sgi < 2; ++sgi) {
-      DMEL_TRY(find(r.seg[sgi].key, &src.seg[sgi].w));
-      src.seg[sgi].rs = r.seg[sgi].rs; src.seg[sgi].cs = r.seg[sgi].cs; src.seg[sgi].ts = r.seg[sgi].ts; src.seg[sgi].rev = r.seg[sgi].rev;
-    }
-    DMEL_TRY(find(r.b0, &src.b0));
-    DMEL_TRY(find(r.b1, &src.b1));
-    DMEL_TRY(launch_repack(*r.pc, src, (hipStream_t)stream));
-  }
-  return batch.flush();
+  Refresh r("wavenet_refresh", stream);
+  DMEL_TRY(r.open(n, keys, device_tensors));
+  DMEL_TRY(m->each_image([&](WeightImage& im) { return r.add(im); }));
+  return r.run();      // all convolutions of the network in one launch
 }
 
 extern "C" size_t dmel_wavenet_train_workspace_bytes(const dmel_wavenet* m, int N, int64_t T) {
   if (!m || N <= 0 || T <= 0) return 0;
   return train_plan(m, N, T, nullptr).bytes;
 }
-extern "C" int64_t dmel_wavenet_grad_floats(const dmel_wavenet* m) { return m && m->train_ready ? m->grad_floats : 0; }
+extern "C" int64_t dmel_wavenet_grad_floats(const dmel_wavenet* m) { return train_grad_floats(m); }
 extern "C" int dmel_wavenet_grad_slot(const dmel_wavenet* m, const char* key, int64_t* offset, int64_t* numel) {
-  DMEL_CHECK_ARG(m && key && offset && numel, "wavenet_grad_slot: NULL argument");
-  if (!m->train_ready) { set_error("wavenet_grad_slot: training was not enabled before finalize"); return DMEL_EMISSING; }
-  for (const auto& s : m->slots)
-    if (s.key == key) { *offset = s.offset; *numel = s.numel; return DMEL_OK; }
-  set_error("wavenet_grad_slot: '%s' is not a trained parameter of this WaveNet", key);
-  return DMEL_EINVAL;
+  return train_grad_slot(m, "wavenet", "a trained parameter of this WaveNet", key, offset, numel);
 }
 
 extern "C" int dmel_wavenet_forward_train(const dmel_wavenet* m, const float* x, const float* condition, float* y, int N, int64_t T,
@@ -936,9 +1046,8 @@ extern "C" int dmel_wavenet_backward_hooked(const dmel_wavenet* m, const float* 
   ClearedRange cleared(grads, (size_t)m->grad_floats * sizeof(float), st);      // one memset for the ~120 gradient tensors of the network
   DMEL_TRY(cleared.error());
   auto G = [&](const std::string& key) -> float* {
-    for (const auto& s : m->slots)
-      if (s.key == key) return grads + s.offset;
-    return nullptr;
+    const int64_t o = m->offset_of(key);
+    return o < 0 ? nullptr : grads + o;
   };
   // contiguous region of the flat gradient buffer that belongs to the slots whose key starts with `prefix` (slots are laid out
   // input_projection | residual_layers.0 | ... | residual_layers.L-1 | skip_projection | output_projection)
@@ -1032,10 +1141,12 @@ extern "C" int dmel_wavenet_backward_hooked(const dmel_wavenet* m, const float* 
 // =====================================================================================================
 namespace {
 struct ConvNeXt {                // firefly.py:337-402
+  std::string prefix;            // state-dict prefix of its nine tensors
   DevBuf dw_w, dw_b, ln_w, ln_b, gamma;
-  PackedConv pw1, pw2;
+  WeightImage pw1, pw2;
+  WeightImage pw1T, pw2T;        // training: transposed images, backward-data of the two Linear layers
 };
-int build_convnext(ConvNeXt& cx, const TensorStore& ts, const std::string& p, int C) {
+int build_convnext(ConvNeXt& cx, const TensorStore& ts, const std::string& p, int C, bool train) {
   const HostTensor* dw = ts.need(p + "dwconv.weight", {C, 1, 7});
   const HostTensor* db = ts.need(p + "dwconv.bias", {C});
   const HostTensor* lw = ts.need(p + "norm.weight", {C});
@@ -1046,16 +1157,32 @@ int build_convnext(ConvNeXt& cx, const TensorStore& ts, const std::string& p, in
   const HostTensor* b2 = ts.need(p + "pwconv2.bias", {C});
   const HostTensor* ga = ts.need(p + "gamma", {C});
   if (!dw || !db || !lw || !lb || !w1 || !b1 || !w2 || !b2 || !ga) return DMEL_EMISSING;
+  cx.prefix = p;
   DMEL_TRY(upload_vec(cx.dw_w, dw->v)); DMEL_TRY(upload_vec(cx.dw_b, db->v));
   DMEL_TRY(upload_vec(cx.ln_w, lw->v)); DMEL_TRY(upload_vec(cx.ln_b, lb->v));
   DMEL_TRY(upload_vec(cx.gamma, ga->v));
-  PackDesc d;
-  d.mode = EPI_LINEAR; d.nseg = 1; d.C = 4 * C; d.seg[0].Cin = C;
-  DMEL_TRY(pack_conv(cx.pw1, d, [&](int, int row, int ci, int) { return w1->v[(size_t)row * C + ci]; },
-                     [&](int row) { return b1->v[row]; }));
-  d.C = C; d.seg[0].Cin = 4 * C;
-  DMEL_TRY(pack_conv(cx.pw2, d, [&](int, int row, int ci, int) { return w2->v[(size_t)row * 4 * C + ci]; },
-                     [&](int row) { return b2->v[row]; }));
+  PackDesc d, e;
+  d.mode = EPI_LINEAR; d.nseg = 1; d.C = 4 * C; d.seg[0].Cin = C;             // pwconv1, and W2^T: d v (C) -> d g (4C)
+  e.mode = EPI_LINEAR; e.nseg = 1; e.C = C; e.seg[0].Cin = 4 * C;             // pwconv2, and W1^T: d u (4C) -> d h1 (C)
+  ImageSrc s1, s2, s1T, s2T;
+  s1.seg[0] = seg_rows(p + "pwconv1.weight", C); s1.b0 = p + "pwconv1.bias";
+  s2.seg[0] = seg_rows(p + "pwconv2.weight", 4 * C); s2.b0 = p + "pwconv2.bias";
+  DMEL_TRY(pack_image(cx.pw1, d, s1, ts));
+  DMEL_TRY(pack_image(cx.pw2, e, s2, ts));
+  if (!train) return DMEL_OK;
+  s1T.seg[0] = seg_cols(p + "pwconv1.weight", C);
+  s2T.seg[0] = seg_cols(p + "pwconv2.weight", 4 * C);
+  DMEL_TRY(pack_image(cx.pw1T, e, s1T, ts));
+  return pack_image(cx.pw2T, d, s2T, ts);
+}
+// the refresh of one block: five plain copies, two images (four when it trains)
+int refresh_convnext(Refresh& r, ConvNeXt& cx, int C, bool train) {
+  const std::string& p = cx.prefix;
+  DMEL_TRY(r.add(cx.pw1)); DMEL_TRY(r.add(cx.pw2));
+  DMEL_TRY(r.copy(cx.dw_w.as<float>(), p + "dwconv.weight", (size_t)C * 7)); DMEL_TRY(r.copy(cx.dw_b.as<float>(), p + "dwconv.bias", C));
+  DMEL_TRY(r.copy(cx.ln_w.as<float>(), p + "norm.weight", C)); DMEL_TRY(r.copy(cx.ln_b.as<float>(), p + "norm.bias", C));
+  DMEL_TRY(r.copy(cx.gamma.as<float>(), p + "gamma", C));
+  if (train) { DMEL_TRY(r.add(cx.pw1T)); DMEL_TRY(r.add(cx.pw2T)); }
   return DMEL_OK;
 }
 // y = x + gamma * pwconv2(gelu(pwconv1(LN(dwconv(x)))))      x, y: (N, C, T); y may alias x; h1: (N,C,T), h2: (N,4C,T)
@@ -1079,21 +1206,10 @@ int run_convnext(const ConvNeXt& cx, const float* x, float* y, float* h1, float*
 }  // namespace
 
 // ---- standalone ConvNeXtBlock handle (firefly.py:337-402), inference and training -----------------------------------
-struct dmel_convnext {
-  int train_precision = 0;     // DMEL_PRECISION_BF16: bf16 training mode
+struct dmel_convnext : TrainHandle {
   int C = 0;
-  TensorStore ts;
-  bool ready = false, train = false, train_ready = false;
   ConvNeXt cx;
-  PackedConv pw1T, pw2T;          // transposed images: backward-data of the two Linear layers
-  struct GradSlot { std::string key; int64_t offset, numel; };
-  std::vector<GradSlot> slots;
-  int64_t grad_floats = 0;
 };
-
-namespace {
-int pack_convnext_T(PackedConv& pw1T, PackedConv& pw2T, const TensorStore& ts, const std::string& p, int C);
-}
 
 extern "C" int dmel_convnext_create(dmel_convnext** out, int dim) {
   DMEL_CHECK_ARG(out && dim > 0, "convnext_create: bad argument");
@@ -1104,35 +1220,25 @@ extern "C" int dmel_convnext_create(dmel_convnext** out, int dim) {
 }
 extern "C" void dmel_convnext_destroy(dmel_convnext* m) { delete m; }
 extern "C" int dmel_convnext_set_tensor(dmel_convnext* m, const char* key, const float* data, const int64_t* shape, int ndim) {
-  DMEL_CHECK_ARG(m, "NULL handle");
-  m->ready = false;
-  return m->ts.set(key, data, shape, ndim);
+  return train_set_tensor(m, key, data, shape, ndim);
 }
-extern "C" int dmel_convnext_set_train_precision(dmel_convnext* m, int precision) {
-  DMEL_CHECK_ARG(m && (precision == DMEL_PRECISION_FP32 || precision == DMEL_PRECISION_BF16), "convnext_set_train_precision: DMEL_PRECISION_FP32 or DMEL_PRECISION_BF16");
-  m->train_precision = precision;
-  return DMEL_OK;
+extern "C" int dmel_convnext_set_train_precision(dmel_convnext* m, int precision) { return train_set_precision(m, "convnext", precision); }
+extern "C" int dmel_convnext_enable_training(dmel_convnext* m, int on) { return train_enable(m, on); }
+namespace {
+// the nine gradient slots of a block, in the order of its state dict
+void convnext_slots(TrainHandle& h, const std::string& p, int C) {
+  h.add(p + "dwconv.weight", (int64_t)C * 7); h.add(p + "dwconv.bias", C); h.add(p + "norm.weight", C); h.add(p + "norm.bias", C);
+  h.add(p + "pwconv1.weight", (int64_t)4 * C * C); h.add(p + "pwconv1.bias", 4 * C); h.add(p + "pwconv2.weight", (int64_t)4 * C * C);
+  h.add(p + "pwconv2.bias", C); h.add(p + "gamma", C);
 }
-extern "C" int dmel_convnext_enable_training(dmel_convnext* m, int on) {
-  DMEL_CHECK_ARG(m, "NULL handle");
-  m->train = on != 0;
-  m->ready = false;
-  m->train_ready = false;
-  return DMEL_OK;
-}
+}  // namespace
 extern "C" int dmel_convnext_finalize(dmel_convnext* m) {
   DMEL_CHECK_ARG(m, "NULL handle");
-  const int C = m->C;
-  DMEL_TRY(build_convnext(m->cx, m->ts, "", C));
+  m->ready = m->train_ready = false;      // until every image is packed: a finalize that fails leaves a handle that refuses to run
+  DMEL_TRY(build_convnext(m->cx, m->ts, "", m->C, m->train));
   if (m->train) {
-    DMEL_TRY(pack_convnext_T(m->pw1T, m->pw2T, m->ts, "", C));
-    m->slots.clear();
-    int64_t off = 0;
-    auto slot = [&](const char* key, int64_t numel) { m->slots.push_back({key, off, numel}); off += numel; };
-    slot("dwconv.weight", (int64_t)C * 7); slot("dwconv.bias", C); slot("norm.weight", C); slot("norm.bias", C);
-    slot("pwconv1.weight", (int64_t)4 * C * C); slot("pwconv1.bias", 4 * C); slot("pwconv2.weight", (int64_t)4 * C * C);
-    slot("pwconv2.bias", C); slot("gamma", C);
-    m->grad_floats = off;
+    m->clear_slots();
+    convnext_slots(*m, "", m->C);
     m->train_ready = true;
   }
   m->ts.t.clear();
@@ -1176,6 +1282,11 @@ CxPlan cx_plan(const dmel_convnext* m, int N, int64_t T, void* ws) {
   return p;
 }
 struct CxGrads { float *dw_w, *dw_b, *ln_w, *ln_b, *w1, *b1, *w2, *b2, *gamma; };
+CxGrads cx_grads(const TrainHandle& h, float* grads, const std::string& p) {
+  auto G = [&](const char* k) { return grads + h.offset_of(p + k); };
+  return CxGrads{G("dwconv.weight"), G("dwconv.bias"), G("norm.weight"), G("norm.bias"), G("pwconv1.weight"), G("pwconv1.bias"),
+                 G("pwconv2.weight"), G("pwconv2.bias"), G("gamma")};
+}
 
 // firefly.py:383-402 unfused, keeping the pre-norm, normed, pre-GELU, post-GELU and pre-scale tensors for backward
 int convnext_train_fwd(const ConvNeXt& cx, const CxPlan& p, const float* x, float* y, int N, int C, int64_t T, hipStream_t st) {
@@ -1187,33 +1298,23 @@ int convnext_train_fwd(const ConvNeXt& cx, const CxPlan& p, const float* x, floa
   DMEL_TRY(launch_conv(cx.pw2, b, st));
   return launch_layerscale_res_fwd(x, p.V, cx.gamma.as<float>(), y, N, C, T, st);
 }
-int convnext_bwd(const ConvNeXt& cx, const PackedConv& pw1T, const PackedConv& pw2T, const CxPlan& p, const CxGrads& g, const float* x,
-                 const float* dy, float* dx, int N, int C, int64_t T, hipStream_t st) {
+int convnext_bwd(const ConvNeXt& cx, const CxPlan& p, const CxGrads& g, const float* x, const float* dy, float* dx, int N, int C, int64_t T,
+                 hipStream_t st) {
   DMEL_TRY(launch_layerscale_bwd(dy, p.V, cx.gamma.as<float>(), p.DV, g.gamma, N, C, T, st));          // y = x + gamma * V
   DMEL_TRY(launch_conv_wgrad(p.G, p.DV, g.w2, g.b2, C, 4 * C, 1, 1, N, T, st));                         // V = pwconv2(G)
   {
     ConvRun r = run_1seg(p.DV, C, T, p.DG, 4 * C, T, N);
-    DMEL_TRY(launch_conv(pw2T, r, st));
+    DMEL_TRY(launch_conv(cx.pw2T, r, st));
   }
   DMEL_TRY(launch_gelu_bwd(p.DG, p.U, p.DG, (int64_t)(4 * p.n), st));                                   // G = gelu(U); d U overwrites d G
   DMEL_TRY(launch_conv_wgrad(p.H1, p.DG, g.w1, g.b1, 4 * C, C, 1, 1, N, T, st));                        // U = pwconv1(H1)
   {
     ConvRun r = run_1seg(p.DG, 4 * C, T, p.DH1, C, T, N);
-    DMEL_TRY(launch_conv(pw1T, r, st));
+    DMEL_TRY(launch_conv(cx.pw1T, r, st));
   }
   // H1 = LayerNorm(H0), H0 = dwconv(x); dx = dy (identity path) + dwconv^T(d H0)
   DMEL_TRY(launch_ln_bwd(p.DH1, p.H0, cx.ln_w.as<float>(), p.DH0, g.ln_w, g.ln_b, N, C, T, st));
   return launch_dwconv_bwd(p.DH0, x, cx.dw_w.as<float>(), dy, dx, g.dw_w, g.dw_b, N, C, T, st);
-}
-int pack_convnext_T(PackedConv& pw1T, PackedConv& pw2T, const TensorStore& ts, const std::string& p, int C) {
-  const HostTensor* w1 = ts.need(p + "pwconv1.weight", {4 * C, C});
-  const HostTensor* w2 = ts.need(p + "pwconv2.weight", {C, 4 * C});
-  if (!w1 || !w2) return DMEL_EMISSING;
-  PackDesc d;
-  d.mode = EPI_LINEAR; d.nseg = 1; d.C = C; d.seg[0].Cin = 4 * C;          // d u (4C) -> d h1 (C): W1^T
-  DMEL_TRY(pack_conv(pw1T, d, [&](int, int row, int cc, int) { return w1->v[(size_t)cc * C + row]; }, [&](int) { return 0.f; }));
-  d.C = 4 * C; d.seg[0].Cin = C;                                           // d v (C) -> d g (4C): W2^T
-  return pack_conv(pw2T, d, [&](int, int row, int cc, int) { return w2->v[(size_t)cc * 4 * C + row]; }, [&](int) { return 0.f; });
 }
 }  // namespace
 
@@ -1221,14 +1322,9 @@ extern "C" size_t dmel_convnext_train_workspace_bytes(const dmel_convnext* m, in
   if (!m || N <= 0 || T <= 0) return 0;
   return cx_plan(m, N, T, nullptr).bytes;
 }
-extern "C" int64_t dmel_convnext_grad_floats(const dmel_convnext* m) { return m && m->train_ready ? m->grad_floats : 0; }
+extern "C" int64_t dmel_convnext_grad_floats(const dmel_convnext* m) { return train_grad_floats(m); }
 extern "C" int dmel_convnext_grad_slot(const dmel_convnext* m, const char* key, int64_t* offset, int64_t* numel) {
-  DMEL_CHECK_ARG(m && key && offset && numel, "convnext_grad_slot: NULL argument");
-  if (!m->train_ready) { set_error("convnext_grad_slot: training was not enabled before finalize"); return DMEL_EMISSING; }
-  for (const auto& s : m->slots)
-    if (s.key == key) { *offset = s.offset; *numel = s.numel; return DMEL_OK; }
-  set_error("convnext_grad_slot: '%s' is not a parameter of ConvNeXtBlock", key);
-  return DMEL_EINVAL;
+  return train_grad_slot(m, "convnext", "a parameter of ConvNeXtBlock", key, offset, numel);
 }
 
 extern "C" int dmel_convnext_forward_train(const dmel_convnext* m, const float* x, float* y, int N, int64_t T, void* workspace,
@@ -1250,39 +1346,18 @@ extern "C" int dmel_convnext_backward(const dmel_convnext* m, const float* x, co
   DMEL_CHECK_ARG(N > 0 && T > 0, "convnext_backward: bad shape");
   const CxPlan p = cx_plan(m, N, T, workspace);
   DMEL_CHECK_ARG(workspace_bytes >= p.bytes, "convnext_backward: workspace too small (%zu < %zu)", workspace_bytes, p.bytes);
-  auto G = [&](const char* key) -> float* {
-    for (const auto& s : m->slots)
-      if (s.key == key) return grads + s.offset;
-    return nullptr;
-  };
-  CxGrads g{G("dwconv.weight"), G("dwconv.bias"), G("norm.weight"), G("norm.bias"), G("pwconv1.weight"), G("pwconv1.bias"),
-            G("pwconv2.weight"), G("pwconv2.bias"), G("gamma")};
-  return convnext_bwd(m->cx, m->pw1T, m->pw2T, p, g, x, dy, dx, N, m->C, T, (hipStream_t)stream);
+  return convnext_bwd(m->cx, p, cx_grads(*m, grads, ""), x, dy, dx, N, m->C, T, (hipStream_t)stream);
 }
 
-struct dmel_quantizer {
-  int train_precision = 0;     // DMEL_PRECISION_BF16: bf16 training mode
+struct dmel_quantizer : TrainHandle {
   int dim, G, Cg, D, nf;
   int factors[4];
   int levels[4];
   FsqConst fk;
-  TensorStore ts;
-  bool ready = false;
-  std::vector<PackedConv> down, up;
-  std::vector<ConvNeXt> down_cx, up_cx;
+  // per stage: the k2s2 conv / transposed conv with its ConvNeXt block, and (training) their backward-data images
+  struct Stage { WeightImage down, up, down_dx, up_dx; ConvNeXt down_cx, up_cx; };
+  std::vector<Stage> stage;
   DevBuf w_in, b_in, w_out, b_out;
-  // training path
-  bool train = false, train_ready = false;
-  std::vector<PackedConv> down_dx, up_dx;                      // backward-data images of the k2s2 conv / transposed conv
-  std::vector<PackedConv> down_pw1T, down_pw2T, up_pw1T, up_pw2T;
-  struct GradSlot { std::string key; int64_t offset, numel; };
-  std::vector<GradSlot> slots;
-  int64_t grad_floats = 0;
-  int64_t slot_of(const std::string& key) const {
-    for (const auto& s : slots)
-      if (s.key == key) return s.offset;
-    return -1;
-  }
 };
 
 extern "C" int dmel_quantizer_create(dmel_quantizer** out, int input_dim, int n_groups, const int* levels, int n_levels,
@@ -1312,40 +1387,54 @@ extern "C" int dmel_quantizer_set_strict(dmel_quantizer* q, int on) {
 }
 extern "C" void dmel_quantizer_destroy(dmel_quantizer* q) { delete q; }
 extern "C" int dmel_quantizer_set_tensor(dmel_quantizer* q, const char* key, const float* data, const int64_t* shape, int ndim) {
-  DMEL_CHECK_ARG(q, "NULL handle");
-  q->ready = false;
-  return q->ts.set(key, data, shape, ndim);
+  return train_set_tensor(q, key, data, shape, ndim);
 }
 
 extern "C" int dmel_quantizer_finalize(dmel_quantizer* q) {
   DMEL_CHECK_ARG(q, "NULL handle");
+  q->ready = q->train_ready = false;      // until every image is packed: a finalize that fails leaves a handle that refuses to run
   const int C = q->Cg, G = q->G, D = q->D;
-  q->down.clear(); q->up.clear(); q->down_cx.clear(); q->up_cx.clear();
-  q->down.resize(q->nf); q->up.resize(q->nf); q->down_cx.resize(q->nf); q->up_cx.resize(q->nf);
+  q->stage.clear();
+  q->stage.resize(q->nf);
+  q->clear_slots();
+  PackDesc k2s2, k2s2T;
+  k2s2.mode = EPI_LINEAR; k2s2.nseg = 2; k2s2.C = C;                   // Conv1d(k=2, stride=2): two 1-tap segments reading x[2s] and x[2s+1]
+  for (int s = 0; s < 2; ++s) { k2s2.seg[s].Cin = C; k2s2.seg[s].tstride = 2; k2s2.seg[s].toff = s; }
+  k2s2T.mode = EPI_LINEAR; k2s2T.nseg = 1; k2s2T.C = C; k2s2T.phases = 2; k2s2T.seg[0].Cin = C;      // its transpose: phase-major rows
+  // the two views of a (C, C, 2) weight: rows as they lie with tap sg of segment sg, value(sg, row, ci) = w[(row*C + ci)*2 + sg];
+  // and phase-major rows over the transpose, value(row = (ph, co), ci) = w[(ci*C + co)*2 + ph]
+  auto strided = [&](const std::string& key) {
+    ImageSrc v;
+    for (int sg = 0; sg < 2; ++sg) { v.seg[sg].key = key; v.seg[sg].off = sg; v.seg[sg].rs = 2 * C; v.seg[sg].cs = 2; }
+    return v;
+  };
+  auto phased = [&](const std::string& key) {
+    ImageSrc v;
+    v.seg[0].key = key; v.seg[0].rs = 2; v.seg[0].cs = 2 * C; v.seg[0].ps = 1; v.seg[0].pC = C;
+    return v;
+  };
   for (int i = 0; i < q->nf; ++i) {
-    {  // downsample.{i}.0 = Conv1d(C, C, k=2, stride=2): two 1-tap segments reading x[2s] and x[2s+1]
-      const std::string p = "downsample." + std::to_string(i) + ".0.";
-      const HostTensor* w = q->ts.need(p + "weight", {C, C, 2});
-      const HostTensor* b = q->ts.need(p + "bias", {C});
+    dmel_quantizer::Stage& sg = q->stage[i];
+    const std::string pd = "downsample." + std::to_string(i) + ".", pu = "upsample." + std::to_string(i) + ".";
+    for (int up = 0; up < 2; ++up) {
+      const std::string& p = up ? pu : pd;
+      const HostTensor* w = q->ts.need(p + "0.weight", {C, C, 2});
+      const HostTensor* b = q->ts.need(p + "0.bias", {C});
       if (!w || !b) return DMEL_EMISSING;
-      PackDesc d;
-      d.mode = EPI_LINEAR; d.nseg = 2; d.C = C;
-      for (int s = 0; s < 2; ++s) { d.seg[s].Cin = C; d.seg[s].tstride = 2; d.seg[s].toff = s; }
-      DMEL_TRY(pack_conv(q->down[i], d, [&](int sg, int row, int ci, int) { return w->v[((size_t)row * C + ci) * 2 + sg]; },
-                         [&](int row) { return b->v[row]; }));
-      DMEL_TRY(build_convnext(q->down_cx[i], q->ts, "downsample." + std::to_string(i) + ".1.", C));
+      // upsample.{i}.0 = ConvTranspose1d, weight (Cin, Cout, 2): out[2q+ph] = W[:, :, ph]^T x[q], one bias per output channel for both phases
+      ImageSrc src = up ? phased(p + "0.weight") : strided(p + "0.weight");
+      src.b0 = p + "0.bias";
+      src.bias_mod = up ? C : 0;
+      DMEL_TRY(pack_image(up ? sg.up : sg.down, up ? k2s2T : k2s2, src, q->ts));
+      DMEL_TRY(build_convnext(up ? sg.up_cx : sg.down_cx, q->ts, p + "1.", C, q->train));
     }
-    {  // upsample.{i}.0 = ConvTranspose1d(C, C, k=2, stride=2): weight (Cin, Cout, 2); out[2q+ph] = W[:, :, ph]^T x[q]
-      const std::string p = "upsample." + std::to_string(i) + ".0.";
-      const HostTensor* w = q->ts.need(p + "weight", {C, C, 2});
-      const HostTensor* b = q->ts.need(p + "bias", {C});
-      if (!w || !b) return DMEL_EMISSING;
-      PackDesc d;
-      d.mode = EPI_LINEAR; d.nseg = 1; d.C = C; d.phases = 2; d.seg[0].Cin = C;
-      DMEL_TRY(pack_conv(q->up[i], d,
-                         [&](int, int row, int ci, int) { int ph = row / C, co = row % C; return w->v[((size_t)ci * C + co) * 2 + ph]; },
-                         [&](int row) { return b->v[row % C]; }));
-      DMEL_TRY(build_convnext(q->up_cx[i], q->ts, "upsample." + std::to_string(i) + ".1.", C));
+    if (!q->train) continue;
+    // d x[ci, 2q + k] = sum_co W[co, ci, k] d y[co, q]: a k2s2 transposed conv;  d x[ci, q] = sum_{co, k} W[ci, co, k] d y[co, 2q + k]: a k2s2 conv
+    DMEL_TRY(pack_image(sg.down_dx, k2s2T, phased(pd + "0.weight"), q->ts));
+    DMEL_TRY(pack_image(sg.up_dx, k2s2, strided(pu + "0.weight"), q->ts));
+    for (const std::string* p : {&pd, &pu}) {
+      q->add(*p + "0.weight", (int64_t)C * C * 2); q->add(*p + "0.bias", C);
+      convnext_slots(*q, *p + "1.", C);
     }
   }
   std::vector<float> wi((size_t)G * D * C), bi((size_t)G * D), wo((size_t)G * C * D), bo((size_t)G * C);
@@ -1364,46 +1453,8 @@ extern "C" int dmel_quantizer_finalize(dmel_quantizer* q) {
   DMEL_TRY(upload_vec(q->w_in, wi)); DMEL_TRY(upload_vec(q->b_in, bi));
   DMEL_TRY(upload_vec(q->w_out, wo)); DMEL_TRY(upload_vec(q->b_out, bo));
   if (q->train) {
-    q->down_dx.clear(); q->up_dx.clear(); q->down_pw1T.clear(); q->down_pw2T.clear(); q->up_pw1T.clear(); q->up_pw2T.clear();
-    q->down_dx.resize(q->nf); q->up_dx.resize(q->nf);
-    q->down_pw1T.resize(q->nf); q->down_pw2T.resize(q->nf); q->up_pw1T.resize(q->nf); q->up_pw2T.resize(q->nf);
-    q->slots.clear();
-    int64_t off = 0;
-    auto slot = [&](const std::string& key, int64_t numel) { q->slots.push_back({key, off, numel}); off += numel; };
-    const char* cxk[9] = {"dwconv.weight", "dwconv.bias", "norm.weight", "norm.bias", "pwconv1.weight", "pwconv1.bias", "pwconv2.weight",
-                          "pwconv2.bias", "gamma"};
-    const int64_t cxn[9] = {(int64_t)C * 7, C, C, C, (int64_t)4 * C * C, 4 * C, (int64_t)4 * C * C, C, C};
-    for (int i = 0; i < q->nf; ++i) {
-      const std::string pd = "downsample." + std::to_string(i) + ".", pu = "upsample." + std::to_string(i) + ".";
-      const HostTensor* wd = q->ts.need(pd + "0.weight", {C, C, 2});
-      const HostTensor* wu = q->ts.need(pu + "0.weight", {C, C, 2});
-      if (!wd || !wu) return DMEL_EMISSING;
-      {  // d x[ci, 2q + k] = sum_co W[co, ci, k] d y[co, q]: a k2s2 transposed conv (phase-major rows)
-        PackDesc d;
-        d.mode = EPI_LINEAR; d.nseg = 1; d.C = C; d.phases = 2; d.seg[0].Cin = C;
-        DMEL_TRY(pack_conv(q->down_dx[i], d,
-                           [&](int, int row, int cc, int) { int ph = row / C, ci = row % C; return wd->v[((size_t)cc * C + ci) * 2 + ph]; },
-                           [&](int) { return 0.f; }));
-      }
-      {  // d x[ci, q] = sum_{co, k} W[ci, co, k] d y[co, 2q + k]: a k2s2 conv (two strided 1-tap segments)
-        PackDesc d;
-        d.mode = EPI_LINEAR; d.nseg = 2; d.C = C;
-        for (int sgi = 0; sgi < 2; ++sgi) { d.seg[sgi].Cin = C; d.seg[sgi].tstride = 2; d.seg[sgi].toff = sgi; }
-        DMEL_TRY(pack_conv(q->up_dx[i], d, [&](int sg, int row, int cc, int) { return wu->v[((size_t)row * C + cc) * 2 + sg]; },
-                           [&](int) { return 0.f; }));
-      }
-      DMEL_TRY(pack_convnext_T(q->down_pw1T[i], q->down_pw2T[i], q->ts, pd + "1.", C));
-      DMEL_TRY(pack_convnext_T(q->up_pw1T[i], q->up_pw2T[i], q->ts, pu + "1.", C));
-      slot(pd + "0.weight", (int64_t)C * C * 2); slot(pd + "0.bias", C);
-      for (int k = 0; k < 9; ++k) slot(pd + "1." + cxk[k], cxn[k]);
-      slot(pu + "0.weight", (int64_t)C * C * 2); slot(pu + "0.bias", C);
-      for (int k = 0; k < 9; ++k) slot(pu + "1." + cxk[k], cxn[k]);
-    }
     // FSQ parameter gradients come out in the packed (G, ...) layouts: group g's tensor is the g-th block of each region
-    const int64_t o_wi = off; off += (int64_t)G * D * C;
-    const int64_t o_bi = off; off += (int64_t)G * D;
-    const int64_t o_wo = off; off += (int64_t)G * C * D;
-    const int64_t o_bo = off; off += (int64_t)G * C;
+    const int64_t o_wi = q->grad_floats, o_bi = o_wi + (int64_t)G * D * C, o_wo = o_bi + (int64_t)G * D, o_bo = o_wo + (int64_t)G * C * D;
     for (int g = 0; g < G; ++g) {
       const std::string p = "residual_fsq.rvqs." + std::to_string(g) + ".";
       q->slots.push_back({p + "project_in.weight", o_wi + (int64_t)g * D * C, (int64_t)D * C});
@@ -1411,11 +1462,10 @@ extern "C" int dmel_quantizer_finalize(dmel_quantizer* q) {
       q->slots.push_back({p + "project_out.weight", o_wo + (int64_t)g * C * D, (int64_t)C * D});
       q->slots.push_back({p + "project_out.bias", o_bo + (int64_t)g * C, C});
     }
-    q->slots.push_back({"#fsq.w_in", o_wi, (int64_t)G * D * C});
-    q->slots.push_back({"#fsq.b_in", o_bi, (int64_t)G * D});
-    q->slots.push_back({"#fsq.w_out", o_wo, (int64_t)G * C * D});
-    q->slots.push_back({"#fsq.b_out", o_bo, (int64_t)G * C});
-    q->grad_floats = off;
+    q->add("#fsq.w_in", (int64_t)G * D * C);
+    q->add("#fsq.b_in", (int64_t)G * D);
+    q->add("#fsq.w_out", (int64_t)G * C * D);
+    q->add("#fsq.b_out", (int64_t)G * C);
     q->train_ready = true;
   }
   q->ts.t.clear();
@@ -1423,18 +1473,8 @@ extern "C" int dmel_quantizer_finalize(dmel_quantizer* q) {
   return DMEL_OK;
 }
 
-extern "C" int dmel_quantizer_set_train_precision(dmel_quantizer* q, int precision) {
-  DMEL_CHECK_ARG(q && (precision == DMEL_PRECISION_FP32 || precision == DMEL_PRECISION_BF16), "quantizer_set_train_precision: DMEL_PRECISION_FP32 or DMEL_PRECISION_BF16");
-  q->train_precision = precision;
-  return DMEL_OK;
-}
-extern "C" int dmel_quantizer_enable_training(dmel_quantizer* q, int on) {
-  DMEL_CHECK_ARG(q, "NULL handle");
-  q->train = on != 0;
-  q->ready = false;
-  q->train_ready = false;
-  return DMEL_OK;
-}
+extern "C" int dmel_quantizer_set_train_precision(dmel_quantizer* q, int precision) { return train_set_precision(q, "quantizer", precision); }
+extern "C" int dmel_quantizer_enable_training(dmel_quantizer* q, int on) { return train_enable(q, on); }
 
 static size_t quantizer_plan(const dmel_quantizer* q, int B, int64_t Tmax, void* ws, float** a, float** b, float** h1, float** h2) {
   Arena ar(ws, (size_t)-1);
@@ -1504,8 +1544,8 @@ static int quantizer_encode_run(const dmel_quantizer* q, const float* z, const i
     }
     r.B = N; r.Tcols = Tn; r.y = o; r.y_bs = (int64_t)C * Tn; r.y_cs = Tn; r.Tout = Tn;
     r.out_len = len_at(i + 1); r.len_div = lengths ? q->G : 1;
-    DMEL_TRY(launch_conv(q->down[i], r, st));
-    DMEL_TRY(run_convnext(q->down_cx[i], o, o, h1, h2, N, C, Tn, st, len_at(i + 1), lengths ? q->G : 1));
+    DMEL_TRY(launch_conv(q->stage[i].down, r, st));
+    DMEL_TRY(run_convnext(q->stage[i].down_cx, o, o, h1, h2, N, C, Tn, st, len_at(i + 1), lengths ? q->G : 1));
     cur = o;
     Tc = Tn;
   }
@@ -1551,8 +1591,8 @@ static int quantizer_decode_run(const dmel_quantizer* q, const int32_t* ids, con
     ConvRun r = run_1seg(cur, C, Tc, o, C, Tn, N);
     r.Tcols = Tc; r.out_tstride = 2; r.Tout = Tn;
     r.seg[0].in_len = len_at(j); r.out_len = len_at(j + 1); r.len_div = lengths ? q->G : 1;      // out_len counts OUTPUT columns (conv_dev.h)
-    DMEL_TRY(launch_conv(q->up[j], r, st));
-    DMEL_TRY(run_convnext(q->up_cx[j], o, o, h1, h2, N, C, Tn, st, len_at(j + 1), lengths ? q->G : 1));
+    DMEL_TRY(launch_conv(q->stage[j].up, r, st));
+    DMEL_TRY(run_convnext(q->stage[j].up_cx, o, o, h1, h2, N, C, Tn, st, len_at(j + 1), lengths ? q->G : 1));
     cur = o;
     Tc = Tn;
   }
@@ -1574,90 +1614,22 @@ extern "C" int dmel_quantizer_decode_items(const dmel_quantizer* q, const int32_
 extern "C" int dmel_quantizer_refresh(dmel_quantizer* q, int n, const char* const* keys, const float* const* device_tensors, void* stream) {
   DMEL_CHECK_ARG(q && keys && device_tensors && n > 0, "quantizer_refresh: bad argument");
   if (!q->ready) { set_error("quantizer_refresh: handle not finalized"); return DMEL_EMISSING; }
-  std::map<std::string, const float*> dev;
-  for (int i = 0; i < n; ++i) {
-    DMEL_CHECK_ARG(keys[i] && device_tensors[i], "quantizer_refresh: NULL entry %d", i);
-    dev[keys[i]] = device_tensors[i];
+  Refresh r("quantizer_refresh", stream);
+  DMEL_TRY(r.open(n, keys, device_tensors));
+  const int C = q->Cg, D = q->D;
+  for (auto& sg : q->stage) {
+    DMEL_TRY(r.add(sg.down)); DMEL_TRY(refresh_convnext(r, sg.down_cx, C, q->train_ready));
+    DMEL_TRY(r.add(sg.up)); DMEL_TRY(refresh_convnext(r, sg.up_cx, C, q->train_ready));
+    if (q->train_ready) { DMEL_TRY(r.add(sg.down_dx)); DMEL_TRY(r.add(sg.up_dx)); }
   }
-  const int C = q->Cg, G = q->G, D = q->D;
-  {  // every key is resolved before the first copy or launch: a refused refresh leaves the handle as it was
-    std::vector<std::string> need;
-    for (int i = 0; i < q->nf; ++i)
-      for (const char* side : {"downsample.", "upsample."}) {
-        const std::string p = side + std::to_string(i) + ".";
-        for (const char* k : {"0.weight", "0.bias", "1.pwconv1.weight", "1.pwconv1.bias", "1.pwconv2.weight", "1.pwconv2.bias", "1.dwconv.weight",
-                              "1.dwconv.bias", "1.norm.weight", "1.norm.bias", "1.gamma"})
-          need.push_back(p + k);
-      }
-    for (int g = 0; g < G; ++g)
-      for (const char* k : {"project_in.weight", "project_in.bias", "project_out.weight", "project_out.bias"})
-        need.push_back("residual_fsq.rvqs." + std::to_string(g) + "." + k);
-    for (const auto& k : need)
-      if (!dev.count(k)) { set_error("quantizer_refresh: tensor '%s' was not provided", k.c_str()); return DMEL_EMISSING; }
-  }
-  auto T = [&](const std::string& k) -> const float* { return dev.find(k)->second; };      // present: checked above
-  hipStream_t st = (hipStream_t)stream;
-  RepackBatch batch(st);
-  auto copy = [&](DevBuf& dst, const float* src, size_t count) -> int {
-    DMEL_HIP(hipMemcpyAsync(dst.p, src, count * sizeof(float), hipMemcpyDeviceToDevice, st));
-    return DMEL_OK;
-  };
-  auto seg = [](const float* w, int64_t rs, int64_t cs, int64_t ps = 0, int pC = 0) {
-    RepackSeg s;
-    s.w = w; s.rs = rs; s.cs = cs; s.ps = ps; s.pC = pC;
-    return s;
-  };
-  auto refresh_cx = [&](ConvNeXt& cx, PackedConv* pw1T, PackedConv* pw2T, const std::string& p) -> int {
-    const float *w1 = T(p + "pwconv1.weight"), *b1 = T(p + "pwconv1.bias"), *w2 = T(p + "pwconv2.weight"), *b2 = T(p + "pwconv2.bias");
-    const float *dw = T(p + "dwconv.weight"), *db = T(p + "dwconv.bias"), *lw = T(p + "norm.weight"), *lb = T(p + "norm.bias");
-    const float* ga = T(p + "gamma");
-    DMEL_TRY(copy(cx.dw_w, dw, (size_t)C * 7)); DMEL_TRY(copy(cx.dw_b, db, C)); DMEL_TRY(copy(cx.ln_w, lw, C));
-    DMEL_TRY(copy(cx.ln_b, lb, C)); DMEL_TRY(copy(cx.gamma, ga, C));
-    RepackSrc a; a.seg[0] = seg(w1, C, 1); a.b0 = b1;
-    DMEL_TRY(launch_repack(cx.pw1, a, st));
-    RepackSrc b; b.seg[0] = seg(w2, 4 * C, 1); b.b0 = b2;
-    DMEL_TRY(launch_repack(cx.pw2, b, st));
-    if (pw1T) {
-      RepackSrc c; c.seg[0] = seg(w1, 1, C);
-      DMEL_TRY(launch_repack(*pw1T, c, st));
-      RepackSrc d; d.seg[0] = seg(w2, 1, 4 * C);
-      DMEL_TRY(launch_repack(*pw2T, d, st));
-    }
-    return DMEL_OK;
-  };
-  for (int i = 0; i < q->nf; ++i) {
-    const std::string pd = "downsample." + std::to_string(i) + ".", pu = "upsample." + std::to_string(i) + ".";
-    const float *wd = T(pd + "0.weight"), *bd = T(pd + "0.bias"), *wu = T(pu + "0.weight"), *bu = T(pu + "0.bias");
-    {  // value(sg, row, ci) = wd[(row*C + ci)*2 + sg]
-      RepackSrc a; a.seg[0] = seg(wd, 2 * C, 2); a.seg[1] = seg(wd + 1, 2 * C, 2); a.b0 = bd;
-      DMEL_TRY(launch_repack(q->down[i], a, st));
-    }
-    {  // value(row = (ph, co), ci) = wu[(ci*C + co)*2 + ph]; bias[co]
-      RepackSrc a; a.seg[0] = seg(wu, 2, 2 * C, 1, C); a.b0 = bu; a.bias_mod = C;
-      DMEL_TRY(launch_repack(q->up[i], a, st));
-    }
-    DMEL_TRY(refresh_cx(q->down_cx[i], q->train_ready ? &q->down_pw1T[i] : nullptr, q->train_ready ? &q->down_pw2T[i] : nullptr, pd + "1."));
-    DMEL_TRY(refresh_cx(q->up_cx[i], q->train_ready ? &q->up_pw1T[i] : nullptr, q->train_ready ? &q->up_pw2T[i] : nullptr, pu + "1."));
-    if (q->train_ready) {
-      {  // value(row = (ph, ci), cc) = wd[(cc*C + ci)*2 + ph]
-        RepackSrc a; a.seg[0] = seg(wd, 2, 2 * C, 1, C);
-        DMEL_TRY(launch_repack(q->down_dx[i], a, st));
-      }
-      {  // value(sg, row, cc) = wu[(row*C + cc)*2 + sg]
-        RepackSrc a; a.seg[0] = seg(wu, 2 * C, 2); a.seg[1] = seg(wu + 1, 2 * C, 2);
-        DMEL_TRY(launch_repack(q->up_dx[i], a, st));
-      }
-    }
-  }
-  for (int g = 0; g < G; ++g) {
+  for (int g = 0; g < q->G; ++g) {
     const std::string p = "residual_fsq.rvqs." + std::to_string(g) + ".";
-    const float *a = T(p + "project_in.weight"), *ab = T(p + "project_in.bias"), *o = T(p + "project_out.weight"), *ob = T(p + "project_out.bias");
-    DMEL_HIP(hipMemcpyAsync(q->w_in.as<float>() + (size_t)g * D * C, a, (size_t)D * C * sizeof(float), hipMemcpyDeviceToDevice, st));
-    DMEL_HIP(hipMemcpyAsync(q->b_in.as<float>() + (size_t)g * D, ab, (size_t)D * sizeof(float), hipMemcpyDeviceToDevice, st));
-    DMEL_HIP(hipMemcpyAsync(q->w_out.as<float>() + (size_t)g * C * D, o, (size_t)C * D * sizeof(float), hipMemcpyDeviceToDevice, st));
-    DMEL_HIP(hipMemcpyAsync(q->b_out.as<float>() + (size_t)g * C, ob, (size_t)C * sizeof(float), hipMemcpyDeviceToDevice, st));
+    DMEL_TRY(r.copy(q->w_in.as<float>() + (size_t)g * D * C, p + "project_in.weight", (size_t)D * C));
+    DMEL_TRY(r.copy(q->b_in.as<float>() + (size_t)g * D, p + "project_in.bias", D));
+    DMEL_TRY(r.copy(q->w_out.as<float>() + (size_t)g * C * D, p + "project_out.weight", (size_t)C * D));
+    DMEL_TRY(r.copy(q->b_out.as<float>() + (size_t)g * C, p + "project_out.bias", C));
   }
-  return batch.flush();
+  return r.run();
 }
 
 // ---- quantiser training path: DownsampleFiniteScalarQuantize.forward (dowmsample_fsq.py:86-122) and its backward ----------
@@ -1701,25 +1673,15 @@ QPlan q_plan(const dmel_quantizer* q, int B, int64_t T, void* ws) {
   p.bytes = align_up(a.off, 256);
   return p;
 }
-CxGrads cx_grads(const dmel_quantizer* q, float* grads, const std::string& p) {
-  auto G = [&](const char* k) { return grads + q->slot_of(p + k); };
-  return CxGrads{G("dwconv.weight"), G("dwconv.bias"), G("norm.weight"), G("norm.bias"), G("pwconv1.weight"), G("pwconv1.bias"),
-                 G("pwconv2.weight"), G("pwconv2.bias"), G("gamma")};
-}
 }  // namespace
 
 extern "C" size_t dmel_quantizer_train_workspace_bytes(const dmel_quantizer* q, int B, int64_t T) {
   if (!q || B <= 0 || T <= 0) return 0;
   return q_plan(q, B, T, nullptr).bytes;
 }
-extern "C" int64_t dmel_quantizer_grad_floats(const dmel_quantizer* q) { return q && q->train_ready ? q->grad_floats : 0; }
+extern "C" int64_t dmel_quantizer_grad_floats(const dmel_quantizer* q) { return train_grad_floats(q); }
 extern "C" int dmel_quantizer_grad_slot(const dmel_quantizer* q, const char* key, int64_t* offset, int64_t* numel) {
-  DMEL_CHECK_ARG(q && key && offset && numel, "quantizer_grad_slot: NULL argument");
-  if (!q->train_ready) { set_error("quantizer_grad_slot: training was not enabled before finalize"); return DMEL_EMISSING; }
-  for (const auto& s : q->slots)
-    if (s.key == key) { *offset = s.offset; *numel = s.numel; return DMEL_OK; }
-  set_error("quantizer_grad_slot: '%s' is not a trained parameter of this quantiser", key);
-  return DMEL_EINVAL;
+  return train_grad_slot(q, "quantizer", "a trained parameter of this quantiser", key, offset, numel);
 }
 
 // z (B*G, Cg, T) -> zq (B*G, Cg, T) [= (B, G*Cg, T)], ids (B, G, T4), latents (B*G, Cg, T4); zq is zero-padded from 2^nf * T4 to T
@@ -1741,9 +1703,9 @@ extern "C" int dmel_quantizer_forward_train(const dmel_quantizer* q, const float
     ConvRun r;
     for (int s = 0; s < 2; ++s) { r.seg[s].x = cur; r.seg[s].bstride = (int64_t)C * sgq.Tin; r.seg[s].cstride = sgq.Tin; r.seg[s].Tin = sgq.Tin; }
     r.B = N; r.Tcols = sgq.Tout; r.y = sgq.conv; r.y_bs = (int64_t)C * sgq.Tout; r.y_cs = sgq.Tout; r.Tout = sgq.Tout;
-    DMEL_TRY(launch_conv(q->down[i], r, st));
+    DMEL_TRY(launch_conv(q->stage[i].down, r, st));
     float* o = (i == q->nf - 1) ? p.lat : p.down[i + 1].in;
-    DMEL_TRY(convnext_train_fwd(q->down_cx[i], sgq.cx, sgq.conv, o, N, C, sgq.Tout, st));
+    DMEL_TRY(convnext_train_fwd(q->stage[i].down_cx, sgq.cx, sgq.conv, o, N, C, sgq.Tout, st));
     cur = o;
   }
   DMEL_TRY(launch_fsq_encode(p.lat, q->w_in.as<float>(), q->b_in.as<float>(), p.ids, nullptr, q->fk, B, q->G, C, p.T4, st));
@@ -1755,9 +1717,9 @@ extern "C" int dmel_quantizer_forward_train(const dmel_quantizer* q, const float
     const QStage& sgq = p.up[j];
     ConvRun r = run_1seg(cur, C, sgq.Tin, sgq.conv, C, sgq.Tout, N);
     r.Tcols = sgq.Tin; r.out_tstride = 2; r.Tout = sgq.Tout;
-    DMEL_TRY(launch_conv(q->up[j], r, st));
+    DMEL_TRY(launch_conv(q->stage[j].up, r, st));
     float* o = (j == q->nf - 1) ? p.ga : p.up[j + 1].in;
-    DMEL_TRY(convnext_train_fwd(q->up_cx[j], sgq.cx, sgq.conv, o, N, C, sgq.Tout, st));
+    DMEL_TRY(convnext_train_fwd(q->stage[j].up_cx, sgq.cx, sgq.conv, o, N, C, sgq.Tout, st));
     cur = o;
   }
   const int64_t Tfull = p.up[q->nf - 1].Tout, diff = T - Tfull, left = diff / 2;
@@ -1796,45 +1758,45 @@ extern "C" int dmel_quantizer_backward(const dmel_quantizer* q, const float* z, 
   for (int j = q->nf - 1; j >= 0; --j) {      // upsample.{j}: ConvTranspose1d(k2, s2) -> ConvNeXtBlock
     const QStage& sgq = p.up[j];
     const std::string pu = "upsample." + std::to_string(j) + ".";
-    DMEL_TRY(convnext_bwd(q->up_cx[j], q->up_pw1T[j], q->up_pw2T[j], sgq.cx, cx_grads(q, grads, pu + "1."), sgq.conv, g, other, N, C,
+    DMEL_TRY(convnext_bwd(q->stage[j].up_cx, sgq.cx, cx_grads(*q, grads, pu + "1."), sgq.conv, g, other, N, C,
                           sgq.Tout, st));
     std::swap(g, other);                       // g = d (transposed conv output), length Tout
-    float* dw = grads + q->slot_of(pu + "0.weight");
+    float* dw = grads + q->offset_of(pu + "0.weight");
     DMEL_TRY(zero_unless_cleared(dw, (size_t)C * C * 2 * sizeof(float), st));
     for (int k = 0; k < 2; ++k)                // d W[ci, co, k] = sum x[ci, q] d y[co, 2q + k]
       DMEL_TRY(launch_conv_wgrad_strided(sgq.in, g, dw, C, C, 2, k, sgq.Tin, sgq.Tout, 2, k, N, st));
-    DMEL_TRY(launch_conv_bgrad(g, grads + q->slot_of(pu + "0.bias"), C, N, sgq.Tout, st));
+    DMEL_TRY(launch_conv_bgrad(g, grads + q->offset_of(pu + "0.bias"), C, N, sgq.Tout, st));
     {
       ConvRun r;
       for (int s = 0; s < 2; ++s) { r.seg[s].x = g; r.seg[s].bstride = (int64_t)C * sgq.Tout; r.seg[s].cstride = sgq.Tout; r.seg[s].Tin = sgq.Tout; }
       r.B = N; r.Tcols = sgq.Tin; r.y = other; r.y_bs = (int64_t)C * sgq.Tin; r.y_cs = sgq.Tin; r.Tout = sgq.Tin;
-      DMEL_TRY(launch_conv(q->up_dx[j], r, st));
+      DMEL_TRY(launch_conv(q->stage[j].up_dx, r, st));
     }
     std::swap(g, other);                       // g = d (stage input), length Tin
   }
   // FSQ (straight-through)
   DMEL_TRY(launch_fsq_backward(p.lat, g, q->w_in.as<float>(), q->b_in.as<float>(), q->w_out.as<float>(), other,
-                               grads + q->slot_of("#fsq.w_in"), grads + q->slot_of("#fsq.b_in"), grads + q->slot_of("#fsq.w_out"),
-                               grads + q->slot_of("#fsq.b_out"), p.scratch, q->fk, B, q->G, C, p.T4, st));
+                               grads + q->offset_of("#fsq.w_in"), grads + q->offset_of("#fsq.b_in"), grads + q->offset_of("#fsq.w_out"),
+                               grads + q->offset_of("#fsq.b_out"), p.scratch, q->fk, B, q->G, C, p.T4, st));
   std::swap(g, other);
   for (int i = q->nf - 1; i >= 0; --i) {      // downsample.{i}: Conv1d(k2, s2) -> ConvNeXtBlock
     const QStage& sgq = p.down[i];
     const std::string pd = "downsample." + std::to_string(i) + ".";
-    DMEL_TRY(convnext_bwd(q->down_cx[i], q->down_pw1T[i], q->down_pw2T[i], sgq.cx, cx_grads(q, grads, pd + "1."), sgq.conv, g, other, N, C,
+    DMEL_TRY(convnext_bwd(q->stage[i].down_cx, sgq.cx, cx_grads(*q, grads, pd + "1."), sgq.conv, g, other, N, C,
                           sgq.Tout, st));
     std::swap(g, other);                       // g = d (conv output), length Tout
     const float* xin = i == 0 ? z : sgq.in;
-    float* dw = grads + q->slot_of(pd + "0.weight");
+    float* dw = grads + q->offset_of(pd + "0.weight");
     DMEL_TRY(zero_unless_cleared(dw, (size_t)C * C * 2 * sizeof(float), st));
     for (int k = 0; k < 2; ++k)                // d W[co, ci, k] = sum d y[co, q] x[ci, 2q + k]
       DMEL_TRY(launch_conv_wgrad_strided(g, xin, dw, C, C, 2, k, sgq.Tout, sgq.Tin, 2, k, N, st));
-    DMEL_TRY(launch_conv_bgrad(g, grads + q->slot_of(pd + "0.bias"), C, N, sgq.Tout, st));
+    DMEL_TRY(launch_conv_bgrad(g, grads + q->offset_of(pd + "0.bias"), C, N, sgq.Tout, st));
     float* dst = i == 0 ? dz : other;
     if (sgq.Tin != 2 * sgq.Tout) DMEL_HIP(hipMemsetAsync(dst, 0, NC * sgq.Tin * sizeof(float), st));   // odd length: the last sample is unused
     {
       ConvRun r = run_1seg(g, C, sgq.Tout, dst, C, sgq.Tin, N);
       r.Tcols = sgq.Tout; r.out_tstride = 2; r.Tout = sgq.Tin;
-      DMEL_TRY(launch_conv(q->down_dx[i], r, st));
+      DMEL_TRY(launch_conv(q->stage[i].down_dx, r, st));
     }
     if (i > 0) std::swap(g, other);
   }
@@ -1852,9 +1814,8 @@ extern "C" int dmel_quantizer_backward(const dmel_quantizer* q, const float* z, 
 namespace {
 struct DLayer {
   int Cin, Cout, kw, sw, pw;
-  PackedConv fwd[3];                      // per kernel row dh
-  std::vector<float> w;                   // folded weight (Cout, Cin, 3, kw), kept for the training images
-  PackedConv bwd[3][2];                   // backward-data per kernel row (and per output phase for the stride-2 layers)
+  WeightImage fwd[3];                     // per kernel row dh
+  WeightImage bwd[3][2];                  // backward-data per kernel row (and per output phase for the stride-2 layers)
   DevBuf g_dev, v_dev;                    // weight-norm parameters on the device (for d g / d v)
 };
 constexpr int kDiscLayers = 6;
@@ -1863,19 +1824,8 @@ const int kDiscCfg[kDiscLayers][5] = {{1, 64, 9, 1, 4}, {64, 128, 9, 2, 4}, {128
 int64_t disc_out_w(const DLayer& l, int64_t W) { return (W + 2 * l.pw - l.kw) / l.sw + 1; }
 }  // namespace
 
-struct dmel_discriminator {
-  int train_precision = 0;     // DMEL_PRECISION_BF16: bf16 training mode
-  TensorStore ts;
-  bool ready = false, train = false, train_ready = false;
+struct dmel_discriminator : TrainHandle {
   DLayer layer[kDiscLayers];
-  struct GradSlot { std::string key; int64_t offset, numel; };
-  std::vector<GradSlot> slots;
-  int64_t grad_floats = 0;
-  int64_t slot_of(const std::string& key) const {
-    for (const auto& sl : slots)
-      if (sl.key == key) return sl.offset;
-    return -1;
-  }
 };
 
 extern "C" int dmel_discriminator_create(dmel_discriminator** out) {
@@ -1890,56 +1840,40 @@ extern "C" int dmel_discriminator_create(dmel_discriminator** out) {
 }
 extern "C" void dmel_discriminator_destroy(dmel_discriminator* d) { delete d; }
 extern "C" int dmel_discriminator_set_tensor(dmel_discriminator* d, const char* key, const float* data, const int64_t* shape, int ndim) {
-  DMEL_CHECK_ARG(d, "NULL handle");
-  d->ready = false;
-  return d->ts.set(key, data, shape, ndim);
+  return train_set_tensor(d, key, data, shape, ndim);
 }
 
-static int disc_pack_forward(DLayer& l, const std::vector<float>& bias) {
-  const int Cin = l.Cin, kw = l.kw;
-  const std::vector<float>& w = l.w;
-  for (int dh = 0; dh < 3; ++dh) {
-    PackDesc d;
-    d.mode = EPI_LINEAR; d.C = l.Cout;
-    auto W = [&, dh](int row, int ci, int dw) { return w[(((size_t)row * Cin + ci) * 3 + dh) * kw + dw]; };
-    auto B = [&, dh](int row) { return dh == 1 ? bias[row] : 0.f; };     // the bias rides the centre row's launch
-    if (l.sw == 1) {
-      d.nseg = 1;
-      d.seg[0].Cin = Cin; d.seg[0].taps = kw; d.seg[0].dil = 1; d.seg[0].pad_left = l.pw;
-      DMEL_TRY(pack_conv(l.fwd[dh], d, [&](int, int row, int ci, int tap) { return W(row, ci, tap); }, B));
-    } else {
-      d.nseg = 2;                                                       // even taps on x[2w' + ...], odd taps on x[2w' + 1 + ...]
-      for (int sg = 0; sg < 2; ++sg) {
-        d.seg[sg].Cin = Cin; d.seg[sg].taps = (kw + 1 - sg) / 2; d.seg[sg].dil = 1; d.seg[sg].tstride = 2; d.seg[sg].toff = sg;
-        d.seg[sg].pad_left = l.pw;
-      }
-      DMEL_TRY(pack_conv(l.fwd[dh], d, [&](int sg, int row, int ci, int tap) { return W(row, ci, 2 * tap + sg); }, B));
-    }
-  }
-  return DMEL_OK;
-}
-
-// backward-data images.  y[n] (+)= W_dh * x[n + dh - 1]  =>  d x[m] (+)= W_dh^T * d y[m - dh + 1]:
+// The images of layer `p` over its folded weight W (Cout, Cin, 3, kw), one set per kernel row dh (the view's offset picks the row).
+// Forward: value(row = co, ci, tap) = W[co][ci][dh][sw * tap + sg]; stride 2 is two segments, even taps on x[2w' + ...], odd taps on
+// x[2w' + 1 + ...]; the bias rides the centre row's launch.
+// Backward-data.  y[n] (+)= W_dh * x[n + dh - 1]  =>  d x[m] (+)= W_dh^T * d y[m - dh + 1]:
 //   stride 1: the same convolution with the taps reversed (kw = 2 pw + 1, so the padding is unchanged);
 //   stride 2: output phase ph of d x takes the taps dw = ph (mod 2): d x[2q + ph] = sum_t W[.., 8 - 2t - ph] d y[q + t - (2 - ph)].
-static int disc_pack_backward(DLayer& l) {
-  const int Cin = l.Cin, kw = l.kw;
-  const std::vector<float>& w = l.w;
+static int disc_pack_layer(DLayer& l, const std::string& p, const TensorStore& ts, const float* w, bool train) {
+  const int Cin = l.Cin, kw = l.kw, nseg = l.sw == 1 ? 1 : 2;
+  const int64_t inner = (int64_t)Cin * 3 * kw;
   for (int dh = 0; dh < 3; ++dh) {
-    auto W = [&, dh](int co, int ci, int dw) { return w[(((size_t)co * Cin + ci) * 3 + dh) * kw + dw]; };
-    if (l.sw == 1) {
-      PackDesc d;
-      d.mode = EPI_LINEAR; d.C = Cin; d.nseg = 1;
-      d.seg[0].Cin = l.Cout; d.seg[0].taps = kw; d.seg[0].dil = 1; d.seg[0].pad_left = l.pw;
-      DMEL_TRY(pack_conv(l.bwd[dh][0], d, [&](int, int row, int cc, int tap) { return W(cc, row, kw - 1 - tap); }, [&](int) { return 0.f; }));
-    } else {
-      for (int ph = 0; ph < 2; ++ph) {
-        PackDesc d;
-        d.mode = EPI_LINEAR; d.C = Cin; d.nseg = 1;
-        d.seg[0].Cin = l.Cout; d.seg[0].taps = 5 - ph; d.seg[0].dil = 1; d.seg[0].pad_left = 2 - ph;
-        DMEL_TRY(pack_conv(l.bwd[dh][ph], d, [&](int, int row, int cc, int tap) { return W(cc, row, 8 - 2 * tap - ph); },
-                           [&](int) { return 0.f; }));
-      }
+    PackDesc d;
+    d.mode = EPI_LINEAR; d.C = l.Cout; d.nseg = nseg;
+    ImageSrc src;
+    for (int sg = 0; sg < nseg; ++sg) {
+      d.seg[sg].Cin = Cin; d.seg[sg].taps = (kw + l.sw - 1 - sg) / l.sw; d.seg[sg].dil = 1; d.seg[sg].tstride = l.sw; d.seg[sg].toff = sg;
+      d.seg[sg].pad_left = l.pw;
+      ImageSeg& v = src.seg[sg];
+      v.key = kFoldedWeight; v.off = dh * kw + sg; v.rs = inner; v.cs = 3 * kw; v.ts = l.sw;
+    }
+    if (dh == 1) src.b0 = p + "bias";
+    DMEL_TRY(pack_image(l.fwd[dh], d, src, ts, w));
+    for (int ph = 0; train && ph < nseg; ++ph) {
+      PackDesc e;
+      e.mode = EPI_LINEAR; e.C = Cin; e.nseg = 1;
+      e.seg[0].Cin = l.Cout; e.seg[0].dil = 1;
+      ImageSrc t;
+      ImageSeg& v = t.seg[0];
+      v.key = kFoldedWeight; v.rs = 3 * kw; v.cs = inner;
+      if (l.sw == 1) { e.seg[0].taps = kw; e.seg[0].pad_left = l.pw; v.off = dh * kw; v.ts = 1; v.rev = 1; }
+      else { e.seg[0].taps = 5 - ph; e.seg[0].pad_left = 2 - ph; v.off = dh * kw + 8 - ph; v.ts = -2; }
+      DMEL_TRY(pack_image(l.bwd[dh][ph], e, t, ts, w));
     }
   }
   return DMEL_OK;
@@ -1947,53 +1881,34 @@ static int disc_pack_backward(DLayer& l) {
 
 extern "C" int dmel_discriminator_finalize(dmel_discriminator* d) {
   DMEL_CHECK_ARG(d, "NULL handle");
+  d->ready = d->train_ready = false;      // until every image is packed: a finalize that fails leaves a handle that refuses to run
+  d->clear_slots();
+  std::vector<float> w;                   // folded weight (Cout, Cin, 3, kw)
   for (int i = 0; i < kDiscLayers; ++i) {
     DLayer& l = d->layer[i];
     const std::string p = "blocks." + std::to_string(2 * i) + ".";
-    if (!d->ts.conv_weight(p, {l.Cout, l.Cin, 3, l.kw}, l.w)) return DMEL_EMISSING;
-    const HostTensor* b = d->ts.need(p + "bias", {l.Cout});
-    if (!b) return DMEL_EMISSING;
-    DMEL_TRY(disc_pack_forward(l, b->v));
+    if (!d->ts.conv_weight(p, {l.Cout, l.Cin, 3, l.kw}, w)) return DMEL_EMISSING;
+    if (!d->ts.need(p + "bias", {l.Cout})) return DMEL_EMISSING;
     if (d->train) {
       const HostTensor* g0 = d->ts.need(p + "parametrizations.weight.original0", {l.Cout, 1, 1, 1});
       const HostTensor* v0 = d->ts.need(p + "parametrizations.weight.original1", {l.Cout, l.Cin, 3, l.kw});
       if (!g0 || !v0) { set_error("discriminator training needs the weight-normed form (parametrizations.weight.original0|1) of '%s'", p.c_str()); return DMEL_EMISSING; }
       DMEL_TRY(upload_vec(l.g_dev, g0->v));
       DMEL_TRY(upload_vec(l.v_dev, v0->v));
-      DMEL_TRY(disc_pack_backward(l));
+      d->add(p + "bias", l.Cout);
+      d->add(p + "parametrizations.weight.original0", l.Cout);
+      d->add(p + "parametrizations.weight.original1", (int64_t)l.Cout * l.Cin * 3 * l.kw);
     }
+    DMEL_TRY(disc_pack_layer(l, p, d->ts, w.data(), d->train));
   }
-  if (d->train) {
-    d->slots.clear();
-    int64_t off = 0;
-    for (int i = 0; i < kDiscLayers; ++i) {
-      const DLayer& l = d->layer[i];
-      const std::string p = "blocks." + std::to_string(2 * i) + ".";
-      d->slots.push_back({p + "bias", off, l.Cout}); off += l.Cout;
-      d->slots.push_back({p + "parametrizations.weight.original0", off, l.Cout}); off += l.Cout;
-      const int64_t nw = (int64_t)l.Cout * l.Cin * 3 * l.kw;
-      d->slots.push_back({p + "parametrizations.weight.original1", off, nw}); off += nw;
-    }
-    d->grad_floats = off;
-    d->train_ready = true;
-  }
+  d->train_ready = d->train;
   d->ts.t.clear();
   d->ready = true;
   return DMEL_OK;
 }
 
-extern "C" int dmel_discriminator_set_train_precision(dmel_discriminator* d, int precision) {
-  DMEL_CHECK_ARG(d && (precision == DMEL_PRECISION_FP32 || precision == DMEL_PRECISION_BF16), "discriminator_set_train_precision: DMEL_PRECISION_FP32 or DMEL_PRECISION_BF16");
-  d->train_precision = precision;
-  return DMEL_OK;
-}
-extern "C" int dmel_discriminator_enable_training(dmel_discriminator* d, int on) {
-  DMEL_CHECK_ARG(d, "NULL handle");
-  d->train = on != 0;
-  d->ready = false;
-  d->train_ready = false;
-  return DMEL_OK;
-}
+extern "C" int dmel_discriminator_set_train_precision(dmel_discriminator* d, int precision) { return train_set_precision(d, "discriminator", precision); }
+extern "C" int dmel_discriminator_enable_training(dmel_discriminator* d, int on) { return train_enable(d, on); }
 
 namespace {
 // Flattened image layout.  An activation (B, C, H, W) is stored as B items of C rows of (H + 2) * P floats: image row h sits at
@@ -2229,22 +2144,15 @@ extern "C" int dmel_discriminator_refresh(dmel_discriminator* d, int n, const ch
                                           void* stream) {
   DMEL_CHECK_ARG(d && keys && device_tensors && n > 0, "discriminator_refresh: bad argument");
   if (!d->ready) { set_error("discriminator_refresh: handle not finalized"); return DMEL_EMISSING; }
-  std::map<std::string, const float*> dev;
-  for (int i = 0; i < n; ++i) {
-    DMEL_CHECK_ARG(keys[i] && device_tensors[i], "discriminator_refresh: NULL entry %d", i);
-    dev[keys[i]] = device_tensors[i];
-  }
+  Refresh r("discriminator_refresh", stream);
+  DMEL_TRY(r.open(n, keys, device_tensors));
   // every key is resolved before the first launch: a refused refresh leaves the handle as it was
-  const float *bias[kDiscLayers], *wg[kDiscLayers], *wv[kDiscLayers];
+  const float *wg[kDiscLayers], *wv[kDiscLayers];
   for (int i = 0; i < kDiscLayers; ++i) {
     const std::string p = "blocks." + std::to_string(2 * i) + ".";
-    const std::pair<const char*, const float**> want[3] = {
-        {"bias", &bias[i]}, {"parametrizations.weight.original0", &wg[i]}, {"parametrizations.weight.original1", &wv[i]}};
-    for (const auto& kv : want) {
-      auto it = dev.find(p + kv.first);
-      if (it == dev.end()) { set_error("discriminator_refresh: tensor '%s%s' was not provided", p.c_str(), kv.first); return DMEL_EMISSING; }
-      *kv.second = it->second;
-    }
+    if (!r.find(p + "bias")) return DMEL_EMISSING;
+    DMEL_TRY(r.need(p + "parametrizations.weight.original0", &wg[i]));
+    DMEL_TRY(r.need(p + "parametrizations.weight.original1", &wv[i]));
   }
   hipStream_t st = (hipStream_t)stream;
   DevBuf& fold = *thread_scratch(2, st);
@@ -2256,38 +2164,20 @@ extern "C" int dmel_discriminator_refresh(dmel_discriminator* d, int n, const ch
   }
   for (int i = 0; i < kDiscLayers; ++i) {
     DLayer& l = d->layer[i];
-    const float *b = bias[i], *g = wg[i], *v = wv[i];
+    const std::string p = "blocks." + std::to_string(2 * i) + ".";
     const int64_t inner = (int64_t)l.Cin * 3 * l.kw;
     float* w = fold.as<float>();
-    hipLaunchKernelGGL(weight_norm_fwd_kernel, dim3((unsigned)l.Cout), dim3(256), 0, st, v, g, w, inner);
+    hipLaunchKernelGGL(weight_norm_fwd_kernel, dim3((unsigned)l.Cout), dim3(256), 0, st, wv[i], wg[i], w, inner);
     DMEL_HIP(hipGetLastError());
     if (l.g_dev.p) {
-      DMEL_HIP(hipMemcpyAsync(l.g_dev.p, g, (size_t)l.Cout * sizeof(float), hipMemcpyDeviceToDevice, st));
-      DMEL_HIP(hipMemcpyAsync(l.v_dev.p, v, (size_t)l.Cout * inner * sizeof(float), hipMemcpyDeviceToDevice, st));
+      DMEL_TRY(r.copy(l.g_dev.as<float>(), p + "parametrizations.weight.original0", (size_t)l.Cout));
+      DMEL_TRY(r.copy(l.v_dev.as<float>(), p + "parametrizations.weight.original1", (size_t)l.Cout * inner));
     }
-    RepackBatch batch(st);      // the 3-9 images of this layer in one launch
     for (int dh = 0; dh < 3; ++dh) {
-      {
-        RepackSrc src;
-        const int nseg = l.sw == 1 ? 1 : 2;
-        for (int sg = 0; sg < nseg; ++sg) {           // value(row = co, ci, tap) = W[co][ci][dh][sw * tap + sg]
-          src.seg[sg].w = w + dh * l.kw + sg; src.seg[sg].rs = inner; src.seg[sg].cs = 3 * l.kw; src.seg[sg].ts = l.sw;
-        }
-        src.b0 = dh == 1 ? b : nullptr;
-        DMEL_TRY(launch_repack(l.fwd[dh], src, st));
-      }
-      if (d->train_ready) {
-        const int nph = l.sw == 1 ? 1 : 2;
-        for (int ph = 0; ph < nph; ++ph) {             // value(row = ci, cc = co, tap) = W[co][ci][dh][kw-1-tap | 8 - 2 tap - ph]
-          RepackSrc src;
-          src.seg[0].rs = 3 * l.kw; src.seg[0].cs = inner;
-          if (l.sw == 1) { src.seg[0].w = w + dh * l.kw; src.seg[0].ts = 1; src.seg[0].rev = 1; }
-          else { src.seg[0].w = w + dh * l.kw + 8 - ph; src.seg[0].ts = -2; }
-          DMEL_TRY(launch_repack(l.bwd[dh][ph], src, st));
-        }
-      }
+      DMEL_TRY(r.add(l.fwd[dh], w));
+      for (int ph = 0; d->train_ready && ph < (l.sw == 1 ? 1 : 2); ++ph) DMEL_TRY(r.add(l.bwd[dh][ph], w));
     }
-    DMEL_TRY(batch.flush());
+    DMEL_TRY(r.run());      // the 3-9 images of this layer in one launch
     // the folded weight buffer is reused by the next layer: the launches above are ordered on the same stream
   }
   return DMEL_OK;
@@ -2297,14 +2187,9 @@ extern "C" size_t dmel_discriminator_train_workspace_bytes(const dmel_discrimina
   if (!d || B <= 0 || H <= 0 || W <= 0) return 0;
   return disc_train_plan(d, B, H, W, nullptr).bytes;
 }
-extern "C" int64_t dmel_discriminator_grad_floats(const dmel_discriminator* d) { return d && d->train_ready ? d->grad_floats : 0; }
+extern "C" int64_t dmel_discriminator_grad_floats(const dmel_discriminator* d) { return train_grad_floats(d); }
 extern "C" int dmel_discriminator_grad_slot(const dmel_discriminator* d, const char* key, int64_t* offset, int64_t* numel) {
-  DMEL_CHECK_ARG(d && key && offset && numel, "discriminator_grad_slot: NULL argument");
-  if (!d->train_ready) { set_error("discriminator_grad_slot: training was not enabled before finalize"); return DMEL_EMISSING; }
-  for (const auto& sl : d->slots)
-    if (sl.key == key) { *offset = sl.offset; *numel = sl.numel; return DMEL_OK; }
-  set_error("discriminator_grad_slot: '%s' is not a parameter of the discriminator", key);
-  return DMEL_EINVAL;
+  return train_grad_slot(d, "discriminator", "a parameter of the discriminator", key, offset, numel);
 }
 
 extern "C" int dmel_discriminator_forward_train(const dmel_discriminator* d, const float* x, float* y, int B, int H, int64_t W,
@@ -2353,7 +2238,7 @@ extern "C" int dmel_discriminator_backward(const dmel_discriminator* d, const fl
     }
     // bias and weight gradients: one launch per kernel row, the kw horizontal taps on the grid.  The fp16-split kernels that read g (the
     // weight gradients and, below, backward-data) scale it by its max, found once per layer.
-    DMEL_TRY(launch_conv_bgrad(g, grads + d->slot_of(pk + "bias"), l.Cout, B, Tout, st));
+    DMEL_TRY(launch_conv_bgrad(g, grads + d->offset_of(pk + "bias"), l.Cout, B, Tout, st));
     DMEL_HIP(hipMemsetAsync(t.dwfold, 0, (size_t)l.Cout * l.Cin * 3 * l.kw * sizeof(float), st));
     const uint32_t* g_absmax = nullptr;
     DMEL_TRY(launch_absmax(g, (int64_t)B * l.Cout * Tout, st, &g_absmax));
@@ -2361,8 +2246,8 @@ extern "C" int dmel_discriminator_backward(const dmel_discriminator* d, const fl
       DMEL_TRY(launch_conv_wgrad_strided(g, p.act[i] + (int64_t)(dh - 1) * p.P[i], t.dwfold, l.Cout, l.Cin, l.sw, -l.pw, Tout, Tin, 3 * l.kw,
                                          dh * l.kw, B, st, l.kw, g_absmax));
     hipLaunchKernelGGL(weight_norm_bwd_kernel, dim3((unsigned)l.Cout), dim3(256), 0, st, t.dwfold, l.v_dev.as<float>(), l.g_dev.as<float>(),
-                       grads + d->slot_of(pk + "parametrizations.weight.original0"),
-                       grads + d->slot_of(pk + "parametrizations.weight.original1"), (int64_t)l.Cin * 3 * l.kw);
+                       grads + d->offset_of(pk + "parametrizations.weight.original0"),
+                       grads + d->offset_of(pk + "parametrizations.weight.original1"), (int64_t)l.Cin * 3 * l.kw);
     DMEL_HIP(hipGetLastError());
     if (i == 0 && !dx) break;
     // backward-data into the other buffer (B, Cin, Hp * P[i])

@@ -1,5 +1,12 @@
-"""The device-side weight re-pack (dmel_*_refresh: repack_kernel / repack_unit in csrc/train_ops.hip, the per-module recipes in
-csrc/modules.hip, weight_norm_fwd_kernel) held to the host packer (pack_conv, csrc/conv.h), image by image.
+"""The device-side weight re-pack (dmel_*_refresh: repack_kernel / repack_unit in csrc/train_ops.hip, weight_norm_fwd_kernel in
+csrc/modules.hip) held to the host packer (pack_conv, csrc/conv.h), image by image.
+
+Every trainable image is described ONCE, next to the image itself (WeightImage::src in csrc/modules.hip, filled in by the finalize
+code of each module): affine views over named tensors.  Routes A and B below share that
+description and differ in the EVALUATOR: the host accessor view_weight / view_bias under pack_conv against repack_unit on the device,
+each with its own copy of the addressing and of the four roundings.  That is what this module proves: the two evaluators agree bit for
+bit.  That the descriptions themselves are right is held by the float64 comparisons here and in test_gpu_parity.py, and by the recorded
+image fingerprints of tests/test_host_asan.py.
 
 From the second optimiser step on, every convolution of a training run reads images written by that kernel.  Each case here
 reaches the same parameter values W2 by two routes:
@@ -128,6 +135,8 @@ WAVENETS = {
     "decoder": (dict(input_channels=48, output_channels=20, residual_channels=48, residual_layers=4, dilation_cycle=4,
                      condition_channels=48), 3, 61),
     "no projections": (dict(residual_channels=64, residual_layers=3, dilation_cycle=2), 2, 130),
+    # the gate's SECOND segment ends in a partial K step: 24 condition channels, no multiple of 16
+    "ragged condition": (dict(input_channels=10, residual_channels=48, residual_layers=2, dilation_cycle=2, condition_channels=24), 2, 40),
     "real decoder widths": (dict(input_channels=560, output_channels=80, residual_channels=560, residual_layers=2, dilation_cycle=4,
                                  condition_channels=560), 2, 92),
 }
@@ -296,10 +305,10 @@ def test_refresh_at_the_edges_of_the_three_roundings(dev):
 
 
 # ==================================================================================================== quantiser
-def make_quantizer(levels, prebound, G, seed, dev):
+def make_quantizer(levels, prebound, G, seed, dev, Cg=70):
     from dmel_codec_amd.models.modules.dowmsample_fsq import DownsampleFiniteScalarQuantize
     torch.manual_seed(seed)
-    q = DownsampleFiniteScalarQuantize(input_dim=70 * G, n_codebooks=1, n_groups=G, levels=levels, downsample_factor=[2, 2], is_dmel=True,
+    q = DownsampleFiniteScalarQuantize(input_dim=Cg * G, n_codebooks=1, n_groups=G, levels=levels, downsample_factor=[2, 2], is_dmel=True,
                                        fsq_prebound=prebound)
     with torch.no_grad():
         redraw_quantizer(q, seed)
@@ -341,9 +350,25 @@ def test_quantizer_refresh_equals_rebuild(dev, levels, prebound, G, T, B):
     """dmel_quantizer_refresh: the two-segment `down`, the phase-major `up` with one bias per channel shared by the phases (bias_mod), the
     ConvNeXt pointwise pairs and their transposes pw1T / pw2T, down_dx (phase-major) and up_dx (two segments), and the parameter buffers
     that are plain copies (depthwise, LayerNorm, gamma, FSQ projections)."""
-    Cg, seed = 70, 300 + 10 * G + len(levels) + T
-    a, a2 = make_quantizer(levels, prebound, G, seed + 2, dev), make_quantizer(levels, prebound, G, seed + 2, dev)
-    b = make_quantizer(levels, prebound, G, seed + 1, dev)
+    quantizer_refresh_case(dev, levels, prebound, G, T, B, 70)
+
+
+# dmel_quantizer_create accepts any channel count per group (it only asks input_dim % n_groups == 0), but with ONE channel the ConvNeXt
+# LayerNorm is degenerate: the normalised value is identically 0, every gradient through it is exactly 0 in float64, and the relative
+# bars below divide by that 0 (measured on the commit before the descriptions were unified: it fails there too, for that reason alone).
+# Cg = 3 is the smallest odd count with a LayerNorm that normalises something, and no multiple of 16: the phase-major `up` / `down_dx`
+# images hold 2 x 3 real rows in 2 x 32 packed ones.  T = 5: the two stride-2 stages admit 4 at the least, plus one (the trailing column
+# is dropped on the way down and zero-padded on the way up).
+@pytest.mark.parametrize("Cg", [3])
+def test_quantizer_refresh_equals_rebuild_odd_group_width(dev, Cg):
+    """The phase-major view (ps / pC, bias_mod) with padded rows at the smallest shapes: one item, five frames."""
+    quantizer_refresh_case(dev, [7, 5, 5], True, 2, 5, 1, Cg)
+
+
+def quantizer_refresh_case(dev, levels, prebound, G, T, B, Cg):
+    seed = 300 + 10 * G + len(levels) + T
+    a, a2 = make_quantizer(levels, prebound, G, seed + 2, dev, Cg), make_quantizer(levels, prebound, G, seed + 2, dev, Cg)
+    b = make_quantizer(levels, prebound, G, seed + 1, dev, Cg)
     state = refresh_to(b, lambda q: redraw_quantizer(q, seed + 2))
     assert all(torch.equal(p, q) for p, q in zip(a.parameters(), b.parameters()))
     # as in test_quantizer_training_forward_backward: an input that keeps a 1e-4 margin to every quantisation boundary in the float64
@@ -377,7 +402,7 @@ def test_quantizer_refresh_equals_rebuild(dev, levels, prebound, G, T, B):
         f.below(f"{route}: dz vs float64", rel_err(out["dz [train fp32]"], z64.grad), 1e-4)
         for k, _ in a.named_parameters():
             f.below(f"{route}: d {k} [train fp32] vs float64", rel_err(pg[f"d {k} [train fp32]"], sd64[k].grad), 2e-4)
-    report(f"[repack] quantizer levels {levels} G {G}: {len(out_a)} outputs / input gradients bit-equal between refresh and rebuild; "
+    report(f"[repack] quantizer levels {levels} G {G} Cg {Cg}: {len(out_a)} outputs / input gradients bit-equal between refresh and rebuild; "
            f"{loose} of {len(pg_a)} parameter gradients differ between two rebuilds (atomics)")
     f.done()
 
@@ -633,3 +658,35 @@ def test_refused_discriminator_refresh_leaves_the_handle_unchanged(dev):
     scale = ref_cpu.discriminator_forward({k: v.double().abs() for k, v in w2.items()}, "", x.double().abs())
     assert_close_to_truth(y2, ref_cpu.discriminator_forward(w2, "", x), y64, "discriminator logits after a refused, then a complete refresh")
     assert per_element(y2, forward(target), scale) < DISC_TAU
+
+
+# ==================================================================================================== launch counts
+def kernel_launches(fn):
+    """Names of the device kernels launched while fn runs (the library keeps no profile record for the re-pack: the profiler's trace)."""
+    from torch.profiler import ProfilerActivity, profile
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    return [e.name for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA]
+
+
+def test_refresh_launch_counts(dev):
+    """One refresh is ONE repack launch for a WaveNet, one (next to its plain copies) for the quantiser, and one weight-norm fold launch
+    plus one repack launch for each of the discriminator's six layers."""
+    m = make_wavenet(WAVENETS["decoder"][0], 81, dev)
+    q = make_quantizer([7, 5, 5], True, 2, 82, dev)
+    d = make_discriminator(ref_cpu.seeded_discriminator_sd(83), dev)
+    w2 = discriminator_sd(84)
+    counts = {}
+    for name, mod, redraw in (("wavenet", m, lambda mm: randomise(mm, 91)), ("quantizer", q, lambda qq: redraw_quantizer(qq, 92)),
+                              ("discriminator", d, lambda dd: load_in_place(dd, w2))):
+        refresh_to(mod, redraw)                      # the first refresh uploads the job tables; the counted one finds them cached
+        with torch.no_grad():
+            redraw(mod)
+        h, gen = mod._handle, mod._generation
+        names = kernel_launches(lambda: build_handle(mod))
+        assert (mod._handle, mod._generation) == (h, gen + 1)
+        counts[name] = (sum("repack_kernel" in k for k in names), sum("weight_norm_fwd_kernel" in k for k in names))
+        report(f"[repack] {name}: one refresh launched {counts[name][0]} repack and {counts[name][1]} fold kernels ({len(names)} device kernels in all)")
+    assert counts == {"wavenet": (1, 0), "quantizer": (1, 0), "discriminator": (6, 6)}, counts

@@ -2,6 +2,10 @@
 // set_tensor for every state-dict key -> finalize (weight-norm folding, re-tiling into MFMA fragment order, three weight images,
 // transposed / training images, mel and chunk tables) -> workspace planning -> forward / training entry points (argument checks, tile
 // selection, launch assembly; the kernels themselves do not run).  Exits non-zero on any error return; ASan aborts on any bad access.
+// After every module handle's finalize it prints one "uploads <label>: ..." line, the sorted (bytes, FNV-1a) pairs of everything the
+// handle uploaded between create and the return of finalize (fake_hip.cpp): tests/test_host_asan.py holds them to a recorded fixture,
+// so no byte of a packed weight image moves unnoticed.  Only the handles built under `Fingerprinted` print (the small ones: the line of
+// a 20-layer WaveNet is 20 KB).  New handles go at the END of main: the weights are draws of one generator.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -10,6 +14,18 @@
 #include <vector>
 
 #include "../../include/dmel_hip.h"
+
+extern "C" void fake_hip_record_uploads(void);
+extern "C" void fake_hip_print_uploads(const char* label);
+static bool g_fingerprint = false;
+struct Fingerprinted { Fingerprinted() { g_fingerprint = true; } ~Fingerprinted() { g_fingerprint = false; } };
+static void record_uploads() { if (g_fingerprint) fake_hip_record_uploads(); }
+static void print_uploads(const std::string& l) { if (g_fingerprint) fake_hip_print_uploads(l.c_str()); }
+static std::string label(const char* name, std::initializer_list<int> v) {
+  std::string s = name;
+  for (int x : v) s += "_" + std::to_string(x);
+  return s;
+}
 
 static std::mt19937 rng(7);
 static int failures = 0;
@@ -31,6 +47,7 @@ static std::vector<float> buf(size_t n) { return std::vector<float>(n + 64, 0.25
 
 static void wavenet(int Cin, int Cout, int C, int L, int cycle, int Cc, int N, int T, bool train) {
   dmel_wavenet* m = nullptr;
+  record_uploads();
   CK(dmel_wavenet_create(&m, Cin, Cout, C, L, cycle, Cc));
   if (train) CK(dmel_wavenet_enable_training(m, 1));
   auto S = [&](const std::string& k, std::vector<int64_t> s) { set(m, dmel_wavenet_set_tensor, k, s); };
@@ -44,6 +61,7 @@ static void wavenet(int Cin, int Cout, int C, int L, int cycle, int Cc, int N, i
   S("skip_projection.conv.weight", {C, C, 1}); S("skip_projection.conv.bias", {C});
   if (Cout != C) { S("output_projection.conv.weight", {Cout, C, 1}); S("output_projection.conv.bias", {Cout}); }
   CK(dmel_wavenet_finalize(m));
+  print_uploads(label("wavenet", {Cin, Cout, C, L, cycle, Cc, (int)train}));
   auto x = buf((size_t)N * Cin * T), c = buf((size_t)N * (Cc ? Cc : 1) * T), y = buf((size_t)N * Cout * T);
   std::vector<int64_t> lens(N, T - 1);
   std::vector<char> ws(dmel_wavenet_workspace_bytes(m, N, T) + 256);
@@ -189,6 +207,7 @@ static void convnext_keys(const std::string& p, int C, const std::function<void(
 static void quantizer(int G, int C, std::vector<int> levels, int B, int T) {
   dmel_quantizer* q = nullptr;
   int f[2] = {2, 2};
+  record_uploads();
   CK(dmel_quantizer_create(&q, G * C, G, levels.data(), (int)levels.size(), f, 2, 1));
   CK(dmel_quantizer_enable_training(q, 1));
   std::function<void(const std::string&, std::vector<int64_t>)> S = [&](const std::string& k, std::vector<int64_t> s) { set(q, dmel_quantizer_set_tensor, k, s); };
@@ -204,6 +223,7 @@ static void quantizer(int G, int C, std::vector<int> levels, int B, int T) {
     S(p + "project_in.weight", {D, C}); S(p + "project_in.bias", {D}); S(p + "project_out.weight", {C, D}); S(p + "project_out.bias", {C});
   }
   CK(dmel_quantizer_finalize(q));
+  print_uploads(label("quantizer", {G, C, (int)levels.size()}));
   const int T4 = T / 4;
   auto z = buf((size_t)B * G * C * T), zq = buf((size_t)B * G * C * T), pre = buf((size_t)G * B * T4 * D), lat = buf((size_t)B * G * C * T4);
   std::vector<int32_t> ids((size_t)B * G * T4 + 16, 3);
@@ -220,6 +240,7 @@ static void quantizer(int G, int C, std::vector<int> levels, int B, int T) {
 
 static void discriminator(int B, int H, int W) {
   dmel_discriminator* d = nullptr;
+  record_uploads();
   CK(dmel_discriminator_create(&d));
   CK(dmel_discriminator_enable_training(d, 1));
   const int cin[6] = {1, 64, 128, 256, 512, 1024}, cout[6] = {64, 128, 256, 512, 1024, 1}, kw[6] = {9, 9, 9, 9, 3, 3};
@@ -230,6 +251,7 @@ static void discriminator(int B, int H, int W) {
     set(d, dmel_discriminator_set_tensor, p + "parametrizations.weight.original1", {cout[i], cin[i], 3, kw[i]});
   }
   CK(dmel_discriminator_finalize(d));
+  print_uploads("discriminator");
   const int64_t Wo = dmel_discriminator_out_frames(d, W);
   auto x = buf((size_t)B * H * W), y = buf((size_t)B * H * Wo), dx = buf((size_t)B * H * W);
   std::vector<char> ws(dmel_discriminator_workspace_bytes(d, B, H, W) + 256), tw(dmel_discriminator_train_workspace_bytes(d, B, H, W) + 256);
@@ -249,6 +271,7 @@ static void bigvgan(int n_up, const int* rates, const int* ks, int C0, int mels,
   for (int j = 0; j < 3; ++j) { c.resblock_kernel_sizes[j] = rk[j]; for (int l = 0; l < 3; ++l) c.resblock_dilations[j][l] = rd[l]; }
   c.snake_logscale = 1; c.use_tanh_at_final = 1; c.use_bias_at_final = 1; c.resblock_type = resblock;
   dmel_bigvgan* m = nullptr;
+  record_uploads();
   CK(dmel_bigvgan_create(&m, &c));
   auto W = [&](const std::string& p, std::vector<int64_t> shape, bool bias) {
     if (weight_norm) {
@@ -285,6 +308,7 @@ static void bigvgan(int n_up, const int* rates, const int* ks, int C0, int mels,
   W("conv_post.", {1, ch, 7}, true);
   (void)A;
   CK(dmel_bigvgan_finalize(m));
+  print_uploads(label("bigvgan", {n_up, C0, mels, resblock, (int)weight_norm}));
   int up = 1;
   for (int i = 0; i < n_up; ++i) up *= rates[i];
   auto mel = buf((size_t)B * mels * T), y = buf((size_t)B * T * up);
@@ -321,14 +345,16 @@ int main() {
   wavenet(560, 80, 560, 4, 4, 560, 3, 92, true);        // decoder (conditioned, output projection, XCD-chunked grids, streaming)
   wavenet(64, 64, 64, 5, 0, 64, 2, 40, false);
   quantizer(8, 70, {7, 5, 5}, 3, 93);
-  quantizer(2, 70, {8, 6}, 2, 47);
+  { Fingerprinted fp; quantizer(2, 70, {8, 6}, 2, 47); }
   {
     dmel_convnext* cx = nullptr;
+    record_uploads();
     CK(dmel_convnext_create(&cx, 70));
     CK(dmel_convnext_enable_training(cx, 1));
     std::function<void(const std::string&, std::vector<int64_t>)> S = [&](const std::string& k, std::vector<int64_t> s) { set(cx, dmel_convnext_set_tensor, k, s); };
     convnext_keys("", 70, S);
     CK(dmel_convnext_finalize(cx));
+    print_uploads("convnext_70");
     const int N = 6, T = 46;
     auto x = buf((size_t)N * 70 * T), y = buf((size_t)N * 70 * T), g = buf((size_t)dmel_convnext_grad_floats(cx));
     std::vector<char> ws(dmel_convnext_workspace_bytes(cx, N, T) + 256), tw(dmel_convnext_train_workspace_bytes(cx, N, T) + 256);
@@ -338,9 +364,9 @@ int main() {
     dmel_convnext_destroy(cx);
   }
   discriminator(2, 80, 93);
-  discriminator(1, 16, 60);
+  { Fingerprinted fp; discriminator(1, 16, 60); }
   { const int r[4] = {8, 8, 2, 2}, k[4] = {16, 16, 4, 4}; bigvgan(4, r, k, 512, 80, 1, true, 2, 12); }
-  { const int r[2] = {4, 2}, k[2] = {8, 4}; bigvgan(2, r, k, 32, 20, 2, false, 2, 9); }
+  { Fingerprinted fp; const int r[2] = {4, 2}, k[2] = {8, 4}; bigvgan(2, r, k, 32, 20, 2, false, 2, 9); }
   { const int r[6] = {4, 4, 2, 2, 2, 2}, k[6] = {8, 8, 4, 4, 4, 4}; bigvgan(6, r, k, 96, 100, 1, true, 1, 3); }
   {   // standalone transposed convolution / output convolution
     for (int stride : {2, 8}) {
@@ -525,6 +551,10 @@ int main() {
     CK(dmel_aa_snake_f32(xs.data(), ys.data(), al.data(), be.data(), taps.data(), taps.data(), 1, 2, 8, 3000, nullptr));
     CK(dmel_aa_snake_backward_f32(xs.data(), ys.data(), xs.data(), al.data(), be.data(), da.data(), db.data(), taps.data(), taps.data(), 1, 2, 8, 3000, nullptr));
   }
+  // drawn last, so that the handles above keep their weights: narrow encoder-like and conditioned stacks with every training image
+  Fingerprinted fp;
+  wavenet(10, 70, 70, 5, 4, 0, 4, 17, true);
+  wavenet(48, 20, 48, 4, 4, 48, 2, 19, true);
   std::printf(failures ? "host ASan run: %d FAILURES\n" : "host ASan run: all entry points returned success, no sanitizer report\n", failures);
   return failures ? 1 : 0;
 }

@@ -5,13 +5,59 @@
 // pool; SURVEY.md section 5 asks for an ASan build of the CPU side.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <set>
+#include <utility>
+#include <vector>
+
+// Fingerprints of what a handle uploads (tests/golden/host_image_fingerprints.txt): while recording, every host -> device hipMemcpy
+// contributes (byte count, 64-bit FNV-1a of the bytes); fake_hip_print_uploads prints them SORTED on one line, so that the order of the
+// uploads is free to change while no byte of any image is.  A table of device addresses (every 8-byte word the start of a live
+// allocation) differs from run to run: it is printed as <bytes>:addresses.
+static bool g_record = false;
+static std::vector<std::pair<size_t, uint64_t>> g_uploads;
+static std::set<const void*> g_live;
+static uint64_t fingerprint(const void* s, size_t n) {
+  bool addresses = n >= 8 && n % 8 == 0;
+  for (size_t i = 0; addresses && i < n; i += 8) {
+    const void* p;
+    std::memcpy(&p, (const char*)s + i, 8);
+    addresses = g_live.count(p) != 0;
+  }
+  if (addresses) return 0;
+  uint64_t h = 0xcbf29ce484222325ull;
+  for (size_t i = 0; i < n; ++i) h = (h ^ ((const unsigned char*)s)[i]) * 0x100000001b3ull;
+  return h;
+}
+extern "C" void fake_hip_record_uploads(void) { g_uploads.clear(); g_record = true; }
+extern "C" void fake_hip_print_uploads(const char* label) {
+  std::sort(g_uploads.begin(), g_uploads.end());
+  std::printf("uploads %s:", label);
+  for (auto& u : g_uploads) {
+    if (u.second) std::printf(" %zu:%016llx", u.first, (unsigned long long)u.second);
+    else std::printf(" %zu:addresses", u.first);
+  }
+  std::printf("\n");
+  g_uploads.clear();
+  g_record = false;
+}
 
 extern "C" {
-hipError_t hipMalloc(void** p, size_t n) { *p = std::malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
-hipError_t hipFree(void* p) { std::free(p); return hipSuccess; }
-hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { std::memcpy(d, s, n); return hipSuccess; }
+hipError_t hipMalloc(void** p, size_t n) {
+  *p = std::malloc(n ? n : 1);
+  if (*p) g_live.insert(*p);
+  return *p ? hipSuccess : hipErrorOutOfMemory;
+}
+hipError_t hipFree(void* p) { g_live.erase(p); std::free(p); return hipSuccess; }
+hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind kind) {
+  if (g_record && kind == hipMemcpyHostToDevice) g_uploads.push_back({n, fingerprint(s, n)});
+  std::memcpy(d, s, n);
+  return hipSuccess;
+}
 hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { std::memmove(d, s, n); return hipSuccess; }
 hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { std::memset(d, v, n); return hipSuccess; }
 hipError_t hipMemcpy2DAsync(void* d, size_t dp, const void* s, size_t sp, size_t w, size_t h, hipMemcpyKind, hipStream_t) {
