@@ -1482,3 +1482,140 @@ extern "C" int dmel_stream_pack_items(const void* const* src, void* const* dst, 
   DMEL_HIP(hipGetLastError());
   return DMEL_OK;
 }
+
+namespace dmel {
+
+// ---- voice activity and end of turn on log-mel frames (include/dmel_hip.h: dmel_voice_items; the rule: utils/voice.py) ---------------
+// Row s of the table is (frames, threshold, min_level, fall, rise, rise_speech, band_lo, band_hi, min_bands, attack, release, 0), twelve
+// 4-byte words; workgroup s is ONE wave and owns slot s, lane l the bands l and l + 64, whose floors stay in registers from the first
+// frame of the launch to the last.  The slot's tile passes through LDS in chunks of kVoiceChunk frames: the wave reads 64 consecutive
+// frames of one band per instruction (256 contiguous bytes) and writes them as one row of pitch kVoiceChunk + 1 words, so that the
+// frame loop's column reads (lane l at word l * 65 + t) hit 32 different banks in each half of the wave.  The frame loop is
+// sequential: the coefficient of frame f depends on the state after frame f - 1.  The band count is two ballots; every lane then
+// runs the same state machine on the same integers, so nothing inside the frame loop waits for another lane.  Lane t keeps the two
+// output bytes of frame t of the chunk and stores them behind the loop: 64 consecutive bytes per row.  The floor update is three
+// separately rounded operations (fp contract(off) in voice_floor, as fade_blend above): what the fp32 host expression gives.  Plain
+// stores, no atomics.
+constexpr int kVoiceWords = 12, kVoiceChunk = 64, kVoiceMaxMels = 128, kVoicePitch = kVoiceChunk + 1;
+__device__ __forceinline__ float voice_floor(float fl, float L, bool first, float fall, float up, float min_level) {
+#pragma clang fp contract(off)
+  float v = L;
+  if (!first) {
+    const float c = L < fl ? fall : up;
+    const float d = L - fl;
+    const float p = c * d;
+    v = fl + p;
+  }
+  return v < min_level ? min_level : v;
+}
+__global__ __launch_bounds__(64) void voice_kernel(const float* __restrict__ mel, int64_t item_stride, int64_t band_stride, int n_mels,
+                                                   const uint32_t* __restrict__ tab, uint32_t* __restrict__ state,
+                                                   uint8_t* __restrict__ flags, uint8_t* __restrict__ counts, int64_t out_pitch) {
+  __shared__ float tile[kVoiceMaxMels * kVoicePitch];
+  const int s = blockIdx.x, lane = threadIdx.x;
+  const uint32_t* row = tab + (size_t)s * kVoiceWords;
+  const int n = (int)row[0];
+  if (n <= 0) return;                                   // idle (uniform: in front of the first barrier)
+  const float thr = __uint_as_float(row[1]), min_level = __uint_as_float(row[2]), fall = __uint_as_float(row[3]);
+  const float rise = __uint_as_float(row[4]), rise_speech = __uint_as_float(row[5]);
+  const int lo = (int)row[6], hi = (int)row[7], min_bands = (int)row[8], attack = (int)row[9], release = (int)row[10];
+  uint32_t* srow = state + (size_t)s * (n_mels + 8);
+  const int32_t* ints = reinterpret_cast<const int32_t*>(srow + n_mels);
+  const int b0 = lane, b1 = lane + 64;
+  const bool have0 = b0 < n_mels, have1 = b1 < n_mels;
+  const bool win0 = have0 && b0 >= lo && b0 < hi, win1 = have1 && b1 >= lo && b1 < hi;
+  float fl0 = have0 ? __uint_as_float(srow[b0]) : 0.0f, fl1 = have1 ? __uint_as_float(srow[b1]) : 0.0f;
+  int st = ints[0], run = ints[1], seen = ints[2], start = ints[3], end = ints[4], starts = ints[5], act_frames = ints[6];
+  if (seen == 0) start = end = -1;                      // a zeroed row: the fresh session
+  const float* src = mel + (int64_t)s * item_stride;
+  for (int f0 = 0; f0 < n; f0 += kVoiceChunk) {
+    const int m = min(kVoiceChunk, n - f0);
+    if (lane < m)
+      for (int b = 0; b < n_mels; ++b) tile[b * kVoicePitch + lane] = src[(int64_t)b * band_stride + f0 + lane];
+    __syncthreads();
+    uint32_t my_flag = 0, my_count = 0;
+    for (int t = 0; t < m; ++t) {
+      const float L0 = have0 ? tile[b0 * kVoicePitch + t] : 0.0f, L1 = have1 ? tile[b1 * kVoicePitch + t] : 0.0f;
+      const float up = st == 0 ? rise : rise_speech;
+      fl0 = voice_floor(fl0, L0, seen == 0, fall, up, min_level);
+      fl1 = voice_floor(fl1, L1, seen == 0, fall, up, min_level);
+      const bool e0 = win0 && L0 > min_level && (L0 - fl0) > thr, e1 = win1 && L1 > min_level && (L1 - fl1) > thr;
+      const int count = __popcll(__ballot(e0)) + __popcll(__ballot(e1));
+      const int active = count >= min_bands ? 1 : 0;
+      run = (active != (st == 1 ? 1 : 0)) ? run + 1 : 0;
+      if (st == 0 && run >= attack) {
+        st = 1; start = seen - run + 1; starts += 1; run = 0;
+      } else if (st == 1 && run >= release) {
+        st = 0; end = seen - run + 1; run = 0;
+      }
+      seen += 1;
+      act_frames += active;
+      if (lane == t) { my_flag = (uint32_t)(active | st << 1); my_count = (uint32_t)count; }
+    }
+    if (lane < m) {
+      if (flags) flags[(int64_t)s * out_pitch + f0 + lane] = (uint8_t)my_flag;
+      if (counts) counts[(int64_t)s * out_pitch + f0 + lane] = (uint8_t)my_count;
+    }
+    __syncthreads();                                    // the next chunk overwrites the tile
+  }
+  if (have0) srow[b0] = __float_as_uint(fl0);
+  if (have1) srow[b1] = __float_as_uint(fl1);
+  if (lane < 8) {
+    const int v = lane == 0 ? st : lane == 1 ? run : lane == 2 ? seen : lane == 3 ? start : lane == 4 ? end : lane == 5 ? starts
+                : lane == 6 ? act_frames : 0;
+    srow[n_mels + lane] = (uint32_t)v;
+  }
+}
+
+}  // namespace dmel
+
+extern "C" int dmel_voice_items(const float* mel, int64_t item_stride, int64_t band_stride, int n_mels, int S, const int64_t* n_frames,
+                                const float* fparams, const int32_t* iparams, void* state, uint8_t* flags, uint8_t* counts,
+                                int64_t out_pitch, void* table_scratch, void* stream) {
+  using namespace dmel;
+  DMEL_CHECK_ARG(mel && n_frames && fparams && iparams && state && table_scratch, "voice_items: NULL argument");
+  DMEL_CHECK_ARG(S >= 1 && S <= 65535, "voice_items: %d items, expected 1 .. 65535", S);
+  DMEL_CHECK_ARG(n_mels >= 1 && n_mels <= kVoiceMaxMels, "voice_items: %d mel bands, expected 1 .. %d", n_mels, kVoiceMaxMels);
+  DMEL_CHECK_ARG((((uintptr_t)mel | (uintptr_t)state | (uintptr_t)table_scratch) & 3) == 0,
+                 "voice_items: mel, state or table_scratch is not 4-byte aligned");
+  DMEL_CHECK_ARG(item_stride >= 0 && band_stride >= 0, "voice_items: negative strides (%lld, %lld)", (long long)item_stride,
+                 (long long)band_stride);
+  std::vector<uint32_t> tab((size_t)kVoiceWords * S, 0u);
+  int64_t live = 0;
+  double bytes = 0.0;
+  for (int s = 0; s < S; ++s) {
+    const int64_t n = n_frames[s];
+    DMEL_CHECK_ARG(n >= 0 && n <= 0x7fffffff, "voice_items: item %d: %lld frames, expected 0 .. 2^31 - 1", s, (long long)n);
+    if (n == 0) continue;                               // idle: its parameters are not looked at (the table row stays 0)
+    DMEL_CHECK_ARG(out_pitch >= n, "voice_items: item %d: %lld frames exceed the output pitch %lld", s, (long long)n, (long long)out_pitch);
+    const float* fp = fparams + (size_t)5 * s;
+    const int32_t* ip = iparams + (size_t)5 * s;
+    for (int k = 0; k < 5; ++k) DMEL_CHECK_ARG(std::isfinite(fp[k]), "voice_items: item %d: float parameter %d is not finite", s, k);
+    DMEL_CHECK_ARG(fp[0] > 0.0f, "voice_items: item %d: threshold %g, expected > 0", s, (double)fp[0]);
+    DMEL_CHECK_ARG(fp[2] > 0.0f && fp[2] <= 1.0f && fp[3] > 0.0f && fp[3] <= 1.0f,
+                   "voice_items: item %d: fall %g or rise %g outside (0, 1]", s, (double)fp[2], (double)fp[3]);
+    DMEL_CHECK_ARG(fp[4] >= 0.0f && fp[4] <= 1.0f, "voice_items: item %d: rise_speech %g outside [0, 1]", s, (double)fp[4]);
+    DMEL_CHECK_ARG(ip[0] >= 0 && ip[0] < ip[1] && ip[1] <= n_mels, "voice_items: item %d: bands [%d, %d) are not a window of the %d bands",
+                   s, ip[0], ip[1], n_mels);
+    DMEL_CHECK_ARG(ip[2] >= 1 && ip[2] <= ip[1] - ip[0], "voice_items: item %d: min_bands %d outside [1, %d]", s, ip[2], ip[1] - ip[0]);
+    DMEL_CHECK_ARG(ip[3] >= 1 && ip[3] <= (1 << 20) && ip[4] >= 1 && ip[4] <= (1 << 20),
+                   "voice_items: item %d: attack_frames %d or release_frames %d outside [1, 2^20]", s, ip[3], ip[4]);
+    uint32_t* it = tab.data() + (size_t)kVoiceWords * s;
+    it[0] = (uint32_t)n;
+    std::memcpy(it + 1, fp, 5 * sizeof(float));
+    std::memcpy(it + 6, ip, 5 * sizeof(int32_t));
+    ++live;
+    bytes += (double)n * (4.0 * n_mels + (flags ? 1 : 0) + (counts ? 1 : 0)) + 8.0 * (n_mels + 8);
+  }
+  if (live == 0) return DMEL_OK;                        // every item idle
+  hipStream_t st = (hipStream_t)stream;
+  DMEL_TRY(launch_table_put(tab.data(), tab.size() * sizeof(uint32_t), table_scratch, st));
+  {
+    // "small" carries the time and the bytes; the second scope only counts: one record per detector launch (dmel_prof_read("voice"))
+    ProfScope ps("small", st, 0.0, bytes), count("voice", st, 0.0, 0.0);
+    hipLaunchKernelGGL(voice_kernel, dim3((unsigned)S), dim3(64), 0, st, mel, item_stride, band_stride, n_mels,
+                       static_cast<const uint32_t*>(table_scratch), static_cast<uint32_t*>(state), flags, counts, out_pitch);
+  }
+  DMEL_HIP(hipGetLastError());
+  return DMEL_OK;
+}

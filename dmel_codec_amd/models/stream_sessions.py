@@ -20,6 +20,7 @@ import torch
 
 from .. import _lib
 from ..utils import crossfade, pcm
+from ..utils import voice as voice_rule
 from .stream_park import ParkingPool
 from .stream_schedule import (DecodeGeometry, DecodeSchedule, EarlyDecodeSchedule, EncodeGeometry, EncodeSchedule, decode_capacity,
                               decode_live_window, decode_rebase, encode_live_window, encode_need_from, resample_max_outputs, session_rows)
@@ -90,6 +91,21 @@ class EncodeSessions(ParkingPool):
     ValueError, no slot taken: the other kind, another geometry, width or depth, a rate the pool did not declare, a window or a
     tail that does not fit, an unknown format version.  Equal weights are the caller's contract (models/stream_park.py).
 
+    A listening session can be asked what every conversational loop asks on each step -- is this person speaking, have they
+    stopped, did they start while we talk -- without audio or mel reaching the host: a pool built with voice=True also serves
+    sessions opened with open(voice=True | VoiceConfig), each with a detector of its own on the log-mel frames the STFT launch
+    writes anyway (the rule, its state and its untuned defaults: utils/voice.py, which is also the host reference the pool is
+    tested against bit for bit).  After the STFT launch of a step, ONE dmel_voice_items launch serves every named slot with
+    detection that received frames, reading the step's temporary mel where it lies; a step without such a slot launches what it
+    did.  The state is one row of n_mels + 8 words per slot (`voice`), zeroed with the slot's other rows, and travels with
+    snapshot / restore as one more segment; push() returns what it returns and never syncs.  voice() -> {slot: VoiceReport} for
+    every slot with detection that is open or ended in the most recent push, from ONE device-to-host copy of that table, the only
+    sync and only when asked; voice_frames(slot) -> (flags, counts), device uint8 views of the frames of the slot's last push
+    (flags: active | speaking << 1 after the frame; counts: the bands that stood out).  The detector sees the codec-rate mel, so
+    rate, format and channels of the wire need nothing.  A pool built without voice=True allocates and launches exactly what it
+    did, refuses open(voice=) and a snapshot that carries a detector; a session without detection in a voice pool snapshots to
+    the bytes it always did.
+
     Only encoders the one-launch streaming kernel takes (residual channels in (32, 80], no condition, no output projection,
     dilations <= 8, fp32): anything else is refused at construction.
 
@@ -98,7 +114,7 @@ class EncodeSessions(ParkingPool):
     process -- a streaming decode, for example -- must call dmel_stft_set_exclusive_cu(1) first, exactly as pipeline.CodecLanes does."""
 
     def __init__(self, codec, slots: int, max_push_samples: int = 7680, sample_rate: Optional[int] = None,
-                 sample_rates: Iterable[int] = ()):
+                 sample_rates: Iterable[int] = (), voice: bool = False):
         enc, tr = codec.encoder, codec.encode_mel_transform
         if sample_rate is not None and int(sample_rate) != int(tr.sample_rate):
             raise NotImplementedError(f"sessions run at the codec's own rate ({tr.sample_rate} Hz); resample in front (StreamResampler), "
@@ -150,24 +166,43 @@ class EncodeSessions(ParkingPool):
         self.s0 = [0] * self.S
         self.tail = [0] * self.S                      # valid samples in the slot's row
         self.pick = [-1] * self.S                     # the channel of its pushes the slot encodes; -1: their mean
+        if not isinstance(voice, bool):
+            raise ValueError(f"voice must be a bool (a session's config goes to open(voice=)), got {voice!r}")
+        self.voice_on = voice                         # the pool keeps detector rows: sessions may open with voice=
+        if voice and not 1 <= self.n_mels <= voice_rule.MAX_MELS:
+            raise NotImplementedError(f"voice detection takes at most {voice_rule.MAX_MELS} mel bands, the transform has {self.n_mels}")
+        self.vcfg: List[Optional[voice_rule.VoiceConfig]] = [None] * self.S      # the slot's detector (None: none)
+        self._voice_n = [0] * self.S                  # frames of the slot's last push: the valid bytes of its flags / counts rows
+        self._voice_ended: set = set()                # slots with detection that ended in the most recent push
 
     def tokens_emitted(self, slot: int) -> int:
         self._check_open(slot)
         return self.sched[slot].tokens
 
     def open(self, sample_rate: Optional[int] = None, sample_format: str = "f32", channels: int = 1,
-             channel: Optional[int] = None) -> int:
+             channel: Optional[int] = None, voice=None) -> int:
         """take a free slot: fresh schedule, state zeroed before its first push.  sample_rate: the rate this session's pushes arrive
         at, one of the declared `sample_rates` (None: the codec's).  sample_format: "f32", "s16" for torch.int16 pushes (16-bit
         signed PCM, x / 32768), or "ulaw" / "alaw" for torch.uint8 pushes (G.711 codes).  channels: 1 .. 8; above 1 the pushes are
-        interleaved frames (n, channels), downmixed to their mean, or to channel `channel` of them (0 .. channels - 1).  Raises when
-        every slot is taken; a refused open takes no slot."""
+        interleaved frames (n, channels), downmixed to their mean, or to channel `channel` of them (0 .. channels - 1).  voice: True
+        (the defaults of utils/voice.py) or a VoiceConfig starts the session's voice-activity detector, on a pool built with
+        voice=True.  Raises when every slot is taken; a refused open takes no slot."""
         rate = self.codec_rate if sample_rate is None else int(sample_rate)
         pick = self._check_wire(rate, sample_format, channels, channel)
+        cfg = self._check_voice(voice_rule.as_config(voice))
         s = self._first_free()
         self._occupy(s, EncodeSchedule(self.geo), 0, rate, sample_format, channels)
         self.s0[s], self.tail[s], self.pick[s] = 0, 0, pick
+        self.vcfg[s], self._voice_n[s] = cfg, 0
         return s
+
+    def _check_voice(self, cfg: Optional[voice_rule.VoiceConfig]) -> Optional[voice_rule.VoiceConfig]:
+        """a session's detector config, refused here for open() and for restore() alike"""
+        if cfg is not None:
+            if not self.voice_on:
+                raise ValueError("voice on a pool built without voice=True: it has no detector rows")
+            cfg.window(self.n_mels)
+        return cfg
 
     def _validate(self, audio: Mapping[int, torch.Tensor], final) -> Dict[int, torch.Tensor]:
         """everything that can be refused, before any state changes and before any device call"""
@@ -218,6 +253,17 @@ class EncodeSessions(ParkingPool):
                         scratch=torch.empty(2 * N * self.C * self.cap + 2 * N + rows, dtype=torch.float32, device=dev),
                         stft_tab=torch.empty(4 * self.S, dtype=torch.int64, device=dev),
                         pcm_tab=torch.empty(4 * self.S, dtype=torch.int64, device=dev))
+        if self.voice_on:                             # dmel_voice_items: a state row per slot, the step's flags and counts (a step's
+            #                                           frames fit the slot's cap columns), 12 words per slot of the table
+            self.buf.update(voice=torch.zeros(self.S, self.n_mels + voice_rule.STATE_INTS, dtype=torch.int32, device=dev),
+                            voice_flags=torch.zeros(self.S, self.cap, dtype=torch.uint8, device=dev),
+                            voice_counts=torch.zeros(self.S, self.cap, dtype=torch.uint8, device=dev),
+                            voice_tab=torch.empty(voice_rule.TABLE_WORDS * self.S, dtype=torch.int32, device=dev))
+
+    def _prepare_slot(self, s: int) -> None:
+        super()._prepare_slot(s)
+        if self.voice_on:
+            self.buf["voice"][s].zero_()              # the fresh detector state (not one of _slot_views: a re-base does not shift it)
 
     def _slot_views(self, s: int):
         b, G = self.buf, self.G
@@ -240,15 +286,21 @@ class EncodeSessions(ParkingPool):
     _live_window = staticmethod(encode_live_window)
 
     def _park_meta(self, s: int) -> dict:
-        return dict(super()._park_meta(s), s0=self.s0[s], tail=self.tail[s], channel=None if self.pick[s] < 0 else self.pick[s])
+        meta = dict(super()._park_meta(s), s0=self.s0[s], tail=self.tail[s], channel=None if self.pick[s] < 0 else self.pick[s])
+        if self.vcfg[s] is not None:                  # only a session with detection carries the key: the others' snapshots are unchanged
+            meta["voice"] = self.vcfg[s].as_dict()
+        return meta
 
     def _park_schedule(self, meta: Mapping) -> EncodeSchedule:
         return EncodeSchedule.from_state(self.geo, meta["schedule"])
 
     def _park_shapes(self, meta: Mapping) -> List[Tuple[str, int, int]]:
         W, rows, rs = meta["window"][1] - meta["window"][0], self.G * self.C, meta["resampler"]
-        return ([("mel", self.n_mels, W)] + [(f"hist.{l}", rows, W) for l in range(self.L + 1)] + [("skip", rows, W), ("feat", rows, W),
-                ("samples", 1, meta["tail"]), ("resampler", 1, rs["fill"] if rs else 0)])
+        shapes = ([("mel", self.n_mels, W)] + [(f"hist.{l}", rows, W) for l in range(self.L + 1)] + [("skip", rows, W), ("feat", rows, W),
+                  ("samples", 1, meta["tail"]), ("resampler", 1, rs["fill"] if rs else 0)])
+        if meta.get("voice") is not None:             # the detector row; a session that has seen no frame owns the zeroed row: nothing
+            shapes.append(("voice", 1, self.n_mels + voice_rule.STATE_INTS if meta["schedule"]["frames"] > 0 else 0))
+        return shapes
 
     def _park_rows(self, s: int) -> Dict[str, torch.Tensor]:
         b, G = self.buf, self.G
@@ -258,10 +310,21 @@ class EncodeSessions(ParkingPool):
             rows[f"hist.{l}"] = b["hist"][l, s * G:(s + 1) * G]             # the slot's G rows are contiguous: one piece per level
         if self.rs is not None and self.rs.buf is not None:
             rows["resampler"] = self.rs.buf["rows"][s:s + 1]
+        if self.voice_on:
+            rows["voice"] = b["voice"][s:s + 1]
         return rows
 
     def _park_widths(self):
         return ("n_mels", self.n_mels), ("codec_rate", self.codec_rate)
+
+    def _park_voice(self, meta: Mapping) -> Optional[voice_rule.VoiceConfig]:
+        """the detector config a snapshot carries (None: none); ValueError where it is no config"""
+        if meta.get("voice") is None:
+            return None
+        try:
+            return voice_rule.VoiceConfig.from_dict(meta["voice"])
+        except TypeError as e:
+            raise ValueError(f"the voice config of the snapshot is not a VoiceConfig: {e}") from None
 
     def _park_fits(self, meta: Mapping, sc: EncodeSchedule) -> None:
         g, (lo, hi) = self.geo, meta["window"]
@@ -270,10 +333,12 @@ class EncodeSessions(ParkingPool):
             raise ValueError(f"a window of {hi - lo} frames and one maximal push ({room} frames) do not fit the capacity {self.cap}")
         if not 0 <= meta["tail"] <= self.width - self.codec_push:
             raise ValueError(f"a sample tail of {meta['tail']} samples and one maximal push do not fit a row of {self.width} samples")
+        self._check_voice(self._park_voice(meta))
 
     def _park_adopt(self, s: int, meta: Mapping) -> None:
         super()._park_adopt(s, meta)
         self.s0[s], self.tail[s], self.pick[s] = meta["s0"], meta["tail"], -1 if meta["channel"] is None else meta["channel"]
+        self.vcfg[s], self._voice_n[s] = self._park_voice(meta), 0
 
     # -- one step ----------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -287,7 +352,9 @@ class EncodeSessions(ParkingPool):
         released = self._resample(converted, final, placed)
         steps = self._intake(audio, released, placed, final)
         with torch.cuda.device(dev):
-            self._stft(steps, dev)
+            mel = self._stft(steps, dev)
+            if self.voice_on:
+                self._voice(steps, final, mel)
             self._wavenet(steps)
             out = self._quantise(steps, dev)
         self._release(final)
@@ -334,9 +401,10 @@ class EncodeSessions(ParkingPool):
             steps[s] = self.sched[s].step(n, s in final)
         return steps
 
-    def _stft(self, steps, dev) -> None:
+    def _stft(self, steps, dev) -> Optional[torch.Tensor]:
         """STFT: the new frames of every slot, each from its own sample tail (re-based first), into the slot's mel columns; the
-        samples no later frame reads leave the tail"""
+        samples no later frame reads leave the tail -> the launch's (S, n_mels, tmax) output, slot s's new frames at its columns
+        [0, frames[1] - frames[0]) (None: no slot had a frame)"""
         b, geo, S = self.buf, self.geo, self.S
         I64 = C.c_int64 * S
         n_frames = [0] * S
@@ -346,7 +414,7 @@ class EncodeSessions(ParkingPool):
             n_frames[s] = st.frames[1] - st.frames[0]
         tmax = max(n_frames)
         if not tmax:
-            return
+            return None
         from ..torch_ops import _stft_plan
         sp = self.codec.encode_mel_transform.spectrogram
         plan = _stft_plan(dev, sp.sample_rate, sp.n_fft, sp.win_length, sp.hop_length, sp.num_mels, float(sp.f_min or 0.0),
@@ -368,6 +436,42 @@ class EncodeSessions(ParkingPool):
                     row = b["samples"][s]
                     row[:keep] = row[drop:drop + keep] if drop >= keep else row[drop:drop + keep].clone()
                     self.s0[s], self.tail[s] = self.s0[s] + drop, keep
+        return mel
+
+    def _voice(self, steps, final, mel: Optional[torch.Tensor]) -> None:
+        """voice activity: ONE launch over the new frames of every named slot with detection, read from the STFT launch's own output"""
+        self._voice_ended = {s for s in final if self.vcfg[s] is not None}
+        counts = [0] * self.S
+        for s, st in steps.items():
+            if self.vcfg[s] is not None:
+                counts[s] = self._voice_n[s] = st.frames[1] - st.frames[0]
+        if mel is None or not any(counts):
+            return
+        b = self.buf
+        voice_rule.voice_items(mel, counts, self.vcfg, b["voice"], b["voice_flags"], b["voice_counts"], table=b["voice_tab"])
+
+    def _voice_slots(self) -> List[int]:
+        return [s for s in range(self.S) if self.vcfg[s] is not None and (self.sched[s] is not None or s in self._voice_ended)]
+
+    def voice(self) -> Dict[int, voice_rule.VoiceReport]:
+        """{slot: VoiceReport} of every slot with detection that is open or ended in the most recent push: ONE device-to-host copy of
+        the detector table (the only sync of the detector, and only here).  A slot that has not been pushed to reports no frames."""
+        slots = self._voice_slots()
+        live = [s for s in slots if not self._fresh[s]] if self.buf is not None else []
+        table = self.buf["voice"].cpu() if live else None
+        zero = voice_rule.fresh_state(self.n_mels)
+        return {s: voice_rule.report(table[s] if s in live else zero, self.geo.hop, self.codec_rate) for s in slots}
+
+    def voice_frames(self, slot: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(flags, counts) of the frames of the slot's last push: device uint8 views (n,), valid until the slot's next push.  flags:
+        active | speaking << 1 (the state after the frame); counts: the bands of the window that stood out of their floors"""
+        if not isinstance(slot, int) or slot not in self._voice_slots():
+            raise ValueError(f"slot {slot!r} has no voice detection (open(voice=)) or is neither open nor ended in the last push")
+        if self.buf is None or self._fresh[slot]:
+            empty = torch.empty(0, dtype=torch.uint8, device=self._device())
+            return empty, empty.clone()
+        n = self._voice_n[slot]
+        return self.buf["voice_flags"][slot, :n], self.buf["voice_counts"][slot, :n]
 
     def _wavenet(self, steps) -> None:
         """encoder WaveNet: every level of every slot advances to its own new frontier"""

@@ -470,6 +470,37 @@ int dmel_stream_fork_items(float* hist, float* skip, float* cond /*nullable*/, f
 int dmel_crossfade_items(float* const* blend /*entries nullable*/, float* const* tail, const float* const* save /*entries nullable*/,
                          const float* const* w, const int64_t* F, int R, void* table_scratch, void* stream);
 
+/* Voice activity and end of turn on log-mel frames, S session slots in ONE launch (csrc/small_ops.hip): the detector of encode
+ * sessions opened with voice= (models/stream_sessions.py), whose rule is utils/voice.py -- the kernel equals voice.scan bit for bit.
+ * Slot s reads frames t in [0, n_frames[s]) of its bands b in [0, n_mels) at mel[s * item_stride + b * band_stride + t] (strides in
+ * floats, frames contiguous) and carries one row of n_mels + 8 4-byte words in `state`: floor[b] (fp32) per band, then eight int32
+ * (state: 0 silence / 1 speech, run, seen, start, end, starts, active_frames, one reserved word kept at 0).  A zeroed row is a
+ * fresh session: seen == 0 makes the first frame initialise the floors and start = end = -1.  Per frame f = seen, L[b] its column:
+ *     fl = seen == 0 ? L[b] : floor[b] + c * (L[b] - floor[b]),  c = L[b] < floor[b] ? fall : state == 0 ? rise : rise_speech
+ *          (subtract, multiply, add: three separately rounded fp32 operations, no fma);   floor[b] = fl < min_level ? min_level : fl
+ *     count = #{b in [band_lo, band_hi): L[b] > min_level && L[b] - floor[b] > threshold};   active = count >= min_bands
+ *     run = (active != (state == 1)) ? run + 1 : 0
+ *     state 0 and run >= attack_frames:  state = 1, start = f - run + 1, starts += 1, run = 0
+ *     state 1 and run >= release_frames: state = 0, end = f - run + 1, run = 0
+ *     seen += 1;  active_frames += active;  flags[s * out_pitch + t] = active | state << 1;  counts[s * out_pitch + t] = count
+ * fparams row s is (threshold, min_level, fall, rise, rise_speech), iparams row s (band_lo, band_hi, min_bands, attack_frames,
+ * release_frames).  flags and counts (each nullable) are rows of out_pitch bytes; the bytes behind a row's n_frames[s] are not
+ * written.  n_frames[s] == 0 is an idle slot: neither its state row nor its output rows nor its parameters are looked at; when
+ * every slot is idle the call returns DMEL_OK and launches nothing.  The frame counter is an int32: 2^31 frames, 265 days at 93.75
+ * frames per second, which nothing checks.  NaN input is outside the contract.  DMEL_EINVAL, nothing launched, dmel_last_error
+ * naming the item: S outside [1, 65535], n_mels outside [1, 128], a NULL mel, state or table, a mel or state pointer that is not
+ * 4-byte aligned, negative strides, a negative n_frames[s] or one above 2^31 - 1, out_pitch below a row's frames, a value of fparams
+ * that is not finite, threshold <= 0, fall or rise outside (0, 1], rise_speech outside [0, 1], a band window that is not
+ * 0 <= lo < hi <= n_mels, min_bands outside [1, hi - lo], attack_frames or release_frames outside [1, 2^20].  n_frames, fparams,
+ * iparams are HOST tables, copied as launch arguments into table_scratch (12 S 4-byte words of device memory, 4-byte aligned): the
+ * caller may overwrite them as soon as the call returns.  One 64-lane wave per slot: a lane owns bands lane and lane + 64 and keeps
+ * their floors in registers for the whole launch; the slot's tile passes through LDS in chunks of 64 frames, read from global memory
+ * along the frames; the frame loop is sequential (the coefficient of a frame depends on the state after the one before it), the band
+ * count two ballots, the state machine uniform over the wave.  Plain vector stores, no atomics. */
+int dmel_voice_items(const float* mel, int64_t item_stride, int64_t band_stride, int n_mels, int S, const int64_t* n_frames,
+                     const float* fparams /* S x 5 */, const int32_t* iparams /* S x 5 */, void* state /* (S, n_mels + 8) words */,
+                     uint8_t* flags /*nullable*/, uint8_t* counts /*nullable*/, int64_t out_pitch, void* table_scratch, void* stream);
+
 /* R independent 2-D copies of 4-byte words in ONE launch (csrc/small_ops.hip): what takes the streaming state of live sessions out of
  * a pool's buffers into a snapshot and back (models/stream_sessions.py: snapshot / restore).  Descriptor r copies rows[r] rows of
  * cols[r] words: row i goes from src[r] + i * src_pitch[r] to dst[r] + i * dst_pitch[r], pitches in words.  Packing reads windows of

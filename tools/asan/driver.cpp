@@ -6,6 +6,8 @@
 // handle uploaded between create and the return of finalize (fake_hip.cpp): tests/test_host_asan.py holds them to a recorded fixture,
 // so no byte of a packed weight image moves unnoticed.  Only the handles built under `Fingerprinted` print (the small ones: the line of
 // a 20-layer WaveNet is 20 KB).  New handles go at the END of main: the weights are draws of one generator.
+#include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -546,6 +548,44 @@ int main() {
       CL[0] = 33; DP[0] = 33;
       RW[0] = 0; CL[1] = 0; SRC[0] = nullptr; DST[1] = nullptr; SP[0] = DP[0] = -1;   // every row idle: pointers and pitches are not looked at
       CK(pack(2));
+    }
+    {
+      // the voice detector: tables of exactly S entries (5 S parameters each), a table scratch of exactly 12 S words; its refusals read
+      // the host tables only
+      const int NM = 80, T = 130;
+      auto mel = buf(3 * NM * T), st = buf(3 * (NM + 8));
+      std::vector<uint8_t> fl(3 * T), ct(3 * T);
+      int64_t NF[3] = {T, 0, 65};
+      float FP[15] = {1.5f, -10.f, 0.1f, 0.02f, 0.002f, NAN, NAN, NAN, NAN, NAN, 1.5f, -10.f, 1.f, 1.f, 0.f};
+      int32_t IP[15] = {0, NM, 4, 3, 47, -9, -9, -9, -9, -9, 3, 9, 6, 1, 1 << 20};      // the idle item's parameters are not looked at
+      std::vector<uint32_t> tab(12 * 3);
+      int nm = NM, S = 3;
+      int64_t pitch = T;
+      auto scan = [&]() { return dmel_voice_items(mel.data(), (int64_t)NM * T, T, nm, S, NF, FP, IP, st.data(), fl.data(), ct.data(), pitch, tab.data(), nullptr); };
+      CK(scan());
+      auto refused = [&](const char* item, const char* what) {
+        const int rc = scan();
+        if (rc != DMEL_EINVAL || !std::strstr(dmel_last_error(), item)) { std::printf("FAIL voice_items accepted %s (%d: %s)\n", what, rc, dmel_last_error()); ++failures; }
+      };
+      S = 0; refused("0 items", "no item");
+      S = 65536; refused("65536 items", "more than 65535 items");
+      S = 3; nm = 0; refused("0 mel bands", "no band");
+      nm = 129; refused("129 mel bands", "more than 128 bands");
+      nm = NM; NF[2] = -1; refused("item 2", "a negative frame count");
+      NF[2] = T + 1; refused("item 2", "more frames than the output pitch");
+      NF[2] = 65; FP[10] = 0.f; refused("item 2", "a threshold of 0");
+      FP[10] = 1.5f; FP[1] = INFINITY; refused("item 0", "a min_level that is not finite");
+      FP[1] = -10.f; FP[2] = 0.f; refused("item 0", "fall = 0");
+      FP[2] = 0.1f; FP[13] = 1.5f; refused("item 2", "rise above 1");
+      FP[13] = 1.f; FP[4] = -0.1f; refused("item 0", "a negative rise_speech");
+      FP[4] = 0.002f; IP[1] = NM + 1; refused("item 0", "a band window behind n_mels");
+      IP[1] = NM; IP[10] = 9; refused("item 2", "an empty band window");
+      IP[10] = 3; IP[12] = 7; refused("item 2", "min_bands above the window");
+      IP[12] = 6; IP[3] = 0; refused("item 0", "attack_frames = 0");
+      IP[3] = 3; IP[14] = (1 << 20) + 1; refused("item 2", "release_frames above 2^20");
+      IP[14] = 1 << 20;
+      NF[0] = NF[2] = 0;                          // every item idle
+      CK(scan());
     }
     auto xs = buf(2 * 8 * 3000), ys = buf(2 * 8 * 3000), da = buf(8), db = buf(8);
     CK(dmel_aa_snake_f32(xs.data(), ys.data(), al.data(), be.data(), taps.data(), taps.data(), 1, 2, 8, 3000, nullptr));
