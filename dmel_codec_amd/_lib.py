@@ -168,6 +168,7 @@ PROTOTYPES = {
     "dmel_conv_backward_data": (C.c_int, [vp, vp, vp, C.c_int, C.c_int64, vp]),
     "dmel_conv_backward_weight": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int64, vp]),
     "dmel_conv_forward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int64, vp]),
+    "dmel_conv_forward_ex": (C.c_int, [vp, vp, vp, C.c_int, C.c_int64, vp, C.c_int, C.c_float, vp, vp, C.c_int, C.c_int, vp]),
     "dmel_stft_grad_create": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, vp]),
     "dmel_stft_grad_destroy": (None, [vp]),
     "dmel_stft_grad_workspace_bytes": (C.c_size_t, [vp, C.c_int, C.c_int64]),

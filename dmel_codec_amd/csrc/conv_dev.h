@@ -3,6 +3,9 @@
 #pragma once
 #include "conv.h"
 
+#include <cstdlib>
+#include <type_traits>
+
 namespace dmel {
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
@@ -47,6 +50,7 @@ struct KArgs {
   // per-item column windows (conv.h ConvRun::win), read by conv_bf16_kernel<WIN> only: row b / len_div of `win`, win_stride int32 each
   const int32_t* win;
   int win_stride, win_shift, win_end, win_valid[2];
+  int fast;                    // conv_fastpath_enabled() at launch: full tiles / interior chunks of the fp16-split kernels skip the edge code
 };
 
 __device__ __forceinline__ float act_apply(float v, int act) {
@@ -64,11 +68,81 @@ __device__ __forceinline__ bool in_gap(const KArgs& a, int q) {
   return a.fold_pitch > 0 && (q % a.fold_pitch) >= a.fold_valid;
 }
 
+// DMEL_CONV_FASTPATH=0: every tile and every staged chunk of the fp16-split kernels takes the edge code (clamps, masks and selects per
+// element), as a tile that straddles the end of a row does anyway; unset or any other value: tiles / chunks that lie wholly inside the
+// tensor take the forms without them (epi_full_tile below, the interior staging of conv_bf16_kernel / conv_pc_kernel).  Same expressions
+// in the same order on both: bit-identical (tests/test_gpu_conv_fastpath.py).  Read per call.
+inline bool conv_fastpath_enabled() {
+  const char* e = getenv("DMEL_CONV_FASTPATH");
+  return !(e && e[0] == '0' && e[1] == 0);
+}
+
+// Lean LINEAR epilogue of one 32 x (32 NT) tile that lies WHOLLY inside the output: its 32 rows below C, its columns below Tcols, Tout
+// and out_len, no fold gap.  Nothing is clamped, masked or selected, and the flags that are uniform over the launch (residual, running
+// sum, 1 / out_div) are template arguments: a launch with out_div == 1 executes no division (v / 1.f == v exactly, so skipping it
+// keeps the bits; the vocoder divides in the last convolution of a stage only).  Addresses are a wave-uniform row base (scalar registers:
+// mtile, the row's constant offset and the channel stride are uniform) plus ONE 32-bit lane byte offset per tensor, computed once from 4 h and
+// the lane's column: no per-row vector multiply, sign extension or 64-bit vector add.  Value expressions and their order are those of the
+// edge loop in conv_epilogue.  As there, all residual / running-sum loads of RB rows are issued before the first use.
+// The 32-bit lane offset of a load / store whose base is wave-uniform, as a value the compiler cannot look through (no instruction is
+// emitted).  Seen through, (uniform base) + (lane offset) is re-associated into a 64-bit lane pointer that is hoisted, and every row /
+// every load then pays a 64-bit vector add for its uniform part; opaque, the access takes the uniform base as its scalar address
+// operand and the offset as its 32-bit vector one (global_load_dword v, v_off, s[base:base+1]).
+__device__ __forceinline__ uint32_t lane_off(uint32_t off) {
+  asm volatile("" : "+v"(off));
+  return off;
+}
+
+template <int NT, int RB, bool RES, bool ACC, bool DIV>
+__device__ __forceinline__ void epi_full_tile(const KArgs& a, const floatx16 (&acc)[NT], int mtile, float* yb, const float* rb, uint32_t yoff,
+                                              uint32_t roff, uint32_t boff) {
+  const int ycs = (int)a.y_cs, rcs = (int)a.res_cs;      // int products: one item's offsets stay below 2^31 (launch_conv checks)
+  const float* bias_t = a.bias + mtile;
+  float* yt = yb + mtile * ycs;
+  const float* rt = RES ? rb + mtile * rcs : nullptr;
+#pragma unroll
+  for (int g = 0; g < 16 / RB; ++g) {
+    float bias[RB], rv[RB][NT], ov[RB][NT];
+#pragma unroll
+    for (int k = 0; k < RB; ++k) {
+      const int r = g * RB + k, row = (r & 3) + 8 * (r >> 2);       // accumulator register r -> row `row` + 4 h of the tile
+      bias[k] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(bias_t + row) + lane_off(boff));
+      if constexpr (RES) {
+        const float* rr = rt + row * rcs;
+        const uint32_t ro = lane_off(roff);
+#pragma unroll
+        for (int ni = 0; ni < NT; ++ni) rv[k][ni] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(rr + ni * 32) + ro);
+      }
+      if constexpr (ACC) {
+        const float* yr = yt + row * ycs;
+        const uint32_t yo = lane_off(yoff);
+#pragma unroll
+        for (int ni = 0; ni < NT; ++ni) ov[k][ni] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(yr + ni * 32) + yo);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < RB; ++k) {
+      const int r = g * RB + k, row = (r & 3) + 8 * (r >> 2);
+      float* yr = yt + row * ycs;
+      const uint32_t yo = lane_off(yoff);
+#pragma unroll
+      for (int ni = 0; ni < NT; ++ni) {
+        float v = acc[ni][r] + bias[k];
+        if constexpr (RES) v += rv[k][ni];
+        if constexpr (ACC) v += ov[k][ni];
+        if constexpr (DIV) v = v / a.out_div;
+        *reinterpret_cast<float*>(reinterpret_cast<char*>(yr + ni * 32) + yo) = v;
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------------------ epilogue (shared by both kernels)
 // Lane (h, l31) holds, for each 32x32 tile, column l31 and rows (r&3) + 8*(r>>2) + 4*h, r = 0..15.
 // Row-only quantities (bias, row offsets, channel map) are computed once per row, outside the column loop.
 // LEAN_ONLY: the caller guarantees the lean LINEAR case (no activation, row scale, phases or output stride): the general loop is not compiled
-template <int MT, int NT, int MODE, int RB = 4, bool LEAN_ONLY = false>      // RB: rows whose residual / running-sum loads are in flight together (lean LINEAR path)
+// FAST: compile epi_full_tile for the lean LINEAR tiles that lie wholly inside the output (the fp16-split kernels; taken when a.fast is set)
+template <int MT, int NT, int MODE, int RB = 4, bool LEAN_ONLY = false, bool FAST = false>      // RB: rows whose residual / running-sum loads are in flight together (lean LINEAR path)
 __device__ __forceinline__ void conv_epilogue(const KArgs& a, floatx16 (&acc)[MT][NT], int mrow0, int colbase, int b, int lb,
                                               int h) {
   const int tcols = (int)a.Tcols;
@@ -90,10 +164,44 @@ __device__ __forceinline__ void conv_epilogue(const KArgs& a, floatx16 (&acc)[MT
         live[ni] = colbase + ni * 32 < olim && !in_gap(a, colbase + ni * 32);
         cq[ni] = min(colbase + ni * 32, tlim - 1);
       }
+      // full-tile test, wave-uniform: the wave's first column (the lane's column less its index in the half-wave) and its row tile
+      bool full_cols = false;
+      float* ybu = nullptr;            // the item's bases from a batch index in a scalar register: with the XCD-chunked grid b is the result of
+      const float* rbu = nullptr;      // vector divisions, and a base in vector registers cannot be the scalar address operand of a load / store
+      if constexpr (FAST) {
+        const int bu = __builtin_amdgcn_readfirstlane(b);
+        ybu = a.y + (int64_t)bu * a.y_bs;
+        rbu = a.res ? a.res + (int64_t)bu * a.res_bs : nullptr;
+        const int col0 = __builtin_amdgcn_readfirstlane(colbase - (int)(__lane_id() & 31));
+        full_cols = a.fast && a.fold_pitch == 0 && col0 + NT * 32 <= min(tlim, olim) &&
+                    tlim <= (1 << 28) && a.y_cs < (1 << 27) && a.res_cs < (1 << 27);      // the lane's BYTE offsets (4 rows + a column) fit 32 bits
+      }
 #pragma unroll
       for (int mi = 0; mi < MT; ++mi) {
         const int mtile = mrow0 + mi * 32;
         if (mtile >= a.mtiles * 32) continue;
+        if constexpr (FAST) {
+          const int mt = __builtin_amdgcn_readfirstlane(mtile);
+          if (full_cols && mt + 32 <= a.C) {
+            const uint32_t yoff = (uint32_t)(4 * h * ycs + colbase) * 4u, roff = (uint32_t)(4 * h * rcs + colbase) * 4u, boff = (uint32_t)(16 * h);      // bytes
+            auto tile = [&](auto R, auto A, auto D) {
+              epi_full_tile<NT, RB, decltype(R)::value, decltype(A)::value, decltype(D)::value>(a, acc[mi], mt, ybu, rbu, yoff, roff, boff);
+            };
+            constexpr std::true_type T{};
+            constexpr std::false_type F{};
+            switch ((rb ? 4 : 0) | (a.accumulate ? 2 : 0) | (a.out_div != 1.f ? 1 : 0)) {
+              case 0: tile(F, F, F); break;
+              case 1: tile(F, F, T); break;
+              case 2: tile(F, T, F); break;
+              case 3: tile(F, T, T); break;
+              case 4: tile(T, F, F); break;
+              case 5: tile(T, F, T); break;
+              case 6: tile(T, T, F); break;
+              default: tile(T, T, T); break;
+            }
+            continue;
+          }
+        }
         // RB rows at a time: all their residual / running-sum loads are issued before the first use, so the wave meets the HBM latency
         // 16 / RB times per tile.  The fp16-split kernel asks for 8 (its second accumulator set is dead here: -0.15 ms per bench step); for the
         // others 8 rows cost 32 registers and a wave of occupancy (100 -> 132 VGPRs on the 128 x 96 tile), so they keep 4.

@@ -392,10 +392,18 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, NP == 2 ? 2 : 1) void conv_
   static_assert(!WIN || (PS == 0 && TAPS == 0 && NP != 1), "per-item windows: generic K loop over fp32 inputs, NP = 2 or 3");
   constexpr int BM = WAVES_M * MT * 32, BN = WAVES_N * NT * 32;
   constexpr int XS = BN + HALO;
+  // The instances with the scalar-base x loads, the interior staging and the full-tile epilogue: the fp16 split of fp32 inputs with taps.
+  // Pointwise instances (HALO = 0) keep the code they had: their launches are the WaveNet projections at one column tile per item, all
+  // edge, and the leaner code moved them from 170 to 167 registers, i.e. from two to three waves per SIMD, which measured 8 % SLOWER on
+  // the 1120 x 560 projection (profiles/conv_vector_diet.txt).
+  constexpr bool DIET = NP == 2 && PS == 0 && !WIN && HALO > 0;
   constexpr int SUB = KG / 2;                            // 16-channel K steps (per tap) per staged chunk
   // Staging map: an item is (8-channel group kg, column j) -- eight channels of one staged column, i.e. one lane's B operand.  The group is
-  // WAVE-UNIFORM (a wave owns one group, or a segment of one, or a few whole groups), so the eight row addresses are scalar registers and
-  // a load is global_load_dword v, v_column_offset, s[row_base]: no vector address arithmetic per element.
+  // WAVE-UNIFORM (a wave owns one group, or a segment of one, or a few whole groups), so the eight row addresses are scalar registers.
+  // DIET instances: a load is global_load_dword v, v_column_offset, s[row_base] with no vector address arithmetic per element -- which the
+  // compiler emits only when the batch index is in a scalar register (b_u) and the lane offset is opaque to it inside the K loop (lane_off,
+  // conv_dev.h); left alone it hoists a 64-bit zero-extended column offset out of the loop and forms every address with a v_lshl_add_u64
+  // (32 per chunk and wave).  The other instances (NP = 1 / 3, PS, WIN, HALO = 0) still do that.
   constexpr int NWV = WAVES_M * WAVES_N;
   static_assert(NWV % KG == 0 || KG % NWV == 0, "waves and staged channel groups must divide one another");
   constexpr int SEG = NWV >= KG ? NWV / KG : 1;          // waves sharing one group's row of columns
@@ -486,6 +494,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, NP == 2 ? 2 : 1) void conv_
   }
   bool xok[NIT];
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+  const int b_u = __builtin_amdgcn_readfirstlane(b);
   const int st_kg0 = (wave_u / SEG) * RPW, st_j0 = (wave_u % SEG) * SL;
   auto load_x = [&](int sg, int chunk) {
     if constexpr (PS != 0) {
@@ -514,7 +523,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, NP == 2 ? 2 : 1) void conv_
       }
       return;
     }
-    const char* xb = reinterpret_cast<const char*>(a.seg[sg].x + (int64_t)b * a.seg[sg].bstride);
+    const char* xb = reinterpret_cast<const char*>(a.seg[sg].x + (int64_t)(DIET ? b_u : b) * a.seg[sg].bstride);
     const int taps = a.seg[sg].taps, dil = a.seg[sg].dil, tstride = a.seg[sg].tstride, Cin = a.seg[sg].Cin;
     const int wx = BN + (taps - 1) * dil;
     const int lim = sg == 0 ? lim0 : lim1;
@@ -534,7 +543,8 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, NP == 2 ? 2 : 1) void conv_
         const int j = min(st_j0 + ps * 64 + lane, XS - 1);
         const int tau = tau0 + j * tstride;
         xok[it] = (j < wx) && (tau >= 0) && (tau < lim);
-        const uint32_t col = (uint32_t)min(max(tau, 0), tin - 1) * 4u;
+        uint32_t col = (uint32_t)min(max(tau, 0), tin - 1) * 4u;
+        if constexpr (DIET) col = lane_off(col);      // keeps the loads in the scalar-base form inside the K loop (conv_dev.h)
 #pragma unroll
         for (int e = 0; e < 8; ++e) xr[it][e] = *reinterpret_cast<const float*>(rowp[e] + col);
       }
@@ -562,6 +572,11 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, NP == 2 ? 2 : 1) void conv_
     // pieces would sum to the unrounded product, and the whole-stack WaveNet kernel, which rounds, would differ in the last bit.
     const float scale = NP == 2 ? a.seg[sg].in_scale * f16_in : a.seg[sg].in_scale;
     const int Cin = a.seg[sg].Cin;
+    // scalars of the interior test below (NP = 2): load_x's window of the segment
+    const bool fast_x = a.fast != 0;
+    const int tstride_x = a.seg[sg].tstride, wx_x = BN + (a.seg[sg].taps - 1) * a.seg[sg].dil;
+    const int lim_x = __builtin_amdgcn_readfirstlane(sg == 0 ? lim0 : lim1);      // uniform values that may sit in vector registers (the
+    const int tau0_x = __builtin_amdgcn_readfirstlane(q0) * tstride_x + a.seg[sg].toff - a.seg[sg].pad_left;      // XCD-chunked grid's divisions)
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
       const int rr = it / NPASS, ps = it % NPASS;
@@ -570,6 +585,28 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, NP == 2 ? 2 : 1) void conv_
       if ((SL % 64 != 0 && jl >= SL) || (XS % SL != 0 && j >= XS)) continue;
       const int i = (st_kg0 + rr) * XS + j;
       const int c0 = chunk * (KG * 8) + (st_kg0 + rr) * 8;        // scalar: the group's first channel
+      if constexpr (DIET) {
+        // INTERIOR item (a wave-uniform test on scalars: the first and last column the wave stores of this item): every column has
+        // j < wx and tau in [0, lim), and the group's eight channels exist.  xok is true and the channel factor is `scale` for every
+        // element, so the selects go, and scale / subtraction / second scale run as packed fp32 on channel pairs (v_pk_mul_f32,
+        // v_pk_add_f32: each half rounds like the scalar instruction).  Same operations in the same order as below: same bits.
+        const int jlo = st_j0 + ps * 64, jhi = min(st_j0 + (ps * 64 + 63 < SL - 1 ? ps * 64 + 63 : SL - 1), XS - 1);
+        if (fast_x && tau0_x + jlo * tstride_x >= 0 && tau0_x + jhi * tstride_x < lim_x && jhi < wx_x && c0 + 8 <= Cin) {
+          typedef float f32x2 __attribute__((ext_vector_type(2)));
+          f16x8 ph, pl;
+#pragma unroll
+          for (int e = 0; e < 8; e += 2) {
+            const f32x2 vv = (f32x2){xr[it][e], xr[it][e + 1]} * scale;
+            const f16x2 hi = __builtin_convertvector(vv, f16x2);
+            const f16x2 lo = __builtin_convertvector((vv - __builtin_convertvector(hi, f32x2)) * kF16LoScale, f16x2);
+            ph[e] = hi[0]; ph[e + 1] = hi[1];
+            pl[e] = lo[0]; pl[e + 1] = lo[1];
+          }
+          dst[i] = __builtin_bit_cast(uint4, ph);
+          dst[PSZ + i] = __builtin_bit_cast(uint4, pl);
+          continue;
+        }
+      }
       float v[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = (xok[it] ? xr[it][e] : 0.f) * (c0 + e < Cin ? scale : 0.f);
@@ -813,7 +850,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, NP == 2 ? 2 : 1) void conv_
     if (a.res) aw.res = a.res + wshift;
     conv_epilogue<MT, NT, MODE, NP == 2 ? 8 : 4>(aw, acc, mblk * BM + wave_m * (MT * 32), q0 + wave_n * (NT * 32) + l31, b, lb, h);
   } else {
-    conv_epilogue<MT, NT, MODE, NP == 2 ? 8 : 4>(a, acc, mblk * BM + wave_m * (MT * 32), q0 + wave_n * (NT * 32) + l31, b, lb, h);
+    conv_epilogue<MT, NT, MODE, NP == 2 ? 8 : 4, false, DIET>(a, acc, mblk * BM + wave_m * (MT * 32), q0 + wave_n * (NT * 32) + l31, b, lb, h);
   }
 }
 
@@ -1195,6 +1232,7 @@ int launch_conv(const PackedConv& pc, const ConvRun& r, hipStream_t stream) {
   ka.fold_pitch = r.fold_pitch; ka.fold_valid = r.fold_valid;
   ka.win = r.win; ka.win_stride = r.win_stride; ka.win_shift = r.win_shift; ka.win_end = r.win_end;
   ka.win_valid[0] = r.win_valid[0]; ka.win_valid[1] = r.win_valid[1];
+  ka.fast = conv_fastpath_enabled() ? 1 : 0;
   if (r.win) {
     if (r.fold_pitch != 0) { set_error("conv (per-item windows): the folded batch has one time axis for all items and no table"); return DMEL_EUNSUPPORTED; }
     if (r.yp) { set_error("conv (per-item windows): the pre-split output path does not read the window table"); return DMEL_EUNSUPPORTED; }
@@ -1299,6 +1337,19 @@ extern "C" int dmel_conv_create(dmel_conv** out, const float* w_host, const floa
 }
 
 extern "C" void dmel_conv_destroy(dmel_conv* c) { delete c; }
+
+extern "C" int dmel_conv_forward_ex(const dmel_conv* c, const float* x, float* y, int B, int64_t T, const float* residual, int accumulate,
+                                    float out_div, const int64_t* in_len, const int64_t* out_len, int fold_pitch, int fold_valid, void* stream) {
+  DMEL_CHECK_ARG(c && x && y, "NULL argument");
+  ConvRun r;
+  r.seg[0].x = x; r.seg[0].bstride = (int64_t)c->Cin * T; r.seg[0].cstride = T; r.seg[0].Tin = T; r.seg[0].in_len = in_len;
+  r.B = B; r.Tcols = T; r.y = y; r.y_bs = (int64_t)c->Cout * T; r.y_cs = T; r.Tout = T;
+  r.res = residual; r.res_bs = r.y_bs; r.res_cs = T;
+  r.accumulate = accumulate ? 1 : 0; r.out_div = out_div; r.out_len = out_len;
+  r.fold_pitch = fold_pitch; r.fold_valid = fold_valid;
+  r.precision = c->precision;
+  return launch_conv(c->pc, r, (hipStream_t)stream);
+}
 
 extern "C" int dmel_conv_forward(const dmel_conv* c, const float* x, float* y, int B, int64_t T, void* stream) {
   DMEL_CHECK_ARG(c && x && y, "NULL argument");

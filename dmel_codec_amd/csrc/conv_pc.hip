@@ -110,7 +110,7 @@ __global__ __launch_bounds__(64 * (WM * WN + NPROD)) void conv_pc_kernel(KArgs a
     for (int ni = 0; ni < NT; ++ni)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[0][ni][r] = fmaf(acl[ni][r], 1.f / kF16LoScale, acc[0][ni][r]);
-    conv_epilogue<1, NT, MODE, 8, MODE == EPI_LINEAR>(a, acc, (mblk * WM + wave_m) * 32, q0 + wave_n * (NT * 32) + l31, b, b / a.len_div, h);
+    conv_epilogue<1, NT, MODE, 8, MODE == EPI_LINEAR, true>(a, acc, (mblk * WM + wave_m) * 32, q0 + wave_n * (NT * 32) + l31, b, b / a.len_div, h);
     return;
   }
 
@@ -135,9 +135,11 @@ __global__ __launch_bounds__(64 * (WM * WN + NPROD)) void conv_pc_kernel(KArgs a
       const int cp = it & 7, tb = tau0 + (it >> 3) * SEG;
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
-        const float* xr = xb + (int64_t)min(chunk * 16 + 2 * cp + c, Cin - 1) * cs;
+        // a wave-uniform row base (scalar registers) plus the lane's 32-bit byte offset: global_load_dword v, v_off, s[row] (lane_off, conv_dev.h)
+        const char* xr = reinterpret_cast<const char*>(xb + (int64_t)min(chunk * 16 + 2 * cp + c, Cin - 1) * cs);
 #pragma unroll
-        for (int k = 0; k < 2; ++k) pre[r][c][k] = xr[min(max(tb + lane + 64 * k, 0), T - 1)];
+        for (int k = 0; k < 2; ++k)
+          pre[r][c][k] = *reinterpret_cast<const float*>(xr + lane_off((uint32_t)min(max(tb + lane + 64 * k, 0), T - 1) * 4u));
       }
     }
   };
@@ -158,6 +160,7 @@ __global__ __launch_bounds__(64 * (WM * WN + NPROD)) void conv_pc_kernel(KArgs a
     const int tau0 = q0 - a.seg[sg].pad_left;
     const int nitems = 8 * ((wx + SEG - 1) / SEG);
     const float scale = a.seg[sg].in_scale * kF16XScale;
+    const bool fast = a.fast != 0;
 #pragma unroll
     for (int r = 0; r < IP; ++r) {
       const int it = p + NPROD * r;
@@ -169,7 +172,17 @@ __global__ __launch_bounds__(64 * (WM * WN + NPROD)) void conv_pc_kernel(KArgs a
       for (int k = 0; k < 2; ++k) {
         const int o = lane + 64 * k, t = tb + o;
         const bool ok = t >= 0 && t < T;
-        {
+        // INTERIOR pass (wave-uniform test on scalars): all 64 columns inside the row and the segment, both channels of the pair real.
+        // No validity selects, no store mask, and the pair is scaled, subtracted and scaled again as packed fp32 -- the operations and
+        // their order are those of the edge code below: same bits.
+        if (fast && tb + 64 * k >= 0 && tb + 64 * k + 63 < T && 64 * k + 63 < w && chunk * 16 + 2 * cp + 1 < Cin) {
+#pragma clang fp contract(off)
+          const pc_f32x2 vv = (pc_f32x2){cur[r][0][k], cur[r][1][k]} * scale;
+          const pc_f16x2 hi = __builtin_convertvector(vv, pc_f16x2);
+          const pc_f16x2 lo = __builtin_convertvector((vv - __builtin_convertvector(hi, pc_f32x2)) * kF16LoScale, pc_f16x2);
+          d32[(j0 + o) * 4] = __builtin_bit_cast(uint32_t, hi);
+          d32[PSZ * 4 + (j0 + o) * 4] = __builtin_bit_cast(uint32_t, lo);
+        } else {
           // the operand split of conv_bf16_kernel<NP = 2>::store_x: the scaled input is ROUNDED to fp32, then split (no contraction)
 #pragma clang fp contract(off)
           const float v0 = (ok ? cur[r][0][k] : 0.f) * sc0, v1 = (ok ? cur[r][1][k] : 0.f) * sc1;
@@ -246,6 +259,7 @@ int launch_conv_pc(const PackedConv& pc, const ConvRun& r, hipStream_t stream) {
   ka.skip_first = r.skip_first; ka.out_div = r.out_div;
   ka.y = r.y; ka.y_bs = r.y_bs; ka.y_cs = r.y_cs; ka.Tout = r.Tout > 0 ? r.Tout : r.Tcols;
   ka.res = r.res; ka.res_bs = r.res_bs; ka.res_cs = r.res_cs; ka.skip = r.skip;
+  ka.fast = conv_fastpath_enabled() ? 1 : 0;
   DMEL_CHECK_ARG((int64_t)d.C * ka.y_cs < ((int64_t)1 << 31) && ka.Tout < ((int64_t)1 << 30), "conv_pc: one batch item of the output exceeds 32-bit offsets");
   ka.mtiles = pc.Mpad / 32;
   const double rows_real = d.mode == EPI_LINEAR ? (double)d.C : 2.0 * d.C;

@@ -714,6 +714,15 @@ int dmel_conv_create(dmel_conv** c, const float* w_host, const float* bias_host 
 void dmel_conv_destroy(dmel_conv* c);
 int dmel_conv_set_precision(dmel_conv* c, int precision);
 int dmel_conv_forward(const dmel_conv* c, const float* x, float* y, int B, int64_t T, void* stream);
+/* dmel_conv_forward with the options of the LINEAR epilogue and of the input staging that the modules use (tests of those paths):
+ *   y = (accumulate ? y : 0) + conv1d(x) + bias (+ residual), then / out_div (1.0f: no division).
+ * residual (B, Cout, T) nullable.  in_len / out_len: device int64[B], nullable -- input columns at or behind in_len[b] read as zero, output
+ * columns at or behind out_len[b] are written as zero.  fold_pitch > 0: the folded batch of short items -- B must be 1, the row holds
+ * T / fold_pitch items of fold_valid columns each, followed by fold_pitch - fold_valid zero columns that the caller keeps zero in x; the
+ * gap columns of y are written as zero. */
+int dmel_conv_forward_ex(const dmel_conv* c, const float* x, float* y, int B, int64_t T, const float* residual /*nullable*/, int accumulate,
+                         float out_div, const int64_t* in_len /*nullable*/, const int64_t* out_len /*nullable*/, int fold_pitch, int fold_valid,
+                         void* stream);
 /* Activation1d fused into the convolution that reads it: y = conv1d(Activation1d(x)) + bias (+ residual), the act -> conv pair of
  * AMPBlock1 / AMPBlock2.forward (bigvgan/bigvgan.py:132-141, :232-237; alias_free_activation/torch/act.py:25-30) as ONE kernel --
  * producer waves compute the anti-aliased Snake of the staged x tile in LDS while consumer waves run the MFMA loop, so the activated
