@@ -1619,3 +1619,228 @@ extern "C" int dmel_voice_items(const float* mel, int64_t item_stride, int64_t b
   DMEL_HIP(hipGetLastError());
   return DMEL_OK;
 }
+
+namespace dmel {
+
+// ---- DTMF keys on codec-rate samples (include/dmel_hip.h: dmel_dtmf_items; the rule and the state row: utils/dtmf.py) ----------------
+// Row s of the table is (first, n_new, N, c_0 .. c_7, emin, rel, max_col_over_row, max_row_over_col, g, hits, misses, 0, 0), twenty
+// 4-byte words; workgroup s owns slot s.  The blocks a launch touches are independent but for the first, which continues the carried
+// s1 / s2 / e of the state row and has consumed `fill` samples already: block j of the launch holds positions [j N, (j + 1) N) of the
+// stream that began `fill` samples in front of column `first`, of which [fill, fill + n_new) exist.  So the parallel axis is
+// (block, filter): nine lanes serve a block -- eight Goertzel recursions and the energy --, a wave seven blocks (lane 63 rests), the
+// four waves of the workgroup 28 blocks per pass.  The samples of a pass go through LDS in chunks of kDtmfChunk per block: row j of
+// the tile is block j's samples [t0, t0 + 64), read from global memory along the row (plain 4-byte loads: `first` is any column) and
+// zero where the stream has no sample; the pitch of 65 words puts the seven rows a wave reads in one step on seven banks, and the
+// nine lanes of a block read one word, a broadcast.  Whole blocks leave their eight powers and their energy in LDS, one thread per
+// block decides, and every thread then runs the same state machine over the pass's decisions in block order (integers only, as
+// voice_kernel does); thread j keeps the two output bytes of block j, thread 0 writes the events.  The trailing partial block's
+// s1 / s2 / e go back to the row.  The recursion, the power, the energy and the compares are separately rounded operations
+// (fp contract(off), as voice_floor above): what the fp32 host expression gives.  Plain stores, no atomics.
+constexpr int kDtmfWords = 20, kDtmfChunk = 64, kDtmfPitch = kDtmfChunk + 1, kDtmfPass = 28, kDtmfState = 128, kDtmfRing = 32;
+constexpr int kDtmfMinBlock = 32, kDtmfMaxBlock = 4096;
+__device__ __forceinline__ void dtmf_step(float x, float c, float& s1, float& s2) {
+#pragma clang fp contract(off)
+  const float p = c * s1;
+  const float q = p - s2;
+  const float s0 = x + q;
+  s2 = s1;
+  s1 = s0;
+}
+__device__ __forceinline__ float dtmf_energy(float e, float x) {
+#pragma clang fp contract(off)
+  const float sq = x * x;
+  return e + sq;
+}
+__device__ __forceinline__ float dtmf_power(float c, float s1, float s2) {
+#pragma clang fp contract(off)
+  const float a = s1 * s1, b = s2 * s2, m = s1 * s2;
+  const float sum = a + b, cm = c * m;
+  return sum - cm;
+}
+// key + 1 of a whole block, or 0: P[0 .. 3] the row powers, P[4 .. 7] the column powers, P[8] the energy
+__device__ __forceinline__ int dtmf_decide(const float* P, float emin, float rel, float mcr, float mrc, float g) {
+#pragma clang fp contract(off)
+  int r = 0, c = 0;
+  for (int j = 1; j < 4; ++j) {
+    if (P[j] > P[r]) r = j;                             // the lowest index wins a tie
+    if (P[4 + j] > P[4 + c]) c = j;
+  }
+  const float Pr = P[r], Pc = P[4 + c], E = P[8];
+  bool ok = E > emin;
+  for (int j = 0; j < 4; ++j) {
+    const float tr = rel * P[j], tc = rel * P[4 + j];
+    if (j != r) ok = ok && Pr > tr;
+    if (j != c) ok = ok && Pc > tc;
+  }
+  const float lim_c = mcr * Pr, lim_r = mrc * Pc, both = Pr + Pc, need = g * E;
+  ok = ok && Pc <= lim_c && Pr <= lim_r && both > need;
+  return ok ? 4 * r + c + 1 : 0;
+}
+__global__ __launch_bounds__(256) void dtmf_kernel(const float* __restrict__ samples, int64_t row_stride, const uint32_t* __restrict__ tab,
+                                                   uint32_t* __restrict__ state, uint8_t* __restrict__ decided,
+                                                   uint8_t* __restrict__ pressed, int64_t out_pitch) {
+  __shared__ float tile[kDtmfPass * kDtmfPitch];
+  __shared__ float pw[kDtmfPass * 9];
+  __shared__ int dec[kDtmfPass];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  const uint32_t* row = tab + (size_t)s * kDtmfWords;
+  const int64_t n_new = (int64_t)(int32_t)row[1];
+  if (n_new <= 0) return;                               // idle (uniform: in front of the first barrier)
+  const int64_t first = (int64_t)(int32_t)row[0];
+  const int N = (int)row[2];
+  const int lane = tid & 63, jb = lane / 9, k = lane - 9 * jb, jw = (tid >> 6) * 7 + jb;      // block jw of the pass, filter k (8: energy)
+  const float coef = k < 8 ? __uint_as_float(row[3 + k]) : 0.0f;
+  const float emin = __uint_as_float(row[11]), rel = __uint_as_float(row[12]), mcr = __uint_as_float(row[13]);
+  const float mrc = __uint_as_float(row[14]), g = __uint_as_float(row[15]);
+  const int hits = (int)row[16], misses = (int)row[17];
+  uint32_t* srow = state + (size_t)s * kDtmfState;
+  const int32_t* ints = reinterpret_cast<const int32_t*>(srow);
+  int fill = ints[17];
+  if ((unsigned)fill >= (unsigned)N) fill = 0;          // no row the rule wrote; keeps every index below inside the launch's columns
+  int blocks = ints[18], down = ints[19], cand = ints[20], run = ints[21], miss = ints[22], events = ints[23];
+  const int64_t end = fill + n_new;                     // positions [fill, end) exist
+  const int64_t nblk = (end + N - 1) / N, done = end / N;
+  const float* src = samples + (int64_t)s * row_stride + first - fill;       // position p is src[p]; only [fill, end) is read
+  uint8_t* dout = decided + (int64_t)s * out_pitch;
+  uint8_t* pout = pressed + (int64_t)s * out_pitch;
+  for (int64_t b0 = 0; b0 < nblk; b0 += kDtmfPass) {
+    const int nb = (int)min((int64_t)kDtmfPass, nblk - b0);
+    const int nd = (int)max((int64_t)0, min((int64_t)nb, done - b0));          // the whole blocks of the pass
+    const int64_t B = b0 + jw;
+    const bool mine = jb < 7 && jw < nb;
+    const int i0 = (mine && B == 0) ? fill : 0;
+    const int i1 = mine ? (int)min((int64_t)N, end - B * N) : 0;
+    float s1 = 0.0f, s2 = 0.0f;                         // the energy lane keeps e in s1
+    if (mine && B == 0) {
+      if (k < 8) { s1 = __uint_as_float(srow[k]); s2 = __uint_as_float(srow[8 + k]); }
+      else s1 = __uint_as_float(srow[16]);
+    }
+    // the samples the pass's blocks still need: [t_lo, t_hi) of each (one block alone may begin and end inside itself)
+    const int t_lo = (nb == 1 && b0 == 0) ? fill : 0;
+    const int t_hi = nb > 1 ? N : (int)min((int64_t)N, end - b0 * N);
+    for (int t0 = t_lo - t_lo % kDtmfChunk; t0 < t_hi; t0 += kDtmfChunk) {
+      for (int idx = tid; idx < nb * kDtmfChunk; idx += 256) {
+        const int r = idx / kDtmfChunk, cidx = idx % kDtmfChunk, i = t0 + cidx;
+        const int64_t p = (b0 + r) * N + i;
+        tile[r * kDtmfPitch + cidx] = (i < N && p >= fill && p < end) ? src[p] : 0.0f;
+      }
+      __syncthreads();
+      if (mine) {
+        const float* xs = tile + jw * kDtmfPitch;
+        const int a = max(i0, t0) - t0, z = min(i1, t0 + kDtmfChunk) - t0;
+        if (k < 8) {
+          for (int t = a; t < z; ++t) dtmf_step(xs[t], coef, s1, s2);
+        } else {
+          for (int t = a; t < z; ++t) s1 = dtmf_energy(s1, xs[t]);
+        }
+      }
+      __syncthreads();                                  // the next chunk overwrites the tile
+    }
+    if (mine) {
+      if (i1 == N) {
+        pw[jw * 9 + k] = k < 8 ? dtmf_power(coef, s1, s2) : s1;
+      } else {                                          // the open block: its carry goes back to the row
+        srow[k < 8 ? k : 16] = __float_as_uint(s1);
+        if (k < 8) srow[8 + k] = __float_as_uint(s2);
+      }
+    }
+    __syncthreads();
+    if (tid < nd) dec[tid] = dtmf_decide(pw + tid * 9, emin, rel, mcr, mrc, g);
+    __syncthreads();
+    uint32_t my_dec = 0, my_down = 0;
+    for (int j = 0; j < nd; ++j) {
+      const int d = dec[j];
+      if (down == 0) {
+        if (d == 0) { cand = 0; run = 0; }
+        else if (d == cand) run += 1;
+        else { cand = d; run = 1; }
+        if (cand != 0 && run >= hits) {
+          down = cand; miss = 0;
+          if (tid == 0) {
+            uint32_t* ev = srow + 32 + 3 * ((uint32_t)events % kDtmfRing);
+            ev[0] = (uint32_t)down; ev[1] = (uint32_t)(blocks - run + 1); ev[2] = 0xffffffffu;
+          }
+          events += 1;
+        }
+      } else if (d == down) {
+        miss = 0;
+      } else {
+        miss += 1;
+        if (miss >= misses) {
+          if (tid == 0) srow[32 + 3 * ((uint32_t)(events - 1) % kDtmfRing) + 2] = (uint32_t)(blocks - miss + 1);
+          down = 0; cand = 0; run = 0; miss = 0;
+        }
+      }
+      blocks += 1;
+      if (tid == j) { my_dec = (uint32_t)d; my_down = (uint32_t)down; }
+    }
+    if (tid < nd) {
+      dout[b0 + tid] = (uint8_t)my_dec;
+      pout[b0 + tid] = (uint8_t)my_down;
+    }
+  }
+  const int left = (int)(end - done * N);               // the open block's samples
+  if (left == 0 && tid < 17) srow[tid] = 0u;            // a whole last block: the carry is the fresh one
+  if (tid == 0) {
+    srow[17] = (uint32_t)left; srow[18] = (uint32_t)blocks; srow[19] = (uint32_t)down; srow[20] = (uint32_t)cand;
+    srow[21] = (uint32_t)run; srow[22] = (uint32_t)miss; srow[23] = (uint32_t)events;
+  }
+}
+
+}  // namespace dmel
+
+extern "C" int dmel_dtmf_items(const float* samples, int64_t row_stride, int S, const int64_t* first, const int64_t* n_new,
+                               const int32_t* N, const float* coef, const float* fparams, const int32_t* iparams, void* state,
+                               uint8_t* decided, uint8_t* pressed, int64_t out_pitch, void* table_scratch, void* stream) {
+  using namespace dmel;
+  DMEL_CHECK_ARG(samples && first && n_new && N && coef && fparams && iparams && state && decided && pressed && table_scratch,
+                 "dtmf_items: NULL argument");
+  DMEL_CHECK_ARG(S >= 1 && S <= 65535, "dtmf_items: %d items, expected 1 .. 65535", S);
+  DMEL_CHECK_ARG((((uintptr_t)samples | (uintptr_t)state | (uintptr_t)table_scratch) & 3) == 0,
+                 "dtmf_items: samples, state or table_scratch is not 4-byte aligned");
+  DMEL_CHECK_ARG(row_stride >= 0 && out_pitch >= 0, "dtmf_items: negative row stride %lld or output pitch %lld", (long long)row_stride,
+                 (long long)out_pitch);
+  std::vector<uint32_t> tab((size_t)kDtmfWords * S, 0u);
+  int64_t live = 0;
+  double bytes = 0.0;
+  for (int s = 0; s < S; ++s) {
+    const int64_t n = n_new[s];
+    DMEL_CHECK_ARG(n >= 0 && n <= 0x3fffffff, "dtmf_items: item %d: %lld new samples, expected 0 .. 2^30 - 1", s, (long long)n);
+    if (n == 0) continue;                               // idle: its parameters are not looked at (the table row stays 0)
+    DMEL_CHECK_ARG(first[s] >= 0 && first[s] <= 0x3fffffff, "dtmf_items: item %d: first column %lld, expected 0 .. 2^30 - 1", s,
+                   (long long)first[s]);
+    const int32_t nb = N[s];
+    DMEL_CHECK_ARG(nb >= kDtmfMinBlock && nb <= kDtmfMaxBlock, "dtmf_items: item %d: a block of %d samples, expected %d .. %d", s, nb,
+                   kDtmfMinBlock, kDtmfMaxBlock);
+    const int64_t most = (n + nb - 1) / nb;             // whatever the open block holds (at most N - 1 samples)
+    DMEL_CHECK_ARG(out_pitch >= most, "dtmf_items: item %d: %lld samples can complete %lld blocks, which exceed the output pitch %lld", s,
+                   (long long)n, (long long)most, (long long)out_pitch);
+    const float* ck = coef + (size_t)8 * s;
+    const float* fp = fparams + (size_t)5 * s;
+    const int32_t* ip = iparams + (size_t)2 * s;
+    for (int k = 0; k < 8; ++k)
+      DMEL_CHECK_ARG(std::isfinite(ck[k]) && ck[k] >= -2.0f && ck[k] <= 2.0f, "dtmf_items: item %d: coefficient %d is not in [-2, 2]", s, k);
+    for (int k = 0; k < 5; ++k)
+      DMEL_CHECK_ARG(std::isfinite(fp[k]) && fp[k] > 0.0f, "dtmf_items: item %d: float parameter %d is not finite and positive", s, k);
+    DMEL_CHECK_ARG(ip[0] >= 1 && ip[0] <= (1 << 20) && ip[1] >= 1 && ip[1] <= (1 << 20),
+                   "dtmf_items: item %d: hits %d or misses %d outside [1, 2^20]", s, ip[0], ip[1]);
+    uint32_t* it = tab.data() + (size_t)kDtmfWords * s;
+    it[0] = (uint32_t)first[s]; it[1] = (uint32_t)n; it[2] = (uint32_t)nb;
+    std::memcpy(it + 3, ck, 8 * sizeof(float));
+    std::memcpy(it + 11, fp, 5 * sizeof(float));
+    std::memcpy(it + 16, ip, 2 * sizeof(int32_t));
+    ++live;
+    bytes += 4.0 * (double)n + 2.0 * (double)most + 8.0 * kDtmfState;
+  }
+  if (live == 0) return DMEL_OK;                        // every item idle
+  hipStream_t st = (hipStream_t)stream;
+  DMEL_TRY(launch_table_put(tab.data(), tab.size() * sizeof(uint32_t), table_scratch, st));
+  {
+    // "small" carries the time and the bytes; the second scope only counts: one record per detector launch (dmel_prof_read("dtmf"))
+    ProfScope ps("small", st, 0.0, bytes), count("dtmf", st, 0.0, 0.0);
+    hipLaunchKernelGGL(dtmf_kernel, dim3((unsigned)S), dim3(256), 0, st, samples, row_stride, static_cast<const uint32_t*>(table_scratch),
+                       static_cast<uint32_t*>(state), decided, pressed, out_pitch);
+  }
+  DMEL_HIP(hipGetLastError());
+  return DMEL_OK;
+}

@@ -400,7 +400,7 @@ class VQGAN(nn.Module):
             yield ids
 
     def encode_sessions(self, slots: int, max_push_samples: int = 7680, sample_rate: Optional[int] = None, sample_rates=(),
-                        voice: bool = False):
+                        voice: bool = False, dtmf: bool = False):
         """A pool of `slots` INDEPENDENT incremental encodes served by one streaming step: sessions open, receive their own number of
         samples per step (at most max_push_samples), stall and close on their own -- what streaming_encoder(batch=B), B streams in
         lockstep, cannot do -- and each one's concatenated ids are the bits of encode() on its own clip.  One STFT launch, one encoder
@@ -412,9 +412,11 @@ class VQGAN(nn.Module):
         count: pool.open(channels=2) starts a session fed interleaved stereo frames (n, 2), downmixed (the mean, or channel=k) inside
         that same launch.  voice=True adds a voice-activity and end-of-turn detector row per slot: pool.open(voice=True | VoiceConfig)
         starts a session's detector, served for all slots of a step by one more launch on the log-mel frames, read with pool.voice()
-        (utils/voice.py has the rule).  See models/stream_sessions.py: EncodeSessions."""
+        (utils/voice.py has the rule).  dtmf=True adds a DTMF key detector row per slot: pool.open(dtmf=True | DtmfConfig) starts a
+        session's detector, served for all slots of a step by one more launch on the codec-rate samples, read with pool.dtmf()
+        (utils/dtmf.py has the rule).  See models/stream_sessions.py: EncodeSessions."""
         from .stream_sessions import EncodeSessions
-        return EncodeSessions(self, slots, max_push_samples, sample_rate, sample_rates, voice)
+        return EncodeSessions(self, slots, max_push_samples, sample_rate, sample_rates, voice, dtmf)
 
     # ------------------------------------------------------------------------------ decode side
     @torch.no_grad()

@@ -20,6 +20,7 @@ import torch
 
 from .. import _lib
 from ..utils import crossfade, pcm
+from ..utils import dtmf as dtmf_rule
 from ..utils import voice as voice_rule
 from .stream_park import ParkingPool
 from .stream_schedule import (DecodeGeometry, DecodeSchedule, EarlyDecodeSchedule, EncodeGeometry, EncodeSchedule, decode_capacity,
@@ -106,6 +107,20 @@ class EncodeSessions(ParkingPool):
     did, refuses open(voice=) and a snapshot that carries a detector; a session without detection in a voice pool snapshots to
     the bytes it always did.
 
+    A session on a phone line can also be asked which keys its caller pressed: a pool built with dtmf=True serves sessions opened
+    with open(dtmf=True | DtmfConfig), each with a DTMF detector of its own on the samples the step leaves in the slot's row anyway --
+    at the codec's rate, as f32, behind the convert, downmix and resample launches, whatever the wire was (the rule, its state
+    row and its caveats: utils/dtmf.py, which is also the host reference the pool is tested against bit for bit).  In front of
+    the STFT launch of a step (which re-bases the sample rows), ONE dmel_dtmf_items launch serves every named slot with a detector
+    that gained samples, over exactly the columns it gained, the resampler's flush of a final push included; a step without such
+    a slot launches what it did.  The state is one row of 128 words per slot (`dtmf`: the open block's filter state, the debounce
+    counters and a ring of the last 32 events), zeroed with the slot's other rows, and travels with snapshot / restore as one
+    more segment; push() returns what it returns and never syncs.  dtmf() -> {slot: DtmfReport} for every slot with a detector that
+    is open or ended in the most recent push, from ONE device-to-host copy of that table, the only sync and only when asked;
+    dtmf_blocks(slot) -> (decided, pressed), device uint8 views of the blocks the slot's last push completed (key + 1, 0: none).
+    Voice and DTMF are independent options of one pool.  A pool built without dtmf=True allocates and launches exactly what it
+    did, refuses open(dtmf=) and a snapshot that carries a detector; a session without one snapshots to the bytes it always did.
+
     Only encoders the one-launch streaming kernel takes (residual channels in (32, 80], no condition, no output projection,
     dilations <= 8, fp32): anything else is refused at construction.
 
@@ -114,7 +129,7 @@ class EncodeSessions(ParkingPool):
     process -- a streaming decode, for example -- must call dmel_stft_set_exclusive_cu(1) first, exactly as pipeline.CodecLanes does."""
 
     def __init__(self, codec, slots: int, max_push_samples: int = 7680, sample_rate: Optional[int] = None,
-                 sample_rates: Iterable[int] = (), voice: bool = False):
+                 sample_rates: Iterable[int] = (), voice: bool = False, dtmf: bool = False):
         enc, tr = codec.encoder, codec.encode_mel_transform
         if sample_rate is not None and int(sample_rate) != int(tr.sample_rate):
             raise NotImplementedError(f"sessions run at the codec's own rate ({tr.sample_rate} Hz); resample in front (StreamResampler), "
@@ -174,26 +189,35 @@ class EncodeSessions(ParkingPool):
         self.vcfg: List[Optional[voice_rule.VoiceConfig]] = [None] * self.S      # the slot's detector (None: none)
         self._voice_n = [0] * self.S                  # frames of the slot's last push: the valid bytes of its flags / counts rows
         self._voice_ended: set = set()                # slots with detection that ended in the most recent push
+        if not isinstance(dtmf, bool):
+            raise ValueError(f"dtmf must be a bool (a session's config goes to open(dtmf=)), got {dtmf!r}")
+        self.dtmf_on = dtmf                           # the pool keeps DTMF detector rows: sessions may open with dtmf=
+        self.dcfg: List[Optional[dtmf_rule.DtmfConfig]] = [None] * self.S        # the slot's DTMF detector (None: none)
+        self._dtmf_n = [0] * self.S                   # blocks the slot's last push completed: the valid bytes of its decided / pressed rows
+        self._dtmf_ended: set = set()                 # slots with a DTMF detector that ended in the most recent push
 
     def tokens_emitted(self, slot: int) -> int:
         self._check_open(slot)
         return self.sched[slot].tokens
 
     def open(self, sample_rate: Optional[int] = None, sample_format: str = "f32", channels: int = 1,
-             channel: Optional[int] = None, voice=None) -> int:
+             channel: Optional[int] = None, voice=None, dtmf=None) -> int:
         """take a free slot: fresh schedule, state zeroed before its first push.  sample_rate: the rate this session's pushes arrive
         at, one of the declared `sample_rates` (None: the codec's).  sample_format: "f32", "s16" for torch.int16 pushes (16-bit
         signed PCM, x / 32768), or "ulaw" / "alaw" for torch.uint8 pushes (G.711 codes).  channels: 1 .. 8; above 1 the pushes are
         interleaved frames (n, channels), downmixed to their mean, or to channel `channel` of them (0 .. channels - 1).  voice: True
         (the defaults of utils/voice.py) or a VoiceConfig starts the session's voice-activity detector, on a pool built with
-        voice=True.  Raises when every slot is taken; a refused open takes no slot."""
+        voice=True.  dtmf: True (the defaults of utils/dtmf.py) or a DtmfConfig starts the session's DTMF key detector, on a pool
+        built with dtmf=True.  Raises when every slot is taken; a refused open takes no slot."""
         rate = self.codec_rate if sample_rate is None else int(sample_rate)
         pick = self._check_wire(rate, sample_format, channels, channel)
         cfg = self._check_voice(voice_rule.as_config(voice))
+        keys = self._check_dtmf(dtmf_rule.as_config(dtmf))
         s = self._first_free()
         self._occupy(s, EncodeSchedule(self.geo), 0, rate, sample_format, channels)
         self.s0[s], self.tail[s], self.pick[s] = 0, 0, pick
         self.vcfg[s], self._voice_n[s] = cfg, 0
+        self.dcfg[s], self._dtmf_n[s] = keys, 0
         return s
 
     def _check_voice(self, cfg: Optional[voice_rule.VoiceConfig]) -> Optional[voice_rule.VoiceConfig]:
@@ -202,6 +226,14 @@ class EncodeSessions(ParkingPool):
             if not self.voice_on:
                 raise ValueError("voice on a pool built without voice=True: it has no detector rows")
             cfg.window(self.n_mels)
+        return cfg
+
+    def _check_dtmf(self, cfg: Optional[dtmf_rule.DtmfConfig]) -> Optional[dtmf_rule.DtmfConfig]:
+        """a session's DTMF config, refused here for open() and for restore() alike"""
+        if cfg is not None:
+            if not self.dtmf_on:
+                raise ValueError("dtmf on a pool built without dtmf=True: it has no detector rows")
+            cfg.block(self.codec_rate)
         return cfg
 
     def _validate(self, audio: Mapping[int, torch.Tensor], final) -> Dict[int, torch.Tensor]:
@@ -260,10 +292,20 @@ class EncodeSessions(ParkingPool):
                             voice_counts=torch.zeros(self.S, self.cap, dtype=torch.uint8, device=dev),
                             voice_tab=torch.empty(voice_rule.TABLE_WORDS * self.S, dtype=torch.int32, device=dev))
 
+        if self.dtmf_on:                              # dmel_dtmf_items: a state row per slot, the step's decisions (a push completes at most
+            #                                           codec_push // 32 + 1 blocks of 32 samples or more), 20 words per slot of the table
+            pitch = self.codec_push // dtmf_rule.MIN_BLOCK + 2
+            self.buf.update(dtmf=torch.zeros(self.S, dtmf_rule.STATE_WORDS, dtype=torch.int32, device=dev),
+                            dtmf_decided=torch.zeros(self.S, pitch, dtype=torch.uint8, device=dev),
+                            dtmf_pressed=torch.zeros(self.S, pitch, dtype=torch.uint8, device=dev),
+                            dtmf_tab=torch.empty(dtmf_rule.TABLE_WORDS * self.S, dtype=torch.int32, device=dev))
+
     def _prepare_slot(self, s: int) -> None:
         super()._prepare_slot(s)
         if self.voice_on:
             self.buf["voice"][s].zero_()              # the fresh detector state (not one of _slot_views: a re-base does not shift it)
+        if self.dtmf_on:
+            self.buf["dtmf"][s].zero_()               # the fresh DTMF state
 
     def _slot_views(self, s: int):
         b, G = self.buf, self.G
@@ -289,6 +331,8 @@ class EncodeSessions(ParkingPool):
         meta = dict(super()._park_meta(s), s0=self.s0[s], tail=self.tail[s], channel=None if self.pick[s] < 0 else self.pick[s])
         if self.vcfg[s] is not None:                  # only a session with detection carries the key: the others' snapshots are unchanged
             meta["voice"] = self.vcfg[s].as_dict()
+        if self.dcfg[s] is not None:                  # likewise
+            meta["dtmf"] = self.dcfg[s].as_dict()
         return meta
 
     def _park_schedule(self, meta: Mapping) -> EncodeSchedule:
@@ -300,6 +344,8 @@ class EncodeSessions(ParkingPool):
                   ("samples", 1, meta["tail"]), ("resampler", 1, rs["fill"] if rs else 0)])
         if meta.get("voice") is not None:             # the detector row; a session that has seen no frame owns the zeroed row: nothing
             shapes.append(("voice", 1, self.n_mels + voice_rule.STATE_INTS if meta["schedule"]["frames"] > 0 else 0))
+        if meta.get("dtmf") is not None:              # the DTMF row; a session that has seen no sample owns the zeroed row: nothing
+            shapes.append(("dtmf", 1, dtmf_rule.STATE_WORDS if meta["schedule"]["samples"] > 0 else 0))
         return shapes
 
     def _park_rows(self, s: int) -> Dict[str, torch.Tensor]:
@@ -312,6 +358,8 @@ class EncodeSessions(ParkingPool):
             rows["resampler"] = self.rs.buf["rows"][s:s + 1]
         if self.voice_on:
             rows["voice"] = b["voice"][s:s + 1]
+        if self.dtmf_on:
+            rows["dtmf"] = b["dtmf"][s:s + 1]
         return rows
 
     def _park_widths(self):
@@ -326,6 +374,15 @@ class EncodeSessions(ParkingPool):
         except TypeError as e:
             raise ValueError(f"the voice config of the snapshot is not a VoiceConfig: {e}") from None
 
+    def _park_dtmf(self, meta: Mapping) -> Optional[dtmf_rule.DtmfConfig]:
+        """the DTMF config a snapshot carries (None: none); ValueError where it is no config"""
+        if meta.get("dtmf") is None:
+            return None
+        try:
+            return dtmf_rule.DtmfConfig.from_dict(meta["dtmf"])
+        except TypeError as e:
+            raise ValueError(f"the dtmf config of the snapshot is not a DtmfConfig: {e}") from None
+
     def _park_fits(self, meta: Mapping, sc: EncodeSchedule) -> None:
         g, (lo, hi) = self.geo, meta["window"]
         room = self.codec_push // g.hop + 1 + (g.n_fft - g.pad + g.hop - 1) // g.hop
@@ -334,11 +391,13 @@ class EncodeSessions(ParkingPool):
         if not 0 <= meta["tail"] <= self.width - self.codec_push:
             raise ValueError(f"a sample tail of {meta['tail']} samples and one maximal push do not fit a row of {self.width} samples")
         self._check_voice(self._park_voice(meta))
+        self._check_dtmf(self._park_dtmf(meta))
 
     def _park_adopt(self, s: int, meta: Mapping) -> None:
         super()._park_adopt(s, meta)
         self.s0[s], self.tail[s], self.pick[s] = meta["s0"], meta["tail"], -1 if meta["channel"] is None else meta["channel"]
         self.vcfg[s], self._voice_n[s] = self._park_voice(meta), 0
+        self.dcfg[s], self._dtmf_n[s] = self._park_dtmf(meta), 0
 
     # -- one step ----------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -350,8 +409,11 @@ class EncodeSessions(ParkingPool):
         self._ensure_buffers(dev)
         converted, placed = self._place(audio)
         released = self._resample(converted, final, placed)
+        tails = list(self.tail) if self.dtmf_on else None
         steps = self._intake(audio, released, placed, final)
         with torch.cuda.device(dev):
+            if self.dtmf_on:
+                self._dtmf(steps, final, tails)
             mel = self._stft(steps, dev)
             if self.voice_on:
                 self._voice(steps, final, mel)
@@ -472,6 +534,47 @@ class EncodeSessions(ParkingPool):
             return empty, empty.clone()
         n = self._voice_n[slot]
         return self.buf["voice_flags"][slot, :n], self.buf["voice_counts"][slot, :n]
+
+    def _dtmf(self, steps, final, tails: List[int]) -> None:
+        """DTMF keys: ONE launch over the samples every named slot with a detector gained in this step -- columns [tail before,
+        tail after) of its row, whichever of the copy, the convert launch and the resample launch put them there -- in front of the
+        STFT phase, which re-bases the rows"""
+        self._dtmf_ended = {s for s in final if self.dcfg[s] is not None}
+        first, n_new = [0] * self.S, [0] * self.S
+        for s, st in steps.items():
+            if self.dcfg[s] is not None:
+                first[s], n_new[s] = tails[s], self.tail[s] - tails[s]
+                N = self.dcfg[s].block(self.codec_rate)
+                self._dtmf_n[s] = st.samples // N - (st.samples - n_new[s]) // N
+        if not any(n_new):
+            return
+        b = self.buf
+        dtmf_rule.dtmf_items(b["samples"], first, n_new, self.dcfg, b["dtmf"], b["dtmf_decided"], b["dtmf_pressed"],
+                             sample_rate=self.codec_rate, table=b["dtmf_tab"])
+
+    def _dtmf_slots(self) -> List[int]:
+        return [s for s in range(self.S) if self.dcfg[s] is not None and (self.sched[s] is not None or s in self._dtmf_ended)]
+
+    def dtmf(self) -> Dict[int, dtmf_rule.DtmfReport]:
+        """{slot: DtmfReport} of every slot with a DTMF detector that is open or ended in the most recent push: ONE device-to-host
+        copy of the detector table (the only sync of the detector, and only here).  A slot that has not been pushed to reports
+        no sample."""
+        slots = self._dtmf_slots()
+        live = [s for s in slots if not self._fresh[s]] if self.buf is not None else []
+        table = self.buf["dtmf"].cpu() if live else None
+        zero = dtmf_rule.fresh_state()
+        return {s: dtmf_rule.report(table[s] if s in live else zero, self.dcfg[s].block(self.codec_rate), self.codec_rate) for s in slots}
+
+    def dtmf_blocks(self, slot: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(decided, pressed) of the blocks the slot's last push completed: device uint8 views (n,), valid until the slot's next
+        push.  decided: the key + 1 the block decided (0: none); pressed: the key + 1 held after the block"""
+        if not isinstance(slot, int) or slot not in self._dtmf_slots():
+            raise ValueError(f"slot {slot!r} has no DTMF detector (open(dtmf=)) or is neither open nor ended in the last push")
+        if self.buf is None or self._fresh[slot]:
+            empty = torch.empty(0, dtype=torch.uint8, device=self._device())
+            return empty, empty.clone()
+        n = self._dtmf_n[slot]
+        return self.buf["dtmf_decided"][slot, :n], self.buf["dtmf_pressed"][slot, :n]
 
     def _wavenet(self, steps) -> None:
         """encoder WaveNet: every level of every slot advances to its own new frontier"""

@@ -501,6 +501,41 @@ int dmel_voice_items(const float* mel, int64_t item_stride, int64_t band_stride,
                      const float* fparams /* S x 5 */, const int32_t* iparams /* S x 5 */, void* state /* (S, n_mels + 8) words */,
                      uint8_t* flags /*nullable*/, uint8_t* counts /*nullable*/, int64_t out_pitch, void* table_scratch, void* stream);
 
+/* DTMF (touch-tone) keys on codec-rate samples, S session slots in ONE launch (csrc/small_ops.hip): the detector of encode sessions
+ * opened with dtmf= (models/stream_sessions.py), whose rule, defaults and caveats are utils/dtmf.py -- the kernel equals dtmf.scan bit
+ * for bit.  Slot s reads its n_new[s] new samples at samples[s * row_stride + first[s] + i] (fp32, any 4-byte offset) and carries one
+ * row of 128 4-byte words in `state`: words 0 .. 7 the s1 and 8 .. 15 the s2 of the eight Goertzel filters in the open (partial)
+ * block (rows 697, 770, 852, 941 Hz, then columns 1209, 1336, 1477, 1633 Hz), 16 its energy, all fp32; then int32: 17 fill (samples
+ * of the open block consumed), 18 blocks, 19 down, 20 candidate, 21 run, 22 miss_run, 23 events; 24 .. 31 reserved, kept at 0;
+ * 32 .. 127 the ring of the last 32 events, (key + 1, start_block, end_block or -1) each, event i at ring[i % 32].  A zeroed row is
+ * a fresh session.  Blocks are N[s] consecutive samples, counted from the session's first; a partial last block is never decided.
+ * Per block and filter k, in sample order from s1 = s2 = 0:   p = c_k * s1, q = p - s2, s0 = x + q, s2 = s1, s1 = s0   (three
+ * separately rounded fp32 operations, no fma);   P_k = (s1 * s1 + s2 * s2) - c_k * (s1 * s2), every operation rounded;   the energy
+ * e = e + x * x.  With r / c the argmax of the row / column powers (the lowest index on a tie), the block decides key 4 r + c where
+ *     E > emin;   P_r > rel * P_j for the other rows, P_c > rel * P_j for the other columns;   P_c <= max_col_over_row * P_r and
+ *     P_r <= max_row_over_col * P_c;   (P_r + P_c) > g * E
+ * and nothing otherwise.  The state machine, per decided block b = blocks with decision d (key + 1, or 0):
+ *     no key down:  d == 0: candidate = run = 0;  d == candidate: run += 1;  else candidate = d, run = 1;
+ *                   candidate and run >= hits: down = candidate, miss_run = 0, ring[events % 32] = (down, b - run + 1, -1), events += 1
+ *     a key down:   d == down: miss_run = 0;  else miss_run += 1, and at miss_run >= misses the newest event's end_block =
+ *                   b - miss_run + 1 and down = candidate = run = miss_run = 0
+ *     blocks += 1;  decided[s * out_pitch + j] = d, pressed[s * out_pitch + j] = down for the j-th block the launch completed
+ * coef row s is c_0 .. c_7 = fp32(2 cos(2 pi f_k / rate)), computed by the caller; fparams row s (emin, rel, max_col_over_row,
+ * max_row_over_col, g); iparams row s (hits, misses).  The bytes behind the blocks a row completed are not written.  n_new[s] == 0
+ * is an idle slot: neither its rows nor its parameters are looked at; when every slot is idle the call returns DMEL_OK and launches
+ * nothing.  NaN input is outside the contract.  DMEL_EINVAL, nothing launched, dmel_last_error naming the item: S outside
+ * [1, 65535], a NULL pointer, samples, state or table not 4-byte aligned, a negative stride or pitch, n_new[s] or first[s] outside
+ * [0, 2^30), N[s] outside [32, 4096], out_pitch below ceil(n_new[s] / N[s]) (the blocks the item can complete with N - 1 samples
+ * carried), a coefficient outside [-2, 2], a value of fparams that is not finite and positive, hits or misses outside [1, 2^20].
+ * first, n_new, N, coef, fparams, iparams are HOST tables, copied as launch arguments into table_scratch (20 S 4-byte words of device
+ * memory, 4-byte aligned): the caller may overwrite them as soon as the call returns.  One workgroup of four waves per slot; nine
+ * lanes serve a block (eight filters and the energy), a wave seven blocks, a pass 28; the samples pass through LDS in chunks of 64
+ * per block.  Plain vector stores, no atomics. */
+int dmel_dtmf_items(const float* samples, int64_t row_stride, int S, const int64_t* first, const int64_t* n_new, const int32_t* N,
+                    const float* coef /* S x 8 */, const float* fparams /* S x 5 */, const int32_t* iparams /* S x 2 */,
+                    void* state /* (S, 128) words */, uint8_t* decided, uint8_t* pressed, int64_t out_pitch, void* table_scratch,
+                    void* stream);
+
 /* R independent 2-D copies of 4-byte words in ONE launch (csrc/small_ops.hip): what takes the streaming state of live sessions out of
  * a pool's buffers into a snapshot and back (models/stream_sessions.py: snapshot / restore).  Descriptor r copies rows[r] rows of
  * cols[r] words: row i goes from src[r] + i * src_pitch[r] to dst[r] + i * dst_pitch[r], pitches in words.  Packing reads windows of

@@ -587,6 +587,43 @@ int main() {
       NF[0] = NF[2] = 0;                          // every item idle
       CK(scan());
     }
+    {
+      // the DTMF detector: tables of exactly S entries (8 S coefficients, 5 S and 2 S parameters), a table scratch of exactly 20 S words;
+      // its refusals read the host tables only
+      const int W = 9000;
+      auto smp = buf(3 * W), st = buf(3 * 128);
+      std::vector<uint8_t> dec(3 * 90), prs(3 * 90);
+      int64_t FI[3] = {5, -7, 1}, NN[3] = {8995, 0, 32 * 90};
+      int32_t BL[3] = {102, -1, 32};                  // the idle item's parameters are not looked at
+      float CO[24], FP[15] = {1.02e-4f, 6.f, 2.51f, 6.31f, 25.5f, NAN, NAN, NAN, NAN, NAN, 3.2e-5f, 6.f, 2.51f, 6.31f, 8.f};
+      for (int k = 0; k < 24; ++k) CO[k] = (k >= 8 && k < 16) ? NAN : 2.f - 0.5f * (float)(k % 8);
+      int32_t IP[6] = {2, 2, -9, -9, 1, 1 << 20};
+      std::vector<uint32_t> tab(20 * 3);
+      int S = 3;
+      int64_t pitch = 90;
+      auto scan = [&]() { return dmel_dtmf_items(smp.data(), W, S, FI, NN, BL, CO, FP, IP, st.data(), dec.data(), prs.data(), pitch, tab.data(), nullptr); };
+      CK(scan());
+      auto refused = [&](const char* item, const char* what) {
+        const int rc = scan();
+        if (rc != DMEL_EINVAL || !std::strstr(dmel_last_error(), item)) { std::printf("FAIL dtmf_items accepted %s (%d: %s)\n", what, rc, dmel_last_error()); ++failures; }
+      };
+      S = 0; refused("0 items", "no item");
+      S = 65536; refused("65536 items", "more than 65535 items");
+      S = 3; NN[2] = -1; refused("item 2", "a negative sample count");
+      NN[2] = 32 * 90 + 1; refused("item 2", "more blocks than the output pitch");
+      NN[2] = 32 * 90; FI[0] = -1; refused("item 0", "a negative first column");
+      FI[0] = 5; BL[2] = 31; refused("item 2", "a block of 31 samples");
+      BL[2] = 32; BL[0] = 4097; refused("item 0", "a block of 4097 samples");
+      BL[0] = 102; CO[17] = 2.5f; refused("item 2", "a coefficient above 2");
+      CO[17] = 1.5f; FP[0] = 0.f; refused("item 0", "emin = 0");
+      FP[0] = 1.02e-4f; FP[11] = INFINITY; refused("item 2", "a rel that is not finite");
+      FP[11] = 6.f; FP[14] = -8.f; refused("item 2", "a negative g");
+      FP[14] = 8.f; IP[0] = 0; refused("item 0", "hits = 0");
+      IP[0] = 2; IP[5] = (1 << 20) + 1; refused("item 2", "misses above 2^20");
+      IP[5] = 1 << 20;
+      NN[0] = NN[2] = 0;                          // every item idle
+      CK(scan());
+    }
     auto xs = buf(2 * 8 * 3000), ys = buf(2 * 8 * 3000), da = buf(8), db = buf(8);
     CK(dmel_aa_snake_f32(xs.data(), ys.data(), al.data(), be.data(), taps.data(), taps.data(), 1, 2, 8, 3000, nullptr));
     CK(dmel_aa_snake_backward_f32(xs.data(), ys.data(), xs.data(), al.data(), be.data(), da.data(), db.data(), taps.data(), taps.data(), 1, 2, 8, 3000, nullptr));

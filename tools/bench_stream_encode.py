@@ -67,7 +67,13 @@ S staggered sessions with voice detection (a pool built with voice=True, every s
 sessions in a pool without the option: the same audio (noise with a harmonic burst in every third push), the same pushes, equal ids,
 interleaved in one process; then the launches of a step of each pool from the library's profile counters -- what is held is that
 the pool without the option launches what it did and the pool with it exactly one kernel more per step that has frames.  Run the
-plain --sessions form on the parent commit for the step time before the option existed.  APPENDS its table to --out."""
+plain --sessions form on the parent commit for the step time before the option existed.  APPENDS its table to --out.
+
+    python tools/bench_stream_encode.py --sessions 16 --dtmf [--label NAME] [--out profiles/sessions_dtmf.txt]
+
+The same comparison for DTMF detection (a pool built with dtmf=True, every session opened with dtmf=True; the audio is noise with a
+keypad tone pair in every third push): equal ids, and exactly one "dtmf" / one "small" launch record more per step and nothing
+else.  No bound on the added time is set; the table shows it next to the plain pool of the same run.  APPENDS its table to --out."""
 import argparse, json, os, statistics, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -88,6 +94,7 @@ ap.add_argument("--channels", type=int, default=1, help="with --sessions: sessio
 ap.add_argument("--ragged", action="store_true", help="with --sessions: another push size per session and step (seeded), chunk / 2 .. chunk")
 ap.add_argument("--park", action="store_true", help="with --sessions: snapshot + restore of all sessions, one launch against torch slices")
 ap.add_argument("--voice", action="store_true", help="with --sessions: sessions with voice detection against the same pool without it")
+ap.add_argument("--dtmf", action="store_true", help="with --sessions: sessions with DTMF detection against the same pool without it")
 ap.add_argument("--label", default="", help="with --sessions: names the table (the commit measured)")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
@@ -97,6 +104,7 @@ if args.out is None:
     args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                             "sessions_park.txt" if args.sessions and args.park else
                             "sessions_voice.txt" if args.sessions and args.voice else
+                            "sessions_dtmf.txt" if args.sessions and args.dtmf else
                             "sessions_channels.txt" if args.sessions and args.channels > 1 else
                             "sessions_pcm.txt" if args.sessions and args.sample_format == "s16" else
                             "sessions_g711.txt" if args.sessions and args.sample_format != "f32" else
@@ -242,18 +250,21 @@ def sessions_section():
     print(json.dumps(r))
 
 
-def sessions_voice_section():
-    """S staggered sessions with voice detection against the same sessions in a pool without the option; the same audio, the same
-    pushes, equal ids; then the launches per step of both pools"""
+def sessions_detector_section(opt):
+    """S staggered sessions with a detector (opt: "voice" or "dtmf") against the same sessions in a pool without the option; the same
+    audio, the same pushes, equal ids; then the launches per step of both pools"""
     import math
     from dmel_codec_amd import _lib
     S, n = args.sessions, args.chunk
     t = torch.arange((args.pushes + 5) * n, device=dev, dtype=torch.float64) / SR
-    tone = (sum(torch.sin(2 * math.pi * 150 * k * t) / k for k in range(1, 21)) * 0.1).float()
+    if opt == "voice":
+        tone = (sum(torch.sin(2 * math.pi * 150 * k * t) / k for k in range(1, 21)) * 0.1).float()
+    else:                                                                       # the key "5": 770 Hz and 1336 Hz
+        tone = ((torch.sin(2 * math.pi * 770 * t) + torch.sin(2 * math.pi * 1336 * t)) * 0.1).float()
     talk = ((torch.arange(t.shape[0], device=dev) // n) % 3 == 0).float()       # a burst in every third push
     audio = torch.randn(S, t.shape[0], device=dev) * 0.01 + tone * talk
-    pools = {"plain": codec.encode_sessions(slots=S, max_push_samples=n), "voice": codec.encode_sessions(slots=S, max_push_samples=n, voice=True)}
-    slots = {k: [p.open(voice=True if k == "voice" else None) for _ in range(S)] for k, p in pools.items()}
+    pools = {"plain": codec.encode_sessions(slots=S, max_push_samples=n), opt: codec.encode_sessions(slots=S, max_push_samples=n, **{opt: True})}
+    slots = {k: [p.open(**({opt: True} if k == opt else {})) for _ in range(S)] for k, p in pools.items()}
     first = [n * (1 + s % 3) // 3 for s in range(S)]            # the starts differ by a third of a push
     pos, ms, same = [0] * S, {k: [] for k in pools}, True
 
@@ -269,16 +280,16 @@ def sessions_voice_section():
 
     for i in range(args.pushes):
         chunks, got = chunks_of(first if i == 0 else [n] * S), {}
-        for k in (("plain", "voice") if i % 2 == 0 else ("voice", "plain")):          # neither always goes first
+        for k in (("plain", opt) if i % 2 == 0 else (opt, "plain")):                  # neither always goes first
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             got[k] = step(k, chunks)
             torch.cuda.synchronize()
             if i >= args.warmup:
                 ms[k].append((time.perf_counter() - t0) * 1e3)
-        same = same and all(torch.equal(a, b) for a, b in zip(got["plain"], got["voice"]))
+        same = same and all(torch.equal(a, b) for a, b in zip(got["plain"], got[opt]))
     # the launches of a step, from the profile counters (their events cost time: counted behind the timed steps)
-    families, launches = ("voice", "small", "stft_logmel", "conv_igemm"), {}
+    families, launches = ("voice", "dtmf", "small", "stft_logmel", "conv_igemm"), {}
     counted = [chunks_of([n] * S) for _ in range(4)]
     _lib.prof_enable(True)
     for k in pools:
@@ -290,30 +301,36 @@ def sessions_voice_section():
             launches[k].append({f: _lib.prof_read(f)["launches"] for f in families})
     _lib.prof_enable(False)
     _lib.prof_reset()
-    reports = pools["voice"].voice()
+    reports = getattr(pools[opt], opt)()
     for k, p in pools.items():
         for s in slots[k]:
             p.close(s)
-    held = all(a["voice"] == 0 and b["voice"] == 1 and b["small"] == a["small"] + 1 and b["stft_logmel"] == a["stft_logmel"]
-               and b["conv_igemm"] == a["conv_igemm"] for a, b in zip(launches["plain"], launches["voice"]))
+    held = all(a[opt] == 0 and b[opt] == 1 and b["small"] == a["small"] + 1 and all(b[f] == a[f] for f in families if f not in (opt, "small"))
+               for a, b in zip(launches["plain"], launches[opt]))
     r = {"sessions": S, "chunk_s": n / SR, "pushes": args.pushes, "warmup": args.warmup, "ids_equal": bool(same), "label": args.label,
-         "launches_per_step": {k: launches[k][0] for k in pools}, "one_more_launch_per_step": bool(held),
-         "speech_starts": sorted({rep.starts for rep in reports.values()}), "frames": sorted({rep.frames for rep in reports.values()})}
+         "launches_per_step": {k: launches[k][0] for k in pools}, "one_more_launch_per_step": bool(held)}
+    if opt == "voice":
+        r.update(speech_starts=sorted({rep.starts for rep in reports.values()}), frames=sorted({rep.frames for rep in reports.values()}))
+        saw = f"the sessions saw {r['frames']} frames and {r['speech_starts']} speech starts each (a burst in every third push)"
+    else:
+        r.update(keys=sorted({rep.digits[-4:] for rep in reports.values()}), events=sorted({rep.total for rep in reports.values()}),
+                 blocks=sorted({rep.blocks for rep in reports.values()}))
+        saw = f"the sessions saw {r['blocks']} blocks and {r['events']} key events each, the last of them {r['keys']} (key 5 in every third push)"
     rows = []
     for k, v in ms.items():
         med = statistics.median(v)
         r[k] = {"median_ms": round(med, 3), "p10_ms": round(pct(v, 0.1), 3), "p90_ms": round(pct(v, 0.9), 3), "n": len(v)}
         rows.append(f"{S:8d}  {k:6s}  {med:9.3f}  {pct(v, 0.1):9.3f}  {pct(v, 0.9):9.3f}  {len(v):4d}  " +
                     "  ".join(f"{f} {launches[k][0][f]}" for f in families))
-    r["added_median_ms"] = round(r["voice"]["median_ms"] - r["plain"]["median_ms"], 3)
+    r["added_median_ms"] = round(r[opt]["median_ms"] - r["plain"]["median_ms"], 3)
     rows.append(f"{S:8d}  detection adds {r['added_median_ms']:.3f} ms to the median step; ids equal: {same}; the pool without the option "
                 f"launches no detector and the pool with it exactly one kernel more per step: {held}")
-    rows.append(f"{S:8d}  the sessions saw {r['frames']} frames and {r['speech_starts']} speech starts each (a burst in every third push)")
-    table = [(f"[{args.label}] " if args.label else "") + f"encode sessions with voice detection, 0.32 s pushes of 24 kHz audio, starts staggered by a "
-             f"third of a push, 80 mel / 8 groups / 70 channels / 20 layers (tools/bench_stream_encode.py --sessions {S} --voice)",
+    rows.append(f"{S:8d}  {saw}")
+    table = [(f"[{args.label}] " if args.label else "") + f"encode sessions with {opt} detection, 0.32 s pushes of 24 kHz audio, starts staggered by a "
+             f"third of a push, 80 mel / 8 groups / 70 channels / 20 layers (tools/bench_stream_encode.py --sessions {S} --{opt})",
              f"wall time of one step (one push for every stream) incl. host synchronisation, {args.pushes - args.warmup} steady-state steps, the two "
              "pools interleaved in one process;",
-             "plain = encode_sessions(S), voice = encode_sessions(S, voice=True) with every session opened with voice=True; launches: records "
+             f"plain = encode_sessions(S), {opt} = encode_sessions(S, {opt}=True) with every session opened with {opt}=True; launches: records "
              "of the profile counters in one step",
              "sessions  pool    median ms     p10 ms     p90 ms     n  launches of one step"] + rows
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
@@ -556,8 +573,10 @@ if args.park and not args.sessions:
     ap.error("--park needs --sessions")
 if args.voice and not args.sessions:
     ap.error("--voice needs --sessions")
-if args.sessions and args.voice:
-    sessions_voice_section()
+if args.dtmf and not args.sessions:
+    ap.error("--dtmf needs --sessions")
+if args.sessions and (args.voice or args.dtmf):
+    sessions_detector_section("voice" if args.voice else "dtmf")
     sys.exit(0)
 if args.sessions and args.park:
     sessions_park_section()
