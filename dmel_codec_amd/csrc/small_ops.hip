@@ -1844,3 +1844,180 @@ extern "C" int dmel_dtmf_items(const float* samples, int64_t row_stride, int S, 
   DMEL_HIP(hipGetLastError());
   return DMEL_OK;
 }
+
+namespace dmel {
+
+// ---- tones spliced into codec-rate audio (include/dmel_hip.h: dmel_tone_items; the rule: utils/tones.py) -----------------------------
+// The table holds R part rows of (dst, src, n, first tile, first segment record, segments), six int64, and behind them the launch's
+// segment records of five int64: the eight 4-byte words of the entry's table (f1, f2, a1, a2, on, off, ramp, ramp_off) and the
+// segment's first sample inside its part -- the part's prefix sums (one record per segment: the entry refuses a segment that two
+// parts would begin at different samples).  A workgroup owns one tile of kToneTile floats of the part that
+// owns tile blockIdx.x: the last one whose first tile is not behind it, as in stream_pack_kernel (an idle part owns no tile).  Tiles
+// are laid on the 16-byte grid of the DESTINATION: a lane owns the four floats of one aligned 16 bytes, so that every lane but the
+// two that meet the ends of a part stores one float4, whatever the offset of dst; those two store their floats one by one.  A copy
+// part loads a float4 where the source shares the destination's offset and single words else; words move as uint32.  A tone part
+// finds the segment of its first sample by bisection over the records' first samples and steps on from there.  The four operations
+// of a sample are rounded one by one (fp contract(off) in tone_sample, as in fade_blend above).  No LDS, no atomics.
+constexpr int kTonePartWords = 6, kToneSegWords = 5, kToneTile = 1024, kToneMaxSegs = 64, kToneMaxRamp = 4096;
+__device__ __forceinline__ float tone_sample(float a1, float s1, float a2, float s2, float g) {
+#pragma clang fp contract(off)
+  const float t1 = a1 * s1;
+  const float t2 = a2 * s2;
+  const float x = t1 + t2;
+  return x * g;
+}
+__global__ __launch_bounds__(256) void tone_kernel(const int64_t* __restrict__ tab, int R, const float* __restrict__ sine, int rate,
+                                                   const float* __restrict__ ramps) {
+  const int64_t tile = blockIdx.x;
+  int a = 0, b = R - 1;
+  while (a < b) {
+    const int mid = (a + b + 1) >> 1;
+    if (tab[(size_t)mid * kTonePartWords + 3] <= tile) a = mid;
+    else b = mid - 1;
+  }
+  const int64_t* row = tab + (size_t)a * kTonePartWords;
+  uint32_t* dst = reinterpret_cast<uint32_t*>(row[0]);
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(row[1]);
+  const int64_t n = row[2], local = tile - row[3];
+  if (n <= 0 || local < 0) return;
+  const int shift = (int)((row[0] >> 2) & 3);                                // floats of dst past a 16-byte boundary
+  const int64_t e = local * kToneTile + 4 * (int64_t)threadIdx.x - shift;    // dst + e is 16-byte aligned
+  if (e >= n || e + 4 <= 0) return;
+  const bool whole = e >= 0 && e + 4 <= n;
+  uint32_t v[4] = {0u, 0u, 0u, 0u};
+  if (src) {
+    if (whole && (reinterpret_cast<uintptr_t>(src + e) & 15) == 0) {
+      const uint4 q = *reinterpret_cast<const uint4*>(src + e);
+      v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (e + j >= 0 && e + j < n) v[j] = src[e + j];
+    }
+  } else {
+    const int64_t* segs = tab + (size_t)R * kTonePartWords + (size_t)row[4] * kToneSegWords;
+    const int count = (int)row[5];
+    const int64_t lo = e < 0 ? 0 : e;
+    int k = 0, kb = count - 1;
+    while (k < kb) {
+      const int mid = (k + kb + 1) >> 1;
+      if (segs[(size_t)mid * kToneSegWords + 4] <= lo) k = mid;
+      else kb = mid - 1;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int64_t t = e + j;
+      if (t < 0 || t >= n) continue;
+      while (k + 1 < count && segs[(size_t)(k + 1) * kToneSegWords + 4] <= t) ++k;
+      const int32_t* w = reinterpret_cast<const int32_t*>(segs + (size_t)k * kToneSegWords);
+      const int64_t i = t - segs[(size_t)k * kToneSegWords + 4];
+      const int on = w[4], ramp = w[6];
+      float y = 0.0f;                                                       // the gap behind the sound
+      if (i < on) {
+        const uint32_t p1 = (uint32_t)(((uint64_t)(uint32_t)w[0] * (uint64_t)i) % (uint64_t)rate);
+        const uint32_t p2 = (uint32_t)(((uint64_t)(uint32_t)w[1] * (uint64_t)i) % (uint64_t)rate);
+        float g = 1.0f;
+        if (i < ramp) g = ramps[(int64_t)w[7] + i];
+        else if (i >= on - ramp) g = ramps[(int64_t)w[7] + (on - 1 - i)];
+        y = tone_sample(__int_as_float(w[2]), sine[p1], __int_as_float(w[3]), sine[p2], g);
+      }
+      v[j] = __float_as_uint(y);
+    }
+  }
+  if (whole) {
+    *reinterpret_cast<uint4*>(dst + e) = make_uint4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (e + j >= 0 && e + j < n) dst[e + j] = v[j];
+  }
+}
+
+}  // namespace dmel
+
+extern "C" int dmel_tone_items(float* const* dst, const float* const* src, const int64_t* n, const int32_t* seg_first,
+                               const int32_t* seg_count, int R, const int32_t* segs, int n_segs, const float* sine, int rate,
+                               const float* ramps, int64_t ramp_floats, void* table_scratch, void* stream) {
+  using namespace dmel;
+  DMEL_CHECK_ARG(dst && src && n && seg_first && seg_count && sine && table_scratch, "tone_items: NULL argument");
+  DMEL_CHECK_ARG(R >= 1 && R <= 65535, "tone_items: %d parts, expected 1 .. 65535", R);
+  DMEL_CHECK_ARG(n_segs >= 0 && n_segs <= kToneMaxSegs * 65535 && (segs || n_segs == 0),
+                 "tone_items: a segment table of %d segments (NULL: %d), expected 0 .. %d", n_segs, (int)!segs, kToneMaxSegs * 65535);
+  DMEL_CHECK_ARG(rate >= 4000 && rate <= 192000, "tone_items: a rate of %d Hz, expected 4000 .. 192000", rate);
+  DMEL_CHECK_ARG(ramp_floats >= 0 && (ramps || ramp_floats == 0), "tone_items: a ramp arena of %lld floats (NULL: %d)",
+                 (long long)ramp_floats, (int)!ramps);
+  DMEL_CHECK_ARG(((uintptr_t)table_scratch & 7) == 0, "tone_items: table_scratch is not 8-byte aligned");
+  DMEL_CHECK_ARG((((uintptr_t)sine | (uintptr_t)ramps) & 3) == 0, "tone_items: sine or ramps is not 4-byte aligned");
+  std::vector<int64_t> tab((size_t)kTonePartWords * R + (size_t)kToneSegWords * n_segs);
+  int64_t* rec = tab.data() + (size_t)kTonePartWords * R;
+  std::vector<int64_t> claimed((size_t)n_segs, -1);   // the first sample a part has given the segment's record (-1: none has)
+  const int64_t limit = (int64_t)1 << 40;
+  int64_t tiles = 0;
+  double bytes = 0.0;
+  for (int r = 0; r < R; ++r) {
+    DMEL_CHECK_ARG(n[r] >= 0 && n[r] < limit, "tone_items: part %d: %lld samples, expected 0 .. 2^40 - 1", r, (long long)n[r]);
+    int64_t* it = tab.data() + (size_t)kTonePartWords * r;
+    it[3] = tiles;
+    if (n[r] == 0) continue;                            // idle: its pointers and segments are not looked at (the table row stays 0)
+    DMEL_CHECK_ARG(dst[r], "tone_items: part %d: NULL destination", r);
+    DMEL_CHECK_ARG((((uintptr_t)dst[r] | (uintptr_t)src[r]) & 3) == 0, "tone_items: part %d: a pointer is not 4-byte aligned", r);
+    it[0] = (int64_t)(uintptr_t)dst[r]; it[1] = (int64_t)(uintptr_t)src[r]; it[2] = n[r];
+    if (!src[r]) {
+      const int first = seg_first[r], count = seg_count[r];
+      DMEL_CHECK_ARG(count >= 1 && count <= kToneMaxSegs && first >= 0 && first <= n_segs - count,
+                     "tone_items: part %d: segments [%d, %d + %d) of a table of %d, expected 1 .. %d segments inside it", r, first, first,
+                     count, n_segs, kToneMaxSegs);
+      int64_t at = 0;
+      for (int k = first; k < first + count; ++k) {
+        const int32_t* w = segs + (size_t)8 * k;
+        float amp[2];
+        std::memcpy(amp, w + 2, sizeof(amp));
+        for (int j = 0; j < 2; ++j) {
+          DMEL_CHECK_ARG(w[j] >= 0 && 2 * (int64_t)w[j] < rate, "tone_items: part %d: segment %d: f%d = %d Hz, expected 0 <= f < %d / 2", r,
+                         k, j + 1, w[j], rate);
+          DMEL_CHECK_ARG(std::isfinite(amp[j]) && amp[j] >= 0.0f && (w[j] != 0 || amp[j] == 0.0f),
+                         "tone_items: part %d: segment %d: amplitude a%d = %g is not finite and >= 0, or not 0 with f%d = 0", r, k, j + 1,
+                         (double)amp[j], j + 1);
+        }
+        DMEL_CHECK_ARG((double)amp[0] + (double)amp[1] <= 1.0, "tone_items: part %d: segment %d: amplitudes %g + %g exceed 1", r, k,
+                       (double)amp[0], (double)amp[1]);
+        const int on = w[4], off = w[5], ramp = w[6], ramp_off = w[7];
+        DMEL_CHECK_ARG(on >= 1 && on < (1 << 24) && off >= 0 && off < (1 << 24),
+                       "tone_items: part %d: segment %d: on = %d, off = %d, expected 1 <= on < 2^24 and 0 <= off < 2^24", r, k, on, off);
+        DMEL_CHECK_ARG(ramp >= 0 && ramp <= on / 2 && ramp <= kToneMaxRamp,
+                       "tone_items: part %d: segment %d: ramp = %d, expected 0 .. min(on / 2, %d)", r, k, ramp, kToneMaxRamp);
+        DMEL_CHECK_ARG(ramp == 0 || (ramp_off >= 0 && (int64_t)ramp_off + ramp <= ramp_floats),
+                       "tone_items: part %d: segment %d: ramp table [%d, %d + %d) lies beyond the arena of %lld floats", r, k, ramp_off,
+                       ramp_off, ramp, (long long)ramp_floats);
+        // one record per segment of the table: parts may share segments only where each segment begins at the same sample in both
+        DMEL_CHECK_ARG(claimed[k] < 0 || claimed[k] == at,
+                       "tone_items: part %d: segment %d begins at sample %lld of this part and at sample %lld of an earlier one: parts "
+                       "may share a segment only at one offset", r, k, (long long)at, (long long)claimed[k]);
+        claimed[k] = at;
+        int64_t* q = rec + (size_t)kToneSegWords * k;
+        std::memcpy(q, w, 8 * sizeof(int32_t));
+        q[4] = at;
+        at += (int64_t)on + off;
+      }
+      DMEL_CHECK_ARG(at == n[r], "tone_items: part %d: its %d segments are %lld samples long, the part %lld: a length mismatch", r, count,
+                     (long long)at, (long long)n[r]);
+      it[4] = first; it[5] = count;
+      bytes += 4.0 * (double)n[r];
+    } else {
+      bytes += 8.0 * (double)n[r];
+    }
+    const int64_t shift = (int64_t)(((uintptr_t)dst[r] >> 2) & 3);
+    tiles += (n[r] + shift + kToneTile - 1) / kToneTile;
+    DMEL_CHECK_ARG(tiles <= 0x7fffffff, "tone_items: part %d: more than 2^31 - 1 tiles", r);
+  }
+  if (tiles == 0) return DMEL_OK;                       // every part idle
+  hipStream_t s = (hipStream_t)stream;
+  DMEL_TRY(launch_table_put(tab.data(), tab.size() * sizeof(int64_t), table_scratch, s));
+  {
+    // "small" carries the time and the bytes; the second scope only counts: one record per tone launch (dmel_prof_read("tones"))
+    ProfScope ps("small", s, 0.0, bytes), count("tones", s, 0.0, 0.0);
+    hipLaunchKernelGGL(tone_kernel, dim3((unsigned)tiles), dim3(256), 0, s, static_cast<const int64_t*>(table_scratch), R, sine, rate, ramps);
+  }
+  DMEL_HIP(hipGetLastError());
+  return DMEL_OK;
+}

@@ -502,7 +502,10 @@ class VQGAN(nn.Module):
         the whole sequence); such a pool holds a shadow row per slot, and sessions opened without a look-ahead stay exact in it.
         crossfade_samples=Fmax with it: pool.open(lookahead_frames=k, crossfade_samples=F) starts a reply whose pieces join without a
         step (the last F samples of a piece wait and are cross-faded into the next decode: utils/crossfade.py);
-        pool.set_lookahead(slot, k) moves a live reply's look-ahead.
+        pool.set_lookahead(slot, k) moves a live reply's look-ahead.  tones=True (max_tone_samples=: two seconds at the vocoder's
+        rate by default): pool.send_dtmf(slot, "42#") and pool.send_tones(slot, program) queue DTMF keys, beeps or call-progress
+        tones (utils/tones.py) at a mel frame of a reply; the step in which its speech reaches that frame splices them in for all
+        slots with one launch, in front of the reply's resampler and wire convert.
         See models/stream_sessions.py: DecodeSessions."""
         from .stream_sessions import DecodeSessions
         return DecodeSessions(self, slots, max_push_tokens, return_audios, **options)

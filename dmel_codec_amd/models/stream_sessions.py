@@ -21,8 +21,9 @@ import torch
 from .. import _lib
 from ..utils import crossfade, pcm
 from ..utils import dtmf as dtmf_rule
+from ..utils import tones as tone_rule
 from ..utils import voice as voice_rule
-from .stream_park import ParkingPool
+from .stream_park import ParkingPool, plain
 from .stream_schedule import (DecodeGeometry, DecodeSchedule, EarlyDecodeSchedule, EncodeGeometry, EncodeSchedule, decode_capacity,
                               decode_live_window, decode_rebase, encode_live_window, encode_need_from, resample_max_outputs, session_rows)
 
@@ -758,6 +759,27 @@ class DecodeSessions(ParkingPool):
     return_audios=False pool, a window or tail that does not fit, an unknown format version.  Equal weights are the caller's
     contract (models/stream_park.py).
 
+    A reply on a phone line also presses keys and plays tones: a pool built with tones=True (and audio) serves
+    send_dtmf(slot, "42#") and send_tones(slot, program), which queue a program of tone segments (utils/tones.py: the rule, the
+    tables and the host reference the pool is tested against bit for bit) at a mel frame of the session -- at_frame=None: behind
+    everything received so far -- and make no device call but the upload of a ramp table of a new length.  With P = at_frame * up
+    and [h0, h1) the codec-rate speech samples the slot hands out in a step (`handed` counts them: emitted * up, less the fade tail
+    that waits), every request with P <= h1 leaves in that step, and every request in the slot's last one; a push of no tokens
+    serves what is due.  ONE dmel_tone_items launch composes speech[h0:P1] | tone 1 | speech[P1:P2] | ... for all such slots,
+    straight where each slot's route reads it: behind its resampler tail (destinations() / push(placed=True); the launch then
+    places the step's other resampled pieces too, since a push is placed as a whole), in its row of a staging buffer the convert
+    launch reads, or in a fresh tensor that is handed out in place of the clone.  So a session's audio is, bit for bit, its wire
+    chain (resample, format, channels) applied to tones.splice(its codec-rate stream, [(P, program), ...]), however the tokens were
+    cut into pushes.  Mel pieces and frames_emitted do not change; a step that serves no request launches, allocates and returns
+    what it did; a pool built without tones=True is what it was and refuses send_*.  Refused with ValueError, nothing queued: a
+    frequency at or above half the session's output rate, an anchor outside [frames_emitted, frames received] or before an earlier
+    request's, more than max_tone_samples (default: two seconds at the vocoder's rate) pending samples or 64 pending segments in the
+    slot.  tones_pending(slot) -> [(at_frame, samples)].  The queue travels with snapshot / restore as plain values (meta keys
+    tones, handed, tone_samples; a pool without tones=True refuses a snapshot with pending requests, a tone pool one above its
+    max_tone_samples; snapshots without the keys restore with none); drop discards it.  The resampler's rows are sized for
+    cap * up + max_tone_samples.  Not served: RFC 4733 telephone-events, tones mixed over speech, non-integer frequencies, tones in
+    the mel; no ITU-T Q.23 / Q.24 conformance is claimed.
+
     Out of scope, NotImplementedError: overlap_vocoder, graph_chunk_tokens, and a pool-wide output_sample_rate (a pool has no rate of
     its own).
 
@@ -768,7 +790,8 @@ class DecodeSessions(ParkingPool):
 
     def __init__(self, codec, slots: int, max_push_tokens: int = 64, return_audios: bool = True, overlap_vocoder: bool = False,
                  graph_chunk_tokens: Optional[int] = None, output_sample_rate: Optional[int] = None,
-                 output_sample_rates: Iterable[int] = (), early_emit: bool = False, crossfade_samples: int = 0):
+                 output_sample_rates: Iterable[int] = (), early_emit: bool = False, crossfade_samples: int = 0, tones: bool = False,
+                 max_tone_samples: Optional[int] = None):
         if overlap_vocoder or graph_chunk_tokens is not None or output_sample_rate is not None:
             raise NotImplementedError("decode sessions launch everything on the current stream, eagerly, and have no rate of their own: "
                                       "overlap_vocoder, graph_chunk_tokens and output_sample_rate belong to StreamingDecoder (a session's "
@@ -811,8 +834,29 @@ class DecodeSessions(ParkingPool):
         self.noise_width = (H + self.max_push) * f        # frames [z_valid, tokens * factor): at most H tokens of them in front of a push
         self.voc_rate = int(codec.vocoder.h.get("sampling_rate", codec.encode_mel_transform.sample_rate)) if return_audios else None
         self.output_sample_rates = tuple(sorted(set(output_sample_rates) - {self.voc_rate}))      # none without audio (refused above)
-        # a step emits frames that all lie in the slot's `cap` columns: at most cap * up samples reach a slot's resampler at once
-        self._init_slots(self.voc_rate, "output_sample_rates", self.cap * self.up)
+        # the pool sends tones (send_dtmf / send_tones): at most max_tone samples of them wait in a slot, and leave in one step
+        if not isinstance(tones, bool):
+            raise ValueError(f"tones must be a bool, got {tones!r}")
+        self.tones_on, self.max_tone = tones, 0
+        if tones:
+            if not return_audios:
+                raise ValueError("tones without audio: return_audios=False leaves nothing to splice them into")
+            tone_rule.check_rate(self.voc_rate)
+            self.max_tone = 2 * self.voc_rate if max_tone_samples is None else max_tone_samples
+            if isinstance(self.max_tone, bool) or not isinstance(self.max_tone, int) or self.max_tone < 1:
+                raise ValueError(f"max_tone_samples must be a positive integer (samples at the vocoder's rate), got {max_tone_samples!r}")
+        elif max_tone_samples is not None:
+            raise ValueError("max_tone_samples on a pool built without tones=True")
+        # a step emits frames that all lie in the slot's `cap` columns: at most cap * up samples, and the tones that waited, reach a
+        # slot's resampler at once
+        self._init_slots(self.voc_rate, "output_sample_rates", self.cap * self.up + self.max_tone)
+        self.tq: List[list] = [[] for _ in range(self.S)]     # the slot's pending requests, (P, program) in the order they leave
+        self.handed = [0] * self.S                        # speech samples at the vocoder's rate the slot has handed out
+        self.tone_samples = [0] * self.S                  # samples its pending requests render to
+        self._ramp_off: Dict[int, int] = {}               # ramp length -> offset of its table in the pool's ramp arena
+        self._ramp_floats = 0
+        self._held: Dict[int, torch.Tensor] = {}          # the float pieces of the step that tones are spliced into
+        self._ending: set = set()
         self.fade = [0] * self.S                          # the slot's cross-fade in samples (0: none)
         self.has_tail = [False] * self.S                  # the slot holds back the last `fade` samples of its newest piece
         self.tok_origin = [0] * self.S                    # absolute index of the token in column 0 of the slot's token tail
@@ -857,7 +901,82 @@ class DecodeSessions(ParkingPool):
         self._occupy(s, sched, 0, rate, sample_format, channels)
         self.tok_origin[s] = self.n_noise[s] = 0
         self.fade[s], self.has_tail[s] = crossfade_samples, False
+        self.tq[s], self.handed[s], self.tone_samples[s] = [], 0, 0
         return s
+
+    # -- tones: DTMF keys, beeps and call-progress tones spliced into a session's audio (utils/tones.py) -----------------------
+    def send_dtmf(self, slot: int, keys: str, *, tone_ms=80, gap_ms=80, level_dbfs=-10.0, twist_db=2.0, ramp_ms=1.0,
+                  at_frame: Optional[int] = None) -> int:
+        """queue the DTMF keys `keys` (tones.dtmf_program at the vocoder's rate) for the slot: send_tones of that program"""
+        if not self.tones_on:
+            raise ValueError("send_dtmf on a pool built without tones=True: it has no tone tables")
+        return self.send_tones(slot, tone_rule.dtmf_program(keys, self.voc_rate, tone_ms, gap_ms, level_dbfs, twist_db, ramp_ms), at_frame)
+
+    def send_tones(self, slot: int, program, at_frame: Optional[int] = None) -> int:
+        """queue a program of tone segments (utils/tones.py) for the slot -> the samples at the vocoder's rate it renders to.  The
+        rendering goes in front of speech sample at_frame * up of the session's audio at the vocoder's rate: at_frame=None is
+        "behind everything received so far" (tokens * factor now); an explicit one lies in [frames_emitted(slot), frames received]
+        and not before an earlier pending request's.  The request leaves with the step in which the session's speech reaches
+        that sample (a push of no tokens will do where it already has), or with its last step.  No device call, apart from the
+        upload of a ramp table of a length the pool has not seen.  ValueError, nothing queued: a pool without tones=True, a
+        program outside the bounds of utils/tones.py, a frequency at or above half the session's output rate, an anchor outside
+        those bounds, more than max_tone_samples pending samples or 64 pending segments in the slot."""
+        if not self.tones_on:
+            raise ValueError("send_tones on a pool built without tones=True: it has no tone tables")
+        self._check_open(slot)
+        program = self._check_tones(tone_rule.check_program(program, self.voc_rate), self.rate[slot])
+        sch, f = self.sched[slot], self.geo.factor
+        frames, last = sch.tokens * f, self.tq[slot][-1][0] // self.up if self.tq[slot] else 0
+        if at_frame is None:
+            at_frame = frames
+        elif isinstance(at_frame, bool) or not isinstance(at_frame, int) or not max(sch.emitted, last) <= at_frame <= frames:
+            raise ValueError(f"slot {slot}: at_frame must be an integer in [{max(sch.emitted, last)}, {frames}] (frames emitted or an "
+                             f"earlier request's anchor .. frames received), got {at_frame!r}")
+        n = tone_rule.length(program)
+        if self.tone_samples[slot] + n > self.max_tone:
+            raise ValueError(f"slot {slot}: {self.tone_samples[slot]} pending samples and {n} more exceed max_tone_samples = {self.max_tone}")
+        if sum(len(p) for _, p in self.tq[slot]) + len(program) > tone_rule.MAX_SEGMENTS:
+            raise ValueError(f"slot {slot}: more than {tone_rule.MAX_SEGMENTS} pending segments")
+        self._ramps_for(program)
+        self.tq[slot].append((at_frame * self.up, program))
+        self.tone_samples[slot] += n
+        return n
+
+    def tones_pending(self, slot: int) -> List[Tuple[int, int]]:
+        """[(at_frame, samples at the vocoder's rate)] of the slot's requests that have not left yet, in the order they will"""
+        self._check_open(slot)
+        return [(P // self.up, tone_rule.length(p)) for P, p in self.tq[slot]]
+
+    def _check_tones(self, program, rate):
+        """a checked program against the rate the session's audio leaves at: what the resampler would fold is refused"""
+        rate = self.voc_rate if rate is None else rate
+        for k, seg in enumerate(program):
+            if max(seg[0], seg[1]) * 2 >= rate:
+                raise ValueError(f"segment {k}: {max(seg[0], seg[1])} Hz is not below half of the session's output rate {rate} Hz")
+        return program
+
+    def _ramps_for(self, program) -> None:
+        """every ramp length of the program has its table in the pool's arena: appended, and uploaded where the arena exists"""
+        for seg in program:
+            n = seg[6]
+            if n and n not in self._ramp_off:
+                self._ramp_off[n], self._ramp_floats = self._ramp_floats, self._ramp_floats + n
+                if self.buf is not None:
+                    self._upload_ramps([n])
+
+    def _upload_ramps(self, lengths) -> None:
+        arena = self.buf["tone_ramps"]
+        if arena.numel() < self._ramp_floats:          # grow: the tables keep their offsets
+            grown = torch.zeros(2 * self._ramp_floats, dtype=torch.float32, device=arena.device)
+            grown[:arena.numel()] = arena
+            self.buf["tone_ramps"] = arena = grown
+        for n in lengths:
+            arena[self._ramp_off[n]:self._ramp_off[n] + n] = torch.tensor(tone_rule.ramp_table(n))
+
+    def drop(self, slot: int) -> None:
+        """ParkingPool.drop; the slot's pending tone requests are discarded with it"""
+        super().drop(slot)
+        self.tq[slot], self.tone_samples[slot] = [], 0      # what the session had not sent is gone with it
 
     def set_lookahead(self, slot: int, lookahead_frames: int) -> None:
         """the look-ahead of an open early session from its next push on.  What has left never comes back: raising it pauses the
@@ -910,6 +1029,15 @@ class DecodeSessions(ParkingPool):
             self.buf["fade_tail"] = torch.zeros(S, self.fade_max, dtype=torch.float32, device=dev)
             self.buf["fade_w"] = torch.zeros(S, self.fade_max, dtype=torch.float32, device=dev)
             self.buf["fade_tab"] = torch.empty(5 * S, dtype=torch.int64, device=dev)
+        if self.tones_on:                             # dmel_tone_items: the sine table of the vocoder's rate, the ramp arena, a row per
+            #                                           slot in which the convert launch finds a spliced piece, and the table: a slot
+            #                                           has at most 64 requests (one segment each at least) between 65 cuts of speech
+            most = tone_rule.MAX_SEGMENTS
+            self.buf.update(tone_sine=torch.tensor(tone_rule.sine_table(self.voc_rate)).to(dev),
+                            tone_ramps=torch.zeros(max(2 * self._ramp_floats, 4 * tone_rule.MAX_RAMP), dtype=torch.float32, device=dev),
+                            tone_stage=torch.empty(S, self.cap * self.up + self.max_tone, dtype=torch.float32, device=dev),
+                            tone_tab=torch.empty(tone_rule.table_words(S * (2 * most + 2), S * most), dtype=torch.int64, device=dev))
+            self._upload_ramps(list(self._ramp_off))
 
     def _slot_views(self, s: int):
         b = self.buf
@@ -934,9 +1062,31 @@ class DecodeSessions(ParkingPool):
 
     def _park_meta(self, s: int) -> dict:
         sch = self.sched[s]
-        return dict(super()._park_meta(s), return_audios=self.return_audios, fade=self.fade[s], has_tail=self.has_tail[s],
+        meta = dict(super()._park_meta(s), return_audios=self.return_audios, fade=self.fade[s], has_tail=self.has_tail[s],
                     lookahead=sch.lookahead if isinstance(sch, EarlyDecodeSchedule) else None, tok_origin=self.tok_origin[s],
                     n_noise=self.n_noise[s])
+        if self.tones_on:                             # only a pool that sends tones writes the keys: the others' snapshots are unchanged
+            meta.update(tones=[[P, plain(p)] for P, p in self.tq[s]], handed=self.handed[s], tone_samples=self.tone_samples[s])
+        return meta
+
+    def _park_tones(self, meta: Mapping) -> list:
+        """the pending requests a snapshot carries as [(P, checked program)] (a snapshot without the key: none); ValueError where
+        they are no requests this pool can send"""
+        pend = meta.get("tones") or []
+        if pend and not self.tones_on:
+            raise ValueError("a session with pending tone requests into a pool built without tones=True")
+        reqs, last = [], 0
+        for q in pend:
+            if len(q) != 2 or isinstance(q[0], bool) or not isinstance(q[0], int) or q[0] < last or q[0] % self.up:
+                raise ValueError(f"the tone requests of the snapshot are no [P, program] list with anchors in order: {q!r}")
+            reqs.append((q[0], self._check_tones(tone_rule.check_program(q[1], self.voc_rate), meta["rate"])))
+            last = q[0]
+        n = sum(tone_rule.length(p) for _, p in reqs)
+        if n > self.max_tone:
+            raise ValueError(f"{n} pending tone samples exceed this pool's max_tone_samples = {self.max_tone}")
+        if sum(len(p) for _, p in reqs) > tone_rule.MAX_SEGMENTS:
+            raise ValueError(f"more than {tone_rule.MAX_SEGMENTS} pending segments")
+        return reqs
 
     def _park_schedule(self, meta: Mapping):
         return (DecodeSchedule if meta["lookahead"] is None else EarlyDecodeSchedule).from_state(self.geo, meta["schedule"])
@@ -978,6 +1128,7 @@ class DecodeSessions(ParkingPool):
             raise ValueError("a cross-fade goes with a look-ahead, and a tail with a cross-fade")
         if meta["lookahead"] is not None and sc.fade_frames != (1 if meta["fade"] else 0):
             raise ValueError("the schedule's fade_frames do not go with the session's cross-fade")
+        self._park_tones(meta)
         lo = meta["window"][0]
         if sc.tokens * f - lo + self.max_push * f > self.cap:
             raise ValueError(f"the frames [{lo}, {sc.tokens * f}) and one maximal push ({self.max_push * f} frames) do not fit the "
@@ -991,6 +1142,12 @@ class DecodeSessions(ParkingPool):
         super()._park_adopt(s, meta)
         for name in ("tok_origin", "n_noise", "fade", "has_tail"):
             getattr(self, name)[s] = meta[name]
+        self.tq[s] = self._park_tones(meta)
+        self.tone_samples[s] = sum(tone_rule.length(p) for _, p in self.tq[s])
+        # a snapshot written without the key: what the session has handed out follows from its schedule and its fade tail
+        self.handed[s] = meta.get("handed", self.sched[s].emitted * self.up - (meta["fade"] if meta["has_tail"] else 0))
+        for _, p in self.tq[s]:
+            self._ramps_for(p)
 
     def _prepare_slot(self, s: int) -> None:
         super()._prepare_slot(s)
@@ -1019,9 +1176,11 @@ class DecodeSessions(ParkingPool):
             # a slot with a look-ahead emits by its own rule, from its shadow row when that ran ahead of the committed one
             steps = {s: early.get(s, st) for s, st in steps.items()}
             row = {s: self.S + s if s in shadows else s for s in steps}
+            self._held, self._ending = {}, final
             out, pieces, wire = self._emit(steps, row, final, dev)
             self._flush_tails(steps, final, out, pieces, wire)
-            self._resample(steps, final, out, pieces, wire, dev)
+            placed = self.tones_on and self._tones(steps, final, out, pieces, wire, dev)
+            self._resample(steps, final, out, pieces, wire, dev, placed)
             self._to_wire(out, wire)
         self._release(final)
         return out
@@ -1121,7 +1280,13 @@ class DecodeSessions(ParkingPool):
             "wavenet_stream_step_items_layered")
 
     def _route(self, s: int, piece: torch.Tensor, out, pieces, wire) -> None:
-        """a new float piece (1, n) of slot s goes to the resampler, else to the wire convert, else it is cloned out"""
+        """a new float piece (1, n) of slot s goes to the resampler, else to the wire convert, else it is cloned out; in a pool that
+        sends tones it is held where a request of the slot is due in this step: the tone launch splices and routes it"""
+        if self.tones_on:
+            self.handed[s] += piece.shape[1]
+            if self.tq[s] and (s in self._ending or self.tq[s][0][0] <= self.handed[s]):
+                self._held[s] = piece[0]
+                return
         if self._converts(s):
             pieces[s] = piece[0]
         elif self._wired(s):
@@ -1177,16 +1342,74 @@ class DecodeSessions(ParkingPool):
                 self._route(s, self.buf["fade_tail"][s, :self.fade[s]][None], out, pieces, wire)
                 self.has_tail[s] = False
 
-    def _resample(self, steps, final, out, pieces, wire, dev) -> None:
+    def _tones(self, steps, final, out, pieces, wire, dev) -> bool:
+        """tones: ONE dmel_tone_items launch composes, for every slot with a request that is due -- its anchor P lies at or in front
+        of the end h1 of the speech the slot has handed out with this step, or the step is the slot's last --, the piece
+        speech[h0:P1] | tone 1 | speech[P1:P2] | ... straight where the slot's route reads it: behind its resampler tail, in its
+        row of the staging buffer the convert launch reads, or in a fresh tensor of the step that is handed out (in place of the
+        clone).  The resampler takes placed chunks or copied ones, not both: where one of the spliced slots leaves at another
+        rate, the launch also copies the pieces of the step's other such slots behind their tails (the copy rs.push would make)
+        -> whether it did"""
+        held = self._held
+        for s in steps:                               # a slot without a piece in this step serves what is due all the same
+            if s not in held and self.tq[s] and (s in final or self.tq[s][0][0] <= self.handed[s]):
+                held[s] = torch.empty(0, dtype=torch.float32, device=dev)
+        if not held:
+            return False
+        b, plan = self.buf, {}
+        for s, x in held.items():
+            due = [q for q in self.tq[s] if s in final or q[0] <= self.handed[s]]
+            plan[s] = (due, x.shape[0] + sum(tone_rule.length(p) for _, p in due))
+        placed = any(self._converts(s) for s in held)
+        if placed:
+            behind = self.rs.destinations({s: plan[s][1] if s in plan else pieces[s].shape[0]
+                                           for s in list(pieces) + [s for s in held if self._converts(s)]})
+        parts = []
+        for s, x in held.items():
+            (due, total), h0 = plan[s], self.handed[s] - x.shape[0]
+            if self._converts(s):
+                d = pieces[s] = behind[s]
+            elif self._wired(s):
+                d = wire[s] = b["tone_stage"][s, :total]
+            else:
+                d = torch.empty(1, total, dtype=torch.float32, device=dev)
+                out[s], d = (d, out[s][1]), d[0]
+            at = a = 0                                # samples of d written, samples of x consumed
+            for P, program in due:
+                c = min(max(P - h0, a), x.shape[0])
+                if c > a:
+                    parts.append((d[at:at + c - a], x[a:c]))
+                    at, a = at + c - a, c
+                n = tone_rule.length(program)
+                parts.append((d[at:at + n], program))
+                at += n
+            if x.shape[0] > a:
+                parts.append((d[at:at + x.shape[0] - a], x[a:]))
+        if placed:
+            for s, y in pieces.items():
+                if s not in held:
+                    if y.shape[0]:
+                        parts.append((behind[s], y))
+                    pieces[s] = behind[s]
+        tone_rule.tone_items(parts, self.voc_rate, sine=b["tone_sine"], ramps=b["tone_ramps"], ramp_off=self._ramp_off,
+                             table=b["tone_tab"])
+        for s, x in held.items():                     # behind the launch: a refused launch loses no request
+            due, total = plan[s]
+            del self.tq[s][:len(due)]
+            self.tone_samples[s] -= total - x.shape[0]
+        return placed
+
+    def _resample(self, steps, final, out, pieces, wire, dev, placed: bool = False) -> None:
         """the playback rates: each piece goes behind its slot's resampler tail, ONE launch converts all slots; a slot without a
-        new piece still takes part when it ends (the outputs that waited for the end of its signal)"""
+        new piece still takes part when it ends (the outputs that waited for the end of its signal).  placed: the tone launch of
+        the step has put the pieces there already"""
         if self.rs is None:
             return
         for s in steps:
             if self._converts(s) and s not in pieces and s in final:
                 pieces[s] = torch.empty(0, dtype=torch.float32, device=dev)
         if pieces:
-            for s, y in self.rs.push(pieces, final & set(pieces)).items():
+            for s, y in self.rs.push(pieces, final & set(pieces), placed=placed).items():
                 if self._wired(s):
                     wire[s] = y
                 else:

@@ -536,6 +536,41 @@ int dmel_dtmf_items(const float* samples, int64_t row_stride, int S, const int64
                     void* state /* (S, 128) words */, uint8_t* decided, uint8_t* pressed, int64_t out_pitch, void* table_scratch,
                     void* stream);
 
+/* Tones spliced into codec-rate audio, R parts in ONE launch (csrc/small_ops.hip): what decode sessions of a pool built with
+ * tones=True send DTMF keys, beeps and call-progress tones with (models/stream_sessions.py: send_dtmf / send_tones), whose rule, tables
+ * and caveats are utils/tones.py -- the kernel equals tones.render bit for bit.  Part r writes n[r] floats at dst[r].  Where src[r] is
+ * not NULL the part is a copy of n[r] floats from src[r] (words move as uint32: nothing is canonicalised).  Otherwise it is the
+ * rendering of the segments [seg_first[r], seg_first[r] + seg_count[r]), 1 .. 64 of them, of the launch's segment table `segs`, and
+ * n[r] must equal their total length.  Tone parts may name the same segments only where every shared segment begins at the same
+ * sample of both parts (equal ranges, or ranges with one first segment): the table holds one prefix sum per segment, and a segment
+ * that a second part would begin elsewhere is refused.  A spliced piece is three or more parts with consecutive dst: head, tone,
+ * tail.  A segment is eight 4-byte words: f1, f2 (int32 Hz, 0 <= f < rate / 2; f = 0 goes with a = 0: no such tone), a1, a2 (fp32, finite, >= 0,
+ * a1 + a2 <= 1), on, off, ramp (int32 samples, 1 <= on < 2^24, 0 <= off < 2^24, 0 <= ramp <= min(on / 2, 4096)) and ramp_off, the
+ * offset of the segment's ramp table in `ramps` (not looked at where ramp == 0).  `sine` holds `rate` floats, sine[j] =
+ * fp32(sin(2 pi j / rate)); the ramp table of a segment holds `ramp` floats, RAMP[i] = fp32(0.5 - 0.5 cos(pi (i + 0.5) / ramp)); both
+ * are computed by the caller in float64 and rounded once: the kernel evaluates no sine and no cosine.  Sample i of a segment,
+ * 0 <= i < on:
+ *     p_k = (f_k * i) mod rate (exact, 64-bit; the phase starts at 0 in every segment);   t_k = a_k * sine[p_k];   x = t_1 + t_2;
+ *     g = RAMP[i] for i < ramp, RAMP[on - 1 - i] for i >= on - ramp, 1.0f otherwise;   y = x * g
+ * four separately rounded fp32 operations, no fma; the samples on .. on + off - 1 are +0.0f.  n[r] == 0 is an idle part: neither its
+ * pointers nor its segments are looked at; when every part is idle the call returns DMEL_OK and launches nothing.  DMEL_EINVAL,
+ * nothing launched, dmel_last_error naming the part: R outside [1, 65535], a NULL table, sine or table_scratch, a NULL segs with
+ * n_segs > 0 or ramps with ramp_floats > 0, n_segs outside [0, 64 * 65535], rate outside [4000, 192000], a sine, ramps, dst or src
+ * that is not 4-byte aligned, a table_scratch that is not 8-byte aligned, n[r] negative or 2^40 and more, a NULL dst of a live part,
+ * a segment range outside the table or of no or more than 64 segments, a segment field outside the bounds above, ramp_off + ramp
+ * beyond ramp_floats, a part whose length is not the total length of its segments, a segment that begins at another sample of
+ * this part than of an earlier part that names it.  OVERLAP IS THE CALLER'S CONTRACT, as in
+ * dmel_stream_pack_items below: nothing checks that a destination is not another part's destination or source.  dst, src, n,
+ * seg_first, seg_count and segs are HOST tables, copied as launch arguments into table_scratch (6 R + 5 n_segs int64 of device
+ * memory, 8-byte aligned): the caller may overwrite them as soon as the call returns.  The grid covers the parts' own tiles of 1024
+ * floats, four per lane, laid on the 16-byte grid of each destination: every lane stores 16 bytes but the two that meet the ends of a
+ * part, which store single floats; both store paths give the same bits.  A lane finds its segment from the part's prefix sums.  Plain
+ * vector stores, no LDS, no atomics.  One profile record per launch in the family "tones" (time and bytes in "small"). */
+int dmel_tone_items(float* const* dst, const float* const* src /*entries nullable*/, const int64_t* n, const int32_t* seg_first,
+                    const int32_t* seg_count, int R, const int32_t* segs /* n_segs x 8 words, nullable when n_segs == 0 */, int n_segs,
+                    const float* sine /* rate floats */, int rate, const float* ramps /*nullable when ramp_floats == 0*/,
+                    int64_t ramp_floats, void* table_scratch, void* stream);
+
 /* R independent 2-D copies of 4-byte words in ONE launch (csrc/small_ops.hip): what takes the streaming state of live sessions out of
  * a pool's buffers into a snapshot and back (models/stream_sessions.py: snapshot / restore).  Descriptor r copies rows[r] rows of
  * cols[r] words: row i goes from src[r] + i * src_pitch[r] to dst[r] + i * dst_pitch[r], pitches in words.  Packing reads windows of

@@ -624,6 +624,56 @@ int main() {
       NN[0] = NN[2] = 0;                          // every item idle
       CK(scan());
     }
+    {
+      // the tone splice: tables of exactly R entries, a segment table of exactly 8 n_segs words, a table scratch of exactly
+      // 6 R + 5 n_segs int64; its refusals read the host tables only
+      auto out = buf(4096), speech = buf(2048), sine = buf(8000), ramps = buf(48);
+      float* DST[4] = {out.data() + 1, out.data() + 101, out.data() + 101 + 360, nullptr};
+      const float* SRC[4] = {speech.data() + 3, nullptr, speech.data() + 103, nullptr};
+      int64_t NN[4] = {100, 360, 50, 0};
+      int32_t SF[4] = {0, 0, 0, -7}, SC[4] = {0, 3, 0, 99};           // the idle part's segments are not looked at
+      int32_t SEG[3 * 8] = {697, 1209, 0, 0, 100, 20, 24, 0, 941, 0, 0, 0, 96, 0, 48, 0, 350, 440, 0, 0, 100, 44, 0, -5};
+      auto amp = [&](int k, int j, float a) { std::memcpy(SEG + 8 * k + 2 + j, &a, sizeof(float)); };
+      amp(0, 0, 0.3f); amp(0, 1, 0.4f); amp(1, 0, 1.0f); amp(2, 0, 0.5f); amp(2, 1, 0.5f);
+      SEG[8 + 7] = 0;                                                  // ramp tables of 24 and of 48 floats: [0, 24) and [0, 48)
+      std::vector<int64_t> tab(6 * 4 + 5 * 3);
+      int R = 4, n_segs = 3, rate = 8000;
+      int64_t ramp_floats = 48;
+      auto splice = [&]() { return dmel_tone_items(DST, SRC, NN, SF, SC, R, SEG, n_segs, sine.data(), rate, ramps.data(), ramp_floats, tab.data(), nullptr); };
+      CK(splice());
+      auto refused = [&](const char* part, const char* what) {
+        const int rc = splice();
+        if (rc != DMEL_EINVAL || !std::strstr(dmel_last_error(), part)) { std::printf("FAIL tone_items accepted %s (%d: %s)\n", what, rc, dmel_last_error()); ++failures; }
+      };
+      R = 0; refused("0 parts", "no part");
+      R = 65536; refused("65536 parts", "more than 65535 parts");
+      R = 4; rate = 3999; refused("3999 Hz", "a rate below 4000 Hz");
+      rate = 192001; refused("192001 Hz", "a rate above 192000 Hz");
+      rate = 8000; NN[2] = -1; refused("part 2", "a negative sample count");
+      NN[2] = 50; DST[0] = nullptr; refused("part 0", "a NULL destination");
+      DST[0] = reinterpret_cast<float*>(reinterpret_cast<char*>(out.data()) + 2); refused("part 0", "a destination that is not 4-byte aligned");
+      DST[0] = out.data() + 1; SC[1] = 4; refused("part 1", "a segment range behind the table");
+      SC[1] = 0; refused("part 1", "a tone part without segments");
+      SC[1] = 3; SF[1] = -1; refused("part 1", "a negative first segment");
+      SF[1] = 0; NN[1] = 361; refused("part 1", "a part longer than its segments");
+      NN[1] = 360; SEG[1] = 4000; refused("part 1", "a frequency of half the rate");
+      SEG[1] = 1209; SEG[8 + 1] = 0; amp(1, 1, 0.1f); refused("part 1", "an amplitude with f = 0");
+      amp(1, 1, 0.0f); amp(2, 1, 0.6f); refused("part 1", "amplitudes that sum above 1");
+      amp(2, 1, NAN); refused("part 1", "an amplitude that is not a number");
+      amp(2, 1, 0.5f); SEG[4] = 0; refused("part 1", "on = 0");
+      SEG[4] = 100; SEG[8 + 5] = 1 << 24; refused("part 1", "off = 2^24");
+      SEG[8 + 5] = 0; SEG[6] = 51; refused("part 1", "a ramp above half the tone");
+      SEG[6] = 24; SEG[8 + 7] = 1; refused("part 1", "a ramp table that ends behind the arena");
+      SEG[8 + 7] = 0; ramp_floats = 47; refused("part 1", "an arena shorter than a ramp table");
+      ramp_floats = 48;
+      // a second tone part on the same table: sharing a segment is fine where it begins at the same sample of both parts only
+      DST[3] = out.data() + 600; NN[3] = 120; SF[3] = 0; SC[3] = 1;
+      CK(splice());
+      NN[3] = 96; SF[3] = 1; refused("part 3", "a segment that begins at sample 0 of this part and at sample 120 of an earlier one");
+      DST[3] = nullptr; NN[3] = 0; SF[3] = -7; SC[3] = 99;
+      NN[0] = NN[1] = NN[2] = 0; DST[0] = nullptr; SC[1] = 0;          // every part idle: pointers and segments are not looked at
+      CK(splice());
+    }
     auto xs = buf(2 * 8 * 3000), ys = buf(2 * 8 * 3000), da = buf(8), db = buf(8);
     CK(dmel_aa_snake_f32(xs.data(), ys.data(), al.data(), be.data(), taps.data(), taps.data(), 1, 2, 8, 3000, nullptr));
     CK(dmel_aa_snake_backward_f32(xs.data(), ys.data(), xs.data(), al.data(), be.data(), da.data(), db.data(), taps.data(), taps.data(), 1, 2, 8, 3000, nullptr));

@@ -68,7 +68,13 @@ the stream, on the bench's synthetic weights.
 
 runs only this: S replies in steady state (64-token pushes), then snapshot + restore of all S of them, (a) as the pool does it -- ONE
 dmel_stream_pack_items launch per direction -- and (b) with one torch slice .clone() per state tensor per slot and a torch.cat, and
-the inverse (tools/bench_park.py): microseconds, bytes moved and GB/s of both, interleaved in one process, APPENDED to --out."""
+the inverse (tools/bench_park.py): microseconds, bytes moved and GB/s of both, interleaved in one process, APPENDED to --out.
+
+    python tools/bench_stream.py --sessions 16 --tones [--output-sample-rate 8000] [--sample-format ulaw] [--steps 40] [--out profiles/sessions_tones.txt]
+
+runs only this: S replies in steady state (16-token pushes) in three pools interleaved in one process -- decode_sessions() without the
+option, decode_sessions(tones=True) with no request due, and the same with a three-key send_dtmf due in every slot in every step: the
+step time of each and the launch records of one step ("tones", "small", "pcm_convert"), APPENDED to --out."""
 import json, math, os, statistics, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -624,6 +630,80 @@ def sessions_park_section(S, steps, out):
     print("\n".join(table), file=sys.stderr)
     print(json.dumps(result))
 
+
+def sessions_tones_section(S, rate, fmt, steps, out):
+    from dmel_codec_amd import _lib
+    chunk, warmup = 16, 8
+    gl = torch.Generator().manual_seed(8)
+    G, Cn = codec.dmel_groups, codec.decoder.input_channels
+    n_steps = warmup + steps
+    ids = torch.randint(0, 175, (S, G, chunk * n_steps), generator=gl, dtype=torch.int32).to(dev)
+    kw = dict(max_push_tokens=chunk, output_sample_rates=(rate,) if rate else ())
+    open_kw = dict(output_sample_rate=rate or None, sample_format=fmt)
+    pools = {"no_tones_pool": codec.decode_sessions(S, **kw), "tones_pool_idle": codec.decode_sessions(S, tones=True, **kw),
+             "tones_pool_3_keys": codec.decode_sessions(S, tones=True, **kw)}
+    slots = {k: [p.open(**open_kw) for _ in range(S)] for k, p in pools.items()}
+    ms, launches, samples = {k: [] for k in pools}, {k: {} for k in pools}, {k: 0 for k in pools}
+    keys, families = list(pools), ("tones", "small", "pcm_convert")
+    for j in range(n_steps):
+        noise = [torch.randn(Cn, chunk * 4, device=dev) for _ in range(S)]
+        counted = j == n_steps - 1                                          # the launch records of the last step, which is not timed
+        for k in (keys if j % 2 == 0 else keys[::-1]):                      # no pool always goes first
+            pool = pools[k]
+            if k == "tones_pool_3_keys":                                    # at the newest frame every slot has handed out: due in this step
+                for s in slots[k]:
+                    pool.send_dtmf(s, "159", at_frame=pool.frames_emitted(s))
+            if counted:
+                _lib.prof_reset(); _lib.prof_enable(True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = pool.push({s: ids[i, :, j * chunk:(j + 1) * chunk] for i, s in enumerate(slots[k])},
+                            noise={s: noise[i] for i, s in enumerate(slots[k])})
+            torch.cuda.synchronize()
+            if counted:
+                launches[k] = {f: _lib.prof_read(f)["launches"] for f in families}
+                _lib.prof_enable(False); _lib.prof_reset()
+            elif j >= warmup:
+                ms[k].append((time.perf_counter() - t0) * 1e3)
+            samples[k] += sum(a.numel() for a, _ in res.values())
+    pct = lambda v, q: sorted(v)[min(len(v) - 1, int(q * len(v)))]
+    result, rows = {"sessions": S, "chunk_tokens": chunk, "output_sample_rate": rate or pools[keys[0]].voc_rate, "sample_format": fmt}, []
+    for k in keys:
+        v = ms[k]
+        result[k] = {"median_ms": round(statistics.median(v), 3), "p10_ms": round(pct(v, 0.1), 3), "p90_ms": round(pct(v, 0.9), 3), "n": len(v),
+                     "launches_per_step": launches[k], "audio_samples": samples[k]}
+        rows.append(f"{S:8d}  {k:18s}  {statistics.median(v):9.3f}  {pct(v, 0.1):9.3f}  {pct(v, 0.9):9.3f}  {len(v):4d}  "
+                    f"{launches[k]['tones']:5d}  {launches[k]['small']:5d}  {launches[k]['pcm_convert']:11d}")
+    # a difference is a cost only where the medians leave each other's p10 .. p90; inside it the pools are level
+    med = [result[k]["median_ms"] for k in keys]
+    level = all(result[k]["p10_ms"] <= m <= result[k]["p90_ms"] for k in keys for m in med)
+    result["level_within_spread"] = level
+    verdict = (f"the three medians lie inside each other's p10 .. p90: level within spread, no cost of the option or of the tone step "
+               f"({S} slots, three keys each) is resolved" if level else
+               f"medians outside each other's p10 .. p90: idle tone pool {med[1] - med[0]:+.3f} ms against the pool without the option, "
+               f"tone step {med[2] - med[1]:+.3f} ms against the idle tone pool (new work: no threshold)")
+    table = [f"{S} decode sessions, {chunk}-token pushes, audio at {result['output_sample_rate']} Hz as {fmt}, 100 mel / 10 groups, BigVGAN base "
+             f"(tools/bench_stream.py --sessions {S} --tones)",
+             f"per-step wall time incl. host synchronisation, {steps} steady-state steps, the three pools interleaved in one process;",
+             "no_tones_pool = decode_sessions() as it was; tones_pool_idle = decode_sessions(tones=True), no request due; tones_pool_3_keys = "
+             "the same with send_dtmf(slot, '159') due in every slot in every step (11520 samples of tones per slot and step)",
+             "launch records of one step: tones (dmel_tone_items), small (all small kernels, the tone launch among them), pcm_convert",
+             "sessions  pool                median ms     p10 ms     p90 ms     n  tones  small  pcm_convert"] + rows + [
+             verdict]
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "a") as f:
+        f.write("\n".join(table) + "\n\n")
+    print("\n".join(table), file=sys.stderr)
+    print(json.dumps(result))
+
+
+if "--tones" in sys.argv:
+    assert "--sessions" in sys.argv, "--tones needs --sessions"
+    sessions_tones_section(int(arg_after("--sessions")), int(arg_after("--output-sample-rate", "0")), arg_after("--sample-format", "f32"),
+                           int(arg_after("--steps", "40")),
+                           arg_after("--out", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                           "sessions_tones.txt")))
+    sys.exit(0)
 
 if "--park" in sys.argv:
     assert "--sessions" in sys.argv, "--park needs --sessions"
