@@ -1847,6 +1847,225 @@ extern "C" int dmel_dtmf_items(const float* samples, int64_t row_stride, int S, 
 
 namespace dmel {
 
+// ---- input level (block AGC) on codec-rate samples (include/dmel_hip.h: dmel_level_items; the rule and the state row: utils/level.py) --
+// Row s of the table is (first, n_new, N, initial_gain, target, emin, min_gain, max_gain, attack, release, gate, ceiling, rN, 0, 0, 0),
+// sixteen 4-byte words; workgroup s owns slot s and re-writes its new samples in place.  Positions are counted as in dtmf_kernel: the
+// stream began `fill` samples in front of column `first`, block j of the launch holds positions [j N, (j + 1) N), of which
+// [fill, fill + n_new) exist.  A pass takes min(64, 4096 / N) blocks (at least one) -- at most 4096 samples, the LDS tile -- through three
+// phases with a barrier between them: (a) every live sample of the pass is read once into the tile, 16 bytes per lane on the aligned
+// body of the range and single words on its head and tail (`first` is any column), and wave w reduces the raw peaks of blocks w,
+// w + 4, ... from the tile (max is exact and order-free); (b) thread 0 runs the recursion of the pass's blocks in block order -- a few
+// dozen scalar operations per block -- and leaves the two gains every block ramps between, and the outputs of the whole ones, in LDS;
+// (c) every thread applies ramp, gain and clamp to its samples from the tile and stores them on the same 16-byte grid.  Nothing of a
+// pass is stored before all of it is read, and passes do not overlap.  peak_out and clamped are reduced over the workgroup behind the
+// last pass.  The ramp, the gain and the envelope step are separately rounded operations (fp contract(off), as dtmf_step above), the
+// division is the correctly rounded one: what the fp32 host expression gives.  Plain stores, no atomics.
+constexpr int kLevelWords = 16, kLevelState = 16, kLevelPassSamples = 4096, kLevelPassBlocks = 64;
+constexpr int kLevelMinBlock = 32, kLevelMaxBlock = 4096;
+__device__ __forceinline__ float level_apply(float x, float ga, float gb, int i, float rN, float ceiling, float& peak, int& clamped) {
+#pragma clang fp contract(off)
+  const float d = gb - ga;
+  const float u = (float)(i + 1) * rN;
+  const float m = d * u;
+  const float gi = ga + m;
+  float y = x * gi;
+  if (y > ceiling) { y = ceiling; ++clamped; }
+  else if (y < -ceiling) { y = -ceiling; ++clamped; }
+  peak = fmaxf(peak, fabsf(y));
+  return y;
+}
+__device__ __forceinline__ float level_envelope(float env, float p, float attack, float release) {
+#pragma clang fp contract(off)
+  const float k = p >= env ? attack : release;
+  float t = p - env;
+  t = k * t;
+  return env + t;
+}
+__device__ __forceinline__ float level_gain(float env, float target, float emin, float gmin, float gmax) {
+  const float e = env > emin ? env : emin;
+  float g = target / e;
+  g = g > gmin ? g : gmin;
+  return g < gmax ? g : gmax;
+}
+__global__ __launch_bounds__(256) void level_kernel(float* __restrict__ samples, int64_t row_stride, const uint32_t* __restrict__ tab,
+                                                    uint32_t* __restrict__ state, float* __restrict__ out_peak,
+                                                    float* __restrict__ out_gain, int64_t out_pitch) {
+  __shared__ float tile[kLevelPassSamples];
+  __shared__ float bpk[kLevelPassBlocks], bga[kLevelPassBlocks], bgb[kLevelPassBlocks], bgo[kLevelPassBlocks];
+  __shared__ float red_peak[4];
+  __shared__ int red_clamped[4];
+  const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint32_t* row = tab + (size_t)s * kLevelWords;
+  const int64_t n_new = (int64_t)(int32_t)row[1];
+  if (n_new <= 0) return;                               // idle (uniform: in front of the first barrier)
+  const int64_t first = (int64_t)(int32_t)row[0];
+  const int N = (int)row[2];
+  const float g0 = __uint_as_float(row[3]), target = __uint_as_float(row[4]), emin = __uint_as_float(row[5]);
+  const float gmin = __uint_as_float(row[6]), gmax = __uint_as_float(row[7]), attack = __uint_as_float(row[8]);
+  const float release = __uint_as_float(row[9]), gate = __uint_as_float(row[10]), ceiling = __uint_as_float(row[11]);
+  const float rN = __uint_as_float(row[12]);
+  uint32_t* srow = state + (size_t)s * kLevelState;
+  int fill = (int)srow[6];
+  if ((unsigned)fill >= (unsigned)N) fill = 0;          // no row the rule wrote; keeps every index below inside the launch's columns
+  // the recursion's state: thread 0 alone advances it
+  float env = __uint_as_float(srow[0]), open_peak = __uint_as_float(srow[3]), peak_in = __uint_as_float(srow[4]);
+  int blocks = (int)srow[7], locked = (int)srow[8], held = (int)srow[9];
+  float ga = locked ? __uint_as_float(srow[1]) : g0, gb = locked ? __uint_as_float(srow[2]) : g0;
+  const int64_t end = fill + n_new;                     // positions [fill, end) exist
+  const int64_t nblk = (end + N - 1) / N, done = end / N;
+  float* src = samples + (int64_t)s * row_stride + first - fill;             // position p is src[p]; only [fill, end) is touched
+  float* opk = out_peak + (int64_t)s * out_pitch;
+  float* ogn = out_gain + (int64_t)s * out_pitch;
+  const int PB = max(1, min(kLevelPassBlocks, kLevelPassSamples / N));
+  float my_peak = 0.0f;
+  int my_clamped = 0;
+  for (int64_t b0 = 0; b0 < nblk; b0 += PB) {
+    const int nb = (int)min((int64_t)PB, nblk - b0);
+    const int nd = (int)max((int64_t)0, min((int64_t)nb, done - b0));          // the whole blocks of the pass
+    const int64_t base = b0 * N;                        // tile[q] is position base + q; q in [lo, hi) exists
+    const int lo = (int)(max((int64_t)fill, base) - base), hi = (int)(min(end, base + (int64_t)nb * N) - base);
+    float* g = src + base;
+    // the 16-byte grid of the range: `head` single words, nv vectors, the words from tail0 on
+    const int head = min(hi - lo, (int)((4u - (unsigned)(((uintptr_t)(g + lo) >> 2) & 3u)) & 3u));
+    const int nv = (hi - lo - head) >> 2, body = lo + head, tail0 = body + 4 * nv;
+    // (a) every sample of the pass into the tile, then the raw peak of every block
+    if (tid < head) tile[lo + tid] = g[lo + tid];
+    for (int v = tid; v < nv; v += 256) {
+      const int q = body + 4 * v;
+      const float4 x = *reinterpret_cast<const float4*>(g + q);
+      tile[q] = x.x; tile[q + 1] = x.y; tile[q + 2] = x.z; tile[q + 3] = x.w;
+    }
+    if (tid < hi - tail0) tile[tail0 + tid] = g[tail0 + tid];
+    __syncthreads();
+    for (int j = wave; j < nb; j += 4) {                // wave-uniform
+      const int a = max(lo, j * N), z = min(hi, (j + 1) * N);
+      float m = 0.0f;
+      for (int q = a + lane; q < z; q += 64) m = fmaxf(m, fabsf(tile[q]));
+      for (int o = 32; o; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+      if (lane == 0) bpk[j] = m;
+    }
+    __syncthreads();
+    // (b) the recursion, in block order
+    if (tid == 0) {
+      for (int j = 0; j < nb; ++j) {
+        bga[j] = ga; bgb[j] = gb;
+        float p = bpk[j];
+        if (b0 + j == 0) p = fmaxf(p, open_peak);       // the block that was open when the launch began
+        if (j >= nd) { open_peak = p; break; }          // the block the launch leaves open (the last one)
+        peak_in = fmaxf(peak_in, p);
+        if (!locked) {
+          if (p >= gate) { env = p; locked = 1; }
+        } else if (p < gate && p < env) {
+          held += 1;
+        } else {
+          env = level_envelope(env, p, attack, release);
+        }
+        const float gn = locked ? level_gain(env, target, emin, gmin, gmax) : g0;
+        ga = gb; gb = gn; open_peak = 0.0f;
+        blocks += 1;
+        bpk[j] = p; bgo[j] = gn;
+      }
+    }
+    __syncthreads();
+    // (c) ramp, gain and clamp, from the tile to the row
+    if (tid < head) {
+      const int q = lo + tid, j = q / N;
+      g[q] = level_apply(tile[q], bga[j], bgb[j], q - j * N, rN, ceiling, my_peak, my_clamped);
+    }
+    for (int v = tid; v < nv; v += 256) {
+      const int q = body + 4 * v;
+      int j = q / N, i = q - j * N;
+      float y[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        y[k] = level_apply(tile[q + k], bga[j], bgb[j], i, rN, ceiling, my_peak, my_clamped);
+        if (++i == N) { i = 0; ++j; }
+      }
+      *reinterpret_cast<float4*>(g + q) = make_float4(y[0], y[1], y[2], y[3]);
+    }
+    if (tid < hi - tail0) {
+      const int q = tail0 + tid, j = q / N;
+      g[q] = level_apply(tile[q], bga[j], bgb[j], q - j * N, rN, ceiling, my_peak, my_clamped);
+    }
+    if (tid < nd) {
+      opk[b0 + tid] = bpk[tid];
+      ogn[b0 + tid] = bgo[tid];
+    }
+    __syncthreads();                                    // the next pass overwrites the tile and the block tables
+  }
+  for (int o = 32; o; o >>= 1) {
+    my_peak = fmaxf(my_peak, __shfl_xor(my_peak, o));
+    my_clamped += __shfl_xor(my_clamped, o);
+  }
+  if (lane == 0) { red_peak[wave] = my_peak; red_clamped[wave] = my_clamped; }
+  __syncthreads();
+  if (tid == 0) {
+    const float pk = fmaxf(fmaxf(red_peak[0], red_peak[1]), fmaxf(red_peak[2], red_peak[3]));
+    const int cl = red_clamped[0] + red_clamped[1] + red_clamped[2] + red_clamped[3];
+    srow[0] = __float_as_uint(env); srow[1] = __float_as_uint(ga); srow[2] = __float_as_uint(gb); srow[3] = __float_as_uint(open_peak);
+    srow[4] = __float_as_uint(peak_in); srow[5] = __float_as_uint(fmaxf(__uint_as_float(srow[5]), pk));
+    srow[6] = (uint32_t)(end - done * N); srow[7] = (uint32_t)blocks; srow[8] = (uint32_t)locked; srow[9] = (uint32_t)held;
+    srow[10] = (uint32_t)((int)srow[10] + cl);
+  }
+}
+
+}  // namespace dmel
+
+extern "C" int dmel_level_items(float* samples, int64_t row_stride, int S, const int64_t* first, const int64_t* n_new, const int32_t* N,
+                                const float* fparams, void* state, float* out_peak, float* out_gain, int64_t out_pitch,
+                                void* table_scratch, void* stream) {
+  using namespace dmel;
+  DMEL_CHECK_ARG(samples && first && n_new && N && fparams && state && out_peak && out_gain && table_scratch, "level_items: NULL argument");
+  DMEL_CHECK_ARG(S >= 1 && S <= 65535, "level_items: %d items, expected 1 .. 65535", S);
+  DMEL_CHECK_ARG((((uintptr_t)samples | (uintptr_t)state | (uintptr_t)out_peak | (uintptr_t)out_gain | (uintptr_t)table_scratch) & 3) == 0,
+                 "level_items: samples, state, out_peak, out_gain or table_scratch is not 4-byte aligned");
+  DMEL_CHECK_ARG(row_stride >= 0 && out_pitch >= 0, "level_items: negative row stride %lld or output pitch %lld", (long long)row_stride,
+                 (long long)out_pitch);
+  static const char* const kNames[10] = {"initial_gain", "target", "emin", "min_gain", "max_gain", "attack", "release", "gate", "ceiling", "rN"};
+  std::vector<uint32_t> tab((size_t)kLevelWords * S, 0u);
+  int64_t live = 0;
+  double bytes = 0.0;
+  for (int s = 0; s < S; ++s) {
+    const int64_t n = n_new[s];
+    DMEL_CHECK_ARG(n >= 0 && n <= 0x3fffffff, "level_items: item %d: %lld new samples, expected 0 .. 2^30 - 1", s, (long long)n);
+    if (n == 0) continue;                               // idle: its parameters are not looked at (the table row stays 0)
+    DMEL_CHECK_ARG(first[s] >= 0 && first[s] <= 0x3fffffff, "level_items: item %d: first column %lld, expected 0 .. 2^30 - 1", s,
+                   (long long)first[s]);
+    const int32_t nb = N[s];
+    DMEL_CHECK_ARG(nb >= kLevelMinBlock && nb <= kLevelMaxBlock, "level_items: item %d: a block of %d samples, expected %d .. %d", s, nb,
+                   kLevelMinBlock, kLevelMaxBlock);
+    const int64_t most = (n + nb - 1) / nb;             // whatever the open block holds (at most N - 1 samples)
+    DMEL_CHECK_ARG(out_pitch >= most, "level_items: item %d: %lld samples can complete %lld blocks, which exceed the output pitch %lld", s,
+                   (long long)n, (long long)most, (long long)out_pitch);
+    const float* fp = fparams + (size_t)10 * s;
+    for (int k = 0; k < 10; ++k)                        // the gate alone may be 0
+      DMEL_CHECK_ARG(std::isfinite(fp[k]) && (fp[k] > 0.0f || (k == 7 && fp[k] == 0.0f)),
+                     "level_items: item %d: float parameter %d (%s) is not finite and positive", s, k, kNames[k]);
+    DMEL_CHECK_ARG(fp[5] <= 1.0f && fp[6] <= 1.0f && fp[9] <= 1.0f, "level_items: item %d: attack %g, release %g or rN %g above 1", s,
+                   (double)fp[5], (double)fp[6], (double)fp[9]);
+    DMEL_CHECK_ARG(fp[3] <= fp[0] && fp[0] <= fp[4], "level_items: item %d: initial_gain %g outside [min_gain, max_gain] = [%g, %g]", s,
+                   (double)fp[0], (double)fp[3], (double)fp[4]);
+    uint32_t* it = tab.data() + (size_t)kLevelWords * s;
+    it[0] = (uint32_t)first[s]; it[1] = (uint32_t)n; it[2] = (uint32_t)nb;
+    std::memcpy(it + 3, fp, 10 * sizeof(float));
+    ++live;
+    bytes += 8.0 * (double)n + 8.0 * (double)most + 8.0 * kLevelState;
+  }
+  if (live == 0) return DMEL_OK;                        // every item idle
+  hipStream_t st = (hipStream_t)stream;
+  DMEL_TRY(launch_table_put(tab.data(), tab.size() * sizeof(uint32_t), table_scratch, st));
+  {
+    // "small" carries the time and the bytes; the second scope only counts: one record per leveller launch (dmel_prof_read("level"))
+    ProfScope ps("small", st, 0.0, bytes), count("level", st, 0.0, 0.0);
+    hipLaunchKernelGGL(level_kernel, dim3((unsigned)S), dim3(256), 0, st, samples, row_stride, static_cast<const uint32_t*>(table_scratch),
+                       static_cast<uint32_t*>(state), out_peak, out_gain, out_pitch);
+  }
+  DMEL_HIP(hipGetLastError());
+  return DMEL_OK;
+}
+
+namespace dmel {
+
 // ---- tones spliced into codec-rate audio (include/dmel_hip.h: dmel_tone_items; the rule: utils/tones.py) -----------------------------
 // The table holds R part rows of (dst, src, n, first tile, first segment record, segments), six int64, and behind them the launch's
 // segment records of five int64: the eight 4-byte words of the entry's table (f1, f2, a1, a2, on, off, ramp, ramp_off) and the

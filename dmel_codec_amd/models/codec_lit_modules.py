@@ -400,7 +400,7 @@ class VQGAN(nn.Module):
             yield ids
 
     def encode_sessions(self, slots: int, max_push_samples: int = 7680, sample_rate: Optional[int] = None, sample_rates=(),
-                        voice: bool = False, dtmf: bool = False):
+                        voice: bool = False, dtmf: bool = False, level: bool = False):
         """A pool of `slots` INDEPENDENT incremental encodes served by one streaming step: sessions open, receive their own number of
         samples per step (at most max_push_samples), stall and close on their own -- what streaming_encoder(batch=B), B streams in
         lockstep, cannot do -- and each one's concatenated ids are the bits of encode() on its own clip.  One STFT launch, one encoder
@@ -414,9 +414,12 @@ class VQGAN(nn.Module):
         starts a session's detector, served for all slots of a step by one more launch on the log-mel frames, read with pool.voice()
         (utils/voice.py has the rule).  dtmf=True adds a DTMF key detector row per slot: pool.open(dtmf=True | DtmfConfig) starts a
         session's detector, served for all slots of a step by one more launch on the codec-rate samples, read with pool.dtmf()
-        (utils/dtmf.py has the rule).  See models/stream_sessions.py: EncodeSessions."""
+        (utils/dtmf.py has the rule).  level=True adds an input leveller row per slot: pool.open(level=True | LevelConfig) starts a
+        session's causal block AGC, which re-writes the session's codec-rate samples in place in one more launch for all slots of a
+        step, in front of the STFT launch, and is read with pool.levels(); such a session's ids are the bits of encode() of
+        level.scan of its clip (utils/level.py has the rule).  See models/stream_sessions.py: EncodeSessions."""
         from .stream_sessions import EncodeSessions
-        return EncodeSessions(self, slots, max_push_samples, sample_rate, sample_rates, voice, dtmf)
+        return EncodeSessions(self, slots, max_push_samples, sample_rate, sample_rates, voice, dtmf, level)
 
     # ------------------------------------------------------------------------------ decode side
     @torch.no_grad()

@@ -21,6 +21,7 @@ import torch
 from .. import _lib
 from ..utils import crossfade, pcm
 from ..utils import dtmf as dtmf_rule
+from ..utils import level as level_rule
 from ..utils import tones as tone_rule
 from ..utils import voice as voice_rule
 from .stream_park import ParkingPool, plain
@@ -122,6 +123,25 @@ class EncodeSessions(ParkingPool):
     Voice and DTMF are independent options of one pool.  A pool built without dtmf=True allocates and launches exactly what it
     did, refuses open(dtmf=) and a snapshot that carries a detector; a session without one snapshots to the bytes it always did.
 
+    The wire delivers whatever level it likes -- a PSTN caller at -35 dBFS, a hot headset at -3 dBFS -- and the encoder was trained
+    on clips peak-normalised to 0.95.  A pool built with level=True serves sessions opened with open(level=True | LevelConfig), each
+    with an input leveller of its own: a causal block AGC with a meter and zero added latency on the same codec-rate samples (the
+    rule, its state row and its caveats: utils/level.py, which is also the host reference the pool is tested against bit for bit).
+    Unlike the detectors it CHANGES the samples the encoder sees.  Behind the DTMF launch of a step -- the detector reads the samples
+    as received: a pool's DTMF reports do not change with level -- and in front of the STFT launch, ONE dmel_level_items launch
+    re-writes in place exactly the columns every named slot with a leveller gained; a step without such a slot launches what it
+    did.  The voice detector sees the levelled mel.  Contract: the ids of a levelled session are the bits of encode(y, len) with
+    y = level.scan(x, config, sample_rate=codec rate)[0] and x the session's clip at the codec's rate (resample(from_wire(clip), r,
+    codec rate)), however the audio was cut into pushes; the other sessions of the pool keep the bits of encode() of their clips.
+    The state is one row of 16 words per slot (`level`), zeroed with the slot's other rows, and travels with snapshot / restore as
+    one more segment; push() returns what it returns and never syncs.  levels() -> {slot: LevelReport} (gain, envelope, peaks,
+    clamped samples, held blocks) for every slot with a leveller that is open or ended in the most recent push, from ONE
+    device-to-host copy of that table, the only sync and only when asked; level_blocks(slot) -> (peaks, gains), device fp32 views
+    of the blocks the slot's last push completed.  A pool built without level=True allocates and launches exactly what it did,
+    refuses open(level=) and a snapshot that carries a leveller; a session without one snapshots to the bytes it always did.  Not
+    served: look-ahead limiting, RMS or loudness (LUFS) metering, the lockstep StreamingEncoder and whole-clip encode() (callers
+    have level.scan / level.level_items), output gain on decode pools, a DTMF detector that reads levelled samples.
+
     Only encoders the one-launch streaming kernel takes (residual channels in (32, 80], no condition, no output projection,
     dilations <= 8, fp32): anything else is refused at construction.
 
@@ -130,7 +150,7 @@ class EncodeSessions(ParkingPool):
     process -- a streaming decode, for example -- must call dmel_stft_set_exclusive_cu(1) first, exactly as pipeline.CodecLanes does."""
 
     def __init__(self, codec, slots: int, max_push_samples: int = 7680, sample_rate: Optional[int] = None,
-                 sample_rates: Iterable[int] = (), voice: bool = False, dtmf: bool = False):
+                 sample_rates: Iterable[int] = (), voice: bool = False, dtmf: bool = False, level: bool = False):
         enc, tr = codec.encoder, codec.encode_mel_transform
         if sample_rate is not None and int(sample_rate) != int(tr.sample_rate):
             raise NotImplementedError(f"sessions run at the codec's own rate ({tr.sample_rate} Hz); resample in front (StreamResampler), "
@@ -196,29 +216,39 @@ class EncodeSessions(ParkingPool):
         self.dcfg: List[Optional[dtmf_rule.DtmfConfig]] = [None] * self.S        # the slot's DTMF detector (None: none)
         self._dtmf_n = [0] * self.S                   # blocks the slot's last push completed: the valid bytes of its decided / pressed rows
         self._dtmf_ended: set = set()                 # slots with a DTMF detector that ended in the most recent push
+        if not isinstance(level, bool):
+            raise ValueError(f"level must be a bool (a session's config goes to open(level=)), got {level!r}")
+        self.level_on = level                         # the pool keeps leveller rows: sessions may open with level=
+        self.lcfg: List[Optional[level_rule.LevelConfig]] = [None] * self.S      # the slot's leveller (None: none)
+        self._level_n = [0] * self.S                  # blocks the slot's last push completed: the valid words of its peak / gain rows
+        self._level_ended: set = set()                # slots with a leveller that ended in the most recent push
 
     def tokens_emitted(self, slot: int) -> int:
         self._check_open(slot)
         return self.sched[slot].tokens
 
     def open(self, sample_rate: Optional[int] = None, sample_format: str = "f32", channels: int = 1,
-             channel: Optional[int] = None, voice=None, dtmf=None) -> int:
+             channel: Optional[int] = None, voice=None, dtmf=None, level=None) -> int:
         """take a free slot: fresh schedule, state zeroed before its first push.  sample_rate: the rate this session's pushes arrive
         at, one of the declared `sample_rates` (None: the codec's).  sample_format: "f32", "s16" for torch.int16 pushes (16-bit
         signed PCM, x / 32768), or "ulaw" / "alaw" for torch.uint8 pushes (G.711 codes).  channels: 1 .. 8; above 1 the pushes are
         interleaved frames (n, channels), downmixed to their mean, or to channel `channel` of them (0 .. channels - 1).  voice: True
         (the defaults of utils/voice.py) or a VoiceConfig starts the session's voice-activity detector, on a pool built with
         voice=True.  dtmf: True (the defaults of utils/dtmf.py) or a DtmfConfig starts the session's DTMF key detector, on a pool
-        built with dtmf=True.  Raises when every slot is taken; a refused open takes no slot."""
+        built with dtmf=True.  level: True (the defaults of utils/level.py) or a LevelConfig starts the session's input leveller, on
+        a pool built with level=True: the encoder then sees the levelled samples.  Raises when every slot is taken; a refused open
+        takes no slot."""
         rate = self.codec_rate if sample_rate is None else int(sample_rate)
         pick = self._check_wire(rate, sample_format, channels, channel)
         cfg = self._check_voice(voice_rule.as_config(voice))
         keys = self._check_dtmf(dtmf_rule.as_config(dtmf))
+        lev = self._check_level(level_rule.as_config(level))
         s = self._first_free()
         self._occupy(s, EncodeSchedule(self.geo), 0, rate, sample_format, channels)
         self.s0[s], self.tail[s], self.pick[s] = 0, 0, pick
         self.vcfg[s], self._voice_n[s] = cfg, 0
         self.dcfg[s], self._dtmf_n[s] = keys, 0
+        self.lcfg[s], self._level_n[s] = lev, 0
         return s
 
     def _check_voice(self, cfg: Optional[voice_rule.VoiceConfig]) -> Optional[voice_rule.VoiceConfig]:
@@ -234,6 +264,14 @@ class EncodeSessions(ParkingPool):
         if cfg is not None:
             if not self.dtmf_on:
                 raise ValueError("dtmf on a pool built without dtmf=True: it has no detector rows")
+            cfg.block(self.codec_rate)
+        return cfg
+
+    def _check_level(self, cfg: Optional[level_rule.LevelConfig]) -> Optional[level_rule.LevelConfig]:
+        """a session's leveller config, refused here for open() and for restore() alike"""
+        if cfg is not None:
+            if not self.level_on:
+                raise ValueError("level on a pool built without level=True: it has no leveller rows")
             cfg.block(self.codec_rate)
         return cfg
 
@@ -300,6 +338,13 @@ class EncodeSessions(ParkingPool):
                             dtmf_decided=torch.zeros(self.S, pitch, dtype=torch.uint8, device=dev),
                             dtmf_pressed=torch.zeros(self.S, pitch, dtype=torch.uint8, device=dev),
                             dtmf_tab=torch.empty(dtmf_rule.TABLE_WORDS * self.S, dtype=torch.int32, device=dev))
+        if self.level_on:                             # dmel_level_items: a state row per slot, the step's block peaks and gains (the pitch
+            #                                           as above), 16 words per slot of the table
+            pitch = self.codec_push // level_rule.MIN_BLOCK + 2
+            self.buf.update(level=torch.zeros(self.S, level_rule.STATE_WORDS, dtype=torch.int32, device=dev),
+                            level_peak=torch.zeros(self.S, pitch, dtype=torch.float32, device=dev),
+                            level_gain=torch.zeros(self.S, pitch, dtype=torch.float32, device=dev),
+                            level_tab=torch.empty(level_rule.TABLE_WORDS * self.S, dtype=torch.int32, device=dev))
 
     def _prepare_slot(self, s: int) -> None:
         super()._prepare_slot(s)
@@ -307,6 +352,8 @@ class EncodeSessions(ParkingPool):
             self.buf["voice"][s].zero_()              # the fresh detector state (not one of _slot_views: a re-base does not shift it)
         if self.dtmf_on:
             self.buf["dtmf"][s].zero_()               # the fresh DTMF state
+        if self.level_on:
+            self.buf["level"][s].zero_()              # the fresh leveller state
 
     def _slot_views(self, s: int):
         b, G = self.buf, self.G
@@ -334,6 +381,8 @@ class EncodeSessions(ParkingPool):
             meta["voice"] = self.vcfg[s].as_dict()
         if self.dcfg[s] is not None:                  # likewise
             meta["dtmf"] = self.dcfg[s].as_dict()
+        if self.lcfg[s] is not None:                  # likewise
+            meta["level"] = self.lcfg[s].as_dict()
         return meta
 
     def _park_schedule(self, meta: Mapping) -> EncodeSchedule:
@@ -347,6 +396,8 @@ class EncodeSessions(ParkingPool):
             shapes.append(("voice", 1, self.n_mels + voice_rule.STATE_INTS if meta["schedule"]["frames"] > 0 else 0))
         if meta.get("dtmf") is not None:              # the DTMF row; a session that has seen no sample owns the zeroed row: nothing
             shapes.append(("dtmf", 1, dtmf_rule.STATE_WORDS if meta["schedule"]["samples"] > 0 else 0))
+        if meta.get("level") is not None:             # the leveller row, likewise
+            shapes.append(("level", 1, level_rule.STATE_WORDS if meta["schedule"]["samples"] > 0 else 0))
         return shapes
 
     def _park_rows(self, s: int) -> Dict[str, torch.Tensor]:
@@ -361,6 +412,8 @@ class EncodeSessions(ParkingPool):
             rows["voice"] = b["voice"][s:s + 1]
         if self.dtmf_on:
             rows["dtmf"] = b["dtmf"][s:s + 1]
+        if self.level_on:
+            rows["level"] = b["level"][s:s + 1]
         return rows
 
     def _park_widths(self):
@@ -384,6 +437,15 @@ class EncodeSessions(ParkingPool):
         except TypeError as e:
             raise ValueError(f"the dtmf config of the snapshot is not a DtmfConfig: {e}") from None
 
+    def _park_level(self, meta: Mapping) -> Optional[level_rule.LevelConfig]:
+        """the leveller config a snapshot carries (None: none); ValueError where it is no config"""
+        if meta.get("level") is None:
+            return None
+        try:
+            return level_rule.LevelConfig.from_dict(meta["level"])
+        except TypeError as e:
+            raise ValueError(f"the level config of the snapshot is not a LevelConfig: {e}") from None
+
     def _park_fits(self, meta: Mapping, sc: EncodeSchedule) -> None:
         g, (lo, hi) = self.geo, meta["window"]
         room = self.codec_push // g.hop + 1 + (g.n_fft - g.pad + g.hop - 1) // g.hop
@@ -393,12 +455,14 @@ class EncodeSessions(ParkingPool):
             raise ValueError(f"a sample tail of {meta['tail']} samples and one maximal push do not fit a row of {self.width} samples")
         self._check_voice(self._park_voice(meta))
         self._check_dtmf(self._park_dtmf(meta))
+        self._check_level(self._park_level(meta))
 
     def _park_adopt(self, s: int, meta: Mapping) -> None:
         super()._park_adopt(s, meta)
         self.s0[s], self.tail[s], self.pick[s] = meta["s0"], meta["tail"], -1 if meta["channel"] is None else meta["channel"]
         self.vcfg[s], self._voice_n[s] = self._park_voice(meta), 0
         self.dcfg[s], self._dtmf_n[s] = self._park_dtmf(meta), 0
+        self.lcfg[s], self._level_n[s] = self._park_level(meta), 0
 
     # -- one step ----------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -410,11 +474,13 @@ class EncodeSessions(ParkingPool):
         self._ensure_buffers(dev)
         converted, placed = self._place(audio)
         released = self._resample(converted, final, placed)
-        tails = list(self.tail) if self.dtmf_on else None
+        tails = list(self.tail) if self.dtmf_on or self.level_on else None
         steps = self._intake(audio, released, placed, final)
         with torch.cuda.device(dev):
             if self.dtmf_on:
                 self._dtmf(steps, final, tails)
+            if self.level_on:
+                self._level(steps, final, tails)
             mel = self._stft(steps, dev)
             if self.voice_on:
                 self._voice(steps, final, mel)
@@ -576,6 +642,48 @@ class EncodeSessions(ParkingPool):
             return empty, empty.clone()
         n = self._dtmf_n[slot]
         return self.buf["dtmf_decided"][slot, :n], self.buf["dtmf_pressed"][slot, :n]
+
+    def _level(self, steps, final, tails: List[int]) -> None:
+        """input level: ONE launch re-writes in place the samples every named slot with a leveller gained in this step -- columns
+        [tail before, tail after) of its row -- behind the DTMF launch, which reads them as received, and in front of the STFT
+        phase, which reads them levelled and re-bases the rows"""
+        self._level_ended = {s for s in final if self.lcfg[s] is not None}
+        first, n_new = [0] * self.S, [0] * self.S
+        for s, st in steps.items():
+            if self.lcfg[s] is not None:
+                first[s], n_new[s] = tails[s], self.tail[s] - tails[s]
+                N = self.lcfg[s].block(self.codec_rate)
+                self._level_n[s] = st.samples // N - (st.samples - n_new[s]) // N
+        if not any(n_new):
+            return
+        b = self.buf
+        level_rule.level_items(b["samples"], first, n_new, self.lcfg, b["level"], b["level_peak"], b["level_gain"],
+                               sample_rate=self.codec_rate, table=b["level_tab"])
+
+    def _level_slots(self) -> List[int]:
+        return [s for s in range(self.S) if self.lcfg[s] is not None and (self.sched[s] is not None or s in self._level_ended)]
+
+    def levels(self) -> Dict[int, level_rule.LevelReport]:
+        """{slot: LevelReport} of every slot with a leveller that is open or ended in the most recent push: ONE device-to-host copy
+        of the leveller table (the only sync of the leveller, and only here).  A slot that has not been pushed to reports no
+        sample."""
+        slots = self._level_slots()
+        live = [s for s in slots if not self._fresh[s]] if self.buf is not None else []
+        table = self.buf["level"].cpu() if live else None
+        zero = level_rule.fresh_state()
+        return {s: level_rule.report(table[s] if s in live else zero, self.lcfg[s].block(self.codec_rate), self.codec_rate,
+                                     self.lcfg[s].initial_gain) for s in slots}
+
+    def level_blocks(self, slot: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(peaks, gains) of the blocks the slot's last push completed: device fp32 views (n,), valid until the slot's next push.
+        peaks: the raw peak of the block; gains: the gain the block after it ramps to"""
+        if not isinstance(slot, int) or slot not in self._level_slots():
+            raise ValueError(f"slot {slot!r} has no leveller (open(level=)) or is neither open nor ended in the last push")
+        if self.buf is None or self._fresh[slot]:
+            empty = torch.empty(0, dtype=torch.float32, device=self._device())
+            return empty, empty.clone()
+        n = self._level_n[slot]
+        return self.buf["level_peak"][slot, :n], self.buf["level_gain"][slot, :n]
 
     def _wavenet(self, steps) -> None:
         """encoder WaveNet: every level of every slot advances to its own new frontier"""

@@ -536,6 +536,41 @@ int dmel_dtmf_items(const float* samples, int64_t row_stride, int S, const int64
                     void* state /* (S, 128) words */, uint8_t* decided, uint8_t* pressed, int64_t out_pitch, void* table_scratch,
                     void* stream);
 
+/* Input level (a causal block AGC with a meter) on codec-rate samples, S session slots in ONE launch (csrc/small_ops.hip): the
+ * leveller of encode sessions opened with level= (models/stream_sessions.py), whose rule, defaults and caveats are utils/level.py -- the
+ * kernel equals level.scan bit for bit.  Slot s RE-WRITES IN PLACE its n_new[s] new samples at samples[s * row_stride + first[s] + i]
+ * (fp32, any 4-byte offset; no other column is written) and carries one row of 16 4-byte words in `state`: fp32 0 env, 1 ga, 2 gb,
+ * 3 open_peak, 4 peak_in, 5 peak_out; int32 6 fill (samples of the open block consumed), 7 blocks, 8 locked, 9 held, 10 clamped;
+ * 11 .. 15 reserved and not written.  A zeroed row is a fresh session: while locked == 0, ga and gb read as initial_gain whatever the
+ * row holds, and a launch with samples writes back what it read.  Blocks are N[s] consecutive samples, counted from the session's
+ * first.  Sample x at position i of the open block, whose start gain is ga and end gain gb (five separately rounded fp32 operations,
+ * no fma):
+ *     d = gb - ga;  u = (float)(i + 1) * rN;  m = d * u;  gi = ga + m;  y = x * gi;
+ *     y > ceiling: y = ceiling, clamped += 1;  y < -ceiling: y = -ceiling, clamped += 1;
+ *     open_peak = max(open_peak, |x|);  peak_out = max(peak_out, |y|)
+ * A completed block, in block order, p = open_peak:
+ *     peak_in = max(peak_in, p);
+ *     not locked:  p >= gate: env = p, locked = 1
+ *     locked:      p < gate and p < env: held += 1;  else k = p >= env ? attack : release, t = p - env, t = k * t, env = env + t
+ *     g = locked ? min(max(target / max(env, emin), min_gain), max_gain) : initial_gain      (the IEEE fp32 division)
+ *     ga = gb, gb = g, open_peak = 0, fill = 0, blocks += 1;  out_peak[s * out_pitch + j] = p, out_gain[s * out_pitch + j] = g for the
+ *     j-th block the launch completed
+ * fparams row s is (initial_gain, target, emin, min_gain, max_gain, attack, release, gate, ceiling, rN), fp32 values computed by the
+ * caller (emin = target / max_gain, rN = 1 / N[s]).  The words behind the blocks a row completed are not written.  n_new[s] == 0 is
+ * an idle slot: neither its rows nor its parameters are looked at; when every slot is idle the call returns DMEL_OK and launches
+ * nothing.  NaN input is outside the contract.  DMEL_EINVAL, nothing launched, dmel_last_error naming the item: S outside [1, 65535],
+ * a NULL pointer, samples, state, out_peak, out_gain or table not 4-byte aligned, a negative stride or pitch, n_new[s] or first[s]
+ * outside [0, 2^30), N[s] outside [32, 4096], out_pitch below ceil(n_new[s] / N[s]) (the blocks the item can complete with N - 1
+ * samples carried), a value of fparams that is not finite and positive (the gate alone may be 0), attack, release or rN above 1,
+ * initial_gain outside [min_gain, max_gain].  first, n_new, N and fparams are HOST tables, copied as launch arguments into
+ * table_scratch (16 S 4-byte words of device memory, 4-byte aligned): the caller may overwrite them as soon as the call returns.  One
+ * workgroup of four waves per slot; a pass takes min(64, 4096 / N) blocks through LDS: read (16 bytes per lane on the aligned body of
+ * the range, single words at its ends) and raw block peaks, the recursion in block order, then ramp, gain and clamp back to the row.
+ * Plain vector stores, no atomics.  One profile record per launch in the family "level" (time and bytes in "small"). */
+int dmel_level_items(float* samples, int64_t row_stride, int S, const int64_t* first, const int64_t* n_new, const int32_t* N,
+                     const float* fparams /* S x 10 */, void* state /* (S, 16) words */, float* out_peak, float* out_gain,
+                     int64_t out_pitch, void* table_scratch, void* stream);
+
 /* Tones spliced into codec-rate audio, R parts in ONE launch (csrc/small_ops.hip): what decode sessions of a pool built with
  * tones=True send DTMF keys, beeps and call-progress tones with (models/stream_sessions.py: send_dtmf / send_tones), whose rule, tables
  * and caveats are utils/tones.py -- the kernel equals tones.render bit for bit.  Part r writes n[r] floats at dst[r].  Where src[r] is

@@ -625,6 +625,44 @@ int main() {
       CK(scan());
     }
     {
+      // the input leveller: tables of exactly S entries (10 S parameters), a table scratch of exactly 16 S words; its refusals read
+      // the host tables only
+      const int W = 9000;
+      auto smp = buf(3 * W), st = buf(3 * 16), pk = buf(3 * 90), gn = buf(3 * 90);
+      int64_t FI[3] = {5, -7, 1}, NN[3] = {8995, 0, 32 * 90};
+      int32_t BL[3] = {240, -1, 32};                  // the idle item's parameters are not looked at
+      float FP[30];
+      const float good[10] = {1.f, 0.5f, 0.5f / 31.6f, 0.1f, 31.6f, 1.f, 0.02f, 0.003f, 1.f, 1.f / 240.f};
+      for (int k = 0; k < 30; ++k) FP[k] = (k >= 10 && k < 20) ? NAN : good[k % 10];
+      FP[27] = 0.f; FP[29] = 1.f / 32.f;              // a gate of 0 is allowed
+      std::vector<uint32_t> tab(16 * 3);
+      int S = 3;
+      int64_t pitch = 90;
+      auto scan = [&]() { return dmel_level_items(smp.data(), W, S, FI, NN, BL, FP, st.data(), pk.data(), gn.data(), pitch, tab.data(), nullptr); };
+      CK(scan());
+      auto refused = [&](const char* item, const char* what) {
+        const int rc = scan();
+        if (rc != DMEL_EINVAL || !std::strstr(dmel_last_error(), item)) { std::printf("FAIL level_items accepted %s (%d: %s)\n", what, rc, dmel_last_error()); ++failures; }
+      };
+      S = 0; refused("0 items", "no item");
+      S = 65536; refused("65536 items", "more than 65535 items");
+      S = 3; NN[2] = -1; refused("item 2", "a negative sample count");
+      NN[2] = 32 * 90 + 1; refused("item 2", "more blocks than the output pitch");
+      NN[2] = 32 * 90; FI[0] = -1; refused("item 0", "a negative first column");
+      FI[0] = 5; BL[2] = 31; refused("item 2", "a block of 31 samples");
+      BL[2] = 32; BL[0] = 4097; refused("item 0", "a block of 4097 samples");
+      BL[0] = 240; FP[1] = 0.f; refused("item 0", "a target of 0");
+      FP[1] = 0.5f; FP[22] = INFINITY; refused("item 2", "an emin that is not finite");
+      FP[22] = 0.5f / 31.6f; FP[27] = -0.003f; refused("item 2", "a negative gate");
+      FP[27] = 0.f; FP[5] = 1.5f; refused("item 0", "attack above 1");
+      FP[5] = 1.f; FP[26] = 2.f; refused("item 2", "release above 1");
+      FP[26] = 0.02f; FP[20] = 40.f; refused("item 2", "initial_gain above max_gain");
+      FP[20] = 1.f; FP[3] = 2.f; refused("item 0", "min_gain above initial_gain");
+      FP[3] = 0.1f;
+      NN[0] = NN[2] = 0;                          // every item idle
+      CK(scan());
+    }
+    {
       // the tone splice: tables of exactly R entries, a segment table of exactly 8 n_segs words, a table scratch of exactly
       // 6 R + 5 n_segs int64; its refusals read the host tables only
       auto out = buf(4096), speech = buf(2048), sine = buf(8000), ramps = buf(48);

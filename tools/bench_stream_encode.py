@@ -73,7 +73,17 @@ plain --sessions form on the parent commit for the step time before the option e
 
 The same comparison for DTMF detection (a pool built with dtmf=True, every session opened with dtmf=True; the audio is noise with a
 keypad tone pair in every third push): equal ids, and exactly one "dtmf" / one "small" launch record more per step and nothing
-else.  No bound on the added time is set; the table shows it next to the plain pool of the same run.  APPENDS its table to --out."""
+else.  No bound on the added time is set; the table shows it next to the plain pool of the same run.  APPENDS its table to --out.
+
+    python tools/bench_stream_encode.py --sessions 16 --level [--label NAME] [--out profiles/sessions_level.txt]
+
+Sessions with an input leveller (a pool built with level=True, every session opened with level=True; lines at four levels 6 dB apart,
+noise with a tone burst in every third push) against the same sessions in a pool without the option and, for scale, in a pool with
+DTMF detection, the three interleaved in one process.  The leveller changes what the encoder sees: the ids of the levelled pool are
+checked against encode() of the host rule's output (utils/level.py: scan) for every clip, those of the plain pool against encode();
+exactly one "level" / one "small" launch record more per step and nothing else; exit status 1 where a check fails.  Run the plain
+--sessions form on the parent commit for the step time before the option existed.  No bound on the added time is set.  APPENDS its
+table to --out."""
 import argparse, json, os, statistics, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -95,6 +105,7 @@ ap.add_argument("--ragged", action="store_true", help="with --sessions: another 
 ap.add_argument("--park", action="store_true", help="with --sessions: snapshot + restore of all sessions, one launch against torch slices")
 ap.add_argument("--voice", action="store_true", help="with --sessions: sessions with voice detection against the same pool without it")
 ap.add_argument("--dtmf", action="store_true", help="with --sessions: sessions with DTMF detection against the same pool without it")
+ap.add_argument("--level", action="store_true", help="with --sessions: sessions with an input leveller against the same pool without it")
 ap.add_argument("--label", default="", help="with --sessions: names the table (the commit measured)")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
@@ -104,6 +115,7 @@ if args.out is None:
     args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                             "sessions_park.txt" if args.sessions and args.park else
                             "sessions_voice.txt" if args.sessions and args.voice else
+                            "sessions_level.txt" if args.sessions and args.level else
                             "sessions_dtmf.txt" if args.sessions and args.dtmf else
                             "sessions_channels.txt" if args.sessions and args.channels > 1 else
                             "sessions_pcm.txt" if args.sessions and args.sample_format == "s16" else
@@ -338,6 +350,117 @@ def sessions_detector_section(opt):
         f.write("\n".join(table) + "\n\n")
     print("\n".join(table), file=sys.stderr)
     print(json.dumps(r))
+
+
+def sessions_level_section():
+    """S staggered sessions with an input leveller against the same sessions in a pool without the option and, for scale, in a pool
+    with DTMF detection; the same audio, the same pushes.  The leveller changes what the encoder sees, so its ids are held to the host
+    rule: encode() of level.scan of each session's clip; then the launches per step of the pools"""
+    import math
+    from dmel_codec_amd import _lib
+    from dmel_codec_amd.utils import level as level_rule
+    S, n = args.sessions, args.chunk
+    t = torch.arange((args.pushes + 5) * n, device=dev, dtype=torch.float64) / SR
+    tone = ((torch.sin(2 * math.pi * 770 * t) + torch.sin(2 * math.pi * 1336 * t)) * 0.1).float()
+    talk = ((torch.arange(t.shape[0], device=dev) // n) % 3 == 0).float()       # a burst in every third push
+    lv = torch.tensor([0.25 * 2 ** (s % 4) for s in range(S)], device=dev)[:, None]        # the lines differ by up to 18 dB
+    audio = (torch.randn(S, t.shape[0], device=dev) * 0.01 + tone * talk) * lv
+    opts = {"plain": {}, "level": {"level": True}, "dtmf": {"dtmf": True}}
+    pools = {k: codec.encode_sessions(slots=S, max_push_samples=n, **o) for k, o in opts.items()}
+    slots = {k: [p.open(**opts[k]) for _ in range(S)] for k, p in pools.items()}
+    first = [n * (1 + s % 3) // 3 for s in range(S)]            # the starts differ by a third of a push
+    pos, ms, ids = [0] * S, {k: [] for k in pools}, {k: [[] for _ in range(S)] for k in ("plain", "level")}
+
+    def step(k, chunks):
+        out = pools[k].push({slots[k][s]: chunks[s] for s in range(S)})
+        return [out[slots[k][s]] for s in range(S)]
+
+    def chunks_of(size):
+        nonlocal pos
+        c = [audio[s, pos[s]:pos[s] + size[s]] for s in range(S)]
+        pos = [p + k for p, k in zip(pos, size)]
+        return c
+
+    order = list(pools)
+    for i in range(args.pushes):
+        chunks = chunks_of(first if i == 0 else [n] * S)
+        for k in order[i % 3:] + order[:i % 3]:                                       # none always goes first
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            got = step(k, chunks)
+            torch.cuda.synchronize()
+            if i >= args.warmup:
+                ms[k].append((time.perf_counter() - t0) * 1e3)
+            if k in ids:
+                for s in range(S):
+                    ids[k][s].append(got[s])
+    # the launches of a step, from the profile counters (their events cost time: counted behind the timed steps)
+    families, launches = ("level", "voice", "dtmf", "small", "stft_logmel", "conv_igemm"), {}
+    counted = [chunks_of([n] * S) for _ in range(4)]
+    _lib.prof_enable(True)
+    for k in pools:
+        launches[k] = []
+        for chunks in counted:
+            _lib.prof_reset()
+            got = step(k, chunks)
+            torch.cuda.synchronize()
+            launches[k].append({f: _lib.prof_read(f)["launches"] for f in families})
+            if k in ids:
+                for s in range(S):
+                    ids[k][s].append(got[s])
+    _lib.prof_enable(False)
+    _lib.prof_reset()
+    reports = pools["level"].levels()
+    for k, p in pools.items():
+        for s in range(S):
+            last = p.close(slots[k][s])
+            if k in ids:
+                ids[k][s].append(last)
+    # the ids: the plain pool's are encode()'s, the levelled pool's encode()'s of the host rule's output
+    same = {"plain": True, "level": True}
+    for s in range(S):
+        x = audio[s, :pos[s]]
+        y = level_rule.scan(x.cpu(), level_rule.LevelConfig(), None, SR)[0].to(dev)
+        for k, clip in (("plain", x), ("level", y)):
+            ref, lens = codec.encode(clip[None], torch.tensor([clip.shape[0]], device=dev))
+            same[k] = same[k] and torch.equal(torch.cat(ids[k][s], dim=1), ref[0, :, :int(lens[0])])
+
+    def one_more(opt):
+        return all(a[opt] == 0 and b[opt] == 1 and b["small"] == a["small"] + 1 and all(b[f] == a[f] for f in families if f not in (opt, "small"))
+                   for a, b in zip(launches["plain"], launches[opt]))
+    held = one_more("level") and one_more("dtmf")
+    r = {"sessions": S, "chunk_s": n / SR, "pushes": args.pushes, "warmup": args.warmup, "ids_equal_encode": bool(same["plain"]),
+         "ids_equal_encode_of_host_rule": bool(same["level"]), "label": args.label, "launches_per_step": {k: launches[k][0] for k in pools},
+         "one_more_launch_per_step": bool(held),
+         "gain_db": [round(min(rep.gain_db for rep in reports.values()), 2), round(max(rep.gain_db for rep in reports.values()), 2)],
+         "clamped": sorted({rep.clamped for rep in reports.values()}), "blocks": sorted({rep.blocks for rep in reports.values()})}
+    rows = []
+    for k, v in ms.items():
+        med = statistics.median(v)
+        r[k] = {"median_ms": round(med, 3), "p10_ms": round(pct(v, 0.1), 3), "p90_ms": round(pct(v, 0.9), 3), "n": len(v)}
+        rows.append(f"{S:8d}  {k:6s}  {med:9.3f}  {pct(v, 0.1):9.3f}  {pct(v, 0.9):9.3f}  {len(v):4d}  " +
+                    "  ".join(f"{f} {launches[k][0][f]}" for f in families))
+    r["added_median_ms"] = {k: round(r[k]["median_ms"] - r["plain"]["median_ms"], 3) for k in ("level", "dtmf")}
+    rows.append(f"{S:8d}  the leveller adds {r['added_median_ms']['level']:.3f} ms to the median step, the DTMF detector (for scale) "
+                f"{r['added_median_ms']['dtmf']:.3f} ms; each pool with an option launches exactly one kernel more per step than the plain one: {held}")
+    rows.append(f"{S:8d}  ids of the plain pool equal encode(): {same['plain']}; ids of the levelled pool equal encode() of the host rule's "
+                f"output (level.scan of each clip): {same['level']}")
+    rows.append(f"{S:8d}  the sessions saw {r['blocks']} blocks each, ended at gains of {r['gain_db'][0]} .. {r['gain_db'][1]} dB and clamped "
+                f"{r['clamped']} samples (lines at four levels 6 dB apart, a tone burst in every third push)")
+    table = [(f"[{args.label}] " if args.label else "") + "encode sessions with an input leveller, 0.32 s pushes of 24 kHz audio, starts staggered by a "
+             f"third of a push, 80 mel / 8 groups / 70 channels / 20 layers (tools/bench_stream_encode.py --sessions {S} --level)",
+             f"wall time of one step (one push for every stream) incl. host synchronisation, {args.pushes - args.warmup} steady-state steps, the "
+             "three pools interleaved in one process;",
+             "plain = encode_sessions(S), level / dtmf = encode_sessions(S, level=True / dtmf=True) with every session opened with the option; "
+             "launches: records of the profile counters in one step",
+             "sessions  pool    median ms     p10 ms     p90 ms     n  launches of one step"] + rows
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "a") as f:
+        f.write("\n".join(table) + "\n\n")
+    print("\n".join(table), file=sys.stderr)
+    print(json.dumps(r))
+    if not (same["plain"] and same["level"] and held):
+        sys.exit(1)
 
 
 def sessions_resample_section():
@@ -575,6 +698,11 @@ if args.voice and not args.sessions:
     ap.error("--voice needs --sessions")
 if args.dtmf and not args.sessions:
     ap.error("--dtmf needs --sessions")
+if args.level and not args.sessions:
+    ap.error("--level needs --sessions")
+if args.sessions and args.level:
+    sessions_level_section()
+    sys.exit(0)
 if args.sessions and (args.voice or args.dtmf):
     sessions_detector_section("voice" if args.voice else "dtmf")
     sys.exit(0)
