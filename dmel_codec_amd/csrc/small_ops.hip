@@ -2066,6 +2066,293 @@ extern "C" int dmel_level_items(float* samples, int64_t row_stride, int S, const
 
 namespace dmel {
 
+// ---- echo cancellation (block NLMS) on codec-rate samples (include/dmel_hip.h: dmel_echo_items; the rule and the state row: utils/echo.py)
+// Row s of the table is (first, n_new, far pointer lo, hi, far_n, L, N, delay, mu, eps, far_floor, double_talk, meter, fN, 0, 0),
+// sixteen 4-byte words; workgroup s owns slot s, appends the slot's new far samples to the ring in its state row and re-writes its new
+// samples in place.  Positions are counted as in level_kernel: the stream began `fill` samples in front of column `first`, block j of
+// the launch holds positions [j N, (j + 1) N), of which [fill, fill + n_new) exist.  A pass takes 2048 / N blocks through LDS: the far
+// window of all of them (L - 1 samples of history in front), their d and e (the open block's first `fill` of each from the state row),
+// then E and max |xd| of every block the pass completes -- 8 chains per block, all blocks at once, outside the serial part.  Then block
+// by block, w fixed in LDS: (a) the (sample, segment) partial dots over the workgroup -- w[k] a broadcast read, xd[t - k] consecutive
+// across lanes -- then the fixed tree, e to LDS and to the row; (b) wave 0 sums d^2 and e^2 (16 lanes, one chain each) and lane 0
+// decides and computes the step; (c) every thread updates its taps k = tid + 256 r, eight chains over the block each.  w is read from
+// the state row once and written once.  Every product and sum is rounded on its own (fp contract(off)); the division is the correctly
+// rounded one.  Plain stores, no atomics.
+constexpr int kEchoWords = 16, kEchoMinTaps = 64, kEchoMaxTaps = 2048, kEchoMinBlock = 16, kEchoMaxBlock = 256, kEchoMaxDelay = 24000;
+constexpr int kEchoRing = 65536, kEchoPass = 2048;
+constexpr int kEchoW = 16, kEchoE = kEchoW + kEchoMaxTaps, kEchoD = kEchoE + kEchoMaxBlock, kEchoFar = kEchoD + kEchoMaxBlock;
+constexpr int kEchoRow = kEchoFar + kEchoRing;
+constexpr int kEchoMaxAhead = kEchoRing - kEchoMaxDelay - kEchoMaxTaps - kEchoMaxBlock;
+__device__ __forceinline__ float echo_tree(const float* s) {
+  return ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
+}
+__global__ __launch_bounds__(256) void echo_kernel(float* __restrict__ samples, int64_t row_stride, const uint32_t* __restrict__ tab,
+                                                   uint32_t* state, int64_t state_pitch, float* __restrict__ out_in,
+                                                   float* __restrict__ out_res, int64_t out_pitch) {
+#pragma clang fp contract(off)
+  __shared__ float w[kEchoMaxTaps], xw[kEchoMaxTaps + kEchoPass], dl[kEchoPass], el[kEchoPass], part[2048];
+  __shared__ float Eb[kEchoPass / kEchoMinBlock], mxb[kEchoPass / kEchoMinBlock];
+  __shared__ float dec_step;
+  __shared__ int dec_adapt, red_missing[4];
+  const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint32_t* row = tab + (size_t)s * kEchoWords;
+  const int n_new = (int)row[1], far_n = (int)row[4];
+  if (n_new <= 0 && far_n <= 0) return;                 // idle (uniform: in front of the first barrier)
+  const int64_t first = (int64_t)(int32_t)row[0];
+  const float* far = reinterpret_cast<const float*>(((uint64_t)row[3] << 32) | (uint64_t)row[2]);
+  const int L = (int)row[5], N = (int)row[6], delay = (int)row[7];
+  const float mu = __uint_as_float(row[8]), eps = __uint_as_float(row[9]), far_floor = __uint_as_float(row[10]);
+  const float dtalk = __uint_as_float(row[11]), meter = __uint_as_float(row[12]), fN = __uint_as_float(row[13]);
+  uint32_t* srow = state + (int64_t)s * state_pitch;
+  float* frow = reinterpret_cast<float*>(srow);
+  float* ring = frow + kEchoFar;
+  const int64_t T = (int64_t)(int32_t)srow[0], F = (int64_t)(int32_t)srow[1];
+  int fill = (int)srow[2];
+  if ((unsigned)fill >= (unsigned)N) fill = 0;          // no row the rule wrote; keeps every index below inside the launch's columns
+  // the far samples of the step: behind the ones the ring has; one whose turn has passed is dropped (its word holds the 0 of its turn)
+  const int64_t room = T + kEchoMaxAhead - F;
+  const int m = (int)max((int64_t)0, min((int64_t)far_n, room));
+  for (int i = tid; i < m; i += 256) {
+    const int64_t j = F + i;
+    if (j >= T - delay) ring[j & (kEchoRing - 1)] = far[i];
+  }
+  const int64_t F2 = F + m;
+  if (n_new <= 0) {                                     // far samples alone (uniform)
+    if (tid == 0) srow[1] = (uint32_t)F2;
+    return;
+  }
+  // a far sample that is not there at its turn reads as 0 from now on
+  int my_missing = 0;
+  for (int i = tid; i < n_new; i += 256) {
+    const int64_t j = T + i - delay;
+    if (j >= F2) { ring[j & (kEchoRing - 1)] = 0.0f; ++my_missing; }
+  }
+  for (int k = tid; k < L; k += 256) w[k] = frow[kEchoW + k];
+  __syncthreads();
+  // the recursion's state: thread 0 alone advances it
+  float sd = __uint_as_float(srow[7]), se = __uint_as_float(srow[8]);
+  int blocks = (int)srow[3], adapted = (int)srow[4], frozen = (int)srow[5];
+  const int64_t end = (int64_t)fill + n_new;            // positions [fill, end) exist
+  const int64_t nblk = (end + N - 1) / N, done = end / N;
+  float* src = samples + (int64_t)s * row_stride + first - fill;              // position p is src[p]; only [fill, end) is touched
+  float* oin = out_in + (int64_t)s * out_pitch;
+  float* ores = out_res + (int64_t)s * out_pitch;
+  const int PB = kEchoPass / N, n8 = N >> 3, l8 = L >> 3, nw = L + N - 1;
+  for (int64_t b0 = 0; b0 < nblk; b0 += PB) {
+    const int nb = (int)min((int64_t)PB, nblk - b0);
+    const int nd = (int)max((int64_t)0, min((int64_t)nb, done - b0));          // the whole blocks of the pass
+    const int64_t base = b0 * N;                        // dl[q] is position base + q; q in [lo, hi) is new
+    const int lo = (int)(max((int64_t)fill, base) - base), hi = (int)(min(end, base + (int64_t)nb * N) - base);
+    const int64_t j0 = T - fill + base - delay - (L - 1);                      // xw[q] = x[j0 + q]: xd of position q - (L - 1)
+    for (int q = tid; q < L - 1 + hi; q += 256) {
+      const int64_t j = j0 + q;
+      xw[q] = j >= 0 ? ring[j & (kEchoRing - 1)] : 0.0f;
+    }
+    for (int q = tid; q < hi; q += 256) {
+      if (q >= lo) {
+        dl[q] = src[base + q];
+      } else {                                          // the open block's samples of earlier launches (first pass only)
+        dl[q] = frow[kEchoD + q];
+        el[q] = frow[kEchoE + q];
+      }
+    }
+    __syncthreads();
+    // E and max |xd| of every whole block of the pass: chain (block c / 8, segment c % 8)
+    for (int c = tid; c < nd * 8; c += 256) {
+      const int q = c & 7;
+      const float* v = xw + (c >> 3) * N;
+      float acc = 0.0f, mx = 0.0f;
+      for (int k = q * nw / 8, z = (q + 1) * nw / 8; k < z; ++k) {
+        const float x = v[k];
+        const float p = x * x;
+        acc = acc + p;
+        mx = fmaxf(mx, fabsf(x));
+      }
+      part[c] = acc;
+      part[1024 + c] = mx;
+    }
+    __syncthreads();
+    for (int j = tid; j < nd; j += 256) {
+      Eb[j] = echo_tree(part + 8 * j);
+      float mx = part[1024 + 8 * j];
+      for (int q = 1; q < 8; ++q) mx = fmaxf(mx, part[1024 + 8 * j + q]);
+      mxb[j] = mx;
+    }
+    __syncthreads();
+    for (int jb = 0; jb < nb; ++jb) {
+      const int pa = max(lo, jb * N), pz = min(hi, (jb + 1) * N), ni = pz - pa;   // the block's new positions
+      // (a) partial dots: pair c is (sample c % ni, segment c / ni)
+      for (int c = tid; c < ni * 8; c += 256) {
+        const int seg = c / ni, i = c - seg * ni;
+        const float* xv = xw + (L - 1) + pa + i;        // xv[-k] = xd[t - k]
+        float acc = 0.0f;
+        for (int k = seg * l8, z = k + l8; k < z; ++k) {
+          const float p = w[k] * xv[-k];
+          acc = acc + p;
+        }
+        part[seg * 256 + i] = acc;
+      }
+      __syncthreads();
+      if (tid < ni) {
+        float sg[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) sg[q] = part[q * 256 + tid];
+        const float e = dl[pa + tid] - echo_tree(sg);
+        el[pa + tid] = e;
+        src[base + pa + tid] = e;
+      }
+      __syncthreads();
+      if (jb >= nd) break;                              // the block the launch leaves open (the last one; uniform)
+      // (b) the block's energies and the decision
+      if (wave == 0) {
+        const float* db = dl + jb * N;
+        const float* eb = el + jb * N;
+        float acc = 0.0f, md = 0.0f;
+        if (lane < 16) {
+          const float* v = lane < 8 ? db : eb;
+          for (int i = (lane & 7) * n8, z = i + n8; i < z; ++i) {
+            const float p = v[i] * v[i];
+            acc = acc + p;
+          }
+        }
+        for (int i = lane; i < N; i += 64) md = fmaxf(md, fabsf(db[i]));
+        for (int o = 32; o; o >>= 1) md = fmaxf(md, __shfl_xor(md, o));
+        float sa[8], sb[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) { sa[q] = __shfl(acc, q); sb[q] = __shfl(acc, 8 + q); }
+        if (lane == 0) {
+          const float Ed = echo_tree(sa), Ee = echo_tree(sb), E = Eb[jb];
+          const float gt = dtalk * mxb[jb];
+          const bool adapt = E >= far_floor && !(dtalk > 0.0f && md > gt);
+          if (adapt) {
+            float t = fN * E;
+            t = t + eps;
+            dec_step = mu / t;
+            adapted += 1;
+          } else {
+            frozen += 1;
+          }
+          dec_adapt = adapt ? 1 : 0;
+          float t = Ed - sd;
+          t = meter * t;
+          sd = sd + t;
+          t = Ee - se;
+          t = meter * t;
+          se = se + t;
+          blocks += 1;
+          oin[b0 + jb] = Ed;
+          ores[b0 + jb] = Ee;
+        }
+      }
+      __syncthreads();
+      // (c) the taps
+      if (dec_adapt) {
+        const float step = dec_step;
+        const float* eb = el + jb * N;
+        for (int k = tid; k < L; k += 256) {
+          const float* xv = xw + (L - 1) + jb * N - k;  // xv[i] = xd[t0 + i - k]
+          float sg[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+          for (int i = 0; i < n8; ++i) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+              const float p = eb[q * n8 + i] * xv[q * n8 + i];
+              sg[q] = sg[q] + p;
+            }
+          }
+          const float t = step * echo_tree(sg);
+          w[k] = w[k] + t;
+        }
+      }
+      __syncthreads();                                  // the next block reads w; the next decision overwrites dec_*
+    }
+    if (b0 + nb >= nblk) {                              // the last pass: the open block's d and e go to the state row, 0 behind them
+      const int open = (int)(end - done * N), at = (int)(done * N - base);
+      if (tid < kEchoMaxBlock) {
+        frow[kEchoE + tid] = tid < open ? el[at + tid] : 0.0f;
+        frow[kEchoD + tid] = tid < open ? dl[at + tid] : 0.0f;
+      }
+    }
+    __syncthreads();                                    // the next pass overwrites the window and the block's rows
+  }
+  for (int k = tid; k < L; k += 256) frow[kEchoW + k] = w[k];
+  for (int o = 32; o; o >>= 1) my_missing += __shfl_xor(my_missing, o);
+  if (lane == 0) red_missing[wave] = my_missing;
+  __syncthreads();
+  if (tid == 0) {
+    srow[0] = (uint32_t)(T + n_new); srow[1] = (uint32_t)F2; srow[2] = (uint32_t)(end - done * N); srow[3] = (uint32_t)blocks;
+    srow[4] = (uint32_t)adapted; srow[5] = (uint32_t)frozen;
+    srow[6] = (uint32_t)((int)srow[6] + red_missing[0] + red_missing[1] + red_missing[2] + red_missing[3]);
+    srow[7] = __float_as_uint(sd); srow[8] = __float_as_uint(se);
+  }
+}
+
+}  // namespace dmel
+
+extern "C" int dmel_echo_items(float* samples, int64_t row_stride, int S, const int64_t* first, const int64_t* n_new,
+                               const void* const* far, const int64_t* far_n, const int32_t* iparams, const float* fparams, void* state,
+                               int64_t state_pitch, float* out_in, float* out_res, int64_t out_pitch, void* table_scratch, void* stream) {
+  using namespace dmel;
+  DMEL_CHECK_ARG(samples && first && n_new && far && far_n && iparams && fparams && state && out_in && out_res && table_scratch,
+                 "echo_items: NULL argument");
+  DMEL_CHECK_ARG(S >= 1 && S <= 65535, "echo_items: %d items, expected 1 .. 65535", S);
+  DMEL_CHECK_ARG((((uintptr_t)samples | (uintptr_t)state | (uintptr_t)out_in | (uintptr_t)out_res | (uintptr_t)table_scratch) & 3) == 0,
+                 "echo_items: samples, state, out_in, out_res or table_scratch is not 4-byte aligned");
+  DMEL_CHECK_ARG(row_stride >= 0 && out_pitch >= 0, "echo_items: negative row stride %lld or output pitch %lld", (long long)row_stride,
+                 (long long)out_pitch);
+  DMEL_CHECK_ARG(state_pitch >= kEchoRow, "echo_items: a state pitch of %lld words, expected at least %d", (long long)state_pitch, kEchoRow);
+  static const char* const kNames[6] = {"mu", "eps", "far_floor", "double_talk", "meter", "fN"};
+  std::vector<uint32_t> tab((size_t)kEchoWords * S, 0u);
+  int64_t live = 0;
+  double flops = 0.0, bytes = 0.0;
+  for (int s = 0; s < S; ++s) {
+    const int64_t n = n_new[s], m = far_n[s];
+    DMEL_CHECK_ARG(n >= 0 && n <= 0x3fffffff, "echo_items: item %d: %lld new samples, expected 0 .. 2^30 - 1", s, (long long)n);
+    DMEL_CHECK_ARG(m >= 0 && m <= 0x3fffffff, "echo_items: item %d: %lld far samples, expected 0 .. 2^30 - 1", s, (long long)m);
+    if (n == 0 && m == 0) continue;                     // idle: its parameters are not looked at (the table row stays 0)
+    DMEL_CHECK_ARG(m == 0 || (far[s] && ((uintptr_t)far[s] & 3) == 0), "echo_items: item %d: %lld far samples at a NULL or unaligned pointer",
+                   s, (long long)m);
+    DMEL_CHECK_ARG(n == 0 || (first[s] >= 0 && first[s] <= 0x3fffffff), "echo_items: item %d: first column %lld, expected 0 .. 2^30 - 1", s,
+                   (long long)first[s]);
+    const int32_t L = iparams[3 * s], N = iparams[3 * s + 1], delay = iparams[3 * s + 2];
+    DMEL_CHECK_ARG(L >= kEchoMinTaps && L <= kEchoMaxTaps && L % 64 == 0, "echo_items: item %d: %d taps, expected a multiple of 64 in %d .. %d",
+                   s, L, kEchoMinTaps, kEchoMaxTaps);
+    DMEL_CHECK_ARG(N >= kEchoMinBlock && N <= kEchoMaxBlock && N % 8 == 0,
+                   "echo_items: item %d: a block of %d samples, expected a multiple of 8 in %d .. %d", s, N, kEchoMinBlock, kEchoMaxBlock);
+    DMEL_CHECK_ARG(delay >= 0 && delay <= kEchoMaxDelay, "echo_items: item %d: a delay of %d samples, expected 0 .. %d", s, delay, kEchoMaxDelay);
+    const int64_t most = (n + N - 1) / N;               // whatever the open block holds (at most N - 1 samples)
+    DMEL_CHECK_ARG(out_pitch >= most, "echo_items: item %d: %lld samples can complete %lld blocks, which exceed the output pitch %lld", s,
+                   (long long)n, (long long)most, (long long)out_pitch);
+    const float* fp = fparams + (size_t)6 * s;
+    for (int k = 0; k < 6; ++k)                         // far_floor and double_talk may be 0
+      DMEL_CHECK_ARG(std::isfinite(fp[k]) && (fp[k] > 0.0f || ((k == 2 || k == 3) && fp[k] == 0.0f)),
+                     "echo_items: item %d: float parameter %d (%s) is not finite and positive", s, k, kNames[k]);
+    DMEL_CHECK_ARG(fp[0] < 2.0f && fp[4] <= 1.0f, "echo_items: item %d: mu %g is not below 2 or meter %g is above 1", s, (double)fp[0],
+                   (double)fp[4]);
+    DMEL_CHECK_ARG(fp[5] == (float)N, "echo_items: item %d: fN %g is not the block of %d samples", s, (double)fp[5], N);
+    uint32_t* it = tab.data() + (size_t)kEchoWords * s;
+    const uint64_t fptr = m ? (uint64_t)(uintptr_t)far[s] : 0;
+    it[0] = (uint32_t)(n ? first[s] : 0); it[1] = (uint32_t)n; it[2] = (uint32_t)fptr; it[3] = (uint32_t)(fptr >> 32); it[4] = (uint32_t)m;
+    it[5] = (uint32_t)L; it[6] = (uint32_t)N; it[7] = (uint32_t)delay;
+    std::memcpy(it + 8, fp, 6 * sizeof(float));
+    ++live;
+    flops += 4.0 * (double)L * (double)n;               // the dots and the tap updates
+    bytes += 8.0 * (double)n + 8.0 * (double)m + 8.0 * (double)most + 8.0 * (kEchoFar + L);
+  }
+  if (live == 0) return DMEL_OK;                        // every item idle
+  hipStream_t st = (hipStream_t)stream;
+  DMEL_TRY(launch_table_put(tab.data(), tab.size() * sizeof(uint32_t), table_scratch, st));
+  {
+    // "small" carries the time and the bytes; the second scope only counts: one record per canceller launch (dmel_prof_read("echo"))
+    ProfScope ps("small", st, flops, bytes), count("echo", st, 0.0, 0.0);
+    hipLaunchKernelGGL(echo_kernel, dim3((unsigned)S), dim3(256), 0, st, samples, row_stride, static_cast<const uint32_t*>(table_scratch),
+                       static_cast<uint32_t*>(state), state_pitch, out_in, out_res, out_pitch);
+  }
+  DMEL_HIP(hipGetLastError());
+  return DMEL_OK;
+}
+
+namespace dmel {
+
 // ---- tones spliced into codec-rate audio (include/dmel_hip.h: dmel_tone_items; the rule: utils/tones.py) -----------------------------
 // The table holds R part rows of (dst, src, n, first tile, first segment record, segments), six int64, and behind them the launch's
 // segment records of five int64: the eight 4-byte words of the entry's table (f1, f2, a1, a2, on, off, ramp, ramp_off) and the

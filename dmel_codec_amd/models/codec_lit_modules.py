@@ -400,7 +400,8 @@ class VQGAN(nn.Module):
             yield ids
 
     def encode_sessions(self, slots: int, max_push_samples: int = 7680, sample_rate: Optional[int] = None, sample_rates=(),
-                        voice: bool = False, dtmf: bool = False, level: bool = False):
+                        voice: bool = False, dtmf: bool = False, level: bool = False, echo: bool = False,
+                        far_room_samples: int = 24000):
         """A pool of `slots` INDEPENDENT incremental encodes served by one streaming step: sessions open, receive their own number of
         samples per step (at most max_push_samples), stall and close on their own -- what streaming_encoder(batch=B), B streams in
         lockstep, cannot do -- and each one's concatenated ids are the bits of encode() on its own clip.  One STFT launch, one encoder
@@ -417,9 +418,13 @@ class VQGAN(nn.Module):
         (utils/dtmf.py has the rule).  level=True adds an input leveller row per slot: pool.open(level=True | LevelConfig) starts a
         session's causal block AGC, which re-writes the session's codec-rate samples in place in one more launch for all slots of a
         step, in front of the STFT launch, and is read with pool.levels(); such a session's ids are the bits of encode() of
-        level.scan of its clip (utils/level.py has the rule).  See models/stream_sessions.py: EncodeSessions."""
+        level.scan of its clip (utils/level.py has the rule).  echo=True adds an echo canceller row per slot: pool.open(echo=True |
+        EchoConfig) starts a session's block NLMS filter, fed the far end with pool.push(audio, far={slot: samples}) -- at most
+        far_room_samples ahead of the slot's own -- which cancels the session's codec-rate samples in place in one more launch for all
+        slots of a step, in front of the DTMF and leveller launches, and is read with pool.echoes() (utils/echo.py has the rule).
+        See models/stream_sessions.py: EncodeSessions."""
         from .stream_sessions import EncodeSessions
-        return EncodeSessions(self, slots, max_push_samples, sample_rate, sample_rates, voice, dtmf, level)
+        return EncodeSessions(self, slots, max_push_samples, sample_rate, sample_rates, voice, dtmf, level, echo, far_room_samples)
 
     # ------------------------------------------------------------------------------ decode side
     @torch.no_grad()

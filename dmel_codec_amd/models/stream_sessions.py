@@ -21,6 +21,7 @@ import torch
 from .. import _lib
 from ..utils import crossfade, pcm
 from ..utils import dtmf as dtmf_rule
+from ..utils import echo as echo_rule
 from ..utils import level as level_rule
 from ..utils import tones as tone_rule
 from ..utils import voice as voice_rule
@@ -142,6 +143,31 @@ class EncodeSessions(ParkingPool):
     served: look-ahead limiting, RMS or loudness (LUFS) metering, the lockstep StreamingEncoder and whole-clip encode() (callers
     have level.scan / level.level_items), output gain on decode pools, a DTMF detector that reads levelled samples.
 
+    What the agent says into the line comes back through the hybrid or the speakerphone: its own keys are read by dtmf(), its own
+    speech trips the voice detector, the leveller locks onto it.  A pool built with echo=True serves sessions opened with
+    open(echo=True | EchoConfig), each with an echo canceller of its own: a block NLMS adaptive FIR of up to 2048 taps with zero
+    added latency on the same codec-rate samples (the rule, its state row and its caveats: utils/echo.py, which is also the host
+    reference the pool is tested against bit for bit).  push(audio, final, far={slot: (m,) f32 device tensor}) hands such a slot
+    the far-end samples at the codec's rate -- naturally the codec-rate f32 audio of the decode session on the same call -- which
+    have their own counter and may run up to far_room_samples ahead of the samples the slot had before the push; a slot may
+    get far samples with an empty audio push, or audio with no far samples.  In front of the DTMF and leveller launches of a step, ONE dmel_echo_items
+    launch appends every named slot's far samples to its history and re-writes in place exactly the columns the slot gained: the
+    order of a step is convert, resample, echo, DTMF, level, STFT, so the DTMF detector and the leveller of an echo session see
+    the cancelled samples; sessions without a canceller see what they saw, and a step without far or new samples for such a slot
+    launches what it did.  Contract: the ids of an echo session are the bits of encode(e, len) with e = echo.scan(x, far,
+    config)[0] over its codec-rate clip x, however both streams were cut (every far sample pushed no later than the sample that
+    needs it); with a leveller as well, of encode(level.scan(e, ...)[0]); its DTMF report is dtmf.scan's over e.  The state is
+    one row of 68112 words per slot (`echo`: counters and meters, the taps, the open block, a ring of far samples), zeroed with
+    the slot's other rows; its first 2576 words and the live part of the ring travel with snapshot / restore as up to three more
+    segments, the far samples queued ahead included; push() returns what it returns and never syncs.  echoes() -> {slot:
+    EchoReport} (ERLE, adapted and frozen blocks, missing far samples) for every slot with a canceller that is open or ended in
+    the most recent push, from ONE device-to-host copy of the rows' headers, the only sync and only when asked;
+    echo_blocks(slot) -> (block_in, block_res), device fp32 views of the energies of the blocks the slot's last push completed.
+    A pool built without echo=True allocates and launches exactly what it did, refuses open(echo=), push(far=) and a snapshot
+    that carries a canceller; a session without one snapshots to the bytes it always did.  Not served: a residual suppressor,
+    comfort noise, a bulk-delay search, stereo far ends, far streams at another rate or format, decode pools, the lockstep
+    StreamingEncoder and whole-clip encode() (callers have echo.scan / echo.echo_items).
+
     Only encoders the one-launch streaming kernel takes (residual channels in (32, 80], no condition, no output projection,
     dilations <= 8, fp32): anything else is refused at construction.
 
@@ -150,7 +176,8 @@ class EncodeSessions(ParkingPool):
     process -- a streaming decode, for example -- must call dmel_stft_set_exclusive_cu(1) first, exactly as pipeline.CodecLanes does."""
 
     def __init__(self, codec, slots: int, max_push_samples: int = 7680, sample_rate: Optional[int] = None,
-                 sample_rates: Iterable[int] = (), voice: bool = False, dtmf: bool = False, level: bool = False):
+                 sample_rates: Iterable[int] = (), voice: bool = False, dtmf: bool = False, level: bool = False,
+                 echo: bool = False, far_room_samples: int = 24000):
         enc, tr = codec.encoder, codec.encode_mel_transform
         if sample_rate is not None and int(sample_rate) != int(tr.sample_rate):
             raise NotImplementedError(f"sessions run at the codec's own rate ({tr.sample_rate} Hz); resample in front (StreamResampler), "
@@ -222,13 +249,22 @@ class EncodeSessions(ParkingPool):
         self.lcfg: List[Optional[level_rule.LevelConfig]] = [None] * self.S      # the slot's leveller (None: none)
         self._level_n = [0] * self.S                  # blocks the slot's last push completed: the valid words of its peak / gain rows
         self._level_ended: set = set()                # slots with a leveller that ended in the most recent push
+        if not isinstance(echo, bool):
+            raise ValueError(f"echo must be a bool (a session's config goes to open(echo=)), got {echo!r}")
+        if isinstance(far_room_samples, bool) or not isinstance(far_room_samples, int) or not 0 <= far_room_samples <= echo_rule.MAX_AHEAD:
+            raise ValueError(f"far_room_samples must be an integer in [0, {echo_rule.MAX_AHEAD}], got {far_room_samples!r}")
+        self.echo_on, self.far_room = echo, far_room_samples         # the pool keeps canceller rows: sessions may open with echo=
+        self.ecfg: List[Optional[echo_rule.EchoConfig]] = [None] * self.S        # the slot's canceller (None: none)
+        self._far = [0] * self.S                      # far samples pushed to the slot (its own samples: sched[s].samples)
+        self._echo_n = [0] * self.S                   # blocks the slot's last push completed: the valid words of its in / res rows
+        self._echo_ended: set = set()                 # slots with a canceller that ended in the most recent push
 
     def tokens_emitted(self, slot: int) -> int:
         self._check_open(slot)
         return self.sched[slot].tokens
 
     def open(self, sample_rate: Optional[int] = None, sample_format: str = "f32", channels: int = 1,
-             channel: Optional[int] = None, voice=None, dtmf=None, level=None) -> int:
+             channel: Optional[int] = None, voice=None, dtmf=None, level=None, echo=None) -> int:
         """take a free slot: fresh schedule, state zeroed before its first push.  sample_rate: the rate this session's pushes arrive
         at, one of the declared `sample_rates` (None: the codec's).  sample_format: "f32", "s16" for torch.int16 pushes (16-bit
         signed PCM, x / 32768), or "ulaw" / "alaw" for torch.uint8 pushes (G.711 codes).  channels: 1 .. 8; above 1 the pushes are
@@ -236,19 +272,22 @@ class EncodeSessions(ParkingPool):
         (the defaults of utils/voice.py) or a VoiceConfig starts the session's voice-activity detector, on a pool built with
         voice=True.  dtmf: True (the defaults of utils/dtmf.py) or a DtmfConfig starts the session's DTMF key detector, on a pool
         built with dtmf=True.  level: True (the defaults of utils/level.py) or a LevelConfig starts the session's input leveller, on
-        a pool built with level=True: the encoder then sees the levelled samples.  Raises when every slot is taken; a refused open
-        takes no slot."""
+        a pool built with level=True: the encoder then sees the levelled samples.  echo: True (the defaults of utils/echo.py) or an
+        EchoConfig starts the session's echo canceller, on a pool built with echo=True: push(far=) then takes its far-end samples.
+        Raises when every slot is taken; a refused open takes no slot."""
         rate = self.codec_rate if sample_rate is None else int(sample_rate)
         pick = self._check_wire(rate, sample_format, channels, channel)
         cfg = self._check_voice(voice_rule.as_config(voice))
         keys = self._check_dtmf(dtmf_rule.as_config(dtmf))
         lev = self._check_level(level_rule.as_config(level))
+        ec = self._check_echo(echo_rule.as_config(echo))
         s = self._first_free()
         self._occupy(s, EncodeSchedule(self.geo), 0, rate, sample_format, channels)
         self.s0[s], self.tail[s], self.pick[s] = 0, 0, pick
         self.vcfg[s], self._voice_n[s] = cfg, 0
         self.dcfg[s], self._dtmf_n[s] = keys, 0
         self.lcfg[s], self._level_n[s] = lev, 0
+        self.ecfg[s], self._echo_n[s], self._far[s] = ec, 0, 0
         return s
 
     def _check_voice(self, cfg: Optional[voice_rule.VoiceConfig]) -> Optional[voice_rule.VoiceConfig]:
@@ -274,6 +313,38 @@ class EncodeSessions(ParkingPool):
                 raise ValueError("level on a pool built without level=True: it has no leveller rows")
             cfg.block(self.codec_rate)
         return cfg
+
+    def _check_echo(self, cfg: Optional[echo_rule.EchoConfig]) -> Optional[echo_rule.EchoConfig]:
+        """a session's canceller config, refused here for open() and for restore() alike"""
+        if cfg is not None and not self.echo_on:
+            raise ValueError("echo on a pool built without echo=True: it has no canceller rows")
+        return cfg
+
+    def _validate_far(self, audio: Mapping[int, torch.Tensor], far) -> Dict[int, torch.Tensor]:
+        """the far samples of a step, refused like the audio: before any state changes and before any device call"""
+        if far is None:
+            return {}
+        if not self.echo_on:
+            raise ValueError("far samples on a pool built without echo=True: it has no canceller rows")
+        dev = next(iter(audio.values())).device
+        out = {}
+        for slot, x in far.items():
+            if slot not in audio:
+                raise ValueError(f"slot {slot!r} has far samples but is not among the pushed slots (an empty push is fine)")
+            if self.ecfg[slot] is None:
+                raise ValueError(f"slot {slot} has far samples and no canceller (open(echo=))")
+            if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.ndim != 1:
+                raise ValueError(f"slot {slot}: far samples are a 1-D fp32 tensor at the codec's rate, got "
+                                 f"{tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__} {getattr(x, 'dtype', '')}")
+            if x.device != dev:
+                raise ValueError(f"slot {slot}: far samples on {x.device}, audio on {dev}")
+            ahead = self._far[slot] + x.shape[0] - self.sched[slot].samples
+            if ahead > self.far_room:
+                raise ValueError(f"slot {slot}: {x.shape[0]} far samples would run {ahead} ahead of the {self.sched[slot].samples} samples "
+                                 f"the slot has seen before this push: far_room_samples = {self.far_room}")
+            if x.shape[0]:
+                out[slot] = x.contiguous()
+        return out
 
     def _validate(self, audio: Mapping[int, torch.Tensor], final) -> Dict[int, torch.Tensor]:
         """everything that can be refused, before any state changes and before any device call"""
@@ -345,6 +416,13 @@ class EncodeSessions(ParkingPool):
                             level_peak=torch.zeros(self.S, pitch, dtype=torch.float32, device=dev),
                             level_gain=torch.zeros(self.S, pitch, dtype=torch.float32, device=dev),
                             level_tab=torch.empty(level_rule.TABLE_WORDS * self.S, dtype=torch.int32, device=dev))
+        if self.echo_on:                              # dmel_echo_items: a state row per slot (the ring of far samples in it), the step's
+            #                                           block energies (blocks of 16 samples or more), 16 words per slot of the table
+            pitch = self.codec_push // echo_rule.MIN_BLOCK + 2
+            self.buf.update(echo=torch.zeros(self.S, echo_rule.ROW_WORDS, dtype=torch.int32, device=dev),
+                            echo_in=torch.zeros(self.S, pitch, dtype=torch.float32, device=dev),
+                            echo_res=torch.zeros(self.S, pitch, dtype=torch.float32, device=dev),
+                            echo_tab=torch.empty(echo_rule.TABLE_WORDS * self.S, dtype=torch.int32, device=dev))
 
     def _prepare_slot(self, s: int) -> None:
         super()._prepare_slot(s)
@@ -354,6 +432,8 @@ class EncodeSessions(ParkingPool):
             self.buf["dtmf"][s].zero_()               # the fresh DTMF state
         if self.level_on:
             self.buf["level"][s].zero_()              # the fresh leveller state
+        if self.echo_on:
+            self.buf["echo"][s].zero_()               # the fresh canceller state, the ring with it
 
     def _slot_views(self, s: int):
         b, G = self.buf, self.G
@@ -383,6 +463,8 @@ class EncodeSessions(ParkingPool):
             meta["dtmf"] = self.dcfg[s].as_dict()
         if self.lcfg[s] is not None:                  # likewise
             meta["level"] = self.lcfg[s].as_dict()
+        if self.ecfg[s] is not None:                  # likewise, and the far samples pushed (the slot's own are the schedule's)
+            meta["echo"], meta["echo_far"] = self.ecfg[s].as_dict(), self._far[s]
         return meta
 
     def _park_schedule(self, meta: Mapping) -> EncodeSchedule:
@@ -398,6 +480,11 @@ class EncodeSessions(ParkingPool):
             shapes.append(("dtmf", 1, dtmf_rule.STATE_WORDS if meta["schedule"]["samples"] > 0 else 0))
         if meta.get("level") is not None:             # the leveller row, likewise
             shapes.append(("level", 1, level_rule.STATE_WORDS if meta["schedule"]["samples"] > 0 else 0))
+        if meta.get("echo") is not None:              # the canceller row without its ring, then the ring's live samples in two runs
+            T, F = meta["schedule"]["samples"], meta["echo_far"]
+            shapes.append(("echo", 1, echo_rule.STATE_WORDS if T > 0 or F > 0 else 0))
+            pieces = echo_rule.ring_pieces(*echo_rule.far_live(self._park_echo(meta), T, F))
+            shapes += [(f"echo_far.{i}", 1, n) for i, (_, n) in enumerate(pieces)]
         return shapes
 
     def _park_rows(self, s: int) -> Dict[str, torch.Tensor]:
@@ -414,7 +501,18 @@ class EncodeSessions(ParkingPool):
             rows["dtmf"] = b["dtmf"][s:s + 1]
         if self.level_on:
             rows["level"] = b["level"][s:s + 1]
+        if self.echo_on:
+            rows["echo"] = b["echo"][s:s + 1]
         return rows
+
+    def _park_places(self, s: int):
+        """the runs of the ring a canceller's snapshot carries begin where the session's counters say: not cached"""
+        places = super()._park_places(s)
+        if self.ecfg[s] is None:
+            return places
+        ptr, pitch, _ = places["echo"]
+        pieces = echo_rule.ring_pieces(*echo_rule.far_live(self.ecfg[s], self.sched[s].samples, self._far[s]))
+        return dict(places, **{f"echo_far.{i}": (ptr + 4 * (echo_rule.O_FAR + col), pitch, False) for i, (col, _) in enumerate(pieces)})
 
     def _park_widths(self):
         return ("n_mels", self.n_mels), ("codec_rate", self.codec_rate)
@@ -446,6 +544,19 @@ class EncodeSessions(ParkingPool):
         except TypeError as e:
             raise ValueError(f"the level config of the snapshot is not a LevelConfig: {e}") from None
 
+    def _park_echo(self, meta: Mapping) -> Optional[echo_rule.EchoConfig]:
+        """the canceller config a snapshot carries (None: none); ValueError where it is no config or its far count is no count"""
+        if meta.get("echo") is None:
+            return None
+        try:
+            cfg = echo_rule.EchoConfig.from_dict(meta["echo"])
+        except TypeError as e:
+            raise ValueError(f"the echo config of the snapshot is not an EchoConfig: {e}") from None
+        F = meta.get("echo_far")
+        if isinstance(F, bool) or not isinstance(F, int) or F < 0:
+            raise ValueError(f"the far samples of the snapshot's canceller are no count: {F!r}")
+        return cfg
+
     def _park_fits(self, meta: Mapping, sc: EncodeSchedule) -> None:
         g, (lo, hi) = self.geo, meta["window"]
         room = self.codec_push // g.hop + 1 + (g.n_fft - g.pad + g.hop - 1) // g.hop
@@ -456,6 +567,9 @@ class EncodeSessions(ParkingPool):
         self._check_voice(self._park_voice(meta))
         self._check_dtmf(self._park_dtmf(meta))
         self._check_level(self._park_level(meta))
+        if self._check_echo(self._park_echo(meta)) is not None and meta["echo_far"] - meta["schedule"]["samples"] > self.far_room:
+            raise ValueError(f"{meta['echo_far']} far samples against {meta['schedule']['samples']} samples of the session do not fit "
+                             f"far_room_samples = {self.far_room}")
 
     def _park_adopt(self, s: int, meta: Mapping) -> None:
         super()._park_adopt(s, meta)
@@ -463,20 +577,26 @@ class EncodeSessions(ParkingPool):
         self.vcfg[s], self._voice_n[s] = self._park_voice(meta), 0
         self.dcfg[s], self._dtmf_n[s] = self._park_dtmf(meta), 0
         self.lcfg[s], self._level_n[s] = self._park_level(meta), 0
+        self.ecfg[s], self._echo_n[s], self._far[s] = self._park_echo(meta), 0, meta.get("echo_far", 0)
 
     # -- one step ----------------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def push(self, audio: Mapping[int, torch.Tensor], final: Iterable[int] = ()) -> Dict[int, torch.Tensor]:
-        """audio: {slot: (n,) samples, n >= 0}; final: slots that end with these samples -> {slot: ids (G, m) int32, m >= 0}"""
+    def push(self, audio: Mapping[int, torch.Tensor], final: Iterable[int] = (),
+             far: Optional[Mapping[int, torch.Tensor]] = None) -> Dict[int, torch.Tensor]:
+        """audio: {slot: (n,) samples, n >= 0}; final: slots that end with these samples; far: {slot: (m,) f32 far-end samples at the
+        codec's rate, m >= 0} for pushed slots with a canceller (a pool built with echo=True) -> {slot: ids (G, m) int32, m >= 0}"""
         final = set(final)
         audio = self._validate(audio, final)
+        far = self._validate_far(audio, far)
         dev = next(iter(audio.values())).device
         self._ensure_buffers(dev)
         converted, placed = self._place(audio)
         released = self._resample(converted, final, placed)
-        tails = list(self.tail) if self.dtmf_on or self.level_on else None
+        tails = list(self.tail) if self.dtmf_on or self.level_on or self.echo_on else None
         steps = self._intake(audio, released, placed, final)
         with torch.cuda.device(dev):
+            if self.echo_on:
+                self._echo(steps, final, tails, far)
             if self.dtmf_on:
                 self._dtmf(steps, final, tails)
             if self.level_on:
@@ -642,6 +762,47 @@ class EncodeSessions(ParkingPool):
             return empty, empty.clone()
         n = self._dtmf_n[slot]
         return self.buf["dtmf_decided"][slot, :n], self.buf["dtmf_pressed"][slot, :n]
+
+    def _echo(self, steps, final, tails: List[int], far: Mapping[int, torch.Tensor]) -> None:
+        """echo: ONE launch appends the step's far samples to the history of every named slot with a canceller and re-writes in place
+        the samples it gained -- columns [tail before, tail after) of its row -- in front of the DTMF and leveller launches, which
+        read them cancelled"""
+        self._echo_ended = {s for s in final if self.ecfg[s] is not None}
+        first, n_new, chunks = [0] * self.S, [0] * self.S, [None] * self.S
+        for s, st in steps.items():
+            if self.ecfg[s] is not None:
+                first[s], n_new[s], chunks[s] = tails[s], self.tail[s] - tails[s], far.get(s)
+                N = self.ecfg[s].block_samples
+                self._echo_n[s] = st.samples // N - (st.samples - n_new[s]) // N
+                self._far[s] += 0 if chunks[s] is None else chunks[s].shape[0]
+        if not any(n_new) and not any(c is not None for c in chunks):
+            return
+        b = self.buf
+        echo_rule.echo_items(b["samples"], first, n_new, chunks, self.ecfg, b["echo"], b["echo_in"], b["echo_res"], table=b["echo_tab"])
+
+    def _echo_slots(self) -> List[int]:
+        return [s for s in range(self.S) if self.ecfg[s] is not None and (self.sched[s] is not None or s in self._echo_ended)]
+
+    def echoes(self) -> Dict[int, echo_rule.EchoReport]:
+        """{slot: EchoReport} of every slot with a canceller that is open or ended in the most recent push: ONE device-to-host copy
+        of the headers of the canceller rows (the only sync of the canceller, and only here).  A slot that has not been pushed to
+        reports no sample."""
+        slots = self._echo_slots()
+        live = [s for s in slots if not self._fresh[s]] if self.buf is not None else []
+        table = self.buf["echo"][:, :echo_rule.HEADER_WORDS].cpu() if live else None
+        zero = torch.zeros(echo_rule.HEADER_WORDS, dtype=torch.int32)
+        return {s: echo_rule.report(table[s] if s in live else zero, self.ecfg[s].block_samples, self.codec_rate) for s in slots}
+
+    def echo_blocks(self, slot: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(block_in, block_res) of the blocks the slot's last push completed: device fp32 views (n,), valid until the slot's next
+        push.  block_in: the energy sum d^2 of the block as received; block_res: sum e^2, what the canceller left of it"""
+        if not isinstance(slot, int) or slot not in self._echo_slots():
+            raise ValueError(f"slot {slot!r} has no echo canceller (open(echo=)) or is neither open nor ended in the last push")
+        if self.buf is None or self._fresh[slot]:
+            empty = torch.empty(0, dtype=torch.float32, device=self._device())
+            return empty, empty.clone()
+        n = self._echo_n[slot]
+        return self.buf["echo_in"][slot, :n], self.buf["echo_res"][slot, :n]
 
     def _level(self, steps, final, tails: List[int]) -> None:
         """input level: ONE launch re-writes in place the samples every named slot with a leveller gained in this step -- columns

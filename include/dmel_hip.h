@@ -571,6 +571,44 @@ int dmel_level_items(float* samples, int64_t row_stride, int S, const int64_t* f
                      const float* fparams /* S x 10 */, void* state /* (S, 16) words */, float* out_peak, float* out_gain,
                      int64_t out_pitch, void* table_scratch, void* stream);
 
+/* Echo cancellation (a block NLMS adaptive FIR with a meter) on codec-rate samples, S session slots in ONE launch
+ * (csrc/small_ops.hip): the canceller of encode sessions opened with echo= (models/stream_sessions.py), whose rule, defaults and caveats
+ * are utils/echo.py -- the kernel equals echo.scan bit for bit.  Slot s first appends its far_n[s] new far-end samples far[s][i] (fp32)
+ * to the far history in its state row, then RE-WRITES IN PLACE its n_new[s] new samples at samples[s * row_stride + first[s] + i]
+ * (fp32, any 4-byte offset; no other column is written) with e = d - yhat.  The state row of slot s is the 68112 4-byte words at
+ * state + s * state_pitch words: int32 0 T (samples seen), 1 F (far samples pushed), 2 fill (samples of the open block), 3 blocks,
+ * 4 adapted, 5 frozen, 6 far_missing; fp32 7 sd, 8 se; 9 .. 15 reserved and not written; fp32 w[2048] at 16 (the first L are used), the
+ * open block's e at 2064 and d at 2320 (256 words each: `fill` values, 0 behind them), and at 2576 a ring of 65536 fp32: far sample
+ * x[j] at word j mod 65536.  A zeroed row is a fresh session.  With xd[t] = x[t - delay] (0 where t < delay; 0, counted in far_missing
+ * and kept 0, where x[t - delay] had not been appended when sample t was processed -- a far sample appended behind its turn is
+ * dropped), sum8 the sum of 8 contiguous segments (boundaries floor(q n / 8)), each ascending from 0.0f, combined as ((s0 + s1) +
+ * (s2 + s3)) + ((s4 + s5) + (s6 + s7)), and every product, sum and division a separately rounded fp32 operation (no fma):
+ *     sample t:   yhat = sum8_k(w[k] * xd[t - k]), k < L;  e = d - yhat
+ *     a completed block of N samples from t0, in block order:
+ *       E = sum8(xd[j]^2), mx = max |xd[j]| over j in [t0 - L + 1, t0 + N);  Ed = sum8(d^2), Ee = sum8(e^2), md = max |d| over the block
+ *       adapt = E >= far_floor && !(double_talk > 0 && md > double_talk * mx);  !adapt: frozen += 1
+ *       adapt: step = mu / (fN * E + eps);  every k: w[k] = w[k] + step * sum8_i(e[i] * xd[t0 + i - k]), i < N;  adapted += 1
+ *       sd = sd + meter * (Ed - sd);  se = se + meter * (Ee - se);  blocks += 1
+ *       out_in[s * out_pitch + j] = Ed, out_res[s * out_pitch + j] = Ee for the j-th block the launch completed
+ * iparams row s is (L, N, delay), fparams row s (mu, eps, far_floor, double_talk, meter, fN = (float)N).  The words behind the blocks a
+ * row completed are not written.  n_new[s] == 0 && far_n[s] == 0 is an idle slot: neither its rows nor its parameters are looked at;
+ * when every slot is idle the call returns DMEL_OK and launches nothing.  The caller keeps F within 39232 samples ahead of T (what the
+ * ring holds next to the longest delay, filter and block): the kernel drops the samples of an append beyond that.  NaN input is
+ * outside the contract.  DMEL_EINVAL, nothing launched, dmel_last_error naming the item: S outside [1, 65535], a NULL pointer,
+ * samples, state, out_in, out_res or table not 4-byte aligned, a negative stride or pitch, state_pitch below 68112, n_new[s], far_n[s]
+ * or first[s] outside [0, 2^30), far[s] NULL or unaligned with far_n[s] > 0, L no multiple of 64 in [64, 2048], N no multiple of 8 in
+ * [16, 256], delay outside [0, 24000], out_pitch below ceil(n_new[s] / N) (the blocks the item can complete with N - 1 samples
+ * carried), a value of fparams that is not finite and positive (far_floor and double_talk may be 0), mu not below 2, meter above 1,
+ * fN != N.  first, n_new, far, far_n, iparams and fparams are HOST tables, copied as launch arguments into table_scratch (16 S 4-byte
+ * words of device memory, 4-byte aligned): the caller may overwrite them as soon as the call returns.  One workgroup of four waves per
+ * slot; a pass takes 2048 / N blocks through LDS, block by block: the (sample, segment) partial dots, the block's energies and the
+ * decision, the tap update; w stays in LDS for the launch.  Plain vector stores, no atomics.  One profile record per launch in the
+ * family "echo" (time, flops and bytes in "small"). */
+int dmel_echo_items(float* samples, int64_t row_stride, int S, const int64_t* first, const int64_t* n_new, const void* const* far,
+                    const int64_t* far_n, const int32_t* iparams /* S x 3 */, const float* fparams /* S x 6 */,
+                    void* state /* S rows of 68112 words */, int64_t state_pitch, float* out_in, float* out_res, int64_t out_pitch,
+                    void* table_scratch, void* stream);
+
 /* Tones spliced into codec-rate audio, R parts in ONE launch (csrc/small_ops.hip): what decode sessions of a pool built with
  * tones=True send DTMF keys, beeps and call-progress tones with (models/stream_sessions.py: send_dtmf / send_tones), whose rule, tables
  * and caveats are utils/tones.py -- the kernel equals tones.render bit for bit.  Part r writes n[r] floats at dst[r].  Where src[r] is

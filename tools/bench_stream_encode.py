@@ -83,7 +83,18 @@ DTMF detection, the three interleaved in one process.  The leveller changes what
 checked against encode() of the host rule's output (utils/level.py: scan) for every clip, those of the plain pool against encode();
 exactly one "level" / one "small" launch record more per step and nothing else; exit status 1 where a check fails.  Run the plain
 --sessions form on the parent commit for the step time before the option existed.  No bound on the added time is set.  APPENDS its
-table to --out."""
+table to --out.
+
+    python tools/bench_stream_encode.py --sessions 16 --echo [--chunk 1920] [--label NAME] [--out profiles/sessions_echo.txt]
+
+Sessions with an echo canceller (a pool built with echo=True, every session opened with echo=True -- 1024 taps, blocks of 32 -- and
+pushed its far end with every push; noise through a line of two reflections) against the same sessions in a pool without the option
+and, for scale, in a pool with an input leveller, the three interleaved in one process.  The ids and reports of the first two
+sessions of the echo pool are checked against encode() / report() of the host rule's output (utils/echo.py: scan; 1024 taps are slow
+on the host), those of the plain pool against encode(); exactly one "echo" / one "small" launch record more per step and nothing
+else; exit status 1 where a check fails.  The canceller's launch alone (all sessions, one push each) is timed with events as well.
+--chunk 1920 makes the pushes 80 ms.  Run the plain --sessions form on the parent commit for the step time before the option
+existed.  No bound on the added time is set.  APPENDS its table to --out."""
 import argparse, json, os, statistics, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -106,6 +117,7 @@ ap.add_argument("--park", action="store_true", help="with --sessions: snapshot +
 ap.add_argument("--voice", action="store_true", help="with --sessions: sessions with voice detection against the same pool without it")
 ap.add_argument("--dtmf", action="store_true", help="with --sessions: sessions with DTMF detection against the same pool without it")
 ap.add_argument("--level", action="store_true", help="with --sessions: sessions with an input leveller against the same pool without it")
+ap.add_argument("--echo", action="store_true", help="with --sessions: sessions with an echo canceller against the same pool without it")
 ap.add_argument("--label", default="", help="with --sessions: names the table (the commit measured)")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
@@ -116,6 +128,7 @@ if args.out is None:
                             "sessions_park.txt" if args.sessions and args.park else
                             "sessions_voice.txt" if args.sessions and args.voice else
                             "sessions_level.txt" if args.sessions and args.level else
+                            "sessions_echo.txt" if args.sessions and args.echo else
                             "sessions_dtmf.txt" if args.sessions and args.dtmf else
                             "sessions_channels.txt" if args.sessions and args.channels > 1 else
                             "sessions_pcm.txt" if args.sessions and args.sample_format == "s16" else
@@ -463,6 +476,154 @@ def sessions_level_section():
         sys.exit(1)
 
 
+def sessions_echo_section():
+    """S staggered sessions with an echo canceller (the defaults: 1024 taps, blocks of 32), each fed its far end with every push,
+    against the same sessions in a pool without the option and, for scale, in a pool with an input leveller; the same audio, the
+    same pushes.  The canceller changes what the encoder sees, so the ids of its first two sessions are held to the host rule:
+    encode() of echo.scan of the session's clip (the host scan of 1024 taps is slow: two sessions, not all); then the launches per
+    step of the pools, and the canceller's launch alone -- S slots, one push each -- timed with events"""
+    from dmel_codec_amd import _lib
+    from dmel_codec_amd.utils import echo as echo_rule
+    S, n = args.sessions, args.chunk
+    total = (args.pushes + 5) * n
+    far = torch.randn(S, total, device=dev) * 0.05
+    mic = torch.zeros_like(far)
+    mic[:, 20:] += 0.3 * far[:, :-20]                                         # the line: two reflections and a little noise
+    mic[:, 45:] -= 0.15 * far[:, :-45]
+    mic += torch.randn(S, total, device=dev) * 0.001
+    opts = {"plain": {}, "echo": {"echo": True}, "level": {"level": True}}
+    pools = {k: codec.encode_sessions(slots=S, max_push_samples=n, **o) for k, o in opts.items()}
+    slots = {k: [p.open(**opts[k]) for _ in range(S)] for k, p in pools.items()}
+    first = [n * (1 + s % 3) // 3 for s in range(S)]            # the starts differ by a third of a push
+    pos, ms, ids = [0] * S, {k: [] for k in pools}, {k: [[] for _ in range(S)] for k in ("plain", "echo")}
+    cuts = [[0] for _ in range(S)]
+
+    def step(k, chunks):
+        kw = {"far": {slots[k][s]: chunks[s][1] for s in range(S)}} if k == "echo" else {}
+        out = pools[k].push({slots[k][s]: chunks[s][0] for s in range(S)}, **kw)
+        return [out[slots[k][s]] for s in range(S)]
+
+    def chunks_of(size):
+        nonlocal pos
+        c = [(mic[s, pos[s]:pos[s] + size[s]], far[s, pos[s]:pos[s] + size[s]]) for s in range(S)]
+        pos = [p + k for p, k in zip(pos, size)]
+        for s in range(S):
+            cuts[s].append(pos[s])
+        return c
+
+    order = list(pools)
+    for i in range(args.pushes):
+        chunks = chunks_of(first if i == 0 else [n] * S)
+        for k in order[i % 3:] + order[:i % 3]:                                       # none always goes first
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            got = step(k, chunks)
+            torch.cuda.synchronize()
+            if i >= args.warmup:
+                ms[k].append((time.perf_counter() - t0) * 1e3)
+            if k in ids:
+                for s in range(S):
+                    ids[k][s].append(got[s])
+    # the launches of a step, from the profile counters (their events cost time: counted behind the timed steps)
+    families, launches = ("echo", "level", "voice", "dtmf", "small", "stft_logmel", "conv_igemm"), {}
+    counted = [chunks_of([n] * S) for _ in range(4)]
+    _lib.prof_enable(True)
+    for k in pools:
+        launches[k] = []
+        for chunks in counted:
+            _lib.prof_reset()
+            got = step(k, chunks)
+            torch.cuda.synchronize()
+            launches[k].append({f: _lib.prof_read(f)["launches"] for f in families})
+            if k in ids:
+                for s in range(S):
+                    ids[k][s].append(got[s])
+    _lib.prof_enable(False)
+    _lib.prof_reset()
+    reports = pools["echo"].echoes()
+    for k, p in pools.items():
+        for s in range(S):
+            last = p.close(slots[k][s])
+            if k in ids:
+                ids[k][s].append(last)
+    # the ids: the plain pool's are encode()'s, the echo pool's encode()'s of the host rule's output, push by push
+    same, checked = {"plain": True, "echo": True}, min(S, 2)
+    for s in range(S):
+        x = mic[s, :pos[s]]
+        clips = [("plain", x)]
+        if s < checked:
+            xs, fs, state, out = x.cpu(), far[s, :pos[s]].cpu(), None, []
+            for a, b in zip(cuts[s], cuts[s][1:]):
+                e, state, _, _ = echo_rule.scan(xs[a:b], fs[a:b], echo_rule.EchoConfig(), state)
+                out.append(e)
+            clips.append(("echo", torch.cat(out).to(dev)))
+            same["echo"] = same["echo"] and reports[slots["echo"][s]] == echo_rule.report(state)
+        for k, clip in clips:
+            ref, lens = codec.encode(clip[None], torch.tensor([clip.shape[0]], device=dev))
+            same[k] = same[k] and torch.equal(torch.cat(ids[k][s], dim=1), ref[0, :, :int(lens[0])])
+
+    def one_more(opt):
+        return all(a[opt] == 0 and b[opt] == 1 and b["small"] == a["small"] + 1 and all(b[f] == a[f] for f in families if f not in (opt, "small"))
+                   for a, b in zip(launches["plain"], launches[opt]))
+    held = one_more("echo") and one_more("level")
+    # the canceller's launch alone: S slots that gain one push each, the far end with it, timed with events
+    cfg = echo_rule.EchoConfig()
+    rows_ = mic[:, :n].contiguous()
+    state = torch.zeros(S, echo_rule.ROW_WORDS, dtype=torch.int32, device=dev)
+    pitch = echo_rule.max_blocks(n, cfg.block_samples) + 1
+    o1, o2 = torch.zeros(S, pitch, device=dev), torch.zeros(S, pitch, device=dev)
+    tab = torch.empty(echo_rule.TABLE_WORDS * S, dtype=torch.int32, device=dev)
+    alone = []
+    for i in range(args.pushes):
+        a = i * n
+        rows_.copy_(mic[:, a:a + n])
+        fars = [far[s, a:a + n].contiguous() for s in range(S)]
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        echo_rule.echo_items(rows_, [0] * S, [n] * S, fars, [cfg] * S, state, o1, o2, table=tab)
+        ev1.record()
+        torch.cuda.synchronize()
+        if i >= args.warmup:
+            alone.append(ev0.elapsed_time(ev1))
+    erle = sorted(rep.erle_db for rep in reports.values())
+    r = {"sessions": S, "chunk_s": n / SR, "pushes": args.pushes, "warmup": args.warmup, "ids_equal_encode": bool(same["plain"]),
+         "ids_equal_encode_of_host_rule": bool(same["echo"]), "sessions_checked_against_host_rule": checked, "label": args.label,
+         "launches_per_step": {k: launches[k][0] for k in pools}, "one_more_launch_per_step": bool(held),
+         "erle_db": [round(erle[0], 1), round(erle[-1], 1)], "taps": cfg.taps, "block_samples": cfg.block_samples,
+         "echo_launch_alone_ms": {"median": round(statistics.median(alone), 4), "p10": round(pct(alone, 0.1), 4),
+                                  "p90": round(pct(alone, 0.9), 4), "n": len(alone)}}
+    rows = []
+    for k, v in ms.items():
+        med = statistics.median(v)
+        r[k] = {"median_ms": round(med, 3), "p10_ms": round(pct(v, 0.1), 3), "p90_ms": round(pct(v, 0.9), 3), "n": len(v)}
+        rows.append(f"{S:8d}  {k:6s}  {med:9.3f}  {pct(v, 0.1):9.3f}  {pct(v, 0.9):9.3f}  {len(v):4d}  " +
+                    "  ".join(f"{f} {launches[k][0][f]}" for f in families))
+    r["added_median_ms"] = {k: round(r[k]["median_ms"] - r["plain"]["median_ms"], 3) for k in ("echo", "level")}
+    rows.append(f"{S:8d}  the canceller adds {r['added_median_ms']['echo']:.3f} ms to the median step, the leveller (for scale) "
+                f"{r['added_median_ms']['level']:.3f} ms; each pool with an option launches exactly one kernel more per step than the plain one: {held}")
+    rows.append(f"{S:8d}  the canceller's launch alone ({S} slots x {n} samples, {cfg.taps} taps, blocks of {cfg.block_samples}; events around "
+                f"echo_items, its table launch included): median {r['echo_launch_alone_ms']['median']:.4f} ms, p10 "
+                f"{r['echo_launch_alone_ms']['p10']:.4f}, p90 {r['echo_launch_alone_ms']['p90']:.4f} over {len(alone)} launches")
+    rows.append(f"{S:8d}  ids of the plain pool equal encode(): {same['plain']}; ids and reports of the first {checked} sessions of the echo pool "
+                f"equal encode() / report() of the host rule (echo.scan of each clip): {same['echo']}")
+    rows.append(f"{S:8d}  the sessions ended at a metered ERLE of {r['erle_db'][0]} .. {r['erle_db'][1]} dB (noise far end, a line of two reflections)")
+    table = [(f"[{args.label}] " if args.label else "") + f"encode sessions with an echo canceller, {n / SR:.2f} s pushes of 24 kHz audio, starts "
+             f"staggered by a third of a push, 80 mel / 8 groups / 70 channels / 20 layers (tools/bench_stream_encode.py --sessions {S} --echo"
+             + (f" --chunk {n}" if n != 7680 else "") + ")",
+             f"wall time of one step (one push for every stream) incl. host synchronisation, {args.pushes - args.warmup} steady-state steps, the "
+             "three pools interleaved in one process;",
+             "plain = encode_sessions(S), echo / level = encode_sessions(S, echo=True / level=True) with every session opened with the option; "
+             "launches: records of the profile counters in one step",
+             "sessions  pool    median ms     p10 ms     p90 ms     n  launches of one step"] + rows
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "a") as f:
+        f.write("\n".join(table) + "\n\n")
+    print("\n".join(table), file=sys.stderr)
+    print(json.dumps(r))
+    if not (same["plain"] and same["echo"] and held):
+        sys.exit(1)
+
+
 def sessions_resample_section():
     """S staggered sessions at their own rates: one pool that converts them in one launch against the codec-rate pool behind S
     StreamResampler(batch=1); the same audio, the same pushes, equal ids"""
@@ -702,6 +863,11 @@ if args.level and not args.sessions:
     ap.error("--level needs --sessions")
 if args.sessions and args.level:
     sessions_level_section()
+    sys.exit(0)
+if args.echo and not args.sessions:
+    ap.error("--echo needs --sessions")
+if args.sessions and args.echo:
+    sessions_echo_section()
     sys.exit(0)
 if args.sessions and (args.voice or args.dtmf):
     sessions_detector_section("voice" if args.voice else "dtmf")
