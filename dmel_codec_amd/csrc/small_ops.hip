@@ -2353,6 +2353,266 @@ extern "C" int dmel_echo_items(float* samples, int64_t row_stride, int S, const 
 
 namespace dmel {
 
+// ---- packet-loss concealment (pitch repeat) on codec-rate samples (include/dmel_hip.h: dmel_conceal_items; the rule and the state
+// row: utils/conceal.py).  Row s of the table is (first, n_new, n_ranges, W, Pmin, Pmax, H, D, F, floor, eps, rD, rF, 0, 0, 0) and
+// behind them the 16 ranges (lo, hi), forty-eight 4-byte words; workgroup s owns slot s.  The ring of the slot's last 4096 output
+// samples is read into LDS once and stays there for the launch; the header lives in registers, the same values in every thread.
+// The row's stretches are walked in order, a barrier behind each, and each stretch is parallel:
+//   good     the first `rec` samples are the recovery (below); the rest is a copy into the ring, the row is not written
+//   onset    e0 by eight lanes; if the search runs, passes of 256 lags: the (lag, segment) partial sums of c and e over the workgroup
+//            -- a[i] a broadcast read, b[i] consecutive across the lanes of one segment -- then one lag per thread: the fixed tree,
+//            q, and the thread's running best; behind the passes a wave and a workgroup argmax on (q, -lag).  q is compared as a
+//            value, so the order of the reduction cannot change the result
+//   lost run, recovery   one lane per sample, 256 at a time: every source lies in front of t0.  A chunk reads, meets a barrier and
+//            then writes: a write behind the fade may lap a ring word a sample in front of it still reads (H + D + Pmax == 4096),
+//            and only samples of the same chunk can meet so, since reading samples precede writing ones
+// At the end the ring words that changed and the header go back.  Every product, sum and division is rounded on its own
+// (fp contract(off)); the division is the correctly rounded one.  Plain stores, no atomics.
+constexpr int kConcealWords = 48, kConcealHeader = 16, kConcealRing = 4096, kConcealRow = kConcealHeader + kConcealRing;
+constexpr int kConcealMaxRanges = 16, kConcealLagPass = 256;
+__device__ __forceinline__ float conceal_synth(const float* ring, int t0, int P, int k, int H, int D, float rD) {
+#pragma clang fp contract(off)
+  if (P == 0 || k >= H + D) return 0.0f;
+  const float v = ring[(unsigned)(t0 - P + k % P) & (kConcealRing - 1)];
+  if (k < H) return v;
+  const float u = (float)(k - H) * rD;
+  const float g = 1.0f - u;
+  return g * v;
+}
+__global__ __launch_bounds__(256) void conceal_kernel(float* __restrict__ samples, int64_t row_stride, const uint32_t* __restrict__ tab,
+                                                      uint32_t* __restrict__ state, int64_t state_pitch, int32_t* __restrict__ out_period,
+                                                      float* __restrict__ out_score, int64_t out_pitch) {
+#pragma clang fp contract(off)
+  __shared__ float ring[kConcealRing], pc[8 * kConcealLagPass], pe[8 * kConcealLagPass];
+  __shared__ float red_q[4];
+  __shared__ int red_p[4];
+  constexpr unsigned M = kConcealRing - 1;
+  const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint32_t* row = tab + (size_t)s * kConcealWords;
+  const int n_new = (int)row[1];
+  if (n_new <= 0) return;                               // idle (uniform: in front of the first barrier)
+  const int64_t first = (int64_t)(int32_t)row[0];
+  const int nr = (int)row[2], W = (int)row[3], Pmin = (int)row[4], Pmax = (int)row[5], H = (int)row[6], D = (int)row[7], F = (int)row[8];
+  const float floor_e = __uint_as_float(row[9]), eps = __uint_as_float(row[10]), rD = __uint_as_float(row[11]), rF = __uint_as_float(row[12]);
+  const uint32_t* rg = row + 16;
+  uint32_t* srow = state + (int64_t)s * state_pitch;
+  float* frow = reinterpret_cast<float*>(srow);
+  // the header: every thread advances its own copy, all alike
+  int T = (int)srow[0], phase = (int)srow[1], t0 = (int)srow[2], P = (int)srow[3], k = (int)srow[4], rec = (int)srow[5];
+  int lost = (int)srow[6], runs = (int)srow[7], muted = (int)srow[8], longest = (int)srow[9], run = (int)srow[10];
+  float q = __uint_as_float(srow[11]), e0 = __uint_as_float(srow[12]);
+  if (P < 0 || P > Pmax) P = 0;                         // no row the rule wrote; keeps k % P and the reads inside the ring
+  if (rec < 0 || rec > F) rec = 0;
+  for (int i = tid; i < kConcealRing; i += 256) ring[i] = frow[kConcealHeader + i];
+  __syncthreads();
+  float* src = samples + (int64_t)s * row_stride + first;                     // only [0, n_new) is touched
+  int32_t* oper = out_period + (int64_t)s * out_pitch;
+  float* osc = out_score + (int64_t)s * out_pitch;
+  const int T_in = T, w8 = W >> 3;
+  int pos = 0, onsets = 0;
+  for (int ri = 0; ri <= nr; ++ri) {
+    const int lo = ri < nr ? (int)rg[2 * ri] : n_new, hi = ri < nr ? (int)rg[2 * ri + 1] : n_new;
+    if (pos < lo) {                                     // a good stretch [pos, lo)
+      if (phase == 1) { longest = max(longest, run); phase = 2; rec = F; }
+      const int len = lo - pos, r = phase == 2 ? min(rec, len) : 0;
+      for (int j0 = 0; j0 < r; j0 += 256) {             // the recovery: the cross-fade from s(k) into x
+        const int j = j0 + tid;
+        float y = 0.0f;
+        if (j < r) {
+          const float x = src[pos + j];
+          const float sv = conceal_synth(ring, t0, P, k + j, H, D, rD);
+          const float w = (float)(F - rec + j + 1) * rF;
+          const float d = x - sv;
+          const float m = w * d;
+          y = sv + m;
+        }
+        __syncthreads();
+        if (j < r) {
+          ring[(unsigned)(T + j) & M] = y;
+          src[pos + j] = y;
+        }
+      }
+      for (int j = r + tid; j < len; j += 256) ring[(unsigned)(T + j) & M] = src[pos + j];
+      if (r) {
+        k += r; rec -= r;
+        if (rec == 0) phase = 0;
+      }
+      T += len; pos = lo;
+      __syncthreads();
+    }
+    if (lo == hi) break;                                // behind the last range
+    if (phase != 1) {                                   // the onset
+      t0 = T; k = 0; P = 0; run = 0; runs += 1; phase = 1; q = 0.0f; e0 = 0.0f;
+      if (T >= W + Pmax) {
+        if (tid < 8) {
+          float acc = 0.0f;
+          for (int i = tid * w8, z = i + w8; i < z; ++i) {
+            const float a = ring[(unsigned)(t0 - W + i) & M];
+            const float p = a * a;
+            acc = acc + p;
+          }
+          pc[tid] = acc;
+        }
+        __syncthreads();
+        e0 = echo_tree(pc);
+        __syncthreads();                                // the passes overwrite pc
+        if (e0 >= floor_e) {
+          float bq = 0.0f;
+          int bp = 0;
+          const int nl = Pmax - Pmin + 1;
+          for (int l0 = 0; l0 < nl; l0 += kConcealLagPass) {
+            const int cnt = min(kConcealLagPass, nl - l0);
+            for (int c = tid; c < cnt * 8; c += 256) {  // pair c is (segment c / cnt, lag Pmin + l0 + c % cnt)
+              const int seg = c / cnt, li = c - seg * cnt, p = Pmin + l0 + li;
+              const int at = t0 - W + seg * w8;
+              float ac = 0.0f, ae = 0.0f;
+              for (int i = 0; i < w8; ++i) {
+                const float a = ring[(unsigned)(at + i) & M], b = ring[(unsigned)(at + i - p) & M];
+                const float ab = a * b;
+                ac = ac + ab;
+                const float bb = b * b;
+                ae = ae + bb;
+              }
+              pc[seg * kConcealLagPass + li] = ac;
+              pe[seg * kConcealLagPass + li] = ae;
+            }
+            __syncthreads();
+            if (tid < cnt) {
+              float sc[8], se[8];
+#pragma unroll
+              for (int g = 0; g < 8; ++g) { sc[g] = pc[g * kConcealLagPass + tid]; se[g] = pe[g * kConcealLagPass + tid]; }
+              const float c = echo_tree(sc), e = echo_tree(se);
+              float qv = 0.0f;
+              if (c > 0.0f) {
+                const float cc = c * c;
+                const float ee = e + eps;
+                qv = cc / ee;
+              }
+              if (qv > bq) { bq = qv; bp = Pmin + l0 + tid; }     // a thread's lags ascend: the lowest of equal ones stays
+            }
+            __syncthreads();
+          }
+          for (int o = 32; o; o >>= 1) {
+            const float oq = __shfl_xor(bq, o);
+            const int op = __shfl_xor(bp, o);
+            if (oq > bq || (oq == bq && op < bp)) { bq = oq; bp = op; }
+          }
+          if (lane == 0) { red_q[wave] = bq; red_p[wave] = bp; }
+          __syncthreads();
+          bq = red_q[0]; bp = red_p[0];
+          for (int v = 1; v < 4; ++v)
+            if (red_q[v] > bq || (red_q[v] == bq && red_p[v] < bp)) { bq = red_q[v]; bp = red_p[v]; }
+          q = bq;
+          P = bq > 0.0f ? bp : 0;
+        }
+      }
+      if (tid == 0) { oper[onsets] = P; osc[onsets] = q; }
+      ++onsets;
+    }
+    const int m = hi - lo;                              // the lost stretch [lo, hi)
+    for (int j0 = 0; j0 < m; j0 += 256) {
+      const int j = j0 + tid;
+      const float y = j < m ? conceal_synth(ring, t0, P, k + j, H, D, rD) : 0.0f;
+      __syncthreads();
+      if (j < m) {
+        ring[(unsigned)(T + j) & M] = y;
+        src[pos + j] = y;
+      }
+    }
+    muted += P == 0 ? m : max(0, k + m - max(k, H + D));
+    k += m; lost += m; run += m; T += m; pos = hi;
+    __syncthreads();
+  }
+  // the ring words the launch wrote, then the header
+  const int changed = min(n_new, kConcealRing);
+  for (int i = tid; i < changed; i += 256) {
+    const unsigned at = (unsigned)(T - changed + i) & M;
+    frow[kConcealHeader + at] = ring[at];
+  }
+  if (tid == 0) {
+    srow[0] = (uint32_t)(T_in + n_new); srow[1] = (uint32_t)phase; srow[2] = (uint32_t)t0; srow[3] = (uint32_t)P; srow[4] = (uint32_t)k;
+    srow[5] = (uint32_t)rec; srow[6] = (uint32_t)lost; srow[7] = (uint32_t)runs; srow[8] = (uint32_t)muted; srow[9] = (uint32_t)longest;
+    srow[10] = (uint32_t)run; srow[11] = __float_as_uint(q); srow[12] = __float_as_uint(e0);
+  }
+}
+
+}  // namespace dmel
+
+extern "C" int dmel_conceal_items(float* samples, int64_t row_stride, int S, const int64_t* first, const int64_t* n_new,
+                                  const int32_t* n_ranges, const int32_t* ranges, const int32_t* iparams, const float* fparams, void* state,
+                                  int64_t state_pitch, int32_t* out_period, float* out_score, int64_t out_pitch, void* table_scratch,
+                                  void* stream) {
+  using namespace dmel;
+  DMEL_CHECK_ARG(samples && first && n_new && n_ranges && ranges && iparams && fparams && state && out_period && out_score && table_scratch,
+                 "conceal_items: NULL argument");
+  DMEL_CHECK_ARG(S >= 1 && S <= 65535, "conceal_items: %d items, expected 1 .. 65535", S);
+  DMEL_CHECK_ARG((((uintptr_t)samples | (uintptr_t)state | (uintptr_t)out_period | (uintptr_t)out_score | (uintptr_t)table_scratch) & 3) == 0,
+                 "conceal_items: samples, state, out_period, out_score or table_scratch is not 4-byte aligned");
+  DMEL_CHECK_ARG(row_stride >= 0 && out_pitch >= 0, "conceal_items: negative row stride %lld or output pitch %lld", (long long)row_stride,
+                 (long long)out_pitch);
+  DMEL_CHECK_ARG(state_pitch >= kConcealRow, "conceal_items: a state pitch of %lld words, expected at least %d", (long long)state_pitch,
+                 kConcealRow);
+  std::vector<uint32_t> tab((size_t)kConcealWords * S, 0u);
+  int64_t live = 0;
+  double bytes = 0.0;
+  for (int s = 0; s < S; ++s) {
+    const int64_t n = n_new[s];
+    DMEL_CHECK_ARG(n >= 0 && n <= 0x3fffffff, "conceal_items: item %d: %lld new samples, expected 0 .. 2^30 - 1", s, (long long)n);
+    if (n == 0) continue;                               // idle: its parameters are not looked at (the table row stays 0)
+    DMEL_CHECK_ARG(first[s] >= 0 && first[s] <= 0x3fffffff, "conceal_items: item %d: first column %lld, expected 0 .. 2^30 - 1", s,
+                   (long long)first[s]);
+    const int32_t nr = n_ranges[s];
+    DMEL_CHECK_ARG(nr >= 0 && nr <= kConcealMaxRanges, "conceal_items: item %d: %d lost ranges, expected 0 .. %d", s, nr, kConcealMaxRanges);
+    DMEL_CHECK_ARG(out_pitch >= nr, "conceal_items: item %d: %d lost ranges can be %d onsets, which exceed the output pitch %lld", s, nr, nr,
+                   (long long)out_pitch);
+    const int32_t* rg = ranges + (size_t)2 * kConcealMaxRanges * s;
+    int64_t lost = 0;
+    for (int r = 0; r < nr; ++r) {
+      const int32_t lo = rg[2 * r], hi = rg[2 * r + 1];
+      DMEL_CHECK_ARG(lo >= 0 && lo < hi && hi <= n, "conceal_items: item %d: range %d is [%d, %d), expected a part of [0, %lld]", s, r, lo, hi,
+                     (long long)n);
+      DMEL_CHECK_ARG(r == 0 || lo > rg[2 * r - 1], "conceal_items: item %d: range %d begins at %d, not behind the end %d of the one before: "
+                     "ranges are sorted and do not touch", s, r, lo, r ? rg[2 * r - 1] : 0);
+      lost += hi - lo;
+    }
+    const int32_t* ip = iparams + (size_t)6 * s;
+    const int32_t W = ip[0], Pmin = ip[1], Pmax = ip[2], H = ip[3], D = ip[4], F = ip[5];
+    DMEL_CHECK_ARG(W >= 8 && W % 8 == 0, "conceal_items: item %d: a window of %d samples, expected a multiple of 8, at least 8", s, W);
+    DMEL_CHECK_ARG(Pmin >= 8 && Pmin <= Pmax, "conceal_items: item %d: a lag range of [%d, %d], expected 8 <= Pmin <= Pmax", s, Pmin, Pmax);
+    DMEL_CHECK_ARG((int64_t)W + Pmax <= kConcealRing, "conceal_items: item %d: a window of %d and a longest period of %d exceed the ring of %d",
+                   s, W, Pmax, kConcealRing);
+    DMEL_CHECK_ARG(H >= 0 && D >= 0 && (int64_t)H + D + Pmax <= kConcealRing,
+                   "conceal_items: item %d: a hold of %d, a fade of %d and a longest period of %d exceed the ring of %d", s, H, D, Pmax,
+                   kConcealRing);
+    DMEL_CHECK_ARG(F >= 1 && F <= 0x3fffffff, "conceal_items: item %d: a recovery of %d samples, expected at least 1", s, F);
+    const float* fp = fparams + (size_t)4 * s;
+    DMEL_CHECK_ARG(std::isfinite(fp[0]) && fp[0] >= 0.0f && std::isfinite(fp[2]) && fp[2] >= 0.0f,
+                   "conceal_items: item %d: floor %g or rD %g is not finite or is negative", s, (double)fp[0], (double)fp[2]);
+    DMEL_CHECK_ARG(std::isfinite(fp[1]) && fp[1] > 0.0f && std::isfinite(fp[3]) && fp[3] > 0.0f && fp[3] <= 1.0f,
+                   "conceal_items: item %d: eps %g or rF %g is not finite and positive, or rF is above 1", s, (double)fp[1], (double)fp[3]);
+    uint32_t* it = tab.data() + (size_t)kConcealWords * s;
+    it[0] = (uint32_t)first[s]; it[1] = (uint32_t)n; it[2] = (uint32_t)nr;
+    std::memcpy(it + 3, ip, 6 * sizeof(int32_t));
+    std::memcpy(it + 9, fp, 4 * sizeof(float));
+    std::memcpy(it + 16, rg, (size_t)2 * nr * sizeof(int32_t));
+    ++live;
+    bytes += 4.0 * (double)n + 4.0 * (double)lost + 8.0 * (double)nr + 4.0 * (kConcealRow + std::min<double>((double)n, kConcealRing));
+  }
+  if (live == 0) return DMEL_OK;                        // every item idle
+  hipStream_t st = (hipStream_t)stream;
+  DMEL_TRY(launch_table_put(tab.data(), tab.size() * sizeof(uint32_t), table_scratch, st));
+  {
+    // "small" carries the time and the bytes; the second scope only counts: one record per concealment launch (dmel_prof_read("conceal"))
+    ProfScope ps("small", st, 0.0, bytes), count("conceal", st, 0.0, 0.0);
+    hipLaunchKernelGGL(conceal_kernel, dim3((unsigned)S), dim3(256), 0, st, samples, row_stride, static_cast<const uint32_t*>(table_scratch),
+                       static_cast<uint32_t*>(state), state_pitch, out_period, out_score, out_pitch);
+  }
+  DMEL_HIP(hipGetLastError());
+  return DMEL_OK;
+}
+
+namespace dmel {
+
 // ---- tones spliced into codec-rate audio (include/dmel_hip.h: dmel_tone_items; the rule: utils/tones.py) -----------------------------
 // The table holds R part rows of (dst, src, n, first tile, first segment record, segments), six int64, and behind them the launch's
 // segment records of five int64: the eight 4-byte words of the entry's table (f1, f2, a1, a2, on, off, ramp, ramp_off) and the

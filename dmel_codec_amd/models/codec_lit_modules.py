@@ -401,7 +401,7 @@ class VQGAN(nn.Module):
 
     def encode_sessions(self, slots: int, max_push_samples: int = 7680, sample_rate: Optional[int] = None, sample_rates=(),
                         voice: bool = False, dtmf: bool = False, level: bool = False, echo: bool = False,
-                        far_room_samples: int = 24000):
+                        far_room_samples: int = 24000, conceal: bool = False):
         """A pool of `slots` INDEPENDENT incremental encodes served by one streaming step: sessions open, receive their own number of
         samples per step (at most max_push_samples), stall and close on their own -- what streaming_encoder(batch=B), B streams in
         lockstep, cannot do -- and each one's concatenated ids are the bits of encode() on its own clip.  One STFT launch, one encoder
@@ -422,9 +422,14 @@ class VQGAN(nn.Module):
         EchoConfig) starts a session's block NLMS filter, fed the far end with pool.push(audio, far={slot: samples}) -- at most
         far_room_samples ahead of the slot's own -- which cancels the session's codec-rate samples in place in one more launch for all
         slots of a step, in front of the DTMF and leveller launches, and is read with pool.echoes() (utils/echo.py has the rule).
+        conceal=True adds a packet-loss concealment row per slot: pool.open(conceal=True | ConcealConfig) starts a session's pitch
+        waveform repetition, told of lost wire frames with pool.push(audio, lost={slot: n}), which re-writes the damaged codec-rate
+        samples in place in one more launch for all slots of a step, in front of the echo launch, and is read with pool.concealed()
+        (utils/conceal.py has the rule).
         See models/stream_sessions.py: EncodeSessions."""
         from .stream_sessions import EncodeSessions
-        return EncodeSessions(self, slots, max_push_samples, sample_rate, sample_rates, voice, dtmf, level, echo, far_room_samples)
+        return EncodeSessions(self, slots, max_push_samples, sample_rate, sample_rates, voice, dtmf, level, echo, far_room_samples,
+                              conceal)
 
     # ------------------------------------------------------------------------------ decode side
     @torch.no_grad()

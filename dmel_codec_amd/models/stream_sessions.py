@@ -19,6 +19,7 @@ from typing import Dict, Iterable, List, Mapping, Optional, Tuple
 import torch
 
 from .. import _lib
+from ..utils import conceal as conceal_rule
 from ..utils import crossfade, pcm
 from ..utils import dtmf as dtmf_rule
 from ..utils import echo as echo_rule
@@ -168,6 +169,32 @@ class EncodeSessions(ParkingPool):
     comfort noise, a bulk-delay search, stereo far ends, far streams at another rate or format, decode pools, the lockstep
     StreamingEncoder and whole-clip encode() (callers have echo.scan / echo.echo_items).
 
+    Every option above assumes that the wire delivers every sample, and RTP does not.  A pool built with conceal=True serves
+    sessions opened with open(conceal=True | ConcealConfig), each with a packet-loss concealment of its own: pitch waveform
+    repetition with zero added latency on the same codec-rate samples (the rule, its state row and its caveats: utils/conceal.py,
+    which is also the host reference the pool is tested against bit for bit).  push(audio, final, lost={slot: n}) says that n
+    frames of the slot's WIRE (its rate; frames, not samples, for a session with channels) were lost in front of this push's
+    samples for that slot; the slot is named in `audio` (an empty chunk is fine) and n + len(chunk) <= max_push_samples, so a longer
+    hole is spread over steps.  The pool puts n frames of the format's silence in front of the chunk (f32 0.0, s16 0, mu-law 0xFF,
+    A-law 0xD5), so the convert launch, the resampler, the schedule, the far alignment and every counter keep the true timeline;
+    it records the wire range, maps it to the codec-rate samples it damages (conceal.damaged: through a resampler, every output
+    whose filter window reads a lost frame) and keeps the part the resampler has not released for later steps.  In front of the
+    echo launch of a step, ONE dmel_conceal_items launch serves every named concealing slot that gained samples -- on steps
+    without a loss too: the ring needs the samples -- and re-writes in place the damaged columns and the recovery behind them:
+    the order of a step is convert, resample, conceal, echo, DTMF, level, STFT.  Contract: the ids of a concealing session are the
+    bits of encode(y, len) with y = conceal.scan(x0, ranges, config)[0], x0 the silence-filled stream at the codec's rate and
+    ranges = conceal.damaged(lost wire ranges, rate, codec rate), however audio and losses were cut into pushes; with echo, DTMF
+    or a leveller their rules apply to y in the order above.  The state is one row of 4112 words per slot (`conceal`: counters
+    and a ring of the last 4096 output samples), zeroed with the slot's other rows; it travels with snapshot / restore as one more
+    segment, the damaged ranges still pending as plain integers in the meta; push() returns what it returns and never syncs.
+    concealed() -> {slot: ConcealReport} (lost and muted samples, runs, the longest, the last period and score) for every
+    concealing slot that is open or ended in the most recent push, from ONE device-to-host copy of the rows' headers, the only
+    sync and only when asked; conceal_onsets(slot) -> (periods, scores), device views of the onsets of the slot's last push.  A
+    pool built without conceal=True allocates and launches exactly what it did, refuses open(conceal=), push(lost=) and a
+    snapshot that carries the option; a session without it snapshots to the bytes it always did.  Not served: jitter buffers and
+    reordering, reading RTP sequence numbers, FEC / RED, decode pools, losses in the far stream, the lockstep StreamingEncoder and
+    whole-clip encode() (callers have conceal.scan / conceal.conceal_items).
+
     Only encoders the one-launch streaming kernel takes (residual channels in (32, 80], no condition, no output projection,
     dilations <= 8, fp32): anything else is refused at construction.
 
@@ -177,7 +204,7 @@ class EncodeSessions(ParkingPool):
 
     def __init__(self, codec, slots: int, max_push_samples: int = 7680, sample_rate: Optional[int] = None,
                  sample_rates: Iterable[int] = (), voice: bool = False, dtmf: bool = False, level: bool = False,
-                 echo: bool = False, far_room_samples: int = 24000):
+                 echo: bool = False, far_room_samples: int = 24000, conceal: bool = False):
         enc, tr = codec.encoder, codec.encode_mel_transform
         if sample_rate is not None and int(sample_rate) != int(tr.sample_rate):
             raise NotImplementedError(f"sessions run at the codec's own rate ({tr.sample_rate} Hz); resample in front (StreamResampler), "
@@ -258,13 +285,21 @@ class EncodeSessions(ParkingPool):
         self._far = [0] * self.S                      # far samples pushed to the slot (its own samples: sched[s].samples)
         self._echo_n = [0] * self.S                   # blocks the slot's last push completed: the valid words of its in / res rows
         self._echo_ended: set = set()                 # slots with a canceller that ended in the most recent push
+        if not isinstance(conceal, bool):
+            raise ValueError(f"conceal must be a bool (a session's config goes to open(conceal=)), got {conceal!r}")
+        self.conceal_on = conceal                     # the pool keeps concealment rows: sessions may open with conceal=
+        self.ccfg: List[Optional[conceal_rule.ConcealConfig]] = [None] * self.S  # the slot's concealment (None: none)
+        self._lost: List[List[Tuple[int, int]]] = [[] for _ in range(self.S)]    # damaged codec-rate ranges not released yet, absolute
+        self._lost_open = [False] * self.S            # the slot's newest sample was a lost one: a range at its next sample is no onset
+        self._conceal_n = [0] * self.S                # onsets of the slot's last push: the valid words of its period / score rows
+        self._conceal_ended: set = set()              # concealing slots that ended in the most recent push
 
     def tokens_emitted(self, slot: int) -> int:
         self._check_open(slot)
         return self.sched[slot].tokens
 
     def open(self, sample_rate: Optional[int] = None, sample_format: str = "f32", channels: int = 1,
-             channel: Optional[int] = None, voice=None, dtmf=None, level=None, echo=None) -> int:
+             channel: Optional[int] = None, voice=None, dtmf=None, level=None, echo=None, conceal=None) -> int:
         """take a free slot: fresh schedule, state zeroed before its first push.  sample_rate: the rate this session's pushes arrive
         at, one of the declared `sample_rates` (None: the codec's).  sample_format: "f32", "s16" for torch.int16 pushes (16-bit
         signed PCM, x / 32768), or "ulaw" / "alaw" for torch.uint8 pushes (G.711 codes).  channels: 1 .. 8; above 1 the pushes are
@@ -274,6 +309,8 @@ class EncodeSessions(ParkingPool):
         built with dtmf=True.  level: True (the defaults of utils/level.py) or a LevelConfig starts the session's input leveller, on
         a pool built with level=True: the encoder then sees the levelled samples.  echo: True (the defaults of utils/echo.py) or an
         EchoConfig starts the session's echo canceller, on a pool built with echo=True: push(far=) then takes its far-end samples.
+        conceal: True (the defaults of utils/conceal.py) or a ConcealConfig starts the session's packet-loss concealment, on a pool
+        built with conceal=True: push(lost=) then takes the frames its wire lost.
         Raises when every slot is taken; a refused open takes no slot."""
         rate = self.codec_rate if sample_rate is None else int(sample_rate)
         pick = self._check_wire(rate, sample_format, channels, channel)
@@ -281,6 +318,7 @@ class EncodeSessions(ParkingPool):
         keys = self._check_dtmf(dtmf_rule.as_config(dtmf))
         lev = self._check_level(level_rule.as_config(level))
         ec = self._check_echo(echo_rule.as_config(echo))
+        cc = self._check_conceal(conceal_rule.as_config(conceal))
         s = self._first_free()
         self._occupy(s, EncodeSchedule(self.geo), 0, rate, sample_format, channels)
         self.s0[s], self.tail[s], self.pick[s] = 0, 0, pick
@@ -288,6 +326,7 @@ class EncodeSessions(ParkingPool):
         self.dcfg[s], self._dtmf_n[s] = keys, 0
         self.lcfg[s], self._level_n[s] = lev, 0
         self.ecfg[s], self._echo_n[s], self._far[s] = ec, 0, 0
+        self.ccfg[s], self._conceal_n[s], self._lost[s], self._lost_open[s] = cc, 0, [], False
         return s
 
     def _check_voice(self, cfg: Optional[voice_rule.VoiceConfig]) -> Optional[voice_rule.VoiceConfig]:
@@ -320,6 +359,33 @@ class EncodeSessions(ParkingPool):
             raise ValueError("echo on a pool built without echo=True: it has no canceller rows")
         return cfg
 
+    def _check_conceal(self, cfg: Optional[conceal_rule.ConcealConfig]) -> Optional[conceal_rule.ConcealConfig]:
+        """a session's concealment config, refused here for open() and for restore() alike"""
+        if cfg is not None:
+            if not self.conceal_on:
+                raise ValueError("conceal on a pool built without conceal=True: it has no concealment rows")
+            cfg.samples(self.codec_rate)
+        return cfg
+
+    def _validate_lost(self, audio: Mapping[int, torch.Tensor], lost) -> Dict[int, int]:
+        """the lost frames of a step, refused like the audio: before any state changes and before any device call -> {slot: n > 0}"""
+        if lost is None:
+            return {}
+        if not self.conceal_on:
+            raise ValueError("lost frames on a pool built without conceal=True: it has no concealment rows")
+        out = {}
+        for slot, n in lost.items():
+            if slot not in audio:
+                raise ValueError(f"slot {slot!r} has lost frames but is not among the pushed slots (an empty push is fine)")
+            self._check_open(slot)
+            if self.ccfg[slot] is None:
+                raise ValueError(f"slot {slot} has lost frames and no concealment (open(conceal=))")
+            if isinstance(n, bool) or not isinstance(n, int) or n < 0:
+                raise ValueError(f"slot {slot}: lost frames are a count, an integer >= 0, got {n!r}")
+            if n:
+                out[slot] = n
+        return out
+
     def _validate_far(self, audio: Mapping[int, torch.Tensor], far) -> Dict[int, torch.Tensor]:
         """the far samples of a step, refused like the audio: before any state changes and before any device call"""
         if far is None:
@@ -346,11 +412,12 @@ class EncodeSessions(ParkingPool):
                 out[slot] = x.contiguous()
         return out
 
-    def _validate(self, audio: Mapping[int, torch.Tensor], final) -> Dict[int, torch.Tensor]:
-        """everything that can be refused, before any state changes and before any device call"""
+    def _validate(self, audio: Mapping[int, torch.Tensor], final, lost: Optional[Mapping[int, int]] = None) -> Dict[int, torch.Tensor]:
+        """everything that can be refused, before any state changes and before any device call; lost: {slot: frames of silence the
+        pool will put in front of the slot's chunk}, which count as pushed"""
         if not audio:
             raise ValueError("push needs at least one slot")
-        out = {}
+        out, lost = {}, lost or {}
         for slot, a in audio.items():
             self._check_open(slot)
             c = self.ch[slot]
@@ -363,8 +430,9 @@ class EncodeSessions(ParkingPool):
                     a = a[0]
                 if a.ndim != 1:
                     raise ValueError(f"slot {slot}: expected mono audio (n,) or (1, n), got {tuple(a.shape)}")
-            if a.shape[0] > self.max_push:
-                raise ValueError(f"slot {slot}: a push of {a.shape[0]} samples exceeds max_push_samples = {self.max_push}")
+            if a.shape[0] + lost.get(slot, 0) > self.max_push:
+                raise ValueError(f"slot {slot}: a push of {a.shape[0]} samples" + (f" behind {lost[slot]} lost ones" if slot in lost else "")
+                                 + f" exceeds max_push_samples = {self.max_push}")
             # the push's dtype is the dtype of the slot's format; an f32 slot refuses the dtypes of the other formats
             if (a.dtype in _WIRE_DTYPES) if self.fmt[slot] == "f32" else (a.dtype != pcm.FORMATS[self.fmt[slot]][1]):
                 raise ValueError(f"slot {slot} was opened with sample_format={self.fmt[slot]!r}: a {a.dtype} push does not match")
@@ -372,10 +440,11 @@ class EncodeSessions(ParkingPool):
         for slot in final:
             if slot not in audio:
                 raise ValueError(f"slot {slot} is in `final` but not among the pushed slots")
-            total = self.sched[slot].samples + out[slot].shape[0]
+            pushed = out[slot].shape[0] + lost.get(slot, 0)
+            total = self.sched[slot].samples + pushed
             if self._converts(slot):                  # its length at the codec's rate, as encode(..., sample_rate=) converts it
                 rs = self.rs.sched[slot]
-                total = rs.total_outputs(rs.samples + out[slot].shape[0])
+                total = rs.total_outputs(rs.samples + pushed)
             if total <= self.geo.pad:
                 raise ValueError(f"slot {slot}: the stream is {total} samples long: encode() needs more than the reflect pad {self.geo.pad}")
         for slot, a in out.items():
@@ -423,6 +492,12 @@ class EncodeSessions(ParkingPool):
                             echo_in=torch.zeros(self.S, pitch, dtype=torch.float32, device=dev),
                             echo_res=torch.zeros(self.S, pitch, dtype=torch.float32, device=dev),
                             echo_tab=torch.empty(echo_rule.TABLE_WORDS * self.S, dtype=torch.int32, device=dev))
+        if self.conceal_on:                           # dmel_conceal_items: a state row per slot (the ring of its output in it), the step's
+            #                                           onsets (at most one per lost range), 48 words per slot of the table
+            self.buf.update(conceal=torch.zeros(self.S, conceal_rule.ROW_WORDS, dtype=torch.int32, device=dev),
+                            conceal_period=torch.zeros(self.S, conceal_rule.MAX_RANGES, dtype=torch.int32, device=dev),
+                            conceal_score=torch.zeros(self.S, conceal_rule.MAX_RANGES, dtype=torch.float32, device=dev),
+                            conceal_tab=torch.empty(conceal_rule.TABLE_WORDS * self.S, dtype=torch.int32, device=dev))
 
     def _prepare_slot(self, s: int) -> None:
         super()._prepare_slot(s)
@@ -434,6 +509,8 @@ class EncodeSessions(ParkingPool):
             self.buf["level"][s].zero_()              # the fresh leveller state
         if self.echo_on:
             self.buf["echo"][s].zero_()               # the fresh canceller state, the ring with it
+        if self.conceal_on:
+            self.buf["conceal"][s].zero_()            # the fresh concealment state, the ring with it
 
     def _slot_views(self, s: int):
         b, G = self.buf, self.G
@@ -465,6 +542,9 @@ class EncodeSessions(ParkingPool):
             meta["level"] = self.lcfg[s].as_dict()
         if self.ecfg[s] is not None:                  # likewise, and the far samples pushed (the slot's own are the schedule's)
             meta["echo"], meta["echo_far"] = self.ecfg[s].as_dict(), self._far[s]
+        if self.ccfg[s] is not None:                  # likewise, and the damaged ranges the resampler has not released yet
+            meta["conceal"], meta["conceal_lost"] = self.ccfg[s].as_dict(), [list(r) for r in self._lost[s]]
+            meta["conceal_open"] = self._lost_open[s]
         return meta
 
     def _park_schedule(self, meta: Mapping) -> EncodeSchedule:
@@ -485,6 +565,8 @@ class EncodeSessions(ParkingPool):
             shapes.append(("echo", 1, echo_rule.STATE_WORDS if T > 0 or F > 0 else 0))
             pieces = echo_rule.ring_pieces(*echo_rule.far_live(self._park_echo(meta), T, F))
             shapes += [(f"echo_far.{i}", 1, n) for i, (_, n) in enumerate(pieces)]
+        if meta.get("conceal") is not None:           # the concealment row, its ring included; a session without a sample owns the zeroed one
+            shapes.append(("conceal", 1, conceal_rule.ROW_WORDS if meta["schedule"]["samples"] > 0 else 0))
         return shapes
 
     def _park_rows(self, s: int) -> Dict[str, torch.Tensor]:
@@ -503,6 +585,8 @@ class EncodeSessions(ParkingPool):
             rows["level"] = b["level"][s:s + 1]
         if self.echo_on:
             rows["echo"] = b["echo"][s:s + 1]
+        if self.conceal_on:
+            rows["conceal"] = b["conceal"][s:s + 1]
         return rows
 
     def _park_places(self, s: int):
@@ -557,6 +641,27 @@ class EncodeSessions(ParkingPool):
             raise ValueError(f"the far samples of the snapshot's canceller are no count: {F!r}")
         return cfg
 
+    def _park_conceal(self, meta: Mapping):
+        """(the concealment config a snapshot carries (None: none), its pending damaged ranges, whether its newest sample was lost);
+        ValueError where it is no config or the ranges are no sorted, separate ranges behind what the session has released"""
+        if meta.get("conceal") is None:
+            return None, [], False
+        try:
+            cfg = conceal_rule.ConcealConfig.from_dict(meta["conceal"])
+        except TypeError as e:
+            raise ValueError(f"the conceal config of the snapshot is not a ConcealConfig: {e}") from None
+        raw, at, ranges = meta.get("conceal_lost"), meta["schedule"]["samples"], []
+        ok = isinstance(raw, (list, tuple)) and all(isinstance(r, (list, tuple)) and len(r) == 2 and all(
+            isinstance(v, int) and not isinstance(v, bool) for v in r) for r in raw)
+        for lo, hi in raw if ok else ():
+            ok = ok and at <= lo < hi
+            at = hi + 1
+            ranges.append((lo, hi))
+        if not ok or not isinstance(meta.get("conceal_open"), bool):
+            raise ValueError(f"conceal_lost of the snapshot is no list of sorted, separate [lo, hi) behind the {meta['schedule']['samples']} "
+                             f"samples the session has released: {raw!r} (conceal_open: {meta.get('conceal_open')!r})")
+        return cfg, ranges, meta["conceal_open"]
+
     def _park_fits(self, meta: Mapping, sc: EncodeSchedule) -> None:
         g, (lo, hi) = self.geo, meta["window"]
         room = self.codec_push // g.hop + 1 + (g.n_fft - g.pad + g.hop - 1) // g.hop
@@ -570,6 +675,7 @@ class EncodeSessions(ParkingPool):
         if self._check_echo(self._park_echo(meta)) is not None and meta["echo_far"] - meta["schedule"]["samples"] > self.far_room:
             raise ValueError(f"{meta['echo_far']} far samples against {meta['schedule']['samples']} samples of the session do not fit "
                              f"far_room_samples = {self.far_room}")
+        self._check_conceal(self._park_conceal(meta)[0])
 
     def _park_adopt(self, s: int, meta: Mapping) -> None:
         super()._park_adopt(s, meta)
@@ -578,23 +684,32 @@ class EncodeSessions(ParkingPool):
         self.dcfg[s], self._dtmf_n[s] = self._park_dtmf(meta), 0
         self.lcfg[s], self._level_n[s] = self._park_level(meta), 0
         self.ecfg[s], self._echo_n[s], self._far[s] = self._park_echo(meta), 0, meta.get("echo_far", 0)
+        self.ccfg[s], self._lost[s], self._lost_open[s] = self._park_conceal(meta)
+        self._conceal_n[s] = 0
 
     # -- one step ----------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def push(self, audio: Mapping[int, torch.Tensor], final: Iterable[int] = (),
-             far: Optional[Mapping[int, torch.Tensor]] = None) -> Dict[int, torch.Tensor]:
+             far: Optional[Mapping[int, torch.Tensor]] = None, lost: Optional[Mapping[int, int]] = None) -> Dict[int, torch.Tensor]:
         """audio: {slot: (n,) samples, n >= 0}; final: slots that end with these samples; far: {slot: (m,) f32 far-end samples at the
-        codec's rate, m >= 0} for pushed slots with a canceller (a pool built with echo=True) -> {slot: ids (G, m) int32, m >= 0}"""
+        codec's rate, m >= 0} for pushed slots with a canceller (a pool built with echo=True); lost: {slot: frames of the slot's wire
+        that were lost in front of these samples} for pushed concealing slots (a pool built with conceal=True)
+        -> {slot: ids (G, m) int32, m >= 0}"""
         final = set(final)
-        audio = self._validate(audio, final)
+        lost = self._validate_lost(audio, lost)
+        audio = self._validate(audio, final, lost)
         far = self._validate_far(audio, far)
+        if lost:
+            audio = self._fill_lost(audio, lost)
         dev = next(iter(audio.values())).device
         self._ensure_buffers(dev)
         converted, placed = self._place(audio)
         released = self._resample(converted, final, placed)
-        tails = list(self.tail) if self.dtmf_on or self.level_on or self.echo_on else None
+        tails = list(self.tail) if self.dtmf_on or self.level_on or self.echo_on or self.conceal_on else None
         steps = self._intake(audio, released, placed, final)
         with torch.cuda.device(dev):
+            if self.conceal_on:
+                self._conceal(steps, final, tails)
             if self.echo_on:
                 self._echo(steps, final, tails, far)
             if self.dtmf_on:
@@ -762,6 +877,72 @@ class EncodeSessions(ParkingPool):
             return empty, empty.clone()
         n = self._dtmf_n[slot]
         return self.buf["dtmf_decided"][slot, :n], self.buf["dtmf_pressed"][slot, :n]
+
+    def _fill_lost(self, audio: Dict[int, torch.Tensor], lost: Mapping[int, int]) -> Dict[int, torch.Tensor]:
+        """the lost frames of a step take their place in the timeline: n frames of the format's silence in front of the slot's chunk,
+        and the wire range they cover, mapped to the codec-rate samples it damages, joins the slot's pending ranges"""
+        audio = dict(audio)
+        for s, n in lost.items():
+            a = audio[s]
+            quiet = torch.full((n,) + tuple(a.shape[1:]), conceal_rule.SILENCE[self.fmt[s]], dtype=a.dtype, device=a.device)
+            audio[s] = torch.cat((quiet, a))
+            at = self.rs.sched[s].samples if self._converts(s) else self.sched[s].samples       # wire frames seen so far
+            new = conceal_rule.damaged([(at, at + n)], self.rate[s], self.codec_rate)
+            # a released output had its whole window in hand before the loss arrived
+            assert all(lo >= self.sched[s].samples for lo, _ in new), (new, self.sched[s].samples)
+            self._lost[s] = conceal_rule.damaged(self._lost[s] + new, self.codec_rate, self.codec_rate)
+        return audio
+
+    def _conceal(self, steps, final, tails: List[int]) -> None:
+        """concealment: ONE launch takes the samples every named concealing slot gained in this step -- columns [tail before, tail
+        after) of its row -- through its rule and re-writes in place the damaged ones and the recovery behind them, in front of the
+        echo, DTMF and leveller launches, which read them concealed.  The part of a damaged range the step released leaves the
+        slot's pending ranges; the rest waits for the samples"""
+        self._conceal_ended = {s for s in final if self.ccfg[s] is not None}
+        first, n_new, ranges = [0] * self.S, [0] * self.S, [[] for _ in range(self.S)]
+        for s, st in steps.items():
+            if self.ccfg[s] is None:
+                continue
+            first[s], n_new[s] = tails[s], self.tail[s] - tails[s]
+            self._conceal_n[s] = 0
+            if not n_new[s]:
+                continue
+            a, b = st.samples - n_new[s], st.samples                          # the absolute samples of the step
+            mine = [(max(lo, a) - a, min(hi, b) - a) for lo, hi in self._lost[s] if lo < b]
+            self._lost[s] = [(max(lo, b), hi) for lo, hi in self._lost[s] if hi > b]
+            ranges[s] = mine
+            self._conceal_n[s] = len(mine) - (1 if mine and mine[0][0] == 0 and self._lost_open[s] else 0)
+            self._lost_open[s] = bool(mine) and mine[-1][1] == n_new[s]
+        for s in self._conceal_ended:                 # what lies behind the end of a stream damages nothing
+            self._lost[s] = []
+        if not any(n_new):
+            return
+        b = self.buf
+        conceal_rule.conceal_items(b["samples"], first, n_new, ranges, self.ccfg, b["conceal"], b["conceal_period"], b["conceal_score"],
+                                   sample_rate=self.codec_rate, table=b["conceal_tab"])
+
+    def _conceal_slots(self) -> List[int]:
+        return [s for s in range(self.S) if self.ccfg[s] is not None and (self.sched[s] is not None or s in self._conceal_ended)]
+
+    def concealed(self) -> Dict[int, conceal_rule.ConcealReport]:
+        """{slot: ConcealReport} of every concealing slot that is open or ended in the most recent push: ONE device-to-host copy of
+        the headers of the concealment rows (the only sync of the option, and only here).  A slot that has not been pushed to
+        reports no sample."""
+        slots = self._conceal_slots()
+        live = [s for s in slots if not self._fresh[s]] if self.buf is not None else []
+        table = self.buf["conceal"][:, :conceal_rule.HEADER_WORDS].cpu() if live else None
+        zero = torch.zeros(conceal_rule.HEADER_WORDS, dtype=torch.int32)
+        return {s: conceal_rule.report(table[s] if s in live else zero, self.codec_rate) for s in slots}
+
+    def conceal_onsets(self, slot: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(periods, scores) of the onsets of the slot's last push: device views (n,), int32 and fp32, valid until the slot's next
+        push.  periods: the lag repeated from each onset on (0: none, the run is silence); scores: its normalised correlation energy"""
+        if not isinstance(slot, int) or slot not in self._conceal_slots():
+            raise ValueError(f"slot {slot!r} has no concealment (open(conceal=)) or is neither open nor ended in the last push")
+        if self.buf is None or self._fresh[slot]:
+            return (torch.empty(0, dtype=torch.int32, device=self._device()), torch.empty(0, dtype=torch.float32, device=self._device()))
+        n = self._conceal_n[slot]
+        return self.buf["conceal_period"][slot, :n], self.buf["conceal_score"][slot, :n]
 
     def _echo(self, steps, final, tails: List[int], far: Mapping[int, torch.Tensor]) -> None:
         """echo: ONE launch appends the step's far samples to the history of every named slot with a canceller and re-writes in place

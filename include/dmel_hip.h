@@ -609,6 +609,47 @@ int dmel_echo_items(float* samples, int64_t row_stride, int S, const int64_t* fi
                     void* state /* S rows of 68112 words */, int64_t state_pitch, float* out_in, float* out_res, int64_t out_pitch,
                     void* table_scratch, void* stream);
 
+/* Packet-loss concealment (pitch waveform repetition) on codec-rate samples, S session slots in ONE launch (csrc/small_ops.hip): the
+ * concealment of encode sessions opened with conceal= (models/stream_sessions.py), whose rule, defaults and caveats are
+ * utils/conceal.py -- the kernel equals conceal.scan bit for bit.  Slot s takes its n_new[s] new samples at
+ * samples[s * row_stride + first[s] + i] (fp32, any 4-byte offset) through the rule; the n_ranges[s] <= 16 ranges [lo, hi) at
+ * ranges[(s * 16 + r) * 2], relative to first[s], are lost: their content is ignored.  Samples are RE-WRITTEN IN PLACE only inside
+ * lost ranges and the recovery stretches behind them; no other column is written.  The state row of slot s is the 4112 4-byte words
+ * at state + s * state_pitch words: int32 0 T (samples seen), 1 phase (0 good, 1 lost, 2 recovering), 2 t0 (the onset), 3 P (the
+ * period, 0: none), 4 k (samples since the onset), 5 rec (recovery samples left), 6 lost, 7 runs, 8 muted, 9 longest, 10 run (length
+ * of the open or last run); fp32 11 q (score of the last search), 12 e0 (its window energy); 13 .. 15 reserved and not written; at
+ * 16 a ring of 4096 fp32: the slot's OUTPUT sample y[t] at word t mod 4096.  A zeroed row is a fresh session.  With sum8 the sum of
+ * 8 contiguous segments, each ascending from 0.0f, combined as ((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7)), and every product,
+ * sum and division a separately rounded fp32 operation (no fma), per sample in order:
+ *     a lost sample with phase != 1, the onset:  t0 = T, k = P = run = 0, q = e0 = 0, runs += 1, phase = 1; if T >= W + Pmax:
+ *       a[i] = ring[t0 - W + i], e0 = sum8(a a); if e0 >= floor, over the lags p in [Pmin, Pmax]: b[i] = ring[t0 - W + i - p],
+ *       c = sum8(a b), e = sum8(b b), q(p) = c > 0 ? (c c) / (e + eps) : 0; q = the largest q(p), P its lowest lag, P = 0 if q == 0;
+ *       out_period[s * out_pitch + j] = P, out_score[s * out_pitch + j] = q for the j-th onset of the launch
+ *     s(k) = 0 if P == 0 or k >= H + D; else v = ring[t0 - P + k mod P]; k < H: s = v; else u = (float)(k - H) rD, g = 1.0f - u, s = g v
+ *     a lost sample:  y = s(k), k += 1, lost += 1, run += 1, muted += 1 where s(k) was the 0 of the first case
+ *     a good sample with phase == 1:  longest = max(longest, run), phase = 2, rec = F
+ *     a good sample with rec > 0:  w = (float)(F - rec + 1) rF, d = x - s(k), m = w d, y = s(k) + m, k += 1, rec -= 1, phase = 0 at rec == 0
+ *     any other good sample:  y = x;       always:  ring[T mod 4096] = y, T += 1
+ * iparams row s is (W, Pmin, Pmax, H, D, F), fparams row s (floor, eps, rD = fp32(1 / D), rF = fp32(1 / (F + 1))).  The words of
+ * out_period and out_score behind the onsets a row had are not written.  n_new[s] == 0 is an idle slot: neither its rows nor its
+ * parameters are looked at; when every slot is idle the call returns DMEL_OK and launches nothing.  NaN input is outside the contract.
+ * DMEL_EINVAL, nothing launched, dmel_last_error naming the item: S outside [1, 65535], a NULL pointer, samples, state, out_period,
+ * out_score or table not 4-byte aligned, a negative stride or pitch, state_pitch below 4112, n_new[s] or first[s] outside [0, 2^30),
+ * n_ranges[s] outside [0, 16], a range that is empty, outside [0, n_new[s]], or not behind the one in front of it with a gap (ranges
+ * are sorted and do not touch), W no multiple of 8 or below 8, Pmin < 8, Pmin > Pmax, W + Pmax > 4096, H < 0, D < 0,
+ * H + D + Pmax > 4096, F < 1, out_pitch below n_ranges[s], floor or rD not finite or negative, eps or rF not finite and positive, rF
+ * above 1.  first, n_new, n_ranges, ranges, iparams and fparams are HOST tables, copied as launch arguments into table_scratch (48 S
+ * 4-byte words of device memory, 4-byte aligned): the caller may overwrite them as soon as the call returns.  One workgroup of four
+ * waves per slot, the ring in LDS for the launch; the row's good and lost stretches are walked in order, each of them in parallel: a
+ * good stretch is a copy into the ring, an onset the (lag, segment) partial sums over the lanes, the fixed tree and a workgroup
+ * argmax on (q, -lag), a lost run and a recovery one lane per sample.  Plain vector stores, no atomics.  One profile record per
+ * launch in the family "conceal" (time and bytes in "small"). */
+int dmel_conceal_items(float* samples, int64_t row_stride, int S, const int64_t* first, const int64_t* n_new,
+                       const int32_t* n_ranges /* S */, const int32_t* ranges /* S x 16 x 2, relative to first[s] */,
+                       const int32_t* iparams /* S x 6: W, Pmin, Pmax, H, D, F */, const float* fparams /* S x 4: floor, eps, rD, rF */,
+                       void* state /* S rows */, int64_t state_pitch, int32_t* out_period, float* out_score, int64_t out_pitch,
+                       void* table_scratch, void* stream);
+
 /* Tones spliced into codec-rate audio, R parts in ONE launch (csrc/small_ops.hip): what decode sessions of a pool built with
  * tones=True send DTMF keys, beeps and call-progress tones with (models/stream_sessions.py: send_dtmf / send_tones), whose rule, tables
  * and caveats are utils/tones.py -- the kernel equals tones.render bit for bit.  Part r writes n[r] floats at dst[r].  Where src[r] is

@@ -663,6 +663,58 @@ int main() {
       CK(scan());
     }
     {
+      // packet-loss concealment: tables of exactly S entries (16 ranges, 6 and 4 parameters each), a table scratch of exactly 48 S
+      // words, out rows of exactly the ranges' count; its refusals read the host tables only
+      const int W = 9000;
+      auto smp = buf(3 * W), st = buf(3 * 4112), sc = buf(3 * 16);
+      std::vector<int32_t> per(3 * 16);
+      int64_t FI[3] = {5, -7, 1}, NN[3] = {8995, 0, 4000};
+      int32_t NR[3] = {16, 99, 2};                    // the idle item's ranges and parameters are not looked at
+      int32_t RG[3 * 32], IP[18];
+      float FP[12];
+      for (int r = 0; r < 16; ++r) { RG[2 * r] = 500 * r; RG[2 * r + 1] = 500 * r + 200 + r; RG[32 + 2 * r] = 9; RG[33 + 2 * r] = 3; RG[64 + 2 * r] = 0; RG[65 + 2 * r] = 0; }
+      RG[64] = 0; RG[65] = 10; RG[66] = 3990; RG[67] = 4000;           // a range at column 0 and one that ends with the item
+      const int32_t gi[6] = {480, 60, 360, 240, 1200, 120};
+      const float gf[4] = {1e-4f, 1e-12f, 1.f / 1200.f, 1.f / 121.f};
+      for (int k = 0; k < 18; ++k) IP[k] = (k >= 6 && k < 12) ? -1 : gi[k % 6];
+      for (int k = 0; k < 12; ++k) FP[k] = (k >= 4 && k < 8) ? NAN : gf[k % 4];
+      std::vector<uint32_t> tab(48 * 3);
+      int S = 3;
+      int64_t pitch = 16, sp = 4112;
+      auto scan = [&]() {
+        return dmel_conceal_items(smp.data(), W, S, FI, NN, NR, RG, IP, FP, st.data(), sp, per.data(), sc.data(), pitch, tab.data(), nullptr);
+      };
+      CK(scan());
+      auto refused = [&](const char* item, const char* what) {
+        const int rc = scan();
+        if (rc != DMEL_EINVAL || !std::strstr(dmel_last_error(), item)) { std::printf("FAIL conceal_items accepted %s (%d: %s)\n", what, rc, dmel_last_error()); ++failures; }
+      };
+      S = 0; refused("0 items", "no item");
+      S = 65536; refused("65536 items", "more than 65535 items");
+      S = 3; sp = 4111; refused("state pitch", "a state pitch below the row");
+      sp = 4112; NN[2] = -1; refused("item 2", "a negative sample count");
+      NN[2] = 4000; FI[0] = -1; refused("item 0", "a negative first column");
+      FI[0] = 5; NR[2] = 17; refused("item 2", "17 ranges");
+      NR[2] = 2; pitch = 15; refused("item 0", "more ranges than the output pitch");
+      pitch = 16; RG[67] = 4001; refused("item 2", "a range behind the item's samples");
+      RG[67] = 4000; RG[66] = 10; refused("item 2", "a range that touches the one before");
+      RG[66] = 3990; RG[3] = RG[2]; refused("item 0", "an empty range");
+      RG[3] = 701; RG[4] = 600; refused("item 0", "ranges that are not sorted");
+      RG[4] = 1000; IP[0] = 484; refused("item 0", "a window that is no multiple of 8");
+      IP[0] = 480; IP[13] = 7; refused("item 2", "Pmin below 8");
+      IP[13] = 361; refused("item 2", "Pmin above Pmax");
+      IP[13] = 60; IP[0] = 3744; refused("item 0", "a window and a period beyond the ring");
+      IP[0] = 480; IP[15] = 2537; refused("item 2", "hold, fade and period beyond the ring");
+      IP[15] = 240; IP[17] = 0; refused("item 2", "a recovery of 0");
+      IP[17] = 120; FP[1] = 0.f; refused("item 0", "eps = 0");
+      FP[1] = 1e-12f; FP[11] = 1.5f; refused("item 2", "rF above 1");
+      FP[11] = 1.f / 121.f; FP[8] = INFINITY; refused("item 2", "a floor that is not finite");
+      FP[8] = 0.f;                                  // a floor of 0 is allowed
+      CK(scan());
+      NN[0] = NN[2] = 0;                          // every item idle
+      CK(scan());
+    }
+    {
       // the tone splice: tables of exactly R entries, a segment table of exactly 8 n_segs words, a table scratch of exactly
       // 6 R + 5 n_segs int64; its refusals read the host tables only
       auto out = buf(4096), speech = buf(2048), sine = buf(8000), ramps = buf(48);

@@ -94,7 +94,18 @@ sessions of the echo pool are checked against encode() / report() of the host ru
 on the host), those of the plain pool against encode(); exactly one "echo" / one "small" launch record more per step and nothing
 else; exit status 1 where a check fails.  The canceller's launch alone (all sessions, one push each) is timed with events as well.
 --chunk 1920 makes the pushes 80 ms.  Run the plain --sessions form on the parent commit for the step time before the option
-existed.  No bound on the added time is set.  APPENDS its table to --out."""
+existed.  No bound on the added time is set.  APPENDS its table to --out.
+
+    python tools/bench_stream_encode.py --sessions 16 --conceal [--loss 0.05] [--label NAME] [--out profiles/sessions_conceal.txt]
+
+Sessions that conceal lost packets (a pool built with conceal=True, every session opened with conceal=True; voiced-like lines, and
+with probability --loss the first 20 ms of a session's push never arrived: push(lost=)) against the same sessions in a pool without
+the option, pushed zeros in the place of a loss, and, for scale, in a pool with an input leveller, the three interleaved in one
+process.  The ids and reports of the first two sessions of the concealing pool are checked against encode() / report() of the host
+rule's output (utils/conceal.py: scan), those of the plain pool against encode() of the zero-filled clips; exactly one "conceal" /
+one "small" launch record more per step and nothing else; exit status 1 where a check fails.  The concealment launch alone (all
+sessions, one push each, without a loss and with a hole in every slot) is timed with events as well.  Run the plain --sessions form
+on the parent commit for the step time before the option existed.  No bound on the added time is set.  APPENDS its table to --out."""
 import argparse, json, os, statistics, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -118,6 +129,8 @@ ap.add_argument("--voice", action="store_true", help="with --sessions: sessions 
 ap.add_argument("--dtmf", action="store_true", help="with --sessions: sessions with DTMF detection against the same pool without it")
 ap.add_argument("--level", action="store_true", help="with --sessions: sessions with an input leveller against the same pool without it")
 ap.add_argument("--echo", action="store_true", help="with --sessions: sessions with an echo canceller against the same pool without it")
+ap.add_argument("--conceal", action="store_true", help="with --sessions: sessions that conceal lost packets against the same pool without it")
+ap.add_argument("--loss", type=float, default=0.05, help="with --conceal: the probability that the first 20 ms of a session's push were lost")
 ap.add_argument("--label", default="", help="with --sessions: names the table (the commit measured)")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
@@ -129,6 +142,7 @@ if args.out is None:
                             "sessions_voice.txt" if args.sessions and args.voice else
                             "sessions_level.txt" if args.sessions and args.level else
                             "sessions_echo.txt" if args.sessions and args.echo else
+                            "sessions_conceal.txt" if args.sessions and args.conceal else
                             "sessions_dtmf.txt" if args.sessions and args.dtmf else
                             "sessions_channels.txt" if args.sessions and args.channels > 1 else
                             "sessions_pcm.txt" if args.sessions and args.sample_format == "s16" else
@@ -624,6 +638,170 @@ def sessions_echo_section():
         sys.exit(1)
 
 
+def sessions_conceal_section():
+    """S staggered sessions that conceal lost packets against the same sessions in a pool without the option, which are pushed zeros
+    in the place of a loss, and, for scale, in a pool with an input leveller (the comparable one-workgroup-per-slot launch); the same
+    audio, the same pushes, the same losses: with probability --loss the first 20 ms of a session's push never arrived.  The option
+    changes what the encoder sees, so the ids of the first two sessions are held to the host rule: encode() of conceal.scan of the
+    zero-filled clip; then the launches per step of the pools, and the concealment launch alone -- S slots, one push each, without a
+    loss and with one in every slot -- timed with events"""
+    import math, random
+    from dmel_codec_amd import _lib
+    from dmel_codec_amd.utils import conceal as conceal_rule
+    S, n, hole = args.sessions, args.chunk, 480
+    rng = random.Random(13)
+    total = (args.pushes + 5) * n
+    t = torch.arange(total, device=dev, dtype=torch.float64) / SR
+    f0 = [90.0 + 17.0 * s for s in range(S)]                                   # a voiced-like line per session: eight harmonics and noise
+    audio = torch.stack([sum(torch.sin(2 * math.pi * f * h * t) * (0.2 / h) for h in range(1, 9)).float() for f in f0])
+    audio += torch.randn(S, total, device=dev) * 0.003
+    opts = {"plain": {}, "conceal": {"conceal": True}, "level": {"level": True}}
+    pools = {k: codec.encode_sessions(slots=S, max_push_samples=n, **o) for k, o in opts.items()}
+    slots = {k: [p.open(**opts[k]) for _ in range(S)] for k, p in pools.items()}
+    first = [n * (1 + s % 3) // 3 for s in range(S)]            # the starts differ by a third of a push
+    pos, ms, ids = [0] * S, {k: [] for k in pools}, {k: [[] for _ in range(S)] for k in ("plain", "conceal")}
+    ranges, n_lost = [[] for _ in range(S)], 0
+
+    def step(k, chunks):
+        if k == "conceal":
+            out = pools[k].push({slots[k][s]: c[hole:] if gone else c for s, (c, gone) in enumerate(chunks)},
+                                lost={slots[k][s]: hole for s, (c, gone) in enumerate(chunks) if gone})
+        else:
+            out = pools[k].push({slots[k][s]: c for s, (c, gone) in enumerate(chunks)})
+        return [out[slots[k][s]] for s in range(S)]
+
+    def chunks_of(size):
+        nonlocal pos, n_lost
+        c = []
+        for s in range(S):
+            gone = size[s] > hole and rng.random() < args.loss
+            if gone:                                                           # what a caller without the option pushes: zeros
+                audio[s, pos[s]:pos[s] + hole] = 0.0
+                ranges[s].append((pos[s], pos[s] + hole))
+                n_lost += 1
+            c.append((audio[s, pos[s]:pos[s] + size[s]], gone))
+        pos = [p + k for p, k in zip(pos, size)]
+        return c
+
+    order = list(pools)
+    for i in range(args.pushes):
+        chunks = chunks_of(first if i == 0 else [n] * S)
+        for k in order[i % 3:] + order[:i % 3]:                                       # none always goes first
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            got = step(k, chunks)
+            torch.cuda.synchronize()
+            if i >= args.warmup:
+                ms[k].append((time.perf_counter() - t0) * 1e3)
+            if k in ids:
+                for s in range(S):
+                    ids[k][s].append(got[s])
+    # the launches of a step, from the profile counters (their events cost time: counted behind the timed steps)
+    families, launches = ("conceal", "level", "voice", "dtmf", "small", "stft_logmel", "conv_igemm"), {}
+    saved, args.loss = args.loss, 0.0                                          # the counted steps lose nothing: the same work in every pool
+    counted = [chunks_of([n] * S) for _ in range(4)]
+    args.loss = saved
+    _lib.prof_enable(True)
+    for k in pools:
+        launches[k] = []
+        for chunks in counted:
+            _lib.prof_reset()
+            got = step(k, chunks)
+            torch.cuda.synchronize()
+            launches[k].append({f: _lib.prof_read(f)["launches"] for f in families})
+            if k in ids:
+                for s in range(S):
+                    ids[k][s].append(got[s])
+    _lib.prof_enable(False)
+    _lib.prof_reset()
+    reports = pools["conceal"].concealed()
+    for k, p in pools.items():
+        for s in range(S):
+            last = p.close(slots[k][s])
+            if k in ids:
+                ids[k][s].append(last)
+    # the ids: the plain pool's are encode()'s of the zero-filled clip, the concealing pool's encode()'s of the host rule's output
+    same, checked = {"plain": True, "conceal": True}, min(S, 2)
+    for s in range(S):
+        x = audio[s, :pos[s]]
+        clips = [("plain", x)]
+        if s < checked:
+            xs, state, out, at = x.cpu(), None, [], 0
+            for lo, hi in ranges[s] + [(pos[s], pos[s])]:                       # one call per range: a call takes at most 16
+                y, state, _, _ = conceal_rule.scan(xs[at:hi], [(lo - at, hi - at)] if hi > lo else [], conceal_rule.ConcealConfig(), state, SR)
+                out.append(y)
+                at = hi
+            clips.append(("conceal", torch.cat(out).to(dev)))
+            same["conceal"] = same["conceal"] and reports[slots["conceal"][s]] == conceal_rule.report(state, SR)
+        for k, clip in clips:
+            ref, lens = codec.encode(clip[None], torch.tensor([clip.shape[0]], device=dev))
+            same[k] = same[k] and torch.equal(torch.cat(ids[k][s], dim=1), ref[0, :, :int(lens[0])])
+
+    def one_more(opt):
+        return all(a[opt] == 0 and b[opt] == 1 and b["small"] == a["small"] + 1 and all(b[f] == a[f] for f in families if f not in (opt, "small"))
+                   for a, b in zip(launches["plain"], launches[opt]))
+    held = one_more("conceal") and one_more("level")
+    # the concealment launch alone: S slots that gain one push each, timed with events; without a loss, then with one in every slot
+    cfg = conceal_rule.ConcealConfig()
+    rows_ = audio[:, :n].contiguous()
+    state = torch.zeros(S, conceal_rule.ROW_WORDS, dtype=torch.int32, device=dev)
+    o1 = torch.zeros(S, conceal_rule.MAX_RANGES, dtype=torch.int32, device=dev)
+    o2 = torch.zeros(S, conceal_rule.MAX_RANGES, device=dev)
+    tab = torch.empty(conceal_rule.TABLE_WORDS * S, dtype=torch.int32, device=dev)
+    alone = {"no_loss": [], "every_slot": []}
+    for i in range(2 * args.pushes):
+        a, which = (i // 2) * n, "every_slot" if i % 2 else "no_loss"
+        rows_.copy_(audio[:, a:a + n])
+        rg = [[(n // 2, n // 2 + hole)] if i % 2 and n > 2 * hole else [] for _ in range(S)]
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        conceal_rule.conceal_items(rows_, [0] * S, [n] * S, rg, [cfg] * S, state, o1, o2, sample_rate=SR, table=tab)
+        ev1.record()
+        torch.cuda.synchronize()
+        if i >= 2 * args.warmup:
+            alone[which].append(ev0.elapsed_time(ev1))
+    r = {"sessions": S, "chunk_s": n / SR, "pushes": args.pushes, "warmup": args.warmup, "loss": args.loss, "lost_packets": n_lost,
+         "ids_equal_encode": bool(same["plain"]), "ids_equal_encode_of_host_rule": bool(same["conceal"]),
+         "sessions_checked_against_host_rule": checked, "label": args.label, "launches_per_step": {k: launches[k][0] for k in pools},
+         "one_more_launch_per_step": bool(held),
+         "lost_samples": sorted({rep.lost_samples for rep in reports.values()}), "muted_samples": sorted({rep.muted_samples for rep in reports.values()}),
+         "conceal_launch_alone_ms": {k: {"median": round(statistics.median(v), 4), "p10": round(pct(v, 0.1), 4), "p90": round(pct(v, 0.9), 4),
+                                         "n": len(v)} for k, v in alone.items()}}
+    rows = []
+    for k, v in ms.items():
+        med = statistics.median(v)
+        r[k] = {"median_ms": round(med, 3), "p10_ms": round(pct(v, 0.1), 3), "p90_ms": round(pct(v, 0.9), 3), "n": len(v)}
+        rows.append(f"{S:8d}  {k:7s}  {med:9.3f}  {pct(v, 0.1):9.3f}  {pct(v, 0.9):9.3f}  {len(v):4d}  " +
+                    "  ".join(f"{f} {launches[k][0][f]}" for f in families))
+    r["added_median_ms"] = {k: round(r[k]["median_ms"] - r["plain"]["median_ms"], 3) for k in ("conceal", "level")}
+    rows.append(f"{S:8d}  concealment adds {r['added_median_ms']['conceal']:.3f} ms to the median step, the leveller (for scale) "
+                f"{r['added_median_ms']['level']:.3f} ms; each pool with an option launches exactly one kernel more per step than the plain one: {held}")
+    la = r["conceal_launch_alone_ms"]
+    rows.append(f"{S:8d}  the concealment launch alone ({S} slots x {n} samples; events around conceal_items, its table launch included): "
+                f"median {la['no_loss']['median']:.4f} ms (p10 {la['no_loss']['p10']:.4f}, p90 {la['no_loss']['p90']:.4f}) without a loss, "
+                f"{la['every_slot']['median']:.4f} ms (p10 {la['every_slot']['p10']:.4f}, p90 {la['every_slot']['p90']:.4f}) with a 20 ms hole, "
+                f"a search of 301 lags, in every slot; {len(alone['no_loss'])} launches each")
+    rows.append(f"{S:8d}  ids of the plain pool equal encode() of the zero-filled clips: {same['plain']}; ids and reports of the first {checked} "
+                f"sessions of the concealing pool equal encode() / report() of the host rule (conceal.scan of each clip): {same['conceal']}")
+    rows.append(f"{S:8d}  {n_lost} packets of 20 ms were lost (--loss {args.loss}); the sessions ended with {r['lost_samples']} lost and "
+                f"{r['muted_samples']} muted samples")
+    table = [(f"[{args.label}] " if args.label else "") + f"encode sessions that conceal lost packets, {n / SR:.2f} s pushes of 24 kHz audio, starts "
+             f"staggered by a third of a push, 80 mel / 8 groups / 70 channels / 20 layers (tools/bench_stream_encode.py --sessions {S} --conceal "
+             f"--loss {args.loss}" + (f" --chunk {n}" if n != 7680 else "") + ")",
+             f"wall time of one step (one push for every stream) incl. host synchronisation, {args.pushes - args.warmup} steady-state steps, the "
+             "three pools interleaved in one process;",
+             "plain = encode_sessions(S), conceal / level = encode_sessions(S, conceal=True / level=True) with every session opened with the "
+             "option; launches: records of the profile counters in one step",
+             "sessions  pool     median ms     p10 ms     p90 ms     n  launches of one step"] + rows
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "a") as f:
+        f.write("\n".join(table) + "\n\n")
+    print("\n".join(table), file=sys.stderr)
+    print(json.dumps(r))
+    if not (same["plain"] and same["conceal"] and held):
+        sys.exit(1)
+
+
 def sessions_resample_section():
     """S staggered sessions at their own rates: one pool that converts them in one launch against the codec-rate pool behind S
     StreamResampler(batch=1); the same audio, the same pushes, equal ids"""
@@ -868,6 +1046,11 @@ if args.echo and not args.sessions:
     ap.error("--echo needs --sessions")
 if args.sessions and args.echo:
     sessions_echo_section()
+    sys.exit(0)
+if args.conceal and not args.sessions:
+    ap.error("--conceal needs --sessions")
+if args.sessions and args.conceal:
+    sessions_conceal_section()
     sys.exit(0)
 if args.sessions and (args.voice or args.dtmf):
     sessions_detector_section("voice" if args.voice else "dtmf")
