@@ -114,6 +114,7 @@ PROTOTYPES = {
     "dmel_voice_items": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int, C.c_int, i64p, f32p, i32p, vp, vp, vp, C.c_int64, vp, vp]),
     "dmel_dtmf_items": (C.c_int, [vp, C.c_int64, C.c_int, i64p, i64p, i32p, f32p, f32p, i32p, vp, vp, vp, C.c_int64, vp, vp]),
     "dmel_level_items": (C.c_int, [vp, C.c_int64, C.c_int, i64p, i64p, i32p, f32p, vp, vp, vp, C.c_int64, vp, vp]),
+    "dmel_denoise_items": (C.c_int, [vp, C.c_int64, C.c_int, i64p, i64p, i32p, i32p, f32p, vp, vp, vp, C.c_int64, vp, vp, vp]),
     "dmel_echo_items": (C.c_int, [vp, C.c_int64, C.c_int, i64p, i64p, C.POINTER(vp), i64p, i32p, f32p, vp, C.c_int64, vp, vp, C.c_int64, vp, vp]),
     "dmel_conceal_items": (C.c_int, [vp, C.c_int64, C.c_int, i64p, i64p, i32p, i32p, i32p, f32p, vp, C.c_int64, vp, vp, C.c_int64, vp, vp]),
     "dmel_tone_items": (C.c_int, [C.POINTER(vp), C.POINTER(vp), i64p, i32p, i32p, C.c_int, i32p, C.c_int, vp, C.c_int, vp, C.c_int64, vp, vp]),

@@ -2066,6 +2066,273 @@ extern "C" int dmel_level_items(float* samples, int64_t row_stride, int S, const
 
 namespace dmel {
 
+// ---- noise suppression (spectral gain) on codec-rate samples (include/dmel_hip.h: dmel_denoise_items; the rule, the constant table and
+// the state row: utils/denoise.py).  Row s of the table is (first, n_new, N, learn_frames, alpha, oma, track, track_ratio, creep,
+// floor_gain, eps, rN, 0, 0, 0, 0), sixteen 4-byte words; workgroup s owns slot s.  It takes the slot's state row, the window and the
+// twiddles of its N (strided out of the constant table) into LDS once, then walks the new samples hop by hop: every thread reads x[p]
+// into the raw window and stores the finished hop's sample to the same column; at a hop boundary the frame runs in LDS -- window,
+// log2 N decimation-in-frequency stages (bin b ends at the bit-reversed index, so no permutation pass), the per-bin recursion on the
+// bins 0 .. H with the mirrored bins written by the thread that owns the bin, log2 N decimation-in-time stages with the conjugate
+// twiddles, window and overlap-add -- 2 log2 N + 5 barriers per frame.  The sums follow the rule's order (64 lane-strided partials, then
+// the xor tree) and every wave computes them, so the silent-frame branch is uniform without a broadcast.  The samples are single
+// words: a hop is at most two per thread, the frame's barriers are the cost, and the result cannot depend on where `first` lies.
+// Every operation is rounded on its own (fp contract(off)), the divisions are the correctly rounded ones.  Plain stores, no atomics.
+constexpr int kDnWords = 16, kDnMinN = 64, kDnMaxN = 1024, kDnMaxH = kDnMaxN / 2;
+constexpr int kDnRaw = 16, kDnTail = kDnRaw + kDnMaxN, kDnHop = kDnTail + kDnMaxH, kDnNz = kDnHop + kDnMaxH, kDnPrev = kDnNz + kDnMaxH + 1;
+constexpr int kDnState = (kDnPrev + kDnMaxH + 1 + 3) / 4 * 4;
+constexpr int kDnTabCos = 2 * kDnMaxN, kDnTabSin = kDnTabCos + kDnMaxH;
+__device__ __forceinline__ float denoise_sum(const float* v, int n, int lane) {
+#pragma clang fp contract(off)
+  float p = 0.0f;
+  for (int b = lane; b < n; b += 64) p = p + v[b];
+  for (int o = 32; o; o >>= 1) p = p + __shfl_xor(p, o);
+  return p;
+}
+__global__ __launch_bounds__(256) void denoise_kernel(float* __restrict__ samples, int64_t row_stride, const uint32_t* __restrict__ tab,
+                                                      uint32_t* __restrict__ state, float* __restrict__ out_in,
+                                                      float* __restrict__ out_out, int64_t out_pitch,
+                                                      const float* __restrict__ transform) {
+#pragma clang fp contract(off)
+  __shared__ float re[kDnMaxN], im[kDnMaxN], win[kDnMaxN], raw[kDnMaxN];
+  __shared__ float twc[kDnMaxH], tws[kDnMaxH], tail[kDnMaxH], hop[kDnMaxH];
+  __shared__ float nz[kDnMaxH + 1], prev[kDnMaxH + 1], pw[kDnMaxH + 1], qw[kDnMaxH + 1];
+  const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const uint32_t* row = tab + (size_t)s * kDnWords;
+  const int64_t n_new = (int64_t)(int32_t)row[1];
+  if (n_new <= 0) return;                               // idle (uniform: in front of the first barrier)
+  const int64_t first = (int64_t)(int32_t)row[0];
+  const int N = (int)row[2], H = N >> 1, r = kDnMaxN / N, bits = 31 - __clz(N), learn = (int)row[3];
+  const float alpha = __uint_as_float(row[4]), oma = __uint_as_float(row[5]), track = __uint_as_float(row[6]);
+  const float ratio = __uint_as_float(row[7]), creep = __uint_as_float(row[8]), floor_gain = __uint_as_float(row[9]);
+  const float eps = __uint_as_float(row[10]), rN = __uint_as_float(row[11]);
+  uint32_t* srow = state + (size_t)s * kDnState;
+  float* frow = reinterpret_cast<float*>(srow);
+  int frames = (int)srow[0], fill = (int)srow[1], learned = (int)srow[2];
+  if ((unsigned)fill >= (unsigned)H) fill = 0;          // no row the rule wrote; keeps every index below inside the LDS arrays
+  float sum_in = frow[3], sum_out = frow[4];
+  for (int i = tid; i < N; i += 256) {
+    raw[i] = frow[kDnRaw + i];
+    win[i] = transform[(2 * i + 1) * r];
+  }
+  for (int i = tid; i < H; i += 256) {
+    tail[i] = frow[kDnTail + i];
+    hop[i] = frow[kDnHop + i];
+    twc[i] = transform[kDnTabCos + i * r];
+    tws[i] = transform[kDnTabSin + i * r];
+  }
+  for (int i = tid; i <= H; i += 256) {
+    nz[i] = frow[kDnNz + i];
+    prev[i] = frow[kDnPrev + i];
+  }
+  __syncthreads();
+  float* g = samples + (int64_t)s * row_stride + first;  // the new samples are g[0 .. n_new)
+  float* oin = out_in + (int64_t)s * out_pitch;
+  float* oout = out_out + (int64_t)s * out_pitch;
+  int64_t at = 0, done = 0;
+  while (at < n_new) {
+    const int m = (int)min((int64_t)(H - fill), n_new - at);
+    for (int i = tid; i < m; i += 256) {                // in: the raw window; out: the hop the last frame finished, same column
+      raw[H + fill + i] = g[at + i];
+      g[at + i] = hop[fill + i];
+    }
+    at += m;
+    fill += m;
+    if (fill < H) break;                                // uniform
+    __syncthreads();
+    for (int i = tid; i < N; i += 256) {
+      re[i] = raw[i] * win[i];
+      im[i] = 0.0f;
+    }
+    for (int h = H; h >= 1; h >>= 1) {                  // forward: decimation in frequency
+      __syncthreads();
+      const int step = H / h;
+      for (int t = tid; t < H; t += 256) {
+        const int j = t & (h - 1), a = ((t - j) << 1) + j, b = a + h;
+        const float wr = twc[j * step], wi = -tws[j * step];
+        const float ar = re[a], ai = im[a], br = re[b], bi = im[b];
+        const float dr = ar - br, di = ai - bi;
+        re[a] = ar + br;
+        im[a] = ai + bi;
+        const float p0 = wr * dr, p1 = wi * di, p2 = wr * di, p3 = wi * dr;
+        re[b] = p0 - p1;
+        im[b] = p2 + p3;
+      }
+    }
+    __syncthreads();
+    for (int b = tid; b <= H; b += 256) {
+      const int idx = (int)(__brev((unsigned)b) >> (32 - bits));
+      const float xr = re[idx], xi = im[idx];
+      const float p0 = xr * xr, p1 = xi * xi;
+      float P = p0 + p1;
+      if (P < 1e-30f) P = 0.0f;
+      pw[b] = P;
+    }
+    __syncthreads();
+    const float p_in = denoise_sum(pw, H + 1, lane);    // the same bits in every wave
+    float p_out = 0.0f;
+    const bool silent = p_in == 0.0f;                   // uniform
+    if (!silent) {
+      for (int b = tid; b <= H; b += 256) {
+        const int idx = (int)(__brev((unsigned)b) >> (32 - bits));
+        const float P = pw[b];
+        float z = nz[b];
+        if (learned < learn) {
+          float d = P - z;
+          d = d / (float)(learned + 1);
+          z = z + d;
+        } else {
+          z = z * creep;
+          const float t = ratio * z;
+          if (P < t) {
+            float d = P - z;
+            d = track * d;
+            z = z + d;
+          }
+        }
+        nz[b] = z;
+        const float den = z > eps ? z : eps;
+        const float post = P / den;
+        float e = post - 1.0f;
+        e = e > 0.0f ? e : 0.0f;
+        const float c0 = alpha * prev[b], c1 = oma * e;
+        const float prio = c0 + c1;
+        const float q = 1.0f + prio;
+        float G = prio / q;
+        G = G > floor_gain ? G : floor_gain;
+        const float g2 = G * G;
+        prev[b] = g2 * post;
+        qw[b] = g2 * P;
+        const float yr = G * re[idx], yi = G * im[idx];
+        re[idx] = yr;
+        im[idx] = yi;
+        if (b > 0 && b < H) {
+          const int mir = (int)(__brev((unsigned)(N - b)) >> (32 - bits));
+          re[mir] = yr;
+          im[mir] = -yi;
+        }
+      }
+      if (learned < learn) ++learned;
+      for (int h = 1; h <= H; h <<= 1) {                // inverse: decimation in time, conjugate twiddles
+        __syncthreads();
+        const int step = H / h;
+        for (int t = tid; t < H; t += 256) {
+          const int j = t & (h - 1), a = ((t - j) << 1) + j, b = a + h;
+          const float wr = twc[j * step], wi = tws[j * step];
+          const float ar = re[a], ai = im[a], br = re[b], bi = im[b];
+          const float p0 = wr * br, p1 = wi * bi, p2 = wr * bi, p3 = wi * br;
+          const float tr = p0 - p1, ti = p2 + p3;
+          re[a] = ar + tr;
+          im[a] = ai + ti;
+          re[b] = ar - tr;
+          im[b] = ai - ti;
+        }
+      }
+      __syncthreads();
+      p_out = denoise_sum(qw, H + 1, lane);
+      sum_in = sum_in + p_in;
+      sum_out = sum_out + p_out;
+    }
+    for (int i = tid; i < H; i += 256) {                // window, overlap-add, and the raw window moves on by one hop
+      float v0 = 0.0f, v1 = 0.0f;
+      if (!silent) {
+        v0 = re[i] * rN;
+        v0 = v0 * win[i];
+        v1 = re[H + i] * rN;
+        v1 = v1 * win[H + i];
+      }
+      const float o = tail[i] + v0;
+      hop[i] = frames ? o : 0.0f;
+      tail[i] = v1;
+      raw[i] = raw[H + i];
+    }
+    if (tid == 0) {
+      oin[done] = p_in;
+      oout[done] = p_out;
+    }
+    ++frames;
+    ++done;
+    fill = 0;
+    __syncthreads();                                    // the next hop streams out of `hop` and into `raw`
+  }
+  __syncthreads();
+  const float nz_sum = denoise_sum(nz, H + 1, lane);
+  for (int i = tid; i < N; i += 256) frow[kDnRaw + i] = raw[i];
+  for (int i = tid; i < H; i += 256) {
+    frow[kDnTail + i] = tail[i];
+    frow[kDnHop + i] = hop[i];
+  }
+  for (int i = tid; i <= H; i += 256) {
+    frow[kDnNz + i] = nz[i];
+    frow[kDnPrev + i] = prev[i];
+  }
+  if (tid == 0) {
+    srow[0] = (uint32_t)frames; srow[1] = (uint32_t)fill; srow[2] = (uint32_t)learned;
+    frow[3] = sum_in; frow[4] = sum_out; frow[5] = nz_sum;
+  }
+}
+
+}  // namespace dmel
+
+extern "C" int dmel_denoise_items(float* samples, int64_t row_stride, int S, const int64_t* first, const int64_t* n_new, const int32_t* N,
+                                  const int32_t* learn_frames, const float* fparams, void* state, float* power_in, float* power_out,
+                                  int64_t out_pitch, const float* transform, void* table_scratch, void* stream) {
+  using namespace dmel;
+  DMEL_CHECK_ARG(samples && first && n_new && N && learn_frames && fparams && state && power_in && power_out && transform && table_scratch,
+                 "denoise_items: NULL argument");
+  DMEL_CHECK_ARG(S >= 1 && S <= 65535, "denoise_items: %d items, expected 1 .. 65535", S);
+  DMEL_CHECK_ARG((((uintptr_t)samples | (uintptr_t)state | (uintptr_t)power_in | (uintptr_t)power_out | (uintptr_t)transform |
+                   (uintptr_t)table_scratch) & 3) == 0,
+                 "denoise_items: samples, state, power_in, power_out, transform or table_scratch is not 4-byte aligned");
+  DMEL_CHECK_ARG(row_stride >= 0 && out_pitch >= 0, "denoise_items: negative row stride %lld or output pitch %lld", (long long)row_stride,
+                 (long long)out_pitch);
+  static const char* const kNames[8] = {"alpha", "oma", "track", "track_ratio", "creep", "floor_gain", "eps", "rN"};
+  static const float kLo[8] = {0.0f, 0.0f, 0.0f, 1.0f, 1.0f, 1e-6f, 1e-30f, 0.0f}, kHi[8] = {1.0f, 1.0f, 1.0f, 1e6f, 2.0f, 1.0f, 1.0f, 1.0f};
+  std::vector<uint32_t> tab((size_t)kDnWords * S, 0u);
+  int64_t live = 0;
+  double bytes = 0.0;
+  for (int s = 0; s < S; ++s) {
+    const int64_t n = n_new[s];
+    DMEL_CHECK_ARG(n >= 0 && n <= 0x3fffffff, "denoise_items: item %d: %lld new samples, expected 0 .. 2^30 - 1", s, (long long)n);
+    if (n == 0) continue;                               // idle: its parameters are not looked at (the table row stays 0)
+    DMEL_CHECK_ARG(first[s] >= 0 && first[s] <= 0x3fffffff, "denoise_items: item %d: first column %lld, expected 0 .. 2^30 - 1", s,
+                   (long long)first[s]);
+    const int32_t nf = N[s];
+    DMEL_CHECK_ARG(nf >= kDnMinN && nf <= kDnMaxN && (nf & (nf - 1)) == 0,
+                   "denoise_items: item %d: a frame of %d samples, expected a power of two in %d .. %d", s, nf, kDnMinN, kDnMaxN);
+    const int64_t hop = nf / 2, most = (n + hop - 1) / hop;                    // whatever the open hop holds (at most H - 1 samples)
+    DMEL_CHECK_ARG(out_pitch >= most, "denoise_items: item %d: %lld samples can complete %lld frames, which exceed the output pitch %lld", s,
+                   (long long)n, (long long)most, (long long)out_pitch);
+    DMEL_CHECK_ARG(learn_frames[s] >= 1 && learn_frames[s] <= 4096, "denoise_items: item %d: learn_frames %d, expected 1 .. 4096", s,
+                   learn_frames[s]);
+    const float* fp = fparams + (size_t)8 * s;
+    for (int k = 0; k < 8; ++k)
+      DMEL_CHECK_ARG(std::isfinite(fp[k]) && fp[k] >= kLo[k] && fp[k] <= kHi[k],
+                     "denoise_items: item %d: float parameter %d (%s) = %g is not finite or outside [%g, %g]", s, k, kNames[k], (double)fp[k],
+                     (double)kLo[k], (double)kHi[k]);
+    DMEL_CHECK_ARG(fp[0] < 1.0f && fp[1] > 0.0f && fp[2] > 0.0f, "denoise_items: item %d: alpha %g must be below 1, oma %g and track %g above 0",
+                   s, (double)fp[0], (double)fp[1], (double)fp[2]);
+    DMEL_CHECK_ARG(fp[7] * (float)nf == 1.0f, "denoise_items: item %d: rN %g is not 1 / %d", s, (double)fp[7], nf);
+    uint32_t* it = tab.data() + (size_t)kDnWords * s;
+    it[0] = (uint32_t)first[s]; it[1] = (uint32_t)n; it[2] = (uint32_t)nf; it[3] = (uint32_t)learn_frames[s];
+    std::memcpy(it + 4, fp, 8 * sizeof(float));
+    ++live;
+    bytes += 8.0 * (double)n + 8.0 * (double)most + 8.0 * (double)(16 + 3 * nf + 2);
+  }
+  if (live == 0) return DMEL_OK;                        // every item idle
+  hipStream_t st = (hipStream_t)stream;
+  DMEL_TRY(launch_table_put(tab.data(), tab.size() * sizeof(uint32_t), table_scratch, st));
+  {
+    // "small" carries the time and the bytes; the second scope only counts: one record per launch (dmel_prof_read("denoise"))
+    ProfScope ps("small", st, 0.0, bytes), count("denoise", st, 0.0, 0.0);
+    hipLaunchKernelGGL(denoise_kernel, dim3((unsigned)S), dim3(256), 0, st, samples, row_stride, static_cast<const uint32_t*>(table_scratch),
+                       static_cast<uint32_t*>(state), power_in, power_out, out_pitch, transform);
+  }
+  DMEL_HIP(hipGetLastError());
+  return DMEL_OK;
+}
+
+namespace dmel {
+
 // ---- echo cancellation (block NLMS) on codec-rate samples (include/dmel_hip.h: dmel_echo_items; the rule and the state row: utils/echo.py)
 // Row s of the table is (first, n_new, far pointer lo, hi, far_n, L, N, delay, mu, eps, far_floor, double_talk, meter, fN, 0, 0),
 // sixteen 4-byte words; workgroup s owns slot s, appends the slot's new far samples to the ring in its state row and re-writes its new

@@ -401,7 +401,7 @@ class VQGAN(nn.Module):
 
     def encode_sessions(self, slots: int, max_push_samples: int = 7680, sample_rate: Optional[int] = None, sample_rates=(),
                         voice: bool = False, dtmf: bool = False, level: bool = False, echo: bool = False,
-                        far_room_samples: int = 24000, conceal: bool = False):
+                        far_room_samples: int = 24000, conceal: bool = False, denoise: bool = False):
         """A pool of `slots` INDEPENDENT incremental encodes served by one streaming step: sessions open, receive their own number of
         samples per step (at most max_push_samples), stall and close on their own -- what streaming_encoder(batch=B), B streams in
         lockstep, cannot do -- and each one's concatenated ids are the bits of encode() on its own clip.  One STFT launch, one encoder
@@ -425,11 +425,14 @@ class VQGAN(nn.Module):
         conceal=True adds a packet-loss concealment row per slot: pool.open(conceal=True | ConcealConfig) starts a session's pitch
         waveform repetition, told of lost wire frames with pool.push(audio, lost={slot: n}), which re-writes the damaged codec-rate
         samples in place in one more launch for all slots of a step, in front of the echo launch, and is read with pool.concealed()
-        (utils/conceal.py has the rule).
+        (utils/conceal.py has the rule).  denoise=True adds a noise suppressor row per slot: pool.open(denoise=True | DenoiseConfig)
+        starts a session's spectral-gain suppressor of steady noise, which re-writes the session's codec-rate samples in place,
+        delayed by its frame, in one more launch for all slots of a step, behind the DTMF launch and in front of the leveller, and
+        is read with pool.denoised() (utils/denoise.py has the rule).
         See models/stream_sessions.py: EncodeSessions."""
         from .stream_sessions import EncodeSessions
         return EncodeSessions(self, slots, max_push_samples, sample_rate, sample_rates, voice, dtmf, level, echo, far_room_samples,
-                              conceal)
+                              conceal, denoise)
 
     # ------------------------------------------------------------------------------ decode side
     @torch.no_grad()

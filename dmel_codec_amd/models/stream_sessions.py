@@ -23,6 +23,7 @@ from ..utils import conceal as conceal_rule
 from ..utils import crossfade, pcm
 from ..utils import dtmf as dtmf_rule
 from ..utils import echo as echo_rule
+from ..utils import denoise as denoise_rule
 from ..utils import level as level_rule
 from ..utils import tones as tone_rule
 from ..utils import voice as voice_rule
@@ -181,7 +182,7 @@ class EncodeSessions(ParkingPool):
     whose filter window reads a lost frame) and keeps the part the resampler has not released for later steps.  In front of the
     echo launch of a step, ONE dmel_conceal_items launch serves every named concealing slot that gained samples -- on steps
     without a loss too: the ring needs the samples -- and re-writes in place the damaged columns and the recovery behind them:
-    the order of a step is convert, resample, conceal, echo, DTMF, level, STFT.  Contract: the ids of a concealing session are the
+    the order of a step is convert, resample, conceal, echo, DTMF, denoise, level, STFT.  Contract: the ids of a concealing session are the
     bits of encode(y, len) with y = conceal.scan(x0, ranges, config)[0], x0 the silence-filled stream at the codec's rate and
     ranges = conceal.damaged(lost wire ranges, rate, codec rate), however audio and losses were cut into pushes; with echo, DTMF
     or a leveller their rules apply to y in the order above.  The state is one row of 4112 words per slot (`conceal`: counters
@@ -195,6 +196,27 @@ class EncodeSessions(ParkingPool):
     reordering, reading RTP sequence numbers, FEC / RED, decode pools, losses in the far stream, the lockstep StreamingEncoder and
     whole-clip encode() (callers have conceal.scan / conceal.conceal_items).
 
+    Nothing above removes a steady background -- a fan, a car cabin, line hiss -- and the leveller brings it up with the speech.  A
+    pool built with denoise=True serves sessions opened with open(denoise=True | DenoiseConfig), each with a noise suppressor of its
+    own: an overlap-add spectral gain over a learnt and slowly tracked noise power per bin (the rule, its constant table, its state
+    row and its caveats: utils/denoise.py, which is also the host reference the pool is tested against bit for bit).  Behind the DTMF
+    launch of a step -- the detector reads the samples as received: a pool's DTMF reports do not change with denoise -- and in front
+    of the leveller, ONE dmel_denoise_items launch re-writes in place exactly the columns every named slot with a suppressor gained;
+    a step without such a slot launches what it did.  IT IS THE FIRST OPTION WITH A DELAY: the samples the leveller, the STFT and the
+    voice detector see are the suppressed ones delayed by the config's frame_samples (512 by default, 21.3 ms at 24 kHz), the
+    session's length and timeline are kept, its first frame_samples samples are zeros and its last frame_samples input samples are
+    not emitted (push that many zeros in front of `final` to have them).  Contract: the ids of a denoising session are the bits of
+    encode(y, len) with y = denoise.scan(x, config)[0] and x the session's clip at the codec's rate; with a leveller as well, of
+    encode(level.scan(y, ...)[0]).  The state is one row of 3092 words per slot (`denoise`), zeroed with the slot's other rows, and
+    travels with snapshot / restore as one more segment; push() returns what it returns and never syncs.  denoised() -> {slot:
+    DenoiseReport} (frames, learning, power in and out, attenuation, noise power) for every slot with a suppressor that is open or
+    ended in the most recent push, from ONE device-to-host copy of the rows' headers, the only sync and only when asked;
+    denoise_frames(slot) -> (power_in, power_out), device fp32 views of the frames the slot's last push completed.  A pool built
+    without denoise=True allocates and launches exactly what it did, refuses open(denoise=) and a snapshot that carries a suppressor;
+    a session without one snapshots to the bytes it always did.  Not served: decode pools and the far stream, the lockstep
+    StreamingEncoder and whole-clip encode() (callers have denoise.scan / denoise.denoise_items), a residual echo suppressor driven
+    by the canceller, comfort noise, transient noise, delay compensation of the reports of the other options.
+
     Only encoders the one-launch streaming kernel takes (residual channels in (32, 80], no condition, no output projection,
     dilations <= 8, fp32): anything else is refused at construction.
 
@@ -204,7 +226,7 @@ class EncodeSessions(ParkingPool):
 
     def __init__(self, codec, slots: int, max_push_samples: int = 7680, sample_rate: Optional[int] = None,
                  sample_rates: Iterable[int] = (), voice: bool = False, dtmf: bool = False, level: bool = False,
-                 echo: bool = False, far_room_samples: int = 24000, conceal: bool = False):
+                 echo: bool = False, far_room_samples: int = 24000, conceal: bool = False, denoise: bool = False):
         enc, tr = codec.encoder, codec.encode_mel_transform
         if sample_rate is not None and int(sample_rate) != int(tr.sample_rate):
             raise NotImplementedError(f"sessions run at the codec's own rate ({tr.sample_rate} Hz); resample in front (StreamResampler), "
@@ -293,13 +315,19 @@ class EncodeSessions(ParkingPool):
         self._lost_open = [False] * self.S            # the slot's newest sample was a lost one: a range at its next sample is no onset
         self._conceal_n = [0] * self.S                # onsets of the slot's last push: the valid words of its period / score rows
         self._conceal_ended: set = set()              # concealing slots that ended in the most recent push
+        if not isinstance(denoise, bool):
+            raise ValueError(f"denoise must be a bool (a session's config goes to open(denoise=)), got {denoise!r}")
+        self.denoise_on = denoise                     # the pool keeps suppressor rows: sessions may open with denoise=
+        self.ncfg: List[Optional[denoise_rule.DenoiseConfig]] = [None] * self.S  # the slot's noise suppressor (None: none)
+        self._denoise_n = [0] * self.S                # frames the slot's last push completed: the valid words of its power rows
+        self._denoise_ended: set = set()              # slots with a suppressor that ended in the most recent push
 
     def tokens_emitted(self, slot: int) -> int:
         self._check_open(slot)
         return self.sched[slot].tokens
 
     def open(self, sample_rate: Optional[int] = None, sample_format: str = "f32", channels: int = 1,
-             channel: Optional[int] = None, voice=None, dtmf=None, level=None, echo=None, conceal=None) -> int:
+             channel: Optional[int] = None, voice=None, dtmf=None, level=None, echo=None, conceal=None, denoise=None) -> int:
         """take a free slot: fresh schedule, state zeroed before its first push.  sample_rate: the rate this session's pushes arrive
         at, one of the declared `sample_rates` (None: the codec's).  sample_format: "f32", "s16" for torch.int16 pushes (16-bit
         signed PCM, x / 32768), or "ulaw" / "alaw" for torch.uint8 pushes (G.711 codes).  channels: 1 .. 8; above 1 the pushes are
@@ -310,7 +338,9 @@ class EncodeSessions(ParkingPool):
         a pool built with level=True: the encoder then sees the levelled samples.  echo: True (the defaults of utils/echo.py) or an
         EchoConfig starts the session's echo canceller, on a pool built with echo=True: push(far=) then takes its far-end samples.
         conceal: True (the defaults of utils/conceal.py) or a ConcealConfig starts the session's packet-loss concealment, on a pool
-        built with conceal=True: push(lost=) then takes the frames its wire lost.
+        built with conceal=True: push(lost=) then takes the frames its wire lost.  denoise: True (the defaults of utils/denoise.py)
+        or a DenoiseConfig starts the session's noise suppressor, on a pool built with denoise=True: the leveller and the encoder
+        then see the suppressed samples, delayed by the config's frame_samples.
         Raises when every slot is taken; a refused open takes no slot."""
         rate = self.codec_rate if sample_rate is None else int(sample_rate)
         pick = self._check_wire(rate, sample_format, channels, channel)
@@ -319,6 +349,7 @@ class EncodeSessions(ParkingPool):
         lev = self._check_level(level_rule.as_config(level))
         ec = self._check_echo(echo_rule.as_config(echo))
         cc = self._check_conceal(conceal_rule.as_config(conceal))
+        nc = self._check_denoise(denoise_rule.as_config(denoise))
         s = self._first_free()
         self._occupy(s, EncodeSchedule(self.geo), 0, rate, sample_format, channels)
         self.s0[s], self.tail[s], self.pick[s] = 0, 0, pick
@@ -327,6 +358,7 @@ class EncodeSessions(ParkingPool):
         self.lcfg[s], self._level_n[s] = lev, 0
         self.ecfg[s], self._echo_n[s], self._far[s] = ec, 0, 0
         self.ccfg[s], self._conceal_n[s], self._lost[s], self._lost_open[s] = cc, 0, [], False
+        self.ncfg[s], self._denoise_n[s] = nc, 0
         return s
 
     def _check_voice(self, cfg: Optional[voice_rule.VoiceConfig]) -> Optional[voice_rule.VoiceConfig]:
@@ -365,6 +397,12 @@ class EncodeSessions(ParkingPool):
             if not self.conceal_on:
                 raise ValueError("conceal on a pool built without conceal=True: it has no concealment rows")
             cfg.samples(self.codec_rate)
+        return cfg
+
+    def _check_denoise(self, cfg: Optional[denoise_rule.DenoiseConfig]) -> Optional[denoise_rule.DenoiseConfig]:
+        """a session's suppressor config, refused here for open() and for restore() alike"""
+        if cfg is not None and not self.denoise_on:
+            raise ValueError("denoise on a pool built without denoise=True: it has no suppressor rows")
         return cfg
 
     def _validate_lost(self, audio: Mapping[int, torch.Tensor], lost) -> Dict[int, int]:
@@ -498,6 +536,14 @@ class EncodeSessions(ParkingPool):
                             conceal_period=torch.zeros(self.S, conceal_rule.MAX_RANGES, dtype=torch.int32, device=dev),
                             conceal_score=torch.zeros(self.S, conceal_rule.MAX_RANGES, dtype=torch.float32, device=dev),
                             conceal_tab=torch.empty(conceal_rule.TABLE_WORDS * self.S, dtype=torch.int32, device=dev))
+        if self.denoise_on:                           # dmel_denoise_items: a state row per slot, the step's frame powers (a push completes
+            #                                           at most codec_push // 32 + 1 frames of hop 32 or more), the constant transform table
+            pitch = self.codec_push // (denoise_rule.MIN_FRAME // 2) + 2
+            self.buf.update(denoise=torch.zeros(self.S, denoise_rule.STATE_WORDS, dtype=torch.int32, device=dev),
+                            denoise_in=torch.zeros(self.S, pitch, dtype=torch.float32, device=dev),
+                            denoise_out=torch.zeros(self.S, pitch, dtype=torch.float32, device=dev),
+                            denoise_transform=denoise_rule.transform_table().to(dev),
+                            denoise_tab=torch.empty(denoise_rule.TABLE_WORDS * self.S, dtype=torch.int32, device=dev))
 
     def _prepare_slot(self, s: int) -> None:
         super()._prepare_slot(s)
@@ -511,6 +557,8 @@ class EncodeSessions(ParkingPool):
             self.buf["echo"][s].zero_()               # the fresh canceller state, the ring with it
         if self.conceal_on:
             self.buf["conceal"][s].zero_()            # the fresh concealment state, the ring with it
+        if self.denoise_on:
+            self.buf["denoise"][s].zero_()            # the fresh suppressor state: windows, overlap tail and noise estimate
 
     def _slot_views(self, s: int):
         b, G = self.buf, self.G
@@ -545,6 +593,8 @@ class EncodeSessions(ParkingPool):
         if self.ccfg[s] is not None:                  # likewise, and the damaged ranges the resampler has not released yet
             meta["conceal"], meta["conceal_lost"] = self.ccfg[s].as_dict(), [list(r) for r in self._lost[s]]
             meta["conceal_open"] = self._lost_open[s]
+        if self.ncfg[s] is not None:                  # likewise
+            meta["denoise"] = self.ncfg[s].as_dict()
         return meta
 
     def _park_schedule(self, meta: Mapping) -> EncodeSchedule:
@@ -567,6 +617,8 @@ class EncodeSessions(ParkingPool):
             shapes += [(f"echo_far.{i}", 1, n) for i, (_, n) in enumerate(pieces)]
         if meta.get("conceal") is not None:           # the concealment row, its ring included; a session without a sample owns the zeroed one
             shapes.append(("conceal", 1, conceal_rule.ROW_WORDS if meta["schedule"]["samples"] > 0 else 0))
+        if meta.get("denoise") is not None:           # the suppressor row, likewise
+            shapes.append(("denoise", 1, denoise_rule.STATE_WORDS if meta["schedule"]["samples"] > 0 else 0))
         return shapes
 
     def _park_rows(self, s: int) -> Dict[str, torch.Tensor]:
@@ -587,6 +639,8 @@ class EncodeSessions(ParkingPool):
             rows["echo"] = b["echo"][s:s + 1]
         if self.conceal_on:
             rows["conceal"] = b["conceal"][s:s + 1]
+        if self.denoise_on:
+            rows["denoise"] = b["denoise"][s:s + 1]
         return rows
 
     def _park_places(self, s: int):
@@ -662,6 +716,15 @@ class EncodeSessions(ParkingPool):
                              f"samples the session has released: {raw!r} (conceal_open: {meta.get('conceal_open')!r})")
         return cfg, ranges, meta["conceal_open"]
 
+    def _park_denoise(self, meta: Mapping) -> Optional[denoise_rule.DenoiseConfig]:
+        """the suppressor config a snapshot carries (None: none); ValueError where it is no config"""
+        if meta.get("denoise") is None:
+            return None
+        try:
+            return denoise_rule.DenoiseConfig.from_dict(meta["denoise"])
+        except TypeError as e:
+            raise ValueError(f"the denoise config of the snapshot is not a DenoiseConfig: {e}") from None
+
     def _park_fits(self, meta: Mapping, sc: EncodeSchedule) -> None:
         g, (lo, hi) = self.geo, meta["window"]
         room = self.codec_push // g.hop + 1 + (g.n_fft - g.pad + g.hop - 1) // g.hop
@@ -676,6 +739,7 @@ class EncodeSessions(ParkingPool):
             raise ValueError(f"{meta['echo_far']} far samples against {meta['schedule']['samples']} samples of the session do not fit "
                              f"far_room_samples = {self.far_room}")
         self._check_conceal(self._park_conceal(meta)[0])
+        self._check_denoise(self._park_denoise(meta))
 
     def _park_adopt(self, s: int, meta: Mapping) -> None:
         super()._park_adopt(s, meta)
@@ -686,6 +750,7 @@ class EncodeSessions(ParkingPool):
         self.ecfg[s], self._echo_n[s], self._far[s] = self._park_echo(meta), 0, meta.get("echo_far", 0)
         self.ccfg[s], self._lost[s], self._lost_open[s] = self._park_conceal(meta)
         self._conceal_n[s] = 0
+        self.ncfg[s], self._denoise_n[s] = self._park_denoise(meta), 0
 
     # -- one step ----------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -705,7 +770,7 @@ class EncodeSessions(ParkingPool):
         self._ensure_buffers(dev)
         converted, placed = self._place(audio)
         released = self._resample(converted, final, placed)
-        tails = list(self.tail) if self.dtmf_on or self.level_on or self.echo_on or self.conceal_on else None
+        tails = list(self.tail) if self.dtmf_on or self.level_on or self.echo_on or self.conceal_on or self.denoise_on else None
         steps = self._intake(audio, released, placed, final)
         with torch.cuda.device(dev):
             if self.conceal_on:
@@ -714,6 +779,8 @@ class EncodeSessions(ParkingPool):
                 self._echo(steps, final, tails, far)
             if self.dtmf_on:
                 self._dtmf(steps, final, tails)
+            if self.denoise_on:
+                self._denoise(steps, final, tails)
             if self.level_on:
                 self._level(steps, final, tails)
             mel = self._stft(steps, dev)
@@ -1026,6 +1093,48 @@ class EncodeSessions(ParkingPool):
             return empty, empty.clone()
         n = self._level_n[slot]
         return self.buf["level_peak"][slot, :n], self.buf["level_gain"][slot, :n]
+
+    def _denoise(self, steps, final, tails: List[int]) -> None:
+        """noise suppression: ONE launch re-writes in place the samples every named slot with a suppressor gained in this step --
+        columns [tail before, tail after) of its row -- behind the DTMF launch, which reads them as received, and in front of the
+        leveller and the STFT phase, which read them suppressed (and delayed by the slot's frame)"""
+        self._denoise_ended = {s for s in final if self.ncfg[s] is not None}
+        first, n_new = [0] * self.S, [0] * self.S
+        for s, st in steps.items():
+            if self.ncfg[s] is not None:
+                first[s], n_new[s] = tails[s], self.tail[s] - tails[s]
+                H = self.ncfg[s].hop
+                self._denoise_n[s] = st.samples // H - (st.samples - n_new[s]) // H
+        if not any(n_new):
+            return
+        b = self.buf
+        denoise_rule.denoise_items(b["samples"], first, n_new, self.ncfg, b["denoise"], b["denoise_in"], b["denoise_out"],
+                                   b["denoise_transform"], table=b["denoise_tab"])
+
+    def _denoise_slots(self) -> List[int]:
+        return [s for s in range(self.S) if self.ncfg[s] is not None and (self.sched[s] is not None or s in self._denoise_ended)]
+
+    def denoised(self) -> Dict[int, denoise_rule.DenoiseReport]:
+        """{slot: DenoiseReport} of every slot with a suppressor that is open or ended in the most recent push: ONE device-to-host
+        copy of the headers of the suppressor rows (the only sync of the suppressor, and only here).  A slot that has not been
+        pushed to reports no sample."""
+        slots = self._denoise_slots()
+        live = [s for s in slots if not self._fresh[s]] if self.buf is not None else []
+        table = self.buf["denoise"][:, :denoise_rule.HEADER_WORDS].cpu() if live else None
+        zero = torch.zeros(denoise_rule.HEADER_WORDS, dtype=torch.int32)
+        return {s: denoise_rule.report(table[s] if s in live else zero, self.ncfg[s].frame_samples, self.codec_rate,
+                                       self.ncfg[s].learn_frames) for s in slots}
+
+    def denoise_frames(self, slot: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(power_in, power_out) of the frames the slot's last push completed: device fp32 views (n,), valid until the slot's next
+        push.  power_in: the sum of the bin powers of the frame as received; power_out: the same behind the gain"""
+        if not isinstance(slot, int) or slot not in self._denoise_slots():
+            raise ValueError(f"slot {slot!r} has no noise suppressor (open(denoise=)) or is neither open nor ended in the last push")
+        if self.buf is None or self._fresh[slot]:
+            empty = torch.empty(0, dtype=torch.float32, device=self._device())
+            return empty, empty.clone()
+        n = self._denoise_n[slot]
+        return self.buf["denoise_in"][slot, :n], self.buf["denoise_out"][slot, :n]
 
     def _wavenet(self, steps) -> None:
         """encoder WaveNet: every level of every slot advances to its own new frontier"""

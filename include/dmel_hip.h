@@ -571,6 +571,34 @@ int dmel_level_items(float* samples, int64_t row_stride, int S, const int64_t* f
                      const float* fparams /* S x 10 */, void* state /* (S, 16) words */, float* out_peak, float* out_gain,
                      int64_t out_pitch, void* table_scratch, void* stream);
 
+/* Noise suppression (a spectral gain over a learnt and tracked noise power) on codec-rate samples, S session slots in ONE launch
+ * (csrc/small_ops.hip): the suppressor of encode sessions opened with denoise= (models/stream_sessions.py), whose rule, constants, table
+ * and caveats are utils/denoise.py -- the kernel equals denoise.scan bit for bit.  Slot s RE-WRITES IN PLACE its n_new[s] new samples at
+ * samples[s * row_stride + first[s] + i] (fp32, any 4-byte offset; no other column is written) with the suppressed signal delayed by
+ * N[s] samples, and carries one row of 3092 4-byte words in `state`: int32 0 frames, 1 fill (samples of the open hop), 2 learned; fp32
+ * 3 sum of power_in, 4 sum of power_out, 5 the sum of the noise powers; 6 .. 15 kept at 0; then fp32 raw[1024] at 16 (the last whole
+ * hop, then the open hop), tail[512] at 1040, hop[512] at 1552 (the finished hop that streams out), Nz[513] at 2064, prev[513] at
+ * 2577.  A zeroed row is a fresh session.  N[s] is the frame, a power of two in 64 .. 1024, the hop is N / 2; frame k is computed when
+ * its last sample arrives: sine window, radix-2 FFT, the per-bin recursion, inverse FFT, window, overlap-add, every fp32 operation
+ * rounded on its own in the order utils/denoise.py states.  power_in[s * out_pitch + j] = the sum of the bin powers of the j-th frame
+ * the launch completed, power_out[...] the same behind the gain.  fparams row s is (alpha, 1 - alpha, track, track_ratio, creep,
+ * floor_gain, eps, 1 / N), fp32 values computed by the caller; learn_frames[s] in 1 .. 4096.  transform: the constant table of 3072
+ * fp32 words on the device (sin(pi k / 2048), k < 2048; cos(2 pi k / 1024), k < 512; sin(2 pi k / 1024), k < 512), computed in float64
+ * by the caller and rounded once; no trigonometry runs on the device.  The words behind the frames a row completed are not written.
+ * n_new[s] == 0 is an idle slot: neither its rows nor its parameters are looked at; when every slot is idle the call returns DMEL_OK
+ * and launches nothing.  NaN input is outside the contract.  DMEL_EINVAL, nothing launched, dmel_last_error naming the item: S outside
+ * [1, 65535], a NULL pointer, a pointer not 4-byte aligned, a negative stride or pitch, n_new[s] or first[s] outside [0, 2^30), N[s] no
+ * power of two in [64, 1024], out_pitch below ceil(n_new[s] / (N[s] / 2)), learn_frames[s] outside [1, 4096], a value of fparams
+ * that is not finite or outside its range (alpha [0, 1), 1 - alpha (0, 1], track (0, 1], track_ratio [1, 1e6], creep [1, 2],
+ * floor_gain [1e-6, 1], eps [1e-30, 1]), rN that is not 1 / N[s].  The host tables are copied as launch arguments into table_scratch
+ * (16 S 4-byte words of device memory): the caller may overwrite them as soon as the call returns.  One workgroup of four waves per
+ * slot, 2 log2 N + 5 barriers per frame; plain stores, no atomics.  One profile record per launch in the family "denoise" (time and
+ * bytes in "small"). */
+int dmel_denoise_items(float* samples, int64_t row_stride, int S, const int64_t* first, const int64_t* n_new, const int32_t* N,
+                       const int32_t* learn_frames, const float* fparams /* S x 8 */, void* state /* (S, 3092) words */,
+                       float* power_in, float* power_out, int64_t out_pitch, const float* transform /* 3072 words */,
+                       void* table_scratch, void* stream);
+
 /* Echo cancellation (a block NLMS adaptive FIR with a meter) on codec-rate samples, S session slots in ONE launch
  * (csrc/small_ops.hip): the canceller of encode sessions opened with echo= (models/stream_sessions.py), whose rule, defaults and caveats
  * are utils/echo.py -- the kernel equals echo.scan bit for bit.  Slot s first appends its far_n[s] new far-end samples far[s][i] (fp32)

@@ -663,6 +663,50 @@ int main() {
       CK(scan());
     }
     {
+      // the noise suppressor: tables of exactly S entries (8 S parameters), a table scratch of exactly 16 S words, a transform table
+      // of exactly 3072 words; its refusals read the host tables only
+      const int W = 9000;
+      auto smp = buf(3 * W), st = buf(3 * 3092), pi = buf(3 * 90), po = buf(3 * 90), tr = buf(3072);
+      int64_t FI[3] = {5, -7, 1}, NN[3] = {8995, 0, 32 * 90};
+      int32_t FR[3] = {512, -1, 64}, LF[3] = {16, -1, 1};   // the idle item's parameters are not looked at
+      float FP[24];
+      const float good[8] = {0.96f, 0.04f, 0.05f, 6.f, 1.002f, 0.126f, 1e-20f, 1.f / 512.f};
+      for (int k = 0; k < 24; ++k) FP[k] = (k >= 8 && k < 16) ? NAN : good[k % 8];
+      FP[16] = 0.f; FP[17] = 1.f; FP[23] = 1.f / 64.f;      // an alpha of 0 is allowed
+      std::vector<uint32_t> tab(16 * 3);
+      int S = 3;
+      int64_t pitch = 90;
+      auto scan = [&]() {
+        return dmel_denoise_items(smp.data(), W, S, FI, NN, FR, LF, FP, st.data(), pi.data(), po.data(), pitch, tr.data(), tab.data(), nullptr);
+      };
+      CK(scan());
+      auto refused = [&](const char* item, const char* what) {
+        const int rc = scan();
+        if (rc != DMEL_EINVAL || !std::strstr(dmel_last_error(), item)) { std::printf("FAIL denoise_items accepted %s (%d: %s)\n", what, rc, dmel_last_error()); ++failures; }
+      };
+      S = 0; refused("0 items", "no item");
+      S = 65536; refused("65536 items", "more than 65535 items");
+      S = 3; NN[2] = -1; refused("item 2", "a negative sample count");
+      NN[2] = 32 * 90 + 1; refused("item 2", "more frames than the output pitch");
+      NN[2] = 32 * 90; FI[0] = -1; refused("item 0", "a negative first column");
+      FI[0] = 5; FR[2] = 32; refused("item 2", "a frame of 32 samples");
+      FR[2] = 96; refused("item 2", "a frame that is no power of two");
+      FR[2] = 64; FR[0] = 2048; refused("item 0", "a frame of 2048 samples");
+      FR[0] = 512; LF[0] = 0; refused("item 0", "learn_frames = 0");
+      LF[0] = 16; LF[2] = 4097; refused("item 2", "learn_frames above 4096");
+      LF[2] = 1; FP[0] = 1.f; refused("item 0", "an alpha of 1");
+      FP[0] = 0.96f; FP[17] = 0.f; refused("item 2", "1 - alpha = 0");
+      FP[17] = 1.f; FP[2] = 1.5f; refused("item 0", "a track above 1");
+      FP[2] = 0.05f; FP[19] = 0.5f; refused("item 2", "a track_ratio below 1");
+      FP[19] = 6.f; FP[4] = INFINITY; refused("item 0", "a creep that is not finite");
+      FP[4] = 1.002f; FP[21] = 0.f; refused("item 2", "a floor_gain of 0");
+      FP[21] = 0.126f; FP[6] = -1e-20f; refused("item 0", "a negative eps");
+      FP[6] = 1e-20f; FP[23] = 1.f / 512.f; refused("item 2", "an rN that is not 1 / N");
+      FP[23] = 1.f / 64.f;
+      NN[0] = NN[2] = 0;                          // every item idle
+      CK(scan());
+    }
+    {
       // packet-loss concealment: tables of exactly S entries (16 ranges, 6 and 4 parameters each), a table scratch of exactly 48 S
       // words, out rows of exactly the ranges' count; its refusals read the host tables only
       const int W = 9000;

@@ -105,7 +105,17 @@ process.  The ids and reports of the first two sessions of the concealing pool a
 rule's output (utils/conceal.py: scan), those of the plain pool against encode() of the zero-filled clips; exactly one "conceal" /
 one "small" launch record more per step and nothing else; exit status 1 where a check fails.  The concealment launch alone (all
 sessions, one push each, without a loss and with a hole in every slot) is timed with events as well.  Run the plain --sessions form
-on the parent commit for the step time before the option existed.  No bound on the added time is set.  APPENDS its table to --out."""
+on the parent commit for the step time before the option existed.  No bound on the added time is set.  APPENDS its table to --out.
+
+    python tools/bench_stream_encode.py --sessions 16 --denoise [--label NAME] [--out profiles/sessions_denoise.txt]
+
+Sessions with a noise suppressor (a pool built with denoise=True, every session opened with denoise=True -- frames of 512, hops of
+256; lines with noise floors 6 dB apart and a tone burst in every third push) against the same sessions in a pool without the option
+and, for scale, in a pool with an input leveller, the three interleaved in one process.  The ids of every session of the denoising
+pool are checked against encode() of the host rule's output (utils/denoise.py: scan), those of the plain pool against encode();
+exactly one "denoise" / one "small" launch record more per step and nothing else; exit status 1 where a check fails.  The
+suppressor's launch alone (all sessions, one push each) is timed with events as well.  Run the plain --sessions form on the parent
+commit for the step time before the option existed.  No bound on the added time is set.  APPENDS its table to --out."""
 import argparse, json, os, statistics, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -130,6 +140,7 @@ ap.add_argument("--dtmf", action="store_true", help="with --sessions: sessions w
 ap.add_argument("--level", action="store_true", help="with --sessions: sessions with an input leveller against the same pool without it")
 ap.add_argument("--echo", action="store_true", help="with --sessions: sessions with an echo canceller against the same pool without it")
 ap.add_argument("--conceal", action="store_true", help="with --sessions: sessions that conceal lost packets against the same pool without it")
+ap.add_argument("--denoise", action="store_true", help="with --sessions: sessions with a noise suppressor against the same pool without it")
 ap.add_argument("--loss", type=float, default=0.05, help="with --conceal: the probability that the first 20 ms of a session's push were lost")
 ap.add_argument("--label", default="", help="with --sessions: names the table (the commit measured)")
 ap.add_argument("--out", default=None)
@@ -143,6 +154,7 @@ if args.out is None:
                             "sessions_level.txt" if args.sessions and args.level else
                             "sessions_echo.txt" if args.sessions and args.echo else
                             "sessions_conceal.txt" if args.sessions and args.conceal else
+                            "sessions_denoise.txt" if args.sessions and args.denoise else
                             "sessions_dtmf.txt" if args.sessions and args.dtmf else
                             "sessions_channels.txt" if args.sessions and args.channels > 1 else
                             "sessions_pcm.txt" if args.sessions and args.sample_format == "s16" else
@@ -802,6 +814,143 @@ def sessions_conceal_section():
         sys.exit(1)
 
 
+def sessions_denoise_section():
+    """S staggered sessions with a noise suppressor against the same sessions in a pool without the option and, for scale, in a pool
+    with an input leveller (the comparable one-workgroup-per-slot launch); the same audio, the same pushes.  The suppressor changes
+    what the encoder sees, so its ids are held to the host rule: encode() of denoise.scan of each session's clip; then the launches
+    per step of the pools, and the suppressor's launch alone -- S slots, one push each -- timed with events"""
+    import math
+    from dmel_codec_amd import _lib
+    from dmel_codec_amd.utils import denoise as denoise_rule
+    S, n = args.sessions, args.chunk
+    t = torch.arange((args.pushes + 5) * n, device=dev, dtype=torch.float64) / SR
+    tone = ((torch.sin(2 * math.pi * 770 * t) + torch.sin(2 * math.pi * 1336 * t)) * 0.1).float()
+    talk = ((torch.arange(t.shape[0], device=dev) // n) % 3 == 0).float()       # a burst in every third push
+    lv = torch.tensor([0.0025 * 2 ** (s % 4) for s in range(S)], device=dev)[:, None]      # noise floors of -52 .. -34 dBFS
+    audio = torch.randn(S, t.shape[0], device=dev) * lv + tone * talk
+    opts = {"plain": {}, "denoise": {"denoise": True}, "level": {"level": True}}
+    pools = {k: codec.encode_sessions(slots=S, max_push_samples=n, **o) for k, o in opts.items()}
+    slots = {k: [p.open(**opts[k]) for _ in range(S)] for k, p in pools.items()}
+    first = [n * (1 + s % 3) // 3 for s in range(S)]            # the starts differ by a third of a push
+    pos, ms, ids = [0] * S, {k: [] for k in pools}, {k: [[] for _ in range(S)] for k in ("plain", "denoise")}
+
+    def step(k, chunks):
+        out = pools[k].push({slots[k][s]: chunks[s] for s in range(S)})
+        return [out[slots[k][s]] for s in range(S)]
+
+    def chunks_of(size):
+        nonlocal pos
+        c = [audio[s, pos[s]:pos[s] + size[s]] for s in range(S)]
+        pos = [p + k for p, k in zip(pos, size)]
+        return c
+
+    order = list(pools)
+    for i in range(args.pushes):
+        chunks = chunks_of(first if i == 0 else [n] * S)
+        for k in order[i % 3:] + order[:i % 3]:                                       # none always goes first
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            got = step(k, chunks)
+            torch.cuda.synchronize()
+            if i >= args.warmup:
+                ms[k].append((time.perf_counter() - t0) * 1e3)
+            if k in ids:
+                for s in range(S):
+                    ids[k][s].append(got[s])
+    # the launches of a step, from the profile counters (their events cost time: counted behind the timed steps)
+    families, launches = ("denoise", "level", "voice", "dtmf", "small", "stft_logmel", "conv_igemm"), {}
+    counted = [chunks_of([n] * S) for _ in range(4)]
+    _lib.prof_enable(True)
+    for k in pools:
+        launches[k] = []
+        for chunks in counted:
+            _lib.prof_reset()
+            got = step(k, chunks)
+            torch.cuda.synchronize()
+            launches[k].append({f: _lib.prof_read(f)["launches"] for f in families})
+            if k in ids:
+                for s in range(S):
+                    ids[k][s].append(got[s])
+    _lib.prof_enable(False)
+    _lib.prof_reset()
+    reports = pools["denoise"].denoised()
+    for k, p in pools.items():
+        for s in range(S):
+            last = p.close(slots[k][s])
+            if k in ids:
+                ids[k][s].append(last)
+    # the ids: the plain pool's are encode()'s, the denoising pool's encode()'s of the host rule's output; the reports the host's
+    same, cfg = {"plain": True, "denoise": True}, denoise_rule.DenoiseConfig()
+    for s in range(S):
+        x = audio[s, :pos[s]]
+        y, state, _, _ = denoise_rule.scan(x.cpu(), cfg)
+        same["denoise"] = same["denoise"] and reports[slots["denoise"][s]] == denoise_rule.report(state, cfg.frame_samples, SR, cfg.learn_frames)
+        for k, clip in (("plain", x), ("denoise", y.to(dev))):
+            ref, lens = codec.encode(clip[None], torch.tensor([clip.shape[0]], device=dev))
+            same[k] = same[k] and torch.equal(torch.cat(ids[k][s], dim=1), ref[0, :, :int(lens[0])])
+
+    def one_more(opt):
+        return all(a[opt] == 0 and b[opt] == 1 and b["small"] == a["small"] + 1 and all(b[f] == a[f] for f in families if f not in (opt, "small"))
+                   for a, b in zip(launches["plain"], launches[opt]))
+    held = one_more("denoise") and one_more("level")
+    # the suppressor's launch alone: S slots that gain one push each, timed with events
+    rows_ = audio[:, :n].contiguous()
+    state = torch.zeros(S, denoise_rule.STATE_WORDS, dtype=torch.int32, device=dev)
+    pitch = denoise_rule.max_frames(n, cfg.frame_samples) + 1
+    o1, o2 = torch.zeros(S, pitch, device=dev), torch.zeros(S, pitch, device=dev)
+    tab = torch.empty(denoise_rule.TABLE_WORDS * S, dtype=torch.int32, device=dev)
+    transform = denoise_rule.transform_table().to(dev)
+    alone = []
+    for i in range(args.pushes):
+        a = i * n
+        rows_.copy_(audio[:, a:a + n])
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        denoise_rule.denoise_items(rows_, [0] * S, [n] * S, [cfg] * S, state, o1, o2, transform, table=tab)
+        ev1.record()
+        torch.cuda.synchronize()
+        if i >= args.warmup:
+            alone.append(ev0.elapsed_time(ev1))
+    att = sorted(rep.attenuation_db for rep in reports.values())
+    r = {"sessions": S, "chunk_s": n / SR, "pushes": args.pushes, "warmup": args.warmup, "ids_equal_encode": bool(same["plain"]),
+         "ids_and_reports_equal_host_rule": bool(same["denoise"]), "label": args.label,
+         "launches_per_step": {k: launches[k][0] for k in pools}, "one_more_launch_per_step": bool(held),
+         "attenuation_db": [round(att[0], 2), round(att[-1], 2)], "frames": sorted({rep.frames for rep in reports.values()}),
+         "frame_samples": cfg.frame_samples,
+         "denoise_launch_alone_ms": {"median": round(statistics.median(alone), 4), "p10": round(pct(alone, 0.1), 4),
+                                     "p90": round(pct(alone, 0.9), 4), "n": len(alone)}}
+    rows = []
+    for k, v in ms.items():
+        med = statistics.median(v)
+        r[k] = {"median_ms": round(med, 3), "p10_ms": round(pct(v, 0.1), 3), "p90_ms": round(pct(v, 0.9), 3), "n": len(v)}
+        rows.append(f"{S:8d}  {k:7s}  {med:9.3f}  {pct(v, 0.1):9.3f}  {pct(v, 0.9):9.3f}  {len(v):4d}  " +
+                    "  ".join(f"{f} {launches[k][0][f]}" for f in families))
+    r["added_median_ms"] = {k: round(r[k]["median_ms"] - r["plain"]["median_ms"], 3) for k in ("denoise", "level")}
+    rows.append(f"{S:8d}  the suppressor adds {r['added_median_ms']['denoise']:.3f} ms to the median step, the leveller (for scale) "
+                f"{r['added_median_ms']['level']:.3f} ms; each pool with an option launches exactly one kernel more per step than the plain one: {held}")
+    rows.append(f"{S:8d}  the suppressor's launch alone ({S} slots x {n} samples, frames of {cfg.frame_samples}: {n // cfg.hop} frames per slot; events "
+                f"around denoise_items, its table launch included): median {r['denoise_launch_alone_ms']['median']:.4f} ms, p10 "
+                f"{r['denoise_launch_alone_ms']['p10']:.4f}, p90 {r['denoise_launch_alone_ms']['p90']:.4f} over {len(alone)} launches")
+    rows.append(f"{S:8d}  ids of the plain pool equal encode(): {same['plain']}; ids and reports of the denoising pool equal encode() / report() "
+                f"of the host rule (denoise.scan of each clip): {same['denoise']}")
+    rows.append(f"{S:8d}  the sessions saw {r['frames']} frames each and attenuated their streams by {r['attenuation_db'][0]} .. "
+                f"{r['attenuation_db'][1]} dB, the tone bursts included (noise floors 6 dB apart, a tone burst in every third push)")
+    table = [(f"[{args.label}] " if args.label else "") + "encode sessions with a noise suppressor, 0.32 s pushes of 24 kHz audio, starts staggered by a "
+             f"third of a push, 80 mel / 8 groups / 70 channels / 20 layers (tools/bench_stream_encode.py --sessions {S} --denoise)",
+             f"wall time of one step (one push for every stream) incl. host synchronisation, {args.pushes - args.warmup} steady-state steps, the "
+             "three pools interleaved in one process;",
+             "plain = encode_sessions(S), denoise / level = encode_sessions(S, denoise=True / level=True) with every session opened with the "
+             "option; launches: records of the profile counters in one step",
+             "sessions  pool     median ms     p10 ms     p90 ms     n  launches of one step"] + rows
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "a") as f:
+        f.write("\n".join(table) + "\n\n")
+    print("\n".join(table), file=sys.stderr)
+    print(json.dumps(r))
+    if not (same["plain"] and same["denoise"] and held):
+        sys.exit(1)
+
+
 def sessions_resample_section():
     """S staggered sessions at their own rates: one pool that converts them in one launch against the codec-rate pool behind S
     StreamResampler(batch=1); the same audio, the same pushes, equal ids"""
@@ -1051,6 +1200,11 @@ if args.conceal and not args.sessions:
     ap.error("--conceal needs --sessions")
 if args.sessions and args.conceal:
     sessions_conceal_section()
+    sys.exit(0)
+if args.denoise and not args.sessions:
+    ap.error("--denoise needs --sessions")
+if args.sessions and args.denoise:
+    sessions_denoise_section()
     sys.exit(0)
 if args.sessions and (args.voice or args.dtmf):
     sessions_detector_section("voice" if args.voice else "dtmf")
