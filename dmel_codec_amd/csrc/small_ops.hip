@@ -3054,3 +3054,312 @@ extern "C" int dmel_tone_items(float* const* dst, const float* const* src, const
   DMEL_HIP(hipGetLastError());
   return DMEL_OK;
 }
+
+namespace dmel {
+
+// ---- reply shaping on codec-rate audio (include/dmel_hip.h: dmel_shape_items; the rule and the state row: utils/shape.py) --------------
+// Row s of the table is 64 4-byte words: dst (2), src (2), n_new, hold, flags (1: final, 2: limit), N, ceiling, release, rN, base,
+// segment count, three zeros, then eight segment records of five words (start relative to the first new sample, ramp, ramp_off, g0,
+// g1); workgroup s owns slot s.  The slot's LOCAL stream is its `hold` held samples of v (from its state row) followed by the n_new new
+// ones, v = z * c; local block j holds local positions [j N, (j + 1) N).  A pass takes PB + 1 consecutive blocks (PB = min(63,
+// 4096 / N), at most 5120 floats) through LDS and emits the first PB of them; the next pass begins at the block the last one kept, so
+// every block's successor is in the tile when it leaves.  Phases of a pass, a barrier between them: (a) the held samples from the row
+// and the new ones from src -- 16 bytes per lane on the aligned body, single words at the ends (src is any 4-byte offset), the
+// commanded gain by a walk over the slot's segments -- into the tile; (b) wave w reduces the peaks of blocks w, w + 4, ...; (c) thread 0
+// runs the s / n recursion over the blocks the pass completes, in block order, and leaves every block's start node in LDS; (d) ramp,
+// gain and clamp from the tile to dst on the 16-byte grid of dst (another buffer than src: the counts differ); (e) behind the last
+// pass the samples that did not leave go back to the row, and the rest of its hold is zeroed.  Without the limiter the same passes run
+// with every node 1.0f (v * 1.0f is v) and nothing held.  Every operation of the rule is rounded on its own (fp contract(off)).  Plain
+// stores, no atomics.
+constexpr int kShapeWords = 64, kShapeHeader = 16, kShapeMinBlock = 32, kShapeMaxBlock = 1024, kShapePassSamples = 4096;
+constexpr int kShapePassBlocks = 63, kShapeTile = kShapePassSamples + kShapeMaxBlock, kShapeMaxSegs = 8, kShapeSegWords = 5;
+constexpr int kShapeMaxRamp = 16384, kShapeSegBase = 16, kShapeFparams = 5;
+__device__ __forceinline__ float shape_gain(const uint32_t* seg, int nseg, float base, const float* __restrict__ ramps, int i) {
+#pragma clang fp contract(off)
+  int k = -1;
+  for (int q = 0; q < nseg; ++q)
+    if ((int)seg[q * kShapeSegWords] <= i) k = q;         // starts do not decrease: the last one at or in front of i
+  if (k < 0) return base;
+  const uint32_t* w = seg + k * kShapeSegWords;
+  const int at = i - (int)w[0], ramp = (int)w[1];
+  const float g1 = __uint_as_float(w[4]);
+  if (at >= ramp) return g1;
+  const float g0 = __uint_as_float(w[3]);
+  const float d = g1 - g0;
+  const float m = d * ramps[(int)w[2] + at];
+  return g0 + m;
+}
+__device__ __forceinline__ float shape_apply(float v, float na, float nb, int i, float rN, float ceiling, float& peak, int& clamped) {
+#pragma clang fp contract(off)
+  const float d = nb - na;
+  const float u = (float)(i + 1) * rN;
+  const float m = d * u;
+  const float gi = na + m;
+  float y = v * gi;
+  if (y > ceiling) { y = ceiling; ++clamped; }
+  else if (y < -ceiling) { y = -ceiling; ++clamped; }
+  peak = fmaxf(peak, fabsf(y));
+  return y;
+}
+__device__ __forceinline__ float shape_step(float s, float p, float ceiling, float release) {
+#pragma clang fp contract(off)
+  const float t = p > ceiling ? ceiling / p : 1.0f;
+  float u = 1.0f - s;
+  u = release * u;
+  const float r = s + u;
+  return t < r ? t : r;
+}
+__global__ __launch_bounds__(256) void shape_kernel(const uint32_t* __restrict__ tab, uint32_t* __restrict__ state, int64_t state_pitch,
+                                                    const float* __restrict__ ramps, float* __restrict__ out_peak,
+                                                    float* __restrict__ out_gain, int64_t out_pitch) {
+  __shared__ float tile[kShapeTile];
+  __shared__ float bpk[kShapePassBlocks + 1], bn[kShapePassBlocks + 2];
+  __shared__ uint32_t seg[kShapeMaxSegs * kShapeSegWords];
+  __shared__ float red_in[4], red_out[4], sh_c;
+  __shared__ int red_clamped[4], sh_leave;
+  const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint32_t* row = tab + (size_t)s * kShapeWords;
+  const int n_new = (int)row[4], flags = (int)row[6];
+  const bool final = flags & 1, limit = flags & 2;
+  if (n_new <= 0 && !final) return;                     // idle (uniform: in front of the first barrier)
+  float* dst = reinterpret_cast<float*>(((uint64_t)row[1] << 32) | row[0]);
+  const float* src = reinterpret_cast<const float*>(((uint64_t)row[3] << 32) | row[2]);
+  const int hold = (int)row[5], N = (int)row[7], nseg = (int)row[12];
+  const float ceiling = __uint_as_float(row[8]), release = __uint_as_float(row[9]), rN = __uint_as_float(row[10]);
+  const float base = __uint_as_float(row[11]);
+  if (tid < kShapeMaxSegs * kShapeSegWords) seg[tid] = row[kShapeSegBase + tid];
+  if (tid == 0) sh_c = 0.0f;
+  uint32_t* srow = state + (size_t)s * state_pitch;
+  float* held = reinterpret_cast<float*>(srow + kShapeHeader);
+  // the recursion's state: thread 0 alone advances it
+  const bool fresh = (int)srow[5] == 0;
+  float sl = fresh ? 1.0f : __uint_as_float(srow[0]), node = fresh ? 1.0f : __uint_as_float(srow[1]);
+  float s_min = fresh ? 1.0f : __uint_as_float(srow[8]), open_peak = 0.0f;
+  int blocks = (int)srow[4], limited = (int)srow[9], n_blk = 0;
+  float* opk = out_peak + (int64_t)s * out_pitch;
+  float* ogn = out_gain + (int64_t)s * out_pitch;
+  const int M = hold + n_new;                           // the local stream
+  const int nb_all = (M + N - 1) / N, PB = min(kShapePassBlocks, kShapePassSamples / N), ov = limit ? 1 : 0;
+  float my_in = 0.0f, my_out = 0.0f;
+  int my_clamped = 0, n_out = 0, n_hold = 0;
+  __syncthreads();                                      // seg, sh_c
+  for (int b0 = 0; b0 < nb_all; b0 += PB) {
+    const bool last = b0 + PB + ov >= nb_all;
+    const int nt = min(PB + ov, nb_all - b0);           // blocks in the tile
+    const int T0 = b0 * N, hiq = min(nt * N, M - T0);   // tile[q] is local position T0 + q; q in [0, hiq) exists
+    // (a) the held samples, then the new ones as v = z * c
+    const int nh = max(0, min(hiq, hold - T0));
+    for (int q = tid; q < nh; q += 256) tile[q] = held[T0 + q];
+    {
+      const int i0 = T0 + nh - hold, cnt = hiq - nh;    // new samples [i0, i0 + cnt) of the launch go to tile[nh ...]
+      const float* g = src + i0;
+      float* t = tile + nh;
+      const int head = min(cnt, (int)((4u - (unsigned)(((uintptr_t)g >> 2) & 3u)) & 3u));
+      const int nv = (cnt - head) >> 2, tail0 = head + 4 * nv;
+      auto take = [&](int e, float z) {
+        const float c = shape_gain(seg, nseg, base, ramps, i0 + e);
+        my_in = fmaxf(my_in, fabsf(z));
+        if (i0 + e == n_new - 1) sh_c = c;
+        t[e] = z * c;
+      };
+      if (tid < head) take(tid, g[tid]);
+      for (int v = tid; v < nv; v += 256) {
+        const int e = head + 4 * v;
+        const float4 x = *reinterpret_cast<const float4*>(g + e);
+        take(e, x.x); take(e + 1, x.y); take(e + 2, x.z); take(e + 3, x.w);
+      }
+      if (tid < cnt - tail0) take(tail0 + tid, g[tail0 + tid]);
+    }
+    __syncthreads();
+    if (limit) {
+      // (b) the peak of every block of the tile
+      for (int j = wave; j < nt; j += 4) {              // wave-uniform
+        const int a = j * N, z = min(hiq, (j + 1) * N);
+        float m = 0.0f;
+        for (int q = a + lane; q < z; q += 64) m = fmaxf(m, fabsf(tile[q]));
+        for (int o = 32; o; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+        if (lane == 0) bpk[j] = m;
+      }
+      __syncthreads();
+      // (c) the recursion, in block order
+      if (tid == 0) {
+        int nc = 0;                                     // blocks of the tile whose start node is known: a prefix
+        for (int j = 0; j < nt; ++j) {
+          if (j == 0 && (b0 > 0 || hold >= N)) {        // completed by an earlier pass or an earlier launch
+            bn[0] = node;
+            nc = 1;
+            continue;
+          }
+          const float p = bpk[j];
+          if (min(hiq, (j + 1) * N) - j * N < N && !final) { open_peak = p; break; }          // the block the launch leaves open
+          const float sb = shape_step(sl, p, ceiling, release);
+          bn[j] = sl < sb ? sl : sb;
+          sl = sb;
+          s_min = s_min < sb ? s_min : sb;
+          limited += p > ceiling ? 1 : 0;
+          blocks += 1;
+          opk[n_blk] = p; ogn[n_blk] = sb;
+          ++n_blk;
+          nc = j + 1;
+        }
+        int leave;
+        if (last && final) { bn[nc] = sl; leave = nc; }
+        else leave = max(0, nc - 1);
+        if (!last) node = bn[PB];
+        else node = leave < nc ? bn[nc - 1] : sl;
+        sh_leave = leave;
+      }
+      __syncthreads();
+    }
+    // (d) ramp, gain and clamp, from the tile to dst on its own 16-byte grid
+    const int leave = limit ? sh_leave : nt;
+    const int hi = min(leave * N, hiq);
+    {
+      float* g = dst + T0;
+      const int head = min(hi, (int)((4u - (unsigned)(((uintptr_t)g >> 2) & 3u)) & 3u));
+      const int nv = (hi - head) >> 2, tail0 = head + 4 * nv;
+      auto one = [&](int q) {
+        const int j = q / N;
+        return shape_apply(tile[q], limit ? bn[j] : 1.0f, limit ? bn[j + 1] : 1.0f, q - j * N, rN, ceiling, my_out, my_clamped);
+      };
+      if (tid < head) g[tid] = one(tid);
+      for (int v = tid; v < nv; v += 256) {
+        const int q = head + 4 * v;
+        const float y0 = one(q), y1 = one(q + 1), y2 = one(q + 2), y3 = one(q + 3);
+        *reinterpret_cast<float4*>(g + q) = make_float4(y0, y1, y2, y3);
+      }
+      if (tid < hi - tail0) g[tail0 + tid] = one(tail0 + tid);
+    }
+    if (last) {
+      n_out = T0 + hi;
+      n_hold = hiq - hi;
+      // (e) what did not leave goes back to the row
+      if (limit) {
+        for (int q = tid; q < n_hold; q += 256) held[q] = tile[hi + q];
+      }
+    }
+    __syncthreads();                                    // the next pass overwrites the tile and the nodes
+    if (last) break;                                    // uniform: the pass that held every block to the end of the stream
+  }
+  if (limit)
+    for (int q = n_hold + tid; q < 2 * N - 1; q += 256) held[q] = 0.0f;
+  for (int o = 32; o; o >>= 1) {
+    my_in = fmaxf(my_in, __shfl_xor(my_in, o));
+    my_out = fmaxf(my_out, __shfl_xor(my_out, o));
+    my_clamped += __shfl_xor(my_clamped, o);
+  }
+  if (lane == 0) { red_in[wave] = my_in; red_out[wave] = my_out; red_clamped[wave] = my_clamped; }
+  __syncthreads();
+  if (tid == 0) {
+    const float pin = fmaxf(fmaxf(red_in[0], red_in[1]), fmaxf(red_in[2], red_in[3]));
+    const float pout = fmaxf(fmaxf(red_out[0], red_out[1]), fmaxf(red_out[2], red_out[3]));
+    const int cl = red_clamped[0] + red_clamped[1] + red_clamped[2] + red_clamped[3];
+    srow[0] = __float_as_uint(sl); srow[1] = __float_as_uint(node); srow[2] = __float_as_uint(open_peak);
+    srow[3] = (uint32_t)n_hold; srow[4] = (uint32_t)blocks; srow[5] = (uint32_t)((int)srow[5] + n_new);
+    srow[6] = (uint32_t)((int)srow[6] + n_out);
+    if (n_new > 0) srow[7] = __float_as_uint(sh_c);
+    srow[8] = __float_as_uint(s_min); srow[9] = (uint32_t)limited; srow[10] = (uint32_t)((int)srow[10] + cl);
+    srow[11] = __float_as_uint(fmaxf(__uint_as_float(srow[11]), pin));
+    srow[12] = __float_as_uint(fmaxf(__uint_as_float(srow[12]), pout));
+  }
+}
+
+}  // namespace dmel
+
+extern "C" int dmel_shape_items(float* const* dst, const int64_t* dst_cap, const float* const* src, const int64_t* n_new,
+                                const int64_t* hold, const int32_t* flags, const int32_t* N, const float* fparams,
+                                const int32_t* seg_count, const int32_t* segs, int S, const float* ramps, int64_t ramp_floats, void* state,
+                                int64_t state_pitch, float* out_peak, float* out_gain, int64_t out_pitch, void* table_scratch,
+                                void* stream) {
+  using namespace dmel;
+  DMEL_CHECK_ARG(dst && dst_cap && src && n_new && hold && flags && N && fparams && seg_count && segs && state && out_peak && out_gain &&
+                     table_scratch,
+                 "shape_items: NULL argument");
+  DMEL_CHECK_ARG(S >= 1 && S <= 65535, "shape_items: %d items, expected 1 .. 65535", S);
+  DMEL_CHECK_ARG(ramp_floats >= 0 && (ramps || ramp_floats == 0), "shape_items: a ramp arena of %lld floats (NULL: %d)",
+                 (long long)ramp_floats, (int)!ramps);
+  DMEL_CHECK_ARG((((uintptr_t)state | (uintptr_t)out_peak | (uintptr_t)out_gain | (uintptr_t)ramps) & 3) == 0,
+                 "shape_items: state, out_peak, out_gain or ramps is not 4-byte aligned");
+  DMEL_CHECK_ARG(((uintptr_t)table_scratch & 7) == 0, "shape_items: table_scratch is not 8-byte aligned");
+  DMEL_CHECK_ARG(state_pitch >= kShapeHeader && out_pitch >= 0, "shape_items: a state pitch of %lld words (at least %d) or a negative "
+                 "output pitch %lld", (long long)state_pitch, kShapeHeader, (long long)out_pitch);
+  static const char* const kNames[kShapeFparams] = {"ceiling", "release", "rN", "base gain", "max_gain"};
+  std::vector<uint32_t> tab((size_t)kShapeWords * S, 0u);
+  int64_t live = 0;
+  double bytes = 0.0;
+  for (int s = 0; s < S; ++s) {
+    const int64_t n = n_new[s];
+    DMEL_CHECK_ARG(n >= 0 && n <= 0x3fffffff, "shape_items: item %d: %lld new samples, expected 0 .. 2^30 - 1", s, (long long)n);
+    DMEL_CHECK_ARG(flags[s] >= 0 && flags[s] <= 3, "shape_items: item %d: flags %d, expected 0 .. 3 (1: final, 2: limit)", s, flags[s]);
+    const bool fin = flags[s] & 1, lim = flags[s] & 2;
+    if (n == 0 && !fin) continue;                       // idle: its parameters are not looked at (the table row stays 0)
+    int32_t nb = N[s];
+    int64_t leave = n, done = 0;
+    if (lim) {
+      DMEL_CHECK_ARG(nb >= kShapeMinBlock && nb <= kShapeMaxBlock, "shape_items: item %d: a block of %d samples, expected %d .. %d", s, nb,
+                     kShapeMinBlock, kShapeMaxBlock);
+      DMEL_CHECK_ARG(hold[s] >= 0 && hold[s] <= 2 * (int64_t)nb - 1, "shape_items: item %d: %lld held samples, expected 0 .. 2 N - 1 = %d", s,
+                     (long long)hold[s], 2 * nb - 1);
+      DMEL_CHECK_ARG(state_pitch >= kShapeHeader + 2 * (int64_t)nb - 1, "shape_items: item %d: a state row of %lld words, a block of %d "
+                     "needs %d", s, (long long)state_pitch, nb, kShapeHeader + 2 * nb - 1);
+      const int64_t total = hold[s] + n;
+      leave = fin ? total : std::max<int64_t>(0, total / nb - 1) * nb;
+      done = total / nb + (fin && total % nb ? 1 : 0) - (hold[s] >= nb ? 1 : 0);
+      DMEL_CHECK_ARG(out_pitch >= done, "shape_items: item %d: the step completes %lld blocks, which exceed the output pitch %lld", s,
+                     (long long)done, (long long)out_pitch);
+    } else {
+      DMEL_CHECK_ARG(hold[s] == 0, "shape_items: item %d: %lld held samples without the limiter", s, (long long)hold[s]);
+      nb = kShapeMaxBlock;                              // the tile's grid; no block of the rule
+    }
+    DMEL_CHECK_ARG(dst_cap[s] >= leave, "shape_items: item %d: the step hands out %lld samples, its destination takes %lld", s,
+                   (long long)leave, (long long)dst_cap[s]);
+    DMEL_CHECK_ARG((dst[s] || leave == 0) && (src[s] || n == 0), "shape_items: item %d: NULL %s", s, src[s] || n == 0 ? "destination" : "source");
+    DMEL_CHECK_ARG((((uintptr_t)dst[s] | (uintptr_t)src[s]) & 3) == 0, "shape_items: item %d: a pointer is not 4-byte aligned", s);
+    const float* fp = fparams + (size_t)kShapeFparams * s;
+    for (int k = 0; k < kShapeFparams; ++k)             // the base gain alone may be 0
+      DMEL_CHECK_ARG(std::isfinite(fp[k]) && (fp[k] > 0.0f || (k == 3 && fp[k] == 0.0f)),
+                     "shape_items: item %d: float parameter %d (%s) is not finite and positive", s, k, kNames[k]);
+    DMEL_CHECK_ARG(fp[1] <= 1.0f && fp[2] <= 1.0f, "shape_items: item %d: release %g or rN %g above 1", s, (double)fp[1], (double)fp[2]);
+    DMEL_CHECK_ARG(fp[3] <= fp[4], "shape_items: item %d: base gain %g above max_gain %g", s, (double)fp[3], (double)fp[4]);
+    const int32_t count = seg_count[s];
+    DMEL_CHECK_ARG(count >= 0 && count <= kShapeMaxSegs, "shape_items: item %d: %d live segments, expected 0 .. %d", s, count, kShapeMaxSegs);
+    uint32_t* it = tab.data() + (size_t)kShapeWords * s;
+    int32_t before = INT32_MIN;
+    for (int k = 0; k < count; ++k) {
+      const int32_t* w = segs + ((size_t)kShapeMaxSegs * s + k) * kShapeSegWords;
+      float g[2];
+      std::memcpy(g, w + 3, sizeof g);
+      DMEL_CHECK_ARG(w[0] >= -(1 << 30) && w[0] <= (1 << 30) && w[0] >= before,
+                     "shape_items: item %d: segment %d: start %d, expected -2^30 .. 2^30 and no decrease", s, k, w[0]);
+      DMEL_CHECK_ARG(w[1] >= 0 && w[1] <= kShapeMaxRamp, "shape_items: item %d: segment %d: ramp = %d, expected 0 .. %d", s, k, w[1],
+                     kShapeMaxRamp);
+      DMEL_CHECK_ARG(w[1] == 0 || (w[2] >= 0 && (int64_t)w[2] + w[1] <= ramp_floats),
+                     "shape_items: item %d: segment %d: ramp table [%d, %d + %d) lies beyond the arena of %lld floats", s, k, w[2], w[2],
+                     w[1], (long long)ramp_floats);
+      for (int j = 0; j < 2; ++j)
+        DMEL_CHECK_ARG(std::isfinite(g[j]) && g[j] >= 0.0f && g[j] <= fp[4],
+                       "shape_items: item %d: segment %d: g%d = %g, expected a finite gain in [0, max_gain = %g]", s, k, j, (double)g[j],
+                       (double)fp[4]);
+      before = w[0];
+      std::memcpy(it + kShapeSegBase + (size_t)kShapeSegWords * k, w, kShapeSegWords * sizeof(int32_t));
+    }
+    const uint64_t d = (uint64_t)(uintptr_t)dst[s], x = (uint64_t)(uintptr_t)src[s];
+    it[0] = (uint32_t)d; it[1] = (uint32_t)(d >> 32); it[2] = (uint32_t)x; it[3] = (uint32_t)(x >> 32);
+    it[4] = (uint32_t)n; it[5] = (uint32_t)hold[s]; it[6] = (uint32_t)flags[s]; it[7] = (uint32_t)nb;
+    std::memcpy(it + 8, fp, 4 * sizeof(float));
+    it[12] = (uint32_t)count;
+    ++live;
+    bytes += 4.0 * (double)n + 4.0 * (double)leave + 8.0 * (double)done + 8.0 * kShapeHeader + (lim ? 8.0 * (2.0 * nb - 1.0) : 0.0);
+  }
+  if (live == 0) return DMEL_OK;                        // every item idle
+  hipStream_t st = (hipStream_t)stream;
+  DMEL_TRY(launch_table_put(tab.data(), tab.size() * sizeof(uint32_t), table_scratch, st));
+  {
+    // "small" carries the time and the bytes; the second scope only counts: one record per shape launch (dmel_prof_read("shape"))
+    ProfScope ps("small", st, 0.0, bytes), count("shape", st, 0.0, 0.0);
+    hipLaunchKernelGGL(shape_kernel, dim3((unsigned)S), dim3(256), 0, st, static_cast<const uint32_t*>(table_scratch),
+                       static_cast<uint32_t*>(state), state_pitch, ramps, out_peak, out_gain, out_pitch);
+  }
+  DMEL_HIP(hipGetLastError());
+  return DMEL_OK;
+}

@@ -521,7 +521,10 @@ class VQGAN(nn.Module):
         pool.set_lookahead(slot, k) moves a live reply's look-ahead.  tones=True (max_tone_samples=: two seconds at the vocoder's
         rate by default): pool.send_dtmf(slot, "42#") and pool.send_tones(slot, program) queue DTMF keys, beeps or call-progress
         tones (utils/tones.py) at a mel frame of a reply; the step in which its speech reaches that frame splices them in for all
-        slots with one launch, in front of the reply's resampler and wire convert.
+        slots with one launch, in front of the reply's resampler and wire convert.  shape=True: pool.open(shape=True | ShapeConfig)
+        starts a reply whose audio passes a commanded gain and a block look-ahead limiter (utils/shape.py), one launch per step for
+        all slots; pool.set_gain(slot, gain_db, ramp_ms) ducks, levels or mutes it, pool.stop(slot, fade_ms) ends it on barge-in with
+        a fade instead of a click.
         See models/stream_sessions.py: DecodeSessions."""
         from .stream_sessions import DecodeSessions
         return DecodeSessions(self, slots, max_push_tokens, return_audios, **options)

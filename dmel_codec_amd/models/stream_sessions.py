@@ -25,6 +25,7 @@ from ..utils import dtmf as dtmf_rule
 from ..utils import echo as echo_rule
 from ..utils import denoise as denoise_rule
 from ..utils import level as level_rule
+from ..utils import shape as shape_rule
 from ..utils import tones as tone_rule
 from ..utils import voice as voice_rule
 from .stream_park import ParkingPool, plain
@@ -1339,6 +1340,22 @@ class DecodeSessions(ParkingPool):
     cap * up + max_tone_samples.  Not served: RFC 4733 telephone-events, tones mixed over speech, non-integer frequencies, tones in
     the mel; no ITU-T Q.23 / Q.24 conformance is claimed.
 
+    How loud a reply is and how it ends: a pool built with shape=True (and audio) serves sessions opened with shape=True or a
+    ShapeConfig (utils/shape.py: the rule, its defaults and its caveats).  set_gain(slot, gain_db, ramp_ms, at_sample) moves the
+    session's commanded gain along a raised cosine from a sample of z -- its float stream at the vocoder's rate behind the tone
+    splice -- on (ducking, output level, float("-inf") for mute); a block look-ahead limiter keeps |y| <= ceiling, for which the
+    audio runs N .. 2 N - 1 samples behind the mel; stop(slot, fade_ms) ends a reply on barge-in: close() behind a fade to 0 and the
+    end E of it, the hold and the resampler flushed at the true length (a stop of an exact session still computes its whole
+    flush).  ONE dmel_shape_items launch per step, between the tone launch and the resampler, serves all shaping slots with a new
+    piece or their end.  A shaping session's audio is, bit for bit, its wire chain (resample, format, channels) applied to
+    shape.scan(tones.splice(its codec-rate stream, inserts), requests, config, end), however the tokens were cut into pushes; mel
+    pieces and frames_emitted do not change; a session opened without shape= and a pool built without shape=True are what they
+    were, and such a pool refuses open(shape=), set_gain, stop, shaped and the snapshot of a shaping session.  shaped() ->
+    {slot: ShapeReport} (one copy of the headers); shape_blocks(slot): per-block (peak, gain) of the last push; samples_fed(slot):
+    "now" of set_gain.  The state travels with snapshot / restore (meta keys shape, shape_segments, shape_base, shape_fed, shape_hold,
+    shape_end; a snapshot without them restores as a session without the option); drop discards it.  The resampler's rows of such
+    a pool hold 2 * 1024 - 1 samples more: what a limiter hands out late.
+
     Out of scope, NotImplementedError: overlap_vocoder, graph_chunk_tokens, and a pool-wide output_sample_rate (a pool has no rate of
     its own).
 
@@ -1350,7 +1367,7 @@ class DecodeSessions(ParkingPool):
     def __init__(self, codec, slots: int, max_push_tokens: int = 64, return_audios: bool = True, overlap_vocoder: bool = False,
                  graph_chunk_tokens: Optional[int] = None, output_sample_rate: Optional[int] = None,
                  output_sample_rates: Iterable[int] = (), early_emit: bool = False, crossfade_samples: int = 0, tones: bool = False,
-                 max_tone_samples: Optional[int] = None):
+                 max_tone_samples: Optional[int] = None, shape: bool = False):
         if overlap_vocoder or graph_chunk_tokens is not None or output_sample_rate is not None:
             raise NotImplementedError("decode sessions launch everything on the current stream, eagerly, and have no rate of their own: "
                                       "overlap_vocoder, graph_chunk_tokens and output_sample_rate belong to StreamingDecoder (a session's "
@@ -1406,9 +1423,26 @@ class DecodeSessions(ParkingPool):
                 raise ValueError(f"max_tone_samples must be a positive integer (samples at the vocoder's rate), got {max_tone_samples!r}")
         elif max_tone_samples is not None:
             raise ValueError("max_tone_samples on a pool built without tones=True")
-        # a step emits frames that all lie in the slot's `cap` columns: at most cap * up samples, and the tones that waited, reach a
-        # slot's resampler at once
-        self._init_slots(self.voc_rate, "output_sample_rates", self.cap * self.up + self.max_tone)
+        # the pool shapes replies (open(shape=), set_gain, stop): a limiter holds back at most 2 N - 1 samples, which leave with a later step
+        if not isinstance(shape, bool):
+            raise ValueError(f"shape must be a bool, got {shape!r}")
+        if shape and not return_audios:
+            raise ValueError("shape without audio: return_audios=False leaves nothing to shape")
+        self.shape_on = shape
+        self.shape_room = 2 * shape_rule.MAX_BLOCK - 1 if shape else 0
+        # a step emits frames that all lie in the slot's `cap` columns: at most cap * up samples, the tones that waited, and what a
+        # limiter held back, reach a slot's resampler at once
+        self._init_slots(self.voc_rate, "output_sample_rates", self.cap * self.up + self.max_tone + self.shape_room)
+        self.scfg: List[Optional[shape_rule.ShapeConfig]] = [None] * self.S
+        self.sreq: List[list] = [[] for _ in range(self.S)]   # the slot's live gain segments (P, g0, g1, ramp), over the base gain sbase
+        self.sbase = [1.0] * self.S
+        self.sfed = [0] * self.S                          # samples of z the slot's shaper has taken
+        self.shold = [0] * self.S                         # samples its limiter holds (the row's `hold`, tracked from the rule's integers)
+        self.send: List[Optional[int]] = [None] * self.S  # the end sample E of a stopped session
+        self._shape_n = [0] * self.S                      # blocks the slot's last push completed
+        self._shape_src: Dict[int, torch.Tensor] = {}     # the float pieces of the step the shaper reads
+        self._sramp_off: Dict[int, int] = {}              # gain ramp length -> offset of its table in the pool's shape arena
+        self._sramp_floats = 0
         self.tq: List[list] = [[] for _ in range(self.S)]     # the slot's pending requests, (P, program) in the order they leave
         self.handed = [0] * self.S                        # speech samples at the vocoder's rate the slot has handed out
         self.tone_samples = [0] * self.S                  # samples its pending requests render to
@@ -1426,15 +1460,22 @@ class DecodeSessions(ParkingPool):
         return self.sched[slot].emitted
 
     def open(self, output_sample_rate: Optional[int] = None, sample_format: str = "f32", channels: int = 1,
-             lookahead_frames: Optional[int] = None, crossfade_samples: int = 0) -> int:
+             lookahead_frames: Optional[int] = None, crossfade_samples: int = 0, shape=None) -> int:
         """take a free slot: fresh schedule, state zeroed before its first push.  output_sample_rate: the rate this session's audio
         leaves at, one of the declared `output_sample_rates` (None: the vocoder's).  sample_format: "f32", "s16" for audio returned
         as torch.int16 (16-bit signed PCM), or "ulaw" / "alaw" for torch.uint8 (G.711 codes).  channels: 1 .. 8; above 1 the audio
         comes back as interleaved frames (n, channels), every channel the mono audio.  lookahead_frames: None for the exact session;
         k >= 0 (mel frames) for a session that emits every frame at most k behind the newest one received, on a pool built with
         early_emit=True.  crossfade_samples: F >= 1 samples (at most the pool's crossfade_samples and one mel frame) over which
-        such a session blends every piece into the next (utils/crossfade.py); its audio runs F samples behind its mel.  Raises when
-        every slot is taken; a refused open takes no slot."""
+        such a session blends every piece into the next (utils/crossfade.py); its audio runs F samples behind its mel.  shape: True
+        or a ShapeConfig (utils/shape.py) for a session whose audio passes the commanded gain and the limiter, on a pool built with
+        shape=True: set_gain and stop serve it, and its audio runs N .. 2 N - 1 samples behind with the limiter.  Raises when every
+        slot is taken; a refused open takes no slot."""
+        scfg = shape_rule.as_config(shape)
+        if scfg is not None:
+            if not self.shape_on:
+                raise ValueError("shape on a pool built without shape=True: it has no rows to hold a reply back in")
+            scfg.block(self.voc_rate)
         if isinstance(crossfade_samples, bool) or not isinstance(crossfade_samples, int) or crossfade_samples < 0:
             raise ValueError(f"crossfade_samples must be an integer >= 0 (samples), got {crossfade_samples!r}")
         if crossfade_samples:
@@ -1461,7 +1502,102 @@ class DecodeSessions(ParkingPool):
         self.tok_origin[s] = self.n_noise[s] = 0
         self.fade[s], self.has_tail[s] = crossfade_samples, False
         self.tq[s], self.handed[s], self.tone_samples[s] = [], 0, 0
+        self._shape_adopt(s, scfg)
         return s
+
+    # -- shaping: output gain, ducking, a limiter and a clean stop (utils/shape.py) ---------------------------------------------
+    def _shape_adopt(self, s: int, cfg, segments=(), base=None, fed: int = 0, hold: int = 0, end=None) -> None:
+        self.scfg[s], self.sreq[s], self.sbase[s] = cfg, [tuple(sg) for sg in segments], cfg.initial_gain if cfg and base is None else base or 0.0
+        self.sfed[s], self.shold[s], self.send[s], self._shape_n[s] = fed, hold, end, 0
+
+    def _shaping(self, slot: int, what: str) -> shape_rule.ShapeConfig:
+        if not self.shape_on:
+            raise ValueError(f"{what} on a pool built without shape=True: it has no rows to hold a reply back in")
+        self._check_open(slot)
+        if self.scfg[slot] is None:
+            raise ValueError(f"{what}: slot {slot} was opened without shape=")
+        return self.scfg[slot]
+
+    def samples_fed(self, slot: int) -> int:
+        """samples of z -- the slot's stream at the vocoder's rate behind the tone splice -- its shaper has taken: "now" of set_gain"""
+        self._shaping(slot, "samples_fed")
+        return self.sfed[slot]
+
+    def _shape_request(self, slot: int, cfg, request, keep_future: bool = True) -> None:
+        now = self.sfed[slot]
+        segs, base = shape_rule.live(self.sreq[slot], self.sbase[slot], now)
+        if not keep_future:
+            segs = [sg for sg in segs if sg[0] <= now]
+        if len(segs) >= shape_rule.MAX_SEGMENTS:
+            raise ValueError(f"slot {slot}: {len(segs)} gain requests are live, a ninth is refused")
+        ramp = request[2]
+        if ramp and ramp not in self._sramp_off:
+            self._sramp_off[ramp], self._sramp_floats = self._sramp_floats, self._sramp_floats + ramp
+            if self.buf is not None:
+                self._upload_shape_ramps([ramp])
+        self.sreq[slot], self.sbase[slot] = segs + [shape_rule.extend(segs, base, request)], base
+
+    def _upload_shape_ramps(self, lengths) -> None:
+        arena = self.buf["shape_ramps"]
+        if arena.numel() < self._sramp_floats:         # grow: the tables keep their offsets
+            grown = torch.zeros(2 * self._sramp_floats, dtype=torch.float32, device=arena.device)
+            grown[:arena.numel()] = arena
+            self.buf["shape_ramps"] = arena = grown
+        for n in lengths:
+            arena[self._sramp_off[n]:self._sramp_off[n] + n] = torch.tensor(shape_rule.ramp_table(n))
+
+    def set_gain(self, slot: int, gain_db: float, ramp_ms: float = 20.0, at_sample: Optional[int] = None) -> int:
+        """move the slot's commanded gain to gain_db (float("-inf"): mute) over ramp_ms, from sample at_sample of z on -> that anchor.
+        at_sample=None is "now", samples_fed(slot); an explicit anchor lies at or beyond that and not before an earlier request's.
+        The request may interrupt a ramp that is under way (utils/shape.py).  No device call, apart from the upload of a ramp table
+        of a length the pool has not seen.  ValueError, nothing queued: a pool or a session without the option, a gain above the
+        config's max_gain, a ramp above 16384 samples, an anchor outside those bounds, a ninth live request."""
+        cfg = self._shaping(slot, "set_gain")
+        if isinstance(gain_db, bool) or not isinstance(gain_db, (int, float)) or gain_db != gain_db or gain_db == math.inf:
+            raise ValueError(f"gain_db must be a level in dB or float('-inf'), got {gain_db!r}")
+        gain = 0.0 if gain_db == -math.inf else 10.0 ** (gain_db / 20.0)
+        now = self.sfed[slot]
+        after = max([now] + [sg[0] for sg in self.sreq[slot]])
+        anchor = now if at_sample is None else at_sample
+        request = shape_rule.check_request((anchor, gain, tone_rule._samples(ramp_ms, self.voc_rate, "ramp_ms")), cfg, after)
+        self._shape_request(slot, cfg, request)
+        return request[0]
+
+    def stop(self, slot: int, fade_ms: float = 20.0):
+        """end a reply on barge-in: close(slot) behind a request (now, 0, ramp) and the end E = now + ramp -> (audio, mel) as close
+        returns them.  The audio is the session's remaining output up to E, faded, the limiter's hold and the resampler flushed at
+        the true length; the mel is the unchanged flush.  The slot is free afterwards; requests anchored behind now and tones behind
+        E are discarded.  A stop of an exact session still computes its whole flush: the cost is not optimised here."""
+        cfg = self._shaping(slot, "stop")
+        now = self.sfed[slot]
+        request = shape_rule.check_request((now, 0.0, tone_rule._samples(fade_ms, self.voc_rate, "fade_ms")), cfg, now)
+        self._shape_request(slot, cfg, request, keep_future=False)
+        self.send[slot] = now + request[2]
+        return self.close(slot)
+
+    def _shape_slots(self) -> List[int]:
+        return [s for s in self.open_slots if self.scfg[s] is not None]
+
+    def shaped(self) -> Dict[int, shape_rule.ShapeReport]:
+        """{slot: ShapeReport} of every open shaping session: ONE device-to-host copy of the rows' headers"""
+        if not self.shape_on:
+            raise ValueError("shaped on a pool built without shape=True")
+        slots = self._shape_slots()
+        live = [s for s in slots if not self._fresh[s]] if self.buf is not None else []
+        table = self.buf["shape"][:, :shape_rule.HEADER].cpu() if live else None
+        zero = torch.zeros(shape_rule.HEADER, dtype=torch.int32)
+        return {s: shape_rule.report(table[s] if s in live else zero, self.scfg[s].block(self.voc_rate), self.voc_rate,
+                                     self.scfg[s].initial_gain) for s in slots}
+
+    def shape_blocks(self, slot: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(peak, gain) of the blocks the slot's last push completed: device fp32 views (n,), valid until the slot's next push.
+        peak: max |v| of the block; gain: the limiter's s behind it"""
+        self._shaping(slot, "shape_blocks")
+        if self.buf is None or self._fresh[slot]:
+            empty = torch.empty(0, dtype=torch.float32, device=self._device())
+            return empty, empty.clone()
+        n = self._shape_n[slot]
+        return self.buf["shape_peak"][slot, :n], self.buf["shape_gain"][slot, :n]
 
     # -- tones: DTMF keys, beeps and call-progress tones spliced into a session's audio (utils/tones.py) -----------------------
     def send_dtmf(self, slot: int, keys: str, *, tone_ms=80, gap_ms=80, level_dbfs=-10.0, twist_db=2.0, ramp_ms=1.0,
@@ -1536,6 +1672,7 @@ class DecodeSessions(ParkingPool):
         """ParkingPool.drop; the slot's pending tone requests are discarded with it"""
         super().drop(slot)
         self.tq[slot], self.tone_samples[slot] = [], 0      # what the session had not sent is gone with it
+        self._shape_adopt(slot, None)
 
     def set_lookahead(self, slot: int, lookahead_frames: int) -> None:
         """the look-ahead of an open early session from its next push on.  What has left never comes back: raising it pauses the
@@ -1597,6 +1734,19 @@ class DecodeSessions(ParkingPool):
                             tone_stage=torch.empty(S, self.cap * self.up + self.max_tone, dtype=torch.float32, device=dev),
                             tone_tab=torch.empty(tone_rule.table_words(S * (2 * most + 2), S * most), dtype=torch.int64, device=dev))
             self._upload_ramps(list(self._ramp_off))
+        if self.shape_on:                             # dmel_shape_items: a state row per slot, the row the tone launch splices a shaping
+            #                                           slot's piece into, the row its route reads the shaped samples from, the
+            #                                           per-block outputs, the table and the arena of gain ramps
+            w = self.cap * self.up + self.max_tone
+            self.buf.update(shape=torch.zeros(S, shape_rule.HEADER + self.shape_room, dtype=torch.int32, device=dev),
+                            shape_out=torch.empty(S, w + self.shape_room, dtype=torch.float32, device=dev),
+                            shape_peak=torch.zeros(S, (w + self.shape_room) // shape_rule.MIN_BLOCK + 2, dtype=torch.float32, device=dev),
+                            shape_gain=torch.zeros(S, (w + self.shape_room) // shape_rule.MIN_BLOCK + 2, dtype=torch.float32, device=dev),
+                            shape_tab=torch.empty(shape_rule.TABLE_WORDS * S, dtype=torch.int32, device=dev),
+                            shape_ramps=torch.zeros(max(2 * self._sramp_floats, 4 * tone_rule.MAX_RAMP), dtype=torch.float32, device=dev))
+            if self.tones_on:
+                self.buf["shape_in"] = torch.empty(S, w, dtype=torch.float32, device=dev)
+            self._upload_shape_ramps(list(self._sramp_off))
 
     def _slot_views(self, s: int):
         b = self.buf
@@ -1626,7 +1776,41 @@ class DecodeSessions(ParkingPool):
                     n_noise=self.n_noise[s])
         if self.tones_on:                             # only a pool that sends tones writes the keys: the others' snapshots are unchanged
             meta.update(tones=[[P, plain(p)] for P, p in self.tq[s]], handed=self.handed[s], tone_samples=self.tone_samples[s])
+        if self.scfg[s] is not None:                  # only a shaping session carries the keys: the others' snapshots are unchanged
+            segs, base = shape_rule.live(self.sreq[s], self.sbase[s], self.sfed[s])
+            meta.update(shape=self.scfg[s].as_dict(), shape_segments=[list(sg) for sg in segs], shape_base=base, shape_fed=self.sfed[s],
+                        shape_hold=self.shold[s], shape_end=self.send[s])
         return meta
+
+    def _park_shape(self, meta: Mapping):
+        """(the shaping config a snapshot carries (None: none), its live segments, base gain, samples fed, samples held, end);
+        ValueError where they are none this pool can continue"""
+        if meta.get("shape") is None:
+            return None, [], None, 0, 0, None
+        if not self.shape_on:
+            raise ValueError("a shaping session into a pool built without shape=True")
+        try:
+            cfg = shape_rule.ShapeConfig.from_dict(meta["shape"])
+        except TypeError as e:
+            raise ValueError(f"the shape config of the snapshot is not a ShapeConfig: {e}") from None
+        N = cfg.block(self.voc_rate)
+        fed, hold, end, base, raw = (meta.get(k) for k in ("shape_fed", "shape_hold", "shape_end", "shape_base", "shape_segments"))
+        ints = all(isinstance(v, int) and not isinstance(v, bool) for v in (fed, hold) + (() if end is None else (end,)))
+        if not ints or fed < 0 or not 0 <= hold <= min(fed, 2 * N - 1 if cfg.limit else 0) or (end is not None and end < fed):
+            raise ValueError(f"the shaper's counts of the snapshot are no counts: fed {fed!r}, hold {hold!r}, end {end!r}")
+        if isinstance(base, bool) or not isinstance(base, (int, float)) or not 0 <= base <= cfg.max_gain:
+            raise ValueError(f"the shaper's base gain of the snapshot is no gain in [0, {cfg.max_gain}]: {base!r}")
+        segs, after = [], 0
+        ok = isinstance(raw, (list, tuple)) and len(raw) <= shape_rule.MAX_SEGMENTS and all(isinstance(q, (list, tuple)) and len(q) == 4
+                                                                                          for q in raw)
+        for q in raw if ok else ():
+            P, g1, ramp = shape_rule.check_request((q[0], q[2], q[3]), cfg, after)
+            shape_rule.check_request((P, q[1], ramp), cfg, after)
+            segs.append((P, float(q[1]), g1, ramp))
+            after = P
+        if not ok:
+            raise ValueError(f"the gain segments of the snapshot are no list of at most {shape_rule.MAX_SEGMENTS} (P, g0, g1, ramp): {raw!r}")
+        return cfg, segs, float(base), fed, hold, end
 
     def _park_tones(self, meta: Mapping) -> list:
         """the pending requests a snapshot carries as [(P, checked program)] (a snapshot without the key: none); ValueError where
@@ -1656,7 +1840,10 @@ class DecodeSessions(ParkingPool):
         return ([(f"hist.{l}", self.C, W) for l in range(self.L + 1)] +
                 [("skip", self.C, W), ("cond", meta["cond_channels"], W), ("mel", meta["n_mels"], W),
                  ("tokens", self.G, exact["tokens"] - meta["tok_origin"]), ("noise", self.C, meta["n_noise"]),
-                 ("fade_tail", 1, meta["fade"] if meta["has_tail"] else 0), ("resampler", 1, rs["fill"] if rs else 0)])
+                 ("fade_tail", 1, meta["fade"] if meta["has_tail"] else 0), ("resampler", 1, rs["fill"] if rs else 0)] +
+                # the shaper's row: header and hold; a session that has fed no sample owns the zeroed row: nothing
+                ([("shape", 1, shape_rule.ShapeConfig.from_dict(meta["shape"]).state_words(self.voc_rate) if meta["shape_fed"] > 0 else 0)]
+                 if meta.get("shape") is not None else []))
 
     def _park_rows(self, s: int) -> Dict[str, torch.Tensor]:
         b = self.buf
@@ -1667,6 +1854,8 @@ class DecodeSessions(ParkingPool):
             rows["fade_tail"] = b["fade_tail"][s:s + 1]
         if self.rs is not None and self.rs.buf is not None:
             rows["resampler"] = self.rs.buf["rows"][s:s + 1]
+        if self.shape_on:
+            rows["shape"] = b["shape"][s:s + 1]
         return rows
 
     def _park_widths(self):
@@ -1688,6 +1877,7 @@ class DecodeSessions(ParkingPool):
         if meta["lookahead"] is not None and sc.fade_frames != (1 if meta["fade"] else 0):
             raise ValueError("the schedule's fade_frames do not go with the session's cross-fade")
         self._park_tones(meta)
+        self._park_shape(meta)
         lo = meta["window"][0]
         if sc.tokens * f - lo + self.max_push * f > self.cap:
             raise ValueError(f"the frames [{lo}, {sc.tokens * f}) and one maximal push ({self.max_push * f} frames) do not fit the "
@@ -1707,11 +1897,20 @@ class DecodeSessions(ParkingPool):
         self.handed[s] = meta.get("handed", self.sched[s].emitted * self.up - (meta["fade"] if meta["has_tail"] else 0))
         for _, p in self.tq[s]:
             self._ramps_for(p)
+        cfg, segs, base, fed, hold, end = self._park_shape(meta)
+        self._shape_adopt(s, cfg, segs, base, fed, hold, end)
+        for sg in segs:
+            if sg[3] and sg[3] not in self._sramp_off:
+                self._sramp_off[sg[3]], self._sramp_floats = self._sramp_floats, self._sramp_floats + sg[3]
+                if self.buf is not None:
+                    self._upload_shape_ramps([sg[3]])
 
     def _prepare_slot(self, s: int) -> None:
         super()._prepare_slot(s)
         if self.fade[s]:                              # not state: rebuilt from F, for a fresh slot and for a restored one
             self.buf["fade_w"][s, :self.fade[s]] = crossfade.weights(self.fade[s]).to(self.buf["fade_w"].device)
+        if self.shape_on:
+            self.buf["shape"][s].zero_()              # the fresh shaper state
 
     # -- one step ----------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -1735,10 +1934,12 @@ class DecodeSessions(ParkingPool):
             # a slot with a look-ahead emits by its own rule, from its shadow row when that ran ahead of the committed one
             steps = {s: early.get(s, st) for s, st in steps.items()}
             row = {s: self.S + s if s in shadows else s for s in steps}
-            self._held, self._ending = {}, final
+            self._held, self._ending, self._shape_src = {}, final, {}
             out, pieces, wire = self._emit(steps, row, final, dev)
             self._flush_tails(steps, final, out, pieces, wire)
             placed = self.tones_on and self._tones(steps, final, out, pieces, wire, dev)
+            if self.shape_on:
+                self._shape(steps, final, out, pieces, wire, dev, placed)
             self._resample(steps, final, out, pieces, wire, dev, placed)
             self._to_wire(out, wire)
         self._release(final)
@@ -1846,6 +2047,9 @@ class DecodeSessions(ParkingPool):
             if self.tq[s] and (s in self._ending or self.tq[s][0][0] <= self.handed[s]):
                 self._held[s] = piece[0]
                 return
+        if self.scfg[s] is not None:                  # a shaping slot's piece is the shaper's source; its route takes what that emits
+            self._shape_src[s] = piece[0]
+            return
         if self._converts(s):
             pieces[s] = piece[0]
         elif self._wired(s):
@@ -1919,14 +2123,17 @@ class DecodeSessions(ParkingPool):
         for s, x in held.items():
             due = [q for q in self.tq[s] if s in final or q[0] <= self.handed[s]]
             plan[s] = (due, x.shape[0] + sum(tone_rule.length(p) for _, p in due))
-        placed = any(self._converts(s) for s in held)
+        routed = [s for s in held if self.scfg[s] is None]      # a shaping slot's splice goes to the shaper's staging row instead
+        placed = any(self._converts(s) for s in routed)
         if placed:
             behind = self.rs.destinations({s: plan[s][1] if s in plan else pieces[s].shape[0]
-                                           for s in list(pieces) + [s for s in held if self._converts(s)]})
+                                           for s in list(pieces) + [s for s in routed if self._converts(s)]})
         parts = []
         for s, x in held.items():
             (due, total), h0 = plan[s], self.handed[s] - x.shape[0]
-            if self._converts(s):
+            if self.scfg[s] is not None:
+                d = self._shape_src[s] = b["shape_in"][s, :total]
+            elif self._converts(s):
                 d = pieces[s] = behind[s]
             elif self._wired(s):
                 d = wire[s] = b["tone_stage"][s, :total]
@@ -1957,6 +2164,43 @@ class DecodeSessions(ParkingPool):
             del self.tq[s][:len(due)]
             self.tone_samples[s] -= total - x.shape[0]
         return placed
+
+    def _shape(self, steps, final, out, pieces, wire, dev, placed: bool) -> None:
+        """shape: ONE dmel_shape_items launch takes, for every shaping slot of the step with a new piece or its end, the piece (as the
+        vocoder or the tone launch left it) through commanded gain and limiter, and writes the samples that leave -- emitted() of
+        them, known from integers -- where the slot's route reads them: its row of a staging buffer (the resampler copies it, the
+        convert launch reads it; behind the resampler tail where the tone launch placed the step's chunks), or a fresh tensor that
+        is handed out.  A slot that ends without a new piece takes part: its hold is flushed."""
+        members = [s for s in steps if self.scfg[s] is not None and (s in final or (s in self._shape_src and self._shape_src[s].shape[0]))]
+        if not members:
+            return
+        b, S = self.buf, self.S
+        src, dst, cfgs, segs, base = [None] * S, [None] * S, [None] * S, [[] for _ in range(S)], [0.0] * S
+        pos, hold, fin, took = [0] * S, [0] * S, [False] * S, {}
+        for s in members:
+            cfg, x = self.scfg[s], self._shape_src.get(s)
+            n = 0 if x is None else x.shape[0]
+            if self.send[s] is not None:              # a stopped session: z is cut at E
+                n = max(0, min(n, self.send[s] - self.sfed[s]))
+            m = shape_rule.emitted(self.shold[s], n, cfg.block(self.voc_rate), s in final, cfg.limit)
+            if self._converts(s):
+                d = self.rs.destinations({s: m})[s] if placed else b["shape_out"][s, :m]
+                if m or s in final:
+                    pieces[s] = d
+            elif self._wired(s):
+                d = wire[s] = b["shape_out"][s, :m]
+            else:
+                d = torch.empty(1, m, dtype=torch.float32, device=dev)
+                out[s], d = (d, out[s][1]), d[0]
+            segs[s], base[s] = shape_rule.live(self.sreq[s], self.sbase[s], self.sfed[s])
+            src[s], dst[s], cfgs[s], pos[s], hold[s], fin[s], took[s] = x[:n] if n else None, d, cfg, self.sfed[s], self.shold[s], s in final, (n, m)
+        shape_rule.shape_items(src, dst, cfgs, segs, base, pos, hold, fin, b["shape"], b["shape_peak"], b["shape_gain"], self.voc_rate,
+                               ramps=b["shape_ramps"], ramp_off=self._sramp_off, table=b["shape_tab"])
+        for s, (n, m) in took.items():                # behind the launch: a refused launch changes no count
+            cfg = self.scfg[s]
+            self._shape_n[s] = shape_rule.completed(self.shold[s], n, cfg.block(self.voc_rate), s in final, cfg.limit)
+            self.sfed[s], self.shold[s] = self.sfed[s] + n, self.shold[s] + n - m
+            self.sreq[s], self.sbase[s] = shape_rule.live(segs[s], base[s], self.sfed[s])
 
     def _resample(self, steps, final, out, pieces, wire, dev, placed: bool = False) -> None:
         """the playback rates: each piece goes behind its slot's resampler tail, ONE launch converts all slots; a slot without a

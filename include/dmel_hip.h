@@ -713,6 +713,55 @@ int dmel_tone_items(float* const* dst, const float* const* src /*entries nullabl
                     const float* sine /* rate floats */, int rate, const float* ramps /*nullable when ramp_floats == 0*/,
                     int64_t ramp_floats, void* table_scratch, void* stream);
 
+/* Reply shaping on codec-rate audio, S session slots in ONE launch (csrc/small_ops.hip): a commanded gain that ramps between requests,
+ * a block look-ahead limiter and a flush at the end of the stream, for decode sessions opened with shape= (models/stream_sessions.py),
+ * whose rule, defaults and caveats are utils/shape.py -- the kernel equals shape.scan bit for bit.  Slot s takes n_new[s] new floats z
+ * at src[s] (any 4-byte offset) and writes the samples that leave to dst[s] (ANOTHER buffer than src[s]: the counts differ; any 4-byte
+ * offset).  flags[s]: bit 0 final (the session's last step: everything held leaves), bit 1 limit.  It carries one row of state_pitch
+ * 4-byte words in `state`: a header of 16 words -- fp32 0 s, 1 node, 2 open_peak; int32 3 hold, 4 blocks, 5 in, 6 out; fp32 7 c_now,
+ * 8 s_min; int32 9 limited, 10 clamped; fp32 11 peak_in, 12 peak_out; 13 .. 15 reserved and not written -- and, with the limiter,
+ * 2 N[s] - 1 floats: the held samples of v, oldest first, zeros behind them.  A zeroed row is a fresh session: while in == 0, s, node
+ * and s_min read as 1.0f whatever the row holds.
+ *   Commanded gain of new sample i (0-based in this launch): the last of the slot's seg_count[s] <= 8 segment records -- five 4-byte
+ * words at segs[(8 s + k) * 5]: start (int32, relative to the launch's first new sample, may be negative, non-decreasing in k), ramp
+ * (int32, 0 .. 16384), ramp_off (int32, offset of its table in `ramps`, not looked at where ramp == 0), g0, g1 (fp32 in
+ * [0, max_gain]) -- with start <= i; none: c = base.  at = i - start:  at < ramp: d = g1 - g0, m = d * ramps[ramp_off + at],
+ * c = g0 + m (separately rounded, no fma);  else c = g1.  A ramp table holds RAMP[k] = fp32(0.5 - 0.5 cos(pi (k + 0.5) / ramp)),
+ * computed by the caller in float64.  v = z * c.
+ *   Limiter: the local stream is the hold[s] held samples followed by the new v; blocks are N[s] samples.  hold[s] is the HOST's count
+ * of the samples the row holds (the caller tracks it from the rule's integers; the kernel trusts it and writes it back), 0 .. 2 N - 1;
+ * at hold >= N the first block is the whole one an earlier launch completed and its start node is word 1.  A completed block b, in
+ * block order, p = max |v| over it:
+ *     t = p > ceiling ? ceiling / p : 1.0f (IEEE division);  u = 1.0f - s;  u = release * u;  r = s + u;  s_b = min(t, r);
+ *     n_b = min(s, s_b);  s = s_b;  s_min = min(s_min, s_b);  limited += p > ceiling;  blocks += 1;
+ *     out_peak[s * out_pitch + j] = p, out_gain[s * out_pitch + j] = s_b for the j-th block the launch completed
+ * Block b leaves when block b + 1 is complete; sample i of it:
+ *     d = n_{b+1} - n_b;  u = (float)(i + 1) * rN;  m = d * u;  gi = n_b + m;  y = v * gi;
+ *     y > ceiling: y = ceiling, clamped += 1;  y < -ceiling: y = -ceiling, clamped += 1;  peak_out = max(peak_out, |y|)
+ * so a launch that is not final hands out max(0, (hold + n_new) / N - 1) * N samples.  A final launch completes the open block over the
+ * samples it has, sets the node behind the last block to s, and hands out hold + n_new samples.  Without the limiter y = clamp(v),
+ * n_new samples leave and hold[s] must be 0.  fparams row s is (ceiling, release, rN, base, max_gain), fp32 values computed by the
+ * caller.  n_new[s] == 0 without final is an idle slot: neither its rows nor its parameters are looked at; when every slot is idle
+ * the call returns DMEL_OK and launches nothing.  NaN and infinite input are outside the contract.  DMEL_EINVAL, nothing launched,
+ * dmel_last_error naming the item: S outside [1, 65535], a NULL table, a NULL ramps with ramp_floats > 0, state, out_peak, out_gain
+ * or ramps not 4-byte aligned, table_scratch not 8-byte aligned, state_pitch below 16 or a negative out_pitch, n_new[s] outside
+ * [0, 2^30), flags[s] outside [0, 3], N[s] outside [32, 1024] with the limiter, hold[s] outside [0, 2 N - 1] (not 0 without the
+ * limiter), state_pitch below 16 + 2 N - 1, out_pitch below the blocks the step completes, dst_cap[s] BELOW THE SAMPLES THE STEP
+ * HANDS OUT, a NULL dst where samples leave or src where n_new > 0, a dst or src that is not 4-byte aligned, a value of fparams that is
+ * not finite and positive (the base gain alone may be 0), release or rN above 1, base above max_gain, more than 8 segments, a start
+ * outside [-2^30, 2^30] or below the one before, a ramp outside [0, 16384] or a table beyond ramp_floats, a g0 or g1 that is not
+ * finite in [0, max_gain].  OVERLAP IS THE CALLER'S CONTRACT, as in dmel_tone_items.  The per-slot arguments are HOST tables, copied
+ * as launch arguments into table_scratch (64 S 4-byte words of device memory, 8-byte aligned): the caller may overwrite them as soon
+ * as the call returns.  One workgroup of four waves per slot; a pass takes min(63, 4096 / N) + 1 blocks through LDS and emits all
+ * but the last: gain and block peaks (wave reductions), the recursion on one lane, then ramp, gain, clamp and the store; the new
+ * hold goes back to the row behind the last pass.  Plain vector stores, no atomics.  One profile record per launch in the family
+ * "shape" (time and bytes in "small"). */
+int dmel_shape_items(float* const* dst /*entries nullable*/, const int64_t* dst_cap, const float* const* src /*entries nullable*/,
+                     const int64_t* n_new, const int64_t* hold, const int32_t* flags, const int32_t* N,
+                     const float* fparams /* S x 5 */, const int32_t* seg_count, const int32_t* segs /* S x 8 x 5 words */, int S,
+                     const float* ramps /*nullable when ramp_floats == 0*/, int64_t ramp_floats, void* state /* (S, state_pitch) words */,
+                     int64_t state_pitch, float* out_peak, float* out_gain, int64_t out_pitch, void* table_scratch, void* stream);
+
 /* R independent 2-D copies of 4-byte words in ONE launch (csrc/small_ops.hip): what takes the streaming state of live sessions out of
  * a pool's buffers into a snapshot and back (models/stream_sessions.py: snapshot / restore).  Descriptor r copies rows[r] rows of
  * cols[r] words: row i goes from src[r] + i * src_pitch[r] to dst[r] + i * dst_pitch[r], pitches in words.  Packing reads windows of

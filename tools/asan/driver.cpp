@@ -808,6 +808,54 @@ int main() {
       NN[0] = NN[1] = NN[2] = 0; DST[0] = nullptr; SC[1] = 0;          // every part idle: pointers and segments are not looked at
       CK(splice());
     }
+    {
+      // reply shaping: tables of exactly S entries, a segment table of exactly 8 * 5 S words, a table scratch of exactly 64 S words; its
+      // refusals read the host tables only.  The buffers are plain vectors: nothing here draws from the generator, so the weights of
+      // the fingerprinted handles below stay what they were
+      const int S0 = 3;
+      std::vector<float> out(2048, 0.f), in(2048, 0.25f), ramps(48, 0.5f), pk(S0 * 8), gn(S0 * 8);
+      std::vector<uint32_t> st((size_t)S0 * (16 + 127), 0u), tab(64 * S0);
+      float* DST[S0] = {out.data() + 1, nullptr, out.data() + 1001};
+      const float* SRC[S0] = {in.data() + 3, nullptr, in.data() + 1002};
+      int64_t CAP[S0] = {192, -1, 300}, NN[S0] = {200, 0, 300}, HD[S0] = {70, -9, 0};
+      int32_t FL[S0] = {2, 2, 1}, BL[S0] = {64, -5, 0}, SC[S0] = {2, 99, 0};       // the idle item's parameters are not looked at
+      float FP[S0 * 5] = {0.98f, 0.1f, 1.f / 64.f, 1.f, 4.f, 0, 0, 0, 0, 0, 0.98f, 0.1f, 1.f / 120.f, 0.5f, 4.f};
+      int32_t SEG[S0 * 8 * 5] = {0};
+      auto seg = [&](int s, int k, int start, int ramp, int off, float g0, float g1) {
+        int32_t* w = SEG + (8 * s + k) * 5;
+        w[0] = start; w[1] = ramp; w[2] = off;
+        std::memcpy(w + 3, &g0, sizeof(float)); std::memcpy(w + 4, &g1, sizeof(float));
+      };
+      seg(0, 0, -10, 48, 0, 1.f, 2.f); seg(0, 1, 100, 0, -3, 2.f, 0.f);
+      int S = S0;
+      int64_t ramp_floats = 48, pitch = 16 + 127, out_pitch = 8;
+      auto shape = [&]() { return dmel_shape_items(DST, CAP, SRC, NN, HD, FL, BL, FP, SC, SEG, S, ramps.data(), ramp_floats, st.data(), pitch,
+                                                   pk.data(), gn.data(), out_pitch, tab.data(), nullptr); };
+      CK(shape());
+      auto refused = [&](const char* item, const char* what) {
+        const int rc = shape();
+        if (rc != DMEL_EINVAL || !std::strstr(dmel_last_error(), item)) { std::printf("FAIL shape_items accepted %s (%d: %s)\n", what, rc, dmel_last_error()); ++failures; }
+      };
+      S = 0; refused("0 items", "no item");
+      S = S0; CAP[0] = 191; refused("item 0", "a destination shorter than what the step hands out");
+      CAP[0] = 192; HD[0] = 128; refused("item 0", "a hold of 2 N samples");
+      HD[0] = 70; BL[0] = 31; refused("item 0", "a block of 31 samples");
+      BL[0] = 64; pitch = 16 + 126; refused("item 0", "a state row shorter than header and hold");
+      pitch = 16 + 127; out_pitch = 2; refused("item 0", "an output pitch below the blocks the step completes");
+      out_pitch = 8; HD[2] = 1; refused("item 2", "held samples without the limiter");
+      HD[2] = 0; CAP[2] = 299; refused("item 2", "a destination shorter than the samples of a step without the limiter");
+      CAP[2] = 300; SRC[2] = nullptr; refused("item 2", "a NULL source");
+      SRC[2] = in.data() + 1002; FP[10] = 0.f; refused("item 2", "a ceiling of 0");
+      FP[10] = 0.98f; FP[13] = 4.5f; refused("item 2", "a base gain above max_gain");
+      FP[13] = 0.5f; SC[0] = 9; refused("item 0", "nine segments");
+      SC[0] = 2; seg(0, 1, -11, 0, 0, 2.f, 0.f); refused("item 0", "a start below the one before");
+      seg(0, 1, 100, 0, -3, 2.f, 0.f); seg(0, 0, -10, 49, 0, 1.f, 2.f); refused("item 0", "a ramp table that ends behind the arena");
+      seg(0, 0, -10, 48, 0, 1.f, NAN); refused("item 0", "a gain that is not a number");
+      seg(0, 0, -10, 48, 0, 1.f, 2.f);
+      CK(shape());
+      NN[0] = NN[2] = 0; FL[2] = 0;               // every item idle
+      CK(shape());
+    }
     auto xs = buf(2 * 8 * 3000), ys = buf(2 * 8 * 3000), da = buf(8), db = buf(8);
     CK(dmel_aa_snake_f32(xs.data(), ys.data(), al.data(), be.data(), taps.data(), taps.data(), 1, 2, 8, 3000, nullptr));
     CK(dmel_aa_snake_backward_f32(xs.data(), ys.data(), xs.data(), al.data(), be.data(), da.data(), db.data(), taps.data(), taps.data(), 1, 2, 8, 3000, nullptr));

@@ -74,7 +74,14 @@ the inverse (tools/bench_park.py): microseconds, bytes moved and GB/s of both, i
 
 runs only this: S replies in steady state (16-token pushes) in three pools interleaved in one process -- decode_sessions() without the
 option, decode_sessions(tones=True) with no request due, and the same with a three-key send_dtmf due in every slot in every step: the
-step time of each and the launch records of one step ("tones", "small", "pcm_convert"), APPENDED to --out."""
+step time of each and the launch records of one step ("tones", "small", "pcm_convert"), APPENDED to --out.
+
+    python tools/bench_stream.py --sessions 16 --shape [--output-sample-rate 8000] [--sample-format ulaw] [--steps 40] [--out profiles/sessions_shape.txt]
+
+runs only this: S replies in steady state (16-token pushes) in three pools interleaved in one process -- decode_sessions() without the
+option, decode_sessions(shape=True) with no shaping slot, and the same with every slot opened with shape=True at +6 dB: the step time
+of each, the launch records of one step ("shape", "small", "pcm_convert") and the time of the dmel_shape_items launch alone, APPENDED
+to --out."""
 import json, math, os, statistics, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -703,6 +710,105 @@ if "--tones" in sys.argv:
                            int(arg_after("--steps", "40")),
                            arg_after("--out", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                                            "sessions_tones.txt")))
+    sys.exit(0)
+
+def sessions_shape_section(S, rate, fmt, steps, out):
+    """three pools interleaved in one process: decode_sessions() as it was, decode_sessions(shape=True) with no shaping slot, and the
+    same with every slot opened with shape=True at +6 dB (the limiter works); below them the shape launch alone"""
+    from dmel_codec_amd import _lib
+    from dmel_codec_amd.utils import shape as shape_rule
+    chunk, warmup = 16, 8
+    gl = torch.Generator().manual_seed(8)
+    G, Cn = codec.dmel_groups, codec.decoder.input_channels
+    n_steps = warmup + steps
+    ids = torch.randint(0, 175, (S, G, chunk * n_steps), generator=gl, dtype=torch.int32).to(dev)
+    kw = dict(max_push_tokens=chunk, output_sample_rates=(rate,) if rate else ())
+    open_kw = dict(output_sample_rate=rate or None, sample_format=fmt)
+    pools = {"no_shape_pool": codec.decode_sessions(S, **kw), "shape_pool_idle": codec.decode_sessions(S, shape=True, **kw),
+             "shape_pool_all": codec.decode_sessions(S, shape=True, **kw)}
+    slots = {k: [p.open(**open_kw, **(dict(shape=True) if k == "shape_pool_all" else {})) for _ in range(S)] for k, p in pools.items()}
+    for s in slots["shape_pool_all"]:
+        pools["shape_pool_all"].set_gain(s, 6.0, ramp_ms=20.0)
+    ms, launches, samples = {k: [] for k in pools}, {k: {} for k in pools}, {k: 0 for k in pools}
+    keys, families = list(pools), ("shape", "small", "pcm_convert")
+    for j in range(n_steps):
+        noise = [torch.randn(Cn, chunk * 4, device=dev) for _ in range(S)]
+        counted = j == n_steps - 1                                          # the launch records of the last step, which is not timed
+        for k in (keys if j % 2 == 0 else keys[::-1]):                      # no pool always goes first
+            pool = pools[k]
+            if counted:
+                _lib.prof_reset(); _lib.prof_enable(True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = pool.push({s: ids[i, :, j * chunk:(j + 1) * chunk] for i, s in enumerate(slots[k])},
+                            noise={s: noise[i] for i, s in enumerate(slots[k])})
+            torch.cuda.synchronize()
+            if counted:
+                launches[k] = {f: _lib.prof_read(f)["launches"] for f in families}
+                _lib.prof_enable(False); _lib.prof_reset()
+            elif j >= warmup:
+                ms[k].append((time.perf_counter() - t0) * 1e3)
+            samples[k] += sum(a.numel() for a, _ in res.values())
+    pct = lambda v, q: sorted(v)[min(len(v) - 1, int(q * len(v)))]
+    result, rows = {"sessions": S, "chunk_tokens": chunk, "output_sample_rate": rate or pools[keys[0]].voc_rate, "sample_format": fmt}, []
+    for k in keys:
+        v = ms[k]
+        result[k] = {"median_ms": round(statistics.median(v), 3), "p10_ms": round(pct(v, 0.1), 3), "p90_ms": round(pct(v, 0.9), 3), "n": len(v),
+                     "launches_per_step": launches[k], "audio_samples": samples[k]}
+        rows.append(f"{S:8d}  {k:18s}  {statistics.median(v):9.3f}  {pct(v, 0.1):9.3f}  {pct(v, 0.9):9.3f}  {len(v):4d}  "
+                    f"{launches[k]['shape']:5d}  {launches[k]['small']:5d}  {launches[k]['pcm_convert']:11d}")
+    reports = pools["shape_pool_all"].shaped()
+    result["limited_blocks"] = sum(r.limited_blocks for r in reports.values())
+    # the launch alone: S slots, one step's samples each, fresh rows every time
+    cfg, n = shape_rule.ShapeConfig(), chunk * 4 * pools[keys[0]].up
+    vr = pools[keys[0]].voc_rate
+    x = (torch.randn(S, n, device=dev) * 0.5).contiguous()
+    y = torch.empty(S, n + 2 * shape_rule.MAX_BLOCK, device=dev)
+    st = torch.zeros(S, cfg.state_words(vr), dtype=torch.int32, device=dev)
+    pk, gn = torch.zeros(S, n // 32 + 2, device=dev), torch.zeros(S, n // 32 + 2, device=dev)
+    tab = torch.empty(shape_rule.TABLE_WORDS * S, dtype=torch.int32, device=dev)
+    ramps, off = shape_rule.ramp_arena([480], dev)
+    alone = []
+    for j in range(warmup + steps):
+        st.zero_()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        shape_rule.shape_items([x[s] for s in range(S)], [y[s] for s in range(S)], [cfg] * S, [[(0, 1.0, 2.0, 480)]] * S, [1.0] * S, [0] * S,
+                               [0] * S, [False] * S, st, pk, gn, vr, ramps=ramps, ramp_off=off, table=tab)
+        torch.cuda.synchronize()
+        if j >= warmup:
+            alone.append((time.perf_counter() - t0) * 1e3)
+    result["launch_alone"] = {"median_ms": round(statistics.median(alone), 4), "p10_ms": round(pct(alone, 0.1), 4),
+                              "p90_ms": round(pct(alone, 0.9), 4), "samples_per_slot": n}
+    med = [result[k]["median_ms"] for k in keys]
+    level = all(result[k]["p10_ms"] <= m <= result[k]["p90_ms"] for k in keys[:2] for m in med[:2])
+    result["idle_level_within_spread"] = level
+    verdict = (("the pool without the option and the shape pool without a shaping slot lie inside each other's p10 .. p90: level within "
+                "spread" if level else f"shape pool without a shaping slot {med[1] - med[0]:+.3f} ms against the pool without the option, outside "
+                "the spread") + f"; every slot shaping {med[2] - med[0]:+.3f} ms against the pool without the option (new work: no threshold)")
+    table = [f"{S} decode sessions, {chunk}-token pushes, audio at {result['output_sample_rate']} Hz as {fmt}, 100 mel / 10 groups, BigVGAN base "
+             f"(tools/bench_stream.py --sessions {S} --shape)",
+             f"per-step wall time incl. host synchronisation, {steps} steady-state steps, the three pools interleaved in one process;",
+             "no_shape_pool = decode_sessions() as it was; shape_pool_idle = decode_sessions(shape=True), no slot opened with shape=; "
+             "shape_pool_all = the same with every slot opened with shape=True and set_gain(+6 dB)",
+             "launch records of one step: shape (dmel_shape_items), small (all small kernels, the shape launch among them), pcm_convert",
+             "sessions  pool                median ms     p10 ms     p90 ms     n  shape  small  pcm_convert"] + rows + [
+             f"dmel_shape_items alone, {S} slots of {n} samples, fresh rows, wall time incl. host synchronisation: median "
+             f"{statistics.median(alone):.4f} ms, p10 {pct(alone, 0.1):.4f}, p90 {pct(alone, 0.9):.4f}; limited blocks over the run: "
+             f"{result['limited_blocks']}", verdict]
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "a") as f:
+        f.write("\n".join(table) + "\n\n")
+    print("\n".join(table), file=sys.stderr)
+    print(json.dumps(result))
+
+
+if "--shape" in sys.argv:
+    assert "--sessions" in sys.argv, "--shape needs --sessions"
+    sessions_shape_section(int(arg_after("--sessions")), int(arg_after("--output-sample-rate", "0")), arg_after("--sample-format", "f32"),
+                           int(arg_after("--steps", "40")),
+                           arg_after("--out", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                           "sessions_shape.txt")))
     sys.exit(0)
 
 if "--park" in sys.argv:
