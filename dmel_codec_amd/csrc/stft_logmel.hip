@@ -116,7 +116,9 @@ struct StftTables {
   const float* mel_w;   // packed non-zero weights
   // balanced mel stage: every band's bin range is cut into chunks of kMelChunk bins (weights zero-padded); chunk i belongs to lane
   // i % 64, pass i / 64
-  const int* ch_k0;     // [64 * passes] first FFT bin of the chunk (clamped so that k0 + kMelChunk - 1 stays inside the magnitude row)
+  const int* ch_k0;     // [64 * passes] first FFT bin of the chunk.  NOT clamped: a band's last chunk may run up to 7 bins past bin H (zero weights
+                        // there); it then reads the seven pad slots mg[H + 1 .. H + 7], which the kernel zeroes itself so that 0 * slot is 0
+                        // whatever the LDS held (tests/test_gpu_stft_matrix.py: a weighted Nyquist bin over NaN-filled LDS)
   const float* ch_w;    // [64 * passes][kMelChunk] weights, zeros past the band's end and for unused chunks
   const int* band_pbeg; // [n_mels] first chunk of the band
   const int* band_pcnt; // [n_mels] number of chunks of the band
