@@ -120,6 +120,8 @@ PROTOTYPES = {
     "dmel_tone_items": (C.c_int, [C.POINTER(vp), C.POINTER(vp), i64p, i32p, i32p, C.c_int, i32p, C.c_int, vp, C.c_int, vp, C.c_int64, vp, vp]),
     "dmel_shape_items": (C.c_int, [C.POINTER(vp), i64p, C.POINTER(vp), i64p, i64p, i32p, i32p, f32p, i32p, i32p, C.c_int, vp, C.c_int64, vp,
                                    C.c_int64, vp, vp, C.c_int64, vp, vp]),
+    "dmel_pace_items": (C.c_int, [C.POINTER(vp), i64p, C.POINTER(vp), i64p, i64p, i32p, i32p, i32p, f32p, i32p, i32p, i32p, C.c_int, vp,
+                                  C.c_int64, i32p, vp, C.c_int64, vp, vp, C.c_int64, vp, vp]),
     "dmel_stream_pack_items": (C.c_int, [C.POINTER(vp), C.POINTER(vp), i64p, i64p, i64p, i64p, C.c_int, vp, vp]),
     "dmel_wavenet_set_tensor":(C.c_int, [vp, C.c_char_p, vp, i64p, C.c_int]),
     "dmel_wavenet_finalize": (C.c_int, [vp]),

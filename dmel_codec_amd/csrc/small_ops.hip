@@ -3363,3 +3363,285 @@ extern "C" int dmel_shape_items(float* const* dst, const int64_t* dst_cap, const
   DMEL_HIP(hipGetLastError());
   return DMEL_OK;
 }
+
+namespace dmel {
+
+// ---- speaking rate on codec-rate audio (include/dmel_hip.h: dmel_pace_items; the rule and the state row: utils/pace.py) ----------------
+// Row s of the table is 64 4-byte words: dst (2), src (2), n_new, hold, flags (1: final), H, D, floor, eps, K, a_{K-1}, a_K, fed, the
+// frames the step completes, the samples it hands out, the base rate, the request count, the offset of the weight table, zeros, and
+// from word 32 eight request records of two words (position relative to the first new sample, permille); workgroup s owns slot s.
+// The slot's stream x is addressed by ABSOLUTE positions: [fed - hold, fed) are the held samples of its state row, [fed, fed + n_new)
+// the new ones, 0.0 behind them.  A WINDOW of 6144 consecutive positions sits in LDS; a frame needs [min(t, a - D), max(t, a + D) + H),
+// at most 2 H + 2 D = 2048 positions, and the window is re-filled from the frame's lowest position when that range leaves it.  The
+// frames of a slot run in order: (a) the natural-continuation test on uniform integers; (b) otherwise the work items are (candidate,
+// sum8 segment) pairs, candidates in passes of 511, the template's own energy riding as one more candidate of the first pass: item
+// c is segment c / cnt, candidate c % cnt, so the lanes of a wave read consecutive window words (conflict-free) and the same template
+// word (a broadcast), each item one sequential sum of H / 8 terms; (c) thread c joins the eight partial sums of candidate c by the
+// fixed tree, forms q and keeps its best (q, |d|, d) key; the keys meet by wave shuffles and one LDS round -- the order is total, so
+// any reduction order gives the same winner; (d) thread i blends sample i and stores it.  Behind the last frame the window is
+// re-filled from the position the rule keeps from, and that part goes back to the row.  Every operation of the rule is rounded on
+// its own (fp contract(off)).  Plain stores, no atomics.
+constexpr int kPaceWords = 64, kPaceHeader = 16, kPaceMinHop = 64, kPaceMaxHop = 512, kPaceMaxSearch = 512, kPaceWindow = 6144;
+constexpr int kPacePass = 511, kPaceStride = kPacePass + 1, kPaceThreads = 512, kPaceMaxReq = 8, kPaceReqBase = 32;
+constexpr int kPaceMinRate = 500, kPaceMaxRate = 2000, kPaceMaxNew = 1 << 26;
+__host__ __device__ __forceinline__ int pace_rate_at(const int32_t* req, int nreq, int base, int64_t rel) {
+  int r = base;
+  for (int q = 0; q < nreq; ++q)
+    if ((int64_t)req[2 * q] <= rel) r = req[2 * q + 1];   // positions do not decrease: the last one at or in front of rel
+  return r;
+}
+__host__ __device__ __forceinline__ int pace_hop(int H, int permille) { return (H * permille + 500) / 1000; }
+// (q, d) beats (oq, od): the larger value, then the smaller |d|, then the negative d
+__device__ __forceinline__ bool pace_better(float q, int d, float oq, int od) {
+  const int a = d < 0 ? -d : d, oa = od < 0 ? -od : od;
+  return q > oq || (q == oq && (a < oa || (a == oa && d < od)));
+}
+__global__ __launch_bounds__(kPaceThreads) void pace_kernel(const uint32_t* __restrict__ tab, uint32_t* __restrict__ state,
+                                                            int64_t state_pitch, const float* __restrict__ weights,
+                                                            int32_t* __restrict__ out_offset, float* __restrict__ out_score,
+                                                            int64_t out_pitch) {
+#pragma clang fp contract(off)
+  __shared__ float win[kPaceWindow];
+  __shared__ float pc[8 * kPaceStride], pe[8 * kPaceStride];
+  __shared__ float red_q[kPaceThreads / 64], sh_e0;
+  __shared__ int red_d[kPaceThreads / 64];
+  const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint32_t* row = tab + (size_t)s * kPaceWords;
+  const int n_new = (int)row[4], flags = (int)row[6];
+  const bool final = flags & 1;
+  if (n_new <= 0 && !final) return;                     // idle (uniform: in front of the first barrier)
+  float* dst = reinterpret_cast<float*>(((uint64_t)row[1] << 32) | row[0]);
+  const float* src = reinterpret_cast<const float*>(((uint64_t)row[3] << 32) | row[2]);
+  const int hold = (int)row[5], H = (int)row[7], D = (int)row[8], h8 = H >> 3;
+  const float floor_e = __uint_as_float(row[9]), eps = __uint_as_float(row[10]);
+  int K = (int)row[11], a_prev = (int)row[12], a_next = (int)row[13];
+  const int fed = (int)row[14], frames = (int)row[15], n_out = (int)row[16], base_rate = (int)row[17], nreq = (int)row[18];
+  const float* W = weights + (int)row[19];
+  const int32_t* req = reinterpret_cast<const int32_t*>(row + kPaceReqBase);
+  uint32_t* srow = state + (size_t)s * state_pitch;
+  float* held = reinterpret_cast<float*>(srow + kPaceHeader);
+  const int sbase = fed - hold, L = fed + n_new;        // the stream has [sbase, L); 0.0 behind L
+  // a row the rule made has |p_{K-1} - a_{K-1}| <= D; the clamp keeps any other row's reads inside the window
+  int p_prev = K > 0 ? max(0, min(max((int)srow[1], a_prev - D), a_prev + D)) : 0;
+  int natural = (int)srow[6], searched = (int)srow[7], quiet = (int)srow[8], permille = (int)srow[12];
+  int last_off = (int)srow[10];
+  float last_q = __uint_as_float(srow[11]);
+  int32_t* ooff = out_offset + (int64_t)s * out_pitch;
+  float* osc = out_score + (int64_t)s * out_pitch;
+  auto fill = [&](int wb) {                             // win[q] = x[wb + q]
+    for (int q = tid; q < kPaceWindow; q += kPaceThreads) {
+      const int pos = wb + q;
+      float v = 0.0f;
+      if (pos >= fed) { if (pos < L) v = src[pos - fed]; }
+      else if (pos >= sbase) v = held[pos - sbase];
+      win[q] = v;
+    }
+  };
+  int wb = 0;
+  bool have = false;
+  for (int j = 0; j < frames; ++j) {
+    const int a = a_next, t = p_prev + H;
+    const bool nat = K == 0 || (a - D <= t && t <= a + D);
+    const int first = K == 0 ? 0 : t;                   // frame 0 reads x[0 : H]
+    const int lo = nat ? first : min(t, max(0, a - D)), hi = (nat ? first : max(t, a + D)) + H;
+    if (!have || lo < wb || hi > wb + kPaceWindow) {    // uniform
+      __syncthreads();                                  // the frame before has read the window
+      fill(lo);
+      wb = lo; have = true;
+      __syncthreads();
+    }
+    int p = first;
+    float q = 0.0f;
+    if (nat) natural += 1;
+    else {
+      const float* T = win + (t - wb);
+      const int dlo = max(-D, -a), nc = D - dlo + 1;    // candidates d = dlo .. D
+      float bq = -1.0f;
+      int bd = 0x7fffffff;
+      for (int c0 = 0; c0 < nc; c0 += kPacePass) {
+        const int real = min(kPacePass, nc - c0), cnt = real + (c0 == 0 ? 1 : 0);      // + the template against itself
+        for (int c = tid; c < cnt * 8; c += kPaceThreads) {
+          const int seg = c / cnt, ci = c - seg * cnt;
+          const float* tp = T + seg * h8;
+          const float* bp = ci < real ? win + (a + dlo + c0 + ci - wb) + seg * h8 : tp;
+          float ac = 0.0f, ae = 0.0f;
+          for (int i = 0; i < h8; ++i) {
+            const float tv = tp[i], bv = bp[i];
+            const float tb = tv * bv;
+            ac = ac + tb;
+            const float bb = bv * bv;
+            ae = ae + bb;
+          }
+          pc[seg * kPaceStride + ci] = ac;
+          pe[seg * kPaceStride + ci] = ae;
+        }
+        __syncthreads();
+        if (tid < cnt) {
+          float sc[8], se[8];
+#pragma unroll
+          for (int g = 0; g < 8; ++g) { sc[g] = pc[g * kPaceStride + tid]; se[g] = pe[g * kPaceStride + tid]; }
+          const float cc = echo_tree(sc), e = echo_tree(se);
+          if (tid < real) {
+            float qv = 0.0f;
+            if (cc > 0.0f) {
+              const float c2 = cc * cc;
+              const float ee = e + eps;
+              qv = c2 / ee;
+            }
+            const int d = dlo + c0 + tid;
+            if (pace_better(qv, d, bq, bd)) { bq = qv; bd = d; }
+          } else sh_e0 = e;
+        }
+        __syncthreads();                                // the next pass overwrites the partial sums
+      }
+      for (int o = 32; o; o >>= 1) {
+        const float oq = __shfl_xor(bq, o);
+        const int od = __shfl_xor(bd, o);
+        if (pace_better(oq, od, bq, bd)) { bq = oq; bd = od; }
+      }
+      if (lane == 0) { red_q[wave] = bq; red_d[wave] = bd; }
+      __syncthreads();
+      bq = red_q[0]; bd = red_d[0];
+      for (int w = 1; w < kPaceThreads / 64; ++w)
+        if (pace_better(red_q[w], red_d[w], bq, bd)) { bq = red_q[w]; bd = red_d[w]; }
+      if (sh_e0 < floor_e) { p = a; quiet += 1; }
+      else { p = a + bd; q = bq; searched += 1; }
+    }
+    const int emit = min(H, n_out - j * H);
+    if (tid < emit) {
+      const float old = win[first - wb + tid];
+      float y = old;
+      if (p != first) {
+        float m = win[p - wb + tid] - old;
+        m = W[tid] * m;
+        y = old + m;
+      }
+      dst[(int64_t)j * H + tid] = y;
+    }
+    if (tid == 0) { ooff[j] = p - a; osc[j] = q; }
+    last_off = p - a; last_q = q;
+    permille = pace_rate_at(req, nreq, base_rate, (int64_t)a - fed);
+    a_prev = a; a_next = a + pace_hop(H, permille);
+    p_prev = p; K += 1;
+  }
+  // what the rule keeps goes back to the row
+  const int cap = 2 * H + 2 * D;
+  int keep = final ? L : (K == 0 ? 0 : min(L, max(0, min(a_prev + H, a_next) - D)));
+  keep = max(keep, max(sbase, L - (cap - 1)));           // no-ops for integers the rule made
+  const int n_hold = L - keep;
+  __syncthreads();                                      // the last frame has read the window, and red_q / sh_e0
+  fill(keep);
+  __syncthreads();
+  for (int q = tid; q < cap; q += kPaceThreads) held[q] = q < n_hold ? win[q] : 0.0f;
+  if (tid == 0) {
+    srow[0] = (uint32_t)K; srow[1] = (uint32_t)p_prev; srow[2] = (uint32_t)a_prev; srow[3] = (uint32_t)a_next;
+    srow[4] = (uint32_t)L; srow[5] = (uint32_t)n_hold; srow[6] = (uint32_t)natural; srow[7] = (uint32_t)searched;
+    srow[8] = (uint32_t)quiet; srow[9] = (uint32_t)((int)srow[9] + n_out); srow[10] = (uint32_t)last_off;
+    srow[11] = __float_as_uint(last_q); srow[12] = (uint32_t)permille;
+  }
+}
+
+}  // namespace dmel
+
+extern "C" int dmel_pace_items(float* const* dst, const int64_t* dst_cap, const float* const* src, const int64_t* n_new,
+                               const int64_t* ints, const int32_t* flags, const int32_t* H, const int32_t* D, const float* fparams,
+                               const int32_t* base_permille, const int32_t* req_count, const int32_t* reqs, int S, const float* weights,
+                               int64_t weight_floats, const int32_t* weight_off, void* state, int64_t state_pitch, int32_t* out_offset,
+                               float* out_score, int64_t out_pitch, void* table_scratch, void* stream) {
+  using namespace dmel;
+  DMEL_CHECK_ARG(dst && dst_cap && src && n_new && ints && flags && H && D && fparams && base_permille && req_count && reqs && weights &&
+                     weight_off && state && out_offset && out_score && table_scratch,
+                 "pace_items: NULL argument");
+  DMEL_CHECK_ARG(S >= 1 && S <= 65535, "pace_items: %d items, expected 1 .. 65535", S);
+  DMEL_CHECK_ARG(weight_floats >= 0, "pace_items: a weight arena of %lld floats", (long long)weight_floats);
+  DMEL_CHECK_ARG((((uintptr_t)state | (uintptr_t)out_offset | (uintptr_t)out_score | (uintptr_t)weights) & 3) == 0,
+                 "pace_items: state, out_offset, out_score or weights is not 4-byte aligned");
+  DMEL_CHECK_ARG(((uintptr_t)table_scratch & 7) == 0, "pace_items: table_scratch is not 8-byte aligned");
+  DMEL_CHECK_ARG(state_pitch >= kPaceHeader && out_pitch >= 0, "pace_items: a state pitch of %lld words (at least %d) or a negative "
+                 "output pitch %lld", (long long)state_pitch, kPaceHeader, (long long)out_pitch);
+  std::vector<uint32_t> tab((size_t)kPaceWords * S, 0u);
+  int64_t live = 0;
+  double bytes = 0.0;
+  for (int s = 0; s < S; ++s) {
+    const int64_t n = n_new[s];
+    DMEL_CHECK_ARG(n >= 0 && n <= kPaceMaxNew, "pace_items: item %d: %lld new samples, expected 0 .. 2^26", s, (long long)n);
+    DMEL_CHECK_ARG(flags[s] >= 0 && flags[s] <= 1, "pace_items: item %d: flags %d, expected 0 .. 1 (1: final)", s, flags[s]);
+    const bool fin = flags[s] & 1;
+    if (n == 0 && !fin) continue;                       // idle: its parameters are not looked at (the table row stays 0)
+    const int32_t h = H[s], d = D[s];
+    DMEL_CHECK_ARG(h >= kPaceMinHop && h <= kPaceMaxHop && h % 8 == 0, "pace_items: item %d: a hop of %d samples, expected a multiple of 8 "
+                   "in %d .. %d", s, h, kPaceMinHop, kPaceMaxHop);
+    DMEL_CHECK_ARG(d >= 0 && d <= kPaceMaxSearch, "pace_items: item %d: a search half-width of %d samples, expected 0 .. %d", s, d,
+                   kPaceMaxSearch);
+    const int64_t* iv = ints + (size_t)5 * s;
+    const int64_t K0 = iv[0], ap0 = iv[1], an0 = iv[2], fed = iv[3], hold = iv[4];
+    DMEL_CHECK_ARG(hold >= 0 && hold < 2 * (int64_t)h + 2 * d, "pace_items: item %d: %lld held samples, expected 0 .. 2 H + 2 D - 1 = %d", s,
+                   (long long)hold, 2 * h + 2 * d - 1);
+    DMEL_CHECK_ARG(state_pitch >= kPaceHeader + 2 * (int64_t)h + 2 * d, "pace_items: item %d: a state row of %lld words, H = %d and D = %d "
+                   "need %d", s, (long long)state_pitch, h, d, kPaceHeader + 2 * h + 2 * d);
+    DMEL_CHECK_ARG(fed >= hold && fed <= ((int64_t)1 << 30), "pace_items: item %d: %lld samples fed, expected the %lld held .. 2^30", s,
+                   (long long)fed, (long long)hold);
+    DMEL_CHECK_ARG(K0 >= 0 && K0 < ((int64_t)1 << 30) && ap0 >= 0 && (K0 == 0 ? an0 == 0 && ap0 == 0
+                                                                              : an0 - ap0 >= h / 2 && an0 - ap0 <= 2 * h && an0 <= fed + 2 * h),
+                   "pace_items: item %d: the integers K = %lld, a_{K-1} = %lld, a_K = %lld are none the rule makes with %lld samples fed", s,
+                   (long long)K0, (long long)ap0, (long long)an0, (long long)fed);
+    DMEL_CHECK_ARG((((uintptr_t)dst[s] | (uintptr_t)src[s]) & 3) == 0, "pace_items: item %d: a pointer is not 4-byte aligned", s);
+    const float* fp = fparams + (size_t)2 * s;
+    DMEL_CHECK_ARG(std::isfinite(fp[0]) && fp[0] >= 0.0f && std::isfinite(fp[1]) && fp[1] > 0.0f,
+                   "pace_items: item %d: floor %g is not finite or is negative, or eps %g is not finite and positive", s, (double)fp[0],
+                   (double)fp[1]);
+    const int32_t base = base_permille[s], count = req_count[s];
+    DMEL_CHECK_ARG(base >= kPaceMinRate && base <= kPaceMaxRate, "pace_items: item %d: a rate of %d permille, expected %d .. %d", s, base,
+                   kPaceMinRate, kPaceMaxRate);
+    DMEL_CHECK_ARG(count >= 0 && count <= kPaceMaxReq, "pace_items: item %d: %d live requests, expected 0 .. %d", s, count, kPaceMaxReq);
+    const int32_t* rq = reqs + (size_t)2 * kPaceMaxReq * s;
+    int32_t before = INT32_MIN;
+    for (int k = 0; k < count; ++k) {
+      DMEL_CHECK_ARG(rq[2 * k] >= -(1 << 30) && rq[2 * k] <= (1 << 30) && rq[2 * k] >= before,
+                     "pace_items: item %d: request %d: position %d, expected -2^30 .. 2^30 and no decrease", s, k, rq[2 * k]);
+      DMEL_CHECK_ARG(rq[2 * k + 1] >= kPaceMinRate && rq[2 * k + 1] <= kPaceMaxRate,
+                     "pace_items: item %d: request %d: a rate of %d permille, expected %d .. %d", s, k, rq[2 * k + 1], kPaceMinRate,
+                     kPaceMaxRate);
+      before = rq[2 * k];
+    }
+    DMEL_CHECK_ARG(weight_off[s] >= 0 && (int64_t)weight_off[s] + h <= weight_floats,
+                   "pace_items: item %d: weight table [%d, %d + %d) lies beyond the arena of %lld floats", s, weight_off[s], weight_off[s], h,
+                   (long long)weight_floats);
+    // the step on integers, as utils/pace.py: advance
+    const int64_t L = fed + n;
+    int64_t K = K0, ap = ap0, an = an0, fr = 0;
+    while (fin ? an < L : L >= (K == 0 ? (int64_t)h : std::max(ap + 2 * h, an + h) + d)) {
+      const int r = pace_rate_at(rq, count, base, an - fed);
+      ap = an; an += pace_hop(h, r);
+      ++K; ++fr;
+    }
+    int64_t leave = fr * h;
+    if (fin && fr) leave -= h - std::min<int64_t>(h, L - ap);
+    DMEL_CHECK_ARG(out_pitch >= fr, "pace_items: item %d: the step completes %lld frames, which exceed the output pitch %lld", s,
+                   (long long)fr, (long long)out_pitch);
+    DMEL_CHECK_ARG(dst_cap[s] >= leave, "pace_items: item %d: the step hands out %lld samples, its destination takes %lld", s,
+                   (long long)leave, (long long)dst_cap[s]);
+    DMEL_CHECK_ARG((dst[s] || leave == 0) && (src[s] || n == 0), "pace_items: item %d: NULL %s", s, src[s] || n == 0 ? "destination" : "source");
+    uint32_t* it = tab.data() + (size_t)kPaceWords * s;
+    const uint64_t dp = (uint64_t)(uintptr_t)dst[s], xp = (uint64_t)(uintptr_t)src[s];
+    it[0] = (uint32_t)dp; it[1] = (uint32_t)(dp >> 32); it[2] = (uint32_t)xp; it[3] = (uint32_t)(xp >> 32);
+    it[4] = (uint32_t)n; it[5] = (uint32_t)hold; it[6] = (uint32_t)flags[s]; it[7] = (uint32_t)h; it[8] = (uint32_t)d;
+    std::memcpy(it + 9, fp, 2 * sizeof(float));
+    it[11] = (uint32_t)K0; it[12] = (uint32_t)ap0; it[13] = (uint32_t)an0; it[14] = (uint32_t)fed; it[15] = (uint32_t)fr;
+    it[16] = (uint32_t)leave; it[17] = (uint32_t)base; it[18] = (uint32_t)count; it[19] = (uint32_t)weight_off[s];
+    std::memcpy(it + kPaceReqBase, rq, (size_t)2 * count * sizeof(int32_t));
+    ++live;
+    bytes += 4.0 * (double)n + 4.0 * (double)leave + 8.0 * (double)fr + 8.0 * kPaceHeader + 4.0 * (double)hold + 4.0 * (2.0 * h + 2.0 * d);
+  }
+  if (live == 0) return DMEL_OK;                        // every item idle
+  hipStream_t st = (hipStream_t)stream;
+  DMEL_TRY(launch_table_put(tab.data(), tab.size() * sizeof(uint32_t), table_scratch, st));
+  {
+    // "small" carries the time and the bytes; the second scope only counts: one record per pace launch (dmel_prof_read("pace"))
+    ProfScope ps("small", st, 0.0, bytes), count("pace", st, 0.0, 0.0);
+    hipLaunchKernelGGL(pace_kernel, dim3((unsigned)S), dim3(kPaceThreads), 0, st, static_cast<const uint32_t*>(table_scratch),
+                       static_cast<uint32_t*>(state), state_pitch, weights, out_offset, out_score, out_pitch);
+  }
+  DMEL_HIP(hipGetLastError());
+  return DMEL_OK;
+}

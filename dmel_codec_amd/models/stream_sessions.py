@@ -25,6 +25,7 @@ from ..utils import dtmf as dtmf_rule
 from ..utils import echo as echo_rule
 from ..utils import denoise as denoise_rule
 from ..utils import level as level_rule
+from ..utils import pace as pace_rule
 from ..utils import shape as shape_rule
 from ..utils import tones as tone_rule
 from ..utils import voice as voice_rule
@@ -1356,6 +1357,26 @@ class DecodeSessions(ParkingPool):
     shape_end; a snapshot without them restores as a session without the option); drop discards it.  The resampler's rows of such
     a pool hold 2 * 1024 - 1 samples more: what a limiter hands out late.
 
+    How fast a reply speaks: a pool built with pace=True (and audio) serves sessions opened with pace=True or a PaceConfig
+    (utils/pace.py: the rule -- WSOLA time-scaling, the pitch stays --, its defaults and its caveats).  set_pace(slot, permille,
+    at_sample) sets the rate (500 .. 2000 permille of the unchanged speed) from an input sample of the slot's pacer on; pace_fed(slot)
+    is "now".  The pacer acts on the slot's speech pieces as _route receives them -- behind the vocoder and the cross-fade, the
+    flushed fade tail included --, in front of the shaper, the resampler and the wire convert: ONE dmel_pace_items launch per step
+    serves all pacing slots with a new piece or their end and writes where the slot's route reads -- the shaper's source row when
+    the session also shapes, else a staging row for the resampler or the convert launch, else a fresh tensor handed out in place of
+    the clone.  A pacing session's audio is, bit for bit, its wire chain applied to pace.scan(its codec-rate stream, requests,
+    config, final=True)[0] -- to shape.scan of that where it also shapes --, however the tokens were cut into pushes; rate 1000 is
+    the plain audio.  For such a session set_gain(at_sample=), samples_fed and stop count in the PACED stream.  Mel pieces and
+    frames_emitted do not change; a session opened without pace= and a pool built without pace=True are what they were, and such a
+    pool refuses open(pace=), set_pace, pace_fed, paced, pace_frames and the snapshot of a pacing session.  paced() ->
+    {slot: PaceReport} (one copy of the headers); pace_frames(slot): per-frame (offset, score) of the last push.  The state travels
+    with snapshot / restore (meta keys pace, pace_ints, pace_requests, pace_base; a snapshot without them restores as a session
+    without the option); drop discards it.  The rows downstream of the pacer -- the shaper's staging, the resampler's rows, the
+    convert staging -- are sized from pace.max_out(cap * up + fade, 512, 512) in such a pool.  Not served: tones on a pacing
+    session (send_dtmf / send_tones are refused: tones must not be stretched, and mapping an anchor frame through a rate that may
+    still change is a separate piece of work), pacing the lockstep StreamingDecoder and whole-clip decode() (callers have
+    pace.scan), a playout buffer that chooses the rate.
+
     Out of scope, NotImplementedError: overlap_vocoder, graph_chunk_tokens, and a pool-wide output_sample_rate (a pool has no rate of
     its own).
 
@@ -1367,7 +1388,7 @@ class DecodeSessions(ParkingPool):
     def __init__(self, codec, slots: int, max_push_tokens: int = 64, return_audios: bool = True, overlap_vocoder: bool = False,
                  graph_chunk_tokens: Optional[int] = None, output_sample_rate: Optional[int] = None,
                  output_sample_rates: Iterable[int] = (), early_emit: bool = False, crossfade_samples: int = 0, tones: bool = False,
-                 max_tone_samples: Optional[int] = None, shape: bool = False):
+                 max_tone_samples: Optional[int] = None, shape: bool = False, pace: bool = False):
         if overlap_vocoder or graph_chunk_tokens is not None or output_sample_rate is not None:
             raise NotImplementedError("decode sessions launch everything on the current stream, eagerly, and have no rate of their own: "
                                       "overlap_vocoder, graph_chunk_tokens and output_sample_rate belong to StreamingDecoder (a session's "
@@ -1430,9 +1451,27 @@ class DecodeSessions(ParkingPool):
             raise ValueError("shape without audio: return_audios=False leaves nothing to shape")
         self.shape_on = shape
         self.shape_room = 2 * shape_rule.MAX_BLOCK - 1 if shape else 0
-        # a step emits frames that all lie in the slot's `cap` columns: at most cap * up samples, the tones that waited, and what a
-        # limiter held back, reach a slot's resampler at once
-        self._init_slots(self.voc_rate, "output_sample_rates", self.cap * self.up + self.max_tone + self.shape_room)
+        # the pool paces replies (open(pace=), set_pace): a step's piece leaves the pacer longer or shorter than it came
+        if not isinstance(pace, bool):
+            raise ValueError(f"pace must be a bool, got {pace!r}")
+        if pace and not return_audios:
+            raise ValueError("pace without audio: return_audios=False leaves nothing to pace")
+        self.pace_on = pace
+        # a step emits frames that all lie in the slot's `cap` columns: at most cap * up samples and the tones that waited -- in a
+        # pace pool at most what the pacer makes of a step's piece (or of a fade tail) -- and what a limiter held back, reach a
+        # slot's resampler at once
+        self.chain_w = self.cap * self.up + self.max_tone
+        if pace:
+            self.chain_w = max(self.chain_w, pace_rule.max_out(self.cap * self.up + self.fade_max, pace_rule.MAX_HOP, pace_rule.MAX_SEARCH))
+        self._init_slots(self.voc_rate, "output_sample_rates", self.chain_w + self.shape_room)
+        self.pcfg: List[Optional[pace_rule.PaceConfig]] = [None] * self.S
+        self.preq: List[list] = [[] for _ in range(self.S)]   # the slot's live rate requests (P, permille), over the rate pbase
+        self.pbase = [1000] * self.S
+        self.pints: List[tuple] = [pace_rule.FRESH] * self.S  # (K, a_{K-1}, a_K, fed): the pacer's integers, tracked from the rule's
+        self._pace_n = [0] * self.S                       # frames the slot's last push completed
+        self._pace_src: Dict[int, torch.Tensor] = {}      # the float pieces of the step the pacer reads
+        self._pw_off: Dict[int, int] = {}                 # hop -> offset of its weight table in the pool's pace arena
+        self._pw_floats = 0
         self.scfg: List[Optional[shape_rule.ShapeConfig]] = [None] * self.S
         self.sreq: List[list] = [[] for _ in range(self.S)]   # the slot's live gain segments (P, g0, g1, ramp), over the base gain sbase
         self.sbase = [1.0] * self.S
@@ -1460,7 +1499,7 @@ class DecodeSessions(ParkingPool):
         return self.sched[slot].emitted
 
     def open(self, output_sample_rate: Optional[int] = None, sample_format: str = "f32", channels: int = 1,
-             lookahead_frames: Optional[int] = None, crossfade_samples: int = 0, shape=None) -> int:
+             lookahead_frames: Optional[int] = None, crossfade_samples: int = 0, shape=None, pace=None) -> int:
         """take a free slot: fresh schedule, state zeroed before its first push.  output_sample_rate: the rate this session's audio
         leaves at, one of the declared `output_sample_rates` (None: the vocoder's).  sample_format: "f32", "s16" for audio returned
         as torch.int16 (16-bit signed PCM), or "ulaw" / "alaw" for torch.uint8 (G.711 codes).  channels: 1 .. 8; above 1 the audio
@@ -1469,8 +1508,14 @@ class DecodeSessions(ParkingPool):
         early_emit=True.  crossfade_samples: F >= 1 samples (at most the pool's crossfade_samples and one mel frame) over which
         such a session blends every piece into the next (utils/crossfade.py); its audio runs F samples behind its mel.  shape: True
         or a ShapeConfig (utils/shape.py) for a session whose audio passes the commanded gain and the limiter, on a pool built with
-        shape=True: set_gain and stop serve it, and its audio runs N .. 2 N - 1 samples behind with the limiter.  Raises when every
-        slot is taken; a refused open takes no slot."""
+        shape=True: set_gain and stop serve it, and its audio runs N .. 2 N - 1 samples behind with the limiter.  pace: True or a
+        PaceConfig (utils/pace.py) for a session whose speech passes the pacer, on a pool built with pace=True: set_pace serves it.
+        Raises when every slot is taken; a refused open takes no slot."""
+        pcfg = pace_rule.as_config(pace)
+        if pcfg is not None:
+            if not self.pace_on:
+                raise ValueError("pace on a pool built without pace=True: it has no rows to hold a reply's samples in")
+            pcfg.samples(self.voc_rate)
         scfg = shape_rule.as_config(shape)
         if scfg is not None:
             if not self.shape_on:
@@ -1503,7 +1548,78 @@ class DecodeSessions(ParkingPool):
         self.fade[s], self.has_tail[s] = crossfade_samples, False
         self.tq[s], self.handed[s], self.tone_samples[s] = [], 0, 0
         self._shape_adopt(s, scfg)
+        self._pace_adopt(s, pcfg)
         return s
+
+    # -- pacing: the speaking rate of a reply (utils/pace.py) ----------------------------------------------------------------------
+    def _pace_adopt(self, s: int, cfg, requests=(), base=None, ints=pace_rule.FRESH) -> None:
+        self.pcfg[s], self.preq[s], self.pbase[s] = cfg, [tuple(r) for r in requests], cfg.initial_permille if cfg and base is None else base or 0
+        self.pints[s], self._pace_n[s] = tuple(ints), 0
+        if cfg is not None:
+            H = cfg.samples(self.voc_rate)[0]
+            if H not in self._pw_off:
+                self._pw_off[H], self._pw_floats = self._pw_floats, self._pw_floats + H
+                if self.buf is not None:
+                    self._upload_pace_weights([H])
+
+    def _upload_pace_weights(self, hops) -> None:
+        arena = self.buf["pace_w"]
+        if arena.numel() < self._pw_floats:            # grow: the tables keep their offsets
+            grown = torch.zeros(2 * self._pw_floats, dtype=torch.float32, device=arena.device)
+            grown[:arena.numel()] = arena
+            self.buf["pace_w"] = arena = grown
+        for h in hops:
+            arena[self._pw_off[h]:self._pw_off[h] + h] = torch.tensor(pace_rule.weight_table(h))
+
+    def _pacing(self, slot: int, what: str) -> pace_rule.PaceConfig:
+        if not self.pace_on:
+            raise ValueError(f"{what} on a pool built without pace=True: it has no rows to hold a reply's samples in")
+        self._check_open(slot)
+        if self.pcfg[slot] is None:
+            raise ValueError(f"{what}: slot {slot} was opened without pace=")
+        return self.pcfg[slot]
+
+    def pace_fed(self, slot: int) -> int:
+        """input samples -- the slot's speech at the vocoder's rate, cross-faded where the session fades -- its pacer has taken:
+        "now" of set_pace"""
+        self._pacing(slot, "pace_fed")
+        return self.pints[slot][3]
+
+    def set_pace(self, slot: int, permille: int, at_sample: Optional[int] = None) -> int:
+        """speak at `permille` of the unchanged speed (500 .. 2000; 1500 is one and a half times as fast) from input sample
+        at_sample of the slot's pacer on -> that position.  at_sample=None is "now", pace_fed(slot); an explicit one lies at or
+        beyond that and not before an earlier request's.  The rate of an output frame is the one in force where the frame before
+        it was cut (utils/pace.py), so a request takes hold within about two hops.  No device call.  ValueError, nothing queued:
+        a pool or a session without the option, a rate outside [500, 2000], a position outside those bounds, a ninth live
+        request."""
+        self._pacing(slot, "set_pace")
+        fed = self.pints[slot][3]
+        after = max([fed] + [r[0] for r in self.preq[slot]])
+        request = pace_rule.check_request((fed if at_sample is None else at_sample, permille), fed, after)
+        if len(self.preq[slot]) >= pace_rule.MAX_REQUESTS:
+            raise ValueError(f"slot {slot}: {len(self.preq[slot])} rate requests are live, a ninth is refused")
+        self.preq[slot] = self.preq[slot] + [request]
+        return request[0]
+
+    def paced(self) -> Dict[int, pace_rule.PaceReport]:
+        """{slot: PaceReport} of every open pacing session: ONE device-to-host copy of the rows' headers"""
+        if not self.pace_on:
+            raise ValueError("paced on a pool built without pace=True")
+        slots = [s for s in self.open_slots if self.pcfg[s] is not None]
+        live = [s for s in slots if not self._fresh[s]] if self.buf is not None else []
+        table = self.buf["pace"][:, :pace_rule.HEADER].cpu() if live else None
+        zero = torch.zeros(pace_rule.HEADER, dtype=torch.int32)
+        return {s: pace_rule.report(table[s] if s in live else zero, self.pcfg[s].initial_permille) for s in slots}
+
+    def pace_frames(self, slot: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(offset, score) of the frames the slot's last push completed: device views (n,), int32 p - a and fp32 q, valid until
+        the slot's next push"""
+        self._pacing(slot, "pace_frames")
+        if self.buf is None or self._fresh[slot]:
+            dev = self._device()
+            return torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.float32, device=dev)
+        n = self._pace_n[slot]
+        return self.buf["pace_off"][slot, :n], self.buf["pace_score"][slot, :n]
 
     # -- shaping: output gain, ducking, a limiter and a clean stop (utils/shape.py) ---------------------------------------------
     def _shape_adopt(self, s: int, cfg, segments=(), base=None, fed: int = 0, hold: int = 0, end=None) -> None:
@@ -1619,6 +1735,8 @@ class DecodeSessions(ParkingPool):
         if not self.tones_on:
             raise ValueError("send_tones on a pool built without tones=True: it has no tone tables")
         self._check_open(slot)
+        if self.pcfg[slot] is not None:
+            raise ValueError(f"slot {slot} paces its reply: tones must not be stretched, and a pacing session sends none")
         program = self._check_tones(tone_rule.check_program(program, self.voc_rate), self.rate[slot])
         sch, f = self.sched[slot], self.geo.factor
         frames, last = sch.tokens * f, self.tq[slot][-1][0] // self.up if self.tq[slot] else 0
@@ -1673,6 +1791,7 @@ class DecodeSessions(ParkingPool):
         super().drop(slot)
         self.tq[slot], self.tone_samples[slot] = [], 0      # what the session had not sent is gone with it
         self._shape_adopt(slot, None)
+        self._pace_adopt(slot, None)
 
     def set_lookahead(self, slot: int, lookahead_frames: int) -> None:
         """the look-ahead of an open early session from its next push on.  What has left never comes back: raising it pauses the
@@ -1737,7 +1856,7 @@ class DecodeSessions(ParkingPool):
         if self.shape_on:                             # dmel_shape_items: a state row per slot, the row the tone launch splices a shaping
             #                                           slot's piece into, the row its route reads the shaped samples from, the
             #                                           per-block outputs, the table and the arena of gain ramps
-            w = self.cap * self.up + self.max_tone
+            w = self.chain_w
             self.buf.update(shape=torch.zeros(S, shape_rule.HEADER + self.shape_room, dtype=torch.int32, device=dev),
                             shape_out=torch.empty(S, w + self.shape_room, dtype=torch.float32, device=dev),
                             shape_peak=torch.zeros(S, (w + self.shape_room) // shape_rule.MIN_BLOCK + 2, dtype=torch.float32, device=dev),
@@ -1747,6 +1866,17 @@ class DecodeSessions(ParkingPool):
             if self.tones_on:
                 self.buf["shape_in"] = torch.empty(S, w, dtype=torch.float32, device=dev)
             self._upload_shape_ramps(list(self._sramp_off))
+        if self.pace_on:                              # dmel_pace_items: a state row per slot, the row its route (or its shaper) reads the
+            #                                           paced samples from, the per-frame outputs, the table and the arena of weights
+            w = pace_rule.max_out(self.cap * self.up + self.fade_max, pace_rule.MAX_HOP, pace_rule.MAX_SEARCH)
+            frames = pace_rule.max_out(self.cap * self.up + self.fade_max, pace_rule.MIN_HOP, pace_rule.MAX_SEARCH) // pace_rule.MIN_HOP
+            self.buf.update(pace=torch.zeros(S, pace_rule.HEADER + 2 * pace_rule.MAX_HOP + 2 * pace_rule.MAX_SEARCH, dtype=torch.int32, device=dev),
+                            pace_out=torch.empty(S, w, dtype=torch.float32, device=dev),
+                            pace_off=torch.zeros(S, frames, dtype=torch.int32, device=dev),
+                            pace_score=torch.zeros(S, frames, dtype=torch.float32, device=dev),
+                            pace_tab=torch.empty(pace_rule.TABLE_WORDS * S, dtype=torch.int32, device=dev),
+                            pace_w=torch.zeros(max(2 * self._pw_floats, 4 * pace_rule.MAX_HOP), dtype=torch.float32, device=dev))
+            self._upload_pace_weights(list(self._pw_off))
 
     def _slot_views(self, s: int):
         b = self.buf
@@ -1780,7 +1910,38 @@ class DecodeSessions(ParkingPool):
             segs, base = shape_rule.live(self.sreq[s], self.sbase[s], self.sfed[s])
             meta.update(shape=self.scfg[s].as_dict(), shape_segments=[list(sg) for sg in segs], shape_base=base, shape_fed=self.sfed[s],
                         shape_hold=self.shold[s], shape_end=self.send[s])
+        if self.pcfg[s] is not None:                  # only a pacing session carries the keys: the others' snapshots are unchanged
+            meta.update(pace=self.pcfg[s].as_dict(), pace_ints=list(self.pints[s]), pace_requests=[list(r) for r in self.preq[s]],
+                        pace_base=self.pbase[s])
         return meta
+
+    def _park_pace(self, meta: Mapping):
+        """(the pacing config a snapshot carries (None: none), its live requests, the rate in force, its integers); ValueError
+        where they are none this pool can continue"""
+        if meta.get("pace") is None:
+            return None, [], None, pace_rule.FRESH
+        if not self.pace_on:
+            raise ValueError("a pacing session into a pool built without pace=True")
+        try:
+            cfg = pace_rule.PaceConfig.from_dict(meta["pace"])
+        except TypeError as e:
+            raise ValueError(f"the pace config of the snapshot is not a PaceConfig: {e}") from None
+        H, D = cfg.samples(self.voc_rate)
+        ints, base, raw = (meta.get(k) for k in ("pace_ints", "pace_base", "pace_requests"))
+        ok = isinstance(ints, (list, tuple)) and len(ints) == 4 and all(isinstance(v, int) and not isinstance(v, bool) and v >= 0 for v in ints)
+        if ok:
+            K, a_prev, a_next, fed = ints
+            ok = (a_prev == a_next == 0) if K == 0 else (H // 2 <= a_next - a_prev <= 2 * H and a_next <= fed + 2 * H)
+        if not ok:
+            raise ValueError(f"the pacer's integers of the snapshot are none the rule makes: {ints!r}")
+        pace_rule.check_permille(base)
+        if not isinstance(raw, (list, tuple)) or len(raw) > pace_rule.MAX_REQUESTS:
+            raise ValueError(f"the rate requests of the snapshot are no list of at most {pace_rule.MAX_REQUESTS} (P, permille): {raw!r}")
+        reqs, after = [], 0
+        for q in raw:
+            reqs.append(pace_rule.check_request(tuple(q) if isinstance(q, (list, tuple)) else q, 0, after))
+            after = reqs[-1][0]
+        return cfg, reqs, base, tuple(ints)
 
     def _park_shape(self, meta: Mapping):
         """(the shaping config a snapshot carries (None: none), its live segments, base gain, samples fed, samples held, end);
@@ -1843,7 +2004,10 @@ class DecodeSessions(ParkingPool):
                  ("fade_tail", 1, meta["fade"] if meta["has_tail"] else 0), ("resampler", 1, rs["fill"] if rs else 0)] +
                 # the shaper's row: header and hold; a session that has fed no sample owns the zeroed row: nothing
                 ([("shape", 1, shape_rule.ShapeConfig.from_dict(meta["shape"]).state_words(self.voc_rate) if meta["shape_fed"] > 0 else 0)]
-                 if meta.get("shape") is not None else []))
+                 if meta.get("shape") is not None else []) +
+                # the pacer's row: header and held samples, likewise
+                ([("pace", 1, pace_rule.PaceConfig.from_dict(meta["pace"]).state_words(self.voc_rate) if meta["pace_ints"][3] > 0 else 0)]
+                 if meta.get("pace") is not None else []))
 
     def _park_rows(self, s: int) -> Dict[str, torch.Tensor]:
         b = self.buf
@@ -1856,6 +2020,8 @@ class DecodeSessions(ParkingPool):
             rows["resampler"] = self.rs.buf["rows"][s:s + 1]
         if self.shape_on:
             rows["shape"] = b["shape"][s:s + 1]
+        if self.pace_on:
+            rows["pace"] = b["pace"][s:s + 1]
         return rows
 
     def _park_widths(self):
@@ -1878,6 +2044,7 @@ class DecodeSessions(ParkingPool):
             raise ValueError("the schedule's fade_frames do not go with the session's cross-fade")
         self._park_tones(meta)
         self._park_shape(meta)
+        self._park_pace(meta)
         lo = meta["window"][0]
         if sc.tokens * f - lo + self.max_push * f > self.cap:
             raise ValueError(f"the frames [{lo}, {sc.tokens * f}) and one maximal push ({self.max_push * f} frames) do not fit the "
@@ -1904,6 +2071,7 @@ class DecodeSessions(ParkingPool):
                 self._sramp_off[sg[3]], self._sramp_floats = self._sramp_floats, self._sramp_floats + sg[3]
                 if self.buf is not None:
                     self._upload_shape_ramps([sg[3]])
+        self._pace_adopt(s, *self._park_pace(meta))
 
     def _prepare_slot(self, s: int) -> None:
         super()._prepare_slot(s)
@@ -1911,6 +2079,8 @@ class DecodeSessions(ParkingPool):
             self.buf["fade_w"][s, :self.fade[s]] = crossfade.weights(self.fade[s]).to(self.buf["fade_w"].device)
         if self.shape_on:
             self.buf["shape"][s].zero_()              # the fresh shaper state
+        if self.pace_on:
+            self.buf["pace"][s].zero_()               # the fresh pacer state
 
     # -- one step ----------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -1934,9 +2104,11 @@ class DecodeSessions(ParkingPool):
             # a slot with a look-ahead emits by its own rule, from its shadow row when that ran ahead of the committed one
             steps = {s: early.get(s, st) for s, st in steps.items()}
             row = {s: self.S + s if s in shadows else s for s in steps}
-            self._held, self._ending, self._shape_src = {}, final, {}
+            self._held, self._ending, self._shape_src, self._pace_src = {}, final, {}, {}
             out, pieces, wire = self._emit(steps, row, final, dev)
             self._flush_tails(steps, final, out, pieces, wire)
+            if self.pace_on:
+                self._pace(steps, final, out, pieces, wire, dev)
             placed = self.tones_on and self._tones(steps, final, out, pieces, wire, dev)
             if self.shape_on:
                 self._shape(steps, final, out, pieces, wire, dev, placed)
@@ -2047,6 +2219,9 @@ class DecodeSessions(ParkingPool):
             if self.tq[s] and (s in self._ending or self.tq[s][0][0] <= self.handed[s]):
                 self._held[s] = piece[0]
                 return
+        if self.pcfg[s] is not None:                  # a pacing slot's piece is the pacer's source; its route takes what that emits
+            self._pace_src[s] = piece[0]
+            return
         if self.scfg[s] is not None:                  # a shaping slot's piece is the shaper's source; its route takes what that emits
             self._shape_src[s] = piece[0]
             return
@@ -2104,6 +2279,41 @@ class DecodeSessions(ParkingPool):
             if self.has_tail[s] and s in steps:
                 self._route(s, self.buf["fade_tail"][s, :self.fade[s]][None], out, pieces, wire)
                 self.has_tail[s] = False
+
+    def _pace(self, steps, final, out, pieces, wire, dev) -> None:
+        """pace: ONE dmel_pace_items launch takes, for every pacing slot of the step with a new piece or its end, the piece (as the
+        vocoder, the cross-fade or the flushed fade tail left it) through the pacer, and writes the samples that leave -- advance()
+        of them, known from integers -- where the slot's route reads them: its row of a staging buffer (the shaper's source where
+        the session shapes; else the resampler copies it -- or the tone launch places it behind the tail with the step's other
+        chunks --, or the convert launch reads it), or a fresh tensor that is handed out."""
+        members = [s for s in steps if self.pcfg[s] is not None and (s in final or (s in self._pace_src and self._pace_src[s].shape[0]))]
+        if not members:
+            return
+        b, S = self.buf, self.S
+        src, dst, cfgs, reqs, fin = [None] * S, [None] * S, [None] * S, [[] for _ in range(S)], [False] * S
+        ints, base = [pace_rule.FRESH] * S, [None] * S
+        for s in members:
+            cfg, x = self.pcfg[s], self._pace_src.get(s)
+            n = 0 if x is None else x.shape[0]
+            H, D = cfg.samples(self.voc_rate)
+            m = pace_rule.advance(self.pints[s], self.preq[s], n, s in final, H, D, self.pbase[s])[2]
+            if self.scfg[s] is not None:
+                d = self._shape_src[s] = b["pace_out"][s, :m]
+            elif self._converts(s):
+                d = b["pace_out"][s, :m]
+                if m or s in final:
+                    pieces[s] = d
+            elif self._wired(s):
+                d = wire[s] = b["pace_out"][s, :m]
+            else:
+                d = torch.empty(1, m, dtype=torch.float32, device=dev)
+                out[s], d = (d, out[s][1]), d[0]
+            src[s], dst[s], cfgs[s], reqs[s], ints[s], base[s], fin[s] = x if n else None, d, cfg, self.preq[s], self.pints[s], self.pbase[s], s in final
+        _, after, frames = pace_rule.pace_items(src, dst, cfgs, reqs, ints, fin, b["pace"], b["pace_off"], b["pace_score"], self.voc_rate,
+                                                weights=b["pace_w"], weight_off=self._pw_off, table=b["pace_tab"], initial=base)
+        for s in members:                             # behind the launch: a refused launch changes no count
+            self.pints[s], self._pace_n[s] = after[s], frames[s]
+            self.preq[s], self.pbase[s] = pace_rule.live(self.preq[s], self.pbase[s], after[s][2])
 
     def _tones(self, steps, final, out, pieces, wire, dev) -> bool:
         """tones: ONE dmel_tone_items launch composes, for every slot with a request that is due -- its anchor P lies at or in front

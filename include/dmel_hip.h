@@ -762,6 +762,51 @@ int dmel_shape_items(float* const* dst /*entries nullable*/, const int64_t* dst_
                      const float* ramps /*nullable when ramp_floats == 0*/, int64_t ramp_floats, void* state /* (S, state_pitch) words */,
                      int64_t state_pitch, float* out_peak, float* out_gain, int64_t out_pitch, void* table_scratch, void* stream);
 
+/* The speaking rate of S decode sessions in ONE launch (csrc/small_ops.hip): WSOLA time-scaling of codec-rate speech, the rule of
+ * dmel_codec_amd/utils/pace.py (scan), bit for bit; fp32 throughout, every operation rounded on its own, IEEE divisions, every sum
+ * in the sum8 order of dmel_echo_items.  Slot s takes n_new[s] new fp32 samples at src[s] (any 4-byte offset) as x[fed ...] and writes
+ * the samples the step hands out to dst[s] (ANOTHER buffer than src[s]: the counts differ; any 4-byte offset).  flags[s]: bit 0 final
+ * (the stream's last step).  It carries one row of state_pitch 4-byte words in `state`: a header of 16 words -- int32 0 K, 1 p_{K-1},
+ * 2 a_{K-1}, 3 a_K, 4 fed, 5 hold, 6 natural, 7 searched, 8 quiet, 9 out, 10 last offset; fp32 11 last q; int32 12 the rate that placed
+ * a_K; 13 .. 15 reserved and not written -- and 2 H + 2 D floats: the held samples x[fed - hold, fed), oldest first, zeros behind them.
+ * A zeroed row is a fresh session.  ints row s is (K, a_{K-1}, a_K, fed, hold), the HOST's integers (the caller tracks them from the
+ * rule's integer helpers; the kernel trusts them and writes them back); p_{K-1} and the counters are the row's.
+ *   Frames: output frame k has the nominal position a_k, a_0 = 0, a_{k+1} = a_k + (H r + 500) / 1000 with r the rate in force at input
+ * position a_k: that of the last of the slot's req_count[s] <= 8 request records -- two int32 at reqs[(8 s + j) * 2]: position relative
+ * to the launch's first new sample (may be negative, non-decreasing in j) and permille -- with position <= a_k - fed, else
+ * base_permille[s].  A step that is not final computes frame 0 when fed + n_new >= H and frame k >= 1 when fed + n_new >=
+ * max(a_{k-1} + 2 H, a_k + H) + D; a final step computes every frame with a_k < fed + n_new, and its last frame hands out
+ * min(H, fed + n_new - a_k) samples; every other frame hands out H.  Samples at or behind fed + n_new read as 0.0.
+ *   Frame 0 is x[0 : H].  Frame k >= 1, t = p_{k-1} + H, old[i] = x[t + i]:  a_k - D <= t <= a_k + D: p_k = t (natural += 1);  else
+ * e0 = sum8(old * old) < floor: p_k = a_k (quiet += 1);  else for every d in [-D, D] with c = a_k + d >= 0, b[i] = x[c + i]:
+ * cc = sum8(old * b), e = sum8(b * b), q = cc > 0 ? (cc * cc) / (e + eps) : 0, and p_k = a_k + d for the d with the largest q, among
+ * equal values the smallest |d|, then the negative one (searched += 1).  Sample i of the frame: p_k == t: old;  else m = x[p_k + i] -
+ * old, m = W[i] * m, y = old + m, W the H floats at weights + weight_off[s]: W[i] = fp32(0.5 - 0.5 cos(pi (i + 0.5) / H)), computed by
+ * the caller in float64.  out_offset[s * out_pitch + j] = p - a and out_score[s * out_pitch + j] = q (0 unless searched) for the j-th
+ * frame the launch completed.  Behind the step the row holds x[keep, fed + n_new), keep = max(0, min(a_{K-1} + H, a_K) - D) (0 while
+ * K == 0); a final step keeps nothing.  fparams row s is (floor, eps).  n_new[s] == 0 without final is an idle slot: neither its rows
+ * nor its parameters are looked at; when every slot is idle the call returns DMEL_OK and launches nothing.  NaN and infinite input
+ * are outside the contract.  DMEL_EINVAL, nothing launched, dmel_last_error naming the item: S outside [1, 65535], a NULL table, a
+ * negative weight_floats, state, out_offset, out_score or weights not 4-byte aligned, table_scratch not 8-byte aligned, state_pitch
+ * below 16 or a negative out_pitch, n_new[s] outside [0, 2^26], flags[s] outside [0, 1], H[s] outside [64, 512] or no multiple of 8,
+ * D[s] outside [0, 512], hold AT OR ABOVE 2 H + 2 D, state_pitch below 16 + 2 H + 2 D, fed below hold or above 2^30, integers the rule
+ * cannot have made (K < 0; K == 0 with a_K != 0; a_K - a_{K-1} outside [H / 2, 2 H]; a_K above fed + 2 H), a dst or src that is not
+ * 4-byte aligned, a floor that is not finite and >= 0 or an eps that is not finite and positive, a base rate or a request's rate
+ * outside [500, 2000], more than 8 requests, a request position outside [-2^30, 2^30] or below the one before, a weight table beyond
+ * weight_floats, out_pitch below the frames the step completes, dst_cap[s] BELOW THE SAMPLES THE STEP HANDS OUT, a NULL dst where
+ * samples leave or src where n_new > 0.  OVERLAP IS THE CALLER'S CONTRACT, as in dmel_tone_items.  The per-slot arguments are HOST
+ * tables, copied as launch arguments into table_scratch (64 S 4-byte words of device memory, 8-byte aligned): the caller may
+ * overwrite them as soon as the call returns.  One workgroup of eight waves per slot, its frames in order; a window of 6144 samples
+ * of the slot's stream sits in LDS and is re-filled as the frames advance; in a searched frame the work items are (candidate, sum8
+ * segment) pairs spread over the workgroup, joined per candidate by the fixed tree, and the argmax is a reduction over (q, |d|, d)
+ * keys.  Plain vector stores, no atomics.  One profile record per launch in the family "pace" (time and bytes in "small"). */
+int dmel_pace_items(float* const* dst /*entries nullable*/, const int64_t* dst_cap, const float* const* src /*entries nullable*/,
+                    const int64_t* n_new, const int64_t* ints /* S x 5 */, const int32_t* flags, const int32_t* H, const int32_t* D,
+                    const float* fparams /* S x 2 */, const int32_t* base_permille, const int32_t* req_count,
+                    const int32_t* reqs /* S x 8 x 2 words */, int S, const float* weights, int64_t weight_floats,
+                    const int32_t* weight_off, void* state /* (S, state_pitch) words */, int64_t state_pitch, int32_t* out_offset,
+                    float* out_score, int64_t out_pitch, void* table_scratch, void* stream);
+
 /* R independent 2-D copies of 4-byte words in ONE launch (csrc/small_ops.hip): what takes the streaming state of live sessions out of
  * a pool's buffers into a snapshot and back (models/stream_sessions.py: snapshot / restore).  Descriptor r copies rows[r] rows of
  * cols[r] words: row i goes from src[r] + i * src_pitch[r] to dst[r] + i * dst_pitch[r], pitches in words.  Packing reads windows of

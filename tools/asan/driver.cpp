@@ -856,6 +856,55 @@ int main() {
       NN[0] = NN[2] = 0; FL[2] = 0;               // every item idle
       CK(shape());
     }
+    {
+      // speaking rate: tables of exactly S entries, 5 S integers, 2 S float parameters, a request table of exactly 8 * 2 S words, a table
+      // scratch of exactly 64 S words; its refusals read the host tables only.  Plain vectors, as above
+      const int S0 = 3, Hh = 64, Dd = 8;
+      std::vector<float> out(4096, 0.f), in(4096, 0.25f), wts(Hh, 0.5f), sc(S0 * 16);
+      std::vector<int32_t> off(S0 * 16);
+      std::vector<uint32_t> st((size_t)S0 * (16 + 2 * Hh + 2 * Dd), 0u), tab(64 * S0);
+      float* DST[S0] = {out.data() + 1, nullptr, out.data() + 2001};
+      const float* SRC[S0] = {in.data() + 3, nullptr, in.data() + 1002};
+      int64_t CAP[S0] = {640, -1, 128}, NN[S0] = {640, 0, 100};
+      // item 0 continues (K = 3, a_2 = 160, a_3 = 240, 400 fed, 100 held), item 1 is idle, item 2 is a whole short stream (final)
+      int64_t IV[S0 * 5] = {3, 160, 240, 400, 100, -1, -1, -1, -1, -1, 0, 0, 0, 0, 0};
+      int32_t FL[S0] = {0, 0, 1}, HH[S0] = {Hh, -5, Hh}, DD[S0] = {Dd, -5, 0}, BP[S0] = {1250, 0, 2000}, RC[S0] = {2, 99, 0};
+      int32_t WO[S0] = {0, -7, 0};
+      float FP[S0 * 2] = {1e-6f, 1e-12f, 0, 0, 0.f, 1e-12f};
+      int32_t RQ[S0 * 8 * 2] = {-50, 1500, 300, 700};
+      int S = S0;
+      int64_t wfloats = Hh, pitch = 16 + 2 * Hh + 2 * Dd, out_pitch = 16;
+      auto pace = [&]() { return dmel_pace_items(DST, CAP, SRC, NN, IV, FL, HH, DD, FP, BP, RC, RQ, S, wts.data(), wfloats, WO, st.data(), pitch,
+                                                 off.data(), sc.data(), out_pitch, tab.data(), nullptr); };
+      CK(pace());
+      auto refused = [&](const char* item, const char* what) {
+        const int rc = pace();
+        if (rc != DMEL_EINVAL || !std::strstr(dmel_last_error(), item)) { std::printf("FAIL pace_items accepted %s (%d: %s)\n", what, rc, dmel_last_error()); ++failures; }
+      };
+      S = 0; refused("0 items", "no item");
+      S = S0; HH[0] = 56; refused("item 0", "a hop of 56 samples");
+      HH[0] = 68; refused("item 0", "a hop that is no multiple of 8");
+      HH[0] = Hh; DD[0] = 513; refused("item 0", "a search half-width of 513 samples");
+      DD[0] = Dd; BP[0] = 499; refused("item 0", "a rate of 499 permille");
+      BP[0] = 1250; RQ[3] = 2001; refused("item 0", "a request at 2001 permille");
+      RQ[3] = 700; RQ[2] = -51; refused("item 0", "a request position below the one before");
+      RQ[2] = 300; RC[0] = 9; refused("item 0", "nine requests");
+      RC[0] = 2; IV[4] = 2 * Hh + 2 * Dd; refused("item 0", "a hold of 2 H + 2 D samples");
+      IV[4] = 100; pitch = 16 + 2 * Hh + 2 * Dd - 1; refused("item 0", "a state row shorter than header and hold");
+      pitch = 16 + 2 * Hh + 2 * Dd; CAP[0] = 63; refused("item 0", "a destination shorter than what the step hands out");
+      CAP[0] = 640; out_pitch = 1; refused("item 0", "an output pitch below the frames the step completes");
+      out_pitch = 16; IV[2] = 160 + 2 * Hh + 1; refused("item 0", "integers the rule cannot have made");
+      IV[2] = 240; IV[12] = 5; refused("item 2", "a fresh slot with a_K = 5");
+      IV[12] = 0; SRC[2] = nullptr; refused("item 2", "a NULL source");
+      SRC[2] = in.data() + 1002; FP[4] = -1.f; refused("item 2", "a negative floor");
+      FP[4] = 0.f; FP[1] = NAN; refused("item 0", "an eps that is not a number");
+      FP[1] = 1e-12f; WO[2] = 1; refused("item 2", "a weight table that ends behind the arena");
+      WO[2] = 0; FL[2] = 2; refused("item 2", "flags above 1");
+      FL[2] = 1;
+      CK(pace());
+      NN[0] = NN[2] = 0; FL[2] = 0;               // every item idle
+      CK(pace());
+    }
     auto xs = buf(2 * 8 * 3000), ys = buf(2 * 8 * 3000), da = buf(8), db = buf(8);
     CK(dmel_aa_snake_f32(xs.data(), ys.data(), al.data(), be.data(), taps.data(), taps.data(), 1, 2, 8, 3000, nullptr));
     CK(dmel_aa_snake_backward_f32(xs.data(), ys.data(), xs.data(), al.data(), be.data(), da.data(), db.data(), taps.data(), taps.data(), 1, 2, 8, 3000, nullptr));

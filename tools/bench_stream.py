@@ -81,7 +81,15 @@ step time of each and the launch records of one step ("tones", "small", "pcm_con
 runs only this: S replies in steady state (16-token pushes) in three pools interleaved in one process -- decode_sessions() without the
 option, decode_sessions(shape=True) with no shaping slot, and the same with every slot opened with shape=True at +6 dB: the step time
 of each, the launch records of one step ("shape", "small", "pcm_convert") and the time of the dmel_shape_items launch alone, APPENDED
-to --out."""
+to --out.
+
+    python tools/bench_stream.py --sessions 16 --pace 1250 [--steps 40] [--out profiles/sessions_pace.txt]
+
+runs only this: S replies in steady state (16-token pushes) in three pools interleaved in one process -- decode_sessions() without the
+option, decode_sessions(pace=True) with every slot pacing at 1000 (no search), and the same at the given rate (one, or a comma list
+assigned round-robin): the step time of each, the launch records of one step ("pace", "small") and, below them, the
+dmel_pace_items launch alone on 16384 new samples per slot at 1000 and at the first rate given, dmel_shape_items on the same samples
+and one vocoder call of a step's batch for scale, APPENDED to --out."""
 import json, math, os, statistics, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -802,6 +810,126 @@ def sessions_shape_section(S, rate, fmt, steps, out):
     print("\n".join(table), file=sys.stderr)
     print(json.dumps(result))
 
+
+def sessions_pace_section(S, rates, steps, out):
+    """three pools interleaved in one process: decode_sessions() as it was, decode_sessions(pace=True) with every slot pacing at 1000,
+    and the same with the slots at `rates`, round-robin; below them the launches alone"""
+    from dmel_codec_amd import _lib
+    from dmel_codec_amd.utils import pace as pace_rule, shape as shape_rule
+    chunk, warmup = 16, 8
+    gl = torch.Generator().manual_seed(8)
+    G, Cn = codec.dmel_groups, codec.decoder.input_channels
+    n_steps = warmup + steps
+    ids = torch.randint(0, 175, (S, G, chunk * n_steps), generator=gl, dtype=torch.int32).to(dev)
+    kw = dict(max_push_tokens=chunk)
+    pools = {"no_pace_pool": codec.decode_sessions(S, **kw), "pace_pool_1000": codec.decode_sessions(S, pace=True, **kw),
+             "pace_pool_rate": codec.decode_sessions(S, pace=True, **kw)}
+    slots = {k: [p.open(**(dict(pace=True) if k != "no_pace_pool" else {})) for _ in range(S)] for k, p in pools.items()}
+    for i, s in enumerate(slots["pace_pool_rate"]):
+        pools["pace_pool_rate"].set_pace(s, rates[i % len(rates)])
+    ms, launches, samples = {k: [] for k in pools}, {k: {} for k in pools}, {k: 0 for k in pools}
+    keys, families = list(pools), ("pace", "small")
+    for j in range(n_steps):
+        noise = [torch.randn(Cn, chunk * 4, device=dev) for _ in range(S)]
+        counted = j == n_steps - 1                                          # the launch records of the last step, which is not timed
+        for k in (keys if j % 2 == 0 else keys[::-1]):                      # no pool always goes first
+            pool = pools[k]
+            if counted:
+                _lib.prof_reset(); _lib.prof_enable(True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = pool.push({s: ids[i, :, j * chunk:(j + 1) * chunk] for i, s in enumerate(slots[k])},
+                            noise={s: noise[i] for i, s in enumerate(slots[k])})
+            torch.cuda.synchronize()
+            if counted:
+                launches[k] = {f: _lib.prof_read(f)["launches"] for f in families}
+                _lib.prof_enable(False); _lib.prof_reset()
+            elif j >= warmup:
+                ms[k].append((time.perf_counter() - t0) * 1e3)
+            samples[k] += sum(a.numel() for a, _ in res.values())
+    pct = lambda v, q: sorted(v)[min(len(v) - 1, int(q * len(v)))]
+    result, rows = {"sessions": S, "chunk_tokens": chunk, "rates": rates}, []
+    for k in keys:
+        v = ms[k]
+        result[k] = {"median_ms": round(statistics.median(v), 3), "p10_ms": round(pct(v, 0.1), 3), "p90_ms": round(pct(v, 0.9), 3), "n": len(v),
+                     "launches_per_step": launches[k], "audio_samples": samples[k]}
+        rows.append(f"{S:8d}  {k:16s}  {statistics.median(v):9.3f}  {pct(v, 0.1):9.3f}  {pct(v, 0.9):9.3f}  {len(v):4d}  "
+                    f"{launches[k]['pace']:4d}  {launches[k]['small']:5d}  {samples[k]:13d}")
+    reports = pools["pace_pool_rate"].paced()
+    result["frames"] = {f: sum(getattr(r, f) for r in reports.values()) for f in ("natural", "searched", "quiet")}
+
+    def timed(fn, before=lambda: None):
+        v = []
+        for j in range(warmup + steps):
+            before()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if j >= warmup:
+                v.append((time.perf_counter() - t0) * 1e3)
+        return {"median_ms": round(statistics.median(v), 4), "p10_ms": round(pct(v, 0.1), 4), "p90_ms": round(pct(v, 0.9), 4)}
+
+    # the launches alone: S slots of 16384 new samples, fresh rows every time
+    n, vr = 16384, pools[keys[0]].voc_rate
+    x = (torch.randn(S, n, device=dev) * 0.3).contiguous()
+    alone = {}
+    for r in (1000, rates[0]):
+        cfg = pace_rule.PaceConfig(initial_permille=r)
+        H, D = cfg.samples(vr)
+        y = torch.empty(S, pace_rule.max_out(n, H, D), device=dev)
+        st = torch.zeros(S, cfg.state_words(vr), dtype=torch.int32, device=dev)
+        off, sc = torch.zeros(S, 2 * n // H + 8, dtype=torch.int32, device=dev), torch.zeros(S, 2 * n // H + 8, device=dev)
+        tab = torch.empty(pace_rule.TABLE_WORDS * S, dtype=torch.int32, device=dev)
+        w, woff = pace_rule.weight_arena([H], dev)
+        alone[f"pace_items_{r}"] = timed(lambda: pace_rule.pace_items([x[s] for s in range(S)], [y[s] for s in range(S)], [cfg] * S, [[]] * S,
+                                                                      [pace_rule.FRESH] * S, [False] * S, st, off, sc, vr, w, woff, tab),
+                                         st.zero_)
+        alone[f"pace_items_{r}"]["searched_frames_per_slot"] = int(st[0, pace_rule.I_SEARCHED])
+    scfg = shape_rule.ShapeConfig()
+    y = torch.empty(S, n + 2 * shape_rule.MAX_BLOCK, device=dev)
+    st = torch.zeros(S, scfg.state_words(vr), dtype=torch.int32, device=dev)
+    pk, gn = torch.zeros(S, n // 32 + 2, device=dev), torch.zeros(S, n // 32 + 2, device=dev)
+    tab = torch.empty(shape_rule.TABLE_WORDS * S, dtype=torch.int32, device=dev)
+    ramps, off = shape_rule.ramp_arena([480], dev)
+    alone["shape_items"] = timed(lambda: shape_rule.shape_items([x[s] for s in range(S)], [y[s] for s in range(S)], [scfg] * S,
+                                                                [[(0, 1.0, 2.0, 480)]] * S, [1.0] * S, [0] * S, [0] * S, [False] * S, st, pk, gn,
+                                                                vr, ramps=ramps, ramp_off=off, table=tab), st.zero_)
+    halo = pools[keys[0]].geo.voc_halo
+    mel = torch.randn(S, codec.decoder.output_channels, chunk * 4 + 2 * halo, device=dev)
+    with torch.no_grad():
+        alone["vocoder_call_of_a_step"] = timed(lambda: codec.vocoder(mel))
+    result["alone"] = alone
+    med = [result[k]["median_ms"] for k in keys]
+    searched, voc = alone[f"pace_items_{rates[0]}"]["median_ms"], alone["vocoder_call_of_a_step"]["median_ms"]
+    verdict = (f"every slot pacing at 1000 {med[1] - med[0]:+.3f} ms, at {','.join(map(str, rates))} {med[2] - med[0]:+.3f} ms against the pool "
+               f"without the option (new work: no threshold); the searched launch alone costs {searched:.4f} ms, "
+               + ("MORE than" if searched > voc else "less than") + f" the vocoder call of a step's batch ({voc:.4f} ms)")
+    table = [f"{S} decode sessions, {chunk}-token pushes, f32 audio at the vocoder's rate, 100 mel / 10 groups, BigVGAN base "
+             f"(tools/bench_stream.py --sessions {S} --pace {','.join(map(str, rates))})",
+             f"per-step wall time incl. host synchronisation, {steps} steady-state steps, the three pools interleaved in one process;",
+             "no_pace_pool = decode_sessions() as it was; pace_pool_1000 = decode_sessions(pace=True), every slot opened with pace=True at 1000; "
+             "pace_pool_rate = the same with set_pace at the rates given",
+             "launch records of one step: pace (dmel_pace_items), small (all small kernels, the pace launch among them); samples handed out",
+             "sessions  pool              median ms     p10 ms     p90 ms     n  pace  small  audio samples"] + rows + [
+             f"frames of pace_pool_rate over the run: {result['frames']}",
+             f"launches alone, {S} slots of {n} new samples, fresh rows, wall time incl. host synchronisation (median, p10, p90 ms):"] + [
+             f"  {k:24s} {v['median_ms']:9.4f} {v['p10_ms']:9.4f} {v['p90_ms']:9.4f}" +
+             (f"   searched frames per slot: {v['searched_frames_per_slot']}" if "searched_frames_per_slot" in v else "")
+             for k, v in alone.items()] + [verdict]
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "a") as f:
+        f.write("\n".join(table) + "\n\n")
+    print("\n".join(table), file=sys.stderr)
+    print(json.dumps(result))
+
+
+if "--pace" in sys.argv:
+    assert "--sessions" in sys.argv, "--pace needs --sessions"
+    sessions_pace_section(int(arg_after("--sessions")), [int(r) for r in arg_after("--pace").split(",")], int(arg_after("--steps", "40")),
+                          arg_after("--out", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                          "sessions_pace.txt")))
+    sys.exit(0)
 
 if "--shape" in sys.argv:
     assert "--sessions" in sys.argv, "--shape needs --sessions"
