@@ -166,6 +166,7 @@ PROTOTYPES = {
     "dmel_conv_transpose1d_destroy": (None, [vp]),
     "dmel_conv_transpose1d_set_precision": (C.c_int, [vp, C.c_int]),
     "dmel_conv_transpose1d_forward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int64, vp]),
+    "dmel_conv_transpose1d_forward_items": (C.c_int, [vp, vp, vp, C.c_int, C.c_int64, vp, vp]),
     "dmel_conv_post_f32": (C.c_int, [vp, vp, C.c_float, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp]),
     "dmel_conv_post_items_f32": (C.c_int, [vp, vp, C.c_float, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp, vp]),
     "dmel_aa_snake_backward_input_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp]),

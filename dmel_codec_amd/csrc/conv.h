@@ -25,6 +25,14 @@ struct PackDesc {
   SegDesc seg[2];
   int C = 0;               // paired modes: channels C (source rows 2C); LINEAR: rows per phase (Cout)
   int phases = 1;          // LINEAR only: phase-major row blocks (transposed conv)
+  // LINEAR, phases == 1, single segment: row_u = 2, 4 or 8 orders the C rows PHASE-MINOR, m = co * row_u + ph -- a transposed convolution of
+  // stride row_u in one image.  Row m of output column q is sample q * row_u + ph of channel co (C / row_u channels, Tout = Tcols * row_u); the
+  // epilogue stores a lane's consecutive phases with one 8- / 16-byte store (conv_dev.h, epi_phase_tile).  No activation, row scale,
+  // residual, running sum, division, fold or windows.  Source row numbering stays the identity.
+  int row_u = 1;
+  // taps per chunk that hold only zero weights by construction (the union of two tap windows): issued, but left out of the algorithmic
+  // flops and bytes the profiler scope reports
+  int dead_taps = 0;
 };
 
 struct PackedConv {
@@ -155,7 +163,7 @@ template <class FW, class FB> int pack_conv(PackedConv& pc, const PackDesc& d, F
   pc.k_real = 0;
   for (int s = 0; s < d.nseg; ++s) {
     pc.steps += (int)((d.seg[s].Cin + kCK - 1) / kCK) * d.seg[s].taps;
-    pc.k_real += (double)d.seg[s].Cin * d.seg[s].taps;
+    pc.k_real += (double)d.seg[s].Cin * (d.seg[s].taps - (s == 0 ? d.dead_taps : 0));
   }
   auto src_row = [&](int m) -> int {  // packed row -> source row or -1
     if (paired) {

@@ -51,6 +51,7 @@ struct KArgs {
   const int32_t* win;
   int win_stride, win_shift, win_end, win_valid[2];
   int fast;                    // conv_fastpath_enabled() at launch: full tiles / interior chunks of the fp16-split kernels skip the edge code
+  int row_u;                   // PackDesc::row_u: > 1 = phase-minor rows of a stride-row_u transposed convolution (epi_phase_rows)
 };
 
 __device__ __forceinline__ float act_apply(float v, int act) {
@@ -137,6 +138,85 @@ __device__ __forceinline__ void epi_full_tile(const KArgs& a, const floatx16 (&a
   }
 }
 
+// Phase-minor rows (PackDesc::row_u = U: packed row m = co U + ph is sample q U + ph of channel co): one 32 x (32 NT) tile that lies WHOLLY
+// inside the output, in the manner of epi_full_tile.  With rows (r & 3) + 8 (r >> 2) + 4 h in accumulator register r, a lane holds V = min(U, 4)
+// consecutive samples of one channel in V consecutive registers:
+//   U = 8: registers 4 g .. 4 g + 3 are phases 4 h .. 4 h + 3 of channel g of the tile's four    -> one 16-byte store; the two half-waves
+//          interleave, so a wave store is 1 KiB contiguous
+//   U = 4: registers 4 g .. 4 g + 3 are phases 0 .. 3 of channel 2 g + h of the tile's eight    -> one 16-byte store, 512 B per channel
+//   U = 2: registers 2 g, 2 g + 1 are phases 0, 1 of channel (g & 1) + 4 (g >> 1) + 2 h of sixteen -> one 8-byte store, 256 B per channel
+// The channel's row base is wave-uniform (scalar), the lane offset (its h part of the channel, its column, its first phase) one 32-bit
+// value computed once by the caller; the bias is read once per channel; no division, no flag.  The value is acc + bias, as in the edge loop.
+template <int U, int NT>
+__device__ __forceinline__ void epi_phase_tile(const KArgs& a, const floatx16 (&acc)[NT], int mtile, float* yb, uint32_t yoff, uint32_t boff) {
+  constexpr int V = U >= 4 ? 4 : 2;
+  typedef float vecf __attribute__((ext_vector_type(V)));
+  const int ycs = (int)a.y_cs;
+  const float* bias_t = a.bias + mtile;
+  float* yt = yb + (mtile / U) * ycs;
+#pragma unroll
+  for (int g = 0; g < 16 / V; ++g) {
+    const int r0 = g * V, row0 = (r0 & 3) + 8 * (r0 >> 2);        // first register of the group -> row `row0` + 4 h of the tile
+    const float bias = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(bias_t + row0) + lane_off(boff));
+    float* yr = yt + (row0 / U) * ycs;
+    const uint32_t yo = lane_off(yoff);
+#pragma unroll
+    for (int ni = 0; ni < NT; ++ni) {
+      vecf v;
+#pragma unroll
+      for (int j = 0; j < V; ++j) v[j] = acc[ni][r0 + j] + bias;
+      *reinterpret_cast<vecf*>(reinterpret_cast<char*>(yr + ni * 32 * U) + yo) = v;
+    }
+  }
+}
+
+// The LINEAR epilogue of a launch with phase-minor rows: full tiles of an output whose base, batch stride and row pitch are aligned to the
+// vector store take epi_phase_tile; a row-edge or column-edge tile, an unaligned output, a launch with DMEL_CONV_FASTPATH=0 take one store per
+// element with the same value expression.  (launch_conv refuses every epilogue option but out_len / fold with row_u > 1.)
+template <int MT, int NT>
+__device__ __forceinline__ void epi_phase_rows(const KArgs& a, const floatx16 (&acc)[MT][NT], int mrow0, int colbase, int b, int olim, int h) {
+  const int u = a.row_u, sh = u == 8 ? 3 : u == 4 ? 2 : 1;
+  const int tcols = (int)a.Tcols, tout = (int)a.Tout, ycs = (int)a.y_cs;
+  const int bu = __builtin_amdgcn_readfirstlane(b);
+  float* ybu = a.y + (int64_t)bu * a.y_bs;
+  const int col0 = __builtin_amdgcn_readfirstlane(colbase - (int)(__lane_id() & 31));
+  const uint32_t vbytes = u >= 4 ? 16u : 8u;
+  const bool aligned = (((uint32_t)reinterpret_cast<uintptr_t>(a.y) | (uint32_t)(a.y_bs * 4) | (uint32_t)(a.y_cs * 4)) & (vbytes - 1)) == 0;
+  const bool full_cols = a.fast && aligned && a.fold_pitch == 0 && col0 + NT * 32 <= tcols && (int64_t)(col0 + NT * 32) * u <= min(tout, olim) &&
+                         tout <= (1 << 28) && a.y_cs < (1 << 27);      // the lane's BYTE offset (two rows + a sample) fits 32 bits
+#pragma unroll
+  for (int mi = 0; mi < MT; ++mi) {
+    const int mtile = mrow0 + mi * 32;
+    if (mtile >= a.mtiles * 32) continue;
+    const int mt = __builtin_amdgcn_readfirstlane(mtile);
+    if (full_cols && mt + 32 <= a.C) {
+      const uint32_t boff = (uint32_t)(16 * h);      // bytes
+      if (u == 8) epi_phase_tile<8, NT>(a, acc[mi], mt, ybu, (uint32_t)(colbase * 8 + 4 * h) * 4u, boff);
+      else if (u == 4) epi_phase_tile<4, NT>(a, acc[mi], mt, ybu, (uint32_t)(h * ycs + colbase * 4) * 4u, boff);
+      else epi_phase_tile<2, NT>(a, acc[mi], mt, ybu, (uint32_t)(2 * h * ycs + colbase * 2) * 4u, boff);
+      continue;
+    }
+    float* yb = a.y + (int64_t)b * a.y_bs;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int m = mtile + (r & 3) + 8 * (r >> 2) + 4 * h;
+      if (m >= a.C) continue;
+      const int co = m >> sh, ph = m & (u - 1);
+      const float bias = a.bias[m];
+      float* yrow = yb + (int64_t)co * ycs;
+#pragma unroll
+      for (int ni = 0; ni < NT; ++ni) {
+        const int q = colbase + ni * 32;
+        const int64_t t = (int64_t)q * u + ph;
+        if (q >= tcols || t >= tout) continue;
+        float v = acc[mi][ni][r] + bias;
+        if (t >= olim || in_gap(a, q)) v = 0.f;
+        yrow[t] = v;
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------------------ epilogue (shared by both kernels)
 // Lane (h, l31) holds, for each 32x32 tile, column l31 and rows (r&3) + 8*(r>>2) + 4*h, r = 0..15.
 // Row-only quantities (bias, row offsets, channel map) are computed once per row, outside the column loop.
@@ -151,6 +231,12 @@ __device__ __forceinline__ void conv_epilogue(const KArgs& a, floatx16 (&acc)[MT
     float* yb = a.y + (int64_t)b * a.y_bs;
     const float* rb = a.res ? a.res + (int64_t)b * a.res_bs : nullptr;
     const int ycs = (int)a.y_cs, rcs = (int)a.res_cs, tout = (int)a.Tout;
+    if constexpr (!LEAN_ONLY) {
+      if (a.row_u > 1) {        // phase-minor rows: a transposed convolution in one image
+        epi_phase_rows<MT, NT>(a, acc, mrow0, colbase, b, olim, h);
+        return;
+      }
+    }
     // The common case (plain conv, optionally + residual: 5 of 6 vocoder convs, every WaveNet projection) gets a loop
     // with no per-element flag tests: the general loop below spends more time in uniform branches than in stores.
     const bool lean = LEAN_ONLY || (a.act == ACT_NONE && !a.row_scale && a.phases == 1 && a.out_tstride == 1 && a.phase_base == 0);

@@ -1233,6 +1233,14 @@ int launch_conv(const PackedConv& pc, const ConvRun& r, hipStream_t stream) {
   ka.win = r.win; ka.win_stride = r.win_stride; ka.win_shift = r.win_shift; ka.win_end = r.win_end;
   ka.win_valid[0] = r.win_valid[0]; ka.win_valid[1] = r.win_valid[1];
   ka.fast = conv_fastpath_enabled() ? 1 : 0;
+  ka.row_u = d.row_u;
+  if (d.row_u != 1) {
+    DMEL_CHECK_ARG((d.row_u == 2 || d.row_u == 4 || d.row_u == 8) && d.mode == EPI_LINEAR && d.phases == 1 && d.nseg == 1 && d.C % d.row_u == 0,
+                   "conv: phase-minor rows need a single-segment LINEAR image of C = channels * row_u rows, row_u 2, 4 or 8");
+    DMEL_CHECK_ARG(r.act == ACT_NONE && !r.row_scale && !r.res && !r.accumulate && r.out_div == 1.f && r.out_tstride == 1 && r.phase_base == 0 &&
+                   !r.win && !r.yp,
+                   "conv: phase-minor rows take no activation, row scale, residual, running sum, division, output stride or windows");
+  }
   if (r.win) {
     if (r.fold_pitch != 0) { set_error("conv (per-item windows): the folded batch has one time axis for all items and no table"); return DMEL_EUNSUPPORTED; }
     if (r.yp) { set_error("conv (per-item windows): the pre-split output path does not read the window table"); return DMEL_EUNSUPPORTED; }
@@ -1244,14 +1252,15 @@ int launch_conv(const PackedConv& pc, const ConvRun& r, hipStream_t stream) {
   ka.yp = reinterpret_cast<uint4*>(r.yp); ka.yp_plane = r.yp_plane; ka.yp_g8 = d.C / 8; ka.yp_only = r.yp_only;
   DMEL_CHECK_ARG(r.fold_pitch == 0 || (r.fold_pitch >= r.fold_valid && r.fold_valid > 0 && r.B == 1 && r.out_tstride == 1),
                  "conv: folded-batch launches are single-item, unit-stride and need 0 < fold_valid <= fold_pitch");
-  DMEL_CHECK_ARG((int64_t)d.C * ka.y_cs < ((int64_t)1 << 31) && ka.Tout < ((int64_t)1 << 30) && ka.Tcols < ((int64_t)1 << 30),
+  DMEL_CHECK_ARG((int64_t)(d.C / d.row_u) * ka.y_cs < ((int64_t)1 << 31) && ka.Tout < ((int64_t)1 << 30) && ka.Tcols < ((int64_t)1 << 30),
                  "conv: one batch item of the output exceeds 32-bit offsets");
   ka.mtiles = pc.Mpad / 32;
   const double rows_real = (d.mode == EPI_LINEAR ? (double)d.C * d.phases : 2.0 * d.C);
   // algorithmic HBM bytes of the launch: every input row once, every output element once (+ the residual / running-sum / skip rows the
   // epilogue reads), the split weight image once
   double in_elems = 0.0;
-  for (int s = 0; s < d.nseg; ++s) in_elems += (double)d.seg[s].Cin * (double)std::min<int64_t>(r.seg[s].Tin, r.Tcols * d.seg[s].tstride + max_halo);
+  const int alg_halo = max_halo - d.dead_taps * d.seg[0].dil;      // the receptive field without the all-zero taps
+  for (int s = 0; s < d.nseg; ++s) in_elems += (double)d.seg[s].Cin * (double)std::min<int64_t>(r.seg[s].Tin, r.Tcols * d.seg[s].tstride + alg_halo);
   double out_elems;
   if (d.mode == EPI_LINEAR) out_elems = (double)d.C * d.phases * (double)r.Tcols * (1.0 + (r.res ? 1.0 : 0.0) + (r.accumulate ? 1.0 : 0.0));
   else if (d.mode == EPI_GATE) out_elems = (double)d.C * (double)r.Tcols;
@@ -1268,14 +1277,15 @@ int launch_conv(const PackedConv& pc, const ConvRun& r, hipStream_t stream) {
   const bool one_piece = r.precision == DMEL_PRECISION_BF16 || train_precision_override() == DMEL_PRECISION_BF16;
   const bool native = !one_piece && (native_fp32 || r.precision == DMEL_PRECISION_FP32_MFMA);
   const double products = one_piece ? 1.0 : native ? 16.0 /* fp32 MFMA: 1/16 of the bf16 rate */ : r.precision == DMEL_PRECISION_FP32_F16X2 ? 3.0 : 6.0;
-  alg_bytes += (double)pc.Mpad * pc.steps * kCK * (one_piece ? 2.0 : native ? 4.0 : r.precision == DMEL_PRECISION_FP32_F16X2 ? 4.0 : 6.0);
+  const double live_taps = (double)(d.seg[0].taps - d.dead_taps) / d.seg[0].taps;      // < 1: the image carries all-zero taps (PackDesc::dead_taps)
+  alg_bytes += live_taps * (double)pc.Mpad * pc.steps * kCK * (one_piece ? 2.0 : native ? 4.0 : r.precision == DMEL_PRECISION_FP32_F16X2 ? 4.0 : 6.0);
   const double alg_flops = 2.0 * alg_cols * rows_real * pc.k_real;
   if (r.win && (one_piece || native)) {
     set_error("conv (per-item windows): %s does not read the window table (the fp16 split and fp32_bf16x3 do)",
               one_piece ? "the bf16-operand kernel" : "the native fp32-MFMA kernel");
     return DMEL_EUNSUPPORTED;
   }
-  ProfScope ps("conv_igemm", stream, alg_flops, alg_bytes, alg_flops * products);
+  ProfScope ps("conv_igemm", stream, alg_flops, alg_bytes, alg_flops * products / live_taps);      // issued: the zero taps are multiplied too
   if (r.win) {
     if (r.precision == DMEL_PRECISION_FP32_F16X2) {
       DMEL_TRY(check_f16_range(pc, r, stream));

@@ -213,7 +213,7 @@ static int launch_pc(const KArgs& ka, int B, hipStream_t st) {
 
 bool conv_pc_eligible(const PackedConv& pc, const ConvRun& r, bool any_size) {
   const PackDesc& d = pc.d;
-  if (d.phases != 1 || r.out_tstride != 1 || r.phase_base != 0 || r.fold_pitch != 0 || r.row_scale || r.yp) return false;
+  if (d.phases != 1 || d.row_u != 1 || r.out_tstride != 1 || r.phase_base != 0 || r.fold_pitch != 0 || r.row_scale || r.yp) return false;
   if (r.win) return false;                    // per-item column windows: this kernel has one window for the whole batch
   if (r.precision != DMEL_PRECISION_FP32_F16X2 || train_precision_override() == DMEL_PRECISION_BF16 || conv_fp32_mfma_forced()) return false;
   if (d.mode == EPI_LINEAR && (r.act != ACT_NONE || r.out_len)) return false;

@@ -392,7 +392,7 @@ static int launch_cs_h(const KArgs& ka, const SnakeArgs& sa, int B, int halo, hi
 
 bool conv_snake_eligible(const PackedConv& pc, const ConvRun& r) {
   const PackDesc& d = pc.d;
-  return d.mode == EPI_LINEAR && d.nseg == 1 && d.phases == 1 && d.seg[0].tstride == 1 && d.seg[0].toff == 0 && r.seg[0].tshift == 0 &&
+  return d.mode == EPI_LINEAR && d.nseg == 1 && d.phases == 1 && d.row_u == 1 && d.seg[0].tstride == 1 && d.seg[0].toff == 0 && r.seg[0].tshift == 0 &&
          (d.seg[0].taps - 1) * d.seg[0].dil <= 64 && r.seg[0].in_len == nullptr && r.out_len == nullptr && r.seg[0].in_scale == 1.f &&
          r.seg[0].in_absmax == nullptr && r.act == ACT_NONE && r.row_scale == nullptr && r.out_tstride == 1 && r.phase_base == 0 &&
          r.fold_pitch == 0 && r.precision == DMEL_PRECISION_FP32_F16X2 && train_precision_override() != DMEL_PRECISION_BF16 &&

@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <map>
 #include <memory>
+#include <mutex>
 
 #include "ops.h"
 
@@ -2290,6 +2291,11 @@ struct AmpBlock {             // AMPBlock1, bigvgan.py:31-147
 struct UpStage {
   int u, k, Cin, Cout;
   PackedConv lo, hi;          // phases [0,u/2) with taps d={-1,0}; phases [u/2,u) with taps d={0,+1}
+  bool one = false;           // u = 2, 4, 8: the stage can run as one launch of `all`
+  // every phase in one image, rows phase-minor (m = co u + ph), taps d={-1,0,+1}.  Packed on the FIRST forward that wants it
+  // (ensure_up_stage_all), from the weights the two images above hold exactly -- like the backward-data images, not at finalize
+  mutable PackedConv all;
+  mutable bool all_ready = false;
   std::vector<PackedConv> dgrad;   // backward-data: u/2 images of two strided two-tap segments each (pack_up_stage_dgrad); empty until asked for
 };
 // ConvTranspose1d(Cin, Cout, k = 2u, stride u, padding u/2) as two groups of u/2 phase sub-convolutions with two taps each:
@@ -2310,11 +2316,44 @@ int pack_up_stage(UpStage& us, const float* w, const float* bias) {
                        },
                        [&](int row) { return bias ? bias[row % Co] : 0.f; }));
   }
+  us.one = u == 2 || u == 4 || u == 8;
+  us.all_ready = false;       // new weights: the one-launch image is re-packed by the next forward
   return DMEL_OK;
+}
+// One image for the whole stage (u = 2, 4, 8): the union of the two tap windows, d = {-1, 0, +1} behind pad_left = 1, over all u phases.
+// The tap a phase does not use (d = +1 below u/2, d = -1 from u/2 on) falls outside [0, k) and carries zero weights: a K step that adds
+// zero products leaves an fp32 accumulator as it was, and the two real taps keep their order (chunk-major, d ascending), so every output
+// keeps the bits of the two launches.  Rows are phase-minor, m = co u + ph: a lane of the 32 x 32 accumulator tile then holds
+// consecutive output samples of one channel in consecutive registers (conv_dev.h, epi_phase_tile), and x is read once per stage.
+int pack_up_stage_all(const UpStage& us, const float* w, const float* bias) {
+  const int u = us.u, k = us.k, hu = u / 2, Co = us.Cout;
+  PackDesc d;
+  d.mode = EPI_LINEAR; d.nseg = 1; d.C = Co * u; d.phases = 1; d.row_u = u; d.dead_taps = 1;
+  d.seg[0].Cin = us.Cin; d.seg[0].taps = 3; d.seg[0].dil = 1; d.seg[0].pad_left = 1;
+  return pack_conv(us.all, d,
+                   [&](int, int row, int ci, int tap) {
+                     const int co = row / u, ph = row % u, kk = ph + hu - u * (tap - 1);
+                     return (kk >= 0 && kk < k) ? w[((size_t)ci * Co + co) * k + kk] : 0.f;
+                   },
+                   [&](int row) { return bias[row / u]; });
+}
+int ensure_up_stage_all(const UpStage& us);
+// DMEL_UPSTAGE_ONE_LAUNCH=0: every transposed convolution runs as the two phase-major launches (A/B, bit-identity tests).  Read per call.
+static bool upstage_one_launch_enabled() {
+  const char* e = getenv("DMEL_UPSTAGE_ONE_LAUNCH");
+  return !(e && e[0] == '0' && e[1] == 0);
 }
 // x (B, Cin, T) -> y (B, Cout, u T).  in_len (nullable, B device int64): item b's valid input columns; what lies behind them reads as zero
 int launch_up_stage(const UpStage& us, const float* x, float* y, int B, int64_t T, int precision, hipStream_t st,
                     const int64_t* in_len = nullptr) {
+  if (us.one && upstage_one_launch_enabled()) {
+    DMEL_TRY(ensure_up_stage_all(us));
+    ConvRun r = run_1seg(x, us.Cin, T, y, us.Cout, T * us.u, B);
+    r.seg[0].in_len = in_len;
+    r.Tcols = T; r.Tout = T * us.u;
+    r.precision = precision;
+    return launch_conv(us.all, r, st);
+  }
   for (int half = 0; half < 2; ++half) {
     ConvRun r = run_1seg(x, us.Cin, T, y, us.Cout, T * us.u, B);
     r.seg[0].in_len = in_len;
@@ -2343,10 +2382,23 @@ struct HostImage {
 };
 // W[co][ci][tap] of a "same" convolution packed by pack_same_conv (one segment, identity row map)
 float same_conv_weight(const HostImage& im, int taps, int co, int ci, int tap) { return im.at(co, (ci / kCK) * taps + tap, ci % kCK); }
-// (Cin, Cout, k) weights of a transposed convolution back from the two forward images of pack_up_stage
+// (Cin, Cout, k) weights of a transposed convolution back from the forward images of pack_up_stage: the one-launch image once a forward
+// has packed it (row co u + ph, three taps per chunk), else the two phase-major ones
 int unpack_up_stage(const UpStage& us, std::vector<float>& w) {
   const int u = us.u, k = us.k, hu = u / 2, Co = us.Cout;
   w.assign((size_t)us.Cin * Co * k, 0.f);
+  if (us.all_ready) {
+    HostImage im;
+    DMEL_TRY(im.load(us.all));
+    for (int co = 0; co < Co; ++co)
+      for (int ph = 0; ph < u; ++ph)
+        for (int ci = 0; ci < us.Cin; ++ci)
+          for (int tap = 0; tap < 3; ++tap) {
+            const int kk = ph + hu - u * (tap - 1);
+            if (kk >= 0 && kk < k) w[((size_t)ci * Co + co) * k + kk] = im.at(co * u + ph, (ci / kCK) * 3 + tap, ci % kCK);
+          }
+    return DMEL_OK;
+  }
   for (int half = 0; half < 2; ++half) {
     const PackedConv& pc = half == 0 ? us.lo : us.hi;
     HostImage im;
@@ -2359,6 +2411,22 @@ int unpack_up_stage(const UpStage& us, std::vector<float>& w) {
             if (kk >= 0 && kk < k) w[((size_t)ci * Co + co) * k + kk] = im.at(p * pc.RP + co, (ci / kCK) * 2 + tap, ci % kCK);
           }
   }
+  return DMEL_OK;
+}
+// The one-launch image of a stage, packed by the first forward that wants it: weights and bias are read back from the phase-major images
+// (the fp32 image and the bias rows hold them exactly; finalize has dropped the state dict).  That call copies between host and device
+// and synchronises, so it must not be the first thing a stream capture records: run one forward before capturing, as the streaming
+// decoder does.  One lock for all stages: lanes and sessions share a vocoder handle between threads.
+int ensure_up_stage_all(const UpStage& us) {
+  static std::mutex mu;
+  std::lock_guard<std::mutex> lock(mu);
+  if (us.all_ready) return DMEL_OK;
+  std::vector<float> w, bias(us.lo.bias.bytes / sizeof(float));
+  DMEL_TRY(unpack_up_stage(us, w));
+  if (!bias.empty()) DMEL_HIP(hipMemcpy(bias.data(), us.lo.bias.p, us.lo.bias.bytes, hipMemcpyDeviceToHost));      // rows [0, Cout): phase 0
+  DMEL_CHECK_ARG((int)bias.size() >= us.Cout, "conv_transpose1d: the phase-major bias image is shorter than Cout");
+  DMEL_TRY(pack_up_stage_all(us, w.data(), bias.data()));
+  us.all_ready = true;
   return DMEL_OK;
 }
 // Backward-data of the transposed convolution:  dx[ci, q] = scale * sum_co sum_kk W[ci, co, kk] dy[co, u q + kk - u/2]  (zero outside
@@ -2440,6 +2508,12 @@ extern "C" int dmel_conv_transpose1d_forward(const dmel_conv_transpose* h, const
   DMEL_CHECK_ARG(h && x && y, "conv_transpose1d_forward: NULL argument");
   DMEL_CHECK_ARG(B > 0 && T > 0, "conv_transpose1d_forward: bad shape");
   return launch_up_stage(h->us, x, y, B, T, h->precision, (hipStream_t)stream);
+}
+extern "C" int dmel_conv_transpose1d_forward_items(const dmel_conv_transpose* h, const float* x, float* y, int B, int64_t T,
+                                                   const int64_t* lengths_dev, void* stream) {
+  DMEL_CHECK_ARG(h && x && y && lengths_dev, "conv_transpose1d_forward_items: NULL argument");
+  DMEL_CHECK_ARG(B > 0 && T > 0, "conv_transpose1d_forward_items: bad shape");
+  return launch_up_stage(h->us, x, y, B, T, h->precision, (hipStream_t)stream, lengths_dev);
 }
 extern "C" int dmel_conv_post_f32(const float* x, const float* w_dev, float bias, int act, float* y, int B, int C, int K, int64_t T, void* stream) {
   DMEL_CHECK_ARG(x && w_dev && y, "conv_post: NULL argument");

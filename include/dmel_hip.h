@@ -1062,6 +1062,17 @@ int dmel_conv_transpose1d_create(dmel_conv_transpose** out, const float* w_host,
 void dmel_conv_transpose1d_destroy(dmel_conv_transpose* h);
 int dmel_conv_transpose1d_set_precision(dmel_conv_transpose* h, int precision);   /* DMEL_PRECISION_* */
 int dmel_conv_transpose1d_forward(const dmel_conv_transpose* h, const float* x, float* y, int B, int64_t T, void* stream);
+/* dmel_conv_transpose1d_forward over items: T is the row pitch of x, lengths_dev (B) device int64 in [0, T]; x[b, :, lengths[b]:] reads as
+ * zero (it is not read), every one of the T * stride output columns is written.
+ * Strides 2, 4 and 8 run as ONE launch: one weight image with all phases (rows channel-major, phase-minor) over the taps d = -1, 0, +1, the
+ * tap a phase does not use carrying zeros, so each output keeps the bits of the two phase-group launches; a lane stores 2 or 4 consecutive
+ * output samples at once where y and its row pitch are 8- / 16-byte aligned, single floats otherwise (any pointer is accepted).  A zero
+ * weight times a non-finite x is NaN: an Inf / NaN sample also reaches the output columns of the neighbouring phase group, which the two
+ * launches kept apart.  The one-launch image is packed by the FIRST forward that wants it (a host <-> device copy and a synchronise, under a
+ * lock): run one forward before capturing the stream into a graph.  DMEL_UPSTAGE_ONE_LAUNCH=0 (environment, read per call) keeps the two
+ * launches. */
+int dmel_conv_transpose1d_forward_items(const dmel_conv_transpose* h, const float* x, float* y, int B, int64_t T, const int64_t* lengths_dev,
+                                        void* stream);
 int dmel_conv_post_f32(const float* x, const float* w_dev, float bias, int act, float* y, int B, int C, int K, int64_t T, void* stream);
 /* dmel_conv_post_f32 over items: T is the row pitch, lengths_dev (B) device int64 in [0, T].  Taps at or beyond lengths[b] read as zero
  * (the item's own zero padding; x is not read there), y[b, 0, :lengths[b]] is BIT-IDENTICAL to dmel_conv_post_f32 on the item alone and
