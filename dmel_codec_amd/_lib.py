@@ -62,6 +62,10 @@ PROTOTYPES = {
     "dmel_stft_window_items_f32": (C.c_int, [vp, vp, C.c_int64, C.c_int64, i64p, i64p, vp, vp, vp, C.c_int, i64p, i64p, i64p, vp, vp]),
     "dmel_aa_snake_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp]),
     "dmel_aa_snake_items_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp, vp]),
+    "dmel_aa_snake3_forward": (C.c_int, [vp] * 12 + [C.c_int, C.c_int, C.c_int, C.c_int64, vp]),
+    "dmel_aa_snake3_forward_items": (C.c_int, [vp] * 12 + [C.c_int, C.c_int, C.c_int, C.c_int64, vp, vp]),
+    "dmel_snake_post_forward": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, vp, C.c_float, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp]),
+    "dmel_snake_post_forward_items": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, vp, C.c_float, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp, vp]),
     "dmel_aa_snake_backward_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp]),
     "dmel_discriminator_create": (C.c_int, [C.POINTER(vp)]),
     "dmel_discriminator_destroy": (None, [vp]),

@@ -47,62 +47,100 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // three threads between the stages, in the tiles that touch a row end only (block-uniform test).
 // The tiles of ONE row: xr / yr point at column 0 of the (b, c) row, T is the number of valid columns of that row (its replicate padding
 // ends at T - 1; nothing at or behind column T is read or written), `first` the first output of this workgroup's nsub tiles.
+// The four stage bodies of a tile, shared by aa_snake_row, aa_snake3_row and snake_post_kernel: one expression per element, so every kernel
+// built from them computes the same bits.
+// this thread's four samples of the tile's row segment: xs[4 tid + i] = x[clamp(t0 - 8 + 4 tid + i, 0, T - 1)]
 template <bool VEC>
-__device__ __forceinline__ void aa_snake_row(const float* __restrict__ xr, float* __restrict__ yr, const float* __restrict__ alpha,
-                                             const float* __restrict__ beta, const Taps12& tu, const Taps12& td, int logscale, int c, int T,
-                                             int first, int nsub, float* xs, float* ve, float* vo) {
-  float a = alpha[c], bt = beta ? beta[c] : a;
+__device__ __forceinline__ f32x4 snake_fetch4(const float* __restrict__ xr, int T, int t0, int tid) {
+  const int s = t0 - 8 + 4 * tid;
+  if (VEC && s >= 0 && s + 4 <= T) return *reinterpret_cast<const f32x4*>(xr + s);
+  f32x4 v;
+  v.x = xr[min(max(s, 0), T - 1)];
+  v.y = xr[min(max(s + 1, 0), T - 1)];
+  v.z = xr[min(max(s + 2, 0), T - 1)];
+  v.w = xr[min(max(s + 3, 0), T - 1)];
+  return v;
+}
+// pairs 4 tid .. 4 tid + 3 of the 2x signal BEFORE the snake: u[2 i] the even, u[2 i + 1] the odd sample of pair 4 tid + i
+__device__ __forceinline__ void snake_up4(const float* xs, int tid, const Taps12& tu, float (&u)[8]) {
+  float w[12];
+  lds_read3_b128(xs + 4 * tid, w);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    float ue = 0.f, uo = 0.f;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      ue = fmaf(tu.f[2 * j + 1], w[i + 7 - j], ue);
+      uo = fmaf(tu.f[2 * j], w[i + 8 - j], uo);
+    }
+    u[2 * i] = ue;
+    u[2 * i + 1] = uo;
+  }
+}
+// u <- snake(u) with one (a, 1 / b) for all eight, stored as the two planes
+__device__ __forceinline__ void snake_store4(float (&u)[8], float a, float inv_b, float* ve, float* vo, int tid) {
+  float aa[8], bb[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) { aa[i] = a; bb[i] = inv_b; }
+  // all eight sin^2 behind ONE wave-uniform test of the large-argument case, so the straight-line bodies interleave (snake_dev.h)
+  snake_n(u, aa, bb);
+  *reinterpret_cast<f32x4*>(ve + 4 * tid) = f32x4{u[0], u[2], u[4], u[6]};
+  *reinterpret_cast<f32x4*>(vo + 4 * tid) = f32x4{u[1], u[3], u[5], u[7]};
+}
+// outputs 4 tid .. 4 tid + 3 of the tile from the two planes
+__device__ __forceinline__ f32x4 snake_down4(const float* ve, const float* vo, int tid, const Taps12& td) {
+  float e[12], o[12];
+  lds_read3_b128(ve + 4 * tid, e);
+  lds_read3_b128(vo + 4 * tid, o);
+  f32x4 out;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    float acc = td.f[0] * o[i];
+#pragma unroll
+    for (int k = 1; k < 6; ++k) {
+      acc = fmaf(td.f[2 * k - 1], e[i + k], acc);
+      acc = fmaf(td.f[2 * k], o[i + k], acc);
+    }
+    out[i] = fmaf(td.f[11], e[i + 6], acc);
+  }
+  return out;
+}
+// the effective (a, 1 / (b + 1e-9)) of channel c
+__device__ __forceinline__ void snake_params(const float* __restrict__ alpha, const float* __restrict__ beta, int logscale, int c, float& a,
+                                             float& inv_b) {
+  a = alpha[c];
+  float bt = beta ? beta[c] : a;
   if (logscale) {
     bt = beta ? expf(bt) : expf(a);
     a = expf(a);
   }
-  const float inv_b = 1.0f / (bt + 1e-9f);
+  inv_b = 1.0f / (bt + 1e-9f);
+}
+
+template <bool VEC>
+__device__ __forceinline__ void aa_snake_row(const float* __restrict__ xr, float* __restrict__ yr, const float* __restrict__ alpha,
+                                             const float* __restrict__ beta, const Taps12& tu, const Taps12& td, int logscale, int c, int T,
+                                             int first, int nsub, float* xs, float* ve, float* vo) {
+  float a, inv_b;
+  snake_params(alpha, beta, logscale, c, a, inv_b);
   // nsub consecutive tiles per workgroup, SOFTWARE-PIPELINED: the row segment of tile s + 1 is fetched into registers before tile s is
   // computed.  A workgroup reads 4 KB and then computes for microseconds without touching memory; without the prefetch the bytes in
   // flight per CU, not instruction issue, set the read rate (Little's law).
   const int tid = threadIdx.x;
-  auto fetch = [&](int t0) {
-    const int s = t0 - 8 + 4 * tid;
-    if (VEC && s >= 0 && s + 4 <= T) return *reinterpret_cast<const f32x4*>(xr + s);
-    f32x4 v;
-    v.x = xr[min(max(s, 0), T - 1)];
-    v.y = xr[min(max(s + 1, 0), T - 1)];
-    v.z = xr[min(max(s + 2, 0), T - 1)];
-    v.w = xr[min(max(s + 3, 0), T - 1)];
-    return v;
-  };
-  float aa[8], bb[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { aa[i] = a; bb[i] = inv_b; }
   f32x4 pre = {0.f, 0.f, 0.f, 0.f};
-  if (first < T) pre = fetch(first);
+  if (first < T) pre = snake_fetch4<VEC>(xr, T, first, tid);
   for (int sub = 0; sub < nsub; ++sub) {
     const int t0 = first + sub * kSnakeFwdTile;
     if (t0 >= T) break;
     const int len = min(kSnakeFwdTile, T - t0);
     if (sub) __syncthreads();                  // the previous tile's reads of xs / ve / vo are done
     *reinterpret_cast<f32x4*>(xs + 4 * tid) = pre;
-    if (sub + 1 < nsub && t0 + kSnakeFwdTile < T) pre = fetch(t0 + kSnakeFwdTile);     // in flight while this tile is computed
+    if (sub + 1 < nsub && t0 + kSnakeFwdTile < T) pre = snake_fetch4<VEC>(xr, T, t0 + kSnakeFwdTile, tid);     // in flight while this tile is computed
     __syncthreads();
     if (4 * tid < len + 6) {
-      float w[12];
-      lds_read3_b128(xs + 4 * tid, w);
       float u[8];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float ue = 0.f, uo = 0.f;
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-          ue = fmaf(tu.f[2 * j + 1], w[i + 7 - j], ue);
-          uo = fmaf(tu.f[2 * j], w[i + 8 - j], uo);
-        }
-        u[2 * i] = ue;
-        u[2 * i + 1] = uo;
-      }
-      // all eight sin^2 behind ONE wave-uniform test of the large-argument case, so the straight-line bodies interleave (snake_dev.h)
-      snake_n(u, aa, bb);
-      *reinterpret_cast<f32x4*>(ve + 4 * tid) = f32x4{u[0], u[2], u[4], u[6]};
-      *reinterpret_cast<f32x4*>(vo + 4 * tid) = f32x4{u[1], u[3], u[5], u[7]};
+      snake_up4(xs, tid, tu, u);
+      snake_store4(u, a, inv_b, ve, vo, tid);
     }
     __syncthreads();
     const int pe = T - t0 + 3;                 // the first pair past the row's end
@@ -114,20 +152,7 @@ __device__ __forceinline__ void aa_snake_row(const float* __restrict__ xr, float
       __syncthreads();
     }
     if (4 * tid < len) {
-      float e[12], o[12];
-      lds_read3_b128(ve + 4 * tid, e);
-      lds_read3_b128(vo + 4 * tid, o);
-      f32x4 out;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float acc = td.f[0] * o[i];
-#pragma unroll
-        for (int k = 1; k < 6; ++k) {
-          acc = fmaf(td.f[2 * k - 1], e[i + k], acc);
-          acc = fmaf(td.f[2 * k], o[i + k], acc);
-        }
-        out[i] = fmaf(td.f[11], e[i + 6], acc);
-      }
+      const f32x4 out = snake_down4(ve, vo, tid, td);
       float* yp = yr + t0 + 4 * tid;
       if (VEC) {                               // T % 4 == 0: len is a multiple of 4, the thread's four outputs are all inside
         *reinterpret_cast<f32x4*>(yp) = out;
@@ -173,6 +198,209 @@ __global__ __launch_bounds__(256) void aa_snake_items_kernel(const float* __rest
   const bool vec = n % 4 == 0 && (reinterpret_cast<uintptr_t>(xr) | reinterpret_cast<uintptr_t>(yr)) % 16 == 0;
   if (vec) aa_snake_row<true>(xr, yr, alpha, beta, tu, td, logscale, c, n, first, nsub, xs, ve, vo);
   else aa_snake_row<false>(xr, yr, alpha, beta, tu, td, logscale, c, n, first, nsub, xs, ve, vo);
+}
+
+// ---- three activations of ONE tensor (the heads of the three AMP blocks behind an up-sampler) ------------------------------------
+// y[k] = activation(x; alpha[k], beta[k]), k = 0..2: per tile the row segment is read and the up-filter evaluated ONCE (u, eight registers),
+// then each parameter set runs snake -> planes -> down-filter -> store.  4 tensors move where three launches move 6.  Each output's
+// arithmetic is aa_snake_row's (the same stage bodies), so y[k] has the bits of a launch of its own.  The planes are double-buffered: set
+// k writes the pair that set k - 2 read, and the barrier inside set k - 1 stands between the two, so a set costs one barrier (the pad
+// patch aside) and a tile four where three separate tiles cost nine.  5 x 4 KB of LDS: eight workgroups per CU, as before.
+// yvec bit k: y[k]'s rows are 16-byte aligned -- the wide store is taken per output (VEC also needs x aligned and T % 4 == 0).
+struct Snake3 {
+  float* y[3];
+  const float* alpha[3];
+  const float* beta[3];      // NULL: Snake (beta = alpha)
+};
+
+template <bool VEC>
+__device__ __forceinline__ void aa_snake3_row(const float* __restrict__ xr, int64_t row, const Snake3& p, const Taps12& tu, const Taps12& td,
+                                              int logscale, int c, int T, int first, int nsub, int yvec, float* xs, float* planes) {
+  float a[3], inv_b[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) snake_params(p.alpha[k], p.beta[k], logscale, c, a[k], inv_b[k]);
+  const int tid = threadIdx.x;
+  f32x4 pre = {0.f, 0.f, 0.f, 0.f};
+  if (first < T) pre = snake_fetch4<VEC>(xr, T, first, tid);
+  int par = 0;
+  for (int sub = 0; sub < nsub; ++sub) {
+    const int t0 = first + sub * kSnakeFwdTile;
+    if (t0 >= T) break;
+    const int len = min(kSnakeFwdTile, T - t0);
+    // xs was last read before the first barrier of the previous tile's set 0: no barrier in front of this store
+    *reinterpret_cast<f32x4*>(xs + 4 * tid) = pre;
+    if (sub + 1 < nsub && t0 + kSnakeFwdTile < T) pre = snake_fetch4<VEC>(xr, T, t0 + kSnakeFwdTile, tid);
+    __syncthreads();
+    const bool pairs = 4 * tid < len + 6;
+    float u[8];
+    if (pairs) snake_up4(xs, tid, tu, u);
+    const int pe = T - t0 + 3;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      float* ve = planes + par * 2 * (kSnakeFwdTile + 16);
+      float* vo = ve + (kSnakeFwdTile + 16);
+      par ^= 1;
+      if (pairs) {
+        float v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = u[i];
+        snake_store4(v, a[k], inv_b[k], ve, vo, tid);
+      }
+      __syncthreads();
+      if (t0 == 0 || pe < len + 6) {
+        if (tid < 3) {
+          if (t0 == 0) ve[tid] = vo[tid] = ve[3];
+          if (pe + tid < len + 6) ve[pe + tid] = vo[pe + tid] = vo[pe - 1];
+        }
+        __syncthreads();
+      }
+      if (4 * tid < len) {
+        const f32x4 out = snake_down4(ve, vo, tid, td);
+        float* yp = p.y[k] + row + t0 + 4 * tid;
+        if (VEC && ((yvec >> k) & 1)) {
+          *reinterpret_cast<f32x4*>(yp) = out;
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            if (4 * tid + i < len) yp[i] = out[i];
+        }
+      }
+    }
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void aa_snake3_kernel(const float* __restrict__ x, Snake3 p, Taps12 tu, Taps12 td, int logscale, int C, int T,
+                                                           int nsub, int yvec) {
+  __shared__ __attribute__((aligned(16))) float xs[kSnakeFwdTile + 16];
+  __shared__ __attribute__((aligned(16))) float planes[4 * (kSnakeFwdTile + 16)];
+  const int c = blockIdx.y, b = blockIdx.z;
+  const int64_t row = ((int64_t)b * C + c) * T;
+  aa_snake3_row<VEC>(x + row, row, p, tu, td, logscale, c, T, blockIdx.x * nsub * kSnakeFwdTile, nsub, yvec, xs, planes);
+}
+
+// per-item form, as aa_snake_items_kernel: the paths are chosen per row
+__global__ __launch_bounds__(256) void aa_snake3_items_kernel(const float* __restrict__ x, Snake3 p, Taps12 tu, Taps12 td, int logscale, int C,
+                                                                 int T, const int64_t* __restrict__ len, int nsub) {
+  __shared__ __attribute__((aligned(16))) float xs[kSnakeFwdTile + 16];
+  __shared__ __attribute__((aligned(16))) float planes[4 * (kSnakeFwdTile + 16)];
+  const int c = blockIdx.y, b = blockIdx.z;
+  const int n = (int)min(max(len[b], (int64_t)0), (int64_t)T);
+  const int first = blockIdx.x * nsub * kSnakeFwdTile;
+  if (first >= n) return;
+  const int64_t row = ((int64_t)b * C + c) * T;
+  const float* xr = x + row;
+  int yvec = 0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) yvec |= (int)(reinterpret_cast<uintptr_t>(p.y[k] + row) % 16 == 0) << k;
+  const bool vec = n % 4 == 0 && reinterpret_cast<uintptr_t>(xr) % 16 == 0;
+  if (vec) aa_snake3_row<true>(xr, row, p, tu, td, logscale, c, n, first, nsub, yvec, xs, planes);
+  else aa_snake3_row<false>(xr, row, p, tu, td, logscale, c, n, first, nsub, 0, xs, planes);
+}
+
+// ---- activation_post + conv_post + tanh | clamp as one launch ----------------------------------------------------------------------
+// y[b, t] = act(bias + sum_c sum_k w[c, k] * A[b, c, t + k - pad]), A = activation(x) inside [0, n) and conv_post's zero padding outside
+// (n = T, or the item's length).  One workgroup owns W = 1008 - 2 H output columns (H = pad rounded up to 4, so W = 1000 for k = 7) of one
+// item and walks the C channels in order: channel c's activation tile -- the 1008 columns from t0 = first - H, computed with
+// aa_snake_row's stage bodies, the row segment of channel c + 1 in flight meanwhile -- goes to an LDS plane instead of HBM, zeroed outside
+// [0, n), and every thread adds its four outputs' K taps of it: acc = fma(w[c, k], A, acc), c outer and k inner from acc = bias, which is
+// conv_post_kernel's order, so y has the bits of the two launches.  The activated tensor (C x T x 4 bytes written and read again) never
+// exists.  t0 is a multiple of 4 and may be negative in an item's first tile: the row segment clamps as ever, the pairs left of pair 0
+// are patched with v[0] wherever pair 0 sits, and columns t < 0 are zeroed like those at or beyond n.  The weights are read through the
+// scalar cache (wave-uniform addresses).
+template <int KT>      // KT = 7: the vocoder's conv_post, the taps as three 16-byte LDS reads; KT = 0: any odd K with pad <= kPostMaxPad
+__global__ __launch_bounds__(256) void snake_post_kernel(const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ alpha,
+                                                            const float* __restrict__ beta, Taps12 tu, Taps12 td, int logscale,
+                                                            const float* __restrict__ w, float bias, int act, int C, int K, int T,
+                                                            const int64_t* __restrict__ len) {
+  __shared__ __attribute__((aligned(16))) float xs[kSnakeFwdTile + 16];
+  __shared__ __attribute__((aligned(16))) float ve[kSnakeFwdTile + 16];
+  __shared__ __attribute__((aligned(16))) float vo[kSnakeFwdTile + 16];
+  __shared__ __attribute__((aligned(16))) float as[kSnakeFwdTile + 16];
+  const int tid = threadIdx.x, b = blockIdx.y;
+  const int pad = (KT ? KT : K) / 2, H = (pad + 3) & ~3, W = kSnakeFwdTile - 2 * H;
+  const int first = blockIdx.x * W;
+  const int n = len ? (int)min(max(len[b], (int64_t)0), (int64_t)T) : T;
+  float* yb = y + (int64_t)b * T;
+  if (first >= n) {                            // a tile wholly behind the item's end (block-uniform): zeros
+    for (int t = first + tid; t < min(first + W, T); t += 256) yb[t] = 0.f;
+    return;
+  }
+  const int t0 = first - H;
+  const int alen = min(kSnakeFwdTile, n - t0);       // activation columns t0 .. t0 + alen - 1 (those below 0 are computed and zeroed)
+  const float* xr = x + (int64_t)b * C * T;
+  const bool vec = T % 4 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0;      // every row then starts on a 16-byte boundary
+  float acc[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) acc[e] = bias;
+  f32x4 pre = vec ? snake_fetch4<true>(xr, n, t0, tid) : snake_fetch4<false>(xr, n, t0, tid);
+  const int pz = 3 - t0;                       // the pair of sample 0, when the tile holds it
+  const int pe = n - t0 + 3;                   // the first pair past the row's end
+  for (int c = 0; c < C; ++c) {
+    float a, inv_b;
+    snake_params(alpha, beta, logscale, c, a, inv_b);
+    // xs / ve+vo / as were last read two / one / three barriers ago
+    *reinterpret_cast<f32x4*>(xs + 4 * tid) = pre;
+    if (c + 1 < C) {
+      xr += T;
+      pre = vec ? snake_fetch4<true>(xr, n, t0, tid) : snake_fetch4<false>(xr, n, t0, tid);
+    }
+    __syncthreads();
+    if (4 * tid < alen + 6) {
+      float u[8];
+      snake_up4(xs, tid, tu, u);
+      snake_store4(u, a, inv_b, ve, vo, tid);
+    }
+    __syncthreads();
+    if (t0 <= 0 || pe < alen + 6) {
+      if (tid < 3) {
+        if (t0 <= 0) ve[pz - 1 - tid] = vo[pz - 1 - tid] = ve[pz];
+        if (pe + tid < alen + 6) ve[pe + tid] = vo[pe + tid] = vo[pe - 1];
+      }
+      __syncthreads();
+    }
+    if (4 * tid < kSnakeFwdTile) {
+      f32x4 out = {0.f, 0.f, 0.f, 0.f};
+      if (4 * tid < alen) out = snake_down4(ve, vo, tid, td);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int t = t0 + 4 * tid + i;
+        if (t < 0 || t >= n) out[i] = 0.f;
+      }
+      *reinterpret_cast<f32x4*>(as + 4 * tid) = out;
+    }
+    __syncthreads();
+    if (4 * tid < W) {
+      const float* wc = w + c * (KT ? KT : K);
+      if (KT == 7) {                           // H = 4, pad = 3: output 4 tid + e reads as[4 tid + e + 1 + k]
+        float v[12];
+        lds_read3_b128(as + 4 * tid, v);
+#pragma unroll
+        for (int k = 0; k < 7; ++k) {
+          const float wv = wc[k];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc[e] = fmaf(wv, v[e + 1 + k], acc[e]);
+        }
+      } else {
+        const float* ap = as + 4 * tid + (H - pad);
+        for (int k = 0; k < K; ++k) {
+          const float wv = wc[k];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc[e] = fmaf(wv, ap[e + k], acc[e]);
+        }
+      }
+    }
+  }
+  if (4 * tid < W) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int t = first + 4 * tid + e;
+      if (t < T) {
+        const float v = act == 2 ? tanhf(acc[e]) : (act == 3 ? fminf(fmaxf(acc[e], -1.f), 1.f) : acc[e]);
+        yb[t] = t < n ? v : 0.f;
+      }
+    }
+  }
 }
 
 // ---- backward ------------------------------------------------------------------------------------------------------
@@ -410,7 +638,99 @@ int launch_aa_snake_items(const float* x, float* y, const float* alpha, const fl
   return DMEL_OK;
 }
 
+// y[k] (B, C, T) = activation(x; alpha[k], beta[k]) for three parameter sets in one launch; len (nullable) as launch_aa_snake_items.
+// The outputs must not overlap x or one another.
+int launch_aa_snake3(const float* x, float* const y[3], const float* const alpha[3], const float* const beta[3], const float* up_taps_host,
+                     const float* down_taps_host, int logscale, int B, int C, int64_t T, const int64_t* len, hipStream_t s) {
+  DMEL_CHECK_ARG(x && y && alpha && beta && up_taps_host && down_taps_host, "aa_snake3: NULL argument");
+  DMEL_CHECK_ARG(y[0] && y[1] && y[2] && alpha[0] && alpha[1] && alpha[2], "aa_snake3: NULL output or alpha");
+  DMEL_CHECK_ARG(y[0] != y[1] && y[0] != y[2] && y[1] != y[2] && x != y[0] && x != y[1] && x != y[2], "aa_snake3: x and the outputs must be distinct");
+  DMEL_CHECK_ARG(B > 0 && C > 0 && T > 0 && B <= 65535 && C <= 65535 && T < ((int64_t)1 << 30), "aa_snake3: bad shape");
+  Taps12 tu, td;
+  for (int i = 0; i < 12; ++i) { tu.f[i] = 2.f * up_taps_host[i]; td.f[i] = down_taps_host[i]; }
+  Snake3 p;
+  int yvec = 0;
+  for (int k = 0; k < 3; ++k) {
+    p.y[k] = y[k]; p.alpha[k] = alpha[k]; p.beta[k] = beta[k];
+    yvec |= (int)(reinterpret_cast<uintptr_t>(y[k]) % 16 == 0) << k;
+  }
+  constexpr int nsub = 3;      // as launch_aa_snake
+  constexpr int span = kSnakeFwdTile * nsub;
+  dim3 grid((unsigned)((T + span - 1) / span), (unsigned)C, (unsigned)B);
+  const bool vec = T % 4 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0;
+  {
+    ProfScope ps("aa_snake", s, 0.0, 16.0 * (double)B * C * (double)T);      // one read, three writes
+    if (len) hipLaunchKernelGGL(aa_snake3_items_kernel, grid, dim3(256), 0, s, x, p, tu, td, logscale, C, (int)T, len, nsub);
+    else if (vec) hipLaunchKernelGGL(aa_snake3_kernel<true>, grid, dim3(256), 0, s, x, p, tu, td, logscale, C, (int)T, nsub, yvec);
+    else hipLaunchKernelGGL(aa_snake3_kernel<false>, grid, dim3(256), 0, s, x, p, tu, td, logscale, C, (int)T, nsub, 0);
+  }
+  DMEL_HIP(hipGetLastError());
+  return DMEL_OK;
+}
+
+// y (B, 1, T) = act(conv_post(activation(x))), x (B, C, T); len (nullable) as launch_conv_post: y[b, len[b]:] = 0.  Accepts what
+// launch_conv_post accepts up to K = 2 * kPostMaxPad + 1 taps.
+constexpr int kPostMaxPad = 128;
+int launch_snake_post(const float* x, float* y, const float* alpha, const float* beta, const float* up_taps_host, const float* down_taps_host,
+                      int logscale, const float* w_dev, float bias, int act, int B, int C, int K, int64_t T, const int64_t* len, hipStream_t s) {
+  DMEL_CHECK_ARG(x && y && alpha && up_taps_host && down_taps_host && w_dev, "snake_post: NULL argument");
+  DMEL_CHECK_ARG(B > 0 && B <= 65535 && C > 0 && K > 0 && (K % 2) == 1 && T > 0 && T < ((int64_t)1 << 30), "snake_post: bad shape");
+  DMEL_CHECK_ARG((size_t)C * K * sizeof(float) <= 48 * 1024, "snake_post: weight table too large");
+  DMEL_CHECK_ARG(K / 2 <= kPostMaxPad, "snake_post: more than %d taps", 2 * kPostMaxPad + 1);
+  Taps12 tu, td;
+  for (int i = 0; i < 12; ++i) { tu.f[i] = 2.f * up_taps_host[i]; td.f[i] = down_taps_host[i]; }
+  const int W = kSnakeFwdTile - 2 * ((K / 2 + 3) & ~3);
+  dim3 grid((unsigned)((T + W - 1) / W), (unsigned)B);
+  {
+    ProfScope ps("small", s, 0.0, 4.0 * B * (double)T * (C + 1));
+    if (K == 7) hipLaunchKernelGGL(snake_post_kernel<7>, grid, dim3(256), 0, s, x, y, alpha, beta, tu, td, logscale, w_dev, bias, act, C, K, (int)T, len);
+    else hipLaunchKernelGGL(snake_post_kernel<0>, grid, dim3(256), 0, s, x, y, alpha, beta, tu, td, logscale, w_dev, bias, act, C, K, (int)T, len);
+  }
+  DMEL_HIP(hipGetLastError());
+  return DMEL_OK;
+}
+
 }  // namespace dmel
+
+extern "C" int dmel_aa_snake3_forward(const float* x, float* y0, float* y1, float* y2, const float* alpha0, const float* beta0,
+                                      const float* alpha1, const float* beta1, const float* alpha2, const float* beta2,
+                                      const float* up_filter12_host, const float* down_filter12_host, int logscale, int B, int C, int64_t T,
+                                      void* stream) {
+  float* const y[3] = {y0, y1, y2};
+  const float* const al[3] = {alpha0, alpha1, alpha2};
+  const float* const be[3] = {beta0, beta1, beta2};
+  return dmel::launch_aa_snake3(x, y, al, be, up_filter12_host, down_filter12_host, logscale, B, C, T, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int dmel_aa_snake3_forward_items(const float* x, float* y0, float* y1, float* y2, const float* alpha0, const float* beta0,
+                                            const float* alpha1, const float* beta1, const float* alpha2, const float* beta2,
+                                            const float* up_filter12_host, const float* down_filter12_host, int logscale, int B, int C,
+                                            int64_t T, const int64_t* lengths_dev, void* stream) {
+  DMEL_CHECK_ARG(lengths_dev, "aa_snake3_forward_items: NULL lengths");
+  float* const y[3] = {y0, y1, y2};
+  const float* const al[3] = {alpha0, alpha1, alpha2};
+  const float* const be[3] = {beta0, beta1, beta2};
+  return dmel::launch_aa_snake3(x, y, al, be, up_filter12_host, down_filter12_host, logscale, B, C, T, lengths_dev, (hipStream_t)stream);
+}
+
+static int snake_post_entry(const float* x, const float* alpha, const float* beta, const float* up, const float* down, int logscale,
+                            const float* w_dev, float bias, int act, float* y, int B, int C, int K, int64_t T, const int64_t* len, void* stream) {
+  DMEL_CHECK_ARG(act == 0 || act == 2 || act == 3, "snake_post: act must be 0 (none), 2 (tanh) or 3 (clamp to [-1, 1])");
+  return dmel::launch_snake_post(x, y, alpha, beta, up, down, logscale, w_dev, bias, act, B, C, K, T, len, (hipStream_t)stream);
+}
+
+extern "C" int dmel_snake_post_forward(const float* x, const float* alpha, const float* beta, const float* up_filter12_host,
+                                       const float* down_filter12_host, int logscale, const float* w_dev, float bias, int act, float* y, int B,
+                                       int C, int K, int64_t T, void* stream) {
+  return snake_post_entry(x, alpha, beta, up_filter12_host, down_filter12_host, logscale, w_dev, bias, act, y, B, C, K, T, nullptr, stream);
+}
+
+extern "C" int dmel_snake_post_forward_items(const float* x, const float* alpha, const float* beta, const float* up_filter12_host,
+                                             const float* down_filter12_host, int logscale, const float* w_dev, float bias, int act, float* y,
+                                             int B, int C, int K, int64_t T, const int64_t* lengths_dev, void* stream) {
+  DMEL_CHECK_ARG(lengths_dev, "snake_post_forward_items: NULL lengths");
+  return snake_post_entry(x, alpha, beta, up_filter12_host, down_filter12_host, logscale, w_dev, bias, act, y, B, C, K, T, lengths_dev, stream);
+}
 
 extern "C" int dmel_aa_snake_items_f32(const float* x, float* y, const float* alpha, const float* beta, const float* up_filter12_host,
                                        const float* down_filter12_host, int logscale, int B, int C, int64_t T, const int64_t* lengths_dev,

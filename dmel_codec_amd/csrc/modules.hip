@@ -2824,6 +2824,24 @@ static int bigvgan_forward_impl(const dmel_bigvgan* m, const float* mel, const i
       DMEL_HIP(hipEventRecord(m->ev_fork, st));
       for (int k = 0; k < dmel_bigvgan::kSide; ++k) DMEL_HIP(hipStreamWaitEvent(m->side[k], m->ev_fork, 0));
     }
+    // The three blocks each begin with an activation of the SAME tensor xu: on one stream they are one launch (aa_snake3_kernel reads and
+    // up-filters xu once) into the three blocks' activation buffers, and each block's l == 0 activation is skipped.  DMEL_SNAKE_HEAD3=0
+    // keeps the three launches (same bits; read per call, for A/B and the equality tests).  The multi-stream form keeps them too: there
+    // the heads are what the stagger events hang on.
+    const char* fuse_env = getenv("DMEL_FUSE_SNAKE");
+    const bool fuse = fuse_env && fuse_env[0] == '1' && !lengths;
+    const char* head_env = getenv("DMEL_SNAKE_HEAD3");
+    const bool head3 = !multi && !fuse && c.num_kernels == 3 && !(head_env && head_env[0] == '0');
+    if (head3) {
+      float* const hy[3] = {bufs[4], bufs[7], bufs[10]};
+      const float *ha[3], *hb[3];
+      for (int j = 0; j < 3; ++j) {
+        const SnakeP& p = m->blocks[(size_t)i * 3 + j].act[0];
+        ha[j] = p.alpha.as<float>();
+        hb[j] = p.beta.as<float>();
+      }
+      DMEL_TRY(launch_aa_snake3(xu, hy, ha, hb, m->taps_up, m->taps_dn, logscale, B, ch, Tc, len, st));
+    }
     for (int j = 0; j < c.num_kernels; ++j) {  // AMPBlock1.forward (bigvgan.py:132-141), summed and averaged (:376-382)
       const AmpBlock& ab = m->blocks[(size_t)i * c.num_kernels + j];
       hipStream_t sj = (multi && j > 0) ? m->side[j - 1] : st;
@@ -2834,8 +2852,6 @@ static int bigvgan_forward_impl(const dmel_bigvgan* m, const float* mel, const i
       // profiles/r03_fused_vs_two_kernels.txt; DESIGN.md section 4 has the probes that explain it), so the two-kernel form stays the
       // default.  Read per call so that a test can flip it inside one process.  The fused kernel has one row length for the whole batch:
       // it stands aside for items.
-      const char* fuse_env = getenv("DMEL_FUSE_SNAKE");
-      const bool fuse = fuse_env && fuse_env[0] == '1' && !lengths;
       for (int l = 0; l < 3; ++l) {
         // stagger the branches by one kernel: started together they run snake|snake|snake then conv|conv|conv in lockstep
         // and the VALU-bound activations never meet the matrix-pipe-bound convolutions on a CU
@@ -2846,7 +2862,7 @@ static int bigvgan_forward_impl(const dmel_bigvgan* m, const float* mel, const i
           r2.res = xin; r2.res_bs = bs; r2.res_cs = Tc;
           r2.precision = prec;
           const bool fuse2 = fuse && conv_snake_eligible(ab.c1[l], r2);
-          if (!fuse2) DMEL_TRY(act(xin, uj, ab.act[l], ch, Tc, len, sj));
+          if (!fuse2 && !(head3 && l == 0)) DMEL_TRY(act(xin, uj, ab.act[l], ch, Tc, len, sj));
           if (!fuse2 && l == 0 && multi && j + 1 < c.num_kernels) DMEL_HIP(hipEventRecord(m->ev_stag[j], sj));
           if (l == 2) {
             r2.accumulate = j > 0;
@@ -2872,7 +2888,7 @@ static int bigvgan_forward_impl(const dmel_bigvgan* m, const float* mel, const i
           DMEL_TRY(launch_conv_snake(ab.c1[l], r1, ab.act[2 * l].alpha.as<float>(), ab.act[2 * l].beta.as<float>(), m->taps_up, m->taps_dn, logscale, sj));
           if (l == 0 && multi && j + 1 < c.num_kernels) DMEL_HIP(hipEventRecord(m->ev_stag[j], sj));
         } else {
-          DMEL_TRY(act(xin, uj, ab.act[2 * l], ch, Tc, len, sj));
+          if (!(head3 && l == 0)) DMEL_TRY(act(xin, uj, ab.act[2 * l], ch, Tc, len, sj));
           if (l == 0 && multi && j + 1 < c.num_kernels) DMEL_HIP(hipEventRecord(m->ev_stag[j], sj));
           DMEL_TRY(launch_conv(ab.c1[l], r1, sj));
         }
@@ -2908,6 +2924,11 @@ static int bigvgan_forward_impl(const dmel_bigvgan* m, const float* mel, const i
   }
   // activation_post, conv_post, tanh | clamp (bigvgan.py:385-391)
   const int64_t* len_out = len_at(c.num_upsamples);
+  // one launch: the activated tensor goes through LDS, not HBM (snake_post_kernel).  DMEL_POST_FUSED=0 keeps the two launches (same bits).
+  const char* post_env = getenv("DMEL_POST_FUSED");
+  if (!(post_env && post_env[0] == '0'))
+    return launch_snake_post(x, audio, m->act_post.alpha.as<float>(), m->act_post.beta.as<float>(), m->taps_up, m->taps_dn, logscale,
+                             m->post_w.as<float>(), m->post_bias, c.use_tanh_at_final ? ACT_TANH : ACT_CLAMP1, B, ch, 7, Tc, len_out, st);
   DMEL_TRY(act(x, ua, m->act_post, ch, Tc, len_out, st));
   return launch_conv_post(ua, audio, m->post_w.as<float>(), m->post_bias, c.use_tanh_at_final ? ACT_TANH : ACT_CLAMP1, B, ch, 7,
                           Tc, st, len_out);

@@ -92,6 +92,13 @@ int launch_aa_snake(const float* x, float* y, const float* alpha, const float* b
 // or beyond len[b] are neither read nor written
 int launch_aa_snake_items(const float* x, float* y, const float* alpha, const float* beta, const float* up_taps_host,
                           const float* down_taps_host, int logscale, int B, int C, int64_t T, const int64_t* len, hipStream_t s);
+// Three activations of one tensor in one launch (the heads of the three AMP blocks of a vocoder stage): y[k] = activation(x; alpha[k],
+// beta[k]), each bit-identical to a launch_aa_snake / launch_aa_snake_items (len != NULL) of its own; x is read and up-filtered once
+int launch_aa_snake3(const float* x, float* const y[3], const float* const alpha[3], const float* const beta[3], const float* up_taps_host,
+                     const float* down_taps_host, int logscale, int B, int C, int64_t T, const int64_t* len, hipStream_t s);
+// launch_aa_snake[_items] + launch_conv_post in one launch, bit-identical to the two; the activated tensor is never written
+int launch_snake_post(const float* x, float* y, const float* alpha, const float* beta, const float* up_taps_host, const float* down_taps_host,
+                      int logscale, const float* w_dev, float bias, int act, int B, int C, int K, int64_t T, const int64_t* len, hipStream_t s);
 // dx of the anti-aliased Snake only (frozen parameters): bit-identical to the dx of the full backward; dx = (dx_act + radd) + racc,
 // both nullable, racc may alias dx
 int launch_aa_snake_bwd_input(const float* x, const float* dy, float* dx, const float* radd, const float* racc, const float* alpha,

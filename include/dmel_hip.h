@@ -291,6 +291,27 @@ int dmel_aa_snake_f32(const float* x, float* y, const float* alpha, const float*
 int dmel_aa_snake_items_f32(const float* x, float* y, const float* alpha, const float* beta, const float* up_filter12_host,
                             const float* down_filter12_host, int logscale, int B, int C, int64_t T, const int64_t* lengths_dev,
                             void* stream);
+/* Three activations of ONE tensor in one launch (extension: the three AMP blocks behind an up-sampler of BigVGAN each begin with an
+ * activation of the same tensor, bigvgan/bigvgan.py:376-382): y_k = activation(x; alpha_k, beta_k), k = 0..2.  x is read and up-filtered
+ * once; every y_k is BIT-IDENTICAL to dmel_aa_snake_f32 (dmel_aa_snake_items_f32 for the items form, same contract: columns at or beyond
+ * lengths[b] are neither read nor written) with its parameters.  beta_k NULL = Snake.  x and the three outputs must be distinct
+ * buffers; each output takes 16-byte stores when it, x and the rows (T % 4 == 0) are 16-byte aligned, dword stores otherwise. */
+int dmel_aa_snake3_forward(const float* x, float* y0, float* y1, float* y2, const float* alpha0, const float* beta0, const float* alpha1,
+                           const float* beta1, const float* alpha2, const float* beta2, const float* up_filter12_host,
+                           const float* down_filter12_host, int logscale, int B, int C, int64_t T, void* stream);
+int dmel_aa_snake3_forward_items(const float* x, float* y0, float* y1, float* y2, const float* alpha0, const float* beta0,
+                                 const float* alpha1, const float* beta1, const float* alpha2, const float* beta2,
+                                 const float* up_filter12_host, const float* down_filter12_host, int logscale, int B, int C, int64_t T,
+                                 const int64_t* lengths_dev, void* stream);
+/* The vocoder's tail in one launch (extension): y (B, 1, T) = act(conv_post(activation(x))), BIT-IDENTICAL to dmel_aa_snake_f32 followed
+ * by dmel_conv_post_f32 (the items form: to dmel_aa_snake_items_f32 followed by dmel_conv_post_items_f32, y[b, 0, lengths[b]:] = 0); the
+ * activated (B, C, T) tensor is never written.  Arguments as in those two; K odd, at most 257 taps. */
+int dmel_snake_post_forward(const float* x, const float* alpha, const float* beta, const float* up_filter12_host,
+                            const float* down_filter12_host, int logscale, const float* w_dev, float bias, int act, float* y, int B, int C,
+                            int K, int64_t T, void* stream);
+int dmel_snake_post_forward_items(const float* x, const float* alpha, const float* beta, const float* up_filter12_host,
+                                  const float* down_filter12_host, int logscale, const float* w_dev, float bias, int act, float* y, int B,
+                                  int C, int K, int64_t T, const int64_t* lengths_dev, void* stream);
 /* Backward of dmel_aa_snake_f32 (the reference's fused kernel has none: alias_free_activation/cuda/activation1d.py:29-32;
  * SURVEY.md section 8(f) rank 1, C-ABI row `aa_snake(+_bwd)`): dx (B, C, T), dalpha (C), dbeta (C; NULL exactly when beta is NULL,
  * i.e. Snake, whose single parameter then receives both contributions).  Gradients are with respect to the STORED parameters

@@ -908,6 +908,22 @@ int main() {
     auto xs = buf(2 * 8 * 3000), ys = buf(2 * 8 * 3000), da = buf(8), db = buf(8);
     CK(dmel_aa_snake_f32(xs.data(), ys.data(), al.data(), be.data(), taps.data(), taps.data(), 1, 2, 8, 3000, nullptr));
     CK(dmel_aa_snake_backward_f32(xs.data(), ys.data(), xs.data(), al.data(), be.data(), da.data(), db.data(), taps.data(), taps.data(), 1, 2, 8, 3000, nullptr));
+    {
+      // the one-launch forms of the vocoder's head activations and tail: pointer tables, the alignment mask, the tap-count limit
+      auto y1 = buf(2 * 8 * 3000), y2 = buf(2 * 8 * 3000), w = buf(8 * 257), yp = buf(2 * 3000);
+      std::vector<int64_t> ln = {3000, 17};
+      CK(dmel_aa_snake3_forward(xs.data(), ys.data(), y1.data() + 1, y2.data(), al.data(), be.data(), al.data(), nullptr, al.data(), be.data(),
+                                taps.data(), taps.data(), 1, 2, 8, 3000, nullptr));
+      CK(dmel_aa_snake3_forward_items(xs.data(), ys.data(), y1.data(), y2.data(), al.data(), be.data(), al.data(), nullptr, al.data(), be.data(),
+                                      taps.data(), taps.data(), 0, 2, 8, 3000, ln.data(), nullptr));
+      if (dmel_aa_snake3_forward(xs.data(), ys.data(), ys.data(), y2.data(), al.data(), be.data(), al.data(), nullptr, al.data(), be.data(),
+                                 taps.data(), taps.data(), 1, 2, 8, 3000, nullptr) != DMEL_EINVAL) { std::printf("FAIL aa_snake3 accepted aliased outputs\n"); ++failures; }
+      for (int K : {1, 7, 257})
+        CK(dmel_snake_post_forward(xs.data(), al.data(), be.data(), taps.data(), taps.data(), 1, w.data(), 0.1f, 2, yp.data(), 2, 8, K, 3000, nullptr));
+      CK(dmel_snake_post_forward_items(xs.data(), al.data(), nullptr, taps.data(), taps.data(), 1, w.data(), 0.f, 3, yp.data(), 2, 8, 7, 3000, ln.data(), nullptr));
+      if (dmel_snake_post_forward(xs.data(), al.data(), be.data(), taps.data(), taps.data(), 1, w.data(), 0.f, 2, yp.data(), 2, 8, 259, 3000, nullptr) != DMEL_EINVAL ||
+          !std::strstr(dmel_last_error(), "taps")) { std::printf("FAIL snake_post accepted 259 taps\n"); ++failures; }
+    }
   }
   // drawn last, so that the handles above keep their weights: narrow encoder-like and conditioned stacks with every training image
   Fingerprinted fp;
