@@ -152,6 +152,10 @@ PROTOTYPES = {
     "dmel_quantizer_forward_train": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int64, vp, C.c_size_t, vp]),
     "dmel_quantizer_backward": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int64, vp, C.c_size_t, vp]),
     "dmel_mask_add_quality_f32": (C.c_int, [vp, vp, vp, vp, C.c_float, C.c_int, C.c_int, C.c_int64, vp]),
+    "dmel_fsq_encode_f32": (C.c_int, [vp, vp, vp, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp]),
+    "dmel_fsq_decode_f32": (C.c_int, [vp, vp, vp, C.POINTER(C.c_int), C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp]),
+    "dmel_fsq_backward_f32": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(C.c_int), C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_size_t, C.c_int, C.c_int,
+                                        C.c_int, C.c_int64, vp]),
     "dmel_bigvgan_create": (C.c_int, [C.POINTER(vp), C.POINTER(BigVGANConfig)]),
     "dmel_bigvgan_destroy": (None, [vp]),
     "dmel_bigvgan_set_tensor": (C.c_int, [vp, C.c_char_p, vp, i64p, C.c_int]),

@@ -1190,6 +1190,7 @@ int refresh_convnext(Refresh& r, ConvNeXt& cx, int C, bool train) {
 // len (nullable, N / len_div device int64): per-item form -- row n is an item of len[n / len_div] <= T columns.  The depthwise convolution
 // pads each item with its own zeros, the pointwise convolutions are column-local, and h1, h2 and y come out zero behind the item; x is
 // not read there by the depthwise taps or the staging (the residual load of a masked column is discarded, never stored).
+// (tests/test_gpu_convnext_matrix.py mirrors the workspace order: h1 (N C T floats) at offset 0, h2 (4 N C T) directly behind it)
 int run_convnext(const ConvNeXt& cx, const float* x, float* y, float* h1, float* h2, int N, int C, int64_t T, hipStream_t st,
                  const int64_t* len = nullptr, int len_div = 1) {
   DMEL_TRY(launch_dwconv_ln(x, h1, cx.dw_w.as<float>(), cx.dw_b.as<float>(), cx.ln_w.as<float>(), cx.ln_b.as<float>(), N, C, T, st, nullptr,
@@ -1226,6 +1227,16 @@ extern "C" int dmel_convnext_set_tensor(dmel_convnext* m, const char* key, const
 extern "C" int dmel_convnext_set_train_precision(dmel_convnext* m, int precision) { return train_set_precision(m, "convnext", precision); }
 extern "C" int dmel_convnext_enable_training(dmel_convnext* m, int on) { return train_enable(m, on); }
 namespace {
+// forward_train would run up to 494 channels and backward then fail in launch_ln_bwd with three gradients already written: a training
+// handle is refused here, before any launch
+int check_train_channels(const char* who, int C, bool train) {
+  if (train && C > kLnBwdMaxC) {
+    set_error("%s: a trainable ConvNeXt block has at most %d channels (the LayerNorm backward keeps two [C][33] fp32 tiles in the 64 KiB LDS), got %d",
+              who, kLnBwdMaxC, C);
+    return DMEL_EUNSUPPORTED;
+  }
+  return DMEL_OK;
+}
 // the nine gradient slots of a block, in the order of its state dict
 void convnext_slots(TrainHandle& h, const std::string& p, int C) {
   h.add(p + "dwconv.weight", (int64_t)C * 7); h.add(p + "dwconv.bias", C); h.add(p + "norm.weight", C); h.add(p + "norm.bias", C);
@@ -1236,6 +1247,7 @@ void convnext_slots(TrainHandle& h, const std::string& p, int C) {
 extern "C" int dmel_convnext_finalize(dmel_convnext* m) {
   DMEL_CHECK_ARG(m, "NULL handle");
   m->ready = m->train_ready = false;      // until every image is packed: a finalize that fails leaves a handle that refuses to run
+  DMEL_TRY(check_train_channels("convnext_finalize", m->C, m->train));
   DMEL_TRY(build_convnext(m->cx, m->ts, "", m->C, m->train));
   if (m->train) {
     m->clear_slots();
@@ -1269,6 +1281,7 @@ extern "C" int dmel_convnext_forward_items(const dmel_convnext* m, const float* 
 
 namespace {
 struct CxPlan { float *H0, *H1, *U, *G, *V, *DV, *DG, *DH1, *DH0; size_t n, bytes; };
+// (tests/test_gpu_convnext_matrix.py mirrors this order and the 256-byte alignment of every take)
 CxPlan cx_plan_at(Arena& a, size_t n) {
   CxPlan p{};
   p.n = n;
@@ -1395,6 +1408,7 @@ extern "C" int dmel_quantizer_finalize(dmel_quantizer* q) {
   DMEL_CHECK_ARG(q, "NULL handle");
   q->ready = q->train_ready = false;      // until every image is packed: a finalize that fails leaves a handle that refuses to run
   const int C = q->Cg, G = q->G, D = q->D;
+  DMEL_TRY(check_train_channels("quantizer_finalize", C, q->train));
   q->stage.clear();
   q->stage.resize(q->nf);
   q->clear_slots();

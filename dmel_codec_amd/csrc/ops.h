@@ -134,7 +134,9 @@ int launch_layerscale_res_fwd(const float* x, const float* v, const float* gamma
 int launch_layerscale_bwd(const float* dy, const float* v, const float* gamma, float* dv, float* dgamma, int N, int C, int64_t T,
                           hipStream_t s);
 // LayerNorm over channels (eps 1e-6, biased variance) backward: dh0 from dh1 and the saved pre-norm h0; dln_w / dln_b accumulated
-// with atomics into zero-initialised buffers
+// with atomics into zero-initialised buffers.  Two [C][33] fp32 tiles and 4 x 32 statistics share the 64 KiB LDS: C <= kLnBwdMaxC, which
+// is what a trainable ConvNeXt block may have (the forward's single tile would take 494; finalize refuses a training handle above this)
+constexpr int kLnBwdMaxC = (64 * 1024 / 4 - 4 * 32) / (2 * 33);      // 246
 int launch_ln_bwd(const float* dh1, const float* h0, const float* ln_w, float* dh0, float* dln_w, float* dln_b, int N, int C, int64_t T,
                   hipStream_t s);
 // depthwise k=7 conv backward: dx = dres + conv_transpose(dh0) (dres nullable), ddw (C, 7), ddb (C) overwritten

@@ -110,6 +110,7 @@ __device__ __forceinline__ float fsq_bound(float z, const FsqConst& k, int j) {
 
 // z: (B*G, C, T4) channel-major rows of group g of item b at row b*G+g.  w_in: (G, D, C), b_in: (G, D).
 // ids: (B, G, T4) int32.  prequant (optional): (G, B, T4, D).  len (nullable, B device int64): per-item token counts, clamped to [0, T4].
+// Behind an item's count ids and prequant are written as 0 / 0.f.
 __global__ __launch_bounds__(256) void fsq_encode_kernel(const float* __restrict__ z, const float* __restrict__ w_in,
                                                          const float* __restrict__ b_in, int32_t* __restrict__ ids,
                                                          float* __restrict__ prequant, FsqConst k, int B, int G, int C,
@@ -120,8 +121,10 @@ __global__ __launch_bounds__(256) void fsq_encode_kernel(const float* __restrict
   const int64_t l = i % T4;
   const int g = (int)((i / T4) % G);
   const int b = (int)(i / (T4 * G));
-  if (len && l >= min(max(len[b], (int64_t)0), T4)) {      // items: behind item b's token count the id is 0 and z is not read
+  if (len && l >= min(max(len[b], (int64_t)0), T4)) {      // items: behind item b's token count the id and prequant are 0 and z is not read
     ids[i] = 0;
+    if (prequant)
+      for (int j = 0; j < k.n_levels; ++j) prequant[(((int64_t)g * B + b) * T4 + l) * k.n_levels + j] = 0.f;
     return;
   }
   const float* zr = z + ((int64_t)(b * G + g) * C) * T4 + l;
@@ -1048,6 +1051,51 @@ extern "C" int dmel_mask_add_quality_f32(float* z, const int64_t* lengths, const
   }
   DMEL_HIP(hipGetLastError());
   return DMEL_OK;
+}
+
+// ---- the FSQ kernels alone (include/dmel_hip.h: dmel_fsq_*_f32): the launchers above on caller-supplied packed parameters -------------
+static int fsq_entry_const(dmel::FsqConst& k, const char* who, const int* levels, int n_levels, int prebound, int strict, int B, int G, int C,
+                           int64_t T4) {
+  DMEL_CHECK_ARG(levels && n_levels >= 1 && n_levels <= 4, "%s: 1..4 levels", who);
+  DMEL_CHECK_ARG(B > 0 && G > 0 && C > 0 && T4 > 0 && (int64_t)B * G * C * T4 < ((int64_t)1 << 31) * 256, "%s: bad shape", who);
+  int64_t codes = 1;
+  for (int j = 0; j < n_levels; ++j) {
+    DMEL_CHECK_ARG(levels[j] >= 2 && levels[j] <= 1024, "%s: level %d outside 2..1024", who, levels[j]);
+    codes *= levels[j];
+  }
+  DMEL_CHECK_ARG(codes < ((int64_t)1 << 31), "%s: the codebook does not fit an int32 id", who);
+  DMEL_TRY(dmel::make_fsq_const(k, levels, n_levels, prebound != 0));
+  k.strict = strict != 0;
+  return DMEL_OK;
+}
+
+extern "C" int dmel_fsq_encode_f32(const float* z, const float* w_in, const float* b_in, const int* levels, int n_levels, int prebound,
+                                   int strict, const int64_t* lengths_dev, int32_t* ids, float* prequant, int B, int G, int C, int64_t T4,
+                                   void* stream) {
+  DMEL_CHECK_ARG(z && w_in && b_in && ids, "fsq_encode: NULL argument");
+  dmel::FsqConst k;
+  DMEL_TRY(fsq_entry_const(k, "fsq_encode", levels, n_levels, prebound, strict, B, G, C, T4));
+  return dmel::launch_fsq_encode(z, w_in, b_in, ids, prequant, k, B, G, C, T4, (hipStream_t)stream, lengths_dev);
+}
+
+extern "C" int dmel_fsq_decode_f32(const int32_t* ids, const float* w_out, const float* b_out, const int* levels, int n_levels,
+                                   const int64_t* lengths_dev, float* z, int B, int G, int C, int64_t T4, void* stream) {
+  DMEL_CHECK_ARG(ids && w_out && b_out && z, "fsq_decode: NULL argument");
+  dmel::FsqConst k;
+  DMEL_TRY(fsq_entry_const(k, "fsq_decode", levels, n_levels, 0, 0, B, G, C, T4));
+  return dmel::launch_fsq_decode(ids, w_out, b_out, z, k, B, G, C, T4, (hipStream_t)stream, lengths_dev);
+}
+
+extern "C" int dmel_fsq_backward_f32(const float* x, const float* dout, const float* w_in, const float* b_in, const float* w_out,
+                                     const int* levels, int n_levels, int prebound, float* dx, float* dw_in, float* db_in, float* dw_out,
+                                     float* db_out, float* scratch, size_t scratch_floats, int B, int G, int C, int64_t T4, void* stream) {
+  DMEL_CHECK_ARG(x && dout && w_in && b_in && w_out && dx && dw_in && db_in && dw_out && db_out && scratch, "fsq_backward: NULL argument");
+  dmel::FsqConst k;
+  DMEL_TRY(fsq_entry_const(k, "fsq_backward", levels, n_levels, prebound, 0, B, G, C, T4));
+  DMEL_CHECK_ARG(G <= 65535, "fsq_backward: %d groups exceed the grid", G);
+  const size_t need = (size_t)2 * B * G * T4 * n_levels;
+  DMEL_CHECK_ARG(scratch_floats >= need, "fsq_backward: scratch too small (%zu < %zu floats)", scratch_floats, need);
+  return dmel::launch_fsq_backward(x, dout, w_in, b_in, w_out, dx, dw_in, db_in, dw_out, db_out, scratch, k, B, G, C, T4, (hipStream_t)stream);
 }
 
 extern "C" int dmel_resample_f32(const float* x, float* y, const float* filter_bank_dev, int B, int64_t L, int64_t Lout, int orig_freq,

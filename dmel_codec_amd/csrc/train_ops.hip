@@ -493,7 +493,9 @@ int launch_ln_bwd(const float* dh1, const float* h0, const float* ln_w, float* d
                   hipStream_t s) {
   DMEL_CHECK_ARG(N > 0 && N <= 65535 && C > 0 && T > 0, "ln_bwd: bad shape");
   const size_t lds = ((size_t)2 * C * (kLnTile + 1) + 4 * kLnTile) * sizeof(float);
-  DMEL_CHECK_ARG(lds <= 64 * 1024, "ln_bwd: %d channels exceed the LDS tile", C);
+  static_assert(((size_t)2 * kLnBwdMaxC * (kLnTile + 1) + 4 * kLnTile) * sizeof(float) <= 64 * 1024 &&
+                    ((size_t)2 * (kLnBwdMaxC + 1) * (kLnTile + 1) + 4 * kLnTile) * sizeof(float) > 64 * 1024, "kLnBwdMaxC (ops.h) is the LDS limit");
+  DMEL_CHECK_ARG(lds <= 64 * 1024, "ln_bwd: %d channels exceed the LDS tile (at most %d)", C, kLnBwdMaxC);
   DMEL_TRY(zero_unless_cleared(dln_w, (size_t)C * sizeof(float), s));
   DMEL_TRY(zero_unless_cleared(dln_b, (size_t)C * sizeof(float), s));
   dim3 grid((unsigned)((T + kLnTile - 1) / kLnTile), (unsigned)N);

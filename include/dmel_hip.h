@@ -851,7 +851,9 @@ int dmel_stream_pack_items(const void* const* src, void* const* dst, const int64
  * LayerNorm_C(dwconv7(x))))), x / y (N, dim, T).  set_tensor keys: dwconv.weight (dim,1,7), dwconv.bias, norm.weight, norm.bias,
  * pwconv1.weight (4 dim, dim), pwconv1.bias, pwconv2.weight (dim, 4 dim), pwconv2.bias, gamma.  The training entry points follow the
  * WaveNet ones (enable_training before finalize; forward_train keeps its intermediates in the workspace that backward is given again;
- * parameter gradients in one flat buffer addressed through grad_slot; dx is always produced). */
+ * parameter gradients in one flat buffer addressed through grad_slot; dx is always produced).  dim <= 494 (one [dim][33] fp32 tile in
+ * the 64 KiB LDS; forward returns an error above it and writes nothing); a TRAINING handle has dim <= 246 (the LayerNorm backward keeps
+ * two such tiles): finalize refuses a larger one with DMEL_EUNSUPPORTED, and so does dmel_quantizer_finalize for dim_per_group. */
 typedef struct dmel_convnext dmel_convnext;
 int dmel_convnext_create(dmel_convnext** m, int dim);
 void dmel_convnext_destroy(dmel_convnext* m);
@@ -938,6 +940,25 @@ int dmel_quantizer_backward(const dmel_quantizer* q, const float* z, const float
  * (quality_projection = nn.Linear(1, C) applied to the constant 2.0).  w, bias: device (C). */
 int dmel_mask_add_quality_f32(float* z, const int64_t* lengths, const float* w, const float* bias, float value,
                               int B, int C, int64_t T, void* stream);
+
+/* The FSQ kernels of the quantiser alone, without the down- / up-sampling stacks around them, on device pointers in the handle's packed
+ * layouts: w_in (G, D, C), b_in (G, D), w_out (G, C, D), b_out (G, C), D = n_levels (1..4, host int array `levels`, each 2..1024, product
+ * below 2^31).  z / x / dout / dx: (B*G, C, T4) with group g of item b at row b*G + g; ids (B, G, T4) int32; prequant (G, B, T4, D),
+ * nullable.  lengths_dev (B device int64, nullable): token counts, clamped into [0, T4] on the device -- ids, prequant (when given) and z
+ * at or behind item b's count are written as 0 / 0.f and the z / ids there are not read.  strict: as dmel_quantizer_set_strict.
+ *   encode:   ids and prequant = bound(bound?(W_in z + b_in)) (bounded once more first when prebound), rounded half to even.
+ *   decode:   z = W_out code + b_out, code_j = (digit_j - levels_j / 2) / (levels_j / 2).
+ *   backward: the straight-through estimator; dx and the four parameter gradients (overwritten, not accumulated); scratch: device,
+ *             at least 2 * B * G * T4 * D floats.
+ * A bad argument (NULL, a shape or level outside the ranges, a scratch too small) is DMEL_EINVAL and writes nothing. */
+int dmel_fsq_encode_f32(const float* z, const float* w_in, const float* b_in, const int* levels, int n_levels, int prebound, int strict,
+                        const int64_t* lengths_dev /*nullable*/, int32_t* ids, float* prequant /*nullable*/, int B, int G, int C, int64_t T4,
+                        void* stream);
+int dmel_fsq_decode_f32(const int32_t* ids, const float* w_out, const float* b_out, const int* levels, int n_levels,
+                        const int64_t* lengths_dev /*nullable*/, float* z, int B, int G, int C, int64_t T4, void* stream);
+int dmel_fsq_backward_f32(const float* x, const float* dout, const float* w_in, const float* b_in, const float* w_out, const int* levels,
+                          int n_levels, int prebound, float* dx, float* dw_in, float* db_in, float* dw_out, float* db_out, float* scratch,
+                          size_t scratch_floats, int B, int G, int C, int64_t T4, void* stream);
 
 /* BigVGAN generator      replaces models/modules/bigvgan/bigvgan.py:367-393 (+ AMPBlock1 :132-141, AMPBlock2 :232-237) */
 typedef struct dmel_bigvgan dmel_bigvgan;
